@@ -2,7 +2,15 @@
 """bench.py — headline benchmark of the SAC-COT hot path on MI355X (contract: see the task brief / DESIGN.md §6).
 
     python bench.py --gpus N --steps K --warmup W [--config C2] [--scaling weak|strong] [--shard ab|replicated]
+                    [--dump-outputs DIR] [--full]
     (N > 1: launched by the driver as  python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, the workload, how the
+timed frames ran).  `--full` adds everything else this script measures or checks, in the same line: the waited form, the
+identical-frame and 256-frame streams, per-stage brackets and rooflines and, on one GPU, the cold call, host I/O, varying-n,
+no-dense-S, native multi-device and calls-in-flight legs, the CPU baseline and the parity of every scene with the CPU restatement.
+`--dump-outputs DIR` writes what the last timed step delivered to its caller (R.npy, t.npy, mask.npy, winner.npy) after the timed
+steps; the scenes are seeded, so two builds can be compared output for output.
 
 A *step* is one full pass of the hot path over one synthetic correspondence set already resident in HBM:
 stage A (compat graph) -> B (top-T triangles) -> C1 (Kabsch) -> C2 (score + arg-max) -> C3 (winner + inlier mask).
@@ -120,6 +128,17 @@ def issue_model(n: int, n_local: int, us: float, info: dict) -> dict:
             "recounts": info.get("filter_recounts")}
 
 
+def dump_outputs(d: str, Rt, mask, rc: int, st: dict) -> None:
+    """--dump-outputs: the outputs of the last timed step as its caller receives them — (R, t) and the inlier mask from device
+    memory, the winner (status, rank of the winning hypothesis, its inlier count) from the returned statistics."""
+    os.makedirs(d, exist_ok=True)
+    Rt = Rt.cpu().numpy()
+    np.save(os.path.join(d, "R.npy"), Rt[:9].reshape(3, 3))
+    np.save(os.path.join(d, "t.npy"), Rt[9:].copy())
+    np.save(os.path.join(d, "mask.npy"), mask.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(d, "winner.npy"), np.array([rc, st["best_rank"], st["best_count"]], dtype=np.float64))
+
+
 def spawn_ranks(n: int, deadline_s: float = 1500.0) -> int:
     """`python bench.py --gpus N` started WITHOUT a launcher (WORLD_SIZE unset): start the N ranks as fresh child
     processes — this parent has not touched the GPU (torch is not even imported yet) and never does; no re-exec.  The
@@ -221,15 +240,21 @@ def main() -> int:
                          "frame to frame); frame f registers scene f mod SCENES.  1 = every frame the config's own scene (rounds 1 - 4)")
     ap.add_argument("--hot-timing-every", type=int, default=8,
                     help="SC_FLAG_TIMING_HOT (the dominant kernel's duration from its dispatch packets' timestamps) on every N-th timed frame (0: none)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline (see the module docstring); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last timed step's (R, t), inlier mask and winner as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline or CPU parity")
     ap.add_argument("--headline-only", action="store_true",
-                    help="only the timed loop and the per-stage passes (no cold call, host-I/O, varying-N, no-dense-S or CPU "
+                    help="with --full: only the timed loop and the per-stage passes (no cold call, host-I/O, varying-N, no-dense-S or CPU "
                          "legs): what the rocprofv3 kernel-stats and PMC passes profile")
     ap.add_argument("--no-dense-s", action="store_true", help="SC_FLAG_NO_DENSE_S in the timed loop (bit rows only)")
     ap.add_argument("--debug", default="", help="sc_debug knobs for experiments: key=value,key=value")
     ap.add_argument("--split-sample", choices=("auto", "on", "off"), default="auto",
                     help="--shard replicated only: on = shard stage B's CERTIFYING pruning sample (one extra 1 KiB all-reduce); auto / off: every rank takes the whole ESTIMATING sample (SC_FLAG_EST_BOUND)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn_ranks(args.gpus)
@@ -279,7 +304,7 @@ def main() -> int:
 
     # ---- cold call: a fresh context, host arrays in, outputs back (workspace allocation, first launches) ----------
     cold_ms = None
-    if world == 1 and not args.headline_only:
+    if world == 1 and args.full and not args.headline_only:
         r0 = pkg.Registrar(local_rank)
         tc = time.perf_counter()
         r0.register(scene.src, scene.tgt, params=pkg.make_params(flags=base_flags, **kw))
@@ -472,38 +497,42 @@ def main() -> int:
             if per_scene.setdefault(k_, (rc_, rk_, cn_)) != (rc_, rk_, cn_):
                 print(f"bench.py: two frames of scene {k_} disagree: {per_scene[k_]} vs {(rc_, rk_, cn_)}", file=sys.stderr)
                 return 1
-        got_stream = (Rt_all.cpu().numpy().copy(), mask_all.cpu().numpy().copy())
-        # ---- the waited form: the same frames, each begun only when the previous winner has reached the host
-        w_s = []
-        fence()
-        tw0 = time.perf_counter()
-        for f in range(args.steps):
-            ts0 = time.perf_counter()
-            a_ = ptrs[f % K]
-            if world == 1:
-                rcw, stw = reg.register_device(a_[0], a_[1], cfg.n, p_hot, a_[2], a_[3])
-            else:
-                rcw, stw = rs.waited(0, *a_)
-            w_s.append(time.perf_counter() - ts0)
-            if per_scene[f % K] != (rcw, stw["best_rank"], stw["best_count"]):
-                print(f"bench.py: waited and streamed frames of scene {f % K} disagree: {(rcw, stw['best_rank'], stw['best_count'])} vs {per_scene[f % K]}", file=sys.stderr)
+        if args.dump_outputs and rank == 0:
+            k_last = (args.steps - 1) % K   # (the frame's outputs are in its scene's slot)
+            dump_outputs(args.dump_outputs, Rt_all[k_last], mask_all[k_last], rc, st)
+        if args.full:
+            got_stream = (Rt_all.cpu().numpy().copy(), mask_all.cpu().numpy().copy())
+            # ---- the waited form: the same frames, each begun only when the previous winner has reached the host
+            w_s = []
+            fence()
+            tw0 = time.perf_counter()
+            for f in range(args.steps):
+                ts0 = time.perf_counter()
+                a_ = ptrs[f % K]
+                if world == 1:
+                    rcw, stw = reg.register_device(a_[0], a_[1], cfg.n, p_hot, a_[2], a_[3])
+                else:
+                    rcw, stw = rs.waited(0, *a_)
+                w_s.append(time.perf_counter() - ts0)
+                if per_scene[f % K] != (rcw, stw["best_rank"], stw["best_count"]):
+                    print(f"bench.py: waited and streamed frames of scene {f % K} disagree: {(rcw, stw['best_rank'], stw['best_count'])} vs {per_scene[f % K]}", file=sys.stderr)
+                    return 1
+            fence()
+            dtw = time.perf_counter() - tw0
+            got_waited = (Rt_all.cpu().numpy(), mask_all.cpu().numpy())
+            seen = sorted(per_scene)
+            if not (np.array_equal(got_stream[0][seen].view(np.uint32), got_waited[0][seen].view(np.uint32)) and np.array_equal(got_stream[1][seen], got_waited[1][seen])):
+                print("bench.py: (R, t) or mask of a streamed frame differs from the waited call's", file=sys.stderr)
                 return 1
-        fence()
-        dtw = time.perf_counter() - tw0
-        got_waited = (Rt_all.cpu().numpy(), mask_all.cpu().numpy())
-        seen = sorted(per_scene)
-        if not (np.array_equal(got_stream[0][seen].view(np.uint32), got_waited[0][seen].view(np.uint32)) and np.array_equal(got_stream[1][seen], got_waited[1][seen])):
-            print("bench.py: (R, t) or mask of a streamed frame differs from the waited call's", file=sys.stderr)
-            return 1
-        if world > 1:
-            twm = torch.tensor([dtw], dtype=torch.float64, device=dev)
-            dist.all_reduce(twm, op=dist.ReduceOp.MAX)
-            dtw = float(twm.item())
-        waited = {"ms_per_step": dtw / args.steps * 1e3, "ms_per_step_median": float(np.median(w_s)) * 1e3,
-                  "hypotheses_per_s": T_total * args.steps / dtw,
-                  "note": "the same frames, each begun only when the previous winner has reached the host (--frames-in-flight 1: "
-                          "the headline form of rounds 1 - 3, there on one repeated scene)"}
-        if not args.headline_only:
+            if world > 1:
+                twm = torch.tensor([dtw], dtype=torch.float64, device=dev)
+                dist.all_reduce(twm, op=dist.ReduceOp.MAX)
+                dtw = float(twm.item())
+            waited = {"ms_per_step": dtw / args.steps * 1e3, "ms_per_step_median": float(np.median(w_s)) * 1e3,
+                      "hypotheses_per_s": T_total * args.steps / dtw,
+                      "note": "the same frames, each begun only when the previous winner has reached the host (--frames-in-flight 1: "
+                              "the headline form of rounds 1 - 3, there on one repeated scene)"}
+        if args.full and not args.headline_only:
             # ---- r04's headline form beside it: every frame the SAME scene (the config's own), streamed
             dti, resi, si, _, _, _ = run_stream(args.steps, lambda f: 0)
             if world > 1:
@@ -546,51 +575,90 @@ def main() -> int:
                 hot_score += st["us_score"]; n_hot_timed += 1
         fence()
         dt = time.perf_counter() - t0
-    # (the stage passes, the CPU baseline and the legs below run the config's own scene, scenes[0]: make it the context's last call)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, d_Rt, d_mask, rc, st)
+    # (the line's `config` and `winner`, the stage passes, the CPU baseline and the legs below: the config's own scene, scenes[0];
+    # make it the context's last call)
     rc, st = step(p_hot, 0)
-    # ---- per-stage times of THE SAME code path: one bracket per pass (SC_FLAG_TIMING_ONE: two event records per call,
-    # speculative launches on), a few passes per stage; then one fully bracketed pass for the key kernel alone
-    n_diag = max(3, min(8, args.steps))
-    avg = {}
-    for k, name in enumerate(STAGES):
-        prm = mk(pkg.SC_FLAG_TIMING_ONE | pkg.SC_TIMING_STAGE(k))
-        acc = []
-        for _ in range(n_diag):
-            _, sd = step(prm)
-            acc.append(sd["us_" + name])
-        avg[name] = float(np.median(acc))
-    p_all = mk(pkg.SC_FLAG_TIMING)
-    tk = []
-    for _ in range(5):
-        _, sd = step(p_all)
-        tk.append(sd["us_trikeys"])
-    tk = float(np.median(tk))   # (a mean of three once carried a 40 us outlier into roofline_other)
+    if args.full:
+        # ---- per-stage times of THE SAME code path: one bracket per pass (SC_FLAG_TIMING_ONE: two event records per call,
+        # speculative launches on), a few passes per stage; then one fully bracketed pass for the key kernel alone
+        n_diag = max(3, min(8, args.steps))
+        avg = {}
+        for k, name in enumerate(STAGES):
+            prm = mk(pkg.SC_FLAG_TIMING_ONE | pkg.SC_TIMING_STAGE(k))
+            acc = []
+            for _ in range(n_diag):
+                _, sd = step(prm)
+                acc.append(sd["us_" + name])
+            avg[name] = float(np.median(acc))
+        p_all = mk(pkg.SC_FLAG_TIMING)
+        tk = []
+        for _ in range(5):
+            _, sd = step(p_all)
+            tk.append(sd["us_trikeys"])
+        tk = float(np.median(tk))   # (a mean of three once carried a 40 us outlier into roofline_other)
     fence()
     if world > 1:
         tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
-    if n_hot_timed:
-        us_score = hot_score / n_hot_timed  # the roofline duration of the dominant kernel: measured inside the timed steps
-    else:                                   # (--hot-timing-every 0: from eight calls after them)
-        us_score = sum(step(p_hot, f % K)[1]["us_score"] for f in range(8)) / 8
-        step(p_hot, 0)
-    c2_info = reg.debug_last()         # which C2 kernel the last call ran, the filter's hand-overs
-    # the filter kernel alone (its own dispatch timestamps; us_score spans filter + exact pass): eight more calls, outside the timed region
-    us_filter = []
-    for _ in range(8 if (world == 1 and c2_info["c2_kernel"] in (1, 2)) else 0):   # (one rank only: no collective may depend on a measurement)
-        step(p_hot)
-        us_filter.append(reg.debug_last()["us_c2_filter"])
-    us_filter = [u for u in us_filter if u > 0.0]
-    us_filter = sum(us_filter) / len(us_filter) if us_filter else None
+    if args.full:
+        if n_hot_timed:
+            us_score = hot_score / n_hot_timed  # the roofline duration of the dominant kernel: measured inside the timed steps
+        else:                                   # (--hot-timing-every 0: from eight calls after them)
+            us_score = sum(step(p_hot, f % K)[1]["us_score"] for f in range(8)) / 8
+            step(p_hot, 0)
+        c2_info = reg.debug_last()         # which C2 kernel the last call ran, the filter's hand-overs
+        # the filter kernel alone (its own dispatch timestamps; us_score spans filter + exact pass): eight more calls, outside the timed region
+        us_filter = []
+        for _ in range(8 if (world == 1 and c2_info["c2_kernel"] in (1, 2)) else 0):   # (one rank only: no collective may depend on a measurement)
+            step(p_hot)
+            us_filter.append(reg.debug_last()["us_c2_filter"])
+        us_filter = [u for u in us_filter if u > 0.0]
+        us_filter = sum(us_filter) / len(us_filter) if us_filter else None
 
+    out = None
     if rank == 0:
         n = cfg.n
         ms_per_step = dt / args.steps * 1e3
         value = T_total * args.steps / dt
         n_local = st["tri_scored"]
-        rows_local = n if not sharded_ab else int(ss.plan.rows_per_rank)
         dense = not args.no_dense_s
+        mode = "shard_ab" if sharded_ab else ("replicated_AB" if world > 1 else "single")
+        out = {
+            "metric": "triangle-hypotheses scored/sec (end-to-end: compat graph + ranked triangles + SVD + scoring + mask)",
+            "value": value, "unit": "hypotheses/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": ms_per_step, "ms_per_step_median": float(np.median(step_s)) * 1e3,
+            "ms_per_step_min_max": [round(float(np.min(step_s)) * 1e3, 4), round(float(np.max(step_s)) * 1e3, 4)],
+            "ms_of_each_timed_step": [round(float(x) * 1e3, 4) for x in step_s[:64]],
+            "higher_is_better": True, "scaling": args.scaling,
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic" + (" (REHEARSAL: all ranks on one GPU over gloo)" if rehearsal else ""),
+            "config": {"workload": f"{cfg.name}: N={n} synthetic correspondences (L={cfg.L}, tau={cfg.tau}; "
+                                   + (f"a stream of {K} DISTINCT scenes, seeds {cfg.seed} + k, inlier ratio {cfg.rho * 2 / 3:.0%} .. {cfg.rho * 4 / 3:.0%}: frame f registers scene f mod {K}"
+                                      if K > 1 else f"{cfg.rho:.0%} inliers, one scene repeated")
+                                   + f"), T_total={T_total} ranked triangles scored per step ({n_local} on this GPU)",
+                       "n_corr": n, "triangles_total": T_total, "triangles_this_gpu": n_local, "scenes": K,
+                       "edges": st["edges"], "triangles_enumerated": st["tri_total"],
+                       "edges_note": "`edges`, `triangles_enumerated`, `winner`, `stage_us`, the rooflines' counts: the config's own scene (scene 0 of the stream)",
+                       "parallelism": f"{mode}{world}", "dense_S": dense},
+            "winner": {"rank": st["best_rank"], "inliers": st["best_count"], "status": rc},
+            "how_the_timed_frames_ran": counters,
+            "how_the_timed_frames_ran_note": "cumulative counters of the two contexts over the timed frames (sc_debug_last): host_free = enqueued without a "
+                                             "host wait and valid at its end; host_free_then_repeated = a count outgrew what the launches covered (or "
+                                             "another assumption failed): the frame ran again the waiting way INSIDE the timed region; estimate_failed = "
+                                             "stage B's estimated pruning bound was too high: repeated with a certifying sample",
+            "step_form": ("stream of DISTINCT frames: step k + 1 enqueued before step k's winner is waited for ("
+                          + ("sc_register_device_async" if world == 1 else "host-free sc_hypothesize_device, all-gather, sc_finalize_gathered_device_async")
+                          + " / sc_wait, two contexts on one stream; serial on the GPU)") if pipelined else "waited: a step begins when the previous winner is on the host",
+        }
+        if sharded_ab:
+            out["config"]["bytes_received_per_step"] = ss.bytes_exchanged()
+        elif world > 1:
+            out["config"]["pruning_sample"] = "sharded + 1 KiB all-reduce" if split else "replicated"
+
+    if rank == 0 and args.full:
+        rows_local = n if not sharded_ab else int(ss.plan.rows_per_rank)
         # ---- rooflines (algorithmic bytes / flops per launch: DESIGN.md §5)
         compat_bytes = (4 * rows_local * n if dense else 0) + rows_local * n / 8 + 24 * n
         compat_gbs = compat_bytes / (max(avg["compat"], 1e-3) * 1e-6) / 1e9
@@ -683,23 +751,7 @@ def main() -> int:
                 r["traffic_source"] = pmc_src
         dominant, other = roofs[0], roofs[1:]
 
-        mode = "shard_ab" if sharded_ab else ("replicated_AB" if world > 1 else "single")
-        out = {
-            "metric": "triangle-hypotheses scored/sec (end-to-end: compat graph + ranked triangles + SVD + scoring + mask)",
-            "value": value, "unit": "hypotheses/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step, "ms_per_step_median": float(np.median(step_s)) * 1e3,
-            "ms_per_step_min_max": [round(float(np.min(step_s)) * 1e3, 4), round(float(np.max(step_s)) * 1e3, 4)],
-            "ms_of_each_timed_step": [round(float(x) * 1e3, 4) for x in step_s[:64]],
-            "higher_is_better": True, "scaling": args.scaling,
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic" + (" (REHEARSAL: all ranks on one GPU over gloo)" if rehearsal else ""),
-            "config": {"workload": f"{cfg.name}: N={n} synthetic correspondences (L={cfg.L}, tau={cfg.tau}; "
-                                   + (f"a stream of {K} DISTINCT scenes, seeds {cfg.seed} + k, inlier ratio {cfg.rho * 2 / 3:.0%} .. {cfg.rho * 4 / 3:.0%}: frame f registers scene f mod {K}"
-                                      if K > 1 else f"{cfg.rho:.0%} inliers, one scene repeated")
-                                   + f"), T_total={T_total} ranked triangles scored per step ({n_local} on this GPU)",
-                       "n_corr": n, "triangles_total": T_total, "triangles_this_gpu": n_local, "scenes": K,
-                       "edges": st["edges"], "triangles_enumerated": st["tri_total"],
-                       "edges_note": "`edges`, `triangles_enumerated`, `winner`, `stage_us`, the rooflines' counts: the config's own scene (scene 0 of the stream)",
-                       "parallelism": f"{mode}{world}", "dense_S": dense},
+        out.update({
             "score_stage_hyp_per_s": n_local * world / ((avg["kabsch"] + avg["score"] + avg["argmax"]) * 1e-6),
             "stage_us": {k: round(v, 2) for k, v in avg.items()} | {"trikeys": round(tk, 2)},
             # the stage as a whole — triangles enumerated per second and the bytes the row asks for (bit matrix once,
@@ -712,27 +764,14 @@ def main() -> int:
                                 "the pruned graph holds, a fraction of the graph's triangles; the stage is ten dependent launches of gathers, latency-bound"},
             "stage_us_note": "one HIP-event bracket per pass on the hot path (SC_FLAG_TIMING_ONE), median of the passes; `triangles` includes its "
                              "read-backs" + (" and the collectives between the phases" if sharded_ab else ""),
-            "winner": {"rank": st["best_rank"], "inliers": st["best_count"], "status": rc},
             "host_gap_us": round(ms_per_step * 1e3 - sum(avg.values()), 1),
             "host_gap_note": "step minus the sum of the stage brackets (taken on waited calls): the ramps between the stages; in the waited "
                              "form also the launch of the first kernel into an idle queue, the winner's way back to the host, Python between the calls",
-            "how_the_timed_frames_ran": counters,
-            "how_the_timed_frames_ran_note": "cumulative counters of the two contexts over the timed frames (sc_debug_last): host_free = enqueued without a "
-                                             "host wait and valid at its end; host_free_then_repeated = a count outgrew what the launches covered (or "
-                                             "another assumption failed): the frame ran again the waiting way INSIDE the timed region; estimate_failed = "
-                                             "stage B's estimated pruning bound was too high: repeated with a certifying sample",
             "stream_long": stream_long, "stream_identical_frames": stream_identical,
-            "step_form": ("stream of DISTINCT frames: step k + 1 enqueued before step k's winner is waited for ("
-                          + ("sc_register_device_async" if world == 1 else "host-free sc_hypothesize_device, all-gather, sc_finalize_gathered_device_async")
-                          + " / sc_wait, two contexts on one stream; serial on the GPU)") if pipelined else "waited: a step begins when the previous winner is on the host",
             "waited": waited,
             "bytes_moved_algorithmic": st.get("bytes_moved"),
             "roofline": dominant, "roofline_other": other,
-        }
-        if sharded_ab:
-            out["config"]["bytes_received_per_step"] = ss.bytes_exchanged()
-        elif world > 1:
-            out["config"]["pruning_sample"] = "sharded + 1 KiB all-reduce" if split else "replicated"
+        })
 
         if world == 1 and args.headline_only:
             pass
@@ -927,6 +966,7 @@ def main() -> int:
                                              f"(N={n}, T={T_total}) through oracle/saccot_oracle.c — this repo's CPU "
                                              "restatement (the reference has no CPU path); OpenMP over rows in stages A "
                                              "and B and over hypotheses in C; a reported baseline, not a target"}
+    if rank == 0:
         print(json.dumps(out))
 
     if world > 1:

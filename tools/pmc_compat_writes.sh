@@ -9,7 +9,7 @@ i=0
 for V in "" "--debug compat_rows=32" "--debug compat_store_mode=4" "--debug compat_store_mode=1" "--no-dense-s" "--debug compat_one_phase=1"; do
   i=$((i+1))
   timeout -k 10 90 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$OUT/v$i" -- \
-    python3 "$R/bench.py" --config C2 --steps 3 --warmup 1 --headline-only $V > "$OUT/v$i.log" 2>&1 || { echo "variant $V failed"; tail -5 "$OUT/v$i.log"; exit 1; }
+    python3 "$R/bench.py" --config C2 --steps 3 --warmup 1 --full --headline-only $V > "$OUT/v$i.log" 2>&1 || { echo "variant $V failed"; tail -5 "$OUT/v$i.log"; exit 1; }
   python3 - "$OUT/v$i" "$V" <<'PY'
 import csv, glob, sys, collections
 acc = collections.defaultdict(list); dur = []

@@ -11,7 +11,7 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 for V in "$@"; do
   timeout -k 10 240 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_MFMA SQ_WAVE_CYCLES SQ_WAVES SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_WAIT_ANY \
-    --output-format csv -d "$OUT/v$V" -- python3 "$R/bench.py" --config "$CFG" --steps 3 --warmup 1 --headline-only --debug filter_variant=$V \
+    --output-format csv -d "$OUT/v$V" -- python3 "$R/bench.py" --config "$CFG" --steps 3 --warmup 1 --full --headline-only --debug filter_variant=$V \
     > "$OUT/v$V.log" 2>&1 || { echo "variant $V failed"; tail -5 "$OUT/v$V.log"; exit 1; }
   python3 - "$OUT/v$V" "$V" <<'PY'
 import csv, glob, sys, collections

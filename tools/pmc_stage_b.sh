@@ -11,7 +11,7 @@ cd /tmp && export TMPDIR=/tmp
 run() {  # name counters...
   local name=$1; shift
   timeout -k 10 240 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d "$OUT/$name" -- \
-    python3 "$R/bench.py" --steps 8 --warmup 3 --headline-only --scenes 8 > "$OUT/$name.log" 2>&1 || { echo "pass $name failed"; tail -5 "$OUT/$name.log"; return 1; }
+    python3 "$R/bench.py" --steps 8 --warmup 3 --full --headline-only --scenes 8 > "$OUT/$name.log" 2>&1 || { echo "pass $name failed"; tail -5 "$OUT/$name.log"; return 1; }
   echo "pass $name ok"
 }
 run req TCC_REQ_sum TCC_READ_sum TCC_HIT_sum TCC_MISS_sum &&

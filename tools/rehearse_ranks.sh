@@ -7,7 +7,7 @@ for N in "$@"; do
  for MODE in "ab weak" "ab strong" "replicated weak"; do
   set -- $MODE; SH=$1; SC=$2
   SC_BENCH_REHEARSAL=1 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 \
-    --master-port $((29500 + N)) $R/bench.py --gpus $N --steps 5 --warmup 2 --no-cpu-baseline --shard $SH --scaling $SC \
+    --master-port $((29500 + N)) $R/bench.py --gpus $N --steps 5 --warmup 2 --no-cpu-baseline --full --shard $SH --scaling $SC \
     > $R/gpurun_out/rehearse_${N}_${SH}_${SC}.json 2> $R/gpurun_out/rehearse_${N}_${SH}_${SC}.err \
     || { tail -15 $R/gpurun_out/rehearse_${N}_${SH}_${SC}.err; exit 1; }
   python3 - <<PY

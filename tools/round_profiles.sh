@@ -10,12 +10,12 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out
 mkdir -p $O
 if [[ $PART == *a* ]]; then
-bash tools/gpu_check.sh $TAG > $O/${TAG}_gpu_check.txt 2>&1 || { tail -20 $O/${TAG}_gpu_check.txt; exit 1; }
+SC_OUT=$O bash tools/gpu_check.sh $TAG > $O/${TAG}_gpu_check.txt 2>&1 || { tail -20 $O/${TAG}_gpu_check.txt; exit 1; }
 tail -32 $O/${TAG}_gpu_check.txt
 for c in C1 C3 C4; do
-  timeout -k 10 300 python bench.py --config $c --steps 20 --warmup 3 --no-cpu-baseline > $O/${TAG}_bench_$c.json 2> $O/${TAG}_bench_$c.err || { tail -5 $O/${TAG}_bench_$c.err; exit 1; }
+  timeout -k 10 300 python bench.py --config $c --steps 20 --warmup 3 --no-cpu-baseline --full > $O/${TAG}_bench_$c.json 2> $O/${TAG}_bench_$c.err || { tail -5 $O/${TAG}_bench_$c.err; exit 1; }
   python3 -c "import json; d=json.load(open('$O/${TAG}_bench_$c.json')); print('$c ms/step %.4f value %.1f M/s' % (d['ms_per_step'], d['value']/1e6), d['stage_us'], d['roofline']['kernel'], d['roofline']['frac'], [ (r['kernel'], r['frac']) for r in d['roofline_other']])"
-  bash tools/prof_config.sh ${TAG}_$c $c --headline-only > $O/${TAG}_kernels_$c.txt 2>&1 || { tail -5 $O/${TAG}_kernels_$c.txt; exit 1; }   # (the other configs' kernel stats)
+  SC_OUT=$O bash tools/prof_config.sh ${TAG}_$c $c --headline-only > $O/${TAG}_kernels_$c.txt 2>&1 || { tail -5 $O/${TAG}_kernels_$c.txt; exit 1; }   # (the other configs' kernel stats)
   tail -24 $O/${TAG}_kernels_$c.txt
 done
 bash tools/pmc_collect.sh > $O/${TAG}_pmc.txt 2>&1 && python3 tools/pmc_summarize.py >> $O/${TAG}_pmc.txt 2>&1 || { tail -8 $O/${TAG}_pmc.txt; exit 1; }
