@@ -555,9 +555,31 @@ void launch_argmax(const Shard& sh, const uint32_t* partial, uint32_t n_chunks, 
 // reduced pair.
 // sh / RtSoA: this rank's shard and the (R,t) planes phase 1 produced — a locally scored winner is looked up there.
 // dp (optional; host-free calls): what the call's earlier kernels would have published to the host one by one — stage B's two counts
-// (device words; they go to dp->host[0] as ONE word: edges | triangles << 32, ~0 if either needs more than 32 bits) and, with_stats,
-// the staging kernel's coordinate statistics (FX_MX_WORDS words -> [13] maxima, [16 .. 21] boxes) — written by THIS kernel, before
+// (device words; they go to dp->host[HW_EDGES] as ONE word: edges | triangles << 32, ~0 if either needs more than 32 bits) and, with_stats,
+// the staging kernel's coordinate statistics (FX_MX_WORDS words -> HW_COORD_MAX, HW_BOX .. + 5) — written by THIS kernel, before
 // the winner.  Those kernels then publish nothing: a system-scope store costs the kernel that makes it ~0.5 us.
+// The host words: one host-pinned area of HW_COUNT x u64 per context (sc_ctx::pinned), through which the kernels hand single results to
+// the host.  The host ARMS a word it will poll (all ones: "pending"), or CLEARS a flag a kernel only ever sets; the kernel named
+// writes it with a system-scope store; the host reads it after polling it, or after the winner word — the last store of a call.
+enum HostWord : int {
+  HW_EDGES = 0,         // edge count.  Armed by run_row_stats / run_edges, written by the scan (or fused row / edge kernel), polled by run_edges.
+                        // Host-free call: edges | triangles << 32 in ONE word, written by the finalize kernel (DeferredPub), read by finalize_wait
+  HW_BAD_INPUT = 1,     // non-finite input coordinate.  Cleared by stage_inputs, set (low half) by the staging kernel, read by run_edges / finalize_wait / the hooks
+  HW_TRIANGLES = 2,     // triangle count (of the pruned graph when pruning).  Armed and polled by run_select, written by the scan of the counts
+  HW_TOTAL = 4,         // 3-cliques of the unpruned graph (SC_FLAG_EXACT_TOTAL).  Written by its scan in run_edges, read by run_select behind HW_TRIANGLES
+  HW_EV_OVERFLOW = 5,   // an event-list region was full.  Cleared by run_select, set (low half) by the counting pass, read by run_select / finalize_wait
+  HW_MERGED_T = 6,      // sharded select: merged T_eff.  Armed and polled by sc_shard_score_device, written by merge_prepare ...
+  HW_MERGED_M = 7,      // ... together with the number of candidates merged (written before HW_MERGED_T)
+  HW_WINNER = 8,        // the winner's key: the last word a call writes.  Armed by finalize_enqueue, written by the finalize kernel, polled by finalize_wait
+  HW_WINNER_POS = 9,    // rank << 32 | position of the winner (all ones: the pair decodes to nothing).  Written before HW_WINNER, read behind it
+  HW_CAND_CUT = 12,     // a cut candidate list mattered (SC_ERETRY).  Cleared by sc_shard_score_device, set by merge_check, read by finalize_wait
+  HW_COORD_MAX = 13,    // max|tgt| << 32 | max|src|.  Armed by stage_inputs, written by the staging kernel (host-free: by the finalize kernel, every 64th
+                        // call), read with acquire by read_coord_stats; sc_score_host polls it
+  HW_SELECT_SHORT = 14, // the select found fewer keys above the pruning bound than promised.  Cleared by run_edges, set by select / compaction, read by finalize_wait
+  HW_MERGE_SHORT = 15,  // the merged candidates hold fewer than T keys above an estimated bound.  Cleared by sc_shard_score_device, set by merge_prepare, read by finalize_wait
+  HW_BOX = 16,          // .. 21: the two bounding boxes, (key of -min) << 32 | key of max per axis.  Written BEFORE HW_COORD_MAX by the same kernel, read behind it
+  HW_COUNT = 22
+};
 struct DeferredPub {
   const uint64_t* dev_edges;
   const uint64_t* dev_triangles;

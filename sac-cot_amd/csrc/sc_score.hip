@@ -2063,10 +2063,10 @@ __global__ __launch_bounds__(256) void finalize_kernel(const float* __restrict__
         // kernel by the statistics of an earlier frame anyway, and any pick gives the same counts.
         auto put = [&](int idx, unsigned long long v) { __hip_atomic_store(&dp.host[idx], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); };
         const unsigned long long e = *dp.dev_edges, m = *dp.dev_triangles;
-        put(0, (e < (1ull << 32) && m < (1ull << 32)) ? (e | (m << 32)) : ~0ull);
+        put(HW_EDGES, (e < (1ull << 32) && m < (1ull << 32)) ? (e | (m << 32)) : ~0ull);
         if (dp.with_stats) {
-          for (int k = 0; k < 6; k++) put(16 + k, ((unsigned long long)dp.coord_max[8 + k] << 32) | dp.coord_max[2 + k]);
-          put(13, ((unsigned long long)dp.coord_max[1] << 32) | dp.coord_max[0]);
+          for (int k = 0; k < 6; k++) put(HW_BOX + k, ((unsigned long long)dp.coord_max[8 + k] << 32) | dp.coord_max[2 + k]);
+          put(HW_COORD_MAX, ((unsigned long long)dp.coord_max[1] << 32) | dp.coord_max[0]);
         }
       }
       if (host_out) {  // [0] last: the host polls it (release orders the others before it)
