@@ -34,7 +34,7 @@ extern "C" {
 #endif
 
 #define SC_VERSION_MAJOR 0
-#define SC_VERSION_MINOR 8   /* 0.8: sc_debug_info grew cumulative counters of how a context's frames ran (saccot_debug.h); every entry refuses a context with an outstanding call; a host-free enqueue that does not fit the workspace cap runs the waited way.  0.7: sc_finalize_gathered_device_async (+ sc_wait), sc_hypothesize_device with SC_FLAG_EST_BOUND host-free on a repeated shape.  0.6: SC_FLAG_EST_BOUND also on sc_hypothesize_device (SC_EBOUND from the finalize call); SC_FLAG_SHARD_AB (sc_register_multi replicates stages A and B on small graphs unless told otherwise); sc_debug / sc_debug_info grew (the Gram filter's frame and cut: saccot_debug.h).  0.5: sc_register_device_async / sc_wait (host-free enqueue), SC_FLAG_EST_BOUND / SC_EBOUND (sharded stage B pruned by an estimated bound), sc_stats.bytes_moved, the debug hooks moved to
+#define SC_VERSION_MINOR 9   /* 0.9: sc_peel / sc_peel_device / sc_register_instances (further rigid motions from a scored frame).  0.8: sc_debug_info grew cumulative counters of how a context's frames ran (saccot_debug.h); every entry refuses a context with an outstanding call; a host-free enqueue that does not fit the workspace cap runs the waited way.  0.7: sc_finalize_gathered_device_async (+ sc_wait), sc_hypothesize_device with SC_FLAG_EST_BOUND host-free on a repeated shape.  0.6: SC_FLAG_EST_BOUND also on sc_hypothesize_device (SC_EBOUND from the finalize call); SC_FLAG_SHARD_AB (sc_register_multi replicates stages A and B on small graphs unless told otherwise); sc_debug / sc_debug_info grew (the Gram filter's frame and cut: saccot_debug.h).  0.5: sc_register_device_async / sc_wait (host-free enqueue), SC_FLAG_EST_BOUND / SC_EBOUND (sharded stage B pruned by an estimated bound), sc_stats.bytes_moved, the debug hooks moved to
                                 saccot_debug.h; 0.4: sc_debug_last / sc_debug_info, sc_debug.filter_blind; 0.3: sc_set_debug (no environment variables), SC_FLAG_NO_DENSE_S, sc_shard_* (stages A and B sharded); 0.2: SC_FLAG_TIMING_HOT,
                                 SC_STREAM_DEFAULT, sc_hypothesize_begin/end_device, sc_finalize_gathered_device */
 
@@ -217,6 +217,50 @@ int sc_register_device(sc_ctx* ctx, const float* d_src, const float* d_tgt, int6
 int sc_register_device_async(sc_ctx* ctx, const float* d_src, const float* d_tgt, int64_t n,
                              const sc_params* params, float* d_Rt, uint8_t* d_mask);
 int sc_wait(sc_ctx* ctx, sc_stats* stats);
+
+/* ---- further rigid motions from a scored frame: sc_peel ---------------------------------------------
+ * sc_register answers "which ONE rigid motion explains most correspondences".  The T scored hypotheses stay in the
+ * context; a ROUND re-scores them over the correspondences no earlier winner has claimed — stages C2 + C3 only, a
+ * fraction of a frame — and returns the next motion: a second instance, the background, or a runner-up that is
+ * distinct from the winner (winner 236 inliers, next round 4: unambiguous; 236 then 210: a repeated structure).
+ *
+ * A FRAME is what an sc_register / sc_register_device / sc_register_device_async + sc_wait call that returned SC_OK
+ * (shard_world == 1) leaves in its context.  Its mask is the claimed set C_0.  Round r >= 1:
+ *   1. alive = correspondences not in C_{r-1};
+ *   2. score_r(h) of every hypothesis h of the frame's selection = the frame's score_mode over the alive ones only
+ *      (canonical fp32 chain; sums of integers, so independent of order);
+ *   3. winner = largest score_r, ties by best ranking key, then lowest (i, j, k): the frame's own total order;
+ *   4. every score_r == 0: SC_ENOHYP, R = I, t = 0, mask all zero, C_r = C_{r-1}; a further call returns the same;
+ *   5. mask_r[m] = alive[m] and |R p_m + t - q_m|^2 < tau^2 (the winner's fp32 (R, t)), n bytes in the caller's
+ *      ORIGINAL indexing; C_r = C_{r-1} u mask_r;
+ *   6. with SC_FLAG_REFINE in the frame's parameters (R, t) is the fp64 refit over mask_r; mask_r stays the fp32 winner's;
+ *   7. stats: n, edges, tri_total, tri_kept as the frame reported them, tri_scored = tri_kept, best_rank = the winner's
+ *      index in the ranked list, best_count = score_r(winner) (inlier-count mode: == popcount(mask_r)).  A frame with
+ *      SC_FLAG_TIMING: us_stage = the claim + compact launch, us_score, us_argmax, us_mask (with the refit), us_total.
+ * A round's results are a function of the frame's input and r only — not of how the frame was enqueued (waited,
+ * host-free, repeated), of which C2 kernel scored it, or of the context's history.
+ * What ends a frame: any other computing entry on the context (sc_register*, sc_hypothesize*, sc_finalize*, sc_shard_*,
+ * every sc_*_host hook), or a frame call that did not return SC_OK.  sc_peel* without a frame: SC_EINVAL (sc_last_error
+ * says so); with a call outstanding: SC_EINVAL as everywhere.  d_src / d_tgt need not stay valid after the frame call:
+ * rounds read the context's staged copy.  Rounds wait for their winner (there is no async form).  Sharded and multi-GPU
+ * forms (sc_hypothesize*, sc_shard_*, sc_register_multi) leave no frame.
+ * NOT "run the path again on the rest": the compatibility graph and the ranked list are the frame's.  A motion none of
+ * whose triangles made the frame's top T cannot be found by peeling — for that case run a second sc_register on the
+ * correspondences no round has claimed.
+ * The first round allocates the rounds' workspace (a second set of planes, n claimed bytes; they count toward
+ * workspace_bytes); a context that never peels allocates and runs nothing new. */
+/* round r of the frame in ctx; outputs in HBM (d_Rt: 12 floats), visibility as for sc_register_device */
+int sc_peel_device(sc_ctx* ctx, float* d_Rt, uint8_t* d_mask, sc_stats* stats);
+/* the same, host outputs */
+int sc_peel(sc_ctx* ctx, float R[9], float t[3], uint8_t* mask, sc_stats* stats);
+/* frame + rounds in one call (host arrays): stops after max_instances motions (1 .. 65536), or at the first whose
+ * best_count < min_score (that one is not returned), or at SC_ENOHYP.  Motion 0 is the frame's winner, motion k round k's.
+ * Rt: max_instances x 12; score: max_instances; label: n x int32, the index of the motion that claimed correspondence m,
+ * -1 for none (built on the device, copied out once); *n_found >= 0.  Returns the frame's status if the frame fails
+ * (SC_ENOHYP: *n_found = 0, label all -1), else SC_OK.  stats: the frame's.  Rounds may follow (sc_peel). */
+int sc_register_instances(sc_ctx* ctx, const float* src, const float* tgt, int64_t n, const sc_params* params,
+                          uint32_t max_instances, uint32_t min_score, float* Rt, uint32_t* score, int32_t* label,
+                          uint32_t* n_found, sc_stats* stats);
 
 /* ---- two-phase form for one-process-per-GPU sharding --------------------------------
  * Phase 1: A and B replicated, C1+C2 on this rank's blocks of the top-T list; writes this rank's winner key

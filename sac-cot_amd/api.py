@@ -36,6 +36,7 @@ SC_HIST_WORDS = 256  # u32 words of the pruning-sample histogram (sc_hypothesize
 
 EXPORTS = ["sc_version", "sc_strerror", "sc_default_params", "sc_create", "sc_destroy", "sc_set_stream",
            "sc_last_error", "sc_set_debug", "sc_debug_last", "sc_register", "sc_register_device", "sc_register_device_async", "sc_wait",
+           "sc_peel", "sc_peel_device", "sc_register_instances",
            "sc_hypothesize_device", "sc_finalize_device",
            "sc_hypothesize_begin_device", "sc_hypothesize_end_device", "sc_finalize_gathered_device", "sc_finalize_gathered_device_async",
            "sc_shard_plan_query", "sc_shard_compat_device", "sc_shard_edges_device", "sc_shard_select_device",
@@ -149,6 +150,10 @@ def load_library() -> C.CDLL:
     L.sc_register_device.argtypes = [vp, vp, vp, C.c_int64, pp, vp, vp, sp]
     L.sc_register_device_async.argtypes = [vp, vp, vp, C.c_int64, pp, vp, vp]
     L.sc_wait.argtypes = [vp, sp]
+    L.sc_peel.argtypes = [vp, f32p, f32p, u8p, sp]
+    L.sc_peel_device.argtypes = [vp, vp, vp, sp]
+    L.sc_register_instances.argtypes = [vp, f32p, f32p, C.c_int64, pp, C.c_uint32, C.c_uint32, f32p, u32p, C.POINTER(C.c_int32),
+                                        u32p, sp]
     L.sc_hypothesize_device.argtypes = [vp, vp, vp, C.c_int64, pp, vp, sp]
     L.sc_finalize_device.argtypes = [vp, vp, vp, vp, sp]
     L.sc_hypothesize_begin_device.argtypes = [vp, vp, vp, C.c_int64, pp, vp, sp]
@@ -210,6 +215,7 @@ class Registrar:
                               + self._lib.sc_strerror(rc).decode())
         self._h = h
         self.device = device
+        self._frame_n = 0  # correspondences of the last register* call: what peel() sizes its mask by
 
     def close(self):
         if getattr(self, "_h", None):
@@ -274,6 +280,7 @@ class Registrar:
         n = src.shape[0] if p.layout == SC_AOS else src.shape[1]
         R = np.zeros(9, np.float32); t = np.zeros(3, np.float32); mask = np.zeros(n, np.uint8)
         st = ScStats(C.sizeof(ScStats))
+        self._frame_n = n
         rc = self._check(self._lib.sc_register(self._h, _p(src, C.c_float), _p(tgt, C.c_float), n, C.byref(p),
                                                _p(R, C.c_float), _p(t, C.c_float), _p(mask, C.c_uint8), C.byref(st)),
                          allow=(SC_ENOHYP,))
@@ -282,6 +289,7 @@ class Registrar:
     # ---- device-resident forms (pointers are ints: torch .data_ptr()) -------------------------------------
     def register_device(self, d_src: int, d_tgt: int, n: int, params: ScParams, d_Rt: int, d_mask: int):
         st = ScStats(C.sizeof(ScStats))
+        self._frame_n = n
         rc = self._check(self._lib.sc_register_device(self._h, d_src, d_tgt, n, C.byref(params), d_Rt, d_mask,
                                                       C.byref(st)), allow=(SC_ENOHYP,))
         return rc, st.as_dict()
@@ -289,6 +297,7 @@ class Registrar:
     def register_device_async(self, d_src: int, d_tgt: int, n: int, params: ScParams, d_Rt: int, d_mask: int):
         """sc_register_device_async: enqueue the whole path and return; `wait()` delivers status and statistics.  At most
         one call outstanding per Registrar; inputs must stay valid until wait() returns."""
+        self._frame_n = n
         self._check(self._lib.sc_register_device_async(self._h, d_src, d_tgt, n, C.byref(params), d_Rt, d_mask))
 
     def wait(self):
@@ -296,6 +305,40 @@ class Registrar:
         st = ScStats(C.sizeof(ScStats))
         rc = self._check(self._lib.sc_wait(self._h, C.byref(st)), allow=(SC_ENOHYP, SC_ERETRY, SC_EBOUND))
         return rc, st.as_dict()
+
+    # ---- further rigid motions from the frame the last register* call left (include/saccot.h, sc_peel) ------
+    def peel(self):
+        """sc_peel: the next round on the frame in this context -> dict(status, R, t, mask, stats) like register()'s; SC_ENOHYP
+        (no hypothesis explains an unclaimed correspondence) is a status, not an exception.  The frame's n sizes the mask."""
+        R = np.zeros(9, np.float32); t = np.zeros(3, np.float32)
+        n = self._frame_n
+        mask = np.zeros(max(n, 1), np.uint8)
+        st = ScStats(C.sizeof(ScStats))
+        rc = self._check(self._lib.sc_peel(self._h, _p(R, C.c_float), _p(t, C.c_float), _p(mask, C.c_uint8), C.byref(st)),
+                         allow=(SC_ENOHYP,))
+        return dict(status=rc, R=R.reshape(3, 3), t=t, mask=mask[:n], stats=st.as_dict())
+
+    def peel_device(self, d_Rt: int, d_mask: int):
+        """sc_peel_device: the same with the outputs in HBM (d_Rt: 12 floats, d_mask: n bytes) -> (status, stats)."""
+        st = ScStats(C.sizeof(ScStats))
+        rc = self._check(self._lib.sc_peel_device(self._h, d_Rt, d_mask, C.byref(st)), allow=(SC_ENOHYP,))
+        return rc, st.as_dict()
+
+    def register_instances(self, src, tgt, max_instances: int = 8, min_score: int = 0, params: ScParams | None = None, **kw):
+        """sc_register_instances: the frame and its rounds in one call -> dict(status, Rt (k,12), score (k,), label (n,) int32:
+        the motion that claimed each correspondence, -1 for none; stats: the frame's)."""
+        p = params or make_params(**kw)
+        src, tgt = _f32c(src), _f32c(tgt)
+        n = src.shape[0] if p.layout == SC_AOS else src.shape[1]
+        Rt = np.zeros((max_instances, 12), np.float32); score = np.zeros(max_instances, np.uint32)
+        label = np.full(n, -1, np.int32); found = C.c_uint32(0)
+        st = ScStats(C.sizeof(ScStats))
+        rc = self._check(self._lib.sc_register_instances(self._h, _p(src, C.c_float), _p(tgt, C.c_float), n, C.byref(p),
+                                                         max_instances, min_score, _p(Rt, C.c_float), _p(score, C.c_uint32),
+                                                         _p(label, C.c_int32), C.byref(found), C.byref(st)), allow=(SC_ENOHYP,))
+        self._frame_n = n
+        k = int(found.value)
+        return dict(status=rc, Rt=Rt[:k].copy(), score=score[:k].copy(), label=label, stats=st.as_dict())
 
     def hypothesize_device(self, d_src: int, d_tgt: int, n: int, params: ScParams, d_key: int):
         st = ScStats(C.sizeof(ScStats))

@@ -81,6 +81,12 @@ struct Pass {
   // sharded A + B (sc_shard_*_device): the phase reached (0: none) and the gathered candidate blobs
   bool sharded_ab = false; int shard_phase = 0;
   const void* cand_all = nullptr; size_t cand_bytes = 0;
+  // rounds on this pass's frame (sc_peel): set where a frame's status becomes SC_OK (sc_wait, whichever way the frame ran), gone with
+  // the pass (pass_begin) or when any other computing entry is called (peel_end)
+  bool peelable = false;
+  uint32_t peel_round = 0;           // rounds done
+  uint32_t peel_prev = 0xFFFFFFFFu;  // position of the winner whose mask the next round's claim step folds in (all ones: none)
+  uint32_t peel_claimed = 0;         // inlier-count mode: correspondences claimed so far (the best_counts add up to it)
 };
 
 // One call of an entry point as its caller sees it: it survives the library's own repeat of the call (sc_wait -> register_waited: a
@@ -113,7 +119,8 @@ struct sc_ctx {
   // workspace (grow-only)
   Buf in_src, in_tgt, planes, S, bits, deg, degp, wpre, ebase, edge_off, scan_tmp, ei, ej, es, ebi, ebj, tcnt, toff, wkey, kcol, ctl, events, blk_gt,
       blk_eq, blk_minmax, bits2, off_gt, off_eq, sel_ord, sel_key, sortkey, sorted, sort_tmp, tri, tri_rk, key_rk, rt, rt_aos, partial, cnt, key, rt12,
-      mask, refine_tmp, amx_pairs, strong, rowcost, cost_pre, lb_state, lb_ticket, fx_tile, fx_state, fx_mx, fx_part, fx_coef, guard_tmp, fx_frame, ref_cand;
+      mask, refine_tmp, amx_pairs, strong, rowcost, cost_pre, lb_state, lb_ticket, fx_tile, fx_state, fx_mx, fx_part, fx_coef, guard_tmp, fx_frame, ref_cand,
+      peel_planes, peel_claimed, peel_words, peel_label;  // sc_peel / sc_register_instances: allocated by the first round, never by a frame
   // the XCD-aware block orders of stage A (compat_wg_map), one per row width met so far: a context that alternates between a few
   // sizes must not rebuild and upload the map on every call (that cost 2 ms per call in bench.py's varying-n leg)
   static constexpr int N_WG_MAPS = 8;
@@ -921,6 +928,9 @@ int busy(sc_ctx* c) {  // an sc_register_device_async / sc_finalize_gathered_dev
   return SC_EINVAL;
 }
 
+// Any computing entry other than sc_peel* ends the frame the context may hold (include/saccot.h, sc_peel)
+void peel_end(sc_ctx* c) { c->pass.peelable = false; }
+
 // The stage hooks start no pass: they run on whatever the last one left, and clear what would change their kernels
 int host_to_planes(sc_ctx* c, const float* src, const float* tgt, int64_t n, const sc_params* p) {
   { const int brc = busy(c); if (brc) return brc; }
@@ -1010,7 +1020,8 @@ void sc_destroy(sc_ctx* c) {
   Buf* bufs[] = {&c->in_src, &c->in_tgt, &c->planes, &c->S, &c->bits, &c->deg, &c->degp, &c->wpre, &c->ebase, &c->edge_off, &c->scan_tmp,
                  &c->ei, &c->ej, &c->es, &c->ebi, &c->ebj, &c->tcnt, &c->toff, &c->wkey, &c->kcol, &c->ctl, &c->events, &c->blk_gt, &c->blk_eq, &c->blk_minmax, &c->bits2, &c->off_gt,
                  &c->off_eq, &c->sel_ord, &c->sel_key, &c->sortkey, &c->sorted, &c->sort_tmp, &c->tri, &c->tri_rk, &c->key_rk, &c->rt,
-                 &c->rt_aos, &c->partial, &c->cnt, &c->key, &c->rt12, &c->mask, &c->refine_tmp, &c->amx_pairs, &c->strong, &c->rowcost, &c->cost_pre, &c->lb_state, &c->lb_ticket, &c->fx_tile, &c->fx_state, &c->fx_mx, &c->fx_part, &c->fx_coef, &c->guard_tmp, &c->fx_frame, &c->ref_cand};
+                 &c->rt_aos, &c->partial, &c->cnt, &c->key, &c->rt12, &c->mask, &c->refine_tmp, &c->amx_pairs, &c->strong, &c->rowcost, &c->cost_pre, &c->lb_state, &c->lb_ticket, &c->fx_tile, &c->fx_state, &c->fx_mx, &c->fx_part, &c->fx_coef, &c->guard_tmp, &c->fx_frame, &c->ref_cand,
+                 &c->peel_planes, &c->peel_claimed, &c->peel_words, &c->peel_label};
   for (sc_ctx::WgMap& m : c->wg_maps) if (m.buf.p) (void)hipFree(m.buf.p);
   for (Buf* b : bufs) if (b->p) (void)hipFree(b->p);
   for (int i = 0; i < N_EVENTS; i++) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
@@ -1115,6 +1126,7 @@ namespace {
 // A frame starts here and nowhere else: every entry point that begins a call of its own (not the library's repeat of one) comes
 // through here, and finds nothing of the previous frame
 int frame_begin(sc_ctx* c) {
+  peel_end(c);
   const int rc = busy(c);
   if (!rc) c->frame = Frame{};
   return rc;
@@ -1377,6 +1389,7 @@ int sc_hypothesize_begin_device(sc_ctx* c, const float* d_src, const float* d_tg
 
 int sc_hypothesize_end_device(sc_ctx* c, const uint32_t* d_hist, uint64_t* d_key, sc_stats* stats) {
   if (!c || !d_hist || !d_key) return SC_EINVAL;
+  peel_end(c);
   { const int brc = busy(c); if (brc) return brc; }
   if (!c->pass.begun) { c->last_error = "sc_hypothesize_end_device without a preceding sc_hypothesize_begin_device"; return SC_EINVAL; }
   HIPCHK(c, hipSetDevice(c->device));
@@ -1433,6 +1446,7 @@ int sc_shard_compat_device(sc_ctx* c, const float* d_src, const float* d_tgt, in
 
 int sc_shard_edges_device(sc_ctx* c, uint32_t* d_hist) {
   if (!c || !d_hist) return SC_EINVAL;
+  peel_end(c);
   { const int brc = busy(c); if (brc) return brc; }
   if (!c->pass.sharded_ab || c->pass.shard_phase != 1) { c->last_error = "sc_shard_edges_device: call sc_shard_compat_device first"; return SC_EINVAL; }
   HIPCHK(c, hipSetDevice(c->device));
@@ -1447,6 +1461,7 @@ int sc_shard_edges_device(sc_ctx* c, uint32_t* d_hist) {
 
 int sc_shard_select_device(sc_ctx* c, const uint32_t* d_hist, void* d_cand_mine) {
   if (!c || !d_hist || !d_cand_mine) return SC_EINVAL;
+  peel_end(c);
   { const int brc = busy(c); if (brc) return brc; }
   if (!c->pass.sharded_ab || c->pass.shard_phase != 2) { c->last_error = "sc_shard_select_device: call sc_shard_edges_device first"; return SC_EINVAL; }
   HIPCHK(c, hipSetDevice(c->device));
@@ -1470,6 +1485,7 @@ int sc_shard_select_device(sc_ctx* c, const uint32_t* d_hist, void* d_cand_mine)
 
 int sc_shard_score_device(sc_ctx* c, const void* d_cand_all, uint64_t* d_key, sc_stats* stats) {
   if (!c || !d_cand_all || !d_key) return SC_EINVAL;
+  peel_end(c);
   { const int brc = busy(c); if (brc) return brc; }
   if (!c->pass.sharded_ab || c->pass.shard_phase != 3) { c->last_error = "sc_shard_score_device: call sc_shard_select_device first"; return SC_EINVAL; }
   HIPCHK(c, hipSetDevice(c->device));
@@ -1735,6 +1751,7 @@ static int finalize_status(sc_ctx* c, int rc) {
 // the finalize call's two forms: arguments, a free context, a hypothesize half to finalize; then the winner / mask kernel is enqueued
 static int finalize_begin(sc_ctx* c, const uint64_t* d_keys, int n_pairs, float* d_Rt, uint8_t* d_mask) {
   if (!c || !d_keys || !d_Rt || !d_mask || n_pairs < 1 || n_pairs > 4096) return SC_EINVAL;
+  peel_end(c);
   { const int brc = busy(c); if (brc) return brc; }
   if (!c->pass.have_hyp) { c->last_error = "sc_finalize_device without a preceding sc_hypothesize_device"; return SC_EINVAL; }
   HIPCHK(c, hipSetDevice(c->device));
@@ -1762,6 +1779,7 @@ int sc_finalize_gathered_device_async(sc_ctx* c, const uint64_t* d_keys, int n_p
 int sc_register_device_async(sc_ctx* c, const float* d_src, const float* d_tgt, int64_t n, const sc_params* p,
                              float* d_Rt, uint8_t* d_mask) {
   if (!c || !d_src || !d_tgt || !d_Rt || !d_mask) return SC_EINVAL;
+  peel_end(c);
   if (c->frame.pending) { c->last_error = "sc_register_device_async: a call is already outstanding on this context (sc_wait first)"; return SC_EINVAL; }
   int rc = check_params(p);
   if (rc) return rc;
@@ -1816,6 +1834,13 @@ int sc_wait(sc_ctx* c, sc_stats* stats) {
   }
   count_frame(c, rc);
   if (stats && stats->size == sizeof(sc_stats)) *stats = c->frame.pend_stats;
+  if (rc == SC_OK) {
+    // a frame: sc_peel may follow.  The same state whichever way the frame ran (waited, host-free, repeated after a miss): the
+    // winner's words are those of the pass that delivered the outputs
+    c->pass.peelable = true; c->pass.peel_round = 0;
+    c->pass.peel_prev = (uint32_t)c->pinned[HW_WINNER_POS];
+    c->pass.peel_claimed = (uint32_t)(c->pinned[HW_WINNER] >> 32);
+  }
   return rc;
 }
 
@@ -1827,6 +1852,7 @@ int sc_register_device(sc_ctx* c, const float* d_src, const float* d_tgt, int64_
 
 int sc_register(sc_ctx* c, const float* src, const float* tgt, int64_t n, const sc_params* p, float R[9],
                 float t[3], uint8_t* mask, sc_stats* stats) {
+  if (c) peel_end(c);
   if (!c || !src || !tgt || !R || !t || !mask || n < 3 || n > (1 << 24)) return SC_EINVAL;
   int rc = check_params(p);
   if (rc) return rc;
@@ -1885,6 +1911,172 @@ int sc_register(sc_ctx* c, const float* src, const float* tgt, int64_t n, const 
   return rc;
 }
 
+// ---- rounds on a scored frame (include/saccot.h, sc_peel) ----------------------------------------------
+//
+// claim + compact -> score -> arg-max -> winner / mask (+ refit): four launches of a dependent chain (five with SC_FLAG_REFINE), then
+// the wait for the winner.  Stage C2 of a round is the PLAIN fp32 kernel (launch_score) on the compacted planes, in every score
+// mode: exact by construction.  The frame's filter path is not reused: its tile, its coefficient permutation and its reference
+// frame are built inside the frame's Kabsch launch for the frame's n correspondences (FilterPlan is planned by n, the Gram cut's
+// reference was elected for the frame's winner, whose correspondences are the first to go) — a round would have to rebuild all
+// three for n_alive points, which costs more launches than the filter saves at a round's size.
+static int peel_round(sc_ctx* c, float* d_Rt, uint8_t* d_mask, sc_stats* stats) {
+  { const int brc = busy(c); if (brc) return brc; }
+  if (!c->pass.peelable) {
+    c->last_error = "sc_peel: no frame on this context (a round follows an sc_register* call that returned SC_OK with shard_world == 1; any other computing call ends the frame)";
+    return SC_EINVAL;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  Pass& ps = c->pass;
+  const sc_params* p = &ps.params;
+  const Shard& sh = ps.sh;  // one rank: n_local == T_eff, a position in the selection IS the index into c->rt
+  hipStream_t st = c->stream;
+  const size_t n = (size_t)ps.n, ld = (size_t)ps.ld;
+  int rc;
+  ENSURE(c, c->peel_planes, 6 * ld * sizeof(float));
+  ENSURE(c, c->peel_claimed, n);
+  if (!c->peel_words.p) {
+    ENSURE(c, c->peel_words, sizeof(PeelWords));
+    HIPCHK(c, hipMemsetAsync(c->peel_words.p, 0, c->peel_words.cap, st));
+  }
+  PeelWords* words = c->peel_words.as<PeelWords>();
+  if ((rc = rec(c, 0))) return rc;
+  LbArgs lb;
+  if ((rc = lb_next(c, (size_t)peel_compact_tiles(ps.n) * 8, 2, 0, &lb))) return rc;
+  // the host sizes the scoring launch by n_alive: in inlier-count mode it knows it (n minus the best_counts so far: best_count ==
+  // popcount(mask) there); in the truncated modes the compaction hands it over (one word, polled)
+  const bool read_alive = p->score_mode != SC_SCORE_COUNT;
+  if (read_alive) arm_word(c, HW_PEEL_ALIVE);
+  launch_peel_compact(points_of(c), c->rt.as<float>(), sh.ld_local, ps.peel_prev, ps.dv.tau2, ps.peel_round == 0,
+                      c->peel_claimed.as<uint8_t>(), c->peel_planes.as<float>(), words, lb, read_alive ? &c->pinned[HW_PEEL_ALIVE] : nullptr, st);
+  ps.peel_prev = 0xFFFFFFFFu;  // folded in
+  if ((rc = rec(c, 1))) return rc;
+  uint64_t n_alive = n - ps.peel_claimed;
+  if (read_alive) {
+    if ((rc = wait_word(c, HW_PEEL_ALIVE))) return rc;
+    n_alive = c->pinned[HW_PEEL_ALIVE];
+    if (n_alive > n) { c->last_error = "internal: the compaction kept more correspondences than the frame has"; return SC_EHIP; }
+  }
+  int npairs = 0;
+  if (n_alive != 0) {  // (nothing alive: every score is 0 — the winner kernel reports "no hypothesis" from zero pairs)
+    const Points alive{c->peel_planes.as<float>(), (int)n_alive, ps.ld};  // (the six planes only: the plain kernel reads nothing else)
+    const uint32_t rows = score_chunks((int)n_alive, sh.ld_local);
+    ENSURE(c, c->partial, (size_t)rows * sh.ld_local * 4);
+    launch_score(alive, c->rt.as<float>(), nullptr, sh, ps.dv, p->score_mode, c->partial.as<uint32_t>(), c->tn, st);
+    if ((rc = rec(c, 2))) return rc;
+    ENSURE(c, c->cnt, (size_t)sh.ld_local * 4);
+    ENSURE(c, c->amx_pairs, argmax_scratch_bytes(sh.ld_local));
+    launch_argmax(sh, c->partial.as<uint32_t>(), rows, c->sel_key.as<uint32_t>(), c->cnt.as<uint32_t>(), c->amx_pairs.as<uint64_t>(),
+                  &c->ctl.as<ControlBlock>()->amx_ticket, nullptr, st);  // (one pair per workgroup: the winner kernel reduces them)
+    npairs = (int)argmax_blocks(sh.ld_local);
+  } else if ((rc = rec(c, 2))) return rc;
+  if ((rc = rec(c, 3))) return rc;
+  arm_word(c, HW_WINNER);
+  launch_peel_winner(points_of(c), c->peel_claimed.as<uint8_t>(), c->rt.as<float>(), sh.ld_local, c->sel_key.as<uint32_t>(), ps.T_eff,
+                     c->amx_pairs.as<uint64_t>(), npairs, ps.dv.tau2, d_Rt, d_mask, words, &c->pinned[HW_WINNER], st);
+  if (ps.refine) {  // fp64 refit over mask_r, in refine_kernel's canonical order over the ORIGINAL indices (the mask stays the fp32 winner's)
+    ENSURE(c, c->refine_tmp, refine_scratch_bytes(ps.n));
+    launch_refine(points_of(c), d_mask, reinterpret_cast<const uint64_t*>(words->key2), c->refine_tmp.as<double>(), d_Rt, st);
+  }
+  if ((rc = rec(c, 4))) return rc;
+  // outputs: complete on return with the private stream, stream-ordered with a caller's (as sc_register_device)
+  if (ps.timing || c->stream == c->own_stream) HIPCHK(c, hipStreamSynchronize(st));
+  if ((rc = wait_word(c, HW_WINNER))) return rc;
+  HIPCHK(c, hipGetLastError());
+  const uint64_t key = c->pinned[HW_WINNER];
+  ps.peel_round++;
+  if (key) {
+    ps.peel_prev = (uint32_t)c->pinned[HW_WINNER_POS];
+    if (!read_alive) ps.peel_claimed += (uint32_t)(key >> 32);
+  }
+  if (stats && stats->size == sizeof(sc_stats)) {
+    fill_stats(c, stats);  // n, edges, tri_total, tri_kept, tri_scored: the frame's
+    stats->best_count = (uint32_t)(key >> 32);
+    stats->best_rank = key ? (uint32_t)(c->pinned[HW_WINNER_POS] >> 32) : 0u;
+    if (ps.timing) {  // the frame asked for SC_FLAG_TIMING: the round's brackets (us_stage: the claim + compact launch)
+      stats->us_stage = ev_us(c, 0, 1);
+      stats->us_score = ev_us(c, 1, 2);
+      stats->us_argmax = ev_us(c, 2, 3);
+      stats->us_mask = ev_us(c, 3, 4);
+      stats->us_compat = stats->us_triangles = stats->us_trikeys = stats->us_kabsch = 0.f;
+      stats->us_total = stats->us_stage + stats->us_score + stats->us_argmax + stats->us_mask;
+    }
+  }
+  return key ? SC_OK : SC_ENOHYP;
+}
+
+int sc_peel_device(sc_ctx* c, float* d_Rt, uint8_t* d_mask, sc_stats* stats) {
+  if (!c || !d_Rt || !d_mask) return SC_EINVAL;
+  return peel_round(c, d_Rt, d_mask, stats);
+}
+
+int sc_peel(sc_ctx* c, float R[9], float t[3], uint8_t* mask, sc_stats* stats) {
+  if (!c || !R || !t || !mask) return SC_EINVAL;
+  { const int brc = busy(c); if (brc) return brc; }
+  if (!c->pass.peelable) return peel_round(c, nullptr, nullptr, stats);  // (refused there, with the text)
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t n = (size_t)c->pass.n;
+  ENSURE(c, c->rt12, 64);
+  ENSURE(c, c->mask, n);
+  const int rc = peel_round(c, c->rt12.as<float>(), c->mask.as<uint8_t>(), stats);
+  if (rc != SC_OK && rc != SC_ENOHYP) return rc;
+  float Rt[12];
+  HIPCHK(c, hipMemcpyAsync(Rt, c->rt12.p, 48, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(mask, c->mask.p, n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  memcpy(R, Rt, 36);
+  memcpy(t, Rt + 9, 12);
+  return rc;
+}
+
+int sc_register_instances(sc_ctx* c, const float* src, const float* tgt, int64_t n, const sc_params* p, uint32_t max_instances,
+                          uint32_t min_score, float* Rt, uint32_t* score, int32_t* label, uint32_t* n_found, sc_stats* stats) {
+  if (c) peel_end(c);
+  if (!c || !src || !tgt || !Rt || !score || !label || !n_found || max_instances == 0 || max_instances > 65536 || n < 3 || n > (1 << 24))
+    return SC_EINVAL;
+  *n_found = 0;
+  int rc = check_params(p);
+  if (rc) return rc;
+  if (p->shard_world != 1) return SC_EINVAL;
+  { const int brc = busy(c); if (brc) return brc; }
+  HIPCHK(c, hipSetDevice(c->device));
+  c->cap_bytes = p->max_workspace ? p->max_workspace : (64ull << 30);
+  ENSURE(c, c->in_src, (size_t)n * 12);
+  ENSURE(c, c->in_tgt, (size_t)n * 12);
+  ENSURE(c, c->rt12, (size_t)max_instances * 48 + 16);
+  ENSURE(c, c->mask, (size_t)n);
+  ENSURE(c, c->peel_label, (size_t)n * 4);
+  hipStream_t st = c->stream;
+  HIPCHK(c, hipMemcpyAsync(c->in_src.p, src, (size_t)n * 12, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(c->in_tgt.p, tgt, (size_t)n * 12, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemsetAsync(c->peel_label.p, 0xFF, (size_t)n * 4, st));  // -1: claimed by no motion
+  sc_stats fs{}; fs.size = sizeof(sc_stats);
+  rc = sc_register_device(c, c->in_src.as<float>(), c->in_tgt.as<float>(), n, p, c->rt12.as<float>(), c->mask.as<uint8_t>(), &fs);
+  if (stats && stats->size == sizeof(sc_stats)) *stats = fs;
+  if (rc != SC_OK && rc != SC_ENOHYP) return rc;
+  uint32_t k = 0;
+  // motion 0 is the frame's winner; motion k the winner of round k.  The label is built on the device, one launch per accepted
+  // motion, and copied out once; a round's n mask bytes never travel
+  if (rc == SC_OK && fs.best_count >= min_score) {
+    launch_peel_label(c->mask.as<uint8_t>(), (int)n, 0, c->peel_label.as<int32_t>(), st);
+    score[0] = fs.best_count;
+    for (k = 1; k < max_instances; k++) {
+      sc_stats rs{}; rs.size = sizeof(sc_stats);
+      const int prc = peel_round(c, c->rt12.as<float>() + 12 * (size_t)k, c->mask.as<uint8_t>(), &rs);
+      if (prc == SC_ENOHYP) break;
+      if (prc != SC_OK) return prc;
+      if (rs.best_count < min_score) break;
+      launch_peel_label(c->mask.as<uint8_t>(), (int)n, (int32_t)k, c->peel_label.as<int32_t>(), st);
+      score[k] = rs.best_count;
+    }
+  }
+  if (k) HIPCHK(c, hipMemcpyAsync(Rt, c->rt12.p, (size_t)k * 48, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(label, c->peel_label.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  HIPCHK(c, hipGetLastError());
+  *n_found = k;
+  return rc;
+}
+
 // ---- stage hooks ------------------------------------------------------------------------------------
 
 int sc_compat_host(sc_ctx* c, const float* src, const float* tgt, int64_t n, const sc_params* p, float* S,
@@ -1893,7 +2085,7 @@ int sc_compat_host(sc_ctx* c, const float* src, const float* tgt, int64_t n, con
   int rc = check_params(p);
   if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
-  c->pass.have_hyp = false;
+  c->pass.have_hyp = false; peel_end(c);
   const bool dense = S != nullptr && !(p->flags & SC_FLAG_NO_DENSE_S);
   if (S && !dense) { c->last_error = "sc_compat_host: S requested together with SC_FLAG_NO_DENSE_S"; return SC_EINVAL; }
   if ((rc = host_to_planes(c, src, tgt, n, p))) return rc;
@@ -1917,7 +2109,7 @@ int sc_triangles_host(sc_ctx* c, const float* src, const float* tgt, int64_t n, 
   int rc = check_params(p);
   if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
-  c->pass.have_hyp = false;
+  c->pass.have_hyp = false; peel_end(c);
   if ((rc = host_to_planes(c, src, tgt, n, p))) return rc;
   if ((rc = run_compat(c, false))) return rc;  // the ranked list needs the bit rows only
   if ((rc = run_row_stats(c, may_prune(p)))) return rc;
@@ -1953,7 +2145,7 @@ int sc_kabsch_host(sc_ctx* c, const float* src, const float* tgt, int64_t n, con
   if (rc) return rc;
   for (size_t k = 0; k < (size_t)n_tri * 3; k++) if ((int64_t)tri[k] >= n) return SC_EINVAL;
   HIPCHK(c, hipSetDevice(c->device));
-  c->pass.have_hyp = false;
+  c->pass.have_hyp = false; peel_end(c);
   if ((rc = host_to_planes(c, src, tgt, n, p))) return rc;
   if (n_tri == 0) return check_flag(c);
   ENSURE(c, c->tri, (size_t)n_tri * 12);
@@ -1973,7 +2165,7 @@ int sc_score_host(sc_ctx* c, const float* src, const float* tgt, int64_t n, cons
   int rc = check_params(p);
   if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
-  c->pass.have_hyp = false;
+  c->pass.have_hyp = false; peel_end(c);
   if ((rc = host_to_planes(c, src, tgt, n, p))) return rc;
   Shard sh;
   sh.T_eff = n_hyp; sh.block = 0x40000000u; sh.rank = 0; sh.world = 1; sh.n_local = n_hyp;
@@ -2012,7 +2204,7 @@ int sc_mask_host(sc_ctx* c, const float* src, const float* tgt, int64_t n, const
   int rc = check_params(p);
   if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
-  c->pass.have_hyp = false;
+  c->pass.have_hyp = false; peel_end(c);
   if ((rc = host_to_planes(c, src, tgt, n, p))) return rc;
   ENSURE(c, c->rt12, 64);
   ENSURE(c, c->mask, (size_t)n);

@@ -572,6 +572,7 @@ enum HostWord : int {
   HW_MERGED_M = 7,      // ... together with the number of candidates merged (written before HW_MERGED_T)
   HW_WINNER = 8,        // the winner's key: the last word a call writes.  Armed by finalize_enqueue, written by the finalize kernel, polled by finalize_wait
   HW_WINNER_POS = 9,    // rank << 32 | position of the winner (all ones: the pair decodes to nothing).  Written before HW_WINNER, read behind it
+  HW_PEEL_ALIVE = 10,   // sc_peel, truncated score modes: correspondences a round's compaction kept.  Armed and polled by the round, written by the compaction kernel
   HW_CAND_CUT = 12,     // a cut candidate list mattered (SC_ERETRY).  Cleared by sc_shard_score_device, set by merge_check, read by finalize_wait
   HW_COORD_MAX = 13,    // max|tgt| << 32 | max|src|.  Armed by stage_inputs, written by the staging kernel (host-free: by the finalize kernel, every 64th
                         // call), read with acquire by read_coord_stats; sc_score_host polls it
@@ -597,5 +598,30 @@ void launch_refine(const Points& pts, const uint8_t* mask, const uint64_t* key2,
                    hipStream_t st);
 // mask of an explicit hypothesis (stage hook)
 void launch_mask(const Points& pts, const float* Rt12, float tau2, uint8_t* mask, hipStream_t st);
+
+// ---- rounds on a scored frame (sc_peel; sc_peel.hip) ---------------------------------------------------
+// The device words of a context's rounds (zeroed once; every kernel leaves the counters zero)
+struct PeelWords {
+  unsigned long long fin_word;  // peel_winner_kernel: workgroups finished << 32 | rank count so far (as ControlBlock::fin_word)
+  unsigned long long key2[2];   // the round's reduced winner pair (launch_refine reads [0])
+  uint32_t n_alive;             // peel_compact_kernel: correspondences it kept
+  uint32_t pad;
+};
+// claim + compact, ONE launch: claimed[m] |= (|R p_m + t - q_m|^2 < tau2) for the hypothesis at position prev_pos of RtSoA (the
+// winner of the round before; prev_pos == ~0u: nothing to fold in), then the correspondences still unclaimed go, order preserved,
+// into the six planes of `alive` (stride pts.ld).  fresh: `claimed` holds nothing yet (round 1): read as zeros, written whole.
+// lb: a look-back launch of peel_compact_tiles(n) tiles (8 bytes of descriptor each).  host_alive (optional, pinned): receives the
+// number kept (the host needs it to size the scoring launch where the scores do not tell it: the truncated score modes).
+uint32_t peel_compact_tiles(int n);
+void launch_peel_compact(const Points& pts, const float* RtSoA, uint32_t ld_local, uint32_t prev_pos, float tau2, bool fresh,
+                         uint8_t* claimed, float* alive, PeelWords* words, LbArgs lb, uint64_t* host_alive, hipStream_t st);
+// winner + mask of a round: finalize_kernel's work on ONE shard (the hypothesis at position g is RtSoA[.. + g]) with
+// mask[m] = !claimed[m] && inlier.  pairs / npairs: what launch_argmax left (key2 == nullptr form); npairs == 0: no hypothesis
+// (identity, zero mask).  host_out as launch_finalize's.
+void launch_peel_winner(const Points& pts, const uint8_t* claimed, const float* RtSoA, uint32_t ld_local, const uint32_t* sel_key,
+                        uint32_t T, const uint64_t* pairs, int npairs, float tau2, float* Rt12, uint8_t* mask, PeelWords* words,
+                        uint64_t* host_out, hipStream_t st);
+// label[m] = value where mask[m] (sc_register_instances: one launch per accepted motion)
+void launch_peel_label(const uint8_t* mask, int n, int32_t value, int32_t* label, hipStream_t st);
 
 }  // namespace sc

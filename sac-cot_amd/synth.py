@@ -109,6 +109,62 @@ def make_scene(n: int, rho: float, L: float, tau: float, seed: int) -> Scene:
     return Scene(p.astype(np.float32), q.astype(np.float32), R, t, inl)
 
 
+@dataclasses.dataclass
+class MotionScene:
+    src: np.ndarray       # (n,3) float32
+    tgt: np.ndarray       # (n,3) float32
+    label: np.ndarray     # (n,) int32 — the motion a correspondence follows, -1: an outlier
+    motions: list         # [(R (3,3) float64, t (3,) float64)] per motion
+
+
+def _pose(seed: int, L: float) -> tuple[np.ndarray, np.ndarray]:
+    """The rigid motion make_scene draws for `seed` (streams 2 and 3), the same bits."""
+    qn = gauss(seed, 2, np.arange(4, dtype=np.uint64))
+    qn = qn / np.sqrt((qn * qn).sum())
+    w, x, y, z = qn
+    R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                  [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                  [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]], dtype=np.float64)
+    t = (uniform01(seed, 3, np.arange(3, dtype=np.uint64)) - 0.5) * L
+    return R, t
+
+
+def make_scene_motions(n: int, rhos, L: float, tau: float, seed: int) -> MotionScene:
+    """A scene with len(rhos) rigid motions: make_scene(n, sum(rhos), L, tau, seed) — its source points, its outliers, its noise —
+    whose true correspondences are dealt to the motions in index order: motion k > 0 takes floor(rhos[k] n) of them from the END
+    (the last motion the very last ones), motion 0 keeps the rest.  Motion 0 is make_scene's own; motion k is the one make_scene
+    draws for seed + k.  Only the counter-hash streams: reproducible without numpy's RNG."""
+    rhos = [float(r) for r in rhos]
+    if not rhos:
+        raise ValueError("make_scene_motions needs at least one motion")
+    a = make_scene(n, sum(rhos), L, tau, seed)
+    idx = np.flatnonzero(a.inlier)
+    p = a.src.astype(np.float64)
+    qt = np.empty_like(p)
+    for r in range(3):
+        qt[:, r] = a.R_gt[r, 0] * p[:, 0] + a.R_gt[r, 1] * p[:, 1] + a.R_gt[r, 2] * p[:, 2] + a.t_gt[r]
+    noise = a.tgt.astype(np.float64) - qt
+    tgt = a.tgt.copy()
+    label = np.full(n, -1, dtype=np.int32)
+    label[idx] = 0
+    motions = [(a.R_gt, a.t_gt)]
+    end = idx.size
+    taken = []
+    for k in range(len(rhos) - 1, 0, -1):
+        cnt = min(int(np.floor(rhos[k] * n)), end)
+        taken.append((k, idx[end - cnt:end]))
+        end -= cnt
+    for k, own in sorted(taken):
+        R, t = _pose(seed + k, L)
+        motions.append((R, t))
+        q = np.empty((own.size, 3), dtype=np.float64)
+        for r in range(3):
+            q[:, r] = R[r, 0] * p[own, 0] + R[r, 1] * p[own, 1] + R[r, 2] * p[own, 2] + t[r]
+        tgt[own] = (q + noise[own]).astype(np.float32)
+        label[own] = k
+    return MotionScene(a.src, tgt, label, motions)
+
+
 def make_config_scene(name: str) -> tuple[Config, Scene]:
     cfg = CONFIGS[name]
     return cfg, make_scene(cfg.n, cfg.rho, cfg.L, cfg.tau, cfg.seed)
