@@ -115,7 +115,15 @@ extern "C" {
 
 typedef struct sc_ctx sc_ctx;
 
-/* All tunables of the path (SURVEY §8a `sc_params`).  POD; `size` must be sizeof(sc_params). */
+/* All tunables of the path (SURVEY §8a `sc_params`).  POD; `size` must be sizeof(sc_params).
+ * Numeric domain: any finite coordinate, any positive finite sigma / tau, min_len >= 0, 0 < t_cmp < 1 is accepted and
+ * computed as the CPU restatement computes it, bit for bit.  The units of length are free within limits: multiplying the coordinates
+ * and sigma, tau, min_len by 2^k leaves the graph, the ranked list, R, the scores, the mask and the winner unchanged and multiplies t by
+ * 2^k exactly, as long as the SQUARED lengths the path compares stay normal fp32 numbers — for pair lengths, tau and min_len between
+ * ~1e-18 and ~4e18 and sigma above ~1e-15 they do (a scene of extent 1 with sigma = tau = min_len = 0.05: -46 <= k <= 62; adjacency and inlier counts alone
+ * from k = -58; the Kabsch stage normalises its triangle and holds from -80 to 120).  Outside nothing fails: a pair whose squared
+ * length overflows is no edge, so the graph thins out and in the end the call returns SC_ENOHYP; squared lengths that underflow lose
+ * bits or vanish, and results drift from the scale-covariant ones. */
 typedef struct sc_params {
   uint32_t size;            /* = sizeof(sc_params); versioning                                          */
   float    sigma;           /* rigidity scale: s_ij = exp(-d^2 / (2 sigma^2)), d = | |pi-pj| - |qi-qj| | */

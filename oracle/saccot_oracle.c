@@ -307,6 +307,20 @@ void so_kabsch3_one(const float P[9], const float Q[9], float Rt[12]) {
   }
   for (int m = 0; m < 3; m++)
     for (int c = 0; c < 3; c++) { a[m][c] = P[3 * m + c] - pc[c]; b[m][c] = Q[3 * m + c] - qc[c]; }
+  /* The unit of length leaves here: each of the two centred triangles is multiplied by the power of
+   * two 2^(127 - E), E the largest biased exponent among its nine entries (E = 0 for zeros and subnormals; the factor stops
+   * at 2^-126, so E = 254 and the non-finite E = 255 take that).  Multiplying by a power of two is exact, so H, alpha, beta,
+   * gamma below are the unnormalised values times a power of two — fourth powers of the triangle's size no longer over- or
+   * underflow — and R has the same bits wherever they did not.  t below is made from the unscaled centroids. */
+  float* const side[2] = {&a[0][0], &b[0][0]};
+  for (int s = 0; s < 2; s++) {
+    uint32_t E = 0;
+    for (int k = 0; k < 9; k++) { uint32_t e = (as_u32(side[s][k]) >> 23) & 0xFFu; if (e > E) E = e; }
+    int sh = 127 - (int)E;
+    if (sh < -126) sh = -126;
+    const float f = ldexpf(1.0f, sh);
+    for (int k = 0; k < 9; k++) side[s][k] *= f;
+  }
   /* columns of H: B[col][row] = H[row][col] */
   float B[3][3], V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
   for (int r = 0; r < 3; r++)
@@ -354,6 +368,11 @@ void so_kabsch3_one(const float P[9], const float Q[9], float Rt[12]) {
       Rt[3 * r + c] = fmaf(v3[r], u3[c], fmaf(v2[r], u2[c], v1[r] * u1[c]));
   for (int r = 0; r < 3; r++)
     Rt[9 + r] = qc[r] - fmaf(Rt[3 * r + 2], pc[2], fmaf(Rt[3 * r + 1], pc[1], Rt[3 * r] * pc[0]));
+  /* rank 1 exactly (collinear or coincident points): the second squared singular value, of entries normalised to [1, 2), went
+   * below 2^-100 — far under the ~2^-50 that rounding leaves of a rank-1 H.  No rotation, no hypothesis: all twelve NaN (what the
+   * unnormalised code got from 0 / 0 once that column had underflowed).  A NaN norm takes the same way. */
+  if (!(nrm[i2] >= 0x1p-100f))
+    for (int c = 0; c < 12; c++) Rt[c] = NAN;
 }
 
 void so_kabsch3(const float* src, const float* tgt, int64_t n, const uint32_t* tri, uint32_t T, float* Rt,

@@ -111,6 +111,26 @@ __device__ __forceinline__ void kabsch3(const float P[9], const float Q[9], floa
   for (int m = 0; m < 3; m++)
 #pragma unroll
     for (int c = 0; c < 3; c++) { a[m][c] = P[3 * m + c] - pc[c]; b[m][c] = Q[3 * m + c] - qc[c]; }
+  // Unit of length out: a and b are each multiplied by the power of two that brings their largest entry into [1, 2)
+  // (largest exponent field E -> factor 2^(127 - E), held at 2^-126 from E = 254 on).  Exact, so H and every Jacobi
+  // quantity are the unnormalised ones times a power of two and R keeps its bits wherever those neither over- nor
+  // underflowed; alpha, beta, gamma are fourth powers of the triangle's size and did both.  t uses the unscaled centroids.
+  {
+    int ea = 0, eb = 0;
+#pragma unroll
+    for (int m = 0; m < 3; m++)
+#pragma unroll
+      for (int c = 0; c < 3; c++) {
+        ea = max(ea, __float_as_int(a[m][c]) & 0x7F800000);
+        eb = max(eb, __float_as_int(b[m][c]) & 0x7F800000);
+      }
+    const float sa = __int_as_float(max(0x7F000000 - ea, 0x00800000));
+    const float sb = __int_as_float(max(0x7F000000 - eb, 0x00800000));
+#pragma unroll
+    for (int m = 0; m < 3; m++)
+#pragma unroll
+      for (int c = 0; c < 3; c++) { a[m][c] *= sa; b[m][c] *= sb; }
+  }
   float B[3][3], V[3][3] = {{1.f, 0.f, 0.f}, {0.f, 1.f, 0.f}, {0.f, 0.f, 1.f}};
 #pragma unroll
   for (int r = 0; r < 3; r++)
@@ -162,7 +182,8 @@ __device__ __forceinline__ void kabsch3(const float P[9], const float Q[9], floa
     v1[r] = (i1 == 0) ? V[0][r] : (i1 == 1 ? V[1][r] : V[2][r]);
     v2[r] = (i2 == 0) ? V[0][r] : (i2 == 1 ? V[1][r] : V[2][r]);
   }
-  float s1 = sqrt_rn(dot3(b1, b1)), s2 = sqrt_rn(dot3(b2, b2));
+  const float m2 = dot3(b2, b2);
+  float s1 = sqrt_rn(dot3(b1, b1)), s2 = sqrt_rn(m2);
   float u1[3], u2[3], u3[3], v3[3];
 #pragma unroll
   for (int r = 0; r < 3; r++) { u1[r] = div_rn(b1[r], s1); u2[r] = div_rn(b2[r], s2); }
@@ -175,6 +196,13 @@ __device__ __forceinline__ void kabsch3(const float P[9], const float Q[9], floa
 #pragma unroll
   for (int r = 0; r < 3; r++)
     Rt[9 + r] = qc[r] - fma_(Rt[3 * r + 2], pc[2], fma_(Rt[3 * r + 1], pc[1], Rt[3 * r] * pc[0]));
+  // A second singular value that the sweeps took below 2^-50 of the normalised entries (collinear or coincident points: H of rank
+  // 1 exactly) defines no rotation: no hypothesis.  Unnormalised, that column underflowed to 0 and 0 / 0 said the same; what is left
+  // of it down there is subnormal arithmetic, which must decide nothing.  (Rounding alone leaves a rank-1 H about 2^-25 here.)
+  if (!(m2 >= 0x1p-100f)) {
+#pragma unroll
+    for (int c = 0; c < 12; c++) Rt[c] = __builtin_nanf("");
+  }
 }
 
 __device__ __forceinline__ bool finite12(const float* M) {

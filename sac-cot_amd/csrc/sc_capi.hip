@@ -284,6 +284,15 @@ Derived derive(const sc_params* p) {
   return d;
 }
 
+// The smallest key a triangle can have in weight ranking: every edge has s >= t_cmp up to rounding (0.1 % slack), so w >= ~3 t_cmp — what
+// the select's a-priori window and the pruning samples' floors rest on.  NOT when -1 / (2 sigma^2) overflowed fp32 (sigma below 2^-64.5 =
+// 3.8e-20): (d * d) * -inf is -inf or NaN, sc_expf clamps both to its floor, every weight is e^-87 and nothing bounds the keys from below
+// (tests/test_gpu_range.py: the select then returned keys of its window, [2, 3], that no triangle has).
+float key_floor(const sc_params* p) {
+  const float nis = (float)(-1.0 / (2.0 * (double)p->sigma * (double)p->sigma));  // derive()'s neg_inv2sig2
+  return std::isfinite(nis) ? 3.0f * p->t_cmp * 0.999f : 0.0f;
+}
+
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
 Points points_of(const sc_ctx* c) { return Points{c->planes.as<float>(), c->pass.n, c->pass.ld}; }
@@ -510,7 +519,7 @@ bool may_prune(const sc_params* p) { return p->rank_mode == SC_RANK_WEIGHT && !(
 // will be an estimate (the same conditions as sample_plan's in run_edges, minus what only the edge count decides) and the
 // bit rows are short enough for the kernel
 bool edge_build_ok(const sc_ctx* c, const sc_params* p, int64_t n, bool may_estimate) {
-  const bool window_known = p->rank_mode == SC_RANK_WEIGHT && 3.0f * p->t_cmp * 0.999f >= 2.0f;
+  const bool window_known = p->rank_mode == SC_RANK_WEIGHT && key_floor(p) >= 2.0f;
   return may_estimate && !c->est_failed && window_known && may_prune(p) && !c->tn.no_events && !c->tn.no_estimate &&
          c->tn.sample_mode == 0 && !c->tn.no_edge_build && !c->tn.rows_unfused && edge_build_fits((int)n) &&  // (stage C may be dealt over ranks: shard_world)
          p->max_triangles != 0;
@@ -640,7 +649,7 @@ int run_edges(sc_ctx* c, const sc_params* p, uint32_t* hist, uint32_t part, uint
     // the smallest possible weight is ~3 t_cmp (every edge has s >= t_cmp up to rounding); 0.1 % slack
     // An ESTIMATED bound where the call can be repeated should the select find it too high (sc_tri.hip 3c): the common
     // form only — event list, a-priori select window (the check rides the window's first round), the whole sample here
-    const bool window_known = p->rank_mode == SC_RANK_WEIGHT && 3.0f * p->t_cmp * 0.999f >= 2.0f;
+    const bool window_known = p->rank_mode == SC_RANK_WEIGHT && key_floor(p) >= 2.0f;
     // (sharded, SC_FLAG_EST_BOUND: every rank takes the WHOLE sample — it is cheaper than the latency of the all-reduce that
     // would sum the ranks' shares — and the merge of the candidates verifies the bound: sc_shard_score_device)
     const bool est_local = c->pass.mode.may_estimate && !c->est_failed && hist == nullptr && parts == 1 && !c->pass.sharded_ab;
@@ -664,7 +673,7 @@ int run_edges(sc_ctx* c, const sc_params* p, uint32_t* hist, uint32_t part, uint
         c->pass.ref_cand_n = sample_candidate_blocks(E, c->tn);
       }
       launch_sample_estimate(g, build ? nullptr : c->ebi.as<uint32_t>(), build ? nullptr : c->ebj.as<uint32_t>(), c->ei.as<uint32_t>(),
-                             c->ej.as<uint32_t>(), c->es.as<float>(), E, 3.0f * p->t_cmp * 0.999f, c->pass.plan.rate, ctl->prune_hist, c->tn,
+                             c->ej.as<uint32_t>(), c->es.as<float>(), E, key_floor(p), c->pass.plan.rate, ctl->prune_hist, c->tn,
                              st, E_dev, c->ebase.as<uint32_t>(), cand, cand ? ctl->ref_slot : nullptr);
     } else {
       // SC_FLAG_EST_BOUND on the phase API where the plan is NOT an estimate (select window unknown: t_cmp below ~0.668; sc_debug's
@@ -673,7 +682,7 @@ int run_edges(sc_ctx* c, const sc_params* p, uint32_t* hist, uint32_t part, uint
       // bounds, cut the strong list differently, and the merged top-T could miss triangles)
       const bool whole = est_shard;
       launch_sample_hist(g, c->ebi.as<uint32_t>(), c->ebj.as<uint32_t>(), c->ei.as<uint32_t>(), c->ej.as<uint32_t>(),
-                         c->es.as<float>(), E, p->max_triangles, 3.0f * p->t_cmp * 0.999f, whole ? 0u : part, whole ? 1u : parts,
+                         c->es.as<float>(), E, p->max_triangles, key_floor(p), whole ? 0u : part, whole ? 1u : parts,
                          ctl->prune_hist, ctl->es_hist, c->tn, st, E_dev, spec ? c->E_last : 0);
     }
     if (hist) launch_hist_reduce(ctl->prune_hist, hist, st);  // the exchanged form: one 256-bin histogram
@@ -730,7 +739,7 @@ int run_select(sc_ctx* c, const sc_params* p, const uint32_t* hist, bool want_li
     // whole strong matrix, so every rank computes the same cut: the pruning kernel lists EVERY strong edge, two small
     // launches make the cut, and the counting pass skips the edges of the other ranks.
     launch_prune_bits(g, hist ? hist : ctl->prune_hist, hist == nullptr, c->ei.as<uint32_t>(), c->ej.as<uint32_t>(), c->es.as<float>(), E,
-                      c->pass.est_active ? c->pass.plan.hist_want : (uint64_t)p->max_triangles, 3.0f * p->t_cmp * 0.999f, c->bits2.as<uint64_t>(), &ctl->smin, &ctl->klb, sl,
+                      c->pass.est_active ? c->pass.plan.hist_want : (uint64_t)p->max_triangles, key_floor(p), c->bits2.as<uint64_t>(), &ctl->smin, &ctl->klb, sl,
                       c->tcnt.as<uint32_t>(), recut ? nullptr : own_range_of(c), st, E_dev, c->pass.est_active,
                       spec && c->pass.build && !c->pass.sharded_ab);  // (the scan of such a call is trimmed to the real edges: below)
     if (recut) {
@@ -779,7 +788,7 @@ int run_select(sc_ctx* c, const sc_params* p, const uint32_t* hist, bool want_li
   // calls (it takes everything else from device memory).  Only in the common form — events, a-priori select window —
   // and not when every stage is bracketed by events; re-run below if the count outgrew the arrays or a region overflowed.
   SelectState* sel = &c->ctl.as<ControlBlock>()->sel;
-  const bool window_known = p->rank_mode == SC_RANK_WEIGHT && 3.0f * p->t_cmp * 0.999f >= 2.0f;
+  const bool window_known = p->rank_mode == SC_RANK_WEIGHT && key_floor(p) >= 2.0f;
   uint64_t spec_cap = 0;
   if (use_events && window_known && !c->pass.timing) {
     spec_cap = c->wkey.cap / 4 < c->kcol.cap / 8 ? c->wkey.cap / 4 : c->kcol.cap / 8;
@@ -1499,7 +1508,7 @@ int sc_shard_score_device(sc_ctx* c, const void* d_cand_all, uint64_t* d_key, sc
   // Merge: the same exact select + (i,j,k)-order compaction as on one GPU, over the concatenated candidate keys.
   ControlBlock* ctl = c->ctl.as<ControlBlock>();
   SelectState* sel = &ctl->sel;
-  const bool window_known = p->rank_mode == SC_RANK_WEIGHT && 3.0f * p->t_cmp * 0.999f >= 2.0f;
+  const bool window_known = p->rank_mode == SC_RANK_WEIGHT && key_floor(p) >= 2.0f;
   const KeyView view = cand_view(d_cand_all, blob_bytes, G, cap);
   const size_t nb = compact_blocks(view.M);
   ENSURE(c, c->blk_gt, nb * 4);
@@ -1695,7 +1704,7 @@ bool fast_plan(const sc_ctx* c, int64_t n, const sc_params* p, PassMode* mode) {
   if (!c->fast_ok || c->tn.no_fast || c->tn.no_events || n != c->last_n) return false;
   if (p->flags & (SC_FLAG_TIMING | SC_FLAG_EXACT_TOTAL | SC_FLAG_NO_PRUNE)) return false;
   if (!same_shape(p, &c->last_p)) return false;
-  if (!(p->rank_mode == SC_RANK_WEIGHT && 3.0f * p->t_cmp * 0.999f >= 2.0f)) return false;  // the a-priori select window
+  if (!(p->rank_mode == SC_RANK_WEIGHT && key_floor(p) >= 2.0f)) return false;  // the a-priori select window
   const uint64_t ecap = edge_capacity(c, edge_build_ok(c, p, n, true));  // (every entry point that comes here may estimate; the fused edge kernel writes no per-edge bases)
   const uint64_t kcap = c->wkey.cap / 4 < c->kcol.cap / 8 ? c->wkey.cap / 4 : c->kcol.cap / 8;
   // the last call's counts plus half, and the largest counts of the shape's recent calls plus a quarter (sc_ctx::E_hi)
