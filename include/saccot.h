@@ -34,7 +34,7 @@ extern "C" {
 #endif
 
 #define SC_VERSION_MAJOR 0
-#define SC_VERSION_MINOR 9   /* 0.9: sc_peel / sc_peel_device / sc_register_instances (further rigid motions from a scored frame).  0.8: sc_debug_info grew cumulative counters of how a context's frames ran (saccot_debug.h); every entry refuses a context with an outstanding call; a host-free enqueue that does not fit the workspace cap runs the waited way.  0.7: sc_finalize_gathered_device_async (+ sc_wait), sc_hypothesize_device with SC_FLAG_EST_BOUND host-free on a repeated shape.  0.6: SC_FLAG_EST_BOUND also on sc_hypothesize_device (SC_EBOUND from the finalize call); SC_FLAG_SHARD_AB (sc_register_multi replicates stages A and B on small graphs unless told otherwise); sc_debug / sc_debug_info grew (the Gram filter's frame and cut: saccot_debug.h).  0.5: sc_register_device_async / sc_wait (host-free enqueue), SC_FLAG_EST_BOUND / SC_EBOUND (sharded stage B pruned by an estimated bound), sc_stats.bytes_moved, the debug hooks moved to
+#define SC_VERSION_MINOR 10  /* 0.10: sc_match / sc_match_device / sc_register_features (descriptor matching on the GPU, feeding the registration).  0.9: sc_peel / sc_peel_device / sc_register_instances (further rigid motions from a scored frame).  0.8: sc_debug_info grew cumulative counters of how a context's frames ran (saccot_debug.h); every entry refuses a context with an outstanding call; a host-free enqueue that does not fit the workspace cap runs the waited way.  0.7: sc_finalize_gathered_device_async (+ sc_wait), sc_hypothesize_device with SC_FLAG_EST_BOUND host-free on a repeated shape.  0.6: SC_FLAG_EST_BOUND also on sc_hypothesize_device (SC_EBOUND from the finalize call); SC_FLAG_SHARD_AB (sc_register_multi replicates stages A and B on small graphs unless told otherwise); sc_debug / sc_debug_info grew (the Gram filter's frame and cut: saccot_debug.h).  0.5: sc_register_device_async / sc_wait (host-free enqueue), SC_FLAG_EST_BOUND / SC_EBOUND (sharded stage B pruned by an estimated bound), sc_stats.bytes_moved, the debug hooks moved to
                                 saccot_debug.h; 0.4: sc_debug_last / sc_debug_info, sc_debug.filter_blind; 0.3: sc_set_debug (no environment variables), SC_FLAG_NO_DENSE_S, sc_shard_* (stages A and B sharded); 0.2: SC_FLAG_TIMING_HOT,
                                 SC_STREAM_DEFAULT, sc_hypothesize_begin/end_device, sc_finalize_gathered_device */
 
@@ -247,7 +247,7 @@ int sc_wait(sc_ctx* ctx, sc_stats* stats);
  *      SC_FLAG_TIMING: us_stage = the claim + compact launch, us_score, us_argmax, us_mask (with the refit), us_total.
  * A round's results are a function of the frame's input and r only — not of how the frame was enqueued (waited,
  * host-free, repeated), of which C2 kernel scored it, or of the context's history.
- * What ends a frame: any other computing entry on the context (sc_register*, sc_hypothesize*, sc_finalize*, sc_shard_*,
+ * What ends a frame: any other computing entry on the context (sc_register*, sc_match*, sc_hypothesize*, sc_finalize*, sc_shard_*,
  * every sc_*_host hook), or a frame call that did not return SC_OK.  sc_peel* without a frame: SC_EINVAL (sc_last_error
  * says so); with a call outstanding: SC_EINVAL as everywhere.  d_src / d_tgt need not stay valid after the frame call:
  * rounds read the context's staged copy.  Rounds wait for their winner (there is no async form).  Sharded and multi-GPU
@@ -269,6 +269,54 @@ int sc_peel(sc_ctx* ctx, float R[9], float t[3], uint8_t* mask, sc_stats* stats)
 int sc_register_instances(sc_ctx* ctx, const float* src, const float* tgt, int64_t n, const sc_params* params,
                           uint32_t max_instances, uint32_t min_score, float* Rt, uint32_t* score, int32_t* label,
                           uint32_t* n_found, sc_stats* stats);
+
+/* ---- descriptor matching: two sets of keypoint descriptors in, putative correspondences out --------------
+ * What stands in front of sc_register in a caller's frame: source keypoint i has a descriptor fsrc[i] (FPFH 33-D, FCGF 32-D,
+ * SHOT 352-D ...), target keypoint j has ftgt[j]; a correspondence is (i, the j whose descriptor is nearest).  Brute force, exact,
+ * and a function of the input alone, bit for bit:
+ *   fsrc: ns x dim, ftgt: nt x dim, fp32, row-major, finite; 1 <= dim <= 1024, 1 <= ns, nt <= 2^24.
+ *   distance of row i and row j, fp32, every operation rounded to nearest, no fused multiply-add, c ascending:
+ *       acc = 0;  for c in 0 .. dim-1:  d = a[c] - b[c];  acc = acc + d * d
+ *   (symmetric bit for bit; a sum that overflows to +inf is legal and ordered like any other value).
+ *   The candidates of source row i are ordered by the u64 key (bits(acc) << 32) | j, ascending: nearest first, ties to the lower
+ *   index.  The reverse order, for target row j, is (bits(acc) << 32) | i.
+ *   knn = k (1 .. 4): row i yields its k smallest keys in order (fewer if nt < k).
+ *   SC_MATCH_MUTUAL (k = 1 only): (i, j) is kept iff j is i's minimum and i is j's minimum under the reverse order.
+ *   ratio in (0, 1) (k = 1 only; 0 = off): (i, j) is kept iff acc1 < r2 * acc2, r2 = (float)((double)ratio * ratio), one fp32
+ *   multiply, acc2 the distance of i's second-smallest key; kept when nt == 1.  Both tests may be combined.
+ * Output: corr (n x 2 int32: i, j) in ascending (i, rank) order, d2 (n x fp32: acc), and the count n <= ns * knn.
+ * A NaN or infinity among the descriptors is SC_EINVAL; it is found on the device by the pass that reads it.
+ * Workspace (the slices' partial lists, the column minima) belongs to the context like every other buffer: allocated by the first
+ * match, grown on demand, counted in workspace_bytes and held against the cap of the last sc_params the context saw (64 GiB before
+ * any); a context that never matches allocates and runs nothing new.  sc_match* ends the frame a context may hold (sc_peel). */
+#define SC_MATCH_MUTUAL 1u
+typedef struct sc_match_params {
+  uint32_t size;         /* = sizeof(sc_match_params)                                                  */
+  uint32_t dim;          /* D: floats per descriptor, 1 .. 1024                                         */
+  uint32_t knn;          /* k: 1 .. 4                                                                   */
+  uint32_t flags;        /* SC_MATCH_*                                                                  */
+  float    ratio;        /* 0 = off, else in (0, 1): the ratio test (k = 1)                             */
+  uint32_t reserved[3];  /* must be 0                                                                   */
+} sc_match_params;
+int sc_match_default_params(sc_match_params* mp);   /* size set, dim 0 (the caller sets it), knn 1, no flags, ratio 0 */
+/* Every buffer in HBM.  d_corr: ns * knn x 2 int32, d_d2: ns * knn floats, d_count: 2 x u32.  Enqueues on the context's stream and
+ * returns without waiting: d_count[0] = n and the first n entries of d_corr / d_d2 are valid in stream order; d_count[1] = 1 if a
+ * non-finite descriptor was read (then n = 0 and d_corr / d_d2 are unspecified).  Parameter errors return SC_EINVAL at once. */
+int sc_match_device(sc_ctx* ctx, const float* d_fsrc, int64_t ns, const float* d_ftgt, int64_t nt, const sc_match_params* mp,
+                    int32_t* d_corr, float* d_d2, uint32_t* d_count);
+/* The same with host arrays (corr, d2: room for ns * knn entries; the first *n are written); waits.  A non-finite descriptor:
+ * SC_EINVAL, *n = 0. */
+int sc_match(sc_ctx* ctx, const float* fsrc, int64_t ns, const float* ftgt, int64_t nt, const sc_match_params* mp,
+             int32_t* corr, float* d2, uint32_t* n);
+/* Descriptors in, (R, t), correspondences and mask out (host arrays): sc_match on the descriptors, then sc_register on
+ * (src_pts[corr[m][0]], tgt_pts[corr[m][1]]), m < n — the matched points are gathered on the device and nothing but the count
+ * crosses the host in between (one wait).  src_pts: ns points, tgt_pts: nt points, params->layout; mask: room for ns * knn bytes,
+ * mask[m] belongs to corr[m].  corr, d2, *n are valid whenever the match itself succeeded (every status but SC_EINVAL / SC_ENOMEM /
+ * SC_EHIP); n < 3: SC_ENOHYP with R = I, t = 0 and the mask untouched; otherwise status, R, t, mask and stats are exactly those of
+ * sc_register(ctx, gathered src, gathered tgt, n, params, ...), and the call leaves that frame: sc_peel may follow. */
+int sc_register_features(sc_ctx* ctx, const float* src_pts, const float* fsrc, int64_t ns, const float* tgt_pts,
+                         const float* ftgt, int64_t nt, const sc_match_params* mp, const sc_params* params, float R[9],
+                         float t[3], int32_t* corr, float* d2, uint32_t* n, uint8_t* mask, sc_stats* stats);
 
 /* ---- two-phase form for one-process-per-GPU sharding --------------------------------
  * Phase 1: A and B replicated, C1+C2 on this rank's blocks of the top-T list; writes this rank's winner key

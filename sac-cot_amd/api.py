@@ -24,6 +24,7 @@ SC_RANK_WEIGHT, SC_RANK_DEGREE = 0, 1
 SC_SCORE_COUNT, SC_SCORE_MSE, SC_SCORE_MAE = 0, 1, 2
 SC_FLAG_TIMING, SC_FLAG_EXACT_TOTAL, SC_FLAG_NO_PRUNE, SC_FLAG_REFINE, SC_FLAG_TIMING_HOT, SC_FLAG_NO_DENSE_S = 1, 2, 4, 8, 16, 32
 SC_FLAG_TIMING_ONE = 64
+SC_MATCH_MUTUAL = 1  # sc_match_params.flags: keep (i, j) only if each is the other's nearest (knn == 1)
 
 
 def SC_TIMING_STAGE(k: int) -> int:
@@ -37,6 +38,7 @@ SC_HIST_WORDS = 256  # u32 words of the pruning-sample histogram (sc_hypothesize
 EXPORTS = ["sc_version", "sc_strerror", "sc_default_params", "sc_create", "sc_destroy", "sc_set_stream",
            "sc_last_error", "sc_set_debug", "sc_debug_last", "sc_register", "sc_register_device", "sc_register_device_async", "sc_wait",
            "sc_peel", "sc_peel_device", "sc_register_instances",
+           "sc_match_default_params", "sc_match_device", "sc_match", "sc_register_features",
            "sc_hypothesize_device", "sc_finalize_device",
            "sc_hypothesize_begin_device", "sc_hypothesize_end_device", "sc_finalize_gathered_device", "sc_finalize_gathered_device_async",
            "sc_shard_plan_query", "sc_shard_compat_device", "sc_shard_edges_device", "sc_shard_select_device",
@@ -64,6 +66,12 @@ class ScStats(C.Structure):
 
     def as_dict(self) -> dict:
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "size"}
+
+
+class ScMatchParams(C.Structure):
+    """Mirror of `sc_match_params` (include/saccot.h): descriptor length, neighbours per row (1 .. 4), SC_MATCH_* flags, ratio test."""
+    _fields_ = [("size", C.c_uint32), ("dim", C.c_uint32), ("knn", C.c_uint32), ("flags", C.c_uint32), ("ratio", C.c_float),
+                ("reserved", C.c_uint32 * 3)]
 
 
 class ScShardPlan(C.Structure):
@@ -154,6 +162,11 @@ def load_library() -> C.CDLL:
     L.sc_peel_device.argtypes = [vp, vp, vp, sp]
     L.sc_register_instances.argtypes = [vp, f32p, f32p, C.c_int64, pp, C.c_uint32, C.c_uint32, f32p, u32p, C.POINTER(C.c_int32),
                                         u32p, sp]
+    mp, i32p = C.POINTER(ScMatchParams), C.POINTER(C.c_int32)
+    L.sc_match_default_params.argtypes = [mp]
+    L.sc_match_device.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, mp, vp, vp, vp]
+    L.sc_match.argtypes = [vp, f32p, C.c_int64, f32p, C.c_int64, mp, i32p, f32p, u32p]
+    L.sc_register_features.argtypes = [vp, f32p, f32p, C.c_int64, f32p, f32p, C.c_int64, mp, pp, f32p, f32p, i32p, f32p, u32p, u8p, sp]
     L.sc_hypothesize_device.argtypes = [vp, vp, vp, C.c_int64, pp, vp, sp]
     L.sc_finalize_device.argtypes = [vp, vp, vp, vp, sp]
     L.sc_hypothesize_begin_device.argtypes = [vp, vp, vp, C.c_int64, pp, vp, sp]
@@ -184,6 +197,11 @@ def make_params(sigma=0.1, t_cmp=0.9, tau=0.1, min_len=0.1, max_triangles=50000,
                 score_mode=0, shard_cand_level=0) -> ScParams:
     return ScParams(C.sizeof(ScParams), sigma, t_cmp, tau, min_len, max_triangles, rank_mode, layout, shard_rank,
                     shard_world, shard_block, flags, max_workspace, score_mode, shard_cand_level)
+
+
+def make_match_params(dim: int, knn: int = 1, mutual: bool = False, ratio: float = 0.0, flags: int = 0) -> ScMatchParams:
+    """sc_match_params for descriptors of length `dim`: knn 1 .. 4; mutual / ratio (in (0, 1), 0 = off) with knn == 1 only."""
+    return ScMatchParams(C.sizeof(ScMatchParams), dim, knn, flags | (SC_MATCH_MUTUAL if mutual else 0), ratio)
 
 
 def shard_plan(params: ScParams, n: int) -> ScShardPlan:
@@ -339,6 +357,51 @@ class Registrar:
         self._frame_n = n
         k = int(found.value)
         return dict(status=rc, Rt=Rt[:k].copy(), score=score[:k].copy(), label=label, stats=st.as_dict())
+
+    # ---- descriptor matching (include/saccot.h, sc_match) ------------------------------------------------------
+    def match(self, fsrc, ftgt, mparams: ScMatchParams | None = None, **kw):
+        """sc_match: (ns, D) and (nt, D) descriptors -> dict(n, corr (n, 2) int32: source row, target row, in ascending (row, rank)
+        order; d2 (n,) float32: the canonical squared distances).  kw: knn, mutual, ratio (make_match_params)."""
+        fsrc, ftgt = _f32c(fsrc), _f32c(ftgt)
+        if fsrc.ndim != 2 or ftgt.ndim != 2 or fsrc.shape[1] != ftgt.shape[1]:
+            raise ValueError("match: fsrc (ns, D) and ftgt (nt, D) with one D")
+        m = mparams or make_match_params(fsrc.shape[1], **kw)
+        cap = max(fsrc.shape[0] * max(int(m.knn), 1), 1)
+        corr = np.zeros((cap, 2), np.int32); d2 = np.zeros(cap, np.float32); n = C.c_uint32(0)
+        self._check(self._lib.sc_match(self._h, _p(fsrc, C.c_float), fsrc.shape[0], _p(ftgt, C.c_float), ftgt.shape[0], C.byref(m),
+                                       _p(corr, C.c_int32), _p(d2, C.c_float), C.byref(n)))
+        k = int(n.value)
+        return dict(n=k, corr=corr[:k].copy(), d2=d2[:k].copy())
+
+    def match_device(self, d_fsrc: int, ns: int, d_ftgt: int, nt: int, mparams: ScMatchParams, d_corr: int, d_d2: int, d_count: int):
+        """sc_match_device: everything in HBM (d_corr: ns * knn x 2 int32, d_d2: ns * knn float32, d_count: 2 x uint32 — the
+        count, and 1 if a non-finite descriptor was read); enqueues on the context's stream and returns without waiting."""
+        self._check(self._lib.sc_match_device(self._h, d_fsrc, ns, d_ftgt, nt, C.byref(mparams), d_corr, d_d2, d_count))
+
+    def register_features(self, src_pts, fsrc, tgt_pts, ftgt, mparams: ScMatchParams | None = None, params: ScParams | None = None,
+                          knn: int = 1, mutual: bool = False, ratio: float = 0.0, **kw):
+        """sc_register_features: keypoints and their descriptors in -> dict(status, R, t, n, corr (n, 2), d2 (n,), mask (n,), stats):
+        sc_match on the descriptors, then sc_register on the matched points, gathered on the device.  Fewer than 3 matches:
+        SC_ENOHYP, R = I.  Leaves a frame of n correspondences: peel() may follow."""
+        p = params or make_params(**kw)
+        src_pts, tgt_pts, fsrc, ftgt = _f32c(src_pts), _f32c(tgt_pts), _f32c(fsrc), _f32c(ftgt)
+        m = mparams or make_match_params(fsrc.shape[1], knn, mutual, ratio)
+        ns, nt = fsrc.shape[0], ftgt.shape[0]
+        if (src_pts.shape[0] if p.layout == SC_AOS else src_pts.shape[1]) != ns or \
+                (tgt_pts.shape[0] if p.layout == SC_AOS else tgt_pts.shape[1]) != nt or fsrc.shape[1] != ftgt.shape[1]:
+            raise ValueError("register_features: one descriptor row per point, one D")
+        cap = max(ns * max(int(m.knn), 1), 1)
+        corr = np.zeros((cap, 2), np.int32); d2 = np.zeros(cap, np.float32); n = C.c_uint32(0)
+        R = np.zeros(9, np.float32); t = np.zeros(3, np.float32); mask = np.zeros(cap, np.uint8)
+        st = ScStats(C.sizeof(ScStats))
+        rc = self._check(self._lib.sc_register_features(self._h, _p(src_pts, C.c_float), _p(fsrc, C.c_float), ns, _p(tgt_pts, C.c_float),
+                                                        _p(ftgt, C.c_float), nt, C.byref(m), C.byref(p), _p(R, C.c_float),
+                                                        _p(t, C.c_float), _p(corr, C.c_int32), _p(d2, C.c_float), C.byref(n),
+                                                        _p(mask, C.c_uint8), C.byref(st)), allow=(SC_ENOHYP,))
+        k = int(n.value)
+        self._frame_n = k
+        return dict(status=rc, R=R.reshape(3, 3), t=t, n=k, corr=corr[:k].copy(), d2=d2[:k].copy(), mask=mask[:k].copy(),
+                    stats=st.as_dict())
 
     def hypothesize_device(self, d_src: int, d_tgt: int, n: int, params: ScParams, d_key: int):
         st = ScStats(C.sizeof(ScStats))

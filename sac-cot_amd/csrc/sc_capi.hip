@@ -120,7 +120,10 @@ struct sc_ctx {
   Buf in_src, in_tgt, planes, S, bits, deg, degp, wpre, ebase, edge_off, scan_tmp, ei, ej, es, ebi, ebj, tcnt, toff, wkey, kcol, ctl, events, blk_gt,
       blk_eq, blk_minmax, bits2, off_gt, off_eq, sel_ord, sel_key, sortkey, sorted, sort_tmp, tri, tri_rk, key_rk, rt, rt_aos, partial, cnt, key, rt12,
       mask, refine_tmp, amx_pairs, strong, rowcost, cost_pre, lb_state, lb_ticket, fx_tile, fx_state, fx_mx, fx_part, fx_coef, guard_tmp, fx_frame, ref_cand,
-      peel_planes, peel_claimed, peel_words, peel_label;  // sc_peel / sc_register_instances: allocated by the first round, never by a frame
+      peel_planes, peel_claimed, peel_words, peel_label,  // sc_peel / sc_register_instances: allocated by the first round, never by a frame
+      // sc_match / sc_register_features: allocated by the first match, never by a frame.  part: the slices' partial lists; words: the
+      // "clean" word, the host entries' count pair, then the column minima; the rest: device copies of the host entries' arrays
+      match_part, match_words, match_fsrc, match_ftgt, match_psrc, match_ptgt, match_corr, match_d2, match_gsrc, match_gtgt;
   // the XCD-aware block orders of stage A (compat_wg_map), one per row width met so far: a context that alternates between a few
   // sizes must not rebuild and upload the map on every call (that cost 2 ms per call in bench.py's varying-n leg)
   static constexpr int N_WG_MAPS = 8;
@@ -1030,7 +1033,9 @@ void sc_destroy(sc_ctx* c) {
                  &c->ei, &c->ej, &c->es, &c->ebi, &c->ebj, &c->tcnt, &c->toff, &c->wkey, &c->kcol, &c->ctl, &c->events, &c->blk_gt, &c->blk_eq, &c->blk_minmax, &c->bits2, &c->off_gt,
                  &c->off_eq, &c->sel_ord, &c->sel_key, &c->sortkey, &c->sorted, &c->sort_tmp, &c->tri, &c->tri_rk, &c->key_rk, &c->rt,
                  &c->rt_aos, &c->partial, &c->cnt, &c->key, &c->rt12, &c->mask, &c->refine_tmp, &c->amx_pairs, &c->strong, &c->rowcost, &c->cost_pre, &c->lb_state, &c->lb_ticket, &c->fx_tile, &c->fx_state, &c->fx_mx, &c->fx_part, &c->fx_coef, &c->guard_tmp, &c->fx_frame, &c->ref_cand,
-                 &c->peel_planes, &c->peel_claimed, &c->peel_words, &c->peel_label};
+                 &c->peel_planes, &c->peel_claimed, &c->peel_words, &c->peel_label,
+                 &c->match_part, &c->match_words, &c->match_fsrc, &c->match_ftgt, &c->match_psrc, &c->match_ptgt, &c->match_corr, &c->match_d2,
+                 &c->match_gsrc, &c->match_gtgt};
   for (sc_ctx::WgMap& m : c->wg_maps) if (m.buf.p) (void)hipFree(m.buf.p);
   for (Buf* b : bufs) if (b->p) (void)hipFree(b->p);
   for (int i = 0; i < N_EVENTS; i++) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
@@ -2083,6 +2088,177 @@ int sc_register_instances(sc_ctx* c, const float* src, const float* tgt, int64_t
   HIPCHK(c, hipStreamSynchronize(st));
   HIPCHK(c, hipGetLastError());
   *n_found = k;
+  return rc;
+}
+
+// ---- descriptor matching (include/saccot.h, sc_match) -----------------------------------------------------
+//
+// memset (the "clean" word and, for SC_MATCH_MUTUAL, the column minima: all ones) -> distance + select -> finish: three stream
+// operations, no host wait.  The host entries then poll ONE word (count | non-finite flag << 32).
+namespace {
+
+constexpr size_t MATCH_WORDS_HEAD = 64;  // match_words: [0] clean, [2], [3] the host entries' count pair; the column minima from byte 64
+
+int match_check(sc_ctx* c, const sc_match_params* mp, int64_t ns, int64_t nt, MatchJob* job) {
+  if (!mp || mp->size != sizeof(sc_match_params)) { c->last_error = "sc_match: bad sc_match_params.size"; return SC_EINVAL; }
+  if (mp->dim < 1 || mp->dim > 1024 || mp->knn < 1 || mp->knn > 4 || (mp->flags & ~SC_MATCH_MUTUAL) != 0 || mp->reserved[0] != 0 ||
+      mp->reserved[1] != 0 || mp->reserved[2] != 0 || ns < 1 || nt < 1 || ns > (1 << 24) || nt > (1 << 24)) {
+    c->last_error = "sc_match: dim 1 .. 1024, knn 1 .. 4, known flags, reserved words 0, 1 <= ns, nt <= 2^24";
+    return SC_EINVAL;
+  }
+  if (!(mp->ratio >= 0.f && mp->ratio < 1.f)) { c->last_error = "sc_match: ratio must be 0 (off) or in (0, 1)"; return SC_EINVAL; }
+  if (mp->knn != 1 && ((mp->flags & SC_MATCH_MUTUAL) || mp->ratio > 0.f)) {
+    c->last_error = "sc_match: SC_MATCH_MUTUAL and the ratio test need knn == 1";
+    return SC_EINVAL;
+  }
+  job->ns = (uint32_t)ns; job->nt = (uint32_t)nt; job->dim = mp->dim; job->knn = mp->knn;
+  job->mutual = (mp->flags & SC_MATCH_MUTUAL) ? 1u : 0u;
+  job->r2 = mp->ratio > 0.f ? (float)((double)mp->ratio * (double)mp->ratio) : 0.f;
+  return SC_OK;
+}
+
+int match_enqueue(sc_ctx* c, const MatchJob& job, int32_t* d_corr, float* d_d2, uint32_t* d_count, const MatchGather& g, bool to_host) {
+  hipStream_t st = c->stream;
+  const MatchPlan plan = match_plan(job.ns, job.nt, job.knn, job.r2);
+  ENSURE(c, c->match_part, plan.part_bytes);
+  const size_t words_bytes = MATCH_WORDS_HEAD + (job.mutual ? (size_t)job.nt * 8 : 0);
+  ENSURE(c, c->match_words, words_bytes);
+  HIPCHK(c, hipMemsetAsync(c->match_words.p, 0xFF, words_bytes, st));
+  LbArgs lb;
+  { const int lrc = lb_next(c, (size_t)match_finish_tiles(job.ns) * 8, 3, 0, &lb); if (lrc) return lrc; }
+  uint32_t* clean = c->match_words.as<uint32_t>();
+  uint64_t* colmin = job.mutual ? reinterpret_cast<uint64_t*>(static_cast<char*>(c->match_words.p) + MATCH_WORDS_HEAD) : nullptr;
+  if (to_host) arm_word(c, HW_MATCH);
+  launch_match_dist(job, plan, c->match_part.as<uint64_t>(), colmin, clean, st);
+  launch_match_finish(job, plan, c->match_part.as<uint64_t>(), colmin, clean, d_corr, d_d2, d_count ? d_count : clean + 2, g, lb,
+                      to_host ? &c->pinned[HW_MATCH] : nullptr, st);
+  HIPCHK(c, hipGetLastError());
+  return SC_OK;
+}
+
+// the host entries' one wait: the count, or SC_EINVAL for a non-finite descriptor
+int match_wait(sc_ctx* c, uint32_t* n) {
+  *n = 0;
+  { const int wrc = wait_word(c, HW_MATCH); if (wrc) return wrc; }
+  const uint64_t w = c->pinned[HW_MATCH];
+  if (w >> 32) { c->last_error = "non-finite descriptor"; return SC_EINVAL; }
+  *n = (uint32_t)w;
+  return SC_OK;
+}
+
+}  // namespace
+
+int sc_match_default_params(sc_match_params* mp) {
+  if (!mp) return SC_EINVAL;
+  memset(mp, 0, sizeof *mp);
+  mp->size = sizeof(sc_match_params);
+  mp->knn = 1;
+  return SC_OK;
+}
+
+int sc_match_device(sc_ctx* c, const float* d_fsrc, int64_t ns, const float* d_ftgt, int64_t nt, const sc_match_params* mp,
+                    int32_t* d_corr, float* d_d2, uint32_t* d_count) {
+  if (!c || !d_fsrc || !d_ftgt || !d_corr || !d_d2 || !d_count) return SC_EINVAL;
+  peel_end(c);
+  { const int brc = busy(c); if (brc) return brc; }
+  MatchJob job{d_fsrc, d_ftgt};
+  { const int rc = match_check(c, mp, ns, nt, &job); if (rc) return rc; }
+  HIPCHK(c, hipSetDevice(c->device));
+  return match_enqueue(c, job, d_corr, d_d2, d_count, MatchGather{}, false);
+}
+
+int sc_match(sc_ctx* c, const float* fsrc, int64_t ns, const float* ftgt, int64_t nt, const sc_match_params* mp, int32_t* corr,
+             float* d2, uint32_t* n) {
+  if (!c || !fsrc || !ftgt || !corr || !d2 || !n) return SC_EINVAL;
+  *n = 0;
+  peel_end(c);
+  { const int brc = busy(c); if (brc) return brc; }
+  MatchJob job{};
+  int rc = match_check(c, mp, ns, nt, &job);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  const size_t sb = (size_t)job.ns * job.dim * 4, tb = (size_t)job.nt * job.dim * 4, cap = (size_t)job.ns * job.knn;
+  ENSURE(c, c->match_fsrc, sb);
+  ENSURE(c, c->match_ftgt, tb);
+  ENSURE(c, c->match_corr, cap * 8);
+  ENSURE(c, c->match_d2, cap * 4);
+  HIPCHK(c, hipMemcpyAsync(c->match_fsrc.p, fsrc, sb, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(c->match_ftgt.p, ftgt, tb, hipMemcpyHostToDevice, st));
+  job.fsrc = c->match_fsrc.as<float>(); job.ftgt = c->match_ftgt.as<float>();
+  if ((rc = match_enqueue(c, job, c->match_corr.as<int32_t>(), c->match_d2.as<float>(), nullptr, MatchGather{}, true))) return rc;
+  uint32_t found = 0;
+  if ((rc = match_wait(c, &found))) return rc;
+  if (found) {
+    HIPCHK(c, hipMemcpyAsync(corr, c->match_corr.p, (size_t)found * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(d2, c->match_d2.p, (size_t)found * 4, hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(c, hipStreamSynchronize(st));
+  *n = found;
+  return SC_OK;
+}
+
+int sc_register_features(sc_ctx* c, const float* src_pts, const float* fsrc, int64_t ns, const float* tgt_pts, const float* ftgt,
+                         int64_t nt, const sc_match_params* mp, const sc_params* p, float R[9], float t[3], int32_t* corr, float* d2,
+                         uint32_t* n, uint8_t* mask, sc_stats* stats) {
+  if (!c || !src_pts || !fsrc || !tgt_pts || !ftgt || !R || !t || !corr || !d2 || !n || !mask) return SC_EINVAL;
+  *n = 0;
+  peel_end(c);
+  { const int brc = busy(c); if (brc) return brc; }
+  int rc = check_params(p);
+  if (rc) return rc;
+  if (p->shard_world != 1) return SC_EINVAL;
+  MatchJob job{};
+  if ((rc = match_check(c, mp, ns, nt, &job))) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  c->cap_bytes = p->max_workspace ? p->max_workspace : (64ull << 30);
+  hipStream_t st = c->stream;
+  const size_t sb = (size_t)job.ns * job.dim * 4, tb = (size_t)job.nt * job.dim * 4, cap = (size_t)job.ns * job.knn;
+  ENSURE(c, c->match_fsrc, sb);
+  ENSURE(c, c->match_ftgt, tb);
+  ENSURE(c, c->match_psrc, (size_t)job.ns * 12);
+  ENSURE(c, c->match_ptgt, (size_t)job.nt * 12);
+  ENSURE(c, c->match_corr, cap * 8);
+  ENSURE(c, c->match_d2, cap * 4);
+  ENSURE(c, c->match_gsrc, cap * 12);
+  ENSURE(c, c->match_gtgt, cap * 12);
+  HIPCHK(c, hipMemcpyAsync(c->match_fsrc.p, fsrc, sb, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(c->match_ftgt.p, ftgt, tb, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(c->match_psrc.p, src_pts, (size_t)job.ns * 12, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(c->match_ptgt.p, tgt_pts, (size_t)job.nt * 12, hipMemcpyHostToDevice, st));
+  job.fsrc = c->match_fsrc.as<float>(); job.ftgt = c->match_ftgt.as<float>();
+  const bool soa = p->layout == SC_SOA;
+  // the gathered correspondences are written n x 3 whatever the caller's layout: n is not known while they are written
+  const MatchGather g{c->match_psrc.as<float>(), c->match_ptgt.as<float>(), soa ? 1u : 3u, soa ? job.ns : 1u, soa ? 1u : 3u,
+                      soa ? job.nt : 1u, c->match_gsrc.as<float>(), c->match_gtgt.as<float>()};
+  if ((rc = match_enqueue(c, job, c->match_corr.as<int32_t>(), c->match_d2.as<float>(), nullptr, g, true))) return rc;
+  uint32_t found = 0;
+  if ((rc = match_wait(c, &found))) return rc;  // the one host wait between matching and registration
+  if (found) {
+    HIPCHK(c, hipMemcpyAsync(corr, c->match_corr.p, (size_t)found * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(d2, c->match_d2.p, (size_t)found * 4, hipMemcpyDeviceToHost, st));
+  }
+  *n = found;
+  if (found < 3) {
+    HIPCHK(c, hipStreamSynchronize(st));
+    const float ident[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
+    memcpy(R, ident, 36);
+    memset(t, 0, 12);
+    return SC_ENOHYP;
+  }
+  sc_params pg = *p;
+  pg.layout = SC_AOS;
+  ENSURE(c, c->rt12, 64);
+  ENSURE(c, c->mask, (size_t)found);
+  rc = sc_register_device(c, c->match_gsrc.as<float>(), c->match_gtgt.as<float>(), found, &pg, c->rt12.as<float>(),
+                          c->mask.as<uint8_t>(), stats);
+  if (rc != SC_OK && rc != SC_ENOHYP) { (void)hipStreamSynchronize(st); return rc; }
+  float Rt[12];
+  HIPCHK(c, hipMemcpyAsync(Rt, c->rt12.p, 48, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(mask, c->mask.p, (size_t)found, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  memcpy(R, Rt, 36);
+  memcpy(t, Rt + 9, 12);
   return rc;
 }
 

@@ -573,7 +573,8 @@ enum HostWord : int {
   HW_WINNER = 8,        // the winner's key: the last word a call writes.  Armed by finalize_enqueue, written by the finalize kernel, polled by finalize_wait
   HW_WINNER_POS = 9,    // rank << 32 | position of the winner (all ones: the pair decodes to nothing).  Written before HW_WINNER, read behind it
   HW_PEEL_ALIVE = 10,   // sc_peel, truncated score modes: correspondences a round's compaction kept.  Armed and polled by the round, written by the compaction kernel
-  HW_CAND_CUT = 12,     // a cut candidate list mattered (SC_ERETRY).  Cleared by sc_shard_score_device, set by merge_check, read by finalize_wait
+  HW_MATCH = 11,        // sc_match / sc_register_features: matches kept | non-finite flag << 32.  Armed and polled by the host entries, written by the finish kernel
+  HW_CAND_CUT = 12,    // a cut candidate list mattered (SC_ERETRY).  Cleared by sc_shard_score_device, set by merge_check, read by finalize_wait
   HW_COORD_MAX = 13,    // max|tgt| << 32 | max|src|.  Armed by stage_inputs, written by the staging kernel (host-free: by the finalize kernel, every 64th
                         // call), read with acquire by read_coord_stats; sc_score_host polls it
   HW_SELECT_SHORT = 14, // the select found fewer keys above the pruning bound than promised.  Cleared by run_edges, set by select / compaction, read by finalize_wait
@@ -623,5 +624,37 @@ void launch_peel_winner(const Points& pts, const uint8_t* claimed, const float* 
                         uint64_t* host_out, hipStream_t st);
 // label[m] = value where mask[m] (sc_register_instances: one launch per accepted motion)
 void launch_peel_label(const uint8_t* mask, int n, int32_t value, int32_t* label, hipStream_t st);
+
+// ---- descriptor matching (sc_match; sc_match.hip) -------------------------------------------------------
+// One call: fsrc ns x dim, ftgt nt x dim (row-major fp32, device); knn 1 .. 4; mutual / r2 (> 0: the ratio test, r2 = ratio^2) with
+// knn == 1 only.  A key is (bits of the canonical squared distance) << 32 | index.
+struct MatchJob {
+  const float* fsrc; const float* ftgt;
+  uint32_t ns, nt, dim, knn, mutual;
+  float r2;
+};
+// How the distance launch is cut: row_blocks x slices workgroups, a slice = tiles_per_slice column tiles; every (row, slice) leaves kp
+// ascending keys in `part` (key q of slice s of row i at part[(s * kp + q) * ld_part + i]; all ones: none), part_bytes in all.
+struct MatchPlan {
+  uint32_t kp, row_blocks, slices, tiles_per_slice;
+  size_t ld_part, part_bytes;
+};
+MatchPlan match_plan(uint32_t ns, uint32_t nt, uint32_t knn, float r2);
+// sc_register_features: the matched points, gathered by the finish launch into two n x 3 arrays (gsrc == nullptr: no gather).
+// Point i of src is src[i * s_elem + c * s_comp] (either layout of sc_params).
+struct MatchGather {
+  const float* src; const float* tgt;
+  uint32_t s_elem, s_comp, t_elem, t_comp;
+  float* gsrc; float* gtgt;
+};
+// colmin (SC_MATCH_MUTUAL, else nullptr): nt keys (distance << 32 | row), all ones at launch.  clean: one word, non-zero at launch,
+// cleared when a non-finite descriptor is read.
+void launch_match_dist(const MatchJob& job, const MatchPlan& plan, uint64_t* part, uint64_t* colmin, uint32_t* clean, hipStream_t st);
+// merge + mutual / ratio + compaction in (row, rank) order: corr (n x 2 int32), d2 (n), count[0] = n, count[1] = 1 if a non-finite
+// descriptor was read (then n = 0 and nothing else is written).  lb: a look-back launch of match_finish_tiles(ns) tiles (8 bytes of
+// descriptor each).  host_word (optional, pinned): receives n | flag << 32.
+uint32_t match_finish_tiles(uint32_t ns);
+void launch_match_finish(const MatchJob& job, const MatchPlan& plan, const uint64_t* part, const uint64_t* colmin, const uint32_t* clean,
+                         int32_t* corr, float* d2, uint32_t* count, const MatchGather& g, LbArgs lb, uint64_t* host_word, hipStream_t st);
 
 }  // namespace sc

@@ -1,0 +1,284 @@
+// sc_match.hip — descriptor matching (include/saccot.h, sc_match): brute-force nearest neighbours between two descriptor sets under a
+// total order, then mutual / ratio test and an order-preserving compaction.  Two launches:
+//
+//   match_dist_kernel    all-pairs canonical distance + per-row selection.  Register-tiled like an SGEMM: a workgroup owns 128 source
+//                        rows and a SLICE of the target columns, which it walks in tiles of 64; both tiles are staged in LDS in
+//                        chunks of 16 components (transposed: component-major, so a thread reads its 8 rows and 4 columns of one
+//                        component with three 16-byte reads), every thread carries an 8 x 4 block of sums in registers across the
+//                        chunks (the last chunk is cut short at D) — the chain of a pair is sequential in c, D = 1024 needs no
+//                        more LDS than D = 16.  The sums are held as pairs of adjacent columns (a 2-vector subtract, multiply, add per pair: no fused multiply-add,
+//                        whatever the build's contraction setting).  Zero padding in c is exact: (0 - 0)^2 adds +0 to a sum >= 0.
+//                        Selection: a row's KP smallest keys (distance bits << 32 | column) of the slice live in LDS and take
+//                        candidates through a cascade of 64-bit minima — slot q keeps the smaller of (what it holds, what arrives)
+//                        and passes the larger on to slot q + 1.  Every key goes through slot 0, so slot 0 ends as the minimum of
+//                        all; what slot 1 sees is everything else; and so on: the KP smallest in order, whatever the interleaving.
+//                        The slice's lists go to workspace (part); the column minima that SC_MATCH_MUTUAL needs combine through
+//                        LDS and then global 64-bit atomic minima (a minimum is order-free: deterministic).  A non-finite
+//                        descriptor clears the `clean` word: every element is read by some workgroup.
+//   match_finish_kernel  one thread per source row: merges the row's slices under the same order, applies mutual / ratio, takes its
+//                        output slots from a decoupled look-back over the tiles (sc_block.hpp, as peel_compact_kernel), writes
+//                        corr / d2 in ascending (row, rank) order, gathers the matched points for sc_register_features, and the
+//                        last tile writes the count and the non-finite flag.
+#include <cstddef>
+
+#include "sc_block.hpp"
+#include "sc_kernels.hpp"
+
+#pragma clang fp contract(off)  // the canonical distance rounds the product and the sum separately
+
+namespace sc {
+
+namespace {
+
+constexpr int MT_ROWS = 128, MT_COLS = 64, MT_KC = 16, MT_THREADS = 256;
+constexpr int MT_LDA = MT_ROWS + 4, MT_LDB = MT_COLS + 4;  // 16-byte aligned rows; the pad spreads the transposing stores over the banks
+constexpr int FIN_THREADS = 256;
+constexpr unsigned long long KEY_NONE = ~0ull;  // above every real key: a real key's low half is an index < 2^24
+
+typedef float f2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ bool not_finite(float v) { return (__float_as_uint(v) & 0x7F800000u) == 0x7F800000u; }
+
+// slot q keeps the smaller, the larger moves on (see the head of the file)
+template <int KP>
+__device__ __forceinline__ void top_insert(unsigned long long* list, unsigned long long key) {
+#pragma unroll
+  for (int q = 0; q < KP; q++) {
+    const unsigned long long old = atomicMin(&list[q], key);
+    if (old > key) key = old;
+    if (key == KEY_NONE) break;  // (an empty slot was filled: nothing left to pass on)
+  }
+}
+
+// one component: the thread's 8 rows (pa) against its 4 columns (pb), as two column pairs
+__device__ __forceinline__ void tile_step(f2 (&acc)[8][2], const float* pa, const float* pb) {
+  const float4 a0 = *reinterpret_cast<const float4*>(pa);
+  const float4 a1 = *reinterpret_cast<const float4*>(pa + 4);
+  const float4 b = *reinterpret_cast<const float4*>(pb);
+  const float a[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+  const f2 b01 = f2{b.x, b.y}, b23 = f2{b.z, b.w};
+#pragma unroll
+  for (int r = 0; r < 8; r++) {
+    const f2 ar = f2{a[r], a[r]};
+    const f2 d0 = ar - b01, d1 = ar - b23;
+    acc[r][0] = acc[r][0] + d0 * d0;
+    acc[r][1] = acc[r][1] + d1 * d1;
+  }
+}
+
+template <int KP>
+__global__ __launch_bounds__(MT_THREADS) void match_dist_kernel(const float* __restrict__ fsrc, uint32_t ns,
+                                                                const float* __restrict__ ftgt, uint32_t nt, uint32_t D,
+                                                                uint32_t tiles_per_slice, unsigned long long* __restrict__ part,
+                                                                size_t ld_part, unsigned long long* __restrict__ colmin,
+                                                                uint32_t* __restrict__ clean) {
+  __shared__ __attribute__((aligned(16))) float sA[MT_KC][MT_LDA];
+  __shared__ __attribute__((aligned(16))) float sB[MT_KC][MT_LDB];
+  __shared__ unsigned long long s_top[MT_ROWS][KP];
+  __shared__ unsigned long long s_col[MT_COLS];
+  const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;  // the thread's 4 columns / 8 rows; also (component, row) when it loads
+  const uint32_t row0 = blockIdx.x * MT_ROWS;
+  const uint32_t n_tiles = (nt + MT_COLS - 1) / MT_COLS;
+  const uint32_t tile_lo = blockIdx.y * tiles_per_slice;
+  const uint32_t tile_hi = tile_lo + tiles_per_slice < n_tiles ? tile_lo + tiles_per_slice : n_tiles;
+  for (int e = threadIdx.x; e < MT_ROWS * KP; e += MT_THREADS) (&s_top[0][0])[e] = KEY_NONE;
+  bool bad = false;
+  for (uint32_t tile = tile_lo; tile < tile_hi; tile++) {
+    const uint32_t col0 = tile * MT_COLS;
+    if (threadIdx.x < MT_COLS) s_col[threadIdx.x] = KEY_NONE;
+    f2 acc[8][2];
+#pragma unroll
+    for (int r = 0; r < 8; r++) { acc[r][0] = f2{0.f, 0.f}; acc[r][1] = f2{0.f, 0.f}; }
+    for (uint32_t c0 = 0; c0 < D; c0 += MT_KC) {
+      const uint32_t c = c0 + tx;
+      float va[MT_ROWS / 16], vb[MT_COLS / 16];
+#pragma unroll
+      for (int it = 0; it < MT_ROWS / 16; it++) {
+        const uint32_t row = row0 + ty + 16 * it;
+        va[it] = (row < ns && c < D) ? fsrc[(size_t)row * D + c] : 0.f;
+      }
+#pragma unroll
+      for (int it = 0; it < MT_COLS / 16; it++) {
+        const uint32_t col = col0 + ty + 16 * it;
+        vb[it] = (col < nt && c < D) ? ftgt[(size_t)col * D + c] : 0.f;
+      }
+      __syncthreads();  // the chunk before is consumed (and, first chunk: the lists' and s_col's initial values are written)
+#pragma unroll
+      for (int it = 0; it < MT_ROWS / 16; it++) { bad = bad || not_finite(va[it]); sA[tx][ty + 16 * it] = va[it]; }
+#pragma unroll
+      for (int it = 0; it < MT_COLS / 16; it++) { bad = bad || not_finite(vb[it]); sB[tx][ty + 16 * it] = vb[it]; }
+      __syncthreads();
+      // the last chunk of a descriptor is cut short (D = 33: 16 + 16 + 1 components, not 48); the bound is uniform
+      const uint32_t lim = D - c0 < (uint32_t)MT_KC ? D - c0 : (uint32_t)MT_KC;
+      if (lim == (uint32_t)MT_KC) {
+#pragma unroll
+        for (int k = 0; k < MT_KC; k++) tile_step(acc, &sA[k][ty * 8], &sB[k][tx * 4]);
+      } else {
+        for (uint32_t k = 0; k < lim; k++) tile_step(acc, &sA[k][ty * 8], &sB[k][tx * 4]);
+      }
+    }
+    // selection.  (Every thread is behind the last chunk's second barrier: the lists and s_col hold at least their initial values.)
+    const uint32_t colb = col0 + tx * 4;
+    unsigned long long cmin[4] = {KEY_NONE, KEY_NONE, KEY_NONE, KEY_NONE};
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+      const uint32_t lr = ty * 8 + r, row = row0 + lr;
+      if (row >= ns) continue;
+      const float v[4] = {acc[r][0].x, acc[r][0].y, acc[r][1].x, acc[r][1].y};
+      unsigned long long* list = &s_top[lr][0];
+      // what the list's last slot holds only ever falls: an old value lets a candidate through that the cascade then passes out again
+      const unsigned long long worst = *reinterpret_cast<volatile unsigned long long*>(&list[KP - 1]);
+      unsigned long long best = KEY_NONE;
+#pragma unroll
+      for (int cc = 0; cc < 4; cc++) {
+        if (colb + cc >= nt) continue;
+        const unsigned long long hi = (unsigned long long)__float_as_uint(v[cc]) << 32;
+        const unsigned long long key = hi | (colb + cc);
+        const unsigned long long rkey = hi | row;
+        cmin[cc] = rkey < cmin[cc] ? rkey : cmin[cc];
+        if (KP == 1) best = key < best ? key : best;
+        else if (key < worst) top_insert<KP>(list, key);
+      }
+      if (KP == 1 && best < worst) atomicMin(&list[0], best);
+    }
+    if (colmin) {
+#pragma unroll
+      for (int cc = 0; cc < 4; cc++)
+        if (cmin[cc] != KEY_NONE) atomicMin(&s_col[tx * 4 + cc], cmin[cc]);
+      __syncthreads();
+      if (threadIdx.x < MT_COLS && col0 + threadIdx.x < nt) {
+        const unsigned long long v = s_col[threadIdx.x];
+        unsigned long long* g = &colmin[col0 + threadIdx.x];
+        if (v < __hip_atomic_load(g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(g, v);
+      }
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < MT_ROWS && row0 + threadIdx.x < ns) {
+#pragma unroll
+    for (int q = 0; q < KP; q++) part[((size_t)blockIdx.y * KP + q) * ld_part + row0 + threadIdx.x] = s_top[threadIdx.x][q];
+  }
+  if (bad) __hip_atomic_store(clean, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ __launch_bounds__(FIN_THREADS) void match_finish_kernel(const unsigned long long* __restrict__ part, size_t ld_part,
+                                                                   uint32_t slices, uint32_t kp, MatchJob job,
+                                                                   const unsigned long long* __restrict__ colmin,
+                                                                   const uint32_t* __restrict__ clean, int32_t* __restrict__ corr,
+                                                                   float* __restrict__ d2, uint32_t* __restrict__ count,
+                                                                   MatchGather g, LbArgs lb, uint64_t* host_word) {
+  __shared__ uint32_t s_tile;
+  __shared__ uint64_t s_scan[FIN_THREADS / 64];
+  __shared__ uint64_t s_prefix;
+  if (threadIdx.x == 0) s_tile = __hip_atomic_fetch_add(lb.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __syncthreads();
+  const uint32_t tile = s_tile;
+  if (tile >= gridDim.x) return;  // (a ticket that was not zero at launch: never index memory with it)
+  const uint32_t i = tile * FIN_THREADS + threadIdx.x;
+  const bool ok = __hip_atomic_load(clean, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
+  unsigned long long top[4] = {KEY_NONE, KEY_NONE, KEY_NONE, KEY_NONE};
+  uint32_t cnt = 0;
+  if (ok && i < job.ns) {
+    for (uint32_t s = 0; s < slices; s++) {
+      for (uint32_t q = 0; q < kp; q++) {
+        unsigned long long key = part[((size_t)s * kp + q) * ld_part + i];
+        if (key >= top[3]) break;  // (a slice's list ascends)
+#pragma unroll
+        for (int w = 0; w < 4; w++) {
+          const unsigned long long lo = key < top[w] ? key : top[w];
+          key = key < top[w] ? top[w] : key;
+          top[w] = lo;
+        }
+      }
+    }
+    if (job.mutual || job.r2 > 0.f) {
+      bool keep = top[0] != KEY_NONE;
+      const uint32_t j = (uint32_t)top[0];
+      if (keep && job.mutual) keep = j < job.nt && colmin[j] == ((top[0] & 0xFFFFFFFF00000000ull) | i);
+      if (keep && job.r2 > 0.f && top[1] != KEY_NONE)
+        keep = __uint_as_float((uint32_t)(top[0] >> 32)) < __fmul_rn(job.r2, __uint_as_float((uint32_t)(top[1] >> 32)));
+      cnt = keep ? 1u : 0u;
+    } else {
+#pragma unroll
+      for (int w = 0; w < 4; w++) cnt += (w < (int)job.knn && top[w] != KEY_NONE) ? 1u : 0u;
+    }
+  }
+  uint64_t tot;
+  const uint64_t ex = block_exscan_u64(cnt, s_scan, &tot);
+  if (threadIdx.x < 64) {
+    uint64_t* const desc[1] = {lb.desc};
+    const uint64_t own[1] = {tot};
+    uint64_t pre[1];
+    lb_lookback<1>(desc, tile, lb.epoch, own, pre, lb.err);
+    if (threadIdx.x == 0) s_prefix = pre[0];
+  }
+  __syncthreads();
+  const uint64_t pre = s_prefix;
+  const size_t cap = (size_t)job.ns * job.knn;
+#pragma unroll
+  for (int w = 0; w < 4; w++) {
+    if (w >= (int)cnt) break;
+    const size_t slot = (size_t)(pre + ex + w);
+    const uint32_t j = (uint32_t)top[w];
+    if (slot >= cap || j >= job.nt) break;  // (cannot happen: a row emits at most knn keys, each with a column of this call)
+    corr[2 * slot] = (int32_t)i;
+    corr[2 * slot + 1] = (int32_t)j;
+    d2[slot] = __uint_as_float((uint32_t)(top[w] >> 32));
+    if (g.gsrc) {
+#pragma unroll
+      for (int c = 0; c < 3; c++) {
+        g.gsrc[3 * slot + c] = g.src[(size_t)i * g.s_elem + (size_t)c * g.s_comp];
+        g.gtgt[3 * slot + c] = g.tgt[(size_t)j * g.t_elem + (size_t)c * g.t_comp];
+      }
+    }
+  }
+  if (tile == gridDim.x - 1 && threadIdx.x == 0) {
+    const uint32_t n = ok ? (uint32_t)(pre + tot) : 0u;
+    count[0] = n;
+    count[1] = ok ? 0u : 1u;
+    if (host_word) publish_host(host_word, (uint64_t)n | ((uint64_t)(ok ? 0u : 1u) << 32));
+    __hip_atomic_store(lb.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // every tile has taken its ticket
+  }
+}
+
+}  // namespace
+
+MatchPlan match_plan(uint32_t ns, uint32_t nt, uint32_t knn, float r2) {
+  MatchPlan p;
+  p.kp = r2 > 0.f ? 2u : knn;  // the ratio test looks at the second-smallest key
+  p.row_blocks = (ns + MT_ROWS - 1) / MT_ROWS;
+  const uint32_t tiles = (nt + MT_COLS - 1) / MT_COLS;
+  // enough workgroups to fill the device a few times over (256 CUs, several resident workgroups each); never more than 1024 slices:
+  // the finish kernel reads slices * kp keys per row
+  uint32_t want = (4096 + p.row_blocks - 1) / p.row_blocks;
+  if (want > 1024) want = 1024;
+  if (want > tiles) want = tiles;
+  p.tiles_per_slice = (tiles + want - 1) / want;
+  p.slices = (tiles + p.tiles_per_slice - 1) / p.tiles_per_slice;
+  p.ld_part = (size_t)p.row_blocks * MT_ROWS;
+  p.part_bytes = p.ld_part * p.slices * p.kp * sizeof(uint64_t);
+  return p;
+}
+
+uint32_t match_finish_tiles(uint32_t ns) { return (ns + FIN_THREADS - 1) / FIN_THREADS; }
+
+void launch_match_dist(const MatchJob& job, const MatchPlan& plan, uint64_t* part, uint64_t* colmin, uint32_t* clean, hipStream_t st) {
+  const dim3 grid(plan.row_blocks, plan.slices), block(MT_THREADS);
+  unsigned long long* p = reinterpret_cast<unsigned long long*>(part);
+  unsigned long long* cm = reinterpret_cast<unsigned long long*>(colmin);
+  switch (plan.kp) {
+    case 1: hipLaunchKernelGGL(match_dist_kernel<1>, grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean); break;
+    case 2: hipLaunchKernelGGL(match_dist_kernel<2>, grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean); break;
+    case 3: hipLaunchKernelGGL(match_dist_kernel<3>, grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean); break;
+    default: hipLaunchKernelGGL(match_dist_kernel<4>, grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean); break;
+  }
+}
+
+void launch_match_finish(const MatchJob& job, const MatchPlan& plan, const uint64_t* part, const uint64_t* colmin, const uint32_t* clean,
+                         int32_t* corr, float* d2, uint32_t* count, const MatchGather& g, LbArgs lb, uint64_t* host_word, hipStream_t st) {
+  hipLaunchKernelGGL(match_finish_kernel, dim3(match_finish_tiles(job.ns)), dim3(FIN_THREADS), 0, st,
+                     reinterpret_cast<const unsigned long long*>(part), plan.ld_part, plan.slices, plan.kp, job,
+                     reinterpret_cast<const unsigned long long*>(colmin), clean, corr, d2, count, g, lb, host_word);
+}
+
+}  // namespace sc

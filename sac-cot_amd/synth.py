@@ -165,6 +165,46 @@ def make_scene_motions(n: int, rhos, L: float, tau: float, seed: int) -> MotionS
     return MotionScene(a.src, tgt, label, motions)
 
 
+@dataclasses.dataclass
+class FeatureScene:
+    src_pts: np.ndarray   # (n,3) float32 — source keypoints
+    tgt_pts: np.ndarray   # (nt,3) float32 — target keypoints: the true counterparts and clutter, shuffled
+    fsrc: np.ndarray      # (n,dim) float32 — one descriptor per source keypoint
+    ftgt: np.ndarray      # (nt,dim) float32
+    truth: np.ndarray     # (n,) int32 — the target row that is source row i's true counterpart, -1: it has none
+    R_gt: np.ndarray      # (3,3) float64
+    t_gt: np.ndarray      # (3,) float64
+
+
+def make_feature_scene(cfg: Config, nt_extra: int, dim: int, sd: float, seed: int | None = None) -> FeatureScene:
+    """Two keypoint clouds with descriptors, for the matcher in front of the registration (sc_match / sc_register_features).
+    make_scene(cfg.n, 2 * cfg.rho, ...) gives the source points and, for its "inlier" rows (the overlap), their true counterparts;
+    the target cloud holds cfg.n + nt_extra points — those counterparts, and uniform clutter in the target box in place of every
+    other row — in an order shuffled by the counter hash.  Descriptors: unit Gaussians per source point; a counterpart's is its
+    source's plus sd x Gaussian noise; clutter's are independent.  Streams 7 .. 11 of `seed` (default: the config's)."""
+    seed = cfg.seed if seed is None else seed
+    n, nt = cfg.n, cfg.n + nt_extra
+    sc = make_scene(n, 2 * cfg.rho, cfg.L, cfg.tau, seed)
+    perm = np.argsort(_bits(seed, 7, np.arange(nt, dtype=np.uint64)), kind="stable")  # row r of the recipe lands at target row perm[r]
+    idx_s = np.arange(n * dim, dtype=np.uint64).reshape(n, dim)
+    idx_t = np.arange(nt * dim, dtype=np.uint64).reshape(nt, dim)
+    fs = gauss(seed, 8, idx_s)
+    f_rows = gauss(seed, 9, idx_t)
+    noise = gauss(seed, 10, idx_s) * sd
+    lo, hi = sc.tgt.min(axis=0), sc.tgt.max(axis=0)
+    p_rows = lo + uniform01(seed, 11, np.arange(nt * 3, dtype=np.uint64).reshape(nt, 3)) * (hi - lo)
+    own = np.flatnonzero(sc.inlier)
+    p_rows[own] = sc.tgt[own]
+    f_rows[own] = fs[own] + noise[own]
+    tgt_pts = np.empty((nt, 3), np.float32)
+    ftgt = np.empty((nt, dim), np.float32)
+    tgt_pts[perm] = p_rows.astype(np.float32)
+    ftgt[perm] = f_rows.astype(np.float32)
+    truth = np.full(n, -1, dtype=np.int32)
+    truth[own] = perm[own]
+    return FeatureScene(sc.src, tgt_pts, fs.astype(np.float32), ftgt, truth, sc.R_gt, sc.t_gt)
+
+
 def make_config_scene(name: str) -> tuple[Config, Scene]:
     cfg = CONFIGS[name]
     return cfg, make_scene(cfg.n, cfg.rho, cfg.L, cfg.tau, cfg.seed)
