@@ -1,175 +1,25 @@
-// sc_capi.hip — the C ABI of include/saccot.h: context, grow-only device workspace, stage sequencing.
+// sc_capi.hip — the core of the C ABI of include/saccot.h: the context's lifetime and its grow-only device workspace, sc_set_debug /
+// sc_debug_last, pass and frame, every run_* stage sequencer, and the register, hypothesize, finalize, shard and wait entries.  The
+// rest of the ABI sits in host-only files of its own, on sc_ctx.hpp (sc_ctx itself and the shared helpers): sc_capi_hooks.hip (the
+// sc_*_host stage hooks), sc_capi_peel.hip (sc_peel*, sc_register_instances), sc_capi_match.hip (sc_match*, sc_register_features).
 //
-// There is no reference interface to mirror (the reference tree is /root/reference/README.md:1-2); the
-// boundary is SURVEY.md §8(b).  Everything that computes runs on the GPU: this file only validates,
-// allocates, enqueues kernels (sc_kernels.hpp) and copies.  Two small read-backs (edge count, triangle
-// count) size the data-dependent buffers; there is no CPU fallback of any stage.
-#include <hip/hip_runtime.h>
+// There is no reference interface to mirror (the reference tree holds a two-line README.md and no code, which is why there is no
+// oracle/_ref); the boundary is SURVEY.md §8(b).  Everything that computes runs on the GPU: these files only validate, allocate,
+// enqueue kernels (sc_kernels.hpp) and copy.  Two small read-backs (edge count, triangle count) size the data-dependent buffers;
+// there is no CPU fallback of any stage.
 #include <atomic>
 #include <chrono>
-
 #include <cmath>
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <new>
-#include <string>
 #include <utility>
 
-#include "../../include/saccot.h"
-#include "../../include/saccot_debug.h"
-#include "sc_kernels.hpp"
+#include "sc_ctx.hpp"
 #include "sc_gramref.hpp"
 
 using namespace sc;
 
-namespace {
-
-struct Buf {
-  void* p = nullptr;
-  size_t cap = 0;
-  template <class T> T* as() const { return static_cast<T*>(p); }
-};
-
-constexpr int N_EVENTS = 12;  // 0..8 stage brackets, 9..10 the key kernel (all reused by calibrate_events), 11 the stop of stage C2's filter kernel (SC_FLAG_TIMING_HOT)
-constexpr int N_PINNED = HW_COUNT;  // the host words (sc_kernels.hpp, HostWord)
-static_assert(HW_MERGED_M == HW_MERGED_T + 1 && HW_WINNER_POS == HW_WINNER + 1, "merge_prepare and the finalize kernel write word pairs");
-
-// How a pass is enqueued: decided by the entry point BEFORE the pass starts and handed to hyp_begin, which stores it in the fresh pass.
-struct PassMode {
-  // the entry point can repeat the call (sc_register*), or its caller does (sc_hypothesize_device with SC_FLAG_EST_BOUND): stage B
-  // may prune by an ESTIMATED bound (sc_tri.hip 3c); the select verifies it, finalize_wait reads the verdict
-  bool may_estimate = false;
-  // host-free enqueue (include/saccot.h): a call of the last one's shape does not wait for stage B's two counts; its launches cover E_cov
-  // edges / M_cov keys (fast_plan) and read the real counts from device memory; finalize_wait validates, and the call is repeated the waiting
-  // way when a count outgrew the cover.  pass_end takes host_free back; the covers stay for sc_debug_last.
-  bool host_free = false;
-  uint64_t E_cov = 0, M_cov = 0;
-};
-
-// One run through hyp_begin (or sc_shard_compat_device) to finalize_wait.  Assigned Pass{} in pass_begin and nowhere else: what a pass
-// did not set itself reads as "no".  Fields are READ after the pass as well — by a finalize call that comes later (have_hyp links the
-// two, and it may come twice), by note_completed (E, M, n, params, use_events), by fill_stats and sc_debug_last (counts, covers, filter_*,
-// est_state, hot_ext) — so nothing is cleared when a pass ends except mode.host_free.  The stage hooks (sc_*_host) start no pass: they
-// run single kernels on the context's buffers and touch only what host_to_planes says.
-struct Pass {
-  PassMode mode;
-  int n = 0, ld = 0; uint32_t T_eff = 0;
-  uint64_t E = 0, M = 0, M_total = 0;  // stage B's counts (host-free: the covers until finalize_wait has validated, then the real ones)
-  bool pruned = false, use_events = false, have_total = false;
-  Derived dv{}; Shard sh{};
-  bool begun = false, have_hyp = false;  // sc_hypothesize_begin_device is done (_end may follow); the hypothesize half is done (finalize may follow)
-  sc_params params{};
-  bool timing = false, timing_hot = false, timed_trikeys = false, refine = false;
-  int timing_one = -1;      // SC_FLAG_TIMING_ONE: the one stage bracket recorded (0 .. 6), -1: none
-  bool hot_ext = false;     // SC_FLAG_TIMING_HOT took its timestamps from the kernels' dispatch packets (run_stage_c)
-  uint32_t amx_blocks = 0;  // workgroups of the arg-max launch whose pairs this context's finalize step reduces itself (0: one reduced pair in `key`)
-  uint64_t* bits_cur = nullptr;  // the adjacency bit matrix: the context's own buffer, or — sharded stage A — the caller's all-gathered one
-  bool rows_fused = false;  // run_row_stats already produced edge_off / ebase / cost_pre and armed the edge count
-  bool build = false;       // launch_edge_build: row statistics + edge list + estimating sample in one launch
-  bool regular = false;     // every assumption of the host-free form was met (run_select, finalize_wait): note_completed files it as fast_ok
-  bool est_active = false;  // stage B prunes by an estimate
-  bool est_void = false;    // ... which could not be verified on the path taken (event overflow): repeat
-  int est_state = 0;        // 0 certified bound (or no pruning), 1 estimated and verified: finalize_wait's verdict, read by count_frame
-  SamplePlan plan{false, 1u, 0};
-  // stage C2's reference frame (sc_gramref.hpp): on the hot path the estimating sample leaves candidate triangles behind (ref_cand_n of
-  // them) and the counting pass carries the vote as an extra workgroup (ref_done); everywhere else stage C votes in a launch of its own
-  uint32_t ref_cand_n = 0; bool ref_done = false;
-  bool filter_on = false;   // C2 goes through a matrix-pipe filter (decided ONCE per pass: decide_filter)
-  int filter_mode = 0;      // ... which: 1 linear, 2 Gram (0: the plain fp32 kernel)
-  FilterPlan fx_plan{};     // ... with this plan
-  // sharded A + B (sc_shard_*_device): the phase reached (0: none) and the gathered candidate blobs
-  bool sharded_ab = false; int shard_phase = 0;
-  const void* cand_all = nullptr; size_t cand_bytes = 0;
-  // rounds on this pass's frame (sc_peel): set where a frame's status becomes SC_OK (sc_wait, whichever way the frame ran), gone with
-  // the pass (pass_begin) or when any other computing entry is called (peel_end)
-  bool peelable = false;
-  uint32_t peel_round = 0;           // rounds done
-  uint32_t peel_prev = 0xFFFFFFFFu;  // position of the winner whose mask the next round's claim step folds in (all ones: none)
-  uint32_t peel_claimed = 0;         // inlier-count mode: correspondences claimed so far (the best_counts add up to it)
-};
-
-// One call of an entry point as its caller sees it: it survives the library's own repeat of the call (sc_wait -> register_waited: a
-// second pass) and ends in count_frame.  Assigned Frame{} in frame_begin and nowhere else.
-struct Frame {
-  int fast_state = 0;            // 0 waited, 1 host-free and valid, 2 host-free, failed validation, repeated
-  bool est_failed_call = false;  // a pass of this frame saw its estimate fail (sc_debug_last: prune_bound 2); the repeat must not forget it
-  // the outstanding half of sc_register_device_async / sc_finalize_gathered_device_async (at most one per context)
-  bool pending = false;
-  bool pend_done = false; int pending_rc = 0;  // ... and it was a waited call: complete, with this status
-  bool pend_finalize = false;  // ... it is sc_finalize_gathered_device_async's (sc_wait: no repeat inside the library)
-  const float* pend_src = nullptr; const float* pend_tgt = nullptr; float* pend_Rt = nullptr; uint8_t* pend_mask = nullptr;
-  int64_t pend_n = 0; sc_params pend_p{}; sc_stats pend_stats{};
-};
-
-}  // namespace
-
-// The context.  What lives as long as it does is a direct member; the call in flight is `frame` and, inside it, `pass`.
-struct sc_ctx {
-  int device = 0;
-  hipStream_t own_stream = nullptr;
-  hipStream_t stream = nullptr;
-  std::string last_error;
-  size_t held = 0;
-  uint64_t cap_bytes = 64ull << 30;  // what ensure() holds `held` against: every entry point sets it from its sc_params
-  hipEvent_t ev[N_EVENTS] = {};
-  float ev_overhead_us = -1.f;  // cost of one event record inside a bracket (calibrate_events); < 0: not measured yet (on this stream)
-  uint64_t* pinned = nullptr;  // N_PINNED x u64 host-pinned area the kernels write results into, indexed by HostWord
-
-  // workspace (grow-only)
-  Buf in_src, in_tgt, planes, S, bits, deg, degp, wpre, ebase, edge_off, scan_tmp, ei, ej, es, ebi, ebj, tcnt, toff, wkey, kcol, ctl, events, blk_gt,
-      blk_eq, blk_minmax, bits2, off_gt, off_eq, sel_ord, sel_key, sortkey, sorted, sort_tmp, tri, tri_rk, key_rk, rt, rt_aos, partial, cnt, key, rt12,
-      mask, refine_tmp, amx_pairs, strong, rowcost, cost_pre, lb_state, lb_ticket, fx_tile, fx_state, fx_mx, fx_part, fx_coef, guard_tmp, fx_frame, ref_cand,
-      peel_planes, peel_claimed, peel_words, peel_label,  // sc_peel / sc_register_instances: allocated by the first round, never by a frame
-      // sc_match / sc_register_features: allocated by the first match, never by a frame.  part: the slices' partial lists; words: the
-      // "clean" word, the host entries' count pair, then the column minima; the rest: device copies of the host entries' arrays
-      match_part, match_words, match_fsrc, match_ftgt, match_psrc, match_ptgt, match_corr, match_d2, match_gsrc, match_gtgt;
-  // the XCD-aware block orders of stage A (compat_wg_map), one per row width met so far: a context that alternates between a few
-  // sizes must not rebuild and upload the map on every call (that cost 2 ms per call in bench.py's varying-n leg)
-  static constexpr int N_WG_MAPS = 8;
-  struct WgMap { int W = 0; uint32_t len = 0; Buf buf; uint64_t used = 0; } wg_maps[N_WG_MAPS];
-  uint64_t wg_map_clock = 0;
-  // sc_register (host arrays in, host arrays out): pinned, device-mapped staging areas — the staging kernel reads the
-  // correspondences straight from host memory and the finalize kernel writes (R, t, mask) straight into it: no copies
-  void* h_in = nullptr; size_t h_in_cap = 0;
-  void* h_out = nullptr; size_t h_out_cap = 0;
-  uint64_t ev_capacity = 1ull << 21;  // event records (32 B each); doubled after an overflow
-  Tuning tn;  // defaults unless sc_set_debug() changed them; the library reads no environment variable
-  // decoupled look-back launches (single-pass scan, fused compaction): their state area and its epoch
-  uint32_t lb_epoch = 0; void* lb_zeroed = nullptr; size_t lb_zeroed_cap = 0;
-  // run-time probe of the matrix pipe's accumulation model (sc_score.hip gram_guard): 0 not run, 1 holds, 2 violated
-  int gram_guard = 0; float gram_guard_worst = 0.f;
-
-  // ---- history: what a completed call leaves for the next one (note_completed writes it, fast_plan / room_of / edge_build_ok read it)
-  bool fast_ok = false;      // the last completed call was regular (events, a-priori window, T triangles found): the next may be enqueued host-free
-  uint64_t E_last = 0, M_last = 0;
-  int last_n = 0;
-  sc_params last_p{};
-  // r05: what the covers are sized by.  A stream of DIFFERENT frames of one shape (bench.py's: 32 scenes whose inlier ratio moves the
-  // edge count by 1.6 x and the triangle count by 4 x) outgrew "the last call's counts plus half" in a frame out of six; the covers now
-  // follow the largest counts of the last HI_WINDOW .. 2 HI_WINDOW completed calls of the shape (two buckets: the current one and the one
-  // before it), so a stream pays for the spread of its frames once.  A change of shape empties the window (note_completed).
-  static constexpr uint32_t HI_WINDOW = 64, HI_YOUNG = 8;
-  uint64_t E_hi[2] = {0, 0}, M_hi[2] = {0, 0};
-  uint32_t hi_n = 0, hi_seen = 0;  // calls in the current bucket; regular calls of this shape seen so far (saturating)
-  bool est_failed = false;   // an estimate failed on this context: it certifies for the next est_holdoff completed calls (sc_set_debug resets)
-  // r04c: not for ever.  One frame whose estimate fails — a change of scene — used to cost the context its estimating sample (25 us per
-  // C2 call) for the rest of its life; now the k-th failure costs 64 << min(k - 1, 6) certifying calls, then the context estimates
-  // again: a stream whose estimates always fail wastes one repeated call in 4096.
-  uint32_t est_holdoff = 0, est_failures = 0;
-  // the coordinate maxima and boxes the staging kernel of the last completed call published (use_filter): what a host-free call
-  // picks stage C2's kernel by when it is enqueued before its own staging kernel has run — a second frame in flight on the stream
-  uint64_t mx_last = ~0ull, box_last[6] = {0, 0, 0, 0, 0, 0};
-  // cumulative over the context's life (sc_debug_last): how its sc_register_device(_async) / host-free sc_hypothesize_device calls
-  // were enqueued and how stage B's pruning bound fared — what a stream of frames reports (a per-call field would only say the last)
-  uint64_t n_frames = 0, n_fast_ok = 0, n_fast_repeat = 0, n_est_ok = 0, n_est_fail = 0;
-  uint64_t n_spec_grow = 0;  // buffers re-allocated (a stream synchronisation each) inside host-free enqueues
-
-  Frame frame;  // the call in flight, as the caller sees it
-  Pass pass;    // ... and the library's current (or last) run through the stages for it
-};
-
-namespace {
+namespace sc {
 
 int fail_hip(sc_ctx* c, hipError_t e, const char* what) {
   char buf[256];
@@ -177,12 +27,6 @@ int fail_hip(sc_ctx* c, hipError_t e, const char* what) {
   if (c) c->last_error = buf;
   return SC_EHIP;
 }
-
-#define HIPCHK(c, expr)                                        \
-  do {                                                         \
-    hipError_t _e = (expr);                                    \
-    if (_e != hipSuccess) return fail_hip((c), _e, #expr);     \
-  } while (0)
 
 int ensure(sc_ctx* c, Buf& b, size_t bytes) {
   if (bytes <= b.cap) return SC_OK;
@@ -209,12 +53,6 @@ int ensure(sc_ctx* c, Buf& b, size_t bytes) {
   return SC_OK;
 }
 
-#define ENSURE(c, buf, bytes)                      \
-  do {                                             \
-    int _rc = ensure((c), (buf), (bytes));         \
-    if (_rc != SC_OK) return _rc;                  \
-  } while (0)
-
 // `need` bytes now, `room` bytes wanted (room for the counts of the NEXT calls of this shape: a host-free call's launches are
 // sized by a cover of the recent counts and must fit the arrays it finds — fast_plan); under a tight workspace cap: just `need`
 int ensure_room(sc_ctx* c, Buf& b, size_t need, size_t room) {
@@ -224,18 +62,12 @@ int ensure_room(sc_ctx* c, Buf& b, size_t need, size_t room) {
   }
   return ensure(c, b, need);
 }
-#define ENSURE_ROOM(c, buf, need, room)                        \
-  do {                                                         \
-    int _rc = ensure_room((c), (buf), (need), (room));         \
-    if (_rc != SC_OK) return _rc;                              \
-  } while (0)
-
 // what a host-free repetition of a call's shape is sized to cover (fast_plan): the last count plus half, and the largest count of
 // the shape's recent calls plus a quarter (sc_ctx::E_hi / M_hi)
 // While the shape is young on this context (fewer than HI_YOUNG of its calls seen) the last count is doubled instead: the first
 // frames of a stream say little about the spread of the frames to come, and a miss costs a whole repeated call (bench.py's
 // stream, frames of 386 k .. 697 k edges: with "plus half" from the first frame on, one of the first twenty was repeated).
-uint64_t cover_of(uint64_t last, const uint64_t hi[2], bool young) {
+static uint64_t cover_of(uint64_t last, const uint64_t hi[2], bool young) {
   const uint64_t h = hi[0] > hi[1] ? hi[0] : hi[1];
   const uint64_t b = h + h / 4;
   // young: twice the last count (or the window's maximum plus a quarter, if larger); later the window alone decides — the last
@@ -246,16 +78,23 @@ uint64_t cover_of(uint64_t last, const uint64_t hi[2], bool young) {
 }
 
 // entries the edge arrays hold (what fast_plan caps a host-free call's edge cover by)
-uint64_t edge_capacity(const sc_ctx* c, bool build) {
+static uint64_t edge_capacity(const sc_ctx* c, bool build) {
   uint64_t cap = c->es.cap / 4 >= 2 ? c->es.cap / 4 - 2 : 0;  // es carries two pad entries
   for (const Buf* b : {&c->ei, &c->ej}) cap = b->cap / 4 < cap ? b->cap / 4 : cap;
   if (!build) for (const Buf* b : {&c->ebi, &c->ebj}) cap = b->cap / 4 < cap ? b->cap / 4 : cap;
   return cap;
 }
-bool same_shape(const sc_params* p, const sc_params* q);
+// the parameters that make two calls "the same shape" (a host-free call repeats the last call's; timing flags aside)
+static bool same_shape(const sc_params* p, const sc_params* q) {
+  constexpr uint32_t TIMING_BITS = SC_FLAG_TIMING | SC_FLAG_TIMING_HOT | SC_FLAG_TIMING_ONE | (15u << 8);
+  return p->sigma == q->sigma && p->t_cmp == q->t_cmp && p->tau == q->tau && p->min_len == q->min_len &&
+         p->max_triangles == q->max_triangles && p->rank_mode == q->rank_mode && p->layout == q->layout &&
+         p->shard_world == q->shard_world && p->shard_rank == q->shard_rank && p->shard_block == q->shard_block &&
+         p->score_mode == q->score_mode && (p->flags & ~TIMING_BITS) == (q->flags & ~TIMING_BITS);
+}
 // entries a waited call leaves in an array indexed by one of stage B's two counts: what the host-free repetitions of its shape
 // will want to cover (the window's maxima only while the shape continues: note_completed empties it after a change)
-uint64_t room_of(const sc_ctx* c, uint64_t count, const uint64_t hi[2]) {
+static uint64_t room_of(const sc_ctx* c, uint64_t count, const uint64_t hi[2]) {
   static const uint64_t none[2] = {0, 0};
   const bool continues = c->pass.n == c->last_n && same_shape(&c->pass.params, &c->last_p);
   return cover_of(count, continues ? hi : none, !continues || c->hi_seen < sc_ctx::HI_YOUNG);
@@ -291,15 +130,17 @@ Derived derive(const sc_params* p) {
 // the select's a-priori window and the pruning samples' floors rest on.  NOT when -1 / (2 sigma^2) overflowed fp32 (sigma below 2^-64.5 =
 // 3.8e-20): (d * d) * -inf is -inf or NaN, sc_expf clamps both to its floor, every weight is e^-87 and nothing bounds the keys from below
 // (tests/test_gpu_range.py: the select then returned keys of its window, [2, 3], that no triangle has).
-float key_floor(const sc_params* p) {
+static float key_floor(const sc_params* p) {
   const float nis = (float)(-1.0 / (2.0 * (double)p->sigma * (double)p->sigma));  // derive()'s neg_inv2sig2
   return std::isfinite(nis) ? 3.0f * p->t_cmp * 0.999f : 0.0f;
 }
+// ... and whether that floor puts every key into the a-priori window [2, 3]: what the select, the estimating sample, the fused edge
+// kernel and the host-free form all go by — one answer for all of them
+static bool window_known(const sc_params* p) { return p->rank_mode == SC_RANK_WEIGHT && key_floor(p) >= 2.0f; }
 
-inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
+static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
-Points points_of(const sc_ctx* c) { return Points{c->planes.as<float>(), c->pass.n, c->pass.ld}; }
-Graph graph_of(const sc_ctx* c) {
+static Graph graph_of(const sc_ctx* c) {
   return Graph{c->pass.bits_cur, c->S.as<float>(), c->deg.as<uint32_t>(), c->degp.as<uint32_t>(),
                c->wpre.as<uint32_t>(), c->pass.n, c->pass.ld, c->pass.ld >> 6};
 }
@@ -327,18 +168,18 @@ int lb_next(sc_ctx* c, size_t bytes, int slot, size_t desc_off, LbArgs* out) {
 }
 
 // how many triangles stage B selects: T — or, when B is sharded, what one candidate blob holds (this rank's own best)
-uint32_t select_want(const sc_ctx* c, const sc_params* p) {
+static uint32_t select_want(const sc_ctx* c, const sc_params* p) {
   if (!c->pass.sharded_ab) return p->max_triangles;
   const uint32_t cap = (uint32_t)cand_cap(p->max_triangles, (uint32_t)p->shard_world, p->shard_cand_level);
   return cap < p->max_triangles ? cap : p->max_triangles;
 }
 
 // sharded stage B: the device-side edge range [lo, hi) this rank enumerates (nullptr: every edge)
-const uint64_t* own_range_of(const sc_ctx* c) {
+static const uint64_t* own_range_of(const sc_ctx* c) {
   return c->pass.sharded_ab ? c->ctl.as<ControlBlock>()->own_edge : nullptr;
 }
 
-TriSource tri_source_of(const sc_ctx* c) {
+static TriSource tri_source_of(const sc_ctx* c) {
   TriSource ts{c->sel_ord.as<uint64_t>(), c->kcol.as<uint2>(), c->ei.as<uint32_t>(), c->ej.as<uint32_t>(), nullptr, 0, 0, 0u, 0u, 0ull};
   if (c->pass.mode.host_free) { ts.lim_vertex = (uint32_t)c->pass.n; ts.lim_edge = (uint32_t)c->pass.mode.E_cov; ts.lim_ord = c->pass.mode.M_cov; }
   // an ESTIMATED pruning bound that turns out too high leaves a selection shorter than the T_eff the launches were sized for
@@ -363,11 +204,31 @@ int rec(sc_ctx* c, int i) {
   return SC_OK;
 }
 
-int calibrate_events(sc_ctx* c);
-bool fast_plan(const sc_ctx* c, int64_t n, const sc_params* p, PassMode* mode);
+// A bracket of two event records contains the cost of one record (a barrier packet with a timestamp: ~4-5 us of
+// stream time on this part) on top of what lies between them.  That cost is measured once per context — an empty
+// bracket on the idle stream — and subtracted, so that a bracket around one kernel reads like the profiler's duration
+// of that kernel (plus any genuine launch gap).
+static int calibrate_events(sc_ctx* c) {
+  if (c->ev_overhead_us >= 0.f) return SC_OK;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  float best = 1e9f;
+  for (int rep = 0; rep < 5; rep++) {
+    // a chain of back-to-back records: the first interval includes waking an idle queue, the later ones are the
+    // steady cost of a record that follows other work — which is what sits inside a stage bracket
+    for (int k = 0; k < 6; k++) HIPCHK(c, hipEventRecord(c->ev[k], c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int k = 2; k < 5; k++) {
+      float ms = 0.f;
+      if (hipEventElapsedTime(&ms, c->ev[k], c->ev[k + 1]) == hipSuccess && ms * 1000.f < best) best = ms * 1000.f;
+    }
+  }
+  c->ev_overhead_us = best < 1e8f ? best : 0.f;
+  return SC_OK;
+}
+static bool fast_plan(const sc_ctx* c, int64_t n, const sc_params* p, PassMode* mode);
 
 // SC_FLAG_TIMING / _HOT / _ONE -> the context's timing state for this call
-int set_timing(sc_ctx* c, const sc_params* p) {
+static int set_timing(sc_ctx* c, const sc_params* p) {
   c->pass.timing = (p->flags & SC_FLAG_TIMING) != 0;
   c->pass.timing_hot = !c->pass.timing && (p->flags & SC_FLAG_TIMING_HOT) != 0;
   c->pass.timing_one = -1;
@@ -449,10 +310,8 @@ int run_compat(sc_ctx* c, bool dense) {
 }
 
 // deg / deg+ / word-prefix popcounts from the bit rows (first kernel of stage B's timing bracket)
-void arm_word(sc_ctx* c, HostWord w);
-
 // hot: the fused form (row statistics + CSR offsets + edge count in one launch; run_edges then launches no scan)
-int run_row_stats(sc_ctx* c, bool will_prune, bool hot = false) {
+int run_row_stats(sc_ctx* c, bool will_prune, bool hot) {
   c->pass.rows_fused = false;
   if (hot && c->pass.build) {  // launch_edge_build (run_edges) does all of it
     ENSURE(c, c->bits2, (size_t)c->pass.n * (c->pass.ld >> 6) * sizeof(uint64_t));
@@ -477,7 +336,7 @@ int run_row_stats(sc_ctx* c, bool will_prune, bool hot = false) {
     uint64_t* cost_pre = nullptr;
     if (c->pass.sharded_ab) { ENSURE(c, c->cost_pre, (n + 1) * sizeof(uint64_t)); cost_pre = c->cost_pre.as<uint64_t>(); }
     LbArgs lb;
-    { const int lrc = lb_next(c, row_stats_scan_state_bytes(c->pass.n), 0, 0, &lb); if (lrc) return lrc; }
+    SC_TRY(lb_next(c, row_stats_scan_state_bytes(c->pass.n), 0, 0, &lb));
     arm_word(c, HW_EDGES);  // read-back #1 (the edge count) is published by this kernel
     launch_row_stats_scan(points_of(c), c->pass.bits_cur, c->deg.as<uint32_t>(), c->degp.as<uint32_t>(), c->wpre.as<uint32_t>(),
                           zero_rows, c->edge_off.as<uint64_t>(), c->ebase.as<uint32_t>(), cost_pre, lb, &c->pinned[HW_EDGES],
@@ -493,13 +352,11 @@ int run_row_stats(sc_ctx* c, bool will_prune, bool hot = false) {
 // Read-backs: the producing kernel stores its 8-byte result into host-pinned memory (publish_host) and the host
 // polls that word instead of blocking in hipStreamSynchronize (whose wake-up alone costs ~10 us, twice per call).
 // After ~1 ms of polling it falls back to the blocking wait (very long stages, or a failed launch).
-constexpr uint64_t PIN_PENDING = ~0ull;
-inline void cpu_relax() {
+static inline void cpu_relax() {
 #if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
   __builtin_ia32_pause();
 #endif
 }
-void arm_word(sc_ctx* c, HostWord w) { c->pinned[w] = PIN_PENDING; }
 int wait_word(sc_ctx* c, HostWord idx) {
   volatile uint64_t* w = &c->pinned[idx];
   const auto t0 = std::chrono::steady_clock::now();
@@ -516,14 +373,11 @@ int wait_word(sc_ctx* c, HostWord idx) {
   return SC_OK;
 }
 
-bool may_prune(const sc_params* p) { return p->rank_mode == SC_RANK_WEIGHT && !(p->flags & SC_FLAG_NO_PRUNE); }
-
 // The hot path's fused form of row_stats_scan + edge_fill + the estimating sample (sc_tri.hip 1'): where the pruning bound
 // will be an estimate (the same conditions as sample_plan's in run_edges, minus what only the edge count decides) and the
 // bit rows are short enough for the kernel
-bool edge_build_ok(const sc_ctx* c, const sc_params* p, int64_t n, bool may_estimate) {
-  const bool window_known = p->rank_mode == SC_RANK_WEIGHT && key_floor(p) >= 2.0f;
-  return may_estimate && !c->est_failed && window_known && may_prune(p) && !c->tn.no_events && !c->tn.no_estimate &&
+static bool edge_build_ok(const sc_ctx* c, const sc_params* p, int64_t n, bool may_estimate) {
+  return may_estimate && !c->est_failed && window_known(p) && may_prune(p) && !c->tn.no_events && !c->tn.no_estimate &&
          c->tn.sample_mode == 0 && !c->tn.no_edge_build && !c->tn.rows_unfused && edge_build_fits((int)n) &&  // (stage C may be dealt over ranks: shard_world)
          p->max_triangles != 0;
 }
@@ -532,7 +386,7 @@ bool edge_build_ok(const sc_ctx* c, const sc_params* p, int64_t n, bool may_esti
 // into `hist` (256 u32 on the device, already zero; nullptr = the control block's own histogram).  Sets c->pass.E and the
 // decisions the second half needs.
 // the Gram filter's frame (sc_gramref.hpp): 512 bytes per context
-int ensure_frame(sc_ctx* c) {
+static int ensure_frame(sc_ctx* c) {
   if (!c->fx_frame.p) {
     ENSURE(c, c->fx_frame, gram_frame_bytes());
     HIPCHK(c, hipMemsetAsync(c->fx_frame.p, 0, gram_frame_bytes(), c->stream));
@@ -540,7 +394,7 @@ int ensure_frame(sc_ctx* c) {
   return SC_OK;
 }
 
-int run_edges(sc_ctx* c, const sc_params* p, uint32_t* hist, uint32_t part, uint32_t parts) {
+static int run_edges(sc_ctx* c, const sc_params* p, uint32_t* hist, uint32_t part, uint32_t parts) {
   const size_t n = c->pass.n;
   hipStream_t st = c->stream;
   c->pass.ref_cand_n = 0; c->pass.ref_done = false;
@@ -558,8 +412,8 @@ int run_edges(sc_ctx* c, const sc_params* p, uint32_t* hist, uint32_t part, uint
   ScanExtra xc;  // (sharded) the scan of the row costs
   if (!fused && scan_writes_ebase(n)) {  // tiled scans: the single-pass form, each on its own half of the state area
     const size_t half = scan_temp_bytes(n);
-    { const int lrc = lb_next(c, 2 * half, 0, 0, &xe.lb); if (lrc) return lrc; }
-    if (c->pass.sharded_ab) { const int lrc = lb_next(c, 2 * half, 1, half, &xc.lb); if (lrc) return lrc; }  // (same size: the area stays)
+    SC_TRY(lb_next(c, 2 * half, 0, 0, &xe.lb));
+    if (c->pass.sharded_ab) SC_TRY(lb_next(c, 2 * half, 1, half, &xc.lb));  // (same size: the area stays)
   }
   if (c->pass.sharded_ab) {
     // also the prefix of the per-row work estimate and, from it, this rank's contiguous row / edge range
@@ -598,7 +452,7 @@ int run_edges(sc_ctx* c, const sc_params* p, uint32_t* hist, uint32_t part, uint
   const bool spec = c->pass.mode.host_free;
   const uint64_t* E_dev = spec ? c->edge_off.as<uint64_t>() + n : nullptr;
   if (!spec) {
-    { const int wrc = wait_word(c, HW_EDGES); if (wrc) return wrc; }
+    SC_TRY(wait_word(c, HW_EDGES));
     if ((uint32_t)c->pinned[HW_BAD_INPUT] != 0) { c->last_error = "non-finite input coordinate"; return SC_EINVAL; }
   }
   const uint64_t E = c->pass.E = spec ? c->pass.mode.E_cov : c->pinned[HW_EDGES];
@@ -652,12 +506,11 @@ int run_edges(sc_ctx* c, const sc_params* p, uint32_t* hist, uint32_t part, uint
     // the smallest possible weight is ~3 t_cmp (every edge has s >= t_cmp up to rounding); 0.1 % slack
     // An ESTIMATED bound where the call can be repeated should the select find it too high (sc_tri.hip 3c): the common
     // form only — event list, a-priori select window (the check rides the window's first round), the whole sample here
-    const bool window_known = p->rank_mode == SC_RANK_WEIGHT && key_floor(p) >= 2.0f;
     // (sharded, SC_FLAG_EST_BOUND: every rank takes the WHOLE sample — it is cheaper than the latency of the all-reduce that
     // would sum the ranks' shares — and the merge of the candidates verifies the bound: sc_shard_score_device)
     const bool est_local = c->pass.mode.may_estimate && !c->est_failed && hist == nullptr && parts == 1 && !c->pass.sharded_ab;
     const bool est_shard = c->pass.sharded_ab && hist != nullptr && (p->flags & SC_FLAG_EST_BOUND) != 0;
-    c->pass.plan = sample_plan(p->max_triangles, (est_local || est_shard) && c->pass.use_events && window_known, c->tn,
+    c->pass.plan = sample_plan(p->max_triangles, (est_local || est_shard) && c->pass.use_events && window_known(p), c->tn,
                           spec ? c->E_last : E, g.W);
     c->pass.est_active = c->pass.plan.estimate;
     if (build && !c->pass.plan.estimate) { c->last_error = "internal: the fused edge kernel ran but the bound is not an estimate"; return SC_EHIP; }
@@ -697,7 +550,7 @@ int run_edges(sc_ctx* c, const sc_params* p, uint32_t* hist, uint32_t part, uint
 // Two launches (count per tile; write, every tile summing the counts before it by itself).  (The ONE-launch form — counts of the
 // earlier tiles by decoupled look-back — was built as VERDICT r01 asked, bit-exact and slower: 16.4 us against 4.7 + 4.7 on C2;
 // removed in r05.)  Tuning::compact_self_max == 0 (a test) takes the scanned three-launch form.
-int run_compaction(sc_ctx* c, const KeyView& view, size_t nb, int rounds, uint64_t* host_short) {
+static int run_compaction(sc_ctx* c, const KeyView& view, size_t nb, int rounds, uint64_t* host_short) {
   hipStream_t st = c->stream;
   SelectState* sel = &c->ctl.as<ControlBlock>()->sel;
   launch_compact_count(view, sel, rounds, c->blk_gt.as<uint32_t>(), c->blk_eq.as<uint32_t>(), st, host_short);
@@ -716,7 +569,7 @@ int run_compaction(sc_ctx* c, const KeyView& view, size_t nb, int rounds, uint64
 // Stage B, second half: prune with the (summed) sample histogram, enumerate, select.  On return c->pass.M, c->pass.T_eff are set
 // and sel_ord / sel_key hold the selection.  want_list: also materialise the T x 3 triangle list (stage hook; the hot
 // path reads triangles through TriSource).  hist == nullptr: the control block's own histogram.
-int run_select(sc_ctx* c, const sc_params* p, const uint32_t* hist, bool want_list) {
+static int run_select(sc_ctx* c, const sc_params* p, const uint32_t* hist, bool want_list) {
   hipStream_t st = c->stream;
   const uint64_t E = c->pass.E;
   if (E == 0) return SC_OK;
@@ -765,8 +618,7 @@ int run_select(sc_ctx* c, const sc_params* p, const uint32_t* hist, bool want_li
                     reinterpret_cast<uint32_t*>(&c->pinned[HW_EV_OVERFLOW]));
     GramRefJob ref{};
     if (c->pass.ref_cand_n) {  // (run_edges) one extra workgroup votes for stage C2's reference frame under this launch
-      int frc = ensure_frame(c);
-      if (frc) return frc;
+      SC_TRY(ensure_frame(c));
       ref = gram_ref_job(points_of(c), c->fx_mx.as<uint32_t>(), c->pass.dv.tau2, c->tn, c->fx_frame.p);
       ref.src.cand = c->ref_cand.as<uint4>(); ref.src.n_cand = c->pass.ref_cand_n; ref.src.cand_slot = c->ctl.as<ControlBlock>()->ref_slot;
       c->pass.ref_done = true;
@@ -785,15 +637,14 @@ int run_select(sc_ctx* c, const sc_params* p, const uint32_t* hist, bool want_li
   // a host-free call on the fused edge kernel: the launches cover E edges, the graph has fewer — the scan skips the tiles beyond
   // them (the pruning kernel's workgroups there have left without writing their counts)
   if (spec && c->pass.build && !c->pass.sharded_ab) xr.range = c->ctl.as<ControlBlock>()->live_edges;
-  { const int lrc = lb_next(c, scan_temp_bytes(E), 0, 0, &xr.lb); if (lrc) return lrc; }
+  SC_TRY(lb_next(c, scan_temp_bytes(E), 0, 0, &xr.lb));
   launch_scan_u32(c->tcnt.as<uint32_t>(), E, c->toff.as<uint64_t>(), c->scan_tmp.p, c->tn, st, spec ? nullptr : &c->pinned[HW_TRIANGLES], &xr);
   // While the host polls for the count, the key kernel already runs into the key arrays this context holds from earlier
   // calls (it takes everything else from device memory).  Only in the common form — events, a-priori select window —
   // and not when every stage is bracketed by events; re-run below if the count outgrew the arrays or a region overflowed.
   SelectState* sel = &c->ctl.as<ControlBlock>()->sel;
-  const bool window_known = p->rank_mode == SC_RANK_WEIGHT && key_floor(p) >= 2.0f;
   uint64_t spec_cap = 0;
-  if (use_events && window_known && !c->pass.timing) {
+  if (use_events && window_known(p) && !c->pass.timing) {
     spec_cap = c->wkey.cap / 4 < c->kcol.cap / 8 ? c->wkey.cap / 4 : c->kcol.cap / 8;
     if (spec) spec_cap = c->pass.mode.M_cov;  // (<= that capacity: fast_plan)
     if (spec_cap) {
@@ -805,7 +656,7 @@ int run_select(sc_ctx* c, const sc_params* p, const uint32_t* hist, bool want_li
   }
   // host-free call: no wait — M is what the key arrays and the launches below cover, T_eff the requested T; the kernels
   // read the real count from toff[E] (= the scan's total: the counts of [real E, E) are zero) and sc_wait validates
-  if (!spec) { const int wrc = wait_word(c, HW_TRIANGLES); if (wrc) return wrc; }
+  if (!spec) SC_TRY(wait_word(c, HW_TRIANGLES));
   c->pass.M_total = spec ? c->pass.mode.M_cov : (have_total ? c->pinned[HW_TOTAL] : c->pinned[HW_TRIANGLES]);
   const uint64_t M = c->pass.M = spec ? c->pass.mode.M_cov : c->pinned[HW_TRIANGLES];
   if (M == 0) {
@@ -843,7 +694,7 @@ int run_select(sc_ctx* c, const sc_params* p, const uint32_t* hist, bool want_li
     c->ev_capacity = want_cap;
   }
   // weight keys of a graph whose edges all weigh >= 2/3 (0.1 % slack) lie in [2.0, 3.0]: window known a priori
-  const bool fast_window = events_ok && window_known;
+  const bool fast_window = events_ok && window_known(p);
   const bool keys_done = spec_cap != 0 && events_ok && M <= spec_cap && !key_arrays_moved;  // the speculative pass wrote every key
   if (keys_done) {
     // nothing to do
@@ -863,7 +714,7 @@ int run_select(sc_ctx* c, const sc_params* p, const uint32_t* hist, bool want_li
   // an estimated bound is verified by the first round over the a-priori window; any other path leaves it unverified
   if (c->pass.est_active && !fast_window) c->pass.est_void = true;
   launch_select_rounds(view, sel, fast_window ? 2 : 3, c->tn, st, c->pass.sharded_ab ? nullptr : &c->pinned[HW_SELECT_SHORT]);
-  { const int crc = run_compaction(c, view, nb, fast_window ? 2 : 3, c->pass.sharded_ab ? nullptr : &c->pinned[HW_SELECT_SHORT]); if (crc) return crc; }
+  SC_TRY(run_compaction(c, view, nb, fast_window ? 2 : 3, c->pass.sharded_ab ? nullptr : &c->pinned[HW_SELECT_SHORT]));
   // the list stays in ordinal order: no sort on the hot path (the winner is found by (count, key, position))
   if (want_list)
     launch_tri_decode(c->ei.as<uint32_t>(), c->ej.as<uint32_t>(), c->kcol.as<uint2>(), c->sel_ord.as<uint64_t>(), T_eff,
@@ -874,14 +725,12 @@ int run_select(sc_ctx* c, const sc_params* p, const uint32_t* hist, bool want_li
 }
 
 int run_triangles(sc_ctx* c, const sc_params* p, bool want_list) {
-  const int rc = run_edges(c, p, nullptr, 0, 1);
-  return rc ? rc : run_select(c, p, nullptr, want_list);
+  SC_TRY(run_edges(c, p, nullptr, 0, 1));
+  return run_select(c, p, nullptr, want_list);
 }
 
 void fill_stats(const sc_ctx* c, sc_stats* s) {
-  if (!s) return;
-  const uint32_t sz = s->size;
-  if (sz != sizeof(sc_stats)) return;
+  if (!s || s->size != sizeof(sc_stats)) return;
   s->n = (uint32_t)c->pass.n;
   s->edges = c->pass.E;
   s->tri_total = c->pass.M_total;
@@ -896,29 +745,7 @@ void fill_stats(const sc_ctx* c, sc_stats* s) {
                    + 52 * (uint64_t)c->pass.sh.n_local + 24 * n + n;   // C: (R,t) out and in, counts, the correspondences, the mask
 }
 
-// A bracket of two event records contains the cost of one record (a barrier packet with a timestamp: ~4-5 us of
-// stream time on this part) on top of what lies between them.  That cost is measured once per context — an empty
-// bracket on the idle stream — and subtracted, so that a bracket around one kernel reads like the profiler's duration
-// of that kernel (plus any genuine launch gap).
-int calibrate_events(sc_ctx* c) {
-  if (c->ev_overhead_us >= 0.f) return SC_OK;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  float best = 1e9f;
-  for (int rep = 0; rep < 5; rep++) {
-    // a chain of back-to-back records: the first interval includes waking an idle queue, the later ones are the
-    // steady cost of a record that follows other work — which is what sits inside a stage bracket
-    for (int k = 0; k < 6; k++) HIPCHK(c, hipEventRecord(c->ev[k], c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (int k = 2; k < 5; k++) {
-      float ms = 0.f;
-      if (hipEventElapsedTime(&ms, c->ev[k], c->ev[k + 1]) == hipSuccess && ms * 1000.f < best) best = ms * 1000.f;
-    }
-  }
-  c->ev_overhead_us = best < 1e8f ? best : 0.f;
-  return SC_OK;
-}
-
-float ev_us_raw(sc_ctx* c, int a, int b) {  // start / stop of kernel dispatches: nothing to subtract
+static float ev_us_raw(sc_ctx* c, int a, int b) {  // start / stop of kernel dispatches: nothing to subtract
   float ms = 0.f;
   if (hipEventSynchronize(c->ev[b]) != hipSuccess || hipEventElapsedTime(&ms, c->ev[a], c->ev[b]) != hipSuccess) {
     (void)hipGetLastError();
@@ -934,39 +761,33 @@ float ev_us(sc_ctx* c, int a, int b) {
   return us > 0.f ? us : 0.f;
 }
 
-int busy(sc_ctx* c) {  // an sc_register_device_async / sc_finalize_gathered_device_async call is outstanding on this context
-  if (!c->frame.pending) return SC_OK;
-  c->last_error = "a call is outstanding on this context (sc_wait first)";
-  return SC_EINVAL;
+int entry_checks(sc_ctx* c, const sc_params* p, unsigned checks) {
+  if (checks & ENDS_FRAME) peel_end(c);
+  if (checks & NOT_BUSY) SC_TRY(busy(c));
+  if (checks & PARAMS) SC_TRY(check_params(p));
+  if ((checks & ONE_RANK) && p->shard_world != 1) return SC_EINVAL;
+  return SC_OK;
 }
 
-// Any computing entry other than sc_peel* ends the frame the context may hold (include/saccot.h, sc_peel)
-void peel_end(sc_ctx* c) { c->pass.peelable = false; }
-
-// The stage hooks start no pass: they run on whatever the last one left, and clear what would change their kernels
-int host_to_planes(sc_ctx* c, const float* src, const float* tgt, int64_t n, const sc_params* p) {
-  { const int brc = busy(c); if (brc) return brc; }
-  c->pass.mode.host_free = false;  // (a host-free call that was never finalized must not leave its covers to a stage hook)
-  c->pass.mode.may_estimate = false;  // (a hook cannot repeat itself: certified bounds only)
-  c->pass.build = false;  // (stage hooks: the separate kernels)
-  c->pass.timing = c->pass.timing_hot = false; c->pass.timing_one = -1;  // (... and no event brackets)
-  c->cap_bytes = p->max_workspace ? p->max_workspace : (64ull << 30);
-  c->pass.dv = derive(p);
-  if (!src || !tgt || n < 3 || n > (1 << 24)) return SC_EINVAL;
+int points_to_device(sc_ctx* c, const float* src, const float* tgt, int64_t n) {
   ENSURE(c, c->in_src, (size_t)n * 12);
   ENSURE(c, c->in_tgt, (size_t)n * 12);
   HIPCHK(c, hipMemcpyAsync(c->in_src.p, src, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->in_tgt.p, tgt, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
-  return stage_inputs(c, c->in_src.as<float>(), c->in_tgt.as<float>(), n, p);
-}
-
-int check_flag(sc_ctx* c) {
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if ((uint32_t)c->pinned[HW_BAD_INPUT] != 0) { c->last_error = "non-finite input coordinate"; return SC_EINVAL; }
   return SC_OK;
 }
 
-}  // namespace
+int outputs_to_host(sc_ctx* c, size_t n, float R[9], float t[3], uint8_t* mask) {
+  float Rt[12];
+  HIPCHK(c, hipMemcpyAsync(Rt, c->rt12.p, 48, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(mask, c->mask.p, n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  memcpy(R, Rt, 36);
+  memcpy(t, Rt + 9, 12);
+  return SC_OK;
+}
+
+}  // namespace sc
 
 extern "C" {
 
@@ -1029,15 +850,8 @@ void sc_destroy(sc_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);  // nullptr = the default stream
-  Buf* bufs[] = {&c->in_src, &c->in_tgt, &c->planes, &c->S, &c->bits, &c->deg, &c->degp, &c->wpre, &c->ebase, &c->edge_off, &c->scan_tmp,
-                 &c->ei, &c->ej, &c->es, &c->ebi, &c->ebj, &c->tcnt, &c->toff, &c->wkey, &c->kcol, &c->ctl, &c->events, &c->blk_gt, &c->blk_eq, &c->blk_minmax, &c->bits2, &c->off_gt,
-                 &c->off_eq, &c->sel_ord, &c->sel_key, &c->sortkey, &c->sorted, &c->sort_tmp, &c->tri, &c->tri_rk, &c->key_rk, &c->rt,
-                 &c->rt_aos, &c->partial, &c->cnt, &c->key, &c->rt12, &c->mask, &c->refine_tmp, &c->amx_pairs, &c->strong, &c->rowcost, &c->cost_pre, &c->lb_state, &c->lb_ticket, &c->fx_tile, &c->fx_state, &c->fx_mx, &c->fx_part, &c->fx_coef, &c->guard_tmp, &c->fx_frame, &c->ref_cand,
-                 &c->peel_planes, &c->peel_claimed, &c->peel_words, &c->peel_label,
-                 &c->match_part, &c->match_words, &c->match_fsrc, &c->match_ftgt, &c->match_psrc, &c->match_ptgt, &c->match_corr, &c->match_d2,
-                 &c->match_gsrc, &c->match_gtgt};
   for (sc_ctx::WgMap& m : c->wg_maps) if (m.buf.p) (void)hipFree(m.buf.p);
-  for (Buf* b : bufs) if (b->p) (void)hipFree(b->p);
+  for (size_t k = 0; k < N_WORKSPACE_BUFS; k++) if (workspace_bufs(c)[k].p) (void)hipFree(workspace_bufs(c)[k].p);  // every Buf of sc::Workspace
   for (int i = 0; i < N_EVENTS; i++) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
   if (c->pinned) (void)hipHostFree(c->pinned);
   if (c->h_in) (void)hipHostFree(c->h_in);
@@ -1048,7 +862,7 @@ void sc_destroy(sc_ctx* c) {
 
 int sc_set_stream(sc_ctx* c, void* hip_stream) {
   if (!c) return SC_EINVAL;
-  { const int brc = busy(c); if (brc) return brc; }
+  SC_TRY(busy(c));
   (void)hipSetDevice(c->device);
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->ev_overhead_us = -1.f;  // event cost differs between streams: calibrate again on the next timed call
@@ -1061,7 +875,7 @@ const char* sc_last_error(const sc_ctx* c) { return c ? c->last_error.c_str() : 
 
 int sc_set_debug(sc_ctx* c, const sc_debug* d) {
   if (!c) return SC_EINVAL;
-  { const int brc = busy(c); if (brc) return brc; }
+  SC_TRY(busy(c));
   if (!d) { c->tn = Tuning(); c->fast_ok = false; c->est_failed = false; c->est_holdoff = 0; c->est_failures = 0; return SC_OK; }
   if (d->size != sizeof(sc_debug)) return SC_EINVAL;
   auto tg_ok = [](uint32_t t) { return t == 0 || t == 4 || t == 8 || t == 16 || t == 32 || t == 64; };
@@ -1135,26 +949,34 @@ int sc_debug_last(sc_ctx* c, sc_debug_info* out) {
 
 }  // extern "C" (the two halves below are internal)
 
-namespace {
+namespace sc {
+
+// An entry that continues what an earlier one began (the _end, shard and finalize entries): frame over, context free, the earlier
+// half there — `otherwise` is the refusal's text — then the device
+static int continue_pass(sc_ctx* c, bool in_order, const char* otherwise) {
+  SC_TRY(entry_checks(c, nullptr, ENDS_FRAME | NOT_BUSY));
+  if (!in_order) { c->last_error = otherwise; return SC_EINVAL; }
+  HIPCHK(c, hipSetDevice(c->device));
+  return SC_OK;
+}
 
 // A frame starts here and nowhere else: every entry point that begins a call of its own (not the library's repeat of one) comes
 // through here, and finds nothing of the previous frame
-int frame_begin(sc_ctx* c) {
-  peel_end(c);
-  const int rc = busy(c);
-  if (!rc) c->frame = Frame{};
-  return rc;
+static int frame_begin(sc_ctx* c) {
+  SC_TRY(entry_checks(c, nullptr, ENDS_FRAME | NOT_BUSY));
+  c->frame = Frame{};
+  return SC_OK;
 }
 // A pass starts here and nowhere else (hyp_begin, sc_shard_compat_device): afterwards it holds its mode, its parameters and what follows
 // from them, and "no" for everything else — no stage may assume anything an earlier pass did
-int pass_begin(sc_ctx* c, const sc_params* p, const PassMode& mode) {
-  { const int brc = busy(c); if (brc) return brc; }
+static int pass_begin(sc_ctx* c, const sc_params* p, const PassMode& mode) {
+  SC_TRY(busy(c));
   HIPCHK(c, hipSetDevice(c->device));
   c->pass = Pass{};
   c->pass.mode = mode;
-  { const int rc = set_timing(c, p); if (rc) return rc; }
+  SC_TRY(set_timing(c, p));
   c->pass.refine = (p->flags & SC_FLAG_REFINE) != 0;
-  c->cap_bytes = p->max_workspace ? p->max_workspace : (64ull << 30);
+  c->cap_bytes = workspace_cap(p);
   c->pass.dv = derive(p);
   c->pass.params = *p;
   return SC_OK;
@@ -1163,14 +985,13 @@ int pass_begin(sc_ctx* c, const sc_params* p, const PassMode& mode) {
 // A pass ends when its finalize step starts to wait (or its enqueue fails): nothing more is enqueued host-free, whichever way
 // finalize_wait is left — validated, void, failed, timed out.  ensure() and tri_source_of() read the flag, so an entry that starts no
 // pass of its own (a stage hook, a second finalize call) must not find it set.  Returns whether the pass was host-free.
-bool pass_end(sc_ctx* c) { return std::exchange(c->pass.mode.host_free, false); }
+static bool pass_end(sc_ctx* c) { return std::exchange(c->pass.mode.host_free, false); }
 
 // phase 1, first half: staging, stage A, the edge list and this process's share of the pruning sample
-int hyp_begin(sc_ctx* c, const float* d_src, const float* d_tgt, int64_t n, const sc_params* p, uint32_t* d_hist,
+static int hyp_begin(sc_ctx* c, const float* d_src, const float* d_tgt, int64_t n, const sc_params* p, uint32_t* d_hist,
               uint32_t part, uint32_t parts, const PassMode& mode) {
-  int rc = check_params(p);
-  if (rc) return rc;
-  if ((rc = pass_begin(c, p, mode))) return rc;
+  SC_TRY(check_params(p));
+  SC_TRY(pass_begin(c, p, mode));
   // SC_FLAG_EST_BOUND outside the sc_shard_* phase API: sc_hypothesize_device only (stages A and B replicated, every rank takes the
   // whole estimating sample; a shared histogram — sc_hypothesize_begin / _end_device — is a certifying sample's)
   if ((p->flags & SC_FLAG_EST_BOUND) && !(d_hist == nullptr && parts == 1 && mode.may_estimate)) {
@@ -1178,18 +999,16 @@ int hyp_begin(sc_ctx* c, const float* d_src, const float* d_tgt, int64_t n, cons
     return SC_EINVAL;
   }
   c->pass.build = d_hist == nullptr && parts == 1 && edge_build_ok(c, p, n, mode.may_estimate);
-  if ((rc = rec(c, 0))) return rc;
-  if ((rc = stage_inputs(c, d_src, d_tgt, n, p))) return rc;
-  if ((rc = rec(c, 1))) return rc;
-  if ((rc = run_compat(c, !(p->flags & SC_FLAG_NO_DENSE_S)))) return rc;
-  if ((rc = rec(c, 2))) return rc;
-  if ((rc = run_row_stats(c, may_prune(p), true))) return rc;
-  if ((rc = run_edges(c, p, d_hist, part, parts))) return rc;
+  SC_TRY(rec(c, 0));
+  SC_TRY(stage_inputs(c, d_src, d_tgt, n, p));
+  SC_TRY(rec(c, 1));
+  SC_TRY(run_compat(c, !(p->flags & SC_FLAG_NO_DENSE_S)));
+  SC_TRY(rec(c, 2));
+  SC_TRY(run_row_stats(c, may_prune(p), true));
+  SC_TRY(run_edges(c, p, d_hist, part, parts));
   c->pass.begun = true;
   return SC_OK;
 }
-
-int run_stage_c(sc_ctx* c, uint64_t* d_key, sc_stats* stats);
 
 // C2: the counts of this shard's hypotheses into c->partial; *rows: rows of c->partial the arg-max has to add up.
 // SC_SCORE_COUNT runs the matrix-pipe filter + the exact fix-up (sc_score.hip); the truncated scores, and
@@ -1207,14 +1026,14 @@ int run_stage_c(sc_ctx* c, uint64_t* d_key, sc_stats* stats);
 // acquire semantics and the boxes only afterwards (the fence used to sit behind both loads, which only the
 // load order of x86 made right)
 struct CoordStats { uint64_t mx, box[6]; };
-CoordStats read_coord_stats(const sc_ctx* c) {
+static CoordStats read_coord_stats(const sc_ctx* c) {
   CoordStats cs;
   cs.mx = __atomic_load_n(&c->pinned[HW_COORD_MAX], __ATOMIC_ACQUIRE);
   for (int k = 0; k < 6; k++) cs.box[k] = *const_cast<volatile uint64_t*>(&c->pinned[HW_BOX + k]);
   return cs;
 }
 // ... and what stage C2's kernel is picked by: nothing when blind, else those — or the last completed call's
-CoordStats filter_stats(const sc_ctx* c) {
+static CoordStats filter_stats(const sc_ctx* c) {
   CoordStats cs = read_coord_stats(c);
   if (c->tn.filter_blind) { cs.mx = ~0ull; return cs; }
   // A host-free call enqueued while the previous frame still runs (sc_register_device_async on a second context of the stream)
@@ -1227,13 +1046,13 @@ CoordStats filter_stats(const sc_ctx* c) {
   }
   return cs;
 }
-int use_filter(const sc_ctx* c, const sc_params* p, const Shard& sh) {
+static int use_filter(const sc_ctx* c, const sc_params* p, const Shard& sh) {
   const CoordStats cs = filter_stats(c);
   return score_filter_mode(p->score_mode, c->tn, c->pass.n, sh.ld_local, cs.mx, cs.mx == ~0ull ? nullptr : cs.box, c->pass.dv.tau2);
 }
 // The Gram filter's bound rests on a measured model of the matrix pipe (sc_score.hip, gram_guard_kernel): probe the pipe this
 // context runs on, once, the first time a call would choose that filter.  0 not run, 1 the model holds, 2 violated.
-int run_gram_guard(sc_ctx* c) {
+static int run_gram_guard(sc_ctx* c) {
   if (c->gram_guard != 0) return SC_OK;
   ENSURE(c, c->guard_tmp, 64);
   float worst = 0.f; bool sub_ok = false; uint32_t compared = 0;
@@ -1246,8 +1065,7 @@ int run_gram_guard(sc_ctx* c) {
 int decide_filter(sc_ctx* c, const sc_params* p, const Shard& sh) {
   c->pass.filter_mode = use_filter(c, p, sh);
   if (c->pass.filter_mode == 2) {
-    const int rc = run_gram_guard(c);
-    if (rc) return rc;
+    SC_TRY(run_gram_guard(c));
     if (c->gram_guard == 2 || c->tn.gram_guard_fail) {
       // this pipe does not add the way the Gram bound assumes (or a test says so): the linear filter, whose bound allows a
       // truncating accumulation, where tau is on its scale; the plain kernel otherwise
@@ -1263,27 +1081,26 @@ int decide_filter(sc_ctx* c, const sc_params* p, const Shard& sh) {
 }
 
 // the filter's buffers for this shard, and the job that fills the tile / clears the state
-int filter_job(sc_ctx* c, const Shard& sh, FilterTileJob* job) {
+static int filter_job(sc_ctx* c, const Shard& sh, FilterTileJob* job) {
   const FilterPlan& fp = c->pass.fx_plan;
   ENSURE(c, c->fx_tile, fp.tile_bytes);
   ENSURE(c, c->fx_state, fp.state_bytes);
   if (fp.coef_bytes) ENSURE(c, c->fx_coef, fp.coef_bytes);
   uint32_t* mx = c->fx_mx.as<uint32_t>();
-  if (fp.mode == 2) { const int frc = ensure_frame(c); if (frc) return frc; }
+  if (fp.mode == 2) SC_TRY(ensure_frame(c));
   *job = filter_tile_job(fp, mx, nullptr, c->fx_tile.p, c->fx_state.p, c->fx_coef.p, sh.ld_local, c->pass.dv.tau2, c->fx_frame.p);
   return SC_OK;
 }
 
-int run_score(sc_ctx* c, const sc_params* p, const Shard& sh, uint32_t* rows, bool tile_done, hipEvent_t ev0 = nullptr,
-              hipEvent_t ev1 = nullptr, hipEvent_t ev_mid = nullptr) {
+int run_score(sc_ctx* c, const sc_params* p, const Shard& sh, uint32_t* rows, bool tile_done, hipEvent_t ev0, hipEvent_t ev1,
+              hipEvent_t ev_mid) {
   if (c->pass.filter_on) {  // decide_filter() ran earlier in this call
     const FilterPlan& fp = c->pass.fx_plan;
     *rows = fp.splits;
     ENSURE(c, c->partial, (size_t)fp.splits * sh.ld_local * 4);
     if (!tile_done) {  // (the stage hook; the path builds the tile inside the Kabsch launch)
       FilterTileJob job;
-      int rc = filter_job(c, sh, &job);
-      if (rc) return rc;
+      SC_TRY(filter_job(c, sh, &job));
       if (fp.mode == 2)  // the frame first: tile and coefficients are made in it (the hypotheses exist already: it votes among them)
         launch_gram_ref(points_of(c), TriSource{}, sh, c->rt.as<float>(), nullptr, c->fx_mx.as<uint32_t>(), c->pass.dv.tau2, c->tn,
                         c->fx_frame.p, c->stream);
@@ -1301,20 +1118,10 @@ int run_score(sc_ctx* c, const sc_params* p, const Shard& sh, uint32_t* rows, bo
   return SC_OK;
 }
 
-// phase 1, second half: prune with the (summed) histogram, enumerate, select, then stage C on this rank's share
-int hyp_end(sc_ctx* c, const uint32_t* d_hist, uint64_t* d_key, sc_stats* stats) {
-  const sc_params* p = &c->pass.params;
-  int rc;
-  c->pass.begun = false;
-  if ((rc = run_select(c, p, d_hist, false))) return rc;
-  return run_stage_c(c, d_key, stats);
-}
-
 // stage C on this rank's blocks of the (replicated) selection: C1, C2, arg-max key pair -> d_key
-int run_stage_c(sc_ctx* c, uint64_t* d_key, sc_stats* stats) {
+static int run_stage_c(sc_ctx* c, uint64_t* d_key, sc_stats* stats) {
   const sc_params* p = &c->pass.params;
-  int rc;
-  if ((rc = rec(c, 3))) return rc;
+  SC_TRY(rec(c, 3));
   Shard sh;
   sh.T_eff = c->pass.T_eff;
   sh.block = p->shard_block ? p->shard_block : 1024u;
@@ -1326,12 +1133,12 @@ int run_stage_c(sc_ctx* c, uint64_t* d_key, sc_stats* stats) {
   if (sh.n_local) {
     ENSURE(c, c->rt, (size_t)12 * sh.ld_local * 4);
     ENSURE(c, c->cnt, (size_t)sh.ld_local * 4);
-    if ((rc = decide_filter(c, p, sh))) return rc;
+    SC_TRY(decide_filter(c, p, sh));
     const bool filter = c->pass.filter_on;
     const bool aos = filter;  // (the exact pass reads 12 consecutive floats per hypothesis)
     if (aos) ENSURE(c, c->rt_aos, (size_t)12 * sh.ld_local * 4);
     FilterTileJob job;
-    if (filter && (rc = filter_job(c, sh, &job))) return rc;
+    if (filter) SC_TRY(filter_job(c, sh, &job));
     // host-free call: the selection may turn out shorter than the T this launch was sized for (then the call is repeated);
     // its real length is what the select left in sel.want
     const uint64_t* t_eff_dev = (c->pass.mode.host_free || c->pass.est_active) ? &c->ctl.as<ControlBlock>()->sel.want : nullptr;
@@ -1347,10 +1154,10 @@ int run_stage_c(sc_ctx* c, uint64_t* d_key, sc_stats* stats) {
   // the two records of a bracket opened ~4.5 us gaps before and after the stage — 3 % of a C2 step)
   const bool hot_ext = c->pass.timing_hot && sh.n_local != 0;
   c->pass.hot_ext = hot_ext;
-  if (!hot_ext && (rc = rec(c, 4))) return rc;
+  if (!hot_ext) SC_TRY(rec(c, 4));
   uint32_t score_rows = 0;
-  if ((rc = run_score(c, p, sh, &score_rows, true, hot_ext ? c->ev[4] : nullptr, hot_ext ? c->ev[5] : nullptr, hot_ext ? c->ev[11] : nullptr))) return rc;
-  if (!hot_ext && (rc = rec(c, 5))) return rc;
+  SC_TRY(run_score(c, p, sh, &score_rows, true, hot_ext ? c->ev[4] : nullptr, hot_ext ? c->ev[5] : nullptr, hot_ext ? c->ev[11] : nullptr));
+  if (!hot_ext) SC_TRY(rec(c, 5));
   ENSURE(c, c->amx_pairs, argmax_scratch_bytes(sh.ld_local));
   // the winner pair: reduced by the launch for a caller that gathers it; left as one pair per workgroup for this context's own
   // finalize step (sc_register*: d_key is the context's own word), whose workgroups reduce them themselves
@@ -1358,14 +1165,22 @@ int run_stage_c(sc_ctx* c, uint64_t* d_key, sc_stats* stats) {
   c->pass.amx_blocks = own_pairs ? argmax_blocks(sh.ld_local) : 0u;
   launch_argmax(sh, c->partial.as<uint32_t>(), score_rows, c->pass.T_eff ? c->sel_key.as<uint32_t>() : nullptr,
                 c->cnt.as<uint32_t>(), c->amx_pairs.as<uint64_t>(), &c->ctl.as<ControlBlock>()->amx_ticket, own_pairs ? nullptr : d_key, c->stream);
-  if ((rc = rec(c, 6))) return rc;
+  SC_TRY(rec(c, 6));
   HIPCHK(c, hipGetLastError());
   c->pass.have_hyp = true;
   fill_stats(c, stats);  // counts only: the event times are read by sc_finalize_device, after ITS synchronisation
   return SC_OK;
 }
 
-}  // namespace
+// phase 1, second half: prune with the (summed) histogram, enumerate, select, then stage C on this rank's share
+static int hyp_end(sc_ctx* c, const uint32_t* d_hist, uint64_t* d_key, sc_stats* stats) {
+  const sc_params* p = &c->pass.params;
+  c->pass.begun = false;
+  SC_TRY(run_select(c, p, d_hist, false));
+  return run_stage_c(c, d_key, stats);
+}
+
+}  // namespace sc
 
 extern "C" {
 
@@ -1376,7 +1191,7 @@ int sc_hypothesize_device(sc_ctx* c, const float* d_src, const float* d_tgt, int
   // sc_finalize(_gathered)_device returns SC_EBOUND when it was too high (on every rank of a job alike: stages A and B are
   // replicated and deterministic): the caller repeats both calls without the flag
   const bool est = p && p->size == sizeof(sc_params) && (p->flags & SC_FLAG_EST_BOUND) != 0;
-  { const int frc = frame_begin(c); if (frc) return frc; }
+  SC_TRY(frame_begin(c));
   // r04c: with the flag, a call that repeats the last call's shape on this context is enqueued HOST-FREE, as sc_register_device's
   // is (fast_plan): no wait for stage B's two counts — the rank's host thread is free to enqueue the job's next frame.  The
   // finalize call validates; a count that outgrew what the launches covered comes back as SC_EBOUND too ("repeat both calls
@@ -1393,9 +1208,8 @@ int sc_hypothesize_device(sc_ctx* c, const float* d_src, const float* d_tgt, int
 
 int sc_hypothesize_begin_device(sc_ctx* c, const float* d_src, const float* d_tgt, int64_t n, const sc_params* p,
                                 uint32_t* d_hist, sc_stats* stats) {
-  if (!c || !d_src || !d_tgt || !d_hist) return SC_EINVAL;
-  if (!p || p->size != sizeof(sc_params)) return SC_EINVAL;
-  { const int frc = frame_begin(c); if (frc) return frc; }
+  if (!c || !d_src || !d_tgt || !d_hist || !p || p->size != sizeof(sc_params)) return SC_EINVAL;
+  SC_TRY(frame_begin(c));
   const int rc = hyp_begin(c, d_src, d_tgt, n, p, d_hist, (uint32_t)p->shard_rank, (uint32_t)p->shard_world, PassMode{});
   if (rc == SC_OK) fill_stats(c, stats);
   return rc;
@@ -1403,10 +1217,7 @@ int sc_hypothesize_begin_device(sc_ctx* c, const float* d_src, const float* d_tg
 
 int sc_hypothesize_end_device(sc_ctx* c, const uint32_t* d_hist, uint64_t* d_key, sc_stats* stats) {
   if (!c || !d_hist || !d_key) return SC_EINVAL;
-  peel_end(c);
-  { const int brc = busy(c); if (brc) return brc; }
-  if (!c->pass.begun) { c->last_error = "sc_hypothesize_end_device without a preceding sc_hypothesize_begin_device"; return SC_EINVAL; }
-  HIPCHK(c, hipSetDevice(c->device));
+  SC_TRY(continue_pass(c, c->pass.begun, "sc_hypothesize_end_device without a preceding sc_hypothesize_begin_device"));
   return hyp_end(c, d_hist, d_key, stats);
 }
 
@@ -1414,8 +1225,7 @@ int sc_hypothesize_end_device(sc_ctx* c, const uint32_t* d_hist, uint64_t* d_key
 
 int sc_shard_plan_query(const sc_params* p, int64_t n, sc_shard_plan* out) {
   if (!out || out->size != sizeof(sc_shard_plan)) return SC_EINVAL;
-  const int rc = check_params(p);
-  if (rc) return rc;
+  SC_TRY(check_params(p));
   if (n < 3 || n > (1 << 24) || p->shard_world > 64) return SC_EINVAL;
   const uint64_t ld = (uint64_t)round_up((int)n, 64), W = ld >> 6, G = (uint64_t)p->shard_world;
   const uint64_t R = (((uint64_t)n + G - 1) / G + 63) / 64 * 64;  // rows per rank, a multiple of the tile block
@@ -1430,16 +1240,15 @@ int sc_shard_plan_query(const sc_params* p, int64_t n, sc_shard_plan* out) {
 int sc_shard_compat_device(sc_ctx* c, const float* d_src, const float* d_tgt, int64_t n, const sc_params* p,
                            void* d_bits_all) {
   if (!c || !d_src || !d_tgt || !d_bits_all) return SC_EINVAL;
-  int rc = check_params(p);
-  if (rc) return rc;
+  SC_TRY(check_params(p));
   if (p->shard_world > 64) return SC_EINVAL;
-  if ((rc = frame_begin(c))) return rc;
-  if ((rc = pass_begin(c, p, PassMode{}))) return rc;  // (waited, certified bounds, the separate kernels)
-  if ((rc = rec(c, 0))) return rc;
-  if ((rc = stage_inputs(c, d_src, d_tgt, n, p))) return rc;
-  if ((rc = rec(c, 1))) return rc;
+  SC_TRY(frame_begin(c));
+  SC_TRY(pass_begin(c, p, PassMode{}));  // (waited, certified bounds, the separate kernels)
+  SC_TRY(rec(c, 0));
+  SC_TRY(stage_inputs(c, d_src, d_tgt, n, p));
+  SC_TRY(rec(c, 1));
   sc_shard_plan plan; plan.size = sizeof plan;
-  if ((rc = sc_shard_plan_query(p, n, &plan))) return rc;
+  SC_TRY(sc_shard_plan_query(p, n, &plan));
   const int R = (int)plan.rows_per_rank;
   const int r0 = p->shard_rank * R < c->pass.n ? p->shard_rank * R : c->pass.n, r1 = r0 + R < c->pass.n ? r0 + R : c->pass.n;
   const size_t W = (size_t)c->pass.ld >> 6;
@@ -1452,7 +1261,7 @@ int sc_shard_compat_device(sc_ctx* c, const float* d_src, const float* d_tgt, in
   c->pass.sharded_ab = true;
   // world == 1: [0, n) -> the symmetric tiles; else the one-sided row-block form, bit rows at their global index
   launch_compat(points_of(c), c->pass.dv, dense ? c->S.as<float>() : nullptr, c->pass.bits_cur, r0, r1, c->tn, c->stream);
-  if ((rc = rec(c, 2))) return rc;
+  SC_TRY(rec(c, 2));
   HIPCHK(c, hipGetLastError());
   c->pass.shard_phase = 1;
   return SC_OK;
@@ -1460,29 +1269,21 @@ int sc_shard_compat_device(sc_ctx* c, const float* d_src, const float* d_tgt, in
 
 int sc_shard_edges_device(sc_ctx* c, uint32_t* d_hist) {
   if (!c || !d_hist) return SC_EINVAL;
-  peel_end(c);
-  { const int brc = busy(c); if (brc) return brc; }
-  if (!c->pass.sharded_ab || c->pass.shard_phase != 1) { c->last_error = "sc_shard_edges_device: call sc_shard_compat_device first"; return SC_EINVAL; }
-  HIPCHK(c, hipSetDevice(c->device));
+  SC_TRY(continue_pass(c, c->pass.sharded_ab && c->pass.shard_phase == 1, "sc_shard_edges_device: call sc_shard_compat_device first"));
   const sc_params* p = &c->pass.params;
   c->pass.shard_phase = 0;
-  int rc;
-  if ((rc = run_row_stats(c, may_prune(p), true))) return rc;
-  if ((rc = run_edges(c, p, d_hist, (uint32_t)p->shard_rank, (uint32_t)p->shard_world))) return rc;
+  SC_TRY(run_row_stats(c, may_prune(p), true));
+  SC_TRY(run_edges(c, p, d_hist, (uint32_t)p->shard_rank, (uint32_t)p->shard_world));
   c->pass.shard_phase = 2;
   return SC_OK;
 }
 
 int sc_shard_select_device(sc_ctx* c, const uint32_t* d_hist, void* d_cand_mine) {
   if (!c || !d_hist || !d_cand_mine) return SC_EINVAL;
-  peel_end(c);
-  { const int brc = busy(c); if (brc) return brc; }
-  if (!c->pass.sharded_ab || c->pass.shard_phase != 2) { c->last_error = "sc_shard_select_device: call sc_shard_edges_device first"; return SC_EINVAL; }
-  HIPCHK(c, hipSetDevice(c->device));
+  SC_TRY(continue_pass(c, c->pass.sharded_ab && c->pass.shard_phase == 2, "sc_shard_select_device: call sc_shard_edges_device first"));
   const sc_params* p = &c->pass.params;
   c->pass.shard_phase = 0;
-  int rc;
-  if ((rc = run_select(c, p, d_hist, false))) return rc;   // this rank's own top-T, in (i,j,k) order
+  SC_TRY(run_select(c, p, d_hist, false));   // this rank's own top-T, in (i,j,k) order
   const CandBlob b = cand_blob(d_cand_mine, cand_cap(p->max_triangles, (uint32_t)p->shard_world, p->shard_cand_level));
   if (c->pass.M == 0) {  // nothing enumerated here (also E == 0): an empty blob
     HIPCHK(c, hipMemsetAsync(b.hdr, 0, CAND_HDR_WORDS * 8, c->stream));
@@ -1499,10 +1300,7 @@ int sc_shard_select_device(sc_ctx* c, const uint32_t* d_hist, void* d_cand_mine)
 
 int sc_shard_score_device(sc_ctx* c, const void* d_cand_all, uint64_t* d_key, sc_stats* stats) {
   if (!c || !d_cand_all || !d_key) return SC_EINVAL;
-  peel_end(c);
-  { const int brc = busy(c); if (brc) return brc; }
-  if (!c->pass.sharded_ab || c->pass.shard_phase != 3) { c->last_error = "sc_shard_score_device: call sc_shard_select_device first"; return SC_EINVAL; }
-  HIPCHK(c, hipSetDevice(c->device));
+  SC_TRY(continue_pass(c, c->pass.sharded_ab && c->pass.shard_phase == 3, "sc_shard_score_device: call sc_shard_select_device first"));
   const sc_params* p = &c->pass.params;
   c->pass.shard_phase = 0;
   hipStream_t st = c->stream;
@@ -1513,7 +1311,6 @@ int sc_shard_score_device(sc_ctx* c, const void* d_cand_all, uint64_t* d_key, sc
   // Merge: the same exact select + (i,j,k)-order compaction as on one GPU, over the concatenated candidate keys.
   ControlBlock* ctl = c->ctl.as<ControlBlock>();
   SelectState* sel = &ctl->sel;
-  const bool window_known = p->rank_mode == SC_RANK_WEIGHT && key_floor(p) >= 2.0f;
   const KeyView view = cand_view(d_cand_all, blob_bytes, G, cap);
   const size_t nb = compact_blocks(view.M);
   ENSURE(c, c->blk_gt, nb * 4);
@@ -1525,14 +1322,14 @@ int sc_shard_score_device(sc_ctx* c, const void* d_cand_all, uint64_t* d_key, sc
   ENSURE(c, c->sel_key, (size_t)T * 4);
   arm_word(c, HW_MERGED_T);
   c->pinned[HW_MERGE_SHORT] = 0;  // "an estimated bound promised T keys above it and the merged candidates hold fewer" (merge_prepare_kernel)
-  launch_merge_prepare(d_cand_all, blob_bytes, G, T, window_known, &ctl->klb, sel, &c->pinned[HW_MERGED_T], st,
+  launch_merge_prepare(d_cand_all, blob_bytes, G, T, window_known(p), &ctl->klb, sel, &c->pinned[HW_MERGED_T], st,
                        c->pass.est_active ? &c->pinned[HW_MERGE_SHORT] : nullptr);
-  launch_select_rounds(view, sel, window_known ? 2 : 3, c->tn, st);
+  launch_select_rounds(view, sel, window_known(p) ? 2 : 3, c->tn, st);
   c->pinned[HW_CAND_CUT] = 0;  // "a cut candidate list could have mattered": read by the finalize call (SC_ERETRY)
-  { const int crc = run_compaction(c, view, nb, window_known ? 2 : 3, nullptr); if (crc) return crc; }
+  SC_TRY(run_compaction(c, view, nb, window_known(p) ? 2 : 3, nullptr));
   launch_merge_check(d_cand_all, blob_bytes, G, sel, &c->pinned[HW_CAND_CUT], st);  // (behind the compaction: its counting kernel is what resolves the last round into k*)
   // the merged length, published by merge_prepare long before the compaction ends: the poll costs no GPU time
-  { const int wrc = wait_word(c, HW_MERGED_T); if (wrc) return wrc; }
+  SC_TRY(wait_word(c, HW_MERGED_T));
   c->pass.T_eff = (uint32_t)c->pinned[HW_MERGED_T];
   c->pass.M = c->pass.M_total = c->pinned[HW_MERGED_M];
   return run_stage_c(c, d_key, stats);
@@ -1544,14 +1341,13 @@ int sc_finalize_device(sc_ctx* c, const uint64_t* d_key, float* d_Rt, uint8_t* d
 
 }  // extern "C" (the halves of the finalize step and the host-free machinery are internal)
 
-namespace {
+namespace sc {
 
 constexpr int SC_ESPEC = -100;  // internal: a host-free call failed validation (never leaves the library)
 
 // phase 2, first half: the winner / mask kernel (and the optional refit) are enqueued; nothing is waited for
-int finalize_enqueue(sc_ctx* c, const uint64_t* d_keys, int n_pairs, float* d_Rt, uint8_t* d_mask) {
-  int rc;
-  if ((rc = rec(c, 7))) return rc;
+static int finalize_enqueue(sc_ctx* c, const uint64_t* d_keys, int n_pairs, float* d_Rt, uint8_t* d_mask) {
+  SC_TRY(rec(c, 7));
   ControlBlock* ctl = c->ctl.as<ControlBlock>();
   arm_word(c, HW_WINNER);
   // a host-free call's kernels have published nothing yet: this one hands the counts and the coordinate statistics over with the winner
@@ -1569,17 +1365,8 @@ int finalize_enqueue(sc_ctx* c, const uint64_t* d_keys, int n_pairs, float* d_Rt
   return rec(c, 8);
 }
 
-// the parameters that make two calls "the same shape" (a host-free call repeats the last call's; timing flags aside)
-bool same_shape(const sc_params* p, const sc_params* q) {
-  constexpr uint32_t TIMING_BITS = SC_FLAG_TIMING | SC_FLAG_TIMING_HOT | SC_FLAG_TIMING_ONE | (15u << 8);
-  return p->sigma == q->sigma && p->t_cmp == q->t_cmp && p->tau == q->tau && p->min_len == q->min_len &&
-         p->max_triangles == q->max_triangles && p->rank_mode == q->rank_mode && p->layout == q->layout &&
-         p->shard_world == q->shard_world && p->shard_rank == q->shard_rank && p->shard_block == q->shard_block &&
-         p->score_mode == q->score_mode && (p->flags & ~TIMING_BITS) == (q->flags & ~TIMING_BITS);
-}
-
 // what the next call on this context may assume (fast_plan): the call that just completed was a "regular" one
-void note_completed(sc_ctx* c, bool regular) {
+static void note_completed(sc_ctx* c, bool regular) {
   c->fast_ok = regular && !c->pass.sharded_ab && c->pass.E >= 4096 && c->pass.T_eff == c->pass.params.max_triangles;  // (stages A and B whole on this GPU: one rank, or replicated ranks)
   if (c->pass.n != c->last_n || !same_shape(&c->pass.params, &c->last_p)) { c->E_hi[0] = c->E_hi[1] = c->M_hi[0] = c->M_hi[1] = 0; c->hi_n = 0; c->hi_seen = 0; }
   if (c->fast_ok) {  // (the counts of a regular call of this shape: what a host-free repetition has to cover)
@@ -1604,15 +1391,14 @@ void note_completed(sc_ctx* c, bool regular) {
 }
 
 // phase 2, second half: wait for the winner; a host-free call is validated here
-int finalize_wait(sc_ctx* c, sc_stats* stats) {
-  int rc;
+static int finalize_wait(sc_ctx* c, sc_stats* stats) {
   // The finalize kernel publishes key / position / rank.  On a caller-provided stream (sc_set_stream) d_Rt and d_mask
   // are complete in stream order, like any other work the caller enqueues there; on the context's private stream —
   // which the caller cannot order against — and when the per-stage events are read below, wait for everything.
   const bool was_spec = pass_end(c);
   if (c->pass.timing || c->stream == c->own_stream) HIPCHK(c, hipStreamSynchronize(c->stream));
   else if (c->pass.timing_one == 6) HIPCHK(c, hipEventSynchronize(c->ev[8]));  // the mask bracket ends after the kernel polled below
-  if ((rc = wait_word(c, HW_WINNER))) { c->fast_ok = false; return rc; }
+  if (const int rc = wait_word(c, HW_WINNER)) { c->fast_ok = false; return rc; }
   HIPCHK(c, hipGetLastError());
   if (was_spec) {
     // Host-free call: every kernel of it has finished (the winner word is the last thing the stream writes), so the two
@@ -1705,11 +1491,11 @@ int finalize_wait(sc_ctx* c, sc_stats* stats) {
 
 // May this call be enqueued host-free?  Only a repetition of the last call's shape on this context, and only when that call
 // was regular (note_completed); sets what the launches cover: the last counts plus half, within what the arrays hold.
-bool fast_plan(const sc_ctx* c, int64_t n, const sc_params* p, PassMode* mode) {
+static bool fast_plan(const sc_ctx* c, int64_t n, const sc_params* p, PassMode* mode) {
   if (!c->fast_ok || c->tn.no_fast || c->tn.no_events || n != c->last_n) return false;
   if (p->flags & (SC_FLAG_TIMING | SC_FLAG_EXACT_TOTAL | SC_FLAG_NO_PRUNE)) return false;
   if (!same_shape(p, &c->last_p)) return false;
-  if (!(p->rank_mode == SC_RANK_WEIGHT && key_floor(p) >= 2.0f)) return false;  // the a-priori select window
+  if (!window_known(p)) return false;  // the a-priori select window
   const uint64_t ecap = edge_capacity(c, edge_build_ok(c, p, n, true));  // (every entry point that comes here may estimate; the fused edge kernel writes no per-edge bases)
   const uint64_t kcap = c->wkey.cap / 4 < c->kcol.cap / 8 ? c->wkey.cap / 4 : c->kcol.cap / 8;
   // the last call's counts plus half, and the largest counts of the shape's recent calls plus a quarter (sc_ctx::E_hi)
@@ -1725,7 +1511,7 @@ bool fast_plan(const sc_ctx* c, int64_t n, const sc_params* p, PassMode* mode) {
 // the whole path the waiting way (what sc_register_device always did): complete on return.  The only caller of the phases
 // that may prune by an ESTIMATED bound (it can repeat the call): a failed estimate comes back as SC_ESPEC from finalize_wait
 // and has switched estimating off for this context, so the second pass certifies.
-int register_waited(sc_ctx* c, const float* d_src, const float* d_tgt, int64_t n, const sc_params* p, float* d_Rt,
+static int register_waited(sc_ctx* c, const float* d_src, const float* d_tgt, int64_t n, const sc_params* p, float* d_Rt,
                     uint8_t* d_mask, sc_stats* stats) {
   int rc = SC_OK;
   for (int pass = 0; pass < 2; pass++) {
@@ -1741,7 +1527,7 @@ int register_waited(sc_ctx* c, const float* d_src, const float* d_tgt, int64_t n
   return SC_EHIP;
 }
 
-}  // namespace
+}  // namespace sc
 
 extern "C" {
 
@@ -1765,25 +1551,20 @@ static int finalize_status(sc_ctx* c, int rc) {
 // the finalize call's two forms: arguments, a free context, a hypothesize half to finalize; then the winner / mask kernel is enqueued
 static int finalize_begin(sc_ctx* c, const uint64_t* d_keys, int n_pairs, float* d_Rt, uint8_t* d_mask) {
   if (!c || !d_keys || !d_Rt || !d_mask || n_pairs < 1 || n_pairs > 4096) return SC_EINVAL;
-  peel_end(c);
-  { const int brc = busy(c); if (brc) return brc; }
-  if (!c->pass.have_hyp) { c->last_error = "sc_finalize_device without a preceding sc_hypothesize_device"; return SC_EINVAL; }
-  HIPCHK(c, hipSetDevice(c->device));
+  SC_TRY(continue_pass(c, c->pass.have_hyp, "sc_finalize_device without a preceding sc_hypothesize_device"));
   return finalize_enqueue(c, d_keys, n_pairs, d_Rt, d_mask);
 }
 
 int sc_finalize_gathered_device(sc_ctx* c, const uint64_t* d_keys, int n_pairs, float* d_Rt, uint8_t* d_mask,
                                 sc_stats* stats) {
-  int rc = finalize_begin(c, d_keys, n_pairs, d_Rt, d_mask);
-  if (rc) return rc;
-  rc = finalize_status(c, finalize_wait(c, stats));
+  SC_TRY(finalize_begin(c, d_keys, n_pairs, d_Rt, d_mask));
+  const int rc = finalize_status(c, finalize_wait(c, stats));
   count_frame(c, rc);
   return rc;
 }
 
 int sc_finalize_gathered_device_async(sc_ctx* c, const uint64_t* d_keys, int n_pairs, float* d_Rt, uint8_t* d_mask) {
-  const int rc = finalize_begin(c, d_keys, n_pairs, d_Rt, d_mask);
-  if (rc) return rc;
+  SC_TRY(finalize_begin(c, d_keys, n_pairs, d_Rt, d_mask));
   c->frame.pend_stats = sc_stats{};
   c->frame.pend_stats.size = sizeof(sc_stats);
   c->frame.pending = true; c->frame.pend_done = false; c->frame.pend_finalize = true;
@@ -1795,18 +1576,16 @@ int sc_register_device_async(sc_ctx* c, const float* d_src, const float* d_tgt, 
   if (!c || !d_src || !d_tgt || !d_Rt || !d_mask) return SC_EINVAL;
   peel_end(c);
   if (c->frame.pending) { c->last_error = "sc_register_device_async: a call is already outstanding on this context (sc_wait first)"; return SC_EINVAL; }
-  int rc = check_params(p);
-  if (rc) return rc;
-  if (p->shard_world != 1) return SC_EINVAL;
+  SC_TRY(entry_checks(c, p, PARAMS | ONE_RANK));  // (the frame ended above; "busy" has this entry's own text)
   HIPCHK(c, hipSetDevice(c->device));
   ENSURE(c, c->key, 64);
-  if ((rc = frame_begin(c))) return rc;
+  SC_TRY(frame_begin(c));
   c->frame.pend_src = d_src; c->frame.pend_tgt = d_tgt; c->frame.pend_n = n; c->frame.pend_p = *p; c->frame.pend_Rt = d_Rt; c->frame.pend_mask = d_mask;
   c->frame.pend_stats.size = sizeof(sc_stats);
   PassMode mode{true};  // (sc_wait repeats a call whose estimated pruning bound fails, like any other failed assumption)
   if (fast_plan(c, n, p, &mode)) {
     // host-free: the whole chain is enqueued without looking at anything the GPU produces; sc_wait validates
-    rc = hyp_begin(c, d_src, d_tgt, n, p, nullptr, 0, 1, mode);
+    int rc = hyp_begin(c, d_src, d_tgt, n, p, nullptr, 0, 1, mode);
     if (!rc) rc = hyp_end(c, nullptr, c->key.as<uint64_t>(), &c->frame.pend_stats);
     if (!rc) rc = finalize_enqueue(c, c->key.as<uint64_t>(), 1, d_Rt, d_mask);
     if (!rc) {
@@ -1820,7 +1599,7 @@ int sc_register_device_async(sc_ctx* c, const float* d_src, const float* d_tgt, 
     (void)hipStreamSynchronize(c->stream);
     (void)hipGetLastError();
   }
-  rc = register_waited(c, d_src, d_tgt, n, p, d_Rt, d_mask, &c->frame.pend_stats);
+  const int rc = register_waited(c, d_src, d_tgt, n, p, d_Rt, d_mask, &c->frame.pend_stats);
   if (rc != SC_OK && rc != SC_ENOHYP) return rc;
   c->frame.pending = true; c->frame.pend_done = true; c->frame.pending_rc = rc; c->frame.pend_finalize = false;
   return SC_OK;
@@ -1833,10 +1612,10 @@ int sc_wait(sc_ctx* c, sc_stats* stats) {
   c->frame.pending = false;
   if (c->frame.pend_finalize) {  // sc_finalize_gathered_device's second half
     c->frame.pend_finalize = false;
-    const int frc = finalize_status(c, finalize_wait(c, &c->frame.pend_stats));
-    count_frame(c, frc);
-    if (stats && stats->size == sizeof(sc_stats)) *stats = c->frame.pend_stats;
-    return frc;
+    const int rc = finalize_status(c, finalize_wait(c, &c->frame.pend_stats));
+    count_frame(c, rc);
+    copy_stats(stats, c->frame.pend_stats);
+    return rc;
   }
   int rc = c->frame.pending_rc;
   if (!c->frame.pend_done) {
@@ -1847,7 +1626,7 @@ int sc_wait(sc_ctx* c, sc_stats* stats) {
     }
   }
   count_frame(c, rc);
-  if (stats && stats->size == sizeof(sc_stats)) *stats = c->frame.pend_stats;
+  copy_stats(stats, c->frame.pend_stats);
   if (rc == SC_OK) {
     // a frame: sc_peel may follow.  The same state whichever way the frame ran (waited, host-free, repeated after a miss): the
     // winner's words are those of the pass that delivered the outputs
@@ -1860,19 +1639,17 @@ int sc_wait(sc_ctx* c, sc_stats* stats) {
 
 int sc_register_device(sc_ctx* c, const float* d_src, const float* d_tgt, int64_t n, const sc_params* p,
                        float* d_Rt, uint8_t* d_mask, sc_stats* stats) {
-  const int rc = sc_register_device_async(c, d_src, d_tgt, n, p, d_Rt, d_mask);
-  return rc ? rc : sc_wait(c, stats);
+  SC_TRY(sc_register_device_async(c, d_src, d_tgt, n, p, d_Rt, d_mask));
+  return sc_wait(c, stats);
 }
 
 int sc_register(sc_ctx* c, const float* src, const float* tgt, int64_t n, const sc_params* p, float R[9],
                 float t[3], uint8_t* mask, sc_stats* stats) {
   if (c) peel_end(c);
   if (!c || !src || !tgt || !R || !t || !mask || n < 3 || n > (1 << 24)) return SC_EINVAL;
-  int rc = check_params(p);
-  if (rc) return rc;
-  if (p->shard_world != 1) return SC_EINVAL;
+  SC_TRY(entry_checks(c, p, PARAMS | ONE_RANK));  // (busy: sc_register_device_async's answer, below)
   HIPCHK(c, hipSetDevice(c->device));
-  c->cap_bytes = p->max_workspace ? p->max_workspace : (64ull << 30);
+  c->cap_bytes = workspace_cap(p);
   if (n <= (1 << 20)) {
     // Zero-copy form (up to 1 M correspondences = 24 MB in, 1 MB out over the host link): two memcpys on the host into a
     // pinned, device-mapped area; the staging kernel reads it, the finalize kernel writes (R, t) and the mask into the
@@ -1887,8 +1664,8 @@ int sc_register(sc_ctx* c, const float* src, const float* tgt, int64_t n, const 
       *cap = sz;
       return SC_OK;
     };
-    if ((rc = grow(&c->h_in, &c->h_in_cap, in_bytes))) return rc;
-    if ((rc = grow(&c->h_out, &c->h_out_cap, out_bytes))) return rc;
+    SC_TRY(grow(&c->h_in, &c->h_in_cap, in_bytes));
+    SC_TRY(grow(&c->h_out, &c->h_out_cap, out_bytes));
     float* hs = static_cast<float*>(c->h_in);
     float* ht = hs + (size_t)n * 3;
     memcpy(hs, src, (size_t)n * 12);
@@ -1897,7 +1674,7 @@ int sc_register(sc_ctx* c, const float* src, const float* tgt, int64_t n, const 
     HIPCHK(c, hipHostGetDevicePointer(&d_s, hs, 0));
     HIPCHK(c, hipHostGetDevicePointer(&d_t, ht, 0));
     HIPCHK(c, hipHostGetDevicePointer(&d_o, c->h_out, 0));
-    rc = sc_register_device(c, static_cast<float*>(d_s), static_cast<float*>(d_t), n, p, static_cast<float*>(d_o),
+    const int rc = sc_register_device(c, static_cast<float*>(d_s), static_cast<float*>(d_t), n, p, static_cast<float*>(d_o),
                             static_cast<uint8_t*>(d_o) + 64, stats);
     if (rc != SC_OK && rc != SC_ENOHYP) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));  // (idle already on the private stream; a caller's stream may hold the refit)
@@ -1907,499 +1684,14 @@ int sc_register(sc_ctx* c, const float* src, const float* tgt, int64_t n, const 
     memcpy(mask, static_cast<const uint8_t*>(c->h_out) + 64, (size_t)n);
     return rc;
   }
-  ENSURE(c, c->in_src, (size_t)n * 12);
-  ENSURE(c, c->in_tgt, (size_t)n * 12);
   ENSURE(c, c->rt12, 64);
   ENSURE(c, c->mask, (size_t)n);
-  HIPCHK(c, hipMemcpyAsync(c->in_src.p, src, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->in_tgt.p, tgt, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
-  rc = sc_register_device(c, c->in_src.as<float>(), c->in_tgt.as<float>(), n, p, c->rt12.as<float>(),
+  SC_TRY(points_to_device(c, src, tgt, n));
+  const int rc = sc_register_device(c, c->in_src.as<float>(), c->in_tgt.as<float>(), n, p, c->rt12.as<float>(),
                           c->mask.as<uint8_t>(), stats);
   if (rc != SC_OK && rc != SC_ENOHYP) return rc;
-  float Rt[12];
-  HIPCHK(c, hipMemcpyAsync(Rt, c->rt12.p, 48, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(mask, c->mask.p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  memcpy(R, Rt, 36);
-  memcpy(t, Rt + 9, 12);
+  SC_TRY(outputs_to_host(c, (size_t)n, R, t, mask));
   return rc;
-}
-
-// ---- rounds on a scored frame (include/saccot.h, sc_peel) ----------------------------------------------
-//
-// claim + compact -> score -> arg-max -> winner / mask (+ refit): four launches of a dependent chain (five with SC_FLAG_REFINE), then
-// the wait for the winner.  Stage C2 of a round is the PLAIN fp32 kernel (launch_score) on the compacted planes, in every score
-// mode: exact by construction.  The frame's filter path is not reused: its tile, its coefficient permutation and its reference
-// frame are built inside the frame's Kabsch launch for the frame's n correspondences (FilterPlan is planned by n, the Gram cut's
-// reference was elected for the frame's winner, whose correspondences are the first to go) — a round would have to rebuild all
-// three for n_alive points, which costs more launches than the filter saves at a round's size.
-static int peel_round(sc_ctx* c, float* d_Rt, uint8_t* d_mask, sc_stats* stats) {
-  { const int brc = busy(c); if (brc) return brc; }
-  if (!c->pass.peelable) {
-    c->last_error = "sc_peel: no frame on this context (a round follows an sc_register* call that returned SC_OK with shard_world == 1; any other computing call ends the frame)";
-    return SC_EINVAL;
-  }
-  HIPCHK(c, hipSetDevice(c->device));
-  Pass& ps = c->pass;
-  const sc_params* p = &ps.params;
-  const Shard& sh = ps.sh;  // one rank: n_local == T_eff, a position in the selection IS the index into c->rt
-  hipStream_t st = c->stream;
-  const size_t n = (size_t)ps.n, ld = (size_t)ps.ld;
-  int rc;
-  ENSURE(c, c->peel_planes, 6 * ld * sizeof(float));
-  ENSURE(c, c->peel_claimed, n);
-  if (!c->peel_words.p) {
-    ENSURE(c, c->peel_words, sizeof(PeelWords));
-    HIPCHK(c, hipMemsetAsync(c->peel_words.p, 0, c->peel_words.cap, st));
-  }
-  PeelWords* words = c->peel_words.as<PeelWords>();
-  if ((rc = rec(c, 0))) return rc;
-  LbArgs lb;
-  if ((rc = lb_next(c, (size_t)peel_compact_tiles(ps.n) * 8, 2, 0, &lb))) return rc;
-  // the host sizes the scoring launch by n_alive: in inlier-count mode it knows it (n minus the best_counts so far: best_count ==
-  // popcount(mask) there); in the truncated modes the compaction hands it over (one word, polled)
-  const bool read_alive = p->score_mode != SC_SCORE_COUNT;
-  if (read_alive) arm_word(c, HW_PEEL_ALIVE);
-  launch_peel_compact(points_of(c), c->rt.as<float>(), sh.ld_local, ps.peel_prev, ps.dv.tau2, ps.peel_round == 0,
-                      c->peel_claimed.as<uint8_t>(), c->peel_planes.as<float>(), words, lb, read_alive ? &c->pinned[HW_PEEL_ALIVE] : nullptr, st);
-  ps.peel_prev = 0xFFFFFFFFu;  // folded in
-  if ((rc = rec(c, 1))) return rc;
-  uint64_t n_alive = n - ps.peel_claimed;
-  if (read_alive) {
-    if ((rc = wait_word(c, HW_PEEL_ALIVE))) return rc;
-    n_alive = c->pinned[HW_PEEL_ALIVE];
-    if (n_alive > n) { c->last_error = "internal: the compaction kept more correspondences than the frame has"; return SC_EHIP; }
-  }
-  int npairs = 0;
-  if (n_alive != 0) {  // (nothing alive: every score is 0 — the winner kernel reports "no hypothesis" from zero pairs)
-    const Points alive{c->peel_planes.as<float>(), (int)n_alive, ps.ld};  // (the six planes only: the plain kernel reads nothing else)
-    const uint32_t rows = score_chunks((int)n_alive, sh.ld_local);
-    ENSURE(c, c->partial, (size_t)rows * sh.ld_local * 4);
-    launch_score(alive, c->rt.as<float>(), nullptr, sh, ps.dv, p->score_mode, c->partial.as<uint32_t>(), c->tn, st);
-    if ((rc = rec(c, 2))) return rc;
-    ENSURE(c, c->cnt, (size_t)sh.ld_local * 4);
-    ENSURE(c, c->amx_pairs, argmax_scratch_bytes(sh.ld_local));
-    launch_argmax(sh, c->partial.as<uint32_t>(), rows, c->sel_key.as<uint32_t>(), c->cnt.as<uint32_t>(), c->amx_pairs.as<uint64_t>(),
-                  &c->ctl.as<ControlBlock>()->amx_ticket, nullptr, st);  // (one pair per workgroup: the winner kernel reduces them)
-    npairs = (int)argmax_blocks(sh.ld_local);
-  } else if ((rc = rec(c, 2))) return rc;
-  if ((rc = rec(c, 3))) return rc;
-  arm_word(c, HW_WINNER);
-  launch_peel_winner(points_of(c), c->peel_claimed.as<uint8_t>(), c->rt.as<float>(), sh.ld_local, c->sel_key.as<uint32_t>(), ps.T_eff,
-                     c->amx_pairs.as<uint64_t>(), npairs, ps.dv.tau2, d_Rt, d_mask, words, &c->pinned[HW_WINNER], st);
-  if (ps.refine) {  // fp64 refit over mask_r, in refine_kernel's canonical order over the ORIGINAL indices (the mask stays the fp32 winner's)
-    ENSURE(c, c->refine_tmp, refine_scratch_bytes(ps.n));
-    launch_refine(points_of(c), d_mask, reinterpret_cast<const uint64_t*>(words->key2), c->refine_tmp.as<double>(), d_Rt, st);
-  }
-  if ((rc = rec(c, 4))) return rc;
-  // outputs: complete on return with the private stream, stream-ordered with a caller's (as sc_register_device)
-  if (ps.timing || c->stream == c->own_stream) HIPCHK(c, hipStreamSynchronize(st));
-  if ((rc = wait_word(c, HW_WINNER))) return rc;
-  HIPCHK(c, hipGetLastError());
-  const uint64_t key = c->pinned[HW_WINNER];
-  ps.peel_round++;
-  if (key) {
-    ps.peel_prev = (uint32_t)c->pinned[HW_WINNER_POS];
-    if (!read_alive) ps.peel_claimed += (uint32_t)(key >> 32);
-  }
-  if (stats && stats->size == sizeof(sc_stats)) {
-    fill_stats(c, stats);  // n, edges, tri_total, tri_kept, tri_scored: the frame's
-    stats->best_count = (uint32_t)(key >> 32);
-    stats->best_rank = key ? (uint32_t)(c->pinned[HW_WINNER_POS] >> 32) : 0u;
-    if (ps.timing) {  // the frame asked for SC_FLAG_TIMING: the round's brackets (us_stage: the claim + compact launch)
-      stats->us_stage = ev_us(c, 0, 1);
-      stats->us_score = ev_us(c, 1, 2);
-      stats->us_argmax = ev_us(c, 2, 3);
-      stats->us_mask = ev_us(c, 3, 4);
-      stats->us_compat = stats->us_triangles = stats->us_trikeys = stats->us_kabsch = 0.f;
-      stats->us_total = stats->us_stage + stats->us_score + stats->us_argmax + stats->us_mask;
-    }
-  }
-  return key ? SC_OK : SC_ENOHYP;
-}
-
-int sc_peel_device(sc_ctx* c, float* d_Rt, uint8_t* d_mask, sc_stats* stats) {
-  if (!c || !d_Rt || !d_mask) return SC_EINVAL;
-  return peel_round(c, d_Rt, d_mask, stats);
-}
-
-int sc_peel(sc_ctx* c, float R[9], float t[3], uint8_t* mask, sc_stats* stats) {
-  if (!c || !R || !t || !mask) return SC_EINVAL;
-  { const int brc = busy(c); if (brc) return brc; }
-  if (!c->pass.peelable) return peel_round(c, nullptr, nullptr, stats);  // (refused there, with the text)
-  HIPCHK(c, hipSetDevice(c->device));
-  const size_t n = (size_t)c->pass.n;
-  ENSURE(c, c->rt12, 64);
-  ENSURE(c, c->mask, n);
-  const int rc = peel_round(c, c->rt12.as<float>(), c->mask.as<uint8_t>(), stats);
-  if (rc != SC_OK && rc != SC_ENOHYP) return rc;
-  float Rt[12];
-  HIPCHK(c, hipMemcpyAsync(Rt, c->rt12.p, 48, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(mask, c->mask.p, n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  memcpy(R, Rt, 36);
-  memcpy(t, Rt + 9, 12);
-  return rc;
-}
-
-int sc_register_instances(sc_ctx* c, const float* src, const float* tgt, int64_t n, const sc_params* p, uint32_t max_instances,
-                          uint32_t min_score, float* Rt, uint32_t* score, int32_t* label, uint32_t* n_found, sc_stats* stats) {
-  if (c) peel_end(c);
-  if (!c || !src || !tgt || !Rt || !score || !label || !n_found || max_instances == 0 || max_instances > 65536 || n < 3 || n > (1 << 24))
-    return SC_EINVAL;
-  *n_found = 0;
-  int rc = check_params(p);
-  if (rc) return rc;
-  if (p->shard_world != 1) return SC_EINVAL;
-  { const int brc = busy(c); if (brc) return brc; }
-  HIPCHK(c, hipSetDevice(c->device));
-  c->cap_bytes = p->max_workspace ? p->max_workspace : (64ull << 30);
-  ENSURE(c, c->in_src, (size_t)n * 12);
-  ENSURE(c, c->in_tgt, (size_t)n * 12);
-  ENSURE(c, c->rt12, (size_t)max_instances * 48 + 16);
-  ENSURE(c, c->mask, (size_t)n);
-  ENSURE(c, c->peel_label, (size_t)n * 4);
-  hipStream_t st = c->stream;
-  HIPCHK(c, hipMemcpyAsync(c->in_src.p, src, (size_t)n * 12, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(c->in_tgt.p, tgt, (size_t)n * 12, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemsetAsync(c->peel_label.p, 0xFF, (size_t)n * 4, st));  // -1: claimed by no motion
-  sc_stats fs{}; fs.size = sizeof(sc_stats);
-  rc = sc_register_device(c, c->in_src.as<float>(), c->in_tgt.as<float>(), n, p, c->rt12.as<float>(), c->mask.as<uint8_t>(), &fs);
-  if (stats && stats->size == sizeof(sc_stats)) *stats = fs;
-  if (rc != SC_OK && rc != SC_ENOHYP) return rc;
-  uint32_t k = 0;
-  // motion 0 is the frame's winner; motion k the winner of round k.  The label is built on the device, one launch per accepted
-  // motion, and copied out once; a round's n mask bytes never travel
-  if (rc == SC_OK && fs.best_count >= min_score) {
-    launch_peel_label(c->mask.as<uint8_t>(), (int)n, 0, c->peel_label.as<int32_t>(), st);
-    score[0] = fs.best_count;
-    for (k = 1; k < max_instances; k++) {
-      sc_stats rs{}; rs.size = sizeof(sc_stats);
-      const int prc = peel_round(c, c->rt12.as<float>() + 12 * (size_t)k, c->mask.as<uint8_t>(), &rs);
-      if (prc == SC_ENOHYP) break;
-      if (prc != SC_OK) return prc;
-      if (rs.best_count < min_score) break;
-      launch_peel_label(c->mask.as<uint8_t>(), (int)n, (int32_t)k, c->peel_label.as<int32_t>(), st);
-      score[k] = rs.best_count;
-    }
-  }
-  if (k) HIPCHK(c, hipMemcpyAsync(Rt, c->rt12.p, (size_t)k * 48, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(label, c->peel_label.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  HIPCHK(c, hipGetLastError());
-  *n_found = k;
-  return rc;
-}
-
-// ---- descriptor matching (include/saccot.h, sc_match) -----------------------------------------------------
-//
-// memset (the "clean" word and, for SC_MATCH_MUTUAL, the column minima: all ones) -> distance + select -> finish: three stream
-// operations, no host wait.  The host entries then poll ONE word (count | non-finite flag << 32).
-namespace {
-
-constexpr size_t MATCH_WORDS_HEAD = 64;  // match_words: [0] clean, [2], [3] the host entries' count pair; the column minima from byte 64
-
-int match_check(sc_ctx* c, const sc_match_params* mp, int64_t ns, int64_t nt, MatchJob* job) {
-  if (!mp || mp->size != sizeof(sc_match_params)) { c->last_error = "sc_match: bad sc_match_params.size"; return SC_EINVAL; }
-  if (mp->dim < 1 || mp->dim > 1024 || mp->knn < 1 || mp->knn > 4 || (mp->flags & ~SC_MATCH_MUTUAL) != 0 || mp->reserved[0] != 0 ||
-      mp->reserved[1] != 0 || mp->reserved[2] != 0 || ns < 1 || nt < 1 || ns > (1 << 24) || nt > (1 << 24)) {
-    c->last_error = "sc_match: dim 1 .. 1024, knn 1 .. 4, known flags, reserved words 0, 1 <= ns, nt <= 2^24";
-    return SC_EINVAL;
-  }
-  if (!(mp->ratio >= 0.f && mp->ratio < 1.f)) { c->last_error = "sc_match: ratio must be 0 (off) or in (0, 1)"; return SC_EINVAL; }
-  if (mp->knn != 1 && ((mp->flags & SC_MATCH_MUTUAL) || mp->ratio > 0.f)) {
-    c->last_error = "sc_match: SC_MATCH_MUTUAL and the ratio test need knn == 1";
-    return SC_EINVAL;
-  }
-  job->ns = (uint32_t)ns; job->nt = (uint32_t)nt; job->dim = mp->dim; job->knn = mp->knn;
-  job->mutual = (mp->flags & SC_MATCH_MUTUAL) ? 1u : 0u;
-  job->r2 = mp->ratio > 0.f ? (float)((double)mp->ratio * (double)mp->ratio) : 0.f;
-  return SC_OK;
-}
-
-int match_enqueue(sc_ctx* c, const MatchJob& job, int32_t* d_corr, float* d_d2, uint32_t* d_count, const MatchGather& g, bool to_host) {
-  hipStream_t st = c->stream;
-  const MatchPlan plan = match_plan(job.ns, job.nt, job.knn, job.r2);
-  ENSURE(c, c->match_part, plan.part_bytes);
-  const size_t words_bytes = MATCH_WORDS_HEAD + (job.mutual ? (size_t)job.nt * 8 : 0);
-  ENSURE(c, c->match_words, words_bytes);
-  HIPCHK(c, hipMemsetAsync(c->match_words.p, 0xFF, words_bytes, st));
-  LbArgs lb;
-  { const int lrc = lb_next(c, (size_t)match_finish_tiles(job.ns) * 8, 3, 0, &lb); if (lrc) return lrc; }
-  uint32_t* clean = c->match_words.as<uint32_t>();
-  uint64_t* colmin = job.mutual ? reinterpret_cast<uint64_t*>(static_cast<char*>(c->match_words.p) + MATCH_WORDS_HEAD) : nullptr;
-  if (to_host) arm_word(c, HW_MATCH);
-  launch_match_dist(job, plan, c->match_part.as<uint64_t>(), colmin, clean, st);
-  launch_match_finish(job, plan, c->match_part.as<uint64_t>(), colmin, clean, d_corr, d_d2, d_count ? d_count : clean + 2, g, lb,
-                      to_host ? &c->pinned[HW_MATCH] : nullptr, st);
-  HIPCHK(c, hipGetLastError());
-  return SC_OK;
-}
-
-// the host entries' one wait: the count, or SC_EINVAL for a non-finite descriptor
-int match_wait(sc_ctx* c, uint32_t* n) {
-  *n = 0;
-  { const int wrc = wait_word(c, HW_MATCH); if (wrc) return wrc; }
-  const uint64_t w = c->pinned[HW_MATCH];
-  if (w >> 32) { c->last_error = "non-finite descriptor"; return SC_EINVAL; }
-  *n = (uint32_t)w;
-  return SC_OK;
-}
-
-}  // namespace
-
-int sc_match_default_params(sc_match_params* mp) {
-  if (!mp) return SC_EINVAL;
-  memset(mp, 0, sizeof *mp);
-  mp->size = sizeof(sc_match_params);
-  mp->knn = 1;
-  return SC_OK;
-}
-
-int sc_match_device(sc_ctx* c, const float* d_fsrc, int64_t ns, const float* d_ftgt, int64_t nt, const sc_match_params* mp,
-                    int32_t* d_corr, float* d_d2, uint32_t* d_count) {
-  if (!c || !d_fsrc || !d_ftgt || !d_corr || !d_d2 || !d_count) return SC_EINVAL;
-  peel_end(c);
-  { const int brc = busy(c); if (brc) return brc; }
-  MatchJob job{d_fsrc, d_ftgt};
-  { const int rc = match_check(c, mp, ns, nt, &job); if (rc) return rc; }
-  HIPCHK(c, hipSetDevice(c->device));
-  return match_enqueue(c, job, d_corr, d_d2, d_count, MatchGather{}, false);
-}
-
-int sc_match(sc_ctx* c, const float* fsrc, int64_t ns, const float* ftgt, int64_t nt, const sc_match_params* mp, int32_t* corr,
-             float* d2, uint32_t* n) {
-  if (!c || !fsrc || !ftgt || !corr || !d2 || !n) return SC_EINVAL;
-  *n = 0;
-  peel_end(c);
-  { const int brc = busy(c); if (brc) return brc; }
-  MatchJob job{};
-  int rc = match_check(c, mp, ns, nt, &job);
-  if (rc) return rc;
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t st = c->stream;
-  const size_t sb = (size_t)job.ns * job.dim * 4, tb = (size_t)job.nt * job.dim * 4, cap = (size_t)job.ns * job.knn;
-  ENSURE(c, c->match_fsrc, sb);
-  ENSURE(c, c->match_ftgt, tb);
-  ENSURE(c, c->match_corr, cap * 8);
-  ENSURE(c, c->match_d2, cap * 4);
-  HIPCHK(c, hipMemcpyAsync(c->match_fsrc.p, fsrc, sb, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(c->match_ftgt.p, ftgt, tb, hipMemcpyHostToDevice, st));
-  job.fsrc = c->match_fsrc.as<float>(); job.ftgt = c->match_ftgt.as<float>();
-  if ((rc = match_enqueue(c, job, c->match_corr.as<int32_t>(), c->match_d2.as<float>(), nullptr, MatchGather{}, true))) return rc;
-  uint32_t found = 0;
-  if ((rc = match_wait(c, &found))) return rc;
-  if (found) {
-    HIPCHK(c, hipMemcpyAsync(corr, c->match_corr.p, (size_t)found * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(d2, c->match_d2.p, (size_t)found * 4, hipMemcpyDeviceToHost, st));
-  }
-  HIPCHK(c, hipStreamSynchronize(st));
-  *n = found;
-  return SC_OK;
-}
-
-int sc_register_features(sc_ctx* c, const float* src_pts, const float* fsrc, int64_t ns, const float* tgt_pts, const float* ftgt,
-                         int64_t nt, const sc_match_params* mp, const sc_params* p, float R[9], float t[3], int32_t* corr, float* d2,
-                         uint32_t* n, uint8_t* mask, sc_stats* stats) {
-  if (!c || !src_pts || !fsrc || !tgt_pts || !ftgt || !R || !t || !corr || !d2 || !n || !mask) return SC_EINVAL;
-  *n = 0;
-  peel_end(c);
-  { const int brc = busy(c); if (brc) return brc; }
-  int rc = check_params(p);
-  if (rc) return rc;
-  if (p->shard_world != 1) return SC_EINVAL;
-  MatchJob job{};
-  if ((rc = match_check(c, mp, ns, nt, &job))) return rc;
-  HIPCHK(c, hipSetDevice(c->device));
-  c->cap_bytes = p->max_workspace ? p->max_workspace : (64ull << 30);
-  hipStream_t st = c->stream;
-  const size_t sb = (size_t)job.ns * job.dim * 4, tb = (size_t)job.nt * job.dim * 4, cap = (size_t)job.ns * job.knn;
-  ENSURE(c, c->match_fsrc, sb);
-  ENSURE(c, c->match_ftgt, tb);
-  ENSURE(c, c->match_psrc, (size_t)job.ns * 12);
-  ENSURE(c, c->match_ptgt, (size_t)job.nt * 12);
-  ENSURE(c, c->match_corr, cap * 8);
-  ENSURE(c, c->match_d2, cap * 4);
-  ENSURE(c, c->match_gsrc, cap * 12);
-  ENSURE(c, c->match_gtgt, cap * 12);
-  HIPCHK(c, hipMemcpyAsync(c->match_fsrc.p, fsrc, sb, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(c->match_ftgt.p, ftgt, tb, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(c->match_psrc.p, src_pts, (size_t)job.ns * 12, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(c->match_ptgt.p, tgt_pts, (size_t)job.nt * 12, hipMemcpyHostToDevice, st));
-  job.fsrc = c->match_fsrc.as<float>(); job.ftgt = c->match_ftgt.as<float>();
-  const bool soa = p->layout == SC_SOA;
-  // the gathered correspondences are written n x 3 whatever the caller's layout: n is not known while they are written
-  const MatchGather g{c->match_psrc.as<float>(), c->match_ptgt.as<float>(), soa ? 1u : 3u, soa ? job.ns : 1u, soa ? 1u : 3u,
-                      soa ? job.nt : 1u, c->match_gsrc.as<float>(), c->match_gtgt.as<float>()};
-  if ((rc = match_enqueue(c, job, c->match_corr.as<int32_t>(), c->match_d2.as<float>(), nullptr, g, true))) return rc;
-  uint32_t found = 0;
-  if ((rc = match_wait(c, &found))) return rc;  // the one host wait between matching and registration
-  if (found) {
-    HIPCHK(c, hipMemcpyAsync(corr, c->match_corr.p, (size_t)found * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(d2, c->match_d2.p, (size_t)found * 4, hipMemcpyDeviceToHost, st));
-  }
-  *n = found;
-  if (found < 3) {
-    HIPCHK(c, hipStreamSynchronize(st));
-    const float ident[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
-    memcpy(R, ident, 36);
-    memset(t, 0, 12);
-    return SC_ENOHYP;
-  }
-  sc_params pg = *p;
-  pg.layout = SC_AOS;
-  ENSURE(c, c->rt12, 64);
-  ENSURE(c, c->mask, (size_t)found);
-  rc = sc_register_device(c, c->match_gsrc.as<float>(), c->match_gtgt.as<float>(), found, &pg, c->rt12.as<float>(),
-                          c->mask.as<uint8_t>(), stats);
-  if (rc != SC_OK && rc != SC_ENOHYP) { (void)hipStreamSynchronize(st); return rc; }
-  float Rt[12];
-  HIPCHK(c, hipMemcpyAsync(Rt, c->rt12.p, 48, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(mask, c->mask.p, (size_t)found, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  memcpy(R, Rt, 36);
-  memcpy(t, Rt + 9, 12);
-  return rc;
-}
-
-// ---- stage hooks ------------------------------------------------------------------------------------
-
-int sc_compat_host(sc_ctx* c, const float* src, const float* tgt, int64_t n, const sc_params* p, float* S,
-                   uint64_t* bits, uint32_t* deg) {
-  if (!c) return SC_EINVAL;
-  int rc = check_params(p);
-  if (rc) return rc;
-  HIPCHK(c, hipSetDevice(c->device));
-  c->pass.have_hyp = false; peel_end(c);
-  const bool dense = S != nullptr && !(p->flags & SC_FLAG_NO_DENSE_S);
-  if (S && !dense) { c->last_error = "sc_compat_host: S requested together with SC_FLAG_NO_DENSE_S"; return SC_EINVAL; }
-  if ((rc = host_to_planes(c, src, tgt, n, p))) return rc;
-  if ((rc = run_compat(c, dense))) return rc;
-  if ((rc = run_row_stats(c, false))) return rc;
-  if ((rc = check_flag(c))) return rc;
-  const size_t W = (size_t)c->pass.ld >> 6;
-  if (S)
-    HIPCHK(c, hipMemcpy2DAsync(S, (size_t)n * 4, c->S.p, (size_t)c->pass.ld * 4, (size_t)n * 4, (size_t)n,
-                               hipMemcpyDeviceToHost, c->stream));
-  if (bits) HIPCHK(c, hipMemcpyAsync(bits, c->bits.p, (size_t)n * W * 8, hipMemcpyDeviceToHost, c->stream));
-  if (deg) HIPCHK(c, hipMemcpyAsync(deg, c->deg.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipGetLastError());
-  return SC_OK;
-}
-
-int sc_triangles_host(sc_ctx* c, const float* src, const float* tgt, int64_t n, const sc_params* p, uint32_t* tri,
-                      uint32_t* key, uint32_t* t_eff, uint64_t* tri_total, uint64_t* edges) {
-  if (!c || !tri || !t_eff) return SC_EINVAL;
-  int rc = check_params(p);
-  if (rc) return rc;
-  HIPCHK(c, hipSetDevice(c->device));
-  c->pass.have_hyp = false; peel_end(c);
-  if ((rc = host_to_planes(c, src, tgt, n, p))) return rc;
-  if ((rc = run_compat(c, false))) return rc;  // the ranked list needs the bit rows only
-  if ((rc = run_row_stats(c, may_prune(p)))) return rc;
-  sc_params pe = *p;
-  pe.flags |= SC_FLAG_EXACT_TOTAL;  // the hook reports the 3-clique count of the whole graph
-  if ((rc = run_triangles(c, &pe, true))) return rc;
-  *t_eff = c->pass.T_eff;
-  if (tri_total) *tri_total = c->pass.M_total;
-  if (edges) *edges = c->pass.E;
-  if (c->pass.T_eff) {
-    // the hook returns the RANKED list; the hot path itself never sorts
-    const size_t T = c->pass.T_eff, sort_bytes = sort_temp_bytes(T);
-    ENSURE(c, c->sortkey, T * 8);
-    ENSURE(c, c->sorted, T * 8);
-    ENSURE(c, c->sort_tmp, sort_bytes + 16);
-    ENSURE(c, c->tri_rk, T * 12);
-    ENSURE(c, c->key_rk, T * 4);
-    launch_rank_order(c->tri.as<uint32_t>(), c->sel_key.as<uint32_t>(), c->pass.T_eff, c->sortkey.as<uint64_t>(),
-                      c->sorted.as<uint64_t>(), c->sort_tmp.p, sort_bytes, c->tri_rk.as<uint32_t>(),
-                      c->key_rk.as<uint32_t>(), c->stream);
-    HIPCHK(c, hipMemcpyAsync(tri, c->tri_rk.p, T * 12, hipMemcpyDeviceToHost, c->stream));
-    if (key) HIPCHK(c, hipMemcpyAsync(key, c->key_rk.p, T * 4, hipMemcpyDeviceToHost, c->stream));
-  }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipGetLastError());
-  return SC_OK;
-}
-
-int sc_kabsch_host(sc_ctx* c, const float* src, const float* tgt, int64_t n, const sc_params* p,
-                   const uint32_t* tri, uint32_t n_tri, float* Rt) {
-  if (!c || !tri || !Rt) return SC_EINVAL;
-  int rc = check_params(p);
-  if (rc) return rc;
-  for (size_t k = 0; k < (size_t)n_tri * 3; k++) if ((int64_t)tri[k] >= n) return SC_EINVAL;
-  HIPCHK(c, hipSetDevice(c->device));
-  c->pass.have_hyp = false; peel_end(c);
-  if ((rc = host_to_planes(c, src, tgt, n, p))) return rc;
-  if (n_tri == 0) return check_flag(c);
-  ENSURE(c, c->tri, (size_t)n_tri * 12);
-  ENSURE(c, c->rt_aos, (size_t)n_tri * 48);
-  HIPCHK(c, hipMemcpyAsync(c->tri.p, tri, (size_t)n_tri * 12, hipMemcpyHostToDevice, c->stream));
-  launch_kabsch_aos(points_of(c), c->tri.as<uint32_t>(), n_tri, c->rt_aos.as<float>(), c->stream);
-  if ((rc = check_flag(c))) return rc;
-  HIPCHK(c, hipMemcpyAsync(Rt, c->rt_aos.p, (size_t)n_tri * 48, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipGetLastError());
-  return SC_OK;
-}
-
-int sc_score_host(sc_ctx* c, const float* src, const float* tgt, int64_t n, const sc_params* p, const float* Rt,
-                  uint32_t n_hyp, uint32_t* cnt, uint64_t* key) {
-  if (!c || !Rt || !key) return SC_EINVAL;
-  int rc = check_params(p);
-  if (rc) return rc;
-  HIPCHK(c, hipSetDevice(c->device));
-  c->pass.have_hyp = false; peel_end(c);
-  if ((rc = host_to_planes(c, src, tgt, n, p))) return rc;
-  Shard sh;
-  sh.T_eff = n_hyp; sh.block = 0x40000000u; sh.rank = 0; sh.world = 1; sh.n_local = n_hyp;
-  sh.ld_local = (uint32_t)(((uint64_t)n_hyp + 255u) / 256u * 256u);
-  ENSURE(c, c->key, 64);
-  if (n_hyp) {
-    ENSURE(c, c->rt_aos, (size_t)sh.ld_local * 48);  // (the scoring kernel may read whole 256-hypothesis groups)
-    ENSURE(c, c->rt, (size_t)12 * sh.ld_local * 4);
-    HIPCHK(c, hipMemcpyAsync(c->rt_aos.p, Rt, (size_t)n_hyp * 48, hipMemcpyHostToDevice, c->stream));
-    if (sh.ld_local > n_hyp)  // the padding hypotheses read as zeros in both layouts
-      HIPCHK(c, hipMemsetAsync(c->rt_aos.as<char>() + (size_t)n_hyp * 48, 0, (size_t)(sh.ld_local - n_hyp) * 48, c->stream));
-    launch_rt_to_soa(c->rt_aos.as<float>(), n_hyp, sh.ld_local, c->rt.as<float>(), c->stream);
-  }
-  // the choice of the C2 kernel looks at the coordinate maxima the staging kernel publishes: wait for them (the path
-  // proper never has to — it has polled later results of the same stream by the time it gets here)
-  if (!c->tn.filter_blind && (rc = wait_word(c, HW_COORD_MAX))) return rc;
-  c->pass.sh = sh;
-  if ((rc = decide_filter(c, p, sh))) return rc;
-  uint32_t score_rows = 0;
-  if ((rc = run_score(c, p, sh, &score_rows, false))) return rc;
-  ENSURE(c, c->cnt, (size_t)(sh.ld_local ? sh.ld_local : 256) * 4);
-  ENSURE(c, c->amx_pairs, argmax_scratch_bytes(sh.ld_local));
-  launch_argmax(sh, c->partial.as<uint32_t>(), score_rows, nullptr, c->cnt.as<uint32_t>(), c->amx_pairs.as<uint64_t>(),
-                &c->ctl.as<ControlBlock>()->amx_ticket, c->key.as<uint64_t>(), c->stream);  // positions in Rt ARE the rank indices here: single-stage key
-  if ((rc = check_flag(c))) return rc;
-  if (cnt && n_hyp) HIPCHK(c, hipMemcpyAsync(cnt, c->cnt.p, (size_t)n_hyp * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(key, c->key.p, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipGetLastError());
-  return SC_OK;
-}
-
-int sc_mask_host(sc_ctx* c, const float* src, const float* tgt, int64_t n, const sc_params* p, const float Rt[12],
-                 uint8_t* mask) {
-  if (!c || !Rt || !mask) return SC_EINVAL;
-  int rc = check_params(p);
-  if (rc) return rc;
-  HIPCHK(c, hipSetDevice(c->device));
-  c->pass.have_hyp = false; peel_end(c);
-  if ((rc = host_to_planes(c, src, tgt, n, p))) return rc;
-  ENSURE(c, c->rt12, 64);
-  ENSURE(c, c->mask, (size_t)n);
-  HIPCHK(c, hipMemcpyAsync(c->rt12.p, Rt, 48, hipMemcpyHostToDevice, c->stream));
-  launch_mask(points_of(c), c->rt12.as<float>(), c->pass.dv.tau2, c->mask.as<uint8_t>(), c->stream);
-  if ((rc = check_flag(c))) return rc;
-  HIPCHK(c, hipMemcpyAsync(mask, c->mask.p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipGetLastError());
-  return SC_OK;
 }
 
 }  // extern "C"

@@ -1,0 +1,218 @@
+// sc_ctx.hpp — private to the host side of the C ABI (sc_capi*.hip): the context and its call state, the status macros, and the
+// host helpers that more than one of those files uses.  No kernel source includes this header.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <string>
+#include <type_traits>
+
+#include "../../include/saccot.h"
+#include "../../include/saccot_debug.h"
+#include "sc_kernels.hpp"
+
+namespace sc {
+
+struct Buf {
+  void* p = nullptr;
+  size_t cap = 0;
+  template <class T> T* as() const { return static_cast<T*>(p); }
+};
+
+constexpr int N_EVENTS = 12;  // 0..8 stage brackets, 9..10 the key kernel (all reused by calibrate_events), 11 the stop of stage C2's filter kernel (SC_FLAG_TIMING_HOT)
+constexpr int N_PINNED = HW_COUNT;  // the host words (sc_kernels.hpp, HostWord)
+static_assert(HW_MERGED_M == HW_MERGED_T + 1 && HW_WINNER_POS == HW_WINNER + 1, "merge_prepare and the finalize kernel write word pairs");
+
+// How a pass is enqueued: decided by the entry point BEFORE the pass starts and handed to hyp_begin, which stores it in the fresh pass.
+struct PassMode {
+  // the entry point can repeat the call (sc_register*), or its caller does (sc_hypothesize_device with SC_FLAG_EST_BOUND): stage B
+  // may prune by an ESTIMATED bound (sc_tri.hip 3c); the select verifies it, finalize_wait reads the verdict
+  bool may_estimate = false;
+  // host-free enqueue (include/saccot.h): a call of the last one's shape does not wait for stage B's two counts; its launches cover E_cov
+  // edges / M_cov keys (fast_plan) and read the real counts from device memory; finalize_wait validates, and the call is repeated the waiting
+  // way when a count outgrew the cover.  pass_end takes host_free back; the covers stay for sc_debug_last.
+  bool host_free = false;
+  uint64_t E_cov = 0, M_cov = 0;
+};
+
+// One run through hyp_begin (or sc_shard_compat_device) to finalize_wait.  Assigned Pass{} in pass_begin and nowhere else: what a pass
+// did not set itself reads as "no".  Fields are READ after the pass as well — by a finalize call that comes later (have_hyp links the
+// two, and it may come twice), by note_completed (E, M, n, params, use_events), by fill_stats and sc_debug_last (counts, covers, filter_*,
+// est_state, hot_ext) — so nothing is cleared when a pass ends except mode.host_free.  The stage hooks (sc_*_host) start no pass: they
+// run single kernels on the context's buffers and touch only what host_to_planes says.
+struct Pass {
+  PassMode mode;
+  int n = 0, ld = 0; uint32_t T_eff = 0;
+  uint64_t E = 0, M = 0, M_total = 0;  // stage B's counts (host-free: the covers until finalize_wait has validated, then the real ones)
+  bool pruned = false, use_events = false, have_total = false;
+  Derived dv{}; Shard sh{};
+  bool begun = false, have_hyp = false;  // sc_hypothesize_begin_device is done (_end may follow); the hypothesize half is done (finalize may follow)
+  sc_params params{};
+  bool timing = false, timing_hot = false, timed_trikeys = false, refine = false;
+  int timing_one = -1;      // SC_FLAG_TIMING_ONE: the one stage bracket recorded (0 .. 6), -1: none
+  bool hot_ext = false;     // SC_FLAG_TIMING_HOT took its timestamps from the kernels' dispatch packets (run_stage_c)
+  uint32_t amx_blocks = 0;  // workgroups of the arg-max launch whose pairs this context's finalize step reduces itself (0: one reduced pair in `key`)
+  uint64_t* bits_cur = nullptr;  // the adjacency bit matrix: the context's own buffer, or — sharded stage A — the caller's all-gathered one
+  bool rows_fused = false;  // run_row_stats already produced edge_off / ebase / cost_pre and armed the edge count
+  bool build = false;       // launch_edge_build: row statistics + edge list + estimating sample in one launch
+  bool regular = false;     // every assumption of the host-free form was met (run_select, finalize_wait): note_completed files it as fast_ok
+  bool est_active = false;  // stage B prunes by an estimate
+  bool est_void = false;    // ... which could not be verified on the path taken (event overflow): repeat
+  int est_state = 0;        // 0 certified bound (or no pruning), 1 estimated and verified: finalize_wait's verdict, read by count_frame
+  SamplePlan plan{false, 1u, 0};
+  // stage C2's reference frame (sc_gramref.hpp): on the hot path the estimating sample leaves candidate triangles behind (ref_cand_n of
+  // them) and the counting pass carries the vote as an extra workgroup (ref_done); everywhere else stage C votes in a launch of its own
+  uint32_t ref_cand_n = 0; bool ref_done = false;
+  bool filter_on = false;   // C2 goes through a matrix-pipe filter (decided ONCE per pass: decide_filter)
+  int filter_mode = 0;      // ... which: 1 linear, 2 Gram (0: the plain fp32 kernel)
+  FilterPlan fx_plan{};     // ... with this plan
+  // sharded A + B (sc_shard_*_device): the phase reached (0: none) and the gathered candidate blobs
+  bool sharded_ab = false; int shard_phase = 0;
+  const void* cand_all = nullptr; size_t cand_bytes = 0;
+  // rounds on this pass's frame (sc_peel): set where a frame's status becomes SC_OK (sc_wait, whichever way the frame ran), gone with
+  // the pass (pass_begin) or when any other computing entry is called (peel_end)
+  bool peelable = false;
+  uint32_t peel_round = 0;           // rounds done
+  uint32_t peel_prev = 0xFFFFFFFFu;  // position of the winner whose mask the next round's claim step folds in (all ones: none)
+  uint32_t peel_claimed = 0;         // inlier-count mode: correspondences claimed so far (the best_counts add up to it)
+};
+
+// One call of an entry point as its caller sees it: it survives the library's own repeat of the call (sc_wait -> register_waited: a
+// second pass) and ends in count_frame.  Assigned Frame{} in frame_begin and nowhere else.
+struct Frame {
+  int fast_state = 0;            // 0 waited, 1 host-free and valid, 2 host-free, failed validation, repeated
+  bool est_failed_call = false;  // a pass of this frame saw its estimate fail (sc_debug_last: prune_bound 2); the repeat must not forget it
+  // the outstanding half of sc_register_device_async / sc_finalize_gathered_device_async (at most one per context)
+  bool pending = false;
+  bool pend_done = false; int pending_rc = 0;  // ... and it was a waited call: complete, with this status
+  bool pend_finalize = false;  // ... it is sc_finalize_gathered_device_async's (sc_wait: no repeat inside the library)
+  const float* pend_src = nullptr; const float* pend_tgt = nullptr; float* pend_Rt = nullptr; uint8_t* pend_mask = nullptr;
+  int64_t pend_n = 0; sc_params pend_p{}; sc_stats pend_stats{};
+};
+
+// The grow-only device workspace: Buf members and nothing else.  sc_destroy walks it as an array (workspace_bufs), so a Buf declared
+// here is freed; there is no second list to keep in step.
+struct Workspace {
+  Buf in_src, in_tgt, planes, S, bits, deg, degp, wpre, ebase, edge_off, scan_tmp, ei, ej, es, ebi, ebj, tcnt, toff, wkey, kcol, ctl, events, blk_gt,
+      blk_eq, blk_minmax, bits2, off_gt, off_eq, sel_ord, sel_key, sortkey, sorted, sort_tmp, tri, tri_rk, key_rk, rt, rt_aos, partial, cnt, key, rt12,
+      mask, refine_tmp, amx_pairs, strong, rowcost, cost_pre, lb_state, lb_ticket, fx_tile, fx_state, fx_mx, fx_part, fx_coef, guard_tmp, fx_frame, ref_cand,
+      peel_planes, peel_claimed, peel_words, peel_label,  // sc_peel / sc_register_instances: allocated by the first round, never by a frame
+      // sc_match / sc_register_features: allocated by the first match, never by a frame.  part: the slices' partial lists; words: the
+      // "clean" word, the host entries' count pair, then the column minima; the rest: device copies of the host entries' arrays
+      match_part, match_words, match_fsrc, match_ftgt, match_psrc, match_ptgt, match_corr, match_d2, match_gsrc, match_gtgt;
+};
+constexpr size_t N_WORKSPACE_BUFS = sizeof(Workspace) / sizeof(Buf);
+static_assert(std::is_standard_layout<Workspace>::value && alignof(Workspace) == alignof(Buf) && sizeof(Workspace) == N_WORKSPACE_BUFS * sizeof(Buf),
+              "Workspace holds Buf members only: it is walked as an array of them");
+inline Buf* workspace_bufs(Workspace* w) { return reinterpret_cast<Buf*>(w); }
+
+}  // namespace sc
+
+// The context.  What lives as long as it does is a direct member; the call in flight is `frame` and, inside it, `pass`.
+struct sc_ctx : sc::Workspace {  // (the workspace buffers are direct members too: c->planes)
+  int device = 0;
+  hipStream_t own_stream = nullptr;
+  hipStream_t stream = nullptr;
+  std::string last_error;
+  size_t held = 0;
+  uint64_t cap_bytes = 64ull << 30;  // what ensure() holds `held` against: every entry point sets it from its sc_params
+  hipEvent_t ev[sc::N_EVENTS] = {};
+  float ev_overhead_us = -1.f;  // cost of one event record inside a bracket (calibrate_events); < 0: not measured yet (on this stream)
+  uint64_t* pinned = nullptr;  // N_PINNED x u64 host-pinned area the kernels write results into, indexed by HostWord
+
+  // the XCD-aware block orders of stage A (compat_wg_map), one per row width met so far: a context that alternates between a few
+  // sizes must not rebuild and upload the map on every call (that cost 2 ms per call in bench.py's varying-n leg)
+  static constexpr int N_WG_MAPS = 8;
+  struct WgMap { int W = 0; uint32_t len = 0; sc::Buf buf; uint64_t used = 0; } wg_maps[N_WG_MAPS];
+  uint64_t wg_map_clock = 0;
+  // sc_register (host arrays in, host arrays out): pinned, device-mapped staging areas — the staging kernel reads the
+  // correspondences straight from host memory and the finalize kernel writes (R, t, mask) straight into it: no copies
+  void* h_in = nullptr; size_t h_in_cap = 0;
+  void* h_out = nullptr; size_t h_out_cap = 0;
+  uint64_t ev_capacity = 1ull << 21;  // event records (32 B each); doubled after an overflow
+  sc::Tuning tn;  // defaults unless sc_set_debug() changed them; the library reads no environment variable
+  // decoupled look-back launches (single-pass scan, fused compaction): their state area and its epoch
+  uint32_t lb_epoch = 0; void* lb_zeroed = nullptr; size_t lb_zeroed_cap = 0;
+  // run-time probe of the matrix pipe's accumulation model (sc_score.hip gram_guard): 0 not run, 1 holds, 2 violated
+  int gram_guard = 0; float gram_guard_worst = 0.f;
+
+  // ---- history: what a completed call leaves for the next one (note_completed writes it, fast_plan / room_of / edge_build_ok read it)
+  bool fast_ok = false;      // the last completed call was regular (events, a-priori window, T triangles found): the next may be enqueued host-free
+  uint64_t E_last = 0, M_last = 0;
+  int last_n = 0;
+  sc_params last_p{};
+  // r05: what the covers are sized by.  A stream of DIFFERENT frames of one shape (bench.py's: 32 scenes whose inlier ratio moves the
+  // edge count by 1.6 x and the triangle count by 4 x) outgrew "the last call's counts plus half" in a frame out of six; the covers now
+  // follow the largest counts of the last HI_WINDOW .. 2 HI_WINDOW completed calls of the shape (two buckets: the current one and the one
+  // before it), so a stream pays for the spread of its frames once.  A change of shape empties the window (note_completed).
+  static constexpr uint32_t HI_WINDOW = 64, HI_YOUNG = 8;
+  uint64_t E_hi[2] = {0, 0}, M_hi[2] = {0, 0};
+  uint32_t hi_n = 0, hi_seen = 0;  // calls in the current bucket; regular calls of this shape seen so far (saturating)
+  bool est_failed = false;   // an estimate failed on this context: it certifies for the next est_holdoff completed calls (sc_set_debug resets)
+  // r04c: not for ever.  One frame whose estimate fails — a change of scene — used to cost the context its estimating sample (25 us per
+  // C2 call) for the rest of its life; now the k-th failure costs 64 << min(k - 1, 6) certifying calls, then the context estimates
+  // again: a stream whose estimates always fail wastes one repeated call in 4096.
+  uint32_t est_holdoff = 0, est_failures = 0;
+  // the coordinate maxima and boxes the staging kernel of the last completed call published (use_filter): what a host-free call
+  // picks stage C2's kernel by when it is enqueued before its own staging kernel has run — a second frame in flight on the stream
+  uint64_t mx_last = ~0ull, box_last[6] = {0, 0, 0, 0, 0, 0};
+  // cumulative over the context's life (sc_debug_last): how its sc_register_device(_async) / host-free sc_hypothesize_device calls
+  // were enqueued and how stage B's pruning bound fared — what a stream of frames reports (a per-call field would only say the last)
+  uint64_t n_frames = 0, n_fast_ok = 0, n_fast_repeat = 0, n_est_ok = 0, n_est_fail = 0;
+  uint64_t n_spec_grow = 0;  // buffers re-allocated (a stream synchronisation each) inside host-free enqueues
+
+  sc::Frame frame;  // the call in flight, as the caller sees it
+  sc::Pass pass;    // ... and the library's current (or last) run through the stages for it
+};
+
+namespace sc {
+
+int fail_hip(sc_ctx* c, hipError_t e, const char* what);
+// evaluate; a HIP error (with its text in last_error as SC_EHIP), or a status other than SC_OK, is the caller's status
+#define HIPCHK(c, expr) do { const hipError_t _e = (expr); if (_e != hipSuccess) return fail_hip((c), _e, #expr); } while (0)
+#define SC_TRY(expr) do { const int _rc = (expr); if (_rc != SC_OK) return _rc; } while (0)
+#define ENSURE(c, buf, bytes) SC_TRY(ensure((c), (buf), (bytes)))
+#define ENSURE_ROOM(c, buf, need, room) SC_TRY(ensure_room((c), (buf), (need), (room)))
+
+// ---- defined in sc_capi.hip, used by the other host files as well (what each does is said at its definition)
+int ensure(sc_ctx* c, Buf& b, size_t bytes);
+int ensure_room(sc_ctx* c, Buf& b, size_t need, size_t room);
+int check_params(const sc_params* p);
+Derived derive(const sc_params* p);
+inline uint64_t workspace_cap(const sc_params* p) { return p->max_workspace ? p->max_workspace : (64ull << 30); }
+inline Points points_of(const sc_ctx* c) { return Points{c->planes.as<float>(), c->pass.n, c->pass.ld}; }
+int lb_next(sc_ctx* c, size_t bytes, int slot, size_t desc_off, LbArgs* out);
+int rec(sc_ctx* c, int i);
+float ev_us(sc_ctx* c, int a, int b);
+constexpr uint64_t PIN_PENDING = ~0ull;  // a host word whose kernel has not delivered yet (wait_word polls it)
+inline void arm_word(sc_ctx* c, HostWord w) { c->pinned[w] = PIN_PENDING; }
+int wait_word(sc_ctx* c, HostWord idx);
+// an sc_register_device_async / sc_finalize_gathered_device_async call is outstanding on this context
+inline int busy(sc_ctx* c) { return c->frame.pending ? (c->last_error = "a call is outstanding on this context (sc_wait first)", SC_EINVAL) : SC_OK; }
+// Any computing entry other than sc_peel* ends the frame the context may hold (include/saccot.h, sc_peel)
+inline void peel_end(sc_ctx* c) { c->pass.peelable = false; }
+void fill_stats(const sc_ctx* c, sc_stats* s);
+
+// What an entry point checks before it touches the context, always in this order: peel_end, busy, check_params(p), p->shard_world == 1.
+// Each entry names the ones that apply to it; one whose own order is another (sc_register_device_async, sc_register_instances,
+// sc_compat_host) spells that out itself.
+enum EntryCheck : unsigned { ENDS_FRAME = 1u, NOT_BUSY = 2u, PARAMS = 4u, ONE_RANK = 8u };
+int entry_checks(sc_ctx* c, const sc_params* p, unsigned checks);
+// the caller's sc_stats, if it gave one of this library's size, from the context's copy
+inline void copy_stats(sc_stats* stats, const sc_stats& from) { if (stats && stats->size == sizeof(sc_stats)) *stats = from; }
+// n x 3 host arrays -> in_src / in_tgt (enqueued; the arrays must stay until the stream has passed the copies)
+int points_to_device(sc_ctx* c, const float* src, const float* tgt, int64_t n);
+// rt12 and n bytes of mask -> the caller's host arrays (R and t split); the stream is idle on return
+int outputs_to_host(sc_ctx* c, size_t n, float R[9], float t[3], uint8_t* mask);
+
+// the stage sequencers the stage hooks run one at a time (sc_capi_hooks.hip)
+int stage_inputs(sc_ctx* c, const float* d_src, const float* d_tgt, int64_t n, const sc_params* p);
+int run_compat(sc_ctx* c, bool dense);
+int run_row_stats(sc_ctx* c, bool will_prune, bool hot = false);
+inline bool may_prune(const sc_params* p) { return p->rank_mode == SC_RANK_WEIGHT && !(p->flags & SC_FLAG_NO_PRUNE); }
+int run_triangles(sc_ctx* c, const sc_params* p, bool want_list);
+int decide_filter(sc_ctx* c, const sc_params* p, const Shard& sh);
+int run_score(sc_ctx* c, const sc_params* p, const Shard& sh, uint32_t* rows, bool tile_done, hipEvent_t ev0 = nullptr,
+              hipEvent_t ev1 = nullptr, hipEvent_t ev_mid = nullptr);
+
+}  // namespace sc
