@@ -74,6 +74,13 @@ __device__ __forceinline__ float pair_weight(float dp, float dq, float d_thr, fl
   return edge ? sc_expf((d * d) * neg_inv2sig2) : 0.0f;
 }
 
+// Stage B weight key of triangle (i, j, k), i < j < k: bits((s_ij + s_ik) + s_jk), the two adds in this
+// order.  (The weights lie in (0, 1], so the key is a positive float: its bits order as the floats do, and every
+// later step — select, histograms, sort — works on the integer.)
+__device__ __forceinline__ uint32_t tri_key_weight(float s_ij, float s_ik, float s_jk) {
+  return __float_as_uint((s_ij + s_ik) + s_jk);
+}
+
 // Stage C2/C3 inlier test: e_c = t_c + fma(r_c2,pz, fma(r_c1,py, fma(r_c0,px, -q_c))).
 // (t_c + x is bit-identical to fmaf(t_c, 1, x); the chain is the k-ordered form of a 16x16x4 f32 MFMA
 // with C = -q, kept so an MFMA variant stays bit-compatible.)

@@ -1,4 +1,10 @@
-// sc_block.hpp — workgroup-level reduce / exclusive scan helpers (64-lane waves, LDS cross-wave step).
+// sc_block.hpp — wave- and workgroup-level scan / reduce helpers (64-lane waves, LDS cross-wave step):
+//   mask_above                           bits strictly above one bit of a 64-bit word
+//   wave_inscan                          inclusive scan over the wave (the six __shfl_up steps)
+//   group_exscan                         exclusive scan over a 16- or 64-lane group of the wave, with the group's sum
+//   block_reduce_u64 / block_exscan_u64  sum and exclusive scan over the workgroup
+//   lb_*                                 decoupled look-back over the tiles of one launch
+// (mask_above and group_exscan came from sc_tri.hip; wave_inscan replaces the single-value loops sc_compat.hip and sc_tri.hip wrote out by hand.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -8,6 +14,36 @@ namespace sc {
 // A result the HOST polls for in pinned memory (sc_capi.hip wait_word): one system-scope release store.
 __device__ __forceinline__ void publish_host(uint64_t* p, uint64_t v) {
   __hip_atomic_store(p, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+__device__ __forceinline__ uint64_t mask_above(int bit) {  // bits strictly above `bit` (0..63)
+  return bit == 63 ? 0ull : (~0ull << (bit + 1));
+}
+
+// inclusive scan of one value per lane over the wave: the six __shfl_up steps
+template <typename T>
+__device__ __forceinline__ T wave_inscan(T v) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const T t = __shfl_up(v, o);
+    if (lane >= o) v += t;
+  }
+  return v;
+}
+
+// exclusive prefix over the `width`-lane group of a wave (width = 16 or 64); *total = group sum
+template <int WIDTH>
+__device__ __forceinline__ uint32_t group_exscan(uint32_t v, uint32_t* total) {
+  const int gl = threadIdx.x & (WIDTH - 1);
+  uint32_t inc = v;
+#pragma unroll
+  for (int o = 1; o < WIDTH; o <<= 1) {
+    uint32_t t = __shfl_up(inc, o, WIDTH);
+    if (gl >= o) inc += t;
+  }
+  *total = __shfl(inc, WIDTH - 1, WIDTH);
+  return inc - v;
 }
 
 // sum over the block; lds: >= blockDim.x/64 entries.  Every thread gets the total.
@@ -26,6 +62,8 @@ __device__ __forceinline__ uint64_t block_reduce_u64(uint64_t v, uint64_t* lds) 
 // exclusive scan of one value per thread across the block; returns the exclusive prefix, *total = block sum
 __device__ __forceinline__ uint64_t block_exscan_u64(uint64_t v, uint64_t* lds, uint64_t* total) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  // (wave_inscan's steps, in line on purpose: through the call hipcc orders the loop over the waves below differently in
+  // sc_match.hip's match_finish_kernel — the same instructions in another order — and that file's code was to stay byte for byte)
   uint64_t inc = v;
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) {

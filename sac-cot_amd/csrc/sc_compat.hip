@@ -455,6 +455,35 @@ __global__ __launch_bounds__(64 * COMPAT_WAVES) void compat_tiles_kernel(const f
   }
 }
 
+// What one wave learns from the words of row i (row_stats_kernel, row_stats_scan_kernel): it writes wpre[i][w] = #set bits of
+// the row in words [0, w) and clears the row of zero_rows (optional); d_all = the row's degree (wave-uniform); d_up, cost = this
+// LANE's share of deg+ (bits above i) and of the row's stage B cost (see rowcost below) — the caller sums them over the wave.
+struct RowWordStats { uint32_t d_all, d_up; uint64_t cost; };
+__device__ __forceinline__ RowWordStats row_word_stats(const uint64_t* __restrict__ bits, int i, int W, uint32_t* __restrict__ wpre,
+                                                       uint64_t* __restrict__ zero_rows) {
+  const int lane = threadIdx.x & 63;
+  if (zero_rows)
+    for (int w = lane; w < W; w += 64) zero_rows[(size_t)i * W + w] = 0ull;
+  uint32_t d_all = 0, d_up = 0;
+  uint64_t cost = 0;
+  for (int wb = 0; wb < W; wb += 64) {
+    const int w = wb + lane;
+    const uint64_t v = w < W ? bits[(size_t)i * W + w] : 0ull;
+    const uint32_t pc = (uint32_t)__popcll(v);
+    const uint32_t inc = wave_inscan(pc);  // of the word popcounts
+    if (w < W) {
+      wpre[(size_t)i * W + w] = d_all + inc - pc;
+      uint64_t up = v;
+      if (w < (i >> 6)) up = 0;
+      else if (w == (i >> 6)) up &= mask_above(i & 63);
+      d_up += __popcll(up);
+      cost += (uint64_t)__popcll(up) * (uint64_t)(W - w + 4);
+    }
+    d_all += __shfl(inc, 63);
+  }
+  return RowWordStats{d_all, d_up, cost};
+}
+
 // deg[i], degp[i] (bits above i) and wpre[i][w] = #set bits of row i in words [0, w): one wave per row.
 // rowcost (optional): estimate of stage B's work for the edges (i, j), j > i, of row i — the words the counting pass
 // ANDs for each of them plus a constant: sum over j of (W - j / 64 + 4), saturated to u32.  Its prefix over the rows
@@ -467,39 +496,16 @@ __global__ __launch_bounds__(256) void row_stats_kernel(const uint64_t* __restri
   const int lane = threadIdx.x & 63;
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (i >= n) return;
-  if (zero_rows)
-    for (int w = lane; w < W; w += 64) zero_rows[(size_t)i * W + w] = 0ull;
-  uint32_t d_all = 0, d_up = 0;
-  uint64_t cost = 0;
-  for (int wb = 0; wb < W; wb += 64) {
-    const int w = wb + lane;
-    const uint64_t v = w < W ? bits[(size_t)i * W + w] : 0ull;
-    const uint32_t pc = (uint32_t)__popcll(v);
-    uint32_t inc = pc;  // inclusive wave scan of the word popcounts
+  RowWordStats rs = row_word_stats(bits, i, W, wpre, zero_rows);
 #pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t t = __shfl_up(inc, o);
-      if (lane >= o) inc += t;
-    }
-    if (w < W) {
-      wpre[(size_t)i * W + w] = d_all + inc - pc;
-      uint64_t up = v;
-      if (w < (i >> 6)) up = 0;
-      else if (w == (i >> 6)) up &= ((i & 63) == 63) ? 0ull : (~0ull << ((i & 63) + 1));
-      d_up += __popcll(up);
-      cost += (uint64_t)__popcll(up) * (uint64_t)(W - w + 4);
-    }
-    d_all += __shfl(inc, 63);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) d_up += __shfl_xor(d_up, o);
+  for (int o = 32; o > 0; o >>= 1) rs.d_up += __shfl_xor(rs.d_up, o);
   if (rowcost) {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) cost += __shfl_xor(cost, o);
+    for (int o = 32; o > 0; o >>= 1) rs.cost += __shfl_xor(rs.cost, o);
   }
   if (lane == 0) {
-    deg[i] = d_all; degp[i] = d_up;
-    if (rowcost) rowcost[i] = cost > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)cost;
+    deg[i] = rs.d_all; degp[i] = rs.d_up;
+    if (rowcost) rowcost[i] = rs.cost > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)rs.cost;
   }
 }
 
@@ -534,28 +540,8 @@ __global__ __launch_bounds__(1024) void row_stats_scan_kernel(const uint64_t* __
     uint32_t d_all = 0, d_up = 0;
     uint64_t cost = 0;
     if (i < n) {  // wave-uniform
-      if (zero_rows)
-        for (int w = lane; w < W; w += 64) zero_rows[(size_t)i * W + w] = 0ull;
-      for (int wb = 0; wb < W; wb += 64) {
-        const int w = wb + lane;
-        const uint64_t v = w < W ? bits[(size_t)i * W + w] : 0ull;
-        const uint32_t pc = (uint32_t)__popcll(v);
-        uint32_t inc = pc;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-          const uint32_t t = __shfl_up(inc, o);
-          if (lane >= o) inc += t;
-        }
-        if (w < W) {
-          wpre[(size_t)i * W + w] = d_all + inc - pc;
-          uint64_t up = v;
-          if (w < (i >> 6)) up = 0;
-          else if (w == (i >> 6)) up &= ((i & 63) == 63) ? 0ull : (~0ull << ((i & 63) + 1));
-          d_up += __popcll(up);
-          cost += (uint64_t)__popcll(up) * (uint64_t)(W - w + 4);
-        }
-        d_all += __shfl(inc, 63);
-      }
+      const RowWordStats rs = row_word_stats(bits, i, W, wpre, zero_rows);
+      d_all = rs.d_all; d_up = rs.d_up; cost = rs.cost;
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) { d_up += __shfl_xor(d_up, o); cost += __shfl_xor(cost, o); }
     }
@@ -567,12 +553,7 @@ __global__ __launch_bounds__(1024) void row_stats_scan_kernel(const uint64_t* __
   __syncthreads();
   if (threadIdx.x >= 64) return;  // wave 0: scan of the tile's 64 rows, look-back, outputs
   const uint64_t mine_e = lane < RS_ROWS ? l_degp[lane] : 0u, mine_c = lane < RS_ROWS ? l_cost[lane] : 0ull;
-  uint64_t inc_e = mine_e, inc_c = mine_c;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint64_t te = __shfl_up(inc_e, o), tc = __shfl_up(inc_c, o);
-    if (lane >= o) { inc_e += te; inc_c += tc; }
-  }
+  const uint64_t inc_e = wave_inscan(mine_e), inc_c = wave_inscan(mine_c);
   const uint64_t tot_e = __shfl(inc_e, 63), tot_c = __shfl(inc_c, 63);
   uint64_t* const desc[2] = {lb.desc, lb.desc + nb};
   const uint64_t own[2] = {tot_e, tot_c};
@@ -802,6 +783,8 @@ __device__ __forceinline__ void scan_tile_load(const uint32_t* __restrict__ in, 
     for (int k = 0; k < 4; k++) { t.v[r][k] = (!dead && scan_live(range, idx + k)) ? t.v[r][k] : 0u; a += t.v[r][k]; }
     mine[r] = a; inc[r] = a;
   }
+  // (wave_inscan's steps for the SCAN_SUB values TOGETHER, step by step: one value after the other, hipcc waits for each sub-tile's
+  // load in turn where this form has all four in flight — 19 more s_waitcnt in scan_lookback_kernel, the hot path's scan)
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1)
 #pragma unroll

@@ -1786,10 +1786,19 @@ void launch_score_filter(const Points& pts, const float* RtSoA, const float* RtA
   // C2's 0.15 M entries are served by 2, more only adds launch tail)
   const uint64_t tests = (uint64_t)pts.n * sh.ld_local;
   const uint32_t exact_mult = tests >= (1ull << 31) ? 8u : (tests >= (1ull << 29) ? 4u : 2u);
+  // hperm / pperm / frame: the Gram filter's permutations and frame (all null after the linear filter)
+  auto launch_exact = [&](const uint32_t* hperm, const uint32_t* pperm, const GramFrame* gframe) {
+    SC_LAUNCH_EV(score_exact_kernel, dim3(FX_NQ * exact_mult), dim3(256), st, (hipEvent_t) nullptr, ev1, pts.planes, pts.n, pts.ld,
+                          reinterpret_cast<const float4*>(RtAoS), sh.ld_local, dv.tau2, fp.windows, fp.splits, fp.n_waves,
+                          static_cast<const uint2*>(f.queue), f.cap_sq, static_cast<const uint32_t*>(f.qcount),
+                          static_cast<const uint32_t*>(f.redo), partial, hperm, pperm, gframe);
+  };
+  // entries of the filter's LDS queue: the kernel's own size unless tuned smaller; one step can add 64 entries
+  const uint32_t ql_max = fp.mode == 2 ? (uint32_t)GX_QL : (uint32_t)FX_QL;
+  uint32_t ql = tn.filter_lds_queue ? tn.filter_lds_queue : ql_max;
+  if (ql > ql_max) ql = ql_max;
+  if (ql < 64) ql = 64;
   if (fp.mode == 2) {
-    uint32_t ql = tn.filter_lds_queue ? tn.filter_lds_queue : (uint32_t)GX_QL;
-    if (ql > (uint32_t)GX_QL) ql = GX_QL;
-    if (ql < 64) ql = 64;
     const GramCoef gc = gram_coef_view(coef, sh.ld_local, frame);
     const uint32_t group_major = (uint64_t)((sh.ld_local + 32 * GX_WAVES - 1) / (32 * GX_WAVES)) * fp.splits <= 1024u ? 1u : 0u;  // (see the kernel)
 #define SC_GRAM_LAUNCH(V)                                                                                                         \
@@ -1813,16 +1822,9 @@ void launch_score_filter(const Points& pts, const float* RtSoA, const float* RtA
       default: SC_GRAM_LAUNCH(0); break;
     }
 #undef SC_GRAM_LAUNCH
-    SC_LAUNCH_EV(score_exact_kernel, dim3(FX_NQ * exact_mult), dim3(256), st, (hipEvent_t) nullptr, ev1, pts.planes, pts.n, pts.ld,
-                          reinterpret_cast<const float4*>(RtAoS), sh.ld_local, dv.tau2, fp.windows, fp.splits, fp.n_waves,
-                          static_cast<const uint2*>(f.queue), f.cap_sq, static_cast<const uint32_t*>(f.qcount),
-                          static_cast<const uint32_t*>(f.redo), partial, static_cast<const uint32_t*>(gc.hperm),
-                          static_cast<const uint32_t*>(gc.pperm), static_cast<const GramFrame*>(gc.frame));
+    launch_exact(gc.hperm, gc.pperm, gc.frame);
     return;
   }
-  uint32_t ql = tn.filter_lds_queue ? tn.filter_lds_queue : (uint32_t)FX_QL;
-  if (ql > (uint32_t)FX_QL) ql = FX_QL;
-  if (ql < 64) ql = 64;  // one step can add 64 entries
   const dim3 grid(sh.ld_local / (8 * FX_WAVES), fp.splits), block(64 * FX_WAVES);
 #define SC_FILTER_LAUNCH(V)                                                                                                  \
   SC_LAUNCH_EV((score_filter_kernel<FX_WAVES, V>), grid, block, st, ev0, ev_mid, RtSoA, sh.ld_local, dv.tau2, \
@@ -1850,11 +1852,7 @@ void launch_score_filter(const Points& pts, const float* RtSoA, const float* RtA
     default: SC_FILTER_LAUNCH(0); break;
   }
 #undef SC_FILTER_LAUNCH
-  SC_LAUNCH_EV(score_exact_kernel, dim3(FX_NQ * exact_mult), dim3(256), st, (hipEvent_t) nullptr, ev1, pts.planes, pts.n, pts.ld,
-                        reinterpret_cast<const float4*>(RtAoS), sh.ld_local, dv.tau2, fp.windows, fp.splits, fp.n_waves,
-                        static_cast<const uint2*>(f.queue), f.cap_sq, static_cast<const uint32_t*>(f.qcount),
-                        static_cast<const uint32_t*>(f.redo), partial, static_cast<const uint32_t*>(nullptr),
-                        static_cast<const uint32_t*>(nullptr), static_cast<const GramFrame*>(nullptr));
+  launch_exact(nullptr, nullptr, nullptr);
 }
 
 hipError_t filter_read_counters(const void* state, const FilterPlan& fp, hipStream_t st, uint64_t* undecided, uint64_t* recounts) {

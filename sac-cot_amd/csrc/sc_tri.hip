@@ -21,25 +21,6 @@
 
 namespace sc {
 
-__device__ __forceinline__ uint64_t mask_above(int bit) {  // bits strictly above `bit` (0..63)
-  return bit == 63 ? 0ull : (~0ull << (bit + 1));
-}
-
-// exclusive prefix over the `width`-lane group of a wave (width = 16 or 64); *total = group sum
-template <int WIDTH>
-__device__ __forceinline__ uint32_t group_exscan(uint32_t v, uint32_t* total) {
-  const int gl = threadIdx.x & (WIDTH - 1);
-  uint32_t inc = v;
-#pragma unroll
-  for (int o = 1; o < WIDTH; o <<= 1) {
-    uint32_t t = __shfl_up(inc, o, WIDTH);
-    if (gl >= o) inc += t;
-  }
-  *total = __shfl(inc, WIDTH - 1, WIDTH);
-  return inc - v;
-}
-
-
 // Pop up to four set bits of m (lowest first).  nb = how many were popped; b[] are their positions (0 for unused
 // slots, so derived indices stay in range).  Lets a lane issue the gathers of four triangles before it consumes the
 // first: a lane's triangles would otherwise cost one dependent L2 round trip each.
@@ -53,6 +34,99 @@ __device__ __forceinline__ int pop4(uint64_t& m, int b[4]) {
     nb += has ? 1 : 0;
   }
   return nb;
+}
+
+// One end of an edge at one 64-column word: the CSR index of the word's first edge (row base + wpre) and the full-graph
+// word; edge (v, k) of that row then sits at first + popc(word & below k).
+struct CsrWord { uint32_t first; uint64_t word; };
+
+// The weights s_ik, s_jk of one pop4 batch.  All eight gathers are issued before the first use; idle slots read es[0]
+// (their modular index may be out of range).
+__device__ __forceinline__ void tri_weights4(const float* __restrict__ es, const int (&b)[4], int nbits, CsrWord ri,
+                                             CsrWord rj, float (&s_ik)[4], float (&s_jk)[4]) {
+#pragma unroll
+  for (int q = 0; q < 4; q++) {
+    const uint64_t below = (1ull << b[q]) - 1ull;
+    const bool live = q < nbits;
+    s_ik[q] = es[live ? ri.first + (uint32_t)__popcll(ri.word & below) : 0u];
+    s_jk[q] = es[live ? rj.first + (uint32_t)__popcll(rj.word & below) : 0u];
+  }
+}
+
+// The extremes of a 256-thread block's keys -> one plain store per block (no same-address atomics: they serialise at
+// ~12 ns each).  Every thread calls it.
+__device__ __forceinline__ void block_minmax_store(uint32_t kmin, uint32_t kmax, uint32_t* __restrict__ blk_min,
+                                                   uint32_t* __restrict__ blk_max) {
+  __shared__ uint32_t lmin[4], lmax[4];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    kmin = min(kmin, (uint32_t)__shfl_xor(kmin, o));
+    kmax = max(kmax, (uint32_t)__shfl_xor(kmax, o));
+  }
+  if ((threadIdx.x & 63) == 0) { lmin[threadIdx.x >> 6] = kmin; lmax[threadIdx.x >> 6] = kmax; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    blk_min[blockIdx.x] = min(min(lmin[0], lmin[1]), min(lmin[2], lmin[3]));
+    blk_max[blockIdx.x] = max(max(lmax[0], lmax[1]), max(lmax[2], lmax[3]));
+  }
+}
+
+// A row's upper-triangle edges, as edge_fill_kernel and edge_build_kernel emit them.  RowSide: what every edge of row i
+// needs of the row itself — its correspondence (wave-uniform: scalar loads), the AoS copy behind the planes that the
+// other end is gathered from (8 floats per correspondence: two 16-byte loads) and the pair test's constants.
+// EdgeOut: the CSR arrays and the entries they hold (writes beyond cap are dropped).
+struct RowSide {
+  int i;
+  float px, py, pz, qx, qy, qz;
+  const float4* __restrict__ aos4;
+  Derived dv;
+};
+struct EdgeOut { uint32_t* __restrict__ ei; uint32_t* __restrict__ ej; float* __restrict__ es; uint64_t cap; };
+
+__device__ __forceinline__ RowSide row_side(const float* __restrict__ planes, int ld, int i, const Derived& dv) {
+  return RowSide{i, planes[i], planes[ld + i], planes[2 * ld + i], planes[3 * ld + i], planes[4 * ld + i], planes[5 * ld + i],
+                 reinterpret_cast<const float4*>(planes + 6 * (size_t)ld), dv};
+}
+
+// One wave, one round of 64 words of the row: lane holds word w with only the bits above the diagonal left in v; the edges go
+// to base, base + 1, ... in column order.  CH column indices are staged per chunk in l_j (this wave's); extra(e, j, weight)
+// runs after the three stores of each edge.  Returns the number of edges of the round.
+template <int CH, typename Extra>
+__device__ __forceinline__ uint32_t row_edges_emit(uint32_t* l_j, uint64_t v, int w, uint64_t base, const RowSide& row,
+                                                   const EdgeOut& out, Extra extra) {
+  const int lane = threadIdx.x & 63;
+  uint32_t tot;
+  const uint32_t r = group_exscan<64>((uint32_t)__popcll(v), &tot);
+  for (uint32_t c0 = 0; c0 < tot; c0 += CH) {  // wave-uniform; one chunk unless the row is very dense
+    // (1) divergent part, LDS only: the columns of this chunk in ascending order
+    uint64_t vv = v;
+    uint32_t rr = r - c0;  // modular: positions outside [0, CH) are skipped
+    while (vv) {
+      const int b = __builtin_ctzll(vv);
+      vv &= vv - 1;
+      if (rr < (uint32_t)CH) l_j[rr] = (uint32_t)(w * 64 + b);
+      rr++;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // LDS is in-order within a wave
+    // (2) flat part, one lane per edge: gathers, weight, coalesced stores
+    const uint32_t cnt = min((uint32_t)CH, tot - c0);
+    for (uint32_t t = lane; t < cnt; t += 64) {
+      const uint32_t j = l_j[t];
+      const uint64_t e = base + c0 + t;
+      if (e >= out.cap) continue;
+      const float4 a4 = row.aos4[2 * (size_t)j], b4 = row.aos4[2 * (size_t)j + 1];
+      const float dp = dist3(row.px, row.py, row.pz, a4.x, a4.y, a4.z);
+      const float dq = dist3(row.qx, row.qy, row.qz, a4.w, b4.x, b4.y);
+      bool edge;
+      const float sw = pair_weight(dp, dq, row.dv.d_thr, row.dv.min_len, row.dv.neg_inv2sig2, edge);
+      out.ei[e] = (uint32_t)row.i;
+      out.ej[e] = j;
+      out.es[e] = sw;
+      extra(e, j, sw);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // l_j is rewritten by the next chunk
+  }
+  return tot;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -98,9 +172,8 @@ __global__ __launch_bounds__(256) void edge_fill_kernel(const uint64_t* __restri
   const uint32_t my_base = ebase_ready ? ebase[i] : (uint32_t)base - (deg[i] - degp[i]);
   if (!ebase_ready && lane == 0) ebase[i] = my_base;
   const int w0 = i >> 6;
-  const float pix = planes[i], piy = planes[ld + i], piz = planes[2 * ld + i];  // wave-uniform: scalar loads
-  const float qix = planes[3 * ld + i], qiy = planes[4 * ld + i], qiz = planes[5 * ld + i];
-  const float4* __restrict__ aos4 = reinterpret_cast<const float4*>(planes + 6 * (size_t)ld);
+  const RowSide row = row_side(planes, ld, i, dv);
+  const EdgeOut out{ei, ej, es, cap};
   for (int wb = w0; wb < W; wb += 64) {
     const int w = wb + lane;
     uint64_t v = 0;
@@ -108,42 +181,12 @@ __global__ __launch_bounds__(256) void edge_fill_kernel(const uint64_t* __restri
       v = bits[(size_t)i * W + w];
       if (w == w0) v &= mask_above(i & 63);
     }
-    uint32_t tot;
-    const uint32_t r = group_exscan<64>((uint32_t)__popcll(v), &tot);
-    for (uint32_t c0 = 0; c0 < tot; c0 += CH) {  // wave-uniform; one chunk unless the row is very dense
-      // (1) divergent part, LDS only: the columns of this chunk in ascending order
-      uint64_t vv = v;
-      uint32_t rr = r - c0;  // modular: positions outside [0, CH) are skipped
-      while (vv) {
-        const int b = __builtin_ctzll(vv);
-        vv &= vv - 1;
-        if (rr < (uint32_t)CH) l_j[wave][rr] = (uint32_t)(w * 64 + b);
-        rr++;
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // LDS is in-order within a wave
-      // (2) flat part, one lane per edge: gathers, weight, coalesced stores
-      const uint32_t cnt = min((uint32_t)CH, tot - c0);
-      for (uint32_t t = lane; t < cnt; t += 64) {
-        const uint32_t j = l_j[wave][t];
-        const uint64_t e = base + c0 + t;
-        if (e >= cap) continue;
-        // the other end from the AoS copy behind the planes (8 floats per correspondence): two 16-byte loads
-        const float4 a4 = aos4[2 * (size_t)j], b4 = aos4[2 * (size_t)j + 1];
-        const float dp = dist3(pix, piy, piz, a4.x, a4.y, a4.z);
-        const float dq = dist3(qix, qiy, qiz, a4.w, b4.x, b4.y);
-        bool edge;
-        const float sw = pair_weight(dp, dq, dv.d_thr, dv.min_len, dv.neg_inv2sig2, edge);
-        ei[e] = (uint32_t)i;
-        ej[e] = j;
-        es[e] = sw;
-        if (es_hist) atomicAdd(&l_h[lane & 1][weight_bin(__float_as_uint(sw), 0u, 0u)], 1u);  // integer sums: order-free
-        // both CSR bases travel with the edge, so stage B fetches an edge in ONE memory level
-        ebi[e] = my_base;
-        ebj[e] = ebase_ready ? ebase[j] : (uint32_t)edge_off[j] - (deg[j] - degp[j]);
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    }
-    base += tot;
+    base += row_edges_emit<CH>(l_j[wave], v, w, base, row, out, [&](uint64_t e, uint32_t j, float sw) {
+      if (es_hist) atomicAdd(&l_h[lane & 1][weight_bin(__float_as_uint(sw), 0u, 0u)], 1u);  // integer sums: order-free
+      // both CSR bases travel with the edge, so stage B fetches an edge in ONE memory level
+      ebi[e] = my_base;
+      ebj[e] = ebase_ready ? ebase[j] : (uint32_t)edge_off[j] - (deg[j] - degp[j]);
+    });
   }
   }  // i < n
   if (es_hist) {
@@ -270,7 +313,6 @@ __global__ __launch_bounds__(256) void tri_keys_kernel(const uint64_t* __restric
                                                        uint32_t* __restrict__ blk_min,
                                                        uint32_t* __restrict__ blk_max,
                                                        const uint64_t* __restrict__ own) {
-  __shared__ uint32_t lmin[4], lmax[4];
   const int gl = threadIdx.x & (TG - 1);
   const uint64_t own_lo = own ? own[0] : 0ull, own_hi = own ? own[1] : E;
   const uint64_t gmask = (TG == 64) ? ~0ull : (((1ull << TG) - 1ull) << ((threadIdx.x & 63) & ~(TG - 1)));
@@ -312,17 +354,9 @@ __global__ __launch_bounds__(256) void tri_keys_kernel(const uint64_t* __restric
           uint32_t key[4];
           if (rank_mode == 0) {
             float s_ik[4], s_jk[4];
+            tri_weights4(es, b, nbits, {pi, fi}, {pj, fj}, s_ik, s_jk);
 #pragma unroll
-            for (int q = 0; q < 4; q++) {  // all eight gathers are issued before the first use
-              const uint64_t below = (1ull << b[q]) - 1ull;
-              const bool live = q < nbits;  // idle slots read es[0]: their modular index may be out of range
-              const uint32_t xi = live ? pi + (uint32_t)__popcll(fi & below) : 0u;
-              const uint32_t xj = live ? pj + (uint32_t)__popcll(fj & below) : 0u;
-              s_ik[q] = es[xi];
-              s_jk[q] = es[xj];
-            }
-#pragma unroll
-            for (int q = 0; q < 4; q++) key[q] = __float_as_uint((s_ij + s_ik[q]) + s_jk[q]);
+            for (int q = 0; q < 4; q++) key[q] = tri_key_weight(s_ij, s_ik[q], s_jk[q]);
           } else {
 #pragma unroll
             for (int q = 0; q < 4; q++) key[q] = dsum_ij + deg[w * 64 + b[q]];
@@ -340,18 +374,7 @@ __global__ __launch_bounds__(256) void tri_keys_kernel(const uint64_t* __restric
       }
     }
   }
-  // block min/max -> one plain store per block (no same-address atomics: they serialise at ~12 ns each)
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    kmin = min(kmin, (uint32_t)__shfl_xor(kmin, o));
-    kmax = max(kmax, (uint32_t)__shfl_xor(kmax, o));
-  }
-  if ((threadIdx.x & 63) == 0) { lmin[threadIdx.x >> 6] = kmin; lmax[threadIdx.x >> 6] = kmax; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    blk_min[blockIdx.x] = min(min(lmin[0], lmin[1]), min(lmin[2], lmin[3]));
-    blk_max[blockIdx.x] = max(max(lmax[0], lmax[1]), max(lmax[2], lmax[3]));
-  }
+  block_minmax_store(kmin, kmax, blk_min, blk_max);
 }
 
 __global__ __launch_bounds__(1024) void key_range_kernel(const uint32_t* __restrict__ blk_min,
@@ -579,7 +602,6 @@ __global__ __launch_bounds__(256) void tri_keys_events_kernel(const uint64_t* __
   // cap: entries wkey / kcol hold.  The host may launch this kernel BEFORE it knows the triangle count (into the
   // arrays of the previous call, while it polls for the count): writes beyond cap are dropped and the host re-runs.
   // For the same reason `want` is clipped here to the count the scan left in toff[E].
-  __shared__ uint32_t lmin[4], lmax[4];
   __shared__ uint64_t pre[EV_SHARDS + 1];
   // Weight keys of a graph whose edges all weigh >= 2/3 live in one binade, [2.0, 3.0]: the select window is known
   // before a single key exists — [certified bound (or 2.0), 3.0] — so no key-range pass, and two 12-bit rounds
@@ -628,17 +650,11 @@ __global__ __launch_bounds__(256) void tri_keys_events_kernel(const uint64_t* __
           int b[4];
           const int nbits = pop4(m, b);
           float s_ik[4], s_jk[4];
-#pragma unroll
-          for (int q = 0; q < 4; q++) {
-            const uint64_t below = (1ull << b[q]) - 1ull;
-            const bool live = q < nbits;  // idle slots read es[0]
-            s_ik[q] = es[live ? pi + (uint32_t)__popcll(fi & below) : 0u];
-            s_jk[q] = es[live ? pj + (uint32_t)__popcll(fj & below) : 0u];
-          }
+          tri_weights4(es, b, nbits, {pi, fi}, {pj, fj}, s_ik, s_jk);
 #pragma unroll
           for (int q = 0; q < 4; q++) {
             if (q < nbits) {
-              const uint32_t key = __float_as_uint((s_ij + s_ik[q]) + s_jk[q]);
+              const uint32_t key = tri_key_weight(s_ij, s_ik[q], s_jk[q]);
               if (out < cap) { kcol[out] = make_uint2(kbase + (uint32_t)b[q], e); wkey[out] = key; }
               out++;
               kmin = min(kmin, key);
@@ -659,17 +675,7 @@ __global__ __launch_bounds__(256) void tri_keys_events_kernel(const uint64_t* __
       }
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    kmin = min(kmin, (uint32_t)__shfl_xor(kmin, o));
-    kmax = max(kmax, (uint32_t)__shfl_xor(kmax, o));
-  }
-  if ((threadIdx.x & 63) == 0) { lmin[threadIdx.x >> 6] = kmin; lmax[threadIdx.x >> 6] = kmax; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    blk_min[blockIdx.x] = min(min(lmin[0], lmin[1]), min(lmin[2], lmin[3]));
-    blk_max[blockIdx.x] = max(max(lmax[0], lmax[1]), max(lmax[2], lmax[3]));
-  }
+  block_minmax_store(kmin, kmax, blk_min, blk_max);
 }
 
 size_t event_bytes(uint64_t capacity) { return (size_t)capacity * 32 + EV_SHARDS * 4 + 64; }
@@ -746,6 +752,22 @@ void launch_tri_keys_events(const Graph& g, const float* es, const uint64_t* tof
 constexpr int PR_BINS = 256;   // coarse is enough: LB only needs to be a valid, reasonably tight lower bound
 constexpr int PR_COPIES = 16;  // one private copy per lane-in-group: same-bin hits land on different LDS words
 constexpr int EST_COPIES = 4;  // the estimating sample (one lane per edge, ~200 hits per workgroup): fewer copies to clear and to add up
+
+// Flush of a workgroup's LDS histogram, COPIES rotated copies laid out [bin][copy], into one of PR_HCOPIES global copies
+// (by block): a thousand blocks adding into the SAME 256 words serialise at the memory side (~12 ns per add and address);
+// the copies are summed by the reader.  Every thread of a 256-thread block calls it; it starts with the barrier that
+// ends the counting.
+template <int COPIES>
+__device__ __forceinline__ void hist_flush(const uint32_t* lh, uint32_t* __restrict__ hist) {
+  __syncthreads();
+  uint32_t* __restrict__ myh = hist + (size_t)(blockIdx.x & (PR_HCOPIES - 1)) * PR_BINS;
+  for (int b = threadIdx.x; b < PR_BINS; b += 256) {
+    uint32_t v = 0;
+#pragma unroll
+    for (int c = 0; c < COPIES; c++) v += lh[b * COPIES + ((c + threadIdx.x) & (COPIES - 1))];
+    if (v) atomicAdd(&myh[b], v);
+  }
+}
 
 __device__ __forceinline__ uint32_t prune_bin(uint32_t key, uint32_t klo, uint32_t shift) {
   if (key <= klo) return 0u;
@@ -896,17 +918,11 @@ __global__ __launch_bounds__(256) void tri_sample_hist_kernel(const uint64_t* __
           int b[4];
           const int nbits = pop4(mr, b);
           float s_ik[4], s_jk[4];
-#pragma unroll
-          for (int q = 0; q < 4; q++) {
-            const uint64_t below = (1ull << b[q]) - 1ull;
-            const bool live = q < nbits;
-            s_ik[q] = es[live ? pi[r] + (uint32_t)__popcll(ai[r] & below) : 0u];
-            s_jk[q] = es[live ? pj[r] + (uint32_t)__popcll(aj[r] & below) : 0u];
-          }
+          tri_weights4(es, b, nbits, {pi[r], ai[r]}, {pj[r], aj[r]}, s_ik, s_jk);
 #pragma unroll
           for (int q = 0; q < 4; q++)
             if (q < nbits)
-              atomicAdd(&lh[prune_bin(__float_as_uint((s_ij + s_ik[q]) + s_jk[q]), klo, shift) * PR_COPIES +
+              atomicAdd(&lh[prune_bin(tri_key_weight(s_ij, s_ik[q], s_jk[q]), klo, shift) * PR_COPIES +
                             (threadIdx.x & (PR_COPIES - 1))], 1u);
         }
       }
@@ -914,16 +930,7 @@ __global__ __launch_bounds__(256) void tri_sample_hist_kernel(const uint64_t* __
   }
   if (TOP) __syncthreads();  // l_e is rewritten by the next chunk
   }  // chunks
-  __syncthreads();
-  // flush into one of PR_HCOPIES global copies (by block): a thousand blocks adding into the SAME 256 words serialise
-  // at the memory side (~12 ns per add and address); the copies are summed by the reader
-  uint32_t* __restrict__ myh = hist + (size_t)(blockIdx.x & (PR_HCOPIES - 1)) * PR_BINS;
-  for (int b = threadIdx.x; b < PR_BINS; b += 256) {
-    uint32_t v = 0;
-#pragma unroll
-    for (int c = 0; c < PR_COPIES; c++) v += lh[b * PR_COPIES + ((c + threadIdx.x) & (PR_COPIES - 1))];
-    if (v) atomicAdd(&myh[b], v);
-  }
+  hist_flush<PR_COPIES>(lh, hist);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1005,31 +1012,18 @@ __global__ __launch_bounds__(256) void tri_sample_words_kernel(const uint64_t* _
         int b[4];
         const int nbits = pop4(m, b);
         float s_ik[4], s_jk[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-          const uint64_t below = (1ull << b[q]) - 1ull;
-          const bool live = q < nbits;
-          s_ik[q] = es[live ? pi + (uint32_t)__popcll(ai & below) : 0u];
-          s_jk[q] = es[live ? pj + (uint32_t)__popcll(aj & below) : 0u];
-        }
+        tri_weights4(es, b, nbits, {pi, ai}, {pj, aj}, s_ik, s_jk);
 #pragma unroll
         for (int q = 0; q < 4; q++)
           if (q < nbits) {
-            const uint32_t kb = __float_as_uint((s_ij + s_ik[q]) + s_jk[q]);  // (keys are positive floats: their bits order like they do)
+            const uint32_t kb = tri_key_weight(s_ij, s_ik[q], s_jk[q]);
             atomicAdd(&lh[est_bin(kb) * EST_COPIES + (threadIdx.x & (EST_COPIES - 1))], 1u);
             if (track && kb > best_key) { best_key = kb; best_e = (uint32_t)e; best_k = (uint32_t)(64 * w + b[q]); }
           }
       }
     }
   }
-  __syncthreads();
-  uint32_t* __restrict__ myh = hist + (size_t)(blockIdx.x & (PR_HCOPIES - 1)) * PR_BINS;
-  for (int b = threadIdx.x; b < PR_BINS; b += 256) {
-    uint32_t v = 0;
-#pragma unroll
-    for (int c = 0; c < EST_COPIES; c++) v += lh[b * EST_COPIES + ((c + threadIdx.x) & (EST_COPIES - 1))];
-    if (v) atomicAdd(&myh[b], v);
-  }
+  hist_flush<EST_COPIES>(lh, hist);
   if (track) {  // (workgroup-uniform) the workgroup's best: by key, then by lowest thread — the sample is deterministic, so is this
     __shared__ uint32_t s_best[4], s_who[4];
     uint32_t bk = best_key;
@@ -1115,10 +1109,10 @@ __global__ __launch_bounds__(64 * EBK_ROWS) void edge_build_kernel(const uint64_
   for (int w8 = 0; w8 < EBK_ROWS; w8++) my_off += s_red[w8];
   for (int r = r0; r < i; r++) my_off += degp[r];  // wave-uniform: scalar loads
   const int wi = i >> 6, bi = i & 63;
-  const float4* __restrict__ aos4 = reinterpret_cast<const float4*>(planes + 6 * (size_t)ld);
-  const float pix = planes[i], piy = planes[ld + i], piz = planes[2 * ld + i];
-  const float qix = planes[3 * ld + i], qiy = planes[4 * ld + i], qiz = planes[5 * ld + i];
-  // ---- the row's words: prefix popcounts, the strong row cleared
+  const RowSide row = row_side(planes, ld, i, dv);
+  const EdgeOut out{ei, ej, es, cap};
+  // ---- the row's words: prefix popcounts, the strong row cleared (not sc_compat.hip's row_word_stats: this form keeps the
+  // upper-triangle words in registers for the edges below and counts the bits BELOW the diagonal, for the CSR base)
   uint32_t d_all = 0, d_low = 0;
   uint64_t up[NCH];
 #pragma unroll
@@ -1144,36 +1138,8 @@ __global__ __launch_bounds__(64 * EBK_ROWS) void edge_build_kernel(const uint64_
   // ---- edges, chunk by chunk
   uint64_t ebase_row = my_off;
 #pragma unroll
-  for (int c = 0; c < NCH; c++) {
-    const int w = 64 * c + lane;
-    const uint64_t v = up[c];
-    uint32_t tot;
-    const uint32_t r = group_exscan<64>((uint32_t)__popcll(v), &tot);
-    for (uint32_t c0 = 0; c0 < tot; c0 += EBK_CH) {  // wave-uniform
-      uint64_t vv = v;
-      uint32_t rr = r - c0;  // modular: positions outside [0, EBK_CH) are skipped
-      while (vv) {
-        const int b = __builtin_ctzll(vv);
-        vv &= vv - 1;
-        if (rr < (uint32_t)EBK_CH) l_j[wave][rr] = (uint32_t)(w * 64 + b);
-        rr++;
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // LDS is in-order within a wave
-      const uint32_t cnt = min((uint32_t)EBK_CH, tot - c0);
-      for (uint32_t t = lane; t < cnt; t += 64) {
-        const uint32_t j = l_j[wave][t];
-        const uint64_t e = ebase_row + c0 + t;
-        if (e >= cap) continue;
-        const float4 a4 = aos4[2 * (size_t)j], b4 = aos4[2 * (size_t)j + 1];
-        bool edge;
-        const float sw = pair_weight(dist3(pix, piy, piz, a4.x, a4.y, a4.z), dist3(qix, qiy, qiz, a4.w, b4.x, b4.y), dv.d_thr, dv.min_len,
-                                     dv.neg_inv2sig2, edge);
-        ei[e] = (uint32_t)i; ej[e] = j; es[e] = sw;
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // l_j is rewritten by the next chunk
-    }
-    ebase_row += tot;
-  }
+  for (int c = 0; c < NCH; c++)
+    ebase_row += row_edges_emit<EBK_CH>(l_j[wave], up[c], 64 * c + lane, ebase_row, row, out, [](uint64_t, uint32_t, float) {});
   if (i == n - 1 && lane == 0) {  // the last row's wave knows the edge count: the host polls for it
     edge_off[n] = ebase_row;
     if (live_range) { live_range[0] = 0ull; live_range[1] = ebase_row; }
@@ -1528,9 +1494,7 @@ __global__ __launch_bounds__(1024) void cost_split_kernel(const uint32_t* __rest
       const int r = rb + 4 * lane;
       const uint4 v = cost4(rowcost, r, r1);
       const uint64_t lane_sum = (uint64_t)v.x + v.y + v.z + v.w;
-      uint64_t inc = lane_sum;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) { const uint64_t t = __shfl_up(inc, o); if (lane >= o) inc += t; }
+      const uint64_t inc = wave_inscan(lane_sum);
       const uint64_t b0 = run + inc - lane_sum;              // sum of the costs before row r
       const uint64_t b1 = b0 + v.x, b2 = b1 + v.y, b3 = b2 + v.z;
       // the first of this lane's four rows whose "before" reaches the target (4: none)
