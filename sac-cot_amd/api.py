@@ -38,6 +38,7 @@ SC_HIST_WORDS = 256  # u32 words of the pruning-sample histogram (sc_hypothesize
 EXPORTS = ["sc_version", "sc_strerror", "sc_default_params", "sc_create", "sc_destroy", "sc_set_stream",
            "sc_last_error", "sc_set_debug", "sc_debug_last", "sc_register", "sc_register_device", "sc_register_device_async", "sc_wait",
            "sc_peel", "sc_peel_device", "sc_register_instances",
+           "sc_polish_default_params", "sc_polish_device", "sc_polish",
            "sc_match_default_params", "sc_match_device", "sc_match", "sc_register_features",
            "sc_hypothesize_device", "sc_finalize_device",
            "sc_hypothesize_begin_device", "sc_hypothesize_end_device", "sc_finalize_gathered_device", "sc_finalize_gathered_device_async",
@@ -72,6 +73,23 @@ class ScMatchParams(C.Structure):
     """Mirror of `sc_match_params` (include/saccot.h): descriptor length, neighbours per row (1 .. 4), SC_MATCH_* flags, ratio test."""
     _fields_ = [("size", C.c_uint32), ("dim", C.c_uint32), ("knn", C.c_uint32), ("flags", C.c_uint32), ("ratio", C.c_float),
                 ("reserved", C.c_uint32 * 3)]
+
+
+class ScPolishParams(C.Structure):
+    """Mirror of `sc_polish_params` (include/saccot.h): hypotheses polished (1 .. 64), refits per candidate at most (1 .. 64)."""
+    _fields_ = [("size", C.c_uint32), ("candidates", C.c_uint32), ("max_iter", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32 * 4)]
+
+
+class ScPolishCand(C.Structure):
+    """Mirror of `sc_polish_cand` (include/saccot.h), 64 bytes: a candidate's last iterate, its position in the ranked list, its frame
+    score, the score of the iterate, the refits that changed (R, t)."""
+    _fields_ = [("Rt", C.c_float * 12), ("rank", C.c_uint32), ("score0", C.c_uint32), ("score", C.c_uint32), ("iters", C.c_uint16),
+                ("reserved", C.c_uint16)]
+
+
+POLISH_CAND_DTYPE = np.dtype([("Rt", np.float32, 12), ("rank", np.uint32), ("score0", np.uint32), ("score", np.uint32),
+                              ("iters", np.uint16), ("reserved", np.uint16)])  # sc_polish_cand as a numpy record
 
 
 class ScShardPlan(C.Structure):
@@ -162,6 +180,10 @@ def load_library() -> C.CDLL:
     L.sc_peel_device.argtypes = [vp, vp, vp, sp]
     L.sc_register_instances.argtypes = [vp, f32p, f32p, C.c_int64, pp, C.c_uint32, C.c_uint32, f32p, u32p, C.POINTER(C.c_int32),
                                         u32p, sp]
+    qp = C.POINTER(ScPolishParams)
+    L.sc_polish_default_params.argtypes = [qp]
+    L.sc_polish_device.argtypes = [vp, qp, vp, vp, vp, vp, sp]
+    L.sc_polish.argtypes = [vp, qp, f32p, f32p, u8p, C.c_void_p, u32p, sp]
     mp, i32p = C.POINTER(ScMatchParams), C.POINTER(C.c_int32)
     L.sc_match_default_params.argtypes = [mp]
     L.sc_match_device.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, mp, vp, vp, vp]
@@ -202,6 +224,11 @@ def make_params(sigma=0.1, t_cmp=0.9, tau=0.1, min_len=0.1, max_triangles=50000,
 def make_match_params(dim: int, knn: int = 1, mutual: bool = False, ratio: float = 0.0, flags: int = 0) -> ScMatchParams:
     """sc_match_params for descriptors of length `dim`: knn 1 .. 4; mutual / ratio (in (0, 1), 0 = off) with knn == 1 only."""
     return ScMatchParams(C.sizeof(ScMatchParams), dim, knn, flags | (SC_MATCH_MUTUAL if mutual else 0), ratio)
+
+
+def make_polish_params(candidates: int = 8, max_iter: int = 16, flags: int = 0) -> ScPolishParams:
+    """sc_polish_params: the best `candidates` hypotheses of the frame (1 .. 64), at most `max_iter` refits each (1 .. 64)."""
+    return ScPolishParams(C.sizeof(ScPolishParams), candidates, max_iter, flags)
 
 
 def shard_plan(params: ScParams, n: int) -> ScShardPlan:
@@ -340,6 +367,29 @@ class Registrar:
         """sc_peel_device: the same with the outputs in HBM (d_Rt: 12 floats, d_mask: n bytes) -> (status, stats)."""
         st = ScStats(C.sizeof(ScStats))
         rc = self._check(self._lib.sc_peel_device(self._h, d_Rt, d_mask, C.byref(st)), allow=(SC_ENOHYP,))
+        return rc, st.as_dict()
+
+    # ---- refits iterated to a fixed point on that frame (include/saccot.h, sc_polish) --------------------------------
+    def polish(self, pparams: ScPolishParams | None = None, **kw):
+        """sc_polish: the frame's best hypotheses, each refitted over its own inliers until nothing changes; the best of them ->
+        dict(status, R, t, mask, n_cand, cand (candidates,) records of POLISH_CAND_DTYPE — those past n_cand zeroed —, stats).  stats["best_count"] is the polished
+        score and may be below the frame's.  kw: candidates, max_iter (make_polish_params)."""
+        q = pparams or make_polish_params(**kw)
+        R = np.zeros(9, np.float32); t = np.zeros(3, np.float32)
+        n = self._frame_n
+        mask = np.zeros(max(n, 1), np.uint8)
+        cand = np.zeros(max(int(q.candidates), 1), POLISH_CAND_DTYPE); k = C.c_uint32(0)
+        st = ScStats(C.sizeof(ScStats))
+        rc = self._check(self._lib.sc_polish(self._h, C.byref(q), _p(R, C.c_float), _p(t, C.c_float), _p(mask, C.c_uint8),
+                                             cand.ctypes.data_as(C.c_void_p), C.byref(k), C.byref(st)), allow=(SC_ENOHYP,))
+        return dict(status=rc, R=R.reshape(3, 3), t=t, mask=mask[:n], n_cand=int(k.value), cand=cand, stats=st.as_dict())
+
+    def polish_device(self, pparams: ScPolishParams, d_Rt: int, d_mask: int, d_cand: int = 0, d_ncand: int = 0):
+        """sc_polish_device: the same with the outputs in HBM (d_Rt: 12 floats, d_mask: n bytes, d_cand: `candidates` records of
+        64 bytes or 0, d_ncand: one uint32 or 0) -> (status, stats)."""
+        st = ScStats(C.sizeof(ScStats))
+        rc = self._check(self._lib.sc_polish_device(self._h, C.byref(pparams), d_Rt, d_mask, d_cand or None, d_ncand or None,
+                                                    C.byref(st)), allow=(SC_ENOHYP,))
         return rc, st.as_dict()
 
     def register_instances(self, src, tgt, max_instances: int = 8, min_score: int = 0, params: ScParams | None = None, **kw):

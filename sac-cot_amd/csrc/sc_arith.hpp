@@ -92,6 +92,17 @@ __device__ __forceinline__ float resid2(const float* __restrict__ M, float px, f
   return fma_(ez, ez, fma_(ey, ey, ex * ex));
 }
 
+// One correspondence's term of a hypothesis's score, score mode chosen at run time (include/saccot.h: 0 inlier count, 1 / 2 the
+// truncated squared / absolute residual; thr: tau^2, 1 / tau^2, 1 / tau).  The C2 kernels spell the same chain with the mode as a
+// template argument (sc_score.hip inlier_bit).
+__device__ __forceinline__ uint32_t score_term(const float* __restrict__ M, float px, float py, float pz, float qx, float qy, float qz,
+                                               float thr, int mode) {
+  const float d2 = resid2(M, px, py, pz, qx, qy, qz);
+  if (mode == 0) return d2 < thr ? 1u : 0u;
+  const float x = mode == 1 ? d2 : sqrt_rn(d2);
+  return (uint32_t)(fmaxf(fma_(-x, thr, 1.0f), 0.0f) * 1024.0f);
+}
+
 __device__ __forceinline__ float dot3(const float* a, const float* b) {
   return fma_(a[2], b[2], fma_(a[1], b[1], a[0] * b[0]));
 }

@@ -56,9 +56,9 @@ static int peel_round(sc_ctx* c, float* d_Rt, uint8_t* d_mask, sc_stats* stats) 
     ENSURE(c, c->partial, (size_t)rows * sh.ld_local * 4);
     launch_score(alive, c->rt.as<float>(), nullptr, sh, ps.dv, p->score_mode, c->partial.as<uint32_t>(), c->tn, st);
     SC_TRY(rec(c, 2));
-    ENSURE(c, c->cnt, (size_t)sh.ld_local * 4);
+    ENSURE(c, c->peel_cnt, (size_t)sh.ld_local * 4);  // (not c->cnt: the frame's scores stay for sc_polish)
     ENSURE(c, c->amx_pairs, argmax_scratch_bytes(sh.ld_local));
-    launch_argmax(sh, c->partial.as<uint32_t>(), rows, c->sel_key.as<uint32_t>(), c->cnt.as<uint32_t>(), c->amx_pairs.as<uint64_t>(),
+    launch_argmax(sh, c->partial.as<uint32_t>(), rows, c->sel_key.as<uint32_t>(), c->peel_cnt.as<uint32_t>(), c->amx_pairs.as<uint64_t>(),
                   &c->ctl.as<ControlBlock>()->amx_ticket, nullptr, st);  // (one pair per workgroup: the winner kernel reduces them)
     npairs = (int)argmax_blocks(sh.ld_local);
   } else SC_TRY(rec(c, 2));

@@ -96,7 +96,12 @@ struct Workspace {
   Buf in_src, in_tgt, planes, S, bits, deg, degp, wpre, ebase, edge_off, scan_tmp, ei, ej, es, ebi, ebj, tcnt, toff, wkey, kcol, ctl, events, blk_gt,
       blk_eq, blk_minmax, bits2, off_gt, off_eq, sel_ord, sel_key, sortkey, sorted, sort_tmp, tri, tri_rk, key_rk, rt, rt_aos, partial, cnt, key, rt12,
       mask, refine_tmp, amx_pairs, strong, rowcost, cost_pre, lb_state, lb_ticket, fx_tile, fx_state, fx_mx, fx_part, fx_coef, guard_tmp, fx_frame, ref_cand,
-      peel_planes, peel_claimed, peel_words, peel_label,  // sc_peel / sc_register_instances: allocated by the first round, never by a frame
+      // sc_peel / sc_register_instances: allocated by the first round, never by a frame.  peel_cnt: a round's scores — the frame's own stay
+      // in `cnt`, where sc_polish reads them whether or not rounds have run
+      peel_planes, peel_claimed, peel_words, peel_label, peel_cnt,
+      // sc_polish: allocated by the first polish, never by a frame.  cand: 64 candidate records, then the word that counts them;
+      // tmp: the chunk sums, candidates x polish_scratch_bytes(n)
+      polish_cand, polish_tmp,
       // sc_match / sc_register_features: allocated by the first match, never by a frame.  part: the slices' partial lists; words: the
       // "clean" word, the host entries' count pair, then the column minima; the rest: device copies of the host entries' arrays
       match_part, match_words, match_fsrc, match_ftgt, match_psrc, match_ptgt, match_corr, match_d2, match_gsrc, match_gtgt;

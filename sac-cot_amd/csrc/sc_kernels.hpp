@@ -625,6 +625,31 @@ void launch_peel_winner(const Points& pts, const uint8_t* claimed, const float* 
 // label[m] = value where mask[m] (sc_register_instances: one launch per accepted motion)
 void launch_peel_label(const uint8_t* mask, int n, int32_t value, int32_t* label, hipStream_t st);
 
+// ---- refits iterated to a fixed point on a scored frame (sc_polish; sc_polish.hip) ---------------------------------
+// One candidate: sc_polish_cand of include/saccot.h, field for field (sc_capi_polish.hip asserts the size).
+struct PolishCand {
+  float Rt[12];              // select: the frame's fp32 (R, t); polish: the last iterate
+  uint32_t rank;             // position in the ranked list
+  uint32_t score0, score;    // frame score; score of the last iterate over all n (the frame's score_mode)
+  uint16_t iters, reserved;  // refits that changed (R, t)
+};
+static_assert(sizeof(PolishCand) == 64, "sc_polish_cand is 64 bytes");
+constexpr uint32_t POLISH_MAX_CAND = 64;
+// The first K = min(want, hypotheses with cnt > 0) of the T hypotheses under (cnt desc, sel_key desc, position asc) — the frame's
+// total order — into cand[0 .. K) in that order, with their rank in the ranked list; cand[K .. want) zeroed; *n_cand = K.  One workgroup.
+void launch_polish_select(const uint32_t* cnt, const uint32_t* sel_key, uint32_t T, const float* RtSoA, uint32_t ld_local, uint32_t want,
+                          PolishCand* cand, uint32_t* n_cand, hipStream_t st);
+// One workgroup per candidate, every iteration inside the launch: mask of (R, t) -> refit in refine_kernel's canonical order -> again,
+// until the refit is declined, returns the same bits, or max_iter refits are done; then the score of the last iterate.
+// scratch: want * polish_scratch_bytes(n).  thr: tau^2, 1 / tau^2 or 1 / tau by score_mode.
+size_t polish_scratch_bytes(int n);
+void launch_polish(const Points& pts, PolishCand* cand, const uint32_t* n_cand, uint32_t want, uint32_t max_iter, float tau2, float thr,
+                   int score_mode, double* scratch, hipStream_t st);
+// The candidate with the largest score (ties: the earlier one) -> Rt12, mask; the records and their number -> out_cand / out_n (either
+// may be null); host_out (pinned, 2 x u64): [1] = rank << 32 | score, then, released, [0] = winner index << 32 | K (0: no candidate).
+void launch_polish_winner(const Points& pts, const PolishCand* cand, const uint32_t* n_cand, uint32_t want, float tau2, float* Rt12,
+                          uint8_t* mask, PolishCand* out_cand, uint32_t* out_n, uint64_t* host_out, hipStream_t st);
+
 // ---- descriptor matching (sc_match; sc_match.hip) -------------------------------------------------------
 // One call: fsrc ns x dim, ftgt nt x dim (row-major fp32, device); knn 1 .. 4; mutual / r2 (> 0: the ratio test, r2 = ratio^2) with
 // knn == 1 only.  A key is (bits of the canonical squared distance) << 32 | index.

@@ -1,0 +1,376 @@
+// sc_polish.hip — refits iterated to a fixed point on a scored frame (include/saccot.h, sc_polish): the kernels of  select -> polish -> winner / mask.
+//
+// A frame leaves its T hypotheses (c->rt), their ranking keys (c->sel_key), their scores over all n correspondences (c->cnt) and the
+// staged planes in the context.  Three launches of a dependent chain, whatever the number of refits:
+//
+//   polish_select_kernel  one workgroup.  The first K <= 64 hypotheses of the frame's total order — score, then ranking key, then
+//                         lowest (i, j, k) — by a radix select over the 96-bit key (score, key, ~position): one byte per pass, most
+//                         significant first from the top byte of the largest score, and it stops as soon as the bucket that holds the K-th key holds nothing but keys that
+//                         are taken (typically after the score's bytes and one or two of the key's).  The K are then ordered among
+//                         themselves, and their ranks in the ranked list counted the way the finalize kernel counts its winner's.
+//   polish_kernel         one workgroup per candidate, EVERY iteration inside the launch.  An iteration is the inlier test of the
+//                         current (R, t) — a wave's ballot per chunk of 64, one word in the spare slot of the chunk's sums: no
+//                         n-sized mask — and so_refine's two passes (oracle/saccot_oracle.c) over the set bits.
+//                         The summation ORDER is the canonical one (64 consecutive indices sequentially, then the chunk sums
+//                         sequentially); the lanes are dealt one per (chunk, component): 7 x ceil(n / 64) sums in pass 1, 9 x in
+//                         pass 2, every chain of 64 independent of the others, and one lane per component adds the chunk sums.  The
+//                         solve (sc_refine.hpp: refine_kernel's own) stays one thread.
+//   polish_winner_kernel  the candidate with the largest polished score, its mask, the records for the caller, the host words.
+#include <cstddef>
+
+#include "sc_arith.hpp"
+#include "sc_block.hpp"
+#include "sc_kernels.hpp"
+#include "sc_refine.hpp"
+
+namespace sc {
+
+namespace {
+
+constexpr int POLISH_THREADS = 1024;
+constexpr int POLISH_BITS_SLOT = 15;  // of a chunk's 16 scratch doubles: its 64 inlier bits (the sums use slots 0 .. 8)
+
+// ---- select ------------------------------------------------------------------------------------------------------------------
+// The 96-bit key of hypothesis g as three words, most significant first: w[0] = score, w[1] = ranking key, w[2] = ~g.
+struct Key96 { uint32_t w[3]; };
+__device__ __forceinline__ bool key_above(const Key96& a, const Key96& b) {  // a > b
+  if (a.w[0] != b.w[0]) return a.w[0] > b.w[0];
+  if (a.w[1] != b.w[1]) return a.w[1] > b.w[1];
+  return a.w[2] > b.w[2];
+}
+
+__global__ __launch_bounds__(POLISH_THREADS) void polish_select_kernel(const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ sel_key,
+                                                                       uint32_t T, const float* __restrict__ RtSoA, uint32_t ld_local,
+                                                                       uint32_t want, PolishCand* __restrict__ cand,
+                                                                       uint32_t* __restrict__ n_cand) {
+  __shared__ uint32_t hist[256];
+  __shared__ uint32_t s_digit, s_above, s_match, s_total, s_count;
+  __shared__ Key96 s_sel[POLISH_MAX_CAND];
+  __shared__ uint32_t s_pos[POLISH_MAX_CAND], s_rank[POLISH_MAX_CAND];
+  const uint32_t tid = threadIdx.x;
+  if (want > POLISH_MAX_CAND) want = POLISH_MAX_CAND;
+  // the prefix fixed so far (value and mask per word), and how many keys are still wanted among those that match it
+  Key96 pre{{0u, 0u, 0u}}, msk{{0u, 0u, 0u}};
+  uint32_t need = want;
+  bool done = false, none = false;
+  // the largest score: the select starts at its highest non-zero byte (an inlier count has two bytes of zeros on top)
+  uint32_t top;
+  {
+    uint32_t mx = 0u;
+#pragma unroll 8
+    for (uint64_t g = tid; g < T; g += POLISH_THREADS) mx = max(mx, cnt[g]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = max(mx, (uint32_t)__shfl_xor(mx, o));
+    if (tid < 256) hist[tid] = 0u;
+    __syncthreads();
+    if ((tid & 63u) == 0u) atomicMax(&hist[0], mx);
+    __syncthreads();
+    top = hist[0];
+    __syncthreads();
+  }
+  const int d0 = top >> 24 ? 11 : (top >> 16 ? 10 : (top >> 8 ? 9 : 8));
+#pragma unroll 1
+  for (int d = d0; d >= 0 && !done; d--) {
+    const int word = 2 - (d >> 2), shift = (d & 3) * 8;
+    if (tid < 256) hist[tid] = 0u;
+    __syncthreads();
+    uint32_t cur = 0u, run = 0u;
+#pragma unroll 8
+    for (uint64_t g = tid; g < T; g += POLISH_THREADS) {  // (both loads unconditional: eight iterations' loads are in flight together)
+      const Key96 k{{cnt[g], sel_key[g], ~(uint32_t)g}};
+      // a hypothesis that explains nothing is no candidate
+      if (k.w[0] != 0u && (k.w[0] & msk.w[0]) == pre.w[0] && (k.w[1] & msk.w[1]) == pre.w[1] && (k.w[2] & msk.w[2]) == pre.w[2]) {
+        // runs of one bucket are counted in a register: in the score's upper bytes nearly every key falls into bucket 0, and
+        // 50 000 atomics on one LDS word cost 20 us a pass
+        const uint32_t b = ((word == 0 ? k.w[0] : (word == 1 ? k.w[1] : k.w[2])) >> shift) & 255u;
+        if (b != cur) {
+          if (run) atomicAdd(&hist[cur], run);
+          cur = b; run = 0u;
+        }
+        run++;
+      }
+    }
+    if (run) atomicAdd(&hist[cur], run);
+    __syncthreads();
+    if (tid < 64) {  // wave 0: the bucket that holds the need-th largest matching key; lane l owns buckets 255 - 4 l .. 252 - 4 l
+      const int hi = 255 - 4 * (int)tid;
+      const uint32_t h0 = hist[hi], h1 = hist[hi - 1], h2 = hist[hi - 2], h3 = hist[hi - 3];
+      const uint32_t own = h0 + h1 + h2 + h3;
+      const uint32_t inc = wave_inscan(own);
+      const uint32_t total = __shfl(inc, 63);
+      const uint32_t nd = need < total ? need : total;  // (first pass only: fewer candidates than asked for)
+      if (tid == 0) s_total = total;
+      const uint32_t exc = inc - own;
+      if (nd != 0u && exc < nd && nd <= inc) {  // exactly one lane
+        uint32_t run = exc; int b = hi; uint32_t h = h0;
+        if (run + h < nd) { run += h; b = hi - 1; h = h1; }
+        if (b == hi - 1 && run + h < nd) { run += h; b = hi - 2; h = h2; }
+        if (b == hi - 2 && run + h < nd) { run += h; b = hi - 3; h = h3; }
+        s_digit = (uint32_t)b; s_above = run; s_match = h;
+      }
+    }
+    __syncthreads();
+    if (s_total == 0u) { none = true; break; }  // (uniform) every score is 0
+    if (need > s_total) need = s_total;
+#pragma unroll
+    for (int w = 0; w < 3; w++)  // (no run-time index into the two keys: they stay in registers)
+      if (w == word) { pre.w[w] |= s_digit << shift; msk.w[w] |= 255u << shift; }
+    need -= s_above;
+    done = s_match == need;  // the bucket holds only keys that are taken: everything at or above the prefix is the selection
+    __syncthreads();         // (hist and the s_ words are rewritten by the next pass)
+  }
+  if (tid == 0) s_count = 0u;
+  if (tid < POLISH_MAX_CAND) s_rank[tid] = 0u;
+  __syncthreads();
+  if (!none) {
+#pragma unroll 8
+    for (uint64_t g = tid; g < T; g += POLISH_THREADS) {
+      const Key96 k{{cnt[g], sel_key[g], ~(uint32_t)g}};
+      const Key96 km{{k.w[0] & msk.w[0], k.w[1] & msk.w[1], k.w[2] & msk.w[2]}};
+      if (k.w[0] != 0u && !key_above(pre, km)) {
+        const uint32_t slot = atomicAdd(&s_count, 1u);
+        if (slot < POLISH_MAX_CAND) s_sel[slot] = k;  // (never more than `want` of them)
+      }
+    }
+  }
+  __syncthreads();
+  const uint32_t K = s_count < want ? s_count : want;
+  // order among the K: a key's place is the number of keys above it (they are distinct)
+  if (tid < K) {
+    uint32_t above = 0;
+    for (uint32_t j = 0; j < K; j++) above += key_above(s_sel[j], s_sel[tid]) ? 1u : 0u;
+    s_pos[above] = tid;
+  }
+  // rank in the ranked list: ranking keys above one's own, and equal keys at lower positions (finalize_kernel's count), eight
+  // candidates per walk over the keys
+  __syncthreads();
+#pragma unroll 1
+  for (uint32_t c0 = 0; c0 < K; c0 += 8) {
+    uint32_t r[8], ck[8], cg[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      const bool live = c0 + j < K;  // (past K: a key nothing is above)
+      r[j] = 0u; ck[j] = live ? s_sel[c0 + j].w[1] : 0xFFFFFFFFu; cg[j] = live ? s_sel[c0 + j].w[2] : 0xFFFFFFFFu;
+    }
+#pragma unroll 8
+    for (uint64_t g = tid; g < T; g += POLISH_THREADS) {
+      const uint32_t k = sel_key[g], ng = ~(uint32_t)g;
+#pragma unroll
+      for (int j = 0; j < 8; j++) r[j] += (k > ck[j] || (k == ck[j] && ng > cg[j])) ? 1u : 0u;
+    }
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      uint32_t v = r[j];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+      if ((tid & 63u) == 0u && v != 0u && c0 + j < K) atomicAdd(&s_rank[c0 + j], v);
+    }
+  }
+  __syncthreads();
+  if (tid < want) {
+    PolishCand out;
+    if (tid < K) {
+      const uint32_t j = s_pos[tid];
+      const uint32_t g = ~s_sel[j].w[2];
+#pragma unroll
+      for (int c = 0; c < 12; c++) out.Rt[c] = RtSoA[(size_t)c * ld_local + g];
+      out.rank = s_rank[j]; out.score0 = s_sel[j].w[0];
+    } else {
+#pragma unroll
+      for (int c = 0; c < 12; c++) out.Rt[c] = 0.f;
+      out.rank = 0u; out.score0 = 0u;
+    }
+    out.score = 0u; out.iters = 0; out.reserved = 0;
+    cand[tid] = out;
+  }
+  if (tid == 0) *n_cand = K;
+}
+
+// ---- polish ------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(POLISH_THREADS) void polish_kernel(const float* __restrict__ planes, int n, int ld, PolishCand* __restrict__ cand,
+                                                                const uint32_t* __restrict__ n_cand, uint32_t max_iter, float tau2,
+                                                                float thr, int score_mode, double* __restrict__ scratch_all) {
+  __shared__ float sRt[12];
+  __shared__ double sS[8], sH[9];
+  __shared__ uint32_t s_go;
+  __shared__ uint64_t s_red[POLISH_THREADS / 64];
+  if (blockIdx.x >= *n_cand) return;  // (uniform)
+  const uint32_t tid = threadIdx.x;
+  const int nch = (n + 63) / 64;
+  double* scratch = scratch_all + (size_t)blockIdx.x * (size_t)nch * 16;  // 16 doubles per chunk: the sums in [0, 9), the inlier bits in [15]
+  unsigned long long* bits = reinterpret_cast<unsigned long long*>(scratch);
+  PolishCand* me = cand + blockIdx.x;
+  if (tid < 12) sRt[tid] = me->Rt[tid];
+  __syncthreads();
+  uint32_t iters = 0;
+#pragma unroll 1
+  for (uint32_t it = 0; it < max_iter; it++) {
+    float M[12];
+#pragma unroll
+    for (int c = 0; c < 12; c++) M[c] = sRt[c];
+    const bool fin = finite12(M);
+    // the inlier bits of (R, t), one 64-bit word per chunk (a wave's ballot), kept in the spare slot of the chunk's sums
+    for (int ch = (int)(tid >> 6); ch < nch; ch += POLISH_THREADS / 64) {
+      const int m = ch * 64 + (int)(tid & 63u);
+      bool inl = false;
+      if (m < n)
+        inl = fin && resid2(M, planes[m], planes[(size_t)ld + m], planes[(size_t)2 * ld + m], planes[(size_t)3 * ld + m],
+                            planes[(size_t)4 * ld + m], planes[(size_t)5 * ld + m]) < tau2;
+      const unsigned long long bal = __ballot(inl);
+      if ((tid & 63u) == 0u) bits[(size_t)ch * 16 + POLISH_BITS_SLOT] = bal;
+    }
+    __threadfence_block();
+    __syncthreads();
+    // pass 1: lane = (chunk, component): count, sum p (3), sum q (3) of the chunk's inliers, sequentially in index order
+    for (int64_t w = tid; w < (int64_t)nch * 7; w += POLISH_THREADS) {
+      const int ch = (int)(w / 7), k = (int)(w % 7);
+      const float* __restrict__ own = planes + (size_t)(k ? k - 1 : 0) * ld + (size_t)ch * 64;
+      unsigned long long b = bits[(size_t)ch * 16 + POLISH_BITS_SLOT];
+      double c = 0.0;
+      while (b) {
+        const int j = __builtin_ctzll(b);
+        b &= b - 1ull;
+        c += k ? (double)own[j] : 1.0;
+      }
+      scratch[(size_t)ch * 16 + k] = c;
+    }
+    __threadfence_block();
+    __syncthreads();
+    if (tid < 7) {  // the chunk sums in chunk order, one lane per component
+      double S = 0.0;
+      for (int ch = 0; ch < nch; ch++) S += scratch[(size_t)ch * 16 + tid];
+      sS[tid] = S;
+    }
+    __syncthreads();
+    const double cnt = sS[0];
+    if (cnt < 3.0) break;  // (uniform) the refit is declined: (R, t) stays
+    const double pc[3] = {sS[1] / cnt, sS[2] / cnt, sS[3] / cnt}, qc[3] = {sS[4] / cnt, sS[5] / cnt, sS[6] / cnt};
+    // pass 2: lane = (chunk, entry of H): h = fma(p_r - pc_r, q_c - qc_c, h) over the chunk's inliers
+    for (int64_t w = tid; w < (int64_t)nch * 9; w += POLISH_THREADS) {
+      const int ch = (int)(w / 9), e = (int)(w % 9), r = e / 3, cc = e % 3;
+      const float* __restrict__ pr = planes + (size_t)r * ld + (size_t)ch * 64;
+      const float* __restrict__ qr = planes + (size_t)(3 + cc) * ld + (size_t)ch * 64;
+      const double pcr = r == 0 ? pc[0] : (r == 1 ? pc[1] : pc[2]), qcc = cc == 0 ? qc[0] : (cc == 1 ? qc[1] : qc[2]);
+      unsigned long long b = bits[(size_t)ch * 16 + POLISH_BITS_SLOT];
+      double h = 0.0;
+      while (b) {
+        const int j = __builtin_ctzll(b);
+        b &= b - 1ull;
+        h = __builtin_fma((double)pr[j] - pcr, (double)qr[j] - qcc, h);
+      }
+      scratch[(size_t)ch * 16 + e] = h;
+    }
+    __threadfence_block();
+    __syncthreads();
+    if (tid < 9) {
+      double S = 0.0;
+      for (int ch = 0; ch < nch; ch++) S += scratch[(size_t)ch * 16 + tid];
+      sH[tid] = S;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      double H[9];
+#pragma unroll
+      for (int k = 0; k < 9; k++) H[k] = sH[k];
+      float out[12];
+      uint32_t go = 0u;
+      if (refine_solve(H, pc, qc, out)) {  // (not finite: declined)
+#pragma unroll
+        for (int c = 0; c < 12; c++) go |= (__float_as_uint(out[c]) != __float_as_uint(M[c])) ? 1u : 0u;
+        if (go) {
+#pragma unroll
+          for (int c = 0; c < 12; c++) sRt[c] = out[c];
+        }
+      }
+      s_go = go;
+    }
+    __syncthreads();
+    if (!s_go) break;  // (uniform) declined, or the fixed point: the refit returned the bits it started from
+    iters++;
+  }
+  // the last iterate's score over all n, in the frame's score mode (a sum of integers: any order)
+  float M[12];
+#pragma unroll
+  for (int c = 0; c < 12; c++) M[c] = sRt[c];
+  uint64_t s = 0;
+  if (finite12(M))
+    for (int m = (int)tid; m < n; m += POLISH_THREADS)
+      s += score_term(M, planes[m], planes[(size_t)ld + m], planes[(size_t)2 * ld + m], planes[(size_t)3 * ld + m],
+                      planes[(size_t)4 * ld + m], planes[(size_t)5 * ld + m], thr, score_mode);
+  s = block_reduce_u64(s, s_red);
+  if (tid < 12) me->Rt[tid] = M[tid];
+  if (tid == 0) { me->score = (uint32_t)s; me->iters = (uint16_t)iters; }
+}
+
+// ---- winner / mask -----------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void polish_winner_kernel(const float* __restrict__ planes, int n, int ld,
+                                                            const PolishCand* __restrict__ cand, const uint32_t* __restrict__ n_cand,
+                                                            uint32_t want, float tau2, float* __restrict__ Rt12, uint8_t* __restrict__ mask,
+                                                            PolishCand* __restrict__ out_cand, uint32_t* __restrict__ out_n,
+                                                            unsigned long long* __restrict__ host_out) {
+  __shared__ float sRt[12];
+  __shared__ uint32_t s_win;
+  const uint32_t K = *n_cand;
+  if (threadIdx.x < 64) {  // largest score, ties to the earlier candidate
+    unsigned long long k = threadIdx.x < K ? (((unsigned long long)cand[threadIdx.x].score << 32) | (0xFFFFFFFFu - threadIdx.x)) : 0ull;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const unsigned long long other = __shfl_xor(k, o);
+      k = other > k ? other : k;
+    }
+    if (threadIdx.x == 0) s_win = K ? 0xFFFFFFFFu - (uint32_t)(k & 0xFFFFFFFFull) : 0u;
+  }
+  __syncthreads();
+  const uint32_t win = s_win;
+  if (threadIdx.x < 12) {
+    const float ident = (threadIdx.x == 0 || threadIdx.x == 4 || threadIdx.x == 8) ? 1.f : 0.f;
+    const float v = K ? cand[win].Rt[threadIdx.x] : ident;
+    sRt[threadIdx.x] = v;
+    if (blockIdx.x == 0) Rt12[threadIdx.x] = v;
+  }
+  __syncthreads();
+  const int m = blockIdx.x * 256 + threadIdx.x;
+  if (m < n) {
+    float M[12];
+#pragma unroll
+    for (int c = 0; c < 12; c++) M[c] = sRt[c];
+    const float d2 = resid2(M, planes[m], planes[(size_t)ld + m], planes[(size_t)2 * ld + m], planes[(size_t)3 * ld + m],
+                            planes[(size_t)4 * ld + m], planes[(size_t)5 * ld + m]);
+    mask[m] = (K != 0u && finite12(M) && d2 < tau2) ? 1 : 0;
+  }
+  if (blockIdx.x != 0) return;
+  if (out_cand) {  // the records, 16 words each (entries past K are zero already)
+    const uint32_t* from = reinterpret_cast<const uint32_t*>(cand);
+    uint32_t* to = reinterpret_cast<uint32_t*>(out_cand);
+    for (uint32_t w = threadIdx.x; w < want * 16u; w += 256u) to[w] = from[w];
+  }
+  if (threadIdx.x == 0) {
+    if (out_n) *out_n = K;
+    const unsigned long long rs = K ? (((unsigned long long)cand[win].rank << 32) | (unsigned long long)cand[win].score) : 0ull;
+    __hip_atomic_store(&host_out[1], rs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    publish_host(reinterpret_cast<uint64_t*>(host_out), ((uint64_t)win << 32) | (uint64_t)K);  // [0] last: the host polls it
+  }
+}
+
+}  // namespace
+
+void launch_polish_select(const uint32_t* cnt, const uint32_t* sel_key, uint32_t T, const float* RtSoA, uint32_t ld_local, uint32_t want,
+                          PolishCand* cand, uint32_t* n_cand, hipStream_t st) {
+  hipLaunchKernelGGL(polish_select_kernel, dim3(1), dim3(POLISH_THREADS), 0, st, cnt, sel_key, T, RtSoA, ld_local, want, cand, n_cand);
+}
+
+size_t polish_scratch_bytes(int n) { return (size_t)((n + 63) / 64) * 16 * sizeof(double); }
+
+void launch_polish(const Points& pts, PolishCand* cand, const uint32_t* n_cand, uint32_t want, uint32_t max_iter, float tau2, float thr,
+                   int score_mode, double* scratch, hipStream_t st) {
+  hipLaunchKernelGGL(polish_kernel, dim3(want), dim3(POLISH_THREADS), 0, st, pts.planes, pts.n, pts.ld, cand, n_cand, max_iter, tau2, thr,
+                     score_mode, scratch);
+}
+
+void launch_polish_winner(const Points& pts, const PolishCand* cand, const uint32_t* n_cand, uint32_t want, float tau2, float* Rt12,
+                          uint8_t* mask, PolishCand* out_cand, uint32_t* out_n, uint64_t* host_out, hipStream_t st) {
+  hipLaunchKernelGGL(polish_winner_kernel, dim3((pts.n + 255) / 256), dim3(256), 0, st, pts.planes, pts.n, pts.ld, cand, n_cand, want, tau2,
+                     Rt12, mask, out_cand, out_n, reinterpret_cast<unsigned long long*>(host_out));
+}
+
+}  // namespace sc
