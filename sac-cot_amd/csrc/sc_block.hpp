@@ -3,6 +3,8 @@
 //   wave_inscan                          inclusive scan over the wave (the six __shfl_up steps)
 //   group_exscan                         exclusive scan over a 16- or 64-lane group of the wave, with the group's sum
 //   block_reduce_u64 / block_exscan_u64  sum and exclusive scan over the workgroup
+//   block_max_u64 / block_lexmax_u64     maximum of a key, and lexicographic maximum of a key pair, over a 256-thread workgroup
+//   last_workgroup_sum                   "one returning atomic, the last workgroup holds the total": the tail of a launch that publishes once
 //   lb_*                                 decoupled look-back over the tiles of one launch
 // (mask_above and group_exscan came from sc_tri.hip; wave_inscan replaces the single-value loops sc_compat.hip and sc_tri.hip wrote out by hand.)
 #pragma once
@@ -81,6 +83,46 @@ __device__ __forceinline__ uint64_t block_exscan_u64(uint64_t v, uint64_t* lds, 
   __syncthreads();
   *total = tot;
   return base + inc - v;
+}
+
+// maximum over a workgroup of 256 threads; lds: 4 entries.  ONE barrier, in front of the reads: the next writer of lds adds its own.
+__device__ __forceinline__ unsigned long long block_max_u64(unsigned long long k, unsigned long long* lds) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long other = __shfl_xor(k, o);
+    k = other > k ? other : k;
+  }
+  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = k;
+  __syncthreads();
+  unsigned long long b = lds[0];
+  for (int w = 1; w < 4; w++) b = lds[w] > b ? lds[w] : b;
+  return b;
+}
+
+// (k0, k1) = the larger of itself and (a, b), pairs ordered lexicographically
+__device__ __forceinline__ void lexmax_take(unsigned long long& k0, unsigned long long& k1, unsigned long long a, unsigned long long b) {
+  if (a > k0 || (a == k0 && b > k1)) { k0 = a; k1 = b; }
+}
+
+// lexicographic maximum over a workgroup of 256, in place: K = max k0, then the largest k1 among the threads that hold K (lds: as above)
+__device__ __forceinline__ void block_lexmax_u64(unsigned long long& k0, unsigned long long& k1, unsigned long long* lds) {
+  const unsigned long long K = block_max_u64(k0, lds);
+  __syncthreads();
+  const unsigned long long P = block_max_u64(k0 == K ? k1 : 0ull, lds);
+  k0 = K; k1 = P;
+}
+
+// The tail of a launch whose LAST workgroup publishes the sum of every workgroup's count.  ONE returning atomic per workgroup:
+// workgroups finished in the high half of *word, the count so far in the low half — the workgroup that finds every other one finished
+// holds the whole count in the value it got back (no second accumulator, no acquire, no load).  One thread per workgroup calls it;
+// true in the last workgroup, which gets *total and leaves *word zero for the next launch.  What is published is the caller's.
+__device__ __forceinline__ bool last_workgroup_sum(unsigned long long* word, uint32_t partial, uint32_t* total) {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+  const unsigned long long was = __hip_atomic_fetch_add(word, (1ull << 32) | (unsigned long long)partial, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if ((uint32_t)(was >> 32) != gridDim.x - 1) return false;
+  *total = (uint32_t)was + partial;
+  __hip_atomic_store(word, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return true;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -14,12 +14,7 @@ using namespace sc;
 extern "C" {
 
 static int peel_round(sc_ctx* c, float* d_Rt, uint8_t* d_mask, sc_stats* stats) {
-  SC_TRY(busy(c));
-  if (!c->pass.peelable) {
-    c->last_error = "sc_peel: no frame on this context (a round follows an sc_register* call that returned SC_OK with shard_world == 1; any other computing call ends the frame)";
-    return SC_EINVAL;
-  }
-  HIPCHK(c, hipSetDevice(c->device));
+  SC_TRY(scored_frame_begin(c, "sc_peel"));
   Pass& ps = c->pass;
   const sc_params* p = &ps.params;
   const Shard& sh = ps.sh;  // one rank: n_local == T_eff, a position in the selection IS the index into c->rt
@@ -71,29 +66,14 @@ static int peel_round(sc_ctx* c, float* d_Rt, uint8_t* d_mask, sc_stats* stats) 
     launch_refine(points_of(c), d_mask, reinterpret_cast<const uint64_t*>(words->key2), c->refine_tmp.as<double>(), d_Rt, st);
   }
   SC_TRY(rec(c, 4));
-  // outputs: complete on return with the private stream, stream-ordered with a caller's (as sc_register_device)
-  if (ps.timing || c->stream == c->own_stream) HIPCHK(c, hipStreamSynchronize(st));
-  SC_TRY(wait_word(c, HW_WINNER));
-  HIPCHK(c, hipGetLastError());
+  SC_TRY(scored_frame_wait(c));
   const uint64_t key = c->pinned[HW_WINNER];
   ps.peel_round++;
   if (key) {
     ps.peel_prev = (uint32_t)c->pinned[HW_WINNER_POS];
     if (!read_alive) ps.peel_claimed += (uint32_t)(key >> 32);
   }
-  if (stats && stats->size == sizeof(sc_stats)) {
-    fill_stats(c, stats);  // n, edges, tri_total, tri_kept, tri_scored: the frame's
-    stats->best_count = (uint32_t)(key >> 32);
-    stats->best_rank = key ? (uint32_t)(c->pinned[HW_WINNER_POS] >> 32) : 0u;
-    if (ps.timing) {  // the frame asked for SC_FLAG_TIMING: the round's brackets (us_stage: the claim + compact launch)
-      stats->us_stage = ev_us(c, 0, 1);
-      stats->us_score = ev_us(c, 1, 2);
-      stats->us_argmax = ev_us(c, 2, 3);
-      stats->us_mask = ev_us(c, 3, 4);
-      stats->us_compat = stats->us_triangles = stats->us_trikeys = stats->us_kabsch = 0.f;
-      stats->us_total = stats->us_stage + stats->us_score + stats->us_argmax + stats->us_mask;
-    }
-  }
+  scored_frame_stats(c, stats, (uint32_t)(key >> 32), key ? (uint32_t)(c->pinned[HW_WINNER_POS] >> 32) : 0u, 4);  // (us_stage: claim + compact)
   return key ? SC_OK : SC_ENOHYP;
 }
 

@@ -42,11 +42,7 @@ static int polish_run(sc_ctx* c, const sc_polish_params* pp, float* d_Rt, uint8_
                       sc_stats* stats) {
   SC_TRY(busy(c));
   SC_TRY(polish_check(c, pp));
-  if (!c->pass.peelable) {
-    c->last_error = "sc_polish: no frame on this context (it follows an sc_register* call that returned SC_OK with shard_world == 1; any other computing call ends the frame)";
-    return SC_EINVAL;
-  }
-  HIPCHK(c, hipSetDevice(c->device));
+  SC_TRY(scored_frame_begin(c, "sc_polish"));
   const Pass& ps = c->pass;
   const sc_params* p = &ps.params;
   const Shard& sh = ps.sh;  // one rank: a position in the selection IS the index into c->rt and c->cnt
@@ -66,23 +62,9 @@ static int polish_run(sc_ctx* c, const sc_polish_params* pp, float* d_Rt, uint8_
   launch_polish_winner(points_of(c), cand, n_cand, want, ps.dv.tau2, d_Rt, d_mask, reinterpret_cast<PolishCand*>(d_cand), d_ncand,
                        &c->pinned[HW_WINNER], st);
   SC_TRY(rec(c, 3));
-  // outputs: complete on return with the private stream, stream-ordered with a caller's (as sc_register_device)
-  if (ps.timing || c->stream == c->own_stream) HIPCHK(c, hipStreamSynchronize(st));
-  SC_TRY(wait_word(c, HW_WINNER));
-  HIPCHK(c, hipGetLastError());
+  SC_TRY(scored_frame_wait(c));
   const uint32_t K = (uint32_t)c->pinned[HW_WINNER];
-  if (stats && stats->size == sizeof(sc_stats)) {
-    fill_stats(c, stats);  // n, edges, tri_total, tri_kept, tri_scored: the frame's
-    stats->best_rank = K ? (uint32_t)(c->pinned[HW_WINNER_POS] >> 32) : 0u;
-    stats->best_count = K ? (uint32_t)c->pinned[HW_WINNER_POS] : 0u;
-    if (ps.timing) {  // the frame asked for SC_FLAG_TIMING: this call's brackets
-      stats->us_stage = ev_us(c, 0, 1);
-      stats->us_score = ev_us(c, 1, 2);
-      stats->us_mask = ev_us(c, 2, 3);
-      stats->us_compat = stats->us_triangles = stats->us_trikeys = stats->us_kabsch = stats->us_argmax = 0.f;
-      stats->us_total = stats->us_stage + stats->us_score + stats->us_mask;
-    }
-  }
+  scored_frame_stats(c, stats, K ? (uint32_t)c->pinned[HW_WINNER_POS] : 0u, K ? (uint32_t)(c->pinned[HW_WINNER_POS] >> 32) : 0u, 3);
   return K ? SC_OK : SC_ENOHYP;
 }
 

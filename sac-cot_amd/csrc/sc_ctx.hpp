@@ -210,6 +210,41 @@ int points_to_device(sc_ctx* c, const float* src, const float* tgt, int64_t n);
 // rt12 and n bytes of mask -> the caller's host arrays (R and t split); the stream is idle on return
 int outputs_to_host(sc_ctx* c, size_t n, float R[9], float t[3], uint8_t* mask);
 
+// ---- a call on a scored frame (sc_peel, sc_polish): what the two share in front of their launches and behind them
+// The entry checks, `busy` first, then "is there a frame"; the refusal names the caller.  Then the context's device.
+inline int scored_frame_begin(sc_ctx* c, const char* who) {
+  SC_TRY(busy(c));
+  if (!c->pass.peelable) {
+    c->last_error = std::string(who) + ": no frame on this context (it follows an sc_register* call that returned SC_OK with shard_world == 1; any other computing call ends the frame)";
+    return SC_EINVAL;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  return SC_OK;
+}
+// Behind the last launch: outputs complete on return with the private stream, stream-ordered with a caller's (as sc_register_device);
+// then the winner's two host words (HW_WINNER, armed by the caller, and HW_WINNER_POS) are there.
+inline int scored_frame_wait(sc_ctx* c) {
+  if (c->pass.timing || c->stream == c->own_stream) HIPCHK(c, hipStreamSynchronize(c->stream));
+  SC_TRY(wait_word(c, HW_WINNER));
+  HIPCHK(c, hipGetLastError());
+  return SC_OK;
+}
+// The caller's sc_stats: the frame's n, edges, tri_*; the winner's count and rank index; if the frame asked for SC_FLAG_TIMING, this call's
+// brackets — events 0 - 1 us_stage, 1 - 2 us_score, 2 - 3 us_argmax (when last_ev == 4), last_ev - 1 .. last_ev us_mask; the others zero.
+inline void scored_frame_stats(sc_ctx* c, sc_stats* stats, uint32_t best_count, uint32_t best_rank, int last_ev) {
+  if (!stats || stats->size != sizeof(sc_stats)) return;
+  fill_stats(c, stats);
+  stats->best_count = best_count;
+  stats->best_rank = best_rank;
+  if (!c->pass.timing) return;
+  stats->us_stage = ev_us(c, 0, 1);
+  stats->us_score = ev_us(c, 1, 2);
+  stats->us_argmax = last_ev == 4 ? ev_us(c, 2, 3) : 0.f;
+  stats->us_mask = ev_us(c, last_ev - 1, last_ev);
+  stats->us_compat = stats->us_triangles = stats->us_trikeys = stats->us_kabsch = 0.f;
+  stats->us_total = stats->us_stage + stats->us_score + stats->us_argmax + stats->us_mask;
+}
+
 // the stage sequencers the stage hooks run one at a time (sc_capi_hooks.hip)
 int stage_inputs(sc_ctx* c, const float* d_src, const float* d_tgt, int64_t n, const sc_params* p);
 int run_compat(sc_ctx* c, bool dense);

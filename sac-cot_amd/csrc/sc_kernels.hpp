@@ -548,7 +548,7 @@ size_t argmax_scratch_bytes(uint32_t ld_local);
 uint32_t argmax_blocks(uint32_t ld_local);  // workgroups of launch_argmax = pairs it leaves when key2 == nullptr
 void launch_argmax(const Shard& sh, const uint32_t* partial, uint32_t n_chunks, const uint32_t* sel_key,
                    uint32_t* cnt, uint64_t* pairs, uint32_t* ticket, uint64_t* key2, hipStream_t st);
-// C3: winner decode + re-solve + mask.  Rt12 receives R (row-major) and t; identity / zero mask when key2[0] == 0.
+// C3 (sc_final.hip): winner decode + re-solve + mask.  Rt12 receives R (row-major) and t; identity / zero mask when key2[0] == 0.
 // sel_key / T: the ordinal-ordered ranking keys (for the winner's rank index); host_out (pinned, 2 x u64) receives
 // [1] = rank index << 32 | position (all ones: the key pair decodes to nothing of the selection) and then, released, [0] = key2[0].
 // key2: npairs key pairs (all-gathered, one per rank; 1 = already reduced); key_out (2 x u64, optional) receives the

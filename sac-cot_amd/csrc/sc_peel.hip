@@ -12,32 +12,20 @@
 //                         decoupled look-back over the tiles (sc_block.hpp), and writes its six coordinates there.  Order
 //                         preserved: a round is then reproducible down to the order in which its scoring kernel meets the points.
 //   peel_winner_kernel    finalize_kernel's work for one shard — reduce the arg-max launch's pairs, load the winner's (R, t), count
-//                         its rank index among the keys, mask — with mask[m] = !claimed[m] && inlier.
+//                         its rank index among the keys, mask — with mask[m] = !claimed[m] && inlier: both compose sc_winner.hpp's steps.
 //   peel_label_kernel     label[m] = r where mask[m] (sc_register_instances).
 #include <cstddef>
 
 #include "sc_arith.hpp"
 #include "sc_block.hpp"
 #include "sc_kernels.hpp"
+#include "sc_winner.hpp"
 
 namespace sc {
 
 namespace {
 
 constexpr int PEEL_THREADS = 256;  // one correspondence per thread: a tile is 256 of them (C2: 20 tiles; 2^24: 65 536, look-back 64 per step)
-
-__device__ __forceinline__ unsigned long long peel_block_max_u64(unsigned long long k, unsigned long long* lds) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long other = __shfl_xor(k, o);
-    k = other > k ? other : k;
-  }
-  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = k;
-  __syncthreads();
-  unsigned long long b = lds[0];
-  for (int w = 1; w < 4; w++) b = lds[w] > b ? lds[w] : b;
-  return b;
-}
 
 __global__ __launch_bounds__(PEEL_THREADS) void peel_compact_kernel(const float* __restrict__ planes, int n, int ld,
                                                                     const float* __restrict__ RtSoA, uint32_t ld_local,
@@ -54,16 +42,13 @@ __global__ __launch_bounds__(PEEL_THREADS) void peel_compact_kernel(const float*
   if (tile >= gridDim.x) return;  // (a ticket that was not zero at launch: never index memory with it)
   const int m = (int)(tile * PEEL_THREADS + threadIdx.x);
   const bool in = m < n;
-  float cp[6];
-#pragma unroll
-  for (int c = 0; c < 6; c++) cp[c] = in ? planes[(size_t)c * ld + m] : 0.f;
+  const Corr cp = in ? load_corr(planes, ld, m) : Corr{};
   bool taken = in && !fresh && claimed[m] != 0;
   if (prev_pos != 0xFFFFFFFFu) {  // the winner before this round: its mask, recomputed (uniform branch)
     float M[12];
 #pragma unroll
     for (int c = 0; c < 12; c++) M[c] = RtSoA[(size_t)c * ld_local + prev_pos];
-    const float d2 = resid2(M, cp[0], cp[1], cp[2], cp[3], cp[4], cp[5]);
-    taken = taken || (finite12(M) && d2 < tau2);
+    taken = taken || is_inlier(M, cp, tau2);
   }
   if (in) claimed[m] = taken ? 1 : 0;
   const bool keep = in && !taken;
@@ -94,7 +79,7 @@ __global__ __launch_bounds__(PEEL_THREADS) void peel_compact_kernel(const float*
     const size_t slot = (size_t)(pre + wave_base + below);  // < n: one slot per alive correspondence
     if (slot < (size_t)n) {
 #pragma unroll
-      for (int c = 0; c < 6; c++) alive[(size_t)c * ld + slot] = cp[c];
+      for (int c = 0; c < 6; c++) alive[(size_t)c * ld + slot] = cp.v[c];
     }
   }
   if (tile == gridDim.x - 1 && threadIdx.x == 0) {
@@ -114,77 +99,25 @@ __global__ __launch_bounds__(256) void peel_winner_kernel(const float* __restric
                                                           unsigned long long* __restrict__ host_out) {
   __shared__ uint64_t lds[8];
   __shared__ float sRt[12];
-  __shared__ uint32_t s_last;
   const int m = blockIdx.x * 256 + threadIdx.x;
-  float cp[6];
-#pragma unroll
-  for (int c = 0; c < 6; c++) cp[c] = m < n ? planes[(size_t)c * ld + m] : 0.f;
+  const Corr cp = m < n ? load_corr(planes, ld, m) : Corr{};
   const bool free_m = m < n && claimed[m] == 0;
-  const uint32_t T4 = T >> 2;  // 16-byte loads, grid-strided
-  const uint4* __restrict__ k4 = reinterpret_cast<const uint4*>(sel_key);
-  // the arg-max launch's per-workgroup pairs -> (best key, lowest position attaining it): a lexicographic max
-  unsigned long long k0 = 0, k1 = 0;
-  for (int w = threadIdx.x; w < npairs; w += 256) {
-    const unsigned long long a = pairs[2 * w], b = pairs[2 * w + 1];
-    if (a > k0 || (a == k0 && b > k1)) { k0 = a; k1 = b; }
-  }
-  {
-    unsigned long long* l4 = reinterpret_cast<unsigned long long*>(lds);
-    const unsigned long long K = peel_block_max_u64(k0, l4);
-    __syncthreads();
-    const unsigned long long P = peel_block_max_u64(k0 == K ? k1 : 0ull, l4);
-    __syncthreads();
-    k0 = K; k1 = P;
-  }
-  uint32_t g = 0;
-  if (k0 != 0) g = 0xFFFFFFFFu - (uint32_t)(k1 & 0xFFFFFFFFull);
-  if (k0 != 0 && g >= T) { k0 = 0; k1 = 0; g = 0; }  // (cannot happen with pairs of this context's own arg-max: never index with it)
-  if (blockIdx.x == 0 && threadIdx.x == 0) { words->key2[0] = k0; words->key2[1] = k0 ? k1 : 0ull; }
-  if (threadIdx.x < 12) {
-    const float ident = (threadIdx.x == 0 || threadIdx.x == 4 || threadIdx.x == 8) ? 1.f : 0.f;
-    const float v = k0 != 0 ? RtSoA[(size_t)threadIdx.x * ld_local + g] : ident;
-    sRt[threadIdx.x] = v;
-    if (blockIdx.x == 0) Rt12[threadIdx.x] = v;
-  }
-  // the winner's rank index: keys above its own, and equal keys at lower positions
-  uint32_t r = 0;
-  if (k0 != 0) {
-    const uint32_t wk = (uint32_t)(k0 & 0xFFFFFFFFull);  // = sel_key[g]
-    const uint32_t qs = gridDim.x * 256;
-    for (uint32_t q = blockIdx.x * 256 + threadIdx.x; q < T4; q += qs) {
-      const uint4 v = k4[q];
-      const uint32_t t = q << 2;
-      r += (v.x > wk) || (v.x == wk && t < g);
-      r += (v.y > wk) || (v.y == wk && t + 1 < g);
-      r += (v.z > wk) || (v.z == wk && t + 2 < g);
-      r += (v.w > wk) || (v.w == wk && t + 3 < g);
-    }
-    if (blockIdx.x == 0) {
-      const uint32_t t = (T4 << 2) + threadIdx.x;  // the last T % 4 keys
-      if (t < T) { const uint32_t kt = sel_key[t]; r += (kt > wk) || (kt == wk && t < g); }
-    }
-  }
+  const uint4 v_first = rank_prefetch(sel_key, T);
+  // the arg-max launch's per-workgroup pairs -> (best key, lowest position attaining it)
+  unsigned long long k0, k1;
+  reduce_pairs(pairs, npairs, reinterpret_cast<unsigned long long*>(lds), k0, k1);
+  const Winner w = winner_decode(k0, k1, true, T);
+  winner_key_store(words->key2, w);
+  winner_rt_to_lds(RtSoA + w.g, ld_local, w.k0 != 0, sRt, Rt12);
+  uint32_t r = 0;  // (the key's low half is sel_key[g])
+  if (w.k0 != 0) r = rank_count(sel_key, T, v_first, (uint32_t)(w.k0 & 0xFFFFFFFFull), w.g);
   const uint64_t rb = block_reduce_u64(r, lds);  // also the barrier that publishes sRt to the block
-  if (m < n) {
-    float M[12];
-#pragma unroll
-    for (int c = 0; c < 12; c++) M[c] = sRt[c];
-    const bool live = k0 != 0ull && finite12(M);
-    const float d2 = resid2(M, cp[0], cp[1], cp[2], cp[3], cp[4], cp[5]);
-    mask[m] = (free_m && live && d2 < tau2) ? 1 : 0;
-  }
-  if (threadIdx.x == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    const unsigned long long was = __hip_atomic_fetch_add(&words->fin_word, (1ull << 32) | (unsigned long long)(uint32_t)rb,
-                                                          __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s_last = ((uint32_t)(was >> 32) == gridDim.x - 1) ? 1u : 0u;
-    if (s_last) {
-      const uint32_t rank = (uint32_t)was + (uint32_t)rb;
-      __hip_atomic_store(&words->fin_word, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next round
-      __hip_atomic_store(&host_out[1], k0 ? (((unsigned long long)rank << 32) | (unsigned long long)g) : 0ull, __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_SYSTEM);
-      publish_host(reinterpret_cast<uint64_t*>(host_out), k0);  // [0] last: the host polls it (release orders the others before it)
-    }
+  if (m < n) mask[m] = (free_m && winner_inlier(sRt, w.k0 != 0ull, cp, tau2)) ? 1 : 0;
+  uint32_t rank;
+  if (threadIdx.x == 0 && last_workgroup_sum(&words->fin_word, (uint32_t)rb, &rank)) {
+    __hip_atomic_store(&host_out[1], w.k0 ? (((unsigned long long)rank << 32) | (unsigned long long)w.g) : 0ull, __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_SYSTEM);
+    publish_host(reinterpret_cast<uint64_t*>(host_out), w.k0);  // [0] last: the host polls it (release orders the others before it)
   }
 }
 
@@ -207,10 +140,7 @@ void launch_peel_compact(const Points& pts, const float* RtSoA, uint32_t ld_loca
 void launch_peel_winner(const Points& pts, const uint8_t* claimed, const float* RtSoA, uint32_t ld_local, const uint32_t* sel_key,
                         uint32_t T, const uint64_t* pairs, int npairs, float tau2, float* Rt12, uint8_t* mask, PeelWords* words,
                         uint64_t* host_out, hipStream_t st) {
-  uint32_t blocks = (uint32_t)((pts.n + 255) / 256);  // the mask needs these; more only if the key list is long (launch_finalize)
-  const uint32_t for_keys = (T / 4 + 1023) / 1024;
-  if (for_keys > blocks) blocks = for_keys < 1024u ? for_keys : 1024u;
-  hipLaunchKernelGGL(peel_winner_kernel, dim3(blocks), dim3(256), 0, st, pts.planes, pts.n, pts.ld, claimed, RtSoA, ld_local,
+  hipLaunchKernelGGL(peel_winner_kernel, dim3(winner_blocks(pts.n, T)), dim3(256), 0, st, pts.planes, pts.n, pts.ld, claimed, RtSoA, ld_local,
                      sel_key, T, reinterpret_cast<const unsigned long long*>(pairs), npairs, tau2, Rt12, mask, words,
                      reinterpret_cast<unsigned long long*>(host_out));
 }

@@ -22,6 +22,7 @@
 #include "sc_block.hpp"
 #include "sc_kernels.hpp"
 #include "sc_refine.hpp"
+#include "sc_winner.hpp"
 
 namespace sc {
 
@@ -141,7 +142,7 @@ __global__ __launch_bounds__(POLISH_THREADS) void polish_select_kernel(const uin
     for (uint32_t j = 0; j < K; j++) above += key_above(s_sel[j], s_sel[tid]) ? 1u : 0u;
     s_pos[above] = tid;
   }
-  // rank in the ranked list: ranking keys above one's own, and equal keys at lower positions (finalize_kernel's count), eight
+  // rank in the ranked list: the keys that outrank one's own (sc_winner.hpp: what finalize_kernel counts for its winner), eight
   // candidates per walk over the keys
   __syncthreads();
 #pragma unroll 1
@@ -149,14 +150,14 @@ __global__ __launch_bounds__(POLISH_THREADS) void polish_select_kernel(const uin
     uint32_t r[8], ck[8], cg[8];
 #pragma unroll
     for (int j = 0; j < 8; j++) {
-      const bool live = c0 + j < K;  // (past K: a key nothing is above)
-      r[j] = 0u; ck[j] = live ? s_sel[c0 + j].w[1] : 0xFFFFFFFFu; cg[j] = live ? s_sel[c0 + j].w[2] : 0xFFFFFFFFu;
+      const bool live = c0 + j < K;  // (past K: a key nothing outranks)
+      r[j] = 0u; ck[j] = live ? s_sel[c0 + j].w[1] : 0xFFFFFFFFu; cg[j] = live ? ~s_sel[c0 + j].w[2] : 0u;
     }
 #pragma unroll 8
     for (uint64_t g = tid; g < T; g += POLISH_THREADS) {
-      const uint32_t k = sel_key[g], ng = ~(uint32_t)g;
+      const uint32_t k = sel_key[g];
 #pragma unroll
-      for (int j = 0; j < 8; j++) r[j] += (k > ck[j] || (k == ck[j] && ng > cg[j])) ? 1u : 0u;
+      for (int j = 0; j < 8; j++) r[j] += outranks(k, (uint32_t)g, ck[j], cg[j]) ? 1u : 0u;
     }
 #pragma unroll
     for (int j = 0; j < 8; j++) {
@@ -214,8 +215,7 @@ __global__ __launch_bounds__(POLISH_THREADS) void polish_kernel(const float* __r
       const int m = ch * 64 + (int)(tid & 63u);
       bool inl = false;
       if (m < n)
-        inl = fin && resid2(M, planes[m], planes[(size_t)ld + m], planes[(size_t)2 * ld + m], planes[(size_t)3 * ld + m],
-                            planes[(size_t)4 * ld + m], planes[(size_t)5 * ld + m]) < tau2;
+        inl = fin && within_tau(M, load_corr(planes, ld, m), tau2);
       const unsigned long long bal = __ballot(inl);
       if ((tid & 63u) == 0u) bits[(size_t)ch * 16 + POLISH_BITS_SLOT] = bal;
     }
@@ -294,9 +294,10 @@ __global__ __launch_bounds__(POLISH_THREADS) void polish_kernel(const float* __r
   for (int c = 0; c < 12; c++) M[c] = sRt[c];
   uint64_t s = 0;
   if (finite12(M))
-    for (int m = (int)tid; m < n; m += POLISH_THREADS)
-      s += score_term(M, planes[m], planes[(size_t)ld + m], planes[(size_t)2 * ld + m], planes[(size_t)3 * ld + m],
-                      planes[(size_t)4 * ld + m], planes[(size_t)5 * ld + m], thr, score_mode);
+    for (int m = (int)tid; m < n; m += POLISH_THREADS) {
+      const Corr c = load_corr(planes, ld, m);
+      s += score_term(M, c.v[0], c.v[1], c.v[2], c.v[3], c.v[4], c.v[5], thr, score_mode);
+    }
   s = block_reduce_u64(s, s_red);
   if (tid < 12) me->Rt[tid] = M[tid];
   if (tid == 0) { me->score = (uint32_t)s; me->iters = (uint16_t)iters; }
@@ -322,22 +323,10 @@ __global__ __launch_bounds__(256) void polish_winner_kernel(const float* __restr
   }
   __syncthreads();
   const uint32_t win = s_win;
-  if (threadIdx.x < 12) {
-    const float ident = (threadIdx.x == 0 || threadIdx.x == 4 || threadIdx.x == 8) ? 1.f : 0.f;
-    const float v = K ? cand[win].Rt[threadIdx.x] : ident;
-    sRt[threadIdx.x] = v;
-    if (blockIdx.x == 0) Rt12[threadIdx.x] = v;
-  }
+  winner_rt_to_lds(cand[win].Rt, 1, K != 0u, sRt, Rt12);  // (a record's twelve floats are consecutive)
   __syncthreads();
   const int m = blockIdx.x * 256 + threadIdx.x;
-  if (m < n) {
-    float M[12];
-#pragma unroll
-    for (int c = 0; c < 12; c++) M[c] = sRt[c];
-    const float d2 = resid2(M, planes[m], planes[(size_t)ld + m], planes[(size_t)2 * ld + m], planes[(size_t)3 * ld + m],
-                            planes[(size_t)4 * ld + m], planes[(size_t)5 * ld + m]);
-    mask[m] = (K != 0u && finite12(M) && d2 < tau2) ? 1 : 0;
-  }
+  if (m < n) mask[m] = winner_inlier(sRt, K != 0u, load_corr(planes, ld, m), tau2) ? 1 : 0;
   if (blockIdx.x != 0) return;
   if (out_cand) {  // the records, 16 words each (entries past K are zero already)
     const uint32_t* from = reinterpret_cast<const uint32_t*>(cand);

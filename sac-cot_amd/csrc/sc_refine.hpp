@@ -1,4 +1,4 @@
-// sc_refine.hpp — the fp64 solve of the least-squares rigid refit, shared by refine_kernel (sc_score.hip: one refit
+// sc_refine.hpp — the fp64 solve of the least-squares rigid refit, shared by refine_kernel (sc_final.hip: one refit
 // over a given mask) and polish_kernel (sc_polish.hip: refits iterated to a fixed point).  Both kernels sum the centroids and H in
 // the canonical order of oracle/saccot_oracle.c::so_refine; what follows the sums is this one function, run by one thread.
 #pragma once

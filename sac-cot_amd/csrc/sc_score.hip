@@ -1,5 +1,9 @@
-// sc_score.hip — stage C: per-triangle rigid transform (C1), hypothesis x correspondence inlier counting
-// (C2) and the winner's mask (C3).  SURVEY.md §8a rows C1, C2, C3.
+// sc_score.hip — stage C1 and C2: per-triangle rigid transform (C1) and hypothesis x correspondence inlier counting (C2) with its
+// arg-max.  SURVEY.md §8a rows C1, C2.  (C3 — the winner, its mask, the refit — is sc_final.hip.)
+//
+// C1 and C2 stay ONE file: kabsch_shard_kernel calls filter_tile_block and gram_coef_block (the Kabsch launch carries C2's fp16 tile and
+// the Gram coefficient rows), and the library is built without relocatable device code: a __device__ function is callable only from the
+// file that defines it.  Order: plain C2 kernel, arg-max, linear filter, exact pass, Gram tile and coefficients, C1 (behind what it calls), guard, Gram filter, launchers.
 //
 // C2 is the arithmetic-heavy kernel of the path (T*N tests, 27 flop each) and moves almost no HBM bytes
 // (48 B per hypothesis in, 4 B out), so it is bounded by the fp32 vector rate, not by HBM.  Mapping:
@@ -18,7 +22,6 @@
 #include "sc_arith.hpp"
 #include "sc_block.hpp"
 #include "sc_kernels.hpp"
-#include "sc_refine.hpp"
 #include "sc_gramref.hpp"
 
 namespace sc {
@@ -65,86 +68,6 @@ __host__ __device__ inline double gram_eps_sum(double F, double m, double Tn, do
   const double t1 = 2.0 * (m + 1.5 * g) * Qb * Pn, t2 = vb * vb, t3 = 2.0 * F * Tn * Pn, t4 = 2.0 * Tn * vb, t5 = Tn * Tn + 1.5 * st * st;
   const double Sl = 2.0 * (F + 4.5 * g) * Qb * Pn + t3 + t4, S = Sl + t2 + t5;
   return GX_ACC * 1.05 * (t1 + t2 + t3 + t4 + t5) + GX_Q * Sl + GX_NORM * t2 + 1e-8 * S + 3.0 * g * vb * Pn + 1e-4;
-}
-
-// ------------------------------------------------------------------------------------------------
-// C1
-// ------------------------------------------------------------------------------------------------
-__device__ void filter_tile_block(const float* __restrict__ planes, int n, int ld, const FilterTileJob& job, uint32_t block,
-                                  uint32_t blocks);
-__device__ void gram_coef_block(const GramCoef& coef, const float v[12], uint32_t l, uint32_t ldl, uint32_t n_local, float tau2);
-
-__global__ __launch_bounds__(256) void kabsch_shard_kernel(const float* __restrict__ planes, int n, int ld, TriSource ts,
-                                                           Shard sh, float* __restrict__ RtSoA,
-                                                           float* __restrict__ RtAoS, FilterTileJob job,
-                                                           uint32_t kabsch_blocks,
-                                                           const uint64_t* __restrict__ t_eff_dev) {
-  if (blockIdx.x >= kabsch_blocks) {  // the extra workgroups: C2's fp16 tile of the correspondences (see filter_tile_block)
-    filter_tile_block(planes, n, ld, job, blockIdx.x - kabsch_blocks, gridDim.x - kabsch_blocks);
-    return;
-  }
-  const uint32_t l = blockIdx.x * 256 + threadIdx.x;  // < ld_local: a multiple of 256, kabsch_blocks = ld_local / 256
-  float Rt[12];
-  // t_eff_dev: the launch was sized for sh.T_eff = the requested T before the host knew how many triangles there are; a
-  // position beyond the real selection holds nothing that may be dereferenced (the host repeats such a call: sc_capi.hip)
-  const uint32_t g = l < sh.n_local ? shard_global_index(l, sh.block, sh.rank, sh.world) : 0u;
-  uint32_t v[3];
-  if (l < sh.n_local && (!t_eff_dev || (uint64_t)g < *t_eff_dev) && tri_lookup(ts, g, v)) {
-    float P[9], Q[9];
-    load_triangle(planes, ld, v, P, Q);
-    kabsch3(P, Q, Rt);
-  } else {
-#pragma unroll
-    for (int c = 0; c < 12; c++) Rt[c] = 0.0f;
-  }
-#pragma unroll
-  for (int c = 0; c < 12; c++) RtSoA[(size_t)c * sh.ld_local + l] = Rt[c];
-  if (RtAoS) {  // 12 consecutive floats per hypothesis: what the lane = correspondence scoring kernel loads as scalars
-    float4* o = reinterpret_cast<float4*>(RtAoS + 12 * (size_t)l);
-    o[0] = make_float4(Rt[0], Rt[1], Rt[2], Rt[3]);
-    o[1] = make_float4(Rt[4], Rt[5], Rt[6], Rt[7]);
-    o[2] = make_float4(Rt[8], Rt[9], Rt[10], Rt[11]);
-  }
-  // the Gram filter's coefficients of this hypothesis (whole workgroups get here: ld_local is a multiple of 256)
-  if (job.mode == 2) gram_coef_block(job.coef, Rt, l, sh.ld_local, sh.n_local, job.tau2);
-}
-
-void launch_kabsch(const Points& pts, const TriSource& ts, const Shard& sh, float* RtSoA, float* RtAoS,
-                   const FilterTileJob* tile_job, hipStream_t st, const uint64_t* t_eff_dev) {
-  if (sh.ld_local == 0) return;
-  const uint32_t kb = sh.ld_local / 256, tb = tile_job ? (tile_job->rows + 255) / 256 : 0u;
-  hipLaunchKernelGGL(kabsch_shard_kernel, dim3(kb + tb), dim3(256), 0, st, pts.planes, pts.n, pts.ld, ts, sh, RtSoA, RtAoS,
-                     tile_job ? *tile_job : FilterTileJob{}, kb, t_eff_dev);
-}
-
-__global__ __launch_bounds__(256) void kabsch_aos_kernel(const float* __restrict__ planes, int ld,
-                                                         const uint32_t* __restrict__ tri, uint32_t T,
-                                                         float* __restrict__ Rt_out) {
-  const uint32_t h = blockIdx.x * 256 + threadIdx.x;
-  if (h >= T) return;
-  float P[9], Q[9], Rt[12];
-  load_triangle(planes, ld, tri + 3 * (size_t)h, P, Q);
-  kabsch3(P, Q, Rt);
-#pragma unroll
-  for (int c = 0; c < 12; c++) Rt_out[12 * (size_t)h + c] = Rt[c];
-}
-
-void launch_kabsch_aos(const Points& pts, const uint32_t* tri, uint32_t T, float* Rt, hipStream_t st) {
-  if (T == 0) return;
-  hipLaunchKernelGGL(kabsch_aos_kernel, dim3((T + 255) / 256), dim3(256), 0, st, pts.planes, pts.ld, tri, T, Rt);
-}
-
-__global__ __launch_bounds__(256) void rt_to_soa_kernel(const float* __restrict__ Rt, uint32_t T, uint32_t ld_local,
-                                                        float* __restrict__ RtSoA) {
-  const uint32_t l = blockIdx.x * 256 + threadIdx.x;
-  if (l >= ld_local) return;
-#pragma unroll
-  for (int c = 0; c < 12; c++) RtSoA[(size_t)c * ld_local + l] = (l < T) ? Rt[12 * (size_t)l + c] : 0.0f;
-}
-
-void launch_rt_to_soa(const float* Rt, uint32_t T, uint32_t ld_local, float* RtSoA, hipStream_t st) {
-  if (ld_local == 0) return;
-  hipLaunchKernelGGL(rt_to_soa_kernel, dim3(ld_local / 256), dim3(256), 0, st, Rt, T, ld_local, RtSoA);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -338,19 +261,6 @@ __global__ __launch_bounds__(SCORE_THREADS, 8) void score_kernel(const float* __
                     partial);
 }
 
-__device__ __forceinline__ unsigned long long block_max_u64(unsigned long long k, unsigned long long* lds) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long other = __shfl_xor(k, o);
-    k = other > k ? other : k;
-  }
-  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = k;
-  __syncthreads();
-  unsigned long long b = lds[0];
-  for (int w = 1; w < 4; w++) b = lds[w] > b ? lds[w] : b;
-  return b;
-}
-
 // Per-hypothesis count (sum of the chunk partials) and the winner key pair, in ONE launch and without atomics on
 // the keys: every block reduces its hypotheses to (best key, lowest position attaining it) and stores the pair; the
 // block that takes the last ticket reduces the pairs and writes key2[0..1] (so key2 needs no zeroing).
@@ -388,15 +298,13 @@ __global__ __launch_bounds__(256) void score_argmax_kernel(const uint32_t* __res
     if (c) {
       const unsigned long long kk = ((unsigned long long)c << 32) | (unsigned long long)second;
       const unsigned long long pp = (unsigned long long)(0xFFFFFFFFu - g);
-      if (kk > k || (kk == k && pp > pos)) { k = kk; pos = pp; }
+      lexmax_take(k, pos, kk, pp);
     }
   }
-  const unsigned long long bk = block_max_u64(k, lds);
-  __syncthreads();
-  const unsigned long long bp = block_max_u64((k == bk) ? pos : 0ull, lds);
+  block_lexmax_u64(k, pos, lds);
   if (threadIdx.x == 0) {
-    __hip_atomic_store(&pairs[2 * blockIdx.x], bk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(&pairs[2 * blockIdx.x + 1], bp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(&pairs[2 * blockIdx.x], k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(&pairs[2 * blockIdx.x + 1], pos, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   // key2 == nullptr: the pairs go to this context's own finalize_kernel, whose workgroups each reduce them themselves (r05: the
   // release, the ticket and the last workgroup's pass over the pairs were ~2.5 us of this launch's 8.6 at C2)
@@ -413,14 +321,12 @@ __global__ __launch_bounds__(256) void score_argmax_kernel(const uint32_t* __res
   for (uint32_t b = threadIdx.x; b < gridDim.x; b += 256) {
     const unsigned long long a = __hip_atomic_load(&pairs[2 * b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const unsigned long long q = __hip_atomic_load(&pairs[2 * b + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (a > gk || (a == gk && q > gp)) { gk = a; gp = q; }
+    lexmax_take(gk, gp, a, q);
   }
-  const unsigned long long K = block_max_u64(gk, lds);
-  __syncthreads();
-  const unsigned long long P = block_max_u64((gk == K) ? gp : 0ull, lds);
+  block_lexmax_u64(gk, gp, lds);  // (lds: the barrier behind the ticket lies between the two reductions)
   if (threadIdx.x == 0) {
-    key2[0] = K;
-    key2[1] = (K != 0 && sel_key) ? P : 0ull;
+    key2[0] = gk;
+    key2[1] = (gk != 0 && sel_key) ? gp : 0ull;
     __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next launch
   }
 }
@@ -615,47 +521,6 @@ FilterPlan filter_plan(int n, uint32_t ld_local, const Tuning& tn, uint32_t mode
   // Gram: per coefficient row 64 bytes of fp16 halves + C, W, flag, hperm; per tile row pperm
   fp.coef_bytes = mode == 2 ? (size_t)ld_local * (64 + 16) + (size_t)fp.rows * 4 : 0;
   return fp;
-}
-
-// The fp16 image of the correspondences, 32 bytes each, in the K order of the B operand:
-//   [Pxh Pxl Pxh  Pyh Pyl Pyh  Pzh Pzl | Pzh  Qxh Qxl  Qyh Qyl  Qzh Qzl  0];  rows [n, rows) are sentinels (far away).
-// The two 16-byte halves of a correspondence are NOT adjacent: see the group layout at the end of filter_tile_block.
-// mx_cur: max |p| and max |q| of the call (bit patterns; stage_points_kernel's atomicMax).  Also clears the filter's
-// counters and bitmap for this call, so nothing needs a memset.
-__device__ void gram_tile_block(const float* __restrict__ planes, int n, int ld, const FilterTileJob& job, uint32_t block,
-                                uint32_t blocks);
-__device__ void filter_tile_block(const float* __restrict__ planes, int n, int ld, const FilterTileJob& job, uint32_t block,
-                                  uint32_t blocks) {
-  if (job.mode == 2) { gram_tile_block(planes, n, ld, job, block, blocks); return; }
-  const uint32_t m = block * 256 + threadIdx.x;
-  for (uint32_t z = m; z < job.zero_words; z += blocks * 256) job.zero[z] = 0u;
-  const float Pmax = __uint_as_float(job.mx_cur[0]), Qmax = __uint_as_float(job.mx_cur[1]), mxv = fmaxf(Pmax, Qmax);
-  const int e = (int)((__float_as_uint(mxv) >> 23) & 255u) - 127;  // mxv in [2^e, 2^(e+1))
-  int k = 8 - e;
-  k = k > 100 ? 100 : (k < -100 ? -100 : k);
-  const float s = __uint_as_float((uint32_t)(k + 127) << 23);
-  if (m == 0) *static_cast<FilterInfo*>(job.info) = FilterInfo{s, Pmax, Qmax, 0.f};
-  if (m >= job.rows) return;
-  _Float16 hi[6], lo[6];
-#pragma unroll
-  for (int c = 0; c < 6; c++) {
-    const float X = m < (uint32_t)n ? planes[(size_t)c * ld + m] * s : (c < 3 ? 0.f : 32768.f);
-    hi[c] = (_Float16)X;
-    lo[c] = (_Float16)(X - (float)hi[c]);
-  }
-  half8 f0 = {hi[0], lo[0], hi[0], hi[1], lo[1], hi[1], hi[2], lo[2]};
-  half8 f1 = {hi[2], hi[3], lo[3], hi[4], lo[4], hi[5], lo[5], (_Float16)0.f};
-  // per group of 32 correspondences (one MFMA step): the 32 first halves (k0..7), then the 32 second halves (k8..15) —
-  // lane l of a wave then reads the 16 bytes at 16 l of the group's 1 KiB: a linear, bank-conflict-free ds_read_b128
-  // (with the two halves of a correspondence side by side the lanes of a half stride 32 bytes: 2-way conflicts, +4
-  // cycles on each 8-cycle read by SQ_LDS_BANK_CONFLICT)
-  uint4* tile = static_cast<uint4*>(job.tile);
-  const size_t slot = (size_t)(m >> 5) * 64 + (m & 31u);
-  tile[slot] = *reinterpret_cast<uint4*>(&f0);
-  tile[slot + 32] = *reinterpret_cast<uint4*>(&f1);
-}
-__global__ __launch_bounds__(256) void filter_tile_kernel(const float* __restrict__ planes, int n, int ld, FilterTileJob job) {
-  filter_tile_block(planes, n, ld, job, blockIdx.x, gridDim.x);
 }
 
 // F.  Workgroup = FX_WAVES waves; wave w of workgroup b owns hypotheses 8 (FX_WAVES b + w) .. + 7 and never talks to
@@ -1170,6 +1035,45 @@ __device__ void gram_tile_block(const float* __restrict__ planes, int n, int ld,
   }
 }
 
+// The fp16 image of the correspondences, 32 bytes each, in the K order of the B operand:
+//   [Pxh Pxl Pxh  Pyh Pyl Pyh  Pzh Pzl | Pzh  Qxh Qxl  Qyh Qyl  Qzh Qzl  0];  rows [n, rows) are sentinels (far away).
+// The two 16-byte halves of a correspondence are NOT adjacent: see the group layout at the end of filter_tile_block.
+// mx_cur: max |p| and max |q| of the call (bit patterns; stage_points_kernel's atomicMax).  Also clears the filter's
+// counters and bitmap for this call, so nothing needs a memset.
+__device__ void filter_tile_block(const float* __restrict__ planes, int n, int ld, const FilterTileJob& job, uint32_t block,
+                                  uint32_t blocks) {
+  if (job.mode == 2) { gram_tile_block(planes, n, ld, job, block, blocks); return; }
+  const uint32_t m = block * 256 + threadIdx.x;
+  for (uint32_t z = m; z < job.zero_words; z += blocks * 256) job.zero[z] = 0u;
+  const float Pmax = __uint_as_float(job.mx_cur[0]), Qmax = __uint_as_float(job.mx_cur[1]), mxv = fmaxf(Pmax, Qmax);
+  const int e = (int)((__float_as_uint(mxv) >> 23) & 255u) - 127;  // mxv in [2^e, 2^(e+1))
+  int k = 8 - e;
+  k = k > 100 ? 100 : (k < -100 ? -100 : k);
+  const float s = __uint_as_float((uint32_t)(k + 127) << 23);
+  if (m == 0) *static_cast<FilterInfo*>(job.info) = FilterInfo{s, Pmax, Qmax, 0.f};
+  if (m >= job.rows) return;
+  _Float16 hi[6], lo[6];
+#pragma unroll
+  for (int c = 0; c < 6; c++) {
+    const float X = m < (uint32_t)n ? planes[(size_t)c * ld + m] * s : (c < 3 ? 0.f : 32768.f);
+    hi[c] = (_Float16)X;
+    lo[c] = (_Float16)(X - (float)hi[c]);
+  }
+  half8 f0 = {hi[0], lo[0], hi[0], hi[1], lo[1], hi[1], hi[2], lo[2]};
+  half8 f1 = {hi[2], hi[3], lo[3], hi[4], lo[4], hi[5], lo[5], (_Float16)0.f};
+  // per group of 32 correspondences (one MFMA step): the 32 first halves (k0..7), then the 32 second halves (k8..15) —
+  // lane l of a wave then reads the 16 bytes at 16 l of the group's 1 KiB: a linear, bank-conflict-free ds_read_b128
+  // (with the two halves of a correspondence side by side the lanes of a half stride 32 bytes: 2-way conflicts, +4
+  // cycles on each 8-cycle read by SQ_LDS_BANK_CONFLICT)
+  uint4* tile = static_cast<uint4*>(job.tile);
+  const size_t slot = (size_t)(m >> 5) * 64 + (m & 31u);
+  tile[slot] = *reinterpret_cast<uint4*>(&f0);
+  tile[slot + 32] = *reinterpret_cast<uint4*>(&f1);
+}
+__global__ __launch_bounds__(256) void filter_tile_kernel(const float* __restrict__ planes, int n, int ld, FilterTileJob job) {
+  filter_tile_block(planes, n, ld, job, blockIdx.x, gridDim.x);
+}
+
 // Per-hypothesis coefficients of the Gram filter, made ONCE per call (by the Kabsch launch's own threads, or by
 // gram_coef_kernel for the stage hook): thread = hypothesis l of this rank's shard, a whole 256-thread workgroup calls it.
 // The row a hypothesis gets: NEAR ones from the front, everything else from row ldl - 1 down (one atomic per workgroup and
@@ -1299,6 +1203,82 @@ __global__ __launch_bounds__(256) void gram_coef_kernel(const float* __restrict_
 #pragma unroll
   for (int c = 0; c < 12; c++) v[c] = l < ldl ? RtSoA[(size_t)c * ldl + l] : 0.f;
   gram_coef_block(coef, v, l, ldl, n_local, tau2);
+}
+
+// ------------------------------------------------------------------------------------------------
+// C1
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void kabsch_shard_kernel(const float* __restrict__ planes, int n, int ld, TriSource ts,
+                                                           Shard sh, float* __restrict__ RtSoA,
+                                                           float* __restrict__ RtAoS, FilterTileJob job,
+                                                           uint32_t kabsch_blocks,
+                                                           const uint64_t* __restrict__ t_eff_dev) {
+  if (blockIdx.x >= kabsch_blocks) {  // the extra workgroups: C2's fp16 tile of the correspondences (see filter_tile_block)
+    filter_tile_block(planes, n, ld, job, blockIdx.x - kabsch_blocks, gridDim.x - kabsch_blocks);
+    return;
+  }
+  const uint32_t l = blockIdx.x * 256 + threadIdx.x;  // < ld_local: a multiple of 256, kabsch_blocks = ld_local / 256
+  float Rt[12];
+  // t_eff_dev: the launch was sized for sh.T_eff = the requested T before the host knew how many triangles there are; a
+  // position beyond the real selection holds nothing that may be dereferenced (the host repeats such a call: sc_capi.hip)
+  const uint32_t g = l < sh.n_local ? shard_global_index(l, sh.block, sh.rank, sh.world) : 0u;
+  uint32_t v[3];
+  if (l < sh.n_local && (!t_eff_dev || (uint64_t)g < *t_eff_dev) && tri_lookup(ts, g, v)) {
+    float P[9], Q[9];
+    load_triangle(planes, ld, v, P, Q);
+    kabsch3(P, Q, Rt);
+  } else {
+#pragma unroll
+    for (int c = 0; c < 12; c++) Rt[c] = 0.0f;
+  }
+#pragma unroll
+  for (int c = 0; c < 12; c++) RtSoA[(size_t)c * sh.ld_local + l] = Rt[c];
+  if (RtAoS) {  // 12 consecutive floats per hypothesis: what the lane = correspondence scoring kernel loads as scalars
+    float4* o = reinterpret_cast<float4*>(RtAoS + 12 * (size_t)l);
+    o[0] = make_float4(Rt[0], Rt[1], Rt[2], Rt[3]);
+    o[1] = make_float4(Rt[4], Rt[5], Rt[6], Rt[7]);
+    o[2] = make_float4(Rt[8], Rt[9], Rt[10], Rt[11]);
+  }
+  // the Gram filter's coefficients of this hypothesis (whole workgroups get here: ld_local is a multiple of 256)
+  if (job.mode == 2) gram_coef_block(job.coef, Rt, l, sh.ld_local, sh.n_local, job.tau2);
+}
+
+void launch_kabsch(const Points& pts, const TriSource& ts, const Shard& sh, float* RtSoA, float* RtAoS,
+                   const FilterTileJob* tile_job, hipStream_t st, const uint64_t* t_eff_dev) {
+  if (sh.ld_local == 0) return;
+  const uint32_t kb = sh.ld_local / 256, tb = tile_job ? (tile_job->rows + 255) / 256 : 0u;
+  hipLaunchKernelGGL(kabsch_shard_kernel, dim3(kb + tb), dim3(256), 0, st, pts.planes, pts.n, pts.ld, ts, sh, RtSoA, RtAoS,
+                     tile_job ? *tile_job : FilterTileJob{}, kb, t_eff_dev);
+}
+
+__global__ __launch_bounds__(256) void kabsch_aos_kernel(const float* __restrict__ planes, int ld,
+                                                         const uint32_t* __restrict__ tri, uint32_t T,
+                                                         float* __restrict__ Rt_out) {
+  const uint32_t h = blockIdx.x * 256 + threadIdx.x;
+  if (h >= T) return;
+  float P[9], Q[9], Rt[12];
+  load_triangle(planes, ld, tri + 3 * (size_t)h, P, Q);
+  kabsch3(P, Q, Rt);
+#pragma unroll
+  for (int c = 0; c < 12; c++) Rt_out[12 * (size_t)h + c] = Rt[c];
+}
+
+void launch_kabsch_aos(const Points& pts, const uint32_t* tri, uint32_t T, float* Rt, hipStream_t st) {
+  if (T == 0) return;
+  hipLaunchKernelGGL(kabsch_aos_kernel, dim3((T + 255) / 256), dim3(256), 0, st, pts.planes, pts.ld, tri, T, Rt);
+}
+
+__global__ __launch_bounds__(256) void rt_to_soa_kernel(const float* __restrict__ Rt, uint32_t T, uint32_t ld_local,
+                                                        float* __restrict__ RtSoA) {
+  const uint32_t l = blockIdx.x * 256 + threadIdx.x;
+  if (l >= ld_local) return;
+#pragma unroll
+  for (int c = 0; c < 12; c++) RtSoA[(size_t)c * ld_local + l] = (l < T) ? Rt[12 * (size_t)l + c] : 0.0f;
+}
+
+void launch_rt_to_soa(const float* Rt, uint32_t T, uint32_t ld_local, float* RtSoA, hipStream_t st) {
+  if (ld_local == 0) return;
+  hipLaunchKernelGGL(rt_to_soa_kernel, dim3(ld_local / 256), dim3(256), 0, st, Rt, T, ld_local, RtSoA);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1918,276 +1898,6 @@ void launch_argmax(const Shard& sh, const uint32_t* partial, uint32_t n_chunks, 
   const uint32_t blocks = argmax_blocks(sh.ld_local);
   hipLaunchKernelGGL(score_argmax_kernel, dim3(blocks), dim3(256), 0, st, partial, n_chunks, sh, sel_key, cnt,
                      reinterpret_cast<unsigned long long*>(pairs), ticket, reinterpret_cast<unsigned long long*>(key2));
-}
-
-// ------------------------------------------------------------------------------------------------
-// C3
-// ------------------------------------------------------------------------------------------------
-// C3 in ONE launch: every block re-solves the winner (thread 0; deterministic, so all blocks hold the same R,t) while
-// its other threads count their slice of the winner's rank index (#keys above the winner's + #equal keys at lower
-// positions — the number the ranked list would have given it), then masks its 256 correspondences.  The slice counts
-// meet in a control-block counter; the block that takes the last ticket publishes (key, position, rank) to the host.
-// (A single-block rank count cost 42 us at T = 400 k; a separate mask launch another ~4.5 us floor.)
-__global__ __launch_bounds__(256) void finalize_kernel(const float* __restrict__ planes, int n, int ld,
-                                                       TriSource ts, Shard sh, const float* __restrict__ RtSoA,
-                                                       const uint32_t* __restrict__ sel_key, uint32_t T,
-                                                       const unsigned long long* __restrict__ key2, int npairs,
-                                                       unsigned long long* __restrict__ key_out, float tau2,
-                                                       float* __restrict__ Rt12, uint8_t* __restrict__ mask,
-                                                       unsigned long long* __restrict__ fin_word,
-                                                       unsigned long long* __restrict__ host_out, DeferredPub dp) {
-  __shared__ uint64_t lds[8];
-  __shared__ float sRt[12];
-  __shared__ uint32_t s_last;
-  // (what does not depend on the winner is on its way before the pairs are looked at: this thread's correspondence, its first
-  // keys of the rank count — the kernel is a chain of dependent loads, ~1 us each)
-  const int m = blockIdx.x * 256 + threadIdx.x;
-  float cp[6];
-#pragma unroll
-  for (int c = 0; c < 6; c++) cp[c] = m < n ? planes[(size_t)c * ld + m] : 0.f;
-  const uint32_t T4 = T >> 2;  // 16-byte loads, grid-strided
-  const uint4* __restrict__ k4 = reinterpret_cast<const uint4*>(sel_key);
-  const uint32_t q_first = blockIdx.x * 256 + threadIdx.x;
-  uint4 v_first = make_uint4(0u, 0u, 0u, 0u);
-  if (sel_key != nullptr && q_first < T4) v_first = k4[q_first];
-  // key2: npairs winner key pairs (one per rank, all-gathered; npairs = 1: an already reduced pair).  The reduction of
-  // include/saccot.h — K0 = max pair[0], K1 = max pair[1] among the pairs attaining K0 — is a lexicographic max.
-  unsigned long long k0 = 0, k1 = 0;
-  if (npairs <= 8) {
-    for (int w = 0; w < npairs; w++) {  // wave-uniform addresses: scalar loads
-      const unsigned long long a = key2[2 * w], b = key2[2 * w + 1];
-      if (a > k0 || (a == k0 && b > k1)) { k0 = a; k1 = b; }
-    }
-  } else {  // many pairs (the arg-max launch's own workgroups', or a large world's): a thread takes every 256th, the block reduces
-    for (int w = threadIdx.x; w < npairs; w += 256) {
-      const unsigned long long a = key2[2 * w], b = key2[2 * w + 1];
-      if (a > k0 || (a == k0 && b > k1)) { k0 = a; k1 = b; }
-    }
-    unsigned long long* l4 = reinterpret_cast<unsigned long long*>(lds);
-    const unsigned long long K = block_max_u64(k0, l4);
-    __syncthreads();
-    const unsigned long long P = block_max_u64(k0 == K ? k1 : 0ull, l4);
-    __syncthreads();
-    k0 = K; k1 = P;
-  }
-  const bool two_stage = sel_key != nullptr;
-  uint32_t g = 0;
-  if (k0 != 0) g = 0xFFFFFFFFu - (uint32_t)((two_stage ? k1 : k0) & 0xFFFFFFFFull);
-  // The pairs come from the caller (an all-gather): a position outside the selection — a stale or uninitialised pair,
-  // ranks that disagree on T or the parameters — must not index sel_key / the triangle lookup.  It is treated as "no
-  // hypothesis" (identity, zero mask) and reported: host_out[1] = all ones makes the host return SC_EINVAL.
-  const bool bad_pair = k0 != 0 && g >= T;
-  if (bad_pair) { k0 = 0; k1 = 0; g = 0; }
-  if (key_out && blockIdx.x == 0 && threadIdx.x == 0) { key_out[0] = k0; key_out[1] = k0 ? k1 : 0ull; }
-  // The winner's (R,t): if THIS rank scored it, phase 1 left it in RtSoA (kabsch3 is deterministic, so these are the
-  // very bits a re-solve gives) — 12 parallel loads; otherwise thread 0 re-solves it from the replicated selection.
-  const uint32_t gb = sh.block ? g / sh.block : 0u;
-  const bool local = RtSoA != nullptr && k0 != 0 && g < sh.T_eff && (gb % sh.world) == sh.rank;
-  if (local) {
-    const uint32_t l = (gb / sh.world) * sh.block + (g % sh.block);
-    if (threadIdx.x < 12) {
-      const float v = RtSoA[(size_t)threadIdx.x * sh.ld_local + l];
-      sRt[threadIdx.x] = v;
-      if (blockIdx.x == 0) Rt12[threadIdx.x] = v;
-    }
-  } else if (threadIdx.x == 0) {
-    float Rt[12] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f};
-    uint32_t v[3];
-    if (k0 != 0 && tri_lookup(ts, g, v)) {
-      float P[9], Q[9];
-      load_triangle(planes, ld, v, P, Q);
-      kabsch3(P, Q, Rt);
-    }
-#pragma unroll
-    for (int c = 0; c < 12; c++) sRt[c] = Rt[c];
-    if (blockIdx.x == 0) {
-#pragma unroll
-      for (int c = 0; c < 12; c++) Rt12[c] = Rt[c];
-    }
-  }
-  uint32_t r = 0;
-  if (two_stage && k0 != 0) {
-    const uint32_t wk = (uint32_t)(k0 & 0xFFFFFFFFull);  // = sel_key[g]: the key's low half (score_argmax_kernel)
-    auto rank4 = [&](const uint4& v, uint32_t q) {
-      const uint32_t t = q << 2;
-      r += (v.x > wk) || (v.x == wk && t < g);
-      r += (v.y > wk) || (v.y == wk && t + 1 < g);
-      r += (v.z > wk) || (v.z == wk && t + 2 < g);
-      r += (v.w > wk) || (v.w == wk && t + 3 < g);
-    };
-    const uint32_t qs = gridDim.x * 256;
-    if (q_first < T4) rank4(v_first, q_first);
-    uint32_t q = q_first + qs;
-    for (; q + 3 * qs < T4; q += 4 * qs) {  // (four loads in flight: see score_argmax_kernel)
-      const uint4 a0 = k4[q], a1 = k4[q + qs], a2 = k4[q + 2 * qs], a3 = k4[q + 3 * qs];
-      rank4(a0, q); rank4(a1, q + qs); rank4(a2, q + 2 * qs); rank4(a3, q + 3 * qs);
-    }
-    {
-      uint4 w[3];
-#pragma unroll
-      for (uint32_t u = 0; u < 3; u++) w[u] = q + u * qs < T4 ? k4[q + u * qs] : make_uint4(0u, 0u, 0u, 0u);
-#pragma unroll
-      for (uint32_t u = 0; u < 3; u++) if (q + u * qs < T4) rank4(w[u], q + u * qs);
-    }
-    if (blockIdx.x == 0) {
-      const uint32_t t = (T4 << 2) + threadIdx.x;  // the last T % 4 keys
-      if (t < T) { const uint32_t kt = sel_key[t]; r += (kt > wk) || (kt == wk && t < g); }
-    }
-  }
-  const uint64_t rb = block_reduce_u64(r, lds);  // also the barrier that publishes sRt to the block
-  if (m < n) {
-    float M[12];
-#pragma unroll
-    for (int c = 0; c < 12; c++) M[c] = sRt[c];
-    const bool live = k0 != 0ull && finite12(M);
-    const float d2 = resid2(M, cp[0], cp[1], cp[2], cp[3], cp[4], cp[5]);
-    mask[m] = (live && d2 < tau2) ? 1 : 0;
-  }
-  if (threadIdx.x == 0) {
-    // ONE returning atomic per workgroup: workgroups finished in the high half, the rank count so far in the low half — the workgroup
-    // that finds every other one finished holds the whole count in the value it got back (no second accumulator, no acquire, no load)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    const unsigned long long was = __hip_atomic_fetch_add(fin_word, (1ull << 32) | (unsigned long long)(uint32_t)rb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s_last = ((uint32_t)(was >> 32) == gridDim.x - 1) ? 1u : 0u;
-    if (s_last) {
-      const uint32_t rank = (uint32_t)was + (uint32_t)rb;
-      __hip_atomic_store(fin_word, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next call
-      if (host_out && dp.host) {
-        // a host-free call: the words its earlier kernels would have published one by one go to the host HERE, with the winner
-        // (relaxed system-scope stores: the release store of the key below orders them before it).  Every such store costs the
-        // kernel that makes it ~0.5 us (seven of them cost the staging kernel 1.7 us; nine here cost this kernel 5:
-        // profiles/r05_ab_deferred_publish.txt), so stage B's two counts travel in ONE word — edges in the low half, triangles in
-        // the high half, all ones where one of them does not fit (the host then repeats the call) — and the staging kernel's
-        // coordinate statistics only every 64th host-free call of a context (dp.with_stats): a host-free call picks stage C2's
-        // kernel by the statistics of an earlier frame anyway, and any pick gives the same counts.
-        auto put = [&](int idx, unsigned long long v) { __hip_atomic_store(&dp.host[idx], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); };
-        const unsigned long long e = *dp.dev_edges, m = *dp.dev_triangles;
-        put(HW_EDGES, (e < (1ull << 32) && m < (1ull << 32)) ? (e | (m << 32)) : ~0ull);
-        if (dp.with_stats) {
-          for (int k = 0; k < 6; k++) put(HW_BOX + k, ((unsigned long long)dp.coord_max[8 + k] << 32) | dp.coord_max[2 + k]);
-          put(HW_COORD_MAX, ((unsigned long long)dp.coord_max[1] << 32) | dp.coord_max[0]);
-        }
-      }
-      if (host_out) {  // [0] last: the host polls it (release orders the others before it)
-        // ONE word beside the key (a system-scope store costs ~0.5 us: see DeferredPub): the winner's rank index in the high half,
-        // its position in the low half — or all ones: a key pair that decodes to nothing of the selection (the host: SC_EINVAL)
-        const unsigned long long rk = k0 ? (two_stage ? (unsigned long long)rank : (unsigned long long)g) : 0ull;
-        __hip_atomic_store(&host_out[1], bad_pair ? ~0ull : ((rk << 32) | (unsigned long long)g), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        publish_host(reinterpret_cast<uint64_t*>(host_out), k0);
-      }
-    }
-  }
-}
-
-__global__ __launch_bounds__(256) void mask_kernel(const float* __restrict__ planes, int n, int ld,
-                                                   const float* __restrict__ Rt12,
-                                                   const unsigned long long* __restrict__ key, float tau2,
-                                                   uint8_t* __restrict__ mask) {
-  const int m = blockIdx.x * 256 + threadIdx.x;
-  if (m >= n) return;
-  float M[12];
-#pragma unroll
-  for (int c = 0; c < 12; c++) M[c] = Rt12[c];
-  const bool live = (key == nullptr || *key != 0ull) && finite12(M);
-  const float d2 = resid2(M, planes[m], planes[(size_t)ld + m], planes[2 * (size_t)ld + m],
-                          planes[3 * (size_t)ld + m], planes[4 * (size_t)ld + m], planes[5 * (size_t)ld + m]);
-  mask[m] = (live && d2 < tau2) ? 1 : 0;
-}
-
-void launch_finalize(const Points& pts, const TriSource& ts, const Shard& sh, const float* RtSoA,
-                     const uint32_t* sel_key, uint32_t T, const uint64_t* key2, int npairs, uint64_t* key_out, float tau2, float* Rt12, uint8_t* mask,
-                     unsigned long long* fin_word, uint64_t* host_out, hipStream_t st, const DeferredPub* dp) {
-  uint32_t blocks = (uint32_t)((pts.n + 255) / 256);  // the mask needs these; more only if the key list is long
-  const uint32_t for_keys = (T / 4 + 1023) / 1024;    // >= 4 uint4 per thread before another block pays off
-  if (for_keys > blocks) blocks = for_keys < 1024u ? for_keys : 1024u;
-  hipLaunchKernelGGL(finalize_kernel, dim3(blocks), dim3(256), 0, st, pts.planes, pts.n, pts.ld, ts, sh, RtSoA, sel_key, T,
-                     reinterpret_cast<const unsigned long long*>(key2), npairs,
-                     reinterpret_cast<unsigned long long*>(key_out), tau2, Rt12, mask, fin_word,
-                     reinterpret_cast<unsigned long long*>(host_out), dp ? *dp : DeferredPub{nullptr, nullptr, nullptr, nullptr, 0});
-}
-
-// ------------------------------------------------------------------------------------------------
-// Winner refinement (optional — SC_FLAG_REFINE): fp64 least-squares rigid refit over the inlier mask.
-// Canonical order shared with oracle/saccot_oracle.c::so_refine: chunks of 64 consecutive points are summed
-// sequentially in index order (one thread per chunk), chunk sums are added sequentially in chunk order (thread 0);
-// pass 1 gives count and centroids, pass 2 H = sum (p - pc)(q - qc)^T by fma, then the two-dominant-pairs +
-// cross-product construction of kabsch3 in double with 10 Jacobi sweeps.  One workgroup: N is a few thousand.
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(1024) void refine_kernel(const float* __restrict__ planes, int n, int ld,
-                                                      const uint8_t* __restrict__ mask,
-                                                      const unsigned long long* __restrict__ key2,
-                                                      double* __restrict__ scratch, float* __restrict__ Rt12) {
-  __shared__ double cen[8];
-  if (key2[0] == 0ull) return;  // no hypothesis: nothing to refine (uniform)
-  const int nch = (n + 63) / 64;
-  // pass 1: per-chunk count / sum p / sum q
-  for (int ch = threadIdx.x; ch < nch; ch += 1024) {
-    double c[7] = {0, 0, 0, 0, 0, 0, 0};
-    const int m1 = min(n, ch * 64 + 64);
-    for (int m = ch * 64; m < m1; m++) {
-      if (!mask[m]) continue;
-      c[0] += 1.0;
-#pragma unroll
-      for (int k = 0; k < 3; k++) { c[1 + k] += (double)planes[(size_t)k * ld + m]; c[4 + k] += (double)planes[(size_t)(3 + k) * ld + m]; }
-    }
-#pragma unroll
-    for (int k = 0; k < 7; k++) scratch[(size_t)ch * 16 + k] = c[k];
-  }
-  __threadfence_block();
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double S[7] = {0, 0, 0, 0, 0, 0, 0};
-    for (int ch = 0; ch < nch; ch++)
-#pragma unroll
-      for (int k = 0; k < 7; k++) S[k] += scratch[(size_t)ch * 16 + k];
-    cen[0] = S[0];
-#pragma unroll
-    for (int k = 0; k < 3; k++) { cen[1 + k] = S[1 + k] / S[0]; cen[4 + k] = S[4 + k] / S[0]; }
-  }
-  __syncthreads();
-  if (cen[0] < 3.0) return;  // uniform
-  const double pc[3] = {cen[1], cen[2], cen[3]}, qc[3] = {cen[4], cen[5], cen[6]};
-  // pass 2: per-chunk covariance
-  for (int ch = threadIdx.x; ch < nch; ch += 1024) {
-    double h[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    const int m1 = min(n, ch * 64 + 64);
-    for (int m = ch * 64; m < m1; m++) {
-      if (!mask[m]) continue;
-      double a[3], b[3];
-#pragma unroll
-      for (int k = 0; k < 3; k++) {
-        a[k] = (double)planes[(size_t)k * ld + m] - pc[k];
-        b[k] = (double)planes[(size_t)(3 + k) * ld + m] - qc[k];
-      }
-#pragma unroll
-      for (int r = 0; r < 3; r++)
-#pragma unroll
-        for (int c = 0; c < 3; c++) h[3 * r + c] = __builtin_fma(a[r], b[c], h[3 * r + c]);
-    }
-#pragma unroll
-    for (int k = 0; k < 9; k++) scratch[(size_t)ch * 16 + k] = h[k];
-  }
-  __threadfence_block();
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  double H[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  for (int ch = 0; ch < nch; ch++)
-#pragma unroll
-    for (int k = 0; k < 9; k++) H[k] += scratch[(size_t)ch * 16 + k];
-  refine_solve(H, pc, qc, Rt12);  // (a non-finite result leaves Rt12 untouched)
-}
-
-size_t refine_scratch_bytes(int n) { return (size_t)((n + 63) / 64) * 16 * sizeof(double); }
-
-void launch_refine(const Points& pts, const uint8_t* mask, const uint64_t* key2, double* scratch, float* Rt12,
-                   hipStream_t st) {
-  hipLaunchKernelGGL(refine_kernel, dim3(1), dim3(1024), 0, st, pts.planes, pts.n, pts.ld, mask,
-                     reinterpret_cast<const unsigned long long*>(key2), scratch, Rt12);
-}
-
-void launch_mask(const Points& pts, const float* Rt12, float tau2, uint8_t* mask, hipStream_t st) {
-  hipLaunchKernelGGL(mask_kernel, dim3((pts.n + 255) / 256), dim3(256), 0, st, pts.planes, pts.n, pts.ld, Rt12,
-                     (const unsigned long long*)nullptr, tau2, mask);
 }
 
 }  // namespace sc

@@ -12,7 +12,7 @@ import numpy as np
 
 
 def global_index(l: np.ndarray | int, block: int, rank: int, world: int):
-    """Global rank index of local hypothesis l (mirror of shard_global_index in csrc/sc_score.hip)."""
+    """Global rank index of local hypothesis l (mirror of shard_global_index in csrc/sc_gramref.hpp)."""
     l = np.asarray(l, dtype=np.int64)
     return ((l // block) * world + rank) * block + (l % block)
 

@@ -30,18 +30,18 @@ def _scene(pkg, name, seed_offset=0):
 _HYP = {}
 
 
-def _hypotheses(O, name, src, tgt, kw):
+def _hypotheses(O, name, src, tgt, kw, rank_mode=0):
     """Stage A -> ranked list -> Kabsch on the CPU, once per scene and session."""
     if name not in _HYP:
         th = _threads(O)
         S, bits, deg = O.compat(src, tgt, kw["sigma"], kw["t_cmp"], kw["min_len"], kw["tau"], threads=th)
-        tri, key, total = O.triangles(S, bits, deg, kw["max_triangles"], 0, threads=th)
+        tri, key, total = O.triangles(S, bits, deg, kw["max_triangles"], rank_mode, threads=th)
         _HYP[name] = dict(Rt=O.kabsch3(src, tgt, tri, threads=th), t_eff=len(tri), total=total, edges=int(deg.sum()) // 2)
     return _HYP[name]
 
 
-def _expected(O, name, src, tgt, kw, rounds, score_mode=0, refine=False):
-    hyp = _hypotheses(O, name, src, tgt, kw)
+def _expected(O, name, src, tgt, kw, rounds, score_mode=0, refine=False, rank_mode=0):
+    hyp = _hypotheses(O, name, src, tgt, kw, rank_mode)
     Rt, n, th = hyp["Rt"], src.shape[0], _threads(O)
     alive = np.ones(n, bool)
     out = []
@@ -168,6 +168,35 @@ def test_rounds_at_half_a_million_hypotheses(pkg, O):
     finally:
         r.close()
     _assert_rounds(got, exp, hyp, "C4")
+
+
+# ---- 3a: the rank count among thousands of equal keys, grid-strided, with every T % 4 -----------------------------------------
+@pytest.mark.parametrize("T", [20001, 20002, 20003])
+def test_rank_count_among_equal_keys(pkg, O, T):
+    """The rank index is "keys that outrank the winner's: above it, or equal at a lower position", counted over sel_key by the
+    winner kernels (16-byte loads, grid-strided, the last T % 4 keys on workgroup 0) and by sc_polish's select.  Degree ranking on
+    two noise-free cliques (48 and 38 correspondences, 10 outliers) leaves 36 distinct keys among the T, so the winner of round 1
+    (rank 17 399) has thousands of equal keys on both sides of it; n = 96 is one workgroup for the mask, T / 4 > 4096 makes the
+    launch five workgroups; T % 4 = 1, 2, 3.  The CPU composition: 25 906 triangles, t_eff = T; frame rank 0, count 48; round 1
+    rank 17 399, count 38; round 2 SC_ENOHYP — for all three T."""
+    import polish_ref
+    from test_gpu_polish import _assert_polish
+    sc = pkg.synth.make_scene_motions(96, [0.5, 0.4], 1.0, 1e-7, 7)
+    kw = dict(sigma=0.05, t_cmp=0.9, tau=0.05, min_len=0.05, max_triangles=T, rank_mode=1)
+    exp, hyp = _expected(O, f"cliques{T}", sc.src, sc.tgt, kw, 3, rank_mode=1)
+    assert hyp["total"] == 25906 and hyp["t_eff"] == T
+    assert [(e["status"], e["best_rank"], e["best_count"]) for e in exp] == [(SC_OK, 0, 48), (SC_OK, 17399, 38), (SC_ENOHYP, 0, 0)]
+    r = pkg.Registrar(0)
+    try:
+        got = _host_rounds(r, sc.src, sc.tgt, pkg.make_params(**kw), 3)
+        _assert_rounds(got, exp, hyp, f"cliques T={T}")
+        # the eight candidates' rank fields go through the same predicate (polish_select_kernel), on a fresh frame
+        assert r.register(sc.src, sc.tgt, params=pkg.make_params(**kw))["status"] == SC_OK
+        polished = r.polish(candidates=8, max_iter=16)
+    finally:
+        r.close()
+    ref = polish_ref.polish(O, sc.src, sc.tgt, hyp["Rt"], kw["tau"], 0, 8, 16, threads=_threads(O))
+    _assert_polish(polished, ref, 8, f"cliques T={T} polish")
 
 
 # ---- 4: the frame enqueued four ways -------------------------------------------------------------------------------
