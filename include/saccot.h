@@ -39,6 +39,7 @@ extern "C" {
                                 SC_STREAM_DEFAULT, sc_hypothesize_begin/end_device, sc_finalize_gathered_device */
 
 #define SC_HAS_POLISH 1  /* this header declares sc_polish* (added within 0.10) */
+#define SC_HAS_BATCH 1   /* this header declares sc_register_batch* (added within 0.10) */
 
 /* status codes */
 #define SC_OK        0
@@ -227,6 +228,59 @@ int sc_register_device(sc_ctx* ctx, const float* d_src, const float* d_tgt, int6
 int sc_register_device_async(sc_ctx* ctx, const float* d_src, const float* d_tgt, int64_t n,
                              const sc_params* params, float* d_Rt, uint8_t* d_mask);
 int sc_wait(sc_ctx* ctx, sc_stats* stats);
+
+/* ---- many small registrations in one launch: sc_register_batch ---------------------------------------------
+ * sc_register is a chain of about 35 dependent launches: well filled by 5000 correspondences, almost pure launch latency for a few
+ * hundred.  Small problems arriving by the thousand — object-pose candidates of a camera frame, fragment pairs with 250 - 500
+ * keypoints, the cluster pairs of a place-recognition back end — go through ONE launch here, a workgroup per problem, every stage
+ * of the path inside it (sc_batch.hip).  No host read-back, no launch sized by the data, nothing shared between problems.
+ *
+ * Layout: the problems are PACKED.  Problem b owns rows [offset[b], offset[b + 1]) of src / tgt — params->layout SC_AOS: total x 3
+ * row-major; SC_SOA: three planes of total, total = offset[n_problems] — and the same range of mask (total bytes).  offset is a HOST
+ * array of n_problems + 1 words in BOTH forms (the caller knows its sizes); the library copies it and keeps no caller pointer.  One
+ * sc_params serves the whole batch.  3 <= n_b = offset[b + 1] - offset[b] <= SC_BATCH_MAX_N.
+ *
+ * Semantics: for every problem b the record's status, Rt, edges, tri_total, tri_kept, best_rank, best_count and the mask range equal
+ * what sc_register(ctx, problem b alone, n_b, the same params plus SC_FLAG_EXACT_TOTAL) returns, bit for bit, in either ranking mode
+ * and all three score modes.
+ *   - SC_ENOHYP (no triangle, or no hypothesis with a score): R = I, t = 0, mask zero, the counts as sc_register reports them.
+ *   - A problem that holds a non-finite coordinate gets status SC_EINVAL, R = I, t = 0, mask zero, every count 0 (n stays n_b).  It is
+ *     found on the device, does not disturb its neighbours and does not fail the call.
+ *   - A problem's record is a function of its own points and the parameters only: not of its position in the batch, of n_problems, of
+ *     the other problems, or of the context's history.
+ *   - The CALL returns SC_EINVAL, decided on the host before anything is enqueued, sc_last_error naming which: a NULL argument;
+ *     n_problems == 0; an n_b < 3 or > SC_BATCH_MAX_N; offsets that decrease, or a total above 2^31; shard_world != 1; any flag other
+ *     than SC_FLAG_NO_DENSE_S, SC_FLAG_NO_PRUNE, SC_FLAG_EXACT_TOTAL (result-neutral: accepted and ignored) — SC_FLAG_REFINE, the timing
+ *     flags, SC_FLAG_EST_BOUND, SC_FLAG_SHARD_AB are refused: the fp64 refit is not part of a batch member's path; the usual sc_params
+ *     checks; a call outstanding on the context.
+ *   - max_triangles may be anything sc_register accepts: nothing is materialised per hypothesis, so SC_ETOOMANY cannot occur.
+ *   - sc_register_batch_device enqueues on the context's stream and returns without waiting, like sc_match_device: d_res and d_mask are
+ *     complete in stream order.  (It may wait for the previous batch call's copy of ITS offsets out of the staging area the two share.)
+ *     sc_register_batch copies in, enqueues, copies out and waits.
+ *   - The call ends the frame a context may hold and leaves none: sc_peel / sc_polish after it return SC_EINVAL.
+ *   - Workspace: the copy of offset, plus the host form's device copies of its arrays; allocated by the first batch call, counted in
+ *     workspace_bytes and held against params->max_workspace (SC_ENOMEM).  A context that never batches allocates and runs nothing new.
+ * Cost: a problem occupies ONE compute unit's workgroup for (triangles of its graph) x (3 .. 10 enumeration passes) + (kept triangles)
+ * x n_b.  The graphs of a few hundred putative correspondences hold 10^3 .. 10^5 triangles; a DENSE 512-point problem (2 x 10^7
+ * triangles) keeps its workgroup busy for tens of milliseconds while the rest of the batch has long finished — such problems belong
+ * to sc_register.  There is no balancing by problem size. */
+#define SC_BATCH_MAX_N 512u
+typedef struct sc_batch_result {   /* 80 bytes */
+  float    Rt[12];      /* R row-major, then t; R = I, t = 0 unless status == SC_OK        */
+  int32_t  status;      /* SC_OK, SC_ENOHYP, or SC_EINVAL (a non-finite coordinate)        */
+  uint32_t n;           /* correspondences of this problem                                 */
+  uint32_t edges;
+  uint32_t tri_kept;    /* min(T, tri_total)                                               */
+  uint64_t tri_total;   /* 3-cliques of the WHOLE graph (as with SC_FLAG_EXACT_TOTAL)      */
+  uint32_t best_rank;
+  uint32_t best_count;
+} sc_batch_result;
+/* every buffer but offset in HBM: d_src / d_tgt total x 3 floats, d_res n_problems records, d_mask total bytes */
+int sc_register_batch_device(sc_ctx* ctx, const float* d_src, const float* d_tgt, const uint32_t* offset, uint32_t n_problems,
+                             const sc_params* params, sc_batch_result* d_res, uint8_t* d_mask);
+/* the same with host arrays; waits */
+int sc_register_batch(sc_ctx* ctx, const float* src, const float* tgt, const uint32_t* offset, uint32_t n_problems,
+                      const sc_params* params, sc_batch_result* res, uint8_t* mask);
 
 /* ---- further rigid motions from a scored frame: sc_peel ---------------------------------------------
  * sc_register answers "which ONE rigid motion explains most correspondences".  The T scored hypotheses stay in the

@@ -37,6 +37,7 @@ SC_HIST_WORDS = 256  # u32 words of the pruning-sample histogram (sc_hypothesize
 
 EXPORTS = ["sc_version", "sc_strerror", "sc_default_params", "sc_create", "sc_destroy", "sc_set_stream",
            "sc_last_error", "sc_set_debug", "sc_debug_last", "sc_register", "sc_register_device", "sc_register_device_async", "sc_wait",
+           "sc_register_batch", "sc_register_batch_device",
            "sc_peel", "sc_peel_device", "sc_register_instances",
            "sc_polish_default_params", "sc_polish_device", "sc_polish",
            "sc_match_default_params", "sc_match_device", "sc_match", "sc_register_features",
@@ -90,6 +91,18 @@ class ScPolishCand(C.Structure):
 
 POLISH_CAND_DTYPE = np.dtype([("Rt", np.float32, 12), ("rank", np.uint32), ("score0", np.uint32), ("score", np.uint32),
                               ("iters", np.uint16), ("reserved", np.uint16)])  # sc_polish_cand as a numpy record
+
+
+class ScBatchResult(C.Structure):
+    """Mirror of `sc_batch_result` (include/saccot.h), 80 bytes: one problem's record of sc_register_batch."""
+    _fields_ = [("Rt", C.c_float * 12), ("status", C.c_int32), ("n", C.c_uint32), ("edges", C.c_uint32), ("tri_kept", C.c_uint32),
+                ("tri_total", C.c_uint64), ("best_rank", C.c_uint32), ("best_count", C.c_uint32)]
+
+
+BATCH_RESULT_DTYPE = np.dtype([("Rt", np.float32, 12), ("status", np.int32), ("n", np.uint32), ("edges", np.uint32),
+                               ("tri_kept", np.uint32), ("tri_total", np.uint64), ("best_rank", np.uint32),
+                               ("best_count", np.uint32)])  # sc_batch_result as a numpy record
+SC_BATCH_MAX_N = 512
 
 
 class ScShardPlan(C.Structure):
@@ -176,6 +189,8 @@ def load_library() -> C.CDLL:
     L.sc_register_device.argtypes = [vp, vp, vp, C.c_int64, pp, vp, vp, sp]
     L.sc_register_device_async.argtypes = [vp, vp, vp, C.c_int64, pp, vp, vp]
     L.sc_wait.argtypes = [vp, sp]
+    L.sc_register_batch.argtypes = [vp, f32p, f32p, u32p, C.c_uint32, pp, vp, u8p]
+    L.sc_register_batch_device.argtypes = [vp, vp, vp, u32p, C.c_uint32, pp, vp, vp]
     L.sc_peel.argtypes = [vp, f32p, f32p, u8p, sp]
     L.sc_peel_device.argtypes = [vp, vp, vp, sp]
     L.sc_register_instances.argtypes = [vp, f32p, f32p, C.c_int64, pp, C.c_uint32, C.c_uint32, f32p, u32p, C.POINTER(C.c_int32),
@@ -350,6 +365,51 @@ class Registrar:
         st = ScStats(C.sizeof(ScStats))
         rc = self._check(self._lib.sc_wait(self._h, C.byref(st)), allow=(SC_ENOHYP, SC_ERETRY, SC_EBOUND))
         return rc, st.as_dict()
+
+    # ---- many small registrations in one launch (include/saccot.h, sc_register_batch) ------------------------------
+    def register_batch_raw(self, src, tgt, offset, params: ScParams):
+        """sc_register_batch on packed arrays: src / tgt (total, 3) — or (3, total) with SC_SOA —, offset (B + 1,) uint32 ->
+        (records (B,) of BATCH_RESULT_DTYPE, mask (total,) uint8).  A problem's status is a field of its record."""
+        src, tgt = _f32c(src), _f32c(tgt)
+        offset = np.ascontiguousarray(offset, dtype=np.uint32)
+        nb = max(len(offset) - 1, 0)
+        total = int(offset[-1]) if len(offset) else 0
+        res = np.zeros(max(nb, 1), BATCH_RESULT_DTYPE); mask = np.zeros(max(total, 1), np.uint8)
+        self._frame_n = 0
+        self._check(self._lib.sc_register_batch(self._h, _p(src, C.c_float), _p(tgt, C.c_float), _p(offset, C.c_uint32), nb,
+                                                C.byref(params), res.ctypes.data_as(C.c_void_p), _p(mask, C.c_uint8)))
+        return res[:nb], mask[:total]
+
+    def register_batch(self, problems, params: ScParams | None = None, **kw):
+        """sc_register_batch: many small problems (3 .. SC_BATCH_MAX_N correspondences each), one launch.  problems: a list of
+        (src (n_b, 3), tgt (n_b, 3)) pairs, or the packed (src, tgt, offset) themselves (in params' layout).  -> a list of
+        dict(status, R, t, mask, stats) with register()'s keys, one per problem; stats holds n, edges, tri_total, tri_kept, best_rank,
+        best_count.  A problem's SC_ENOHYP / SC_EINVAL (a non-finite coordinate) is its status, not an exception."""
+        p = params or make_params(**kw)
+        if isinstance(problems, tuple) and len(problems) == 3 and not isinstance(problems[0], tuple):
+            src, tgt, offset = problems
+        else:
+            sizes = [np.shape(s)[0] for s, _ in problems]
+            offset = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint32)
+            src = np.concatenate([_f32c(s).reshape(-1, 3) for s, _ in problems]) if sizes else np.zeros((0, 3), np.float32)
+            tgt = np.concatenate([_f32c(t).reshape(-1, 3) for _, t in problems]) if sizes else np.zeros((0, 3), np.float32)
+            if p.layout == SC_SOA:
+                src, tgt = np.ascontiguousarray(src.T), np.ascontiguousarray(tgt.T)
+        res, mask = self.register_batch_raw(src, tgt, offset, p)
+        out = []
+        for b, r in enumerate(res):
+            stats = {k: int(r[k]) for k in ("n", "edges", "tri_total", "tri_kept", "best_rank", "best_count")}
+            out.append(dict(status=int(r["status"]), R=r["Rt"][:9].reshape(3, 3).copy(), t=r["Rt"][9:].copy(),
+                            mask=mask[int(offset[b]): int(offset[b + 1])].copy(), stats=stats))
+        return out
+
+    def register_batch_device(self, d_src: int, d_tgt: int, offset, params: ScParams, d_res: int, d_mask: int):
+        """sc_register_batch_device: points, records (80 bytes each) and mask in HBM, offset a HOST array (B + 1,) uint32; enqueues
+        on the context's stream and returns without waiting."""
+        offset = np.ascontiguousarray(offset, dtype=np.uint32)
+        self._frame_n = 0
+        self._check(self._lib.sc_register_batch_device(self._h, d_src, d_tgt, _p(offset, C.c_uint32), max(len(offset) - 1, 0),
+                                                       C.byref(params), d_res, d_mask))
 
     # ---- further rigid motions from the frame the last register* call left (include/saccot.h, sc_peel) ------
     def peel(self):

@@ -1,7 +1,8 @@
 // sc_capi.hip — the core of the C ABI of include/saccot.h: the context's lifetime and its grow-only device workspace, sc_set_debug /
 // sc_debug_last, pass and frame, every run_* stage sequencer, and the register, hypothesize, finalize, shard and wait entries.  The
 // rest of the ABI sits in host-only files of its own, on sc_ctx.hpp (sc_ctx itself and the shared helpers): sc_capi_hooks.hip (the
-// sc_*_host stage hooks), sc_capi_peel.hip (sc_peel*, sc_register_instances), sc_capi_match.hip (sc_match*, sc_register_features).
+// sc_*_host stage hooks), sc_capi_peel.hip (sc_peel*, sc_register_instances), sc_capi_match.hip (sc_match*, sc_register_features), sc_capi_polish.hip (sc_polish*),
+// sc_capi_batch.hip (sc_register_batch*).
 //
 // There is no reference interface to mirror (the reference tree holds a two-line README.md and no code, which is why there is no
 // oracle/_ref); the boundary is SURVEY.md §8(b).  Everything that computes runs on the GPU: these files only validate, allocate,
@@ -856,6 +857,8 @@ void sc_destroy(sc_ctx* c) {
   if (c->pinned) (void)hipHostFree(c->pinned);
   if (c->h_in) (void)hipHostFree(c->h_in);
   if (c->h_out) (void)hipHostFree(c->h_out);
+  if (c->h_batch_off) (void)hipHostFree(c->h_batch_off);
+  if (c->batch_off_ev) (void)hipEventDestroy(c->batch_off_ev);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;
 }

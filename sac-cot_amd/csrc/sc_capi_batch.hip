@@ -1,0 +1,110 @@
+// sc_capi_batch.hip — the C ABI's batched registration (include/saccot.h, sc_register_batch): sc_register_batch_device and
+// sc_register_batch.  Host-only, on the context and the helpers of sc_ctx.hpp; the kernel is sc_batch.hip's.
+//
+// offsets -> pinned staging -> device copy (enqueued) -> ONE launch, a workgroup per problem.  Nothing is read back: a problem's
+// status is a field of its record.  Everything that can refuse the call is decided on the host before anything is enqueued.
+#include "sc_ctx.hpp"
+
+using namespace sc;
+
+namespace {
+
+constexpr uint32_t BATCH_FLAGS_IGNORED = SC_FLAG_NO_DENSE_S | SC_FLAG_NO_PRUNE | SC_FLAG_EXACT_TOTAL;  // result-neutral
+
+// the caller's offsets: sizes 3 .. SC_BATCH_MAX_N, nothing decreasing, a total of 2^31 at most.  nullptr: they are fine
+const char* batch_offsets_error(const uint32_t* offset, uint32_t n_problems) {
+  if (n_problems == 0) return "sc_register_batch: n_problems == 0";
+  for (uint32_t b = 0; b < n_problems; b++) {
+    if (offset[b + 1] < offset[b]) return "sc_register_batch: offsets decrease";
+    const uint32_t nb = offset[b + 1] - offset[b];
+    if (nb < 3 || nb > SC_BATCH_MAX_N) return "sc_register_batch: a problem has fewer than 3 or more than SC_BATCH_MAX_N correspondences";
+  }
+  if (offset[n_problems] > (1u << 31)) return "sc_register_batch: more than 2^31 correspondences in all";
+  return nullptr;
+}
+
+int batch_check(sc_ctx* c, const uint32_t* offset, uint32_t n_problems, const sc_params* p) {
+  SC_TRY(entry_checks(c, nullptr, ENDS_FRAME | NOT_BUSY));
+  if (check_params(p) != SC_OK) { c->last_error = "sc_register_batch: bad sc_params (size, a range, or a mode)"; return SC_EINVAL; }
+  if (p->shard_world != 1) { c->last_error = "sc_register_batch: shard_world must be 1"; return SC_EINVAL; }
+  if (p->flags & ~BATCH_FLAGS_IGNORED) {
+    c->last_error = "sc_register_batch: only SC_FLAG_NO_DENSE_S, SC_FLAG_NO_PRUNE and SC_FLAG_EXACT_TOTAL are accepted (no refit, no timing, no estimated bound in a batch)";
+    return SC_EINVAL;
+  }
+  if (const char* what = batch_offsets_error(offset, n_problems)) { c->last_error = what; return SC_EINVAL; }
+  return SC_OK;
+}
+
+// offset -> the pinned staging area -> batch_off (enqueued).  The area is the context's: the copy out of the call before must be done
+// before it is overwritten (an event behind that copy — not behind that call's kernel).
+int batch_offsets_to_device(sc_ctx* c, const uint32_t* offset, uint32_t n_problems) {
+  const size_t bytes = ((size_t)n_problems + 1) * 4;
+  ENSURE(c, c->batch_off, bytes);
+  if (!c->batch_off_ev) HIPCHK(c, hipEventCreateWithFlags(&c->batch_off_ev, hipEventDisableTiming));
+  else HIPCHK(c, hipEventSynchronize(c->batch_off_ev));
+  if (c->h_batch_off_cap < bytes) {
+    if (c->h_batch_off) { (void)hipHostFree(c->h_batch_off); c->h_batch_off = nullptr; c->h_batch_off_cap = 0; }
+    const size_t sz = bytes + bytes / 4 + 4096;
+    if (hipHostMalloc(&c->h_batch_off, sz, hipHostMallocDefault) != hipSuccess) {
+      (void)hipGetLastError(); c->h_batch_off = nullptr; c->last_error = "hipHostMalloc failed"; return SC_ENOMEM;
+    }
+    c->h_batch_off_cap = sz;
+  }
+  memcpy(c->h_batch_off, offset, bytes);
+  HIPCHK(c, hipMemcpyAsync(c->batch_off.p, c->h_batch_off, bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipEventRecord(c->batch_off_ev, c->stream));
+  return SC_OK;
+}
+
+int batch_enqueue(sc_ctx* c, const float* d_src, const float* d_tgt, const uint32_t* offset, uint32_t n_problems, const sc_params* p,
+                  sc_batch_result* d_res, uint8_t* d_mask) {
+  SC_TRY(batch_offsets_to_device(c, offset, n_problems));
+  BatchJob job{};
+  job.src = d_src; job.tgt = d_tgt; job.offset = c->batch_off.as<uint32_t>();
+  job.n_problems = n_problems; job.total = offset[n_problems];
+  job.soa = p->layout == SC_SOA; job.T = p->max_triangles; job.rank_mode = p->rank_mode; job.score_mode = p->score_mode;
+  job.dv = derive(p);
+  job.res = reinterpret_cast<BatchRecord*>(d_res); job.mask = d_mask;
+  launch_batch_register(job, c->stream);
+  HIPCHK(c, hipGetLastError());
+  return SC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sc_register_batch_device(sc_ctx* c, const float* d_src, const float* d_tgt, const uint32_t* offset, uint32_t n_problems,
+                             const sc_params* p, sc_batch_result* d_res, uint8_t* d_mask) {
+  if (!c) return SC_EINVAL;
+  if (!d_src || !d_tgt || !offset || !p || !d_res || !d_mask) { c->last_error = "sc_register_batch_device: a NULL argument"; return SC_EINVAL; }
+  SC_TRY(batch_check(c, offset, n_problems, p));
+  HIPCHK(c, hipSetDevice(c->device));
+  c->cap_bytes = workspace_cap(p);
+  return batch_enqueue(c, d_src, d_tgt, offset, n_problems, p, d_res, d_mask);
+}
+
+int sc_register_batch(sc_ctx* c, const float* src, const float* tgt, const uint32_t* offset, uint32_t n_problems, const sc_params* p,
+                      sc_batch_result* res, uint8_t* mask) {
+  if (!c) return SC_EINVAL;
+  if (!src || !tgt || !offset || !p || !res || !mask) { c->last_error = "sc_register_batch: a NULL argument"; return SC_EINVAL; }
+  SC_TRY(batch_check(c, offset, n_problems, p));
+  HIPCHK(c, hipSetDevice(c->device));
+  c->cap_bytes = workspace_cap(p);
+  const size_t total = offset[n_problems], pts = total * 12, recs = (size_t)n_problems * sizeof(sc_batch_result);
+  ENSURE(c, c->batch_src, pts);
+  ENSURE(c, c->batch_tgt, pts);
+  ENSURE(c, c->batch_res, recs);
+  ENSURE(c, c->batch_mask, total);
+  hipStream_t st = c->stream;
+  HIPCHK(c, hipMemcpyAsync(c->batch_src.p, src, pts, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(c->batch_tgt.p, tgt, pts, hipMemcpyHostToDevice, st));
+  SC_TRY(batch_enqueue(c, c->batch_src.as<float>(), c->batch_tgt.as<float>(), offset, n_problems, p,
+                       c->batch_res.as<sc_batch_result>(), c->batch_mask.as<uint8_t>()));
+  HIPCHK(c, hipMemcpyAsync(res, c->batch_res.p, recs, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(mask, c->batch_mask.p, total, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  return SC_OK;
+}
+
+}  // extern "C"

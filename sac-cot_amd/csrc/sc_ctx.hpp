@@ -104,7 +104,10 @@ struct Workspace {
       polish_cand, polish_tmp,
       // sc_match / sc_register_features: allocated by the first match, never by a frame.  part: the slices' partial lists; words: the
       // "clean" word, the host entries' count pair, then the column minima; the rest: device copies of the host entries' arrays
-      match_part, match_words, match_fsrc, match_ftgt, match_psrc, match_ptgt, match_corr, match_d2, match_gsrc, match_gtgt;
+      match_part, match_words, match_fsrc, match_ftgt, match_psrc, match_ptgt, match_corr, match_d2, match_gsrc, match_gtgt,
+      // sc_register_batch: allocated by the first batch call, never by a frame.  off: the copy of the caller's offsets; the rest:
+      // device copies of the host entry's arrays
+      batch_off, batch_src, batch_tgt, batch_res, batch_mask;
 };
 constexpr size_t N_WORKSPACE_BUFS = sizeof(Workspace) / sizeof(Buf);
 static_assert(std::is_standard_layout<Workspace>::value && alignof(Workspace) == alignof(Buf) && sizeof(Workspace) == N_WORKSPACE_BUFS * sizeof(Buf),
@@ -134,6 +137,10 @@ struct sc_ctx : sc::Workspace {  // (the workspace buffers are direct members to
   // correspondences straight from host memory and the finalize kernel writes (R, t, mask) straight into it: no copies
   void* h_in = nullptr; size_t h_in_cap = 0;
   void* h_out = nullptr; size_t h_out_cap = 0;
+  // sc_register_batch: the pinned staging area the caller's offsets pass through on their way to batch_off, and the event behind the
+  // copy out of it (the next batch call waits for it before it overwrites the area)
+  void* h_batch_off = nullptr; size_t h_batch_off_cap = 0;
+  hipEvent_t batch_off_ev = nullptr;
   uint64_t ev_capacity = 1ull << 21;  // event records (32 B each); doubled after an overflow
   sc::Tuning tn;  // defaults unless sc_set_debug() changed them; the library reads no environment variable
   // decoupled look-back launches (single-pass scan, fused compaction): their state area and its epoch

@@ -682,4 +682,30 @@ uint32_t match_finish_tiles(uint32_t ns);
 void launch_match_finish(const MatchJob& job, const MatchPlan& plan, const uint64_t* part, const uint64_t* colmin, const uint32_t* clean,
                          int32_t* corr, float* d2, uint32_t* count, const MatchGather& g, LbArgs lb, uint64_t* host_word, hipStream_t st);
 
+// ---- many small registrations in one launch (sc_register_batch; sc_batch.hip) ------------------------------
+// One problem's result: sc_batch_result of include/saccot.h, field for field (sc_batch.hip asserts the size).
+struct BatchRecord {
+  float Rt[12];
+  int32_t status;
+  uint32_t n, edges, tri_kept;
+  uint64_t tri_total;
+  uint32_t best_rank, best_count;
+};
+constexpr int BATCH_MAX_N = 512;
+// Problem b owns rows [offset[b], offset[b + 1]) of src / tgt (n x 3 row-major, or with soa three planes of `total`) and of mask;
+// 3 <= rows <= BATCH_MAX_N, checked by the caller.  Everything in device memory.
+struct BatchJob {
+  const float* src; const float* tgt;
+  const uint32_t* offset;
+  uint32_t n_problems, total;
+  int soa;
+  uint32_t T;
+  int rank_mode, score_mode;
+  Derived dv;
+  BatchRecord* res;
+  uint8_t* mask;
+};
+// One workgroup per problem; every record and mask range is written (complete in stream order).
+void launch_batch_register(const BatchJob& job, hipStream_t st);
+
 }  // namespace sc
