@@ -40,6 +40,7 @@ extern "C" {
 
 #define SC_HAS_POLISH 1  /* this header declares sc_polish* (added within 0.10) */
 #define SC_HAS_BATCH 1   /* this header declares sc_register_batch* (added within 0.10) */
+#define SC_HAS_MATCH_BATCH 1  /* this header declares sc_match_batch* and sc_register_batch_features* (added within 0.10) */
 
 /* status codes */
 #define SC_OK        0
@@ -431,6 +432,65 @@ int sc_match(sc_ctx* ctx, const float* fsrc, int64_t ns, const float* ftgt, int6
 int sc_register_features(sc_ctx* ctx, const float* src_pts, const float* fsrc, int64_t ns, const float* tgt_pts,
                          const float* ftgt, int64_t nt, const sc_match_params* mp, const sc_params* params, float R[9],
                          float t[3], int32_t* corr, float* d2, uint32_t* n, uint8_t* mask, sc_stats* stats);
+
+/* ---- descriptor matching for a whole batch of small problems: sc_match_batch -----------------------------
+ * What stands in front of sc_register_batch: its callers (pose candidates, fragment pairs of a few hundred keypoints, cluster pairs)
+ * start from two sets of keypoints with descriptors PER PAIR.  Through sc_match_device that is three stream operations per pair and,
+ * for a data-dependent count, a host read per pair before the packed batch can be laid out.  Here the whole batch is matched by two
+ * launches, and sc_register_batch_features* runs sc_register_batch's kernel behind them without a word reaching the host.
+ *
+ * Layout: the problems are PACKED, as in sc_register_batch.  Problem b owns descriptor rows [src_off[b], src_off[b + 1]) of fsrc
+ * (total_s x dim, row-major) and [tgt_off[b], tgt_off[b + 1]) of ftgt (total_t x dim); the same row ranges index src_pts / tgt_pts
+ * (params->layout: SC_AOS total x 3; SC_SOA three planes of total_s, respectively total_t).  Both offset arrays are HOST arrays of
+ * n_problems + 1 words in every form; the library copies them and keeps no caller pointer.  One sc_match_params and one sc_params
+ * serve the whole batch.  1 <= ns_b, nt_b <= SC_MATCH_BATCH_MAX_N.
+ * Outputs live in SLOTS, because the counts are data-dependent and nothing may wait for them: problem b's slot starts at entry
+ * slot[b] = src_off[b] * knn and holds ns_b * knn entries of corr (pairs of int32), d2 and mask.  corr holds indices LOCAL to the
+ * problem: 0 <= i < ns_b, 0 <= j < nt_b.  count: 2 x n_problems words; count[2b] = n_b, count[2b + 1] = 1 if the problem read a
+ * non-finite descriptor (then n_b = 0).  Slot entries past n_b are unspecified.
+ *
+ * Semantics of the match: slot b and its count pair hold (corr, d2, n, flag) of sc_match on problem b alone with the same
+ * sc_match_params, bit for bit — the canonical distance, the u64 key order, knn 1 .. 4 (fewer where nt_b < knn), SC_MATCH_MUTUAL
+ * and ratio with knn == 1, a problem with nt_b == 1 kept under the ratio test, a sum that overflows to +inf legal.  A slot is a
+ * function of its own descriptors and the parameters only: not of the problem's position in the batch, of n_problems, of its
+ * neighbours, or of the context's history.  A non-finite descriptor is found on the device, flags only its own problem and does not
+ * fail the call.
+ * Semantics of sc_register_batch_features*: the match, then for every b
+ *   - flag set: status SC_EINVAL, R = I, t = 0, n = 0, every count 0;
+ *   - n_b < 3: status SC_ENOHYP, R = I, t = 0, n = n_b, every count 0, mask bytes [slot[b], slot[b] + n_b) zero;
+ *   - otherwise the record and mask bytes [slot[b], slot[b] + n_b) are sc_register_batch's on the gathered correspondences
+ *     (src_pts[src_off[b] + i_m], tgt_pts[tgt_off[b] + j_m]), m < n_b — hence sc_register's on them alone with SC_FLAG_EXACT_TOTAL; a
+ *     non-finite point among the gathered ones: SC_EINVAL with n = n_b, as there.  Mask byte slot[b] + m belongs to correspondence m.
+ * Errors: the CALL returns SC_EINVAL, decided on the host before anything is enqueued, sc_last_error naming which: a NULL argument;
+ * n_problems == 0; an ns_b or nt_b of 0 or above SC_MATCH_BATCH_MAX_N; offsets that decrease; total_s * knn > 2^31; any rule of
+ * sc_match_params (see sc_match); a call outstanding on the context.  The features entries also refuse ns_b * knn > SC_BATCH_MAX_N
+ * and everything sc_register_batch refuses of sc_params (shard_world != 1, SC_FLAG_REFINE, the timing flags, SC_FLAG_EST_BOUND,
+ * SC_FLAG_SHARD_AB).
+ * All four entries end the frame a context may hold and leave none: sc_peel / sc_polish after them return SC_EINVAL.  The device
+ * forms enqueue on the context's stream and return without waiting; no word of the GPU's reaches the host, and the number of stream
+ * operations (one copy of the offsets and maps, one memset, two launches, sc_register_batch's one) depends neither on n_problems nor
+ * on any size.  (Like sc_register_batch_device a device form may wait for the previous batch call's copy out of the offset staging
+ * area they share: an event behind that copy, not behind its kernel.)
+ * Workspace: the copies of the offsets, slot starts and tile map, the rows' lists between the two launches, the column minima when
+ * mutual, the gathered points, and the host forms' device copies; allocated by the first such call, counted in workspace_bytes and
+ * held against the cap (SC_ENOMEM).  A context that never calls these entries allocates and runs nothing new. */
+#define SC_MATCH_BATCH_MAX_N 4096u
+/* every buffer but the offsets in HBM: d_corr total_s * knn x 2 int32, d_d2 total_s * knn floats, d_count 2 * n_problems u32 */
+int sc_match_batch_device(sc_ctx* ctx, const float* d_fsrc, const uint32_t* src_off, const float* d_ftgt, const uint32_t* tgt_off,
+                          uint32_t n_problems, const sc_match_params* mp, int32_t* d_corr, float* d_d2, uint32_t* d_count);
+/* the same with host arrays; waits */
+int sc_match_batch(sc_ctx* ctx, const float* fsrc, const uint32_t* src_off, const float* ftgt, const uint32_t* tgt_off,
+                   uint32_t n_problems, const sc_match_params* mp, int32_t* corr, float* d2, uint32_t* count);
+/* match + registration; d_res: n_problems records, d_mask: total_s * knn bytes, the rest as above */
+int sc_register_batch_features_device(sc_ctx* ctx, const float* d_src_pts, const float* d_fsrc, const uint32_t* src_off,
+                                      const float* d_tgt_pts, const float* d_ftgt, const uint32_t* tgt_off, uint32_t n_problems,
+                                      const sc_match_params* mp, const sc_params* params, sc_batch_result* d_res, int32_t* d_corr,
+                                      float* d_d2, uint32_t* d_count, uint8_t* d_mask);
+/* the same with host arrays; waits */
+int sc_register_batch_features(sc_ctx* ctx, const float* src_pts, const float* fsrc, const uint32_t* src_off, const float* tgt_pts,
+                               const float* ftgt, const uint32_t* tgt_off, uint32_t n_problems, const sc_match_params* mp,
+                               const sc_params* params, sc_batch_result* res, int32_t* corr, float* d2, uint32_t* count,
+                               uint8_t* mask);
 
 /* ---- two-phase form for one-process-per-GPU sharding --------------------------------
  * Phase 1: A and B replicated, C1+C2 on this rank's blocks of the top-T list; writes this rank's winner key

@@ -41,6 +41,7 @@ EXPORTS = ["sc_version", "sc_strerror", "sc_default_params", "sc_create", "sc_de
            "sc_peel", "sc_peel_device", "sc_register_instances",
            "sc_polish_default_params", "sc_polish_device", "sc_polish",
            "sc_match_default_params", "sc_match_device", "sc_match", "sc_register_features",
+           "sc_match_batch", "sc_match_batch_device", "sc_register_batch_features", "sc_register_batch_features_device",
            "sc_hypothesize_device", "sc_finalize_device",
            "sc_hypothesize_begin_device", "sc_hypothesize_end_device", "sc_finalize_gathered_device", "sc_finalize_gathered_device_async",
            "sc_shard_plan_query", "sc_shard_compat_device", "sc_shard_edges_device", "sc_shard_select_device",
@@ -103,6 +104,7 @@ BATCH_RESULT_DTYPE = np.dtype([("Rt", np.float32, 12), ("status", np.int32), ("n
                                ("tri_kept", np.uint32), ("tri_total", np.uint64), ("best_rank", np.uint32),
                                ("best_count", np.uint32)])  # sc_batch_result as a numpy record
 SC_BATCH_MAX_N = 512
+SC_MATCH_BATCH_MAX_N = 4096  # rows a side of one problem of sc_match_batch
 
 
 class ScShardPlan(C.Structure):
@@ -204,6 +206,10 @@ def load_library() -> C.CDLL:
     L.sc_match_device.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, mp, vp, vp, vp]
     L.sc_match.argtypes = [vp, f32p, C.c_int64, f32p, C.c_int64, mp, i32p, f32p, u32p]
     L.sc_register_features.argtypes = [vp, f32p, f32p, C.c_int64, f32p, f32p, C.c_int64, mp, pp, f32p, f32p, i32p, f32p, u32p, u8p, sp]
+    L.sc_match_batch_device.argtypes = [vp, vp, u32p, vp, u32p, C.c_uint32, mp, vp, vp, vp]
+    L.sc_match_batch.argtypes = [vp, f32p, u32p, f32p, u32p, C.c_uint32, mp, i32p, f32p, u32p]
+    L.sc_register_batch_features_device.argtypes = [vp, vp, vp, u32p, vp, vp, u32p, C.c_uint32, mp, pp, vp, vp, vp, vp, vp]
+    L.sc_register_batch_features.argtypes = [vp, f32p, f32p, u32p, f32p, f32p, u32p, C.c_uint32, mp, pp, vp, i32p, f32p, u32p, u8p]
     L.sc_hypothesize_device.argtypes = [vp, vp, vp, C.c_int64, pp, vp, sp]
     L.sc_finalize_device.argtypes = [vp, vp, vp, vp, sp]
     L.sc_hypothesize_begin_device.argtypes = [vp, vp, vp, C.c_int64, pp, vp, sp]
@@ -512,6 +518,104 @@ class Registrar:
         self._frame_n = k
         return dict(status=rc, R=R.reshape(3, 3), t=t, n=k, corr=corr[:k].copy(), d2=d2[:k].copy(), mask=mask[:k].copy(),
                     stats=st.as_dict())
+
+    # ---- descriptor matching for a batch of small problems (include/saccot.h, sc_match_batch) -------------------
+    @staticmethod
+    def _offsets(sizes):
+        return np.concatenate([[0], np.cumsum(sizes, dtype=np.int64)]).astype(np.uint32)
+
+    def match_batch_raw(self, fsrc, src_off, ftgt, tgt_off, mparams: ScMatchParams):
+        """sc_match_batch on packed arrays: fsrc (total_s, D), ftgt (total_t, D), both offset arrays (B + 1,) uint32 ->
+        (corr (total_s * knn, 2) int32, d2 (total_s * knn,) float32, count (B, 2) uint32).  Problem b's slot starts at entry
+        src_off[b] * knn; count[b] = (n_b, 1 if the problem read a non-finite descriptor)."""
+        fsrc, ftgt = _f32c(fsrc), _f32c(ftgt)
+        src_off, tgt_off = np.ascontiguousarray(src_off, dtype=np.uint32), np.ascontiguousarray(tgt_off, dtype=np.uint32)
+        nb = max(len(src_off) - 1, 0)
+        slots = (int(src_off[-1]) if len(src_off) else 0) * max(int(mparams.knn), 1)
+        corr = np.zeros((max(slots, 1), 2), np.int32); d2 = np.zeros(max(slots, 1), np.float32); count = np.zeros((max(nb, 1), 2), np.uint32)
+        self._frame_n = 0
+        self._check(self._lib.sc_match_batch(self._h, _p(fsrc, C.c_float), _p(src_off, C.c_uint32), _p(ftgt, C.c_float),
+                                             _p(tgt_off, C.c_uint32), nb, C.byref(mparams), _p(corr, C.c_int32), _p(d2, C.c_float),
+                                             _p(count, C.c_uint32)))
+        return corr[:slots], d2[:slots], count[:nb]
+
+    def match_batch(self, problems, mparams: ScMatchParams | None = None, **kw):
+        """sc_match_batch: problems, a list of (fsrc (ns_b, D), ftgt (nt_b, D)) with one D and 1 .. SC_MATCH_BATCH_MAX_N rows a side ->
+        a list of dict(n, corr (n, 2) int32 local to the problem, d2 (n,), nonfinite) — match() of every problem alone, in two
+        launches for the whole batch.  kw: knn, mutual, ratio (make_match_params).  A non-finite descriptor flags its own problem
+        (nonfinite True, n 0), not the call."""
+        fs = [_f32c(a) for a, _ in problems]; ft = [_f32c(b) for _, b in problems]
+        if not fs or any(a.ndim != 2 or b.ndim != 2 or a.shape[1] != fs[0].shape[1] or b.shape[1] != fs[0].shape[1] for a, b in zip(fs, ft)):
+            raise ValueError("match_batch: at least one problem, fsrc (ns, D) and ftgt (nt, D) with one D for all")
+        m = mparams or make_match_params(fs[0].shape[1], **kw)
+        so, to = self._offsets([len(a) for a in fs]), self._offsets([len(b) for b in ft])
+        corr, d2, count = self.match_batch_raw(np.concatenate(fs), so, np.concatenate(ft), to, m)
+        out = []
+        for b in range(len(fs)):
+            lo, k = int(so[b]) * int(m.knn), int(count[b, 0])
+            out.append(dict(n=k, corr=corr[lo: lo + k].copy(), d2=d2[lo: lo + k].copy(), nonfinite=bool(count[b, 1])))
+        return out
+
+    def match_batch_device(self, d_fsrc: int, src_off, d_ftgt: int, tgt_off, mparams: ScMatchParams, d_corr: int, d_d2: int, d_count: int):
+        """sc_match_batch_device: descriptors and outputs in HBM (d_corr total_s * knn x 2 int32, d_d2 total_s * knn float32, d_count
+        2 x B uint32), the offsets HOST arrays (B + 1,) uint32; enqueues on the context's stream and returns without waiting."""
+        src_off, tgt_off = np.ascontiguousarray(src_off, dtype=np.uint32), np.ascontiguousarray(tgt_off, dtype=np.uint32)
+        self._frame_n = 0
+        self._check(self._lib.sc_match_batch_device(self._h, d_fsrc, _p(src_off, C.c_uint32), d_ftgt, _p(tgt_off, C.c_uint32),
+                                                    max(len(src_off) - 1, 0), C.byref(mparams), d_corr, d_d2, d_count))
+
+    def register_batch_features_raw(self, src_pts, fsrc, src_off, tgt_pts, ftgt, tgt_off, mparams: ScMatchParams, params: ScParams):
+        """sc_register_batch_features on packed arrays (points in params' layout) -> (records (B,), corr, d2, count (B, 2), mask
+        (total_s * knn,)), the last four slot-positioned as in match_batch_raw."""
+        src_pts, fsrc, tgt_pts, ftgt = _f32c(src_pts), _f32c(fsrc), _f32c(tgt_pts), _f32c(ftgt)
+        src_off, tgt_off = np.ascontiguousarray(src_off, dtype=np.uint32), np.ascontiguousarray(tgt_off, dtype=np.uint32)
+        nb = max(len(src_off) - 1, 0)
+        slots = (int(src_off[-1]) if len(src_off) else 0) * max(int(mparams.knn), 1)
+        res = np.zeros(max(nb, 1), BATCH_RESULT_DTYPE); mask = np.zeros(max(slots, 1), np.uint8)
+        corr = np.zeros((max(slots, 1), 2), np.int32); d2 = np.zeros(max(slots, 1), np.float32); count = np.zeros((max(nb, 1), 2), np.uint32)
+        self._frame_n = 0
+        self._check(self._lib.sc_register_batch_features(self._h, _p(src_pts, C.c_float), _p(fsrc, C.c_float), _p(src_off, C.c_uint32),
+                                                         _p(tgt_pts, C.c_float), _p(ftgt, C.c_float), _p(tgt_off, C.c_uint32), nb,
+                                                         C.byref(mparams), C.byref(params), res.ctypes.data_as(C.c_void_p),
+                                                         _p(corr, C.c_int32), _p(d2, C.c_float), _p(count, C.c_uint32), _p(mask, C.c_uint8)))
+        return res[:nb], corr[:slots], d2[:slots], count[:nb], mask[:slots]
+
+    def register_batch_features(self, problems, mparams: ScMatchParams | None = None, params: ScParams | None = None, knn: int = 1,
+                                mutual: bool = False, ratio: float = 0.0, **kw):
+        """sc_register_batch_features: problems, a list of (src_pts (ns_b, 3), fsrc (ns_b, D), tgt_pts (nt_b, 3), ftgt (nt_b, D)) -> one
+        dict per problem shaped like register_batch's (status, R, t, mask, stats) plus corr (n, 2), d2 (n,) and n: the match of
+        every problem, then sc_register_batch's kernel on the matched points, and nothing crosses the host in between.  Fewer than 3
+        matches: SC_ENOHYP; a non-finite descriptor or matched point: SC_EINVAL — a problem's status, not an exception."""
+        p = params or make_params(**kw)
+        ps = [_f32c(a).reshape(-1, 3) for a, _, _, _ in problems]; fs = [_f32c(a) for _, a, _, _ in problems]
+        pt = [_f32c(a).reshape(-1, 3) for _, _, a, _ in problems]; ft = [_f32c(a) for _, _, _, a in problems]
+        if not fs or any(len(a) != len(b) for a, b in zip(ps, fs)) or any(len(a) != len(b) for a, b in zip(pt, ft)) or \
+                any(a.ndim != 2 or a.shape[1] != fs[0].shape[1] for a in fs + ft):
+            raise ValueError("register_batch_features: at least one problem, one descriptor row per point, one D for all")
+        m = mparams or make_match_params(fs[0].shape[1], knn, mutual, ratio)
+        so, to = self._offsets([len(a) for a in fs]), self._offsets([len(a) for a in ft])
+        src, tgt = np.concatenate(ps), np.concatenate(pt)
+        if p.layout == SC_SOA:
+            src, tgt = np.ascontiguousarray(src.T), np.ascontiguousarray(tgt.T)
+        res, corr, d2, count, mask = self.register_batch_features_raw(src, np.concatenate(fs), so, tgt, np.concatenate(ft), to, m, p)
+        out = []
+        for b, r in enumerate(res):
+            lo, k = int(so[b]) * int(m.knn), int(count[b, 0])
+            stats = {f: int(r[f]) for f in ("n", "edges", "tri_total", "tri_kept", "best_rank", "best_count")}
+            out.append(dict(status=int(r["status"]), R=r["Rt"][:9].reshape(3, 3).copy(), t=r["Rt"][9:].copy(),
+                            mask=mask[lo: lo + k].copy(), stats=stats, n=k, corr=corr[lo: lo + k].copy(), d2=d2[lo: lo + k].copy()))
+        return out
+
+    def register_batch_features_device(self, d_src_pts: int, d_fsrc: int, src_off, d_tgt_pts: int, d_ftgt: int, tgt_off,
+                                       mparams: ScMatchParams, params: ScParams, d_res: int, d_corr: int, d_d2: int, d_count: int,
+                                       d_mask: int):
+        """sc_register_batch_features_device: everything but the offsets in HBM (d_res B records of 80 bytes, d_mask total_s * knn
+        bytes, the rest as match_batch_device); enqueues on the context's stream and returns without waiting."""
+        src_off, tgt_off = np.ascontiguousarray(src_off, dtype=np.uint32), np.ascontiguousarray(tgt_off, dtype=np.uint32)
+        self._frame_n = 0
+        self._check(self._lib.sc_register_batch_features_device(self._h, d_src_pts, d_fsrc, _p(src_off, C.c_uint32), d_tgt_pts, d_ftgt,
+                                                                _p(tgt_off, C.c_uint32), max(len(src_off) - 1, 0), C.byref(mparams),
+                                                                C.byref(params), d_res, d_corr, d_d2, d_count, d_mask))
 
     def hypothesize_device(self, d_src: int, d_tgt: int, n: int, params: ScParams, d_key: int):
         st = ScStats(C.sizeof(ScStats))

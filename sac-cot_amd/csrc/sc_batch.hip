@@ -162,14 +162,35 @@ __device__ __forceinline__ void mask_zero(uint8_t* mask, int n) {
   for (int m = threadIdx.x; m < n; m += BT) mask[m] = 0;
 }
 
-__global__ __launch_bounds__(BT) void batch_register_kernel(const BatchJob job) {
+// The kernel's argument is BatchJob (sc_register_batch) or BatchSlotJob (sc_register_batch_features: the problems sit in slots and
+// `count` says how much of each is filled, sc_kernels.hpp).  The plain instantiation is the kernel of sc_register_batch with the
+// kernel argument it always had: COUNTED is a constant of the instantiation, and nothing of the slot form is compiled into it.
+__device__ __forceinline__ const BatchJob& job_of(const BatchJob& a) { return a; }
+__device__ __forceinline__ const BatchJob& job_of(const BatchSlotJob& a) { return a.job; }
+__device__ __forceinline__ const uint32_t* count_of(const BatchJob&) { return nullptr; }
+__device__ __forceinline__ const uint32_t* count_of(const BatchSlotJob& a) { return a.count; }
+
+template <class Arg>
+__global__ __launch_bounds__(BT) void batch_register_kernel(const Arg arg) {
+  constexpr bool COUNTED = sizeof(Arg) != sizeof(BatchJob);
+  const BatchJob& job = job_of(arg);
+  const uint32_t* const count = count_of(arg);
   __shared__ BatchLds L;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const uint32_t off = job.offset[blockIdx.x];
-  const int n = (int)(job.offset[blockIdx.x + 1] - off);  // 3 .. BN: the host checked
+  const int n = COUNTED ? (int)count[2 * blockIdx.x] : (int)(job.offset[blockIdx.x + 1] - off);  // 3 .. BN: the host checked
   const int W = (n + 63) >> 6;
   const Derived dv = job.dv;
   uint8_t* const mask = job.mask + off;
+  if (COUNTED) {  // what the host refuses for the plain form, it cannot know here: the match decided it on the device
+    const bool flagged = count[2 * blockIdx.x + 1] != 0u;
+    if (flagged || n < 3 || n > BN) {  // (n > BN cannot happen: a slot's capacity is at most BN)
+      if (!flagged && n < 3) mask_zero(mask, n);
+      if (tid == 0) record_fill(L, nullptr, (flagged || n > BN) ? SC_EINVAL : SC_ENOHYP, flagged ? 0u : (uint32_t)n, 0u, 0u, 0u, 0u, 0u);
+      record_store(L, job.res);
+      return;
+    }
+  }
 
   // ---- staging: either layout -> planes; a non-finite coordinate ends this problem
   if (tid == 0) L.bad = 0u;
@@ -406,7 +427,11 @@ __global__ __launch_bounds__(BT) void batch_register_kernel(const BatchJob job) 
 }  // namespace
 
 void launch_batch_register(const BatchJob& job, hipStream_t st) {
-  hipLaunchKernelGGL(batch_register_kernel, dim3(job.n_problems), dim3(BT), 0, st, job);
+  hipLaunchKernelGGL(batch_register_kernel<BatchJob>, dim3(job.n_problems), dim3(BT), 0, st, job);
+}
+
+void launch_batch_register_slots(const BatchSlotJob& job, hipStream_t st) {
+  hipLaunchKernelGGL(batch_register_kernel<BatchSlotJob>, dim3(job.job.n_problems), dim3(BT), 0, st, job);
 }
 
 }  // namespace sc

@@ -25,35 +25,18 @@ const char* batch_offsets_error(const uint32_t* offset, uint32_t n_problems) {
 
 int batch_check(sc_ctx* c, const uint32_t* offset, uint32_t n_problems, const sc_params* p) {
   SC_TRY(entry_checks(c, nullptr, ENDS_FRAME | NOT_BUSY));
-  if (check_params(p) != SC_OK) { c->last_error = "sc_register_batch: bad sc_params (size, a range, or a mode)"; return SC_EINVAL; }
-  if (p->shard_world != 1) { c->last_error = "sc_register_batch: shard_world must be 1"; return SC_EINVAL; }
-  if (p->flags & ~BATCH_FLAGS_IGNORED) {
-    c->last_error = "sc_register_batch: only SC_FLAG_NO_DENSE_S, SC_FLAG_NO_PRUNE and SC_FLAG_EXACT_TOTAL are accepted (no refit, no timing, no estimated bound in a batch)";
-    return SC_EINVAL;
-  }
+  SC_TRY(batch_params_check(c, p, "sc_register_batch"));
   if (const char* what = batch_offsets_error(offset, n_problems)) { c->last_error = what; return SC_EINVAL; }
   return SC_OK;
 }
 
-// offset -> the pinned staging area -> batch_off (enqueued).  The area is the context's: the copy out of the call before must be done
-// before it is overwritten (an event behind that copy — not behind that call's kernel).
+// offset -> the pinned staging area -> batch_off (enqueued)
 int batch_offsets_to_device(sc_ctx* c, const uint32_t* offset, uint32_t n_problems) {
   const size_t bytes = ((size_t)n_problems + 1) * 4;
   ENSURE(c, c->batch_off, bytes);
-  if (!c->batch_off_ev) HIPCHK(c, hipEventCreateWithFlags(&c->batch_off_ev, hipEventDisableTiming));
-  else HIPCHK(c, hipEventSynchronize(c->batch_off_ev));
-  if (c->h_batch_off_cap < bytes) {
-    if (c->h_batch_off) { (void)hipHostFree(c->h_batch_off); c->h_batch_off = nullptr; c->h_batch_off_cap = 0; }
-    const size_t sz = bytes + bytes / 4 + 4096;
-    if (hipHostMalloc(&c->h_batch_off, sz, hipHostMallocDefault) != hipSuccess) {
-      (void)hipGetLastError(); c->h_batch_off = nullptr; c->last_error = "hipHostMalloc failed"; return SC_ENOMEM;
-    }
-    c->h_batch_off_cap = sz;
-  }
+  SC_TRY(batch_staging_begin(c, bytes));
   memcpy(c->h_batch_off, offset, bytes);
-  HIPCHK(c, hipMemcpyAsync(c->batch_off.p, c->h_batch_off, bytes, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipEventRecord(c->batch_off_ev, c->stream));
-  return SC_OK;
+  return batch_staging_send(c, c->batch_off, bytes);
 }
 
 int batch_enqueue(sc_ctx* c, const float* d_src, const float* d_tgt, const uint32_t* offset, uint32_t n_problems, const sc_params* p,
@@ -71,6 +54,40 @@ int batch_enqueue(sc_ctx* c, const float* d_src, const float* d_tgt, const uint3
 }
 
 }  // namespace
+
+namespace sc {
+
+int batch_params_check(sc_ctx* c, const sc_params* p, const char* who) {
+  if (check_params(p) != SC_OK) { c->last_error = std::string(who) + ": bad sc_params (size, a range, or a mode)"; return SC_EINVAL; }
+  if (p->shard_world != 1) { c->last_error = std::string(who) + ": shard_world must be 1"; return SC_EINVAL; }
+  if (p->flags & ~BATCH_FLAGS_IGNORED) {
+    c->last_error = std::string(who) + ": only SC_FLAG_NO_DENSE_S, SC_FLAG_NO_PRUNE and SC_FLAG_EXACT_TOTAL are accepted (no refit, no timing, no estimated bound in a batch)";
+    return SC_EINVAL;
+  }
+  return SC_OK;
+}
+
+int batch_staging_begin(sc_ctx* c, size_t bytes) {
+  if (!c->batch_off_ev) HIPCHK(c, hipEventCreateWithFlags(&c->batch_off_ev, hipEventDisableTiming));
+  else HIPCHK(c, hipEventSynchronize(c->batch_off_ev));
+  if (c->h_batch_off_cap < bytes) {
+    if (c->h_batch_off) { (void)hipHostFree(c->h_batch_off); c->h_batch_off = nullptr; c->h_batch_off_cap = 0; }
+    const size_t sz = bytes + bytes / 4 + 4096;
+    if (hipHostMalloc(&c->h_batch_off, sz, hipHostMallocDefault) != hipSuccess) {
+      (void)hipGetLastError(); c->h_batch_off = nullptr; c->last_error = "hipHostMalloc failed"; return SC_ENOMEM;
+    }
+    c->h_batch_off_cap = sz;
+  }
+  return SC_OK;
+}
+
+int batch_staging_send(sc_ctx* c, Buf& dst, size_t bytes) {
+  HIPCHK(c, hipMemcpyAsync(dst.p, c->h_batch_off, bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipEventRecord(c->batch_off_ev, c->stream));
+  return SC_OK;
+}
+
+}  // namespace sc
 
 extern "C" {
 

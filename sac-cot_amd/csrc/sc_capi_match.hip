@@ -7,9 +7,7 @@
 
 using namespace sc;
 
-namespace {
-
-constexpr size_t MATCH_WORDS_HEAD = 64;  // match_words: [0] clean, [2], [3] the host entries' count pair; the column minima from byte 64
+namespace sc {
 
 int match_check(sc_ctx* c, const sc_match_params* mp, int64_t ns, int64_t nt, MatchJob* job) {
   if (!mp || mp->size != sizeof(sc_match_params)) { c->last_error = "sc_match: bad sc_match_params.size"; return SC_EINVAL; }
@@ -28,6 +26,12 @@ int match_check(sc_ctx* c, const sc_match_params* mp, int64_t ns, int64_t nt, Ma
   job->r2 = mp->ratio > 0.f ? (float)((double)mp->ratio * (double)mp->ratio) : 0.f;
   return SC_OK;
 }
+
+}  // namespace sc
+
+namespace {
+
+constexpr size_t MATCH_WORDS_HEAD = 64;  // match_words: [0] clean, [2], [3] the host entries' count pair; the column minima from byte 64
 
 int match_enqueue(sc_ctx* c, const MatchJob& job, int32_t* d_corr, float* d_d2, uint32_t* d_count, const MatchGather& g, bool to_host) {
   hipStream_t st = c->stream;

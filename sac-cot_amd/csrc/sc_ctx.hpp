@@ -107,7 +107,13 @@ struct Workspace {
       match_part, match_words, match_fsrc, match_ftgt, match_psrc, match_ptgt, match_corr, match_d2, match_gsrc, match_gtgt,
       // sc_register_batch: allocated by the first batch call, never by a frame.  off: the copy of the caller's offsets; the rest:
       // device copies of the host entry's arrays
-      batch_off, batch_src, batch_tgt, batch_res, batch_mask;
+      batch_off, batch_src, batch_tgt, batch_res, batch_mask,
+      // sc_match_batch / sc_register_batch_features: allocated by the first such call, never by a frame.  meta: the copies of both
+      // offset arrays, the slot starts and the tile map; top: the rows' lists between the two launches; words: a "clean" word per
+      // problem, then the column minima; gsrc / gtgt: the gathered points, slot-positioned; the rest: device copies of the host
+      // entries' arrays
+      mbatch_meta, mbatch_top, mbatch_words, mbatch_gsrc, mbatch_gtgt, mbatch_fsrc, mbatch_ftgt, mbatch_psrc, mbatch_ptgt, mbatch_corr,
+      mbatch_d2, mbatch_count, mbatch_res, mbatch_mask;
 };
 constexpr size_t N_WORKSPACE_BUFS = sizeof(Workspace) / sizeof(Buf);
 static_assert(std::is_standard_layout<Workspace>::value && alignof(Workspace) == alignof(Buf) && sizeof(Workspace) == N_WORKSPACE_BUFS * sizeof(Buf),
@@ -216,6 +222,17 @@ inline void copy_stats(sc_stats* stats, const sc_stats& from) { if (stats && sta
 int points_to_device(sc_ctx* c, const float* src, const float* tgt, int64_t n);
 // rt12 and n bytes of mask -> the caller's host arrays (R and t split); the stream is idle on return
 int outputs_to_host(sc_ctx* c, size_t n, float R[9], float t[3], uint8_t* mask);
+
+// ---- defined in sc_capi_match.hip / sc_capi_batch.hip, used by sc_capi_match_batch.hip as well
+// the rules of sc_match_params and of ns, nt; fills everything of *job but the descriptor pointers
+int match_check(sc_ctx* c, const sc_match_params* mp, int64_t ns, int64_t nt, MatchJob* job);
+// what a batch entry refuses of sc_params (shard_world != 1, refit, timing, an estimated bound); `who` opens the message
+int batch_params_check(sc_ctx* c, const sc_params* p, const char* who);
+// The pinned staging area that host words of a batch call (offsets, maps) pass through on their way to the device.  begin: the area
+// holds `bytes` and the copy out of the call before is done (an event behind that copy — not behind that call's kernel); the caller
+// fills c->h_batch_off; send: area -> dst (enqueued), and the event behind it.
+int batch_staging_begin(sc_ctx* c, size_t bytes);
+int batch_staging_send(sc_ctx* c, Buf& dst, size_t bytes);
 
 // ---- a call on a scored frame (sc_peel, sc_polish): what the two share in front of their launches and behind them
 // The entry checks, `busy` first, then "is there a frame"; the refusal names the caller.  Then the context's device.

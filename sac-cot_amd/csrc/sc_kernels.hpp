@@ -705,7 +705,39 @@ struct BatchJob {
   BatchRecord* res;
   uint8_t* mask;
 };
+// sc_register_batch_features: the problems sit in SLOTS — job.offset[b] is where problem b starts, count[2b] how many correspondences
+// it holds (at most BATCH_MAX_N: the slots' capacities, checked by the caller) and count[2b + 1] != 0 says its match read a
+// non-finite descriptor.  The kernel then writes the records of the flagged (SC_EINVAL, n = 0) and the short (n < 3: SC_ENOHYP)
+// problems itself.  A type of its own, so that the plain form's kernel argument — and with it its code — stays what it was.
+struct BatchSlotJob {
+  BatchJob job;
+  const uint32_t* count;
+};
 // One workgroup per problem; every record and mask range is written (complete in stream order).
 void launch_batch_register(const BatchJob& job, hipStream_t st);
+void launch_batch_register_slots(const BatchSlotJob& job, hipStream_t st);
+
+// ---- descriptor matching for a batch of small problems (sc_match_batch; sc_match_batch.hip) -----------------
+// Problem b owns rows [src_off[b], src_off[b + 1]) of fsrc and [tgt_off[b], tgt_off[b + 1]) of ftgt (1 .. MATCH_BATCH_MAX_N rows
+// each, checked by the caller) and the output slot that starts at entry slot[b] = src_off[b] * knn.  tile_map: n_tiles pairs
+// (problem, first row of the tile inside it), tiles of MATCH_BATCH_ROWS source rows, none across two problems.  Everything in
+// device memory.  kp = knn, 2 with the ratio test (r2 > 0).
+constexpr int MATCH_BATCH_ROWS = 64;
+constexpr int MATCH_BATCH_MAX_N = 4096;
+struct MatchBatchJob {
+  const float* fsrc; const float* ftgt;
+  const uint32_t* src_off; const uint32_t* tgt_off; const uint32_t* slot; const uint32_t* tile_map;
+  uint32_t n_problems, n_tiles, dim, knn, kp, mutual;
+  float r2;
+  uint64_t* top;     // kp keys per source row, row src_off[b] + i at top + (src_off[b] + i) * kp: written by the distance launch
+  uint64_t* colmin;  // SC_MATCH_MUTUAL, else nullptr: a key per target row (distance << 32 | source row of the problem), all ones at launch
+  uint32_t* clean;   // a word per problem, non-zero at launch, cleared when the problem reads a non-finite descriptor
+  int32_t* corr; float* d2; uint32_t* count;  // the slots, and 2 words per problem: n_b, the non-finite flag
+  MatchGather g;     // sc_register_batch_features: packed points in, slot-positioned n x 3 arrays out (gsrc == nullptr: no gather)
+};
+// a workgroup per tile: the canonical distances of its rows to every target row of the problem, the rows' kp smallest keys -> top
+void launch_match_batch_dist(const MatchBatchJob& job, hipStream_t st);
+// a workgroup per problem: mutual / ratio per row, compaction inside the slot in ascending (row, rank) order, the count pair, the gather
+void launch_match_batch_finish(const MatchBatchJob& job, hipStream_t st);
 
 }  // namespace sc

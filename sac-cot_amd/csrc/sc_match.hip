@@ -23,6 +23,7 @@
 
 #include "sc_block.hpp"
 #include "sc_kernels.hpp"
+#include "sc_match_tile.hpp"
 
 #pragma clang fp contract(off)  // the canonical distance rounds the product and the sum separately
 
@@ -30,41 +31,9 @@ namespace sc {
 
 namespace {
 
-constexpr int MT_ROWS = 128, MT_COLS = 64, MT_KC = 16, MT_THREADS = 256;
+constexpr int MT_ROWS = 128, MT_COLS = 64, MT_THREADS = 256;  // (MT_KC, the key, tile_step and top_insert: sc_match_tile.hpp, shared with sc_match_batch.hip)
 constexpr int MT_LDA = MT_ROWS + 4, MT_LDB = MT_COLS + 4;  // 16-byte aligned rows; the pad spreads the transposing stores over the banks
 constexpr int FIN_THREADS = 256;
-constexpr unsigned long long KEY_NONE = ~0ull;  // above every real key: a real key's low half is an index < 2^24
-
-typedef float f2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ bool not_finite(float v) { return (__float_as_uint(v) & 0x7F800000u) == 0x7F800000u; }
-
-// slot q keeps the smaller, the larger moves on (see the head of the file)
-template <int KP>
-__device__ __forceinline__ void top_insert(unsigned long long* list, unsigned long long key) {
-#pragma unroll
-  for (int q = 0; q < KP; q++) {
-    const unsigned long long old = atomicMin(&list[q], key);
-    if (old > key) key = old;
-    if (key == KEY_NONE) break;  // (an empty slot was filled: nothing left to pass on)
-  }
-}
-
-// one component: the thread's 8 rows (pa) against its 4 columns (pb), as two column pairs
-__device__ __forceinline__ void tile_step(f2 (&acc)[8][2], const float* pa, const float* pb) {
-  const float4 a0 = *reinterpret_cast<const float4*>(pa);
-  const float4 a1 = *reinterpret_cast<const float4*>(pa + 4);
-  const float4 b = *reinterpret_cast<const float4*>(pb);
-  const float a[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-  const f2 b01 = f2{b.x, b.y}, b23 = f2{b.z, b.w};
-#pragma unroll
-  for (int r = 0; r < 8; r++) {
-    const f2 ar = f2{a[r], a[r]};
-    const f2 d0 = ar - b01, d1 = ar - b23;
-    acc[r][0] = acc[r][0] + d0 * d0;
-    acc[r][1] = acc[r][1] + d1 * d1;
-  }
-}
 
 template <int KP>
 __global__ __launch_bounds__(MT_THREADS) void match_dist_kernel(const float* __restrict__ fsrc, uint32_t ns,

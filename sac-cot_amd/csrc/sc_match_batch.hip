@@ -1,0 +1,210 @@
+// sc_match_batch.hip — descriptor matching for a whole batch of small problems (include/saccot.h, sc_match_batch): the kernels.
+// The arithmetic and the selection step are sc_match.hip's (sc_match_tile.hpp), so problem b's slot holds what sc_match returns
+// for problem b alone, bit for bit.  Two launches for the batch, whatever its size:
+//
+//   match_batch_dist_kernel    grid = the flattened list of (problem, tile of 64 source rows); the tile map comes from the host with
+//                              the offsets, and a tile never spans two problems.  A workgroup of 128 threads walks ALL target
+//                              columns of its problem in tiles of 64 — no slices: a row's KP smallest keys complete in the
+//                              workgroup's LDS lists and go to `top` once.  Register tile 8 rows x 4 columns per thread, chunks of 16
+//                              components staged transposed in LDS, zero padding in c and in rows (exact: (0 - 0)^2 adds +0).
+//                              64 rows, not sc_match's 128: problems of 64 - 512 rows leave half as many padded rows on average
+//                              (32 against 64), a batch of 16 problems of 256 rows still makes 64 workgroups, and 11 KB of LDS with
+//                              two waves lets a compute unit hold many of them at once.  The column minima of SC_MATCH_MUTUAL combine in
+//                              LDS, then by 64-bit atomic minima on colmin[tgt_off[b] + j] (a minimum is order-free: deterministic).
+//                              A non-finite descriptor clears the problem's own `clean` word: a problem's tiles together read
+//                              every element of it, and nothing of another problem.
+//   match_batch_finish_kernel  a workgroup of 256 per problem: a thread per source row, 256 rows at a time with a running count —
+//                              mutual / ratio per row, a workgroup scan, and the kept keys go into the problem's slot in ascending
+//                              (row, rank) order with their indices local to the problem; the matched points are gathered
+//                              beside them for sc_register_batch_features; thread 0 writes the count pair.  No look-back across
+//                              problems: a slot's position is known on the host.
+#include <cstddef>
+
+#include "sc_block.hpp"
+#include "sc_kernels.hpp"
+#include "sc_match_tile.hpp"
+
+#pragma clang fp contract(off)  // the canonical distance rounds the product and the sum separately
+
+namespace sc {
+
+namespace {
+
+constexpr int MB_ROWS = MATCH_BATCH_ROWS, MB_COLS = 64, MB_THREADS = 128;
+constexpr int MB_LD = 64 + 4;  // 16-byte aligned rows; the pad spreads the transposing stores over the banks
+constexpr int MBF_THREADS = 256;
+static_assert(MB_ROWS == 64 && MB_THREADS == (MB_ROWS / 8) * (MB_COLS / 4), "a thread owns 8 rows x 4 columns of the tile");
+
+template <int KP>
+__global__ __launch_bounds__(MB_THREADS) void match_batch_dist_kernel(const MatchBatchJob job) {
+  __shared__ __attribute__((aligned(16))) float sA[MT_KC][MB_LD];
+  __shared__ __attribute__((aligned(16))) float sB[MT_KC][MB_LD];
+  __shared__ unsigned long long s_top[MB_ROWS][KP];
+  __shared__ unsigned long long s_col[MB_COLS];
+  const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;  // the thread's 4 columns / 8 rows; also (component, row) when it loads
+  if (blockIdx.x >= job.n_tiles) return;
+  const uint32_t b = job.tile_map[2 * blockIdx.x], row0 = job.tile_map[2 * blockIdx.x + 1];
+  if (b >= job.n_problems) return;  // (cannot happen: the host built the map)
+  const uint32_t so = job.src_off[b], to = job.tgt_off[b];
+  const uint32_t ns = job.src_off[b + 1] - so, nt = job.tgt_off[b + 1] - to, D = job.dim;
+  const float* __restrict__ fsrc = job.fsrc + (size_t)so * D;
+  const float* __restrict__ ftgt = job.ftgt + (size_t)to * D;
+  unsigned long long* const colmin = job.colmin ? reinterpret_cast<unsigned long long*>(job.colmin) + to : nullptr;
+  const uint32_t n_tiles = (nt + MB_COLS - 1) / MB_COLS;
+  for (int e = threadIdx.x; e < MB_ROWS * KP; e += MB_THREADS) (&s_top[0][0])[e] = KEY_NONE;
+  bool bad = false;
+  for (uint32_t tile = 0; tile < n_tiles; tile++) {
+    const uint32_t col0 = tile * MB_COLS;
+    if (threadIdx.x < MB_COLS) s_col[threadIdx.x] = KEY_NONE;
+    f2 acc[8][2];
+#pragma unroll
+    for (int r = 0; r < 8; r++) { acc[r][0] = f2{0.f, 0.f}; acc[r][1] = f2{0.f, 0.f}; }
+    for (uint32_t c0 = 0; c0 < D; c0 += MT_KC) {
+      const uint32_t c = c0 + tx;
+      float va[MB_ROWS / 8], vb[MB_COLS / 8];
+#pragma unroll
+      for (int it = 0; it < MB_ROWS / 8; it++) {
+        const uint32_t row = row0 + ty + 8 * it;
+        va[it] = (row < ns && c < D) ? fsrc[(size_t)row * D + c] : 0.f;
+      }
+#pragma unroll
+      for (int it = 0; it < MB_COLS / 8; it++) {
+        const uint32_t col = col0 + ty + 8 * it;
+        vb[it] = (col < nt && c < D) ? ftgt[(size_t)col * D + c] : 0.f;
+      }
+      __syncthreads();  // the chunk before is consumed (and, first chunk: the lists' and s_col's initial values are written)
+#pragma unroll
+      for (int it = 0; it < MB_ROWS / 8; it++) { bad = bad || not_finite(va[it]); sA[tx][ty + 8 * it] = va[it]; }
+#pragma unroll
+      for (int it = 0; it < MB_COLS / 8; it++) { bad = bad || not_finite(vb[it]); sB[tx][ty + 8 * it] = vb[it]; }
+      __syncthreads();
+      // the last chunk of a descriptor is cut short (D = 33: 16 + 16 + 1 components, not 48); the bound is uniform
+      const uint32_t lim = D - c0 < (uint32_t)MT_KC ? D - c0 : (uint32_t)MT_KC;
+      if (lim == (uint32_t)MT_KC) {
+#pragma unroll
+        for (int k = 0; k < MT_KC; k++) tile_step(acc, &sA[k][ty * 8], &sB[k][tx * 4]);
+      } else {
+        for (uint32_t k = 0; k < lim; k++) tile_step(acc, &sA[k][ty * 8], &sB[k][tx * 4]);
+      }
+    }
+    // selection.  (Every thread is behind the last chunk's second barrier: the lists and s_col hold at least their initial values.)
+    const uint32_t colb = col0 + tx * 4;
+    unsigned long long cmin[4] = {KEY_NONE, KEY_NONE, KEY_NONE, KEY_NONE};
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+      const uint32_t lr = ty * 8 + r, row = row0 + lr;
+      if (row >= ns) continue;
+      const float v[4] = {acc[r][0].x, acc[r][0].y, acc[r][1].x, acc[r][1].y};
+      unsigned long long* list = &s_top[lr][0];
+      // what the list's last slot holds only ever falls: an old value lets a candidate through that the cascade then passes out again
+      const unsigned long long worst = *reinterpret_cast<volatile unsigned long long*>(&list[KP - 1]);
+      unsigned long long best = KEY_NONE;
+#pragma unroll
+      for (int cc = 0; cc < 4; cc++) {
+        if (colb + cc >= nt) continue;
+        const unsigned long long hi = (unsigned long long)__float_as_uint(v[cc]) << 32;
+        const unsigned long long key = hi | (colb + cc);
+        const unsigned long long rkey = hi | row;
+        cmin[cc] = rkey < cmin[cc] ? rkey : cmin[cc];
+        if (KP == 1) best = key < best ? key : best;
+        else if (key < worst) top_insert<KP>(list, key);
+      }
+      if (KP == 1 && best < worst) atomicMin(&list[0], best);
+    }
+    if (colmin) {
+#pragma unroll
+      for (int cc = 0; cc < 4; cc++)
+        if (cmin[cc] != KEY_NONE) atomicMin(&s_col[tx * 4 + cc], cmin[cc]);
+      __syncthreads();
+      if (threadIdx.x < MB_COLS && col0 + threadIdx.x < nt) {
+        const unsigned long long v = s_col[threadIdx.x];
+        unsigned long long* g = &colmin[col0 + threadIdx.x];
+        if (v < __hip_atomic_load(g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(g, v);
+      }
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < MB_ROWS && row0 + threadIdx.x < ns) {
+    unsigned long long* out = reinterpret_cast<unsigned long long*>(job.top) + ((size_t)so + row0 + threadIdx.x) * KP;
+#pragma unroll
+    for (int q = 0; q < KP; q++) out[q] = s_top[threadIdx.x][q];
+  }
+  if (bad) __hip_atomic_store(&job.clean[b], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ __launch_bounds__(MBF_THREADS) void match_batch_finish_kernel(const MatchBatchJob job) {
+  __shared__ uint64_t s_scan[MBF_THREADS / 64];
+  const uint32_t b = blockIdx.x;
+  const uint32_t so = job.src_off[b], to = job.tgt_off[b];
+  const uint32_t ns = job.src_off[b + 1] - so, nt = job.tgt_off[b + 1] - to;
+  const size_t slot = job.slot[b], cap = (size_t)ns * job.knn;
+  const bool ok = job.clean[b] != 0u;  // (written by the launch before this one)
+  const unsigned long long* __restrict__ top = reinterpret_cast<const unsigned long long*>(job.top) + (size_t)so * job.kp;
+  const unsigned long long* __restrict__ colmin = job.colmin ? reinterpret_cast<const unsigned long long*>(job.colmin) + to : nullptr;
+  const MatchGather g = job.g;
+  uint32_t run = 0;  // kept so far, by the rows before this step's
+  for (uint32_t base = 0; ok && base < ns; base += MBF_THREADS) {
+    const uint32_t i = base + threadIdx.x;
+    unsigned long long key[4] = {KEY_NONE, KEY_NONE, KEY_NONE, KEY_NONE};
+    uint32_t cnt = 0;
+    if (i < ns) {
+#pragma unroll
+      for (int q = 0; q < 4; q++)
+        if (q < (int)job.kp) key[q] = top[(size_t)i * job.kp + q];
+      if (job.mutual || job.r2 > 0.f) {
+        bool keep = key[0] != KEY_NONE;
+        const uint32_t j = (uint32_t)key[0];
+        if (keep && job.mutual) keep = j < nt && colmin[j] == ((key[0] & 0xFFFFFFFF00000000ull) | i);
+        if (keep && job.r2 > 0.f && key[1] != KEY_NONE)
+          keep = __uint_as_float((uint32_t)(key[0] >> 32)) < __fmul_rn(job.r2, __uint_as_float((uint32_t)(key[1] >> 32)));
+        cnt = keep ? 1u : 0u;
+      } else {
+#pragma unroll
+        for (int w = 0; w < 4; w++) cnt += (w < (int)job.knn && key[w] != KEY_NONE) ? 1u : 0u;
+      }
+    }
+    uint64_t tot;
+    const uint64_t ex = block_exscan_u64(cnt, s_scan, &tot);
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+      if (w >= (int)cnt) break;
+      const size_t m = (size_t)run + ex + w;
+      const uint32_t j = (uint32_t)key[w];
+      if (m >= cap || j >= nt) break;  // (cannot happen: a row emits at most knn keys, each with a column of its problem)
+      const size_t e = slot + m;
+      job.corr[2 * e] = (int32_t)i;
+      job.corr[2 * e + 1] = (int32_t)j;
+      job.d2[e] = __uint_as_float((uint32_t)(key[w] >> 32));
+      if (g.gsrc) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+          g.gsrc[3 * e + c] = g.src[((size_t)so + i) * g.s_elem + (size_t)c * g.s_comp];
+          g.gtgt[3 * e + c] = g.tgt[((size_t)to + j) * g.t_elem + (size_t)c * g.t_comp];
+        }
+      }
+    }
+    run += (uint32_t)tot;
+  }
+  if (threadIdx.x == 0) {
+    job.count[2 * b] = ok ? run : 0u;
+    job.count[2 * b + 1] = ok ? 0u : 1u;
+  }
+}
+
+}  // namespace
+
+void launch_match_batch_dist(const MatchBatchJob& job, hipStream_t st) {
+  const dim3 grid(job.n_tiles), block(MB_THREADS);
+  switch (job.kp) {
+    case 1: hipLaunchKernelGGL(match_batch_dist_kernel<1>, grid, block, 0, st, job); break;
+    case 2: hipLaunchKernelGGL(match_batch_dist_kernel<2>, grid, block, 0, st, job); break;
+    case 3: hipLaunchKernelGGL(match_batch_dist_kernel<3>, grid, block, 0, st, job); break;
+    default: hipLaunchKernelGGL(match_batch_dist_kernel<4>, grid, block, 0, st, job); break;
+  }
+}
+
+void launch_match_batch_finish(const MatchBatchJob& job, hipStream_t st) {
+  hipLaunchKernelGGL(match_batch_finish_kernel, dim3(job.n_problems), dim3(MBF_THREADS), 0, st, job);
+}
+
+}  // namespace sc
