@@ -3,6 +3,9 @@
 The expected value of every case is tests/batch_ref.py — problem b alone through the CPU restatement's whole path — and everything
 is compared bit for bit: every field of every record and every mask byte.  Every problem holds at most batch_ref.TRI_CAP triangles
 (asserted on the reference's counts), so no workgroup runs long.
+
+Every scene here has unit extent.  tests/test_gpu_batch_range.py runs the same kernel, and its slot form, at the ends of the fp32
+range, and puts the cut among equal keys on every boundary of the three find_cut passes (word, chunk, row and edge ends).
 """
 import ctypes as C
 

@@ -3,6 +3,9 @@
 The expected value of every case is tests/polish_ref.py — the semantics restated on the CPU restatement's O.score / O.mask /
 O.refine — and everything is compared bit for bit: every field of every candidate record, the winner's (R, t), the mask,
 best_rank and best_count.
+
+The scenes here are the configs' own (unit scale).  tests/test_gpu_polish_range.py runs the iterated refit, its candidate select and
+its stop rules at the ends of the fp32 range.
 """
 import ctypes as C
 
