@@ -41,6 +41,7 @@ extern "C" {
 #define SC_HAS_POLISH 1  /* this header declares sc_polish* (added within 0.10) */
 #define SC_HAS_BATCH 1   /* this header declares sc_register_batch* (added within 0.10) */
 #define SC_HAS_MATCH_BATCH 1  /* this header declares sc_match_batch* and sc_register_batch_features* (added within 0.10) */
+#define SC_HAS_POLISH_BATCH 1  /* this header declares sc_polish_batch* (added within 0.10) */
 
 /* status codes */
 #define SC_OK        0
@@ -252,7 +253,8 @@ int sc_wait(sc_ctx* ctx, sc_stats* stats);
  *   - The CALL returns SC_EINVAL, decided on the host before anything is enqueued, sc_last_error naming which: a NULL argument;
  *     n_problems == 0; an n_b < 3 or > SC_BATCH_MAX_N; offsets that decrease, or a total above 2^31; shard_world != 1; any flag other
  *     than SC_FLAG_NO_DENSE_S, SC_FLAG_NO_PRUNE, SC_FLAG_EXACT_TOTAL (result-neutral: accepted and ignored) — SC_FLAG_REFINE, the timing
- *     flags, SC_FLAG_EST_BOUND, SC_FLAG_SHARD_AB are refused: the fp64 refit is not part of a batch member's path; the usual sc_params
+ *     flags, SC_FLAG_EST_BOUND, SC_FLAG_SHARD_AB are refused: the fp64 refit is not part of a batch member's path (it is a launch of
+ *     its own behind it: sc_polish_batch); the usual sc_params
  *     checks; a call outstanding on the context.
  *   - max_triangles may be anything sc_register accepts: nothing is materialised per hypothesis, so SC_ETOOMANY cannot occur.
  *   - sc_register_batch_device enqueues on the context's stream and returns without waiting, like sc_match_device: d_res and d_mask are
@@ -491,6 +493,78 @@ int sc_register_batch_features(sc_ctx* ctx, const float* src_pts, const float* f
                                const float* ftgt, const uint32_t* tgt_off, uint32_t n_problems, const sc_match_params* mp,
                                const sc_params* params, sc_batch_result* res, int32_t* corr, float* d2, uint32_t* count,
                                uint8_t* mask);
+
+/* ---- iterated fp64 refits for a batch's winners: sc_polish_batch ---------------------------------------------
+ * What a frame's caller gets from SC_FLAG_REFINE and sc_polish, for the members of a batch: sc_register_batch* leaves the Kabsch pose
+ * of ONE 3-point sample per problem; sc_polish_batch iterates "inliers of (R, t) -> fp64 least-squares refit -> inliers again" to a
+ * fixed point for every problem of the batch in ONE launch, a workgroup per problem (sc_polish_batch.hip).  sc_register_batch_device
+ * followed by sc_polish_batch_device on the same context is two launches and no host word.
+ *
+ * Layout: the packed problems of sc_register_batch — d_src, d_tgt, offset (a HOST array of n_problems + 1 words), params->layout —
+ * plus d_res, n_problems records of sc_batch_result that hold the input pose and status of every problem.  d_res is READ, never
+ * written, and need not come from sc_register_batch: only its status and Rt are looked at.  d_pol receives n_problems records of
+ * sc_polish_batch_result, d_mask total bytes.
+ *
+ * sc_polish_params is reused: candidates MUST be 1 — a batch member keeps only its winner, nothing is materialised per hypothesis, so
+ * more than one candidate per problem is out of scope —, max_iter 1 .. 64, flags and reserved 0.  sc_params is checked as
+ * sc_register_batch checks it; only tau, score_mode and layout are read.
+ *
+ * Semantics, per problem b with input status SC_OK: Rt_0 = d_res[b].Rt, score0 = its score over all n_b in params->score_mode; then
+ * step 2 of sc_polish, exactly: for it = 1 .. max_iter, mask = the canonical inlier test of Rt_{it-1}, Rt_it = the fp64 refit over
+ * that mask in its canonical order, rounded to fp32; stop when the refit is declined (fewer than 3 inliers, or a non-finite result:
+ * SC_POLISH_STOP_DECLINED), when Rt_it equals Rt_{it-1} bit for bit (SC_POLISH_STOP_FIXED), or after max_iter refits
+ * (SC_POLISH_STOP_MAX_ITER).  iters = the refits that changed (R, t); Rt = the last iterate; score = its score over all n_b; mask byte
+ * m = the canonical inlier test of Rt.  The record equals, bit for bit, what sc_register + sc_polish(candidates = 1, the same max_iter)
+ * return for the problem alone, and with max_iter = 1 its Rt is sc_register's with SC_FLAG_REFINE.
+ *   - A first refit that is declined: status SC_OK, Rt = the input's bits, iters 0, score = score0.
+ *   - Input status != SC_OK: that status is passed through; R = I, t = 0, scores 0, iters 0, stop SC_POLISH_STOP_DECLINED, mask zero.
+ *   - Input status SC_OK but a non-finite coordinate, or a non-finite input Rt: SC_EINVAL with the same output shape.  It is found on
+ *     the device, affects only that problem and does not fail the call.
+ *   - A record is a function of the problem's points, the input Rt, tau, score_mode and max_iter only: not of its position in the
+ *     batch, of the neighbours, or of the context's history.
+ *   - score MAY be below score0 in the inlier-count mode, as sc_polish's may be below the frame's (see there).
+ * d_mask MAY be the buffer sc_register_batch_device wrote: the kernel never reads a mask.
+ *
+ * The slot form follows sc_register_batch_features_device: problem b's correspondences are (src_pts[src_off[b] + corr[slot[b] + m][0]],
+ * tgt_pts[tgt_off[b] + corr[slot[b] + m][1]]), m < count[2b], slot[b] = src_off[b] * knn; d_res, d_pol and the mask bytes are positioned
+ * as that entry positions them.  The kernel gathers while it stages and keeps no state from the features call.  A flagged problem or
+ * one with count[2b] < 3 passes its input status through (SC_EINVAL if that status claims SC_OK); an index in corr outside the problem
+ * is SC_EINVAL for that problem.  knn is the sc_match_params.knn the slots were laid out with (1 .. 4).
+ *
+ * Errors: the CALL returns SC_EINVAL, decided on the host before anything is enqueued, sc_last_error naming which: a NULL argument;
+ * everything sc_register_batch refuses (the slot form: everything sc_register_batch_features refuses of the offsets, ns_b * knn >
+ * SC_BATCH_MAX_N included); pp->size wrong, candidates != 1, max_iter outside 1 .. 64, a non-zero flag or reserved word; a call
+ * outstanding on the context.  The device forms enqueue on the context's stream and return without waiting: outputs are complete in
+ * stream order.  (Like sc_register_batch_device they may wait for the previous batch call's copy out of the offset staging area they
+ * share: an event behind that copy, not behind its kernel.)  All three entries end the frame a context may hold and leave none.
+ * Workspace: the copies of the offsets, plus the host form's device copies of its arrays; allocated by the first such call, counted in
+ * workspace_bytes and held against params->max_workspace (SC_ENOMEM).  A context that never calls these entries allocates and runs
+ * nothing new.  There is no async / wait form and no balancing by problem size. */
+#define SC_POLISH_STOP_FIXED    0   /* the refit returned the bits it started from               */
+#define SC_POLISH_STOP_DECLINED 1   /* fewer than 3 inliers or a non-finite refit; or no pose    */
+#define SC_POLISH_STOP_MAX_ITER 2   /* max_iter refits done, the last one still changed (R, t)  */
+typedef struct sc_polish_batch_result {  /* 64 bytes */
+  float    Rt[12];   /* the last iterate; R = I, t = 0 unless status == SC_OK                  */
+  int32_t  status;   /* SC_OK, or why there is no pose: SC_ENOHYP / SC_EINVAL                  */
+  uint32_t score0;   /* score of the input pose over all n, params->score_mode                 */
+  uint32_t score;    /* score of Rt                                                            */
+  uint16_t iters;    /* refits that changed (R, t)                                             */
+  uint16_t stop;     /* SC_POLISH_STOP_*                                                       */
+} sc_polish_batch_result;
+/* every buffer but offset in HBM: d_src / d_tgt total x 3 floats, d_res / d_pol n_problems records, d_mask total bytes */
+int sc_polish_batch_device(sc_ctx* ctx, const float* d_src, const float* d_tgt, const uint32_t* offset, uint32_t n_problems,
+                           const sc_params* params, const sc_polish_params* pp, const sc_batch_result* d_res,
+                           sc_polish_batch_result* d_pol, uint8_t* d_mask);
+/* the same with host arrays; waits */
+int sc_polish_batch(sc_ctx* ctx, const float* src, const float* tgt, const uint32_t* offset, uint32_t n_problems,
+                    const sc_params* params, const sc_polish_params* pp, const sc_batch_result* res, sc_polish_batch_result* pol,
+                    uint8_t* mask);
+/* behind sc_register_batch_features_device: the points and both offset arrays as given there, its d_corr, d_count and d_res;
+ * d_pol n_problems records, d_mask total_s * knn bytes */
+int sc_polish_batch_slots_device(sc_ctx* ctx, const float* d_src_pts, const uint32_t* src_off, const float* d_tgt_pts,
+                                 const uint32_t* tgt_off, uint32_t n_problems, uint32_t knn, const sc_params* params,
+                                 const sc_polish_params* pp, const int32_t* d_corr, const uint32_t* d_count,
+                                 const sc_batch_result* d_res, sc_polish_batch_result* d_pol, uint8_t* d_mask);
 
 /* ---- two-phase form for one-process-per-GPU sharding --------------------------------
  * Phase 1: A and B replicated, C1+C2 on this rank's blocks of the top-T list; writes this rank's winner key

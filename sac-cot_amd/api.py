@@ -42,6 +42,7 @@ EXPORTS = ["sc_version", "sc_strerror", "sc_default_params", "sc_create", "sc_de
            "sc_polish_default_params", "sc_polish_device", "sc_polish",
            "sc_match_default_params", "sc_match_device", "sc_match", "sc_register_features",
            "sc_match_batch", "sc_match_batch_device", "sc_register_batch_features", "sc_register_batch_features_device",
+           "sc_polish_batch", "sc_polish_batch_device", "sc_polish_batch_slots_device",
            "sc_hypothesize_device", "sc_finalize_device",
            "sc_hypothesize_begin_device", "sc_hypothesize_end_device", "sc_finalize_gathered_device", "sc_finalize_gathered_device_async",
            "sc_shard_plan_query", "sc_shard_compat_device", "sc_shard_edges_device", "sc_shard_select_device",
@@ -104,6 +105,17 @@ BATCH_RESULT_DTYPE = np.dtype([("Rt", np.float32, 12), ("status", np.int32), ("n
                                ("tri_kept", np.uint32), ("tri_total", np.uint64), ("best_rank", np.uint32),
                                ("best_count", np.uint32)])  # sc_batch_result as a numpy record
 SC_BATCH_MAX_N = 512
+
+
+class ScPolishBatchResult(C.Structure):
+    """Mirror of `sc_polish_batch_result` (include/saccot.h), 64 bytes: one problem's record of sc_polish_batch."""
+    _fields_ = [("Rt", C.c_float * 12), ("status", C.c_int32), ("score0", C.c_uint32), ("score", C.c_uint32), ("iters", C.c_uint16),
+                ("stop", C.c_uint16)]
+
+
+POLISH_BATCH_RESULT_DTYPE = np.dtype([("Rt", np.float32, 12), ("status", np.int32), ("score0", np.uint32), ("score", np.uint32),
+                                      ("iters", np.uint16), ("stop", np.uint16)])  # sc_polish_batch_result as a numpy record
+SC_POLISH_STOP_FIXED, SC_POLISH_STOP_DECLINED, SC_POLISH_STOP_MAX_ITER = 0, 1, 2
 SC_MATCH_BATCH_MAX_N = 4096  # rows a side of one problem of sc_match_batch
 
 
@@ -210,6 +222,9 @@ def load_library() -> C.CDLL:
     L.sc_match_batch.argtypes = [vp, f32p, u32p, f32p, u32p, C.c_uint32, mp, i32p, f32p, u32p]
     L.sc_register_batch_features_device.argtypes = [vp, vp, vp, u32p, vp, vp, u32p, C.c_uint32, mp, pp, vp, vp, vp, vp, vp]
     L.sc_register_batch_features.argtypes = [vp, f32p, f32p, u32p, f32p, f32p, u32p, C.c_uint32, mp, pp, vp, i32p, f32p, u32p, u8p]
+    L.sc_polish_batch.argtypes = [vp, f32p, f32p, u32p, C.c_uint32, pp, qp, vp, vp, u8p]
+    L.sc_polish_batch_device.argtypes = [vp, vp, vp, u32p, C.c_uint32, pp, qp, vp, vp, vp]
+    L.sc_polish_batch_slots_device.argtypes = [vp, vp, u32p, vp, u32p, C.c_uint32, C.c_uint32, pp, qp, vp, vp, vp, vp, vp]
     L.sc_hypothesize_device.argtypes = [vp, vp, vp, C.c_int64, pp, vp, sp]
     L.sc_finalize_device.argtypes = [vp, vp, vp, vp, sp]
     L.sc_hypothesize_begin_device.argtypes = [vp, vp, vp, C.c_int64, pp, vp, sp]
@@ -616,6 +631,69 @@ class Registrar:
         self._check(self._lib.sc_register_batch_features_device(self._h, d_src_pts, d_fsrc, _p(src_off, C.c_uint32), d_tgt_pts, d_ftgt,
                                                                 _p(tgt_off, C.c_uint32), max(len(src_off) - 1, 0), C.byref(mparams),
                                                                 C.byref(params), d_res, d_corr, d_d2, d_count, d_mask))
+
+    # ---- iterated fp64 refits for a batch's winners (include/saccot.h, sc_polish_batch) ------------------------------
+    def polish_batch_raw(self, src, tgt, offset, params: ScParams, pparams: ScPolishParams, res):
+        """sc_polish_batch on packed arrays: src / tgt / offset as register_batch_raw's, res (B,) records of BATCH_RESULT_DTYPE (the
+        input poses and statuses; read only) -> (records (B,) of POLISH_BATCH_RESULT_DTYPE, mask (total,) uint8)."""
+        src, tgt = _f32c(src), _f32c(tgt)
+        offset = np.ascontiguousarray(offset, dtype=np.uint32)
+        res = np.ascontiguousarray(res, dtype=BATCH_RESULT_DTYPE)
+        nb = max(len(offset) - 1, 0)
+        if len(res) != nb:
+            raise ValueError("polish_batch_raw: one input record per problem")
+        total = int(offset[-1]) if len(offset) else 0
+        pol = np.zeros(max(nb, 1), POLISH_BATCH_RESULT_DTYPE); mask = np.zeros(max(total, 1), np.uint8)
+        self._frame_n = 0
+        self._check(self._lib.sc_polish_batch(self._h, _p(src, C.c_float), _p(tgt, C.c_float), _p(offset, C.c_uint32), nb,
+                                              C.byref(params), C.byref(pparams), res.ctypes.data_as(C.c_void_p),
+                                              pol.ctypes.data_as(C.c_void_p), _p(mask, C.c_uint8)))
+        return pol[:nb], mask[:total]
+
+    def polish_batch_device(self, d_src: int, d_tgt: int, offset, params: ScParams, pparams: ScPolishParams, d_res: int, d_pol: int,
+                            d_mask: int):
+        """sc_polish_batch_device: points, input records (80 bytes each, read only), output records (64 bytes each) and mask in HBM,
+        offset a HOST array (B + 1,) uint32; enqueues on the context's stream and returns without waiting.  d_mask may be the
+        buffer register_batch_device wrote."""
+        offset = np.ascontiguousarray(offset, dtype=np.uint32)
+        self._frame_n = 0
+        self._check(self._lib.sc_polish_batch_device(self._h, d_src, d_tgt, _p(offset, C.c_uint32), max(len(offset) - 1, 0),
+                                                     C.byref(params), C.byref(pparams), d_res, d_pol, d_mask))
+
+    def polish_batch_slots_device(self, d_src_pts: int, src_off, d_tgt_pts: int, tgt_off, knn: int, params: ScParams,
+                                  pparams: ScPolishParams, d_corr: int, d_count: int, d_res: int, d_pol: int, d_mask: int):
+        """sc_polish_batch_slots_device: behind register_batch_features_device — its points, offsets, d_corr, d_count and d_res; d_pol
+        B records of 64 bytes, d_mask total_s * knn bytes; enqueues on the context's stream and returns without waiting."""
+        src_off, tgt_off = np.ascontiguousarray(src_off, dtype=np.uint32), np.ascontiguousarray(tgt_off, dtype=np.uint32)
+        self._frame_n = 0
+        self._check(self._lib.sc_polish_batch_slots_device(self._h, d_src_pts, _p(src_off, C.c_uint32), d_tgt_pts, _p(tgt_off, C.c_uint32),
+                                                           max(len(src_off) - 1, 0), knn, C.byref(params), C.byref(pparams), d_corr,
+                                                           d_count, d_res, d_pol, d_mask))
+
+    def register_batch_polished(self, problems, params: ScParams | None = None, pparams: ScPolishParams | None = None, max_iter: int = 16,
+                                **kw):
+        """sc_register_batch, then sc_polish_batch on its records.  problems: a list of (src (n_b, 3), tgt (n_b, 3)) pairs -> one dict
+        per problem: register_batch's (status, R, t, mask, stats: the batch record) plus polished = dict(status, R, t, mask, score0,
+        score, iters, stop) — the winner refitted over its own inliers until nothing changes (at most max_iter refits)."""
+        p = params or make_params(**kw)
+        q = pparams or make_polish_params(candidates=1, max_iter=max_iter)
+        sizes = [np.shape(s)[0] for s, _ in problems]
+        offset = self._offsets(sizes)
+        src = np.concatenate([_f32c(s).reshape(-1, 3) for s, _ in problems]) if sizes else np.zeros((0, 3), np.float32)
+        tgt = np.concatenate([_f32c(t).reshape(-1, 3) for _, t in problems]) if sizes else np.zeros((0, 3), np.float32)
+        if p.layout == SC_SOA:
+            src, tgt = np.ascontiguousarray(src.T), np.ascontiguousarray(tgt.T)
+        res, mask = self.register_batch_raw(src, tgt, offset, p)
+        pol, pmask = self.polish_batch_raw(src, tgt, offset, p, q, res)
+        out = []
+        for b, (r, o) in enumerate(zip(res, pol)):
+            lo, hi = int(offset[b]), int(offset[b + 1])
+            stats = {k: int(r[k]) for k in ("n", "edges", "tri_total", "tri_kept", "best_rank", "best_count")}
+            polished = dict(status=int(o["status"]), R=o["Rt"][:9].reshape(3, 3).copy(), t=o["Rt"][9:].copy(), mask=pmask[lo:hi].copy(),
+                            score0=int(o["score0"]), score=int(o["score"]), iters=int(o["iters"]), stop=int(o["stop"]))
+            out.append(dict(status=int(r["status"]), R=r["Rt"][:9].reshape(3, 3).copy(), t=r["Rt"][9:].copy(), mask=mask[lo:hi].copy(),
+                            stats=stats, polished=polished))
+        return out
 
     def hypothesize_device(self, d_src: int, d_tgt: int, n: int, params: ScParams, d_key: int):
         st = ScStats(C.sizeof(ScStats))

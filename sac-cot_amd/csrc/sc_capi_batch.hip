@@ -11,22 +11,10 @@ namespace {
 
 constexpr uint32_t BATCH_FLAGS_IGNORED = SC_FLAG_NO_DENSE_S | SC_FLAG_NO_PRUNE | SC_FLAG_EXACT_TOTAL;  // result-neutral
 
-// the caller's offsets: sizes 3 .. SC_BATCH_MAX_N, nothing decreasing, a total of 2^31 at most.  nullptr: they are fine
-const char* batch_offsets_error(const uint32_t* offset, uint32_t n_problems) {
-  if (n_problems == 0) return "sc_register_batch: n_problems == 0";
-  for (uint32_t b = 0; b < n_problems; b++) {
-    if (offset[b + 1] < offset[b]) return "sc_register_batch: offsets decrease";
-    const uint32_t nb = offset[b + 1] - offset[b];
-    if (nb < 3 || nb > SC_BATCH_MAX_N) return "sc_register_batch: a problem has fewer than 3 or more than SC_BATCH_MAX_N correspondences";
-  }
-  if (offset[n_problems] > (1u << 31)) return "sc_register_batch: more than 2^31 correspondences in all";
-  return nullptr;
-}
-
 int batch_check(sc_ctx* c, const uint32_t* offset, uint32_t n_problems, const sc_params* p) {
   SC_TRY(entry_checks(c, nullptr, ENDS_FRAME | NOT_BUSY));
   SC_TRY(batch_params_check(c, p, "sc_register_batch"));
-  if (const char* what = batch_offsets_error(offset, n_problems)) { c->last_error = what; return SC_EINVAL; }
+  if (const char* what = batch_offsets_error(offset, n_problems)) { c->last_error = std::string("sc_register_batch: ") + what; return SC_EINVAL; }
   return SC_OK;
 }
 
@@ -65,6 +53,17 @@ int batch_params_check(sc_ctx* c, const sc_params* p, const char* who) {
     return SC_EINVAL;
   }
   return SC_OK;
+}
+
+const char* batch_offsets_error(const uint32_t* offset, uint32_t n_problems) {
+  if (n_problems == 0) return "n_problems == 0";
+  for (uint32_t b = 0; b < n_problems; b++) {
+    if (offset[b + 1] < offset[b]) return "offsets decrease";
+    const uint32_t nb = offset[b + 1] - offset[b];
+    if (nb < 3 || nb > SC_BATCH_MAX_N) return "a problem has fewer than 3 or more than SC_BATCH_MAX_N correspondences";
+  }
+  if (offset[n_problems] > (1u << 31)) return "more than 2^31 correspondences in all";
+  return nullptr;
 }
 
 int batch_staging_begin(sc_ctx* c, size_t bytes) {

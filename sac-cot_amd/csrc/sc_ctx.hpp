@@ -113,7 +113,10 @@ struct Workspace {
       // problem, then the column minima; gsrc / gtgt: the gathered points, slot-positioned; the rest: device copies of the host
       // entries' arrays
       mbatch_meta, mbatch_top, mbatch_words, mbatch_gsrc, mbatch_gtgt, mbatch_fsrc, mbatch_ftgt, mbatch_psrc, mbatch_ptgt, mbatch_corr,
-      mbatch_d2, mbatch_count, mbatch_res, mbatch_mask;
+      mbatch_d2, mbatch_count, mbatch_res, mbatch_mask,
+      // sc_polish_batch: allocated by the first such call, never by a frame or by another batch entry.  off: the copy of the caller's
+      // offsets (the slot form: both arrays and the slot starts); the rest: device copies of the host entry's arrays
+      pbatch_off, pbatch_src, pbatch_tgt, pbatch_res, pbatch_pol, pbatch_mask;
 };
 constexpr size_t N_WORKSPACE_BUFS = sizeof(Workspace) / sizeof(Buf);
 static_assert(std::is_standard_layout<Workspace>::value && alignof(Workspace) == alignof(Buf) && sizeof(Workspace) == N_WORKSPACE_BUFS * sizeof(Buf),
@@ -228,6 +231,9 @@ int outputs_to_host(sc_ctx* c, size_t n, float R[9], float t[3], uint8_t* mask);
 int match_check(sc_ctx* c, const sc_match_params* mp, int64_t ns, int64_t nt, MatchJob* job);
 // what a batch entry refuses of sc_params (shard_world != 1, refit, timing, an estimated bound); `who` opens the message
 int batch_params_check(sc_ctx* c, const sc_params* p, const char* who);
+// what a batch entry refuses of the caller's offsets (sizes 3 .. SC_BATCH_MAX_N, nothing decreasing, a total of 2^31 at most): the
+// rule that is broken, for the caller to put its name in front of; nullptr: they are fine
+const char* batch_offsets_error(const uint32_t* offset, uint32_t n_problems);
 // The pinned staging area that host words of a batch call (offsets, maps) pass through on their way to the device.  begin: the area
 // holds `bytes` and the copy out of the call before is done (an event behind that copy — not behind that call's kernel); the caller
 // fills c->h_batch_off; send: area -> dst (enqueued), and the event behind it.

@@ -717,6 +717,41 @@ struct BatchSlotJob {
 void launch_batch_register(const BatchJob& job, hipStream_t st);
 void launch_batch_register_slots(const BatchSlotJob& job, hipStream_t st);
 
+// ---- iterated fp64 refits for a batch's winners (sc_polish_batch; sc_polish_batch.hip) ----------------------
+// One problem's result: sc_polish_batch_result of include/saccot.h, field for field (sc_polish_batch.hip asserts the size).
+struct PolishBatchRecord {
+  float Rt[12];
+  int32_t status;
+  uint32_t score0, score;
+  uint16_t iters, stop;
+};
+// Problem b owns rows [offset[b], offset[b + 1]) of src / tgt and of mask, as in BatchJob; in[b].status and in[b].Rt are the
+// input pose (read, never written), out[b] the result.  thr: tau^2, 1 / tau^2 or 1 / tau by score_mode.  Everything in device memory.
+struct PolishBatchJob {
+  const float* src; const float* tgt;
+  const uint32_t* offset;
+  uint32_t n_problems, total;
+  int soa, score_mode;
+  uint32_t max_iter;
+  float tau2, thr;
+  const BatchRecord* in;
+  PolishBatchRecord* out;
+  uint8_t* mask;
+};
+// The slot form (behind sc_register_batch_features): job.src / job.tgt are the problems' POINTS (job.offset = src_off, job.total =
+// total_s; tgt_off, total_t for the other side), and correspondence m of problem b is (src point corr[2 (slot[b] + m)], tgt point
+// corr[2 (slot[b] + m) + 1]), indices local to the problem, m < count[2b]; count[2b + 1] != 0: the match flagged the problem.
+// Mask bytes at slot[b] + m.  A type of its own, so that the plain form's kernel argument and code do not depend on it.
+struct PolishBatchSlotJob {
+  PolishBatchJob job;
+  const uint32_t* tgt_off; const uint32_t* slot;
+  const int32_t* corr; const uint32_t* count;
+  uint32_t knn, total_t;
+};
+// One workgroup per problem, every refit inside the launch; every record and mask range is written (complete in stream order).
+void launch_polish_batch(const PolishBatchJob& job, hipStream_t st);
+void launch_polish_batch_slots(const PolishBatchSlotJob& job, hipStream_t st);
+
 // ---- descriptor matching for a batch of small problems (sc_match_batch; sc_match_batch.hip) -----------------
 // Problem b owns rows [src_off[b], src_off[b + 1]) of fsrc and [tgt_off[b], tgt_off[b + 1]) of ftgt (1 .. MATCH_BATCH_MAX_N rows
 // each, checked by the caller) and the output slot that starts at entry slot[b] = src_off[b] * knn.  tile_map: n_tiles pairs
