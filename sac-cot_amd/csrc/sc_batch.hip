@@ -5,7 +5,8 @@
 // (ceil(n / 64) u64 per row, 32 KB at most), the degrees — and every stage of sc_register runs on it with the canonical device
 // code of sc_arith.hpp and the order of sc_winner.hpp, so a problem's record equals what sc_register returns for it alone:
 //
-//   staging   either layout -> the planes, the finiteness test on the way (a non-finite coordinate: SC_EINVAL for THIS problem)
+//   staging   either layout -> the planes, the finiteness test on the way (a non-finite coordinate: SC_EINVAL for THIS problem);
+//             this, and how a record and a zero mask are written, is sc_batch_frame.hpp's, shared with sc_polish_batch.hip
 //   stage A   a wave per (row, 64 columns): one pair test per lane (pair_weight on dist3), the wave's ballot IS the bit word; degrees
 //             by popcount.  No dense S: an edge weight is recomputed from the points where a key needs it (the same bits).
 //   stage B   no list.  The triangles i < j < k are ENUMERATED (TriIter: bits_i & bits_j above j), as often as a step needs them:
@@ -23,8 +24,8 @@
 // static deal would leave most lanes waiting for a few.  Cost: (triangles of the graph) x (passes: 3 .. 10) + (kept triangles) x n.
 #include "../../include/saccot.h"
 #include "sc_arith.hpp"
+#include "sc_batch_frame.hpp"
 #include "sc_block.hpp"
-#include "sc_kernels.hpp"
 #include "sc_winner.hpp"
 
 namespace sc {
@@ -147,26 +148,15 @@ __device__ __forceinline__ void find_cut(BatchLds& L, uint32_t need, uint32_t& i
 // the record and nothing else: identity unless Rt is given
 __device__ __forceinline__ void record_fill(BatchLds& L, const float* Rt, int status, uint32_t n, uint32_t edges, uint32_t kept,
                                             uint32_t total, uint32_t rank, uint32_t count) {
-#pragma unroll
-  for (int c = 0; c < 12; c++) L.rec[c] = __float_as_uint(Rt ? Rt[c] : ((c == 0 || c == 4 || c == 8) ? 1.f : 0.f));
+  record_pose(L.rec, Rt);
   L.rec[12] = (uint32_t)status; L.rec[13] = n; L.rec[14] = edges; L.rec[15] = kept;
   L.rec[16] = total; L.rec[17] = 0u;  // tri_total, u64: at most C(512, 3)
   L.rec[18] = rank; L.rec[19] = count;
-}
-// one dword of the record per lane (the barrier publishes what one thread filled)
-__device__ __forceinline__ void record_store(BatchLds& L, BatchRecord* res) {
-  __syncthreads();
-  if (threadIdx.x < REC_WORDS) reinterpret_cast<uint32_t*>(res + blockIdx.x)[threadIdx.x] = L.rec[threadIdx.x];
-}
-__device__ __forceinline__ void mask_zero(uint8_t* mask, int n) {
-  for (int m = threadIdx.x; m < n; m += BT) mask[m] = 0;
 }
 
 // The kernel's argument is BatchJob (sc_register_batch) or BatchSlotJob (sc_register_batch_features: the problems sit in slots and
 // `count` says how much of each is filled, sc_kernels.hpp).  The plain instantiation is the kernel of sc_register_batch with the
 // kernel argument it always had: COUNTED is a constant of the instantiation, and nothing of the slot form is compiled into it.
-__device__ __forceinline__ const BatchJob& job_of(const BatchJob& a) { return a; }
-__device__ __forceinline__ const BatchJob& job_of(const BatchSlotJob& a) { return a.job; }
 __device__ __forceinline__ const uint32_t* count_of(const BatchJob&) { return nullptr; }
 __device__ __forceinline__ const uint32_t* count_of(const BatchSlotJob& a) { return a.count; }
 
@@ -185,9 +175,9 @@ __global__ __launch_bounds__(BT) void batch_register_kernel(const Arg arg) {
   if (COUNTED) {  // what the host refuses for the plain form, it cannot know here: the match decided it on the device
     const bool flagged = count[2 * blockIdx.x + 1] != 0u;
     if (flagged || n < 3 || n > BN) {  // (n > BN cannot happen: a slot's capacity is at most BN)
-      if (!flagged && n < 3) mask_zero(mask, n);
+      if (!flagged && n < 3) mask_zero<BT>(mask, n);
       if (tid == 0) record_fill(L, nullptr, (flagged || n > BN) ? SC_EINVAL : SC_ENOHYP, flagged ? 0u : (uint32_t)n, 0u, 0u, 0u, 0u, 0u);
-      record_store(L, job.res);
+      record_store(L.rec, job.res);
       return;
     }
   }
@@ -195,24 +185,12 @@ __global__ __launch_bounds__(BT) void batch_register_kernel(const Arg arg) {
   // ---- staging: either layout -> planes; a non-finite coordinate ends this problem
   if (tid == 0) L.bad = 0u;
   __syncthreads();
-  {
-    bool bad = false;
-    for (int x = tid; x < 3 * n; x += BT) {
-      int c, m;
-      size_t g;
-      if (job.soa) { c = x / n; m = x - c * n; g = (size_t)c * job.total + off + m; }
-      else { m = x / 3; c = x - 3 * m; g = (size_t)off * 3 + x; }
-      const float p = job.src[g], q = job.tgt[g];
-      bad = bad || !(fabsf(p) < __builtin_inff()) || !(fabsf(q) < __builtin_inff());
-      L.pt[c][m] = p; L.pt[3 + c][m] = q;
-    }
-    if (bad) L.bad = 1u;
-  }
+  if (stage_planes<BT>(L.pt, job.src, job.tgt, job.soa, job.total, off, n)) L.bad = 1u;
   __syncthreads();
   if (L.bad) {
-    mask_zero(mask, n);
+    mask_zero<BT>(mask, n);
     if (tid == 0) record_fill(L, nullptr, SC_EINVAL, (uint32_t)n, 0u, 0u, 0u, 0u, 0u);
-    record_store(L, job.res);
+    record_store(L.rec, job.res);
     return;
   }
 
@@ -257,9 +235,9 @@ __global__ __launch_bounds__(BT) void batch_register_kernel(const Arg arg) {
   }
   const uint32_t kept_n = job.T < total ? job.T : total;
   if (total == 0u) {
-    mask_zero(mask, n);
+    mask_zero<BT>(mask, n);
     if (tid == 0) record_fill(L, nullptr, SC_ENOHYP, (uint32_t)n, edges, 0u, 0u, 0u, 0u);
-    record_store(L, job.res);
+    record_store(L.rec, job.res);
     return;
   }
 
@@ -347,7 +325,7 @@ __global__ __launch_bounds__(BT) void batch_register_kernel(const Arg arg) {
   }
 
   // ---- stages C1 + C2: every kept triangle solved and scored; the winner by (score, key, lowest (i, j, k))
-  const float thr = job.score_mode == SC_SCORE_MSE ? dv.inv_tau2 : (job.score_mode == SC_SCORE_MAE ? dv.inv_tau : dv.tau2);
+  const float thr = score_thr(dv, job.score_mode);
   unsigned long long k0 = 0ull, k1 = 0ull;
   {
     pass_begin(L, 0u);
@@ -389,9 +367,9 @@ __global__ __launch_bounds__(BT) void batch_register_kernel(const Arg arg) {
     block_lexmax_u64(k0, k1, reinterpret_cast<unsigned long long*>(L.red));
   }
   if (k0 == 0ull) {  // no hypothesis has an inlier
-    mask_zero(mask, n);
+    mask_zero<BT>(mask, n);
     if (tid == 0) record_fill(L, nullptr, SC_ENOHYP, (uint32_t)n, edges, kept_n, total, 0u, 0u);
-    record_store(L, job.res);
+    record_store(L.rec, job.res);
     return;
   }
 
@@ -421,7 +399,7 @@ __global__ __launch_bounds__(BT) void batch_register_kernel(const Arg arg) {
   }
   for (int m = tid; m < n; m += BT) mask[m] = is_inlier(M, load_corr(&L.pt[0][0], BN, m), dv.tau2) ? 1 : 0;
   if (tid == 0) record_fill(L, M, SC_OK, (uint32_t)n, edges, kept_n, total, rank, (uint32_t)(k0 >> 32));
-  record_store(L, job.res);
+  record_store(L.rec, job.res);
 }
 
 }  // namespace

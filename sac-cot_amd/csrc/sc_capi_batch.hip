@@ -1,5 +1,7 @@
 // sc_capi_batch.hip — the C ABI's batched registration (include/saccot.h, sc_register_batch): sc_register_batch_device and
-// sc_register_batch.  Host-only, on the context and the helpers of sc_ctx.hpp; the kernel is sc_batch.hip's.
+// sc_register_batch.  Host-only, on the context and the helpers of sc_ctx.hpp; the kernel is sc_batch.hip's.  What every batch
+// entry shares on the host is defined here as well: batch_params_check, batch_offsets_error, the pinned staging area
+// (batch_staging_begin / _send) and batch_offsets_to_device.
 //
 // offsets -> pinned staging -> device copy (enqueued) -> ONE launch, a workgroup per problem.  Nothing is read back: a problem's
 // status is a field of its record.  Everything that can refuse the call is decided on the host before anything is enqueued.
@@ -14,22 +16,13 @@ constexpr uint32_t BATCH_FLAGS_IGNORED = SC_FLAG_NO_DENSE_S | SC_FLAG_NO_PRUNE |
 int batch_check(sc_ctx* c, const uint32_t* offset, uint32_t n_problems, const sc_params* p) {
   SC_TRY(entry_checks(c, nullptr, ENDS_FRAME | NOT_BUSY));
   SC_TRY(batch_params_check(c, p, "sc_register_batch"));
-  if (const char* what = batch_offsets_error(offset, n_problems)) { c->last_error = std::string("sc_register_batch: ") + what; return SC_EINVAL; }
+  if (const char* what = batch_offsets_error(offset, n_problems)) return refuse(c, "sc_register_batch", what);
   return SC_OK;
-}
-
-// offset -> the pinned staging area -> batch_off (enqueued)
-int batch_offsets_to_device(sc_ctx* c, const uint32_t* offset, uint32_t n_problems) {
-  const size_t bytes = ((size_t)n_problems + 1) * 4;
-  ENSURE(c, c->batch_off, bytes);
-  SC_TRY(batch_staging_begin(c, bytes));
-  memcpy(c->h_batch_off, offset, bytes);
-  return batch_staging_send(c, c->batch_off, bytes);
 }
 
 int batch_enqueue(sc_ctx* c, const float* d_src, const float* d_tgt, const uint32_t* offset, uint32_t n_problems, const sc_params* p,
                   sc_batch_result* d_res, uint8_t* d_mask) {
-  SC_TRY(batch_offsets_to_device(c, offset, n_problems));
+  SC_TRY(batch_offsets_to_device(c, offset, n_problems, c->batch_off));
   BatchJob job{};
   job.src = d_src; job.tgt = d_tgt; job.offset = c->batch_off.as<uint32_t>();
   job.n_problems = n_problems; job.total = offset[n_problems];
@@ -46,12 +39,10 @@ int batch_enqueue(sc_ctx* c, const float* d_src, const float* d_tgt, const uint3
 namespace sc {
 
 int batch_params_check(sc_ctx* c, const sc_params* p, const char* who) {
-  if (check_params(p) != SC_OK) { c->last_error = std::string(who) + ": bad sc_params (size, a range, or a mode)"; return SC_EINVAL; }
-  if (p->shard_world != 1) { c->last_error = std::string(who) + ": shard_world must be 1"; return SC_EINVAL; }
-  if (p->flags & ~BATCH_FLAGS_IGNORED) {
-    c->last_error = std::string(who) + ": only SC_FLAG_NO_DENSE_S, SC_FLAG_NO_PRUNE and SC_FLAG_EXACT_TOTAL are accepted (no refit, no timing, no estimated bound in a batch)";
-    return SC_EINVAL;
-  }
+  if (check_params(p) != SC_OK) return refuse(c, who, "bad sc_params (size, a range, or a mode)");
+  if (p->shard_world != 1) return refuse(c, who, "shard_world must be 1");
+  if (p->flags & ~BATCH_FLAGS_IGNORED)
+    return refuse(c, who, "only SC_FLAG_NO_DENSE_S, SC_FLAG_NO_PRUNE and SC_FLAG_EXACT_TOTAL are accepted (no refit, no timing, no estimated bound in a batch)");
   return SC_OK;
 }
 
@@ -86,6 +77,14 @@ int batch_staging_send(sc_ctx* c, Buf& dst, size_t bytes) {
   return SC_OK;
 }
 
+int batch_offsets_to_device(sc_ctx* c, const uint32_t* offset, uint32_t n_problems, Buf& dst) {
+  const size_t bytes = ((size_t)n_problems + 1) * 4;
+  ENSURE(c, dst, bytes);
+  SC_TRY(batch_staging_begin(c, bytes));
+  memcpy(c->h_batch_off, offset, bytes);
+  return batch_staging_send(c, dst, bytes);
+}
+
 }  // namespace sc
 
 extern "C" {
@@ -93,7 +92,7 @@ extern "C" {
 int sc_register_batch_device(sc_ctx* c, const float* d_src, const float* d_tgt, const uint32_t* offset, uint32_t n_problems,
                              const sc_params* p, sc_batch_result* d_res, uint8_t* d_mask) {
   if (!c) return SC_EINVAL;
-  if (!d_src || !d_tgt || !offset || !p || !d_res || !d_mask) { c->last_error = "sc_register_batch_device: a NULL argument"; return SC_EINVAL; }
+  if (!d_src || !d_tgt || !offset || !p || !d_res || !d_mask) return refuse(c, "sc_register_batch_device", "a NULL argument");
   SC_TRY(batch_check(c, offset, n_problems, p));
   HIPCHK(c, hipSetDevice(c->device));
   c->cap_bytes = workspace_cap(p);
@@ -103,7 +102,7 @@ int sc_register_batch_device(sc_ctx* c, const float* d_src, const float* d_tgt, 
 int sc_register_batch(sc_ctx* c, const float* src, const float* tgt, const uint32_t* offset, uint32_t n_problems, const sc_params* p,
                       sc_batch_result* res, uint8_t* mask) {
   if (!c) return SC_EINVAL;
-  if (!src || !tgt || !offset || !p || !res || !mask) { c->last_error = "sc_register_batch: a NULL argument"; return SC_EINVAL; }
+  if (!src || !tgt || !offset || !p || !res || !mask) return refuse(c, "sc_register_batch", "a NULL argument");
   SC_TRY(batch_check(c, offset, n_problems, p));
   HIPCHK(c, hipSetDevice(c->device));
   c->cap_bytes = workspace_cap(p);

@@ -2,10 +2,11 @@
 // sc_match_batch, sc_register_batch_features_device and sc_register_batch_features.  Host-only, on the context and the helpers of
 // sc_ctx.hpp; the kernels are sc_match_batch.hip's and sc_batch.hip's.
 //
-// both offset arrays, the slot starts and the tile map -> pinned staging -> ONE device copy (enqueued) -> memset (a "clean" word per
-// problem and, for SC_MATCH_MUTUAL, the column minima: all ones) -> distance + select -> finish [-> sc_batch.hip's kernel on the
-// slots]: four or five stream operations whatever the batch, and nothing is read back — a problem's count, its non-finite flag and
-// its status are words in device memory.  Everything that can refuse the call is decided on the host before anything is enqueued.
+// both offset arrays and the slot starts (batch_slot_meta, shared with sc_polish_batch_slots_device), then the tile map -> pinned
+// staging -> ONE device copy (enqueued) -> memset (a "clean" word per problem and, for SC_MATCH_MUTUAL, the column minima: all
+// ones) -> distance + select -> finish [-> sc_batch.hip's kernel on the slots]: four or five stream operations whatever the batch,
+// and nothing is read back — a problem's count, its non-finite flag and its status are words in device memory.  Everything that can
+// refuse the call is decided on the host before anything is enqueued.
 #include "sc_ctx.hpp"
 #include "sc_match_batch_check.hpp"
 
@@ -53,9 +54,7 @@ int mbatch_enqueue(sc_ctx* c, const MatchJob& mj, const Sizes& sz, const float* 
   const size_t nb1 = (size_t)sz.n_problems + 1, meta_bytes = (3 * nb1 + 2 * (size_t)sz.n_tiles) * 4;
   SC_TRY(batch_staging_begin(c, meta_bytes));
   uint32_t* h = static_cast<uint32_t*>(c->h_batch_off);
-  memcpy(h, src_off, nb1 * 4);
-  memcpy(h + nb1, tgt_off, nb1 * 4);
-  for (size_t b = 0; b < nb1; b++) h[2 * nb1 + b] = (uint32_t)((uint64_t)src_off[b] * mj.knn);  // (at most 2^31: checked)
+  batch_slot_meta(src_off, tgt_off, sz.n_problems, mj.knn, h);
   match_batch_tile_map(src_off, sz.n_problems, MATCH_BATCH_ROWS, h + 3 * nb1);
   SC_TRY(batch_staging_send(c, c->mbatch_meta, meta_bytes));
   const size_t clean_bytes = (nb1 / 2) * 8, words_bytes = clean_bytes + (mj.mutual ? sz.total_t * 8 : 0);
@@ -105,7 +104,7 @@ extern "C" {
 int sc_match_batch_device(sc_ctx* c, const float* d_fsrc, const uint32_t* src_off, const float* d_ftgt, const uint32_t* tgt_off,
                           uint32_t n_problems, const sc_match_params* mp, int32_t* d_corr, float* d_d2, uint32_t* d_count) {
   if (!c) return SC_EINVAL;
-  if (!d_fsrc || !src_off || !d_ftgt || !tgt_off || !mp || !d_corr || !d_d2 || !d_count) { c->last_error = "sc_match_batch_device: a NULL argument"; return SC_EINVAL; }
+  if (!d_fsrc || !src_off || !d_ftgt || !tgt_off || !mp || !d_corr || !d_d2 || !d_count) return refuse(c, "sc_match_batch_device", "a NULL argument");
   MatchJob mj{};
   Sizes sz{};
   SC_TRY(mbatch_check(c, src_off, tgt_off, n_problems, mp, nullptr, false, &mj, &sz));
@@ -117,7 +116,7 @@ int sc_match_batch_device(sc_ctx* c, const float* d_fsrc, const uint32_t* src_of
 int sc_match_batch(sc_ctx* c, const float* fsrc, const uint32_t* src_off, const float* ftgt, const uint32_t* tgt_off, uint32_t n_problems,
                    const sc_match_params* mp, int32_t* corr, float* d2, uint32_t* count) {
   if (!c) return SC_EINVAL;
-  if (!fsrc || !src_off || !ftgt || !tgt_off || !mp || !corr || !d2 || !count) { c->last_error = "sc_match_batch: a NULL argument"; return SC_EINVAL; }
+  if (!fsrc || !src_off || !ftgt || !tgt_off || !mp || !corr || !d2 || !count) return refuse(c, "sc_match_batch", "a NULL argument");
   MatchJob mj{};
   Sizes sz{};
   SC_TRY(mbatch_check(c, src_off, tgt_off, n_problems, mp, nullptr, false, &mj, &sz));
@@ -146,10 +145,8 @@ int sc_register_batch_features_device(sc_ctx* c, const float* d_src_pts, const f
                                       const sc_match_params* mp, const sc_params* p, sc_batch_result* d_res, int32_t* d_corr, float* d_d2,
                                       uint32_t* d_count, uint8_t* d_mask) {
   if (!c) return SC_EINVAL;
-  if (!d_src_pts || !d_fsrc || !src_off || !d_tgt_pts || !d_ftgt || !tgt_off || !mp || !p || !d_res || !d_corr || !d_d2 || !d_count || !d_mask) {
-    c->last_error = "sc_register_batch_features_device: a NULL argument";
-    return SC_EINVAL;
-  }
+  if (!d_src_pts || !d_fsrc || !src_off || !d_tgt_pts || !d_ftgt || !tgt_off || !mp || !p || !d_res || !d_corr || !d_d2 || !d_count || !d_mask)
+    return refuse(c, "sc_register_batch_features_device", "a NULL argument");
   MatchJob mj{};
   Sizes sz{};
   SC_TRY(mbatch_check(c, src_off, tgt_off, n_problems, mp, p, true, &mj, &sz));
@@ -164,10 +161,8 @@ int sc_register_batch_features(sc_ctx* c, const float* src_pts, const float* fsr
                                const float* ftgt, const uint32_t* tgt_off, uint32_t n_problems, const sc_match_params* mp,
                                const sc_params* p, sc_batch_result* res, int32_t* corr, float* d2, uint32_t* count, uint8_t* mask) {
   if (!c) return SC_EINVAL;
-  if (!src_pts || !fsrc || !src_off || !tgt_pts || !ftgt || !tgt_off || !mp || !p || !res || !corr || !d2 || !count || !mask) {
-    c->last_error = "sc_register_batch_features: a NULL argument";
-    return SC_EINVAL;
-  }
+  if (!src_pts || !fsrc || !src_off || !tgt_pts || !ftgt || !tgt_off || !mp || !p || !res || !corr || !d2 || !count || !mask)
+    return refuse(c, "sc_register_batch_features", "a NULL argument");
   MatchJob mj{};
   Sizes sz{};
   SC_TRY(mbatch_check(c, src_off, tgt_off, n_problems, mp, p, true, &mj, &sz));

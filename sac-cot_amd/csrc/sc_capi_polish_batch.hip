@@ -2,20 +2,16 @@
 // sc_polish_batch_device, sc_polish_batch and sc_polish_batch_slots_device.  Host-only, on the context and the helpers of sc_ctx.hpp;
 // the kernel is sc_polish_batch.hip's.
 //
-// offsets -> pinned staging (the area and event every batch entry shares) -> device copy (enqueued) -> ONE launch, a workgroup per
-// problem.  Nothing is read back: a problem's status is a field of its record.  Everything that can refuse the call is decided on the
-// host before anything is enqueued.
+// offsets -> pinned staging (the area and event every batch entry shares: batch_offsets_to_device; the slot form's three arrays:
+// batch_slot_meta, as sc_capi_match_batch.hip writes them) -> device copy (enqueued) -> ONE launch, a workgroup per problem.
+// Nothing is read back: a problem's status is a field of its record.  Everything that can refuse the call is decided on the host
+// before anything is enqueued.
 #include "sc_ctx.hpp"
 #include "sc_match_batch_check.hpp"
 
 using namespace sc;
 
 namespace {
-
-int refuse(sc_ctx* c, const char* who, const char* what) {
-  c->last_error = std::string(who) + ": " + what;
-  return SC_EINVAL;
-}
 
 // sc_polish_params as a batch takes them: one candidate per problem
 int pbatch_pparams_check(sc_ctx* c, const sc_polish_params* pp, const char* who) {
@@ -40,17 +36,13 @@ PolishBatchJob job_of(const sc_params* p, const sc_polish_params* pp) {
   PolishBatchJob job{};
   job.soa = p->layout == SC_SOA; job.score_mode = p->score_mode; job.max_iter = pp->max_iter;
   job.tau2 = dv.tau2;
-  job.thr = p->score_mode == SC_SCORE_MSE ? dv.inv_tau2 : (p->score_mode == SC_SCORE_MAE ? dv.inv_tau : dv.tau2);
+  job.thr = score_thr(dv, p->score_mode);
   return job;
 }
 
 int pbatch_enqueue(sc_ctx* c, const float* d_src, const float* d_tgt, const uint32_t* offset, uint32_t n_problems, const sc_params* p,
                    const sc_polish_params* pp, const sc_batch_result* d_res, sc_polish_batch_result* d_pol, uint8_t* d_mask) {
-  const size_t bytes = ((size_t)n_problems + 1) * 4;
-  ENSURE(c, c->pbatch_off, bytes);
-  SC_TRY(batch_staging_begin(c, bytes));
-  memcpy(c->h_batch_off, offset, bytes);
-  SC_TRY(batch_staging_send(c, c->pbatch_off, bytes));
+  SC_TRY(batch_offsets_to_device(c, offset, n_problems, c->pbatch_off));
   PolishBatchJob job = job_of(p, pp);
   job.src = d_src; job.tgt = d_tgt; job.offset = c->pbatch_off.as<uint32_t>();
   job.n_problems = n_problems; job.total = offset[n_problems];
@@ -119,10 +111,7 @@ int sc_polish_batch_slots_device(sc_ctx* c, const float* d_src_pts, const uint32
   const size_t nb1 = (size_t)n_problems + 1, bytes = 3 * nb1 * 4;
   ENSURE(c, c->pbatch_off, bytes);
   SC_TRY(batch_staging_begin(c, bytes));
-  uint32_t* h = static_cast<uint32_t*>(c->h_batch_off);
-  memcpy(h, src_off, nb1 * 4);
-  memcpy(h + nb1, tgt_off, nb1 * 4);
-  for (size_t b = 0; b < nb1; b++) h[2 * nb1 + b] = (uint32_t)((uint64_t)src_off[b] * knn);  // (at most 2^31: checked)
+  batch_slot_meta(src_off, tgt_off, n_problems, knn, static_cast<uint32_t*>(c->h_batch_off));
   SC_TRY(batch_staging_send(c, c->pbatch_off, bytes));
   const uint32_t* meta = c->pbatch_off.as<uint32_t>();
   PolishBatchSlotJob slots{};

@@ -208,6 +208,11 @@ float ev_us(sc_ctx* c, int a, int b);
 constexpr uint64_t PIN_PENDING = ~0ull;  // a host word whose kernel has not delivered yet (wait_word polls it)
 inline void arm_word(sc_ctx* c, HostWord w) { c->pinned[w] = PIN_PENDING; }
 int wait_word(sc_ctx* c, HostWord idx);
+// "who: what" into last_error; the status of a refused call
+inline int refuse(sc_ctx* c, const char* who, const char* what) {
+  c->last_error = std::string(who) + ": " + what;
+  return SC_EINVAL;
+}
 // an sc_register_device_async / sc_finalize_gathered_device_async call is outstanding on this context
 inline int busy(sc_ctx* c) { return c->frame.pending ? (c->last_error = "a call is outstanding on this context (sc_wait first)", SC_EINVAL) : SC_OK; }
 // Any computing entry other than sc_peel* ends the frame the context may hold (include/saccot.h, sc_peel)
@@ -239,6 +244,8 @@ const char* batch_offsets_error(const uint32_t* offset, uint32_t n_problems);
 // fills c->h_batch_off; send: area -> dst (enqueued), and the event behind it.
 int batch_staging_begin(sc_ctx* c, size_t bytes);
 int batch_staging_send(sc_ctx* c, Buf& dst, size_t bytes);
+// the caller's offsets (n_problems + 1 words) through that area into dst (enqueued)
+int batch_offsets_to_device(sc_ctx* c, const uint32_t* offset, uint32_t n_problems, Buf& dst);
 
 // ---- a call on a scored frame (sc_peel, sc_polish): what the two share in front of their launches and behind them
 // The entry checks, `busy` first, then "is there a frame"; the refusal names the caller.  Then the context's device.

@@ -6,6 +6,8 @@
 #include <stdint.h>
 #include <vector>
 
+#include "../../include/saccot.h"
+
 namespace sc {
 
 std::vector<uint32_t> compat_wg_map(int W);  // sc_compat.hip: which 64 x 64 block workgroup b of stage A takes (XCD-aware)
@@ -19,6 +21,11 @@ struct Derived {
   float inv_tau2;      // 1 / tau^2   (score modes MSE / MAE, include/saccot.h)
   float inv_tau;       // 1 / tau
 };
+// what score_term compares against (`thr` of the scoring kernels): tau^2, 1 / tau^2 or 1 / tau by score_mode
+__host__ __device__ __forceinline__ float score_thr(const Derived& dv, int score_mode) {
+  const float inv_tau2 = dv.inv_tau2, inv_tau = dv.inv_tau, tau2 = dv.tau2;  // (read first: a choice among values, not among addresses)
+  return score_mode == SC_SCORE_MSE ? inv_tau2 : (score_mode == SC_SCORE_MAE ? inv_tau : tau2);
+}
 
 // Scheduling / fallback knobs of the kernels.  The shipped library reads NO environment variable: these defaults are
 // what runs, and only sc_set_debug() (include/saccot.h, test and tuning hook) changes them, per context.  None of them

@@ -4,6 +4,7 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "../../include/saccot.h"
 
@@ -25,6 +26,15 @@ inline const char* match_batch_offsets_error(const uint32_t* src_off, const uint
   }
   if ((uint64_t)src_off[n_problems] * knn > (1ull << 31)) return "sc_match_batch: more than 2^31 output entries (total_s * knn)";
   return nullptr;
+}
+
+// The slot metadata of n_problems problems, 3 (n_problems + 1) words into meta: src_off | tgt_off | the slot starts src_off * knn
+// (at most 2^31: checked above).
+inline void batch_slot_meta(const uint32_t* src_off, const uint32_t* tgt_off, uint32_t n_problems, uint32_t knn, uint32_t* meta) {
+  const size_t nb1 = (size_t)n_problems + 1;
+  memcpy(meta, src_off, nb1 * 4);
+  memcpy(meta + nb1, tgt_off, nb1 * 4);
+  for (size_t b = 0; b < nb1; b++) meta[2 * nb1 + b] = (uint32_t)((uint64_t)src_off[b] * knn);
 }
 
 // tiles of `rows` source rows, none across two problems (offsets as checked above: every problem has a row)

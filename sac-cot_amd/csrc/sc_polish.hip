@@ -8,20 +8,17 @@
 //                         significant first from the top byte of the largest score, and it stops as soon as the bucket that holds the K-th key holds nothing but keys that
 //                         are taken (typically after the score's bytes and one or two of the key's).  The K are then ordered among
 //                         themselves, and their ranks in the ranked list counted the way the finalize kernel counts its winner's.
-//   polish_kernel         one workgroup per candidate, EVERY iteration inside the launch.  An iteration is the inlier test of the
-//                         current (R, t) — a wave's ballot per chunk of 64, one word in the spare slot of the chunk's sums: no
-//                         n-sized mask — and so_refine's two passes (oracle/saccot_oracle.c) over the set bits.
-//                         The summation ORDER is the canonical one (64 consecutive indices sequentially, then the chunk sums
-//                         sequentially); the lanes are dealt one per (chunk, component): 7 x ceil(n / 64) sums in pass 1, 9 x in
-//                         pass 2, every chain of 64 independent of the others, and one lane per component adds the chunk sums.  The
-//                         solve (sc_refine.hpp: refine_kernel's own) stays one thread.
+//   polish_kernel         one workgroup per candidate, EVERY iteration inside the launch: refit_iterate (sc_refit.hpp, which says
+//                         what an iteration is; sc_polish_batch.hip runs the same function on LDS), here with a chunk's sums and
+//                         its inlier word — in the spare slot of the sums: no n-sized mask — in global scratch.  Then the last
+//                         iterate's score over all n.
 //   polish_winner_kernel  the candidate with the largest polished score, its mask, the records for the caller, the host words.
 #include <cstddef>
 
 #include "sc_arith.hpp"
 #include "sc_block.hpp"
 #include "sc_kernels.hpp"
-#include "sc_refine.hpp"
+#include "sc_refit.hpp"
 #include "sc_winner.hpp"
 
 namespace sc {
@@ -29,7 +26,7 @@ namespace sc {
 namespace {
 
 constexpr int POLISH_THREADS = 1024;
-constexpr int POLISH_BITS_SLOT = 15;  // of a chunk's 16 scratch doubles: its 64 inlier bits (the sums use slots 0 .. 8)
+constexpr int POLISH_CHUNK_DOUBLES = 16, POLISH_BITS_SLOT = 15;  // a chunk's scratch: the sums in [0, 9), its 64 inlier bits in [15]
 
 // ---- select ------------------------------------------------------------------------------------------------------------------
 // The 96-bit key of hypothesis g as three words, most significant first: w[0] = score, w[1] = ranking key, w[2] = ~g.
@@ -188,6 +185,16 @@ __global__ __launch_bounds__(POLISH_THREADS) void polish_select_kernel(const uin
 }
 
 // ---- polish ------------------------------------------------------------------------------------------------------------------
+// refit_iterate's chunk storage (sc_refit.hpp): global scratch, so a block fence publishes a lane's stores before the barrier
+struct PolishScratch {
+  double* base;
+  __device__ __forceinline__ double& sum(int ch, int k) const { return base[(size_t)ch * POLISH_CHUNK_DOUBLES + k]; }
+  __device__ __forceinline__ uint64_t& bits(int ch) const {
+    return reinterpret_cast<uint64_t*>(base)[(size_t)ch * POLISH_CHUNK_DOUBLES + POLISH_BITS_SLOT];
+  }
+  __device__ __forceinline__ void publish() const { __threadfence_block(); }
+};
+
 __global__ __launch_bounds__(POLISH_THREADS) void polish_kernel(const float* __restrict__ planes, int n, int ld, PolishCand* __restrict__ cand,
                                                                 const uint32_t* __restrict__ n_cand, uint32_t max_iter, float tau2,
                                                                 float thr, int score_mode, double* __restrict__ scratch_all) {
@@ -197,97 +204,11 @@ __global__ __launch_bounds__(POLISH_THREADS) void polish_kernel(const float* __r
   __shared__ uint64_t s_red[POLISH_THREADS / 64];
   if (blockIdx.x >= *n_cand) return;  // (uniform)
   const uint32_t tid = threadIdx.x;
-  const int nch = (n + 63) / 64;
-  double* scratch = scratch_all + (size_t)blockIdx.x * (size_t)nch * 16;  // 16 doubles per chunk: the sums in [0, 9), the inlier bits in [15]
-  unsigned long long* bits = reinterpret_cast<unsigned long long*>(scratch);
+  double* scratch = scratch_all + (size_t)blockIdx.x * (size_t)((n + 63) / 64) * POLISH_CHUNK_DOUBLES;
   PolishCand* me = cand + blockIdx.x;
   if (tid < 12) sRt[tid] = me->Rt[tid];
   __syncthreads();
-  uint32_t iters = 0;
-#pragma unroll 1
-  for (uint32_t it = 0; it < max_iter; it++) {
-    float M[12];
-#pragma unroll
-    for (int c = 0; c < 12; c++) M[c] = sRt[c];
-    const bool fin = finite12(M);
-    // the inlier bits of (R, t), one 64-bit word per chunk (a wave's ballot), kept in the spare slot of the chunk's sums
-    for (int ch = (int)(tid >> 6); ch < nch; ch += POLISH_THREADS / 64) {
-      const int m = ch * 64 + (int)(tid & 63u);
-      bool inl = false;
-      if (m < n)
-        inl = fin && within_tau(M, load_corr(planes, ld, m), tau2);
-      const unsigned long long bal = __ballot(inl);
-      if ((tid & 63u) == 0u) bits[(size_t)ch * 16 + POLISH_BITS_SLOT] = bal;
-    }
-    __threadfence_block();
-    __syncthreads();
-    // pass 1: lane = (chunk, component): count, sum p (3), sum q (3) of the chunk's inliers, sequentially in index order
-    for (int64_t w = tid; w < (int64_t)nch * 7; w += POLISH_THREADS) {
-      const int ch = (int)(w / 7), k = (int)(w % 7);
-      const float* __restrict__ own = planes + (size_t)(k ? k - 1 : 0) * ld + (size_t)ch * 64;
-      unsigned long long b = bits[(size_t)ch * 16 + POLISH_BITS_SLOT];
-      double c = 0.0;
-      while (b) {
-        const int j = __builtin_ctzll(b);
-        b &= b - 1ull;
-        c += k ? (double)own[j] : 1.0;
-      }
-      scratch[(size_t)ch * 16 + k] = c;
-    }
-    __threadfence_block();
-    __syncthreads();
-    if (tid < 7) {  // the chunk sums in chunk order, one lane per component
-      double S = 0.0;
-      for (int ch = 0; ch < nch; ch++) S += scratch[(size_t)ch * 16 + tid];
-      sS[tid] = S;
-    }
-    __syncthreads();
-    const double cnt = sS[0];
-    if (cnt < 3.0) break;  // (uniform) the refit is declined: (R, t) stays
-    const double pc[3] = {sS[1] / cnt, sS[2] / cnt, sS[3] / cnt}, qc[3] = {sS[4] / cnt, sS[5] / cnt, sS[6] / cnt};
-    // pass 2: lane = (chunk, entry of H): h = fma(p_r - pc_r, q_c - qc_c, h) over the chunk's inliers
-    for (int64_t w = tid; w < (int64_t)nch * 9; w += POLISH_THREADS) {
-      const int ch = (int)(w / 9), e = (int)(w % 9), r = e / 3, cc = e % 3;
-      const float* __restrict__ pr = planes + (size_t)r * ld + (size_t)ch * 64;
-      const float* __restrict__ qr = planes + (size_t)(3 + cc) * ld + (size_t)ch * 64;
-      const double pcr = r == 0 ? pc[0] : (r == 1 ? pc[1] : pc[2]), qcc = cc == 0 ? qc[0] : (cc == 1 ? qc[1] : qc[2]);
-      unsigned long long b = bits[(size_t)ch * 16 + POLISH_BITS_SLOT];
-      double h = 0.0;
-      while (b) {
-        const int j = __builtin_ctzll(b);
-        b &= b - 1ull;
-        h = __builtin_fma((double)pr[j] - pcr, (double)qr[j] - qcc, h);
-      }
-      scratch[(size_t)ch * 16 + e] = h;
-    }
-    __threadfence_block();
-    __syncthreads();
-    if (tid < 9) {
-      double S = 0.0;
-      for (int ch = 0; ch < nch; ch++) S += scratch[(size_t)ch * 16 + tid];
-      sH[tid] = S;
-    }
-    __syncthreads();
-    if (tid == 0) {
-      double H[9];
-#pragma unroll
-      for (int k = 0; k < 9; k++) H[k] = sH[k];
-      float out[12];
-      uint32_t go = 0u;
-      if (refine_solve(H, pc, qc, out)) {  // (not finite: declined)
-#pragma unroll
-        for (int c = 0; c < 12; c++) go |= (__float_as_uint(out[c]) != __float_as_uint(M[c])) ? 1u : 0u;
-        if (go) {
-#pragma unroll
-          for (int c = 0; c < 12; c++) sRt[c] = out[c];
-        }
-      }
-      s_go = go;
-    }
-    __syncthreads();
-    if (!s_go) break;  // (uniform) declined, or the fixed point: the refit returned the bits it started from
-    iters++;
-  }
+  const uint32_t iters = refit_iterate<POLISH_THREADS>(planes, ld, n, tau2, max_iter, PolishScratch{scratch}, sRt, sS, sH, &s_go).iters;
   // the last iterate's score over all n, in the frame's score mode (a sum of integers: any order)
   float M[12];
 #pragma unroll
@@ -348,7 +269,7 @@ void launch_polish_select(const uint32_t* cnt, const uint32_t* sel_key, uint32_t
   hipLaunchKernelGGL(polish_select_kernel, dim3(1), dim3(POLISH_THREADS), 0, st, cnt, sel_key, T, RtSoA, ld_local, want, cand, n_cand);
 }
 
-size_t polish_scratch_bytes(int n) { return (size_t)((n + 63) / 64) * 16 * sizeof(double); }
+size_t polish_scratch_bytes(int n) { return (size_t)((n + 63) / 64) * POLISH_CHUNK_DOUBLES * sizeof(double); }
 
 void launch_polish(const Points& pts, PolishCand* cand, const uint32_t* n_cand, uint32_t want, uint32_t max_iter, float tau2, float thr,
                    int score_mode, double* scratch, hipStream_t st) {

@@ -2,27 +2,23 @@
 //
 // One workgroup of 256 threads per problem, grid = n_problems, nothing shared between workgroups: no global atomics, no global
 // scratch, no second launch, no host word.  A problem of n <= 512 correspondences lives in LDS — six planes of points (12 KB), the
-// chunk sums (8 chunks x 16 doubles) and the chunks' inlier words — and polish_kernel's iteration (sc_polish.hip) runs on it with the
-// same expressions, so every fp64 chain is the same chain and a problem's record equals what sc_polish(candidates = 1) returns for the
-// same input pose:
+// chunk sums (8 chunks x 16 doubles) and the chunks' inlier words — and the iteration is refit_iterate (sc_refit.hpp), the function
+// polish_kernel (sc_polish.hip) runs on global scratch: one definition of every fp64 chain, so a problem's record equals what
+// sc_polish(candidates = 1) returns for the same input pose:
 //
-//   staging    either layout -> the planes, sc_batch.hip's finiteness test on the way; the slot form gathers through corr while it
-//              stages.  A non-finite coordinate, or a non-finite input (R, t): SC_EINVAL for THIS problem.
+//   staging    either layout -> the planes with the finiteness test on the way (sc_batch_frame.hpp, shared with sc_batch.hip); the
+//              slot form gathers through corr while it stages.  A non-finite coordinate, or a non-finite input (R, t): SC_EINVAL
+//              for THIS problem.
 //   score0     the input pose's score over all n (score_term, a sum of integers).
-//   iteration  the inlier word of a chunk of 64 is a wave's ballot of fin && within_tau; pass 1 (count, sum p, sum q) and pass 2
-//              (H by fma) over the set bits in index order, a lane per (chunk, component): 7 x ceil(n / 64) <= 56 and 9 x <= 72
-//              chains, one round each; one lane per component adds the chunk sums in chunk order; refine_solve on one thread.
-//              Stops when the refit is declined (fewer than 3 inliers, a non-finite result), returns the bits it started from,
-//              or max_iter refits are done.
+//   iteration  refit_iterate on PolishChunks: 7 x ceil(n / 64) <= 56 and 9 x <= 72 chains, one round of the lane deal each.
 //   result     the last iterate's score and mask, and the record, staged in LDS and stored one dword per lane.
 //
 // The iteration is latency-bound (chains of up to 64 dependent fp64 operations), so the workgroup is small and many share a
 // compute unit: DESIGN §5.8a has the LDS table and the occupancy.
 #include "../../include/saccot.h"
-#include "sc_arith.hpp"
+#include "sc_batch_frame.hpp"
 #include "sc_block.hpp"
-#include "sc_kernels.hpp"
-#include "sc_refine.hpp"
+#include "sc_refit.hpp"
 #include "sc_winner.hpp"
 
 namespace sc {
@@ -51,25 +47,19 @@ struct alignas(16) PolishLds {
 };
 static_assert(sizeof(PolishLds) < 16 * 1024, "static LDS: ten workgroups a compute unit");
 
-enum : uint32_t { GO_FIXED = 0u, GO_CHANGED = 1u, GO_DECLINED = 2u };
-
-__device__ __forceinline__ const PolishBatchJob& job_of(const PolishBatchJob& a) { return a; }
-__device__ __forceinline__ const PolishBatchJob& job_of(const PolishBatchSlotJob& a) { return a.job; }
+// refit_iterate's chunk storage (sc_refit.hpp): LDS, which the barrier alone publishes
+struct PolishChunks {
+  PolishLds& L;
+  __device__ __forceinline__ double& sum(int ch, int k) const { return L.sum[ch][k]; }
+  __device__ __forceinline__ uint64_t& bits(int ch) const { return L.bits[ch]; }
+  __device__ __forceinline__ void publish() const {}
+};
 
 // the record and nothing else: identity unless Rt is given
 __device__ __forceinline__ void record_fill(PolishLds& L, const float* Rt, int status, uint32_t score0, uint32_t score, uint32_t iters,
                                             uint32_t stop) {
-#pragma unroll
-  for (int c = 0; c < 12; c++) L.rec[c] = __float_as_uint(Rt ? Rt[c] : ((c == 0 || c == 4 || c == 8) ? 1.f : 0.f));
+  record_pose(L.rec, Rt);
   L.rec[12] = (uint32_t)status; L.rec[13] = score0; L.rec[14] = score; L.rec[15] = iters | (stop << 16);
-}
-// one dword of the record per lane (the barrier publishes what one thread filled)
-__device__ __forceinline__ void record_store(PolishLds& L, PolishBatchRecord* out) {
-  __syncthreads();
-  if (threadIdx.x < REC_WORDS) reinterpret_cast<uint32_t*>(out + blockIdx.x)[threadIdx.x] = L.rec[threadIdx.x];
-}
-__device__ __forceinline__ void mask_zero(uint8_t* mask, int n) {
-  for (int m = threadIdx.x; m < n; m += PT) mask[m] = 0;
 }
 
 // The kernel's argument is PolishBatchJob (sc_polish_batch) or PolishBatchSlotJob (sc_polish_batch_slots_device, sc_kernels.hpp):
@@ -95,9 +85,9 @@ __global__ __launch_bounds__(PT) void polish_batch_kernel(const Arg arg) {
   uint8_t* const mask = job.mask + at;
   const int st_in = job.in[blockIdx.x].status;
   if (st_in != SC_OK || unfit) {  // (uniform) no pose to start from: the input's status is the result's
-    mask_zero(mask, n);
+    mask_zero<PT>(mask, n);
     if (tid == 0) record_fill(L, nullptr, st_in != SC_OK ? st_in : SC_EINVAL, 0u, 0u, 0u, SC_POLISH_STOP_DECLINED);
-    record_store(L, job.out);
+    record_store(L.rec, job.out);
     return;
   }
 
@@ -121,15 +111,7 @@ __global__ __launch_bounds__(PT) void polish_batch_kernel(const Arg arg) {
         }
       }
     } else {
-      for (int x = tid; x < 3 * n; x += PT) {
-        int c, m;
-        size_t g;
-        if (job.soa) { c = x / n; m = x - c * n; g = (size_t)c * job.total + off + m; }
-        else { m = x / 3; c = x - 3 * m; g = (size_t)off * 3 + x; }
-        const float p = job.src[g], q = job.tgt[g];
-        bad = bad || !(fabsf(p) < __builtin_inff()) || !(fabsf(q) < __builtin_inff());
-        L.pt[c][m] = p; L.pt[3 + c][m] = q;
-      }
+      bad = stage_planes<PT>(L.pt, job.src, job.tgt, job.soa, job.total, off, n);
     }
     if (bad) L.bad = 1u;
   }
@@ -138,13 +120,12 @@ __global__ __launch_bounds__(PT) void polish_batch_kernel(const Arg arg) {
 #pragma unroll
   for (int c = 0; c < 12; c++) M[c] = L.Rt[c];
   if (L.bad || !finite12(M)) {  // (uniform)
-    mask_zero(mask, n);
+    mask_zero<PT>(mask, n);
     if (tid == 0) record_fill(L, nullptr, SC_EINVAL, 0u, 0u, 0u, SC_POLISH_STOP_DECLINED);
-    record_store(L, job.out);
+    record_store(L.rec, job.out);
     return;
   }
   const float* const planes = &L.pt[0][0];
-  const int nch = (n + 63) / 64;
 
   // ---- the input pose's score over all n
   uint32_t score0;
@@ -157,93 +138,8 @@ __global__ __launch_bounds__(PT) void polish_batch_kernel(const Arg arg) {
     score0 = (uint32_t)block_reduce_u64(s, L.red);
   }
 
-  // ---- the iteration: polish_kernel's, on LDS
-  uint32_t iters = 0, stop = SC_POLISH_STOP_MAX_ITER;
-#pragma unroll 1
-  for (uint32_t it = 0; it < job.max_iter; it++) {
-#pragma unroll
-    for (int c = 0; c < 12; c++) M[c] = L.Rt[c];
-    const bool fin = finite12(M);
-    // the inlier bits of (R, t), one 64-bit word per chunk (a wave's ballot)
-    for (int ch = tid >> 6; ch < nch; ch += PT / 64) {
-      const int m = ch * 64 + (tid & 63);
-      bool inl = false;
-      if (m < n)
-        inl = fin && within_tau(M, load_corr(planes, PN, m), job.tau2);
-      const unsigned long long bal = __ballot(inl);
-      if ((tid & 63) == 0) L.bits[ch] = bal;
-    }
-    __syncthreads();
-    // pass 1: lane = (chunk, component): count, sum p (3), sum q (3) of the chunk's inliers, sequentially in index order
-    for (int w = tid; w < nch * 7; w += PT) {
-      const int ch = w / 7, k = w % 7;
-      const float* own = planes + (k ? k - 1 : 0) * PN + ch * 64;
-      unsigned long long b = L.bits[ch];
-      double c = 0.0;
-      while (b) {
-        const int j = __builtin_ctzll(b);
-        b &= b - 1ull;
-        c += k ? (double)own[j] : 1.0;
-      }
-      L.sum[ch][k] = c;
-    }
-    __syncthreads();
-    if (tid < 7) {  // the chunk sums in chunk order, one lane per component
-      double S = 0.0;
-      for (int ch = 0; ch < nch; ch++) S += L.sum[ch][tid];
-      L.S[tid] = S;
-    }
-    __syncthreads();
-    const double cnt = L.S[0];
-    if (cnt < 3.0) { stop = SC_POLISH_STOP_DECLINED; break; }  // (uniform) the refit is declined: (R, t) stays
-    const double pc[3] = {L.S[1] / cnt, L.S[2] / cnt, L.S[3] / cnt}, qc[3] = {L.S[4] / cnt, L.S[5] / cnt, L.S[6] / cnt};
-    // pass 2: lane = (chunk, entry of H): h = fma(p_r - pc_r, q_c - qc_c, h) over the chunk's inliers
-    for (int w = tid; w < nch * 9; w += PT) {
-      const int ch = w / 9, e = w % 9, r = e / 3, cc = e % 3;
-      const float* pr = planes + r * PN + ch * 64;
-      const float* qr = planes + (3 + cc) * PN + ch * 64;
-      const double pcr = r == 0 ? pc[0] : (r == 1 ? pc[1] : pc[2]), qcc = cc == 0 ? qc[0] : (cc == 1 ? qc[1] : qc[2]);
-      unsigned long long b = L.bits[ch];
-      double h = 0.0;
-      while (b) {
-        const int j = __builtin_ctzll(b);
-        b &= b - 1ull;
-        h = __builtin_fma((double)pr[j] - pcr, (double)qr[j] - qcc, h);
-      }
-      L.sum[ch][e] = h;
-    }
-    __syncthreads();
-    if (tid < 9) {
-      double S = 0.0;
-      for (int ch = 0; ch < nch; ch++) S += L.sum[ch][tid];
-      L.H[tid] = S;
-    }
-    __syncthreads();
-    if (tid == 0) {
-      double H[9];
-#pragma unroll
-      for (int k = 0; k < 9; k++) H[k] = L.H[k];
-      float out[12];
-      uint32_t go = GO_DECLINED;
-      if (refine_solve(H, pc, qc, out)) {  // (not finite: declined)
-        go = GO_FIXED;
-#pragma unroll
-        for (int c = 0; c < 12; c++) go |= (__float_as_uint(out[c]) != __float_as_uint(M[c])) ? GO_CHANGED : GO_FIXED;
-        if (go) {
-#pragma unroll
-          for (int c = 0; c < 12; c++) L.Rt[c] = out[c];
-        }
-      }
-      L.go = go;
-    }
-    __syncthreads();
-    const uint32_t go = L.go;
-    if (go != GO_CHANGED) {  // (uniform) declined, or the fixed point: the refit returned the bits it started from
-      stop = go == GO_FIXED ? SC_POLISH_STOP_FIXED : SC_POLISH_STOP_DECLINED;
-      break;
-    }
-    iters++;
-  }
+  // ---- the iteration
+  const Refit refit = refit_iterate<PT>(planes, PN, n, job.tau2, job.max_iter, PolishChunks{L}, L.Rt, L.S, L.H, &L.go);
 
   // ---- the last iterate's score over all n (a sum of integers: any order), its mask, the record
 #pragma unroll
@@ -256,8 +152,8 @@ __global__ __launch_bounds__(PT) void polish_batch_kernel(const Arg arg) {
     mask[m] = (fin && within_tau(M, c, job.tau2)) ? 1 : 0;
   }
   const uint32_t score = (uint32_t)block_reduce_u64(s, L.red);
-  if (tid == 0) record_fill(L, M, SC_OK, score0, score, iters, stop);
-  record_store(L, job.out);
+  if (tid == 0) record_fill(L, M, SC_OK, score0, score, refit.iters, refit.stop);
+  record_store(L.rec, job.out);
 }
 
 }  // namespace

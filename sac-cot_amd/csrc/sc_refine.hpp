@@ -1,6 +1,8 @@
-// sc_refine.hpp — the fp64 solve of the least-squares rigid refit, shared by refine_kernel (sc_final.hip: one refit
-// over a given mask) and polish_kernel (sc_polish.hip: refits iterated to a fixed point).  Both kernels sum the centroids and H in
-// the canonical order of oracle/saccot_oracle.c::so_refine; what follows the sums is this one function, run by one thread.
+// sc_refine.hpp — the fp64 solve of the least-squares rigid refit: refine_solve, run by one thread behind the sums
+// of the centroids and H in the canonical order of oracle/saccot_oracle.c::so_refine.  Two callers: refine_kernel (sc_final.hip: one
+// refit over a given n-sized mask, a thread per chunk — its own lane deal) and refit_iterate (sc_refit.hpp: refits iterated to a
+// fixed point, a lane per (chunk, component)), which polish_kernel (sc_polish.hip) and polish_batch_kernel (sc_polish_batch.hip)
+// both instantiate.  Only the solve is shared between the two callers; the iteration around it is shared between the two kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -104,6 +104,21 @@ def test_chunk_edges(pkg, O, reg, n):
     _assert_polish(reg.polish(candidates=8, max_iter=16), _ref(O, f"edge{n}", src, tgt, kw, 8, 16), 8, f"n={n}")
 
 
+def test_the_lane_deal_wraps(pkg, O, reg):
+    """n = 9409: 148 chunks, the last of one element.  The refit deals its sums one lane per (chunk, component) over the 1024 threads of
+    the workgroup, and 7 x 148 = 1036 and 9 x 148 = 1332 both exceed them: the deal's second round runs in both passes (at C1, the
+    largest scene of the other cases, it never does).  C2's extent and tau with an inlier ratio of 0.03 (282 true correspondences,
+    spread over all the chunks) and 300 hypotheses: the reference takes under a second."""
+    cfg = pkg.synth.CONFIGS["C2"]
+    sc = pkg.synth.make_scene(9409, 0.03, cfg.L, cfg.tau, cfg.seed)
+    kw = dict(cfg.params(), max_triangles=300)
+    _frame(reg, pkg, sc.src, sc.tgt, kw)
+    exp = _ref(O, "wrap9409", sc.src, sc.tgt, kw, 2, 16)
+    got = reg.polish(candidates=2, max_iter=16)
+    _assert_polish(got, exp, 2, "n=9409")
+    assert got["n_cand"] == 2 and all(int(c["iters"]) >= 1 for c in got["cand"])  # refits that changed (R, t) went through the deal
+
+
 # ---- 3: one candidate, one refit IS the refit of SC_FLAG_REFINE ---------------------------------------------------------------
 @pytest.mark.parametrize("name", ["C0", "C1"])
 def test_one_refit_of_the_winner_equals_flag_refine(pkg, reg, name):
