@@ -42,6 +42,7 @@ extern "C" {
 #define SC_HAS_BATCH 1   /* this header declares sc_register_batch* (added within 0.10) */
 #define SC_HAS_MATCH_BATCH 1  /* this header declares sc_match_batch* and sc_register_batch_features* (added within 0.10) */
 #define SC_HAS_POLISH_BATCH 1  /* this header declares sc_polish_batch* (added within 0.10) */
+#define SC_HAS_INSTANCES_BATCH 1  /* this header declares sc_register_instances_batch* (added within 0.10) */
 
 /* status codes */
 #define SC_OK        0
@@ -565,6 +566,68 @@ int sc_polish_batch_slots_device(sc_ctx* ctx, const float* d_src_pts, const uint
                                  const uint32_t* tgt_off, uint32_t n_problems, uint32_t knn, const sc_params* params,
                                  const sc_polish_params* pp, const int32_t* d_corr, const uint32_t* d_count,
                                  const sc_batch_result* d_res, sc_polish_batch_result* d_pol, uint8_t* d_mask);
+
+/* ---- several rigid motions per batch problem: sc_register_instances_batch ---------------------------------------------
+ * What sc_register_instances answers for a frame — "which further rigid motions explain the rest?" — for the members of a batch:
+ * a second instance of an object, or a background motion, is the normal case for sc_register_batch's callers.  ONE launch, a
+ * workgroup per problem: it runs the frame exactly as sc_register_batch runs it and then, inside the same workgroup, up to
+ * max_instances - 1 rounds of sc_peel on what the workgroup still holds (the points, the graph, K* and the cut).  No second launch,
+ * no host word, no state in the context.
+ *
+ * Layout: the packed problems of sc_register_batch (d_src, d_tgt, offset a HOST array of n_problems + 1 words, params->layout,
+ * 3 <= n_b <= SC_BATCH_MAX_N).  d_res holds max_instances x n_problems records, MOTION-MAJOR: motion k of problem b is
+ * d_res[k * n_problems + b] — so that ONE PLANE, d_res + k * n_problems, is a valid d_res of sc_polish_batch_device.  d_label: total
+ * int32, positioned like sc_register_batch's mask; d_nfound: n_problems words.  1 <= max_instances <= SC_INSTANCES_BATCH_MAX.
+ *
+ * Semantics, per problem b: sc_register_instances on the problem alone with SC_FLAG_EXACT_TOTAL.
+ *   - Plane 0, d_res[b], is sc_register_batch's record of the problem, bit for bit, whatever min_score is.
+ *   - Motion 0 is found iff plane 0 is SC_OK and its best_count >= min_score.
+ *   - Motion k >= 1 is round k of sc_peel (steps 1 - 5 and 7 of its contract): the alive correspondences are those no earlier motion
+ *     claimed; every KEPT triangle — the frame's selection, K* and the cut as the frame fixed them, triangles whose vertices are
+ *     themselves claimed included — is scored over the alive ones in params->score_mode; the winner by score, then key, then lowest
+ *     (i, j, k); mask_k = alive && the inlier test of the winner's fp32 (R, t).  A round in which every score is 0, or whose winner
+ *     scores < min_score, stops the problem: that motion is not returned.
+ *   - The record of motion k: status SC_OK, Rt the winner's; n, edges, tri_kept, tri_total plane 0's; best_rank the winner's position
+ *     in the ranked list; best_count its score over the alive ones.
+ *   - d_nfound[b] = the number of motions found.
+ *   - Planes k >= max(nfound, 1): R = I, t = 0, the counts plane 0's, best_rank = best_count = 0, status SC_ENOHYP — or plane 0's
+ *     status if that is SC_EINVAL.
+ *   - d_label[offset[b] + m] = the motion that claimed correspondence m, -1 for none; every entry of the problem's range is written.
+ *   - A problem's outputs are a function of its points, the parameters, max_instances and min_score only: not of its position, its
+ *     neighbours, n_problems or the context's history.  A non-finite coordinate is found on the device and ends only its own problem
+ *     (SC_EINVAL in every plane, nfound 0, labels -1).
+ * As with sc_peel this is NOT "run the path again on the rest": a motion none of whose triangles made the frame's top T is not found.
+ *
+ * The features form is sc_register_batch_features_device with rounds: the match, then the kernel on the slots.  d_label holds
+ * total_s * knn entries positioned like that entry's mask: entries [slot[b], slot[b] + n_b) are written, entries past n_b are
+ * unspecified.  A flagged problem and one with n_b < 3 get the records sc_register_batch_features gives them, in every plane, and
+ * nfound 0.
+ *
+ * Errors: the CALL returns SC_EINVAL, decided on the host before anything is enqueued, sc_last_error naming which: everything
+ * sc_register_batch (the features form: sc_register_batch_features) refuses — SC_FLAG_REFINE stays refused —, and max_instances
+ * outside 1 .. SC_INSTANCES_BATCH_MAX.  The device forms enqueue on the context's stream and return without waiting (they may wait
+ * for the previous batch call's copy out of the offset staging area, as the sibling entries do).  All three entries end the frame a
+ * context may hold and leave none.  Workspace: the copy of the offsets (the features form: what sc_register_batch_features_device
+ * holds), plus the host form's device copies of its arrays; allocated by the first such call, counted in workspace_bytes and held
+ * against params->max_workspace (SC_ENOMEM).
+ * Cost: a round is one scoring and one counting enumeration.  The scoring enumeration — (kept triangles) x (alive correspondences)
+ * residuals — is what a frame mostly costs as well, so a round costs up to about a frame: measured, a call that finds two or three
+ * motions costs 2.4 - 2.9 sc_register_batch_device calls.  max_instances and min_score bound it. */
+#define SC_INSTANCES_BATCH_MAX 16u
+/* every buffer but offset in HBM: d_res max_instances x n_problems records, d_label total int32, d_nfound n_problems u32 */
+int sc_register_instances_batch_device(sc_ctx* ctx, const float* d_src, const float* d_tgt, const uint32_t* offset, uint32_t n_problems,
+                                       const sc_params* params, uint32_t max_instances, uint32_t min_score, sc_batch_result* d_res,
+                                       int32_t* d_label, uint32_t* d_nfound);
+/* the same with host arrays; waits */
+int sc_register_instances_batch(sc_ctx* ctx, const float* src, const float* tgt, const uint32_t* offset, uint32_t n_problems,
+                                const sc_params* params, uint32_t max_instances, uint32_t min_score, sc_batch_result* res,
+                                int32_t* label, uint32_t* nfound);
+/* match + instances; d_res max_instances x n_problems records, d_label total_s * knn int32, the rest as sc_register_batch_features_device */
+int sc_register_instances_batch_features_device(sc_ctx* ctx, const float* d_src_pts, const float* d_fsrc, const uint32_t* src_off,
+                                                const float* d_tgt_pts, const float* d_ftgt, const uint32_t* tgt_off,
+                                                uint32_t n_problems, const sc_match_params* mp, const sc_params* params,
+                                                uint32_t max_instances, uint32_t min_score, sc_batch_result* d_res, int32_t* d_corr,
+                                                float* d_d2, uint32_t* d_count, int32_t* d_label, uint32_t* d_nfound);
 
 /* ---- two-phase form for one-process-per-GPU sharding --------------------------------
  * Phase 1: A and B replicated, C1+C2 on this rank's blocks of the top-T list; writes this rank's winner key

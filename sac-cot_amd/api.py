@@ -43,6 +43,7 @@ EXPORTS = ["sc_version", "sc_strerror", "sc_default_params", "sc_create", "sc_de
            "sc_match_default_params", "sc_match_device", "sc_match", "sc_register_features",
            "sc_match_batch", "sc_match_batch_device", "sc_register_batch_features", "sc_register_batch_features_device",
            "sc_polish_batch", "sc_polish_batch_device", "sc_polish_batch_slots_device",
+           "sc_register_instances_batch", "sc_register_instances_batch_device", "sc_register_instances_batch_features_device",
            "sc_hypothesize_device", "sc_finalize_device",
            "sc_hypothesize_begin_device", "sc_hypothesize_end_device", "sc_finalize_gathered_device", "sc_finalize_gathered_device_async",
            "sc_shard_plan_query", "sc_shard_compat_device", "sc_shard_edges_device", "sc_shard_select_device",
@@ -117,6 +118,7 @@ POLISH_BATCH_RESULT_DTYPE = np.dtype([("Rt", np.float32, 12), ("status", np.int3
                                       ("iters", np.uint16), ("stop", np.uint16)])  # sc_polish_batch_result as a numpy record
 SC_POLISH_STOP_FIXED, SC_POLISH_STOP_DECLINED, SC_POLISH_STOP_MAX_ITER = 0, 1, 2
 SC_MATCH_BATCH_MAX_N = 4096  # rows a side of one problem of sc_match_batch
+SC_INSTANCES_BATCH_MAX = 16  # motions per problem of sc_register_instances_batch at most
 
 
 class ScShardPlan(C.Structure):
@@ -225,6 +227,10 @@ def load_library() -> C.CDLL:
     L.sc_polish_batch.argtypes = [vp, f32p, f32p, u32p, C.c_uint32, pp, qp, vp, vp, u8p]
     L.sc_polish_batch_device.argtypes = [vp, vp, vp, u32p, C.c_uint32, pp, qp, vp, vp, vp]
     L.sc_polish_batch_slots_device.argtypes = [vp, vp, u32p, vp, u32p, C.c_uint32, C.c_uint32, pp, qp, vp, vp, vp, vp, vp]
+    L.sc_register_instances_batch.argtypes = [vp, f32p, f32p, u32p, C.c_uint32, pp, C.c_uint32, C.c_uint32, vp, i32p, u32p]
+    L.sc_register_instances_batch_device.argtypes = [vp, vp, vp, u32p, C.c_uint32, pp, C.c_uint32, C.c_uint32, vp, vp, vp]
+    L.sc_register_instances_batch_features_device.argtypes = [vp, vp, vp, u32p, vp, vp, u32p, C.c_uint32, mp, pp, C.c_uint32, C.c_uint32,
+                                                              vp, vp, vp, vp, vp, vp]
     L.sc_hypothesize_device.argtypes = [vp, vp, vp, C.c_int64, pp, vp, sp]
     L.sc_finalize_device.argtypes = [vp, vp, vp, vp, sp]
     L.sc_hypothesize_begin_device.argtypes = [vp, vp, vp, C.c_int64, pp, vp, sp]
@@ -694,6 +700,64 @@ class Registrar:
             out.append(dict(status=int(r["status"]), R=r["Rt"][:9].reshape(3, 3).copy(), t=r["Rt"][9:].copy(), mask=mask[lo:hi].copy(),
                             stats=stats, polished=polished))
         return out
+
+    # ---- several rigid motions per batch problem (include/saccot.h, sc_register_instances_batch) --------------------
+    def register_instances_batch_raw(self, src, tgt, offset, params: ScParams, max_instances: int = 8, min_score: int = 0):
+        """sc_register_instances_batch on packed arrays (src / tgt / offset as register_batch_raw's) -> (records (max_instances, B)
+        of BATCH_RESULT_DTYPE, motion-major: records[k, b] is motion k of problem b; label (total,) int32, the motion that claimed a
+        correspondence, -1 for none; nfound (B,) uint32)."""
+        src, tgt = _f32c(src), _f32c(tgt)
+        offset = np.ascontiguousarray(offset, dtype=np.uint32)
+        nb = max(len(offset) - 1, 0)
+        total = int(offset[-1]) if len(offset) else 0
+        planes = min(max(int(max_instances), 1), SC_INSTANCES_BATCH_MAX)  # (room; the library refuses what is out of range)
+        res = np.zeros((planes, max(nb, 1)), BATCH_RESULT_DTYPE); label = np.zeros(max(total, 1), np.int32)
+        nfound = np.zeros(max(nb, 1), np.uint32)
+        self._frame_n = 0
+        self._check(self._lib.sc_register_instances_batch(self._h, _p(src, C.c_float), _p(tgt, C.c_float), _p(offset, C.c_uint32), nb,
+                                                          C.byref(params), max_instances, min_score, res.ctypes.data_as(C.c_void_p),
+                                                          _p(label, C.c_int32), _p(nfound, C.c_uint32)))
+        return res[:, :nb], label[:total], nfound[:nb]
+
+    def register_instances_batch(self, problems, max_instances: int = 8, min_score: int = 0, params: ScParams | None = None, **kw):
+        """sc_register_instances_batch: problems, a list of (src (n_b, 3), tgt (n_b, 3)) pairs -> one dict per problem: status (plane
+        0's: sc_register_batch's for the problem), Rt (found, 12), score (found,), label (n_b,) int32, stats (plane 0's counts) — the
+        keys of register_instances(), a problem's SC_ENOHYP / SC_EINVAL being its status, not an exception."""
+        p = params or make_params(**kw)
+        sizes = [np.shape(s)[0] for s, _ in problems]
+        offset = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint32)
+        src = np.concatenate([_f32c(s).reshape(-1, 3) for s, _ in problems]) if sizes else np.zeros((0, 3), np.float32)
+        tgt = np.concatenate([_f32c(t).reshape(-1, 3) for _, t in problems]) if sizes else np.zeros((0, 3), np.float32)
+        if p.layout == SC_SOA:
+            src, tgt = np.ascontiguousarray(src.T), np.ascontiguousarray(tgt.T)
+        res, label, nfound = self.register_instances_batch_raw(src, tgt, offset, p, max_instances, min_score)
+        out = []
+        for b in range(len(sizes)):
+            k, r0 = int(nfound[b]), res[0, b]
+            stats = {f: int(r0[f]) for f in ("n", "edges", "tri_total", "tri_kept", "best_rank", "best_count")}
+            out.append(dict(status=int(r0["status"]), Rt=res[:k, b]["Rt"].copy(), score=res[:k, b]["best_count"].copy(),
+                            label=label[int(offset[b]): int(offset[b + 1])].copy(), stats=stats))
+        return out
+
+    def register_instances_batch_device(self, d_src: int, d_tgt: int, offset, params: ScParams, max_instances: int, min_score: int,
+                                        d_res: int, d_label: int, d_nfound: int):
+        """sc_register_instances_batch_device: points, records (max_instances x B of 80 bytes, motion-major), labels (total int32) and
+        nfound (B uint32) in HBM, offset a HOST array (B + 1,) uint32; enqueues on the context's stream and returns without waiting."""
+        offset = np.ascontiguousarray(offset, dtype=np.uint32)
+        self._frame_n = 0
+        self._check(self._lib.sc_register_instances_batch_device(self._h, d_src, d_tgt, _p(offset, C.c_uint32), max(len(offset) - 1, 0),
+                                                                 C.byref(params), max_instances, min_score, d_res, d_label, d_nfound))
+
+    def register_instances_batch_features_device(self, d_src_pts: int, d_fsrc: int, src_off, d_tgt_pts: int, d_ftgt: int, tgt_off,
+                                                 mparams: ScMatchParams, params: ScParams, max_instances: int, min_score: int, d_res: int,
+                                                 d_corr: int, d_d2: int, d_count: int, d_label: int, d_nfound: int):
+        """sc_register_instances_batch_features_device: register_batch_features_device with rounds — d_res max_instances x B records,
+        d_label total_s * knn int32 positioned like that entry's mask, d_nfound B uint32; returns without waiting."""
+        src_off, tgt_off = np.ascontiguousarray(src_off, dtype=np.uint32), np.ascontiguousarray(tgt_off, dtype=np.uint32)
+        self._frame_n = 0
+        self._check(self._lib.sc_register_instances_batch_features_device(
+            self._h, d_src_pts, d_fsrc, _p(src_off, C.c_uint32), d_tgt_pts, d_ftgt, _p(tgt_off, C.c_uint32), max(len(src_off) - 1, 0),
+            C.byref(mparams), C.byref(params), max_instances, min_score, d_res, d_corr, d_d2, d_count, d_label, d_nfound))
 
     def hypothesize_device(self, d_src: int, d_tgt: int, n: int, params: ScParams, d_key: int):
         st = ScStats(C.sizeof(ScStats))

@@ -22,6 +22,16 @@
 //
 // Work items of an enumeration are (row, 16 columns), dealt by an LDS ticket: rows of an inlier hold most of the triangles, and a
 // static deal would leave most lanes waiting for a few.  Cost: (triangles of the graph) x (passes: 3 .. 10) + (kept triangles) x n.
+//
+// sc_register_instances_batch is the same kernel with ROUNDS: after the frame the workgroup still holds the planes, the bit rows, K*
+// and the cut, and a round of sc_peel is the C1 + C2 enumeration once more — every kept triangle scored over the correspondences no
+// earlier motion claimed (a bit per correspondence in LDS; the scoring loop is a broadcast, so skipping a claimed one is a decision
+// of the whole wave) —, the rank enumeration, and the winner's mask among the alive ones.  So the kernel's tail is ONE loop over
+// rounds, the frame being round 0: up to max_instances passes, left at the first round that scores nothing or less than min_score.
+// Without ROUNDS the loop is its first pass: the instantiations of sc_register_batch hold nothing of the rounds, and their code is
+// what it was before there were any.
+#include <type_traits>
+
 #include "../../include/saccot.h"
 #include "sc_arith.hpp"
 #include "sc_batch_frame.hpp"
@@ -32,6 +42,7 @@ namespace sc {
 
 static_assert(sizeof(BatchRecord) == sizeof(sc_batch_result) && sizeof(BatchRecord) == 80 && BATCH_MAX_N == SC_BATCH_MAX_N,
               "BatchRecord is sc_batch_result, 80 bytes");
+static_assert(INSTANCES_BATCH_MAX == SC_INSTANCES_BATCH_MAX && INSTANCES_BATCH_MAX <= 127, "a motion's index fits a label byte");
 
 namespace {
 
@@ -53,6 +64,12 @@ struct alignas(16) BatchLds {
   uint32_t rec[REC_WORDS];
 };
 static_assert(sizeof(BatchLds) < 64 * 1024, "static LDS");
+// with rounds: who is still alive (bit m & 63 of word m >> 6; bits from n on are clear) and which motion claimed whom (-1: none)
+struct alignas(16) RoundsLds : BatchLds {
+  uint64_t alive[BN / 64];
+  int8_t label[BN];
+};
+static_assert(3 * sizeof(RoundsLds) <= 160 * 1024, "three workgroups a compute unit, as without rounds");
 
 __device__ __forceinline__ uint32_t pack3(int i, int j, int k) { return ((uint32_t)i << 18) | ((uint32_t)j << 9) | (uint32_t)k; }
 // is the triangle with this key and packed (i, j, k) among the top T?  (kstar = 0, cut all ones: every triangle is)
@@ -154,30 +171,92 @@ __device__ __forceinline__ void record_fill(BatchLds& L, const float* Rt, int st
   L.rec[18] = rank; L.rec[19] = count;
 }
 
+// ---- rounds (sc_register_instances_batch)
+// The score of (R, t) over the alive correspondences: the set bits of L.alive (bits from n on are clear).  Four correspondences of
+// the planes at a time, as the frame's loop reads them; the planes hold BN entries, so a group of four that straddles n is read and
+// not counted.  Sums of integers: no order matters.
+__device__ __forceinline__ uint32_t score_alive(const RoundsLds& L, const float* M, int n, float thr, int mode) {
+  uint32_t score = 0u;
+  for (int w = 0; 64 * w < n; w++) {
+    const uint64_t a = L.alive[w];
+    for (int q = 0; q < 16 && (a >> (4 * q)) != 0ull; q++) {
+      const uint32_t take = (uint32_t)(a >> (4 * q)) & 15u;
+      if (!take) continue;
+      float4 c6[6];
+#pragma unroll
+      for (int c = 0; c < 6; c++) c6[c] = *reinterpret_cast<const float4*>(&L.pt[c][64 * w + 4 * q]);
+      if (take & 1u) score += score_term(M, c6[0].x, c6[1].x, c6[2].x, c6[3].x, c6[4].x, c6[5].x, thr, mode);
+      if (take & 2u) score += score_term(M, c6[0].y, c6[1].y, c6[2].y, c6[3].y, c6[4].y, c6[5].y, thr, mode);
+      if (take & 4u) score += score_term(M, c6[0].z, c6[1].z, c6[2].z, c6[3].z, c6[4].z, c6[5].z, thr, mode);
+      if (take & 8u) score += score_term(M, c6[0].w, c6[1].w, c6[2].w, c6[3].w, c6[4].w, c6[5].w, thr, mode);
+    }
+  }
+  return score;
+}
+// motion r claims the alive inliers of (R, t).  Correspondence tid + 256 u lies in word wave + 4 u: a wave's ballot is its own word.
+__device__ __forceinline__ void claim(RoundsLds& L, const float* M, int n, float tau2, uint32_t r) {
+  static_assert(BT % 64 == 0 && BN % BT == 0 && BN % 64 == 0, "whole waves, whole strides: a wave owns the alive word it updates");
+#pragma unroll
+  for (int u = 0; u < BN / BT; u++) {
+    const int m = (int)threadIdx.x + BT * u;
+    const bool take = m < n && ((L.alive[m >> 6] >> (m & 63)) & 1ull) && is_inlier(M, load_corr(&L.pt[0][0], BN, m), tau2);
+    const uint64_t taken = __ballot(take);
+    if (take) L.label[m] = (int8_t)r;
+    if ((threadIdx.x & 63) == 0) L.alive[m >> 6] &= ~taken;
+  }
+}
+// Planes [from, max_instances) of a problem: the record staged last with R = I, t = 0, no rank and no score, SC_ENOHYP unless the
+// problem itself is SC_EINVAL — the counts stay plane 0's, which every record of the problem carries.
+__device__ __forceinline__ void planes_empty(BatchLds& L, const BatchJob& job, uint32_t from, uint32_t max_instances) {
+  __syncthreads();  // (the store of the record staged last has read it)
+  if (threadIdx.x == 0) {
+    record_pose(L.rec, nullptr);
+    if (L.rec[12] != (uint32_t)SC_EINVAL) L.rec[12] = (uint32_t)SC_ENOHYP;
+    L.rec[18] = 0u; L.rec[19] = 0u;
+  }
+  for (uint32_t k = from; k < max_instances; k++) record_store(L.rec, job.res + (size_t)k * job.n_problems);
+}
+// a problem without a motion: every label -1 (n of them; none for a flagged problem), nothing found, the further planes
+__device__ __forceinline__ void rounds_none(BatchLds& L, const BatchJob& job, const BatchRounds& rd, uint32_t off, int n) {
+  for (int m = threadIdx.x; m < n; m += BT) rd.label[off + m] = -1;
+  if (threadIdx.x == 0) rd.nfound[blockIdx.x] = 0u;
+  planes_empty(L, job, 1u, rd.max_instances);
+}
+
 // The kernel's argument is BatchJob (sc_register_batch) or BatchSlotJob (sc_register_batch_features: the problems sit in slots and
-// `count` says how much of each is filled, sc_kernels.hpp).  The plain instantiation is the kernel of sc_register_batch with the
-// kernel argument it always had: COUNTED is a constant of the instantiation, and nothing of the slot form is compiled into it.
+// `count` says how much of each is filled, sc_kernels.hpp), or one of the two with rounds (InstBatchJob, InstBatchSlotJob).  The
+// plain instantiation is the kernel of sc_register_batch with the kernel argument it always had: COUNTED and ROUNDS are constants
+// of the instantiation, and nothing of the slot form or of the rounds is compiled into it.
+template <class Arg> struct ArgKind { static constexpr bool COUNTED = false, ROUNDS = false; };
+template <> struct ArgKind<BatchSlotJob> { static constexpr bool COUNTED = true, ROUNDS = false; };
+template <> struct ArgKind<InstBatchJob> { static constexpr bool COUNTED = false, ROUNDS = true; };
+template <> struct ArgKind<InstBatchSlotJob> { static constexpr bool COUNTED = true, ROUNDS = true; };
 __device__ __forceinline__ const uint32_t* count_of(const BatchJob&) { return nullptr; }
 __device__ __forceinline__ const uint32_t* count_of(const BatchSlotJob& a) { return a.count; }
+__device__ __forceinline__ const uint32_t* count_of(const InstBatchJob&) { return nullptr; }
+__device__ __forceinline__ const uint32_t* count_of(const InstBatchSlotJob& a) { return a.count; }
 
 template <class Arg>
 __global__ __launch_bounds__(BT) void batch_register_kernel(const Arg arg) {
-  constexpr bool COUNTED = sizeof(Arg) != sizeof(BatchJob);
+  constexpr bool COUNTED = ArgKind<Arg>::COUNTED, ROUNDS = ArgKind<Arg>::ROUNDS;
   const BatchJob& job = job_of(arg);
   const uint32_t* const count = count_of(arg);
-  __shared__ BatchLds L;
+  __shared__ std::conditional_t<ROUNDS, RoundsLds, BatchLds> L;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const uint32_t off = job.offset[blockIdx.x];
   const int n = COUNTED ? (int)count[2 * blockIdx.x] : (int)(job.offset[blockIdx.x + 1] - off);  // 3 .. BN: the host checked
   const int W = (n + 63) >> 6;
   const Derived dv = job.dv;
-  uint8_t* const mask = job.mask + off;
+  uint8_t* const mask = job.mask + off;  // (with ROUNDS there is none: the labels take its place)
   if (COUNTED) {  // what the host refuses for the plain form, it cannot know here: the match decided it on the device
     const bool flagged = count[2 * blockIdx.x + 1] != 0u;
     if (flagged || n < 3 || n > BN) {  // (n > BN cannot happen: a slot's capacity is at most BN)
-      if (!flagged && n < 3) mask_zero<BT>(mask, n);
+      if constexpr (!ROUNDS) {
+        if (!flagged && n < 3) mask_zero<BT>(mask, n);
+      }
       if (tid == 0) record_fill(L, nullptr, (flagged || n > BN) ? SC_EINVAL : SC_ENOHYP, flagged ? 0u : (uint32_t)n, 0u, 0u, 0u, 0u, 0u);
       record_store(L.rec, job.res);
+      if constexpr (ROUNDS) rounds_none(L, job, arg.rounds, off, (!flagged && n < 3) ? n : 0);
       return;
     }
   }
@@ -188,9 +267,10 @@ __global__ __launch_bounds__(BT) void batch_register_kernel(const Arg arg) {
   if (stage_planes<BT>(L.pt, job.src, job.tgt, job.soa, job.total, off, n)) L.bad = 1u;
   __syncthreads();
   if (L.bad) {
-    mask_zero<BT>(mask, n);
+    if constexpr (!ROUNDS) mask_zero<BT>(mask, n);
     if (tid == 0) record_fill(L, nullptr, SC_EINVAL, (uint32_t)n, 0u, 0u, 0u, 0u, 0u);
     record_store(L.rec, job.res);
+    if constexpr (ROUNDS) rounds_none(L, job, arg.rounds, off, n);
     return;
   }
 
@@ -235,9 +315,10 @@ __global__ __launch_bounds__(BT) void batch_register_kernel(const Arg arg) {
   }
   const uint32_t kept_n = job.T < total ? job.T : total;
   if (total == 0u) {
-    mask_zero<BT>(mask, n);
+    if constexpr (!ROUNDS) mask_zero<BT>(mask, n);
     if (tid == 0) record_fill(L, nullptr, SC_ENOHYP, (uint32_t)n, edges, 0u, 0u, 0u, 0u);
     record_store(L.rec, job.res);
+    if constexpr (ROUNDS) rounds_none(L, job, arg.rounds, off, n);
     return;
   }
 
@@ -324,82 +405,125 @@ __global__ __launch_bounds__(BT) void batch_register_kernel(const Arg arg) {
     }
   }
 
-  // ---- stages C1 + C2: every kept triangle solved and scored; the winner by (score, key, lowest (i, j, k))
+  // ---- stages C1 + C2, the winner, its rank and its mask: once for the frame (round 0) and, with ROUNDS, once more per round of
+  // sc_peel — the same enumerations, scored over the correspondences no earlier motion claimed.  Without ROUNDS the loop is its
+  // first pass and nothing else.
   const float thr = score_thr(dv, job.score_mode);
   unsigned long long k0 = 0ull, k1 = 0ull;
-  {
-    pass_begin(L, 0u);
-    TriIter it(L, n, items);
-    float s_ij = 0.f;
-    for (;;) {
-      bool have = false;
-      uint32_t key = 0u, pk = 0u;
-      while (it.next()) {  // this thread's next kept triangle
-        key = tri_key(L, it, dv, job.rank_mode, s_ij);
-        pk = pack3(it.i, it.j, it.k);
-        if (is_kept(key, pk, kstar, cut)) { have = true; break; }
+  uint32_t found = 0u;  // (with ROUNDS) motions found so far
+  for (uint32_t round = 0u;; round++) {
+    // every kept triangle solved and scored; the winner by (score, key, lowest (i, j, k))
+    {
+      pass_begin(L, 0u);
+      TriIter it(L, n, items);
+      float s_ij = 0.f;
+      for (;;) {
+        bool have = false;
+        uint32_t key = 0u, pk = 0u;
+        while (it.next()) {  // this thread's next kept triangle
+          key = tri_key(L, it, dv, job.rank_mode, s_ij);
+          pk = pack3(it.i, it.j, it.k);
+          if (is_kept(key, pk, kstar, cut)) { have = true; break; }
+        }
+        if (!have) break;
+        float P[9], Q[9], M[12];
+        const int v[3] = {it.i, it.j, it.k};
+#pragma unroll
+        for (int m = 0; m < 3; m++)
+#pragma unroll
+          for (int c = 0; c < 3; c++) { P[3 * m + c] = L.pt[c][v[m]]; Q[3 * m + c] = L.pt[3 + c][v[m]]; }
+        kabsch3(P, Q, M);
+        uint32_t score = 0u;
+        if (finite12(M)) {
+          bool over_all = true;
+          if constexpr (ROUNDS) {
+            if (round) {  // the alive ones only: the same word in every lane, so what is skipped, the whole wave skips
+              over_all = false;
+              score = score_alive(L, M, n, thr, job.score_mode);
+            }
+          }
+          if (over_all) {
+            int m = 0;
+            for (; m + 4 <= n; m += 4) {  // (every lane reads the same 16 bytes of a plane: a broadcast)
+              float4 c6[6];
+#pragma unroll
+              for (int c = 0; c < 6; c++) c6[c] = *reinterpret_cast<const float4*>(&L.pt[c][m]);
+              score += score_term(M, c6[0].x, c6[1].x, c6[2].x, c6[3].x, c6[4].x, c6[5].x, thr, job.score_mode);
+              score += score_term(M, c6[0].y, c6[1].y, c6[2].y, c6[3].y, c6[4].y, c6[5].y, thr, job.score_mode);
+              score += score_term(M, c6[0].z, c6[1].z, c6[2].z, c6[3].z, c6[4].z, c6[5].z, thr, job.score_mode);
+              score += score_term(M, c6[0].w, c6[1].w, c6[2].w, c6[3].w, c6[4].w, c6[5].w, thr, job.score_mode);
+            }
+            for (; m < n; m++)
+              score += score_term(M, L.pt[0][m], L.pt[1][m], L.pt[2][m], L.pt[3][m], L.pt[4][m], L.pt[5][m], thr, job.score_mode);
+          }
+        }
+        if (score) lexmax_take(k0, k1, ((unsigned long long)score << 32) | key, (unsigned long long)(~pk));
       }
-      if (!have) break;
-      float P[9], Q[9], M[12];
-      const int v[3] = {it.i, it.j, it.k};
+      block_lexmax_u64(k0, k1, reinterpret_cast<unsigned long long*>(L.red));
+    }
+    if constexpr (ROUNDS) {
+      if (round && (k0 == 0ull || (uint32_t)(k0 >> 32) < arg.rounds.min_score)) break;  // the round stops the problem
+    }
+    if (k0 == 0ull) {  // no hypothesis has an inlier
+      if constexpr (!ROUNDS) mask_zero<BT>(mask, n);
+      if (tid == 0) record_fill(L, nullptr, SC_ENOHYP, (uint32_t)n, edges, kept_n, total, 0u, 0u);
+      record_store(L.rec, job.res);
+      if constexpr (ROUNDS) rounds_none(L, job, arg.rounds, off, n);
+      return;
+    }
+
+    // the winner: its (R, t) again (the same bits), its rank among the kept, its mask
+    const uint32_t wkey = (uint32_t)k0, wpk = ~(uint32_t)k1;
+    float M[12];
+    {
+      float P[9], Q[9];
+      const int v[3] = {(int)(wpk >> 18), (int)((wpk >> 9) & 511u), (int)(wpk & 511u)};
 #pragma unroll
       for (int m = 0; m < 3; m++)
 #pragma unroll
         for (int c = 0; c < 3; c++) { P[3 * m + c] = L.pt[c][v[m]]; Q[3 * m + c] = L.pt[3 + c][v[m]]; }
       kabsch3(P, Q, M);
-      uint32_t score = 0u;
-      if (finite12(M)) {
-        int m = 0;
-        for (; m + 4 <= n; m += 4) {  // (every lane reads the same 16 bytes of a plane: a broadcast)
-          float4 c6[6];
-#pragma unroll
-          for (int c = 0; c < 6; c++) c6[c] = *reinterpret_cast<const float4*>(&L.pt[c][m]);
-          score += score_term(M, c6[0].x, c6[1].x, c6[2].x, c6[3].x, c6[4].x, c6[5].x, thr, job.score_mode);
-          score += score_term(M, c6[0].y, c6[1].y, c6[2].y, c6[3].y, c6[4].y, c6[5].y, thr, job.score_mode);
-          score += score_term(M, c6[0].z, c6[1].z, c6[2].z, c6[3].z, c6[4].z, c6[5].z, thr, job.score_mode);
-          score += score_term(M, c6[0].w, c6[1].w, c6[2].w, c6[3].w, c6[4].w, c6[5].w, thr, job.score_mode);
-        }
-        for (; m < n; m++)
-          score += score_term(M, L.pt[0][m], L.pt[1][m], L.pt[2][m], L.pt[3][m], L.pt[4][m], L.pt[5][m], thr, job.score_mode);
+    }
+    uint32_t rank;
+    {
+      pass_begin(L, 0u);
+      TriIter it(L, n, items);
+      float s_ij = 0.f;
+      uint32_t r = 0u;
+      while (it.next()) {
+        const uint32_t key = tri_key(L, it, dv, job.rank_mode, s_ij), pk = pack3(it.i, it.j, it.k);
+        if (is_kept(key, pk, kstar, cut) && outranks(key, pk, wkey, wpk)) r++;
       }
-      if (score) lexmax_take(k0, k1, ((unsigned long long)score << 32) | key, (unsigned long long)(~pk));
+      rank = (uint32_t)block_reduce_u64(r, L.red);
     }
-    block_lexmax_u64(k0, k1, reinterpret_cast<unsigned long long*>(L.red));
-  }
-  if (k0 == 0ull) {  // no hypothesis has an inlier
-    mask_zero<BT>(mask, n);
-    if (tid == 0) record_fill(L, nullptr, SC_ENOHYP, (uint32_t)n, edges, kept_n, total, 0u, 0u);
-    record_store(L.rec, job.res);
-    return;
-  }
-
-  // ---- the winner: its (R, t) again (the same bits), its rank among the kept, its mask
-  const uint32_t wkey = (uint32_t)k0, wpk = ~(uint32_t)k1;
-  float M[12];
-  {
-    float P[9], Q[9];
-    const int v[3] = {(int)(wpk >> 18), (int)((wpk >> 9) & 511u), (int)(wpk & 511u)};
-#pragma unroll
-    for (int m = 0; m < 3; m++)
-#pragma unroll
-      for (int c = 0; c < 3; c++) { P[3 * m + c] = L.pt[c][v[m]]; Q[3 * m + c] = L.pt[3 + c][v[m]]; }
-    kabsch3(P, Q, M);
-  }
-  uint32_t rank;
-  {
-    pass_begin(L, 0u);
-    TriIter it(L, n, items);
-    float s_ij = 0.f;
-    uint32_t r = 0u;
-    while (it.next()) {
-      const uint32_t key = tri_key(L, it, dv, job.rank_mode, s_ij), pk = pack3(it.i, it.j, it.k);
-      if (is_kept(key, pk, kstar, cut) && outranks(key, pk, wkey, wpk)) r++;
+    if constexpr (!ROUNDS) {
+      for (int m = tid; m < n; m += BT) mask[m] = is_inlier(M, load_corr(&L.pt[0][0], BN, m), dv.tau2) ? 1 : 0;
+      if (tid == 0) record_fill(L, M, SC_OK, (uint32_t)n, edges, kept_n, total, rank, (uint32_t)(k0 >> 32));
+      record_store(L.rec, job.res);
+      break;
+    } else {
+      const BatchRounds& rd = arg.rounds;
+      if (round == 0u) {  // everyone is alive; motion 0 is the frame's winner if it scores min_score
+        for (int m = tid; m < BN; m += BT) L.label[m] = -1;
+        if (tid < BN / 64) L.alive[tid] = 64 * tid + 64 <= n ? ~0ull : (64 * tid < n ? (1ull << (n & 63)) - 1ull : 0ull);
+        __syncthreads();
+      }
+      if (tid == 0) record_fill(L, M, SC_OK, (uint32_t)n, edges, kept_n, total, rank, (uint32_t)(k0 >> 32));
+      record_store(L.rec, job.res + (size_t)round * job.n_problems);
+      if ((uint32_t)(k0 >> 32) < rd.min_score) break;  // (round 0 only: plane 0 is written whatever min_score is)
+      claim(L, M, n, dv.tau2, round);  // (the next pass's first barrier publishes it)
+      found = round + 1u;
+      if (found == rd.max_instances) break;
+      k0 = 0ull; k1 = 0ull;
     }
-    rank = (uint32_t)block_reduce_u64(r, L.red);
   }
-  for (int m = tid; m < n; m += BT) mask[m] = is_inlier(M, load_corr(&L.pt[0][0], BN, m), dv.tau2) ? 1 : 0;
-  if (tid == 0) record_fill(L, M, SC_OK, (uint32_t)n, edges, kept_n, total, rank, (uint32_t)(k0 >> 32));
-  record_store(L.rec, job.res);
+  if constexpr (ROUNDS) {  // the labels, the count, and the planes without a motion
+    const BatchRounds& rd = arg.rounds;
+    __syncthreads();
+    for (int m = tid; m < n; m += BT) rd.label[off + m] = L.label[m];
+    if (tid == 0) rd.nfound[blockIdx.x] = found;
+    planes_empty(L, job, found ? found : 1u, rd.max_instances);
+  }
 }
 
 }  // namespace
@@ -410,6 +534,14 @@ void launch_batch_register(const BatchJob& job, hipStream_t st) {
 
 void launch_batch_register_slots(const BatchSlotJob& job, hipStream_t st) {
   hipLaunchKernelGGL(batch_register_kernel<BatchSlotJob>, dim3(job.job.n_problems), dim3(BT), 0, st, job);
+}
+
+void launch_instances_batch(const InstBatchJob& job, hipStream_t st) {
+  hipLaunchKernelGGL(batch_register_kernel<InstBatchJob>, dim3(job.job.n_problems), dim3(BT), 0, st, job);
+}
+
+void launch_instances_batch_slots(const InstBatchSlotJob& job, hipStream_t st) {
+  hipLaunchKernelGGL(batch_register_kernel<InstBatchSlotJob>, dim3(job.job.n_problems), dim3(BT), 0, st, job);
 }
 
 }  // namespace sc

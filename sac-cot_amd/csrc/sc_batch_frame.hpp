@@ -10,6 +10,8 @@ namespace sc {
 // The plain job inside either form of a kernel's argument (the slot forms wrap it, sc_kernels.hpp).
 __device__ __forceinline__ const BatchJob& job_of(const BatchJob& a) { return a; }
 __device__ __forceinline__ const BatchJob& job_of(const BatchSlotJob& a) { return a.job; }
+__device__ __forceinline__ const BatchJob& job_of(const InstBatchJob& a) { return a.job; }
+__device__ __forceinline__ const BatchJob& job_of(const InstBatchSlotJob& a) { return a.job; }
 __device__ __forceinline__ const PolishBatchJob& job_of(const PolishBatchJob& a) { return a; }
 __device__ __forceinline__ const PolishBatchJob& job_of(const PolishBatchSlotJob& a) { return a.job; }
 

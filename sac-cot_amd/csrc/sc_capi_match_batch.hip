@@ -14,20 +14,20 @@ using namespace sc;
 
 static_assert(MATCH_BATCH_MAX_N == SC_MATCH_BATCH_MAX_N, "sc_kernels.hpp and saccot.h agree");
 
-namespace {
+using Sizes = MatchBatchSizes;
 
-struct Sizes {
-  uint32_t n_problems, n_tiles;
-  size_t total_s, total_t, slots;  // rows of fsrc, rows of ftgt, output entries (total_s * knn)
-};
+// The match sequence — what is refused, the workspace, the enqueue, the gather's description — is namespace sc's: the entries here
+// and sc_register_instances_batch_features_device (sc_capi_instances_batch.hip) share it (declared in sc_ctx.hpp).
+namespace sc {
 
-// every refusal of the four entries; `p` only for the features entries.  Fills *job (but its pointers) and *sz.
+// every refusal of the entries; `p` only for the features entries, whose name for the messages is `features`.  Fills *job (but its
+// pointers) and *sz.
 int mbatch_check(sc_ctx* c, const uint32_t* src_off, const uint32_t* tgt_off, uint32_t n_problems, const sc_match_params* mp,
-                 const sc_params* p, bool features, MatchJob* job, Sizes* sz) {
+                 const sc_params* p, const char* features, MatchJob* job, Sizes* sz) {
   SC_TRY(entry_checks(c, nullptr, ENDS_FRAME | NOT_BUSY));
   SC_TRY(match_check(c, mp, 1, 1, job));  // the parameter rules; the sizes are the offsets' business
-  if (features) SC_TRY(batch_params_check(c, p, "sc_register_batch_features"));
-  if (const char* what = match_batch_offsets_error(src_off, tgt_off, n_problems, job->knn, features)) { c->last_error = what; return SC_EINVAL; }
+  if (features) SC_TRY(batch_params_check(c, p, features));
+  if (const char* what = match_batch_offsets_error(src_off, tgt_off, n_problems, job->knn, features != nullptr)) { c->last_error = what; return SC_EINVAL; }
   const uint64_t tiles = match_batch_tile_count(src_off, n_problems, MATCH_BATCH_ROWS);
   if (tiles > 0x7FFFFFFFull) { c->last_error = "sc_match_batch: more than 2^31 - 1 row tiles"; return SC_EINVAL; }
   sz->n_problems = n_problems; sz->n_tiles = (uint32_t)tiles;
@@ -75,26 +75,36 @@ int mbatch_enqueue(sc_ctx* c, const MatchJob& mj, const Sizes& sz, const float* 
   return SC_OK;
 }
 
-// sc_batch.hip's kernel on the slots the match filled: the gathered points, the slot starts, the count pairs
-int mbatch_register(sc_ctx* c, const Sizes& sz, const sc_params* p, const uint32_t* d_count, sc_batch_result* d_res, uint8_t* d_mask) {
-  BatchSlotJob slots{};
-  slots.count = d_count;
-  BatchJob& job = slots.job;
+MatchGather gather_of(const sc_ctx* c, const sc_params* p, const Sizes& sz, const float* d_src_pts, const float* d_tgt_pts) {
+  const bool soa = p->layout == SC_SOA;
+  return MatchGather{d_src_pts, d_tgt_pts, soa ? 1u : 3u, soa ? (uint32_t)sz.total_s : 1u, soa ? 1u : 3u, soa ? (uint32_t)sz.total_t : 1u,
+                     c->mbatch_gsrc.as<float>(), c->mbatch_gtgt.as<float>()};
+}
+
+// sc_batch.hip's kernel argument on the slots the match filled: the gathered points, the slot starts (the count pairs are the caller's)
+BatchJob mbatch_slots_job(const sc_ctx* c, const Sizes& sz, const sc_params* p) {
+  BatchJob job{};
   job.src = c->mbatch_gsrc.as<float>(); job.tgt = c->mbatch_gtgt.as<float>();  // n x 3 whatever the caller's layout
   job.offset = c->mbatch_meta.as<uint32_t>() + 2 * ((size_t)sz.n_problems + 1);
   job.n_problems = sz.n_problems; job.total = (uint32_t)sz.slots;
   job.soa = 0; job.T = p->max_triangles; job.rank_mode = p->rank_mode; job.score_mode = p->score_mode;
   job.dv = derive(p);
-  job.res = reinterpret_cast<BatchRecord*>(d_res); job.mask = d_mask;
+  return job;
+}
+
+}  // namespace sc
+
+namespace {
+
+// sc_batch.hip's kernel on the slots the match filled
+int mbatch_register(sc_ctx* c, const Sizes& sz, const sc_params* p, const uint32_t* d_count, sc_batch_result* d_res, uint8_t* d_mask) {
+  BatchSlotJob slots{};
+  slots.count = d_count;
+  slots.job = mbatch_slots_job(c, sz, p);
+  slots.job.res = reinterpret_cast<BatchRecord*>(d_res); slots.job.mask = d_mask;
   launch_batch_register_slots(slots, c->stream);
   HIPCHK(c, hipGetLastError());
   return SC_OK;
-}
-
-MatchGather gather_of(const sc_ctx* c, const sc_params* p, const Sizes& sz, const float* d_src_pts, const float* d_tgt_pts) {
-  const bool soa = p->layout == SC_SOA;
-  return MatchGather{d_src_pts, d_tgt_pts, soa ? 1u : 3u, soa ? (uint32_t)sz.total_s : 1u, soa ? 1u : 3u, soa ? (uint32_t)sz.total_t : 1u,
-                     c->mbatch_gsrc.as<float>(), c->mbatch_gtgt.as<float>()};
 }
 
 }  // namespace
@@ -107,7 +117,7 @@ int sc_match_batch_device(sc_ctx* c, const float* d_fsrc, const uint32_t* src_of
   if (!d_fsrc || !src_off || !d_ftgt || !tgt_off || !mp || !d_corr || !d_d2 || !d_count) return refuse(c, "sc_match_batch_device", "a NULL argument");
   MatchJob mj{};
   Sizes sz{};
-  SC_TRY(mbatch_check(c, src_off, tgt_off, n_problems, mp, nullptr, false, &mj, &sz));
+  SC_TRY(mbatch_check(c, src_off, tgt_off, n_problems, mp, nullptr, nullptr, &mj, &sz));
   HIPCHK(c, hipSetDevice(c->device));
   SC_TRY(mbatch_room(c, mj, sz, false));
   return mbatch_enqueue(c, mj, sz, d_fsrc, d_ftgt, src_off, tgt_off, d_corr, d_d2, d_count, MatchGather{});
@@ -119,7 +129,7 @@ int sc_match_batch(sc_ctx* c, const float* fsrc, const uint32_t* src_off, const 
   if (!fsrc || !src_off || !ftgt || !tgt_off || !mp || !corr || !d2 || !count) return refuse(c, "sc_match_batch", "a NULL argument");
   MatchJob mj{};
   Sizes sz{};
-  SC_TRY(mbatch_check(c, src_off, tgt_off, n_problems, mp, nullptr, false, &mj, &sz));
+  SC_TRY(mbatch_check(c, src_off, tgt_off, n_problems, mp, nullptr, nullptr, &mj, &sz));
   HIPCHK(c, hipSetDevice(c->device));
   const size_t sb = sz.total_s * mj.dim * 4, tb = sz.total_t * mj.dim * 4, cb = (size_t)n_problems * 8;
   SC_TRY(mbatch_room(c, mj, sz, false));
@@ -149,7 +159,7 @@ int sc_register_batch_features_device(sc_ctx* c, const float* d_src_pts, const f
     return refuse(c, "sc_register_batch_features_device", "a NULL argument");
   MatchJob mj{};
   Sizes sz{};
-  SC_TRY(mbatch_check(c, src_off, tgt_off, n_problems, mp, p, true, &mj, &sz));
+  SC_TRY(mbatch_check(c, src_off, tgt_off, n_problems, mp, p, "sc_register_batch_features", &mj, &sz));
   HIPCHK(c, hipSetDevice(c->device));
   c->cap_bytes = workspace_cap(p);
   SC_TRY(mbatch_room(c, mj, sz, true));
@@ -165,7 +175,7 @@ int sc_register_batch_features(sc_ctx* c, const float* src_pts, const float* fsr
     return refuse(c, "sc_register_batch_features", "a NULL argument");
   MatchJob mj{};
   Sizes sz{};
-  SC_TRY(mbatch_check(c, src_off, tgt_off, n_problems, mp, p, true, &mj, &sz));
+  SC_TRY(mbatch_check(c, src_off, tgt_off, n_problems, mp, p, "sc_register_batch_features", &mj, &sz));
   HIPCHK(c, hipSetDevice(c->device));
   c->cap_bytes = workspace_cap(p);
   const size_t sb = sz.total_s * mj.dim * 4, tb = sz.total_t * mj.dim * 4, cb = (size_t)n_problems * 8;

@@ -116,7 +116,11 @@ struct Workspace {
       mbatch_d2, mbatch_count, mbatch_res, mbatch_mask,
       // sc_polish_batch: allocated by the first such call, never by a frame or by another batch entry.  off: the copy of the caller's
       // offsets (the slot form: both arrays and the slot starts); the rest: device copies of the host entry's arrays
-      pbatch_off, pbatch_src, pbatch_tgt, pbatch_res, pbatch_pol, pbatch_mask;
+      pbatch_off, pbatch_src, pbatch_tgt, pbatch_res, pbatch_pol, pbatch_mask,
+      // sc_register_instances_batch: allocated by the first such call, never by a frame or by another batch entry.  off: the copy of
+      // the caller's offsets; the rest: device copies of the host entry's arrays (the features form holds what
+      // sc_register_batch_features_device holds, in the mbatch buffers)
+      ibatch_off, ibatch_src, ibatch_tgt, ibatch_res, ibatch_label, ibatch_nfound;
 };
 constexpr size_t N_WORKSPACE_BUFS = sizeof(Workspace) / sizeof(Buf);
 static_assert(std::is_standard_layout<Workspace>::value && alignof(Workspace) == alignof(Buf) && sizeof(Workspace) == N_WORKSPACE_BUFS * sizeof(Buf),
@@ -246,6 +250,25 @@ int batch_staging_begin(sc_ctx* c, size_t bytes);
 int batch_staging_send(sc_ctx* c, Buf& dst, size_t bytes);
 // the caller's offsets (n_problems + 1 words) through that area into dst (enqueued)
 int batch_offsets_to_device(sc_ctx* c, const uint32_t* offset, uint32_t n_problems, Buf& dst);
+
+// ---- defined in sc_capi_match_batch.hip, used by sc_capi_instances_batch.hip as well: the match sequence of a features entry
+struct MatchBatchSizes {
+  uint32_t n_problems, n_tiles;
+  size_t total_s, total_t, slots;  // rows of fsrc, rows of ftgt, output entries (total_s * knn)
+};
+// every refusal of a batched match; `p` only for a features entry, whose name for the messages is `features` (nullptr: the match
+// alone).  Fills *job (but its pointers) and *sz.
+int mbatch_check(sc_ctx* c, const uint32_t* src_off, const uint32_t* tgt_off, uint32_t n_problems, const sc_match_params* mp,
+                 const sc_params* p, const char* features, MatchJob* job, MatchBatchSizes* sz);
+// the workspace of the match itself (gather: and of the gathered points)
+int mbatch_room(sc_ctx* c, const MatchJob& mj, const MatchBatchSizes& sz, bool gather);
+// the staging copy, the memset and the two launches (mbatch_room has been called)
+int mbatch_enqueue(sc_ctx* c, const MatchJob& mj, const MatchBatchSizes& sz, const float* d_fsrc, const float* d_ftgt, const uint32_t* src_off,
+                   const uint32_t* tgt_off, int32_t* d_corr, float* d_d2, uint32_t* d_count, const MatchGather& g);
+// the caller's points -> the context's slot-positioned n x 3 arrays, as the finish kernel is told
+MatchGather gather_of(const sc_ctx* c, const sc_params* p, const MatchBatchSizes& sz, const float* d_src_pts, const float* d_tgt_pts);
+// the registration kernel's argument on those slots, but for its outputs
+BatchJob mbatch_slots_job(const sc_ctx* c, const MatchBatchSizes& sz, const sc_params* p);
 
 // ---- a call on a scored frame (sc_peel, sc_polish): what the two share in front of their launches and behind them
 // The entry checks, `busy` first, then "is there a frame"; the refusal names the caller.  Then the context's device.

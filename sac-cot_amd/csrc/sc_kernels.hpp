@@ -723,6 +723,27 @@ struct BatchSlotJob {
 // One workgroup per problem; every record and mask range is written (complete in stream order).
 void launch_batch_register(const BatchJob& job, hipStream_t st);
 void launch_batch_register_slots(const BatchSlotJob& job, hipStream_t st);
+// sc_register_instances_batch: the same kernel, followed inside the workgroup by up to max_instances - 1 rounds of sc_peel.  job.res
+// holds max_instances planes of n_problems records, motion-major; job.mask is not used: label (int32, positioned like the mask) says
+// which motion claimed a correspondence, -1 for none; nfound: a word per problem.  Types of their own again, so that the kernels of
+// sc_register_batch keep their arguments and their code.
+constexpr uint32_t INSTANCES_BATCH_MAX = 16;
+struct BatchRounds {
+  uint32_t max_instances, min_score;
+  int32_t* label;
+  uint32_t* nfound;
+};
+struct InstBatchJob {
+  BatchJob job;
+  BatchRounds rounds;
+};
+struct InstBatchSlotJob {
+  BatchJob job;
+  BatchRounds rounds;
+  const uint32_t* count;  // as BatchSlotJob's
+};
+void launch_instances_batch(const InstBatchJob& job, hipStream_t st);
+void launch_instances_batch_slots(const InstBatchSlotJob& job, hipStream_t st);
 
 // ---- iterated fp64 refits for a batch's winners (sc_polish_batch; sc_polish_batch.hip) ----------------------
 // One problem's result: sc_polish_batch_result of include/saccot.h, field for field (sc_polish_batch.hip asserts the size).
