@@ -43,6 +43,7 @@ extern "C" {
 #define SC_HAS_MATCH_BATCH 1  /* this header declares sc_match_batch* and sc_register_batch_features* (added within 0.10) */
 #define SC_HAS_POLISH_BATCH 1  /* this header declares sc_polish_batch* (added within 0.10) */
 #define SC_HAS_INSTANCES_BATCH 1  /* this header declares sc_register_instances_batch* (added within 0.10) */
+#define SC_HAS_PAIRS 1  /* this header declares sc_match_pairs*, sc_register_pairs_features* and sc_polish_pairs_slots_device (added within 0.10) */
 
 /* status codes */
 #define SC_OK        0
@@ -628,6 +629,68 @@ int sc_register_instances_batch_features_device(sc_ctx* ctx, const float* d_src_
                                                 uint32_t n_problems, const sc_match_params* mp, const sc_params* params,
                                                 uint32_t max_instances, uint32_t min_score, sc_batch_result* d_res, int32_t* d_corr,
                                                 float* d_d2, uint32_t* d_count, int32_t* d_label, uint32_t* d_nfound);
+
+/* ---- listed pairs of shared keypoint sets: sc_match_pairs ------------------------------------------------------
+ * The callers of sc_match_batch — fragment pairs, the cluster pairs of a place-recognition back end, object-pose candidates — do
+ * not start from packed problems: they hold a TABLE of keypoint sets and a LIST of pairs drawn from it, and a set takes part in many
+ * pairs.  A packed problem owns its rows, so such a caller had to copy every set's descriptors and points once per pair before the
+ * call (64 sets of 256 keypoints, all 2016 pairs: 144 MB of copies of a 2.3 MB table).  These entries take the table and the list.
+ *
+ * Layout: ONE table of sets.  Set s owns rows [set_off[s], set_off[s + 1]) of feat (total x dim, row-major) and the same rows of
+ * pts (params->layout: SC_AOS total x 3; SC_SOA three planes of total).  set_off is a HOST array of n_sets + 1 words.  pairs is a
+ * HOST array of 2 * n_pairs words: pair p matches source set pairs[2p] against target set pairs[2p + 1].  Source and target come
+ * from the same table (a caller with two collections concatenates them); pairs[2p] == pairs[2p + 1] is legal, a pair may occur
+ * twice, and the list is in any order.  The library copies both host arrays and keeps no caller pointer.
+ * Outputs live in SLOTS, as in sc_match_batch: slot[p] = knn x (the sum of ns_q over q < p), ns_q the rows of pair q's source set
+ * (sc_pairs_layout computes them); corr holds indices LOCAL to the pair's two sets; the count pair sits at count[2p], count[2p + 1];
+ * records at d_res[p], mask bytes at slot[p] + m.  This is what sc_match_batch produces for the same pairs expanded into packed
+ * arrays in list order.
+ *
+ * Semantics: pair p's slot, count pair, record, mask bytes and polish record are, bit for bit, what sc_match_batch_device,
+ * sc_register_batch_features_device and sc_polish_batch_slots_device return for problem p when the caller has expanded the pairs into
+ * packed arrays in list order — and everything those contracts say holds per pair: the canonical distance and the u64 key order, knn
+ * 1 .. 4, SC_MATCH_MUTUAL and ratio with knn == 1, a target set of one row kept under the ratio test, the records of flagged pairs and
+ * of pairs with n_p < 3, entries past n_p unspecified, stream-ordered device forms with no host read.  In addition:
+ *   - A pair's outputs are a function of its two sets and the parameters only: not of its position in the list, of the other pairs,
+ *     of which other pairs share its sets, of n_pairs or of the context's history.  (Two pairs that share a target set do not share
+ *     column minima.)
+ *   - A non-finite descriptor in a set flags every pair that uses that set, and no other pair; the call returns SC_OK.
+ *   - The number of stream operations is the packed form's: it depends neither on n_pairs nor on any size.
+ * Errors: the CALL returns SC_EINVAL, decided on the host before anything is enqueued, sc_last_error naming which: a NULL argument;
+ * n_sets == 0 or n_pairs == 0; set_off decreasing; a set index >= n_sets; a REFERENCED set with 0 rows or more than
+ * SC_MATCH_BATCH_MAX_N (an unreferenced set may have any size); more than 2^31 output entries in all; every rule of sc_match_params /
+ * sc_params / sc_polish_params that the packed entries apply; for the features and polish entries ns_p * knn > SC_BATCH_MAX_N; a call
+ * outstanding on the context.  All entries with a context end the frame it may hold and leave none.  (A device form may wait for
+ * the previous batch call's copy out of the staging area the batch entries share, as the packed forms do.)
+ * Workspace: the pairs' records, slot starts and tile map; the rows' lists (the sum of ns_p x kp keys) and, when mutual, every
+ * pair's own column minima (the sum of nt_p keys); the gathered points; the host forms' device copies of the table and the outputs.
+ * They are the packed entries' buffers — a context that uses both forms holds one set —, allocated by the first such call, counted
+ * in workspace_bytes and held against the cap (SC_ENOMEM).  A context that never calls these entries allocates and runs nothing new.
+ * Not here: a pairs form of sc_register_instances_batch_features, balancing by pair size. */
+/* host only, no context: slot[p] for p <= n_pairs (slot[n_pairs] = the entries in all); SC_EINVAL for a NULL argument, knn outside
+ * 1 .. 4 and anything sc_match_pairs refuses of the table and the list */
+int sc_pairs_layout(const uint32_t* set_off, uint32_t n_sets, const uint32_t* pairs, uint32_t n_pairs, uint32_t knn, uint32_t* slot);
+/* every buffer but set_off and pairs in HBM: d_feat total x dim floats, d_corr slot[n_pairs] x 2 int32, d_d2 slot[n_pairs] floats,
+ * d_count 2 * n_pairs u32 */
+int sc_match_pairs_device(sc_ctx* ctx, const float* d_feat, const uint32_t* set_off, uint32_t n_sets, const uint32_t* pairs,
+                          uint32_t n_pairs, const sc_match_params* mp, int32_t* d_corr, float* d_d2, uint32_t* d_count);
+/* the same with host arrays; waits */
+int sc_match_pairs(sc_ctx* ctx, const float* feat, const uint32_t* set_off, uint32_t n_sets, const uint32_t* pairs, uint32_t n_pairs,
+                   const sc_match_params* mp, int32_t* corr, float* d2, uint32_t* count);
+/* match + registration; d_pts the table's points, d_res n_pairs records, d_mask slot[n_pairs] bytes, the rest as above */
+int sc_register_pairs_features_device(sc_ctx* ctx, const float* d_pts, const float* d_feat, const uint32_t* set_off, uint32_t n_sets,
+                                      const uint32_t* pairs, uint32_t n_pairs, const sc_match_params* mp, const sc_params* params,
+                                      sc_batch_result* d_res, int32_t* d_corr, float* d_d2, uint32_t* d_count, uint8_t* d_mask);
+/* the same with host arrays; waits */
+int sc_register_pairs_features(sc_ctx* ctx, const float* pts, const float* feat, const uint32_t* set_off, uint32_t n_sets,
+                               const uint32_t* pairs, uint32_t n_pairs, const sc_match_params* mp, const sc_params* params,
+                               sc_batch_result* res, int32_t* corr, float* d2, uint32_t* count, uint8_t* mask);
+/* behind sc_register_pairs_features_device, as sc_polish_batch_slots_device is behind sc_register_batch_features_device: the
+ * table's points, set_off and pairs as given there, its d_corr, d_count and d_res; d_pol n_pairs records, d_mask slot[n_pairs] bytes */
+int sc_polish_pairs_slots_device(sc_ctx* ctx, const float* d_pts, const uint32_t* set_off, uint32_t n_sets, const uint32_t* pairs,
+                                 uint32_t n_pairs, uint32_t knn, const sc_params* params, const sc_polish_params* pp,
+                                 const int32_t* d_corr, const uint32_t* d_count, const sc_batch_result* d_res,
+                                 sc_polish_batch_result* d_pol, uint8_t* d_mask);
 
 /* ---- two-phase form for one-process-per-GPU sharding --------------------------------
  * Phase 1: A and B replicated, C1+C2 on this rank's blocks of the top-T list; writes this rank's winner key

@@ -44,6 +44,8 @@ EXPORTS = ["sc_version", "sc_strerror", "sc_default_params", "sc_create", "sc_de
            "sc_match_batch", "sc_match_batch_device", "sc_register_batch_features", "sc_register_batch_features_device",
            "sc_polish_batch", "sc_polish_batch_device", "sc_polish_batch_slots_device",
            "sc_register_instances_batch", "sc_register_instances_batch_device", "sc_register_instances_batch_features_device",
+           "sc_pairs_layout", "sc_match_pairs", "sc_match_pairs_device", "sc_register_pairs_features", "sc_register_pairs_features_device",
+           "sc_polish_pairs_slots_device",
            "sc_hypothesize_device", "sc_finalize_device",
            "sc_hypothesize_begin_device", "sc_hypothesize_end_device", "sc_finalize_gathered_device", "sc_finalize_gathered_device_async",
            "sc_shard_plan_query", "sc_shard_compat_device", "sc_shard_edges_device", "sc_shard_select_device",
@@ -231,6 +233,12 @@ def load_library() -> C.CDLL:
     L.sc_register_instances_batch_device.argtypes = [vp, vp, vp, u32p, C.c_uint32, pp, C.c_uint32, C.c_uint32, vp, vp, vp]
     L.sc_register_instances_batch_features_device.argtypes = [vp, vp, vp, u32p, vp, vp, u32p, C.c_uint32, mp, pp, C.c_uint32, C.c_uint32,
                                                               vp, vp, vp, vp, vp, vp]
+    L.sc_pairs_layout.argtypes = [u32p, C.c_uint32, u32p, C.c_uint32, C.c_uint32, u32p]
+    L.sc_match_pairs_device.argtypes = [vp, vp, u32p, C.c_uint32, u32p, C.c_uint32, mp, vp, vp, vp]
+    L.sc_match_pairs.argtypes = [vp, f32p, u32p, C.c_uint32, u32p, C.c_uint32, mp, i32p, f32p, u32p]
+    L.sc_register_pairs_features_device.argtypes = [vp, vp, vp, u32p, C.c_uint32, u32p, C.c_uint32, mp, pp, vp, vp, vp, vp, vp]
+    L.sc_register_pairs_features.argtypes = [vp, f32p, f32p, u32p, C.c_uint32, u32p, C.c_uint32, mp, pp, vp, i32p, f32p, u32p, u8p]
+    L.sc_polish_pairs_slots_device.argtypes = [vp, vp, u32p, C.c_uint32, u32p, C.c_uint32, C.c_uint32, pp, qp, vp, vp, vp, vp, vp]
     L.sc_hypothesize_device.argtypes = [vp, vp, vp, C.c_int64, pp, vp, sp]
     L.sc_finalize_device.argtypes = [vp, vp, vp, vp, sp]
     L.sc_hypothesize_begin_device.argtypes = [vp, vp, vp, C.c_int64, pp, vp, sp]
@@ -758,6 +766,88 @@ class Registrar:
         self._check(self._lib.sc_register_instances_batch_features_device(
             self._h, d_src_pts, d_fsrc, _p(src_off, C.c_uint32), d_tgt_pts, d_ftgt, _p(tgt_off, C.c_uint32), max(len(src_off) - 1, 0),
             C.byref(mparams), C.byref(params), max_instances, min_score, d_res, d_corr, d_d2, d_count, d_label, d_nfound))
+
+    # ---- listed pairs of shared keypoint sets (include/saccot.h, sc_match_pairs) ------------------------------------
+    @staticmethod
+    def _table(set_off, pairs):
+        set_off = np.ascontiguousarray(set_off, dtype=np.uint32).reshape(-1)
+        pairs = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1)
+        return set_off, pairs, max(len(set_off) - 1, 0), len(pairs) // 2
+
+    @staticmethod
+    def pairs_layout(set_off, pairs, knn: int = 1) -> np.ndarray:
+        """sc_pairs_layout (host only, no context): set_off (S + 1,) uint32, pairs (P, 2) set indices -> slot (P + 1,) uint32,
+        slot[p] the first output entry of pair p and slot[P] the entries in all.  Raises SacCotError for a table or a list the
+        pairs entries refuse."""
+        set_off, pairs, ns, npairs = Registrar._table(set_off, pairs)
+        slot = np.zeros(npairs + 1, np.uint32)
+        rc = load_library().sc_pairs_layout(_p(set_off, C.c_uint32), ns, _p(pairs, C.c_uint32), npairs, knn, _p(slot, C.c_uint32))
+        if rc != SC_OK:
+            raise SacCotError(rc, "sc_pairs_layout")
+        return slot
+
+    def match_pairs(self, feat, set_off, pairs, mparams: ScMatchParams | None = None, **kw):
+        """sc_match_pairs: feat (total, D) the descriptors of a table of sets, set s rows set_off[s] .. set_off[s + 1]; pairs (P, 2),
+        pair p matching source set pairs[p, 0] against target set pairs[p, 1] -> (corr (slots, 2) int32 local to the pair's sets,
+        d2 (slots,), count (P, 2) uint32, slot (P + 1,)): pair p's entries start at slot[p], count[p] = (n_p, 1 if one of its
+        sets holds a non-finite descriptor).  kw: knn, mutual, ratio (make_match_params)."""
+        feat = _f32c(feat)
+        m = mparams or make_match_params(feat.shape[1], **kw)
+        set_off, pairs, ns, npairs = self._table(set_off, pairs)
+        slot = self.pairs_layout(set_off, pairs, int(m.knn))
+        slots = int(slot[-1])
+        corr = np.zeros((max(slots, 1), 2), np.int32); d2 = np.zeros(max(slots, 1), np.float32); count = np.zeros((max(npairs, 1), 2), np.uint32)
+        self._frame_n = 0
+        self._check(self._lib.sc_match_pairs(self._h, _p(feat, C.c_float), _p(set_off, C.c_uint32), ns, _p(pairs, C.c_uint32), npairs,
+                                             C.byref(m), _p(corr, C.c_int32), _p(d2, C.c_float), _p(count, C.c_uint32)))
+        return corr[:slots], d2[:slots], count[:npairs], slot
+
+    def match_pairs_device(self, d_feat: int, set_off, pairs, mparams: ScMatchParams, d_corr: int, d_d2: int, d_count: int):
+        """sc_match_pairs_device: the table's descriptors and the outputs in HBM (d_corr slot[P] x 2 int32, d_d2 slot[P] float32,
+        d_count 2 x P uint32), set_off and pairs HOST arrays; enqueues on the context's stream and returns without waiting."""
+        set_off, pairs, ns, npairs = self._table(set_off, pairs)
+        self._frame_n = 0
+        self._check(self._lib.sc_match_pairs_device(self._h, d_feat, _p(set_off, C.c_uint32), ns, _p(pairs, C.c_uint32), npairs,
+                                                    C.byref(mparams), d_corr, d_d2, d_count))
+
+    def register_pairs_features(self, pts, feat, set_off, pairs, mparams: ScMatchParams | None = None, params: ScParams | None = None,
+                                knn: int = 1, mutual: bool = False, ratio: float = 0.0, **kw):
+        """sc_register_pairs_features: pts the table's points in params' layout ((total, 3), or (3, total) with SC_SOA), feat
+        (total, D), set_off, pairs as match_pairs' -> (records (P,) of BATCH_RESULT_DTYPE, corr, d2, count (P, 2), mask (slots,),
+        slot (P + 1,)): the match of every pair, then sc_register_batch's kernel on the matched points."""
+        pts, feat = _f32c(pts), _f32c(feat)
+        p = params or make_params(**kw)
+        m = mparams or make_match_params(feat.shape[1], knn, mutual, ratio)
+        set_off, pairs, ns, npairs = self._table(set_off, pairs)
+        slot = self.pairs_layout(set_off, pairs, int(m.knn))
+        slots = int(slot[-1])
+        res = np.zeros(max(npairs, 1), BATCH_RESULT_DTYPE); mask = np.zeros(max(slots, 1), np.uint8)
+        corr = np.zeros((max(slots, 1), 2), np.int32); d2 = np.zeros(max(slots, 1), np.float32); count = np.zeros((max(npairs, 1), 2), np.uint32)
+        self._frame_n = 0
+        self._check(self._lib.sc_register_pairs_features(self._h, _p(pts, C.c_float), _p(feat, C.c_float), _p(set_off, C.c_uint32), ns,
+                                                         _p(pairs, C.c_uint32), npairs, C.byref(m), C.byref(p),
+                                                         res.ctypes.data_as(C.c_void_p), _p(corr, C.c_int32), _p(d2, C.c_float),
+                                                         _p(count, C.c_uint32), _p(mask, C.c_uint8)))
+        return res[:npairs], corr[:slots], d2[:slots], count[:npairs], mask[:slots], slot
+
+    def register_pairs_features_device(self, d_pts: int, d_feat: int, set_off, pairs, mparams: ScMatchParams, params: ScParams,
+                                       d_res: int, d_corr: int, d_d2: int, d_count: int, d_mask: int):
+        """sc_register_pairs_features_device: everything but set_off and pairs in HBM (d_res P records of 80 bytes, d_mask slot[P]
+        bytes, the rest as match_pairs_device); enqueues on the context's stream and returns without waiting."""
+        set_off, pairs, ns, npairs = self._table(set_off, pairs)
+        self._frame_n = 0
+        self._check(self._lib.sc_register_pairs_features_device(self._h, d_pts, d_feat, _p(set_off, C.c_uint32), ns, _p(pairs, C.c_uint32),
+                                                                npairs, C.byref(mparams), C.byref(params), d_res, d_corr, d_d2, d_count,
+                                                                d_mask))
+
+    def polish_pairs_slots_device(self, d_pts: int, set_off, pairs, knn: int, params: ScParams, pparams: ScPolishParams, d_corr: int,
+                                  d_count: int, d_res: int, d_pol: int, d_mask: int):
+        """sc_polish_pairs_slots_device: behind register_pairs_features_device — its points, set_off, pairs, d_corr, d_count and
+        d_res; d_pol P records of 64 bytes, d_mask slot[P] bytes; enqueues on the context's stream and returns without waiting."""
+        set_off, pairs, ns, npairs = self._table(set_off, pairs)
+        self._frame_n = 0
+        self._check(self._lib.sc_polish_pairs_slots_device(self._h, d_pts, _p(set_off, C.c_uint32), ns, _p(pairs, C.c_uint32), npairs, knn,
+                                                           C.byref(params), C.byref(pparams), d_corr, d_count, d_res, d_pol, d_mask))
 
     def hypothesize_device(self, d_src: int, d_tgt: int, n: int, params: ScParams, d_key: int):
         st = ScStats(C.sizeof(ScStats))

@@ -14,6 +14,7 @@ __device__ __forceinline__ const BatchJob& job_of(const InstBatchJob& a) { retur
 __device__ __forceinline__ const BatchJob& job_of(const InstBatchSlotJob& a) { return a.job; }
 __device__ __forceinline__ const PolishBatchJob& job_of(const PolishBatchJob& a) { return a; }
 __device__ __forceinline__ const PolishBatchJob& job_of(const PolishBatchSlotJob& a) { return a.job; }
+__device__ __forceinline__ const PolishBatchJob& job_of(const PolishBatchPairsJob& a) { return a.job; }
 
 // Staging: rows [off, off + n) of src / tgt (n x 3 row-major, or with soa three planes of `total`) -> pt (px py pz qx qy qz).
 // true: THIS thread read a non-finite coordinate (the caller ends the problem with SC_EINVAL).

@@ -11,7 +11,8 @@
 
 using namespace sc;
 
-namespace {
+// What sc_polish_pairs_slots_device (sc_capi_pairs.hip) shares with the entries here (declared in sc_ctx.hpp).
+namespace sc {
 
 // sc_polish_params as a batch takes them: one candidate per problem
 int pbatch_pparams_check(sc_ctx* c, const sc_polish_params* pp, const char* who) {
@@ -22,16 +23,8 @@ int pbatch_pparams_check(sc_ctx* c, const sc_polish_params* pp, const char* who)
   return SC_OK;
 }
 
-int pbatch_check(sc_ctx* c, const uint32_t* offset, uint32_t n_problems, const sc_params* p, const sc_polish_params* pp) {
-  SC_TRY(entry_checks(c, nullptr, ENDS_FRAME | NOT_BUSY));
-  SC_TRY(batch_params_check(c, p, "sc_polish_batch"));
-  SC_TRY(pbatch_pparams_check(c, pp, "sc_polish_batch"));
-  if (const char* what = batch_offsets_error(offset, n_problems)) return refuse(c, "sc_polish_batch", what);
-  return SC_OK;
-}
-
 // what the kernel reads of the two parameter blocks (the pointers are the caller's)
-PolishBatchJob job_of(const sc_params* p, const sc_polish_params* pp) {
+PolishBatchJob pbatch_job(const sc_params* p, const sc_polish_params* pp) {
   const Derived dv = derive(p);
   PolishBatchJob job{};
   job.soa = p->layout == SC_SOA; job.score_mode = p->score_mode; job.max_iter = pp->max_iter;
@@ -40,10 +33,22 @@ PolishBatchJob job_of(const sc_params* p, const sc_polish_params* pp) {
   return job;
 }
 
+}  // namespace sc
+
+namespace {
+
+int pbatch_check(sc_ctx* c, const uint32_t* offset, uint32_t n_problems, const sc_params* p, const sc_polish_params* pp) {
+  SC_TRY(entry_checks(c, nullptr, ENDS_FRAME | NOT_BUSY));
+  SC_TRY(batch_params_check(c, p, "sc_polish_batch"));
+  SC_TRY(pbatch_pparams_check(c, pp, "sc_polish_batch"));
+  if (const char* what = batch_offsets_error(offset, n_problems)) return refuse(c, "sc_polish_batch", what);
+  return SC_OK;
+}
+
 int pbatch_enqueue(sc_ctx* c, const float* d_src, const float* d_tgt, const uint32_t* offset, uint32_t n_problems, const sc_params* p,
                    const sc_polish_params* pp, const sc_batch_result* d_res, sc_polish_batch_result* d_pol, uint8_t* d_mask) {
   SC_TRY(batch_offsets_to_device(c, offset, n_problems, c->pbatch_off));
-  PolishBatchJob job = job_of(p, pp);
+  PolishBatchJob job = pbatch_job(p, pp);
   job.src = d_src; job.tgt = d_tgt; job.offset = c->pbatch_off.as<uint32_t>();
   job.n_problems = n_problems; job.total = offset[n_problems];
   job.in = reinterpret_cast<const BatchRecord*>(d_res); job.out = reinterpret_cast<PolishBatchRecord*>(d_pol); job.mask = d_mask;
@@ -115,7 +120,7 @@ int sc_polish_batch_slots_device(sc_ctx* c, const float* d_src_pts, const uint32
   SC_TRY(batch_staging_send(c, c->pbatch_off, bytes));
   const uint32_t* meta = c->pbatch_off.as<uint32_t>();
   PolishBatchSlotJob slots{};
-  slots.job = job_of(p, pp);
+  slots.job = pbatch_job(p, pp);
   PolishBatchJob& job = slots.job;
   job.src = d_src_pts; job.tgt = d_tgt_pts; job.offset = meta;
   job.n_problems = n_problems; job.total = src_off[n_problems];

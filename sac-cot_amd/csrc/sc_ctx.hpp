@@ -108,14 +108,15 @@ struct Workspace {
       // sc_register_batch: allocated by the first batch call, never by a frame.  off: the copy of the caller's offsets; the rest:
       // device copies of the host entry's arrays
       batch_off, batch_src, batch_tgt, batch_res, batch_mask,
-      // sc_match_batch / sc_register_batch_features: allocated by the first such call, never by a frame.  meta: the copies of both
-      // offset arrays, the slot starts and the tile map; top: the rows' lists between the two launches; words: a "clean" word per
+      // sc_match_batch / sc_register_batch_features, and sc_match_pairs / sc_register_pairs_features (a pair is a problem of theirs,
+      // found through a record): allocated by the first such call, never by a frame.  meta: the copies of both offset arrays, the
+      // slot starts and the tile map (pairs: the pairs' records, the slot starts, the tile map); top: the rows' lists between the two launches; words: a "clean" word per
       // problem, then the column minima; gsrc / gtgt: the gathered points, slot-positioned; the rest: device copies of the host
-      // entries' arrays
+      // entries' arrays (pairs: fsrc / psrc hold the one table)
       mbatch_meta, mbatch_top, mbatch_words, mbatch_gsrc, mbatch_gtgt, mbatch_fsrc, mbatch_ftgt, mbatch_psrc, mbatch_ptgt, mbatch_corr,
       mbatch_d2, mbatch_count, mbatch_res, mbatch_mask,
       // sc_polish_batch: allocated by the first such call, never by a frame or by another batch entry.  off: the copy of the caller's
-      // offsets (the slot form: both arrays and the slot starts); the rest: device copies of the host entry's arrays
+      // offsets (the slot form: both arrays and the slot starts; the pairs form: the pairs' records); the rest: device copies of the host entry's arrays
       pbatch_off, pbatch_src, pbatch_tgt, pbatch_res, pbatch_pol, pbatch_mask,
       // sc_register_instances_batch: allocated by the first such call, never by a frame or by another batch entry.  off: the copy of
       // the caller's offsets; the rest: device copies of the host entry's arrays (the features form holds what
@@ -269,6 +270,12 @@ int mbatch_enqueue(sc_ctx* c, const MatchJob& mj, const MatchBatchSizes& sz, con
 MatchGather gather_of(const sc_ctx* c, const sc_params* p, const MatchBatchSizes& sz, const float* d_src_pts, const float* d_tgt_pts);
 // the registration kernel's argument on those slots, but for its outputs
 BatchJob mbatch_slots_job(const sc_ctx* c, const MatchBatchSizes& sz, const sc_params* p);
+
+// ---- defined in sc_capi_polish_batch.hip, used by sc_capi_pairs.hip as well
+// sc_polish_params as a batch takes them (one candidate per problem); `who` opens the message
+int pbatch_pparams_check(sc_ctx* c, const sc_polish_params* pp, const char* who);
+// what the polish kernel reads of the two parameter blocks (the pointers are the caller's)
+PolishBatchJob pbatch_job(const sc_params* p, const sc_polish_params* pp);
 
 // ---- a call on a scored frame (sc_peel, sc_polish): what the two share in front of their launches and behind them
 // The entry checks, `busy` first, then "is there a frame"; the refusal names the caller.  Then the context's device.

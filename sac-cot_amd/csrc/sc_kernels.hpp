@@ -776,9 +776,19 @@ struct PolishBatchSlotJob {
   const int32_t* corr; const uint32_t* count;
   uint32_t knn, total_t;
 };
+// The pairs form (behind sc_register_pairs_features): job.src == job.tgt are the POINTS of the table of sets (job.total its rows;
+// job.offset is not read), and pair p's two sets, its slot and its correspondences are what rec + PAIR_WORDS * p says (PairWord,
+// below); corr, count and the mask bytes as in the slot form.  A third type, for the same reason.
+struct PolishBatchPairsJob {
+  PolishBatchJob job;
+  const uint32_t* rec;
+  const int32_t* corr; const uint32_t* count;
+  uint32_t knn;
+};
 // One workgroup per problem, every refit inside the launch; every record and mask range is written (complete in stream order).
 void launch_polish_batch(const PolishBatchJob& job, hipStream_t st);
 void launch_polish_batch_slots(const PolishBatchSlotJob& job, hipStream_t st);
+void launch_polish_batch_pairs(const PolishBatchPairsJob& job, hipStream_t st);
 
 // ---- descriptor matching for a batch of small problems (sc_match_batch; sc_match_batch.hip) -----------------
 // Problem b owns rows [src_off[b], src_off[b + 1]) of fsrc and [tgt_off[b], tgt_off[b + 1]) of ftgt (1 .. MATCH_BATCH_MAX_N rows
@@ -802,5 +812,32 @@ struct MatchBatchJob {
 void launch_match_batch_dist(const MatchBatchJob& job, hipStream_t st);
 // a workgroup per problem: mutual / ratio per row, compaction inside the slot in ascending (row, rank) order, the count pair, the gather
 void launch_match_batch_finish(const MatchBatchJob& job, hipStream_t st);
+
+// ---- the same for listed pairs of shared sets (sc_match_pairs; sc_match_batch.hip, sc_polish_batch.hip) ----------------
+// One table of sets, feat (total x dim), and a list of pairs drawn from it: the problems of the launches are the PAIRS.  A set
+// serves many pairs, so nothing of a pair can be addressed by its sets' rows: pair p has a record of PAIR_WORDS words (built on the
+// host, sc_pairs_check.hpp) with the first row and the size of both its sets in the table and the bases that are the pair's OWN —
+// its rows' lists in `top`, its column minima in `colmin` (two pairs that share a target set do not share minima), its slot.
+enum PairWord : int {
+  PW_SRC = 0, PW_NS,   // the source set: first row in the table, rows (1 .. MATCH_BATCH_MAX_N, checked by the caller)
+  PW_TGT, PW_NT,       // the target set
+  PW_TOP,              // the pair's first row in `top`: the source rows of the pairs before it (slot / knn)
+  PW_SLOT,             // the pair's first output entry: knn x PW_TOP
+  PW_COL_LO, PW_COL_HI,  // the pair's first key in `colmin`: the target rows of the pairs before it (64 bits: it may pass 2^32)
+  PAIR_WORDS
+};
+// A type of its own, so that the packed form's kernel argument and code stay what they were.  tile_map: n_tiles pairs (pair, first
+// row of the tile inside its source set); g.src == g.tgt: the table's points.
+struct MatchPairsJob {
+  const float* feat;
+  const uint32_t* rec; const uint32_t* tile_map;
+  uint32_t n_problems, n_tiles, dim, knn, kp, mutual;
+  float r2;
+  uint64_t* top; uint64_t* colmin; uint32_t* clean;  // as MatchBatchJob's, at the pair's own bases; a `clean` word per pair
+  int32_t* corr; float* d2; uint32_t* count;
+  MatchGather g;
+};
+void launch_match_pairs_dist(const MatchPairsJob& job, hipStream_t st);
+void launch_match_pairs_finish(const MatchPairsJob& job, hipStream_t st);
 
 }  // namespace sc

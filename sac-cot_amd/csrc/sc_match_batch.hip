@@ -18,6 +18,11 @@
 //                              (row, rank) order with their indices local to the problem; the matched points are gathered
 //                              beside them for sc_register_batch_features; thread 0 writes the count pair.  No look-back across
 //                              problems: a slot's position is known on the host.
+//
+// Both kernels are written once for two arguments: MatchBatchJob — packed problems, addressed by their offsets — and MatchPairsJob
+// (sc_match_pairs: listed pairs of shared sets, addressed by a record per pair, sc_kernels.hpp).  What differs is where a problem's
+// rows, lists, column minima and slot start: MatchView, filled by view_of for either argument; everything behind it is one text, so
+// a pair's slot holds what the packed form returns for the pair expanded.  The packed instantiation reads what it always read.
 #include <cstddef>
 
 #include "sc_block.hpp"
@@ -35,8 +40,26 @@ constexpr int MB_LD = 64 + 4;  // 16-byte aligned rows; the pad spreads the tran
 constexpr int MBF_THREADS = 256;
 static_assert(MB_ROWS == 64 && MB_THREADS == (MB_ROWS / 8) * (MB_COLS / 4), "a thread owns 8 rows x 4 columns of the tile");
 
-template <int KP>
-__global__ __launch_bounds__(MB_THREADS) void match_batch_dist_kernel(const MatchBatchJob job) {
+// Where problem b's data starts.  top_row / col: the problem's first row of lists and first column minimum — the packed form's are
+// its offsets, a pair's are its own (a set that is the target of two pairs has two ranges of minima).
+struct MatchView {
+  const float* fsrc; const float* ftgt;  // the problem's first descriptor row, either side
+  uint32_t so, to, ns, nt;               // first point row and rows, either side (the gather's)
+  size_t top_row, col, slot;
+};
+__device__ __forceinline__ MatchView view_of(const MatchBatchJob& job, uint32_t b) {
+  const uint32_t so = job.src_off[b], to = job.tgt_off[b];
+  return MatchView{job.fsrc + (size_t)so * job.dim, job.ftgt + (size_t)to * job.dim, so, to, job.src_off[b + 1] - so, job.tgt_off[b + 1] - to,
+                   so, to, job.slot[b]};
+}
+__device__ __forceinline__ MatchView view_of(const MatchPairsJob& job, uint32_t p) {
+  const uint32_t* r = job.rec + (size_t)PAIR_WORDS * p;
+  return MatchView{job.feat + (size_t)r[PW_SRC] * job.dim, job.feat + (size_t)r[PW_TGT] * job.dim, r[PW_SRC], r[PW_TGT], r[PW_NS], r[PW_NT],
+                   r[PW_TOP], (size_t)r[PW_COL_LO] | (size_t)r[PW_COL_HI] << 32, r[PW_SLOT]};
+}
+
+template <int KP, class Job>
+__global__ __launch_bounds__(MB_THREADS) void match_batch_dist_kernel(const Job job) {
   __shared__ __attribute__((aligned(16))) float sA[MT_KC][MB_LD];
   __shared__ __attribute__((aligned(16))) float sB[MT_KC][MB_LD];
   __shared__ unsigned long long s_top[MB_ROWS][KP];
@@ -45,11 +68,11 @@ __global__ __launch_bounds__(MB_THREADS) void match_batch_dist_kernel(const Matc
   if (blockIdx.x >= job.n_tiles) return;
   const uint32_t b = job.tile_map[2 * blockIdx.x], row0 = job.tile_map[2 * blockIdx.x + 1];
   if (b >= job.n_problems) return;  // (cannot happen: the host built the map)
-  const uint32_t so = job.src_off[b], to = job.tgt_off[b];
-  const uint32_t ns = job.src_off[b + 1] - so, nt = job.tgt_off[b + 1] - to, D = job.dim;
-  const float* __restrict__ fsrc = job.fsrc + (size_t)so * D;
-  const float* __restrict__ ftgt = job.ftgt + (size_t)to * D;
-  unsigned long long* const colmin = job.colmin ? reinterpret_cast<unsigned long long*>(job.colmin) + to : nullptr;
+  const MatchView v = view_of(job, b);
+  const uint32_t ns = v.ns, nt = v.nt, D = job.dim;
+  const float* __restrict__ fsrc = v.fsrc;
+  const float* __restrict__ ftgt = v.ftgt;
+  unsigned long long* const colmin = job.colmin ? reinterpret_cast<unsigned long long*>(job.colmin) + v.col : nullptr;
   const uint32_t n_tiles = (nt + MB_COLS - 1) / MB_COLS;
   for (int e = threadIdx.x; e < MB_ROWS * KP; e += MB_THREADS) (&s_top[0][0])[e] = KEY_NONE;
   bool bad = false;
@@ -94,7 +117,7 @@ __global__ __launch_bounds__(MB_THREADS) void match_batch_dist_kernel(const Matc
     for (int r = 0; r < 8; r++) {
       const uint32_t lr = ty * 8 + r, row = row0 + lr;
       if (row >= ns) continue;
-      const float v[4] = {acc[r][0].x, acc[r][0].y, acc[r][1].x, acc[r][1].y};
+      const float d[4] = {acc[r][0].x, acc[r][0].y, acc[r][1].x, acc[r][1].y};
       unsigned long long* list = &s_top[lr][0];
       // what the list's last slot holds only ever falls: an old value lets a candidate through that the cascade then passes out again
       const unsigned long long worst = *reinterpret_cast<volatile unsigned long long*>(&list[KP - 1]);
@@ -102,7 +125,7 @@ __global__ __launch_bounds__(MB_THREADS) void match_batch_dist_kernel(const Matc
 #pragma unroll
       for (int cc = 0; cc < 4; cc++) {
         if (colb + cc >= nt) continue;
-        const unsigned long long hi = (unsigned long long)__float_as_uint(v[cc]) << 32;
+        const unsigned long long hi = (unsigned long long)__float_as_uint(d[cc]) << 32;
         const unsigned long long key = hi | (colb + cc);
         const unsigned long long rkey = hi | row;
         cmin[cc] = rkey < cmin[cc] ? rkey : cmin[cc];
@@ -117,30 +140,31 @@ __global__ __launch_bounds__(MB_THREADS) void match_batch_dist_kernel(const Matc
         if (cmin[cc] != KEY_NONE) atomicMin(&s_col[tx * 4 + cc], cmin[cc]);
       __syncthreads();
       if (threadIdx.x < MB_COLS && col0 + threadIdx.x < nt) {
-        const unsigned long long v = s_col[threadIdx.x];
+        const unsigned long long m = s_col[threadIdx.x];
         unsigned long long* g = &colmin[col0 + threadIdx.x];
-        if (v < __hip_atomic_load(g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(g, v);
+        if (m < __hip_atomic_load(g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(g, m);
       }
     }
   }
   __syncthreads();
   if (threadIdx.x < MB_ROWS && row0 + threadIdx.x < ns) {
-    unsigned long long* out = reinterpret_cast<unsigned long long*>(job.top) + ((size_t)so + row0 + threadIdx.x) * KP;
+    unsigned long long* out = reinterpret_cast<unsigned long long*>(job.top) + (v.top_row + row0 + threadIdx.x) * KP;
 #pragma unroll
     for (int q = 0; q < KP; q++) out[q] = s_top[threadIdx.x][q];
   }
   if (bad) __hip_atomic_store(&job.clean[b], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-__global__ __launch_bounds__(MBF_THREADS) void match_batch_finish_kernel(const MatchBatchJob job) {
+template <class Job>
+__global__ __launch_bounds__(MBF_THREADS) void match_batch_finish_kernel(const Job job) {
   __shared__ uint64_t s_scan[MBF_THREADS / 64];
   const uint32_t b = blockIdx.x;
-  const uint32_t so = job.src_off[b], to = job.tgt_off[b];
-  const uint32_t ns = job.src_off[b + 1] - so, nt = job.tgt_off[b + 1] - to;
-  const size_t slot = job.slot[b], cap = (size_t)ns * job.knn;
+  const MatchView v = view_of(job, b);
+  const uint32_t so = v.so, to = v.to, ns = v.ns, nt = v.nt;
+  const size_t slot = v.slot, cap = (size_t)ns * job.knn;
   const bool ok = job.clean[b] != 0u;  // (written by the launch before this one)
-  const unsigned long long* __restrict__ top = reinterpret_cast<const unsigned long long*>(job.top) + (size_t)so * job.kp;
-  const unsigned long long* __restrict__ colmin = job.colmin ? reinterpret_cast<const unsigned long long*>(job.colmin) + to : nullptr;
+  const unsigned long long* __restrict__ top = reinterpret_cast<const unsigned long long*>(job.top) + v.top_row * job.kp;
+  const unsigned long long* __restrict__ colmin = job.colmin ? reinterpret_cast<const unsigned long long*>(job.colmin) + v.col : nullptr;
   const MatchGather g = job.g;
   uint32_t run = 0;  // kept so far, by the rows before this step's
   for (uint32_t base = 0; ok && base < ns; base += MBF_THREADS) {
@@ -193,18 +217,29 @@ __global__ __launch_bounds__(MBF_THREADS) void match_batch_finish_kernel(const M
 
 }  // namespace
 
-void launch_match_batch_dist(const MatchBatchJob& job, hipStream_t st) {
+namespace {
+
+template <class Job>
+void launch_dist(const Job& job, hipStream_t st) {
   const dim3 grid(job.n_tiles), block(MB_THREADS);
   switch (job.kp) {
-    case 1: hipLaunchKernelGGL(match_batch_dist_kernel<1>, grid, block, 0, st, job); break;
-    case 2: hipLaunchKernelGGL(match_batch_dist_kernel<2>, grid, block, 0, st, job); break;
-    case 3: hipLaunchKernelGGL(match_batch_dist_kernel<3>, grid, block, 0, st, job); break;
-    default: hipLaunchKernelGGL(match_batch_dist_kernel<4>, grid, block, 0, st, job); break;
+    case 1: hipLaunchKernelGGL((match_batch_dist_kernel<1, Job>), grid, block, 0, st, job); break;
+    case 2: hipLaunchKernelGGL((match_batch_dist_kernel<2, Job>), grid, block, 0, st, job); break;
+    case 3: hipLaunchKernelGGL((match_batch_dist_kernel<3, Job>), grid, block, 0, st, job); break;
+    default: hipLaunchKernelGGL((match_batch_dist_kernel<4, Job>), grid, block, 0, st, job); break;
   }
 }
 
+}  // namespace
+
+void launch_match_batch_dist(const MatchBatchJob& job, hipStream_t st) { launch_dist(job, st); }
+void launch_match_pairs_dist(const MatchPairsJob& job, hipStream_t st) { launch_dist(job, st); }
+
 void launch_match_batch_finish(const MatchBatchJob& job, hipStream_t st) {
-  hipLaunchKernelGGL(match_batch_finish_kernel, dim3(job.n_problems), dim3(MBF_THREADS), 0, st, job);
+  hipLaunchKernelGGL(match_batch_finish_kernel<MatchBatchJob>, dim3(job.n_problems), dim3(MBF_THREADS), 0, st, job);
+}
+void launch_match_pairs_finish(const MatchPairsJob& job, hipStream_t st) {
+  hipLaunchKernelGGL(match_batch_finish_kernel<MatchPairsJob>, dim3(job.n_problems), dim3(MBF_THREADS), 0, st, job);
 }
 
 }  // namespace sc

@@ -7,7 +7,7 @@
 // sc_polish(candidates = 1) returns for the same input pose:
 //
 //   staging    either layout -> the planes with the finiteness test on the way (sc_batch_frame.hpp, shared with sc_batch.hip); the
-//              slot form gathers through corr while it stages.  A non-finite coordinate, or a non-finite input (R, t): SC_EINVAL
+//              slot form and the pairs form gather through corr while they stage.  A non-finite coordinate, or a non-finite input (R, t): SC_EINVAL
 //              for THIS problem.
 //   score0     the input pose's score over all n (score_term, a sum of integers).
 //   iteration  refit_iterate on PolishChunks: 7 x ceil(n / 64) <= 56 and 9 x <= 72 chains, one round of the lane deal each.
@@ -62,21 +62,39 @@ __device__ __forceinline__ void record_fill(PolishLds& L, const float* Rt, int s
   L.rec[12] = (uint32_t)status; L.rec[13] = score0; L.rec[14] = score; L.rec[15] = iters | (stop << 16);
 }
 
-// The kernel's argument is PolishBatchJob (sc_polish_batch) or PolishBatchSlotJob (sc_polish_batch_slots_device, sc_kernels.hpp):
-// SLOTS is a constant of the instantiation, and nothing of the slot form is compiled into the plain one.
+// Where a gathering form finds problem b: the first row and the rows of its points on either side (src planes of job.total, tgt
+// planes of total_t), and its slot.  The slot form reads its two monotone offset arrays; the pairs form the pair's record — both
+// sides come from one table, and a set may serve many pairs.
+struct PolishSides { uint32_t off, rows, toff, trows, total_t, slot; };
+__device__ __forceinline__ PolishSides sides_of(const PolishBatchJob& job, uint32_t b) {  // plain: the problem's correspondences
+  const uint32_t off = job.offset[b];
+  return PolishSides{off, job.offset[b + 1] - off, 0u, 0u, 0u, off};
+}
+__device__ __forceinline__ PolishSides sides_of(const PolishBatchSlotJob& a, uint32_t b) {
+  const uint32_t off = a.job.offset[b], toff = a.tgt_off[b];
+  return PolishSides{off, a.job.offset[b + 1] - off, toff, a.tgt_off[b + 1] - toff, a.total_t, a.slot[b]};
+}
+__device__ __forceinline__ PolishSides sides_of(const PolishBatchPairsJob& a, uint32_t p) {
+  const uint32_t* r = a.rec + (size_t)PAIR_WORDS * p;
+  return PolishSides{r[PW_SRC], r[PW_NS], r[PW_TGT], r[PW_NT], a.job.total, r[PW_SLOT]};
+}
+
+// The kernel's argument is PolishBatchJob (sc_polish_batch), PolishBatchSlotJob (sc_polish_batch_slots_device) or
+// PolishBatchPairsJob (sc_polish_pairs_slots_device; sc_kernels.hpp): SLOTS — the problem is gathered through corr — is a constant of
+// the instantiation, and nothing of the gathering forms is compiled into the plain one.
 template <class Arg>
 __global__ __launch_bounds__(PT) void polish_batch_kernel(const Arg arg) {
   constexpr bool SLOTS = sizeof(Arg) != sizeof(PolishBatchJob);
   const PolishBatchJob& job = job_of(arg);
   __shared__ PolishLds L;
   const int tid = threadIdx.x;
-  const uint32_t off = job.offset[blockIdx.x];
-  const uint32_t rows = job.offset[blockIdx.x + 1] - off;  // plain: the problem's correspondences; slots: its source points
-  int n = (int)rows;                                        // 3 .. PN: the host checked (slots: decided on the device, checked below)
-  uint32_t at = off;                                        // where the problem's mask bytes start
+  const PolishSides sd = sides_of(arg, blockIdx.x);
+  const uint32_t off = sd.off;
+  const uint32_t rows = sd.rows;  // plain: the problem's correspondences; slots: its source points
+  int n = (int)rows;              // 3 .. PN: the host checked (slots: decided on the device, checked below)
+  const uint32_t at = sd.slot;    // where the problem's mask bytes start
   bool unfit = false;
   if constexpr (SLOTS) {
-    at = arg.slot[blockIdx.x];
     const uint32_t cnt = arg.count[2 * blockIdx.x], cap = rows * arg.knn;  // (cap <= PN: the host checked)
     const bool flagged = arg.count[2 * blockIdx.x + 1] != 0u;
     unfit = flagged || cnt < 3u || cnt > cap;
@@ -98,14 +116,14 @@ __global__ __launch_bounds__(PT) void polish_batch_kernel(const Arg arg) {
   {
     bool bad = false;
     if constexpr (SLOTS) {
-      const uint32_t toff = arg.tgt_off[blockIdx.x], trows = arg.tgt_off[blockIdx.x + 1] - toff;
+      const uint32_t toff = sd.toff, trows = sd.trows;
       for (int m = tid; m < n; m += PT) {
         const uint32_t i = (uint32_t)arg.corr[2 * ((size_t)at + m)], j = (uint32_t)arg.corr[2 * ((size_t)at + m) + 1];
         if (i >= rows || j >= trows) { bad = true; continue; }  // (an index the match cannot have written: nothing is read through it)
 #pragma unroll
         for (int c = 0; c < 3; c++) {
           const float p = job.src[job.soa ? (size_t)c * job.total + off + i : ((size_t)off + i) * 3 + c];
-          const float q = job.tgt[job.soa ? (size_t)c * arg.total_t + toff + j : ((size_t)toff + j) * 3 + c];
+          const float q = job.tgt[job.soa ? (size_t)c * sd.total_t + toff + j : ((size_t)toff + j) * 3 + c];
           bad = bad || !(fabsf(p) < __builtin_inff()) || !(fabsf(q) < __builtin_inff());
           L.pt[c][m] = p; L.pt[3 + c][m] = q;
         }
@@ -164,6 +182,10 @@ void launch_polish_batch(const PolishBatchJob& job, hipStream_t st) {
 
 void launch_polish_batch_slots(const PolishBatchSlotJob& job, hipStream_t st) {
   hipLaunchKernelGGL(polish_batch_kernel<PolishBatchSlotJob>, dim3(job.job.n_problems), dim3(PT), 0, st, job);
+}
+
+void launch_polish_batch_pairs(const PolishBatchPairsJob& job, hipStream_t st) {
+  hipLaunchKernelGGL(polish_batch_kernel<PolishBatchPairsJob>, dim3(job.job.n_problems), dim3(PT), 0, st, job);
 }
 
 }  // namespace sc
