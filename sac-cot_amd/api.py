@@ -298,6 +298,22 @@ def _f32c(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
+def _pack_problems(problems, layout):
+    """A list of (src (n_b, 3), tgt (n_b, 3)) problems -> the packed (src, tgt, offset) of the batch entries, the points in `layout`."""
+    sizes = [np.shape(s)[0] for s, _ in problems]
+    src = np.concatenate([_f32c(s).reshape(-1, 3) for s, _ in problems]) if sizes else np.zeros((0, 3), np.float32)
+    tgt = np.concatenate([_f32c(t).reshape(-1, 3) for _, t in problems]) if sizes else np.zeros((0, 3), np.float32)
+    if layout == SC_SOA:
+        src, tgt = np.ascontiguousarray(src.T), np.ascontiguousarray(tgt.T)
+    return src, tgt, Registrar._offsets(sizes)
+
+
+def _record_dict(r) -> dict:
+    """A BATCH_RESULT_DTYPE record as dict(status, R, t, stats)."""
+    stats = {k: int(r[k]) for k in ("n", "edges", "tri_total", "tri_kept", "best_rank", "best_count")}
+    return dict(status=int(r["status"]), R=r["Rt"][:9].reshape(3, 3).copy(), t=r["Rt"][9:].copy(), stats=stats)
+
+
 class Registrar:
     """One GPU context (`sc_ctx`): one process, one GPU, one stream."""
 
@@ -424,19 +440,9 @@ class Registrar:
         if isinstance(problems, tuple) and len(problems) == 3 and not isinstance(problems[0], tuple):
             src, tgt, offset = problems
         else:
-            sizes = [np.shape(s)[0] for s, _ in problems]
-            offset = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint32)
-            src = np.concatenate([_f32c(s).reshape(-1, 3) for s, _ in problems]) if sizes else np.zeros((0, 3), np.float32)
-            tgt = np.concatenate([_f32c(t).reshape(-1, 3) for _, t in problems]) if sizes else np.zeros((0, 3), np.float32)
-            if p.layout == SC_SOA:
-                src, tgt = np.ascontiguousarray(src.T), np.ascontiguousarray(tgt.T)
+            src, tgt, offset = _pack_problems(problems, p.layout)
         res, mask = self.register_batch_raw(src, tgt, offset, p)
-        out = []
-        for b, r in enumerate(res):
-            stats = {k: int(r[k]) for k in ("n", "edges", "tri_total", "tri_kept", "best_rank", "best_count")}
-            out.append(dict(status=int(r["status"]), R=r["Rt"][:9].reshape(3, 3).copy(), t=r["Rt"][9:].copy(),
-                            mask=mask[int(offset[b]): int(offset[b + 1])].copy(), stats=stats))
-        return out
+        return [dict(_record_dict(r), mask=mask[int(offset[b]): int(offset[b + 1])].copy()) for b, r in enumerate(res)]
 
     def register_batch_device(self, d_src: int, d_tgt: int, offset, params: ScParams, d_res: int, d_mask: int):
         """sc_register_batch_device: points, records (80 bytes each) and mask in HBM, offset a HOST array (B + 1,) uint32; enqueues
@@ -630,9 +636,7 @@ class Registrar:
         out = []
         for b, r in enumerate(res):
             lo, k = int(so[b]) * int(m.knn), int(count[b, 0])
-            stats = {f: int(r[f]) for f in ("n", "edges", "tri_total", "tri_kept", "best_rank", "best_count")}
-            out.append(dict(status=int(r["status"]), R=r["Rt"][:9].reshape(3, 3).copy(), t=r["Rt"][9:].copy(),
-                            mask=mask[lo: lo + k].copy(), stats=stats, n=k, corr=corr[lo: lo + k].copy(), d2=d2[lo: lo + k].copy()))
+            out.append(dict(_record_dict(r), mask=mask[lo: lo + k].copy(), n=k, corr=corr[lo: lo + k].copy(), d2=d2[lo: lo + k].copy()))
         return out
 
     def register_batch_features_device(self, d_src_pts: int, d_fsrc: int, src_off, d_tgt_pts: int, d_ftgt: int, tgt_off,
@@ -691,22 +695,15 @@ class Registrar:
         score, iters, stop) — the winner refitted over its own inliers until nothing changes (at most max_iter refits)."""
         p = params or make_params(**kw)
         q = pparams or make_polish_params(candidates=1, max_iter=max_iter)
-        sizes = [np.shape(s)[0] for s, _ in problems]
-        offset = self._offsets(sizes)
-        src = np.concatenate([_f32c(s).reshape(-1, 3) for s, _ in problems]) if sizes else np.zeros((0, 3), np.float32)
-        tgt = np.concatenate([_f32c(t).reshape(-1, 3) for _, t in problems]) if sizes else np.zeros((0, 3), np.float32)
-        if p.layout == SC_SOA:
-            src, tgt = np.ascontiguousarray(src.T), np.ascontiguousarray(tgt.T)
+        src, tgt, offset = _pack_problems(problems, p.layout)
         res, mask = self.register_batch_raw(src, tgt, offset, p)
         pol, pmask = self.polish_batch_raw(src, tgt, offset, p, q, res)
         out = []
         for b, (r, o) in enumerate(zip(res, pol)):
             lo, hi = int(offset[b]), int(offset[b + 1])
-            stats = {k: int(r[k]) for k in ("n", "edges", "tri_total", "tri_kept", "best_rank", "best_count")}
             polished = dict(status=int(o["status"]), R=o["Rt"][:9].reshape(3, 3).copy(), t=o["Rt"][9:].copy(), mask=pmask[lo:hi].copy(),
                             score0=int(o["score0"]), score=int(o["score"]), iters=int(o["iters"]), stop=int(o["stop"]))
-            out.append(dict(status=int(r["status"]), R=r["Rt"][:9].reshape(3, 3).copy(), t=r["Rt"][9:].copy(), mask=mask[lo:hi].copy(),
-                            stats=stats, polished=polished))
+            out.append(dict(_record_dict(r), mask=mask[lo:hi].copy(), polished=polished))
         return out
 
     # ---- several rigid motions per batch problem (include/saccot.h, sc_register_instances_batch) --------------------
@@ -732,19 +729,13 @@ class Registrar:
         0's: sc_register_batch's for the problem), Rt (found, 12), score (found,), label (n_b,) int32, stats (plane 0's counts) — the
         keys of register_instances(), a problem's SC_ENOHYP / SC_EINVAL being its status, not an exception."""
         p = params or make_params(**kw)
-        sizes = [np.shape(s)[0] for s, _ in problems]
-        offset = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint32)
-        src = np.concatenate([_f32c(s).reshape(-1, 3) for s, _ in problems]) if sizes else np.zeros((0, 3), np.float32)
-        tgt = np.concatenate([_f32c(t).reshape(-1, 3) for _, t in problems]) if sizes else np.zeros((0, 3), np.float32)
-        if p.layout == SC_SOA:
-            src, tgt = np.ascontiguousarray(src.T), np.ascontiguousarray(tgt.T)
+        src, tgt, offset = _pack_problems(problems, p.layout)
         res, label, nfound = self.register_instances_batch_raw(src, tgt, offset, p, max_instances, min_score)
         out = []
-        for b in range(len(sizes)):
-            k, r0 = int(nfound[b]), res[0, b]
-            stats = {f: int(r0[f]) for f in ("n", "edges", "tri_total", "tri_kept", "best_rank", "best_count")}
-            out.append(dict(status=int(r0["status"]), Rt=res[:k, b]["Rt"].copy(), score=res[:k, b]["best_count"].copy(),
-                            label=label[int(offset[b]): int(offset[b + 1])].copy(), stats=stats))
+        for b in range(len(offset) - 1):
+            k, r0 = int(nfound[b]), _record_dict(res[0, b])
+            out.append(dict(status=r0["status"], Rt=res[:k, b]["Rt"].copy(), score=res[:k, b]["best_count"].copy(),
+                            label=label[int(offset[b]): int(offset[b + 1])].copy(), stats=r0["stats"]))
         return out
 
     def register_instances_batch_device(self, d_src: int, d_tgt: int, offset, params: ScParams, max_instances: int, min_score: int,

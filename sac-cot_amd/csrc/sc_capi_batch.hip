@@ -1,7 +1,7 @@
 // sc_capi_batch.hip — the C ABI's batched registration (include/saccot.h, sc_register_batch): sc_register_batch_device and
 // sc_register_batch.  Host-only, on the context and the helpers of sc_ctx.hpp; the kernel is sc_batch.hip's.  What every batch
 // entry shares on the host is defined here as well: batch_params_check, batch_offsets_error, the pinned staging area
-// (batch_staging_begin / _send) and batch_offsets_to_device.
+// (batch_staging_begin / _send), batch_offsets_to_device, and HostArrays, the one statement of a host-array entry.
 //
 // offsets -> pinned staging -> device copy (enqueued) -> ONE launch, a workgroup per problem.  Nothing is read back: a problem's
 // status is a field of its record.  Everything that can refuse the call is decided on the host before anything is enqueued.
@@ -23,11 +23,9 @@ int batch_check(sc_ctx* c, const uint32_t* offset, uint32_t n_problems, const sc
 int batch_enqueue(sc_ctx* c, const float* d_src, const float* d_tgt, const uint32_t* offset, uint32_t n_problems, const sc_params* p,
                   sc_batch_result* d_res, uint8_t* d_mask) {
   SC_TRY(batch_offsets_to_device(c, offset, n_problems, c->batch_off));
-  BatchJob job{};
+  BatchJob job = batch_job_of(p);
   job.src = d_src; job.tgt = d_tgt; job.offset = c->batch_off.as<uint32_t>();
   job.n_problems = n_problems; job.total = offset[n_problems];
-  job.soa = p->layout == SC_SOA; job.T = p->max_triangles; job.rank_mode = p->rank_mode; job.score_mode = p->score_mode;
-  job.dv = derive(p);
   job.res = reinterpret_cast<BatchRecord*>(d_res); job.mask = d_mask;
   launch_batch_register(job, c->stream);
   HIPCHK(c, hipGetLastError());
@@ -85,6 +83,27 @@ int batch_offsets_to_device(sc_ctx* c, const uint32_t* offset, uint32_t n_proble
   return batch_staging_send(c, dst, bytes);
 }
 
+int HostArrays::room() {
+  if (n > MAX) return refuse(c, "HostArrays", "more arrays than it holds");
+  for (int i = 0; i < n; i++) ENSURE(c, *arr[i].buf, arr[i].bytes);
+  return SC_OK;
+}
+
+int HostArrays::send() {
+  for (int i = 0; i < n; i++)
+    if (arr[i].from) HIPCHK(c, hipMemcpyAsync(arr[i].buf->p, arr[i].from, arr[i].bytes, hipMemcpyHostToDevice, c->stream));
+  return SC_OK;
+}
+
+int HostArrays::fetch() {
+  for (int pass = 0; pass < 2; pass++)  // those declared `first`, then the others
+    for (int i = 0; i < n; i++)
+      if (arr[i].to && arr[i].first == (pass == 0))
+        HIPCHK(c, hipMemcpyAsync(arr[i].to, arr[i].buf->p, arr[i].bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SC_OK;
+}
+
 }  // namespace sc
 
 extern "C" {
@@ -106,20 +125,17 @@ int sc_register_batch(sc_ctx* c, const float* src, const float* tgt, const uint3
   SC_TRY(batch_check(c, offset, n_problems, p));
   HIPCHK(c, hipSetDevice(c->device));
   c->cap_bytes = workspace_cap(p);
-  const size_t total = offset[n_problems], pts = total * 12, recs = (size_t)n_problems * sizeof(sc_batch_result);
-  ENSURE(c, c->batch_src, pts);
-  ENSURE(c, c->batch_tgt, pts);
-  ENSURE(c, c->batch_res, recs);
-  ENSURE(c, c->batch_mask, total);
-  hipStream_t st = c->stream;
-  HIPCHK(c, hipMemcpyAsync(c->batch_src.p, src, pts, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(c->batch_tgt.p, tgt, pts, hipMemcpyHostToDevice, st));
+  const size_t total = offset[n_problems], pts = total * 12;
+  HostArrays h(c);
+  h.in(c->batch_src, src, pts);
+  h.in(c->batch_tgt, tgt, pts);
+  h.out(c->batch_res, res, (size_t)n_problems * sizeof(sc_batch_result));
+  h.out(c->batch_mask, mask, total);
+  SC_TRY(h.room());
+  SC_TRY(h.send());
   SC_TRY(batch_enqueue(c, c->batch_src.as<float>(), c->batch_tgt.as<float>(), offset, n_problems, p,
                        c->batch_res.as<sc_batch_result>(), c->batch_mask.as<uint8_t>()));
-  HIPCHK(c, hipMemcpyAsync(res, c->batch_res.p, recs, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(mask, c->batch_mask.p, total, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  return SC_OK;
+  return h.fetch();
 }
 
 }  // extern "C"

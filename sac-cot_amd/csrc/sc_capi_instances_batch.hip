@@ -4,7 +4,7 @@
 //
 // offsets -> pinned staging (the area and event every batch entry shares: batch_offsets_to_device) -> device copy (enqueued) -> ONE
 // launch, a workgroup per problem, the rounds inside it.  The features entry runs sc_capi_match_batch.hip's match sequence
-// (mbatch_check / _room / _enqueue) in front of the launch.  Nothing is read back: a problem's status is a field of its records, its
+// (mbatch_check / _room / _enqueue_packed) in front of the launch; the host entry is a HostArrays (sc_ctx.hpp).  Nothing is read back: a problem's status is a field of its records, its
 // number of motions a word in device memory.  Everything that can refuse the call is decided on the host before anything is enqueued.
 #include "sc_ctx.hpp"
 
@@ -36,11 +36,10 @@ int ibatch_enqueue(sc_ctx* c, const float* d_src, const float* d_tgt, const uint
                    uint32_t max_instances, uint32_t min_score, sc_batch_result* d_res, int32_t* d_label, uint32_t* d_nfound) {
   SC_TRY(batch_offsets_to_device(c, offset, n_problems, c->ibatch_off));
   InstBatchJob inst{};
+  inst.job = batch_job_of(p);
   BatchJob& job = inst.job;
   job.src = d_src; job.tgt = d_tgt; job.offset = c->ibatch_off.as<uint32_t>();
   job.n_problems = n_problems; job.total = offset[n_problems];
-  job.soa = p->layout == SC_SOA; job.T = p->max_triangles; job.rank_mode = p->rank_mode; job.score_mode = p->score_mode;
-  job.dv = derive(p);
   job.res = reinterpret_cast<BatchRecord*>(d_res); job.mask = nullptr;
   inst.rounds = rounds_of(max_instances, min_score, d_label, d_nfound);
   launch_instances_batch(inst, c->stream);
@@ -72,23 +71,18 @@ int sc_register_instances_batch(sc_ctx* c, const float* src, const float* tgt, c
   SC_TRY(ibatch_check(c, offset, n_problems, p, max_instances));
   HIPCHK(c, hipSetDevice(c->device));
   c->cap_bytes = workspace_cap(p);
-  const size_t total = offset[n_problems], pts = total * 12, recs = (size_t)max_instances * n_problems * sizeof(sc_batch_result),
-               found = (size_t)n_problems * 4;
-  ENSURE(c, c->ibatch_src, pts);
-  ENSURE(c, c->ibatch_tgt, pts);
-  ENSURE(c, c->ibatch_res, recs);
-  ENSURE(c, c->ibatch_label, total * 4);
-  ENSURE(c, c->ibatch_nfound, found);
-  hipStream_t st = c->stream;
-  HIPCHK(c, hipMemcpyAsync(c->ibatch_src.p, src, pts, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(c->ibatch_tgt.p, tgt, pts, hipMemcpyHostToDevice, st));
+  const size_t total = offset[n_problems], pts = total * 12;
+  HostArrays h(c);
+  h.in(c->ibatch_src, src, pts);
+  h.in(c->ibatch_tgt, tgt, pts);
+  h.out(c->ibatch_res, res, (size_t)max_instances * n_problems * sizeof(sc_batch_result));
+  h.out(c->ibatch_label, label, total * 4);
+  h.out(c->ibatch_nfound, nfound, (size_t)n_problems * 4);
+  SC_TRY(h.room());
+  SC_TRY(h.send());
   SC_TRY(ibatch_enqueue(c, c->ibatch_src.as<float>(), c->ibatch_tgt.as<float>(), offset, n_problems, p, max_instances, min_score,
                         c->ibatch_res.as<sc_batch_result>(), c->ibatch_label.as<int32_t>(), c->ibatch_nfound.as<uint32_t>()));
-  HIPCHK(c, hipMemcpyAsync(res, c->ibatch_res.p, recs, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(label, c->ibatch_label.p, total * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(nfound, c->ibatch_nfound.p, found, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  return SC_OK;
+  return h.fetch();
 }
 
 int sc_register_instances_batch_features_device(sc_ctx* c, const float* d_src_pts, const float* d_fsrc, const uint32_t* src_off,
@@ -108,7 +102,7 @@ int sc_register_instances_batch_features_device(sc_ctx* c, const float* d_src_pt
   HIPCHK(c, hipSetDevice(c->device));
   c->cap_bytes = workspace_cap(p);
   SC_TRY(mbatch_room(c, mj, sz, true));
-  SC_TRY(mbatch_enqueue(c, mj, sz, d_fsrc, d_ftgt, src_off, tgt_off, d_corr, d_d2, d_count, gather_of(c, p, sz, d_src_pts, d_tgt_pts)));
+  SC_TRY(mbatch_enqueue_packed(c, mj, sz, d_fsrc, d_ftgt, src_off, tgt_off, d_corr, d_d2, d_count, p, d_src_pts, d_tgt_pts));
   InstBatchSlotJob slots{};
   slots.job = mbatch_slots_job(c, sz, p);
   slots.job.res = reinterpret_cast<BatchRecord*>(d_res); slots.job.mask = nullptr;

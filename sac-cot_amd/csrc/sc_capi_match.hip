@@ -138,10 +138,9 @@ int sc_register_features(sc_ctx* c, const float* src_pts, const float* fsrc, int
   SC_TRY(match_stage_host(c, &job, fsrc, ftgt));
   HIPCHK(c, hipMemcpyAsync(c->match_psrc.p, src_pts, (size_t)job.ns * 12, hipMemcpyHostToDevice, st));
   HIPCHK(c, hipMemcpyAsync(c->match_ptgt.p, tgt_pts, (size_t)job.nt * 12, hipMemcpyHostToDevice, st));
-  const bool soa = p->layout == SC_SOA;
   // the gathered correspondences are written n x 3 whatever the caller's layout: n is not known while they are written
-  const MatchGather g{c->match_psrc.as<float>(), c->match_ptgt.as<float>(), soa ? 1u : 3u, soa ? job.ns : 1u, soa ? 1u : 3u,
-                      soa ? job.nt : 1u, c->match_gsrc.as<float>(), c->match_gtgt.as<float>()};
+  const MatchGather g = gather_of(c->match_psrc.as<float>(), job.ns, c->match_ptgt.as<float>(), job.nt, p->layout, c->match_gsrc.as<float>(),
+                                  c->match_gtgt.as<float>());
   SC_TRY(match_enqueue(c, job, c->match_corr.as<int32_t>(), c->match_d2.as<float>(), nullptr, g, true));
   uint32_t found = 0;
   SC_TRY(match_results_to_host(c, corr, d2, &found));  // the one host wait between matching and registration

@@ -6,9 +6,10 @@
 // staging -> ONE device copy (enqueued) -> memset (a "clean" word per problem and, for SC_MATCH_MUTUAL, the column minima: all
 // ones) -> distance + select -> finish [-> sc_batch.hip's kernel on the slots]: four or five stream operations whatever the batch,
 // and nothing is read back — a problem's count, its non-finite flag and its status are words in device memory.  Everything that can
-// refuse the call is decided on the host before anything is enqueued.
+// refuse the call is decided on the host before anything is enqueued.  The sequence is said once, for this packed form and for the
+// pairs form (sc_capi_pairs.hip): mbatch_room, mbatch_enqueue (a template over the form's job type, sc_ctx.hpp), mbatch_slots_job
+// and mbatch_register take what differs — the metadata's layout and fill, the job's own fields, the launch pair — from the caller.
 #include "sc_ctx.hpp"
-#include "sc_match_batch_check.hpp"
 
 using namespace sc;
 
@@ -16,12 +17,11 @@ static_assert(MATCH_BATCH_MAX_N == SC_MATCH_BATCH_MAX_N, "sc_kernels.hpp and sac
 
 using Sizes = MatchBatchSizes;
 
-// The match sequence — what is refused, the workspace, the enqueue, the gather's description — is namespace sc's: the entries here
-// and sc_register_instances_batch_features_device (sc_capi_instances_batch.hip) share it (declared in sc_ctx.hpp).
+// The match sequence — what is refused, the workspace, the enqueue, the registration on the slots — is namespace sc's: the entries
+// here, sc_register_instances_batch_features_device (sc_capi_instances_batch.hip) and the pairs entries (sc_capi_pairs.hip) share it
+// (declared in sc_ctx.hpp).
 namespace sc {
 
-// every refusal of the entries; `p` only for the features entries, whose name for the messages is `features`.  Fills *job (but its
-// pointers) and *sz.
 int mbatch_check(sc_ctx* c, const uint32_t* src_off, const uint32_t* tgt_off, uint32_t n_problems, const sc_match_params* mp,
                  const sc_params* p, const char* features, MatchJob* job, Sizes* sz) {
   SC_TRY(entry_checks(c, nullptr, ENDS_FRAME | NOT_BUSY));
@@ -32,15 +32,15 @@ int mbatch_check(sc_ctx* c, const uint32_t* src_off, const uint32_t* tgt_off, ui
   if (tiles > 0x7FFFFFFFull) { c->last_error = "sc_match_batch: more than 2^31 - 1 row tiles"; return SC_EINVAL; }
   sz->n_problems = n_problems; sz->n_tiles = (uint32_t)tiles;
   sz->total_s = src_off[n_problems]; sz->total_t = tgt_off[n_problems]; sz->slots = sz->total_s * job->knn;
+  sz->meta = match_batch_meta_layout(n_problems, sz->n_tiles);
   return SC_OK;
 }
 
-// the workspace of the match itself
 int mbatch_room(sc_ctx* c, const MatchJob& mj, const Sizes& sz, bool gather) {
   const uint32_t kp = mj.r2 > 0.f ? 2u : mj.knn;
-  ENSURE(c, c->mbatch_meta, (3 * ((size_t)sz.n_problems + 1) + 2 * (size_t)sz.n_tiles) * 4);
+  ENSURE(c, c->mbatch_meta, sz.meta.words * 4);
   ENSURE(c, c->mbatch_top, sz.total_s * kp * 8);
-  ENSURE(c, c->mbatch_words, (((size_t)sz.n_problems + 1) / 2 + (mj.mutual ? sz.total_t : 0)) * 8);
+  ENSURE(c, c->mbatch_words, mbatch_clean_bytes(sz) + (mj.mutual ? sz.total_t * 8 : 0));
   if (gather) {
     ENSURE(c, c->mbatch_gsrc, sz.slots * 12);
     ENSURE(c, c->mbatch_gtgt, sz.slots * 12);
@@ -48,55 +48,30 @@ int mbatch_room(sc_ctx* c, const MatchJob& mj, const Sizes& sz, bool gather) {
   return SC_OK;
 }
 
-// the staging copy, the memset and the two launches (mbatch_room has been called)
-int mbatch_enqueue(sc_ctx* c, const MatchJob& mj, const Sizes& sz, const float* d_fsrc, const float* d_ftgt, const uint32_t* src_off,
-                   const uint32_t* tgt_off, int32_t* d_corr, float* d_d2, uint32_t* d_count, const MatchGather& g) {
-  const size_t nb1 = (size_t)sz.n_problems + 1, meta_bytes = (3 * nb1 + 2 * (size_t)sz.n_tiles) * 4;
-  SC_TRY(batch_staging_begin(c, meta_bytes));
-  uint32_t* h = static_cast<uint32_t*>(c->h_batch_off);
-  batch_slot_meta(src_off, tgt_off, sz.n_problems, mj.knn, h);
-  match_batch_tile_map(src_off, sz.n_problems, MATCH_BATCH_ROWS, h + 3 * nb1);
-  SC_TRY(batch_staging_send(c, c->mbatch_meta, meta_bytes));
-  const size_t clean_bytes = (nb1 / 2) * 8, words_bytes = clean_bytes + (mj.mutual ? sz.total_t * 8 : 0);
-  HIPCHK(c, hipMemsetAsync(c->mbatch_words.p, 0xFF, words_bytes, c->stream));
+int mbatch_enqueue_packed(sc_ctx* c, const MatchJob& mj, const Sizes& sz, const float* d_fsrc, const float* d_ftgt, const uint32_t* src_off,
+                          const uint32_t* tgt_off, int32_t* d_corr, float* d_d2, uint32_t* d_count, const sc_params* p, const float* d_src_pts,
+                          const float* d_tgt_pts) {
   const uint32_t* meta = c->mbatch_meta.as<uint32_t>();
+  const size_t nb1 = (size_t)sz.n_problems + 1;
   MatchBatchJob job{};
   job.fsrc = d_fsrc; job.ftgt = d_ftgt;
-  job.src_off = meta; job.tgt_off = meta + nb1; job.slot = meta + 2 * nb1; job.tile_map = meta + 3 * nb1;
-  job.n_problems = sz.n_problems; job.n_tiles = sz.n_tiles; job.dim = mj.dim; job.knn = mj.knn; job.kp = mj.r2 > 0.f ? 2u : mj.knn;
-  job.mutual = mj.mutual; job.r2 = mj.r2;
-  job.top = c->mbatch_top.as<uint64_t>();
-  job.colmin = mj.mutual ? reinterpret_cast<uint64_t*>(static_cast<char*>(c->mbatch_words.p) + clean_bytes) : nullptr;
-  job.clean = c->mbatch_words.as<uint32_t>();
-  job.corr = d_corr; job.d2 = d_d2; job.count = d_count; job.g = g;
-  launch_match_batch_dist(job, c->stream);
-  launch_match_batch_finish(job, c->stream);
-  HIPCHK(c, hipGetLastError());
-  return SC_OK;
+  job.src_off = meta; job.tgt_off = meta + nb1; job.slot = meta + sz.meta.slot_at;
+  const MatchGather g = p ? gather_of(d_src_pts, (uint32_t)sz.total_s, d_tgt_pts, (uint32_t)sz.total_t, p->layout, c->mbatch_gsrc.as<float>(),
+                                      c->mbatch_gtgt.as<float>())
+                          : MatchGather{};
+  return mbatch_enqueue(
+      c, mj, sz, job, [&](uint32_t* h) { match_batch_meta_fill(src_off, tgt_off, sz.n_problems, mj.knn, MATCH_BATCH_ROWS, sz.meta, h); },
+      launch_match_batch_dist, launch_match_batch_finish, d_corr, d_d2, d_count, g);
 }
 
-MatchGather gather_of(const sc_ctx* c, const sc_params* p, const Sizes& sz, const float* d_src_pts, const float* d_tgt_pts) {
-  const bool soa = p->layout == SC_SOA;
-  return MatchGather{d_src_pts, d_tgt_pts, soa ? 1u : 3u, soa ? (uint32_t)sz.total_s : 1u, soa ? 1u : 3u, soa ? (uint32_t)sz.total_t : 1u,
-                     c->mbatch_gsrc.as<float>(), c->mbatch_gtgt.as<float>()};
-}
-
-// sc_batch.hip's kernel argument on the slots the match filled: the gathered points, the slot starts (the count pairs are the caller's)
 BatchJob mbatch_slots_job(const sc_ctx* c, const Sizes& sz, const sc_params* p) {
-  BatchJob job{};
-  job.src = c->mbatch_gsrc.as<float>(); job.tgt = c->mbatch_gtgt.as<float>();  // n x 3 whatever the caller's layout
-  job.offset = c->mbatch_meta.as<uint32_t>() + 2 * ((size_t)sz.n_problems + 1);
+  BatchJob job = batch_job_of(p);
+  job.src = c->mbatch_gsrc.as<float>(); job.tgt = c->mbatch_gtgt.as<float>(); job.soa = 0;  // n x 3 whatever the caller's layout
+  job.offset = c->mbatch_meta.as<uint32_t>() + sz.meta.slot_at;
   job.n_problems = sz.n_problems; job.total = (uint32_t)sz.slots;
-  job.soa = 0; job.T = p->max_triangles; job.rank_mode = p->rank_mode; job.score_mode = p->score_mode;
-  job.dv = derive(p);
   return job;
 }
 
-}  // namespace sc
-
-namespace {
-
-// sc_batch.hip's kernel on the slots the match filled
 int mbatch_register(sc_ctx* c, const Sizes& sz, const sc_params* p, const uint32_t* d_count, sc_batch_result* d_res, uint8_t* d_mask) {
   BatchSlotJob slots{};
   slots.count = d_count;
@@ -105,6 +80,18 @@ int mbatch_register(sc_ctx* c, const Sizes& sz, const sc_params* p, const uint32
   launch_batch_register_slots(slots, c->stream);
   HIPCHK(c, hipGetLastError());
   return SC_OK;
+}
+
+}  // namespace sc
+
+namespace {
+
+// match, gather, registration on the slots: what both features entries enqueue (mbatch_room has been called)
+int features_enqueue(sc_ctx* c, const MatchJob& mj, const Sizes& sz, const float* d_src_pts, const float* d_fsrc, const uint32_t* src_off,
+                     const float* d_tgt_pts, const float* d_ftgt, const uint32_t* tgt_off, const sc_params* p, sc_batch_result* d_res,
+                     int32_t* d_corr, float* d_d2, uint32_t* d_count, uint8_t* d_mask) {
+  SC_TRY(mbatch_enqueue_packed(c, mj, sz, d_fsrc, d_ftgt, src_off, tgt_off, d_corr, d_d2, d_count, p, d_src_pts, d_tgt_pts));
+  return mbatch_register(c, sz, p, d_count, d_res, d_mask);
 }
 
 }  // namespace
@@ -120,7 +107,7 @@ int sc_match_batch_device(sc_ctx* c, const float* d_fsrc, const uint32_t* src_of
   SC_TRY(mbatch_check(c, src_off, tgt_off, n_problems, mp, nullptr, nullptr, &mj, &sz));
   HIPCHK(c, hipSetDevice(c->device));
   SC_TRY(mbatch_room(c, mj, sz, false));
-  return mbatch_enqueue(c, mj, sz, d_fsrc, d_ftgt, src_off, tgt_off, d_corr, d_d2, d_count, MatchGather{});
+  return mbatch_enqueue_packed(c, mj, sz, d_fsrc, d_ftgt, src_off, tgt_off, d_corr, d_d2, d_count);
 }
 
 int sc_match_batch(sc_ctx* c, const float* fsrc, const uint32_t* src_off, const float* ftgt, const uint32_t* tgt_off, uint32_t n_problems,
@@ -131,23 +118,16 @@ int sc_match_batch(sc_ctx* c, const float* fsrc, const uint32_t* src_off, const 
   Sizes sz{};
   SC_TRY(mbatch_check(c, src_off, tgt_off, n_problems, mp, nullptr, nullptr, &mj, &sz));
   HIPCHK(c, hipSetDevice(c->device));
-  const size_t sb = sz.total_s * mj.dim * 4, tb = sz.total_t * mj.dim * 4, cb = (size_t)n_problems * 8;
+  HostArrays h(c);
+  h.in(c->mbatch_fsrc, fsrc, sz.total_s * mj.dim * 4);
+  h.in(c->mbatch_ftgt, ftgt, sz.total_t * mj.dim * 4);
+  mbatch_outputs(h, c, sz, corr, d2, count);
   SC_TRY(mbatch_room(c, mj, sz, false));
-  ENSURE(c, c->mbatch_fsrc, sb);
-  ENSURE(c, c->mbatch_ftgt, tb);
-  ENSURE(c, c->mbatch_corr, sz.slots * 8);
-  ENSURE(c, c->mbatch_d2, sz.slots * 4);
-  ENSURE(c, c->mbatch_count, cb);
-  hipStream_t st = c->stream;
-  HIPCHK(c, hipMemcpyAsync(c->mbatch_fsrc.p, fsrc, sb, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(c->mbatch_ftgt.p, ftgt, tb, hipMemcpyHostToDevice, st));
-  SC_TRY(mbatch_enqueue(c, mj, sz, c->mbatch_fsrc.as<float>(), c->mbatch_ftgt.as<float>(), src_off, tgt_off, c->mbatch_corr.as<int32_t>(),
-                        c->mbatch_d2.as<float>(), c->mbatch_count.as<uint32_t>(), MatchGather{}));
-  HIPCHK(c, hipMemcpyAsync(corr, c->mbatch_corr.p, sz.slots * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(d2, c->mbatch_d2.p, sz.slots * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(count, c->mbatch_count.p, cb, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  return SC_OK;
+  SC_TRY(h.room());
+  SC_TRY(h.send());
+  SC_TRY(mbatch_enqueue_packed(c, mj, sz, c->mbatch_fsrc.as<float>(), c->mbatch_ftgt.as<float>(), src_off, tgt_off, c->mbatch_corr.as<int32_t>(),
+                               c->mbatch_d2.as<float>(), c->mbatch_count.as<uint32_t>()));
+  return h.fetch();
 }
 
 int sc_register_batch_features_device(sc_ctx* c, const float* d_src_pts, const float* d_fsrc, const uint32_t* src_off,
@@ -163,8 +143,7 @@ int sc_register_batch_features_device(sc_ctx* c, const float* d_src_pts, const f
   HIPCHK(c, hipSetDevice(c->device));
   c->cap_bytes = workspace_cap(p);
   SC_TRY(mbatch_room(c, mj, sz, true));
-  SC_TRY(mbatch_enqueue(c, mj, sz, d_fsrc, d_ftgt, src_off, tgt_off, d_corr, d_d2, d_count, gather_of(c, p, sz, d_src_pts, d_tgt_pts)));
-  return mbatch_register(c, sz, p, d_count, d_res, d_mask);
+  return features_enqueue(c, mj, sz, d_src_pts, d_fsrc, src_off, d_tgt_pts, d_ftgt, tgt_off, p, d_res, d_corr, d_d2, d_count, d_mask);
 }
 
 int sc_register_batch_features(sc_ctx* c, const float* src_pts, const float* fsrc, const uint32_t* src_off, const float* tgt_pts,
@@ -178,34 +157,21 @@ int sc_register_batch_features(sc_ctx* c, const float* src_pts, const float* fsr
   SC_TRY(mbatch_check(c, src_off, tgt_off, n_problems, mp, p, "sc_register_batch_features", &mj, &sz));
   HIPCHK(c, hipSetDevice(c->device));
   c->cap_bytes = workspace_cap(p);
-  const size_t sb = sz.total_s * mj.dim * 4, tb = sz.total_t * mj.dim * 4, cb = (size_t)n_problems * 8;
-  const size_t recs = (size_t)n_problems * sizeof(sc_batch_result);
+  HostArrays h(c);
+  h.in(c->mbatch_fsrc, fsrc, sz.total_s * mj.dim * 4);
+  h.in(c->mbatch_ftgt, ftgt, sz.total_t * mj.dim * 4);
+  h.in(c->mbatch_psrc, src_pts, sz.total_s * 12);
+  h.in(c->mbatch_ptgt, tgt_pts, sz.total_t * 12);
+  mbatch_outputs(h, c, sz, corr, d2, count);
+  h.out(c->mbatch_res, res, (size_t)n_problems * sizeof(sc_batch_result), true);  // the records are fetched first
+  h.out(c->mbatch_mask, mask, sz.slots);
   SC_TRY(mbatch_room(c, mj, sz, true));
-  ENSURE(c, c->mbatch_fsrc, sb);
-  ENSURE(c, c->mbatch_ftgt, tb);
-  ENSURE(c, c->mbatch_psrc, sz.total_s * 12);
-  ENSURE(c, c->mbatch_ptgt, sz.total_t * 12);
-  ENSURE(c, c->mbatch_corr, sz.slots * 8);
-  ENSURE(c, c->mbatch_d2, sz.slots * 4);
-  ENSURE(c, c->mbatch_count, cb);
-  ENSURE(c, c->mbatch_res, recs);
-  ENSURE(c, c->mbatch_mask, sz.slots);
-  hipStream_t st = c->stream;
-  HIPCHK(c, hipMemcpyAsync(c->mbatch_fsrc.p, fsrc, sb, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(c->mbatch_ftgt.p, ftgt, tb, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(c->mbatch_psrc.p, src_pts, sz.total_s * 12, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(c->mbatch_ptgt.p, tgt_pts, sz.total_t * 12, hipMemcpyHostToDevice, st));
-  uint32_t* d_count = c->mbatch_count.as<uint32_t>();
-  SC_TRY(mbatch_enqueue(c, mj, sz, c->mbatch_fsrc.as<float>(), c->mbatch_ftgt.as<float>(), src_off, tgt_off, c->mbatch_corr.as<int32_t>(),
-                        c->mbatch_d2.as<float>(), d_count, gather_of(c, p, sz, c->mbatch_psrc.as<float>(), c->mbatch_ptgt.as<float>())));
-  SC_TRY(mbatch_register(c, sz, p, d_count, c->mbatch_res.as<sc_batch_result>(), c->mbatch_mask.as<uint8_t>()));
-  HIPCHK(c, hipMemcpyAsync(res, c->mbatch_res.p, recs, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(corr, c->mbatch_corr.p, sz.slots * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(d2, c->mbatch_d2.p, sz.slots * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(count, c->mbatch_count.p, cb, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(mask, c->mbatch_mask.p, sz.slots, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  return SC_OK;
+  SC_TRY(h.room());
+  SC_TRY(h.send());
+  SC_TRY(features_enqueue(c, mj, sz, c->mbatch_psrc.as<float>(), c->mbatch_fsrc.as<float>(), src_off, c->mbatch_ptgt.as<float>(),
+                          c->mbatch_ftgt.as<float>(), tgt_off, p, c->mbatch_res.as<sc_batch_result>(), c->mbatch_corr.as<int32_t>(),
+                          c->mbatch_d2.as<float>(), c->mbatch_count.as<uint32_t>(), c->mbatch_mask.as<uint8_t>()));
+  return h.fetch();
 }
 
 }  // extern "C"

@@ -7,8 +7,9 @@
 // shares) -> ONE device copy (enqueued) -> memset (a "clean" word per pair and, for SC_MATCH_MUTUAL, every pair's own column
 // minima: all ones) -> distance + select -> finish [-> sc_batch.hip's kernel on the slots]: the packed form's four or five stream
 // operations, whatever the list, and nothing is read back.  Everything that can refuse the call is decided on the host before
-// anything is enqueued.  The workspace is the packed entries' (the mbatch / pbatch buffers): a pair is a problem of theirs whose rows
-// are found through a record.
+// anything is enqueued.  The workspace is the packed entries' (the mbatch / pbatch buffers), and so is the sequence (mbatch_room,
+// mbatch_enqueue, mbatch_register: sc_ctx.hpp, sc_capi_match_batch.hip): a pair is a problem of theirs whose rows are found through a
+// record.  What is the pairs' own is here: the checks, the staging-area fill and the job's head (pairs_match), the entry points.
 #include "sc_ctx.hpp"
 #include "sc_pairs_check.hpp"
 
@@ -20,9 +21,6 @@ static_assert(PAIR_WORDS == PAIRS_REC_WORDS && PW_SRC == 0 && PW_NS == 1 && PW_T
 namespace {
 
 using Sizes = MatchBatchSizes;  // n_problems: the pairs; total_s / total_t: the source / target rows of all pairs
-
-// device words of the metadata: the records, the slot starts (n_pairs + 1: sc_batch.hip's offset array), the tile map
-size_t meta_words(const Sizes& sz) { return (size_t)PAIR_WORDS * sz.n_problems + sz.n_problems + 1 + 2 * (size_t)sz.n_tiles; }
 
 // every refusal of the entries; `p` only for the features entries, whose name for the messages is `features`.  Fills *job (but its
 // pointers) and *sz.
@@ -36,72 +34,23 @@ int pairs_check(sc_ctx* c, const uint32_t* set_off, uint32_t n_sets, const uint3
   if (t.tiles > 0x7FFFFFFFull) { c->last_error = "sc_match_pairs: more than 2^31 - 1 row tiles"; return SC_EINVAL; }
   sz->n_problems = n_pairs; sz->n_tiles = (uint32_t)t.tiles;
   sz->total_s = t.total_s; sz->total_t = t.total_t; sz->slots = sz->total_s * job->knn;
+  sz->meta = pairs_meta_layout(n_pairs, sz->n_tiles);
   return SC_OK;
 }
 
-// the workspace of the match itself (gather: and of the gathered points)
-int pairs_room(sc_ctx* c, const MatchJob& mj, const Sizes& sz, bool gather) {
-  const uint32_t kp = mj.r2 > 0.f ? 2u : mj.knn;
-  ENSURE(c, c->mbatch_meta, meta_words(sz) * 4);
-  ENSURE(c, c->mbatch_top, sz.total_s * kp * 8);
-  ENSURE(c, c->mbatch_words, (((size_t)sz.n_problems + 1) / 2 + (mj.mutual ? sz.total_t : 0)) * 8);
-  if (gather) {
-    ENSURE(c, c->mbatch_gsrc, sz.slots * 12);
-    ENSURE(c, c->mbatch_gtgt, sz.slots * 12);
-  }
-  return SC_OK;
-}
-
-const uint32_t* slot_starts(const sc_ctx* c, const Sizes& sz) { return c->mbatch_meta.as<uint32_t>() + (size_t)PAIR_WORDS * sz.n_problems; }
-
-// the staging copy, the memset and the two launches (pairs_room has been called).  d_pts: the table's points for the gather
-// (nullptr: the match alone), `total` rows in `layout`.
-int pairs_enqueue(sc_ctx* c, const MatchJob& mj, const Sizes& sz, const float* d_feat, const uint32_t* set_off, const uint32_t* pairs,
-                  int32_t* d_corr, float* d_d2, uint32_t* d_count, const float* d_pts, uint32_t total, int layout) {
-  const size_t np = sz.n_problems, bytes = meta_words(sz) * 4;
-  SC_TRY(batch_staging_begin(c, bytes));
-  uint32_t* h = static_cast<uint32_t*>(c->h_batch_off);
-  pairs_records(set_off, pairs, sz.n_problems, mj.knn, h);
-  pairs_slots(set_off, pairs, sz.n_problems, mj.knn, h + PAIR_WORDS * np);
-  pairs_tile_map(set_off, pairs, sz.n_problems, MATCH_BATCH_ROWS, h + PAIR_WORDS * np + np + 1);
-  SC_TRY(batch_staging_send(c, c->mbatch_meta, bytes));
-  const size_t clean_bytes = ((np + 1) / 2) * 8, words_bytes = clean_bytes + (mj.mutual ? sz.total_t * 8 : 0);
-  HIPCHK(c, hipMemsetAsync(c->mbatch_words.p, 0xFF, words_bytes, c->stream));
-  const uint32_t* meta = c->mbatch_meta.as<uint32_t>();
+// the match on the list (mbatch_room has been called): the records, the slot starts and the tile map into the staging area,
+// MatchPairsJob and its launches.  p, d_pts: a features entry's sc_params and the table's points (`total` rows), for the gather
+// (p == nullptr: the match alone).
+int pairs_match(sc_ctx* c, const MatchJob& mj, const Sizes& sz, const float* d_feat, const uint32_t* set_off, const uint32_t* pairs,
+                int32_t* d_corr, float* d_d2, uint32_t* d_count, const sc_params* p = nullptr, const float* d_pts = nullptr, uint32_t total = 0) {
   MatchPairsJob job{};
   job.feat = d_feat;
-  job.rec = meta; job.tile_map = meta + PAIR_WORDS * np + np + 1;
-  job.n_problems = sz.n_problems; job.n_tiles = sz.n_tiles; job.dim = mj.dim; job.knn = mj.knn; job.kp = mj.r2 > 0.f ? 2u : mj.knn;
-  job.mutual = mj.mutual; job.r2 = mj.r2;
-  job.top = c->mbatch_top.as<uint64_t>();
-  job.colmin = mj.mutual ? reinterpret_cast<uint64_t*>(static_cast<char*>(c->mbatch_words.p) + clean_bytes) : nullptr;
-  job.clean = c->mbatch_words.as<uint32_t>();
-  job.corr = d_corr; job.d2 = d_d2; job.count = d_count;
-  if (d_pts) {  // both sides of a pair are rows of the one table
-    const bool soa = layout == SC_SOA;
-    job.g = MatchGather{d_pts, d_pts, soa ? 1u : 3u, soa ? total : 1u, soa ? 1u : 3u, soa ? total : 1u, c->mbatch_gsrc.as<float>(),
-                        c->mbatch_gtgt.as<float>()};
-  }
-  launch_match_pairs_dist(job, c->stream);
-  launch_match_pairs_finish(job, c->stream);
-  HIPCHK(c, hipGetLastError());
-  return SC_OK;
-}
-
-// sc_batch.hip's kernel on the slots the match filled: launch_batch_register_slots, with the slot starts as its offset array
-int pairs_register(sc_ctx* c, const Sizes& sz, const sc_params* p, const uint32_t* d_count, sc_batch_result* d_res, uint8_t* d_mask) {
-  BatchSlotJob slots{};
-  slots.count = d_count;
-  BatchJob& job = slots.job;
-  job.src = c->mbatch_gsrc.as<float>(); job.tgt = c->mbatch_gtgt.as<float>();  // n x 3 whatever the caller's layout
-  job.offset = slot_starts(c, sz);
-  job.n_problems = sz.n_problems; job.total = (uint32_t)sz.slots;
-  job.soa = 0; job.T = p->max_triangles; job.rank_mode = p->rank_mode; job.score_mode = p->score_mode;
-  job.dv = derive(p);
-  job.res = reinterpret_cast<BatchRecord*>(d_res); job.mask = d_mask;
-  launch_batch_register_slots(slots, c->stream);
-  HIPCHK(c, hipGetLastError());
-  return SC_OK;
+  job.rec = c->mbatch_meta.as<uint32_t>();
+  // both sides of a pair are rows of the one table
+  const MatchGather g = p ? gather_of(d_pts, total, d_pts, total, p->layout, c->mbatch_gsrc.as<float>(), c->mbatch_gtgt.as<float>()) : MatchGather{};
+  return mbatch_enqueue(
+      c, mj, sz, job, [&](uint32_t* h) { pairs_meta_fill(set_off, pairs, sz.n_problems, mj.knn, MATCH_BATCH_ROWS, sz.meta, h); },
+      launch_match_pairs_dist, launch_match_pairs_finish, d_corr, d_d2, d_count, g);
 }
 
 }  // namespace
@@ -123,8 +72,8 @@ int sc_match_pairs_device(sc_ctx* c, const float* d_feat, const uint32_t* set_of
   Sizes sz{};
   SC_TRY(pairs_check(c, set_off, n_sets, pairs, n_pairs, mp, nullptr, nullptr, &mj, &sz));
   HIPCHK(c, hipSetDevice(c->device));
-  SC_TRY(pairs_room(c, mj, sz, false));
-  return pairs_enqueue(c, mj, sz, d_feat, set_off, pairs, d_corr, d_d2, d_count, nullptr, 0, SC_AOS);
+  SC_TRY(mbatch_room(c, mj, sz, false));
+  return pairs_match(c, mj, sz, d_feat, set_off, pairs, d_corr, d_d2, d_count);
 }
 
 int sc_match_pairs(sc_ctx* c, const float* feat, const uint32_t* set_off, uint32_t n_sets, const uint32_t* pairs, uint32_t n_pairs,
@@ -135,21 +84,15 @@ int sc_match_pairs(sc_ctx* c, const float* feat, const uint32_t* set_off, uint32
   Sizes sz{};
   SC_TRY(pairs_check(c, set_off, n_sets, pairs, n_pairs, mp, nullptr, nullptr, &mj, &sz));
   HIPCHK(c, hipSetDevice(c->device));
-  const size_t fb = (size_t)set_off[n_sets] * mj.dim * 4, cb = (size_t)n_pairs * 8;
-  SC_TRY(pairs_room(c, mj, sz, false));
-  ENSURE(c, c->mbatch_fsrc, fb);  // the table: one copy serves both sides
-  ENSURE(c, c->mbatch_corr, sz.slots * 8);
-  ENSURE(c, c->mbatch_d2, sz.slots * 4);
-  ENSURE(c, c->mbatch_count, cb);
-  hipStream_t st = c->stream;
-  HIPCHK(c, hipMemcpyAsync(c->mbatch_fsrc.p, feat, fb, hipMemcpyHostToDevice, st));
-  SC_TRY(pairs_enqueue(c, mj, sz, c->mbatch_fsrc.as<float>(), set_off, pairs, c->mbatch_corr.as<int32_t>(), c->mbatch_d2.as<float>(),
-                       c->mbatch_count.as<uint32_t>(), nullptr, 0, SC_AOS));
-  HIPCHK(c, hipMemcpyAsync(corr, c->mbatch_corr.p, sz.slots * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(d2, c->mbatch_d2.p, sz.slots * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(count, c->mbatch_count.p, cb, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  return SC_OK;
+  HostArrays h(c);
+  h.in(c->mbatch_fsrc, feat, (size_t)set_off[n_sets] * mj.dim * 4);  // the table: one copy serves both sides
+  mbatch_outputs(h, c, sz, corr, d2, count);
+  SC_TRY(mbatch_room(c, mj, sz, false));
+  SC_TRY(h.room());
+  SC_TRY(h.send());
+  SC_TRY(pairs_match(c, mj, sz, c->mbatch_fsrc.as<float>(), set_off, pairs, c->mbatch_corr.as<int32_t>(), c->mbatch_d2.as<float>(),
+                     c->mbatch_count.as<uint32_t>()));
+  return h.fetch();
 }
 
 int sc_register_pairs_features_device(sc_ctx* c, const float* d_pts, const float* d_feat, const uint32_t* set_off, uint32_t n_sets,
@@ -163,9 +106,9 @@ int sc_register_pairs_features_device(sc_ctx* c, const float* d_pts, const float
   SC_TRY(pairs_check(c, set_off, n_sets, pairs, n_pairs, mp, p, "sc_register_pairs_features", &mj, &sz));
   HIPCHK(c, hipSetDevice(c->device));
   c->cap_bytes = workspace_cap(p);
-  SC_TRY(pairs_room(c, mj, sz, true));
-  SC_TRY(pairs_enqueue(c, mj, sz, d_feat, set_off, pairs, d_corr, d_d2, d_count, d_pts, set_off[n_sets], p->layout));
-  return pairs_register(c, sz, p, d_count, d_res, d_mask);
+  SC_TRY(mbatch_room(c, mj, sz, true));
+  SC_TRY(pairs_match(c, mj, sz, d_feat, set_off, pairs, d_corr, d_d2, d_count, p, d_pts, set_off[n_sets]));
+  return mbatch_register(c, sz, p, d_count, d_res, d_mask);
 }
 
 int sc_register_pairs_features(sc_ctx* c, const float* pts, const float* feat, const uint32_t* set_off, uint32_t n_sets,
@@ -179,30 +122,21 @@ int sc_register_pairs_features(sc_ctx* c, const float* pts, const float* feat, c
   SC_TRY(pairs_check(c, set_off, n_sets, pairs, n_pairs, mp, p, "sc_register_pairs_features", &mj, &sz));
   HIPCHK(c, hipSetDevice(c->device));
   c->cap_bytes = workspace_cap(p);
-  const size_t total = set_off[n_sets], fb = total * mj.dim * 4, cb = (size_t)n_pairs * 8;
-  const size_t recs = (size_t)n_pairs * sizeof(sc_batch_result);
-  SC_TRY(pairs_room(c, mj, sz, true));
-  ENSURE(c, c->mbatch_fsrc, fb);  // the table, descriptors and points: one copy of each serves both sides
-  ENSURE(c, c->mbatch_psrc, total * 12);
-  ENSURE(c, c->mbatch_corr, sz.slots * 8);
-  ENSURE(c, c->mbatch_d2, sz.slots * 4);
-  ENSURE(c, c->mbatch_count, cb);
-  ENSURE(c, c->mbatch_res, recs);
-  ENSURE(c, c->mbatch_mask, sz.slots);
-  hipStream_t st = c->stream;
-  HIPCHK(c, hipMemcpyAsync(c->mbatch_fsrc.p, feat, fb, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(c->mbatch_psrc.p, pts, total * 12, hipMemcpyHostToDevice, st));
+  const size_t total = set_off[n_sets];
+  HostArrays h(c);
+  h.in(c->mbatch_fsrc, feat, total * mj.dim * 4);  // the table, descriptors and points: one copy of each serves both sides
+  h.in(c->mbatch_psrc, pts, total * 12);
+  mbatch_outputs(h, c, sz, corr, d2, count);
+  h.out(c->mbatch_res, res, (size_t)n_pairs * sizeof(sc_batch_result), true);  // the records are fetched first
+  h.out(c->mbatch_mask, mask, sz.slots);
+  SC_TRY(mbatch_room(c, mj, sz, true));
+  SC_TRY(h.room());
+  SC_TRY(h.send());
   uint32_t* d_count = c->mbatch_count.as<uint32_t>();
-  SC_TRY(pairs_enqueue(c, mj, sz, c->mbatch_fsrc.as<float>(), set_off, pairs, c->mbatch_corr.as<int32_t>(), c->mbatch_d2.as<float>(), d_count,
-                       c->mbatch_psrc.as<float>(), (uint32_t)total, p->layout));
-  SC_TRY(pairs_register(c, sz, p, d_count, c->mbatch_res.as<sc_batch_result>(), c->mbatch_mask.as<uint8_t>()));
-  HIPCHK(c, hipMemcpyAsync(res, c->mbatch_res.p, recs, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(corr, c->mbatch_corr.p, sz.slots * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(d2, c->mbatch_d2.p, sz.slots * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(count, c->mbatch_count.p, cb, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(mask, c->mbatch_mask.p, sz.slots, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  return SC_OK;
+  SC_TRY(pairs_match(c, mj, sz, c->mbatch_fsrc.as<float>(), set_off, pairs, c->mbatch_corr.as<int32_t>(), c->mbatch_d2.as<float>(), d_count, p,
+                     c->mbatch_psrc.as<float>(), (uint32_t)total));
+  SC_TRY(mbatch_register(c, sz, p, d_count, c->mbatch_res.as<sc_batch_result>(), c->mbatch_mask.as<uint8_t>()));
+  return h.fetch();
 }
 
 int sc_polish_pairs_slots_device(sc_ctx* c, const float* d_pts, const uint32_t* set_off, uint32_t n_sets, const uint32_t* pairs,

@@ -7,11 +7,10 @@
 // Nothing is read back: a problem's status is a field of its record.  Everything that can refuse the call is decided on the host
 // before anything is enqueued.
 #include "sc_ctx.hpp"
-#include "sc_match_batch_check.hpp"
 
 using namespace sc;
 
-// What sc_polish_pairs_slots_device (sc_capi_pairs.hip) shares with the entries here (declared in sc_ctx.hpp).
+// What sc_polish_pairs_slots_device (sc_capi_pairs.hip) shares with the entries here (declared in sc_ctx.hpp, next to batch_job_of).
 namespace sc {
 
 // sc_polish_params as a batch takes them: one candidate per problem
@@ -79,23 +78,18 @@ int sc_polish_batch(sc_ctx* c, const float* src, const float* tgt, const uint32_
   SC_TRY(pbatch_check(c, offset, n_problems, p, pp));
   HIPCHK(c, hipSetDevice(c->device));
   c->cap_bytes = workspace_cap(p);
-  const size_t total = offset[n_problems], pts = total * 12, recs = (size_t)n_problems * sizeof(sc_batch_result),
-               pols = (size_t)n_problems * sizeof(sc_polish_batch_result);
-  ENSURE(c, c->pbatch_src, pts);
-  ENSURE(c, c->pbatch_tgt, pts);
-  ENSURE(c, c->pbatch_res, recs);
-  ENSURE(c, c->pbatch_pol, pols);
-  ENSURE(c, c->pbatch_mask, total);
-  hipStream_t st = c->stream;
-  HIPCHK(c, hipMemcpyAsync(c->pbatch_src.p, src, pts, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(c->pbatch_tgt.p, tgt, pts, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(c->pbatch_res.p, res, recs, hipMemcpyHostToDevice, st));
+  const size_t total = offset[n_problems], pts = total * 12;
+  HostArrays h(c);
+  h.in(c->pbatch_src, src, pts);
+  h.in(c->pbatch_tgt, tgt, pts);
+  h.in(c->pbatch_res, res, (size_t)n_problems * sizeof(sc_batch_result));
+  h.out(c->pbatch_pol, pol, (size_t)n_problems * sizeof(sc_polish_batch_result));
+  h.out(c->pbatch_mask, mask, total);
+  SC_TRY(h.room());
+  SC_TRY(h.send());
   SC_TRY(pbatch_enqueue(c, c->pbatch_src.as<float>(), c->pbatch_tgt.as<float>(), offset, n_problems, p, pp, c->pbatch_res.as<sc_batch_result>(),
                         c->pbatch_pol.as<sc_polish_batch_result>(), c->pbatch_mask.as<uint8_t>()));
-  HIPCHK(c, hipMemcpyAsync(pol, c->pbatch_pol.p, pols, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(mask, c->pbatch_mask.p, total, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  return SC_OK;
+  return h.fetch();
 }
 
 int sc_polish_batch_slots_device(sc_ctx* c, const float* d_src_pts, const uint32_t* src_off, const float* d_tgt_pts, const uint32_t* tgt_off,

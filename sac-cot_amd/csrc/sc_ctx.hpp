@@ -10,6 +10,7 @@
 #include "../../include/saccot.h"
 #include "../../include/saccot_debug.h"
 #include "sc_kernels.hpp"
+#include "sc_match_batch_check.hpp"
 
 namespace sc {
 
@@ -236,14 +237,26 @@ int points_to_device(sc_ctx* c, const float* src, const float* tgt, int64_t n);
 // rt12 and n bytes of mask -> the caller's host arrays (R and t split); the stream is idle on return
 int outputs_to_host(sc_ctx* c, size_t n, float R[9], float t[3], uint8_t* mask);
 
-// ---- defined in sc_capi_match.hip / sc_capi_batch.hip, used by sc_capi_match_batch.hip as well
+// ---- defined in sc_capi_match.hip / sc_capi_batch.hip, used by the other batch files as well
 // the rules of sc_match_params and of ns, nt; fills everything of *job but the descriptor pointers
 int match_check(sc_ctx* c, const sc_match_params* mp, int64_t ns, int64_t nt, MatchJob* job);
+// the caller's points (either layout of sc_params, src_rows / tgt_rows of them) -> two n x 3 arrays, as a finish kernel is told
+inline MatchGather gather_of(const float* src, uint32_t src_rows, const float* tgt, uint32_t tgt_rows, int layout, float* gsrc, float* gtgt) {
+  const bool soa = layout == SC_SOA;
+  return MatchGather{src, tgt, soa ? 1u : 3u, soa ? src_rows : 1u, soa ? 1u : 3u, soa ? tgt_rows : 1u, gsrc, gtgt};
+}
 // what a batch entry refuses of sc_params (shard_world != 1, refit, timing, an estimated bound); `who` opens the message
 int batch_params_check(sc_ctx* c, const sc_params* p, const char* who);
 // what a batch entry refuses of the caller's offsets (sizes 3 .. SC_BATCH_MAX_N, nothing decreasing, a total of 2^31 at most): the
 // rule that is broken, for the caller to put its name in front of; nullptr: they are fine
 const char* batch_offsets_error(const uint32_t* offset, uint32_t n_problems);
+// what the registration kernels read of sc_params (the pointers and sizes are the caller's; a slot form then sets soa = 0)
+inline BatchJob batch_job_of(const sc_params* p) {
+  BatchJob job{};
+  job.soa = p->layout == SC_SOA; job.T = p->max_triangles; job.rank_mode = p->rank_mode; job.score_mode = p->score_mode;
+  job.dv = derive(p);
+  return job;
+}
 // The pinned staging area that host words of a batch call (offsets, maps) pass through on their way to the device.  begin: the area
 // holds `bytes` and the copy out of the call before is done (an event behind that copy — not behind that call's kernel); the caller
 // fills c->h_batch_off; send: area -> dst (enqueued), and the event behind it.
@@ -252,24 +265,84 @@ int batch_staging_send(sc_ctx* c, Buf& dst, size_t bytes);
 // the caller's offsets (n_problems + 1 words) through that area into dst (enqueued)
 int batch_offsets_to_device(sc_ctx* c, const uint32_t* offset, uint32_t n_problems, Buf& dst);
 
-// ---- defined in sc_capi_match_batch.hip, used by sc_capi_instances_batch.hip as well: the match sequence of a features entry
+// The host-array form of a batch entry (defined in sc_capi_batch.hip): the entry declares its arrays — an input is copied in, an
+// output copied out, each through a workspace buffer of the entry's own and each with its byte count said once — and then runs
+//   room (ENSURE every buffer, in declaration order; nothing is enqueued before the last one has its room, so SC_ENOMEM leaves no
+//   copy from the caller's memory in flight) -> send (the copies in, in declaration order) -> the device form's sequence on the
+//   buffers -> fetch (the copies out — those declared `first` before the others, each group in declaration order — and the wait
+//   for the stream).
+struct HostArrays {
+  static constexpr int MAX = 9;  // sc_register_batch_features has nine
+  explicit HostArrays(sc_ctx* ctx) : c(ctx) {}
+  void in(Buf& b, const void* host, size_t bytes) { add(Arr{&b, host, nullptr, bytes, false}); }
+  void out(Buf& b, void* host, size_t bytes, bool first = false) { add(Arr{&b, nullptr, host, bytes, first}); }
+  int room();
+  int send();
+  int fetch();
+
+ private:
+  struct Arr { Buf* buf; const void* from; void* to; size_t bytes; bool first; };
+  void add(const Arr& a) { if (n < MAX) arr[n] = a; n++; }  // (room refuses an entry that declared more)
+  sc_ctx* c;
+  Arr arr[MAX];
+  int n = 0;
+};
+
+// ---- the batched match sequence: defined in sc_capi_match_batch.hip but for the template, used by sc_capi_instances_batch.hip
+// (the packed form) and sc_capi_pairs.hip (a pair is a problem, found through a record) as well
 struct MatchBatchSizes {
   uint32_t n_problems, n_tiles;
   size_t total_s, total_t, slots;  // rows of fsrc, rows of ftgt, output entries (total_s * knn)
+  BatchMetaLayout meta;            // the metadata of the form (sc_match_batch_check.hpp): its words, where the slot starts and the tile map sit
 };
-// every refusal of a batched match; `p` only for a features entry, whose name for the messages is `features` (nullptr: the match
-// alone).  Fills *job (but its pointers) and *sz.
+// the arrays a match writes, as its host entries declare them
+inline void mbatch_outputs(HostArrays& h, sc_ctx* c, const MatchBatchSizes& sz, int32_t* corr, float* d2, uint32_t* count) {
+  h.out(c->mbatch_corr, corr, sz.slots * 8);
+  h.out(c->mbatch_d2, d2, sz.slots * 4);
+  h.out(c->mbatch_count, count, (size_t)sz.n_problems * 8);
+}
+// every refusal of a packed batched match; `p` only for a features entry, whose name for the messages is `features` (nullptr: the
+// match alone).  Fills *job (but its pointers) and *sz.
 int mbatch_check(sc_ctx* c, const uint32_t* src_off, const uint32_t* tgt_off, uint32_t n_problems, const sc_match_params* mp,
                  const sc_params* p, const char* features, MatchJob* job, MatchBatchSizes* sz);
 // the workspace of the match itself (gather: and of the gathered points)
 int mbatch_room(sc_ctx* c, const MatchJob& mj, const MatchBatchSizes& sz, bool gather);
-// the staging copy, the memset and the two launches (mbatch_room has been called)
-int mbatch_enqueue(sc_ctx* c, const MatchJob& mj, const MatchBatchSizes& sz, const float* d_fsrc, const float* d_ftgt, const uint32_t* src_off,
-                   const uint32_t* tgt_off, int32_t* d_corr, float* d_d2, uint32_t* d_count, const MatchGather& g);
-// the caller's points -> the context's slot-positioned n x 3 arrays, as the finish kernel is told
-MatchGather gather_of(const sc_ctx* c, const sc_params* p, const MatchBatchSizes& sz, const float* d_src_pts, const float* d_tgt_pts);
-// the registration kernel's argument on those slots, but for its outputs
+// bytes of the "clean" words in front of the column minima in mbatch_words
+inline size_t mbatch_clean_bytes(const MatchBatchSizes& sz) { return (((size_t)sz.n_problems + 1) / 2) * 8; }
+// The staging copy, the memset and the two launches (mbatch_room has been called).  The form passes what is its own: `fill` writes
+// sz.meta.words words of metadata into the staging area; `job` arrives with its inputs and with its pointers into mbatch_meta, but
+// the tile map, set; dist / finish are its launch pair.  Everything else of the job — the fields MatchBatchJob and MatchPairsJob
+// share by name — is filled here.
+template <class Job, class Fill>
+int mbatch_enqueue(sc_ctx* c, const MatchJob& mj, const MatchBatchSizes& sz, Job job, Fill fill, void (*dist)(const Job&, hipStream_t),
+                   void (*finish)(const Job&, hipStream_t), int32_t* d_corr, float* d_d2, uint32_t* d_count, const MatchGather& g) {
+  const size_t meta_bytes = sz.meta.words * 4;
+  SC_TRY(batch_staging_begin(c, meta_bytes));
+  fill(static_cast<uint32_t*>(c->h_batch_off));
+  SC_TRY(batch_staging_send(c, c->mbatch_meta, meta_bytes));
+  const size_t clean_bytes = mbatch_clean_bytes(sz), words_bytes = clean_bytes + (mj.mutual ? sz.total_t * 8 : 0);
+  HIPCHK(c, hipMemsetAsync(c->mbatch_words.p, 0xFF, words_bytes, c->stream));
+  job.tile_map = c->mbatch_meta.as<uint32_t>() + sz.meta.map_at;
+  job.n_problems = sz.n_problems; job.n_tiles = sz.n_tiles; job.dim = mj.dim; job.knn = mj.knn; job.kp = mj.r2 > 0.f ? 2u : mj.knn;
+  job.mutual = mj.mutual; job.r2 = mj.r2;
+  job.top = c->mbatch_top.as<uint64_t>();
+  job.colmin = mj.mutual ? reinterpret_cast<uint64_t*>(static_cast<char*>(c->mbatch_words.p) + clean_bytes) : nullptr;
+  job.clean = c->mbatch_words.as<uint32_t>();
+  job.corr = d_corr; job.d2 = d_d2; job.count = d_count; job.g = g;
+  dist(job, c->stream);
+  finish(job, c->stream);
+  HIPCHK(c, hipGetLastError());
+  return SC_OK;
+}
+// the packed form of it: both offset arrays, the slot starts and the tile map; MatchBatchJob and its launches.  A features entry
+// passes its sc_params and the problems' points, for the gather into mbatch_gsrc / _gtgt (p == nullptr: the match alone)
+int mbatch_enqueue_packed(sc_ctx* c, const MatchJob& mj, const MatchBatchSizes& sz, const float* d_fsrc, const float* d_ftgt,
+                          const uint32_t* src_off, const uint32_t* tgt_off, int32_t* d_corr, float* d_d2, uint32_t* d_count,
+                          const sc_params* p = nullptr, const float* d_src_pts = nullptr, const float* d_tgt_pts = nullptr);
+// the registration kernel's argument on the slots the match filled (the gathered points, the slot starts), but for its outputs
 BatchJob mbatch_slots_job(const sc_ctx* c, const MatchBatchSizes& sz, const sc_params* p);
+// sc_batch.hip's kernel on those slots (the count pairs are the caller's)
+int mbatch_register(sc_ctx* c, const MatchBatchSizes& sz, const sc_params* p, const uint32_t* d_count, sc_batch_result* d_res, uint8_t* d_mask);
 
 // ---- defined in sc_capi_polish_batch.hip, used by sc_capi_pairs.hip as well
 // sc_polish_params as a batch takes them (one candidate per problem); `who` opens the message

@@ -1,6 +1,7 @@
 // sc_match_batch_check.hpp — what sc_match_batch* decides about the caller's offset arrays on the host, before anything is enqueued,
-// and the tile map it derives from them.  Plain C++ on host memory, no HIP: sc_capi_match_batch.hip includes it, and so does the
-// stand-alone program tests/native/match_batch_check_main.cpp, which runs it under the address and undefined-behaviour sanitizers.
+// and the metadata it derives from them for the device.  Plain C++ on host memory, no HIP: the host files include it (through
+// sc_ctx.hpp), and so does the stand-alone program tests/native/match_batch_check_main.cpp, which runs it under the address and
+// undefined-behaviour sanitizers.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -48,6 +49,20 @@ inline void match_batch_tile_map(const uint32_t* src_off, uint32_t n_problems, u
   size_t t = 0;
   for (uint32_t b = 0; b < n_problems; b++)
     for (uint32_t r = 0; r < src_off[b + 1] - src_off[b]; r += rows) { map[2 * t] = b; map[2 * t + 1] = r; t++; }
+}
+
+// The metadata of a batched match as one device copy holds it: `words` 32-bit words, the slot starts (n_problems + 1 words,
+// sc_batch.hip's offset array) from word slot_at, the tile map (two words a tile) from word map_at.
+struct BatchMetaLayout { size_t words, slot_at, map_at; };
+// the packed form's: src_off | tgt_off | slot starts (batch_slot_meta) | tile map
+inline BatchMetaLayout match_batch_meta_layout(uint32_t n_problems, uint32_t n_tiles) {
+  const size_t nb1 = (size_t)n_problems + 1;
+  return BatchMetaLayout{3 * nb1 + 2 * (size_t)n_tiles, 2 * nb1, 3 * nb1};
+}
+inline void match_batch_meta_fill(const uint32_t* src_off, const uint32_t* tgt_off, uint32_t n_problems, uint32_t knn, uint32_t rows,
+                                  const BatchMetaLayout& at, uint32_t* meta) {
+  batch_slot_meta(src_off, tgt_off, n_problems, knn, meta);
+  match_batch_tile_map(src_off, n_problems, rows, meta + at.map_at);
 }
 
 }  // namespace sc

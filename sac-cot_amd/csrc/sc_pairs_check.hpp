@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "../../include/saccot.h"
+#include "sc_match_batch_check.hpp"
 
 namespace sc {
 
@@ -87,6 +88,18 @@ inline void pairs_tile_map(const uint32_t* set_off, const uint32_t* pairs, uint3
     const uint32_t a = pairs[2 * (size_t)p], ns = set_off[a + 1] - set_off[a];
     for (uint32_t r = 0; r < ns; r += rows) { map[2 * t] = p; map[2 * t + 1] = r; t++; }
   }
+}
+
+// the pairs form's metadata (BatchMetaLayout, sc_match_batch_check.hpp): the records | slot starts | tile map
+inline BatchMetaLayout pairs_meta_layout(uint32_t n_pairs, uint32_t n_tiles) {
+  const size_t recs = (size_t)PAIRS_REC_WORDS * n_pairs;
+  return BatchMetaLayout{recs + n_pairs + 1 + 2 * (size_t)n_tiles, recs, recs + n_pairs + 1};
+}
+inline void pairs_meta_fill(const uint32_t* set_off, const uint32_t* pairs, uint32_t n_pairs, uint32_t knn, uint32_t rows,
+                            const BatchMetaLayout& at, uint32_t* meta) {
+  pairs_records(set_off, pairs, n_pairs, knn, meta);
+  pairs_slots(set_off, pairs, n_pairs, knn, meta + at.slot_at);
+  pairs_tile_map(set_off, pairs, n_pairs, rows, meta + at.map_at);
 }
 
 }  // namespace sc

@@ -21,14 +21,25 @@ static void expect(const char* what, std::vector<uint32_t> so, std::vector<uint3
   if (!ok) { printf("FAIL %s: got %s\n", what, got ? got : "(accepted)"); failures++; }
   if (!got) {  // accepted: the tile map covers every row once, in order, and never crosses a problem
     const uint64_t tiles = sc::match_batch_tile_count(a, nb, 64);
-    uint32_t* map = new uint32_t[2 * tiles];
-    sc::match_batch_tile_map(a, nb, 64, map);
+    // ... inside the metadata as the device copy holds it: one array of exactly match_batch_meta_layout's words, both offset arrays
+    // and the slot starts in front of the map
+    const sc::BatchMetaLayout at = sc::match_batch_meta_layout(nb, (uint32_t)tiles);
+    uint32_t* meta = new uint32_t[at.words];
+    sc::match_batch_meta_fill(a, b, nb, knn, 64, at, meta);
+    const uint32_t* map = meta + at.map_at;
+    const size_t nb1 = (size_t)nb + 1;
+    if (at.slot_at != 2 * nb1 || at.map_at != 3 * nb1 || at.words != at.map_at + 2 * tiles) { printf("FAIL %s: the layout\n", what); failures++; }
+    for (uint32_t p = 0; p <= nb; p++)
+      if (meta[p] != a[p] || meta[nb1 + p] != b[p] || meta[at.slot_at + p] != (uint32_t)((uint64_t)a[p] * knn)) {
+        printf("FAIL %s: offsets / slot %u\n", what, p);
+        failures++;
+      }
     uint64_t t = 0;
     for (uint32_t p = 0; p < nb; p++)
       for (uint32_t r = 0; r < a[p + 1] - a[p]; r += 64, t++)
         if (t >= tiles || map[2 * t] != p || map[2 * t + 1] != r) { printf("FAIL %s: tile %llu\n", what, (unsigned long long)t); failures++; }
     if (t != tiles) { printf("FAIL %s: %llu tiles counted, %llu mapped\n", what, (unsigned long long)tiles, (unsigned long long)t); failures++; }
-    delete[] map;
+    delete[] meta;
   }
   delete[] a;
   delete[] b;

@@ -29,12 +29,13 @@ static void expect(const char* what, std::vector<uint32_t> off, std::vector<uint
     // accepted: the bases of a pair are the sums over the pairs BEFORE it — never a function of its sets' rows in the table, so two
     // pairs that share a set share nothing; the tile map covers every source row of every pair once, in order, inside the pair
     const sc::PairsTotals tot = sc::pairs_totals(so, pr, np, 64);
-    uint32_t* slot = new uint32_t[(size_t)np + 1];
-    uint32_t* rec = new uint32_t[(size_t)sc::PAIRS_REC_WORDS * np];
-    uint32_t* map = new uint32_t[tot.tiles ? 2 * tot.tiles : 1];
-    sc::pairs_slots(so, pr, np, knn, slot);
-    sc::pairs_records(so, pr, np, knn, rec);
-    sc::pairs_tile_map(so, pr, np, 64, map);
+    // the three as the device copy holds them: one array of exactly pairs_meta_layout's words, filled by pairs_meta_fill
+    const sc::BatchMetaLayout at = sc::pairs_meta_layout(np, (uint32_t)tot.tiles);
+    if (at.slot_at != (size_t)sc::PAIRS_REC_WORDS * np || at.map_at != at.slot_at + np + 1 || at.words != at.map_at + 2 * tot.tiles)
+      fail(what, "the metadata's layout", at.words);
+    uint32_t* meta = new uint32_t[at.words];
+    sc::pairs_meta_fill(so, pr, np, knn, 64, at, meta);
+    const uint32_t *rec = meta, *slot = meta + at.slot_at, *map = meta + at.map_at;
     uint64_t rows_s = 0, rows_t = 0, t = 0;
     for (uint32_t p = 0; p < np; p++) {
       const uint32_t a = pr[2 * p], b = pr[2 * p + 1], ns = so[a + 1] - so[a], nt = so[b + 1] - so[b];
@@ -48,9 +49,7 @@ static void expect(const char* what, std::vector<uint32_t> off, std::vector<uint
     }
     if (slot[np] != rows_s * knn || tot.total_s != rows_s || tot.total_t != rows_t) fail(what, "the totals", rows_s);
     if (t != tot.tiles) fail(what, "tiles mapped", t);
-    delete[] slot;
-    delete[] rec;
-    delete[] map;
+    delete[] meta;
   }
   delete[] so;
   delete[] pr;

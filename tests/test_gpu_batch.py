@@ -13,11 +13,15 @@ import numpy as np
 import pytest
 
 import batch_ref
+import instances_batch_ref as IR
+import match_batch_ref as M
+import pairs_ref as P
+import polish_batch_ref as PB
 from conftest import nan_equal_bits
 
 pytestmark = pytest.mark.gpu
 
-SC_OK, SC_EINVAL, SC_ENOHYP = 0, -1, -5
+SC_OK, SC_EINVAL, SC_ENOMEM, SC_ENOHYP = 0, -1, -2, -5
 SC_FLAG_TIMING, SC_FLAG_EXACT_TOTAL, SC_FLAG_REFINE = 1, 2, 8
 FIELDS = ("status", "n", "edges", "tri_kept", "tri_total", "best_rank", "best_count")
 
@@ -248,3 +252,98 @@ def test_refusals_leave_the_context_usable(pkg, O, reg):
         with pytest.raises(pkg.SacCotError) as e:
             call()
         assert e.value.status == SC_EINVAL
+
+
+# ---- 9: a host-array entry that the workspace cap refuses --------------------------------------------------------------------------
+def _assert_records(recs, erecs, what):
+    for b, (g, e) in enumerate(zip(recs, erecs)):
+        assert [int(g[f]) for f in FIELDS] == [int(e[f]) for f in FIELDS], (what, b)
+        assert nan_equal_bits(g["Rt"], e["Rt"]), (what, b)
+
+
+def _assert_slots(got, exp, slot, what):
+    """(records, corr, d2, count, mask) of a features entry against [dict(corr, d2, n, flag, rec, mask)], problem b's slot at slot[b]"""
+    recs, corr, d2, count, mask = got
+    assert len(recs) == len(exp), what
+    _assert_records(recs, [e["rec"] for e in exp], what)
+    for b, e in enumerate(exp):
+        lo, n = int(slot[b]), e["n"]
+        assert count[b].tolist() == [n, e["flag"]], (what, b)
+        assert np.array_equal(corr[lo: lo + n], e["corr"]) and d2[lo: lo + n].tobytes() == e["d2"].tobytes(), (what, b)
+        assert np.array_equal(mask[lo: lo + len(e["mask"])], e["mask"]), (what, b)
+
+
+def test_a_capped_workspace_refuses_before_anything_is_enqueued(pkg, O):
+    """max_workspace = 1: the first buffer an entry asks for is SC_ENOMEM on a fresh context and on a used one — host arithmetic,
+    made before the first copy or launch.  The same call under the default cap on the same context then equals the reference."""
+    import torch
+    reg = pkg.Registrar(0)
+    try:
+        problems = [batch_ref.scene(pkg, 64, .3), batch_ref.scene(pkg, 64, .3, seed=8000)]
+        kw = dict(batch_ref.KW, max_triangles=200)
+        src, tgt, off = _pack(problems)
+        p, tight = pkg.make_params(**kw), pkg.make_params(**kw, max_workspace=1)
+        q = pkg.make_polish_params(candidates=1, max_iter=16)
+        exp = batch_ref.batch(O, problems, kw)
+        mkw = dict(knn=1, mutual=True)
+        mp = pkg.api.make_match_params(33, **mkw)
+        scenes = M.feature_scenes()[:2]  # (the two smallest)
+        so, to = reg._offsets([len(s[1]) for s in scenes]), reg._offsets([len(s[3]) for s in scenes])
+        packed = [np.concatenate([s[k] for s in scenes]) for k in range(4)]
+        tab = P.table()
+        pairs = np.array([(P.R1, P.R2), (P.R2, P.R1)], np.uint32)  # (the two smallest sets)
+
+        def refused(call, what):
+            with pytest.raises(pkg.SacCotError) as e:
+                call()
+            print(what, e.value)
+            assert e.value.status == SC_ENOMEM, what
+
+        # a device form first, on the fresh context: its outputs keep what they held
+        d_src, d_tgt = torch.from_numpy(src).cuda(), torch.from_numpy(tgt).cuda()
+        d_res = torch.full((len(problems) * 80,), 0xAB, dtype=torch.uint8, device="cuda")
+        d_mask = torch.full((int(off[-1]),), 7, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        run = lambda a: reg.register_batch_device(d_src.data_ptr(), d_tgt.data_ptr(), off, a, d_res.data_ptr(), d_mask.data_ptr())  # noqa: E731
+        refused(lambda: run(tight), "sc_register_batch_device")
+        torch.cuda.synchronize()
+        assert bool((d_res == 0xAB).all()) and bool((d_mask == 7).all())
+        run(p)
+        torch.cuda.synchronize()
+        _assert_batch((np.frombuffer(d_res.cpu().numpy().tobytes(), pkg.BATCH_RESULT_DTYPE), d_mask.cpu().numpy(), off), exp,
+                      "sc_register_batch_device")
+
+        # the host forms, each refused by the first buffer of its own that is not there yet, and then run
+        run = lambda a: reg.register_batch_raw(src, tgt, off, a)  # noqa: E731
+        refused(lambda: run(tight), "sc_register_batch")
+        recs, mask = run(p)
+        _assert_batch((recs, mask, off), exp, "sc_register_batch")
+
+        run = lambda a: reg.polish_batch_raw(src, tgt, off, a, q, recs)  # noqa: E731
+        refused(lambda: run(tight), "sc_polish_batch")
+        pol, pmask = run(p)
+        epol, epmasks = PB.batch(O, problems, exp[0], kw["tau"], 0, 16)
+        for b in range(len(problems)):
+            assert [int(pol[b][f]) for f in PB.FIELDS] == [int(epol[b][f]) for f in PB.FIELDS], b
+            assert nan_equal_bits(pol[b]["Rt"], epol[b]["Rt"]) and np.array_equal(pmask[off[b]: off[b + 1]], epmasks[b]), b
+
+        run = lambda a: reg.register_instances_batch_raw(src, tgt, off, a, 4, 4)  # noqa: E731
+        refused(lambda: run(tight), "sc_register_instances_batch")
+        irecs, label, nfound = run(p)
+        erecs, elabels, efound = IR.batch(O, problems, kw, 0, 4, 4)
+        assert irecs.shape == erecs.shape and nfound.tolist() == efound.tolist()
+        for b in range(len(problems)):
+            _assert_records(irecs[:, b], erecs[:, b], ("sc_register_instances_batch", b))
+            assert np.array_equal(label[off[b]: off[b + 1]], elabels[b]), b
+
+        run = lambda a: reg.register_pairs_features(tab["pts"], tab["feat"], tab["set_off"], pairs, mp, a)  # noqa: E731
+        refused(lambda: run(pkg.make_params(**P.KW, max_workspace=1)), "sc_register_pairs_features")
+        got = run(pkg.make_params(**P.KW))
+        _assert_slots(got[:5], P.features(O, tab, pairs, mkw, P.KW), got[5], "sc_register_pairs_features")
+
+        run = lambda a: reg.register_batch_features_raw(packed[0], packed[1], so, packed[2], packed[3], to, mp, a)  # noqa: E731
+        refused(lambda: run(pkg.make_params(**M.KW, max_workspace=1)), "sc_register_batch_features")
+        efeat = [M.features_one(O, s[0], s[1], s[2], s[3], mkw, M.KW) for s in scenes]
+        _assert_slots(run(pkg.make_params(**M.KW)), efeat, so.astype(np.int64) * int(mp.knn), "sc_register_batch_features")
+    finally:
+        reg.close()
