@@ -34,7 +34,8 @@ def empty_plane(rec0):
 
 def rounds(O, src, tgt, kw, score_mode, rec0, max_instances, min_score, info=None):
     """-> (planes (max_instances,), label (n,) int32, nfound) given plane 0's record rec0.  info: a dict that receives `winners`, the
-    (i, j, k) of every found motion's triangle, and `claimed_vertex`, whether a round's winner had a claimed vertex."""
+    (i, j, k) of every found motion's triangle, `claimed_vertex`, whether a round's winner had a claimed vertex, and `end`, why the rounds
+    ended: ("min_score", the best score left, below it) or ("max_instances", max_instances)."""
     n = len(src)
     planes = np.zeros(max_instances, batch_ref.RESULT_DTYPE)
     planes[0] = rec0
@@ -52,6 +53,8 @@ def rounds(O, src, tgt, kw, score_mode, rec0, max_instances, min_score, info=Non
                else np.zeros(len(Rt), np.uint32))
         best_key = O.best_key(cnt)
         if best_key == 0 or (best_key >> 32) < min_score:
+            if info is not None:
+                info["end"] = ("min_score", int(best_key >> 32))
             break
         best = 0xFFFFFFFF - (best_key & 0xFFFFFFFF)
         m = O.mask(src, tgt, Rt[best], kw["tau"]).astype(bool) & alive
@@ -67,6 +70,9 @@ def rounds(O, src, tgt, kw, score_mode, rec0, max_instances, min_score, info=Non
         label[m] = k
         alive &= ~m
         found = k + 1
+    else:
+        if info is not None:
+            info["end"] = ("max_instances", max_instances)
     return planes, label, found
 
 
