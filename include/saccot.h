@@ -44,6 +44,7 @@ extern "C" {
 #define SC_HAS_POLISH_BATCH 1  /* this header declares sc_polish_batch* (added within 0.10) */
 #define SC_HAS_INSTANCES_BATCH 1  /* this header declares sc_register_instances_batch* (added within 0.10) */
 #define SC_HAS_PAIRS 1  /* this header declares sc_match_pairs*, sc_register_pairs_features* and sc_polish_pairs_slots_device (added within 0.10) */
+#define SC_HAS_POSE_INFO 1  /* this header declares sc_pose_info_batch* and sc_pose_info_pairs_slots_device (added within 0.10) */
 
 /* status codes */
 #define SC_OK        0
@@ -691,6 +692,87 @@ int sc_polish_pairs_slots_device(sc_ctx* ctx, const float* d_pts, const uint32_t
                                  uint32_t n_pairs, uint32_t knn, const sc_params* params, const sc_polish_params* pp,
                                  const int32_t* d_corr, const uint32_t* d_count, const sc_batch_result* d_res,
                                  sc_polish_batch_result* d_pol, uint8_t* d_mask);
+
+/* ---- the fp64 information matrix of a batch's poses: sc_pose_info_batch ------------------------------------------
+ * The callers of the batch entries feed every pair's pose into a pose graph or a fusion step as an EDGE, and an edge needs a
+ * weight: the 6 x 6 information matrix of the point-to-point least-squares problem at the pose, summed over the pose's inliers,
+ * and usually the inliers' sum of squared residuals.  These entries compute both for every problem of a batch in ONE launch, a
+ * workgroup per problem (sc_info_batch.hip), behind sc_register_batch* / sc_polish_batch* on the same context and without a host
+ * word.  Three forms, as sc_polish_batch has them: packed, slots (behind sc_register_batch_features_device) and pairs (behind
+ * sc_register_pairs_features_device).
+ *
+ * Layout: the problems as the sibling form takes them (packed: d_src, d_tgt, offset a HOST array of n_problems + 1 words,
+ * params->layout, 3 <= n_b <= SC_BATCH_MAX_N; slots / pairs: the points, the offsets or the table and the list, knn, d_corr and
+ * d_count exactly as sc_polish_batch_slots_device / sc_polish_pairs_slots_device take them).  d_info receives n_problems records of
+ * sc_pose_info_result.
+ * The pose input: d_pose is an array of records of pose_stride bytes; problem b's record starts at byte b * pose_stride and holds
+ * float Rt[12] at byte 0 and int32 status at byte 48 — nothing else of it is read.  sc_batch_result (stride 80) and
+ * sc_polish_batch_result (stride 64) are such records, and so is one plane of sc_register_instances_batch's d_res.  pose_stride must
+ * be a multiple of 4 and at least 52; d_pose must be 4-byte aligned.  d_pose is READ, never written, and need not come from this
+ * library.  Of sc_params only tau and layout are read; it is checked as sc_register_batch checks it.
+ *
+ * Semantics, per problem with input status SC_OK, finite points and a finite Rt (R = Rt[0 .. 8] row-major, t = Rt[9 .. 11]):
+ *   - correspondence m is an inlier iff it passes the canonical fp32 inlier test of (R, t) that the masks use; inliers = their
+ *     number c.
+ *   - for every inlier, in fp64:  x_r = (((double)R[r][0] * p0 + (double)R[r][1] * p1) + (double)R[r][2] * p2) + (double)t_r,
+ *     e_r = x_r - (double)q_r.  The products of two fp32 values are exact in fp64, every sum is rounded to nearest, and there is
+ *     no fused multiply-add anywhere.
+ *   - ten sums: s_r = sum x_r (3), m_rs = sum x_r * x_s for r <= s (6), sse = sum ((e0 * e0 + e1 * e1) + e2 * e2) (1); each in the
+ *     library's canonical order: chunks of 64 consecutive indices summed sequentially from 0.0 in index order over the chunk's
+ *     inliers, then the chunk sums added sequentially in chunk order.
+ *   - the matrix is that of the residual e = x - q under pose' = exp([w, v]) * pose — the perturbation applied on the LEFT, in the
+ *     target frame, rotation first —: J = [-[x]x | I], info = sum J^T J, assembled from the sums entry by entry:
+ *       rotation block           (m00 + m11 + m22) I - M:  info[0] = m11 + m22, info[7] = m00 + m22, info[14] = m00 + m11 (one
+ *                                rounded add each), off the diagonal -m_rs (an exact negation)
+ *       rotation-translation     [s]x: rows (0, -s2, s1), (s2, 0, -s0), (-s1, s0, 0); the translation-rotation block is its transpose
+ *       translation block        c I
+ *     so info is symmetric bit for bit.
+ *   - c == 0: status SC_OK, every byte of info and sse zero.  Nothing is declined for c < 3: a caller that wants a well-posed edge
+ *     looks at inliers and at the matrix.
+ *   - no fp64 chain can overflow for finite fp32 input, whatever Rt holds: |x_r| <= 3 FLT_MAX^2 + FLT_MAX < 2^258, a term is below
+ *     3 * 2^518 and a sum has at most 512 of them: below 2^530, far from DBL_MAX.
+ *   - Input status != SC_OK: that status is passed through with a zero record.
+ *   - Input status SC_OK but a non-finite coordinate, or a non-finite Rt: SC_EINVAL with a zero record.  It is found on the device,
+ *     affects only that problem and does not fail the call.
+ *   - slots / pairs: the problem is gathered through corr while staging.  A flagged problem, or one with count[2b] < 3 or above its
+ *     capacity, passes its input status through (SC_EINVAL if that status claims SC_OK); an index in corr outside the problem is
+ *     SC_EINVAL for that problem.
+ *   - A record is a function of the problem's points, its pose and tau only: not of its position in the batch, of the neighbours,
+ *     of n_problems or of the context's history — bit for bit.
+ *
+ * Errors: the CALL returns SC_EINVAL, decided on the host before anything is enqueued, sc_last_error naming which: a NULL argument;
+ * a pose_stride below 52 or no multiple of 4; everything sc_polish_batch / _slots_device / sc_polish_pairs_slots_device refuses of
+ * the offsets, sc_params, knn, the table and the list; a call outstanding on the context.  The device forms enqueue on the context's
+ * stream and return without waiting: outputs are complete in stream order.  (They may wait for the previous batch call's copy out of
+ * the offset staging area, as the sibling entries do.)  All entries end the frame a context may hold and leave none.
+ * Workspace: the copy of the offsets (records), plus the host form's device copies of its arrays; buffers of these entries' own,
+ * allocated by the first such call, counted in workspace_bytes and held against params->max_workspace (SC_ENOMEM).  A context that
+ * never calls these entries allocates and runs nothing new.
+ * Not here: a mask output (sc_polish_batch writes it); a form for a scored frame (sc_register); weights per correspondence. */
+typedef struct sc_pose_info_result {   /* 320 bytes */
+  double   info[36];    /* 6 x 6 row-major, symmetric; order: rotation x y z, translation x y z */
+  double   sse;         /* sum over the inliers of |R p + t - q|^2, fp64                        */
+  int32_t  status;      /* SC_OK, or why there is no matrix: SC_ENOHYP / SC_EINVAL              */
+  uint32_t inliers;     /* correspondences that pass the canonical inlier test of the pose      */
+  uint32_t reserved[4]; /* written as 0                                                         */
+} sc_pose_info_result;
+/* every buffer but offset in HBM: d_src / d_tgt total x 3 floats, d_pose n_problems records of pose_stride bytes, d_info n_problems records */
+int sc_pose_info_batch_device(sc_ctx* ctx, const float* d_src, const float* d_tgt, const uint32_t* offset, uint32_t n_problems,
+                              const sc_params* params, const void* d_pose, uint32_t pose_stride, sc_pose_info_result* d_info);
+/* the same with host arrays; waits */
+int sc_pose_info_batch(sc_ctx* ctx, const float* src, const float* tgt, const uint32_t* offset, uint32_t n_problems,
+                       const sc_params* params, const void* pose, uint32_t pose_stride, sc_pose_info_result* info);
+/* behind sc_register_batch_features_device (and sc_polish_batch_slots_device): the points and both offset arrays as given there, its
+ * d_corr and d_count */
+int sc_pose_info_batch_slots_device(sc_ctx* ctx, const float* d_src_pts, const uint32_t* src_off, const float* d_tgt_pts,
+                                    const uint32_t* tgt_off, uint32_t n_problems, uint32_t knn, const sc_params* params,
+                                    const int32_t* d_corr, const uint32_t* d_count, const void* d_pose, uint32_t pose_stride,
+                                    sc_pose_info_result* d_info);
+/* behind sc_register_pairs_features_device (and sc_polish_pairs_slots_device): the table's points, set_off and pairs as given there,
+ * its d_corr and d_count; d_pose and d_info n_pairs records */
+int sc_pose_info_pairs_slots_device(sc_ctx* ctx, const float* d_pts, const uint32_t* set_off, uint32_t n_sets, const uint32_t* pairs,
+                                    uint32_t n_pairs, uint32_t knn, const sc_params* params, const int32_t* d_corr,
+                                    const uint32_t* d_count, const void* d_pose, uint32_t pose_stride, sc_pose_info_result* d_info);
 
 /* ---- two-phase form for one-process-per-GPU sharding --------------------------------
  * Phase 1: A and B replicated, C1+C2 on this rank's blocks of the top-T list; writes this rank's winner key

@@ -46,6 +46,7 @@ EXPORTS = ["sc_version", "sc_strerror", "sc_default_params", "sc_create", "sc_de
            "sc_register_instances_batch", "sc_register_instances_batch_device", "sc_register_instances_batch_features_device",
            "sc_pairs_layout", "sc_match_pairs", "sc_match_pairs_device", "sc_register_pairs_features", "sc_register_pairs_features_device",
            "sc_polish_pairs_slots_device",
+           "sc_pose_info_batch", "sc_pose_info_batch_device", "sc_pose_info_batch_slots_device", "sc_pose_info_pairs_slots_device",
            "sc_hypothesize_device", "sc_finalize_device",
            "sc_hypothesize_begin_device", "sc_hypothesize_end_device", "sc_finalize_gathered_device", "sc_finalize_gathered_device_async",
            "sc_shard_plan_query", "sc_shard_compat_device", "sc_shard_edges_device", "sc_shard_select_device",
@@ -119,6 +120,16 @@ class ScPolishBatchResult(C.Structure):
 POLISH_BATCH_RESULT_DTYPE = np.dtype([("Rt", np.float32, 12), ("status", np.int32), ("score0", np.uint32), ("score", np.uint32),
                                       ("iters", np.uint16), ("stop", np.uint16)])  # sc_polish_batch_result as a numpy record
 SC_POLISH_STOP_FIXED, SC_POLISH_STOP_DECLINED, SC_POLISH_STOP_MAX_ITER = 0, 1, 2
+
+
+class ScPoseInfoResult(C.Structure):
+    """Mirror of `sc_pose_info_result` (include/saccot.h), 320 bytes: one problem's record of sc_pose_info_batch."""
+    _fields_ = [("info", C.c_double * 36), ("sse", C.c_double), ("status", C.c_int32), ("inliers", C.c_uint32),
+                ("reserved", C.c_uint32 * 4)]
+
+
+POSE_INFO_RESULT_DTYPE = np.dtype([("info", np.float64, 36), ("sse", np.float64), ("status", np.int32), ("inliers", np.uint32),
+                                   ("reserved", np.uint32, 4)])  # sc_pose_info_result as a numpy record
 SC_MATCH_BATCH_MAX_N = 4096  # rows a side of one problem of sc_match_batch
 SC_INSTANCES_BATCH_MAX = 16  # motions per problem of sc_register_instances_batch at most
 
@@ -239,6 +250,10 @@ def load_library() -> C.CDLL:
     L.sc_register_pairs_features_device.argtypes = [vp, vp, vp, u32p, C.c_uint32, u32p, C.c_uint32, mp, pp, vp, vp, vp, vp, vp]
     L.sc_register_pairs_features.argtypes = [vp, f32p, f32p, u32p, C.c_uint32, u32p, C.c_uint32, mp, pp, vp, i32p, f32p, u32p, u8p]
     L.sc_polish_pairs_slots_device.argtypes = [vp, vp, u32p, C.c_uint32, u32p, C.c_uint32, C.c_uint32, pp, qp, vp, vp, vp, vp, vp]
+    L.sc_pose_info_batch.argtypes = [vp, f32p, f32p, u32p, C.c_uint32, pp, vp, C.c_uint32, vp]
+    L.sc_pose_info_batch_device.argtypes = [vp, vp, vp, u32p, C.c_uint32, pp, vp, C.c_uint32, vp]
+    L.sc_pose_info_batch_slots_device.argtypes = [vp, vp, u32p, vp, u32p, C.c_uint32, C.c_uint32, pp, vp, vp, vp, C.c_uint32, vp]
+    L.sc_pose_info_pairs_slots_device.argtypes = [vp, vp, u32p, C.c_uint32, u32p, C.c_uint32, C.c_uint32, pp, vp, vp, vp, C.c_uint32, vp]
     L.sc_hypothesize_device.argtypes = [vp, vp, vp, C.c_int64, pp, vp, sp]
     L.sc_finalize_device.argtypes = [vp, vp, vp, vp, sp]
     L.sc_hypothesize_begin_device.argtypes = [vp, vp, vp, C.c_int64, pp, vp, sp]
@@ -839,6 +854,52 @@ class Registrar:
         self._frame_n = 0
         self._check(self._lib.sc_polish_pairs_slots_device(self._h, d_pts, _p(set_off, C.c_uint32), ns, _p(pairs, C.c_uint32), npairs, knn,
                                                            C.byref(params), C.byref(pparams), d_corr, d_count, d_res, d_pol, d_mask))
+
+    # ---- the fp64 information matrix of a batch's poses (include/saccot.h, sc_pose_info_batch) -------------------------
+    def pose_info_batch_raw(self, src, tgt, offset, params: ScParams, pose):
+        """sc_pose_info_batch on packed arrays: src / tgt / offset as register_batch_raw's; pose (B,) records of any dtype whose
+        items start with float Rt[12] and int32 status — BATCH_RESULT_DTYPE, POLISH_BATCH_RESULT_DTYPE, a plane of
+        register_instances_batch_raw's records — read only -> records (B,) of POSE_INFO_RESULT_DTYPE."""
+        src, tgt = _f32c(src), _f32c(tgt)
+        offset = np.ascontiguousarray(offset, dtype=np.uint32)
+        pose = np.ascontiguousarray(pose)
+        nb = max(len(offset) - 1, 0)
+        if pose.ndim != 1 or len(pose) != nb:
+            raise ValueError("pose_info_batch_raw: one pose record per problem")
+        info = np.zeros(max(nb, 1), POSE_INFO_RESULT_DTYPE)
+        self._frame_n = 0
+        self._check(self._lib.sc_pose_info_batch(self._h, _p(src, C.c_float), _p(tgt, C.c_float), _p(offset, C.c_uint32), nb,
+                                                 C.byref(params), pose.ctypes.data_as(C.c_void_p), pose.dtype.itemsize,
+                                                 info.ctypes.data_as(C.c_void_p)))
+        return info[:nb]
+
+    def pose_info_batch_device(self, d_src: int, d_tgt: int, offset, params: ScParams, d_pose: int, pose_stride: int, d_info: int):
+        """sc_pose_info_batch_device: points, pose records (pose_stride bytes each, read only) and output records (320 bytes each) in
+        HBM, offset a HOST array (B + 1,) uint32; enqueues on the context's stream and returns without waiting."""
+        offset = np.ascontiguousarray(offset, dtype=np.uint32)
+        self._frame_n = 0
+        self._check(self._lib.sc_pose_info_batch_device(self._h, d_src, d_tgt, _p(offset, C.c_uint32), max(len(offset) - 1, 0),
+                                                        C.byref(params), d_pose, pose_stride, d_info))
+
+    def pose_info_batch_slots_device(self, d_src_pts: int, src_off, d_tgt_pts: int, tgt_off, knn: int, params: ScParams, d_corr: int,
+                                     d_count: int, d_pose: int, pose_stride: int, d_info: int):
+        """sc_pose_info_batch_slots_device: behind register_batch_features_device — its points, offsets, d_corr and d_count; d_pose B
+        records of pose_stride bytes, d_info B records of 320 bytes; enqueues on the context's stream and returns without waiting."""
+        src_off, tgt_off = np.ascontiguousarray(src_off, dtype=np.uint32), np.ascontiguousarray(tgt_off, dtype=np.uint32)
+        self._frame_n = 0
+        self._check(self._lib.sc_pose_info_batch_slots_device(self._h, d_src_pts, _p(src_off, C.c_uint32), d_tgt_pts, _p(tgt_off, C.c_uint32),
+                                                              max(len(src_off) - 1, 0), knn, C.byref(params), d_corr, d_count, d_pose,
+                                                              pose_stride, d_info))
+
+    def pose_info_pairs_slots_device(self, d_pts: int, set_off, pairs, knn: int, params: ScParams, d_corr: int, d_count: int, d_pose: int,
+                                     pose_stride: int, d_info: int):
+        """sc_pose_info_pairs_slots_device: behind register_pairs_features_device — its points, set_off, pairs, d_corr and d_count;
+        d_pose P records of pose_stride bytes, d_info P records of 320 bytes; enqueues on the context's stream and returns without
+        waiting."""
+        set_off, pairs, ns, npairs = self._table(set_off, pairs)
+        self._frame_n = 0
+        self._check(self._lib.sc_pose_info_pairs_slots_device(self._h, d_pts, _p(set_off, C.c_uint32), ns, _p(pairs, C.c_uint32), npairs, knn,
+                                                              C.byref(params), d_corr, d_count, d_pose, pose_stride, d_info))
 
     def hypothesize_device(self, d_src: int, d_tgt: int, n: int, params: ScParams, d_key: int):
         st = ScStats(C.sizeof(ScStats))

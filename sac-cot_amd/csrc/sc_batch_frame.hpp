@@ -1,7 +1,7 @@
-// sc_batch_frame.hpp — the frame around one problem of a batch kernel, shared by batch_register_kernel (sc_batch.hip) and
-// polish_batch_kernel (sc_polish_batch.hip): a workgroup of THREADS threads owns the problem, stages its points into six LDS planes,
+// sc_batch_frame.hpp — the frame around one problem of a batch kernel, shared by batch_register_kernel (sc_batch.hip),
+// polish_batch_kernel (sc_polish_batch.hip) and pose_info_kernel (sc_info_batch.hip): a workgroup of THREADS threads owns the problem, stages its points into six LDS planes,
 // and leaves a record — staged in LDS, stored one dword per lane — and a mask range.  Each kernel keeps its own LDS layout (BatchLds,
-// PolishLds) and the words of its record behind the twelve of (R, t); only these functions are shared.
+// PolishLds, InfoLds) and the words of its record behind the twelve of (R, t); only these functions are shared.
 #pragma once
 #include "sc_kernels.hpp"
 
@@ -15,6 +15,9 @@ __device__ __forceinline__ const BatchJob& job_of(const InstBatchSlotJob& a) { r
 __device__ __forceinline__ const PolishBatchJob& job_of(const PolishBatchJob& a) { return a; }
 __device__ __forceinline__ const PolishBatchJob& job_of(const PolishBatchSlotJob& a) { return a.job; }
 __device__ __forceinline__ const PolishBatchJob& job_of(const PolishBatchPairsJob& a) { return a.job; }
+__device__ __forceinline__ const PoseInfoJob& job_of(const PoseInfoJob& a) { return a; }
+__device__ __forceinline__ const PoseInfoJob& job_of(const PoseInfoSlotJob& a) { return a.job; }
+__device__ __forceinline__ const PoseInfoJob& job_of(const PoseInfoPairsJob& a) { return a.job; }
 
 // Staging: rows [off, off + n) of src / tgt (n x 3 row-major, or with soa three planes of `total`) -> pt (px py pz qx qy qz).
 // true: THIS thread read a non-finite coordinate (the caller ends the problem with SC_EINVAL).

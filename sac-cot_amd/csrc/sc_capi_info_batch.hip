@@ -1,0 +1,148 @@
+// sc_capi_info_batch.hip — the C ABI's fp64 information matrix of a batch's poses (include/saccot.h, sc_pose_info_batch):
+// sc_pose_info_batch_device, sc_pose_info_batch, sc_pose_info_batch_slots_device and sc_pose_info_pairs_slots_device.  Host-only, on
+// the context and the helpers of sc_ctx.hpp; the kernel is sc_info_batch.hip's.
+//
+// offsets -> pinned staging (the area and event every batch entry shares: batch_offsets_to_device; the slot form's three arrays:
+// batch_slot_meta; the pairs form's records: pairs_records) -> device copy (enqueued) -> ONE launch, a workgroup per problem.
+// Nothing is read back: a problem's status is a field of its record.  Everything that can refuse the call is decided on the host
+// before anything is enqueued.
+#include "sc_ctx.hpp"
+#include "sc_pairs_check.hpp"
+
+using namespace sc;
+
+namespace {
+
+constexpr uint32_t POSE_BYTES = 52;  // what is read of a pose record: float Rt[12], int32 status
+
+// the refusals every form shares: the context, sc_params, the stride of the pose records
+int pinfo_common_check(sc_ctx* c, const sc_params* p, uint32_t pose_stride, const char* who) {
+  SC_TRY(entry_checks(c, nullptr, ENDS_FRAME | NOT_BUSY));
+  SC_TRY(batch_params_check(c, p, who));
+  if (pose_stride < POSE_BYTES || pose_stride % 4 != 0) return refuse(c, who, "pose_stride must be a multiple of 4 and at least 52");
+  return SC_OK;
+}
+
+int pinfo_check(sc_ctx* c, const uint32_t* offset, uint32_t n_problems, const sc_params* p, uint32_t pose_stride) {
+  SC_TRY(pinfo_common_check(c, p, pose_stride, "sc_pose_info_batch"));
+  if (const char* what = batch_offsets_error(offset, n_problems)) return refuse(c, "sc_pose_info_batch", what);
+  return SC_OK;
+}
+
+// what the kernel reads of sc_params and of the caller's records (the other pointers are the form's)
+PoseInfoJob pinfo_job(const sc_params* p, uint32_t n_problems, const void* d_pose, uint32_t pose_stride, sc_pose_info_result* d_info) {
+  PoseInfoJob job{};
+  job.soa = p->layout == SC_SOA;
+  job.tau2 = derive(p).tau2;
+  job.n_problems = n_problems;
+  job.pose = d_pose; job.pose_stride = pose_stride;
+  job.out = reinterpret_cast<PoseInfoRecord*>(d_info);
+  return job;
+}
+
+int pinfo_enqueue(sc_ctx* c, const float* d_src, const float* d_tgt, const uint32_t* offset, uint32_t n_problems, const sc_params* p,
+                  const void* d_pose, uint32_t pose_stride, sc_pose_info_result* d_info) {
+  SC_TRY(batch_offsets_to_device(c, offset, n_problems, c->pinfo_off));
+  PoseInfoJob job = pinfo_job(p, n_problems, d_pose, pose_stride, d_info);
+  job.src = d_src; job.tgt = d_tgt; job.offset = c->pinfo_off.as<uint32_t>();
+  job.total = offset[n_problems];
+  launch_pose_info_batch(job, c->stream);
+  HIPCHK(c, hipGetLastError());
+  return SC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sc_pose_info_batch_device(sc_ctx* c, const float* d_src, const float* d_tgt, const uint32_t* offset, uint32_t n_problems,
+                              const sc_params* p, const void* d_pose, uint32_t pose_stride, sc_pose_info_result* d_info) {
+  if (!c) return SC_EINVAL;
+  if (!d_src || !d_tgt || !offset || !p || !d_pose || !d_info) return refuse(c, "sc_pose_info_batch_device", "a NULL argument");
+  SC_TRY(pinfo_check(c, offset, n_problems, p, pose_stride));
+  HIPCHK(c, hipSetDevice(c->device));
+  c->cap_bytes = workspace_cap(p);
+  return pinfo_enqueue(c, d_src, d_tgt, offset, n_problems, p, d_pose, pose_stride, d_info);
+}
+
+int sc_pose_info_batch(sc_ctx* c, const float* src, const float* tgt, const uint32_t* offset, uint32_t n_problems, const sc_params* p,
+                       const void* pose, uint32_t pose_stride, sc_pose_info_result* info) {
+  if (!c) return SC_EINVAL;
+  if (!src || !tgt || !offset || !p || !pose || !info) return refuse(c, "sc_pose_info_batch", "a NULL argument");
+  SC_TRY(pinfo_check(c, offset, n_problems, p, pose_stride));
+  HIPCHK(c, hipSetDevice(c->device));
+  c->cap_bytes = workspace_cap(p);
+  const size_t total = offset[n_problems], pts = total * 12;
+  HostArrays h(c);
+  h.in(c->pinfo_src, src, pts);
+  h.in(c->pinfo_tgt, tgt, pts);
+  h.in(c->pinfo_pose, pose, (size_t)(n_problems - 1) * pose_stride + POSE_BYTES);  // (nothing is read behind the last record's status)
+  h.out(c->pinfo_out, info, (size_t)n_problems * sizeof(sc_pose_info_result));
+  SC_TRY(h.room());
+  SC_TRY(h.send());
+  SC_TRY(pinfo_enqueue(c, c->pinfo_src.as<float>(), c->pinfo_tgt.as<float>(), offset, n_problems, p, c->pinfo_pose.p, pose_stride,
+                       c->pinfo_out.as<sc_pose_info_result>()));
+  return h.fetch();
+}
+
+int sc_pose_info_batch_slots_device(sc_ctx* c, const float* d_src_pts, const uint32_t* src_off, const float* d_tgt_pts,
+                                    const uint32_t* tgt_off, uint32_t n_problems, uint32_t knn, const sc_params* p, const int32_t* d_corr,
+                                    const uint32_t* d_count, const void* d_pose, uint32_t pose_stride, sc_pose_info_result* d_info) {
+  static const char* const who = "sc_pose_info_batch_slots_device";
+  if (!c) return SC_EINVAL;
+  if (!d_src_pts || !src_off || !d_tgt_pts || !tgt_off || !p || !d_corr || !d_count || !d_pose || !d_info)
+    return refuse(c, who, "a NULL argument");
+  SC_TRY(pinfo_common_check(c, p, pose_stride, who));
+  if (knn < 1 || knn > 4) return refuse(c, who, "knn must be 1 .. 4");
+  if (const char* what = match_batch_offsets_error(src_off, tgt_off, n_problems, knn, true)) return refuse(c, who, what);
+  HIPCHK(c, hipSetDevice(c->device));
+  c->cap_bytes = workspace_cap(p);
+  // both offset arrays and the slot starts, one copy
+  const size_t nb1 = (size_t)n_problems + 1, bytes = 3 * nb1 * 4;
+  ENSURE(c, c->pinfo_off, bytes);
+  SC_TRY(batch_staging_begin(c, bytes));
+  batch_slot_meta(src_off, tgt_off, n_problems, knn, static_cast<uint32_t*>(c->h_batch_off));
+  SC_TRY(batch_staging_send(c, c->pinfo_off, bytes));
+  const uint32_t* meta = c->pinfo_off.as<uint32_t>();
+  PoseInfoSlotJob slots{};
+  slots.job = pinfo_job(p, n_problems, d_pose, pose_stride, d_info);
+  PoseInfoJob& job = slots.job;
+  job.src = d_src_pts; job.tgt = d_tgt_pts; job.offset = meta;
+  job.total = src_off[n_problems];
+  slots.tgt_off = meta + nb1; slots.slot = meta + 2 * nb1;
+  slots.corr = d_corr; slots.count = d_count;
+  slots.knn = knn; slots.total_t = tgt_off[n_problems];
+  launch_pose_info_batch_slots(slots, c->stream);
+  HIPCHK(c, hipGetLastError());
+  return SC_OK;
+}
+
+int sc_pose_info_pairs_slots_device(sc_ctx* c, const float* d_pts, const uint32_t* set_off, uint32_t n_sets, const uint32_t* pairs,
+                                    uint32_t n_pairs, uint32_t knn, const sc_params* p, const int32_t* d_corr, const uint32_t* d_count,
+                                    const void* d_pose, uint32_t pose_stride, sc_pose_info_result* d_info) {
+  static const char* const who = "sc_pose_info_pairs_slots_device";
+  if (!c) return SC_EINVAL;
+  if (!d_pts || !set_off || !pairs || !p || !d_corr || !d_count || !d_pose || !d_info) return refuse(c, who, "a NULL argument");
+  SC_TRY(pinfo_common_check(c, p, pose_stride, who));
+  if (const char* what = pairs_error(set_off, n_sets, pairs, n_pairs, knn, true)) return refuse(c, who, what);
+  HIPCHK(c, hipSetDevice(c->device));
+  c->cap_bytes = workspace_cap(p);
+  // the pairs' records, one copy
+  const size_t bytes = (size_t)PAIR_WORDS * n_pairs * 4;
+  ENSURE(c, c->pinfo_off, bytes);
+  SC_TRY(batch_staging_begin(c, bytes));
+  pairs_records(set_off, pairs, n_pairs, knn, static_cast<uint32_t*>(c->h_batch_off));
+  SC_TRY(batch_staging_send(c, c->pinfo_off, bytes));
+  PoseInfoPairsJob arg{};
+  arg.job = pinfo_job(p, n_pairs, d_pose, pose_stride, d_info);
+  PoseInfoJob& job = arg.job;
+  job.src = d_pts; job.tgt = d_pts; job.offset = nullptr;  // both sides are rows of the one table; the records say which
+  job.total = set_off[n_sets];
+  arg.rec = c->pinfo_off.as<uint32_t>();
+  arg.corr = d_corr; arg.count = d_count; arg.knn = knn;
+  launch_pose_info_batch_pairs(arg, c->stream);
+  HIPCHK(c, hipGetLastError());
+  return SC_OK;
+}
+
+}  // extern "C"

@@ -122,7 +122,11 @@ struct Workspace {
       // sc_register_instances_batch: allocated by the first such call, never by a frame or by another batch entry.  off: the copy of
       // the caller's offsets; the rest: device copies of the host entry's arrays (the features form holds what
       // sc_register_batch_features_device holds, in the mbatch buffers)
-      ibatch_off, ibatch_src, ibatch_tgt, ibatch_res, ibatch_label, ibatch_nfound;
+      ibatch_off, ibatch_src, ibatch_tgt, ibatch_res, ibatch_label, ibatch_nfound,
+      // sc_pose_info_batch: allocated by the first such call, never by a frame or by another batch entry.  off: the copy of the
+      // caller's offsets (the slot form: both arrays and the slot starts; the pairs form: the pairs' records); the rest: device copies
+      // of the host entry's arrays
+      pinfo_off, pinfo_src, pinfo_tgt, pinfo_pose, pinfo_out;
 };
 constexpr size_t N_WORKSPACE_BUFS = sizeof(Workspace) / sizeof(Buf);
 static_assert(std::is_standard_layout<Workspace>::value && alignof(Workspace) == alignof(Buf) && sizeof(Workspace) == N_WORKSPACE_BUFS * sizeof(Buf),

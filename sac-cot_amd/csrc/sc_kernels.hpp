@@ -790,6 +790,46 @@ void launch_polish_batch(const PolishBatchJob& job, hipStream_t st);
 void launch_polish_batch_slots(const PolishBatchSlotJob& job, hipStream_t st);
 void launch_polish_batch_pairs(const PolishBatchPairsJob& job, hipStream_t st);
 
+// ---- the fp64 information matrix of a batch's poses (sc_pose_info_batch; sc_info_batch.hip) ------------------
+// One problem's result: sc_pose_info_result of include/saccot.h, field for field (sc_info_batch.hip asserts the size).
+struct PoseInfoRecord {
+  double info[36];
+  double sse;
+  int32_t status;
+  uint32_t inliers;
+  uint32_t reserved[4];
+};
+// Problem b owns rows [offset[b], offset[b + 1]) of src / tgt, as in BatchJob; its pose record starts at byte b * pose_stride of
+// `pose` — float Rt[12] at byte 0, int32 status at byte 48: read, never written —, out[b] is the result.  Everything in device memory.
+struct PoseInfoJob {
+  const float* src; const float* tgt;
+  const uint32_t* offset;
+  uint32_t n_problems, total;
+  int soa;
+  float tau2;
+  const void* pose;
+  uint32_t pose_stride;
+  PoseInfoRecord* out;
+};
+// The slot form and the pairs form: what PolishBatchSlotJob and PolishBatchPairsJob say, field for field.  Types of their own, so
+// that the plain form's kernel argument and code do not depend on them.
+struct PoseInfoSlotJob {
+  PoseInfoJob job;
+  const uint32_t* tgt_off; const uint32_t* slot;
+  const int32_t* corr; const uint32_t* count;
+  uint32_t knn, total_t;
+};
+struct PoseInfoPairsJob {
+  PoseInfoJob job;
+  const uint32_t* rec;
+  const int32_t* corr; const uint32_t* count;
+  uint32_t knn;
+};
+// One workgroup per problem; every record is written (complete in stream order).
+void launch_pose_info_batch(const PoseInfoJob& job, hipStream_t st);
+void launch_pose_info_batch_slots(const PoseInfoSlotJob& job, hipStream_t st);
+void launch_pose_info_batch_pairs(const PoseInfoPairsJob& job, hipStream_t st);
+
 // ---- descriptor matching for a batch of small problems (sc_match_batch; sc_match_batch.hip) -----------------
 // Problem b owns rows [src_off[b], src_off[b + 1]) of fsrc and [tgt_off[b], tgt_off[b + 1]) of ftgt (1 .. MATCH_BATCH_MAX_N rows
 // each, checked by the caller) and the output slot that starts at entry slot[b] = src_off[b] * knn.  tile_map: n_tiles pairs
