@@ -45,6 +45,7 @@ extern "C" {
 #define SC_HAS_INSTANCES_BATCH 1  /* this header declares sc_register_instances_batch* (added within 0.10) */
 #define SC_HAS_PAIRS 1  /* this header declares sc_match_pairs*, sc_register_pairs_features* and sc_polish_pairs_slots_device (added within 0.10) */
 #define SC_HAS_POSE_INFO 1  /* this header declares sc_pose_info_batch* and sc_pose_info_pairs_slots_device (added within 0.10) */
+#define SC_HAS_POSE_INFO_FRAME 1  /* this header declares sc_pose_info_frame* and sc_pose_info_default_params (added within 0.10) */
 
 /* status codes */
 #define SC_OK        0
@@ -748,7 +749,8 @@ int sc_polish_pairs_slots_device(sc_ctx* ctx, const float* d_pts, const uint32_t
  * Workspace: the copy of the offsets (records), plus the host form's device copies of its arrays; buffers of these entries' own,
  * allocated by the first such call, counted in workspace_bytes and held against params->max_workspace (SC_ENOMEM).  A context that
  * never calls these entries allocates and runs nothing new.
- * Not here: a mask output (sc_polish_batch writes it); a form for a scored frame (sc_register); weights per correspondence. */
+ * Not here: a mask output (sc_polish_batch writes it); weights per correspondence.  (The form for a scored frame is
+ * sc_pose_info_frame, below.) */
 typedef struct sc_pose_info_result {   /* 320 bytes */
   double   info[36];    /* 6 x 6 row-major, symmetric; order: rotation x y z, translation x y z */
   double   sse;         /* sum over the inliers of |R p + t - q|^2, fp64                        */
@@ -773,6 +775,88 @@ int sc_pose_info_batch_slots_device(sc_ctx* ctx, const float* d_src_pts, const u
 int sc_pose_info_pairs_slots_device(sc_ctx* ctx, const float* d_pts, const uint32_t* set_off, uint32_t n_sets, const uint32_t* pairs,
                                     uint32_t n_pairs, uint32_t knn, const sc_params* params, const int32_t* d_corr,
                                     const uint32_t* d_count, const void* d_pose, uint32_t pose_stride, sc_pose_info_result* d_info);
+
+/* ---- the fp64 information matrix on a scored frame: sc_pose_info_frame ------------------------------------------
+ * sc_pose_info_batch weighs the edges a batch produces.  The large single frame — sc_register*, sc_peel, sc_register_instances and
+ * sc_polish on 5 000 to 2^24 correspondences — is where the poses multiply: its winner, up to 64 polished candidates and one motion
+ * per round of sc_peel, each of them an edge of a fusion step.  These entries give every such pose its information matrix, the
+ * inliers' sum of squared residuals and their count in ONE launch, a workgroup per pose (sc_info_frame.hip), on the frame the context
+ * holds, without a host word.
+ *
+ * A FRAME is as defined for sc_peel.  The entries read the frame's staged points, its n and its tau, and change nothing in it:
+ * rounds of sc_peel and calls of sc_polish before or after are unaffected and do not affect it, and the call may be repeated.  They
+ * do NOT end the frame — peel a round, take its information matrix, peel the next.  Correspondences are in the caller's ORIGINAL
+ * indexing (the staged planes are in that order: it is the order sc_peel's masks are written in).
+ *
+ * The pose input: d_pose is an array of n_poses records of pose_stride bytes; pose k's record starts at byte k * pose_stride and holds
+ * float Rt[12] at byte 0 — R = Rt[0 .. 8] row-major, t = Rt[9 .. 11] — and, with SC_POSE_INFO_STATUS, an int32 status at byte 48.
+ * Without that flag nothing past byte 47 is read.  d_pose is READ, never written, must be 4-byte aligned and need not come from this
+ * library.  All of these serve:
+ *     the 12 floats of sc_register_device / sc_peel_device      stride 48   no flag
+ *     the Rt array of sc_register_instances                     stride 48   no flag
+ *     sc_polish_cand (rank sits at byte 48)                     stride 64   no flag
+ *     sc_batch_result                                           stride 80   SC_POSE_INFO_STATUS
+ *     sc_polish_batch_result                                    stride 64   SC_POSE_INFO_STATUS
+ * pose_stride is a multiple of 4 and at least 48, at least 52 with the flag.
+ * The selection: which correspondences may be inliers at all.  SC_POSE_INFO_SEL_NONE: every one (d_sel is not read; NULL).
+ * SC_POSE_INFO_SEL_MASK: d_sel holds n bytes, m takes part iff d_sel[m] != 0, the same set for every pose — sc_peel's mask_r: in the
+ * inlier-count mode inliers == that round's best_count for the round's fp32 winner.  SC_POSE_INFO_SEL_LABEL: d_sel holds n int32; for
+ * pose k, m takes part iff d_sel[m] == label0 + (int32)k — sc_register_instances' label with label0 = 0 and its Rt array: in the
+ * inlier-count mode inliers == score[k].  d_sel is READ, never written.
+ *
+ * Semantics, per pose k with a finite Rt (and, with the flag, status SC_OK): sc_pose_info_batch's, word for word.
+ *   - correspondence m is an inlier iff it takes part per sel_mode AND passes the canonical fp32 inlier test of (R, t) that the
+ *     masks use; inliers = their number c.
+ *   - for every inlier, in fp64:  x_r = (((double)R[r][0] * p0 + (double)R[r][1] * p1) + (double)R[r][2] * p2) + (double)t_r,
+ *     e_r = x_r - (double)q_r.  The products of two fp32 values are exact in fp64, every sum is rounded to nearest, and there is
+ *     no fused multiply-add anywhere.
+ *   - ten sums: s_r = sum x_r (3), m_rs = sum x_r * x_s for r <= s (6), sse = sum ((e0 * e0 + e1 * e1) + e2 * e2) (1); each in the
+ *     library's canonical order: chunks of 64 consecutive indices summed sequentially from 0.0 in index order over the chunk's
+ *     inliers, then the chunk sums added sequentially in chunk order.
+ *   - info = sum J^T J, J = [-[x]x | I], assembled from the sums entry by entry exactly as sc_pose_info_batch assembles it (see
+ *     there: the rotation block one rounded add or an exact negation per entry, [s]x and its transpose, c I), so info is symmetric
+ *     bit for bit.
+ *   - c == 0: status SC_OK, every byte of info and sse zero.  Nothing is declined for c < 3.
+ *   - no fp64 chain can overflow for finite fp32 input, whatever Rt holds: |x_r| <= 3 FLT_MAX^2 + FLT_MAX < 2^258, a term is below
+ *     3 * 2^518 < 2^520 and a sum has at most 2^24 of them: below 2^(518 + 2 + 24) = 2^544, far from DBL_MAX.
+ *   - Where both entries can see the same problem — n <= SC_BATCH_MAX_N, the same points, pose and tau, SC_POSE_INFO_SEL_NONE — the
+ *     record equals sc_pose_info_batch's, bit for bit.
+ *   - A record is a function of the frame's input, the pose, the selection and tau only: not of k (but through SEL_LABEL), of
+ *     n_poses, of the other poses, of how the frame was enqueued or of the context's history — bit for bit.
+ *   - With SC_POSE_INFO_STATUS a status other than SC_OK at byte 48 is passed through with a zero record.
+ *   - A non-finite Rt: SC_EINVAL with a zero record, for that pose only.  It is found on the device and does not fail the call.
+ *     (The frame's points are finite already: staging checked them.)
+ *
+ * Errors: the CALL returns SC_EINVAL, decided on the host before anything is enqueued, sc_last_error naming which: a NULL ctx (no
+ * text), ip, d_pose or d_info; ip->size wrong; sel_mode above 2; d_sel NULL with a mode that reads it; label0 != 0 outside
+ * SC_POSE_INFO_SEL_LABEL; an unknown flag or a non-zero reserved word; n_poses 0 or above SC_POSE_INFO_MAX_POSES; a pose_stride
+ * that breaks the rule above; no frame on the context — also after any batch, match or sharded entry, or after a frame call that
+ * returned SC_ENOHYP: sc_peel's refusal, with its text —; a call outstanding on the context.  A refused call leaves the frame.
+ * The device form enqueues on the context's stream and returns without waiting, and needs no host word: d_info is complete in
+ * stream order.  The host form copies in, enqueues, copies out and waits.
+ * Workspace: the chunk sums' scratch — n_poses x ceil(n / 64) x 16 doubles — plus the host form's device copies; buffers of these
+ * entries' own, allocated by the first such call, counted in workspace_bytes and held against the frame's cap (SC_ENOMEM, nothing
+ * enqueued, the frame stays).  A context that never calls these entries allocates and runs nothing new.
+ * Not here: weights per correspondence; a form for sharded / multi-GPU frames, which leave no frame. */
+#define SC_POSE_INFO_MAX_POSES 1024u
+#define SC_POSE_INFO_SEL_NONE  0u   /* every correspondence of the frame may be an inlier                          */
+#define SC_POSE_INFO_SEL_MASK  1u   /* sel: n bytes; m takes part iff sel[m] != 0 (the same set for every pose)     */
+#define SC_POSE_INFO_SEL_LABEL 2u   /* sel: n int32; for pose k, m takes part iff sel[m] == label0 + (int32)k       */
+#define SC_POSE_INFO_STATUS    1u   /* flags: a pose record holds an int32 status at byte 48 (as in the batch form) */
+typedef struct sc_pose_info_params {   /* 32 bytes */
+  uint32_t size;         /* = sizeof(sc_pose_info_params) */
+  uint32_t sel_mode;     /* SC_POSE_INFO_SEL_*            */
+  int32_t  label0;       /* SEL_LABEL only, else 0        */
+  uint32_t flags;        /* SC_POSE_INFO_STATUS or 0      */
+  uint32_t reserved[4];  /* must be 0                     */
+} sc_pose_info_params;
+int sc_pose_info_default_params(sc_pose_info_params* ip);   /* size set, everything else 0 */
+/* d_pose: n_poses records of pose_stride bytes, float Rt[12] at byte 0; d_sel per sel_mode (NULL with SEL_NONE); d_info: n_poses records */
+int sc_pose_info_frame_device(sc_ctx* ctx, const sc_pose_info_params* ip, const void* d_pose, uint32_t pose_stride,
+                              uint32_t n_poses, const void* d_sel, sc_pose_info_result* d_info);
+/* the same with host arrays (pose, sel, info); waits */
+int sc_pose_info_frame(sc_ctx* ctx, const sc_pose_info_params* ip, const void* pose, uint32_t pose_stride,
+                       uint32_t n_poses, const void* sel, sc_pose_info_result* info);
 
 /* ---- two-phase form for one-process-per-GPU sharding --------------------------------
  * Phase 1: A and B replicated, C1+C2 on this rank's blocks of the top-T list; writes this rank's winner key

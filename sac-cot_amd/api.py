@@ -47,6 +47,7 @@ EXPORTS = ["sc_version", "sc_strerror", "sc_default_params", "sc_create", "sc_de
            "sc_pairs_layout", "sc_match_pairs", "sc_match_pairs_device", "sc_register_pairs_features", "sc_register_pairs_features_device",
            "sc_polish_pairs_slots_device",
            "sc_pose_info_batch", "sc_pose_info_batch_device", "sc_pose_info_batch_slots_device", "sc_pose_info_pairs_slots_device",
+           "sc_pose_info_default_params", "sc_pose_info_frame", "sc_pose_info_frame_device",
            "sc_hypothesize_device", "sc_finalize_device",
            "sc_hypothesize_begin_device", "sc_hypothesize_end_device", "sc_finalize_gathered_device", "sc_finalize_gathered_device_async",
            "sc_shard_plan_query", "sc_shard_compat_device", "sc_shard_edges_device", "sc_shard_select_device",
@@ -130,6 +131,18 @@ class ScPoseInfoResult(C.Structure):
 
 POSE_INFO_RESULT_DTYPE = np.dtype([("info", np.float64, 36), ("sse", np.float64), ("status", np.int32), ("inliers", np.uint32),
                                    ("reserved", np.uint32, 4)])  # sc_pose_info_result as a numpy record
+
+
+class ScPoseInfoParams(C.Structure):
+    """Mirror of `sc_pose_info_params` (include/saccot.h), 32 bytes: which correspondences of the frame take part (SC_POSE_INFO_SEL_*),
+    the label of pose 0 (SEL_LABEL), SC_POSE_INFO_STATUS or 0."""
+    _fields_ = [("size", C.c_uint32), ("sel_mode", C.c_uint32), ("label0", C.c_int32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32 * 4)]
+
+
+SC_POSE_INFO_MAX_POSES = 1024
+SC_POSE_INFO_SEL_NONE, SC_POSE_INFO_SEL_MASK, SC_POSE_INFO_SEL_LABEL = 0, 1, 2
+SC_POSE_INFO_STATUS = 1
 SC_MATCH_BATCH_MAX_N = 4096  # rows a side of one problem of sc_match_batch
 SC_INSTANCES_BATCH_MAX = 16  # motions per problem of sc_register_instances_batch at most
 
@@ -254,6 +267,10 @@ def load_library() -> C.CDLL:
     L.sc_pose_info_batch_device.argtypes = [vp, vp, vp, u32p, C.c_uint32, pp, vp, C.c_uint32, vp]
     L.sc_pose_info_batch_slots_device.argtypes = [vp, vp, u32p, vp, u32p, C.c_uint32, C.c_uint32, pp, vp, vp, vp, C.c_uint32, vp]
     L.sc_pose_info_pairs_slots_device.argtypes = [vp, vp, u32p, C.c_uint32, u32p, C.c_uint32, C.c_uint32, pp, vp, vp, vp, C.c_uint32, vp]
+    ip = C.POINTER(ScPoseInfoParams)
+    L.sc_pose_info_default_params.argtypes = [ip]
+    L.sc_pose_info_frame.argtypes = [vp, ip, vp, C.c_uint32, C.c_uint32, vp, vp]
+    L.sc_pose_info_frame_device.argtypes = [vp, ip, vp, C.c_uint32, C.c_uint32, vp, vp]
     L.sc_hypothesize_device.argtypes = [vp, vp, vp, C.c_int64, pp, vp, sp]
     L.sc_finalize_device.argtypes = [vp, vp, vp, vp, sp]
     L.sc_hypothesize_begin_device.argtypes = [vp, vp, vp, C.c_int64, pp, vp, sp]
@@ -294,6 +311,11 @@ def make_match_params(dim: int, knn: int = 1, mutual: bool = False, ratio: float
 def make_polish_params(candidates: int = 8, max_iter: int = 16, flags: int = 0) -> ScPolishParams:
     """sc_polish_params: the best `candidates` hypotheses of the frame (1 .. 64), at most `max_iter` refits each (1 .. 64)."""
     return ScPolishParams(C.sizeof(ScPolishParams), candidates, max_iter, flags)
+
+
+def make_pose_info_params(sel_mode: int = SC_POSE_INFO_SEL_NONE, label0: int = 0, flags: int = 0) -> ScPoseInfoParams:
+    """sc_pose_info_params: sel_mode SC_POSE_INFO_SEL_*, label0 (SEL_LABEL only), flags SC_POSE_INFO_STATUS or 0."""
+    return ScPoseInfoParams(C.sizeof(ScPoseInfoParams), sel_mode, label0, flags)
 
 
 def shard_plan(params: ScParams, n: int) -> ScShardPlan:
@@ -900,6 +922,34 @@ class Registrar:
         self._frame_n = 0
         self._check(self._lib.sc_pose_info_pairs_slots_device(self._h, d_pts, _p(set_off, C.c_uint32), ns, _p(pairs, C.c_uint32), npairs, knn,
                                                               C.byref(params), d_corr, d_count, d_pose, pose_stride, d_info))
+
+    # ---- the same on the frame the last register* call left (include/saccot.h, sc_pose_info_frame) ---------------------------
+    def pose_info_frame(self, pose, iparams: ScPoseInfoParams | None = None, sel=None, **kw):
+        """sc_pose_info_frame: pose (K,) records of any dtype whose items start with float Rt[12] (and, with SC_POSE_INFO_STATUS, an
+        int32 status behind it) — or a float32 array (K, 12) / (12,) —; sel None, (n,) uint8 (SEL_MASK) or (n,) int32 (SEL_LABEL), read
+        only -> records (K,) of POSE_INFO_RESULT_DTYPE.  The frame stays.  kw: sel_mode, label0, flags (make_pose_info_params)."""
+        q = iparams or make_pose_info_params(**kw)
+        pose = np.ascontiguousarray(pose)
+        if pose.dtype.fields is None:
+            pose = np.ascontiguousarray(pose, dtype=np.float32).reshape(-1, 12)
+            stride = 48
+        else:
+            pose = pose.reshape(-1)
+            stride = pose.dtype.itemsize
+        k = len(pose)
+        if sel is not None:
+            sel = np.ascontiguousarray(sel, dtype=np.int32 if q.sel_mode == SC_POSE_INFO_SEL_LABEL else np.uint8)
+            if sel.size != self._frame_n:
+                raise ValueError("pose_info_frame: sel holds one entry per correspondence of the frame")
+        info = np.zeros(max(k, 1), POSE_INFO_RESULT_DTYPE)
+        self._check(self._lib.sc_pose_info_frame(self._h, C.byref(q), pose.ctypes.data_as(C.c_void_p), stride, k,
+                                                 None if sel is None else sel.ctypes.data_as(C.c_void_p), info.ctypes.data_as(C.c_void_p)))
+        return info[:k]
+
+    def pose_info_frame_device(self, iparams: ScPoseInfoParams, d_pose: int, pose_stride: int, n_poses: int, d_sel: int, d_info: int):
+        """sc_pose_info_frame_device: pose records (pose_stride bytes each, read only), the selection (0: none) and the output
+        records (320 bytes each) in HBM; enqueues on the context's stream and returns without waiting.  The frame stays."""
+        self._check(self._lib.sc_pose_info_frame_device(self._h, C.byref(iparams), d_pose, pose_stride, n_poses, d_sel or None, d_info))
 
     def hypothesize_device(self, d_src: int, d_tgt: int, n: int, params: ScParams, d_key: int):
         st = ScStats(C.sizeof(ScStats))

@@ -126,7 +126,11 @@ struct Workspace {
       // sc_pose_info_batch: allocated by the first such call, never by a frame or by another batch entry.  off: the copy of the
       // caller's offsets (the slot form: both arrays and the slot starts; the pairs form: the pairs' records); the rest: device copies
       // of the host entry's arrays
-      pinfo_off, pinfo_src, pinfo_tgt, pinfo_pose, pinfo_out;
+      pinfo_off, pinfo_src, pinfo_tgt, pinfo_pose, pinfo_out,
+      // sc_pose_info_frame: allocated by the first such call, never by a frame or by another entry.  tmp: the chunk sums and bit
+      // words, n_poses x pose_info_frame_scratch_bytes(n) — not polish_tmp: a polish may be enqueued behind the call —; the rest:
+      // device copies of the host entry's arrays
+      pinfo_frame_tmp, pinfo_frame_pose, pinfo_frame_sel, pinfo_frame_out;
 };
 constexpr size_t N_WORKSPACE_BUFS = sizeof(Workspace) / sizeof(Buf);
 static_assert(std::is_standard_layout<Workspace>::value && alignof(Workspace) == alignof(Buf) && sizeof(Workspace) == N_WORKSPACE_BUFS * sizeof(Buf),

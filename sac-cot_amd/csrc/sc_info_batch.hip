@@ -17,6 +17,7 @@
 #include "../../include/saccot.h"
 #include "sc_batch_frame.hpp"
 #include "sc_block.hpp"
+#include "sc_info.hpp"
 #include "sc_winner.hpp"
 
 namespace sc {
@@ -31,7 +32,7 @@ namespace {
 constexpr int IT = 256;           // threads of a workgroup: 4 waves ballot the 8 chunks in two rounds, 80 chains fit one round
 constexpr int IN = BATCH_MAX_N;   // correspondences of a problem at most
 constexpr int ICH = IN / 64;      // chunks of the canonical summation at most
-constexpr int NSUM = 10;          // s0 s1 s2 | m00 m01 m02 m11 m12 m22 | sse
+constexpr int NSUM = INFO_NSUM;   // s0 s1 s2 | m00 m01 m02 m11 m12 m22 | sse (sc_info.hpp)
 constexpr int NROW = 4;           // term rows of a chunk: x0 x1 x2, the residual term
 // A chunk's row of 64 doubles is padded to 65: row (r, ch) then starts 2 (8 r + ch) dwords into the 64-dword bank row, so the lanes
 // of one step of the chains — every (chunk, row) at about the same index — read 32 different banks instead of one.
@@ -75,24 +76,6 @@ __device__ __forceinline__ InfoSides sides_of(const PoseInfoSlotJob& a, uint32_t
 __device__ __forceinline__ InfoSides sides_of(const PoseInfoPairsJob& a, uint32_t p) {
   const uint32_t* r = a.rec + (size_t)PAIR_WORDS * p;
   return InfoSides{r[PW_SRC], r[PW_NS], r[PW_TGT], r[PW_NT], a.job.total, r[PW_SLOT]};
-}
-
-// entry (i, j) of sum J^T J, J = [-[x]x | I], from the ten sums S and the inlier count c (include/saccot.h spells the assembly)
-__device__ __forceinline__ double info_entry(const double* S, int i, int j, uint32_t c) {
-  const double s[3] = {S[0], S[1], S[2]};
-  const double m00 = S[3], m01 = S[4], m02 = S[5], m11 = S[6], m12 = S[7], m22 = S[8];
-  if (i < 3 && j < 3) {
-    if (i == j) return i == 0 ? m11 + m22 : (i == 1 ? m00 + m22 : m00 + m11);
-    const int lo = i < j ? i : j, hi = i < j ? j : i;
-    return -(lo == 0 ? (hi == 1 ? m01 : m02) : m12);
-  }
-  if (i >= 3 && j >= 3) return i == j ? (double)c : 0.0;
-  // [s]x, rows (0, -s2, s1), (s2, 0, -s0), (-s1, s0, 0): entry (r, k) for the upper right block, (k, r) for the lower left
-  const int r = i < 3 ? i : j, k = i < 3 ? j - 3 : i - 3;
-  if (r == k) return 0.0;
-  const int o = 3 - r - k;  // the third index
-  const double v = o == 0 ? s[0] : (o == 1 ? s[1] : s[2]);
-  return ((r + 1) % 3 == k) ? -v : v;  // (0, 1), (1, 2), (2, 0) carry the minus
 }
 
 // The kernel's argument is PoseInfoJob (sc_pose_info_batch), PoseInfoSlotJob (sc_pose_info_batch_slots_device) or PoseInfoPairsJob

@@ -830,6 +830,27 @@ void launch_pose_info_batch(const PoseInfoJob& job, hipStream_t st);
 void launch_pose_info_batch_slots(const PoseInfoSlotJob& job, hipStream_t st);
 void launch_pose_info_batch_pairs(const PoseInfoPairsJob& job, hipStream_t st);
 
+// ---- the same on a scored frame (sc_pose_info_frame; sc_info_frame.hip) -----------------------------------------
+// Pose k's record starts at byte k * pose_stride of `pose` — float Rt[12] at byte 0 and, if `status`, an int32 status at byte 48: read,
+// never written —, out[k] is the result.  sel by sel_mode (SC_POSE_INFO_SEL_*): nullptr, n bytes, or n int32 compared with
+// label0 + k.  scratch: n_poses * pose_info_frame_scratch_bytes(pts.n).  Everything in device memory.
+struct PoseInfoFrameJob {
+  Points pts;  // the frame's staged planes, in the caller's indexing
+  float tau2;
+  uint32_t n_poses;
+  const void* pose;
+  uint32_t pose_stride;
+  int status;
+  const void* sel;
+  uint32_t sel_mode;
+  int32_t label0;
+  double* scratch;
+  PoseInfoRecord* out;
+};
+size_t pose_info_frame_scratch_bytes(int n);
+// ONE launch, a workgroup of 1024 threads per pose; every record is written (complete in stream order).
+void launch_pose_info_frame(const PoseInfoFrameJob& job, hipStream_t st);
+
 // ---- descriptor matching for a batch of small problems (sc_match_batch; sc_match_batch.hip) -----------------
 // Problem b owns rows [src_off[b], src_off[b + 1]) of fsrc and [tgt_off[b], tgt_off[b + 1]) of ftgt (1 .. MATCH_BATCH_MAX_N rows
 // each, checked by the caller) and the output slot that starts at entry slot[b] = src_off[b] * knn.  tile_map: n_tiles pairs
