@@ -46,6 +46,7 @@ extern "C" {
 #define SC_HAS_PAIRS 1  /* this header declares sc_match_pairs*, sc_register_pairs_features* and sc_polish_pairs_slots_device (added within 0.10) */
 #define SC_HAS_POSE_INFO 1  /* this header declares sc_pose_info_batch* and sc_pose_info_pairs_slots_device (added within 0.10) */
 #define SC_HAS_POSE_INFO_FRAME 1  /* this header declares sc_pose_info_frame* and sc_pose_info_default_params (added within 0.10) */
+#define SC_HAS_POLISH_POSES 1  /* this header declares sc_polish_poses* (added within 0.10) */
 
 /* status codes */
 #define SC_OK        0
@@ -857,6 +858,93 @@ int sc_pose_info_frame_device(sc_ctx* ctx, const sc_pose_info_params* ip, const 
 /* the same with host arrays (pose, sel, info); waits */
 int sc_pose_info_frame(sc_ctx* ctx, const sc_pose_info_params* ip, const void* pose, uint32_t pose_stride,
                        uint32_t n_poses, const void* sel, sc_pose_info_result* info);
+
+/* ---- caller-supplied poses refitted on a scored frame: sc_polish_poses ---------------------------------------------
+ * A large frame produces many poses — its winner, one motion per round of sc_peel / sc_register_instances, and poses the caller
+ * brings along: the previous frame's pose, an odometry prior, a pose composed along a loop.  sc_polish iterates only the top
+ * candidates of the frame's own total order, which all belong to the dominant motion; motions 1, 2, ... stay at their 3-point Kabsch
+ * pose (SC_FLAG_REFINE adds at most one refit), and an external pose cannot be polished on a frame at all.  These entries iterate
+ * "inliers of (R, t) -> fp64 least-squares refit -> inliers again" to a fixed point for up to SC_POLISH_POSES_MAX poses of ANY origin
+ * on the frame the context holds: ONE launch, a workgroup per pose (sc_polish_poses.hip), no host word.  It is what
+ * sc_polish_batch_device does for any pose record of a batch, for the frame.
+ *
+ * A FRAME is as defined for sc_peel.  The entries read the frame's staged points, its n, tau and score_mode, and change nothing in
+ * it: they do NOT end the frame, may be repeated, and may be interleaved with sc_peel, sc_polish and sc_pose_info_frame, which are
+ * unaffected and do not affect them.  Correspondences are in the caller's ORIGINAL indexing.
+ *
+ * The pose input follows sc_pose_info_frame exactly: d_pose is an array of n_poses records of pose_stride bytes; pose k's record
+ * starts at byte k * pose_stride and holds float Rt[12] at byte 0 and, with SC_POLISH_POSES_STATUS, an int32 status at byte 48;
+ * without that flag nothing past byte 47 is read.  pose_stride is a multiple of 4 and at least 48, at least 52 with the flag.  d_pose
+ * is READ, never written, must be 4-byte aligned and need not come from this library (see sc_pose_info_frame for the records that
+ * serve).  The output record is sc_polish_batch_result (64 bytes): it is therefore itself a pose record for
+ * sc_pose_info_frame_device (stride 64, SC_POSE_INFO_STATUS) and for a further sc_polish_poses_device (stride 64,
+ * SC_POLISH_POSES_STATUS).  d_mask, if not NULL, receives n_poses x n bytes: pose k's mask is bytes [k * n, (k + 1) * n).
+ *
+ * The selection: which correspondences take part for pose k — part(m).  SC_POLISH_POSES_SEL_NONE: every one (d_sel is not read;
+ * NULL).  _SEL_MASK: d_sel holds n bytes, part(m) iff d_sel[m] != 0, the same set for every pose (sc_peel's mask_r).  _SEL_LABEL:
+ * d_sel holds n int32, part(m) iff d_sel[m] == label0 + k (what motion k of sc_register_instances claimed).  _SEL_ALIVE: d_sel holds
+ * n int32, part(m) iff d_sel[m] < label0 or d_sel[m] >= label0 + k — with sc_register_instances' label and label0 = 0 the
+ * correspondences that were alive in sc_peel's round k: claimed by no motion, or by motion k or a later one.  label0 + k is a
+ * wrapping 32-bit add, compared as int32, as sc_pose_info_frame computes it.  d_sel is READ, never written.
+ *
+ * Semantics, per pose k with a finite Rt (and, with the flag, status SC_OK): step 2 of sc_polish with part ANDed into every inlier
+ * set.  Rt_0 = the input; for it = 1 .. max_iter: mask = part(m) && the canonical inlier test of Rt_{it-1}; Rt_it = the fp64 refit
+ * over that mask in its canonical order — chunks of 64 consecutive ORIGINAL indices — rounded to fp32; stop when the refit is
+ * declined (fewer than 3 inliers, or a non-finite result: SC_POLISH_STOP_DECLINED), when Rt_it equals Rt_{it-1} bit for bit
+ * (SC_POLISH_STOP_FIXED), or after max_iter refits (SC_POLISH_STOP_MAX_ITER).  iters = the refits that changed (R, t); Rt = the last
+ * iterate; score0 / score = the frame's score_mode score of Rt_0 / of Rt over the correspondences that take part; mask byte m =
+ * part(m) && the inlier test of Rt.
+ *   - A first refit that is declined: status SC_OK, Rt = the input's bits, iters 0, score = score0.
+ *   - With the flag, a status other than SC_OK is passed through; R = I, t = 0, scores 0, iters 0, stop SC_POLISH_STOP_DECLINED, mask
+ *     zero.
+ *   - A non-finite Rt: SC_EINVAL with the same output shape, for that pose only.  It is found on the device and does not fail the
+ *     call.  (The frame's points are finite already: staging checked them.)
+ *   - A record is a function of the frame's input, the pose, the selection, tau, score_mode and max_iter only, bit for bit: not of k
+ *     (but through SEL_LABEL / SEL_ALIVE), of n_poses, of the other poses, of how the frame was enqueued or of the context's history.
+ * Equalities, each bit for bit:
+ *   1. SEL_NONE and the frame's fp32 winner as pose: Rt, score0, score, iters and the mask are those of
+ *      sc_polish(candidates = 1, the same max_iter).
+ *   2. SEL_NONE and a hypothesis of the ranked list as pose: the result is that hypothesis' sc_polish_cand record.
+ *   3. n <= SC_BATCH_MAX_N, the same points, pose and parameters, SEL_NONE: the 64-byte record and the mask are sc_polish_batch's.
+ *   4. SEL_ALIVE, label0 = 0, max_iter = 1, and the label and Rt arrays of sc_register_instances WITHOUT SC_FLAG_REFINE: Rt[k] is what
+ *      the same call WITH SC_FLAG_REFINE returns for motion k — both are the refit over mask_k in original indexing — and score0[k]
+ *      is that call's score[k], in every score mode.
+ *   5. SEL_MASK with sc_peel's mask_r and max_iter = 1: Rt is that round's SC_FLAG_REFINE pose.
+ *
+ * Errors: the CALL returns SC_EINVAL, decided on the host before anything is enqueued, sc_last_error naming which: a NULL ctx (no
+ * text), params, d_pose or d_pol; params->size wrong; max_iter outside 1 .. 64; sel_mode above 3; d_sel NULL with a mode that reads
+ * it; label0 != 0 with SEL_NONE or SEL_MASK; an unknown flag or a non-zero reserved word; n_poses 0 or above SC_POLISH_POSES_MAX; a
+ * pose_stride that breaks the rule above; no frame on the context (sc_peel's refusal, with its text); a call outstanding on the
+ * context.  A refused call leaves the frame.  The device form enqueues on the context's stream and returns without waiting, and
+ * needs no host word: d_pol and d_mask are complete in stream order.  The host form copies in, enqueues, copies out and waits.
+ * Workspace: the chunk sums' scratch — n_poses x ceil(n / 64) x 16 doubles, a buffer of these entries' own — plus the host form's
+ * device copies (n_poses x n mask bytes among them when a mask is asked for); allocated by the first such call, counted in
+ * workspace_bytes and held against the frame's cap (SC_ENOMEM, nothing enqueued, the frame stays).  A context that never calls these
+ * entries allocates and runs nothing new.
+ * Not here: a relabelled label output; a form for sharded frames; weights per correspondence; a batch form (sc_polish_batch takes
+ * arbitrary poses already). */
+#define SC_POLISH_POSES_MAX        1024u
+#define SC_POLISH_POSES_SEL_NONE   0u  /* every correspondence takes part                                                    */
+#define SC_POLISH_POSES_SEL_MASK   1u  /* sel: n bytes; m takes part iff sel[m] != 0 (the same set for every pose)            */
+#define SC_POLISH_POSES_SEL_LABEL  2u  /* sel: n int32; pose k: m takes part iff sel[m] == label0 + k                         */
+#define SC_POLISH_POSES_SEL_ALIVE  3u  /* sel: n int32; pose k: m takes part iff sel[m] < label0 or sel[m] >= label0 + k      */
+#define SC_POLISH_POSES_STATUS     1u  /* flags: a pose record holds an int32 status at byte 48                               */
+typedef struct sc_polish_poses_params {  /* 32 bytes */
+  uint32_t size;         /* = sizeof(sc_polish_poses_params)   */
+  uint32_t max_iter;     /* refits per pose at most, 1 .. 64   */
+  uint32_t sel_mode;     /* SC_POLISH_POSES_SEL_*              */
+  int32_t  label0;       /* SEL_LABEL / SEL_ALIVE only, else 0 */
+  uint32_t flags;        /* SC_POLISH_POSES_STATUS or 0        */
+  uint32_t reserved[3];  /* must be 0                          */
+} sc_polish_poses_params;
+int sc_polish_poses_default_params(sc_polish_poses_params* qp);   /* size set, max_iter 16, everything else 0 */
+/* d_pose: n_poses records of pose_stride bytes, float Rt[12] at byte 0; d_sel per sel_mode (NULL with SEL_NONE); d_pol: n_poses
+ * records; d_mask: n_poses x n bytes, or NULL */
+int sc_polish_poses_device(sc_ctx* ctx, const sc_polish_poses_params* qp, const void* d_pose, uint32_t pose_stride,
+                           uint32_t n_poses, const void* d_sel, sc_polish_batch_result* d_pol, uint8_t* d_mask);
+/* the same with host arrays (pose, sel, pol, mask); waits */
+int sc_polish_poses(sc_ctx* ctx, const sc_polish_poses_params* qp, const void* pose, uint32_t pose_stride, uint32_t n_poses,
+                    const void* sel, sc_polish_batch_result* pol, uint8_t* mask);
 
 /* ---- two-phase form for one-process-per-GPU sharding --------------------------------
  * Phase 1: A and B replicated, C1+C2 on this rank's blocks of the top-T list; writes this rank's winner key

@@ -48,6 +48,7 @@ EXPORTS = ["sc_version", "sc_strerror", "sc_default_params", "sc_create", "sc_de
            "sc_polish_pairs_slots_device",
            "sc_pose_info_batch", "sc_pose_info_batch_device", "sc_pose_info_batch_slots_device", "sc_pose_info_pairs_slots_device",
            "sc_pose_info_default_params", "sc_pose_info_frame", "sc_pose_info_frame_device",
+           "sc_polish_poses_default_params", "sc_polish_poses", "sc_polish_poses_device",
            "sc_hypothesize_device", "sc_finalize_device",
            "sc_hypothesize_begin_device", "sc_hypothesize_end_device", "sc_finalize_gathered_device", "sc_finalize_gathered_device_async",
            "sc_shard_plan_query", "sc_shard_compat_device", "sc_shard_edges_device", "sc_shard_select_device",
@@ -143,6 +144,18 @@ class ScPoseInfoParams(C.Structure):
 SC_POSE_INFO_MAX_POSES = 1024
 SC_POSE_INFO_SEL_NONE, SC_POSE_INFO_SEL_MASK, SC_POSE_INFO_SEL_LABEL = 0, 1, 2
 SC_POSE_INFO_STATUS = 1
+
+
+class ScPolishPosesParams(C.Structure):
+    """Mirror of `sc_polish_poses_params` (include/saccot.h), 32 bytes: refits per pose at most (1 .. 64), which correspondences of
+    the frame take part (SC_POLISH_POSES_SEL_*), the label of pose 0 (SEL_LABEL / SEL_ALIVE), SC_POLISH_POSES_STATUS or 0."""
+    _fields_ = [("size", C.c_uint32), ("max_iter", C.c_uint32), ("sel_mode", C.c_uint32), ("label0", C.c_int32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32 * 3)]
+
+
+SC_POLISH_POSES_MAX = 1024
+SC_POLISH_POSES_SEL_NONE, SC_POLISH_POSES_SEL_MASK, SC_POLISH_POSES_SEL_LABEL, SC_POLISH_POSES_SEL_ALIVE = 0, 1, 2, 3
+SC_POLISH_POSES_STATUS = 1
 SC_MATCH_BATCH_MAX_N = 4096  # rows a side of one problem of sc_match_batch
 SC_INSTANCES_BATCH_MAX = 16  # motions per problem of sc_register_instances_batch at most
 
@@ -271,6 +284,10 @@ def load_library() -> C.CDLL:
     L.sc_pose_info_default_params.argtypes = [ip]
     L.sc_pose_info_frame.argtypes = [vp, ip, vp, C.c_uint32, C.c_uint32, vp, vp]
     L.sc_pose_info_frame_device.argtypes = [vp, ip, vp, C.c_uint32, C.c_uint32, vp, vp]
+    zp = C.POINTER(ScPolishPosesParams)
+    L.sc_polish_poses_default_params.argtypes = [zp]
+    L.sc_polish_poses.argtypes = [vp, zp, vp, C.c_uint32, C.c_uint32, vp, vp, vp]
+    L.sc_polish_poses_device.argtypes = [vp, zp, vp, C.c_uint32, C.c_uint32, vp, vp, vp]
     L.sc_hypothesize_device.argtypes = [vp, vp, vp, C.c_int64, pp, vp, sp]
     L.sc_finalize_device.argtypes = [vp, vp, vp, vp, sp]
     L.sc_hypothesize_begin_device.argtypes = [vp, vp, vp, C.c_int64, pp, vp, sp]
@@ -316,6 +333,12 @@ def make_polish_params(candidates: int = 8, max_iter: int = 16, flags: int = 0) 
 def make_pose_info_params(sel_mode: int = SC_POSE_INFO_SEL_NONE, label0: int = 0, flags: int = 0) -> ScPoseInfoParams:
     """sc_pose_info_params: sel_mode SC_POSE_INFO_SEL_*, label0 (SEL_LABEL only), flags SC_POSE_INFO_STATUS or 0."""
     return ScPoseInfoParams(C.sizeof(ScPoseInfoParams), sel_mode, label0, flags)
+
+
+def make_polish_poses_params(max_iter: int = 16, sel_mode: int = SC_POLISH_POSES_SEL_NONE, label0: int = 0, flags: int = 0) -> ScPolishPosesParams:
+    """sc_polish_poses_params: max_iter 1 .. 64, sel_mode SC_POLISH_POSES_SEL_*, label0 (SEL_LABEL / SEL_ALIVE only), flags
+    SC_POLISH_POSES_STATUS or 0."""
+    return ScPolishPosesParams(C.sizeof(ScPolishPosesParams), max_iter, sel_mode, label0, flags)
 
 
 def shard_plan(params: ScParams, n: int) -> ScShardPlan:
@@ -950,6 +973,40 @@ class Registrar:
         """sc_pose_info_frame_device: pose records (pose_stride bytes each, read only), the selection (0: none) and the output
         records (320 bytes each) in HBM; enqueues on the context's stream and returns without waiting.  The frame stays."""
         self._check(self._lib.sc_pose_info_frame_device(self._h, C.byref(iparams), d_pose, pose_stride, n_poses, d_sel or None, d_info))
+
+    # ---- caller-supplied poses refitted on that frame (include/saccot.h, sc_polish_poses) -------------------------------------
+    def polish_poses(self, pose, pparams: ScPolishPosesParams | None = None, sel=None, want_mask: bool = True, **kw):
+        """sc_polish_poses: pose (K,) records of any dtype whose items start with float Rt[12] (and, with SC_POLISH_POSES_STATUS, an
+        int32 status behind it) — or a float32 array (K, 12) / (12,) —; sel None, (n,) uint8 (SEL_MASK) or (n,) int32 (SEL_LABEL,
+        SEL_ALIVE), read only -> (records (K,) of POLISH_BATCH_RESULT_DTYPE, masks (K, n) uint8 or None).  The frame stays.
+        kw: max_iter, sel_mode, label0, flags (make_polish_poses_params)."""
+        q = pparams or make_polish_poses_params(**kw)
+        pose = np.ascontiguousarray(pose)
+        if pose.dtype.fields is None:
+            pose = np.ascontiguousarray(pose, dtype=np.float32).reshape(-1, 12)
+            stride = 48
+        else:
+            pose = pose.reshape(-1)
+            stride = pose.dtype.itemsize
+        k = len(pose)
+        if sel is not None:
+            sel = np.ascontiguousarray(sel, dtype=np.uint8 if q.sel_mode == SC_POLISH_POSES_SEL_MASK else np.int32)
+            if sel.size != self._frame_n:
+                raise ValueError("polish_poses: sel holds one entry per correspondence of the frame")
+        pol = np.zeros(max(k, 1), POLISH_BATCH_RESULT_DTYPE)
+        mask = np.zeros((max(k, 1), max(self._frame_n, 1)), np.uint8) if want_mask else None
+        self._check(self._lib.sc_polish_poses(self._h, C.byref(q), pose.ctypes.data_as(C.c_void_p), stride, k,
+                                              None if sel is None else sel.ctypes.data_as(C.c_void_p), pol.ctypes.data_as(C.c_void_p),
+                                              None if mask is None else mask.ctypes.data_as(C.c_void_p)))
+        return pol[:k], (None if mask is None else mask[:k, :self._frame_n])
+
+    def polish_poses_device(self, pparams: ScPolishPosesParams, d_pose: int, pose_stride: int, n_poses: int, d_sel: int, d_pol: int,
+                            d_mask: int = 0):
+        """sc_polish_poses_device: pose records (pose_stride bytes each, read only), the selection (0: none), the output records (64
+        bytes each) and the masks (n_poses x n bytes; 0: none) in HBM; enqueues on the context's stream and returns without waiting.
+        The frame stays."""
+        self._check(self._lib.sc_polish_poses_device(self._h, C.byref(pparams), d_pose, pose_stride, n_poses, d_sel or None, d_pol,
+                                                     d_mask or None))
 
     def hypothesize_device(self, d_src: int, d_tgt: int, n: int, params: ScParams, d_key: int):
         st = ScStats(C.sizeof(ScStats))

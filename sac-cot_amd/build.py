@@ -11,7 +11,8 @@ LIB = os.path.join(HERE, "libsaccot.so")
 SOURCES = ["sc_compat.hip", "sc_tri.hip", "sc_score.hip", "sc_final.hip", "sc_sort.hip", "sc_capi.hip", "sc_capi_hooks.hip", "sc_capi_peel.hip", "sc_capi_match.hip", "sc_capi_polish.hip", "sc_multi.hip", "sc_peel.hip", "sc_match.hip",
            "sc_polish.hip", "sc_capi_batch.hip", "sc_batch.hip", "sc_capi_match_batch.hip", "sc_match_batch.hip",
            "sc_capi_polish_batch.hip", "sc_polish_batch.hip", "sc_capi_instances_batch.hip", "sc_capi_pairs.hip",
-           "sc_capi_info_batch.hip", "sc_info_batch.hip", "sc_capi_info_frame.hip", "sc_info_frame.hip"]
+           "sc_capi_info_batch.hip", "sc_info_batch.hip", "sc_capi_info_frame.hip", "sc_info_frame.hip",
+           "sc_capi_polish_poses.hip", "sc_polish_poses.hip"]
 HEADERS = ["sc_arith.hpp", "sc_block.hpp", "sc_kernels.hpp", "sc_gramref.hpp", "sc_refine.hpp", "sc_refit.hpp", "sc_batch_frame.hpp", "sc_info.hpp", "sc_winner.hpp", "sc_ctx.hpp", "sc_match_tile.hpp", "sc_match_batch_check.hpp", "sc_pairs_check.hpp", os.path.join("..", "..", "include", "saccot.h"),
            os.path.join("..", "..", "include", "saccot_debug.h")]
 # -ffp-contract=off: the canonical arithmetic (sc_arith.hpp) fuses only where it says fmaf.

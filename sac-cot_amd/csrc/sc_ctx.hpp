@@ -130,7 +130,11 @@ struct Workspace {
       // sc_pose_info_frame: allocated by the first such call, never by a frame or by another entry.  tmp: the chunk sums and bit
       // words, n_poses x pose_info_frame_scratch_bytes(n) — not polish_tmp: a polish may be enqueued behind the call —; the rest:
       // device copies of the host entry's arrays
-      pinfo_frame_tmp, pinfo_frame_pose, pinfo_frame_sel, pinfo_frame_out;
+      pinfo_frame_tmp, pinfo_frame_pose, pinfo_frame_sel, pinfo_frame_out,
+      // sc_polish_poses: allocated by the first such call, never by a frame or by another entry.  tmp: the chunk sums and bit words,
+      // n_poses x polish_poses_scratch_bytes(n) — not polish_tmp and not pinfo_frame_tmp: either call may be enqueued behind this
+      // one —; the rest: device copies of the host entry's arrays
+      ppose_tmp, ppose_pose, ppose_sel, ppose_out, ppose_mask;
 };
 constexpr size_t N_WORKSPACE_BUFS = sizeof(Workspace) / sizeof(Buf);
 static_assert(std::is_standard_layout<Workspace>::value && alignof(Workspace) == alignof(Buf) && sizeof(Workspace) == N_WORKSPACE_BUFS * sizeof(Buf),

@@ -851,6 +851,30 @@ size_t pose_info_frame_scratch_bytes(int n);
 // ONE launch, a workgroup of 1024 threads per pose; every record is written (complete in stream order).
 void launch_pose_info_frame(const PoseInfoFrameJob& job, hipStream_t st);
 
+// ---- caller-supplied poses refitted on a scored frame (sc_polish_poses; sc_polish_poses.hip) ----------------------
+// Pose k's record starts at byte k * pose_stride of `pose` — float Rt[12] at byte 0 and, if `status`, an int32 status at byte 48: read,
+// never written —, out[k] is the result, mask bytes [k * n, (k + 1) * n) its mask (mask == nullptr: none).  sel by sel_mode
+// (SC_POLISH_POSES_SEL_*): nullptr, n bytes, or n int32 compared with label0 and label0 + k.  thr: tau^2, 1 / tau^2 or 1 / tau by
+// score_mode.  scratch: n_poses * polish_poses_scratch_bytes(pts.n).  Everything in device memory.
+struct PolishPosesJob {
+  Points pts;  // the frame's staged planes, in the caller's indexing
+  float tau2, thr;
+  int score_mode;
+  uint32_t max_iter, n_poses;
+  const void* pose;
+  uint32_t pose_stride;
+  int status;
+  const void* sel;
+  uint32_t sel_mode;
+  int32_t label0;
+  double* scratch;
+  PolishBatchRecord* out;
+  uint8_t* mask;
+};
+size_t polish_poses_scratch_bytes(int n);
+// ONE launch, a workgroup of 1024 threads per pose; every record (and mask) is written (complete in stream order).
+void launch_polish_poses(const PolishPosesJob& job, hipStream_t st);
+
 // ---- descriptor matching for a batch of small problems (sc_match_batch; sc_match_batch.hip) -----------------
 // Problem b owns rows [src_off[b], src_off[b + 1]) of fsrc and [tgt_off[b], tgt_off[b + 1]) of ftgt (1 .. MATCH_BATCH_MAX_N rows
 // each, checked by the caller) and the output slot that starts at entry slot[b] = src_off[b] * knn.  tile_map: n_tiles pairs

@@ -14,6 +14,12 @@
 //   uint64_t& bits(int ch)                  chunk ch's 64 inlier bits
 //   void publish()                          before a barrier behind which other lanes read what this one stored: a block fence for
 //                                           global memory, nothing for LDS
+//
+// Which correspondences may be inliers at all is the caller's as well: a participation policy `Part` with
+//   bool operator()(int m) const            correspondence m (< n) takes part
+// ANDed into the inlier bit in the ballot loop and nowhere else: the chains see the bit words only.  The default, EveryIndex, admits
+// every index and folds away: polish_kernel and polish_batch_kernel compile to what they were without it
+// (profiles/polish_poses.txt); polish_poses_kernel (sc_polish_poses.hip) passes the selection of sc_polish_poses.
 #pragma once
 #include "../../include/saccot.h"
 #include "sc_arith.hpp"
@@ -29,9 +35,10 @@ enum : uint32_t { GO_FIXED = 0u, GO_CHANGED = 1u, GO_DECLINED = 2u };  // what t
 // done (_MAX_ITER).  Rt holds the last iterate when it returns, visible to every thread.  S[8], H[9], go: LDS words of the workgroup.
 // Called by all THREADS threads of the workgroup, uniformly.
 struct Refit { uint32_t iters, stop; };  // the refits that changed (R, t); why they stopped (SC_POLISH_STOP_*)
-template <int THREADS, class Chunks>
+struct EveryIndex { __device__ __forceinline__ bool operator()(int) const { return true; } };
+template <int THREADS, class Chunks, class Part = EveryIndex>
 __device__ __forceinline__ Refit refit_iterate(const float* __restrict__ planes, int ld, int n, float tau2, uint32_t max_iter, Chunks ck,
-                                               float* Rt, double* S, double* H, uint32_t* go) {
+                                               float* Rt, double* S, double* H, uint32_t* go, Part part = Part{}) {
   const int tid = threadIdx.x;
   const int nch = (n + 63) / 64;  // (9 nch fits an int whatever n)
   Refit res{0u, SC_POLISH_STOP_MAX_ITER};
@@ -45,8 +52,10 @@ __device__ __forceinline__ Refit refit_iterate(const float* __restrict__ planes,
     for (int ch = tid >> 6; ch < nch; ch += THREADS / 64) {
       const int m = ch * 64 + (tid & 63);
       bool inl = false;
-      if (m < n)
-        inl = fin && within_tau(M, load_corr(planes, ld, m), tau2);
+      if (m < n) {
+        const bool takes = part(m);  // (first: what it loads is in flight beside the correspondence's six)
+        inl = fin && within_tau(M, load_corr(planes, ld, m), tau2) && takes;
+      }
       const unsigned long long bal = __ballot(inl);
       if ((tid & 63) == 0) ck.bits(ch) = bal;
     }
