@@ -47,6 +47,7 @@ extern "C" {
 #define SC_HAS_POSE_INFO 1  /* this header declares sc_pose_info_batch* and sc_pose_info_pairs_slots_device (added within 0.10) */
 #define SC_HAS_POSE_INFO_FRAME 1  /* this header declares sc_pose_info_frame* and sc_pose_info_default_params (added within 0.10) */
 #define SC_HAS_POLISH_POSES 1  /* this header declares sc_polish_poses* (added within 0.10) */
+#define SC_HAS_ASSIGN 1  /* this header declares sc_assign_poses* and sc_assign_default_params (added within 0.10) */
 
 /* status codes */
 #define SC_OK        0
@@ -921,7 +922,7 @@ int sc_pose_info_frame(sc_ctx* ctx, const sc_pose_info_params* ip, const void* p
  * device copies (n_poses x n mask bytes among them when a mask is asked for); allocated by the first such call, counted in
  * workspace_bytes and held against the frame's cap (SC_ENOMEM, nothing enqueued, the frame stays).  A context that never calls these
  * entries allocates and runs nothing new.
- * Not here: a relabelled label output; a form for sharded frames; weights per correspondence; a batch form (sc_polish_batch takes
+ * Not here: a relabelled label output (sc_assign_poses_frame, below, writes it); a form for sharded frames; weights per correspondence; a batch form (sc_polish_batch takes
  * arbitrary poses already). */
 #define SC_POLISH_POSES_MAX        1024u
 #define SC_POLISH_POSES_SEL_NONE   0u  /* every correspondence takes part                                                    */
@@ -945,6 +946,100 @@ int sc_polish_poses_device(sc_ctx* ctx, const sc_polish_poses_params* qp, const 
 /* the same with host arrays (pose, sel, pol, mask); waits */
 int sc_polish_poses(sc_ctx* ctx, const sc_polish_poses_params* qp, const void* pose, uint32_t pose_stride, uint32_t n_poses,
                     const void* sel, sc_polish_batch_result* pol, uint8_t* mask);
+
+/* ---- correspondences labelled by the pose that fits best: sc_assign_poses ------------------------------------------
+ * The library refits a list of poses (sc_polish_poses, sc_polish_batch), weighs it (sc_pose_info_frame, sc_pose_info_batch) and
+ * restricts either to a label array (SEL_LABEL, SEL_ALIVE), but the only label array it produced was the greedy one of
+ * sc_register_instances*: motion k owns what motions 0 .. k-1 left inside tau of its UNREFINED pose.  Once the motions are polished
+ * that label is stale, and a pose a caller brings along has none.  These entries are the hard-assignment step of a multi-model fit:
+ * K pose records in, every correspondence labelled with one pose or -1, and per pose how many correspondences it got and what they
+ * score.  Two forms, where the poses multiply: on a scored frame (ONE kernel launch behind one memset, sc_assign_frame.hip) and on a
+ * packed batch (ONE launch, a workgroup per problem, sc_assign_batch.hip).  No host word in either.
+ *
+ * Definitions, shared by both forms.  Pose records are those of sc_pose_info_frame / sc_polish_poses: float Rt[12] at byte 0 —
+ * R = Rt[0 .. 8] row-major, t = Rt[9 .. 11] — and, where a status is read, an int32 at byte 48; read, never written; 4-byte aligned.
+ *   valid(k)    Rt is finite and, where a status is read, it is SC_OK.
+ *   d2_k(m)     the canonical fp32 squared residual of the masks' inlier test: e_c = t_c + fma(R_c2, pz, fma(R_c1, py, fma(R_c0, px,
+ *               -q_c))), d2 = fma(ez, ez, fma(ey, ey, ex * ex)).
+ *   part(m)     SC_ASSIGN_SEL_NONE: every m.  SC_ASSIGN_SEL_MASK: d_sel holds n bytes, m takes part iff d_sel[m] != 0.
+ *   cand(k, m)  valid(k) && part(m) && d2_k(m) < tau^2 — tau^2 derived as the masks derive it, a float '<': a NaN residual (a finite
+ *               pose with entries near FLT_MAX can produce one) is never a candidate.
+ *   mode        SC_ASSIGN_BEST: label[m] = the candidate k with the smallest d2_k(m), ties to the lowest k; -1 without a candidate.
+ *               SC_ASSIGN_FIRST: label[m] = the lowest candidate k, else -1 — the claim order of sc_peel: on the Rt array of
+ *               sc_register_instances run without SC_FLAG_REFINE it returns that call's label.
+ *   d2 output   optional (NULL): d2_label[m](m), or the bits 0x7F800000 (+inf) where the label is -1.
+ *   record k    sc_assign_result: count = #{m : label[m] == k}; score = the sum over those m of the frame's (params->) score_mode term
+ *               of pose k — in the inlier-count mode score == count —; status SC_OK for a valid pose; a status other than SC_OK at
+ *               byte 48 is passed through and a non-finite Rt gives SC_EINVAL, both with count = score = 0: an invalid pose claims
+ *               nothing, is found on the device and does not fail the call.  reserved is written 0.
+ *   Every output is a function of the points, the poses in their order, the selection, tau and score_mode, bit for bit: not of how the
+ *   frame was enqueued, of the context's history or of the launch geometry (the per-pose sums are sums of integers).
+ *
+ * The frame form.  A FRAME is as defined for sc_peel.  The entries read the frame's staged points, its n, tau and score_mode, change
+ * nothing in it and do NOT end it: they may be repeated and interleaved with sc_peel, sc_polish* and sc_pose_info_frame.  d_label:
+ * n int32 in the caller's ORIGINAL indexing; d_d2: n floats or NULL; d_asg: n_poses records.  SC_ASSIGN_STATUS: the record holds a
+ * status at byte 48; without it nothing past byte 47 is read.  pose_stride is a multiple of 4 and at least 48, at least 52 with the
+ * flag; 1 <= n_poses <= SC_ASSIGN_MAX_POSES.  The device form enqueues two stream operations whatever n and n_poses are — a memset of
+ * d_asg and the kernel — and returns without waiting; the host form copies in, enqueues, copies out and waits.
+ * Errors: the CALL returns SC_EINVAL, decided on the host before anything is enqueued, sc_last_error naming which: a NULL ctx (no
+ * text), ap, d_pose, d_label or d_asg; ap->size wrong; mode above 1; sel_mode above 1; d_sel NULL with SC_ASSIGN_SEL_MASK; an
+ * unknown flag or a non-zero reserved word; n_poses out of range; a pose_stride that breaks the rule; no frame on the context
+ * (sc_peel's refusal, with its text); a call outstanding on the context.  A refused call leaves the frame.
+ * Workspace: the device form needs none — the tallies are added into d_asg itself —; the host form's device copies are buffers of
+ * these entries' own, allocated by the first such call, counted in workspace_bytes and held against the frame's cap (SC_ENOMEM,
+ * nothing enqueued, the frame stays).  A context that never calls these entries allocates nothing new.
+ * The loop this closes, every step stream-ordered: sc_register_instances -> sc_polish_poses_device(SEL_ALIVE) ->
+ * sc_assign_poses_frame_device(BEST) -> sc_polish_poses_device(SEL_LABEL, max_iter = 1) -> sc_pose_info_frame_device(SEL_LABEL), so
+ * that no correspondence is counted in two edges' matrices.
+ *
+ * The batch form, packed only.  The problems of sc_register_batch (d_src, d_tgt, offset a HOST array, params->layout, 3 <= n_b <=
+ * SC_BATCH_MAX_N).  The poses motion-major, exactly as sc_register_instances_batch writes d_res: pose k of problem b starts at byte
+ * (k * n_problems + b) * pose_stride; the status at byte 48 is always read (pose_stride at least 52; SC_ASSIGN_STATUS may be set or
+ * not); 1 <= n_poses <= SC_ASSIGN_BATCH_MAX_POSES; sel_mode must be SC_ASSIGN_SEL_NONE.  d_label: total int32 positioned like
+ * sc_register_batch's mask, every entry of a problem's range written; d_asg: n_poses x n_problems records, motion-major.  params is
+ * checked as sc_register_batch checks it; only tau, score_mode and layout are read.  A problem holding a non-finite coordinate gets
+ * label -1 throughout and SC_EINVAL in every one of its records; its neighbours are untouched.  A problem's outputs do not depend on
+ * its position in the batch or on n_problems.  Like every batch entry it ends the frame a context may hold.  Refusals, workspace
+ * (the copy of the offsets, the host form's device copies) and the offset staging wait are sc_pose_info_batch_device's.
+ * Not here: slots and pairs forms; soft or weighted assignment; a fused "relabel and refit until stable" entry — the caller composes
+ * it from the stream-ordered calls above —; a form for sharded frames, which leave no frame. */
+#define SC_ASSIGN_MAX_POSES       1024u
+#define SC_ASSIGN_BATCH_MAX_POSES 64u
+#define SC_ASSIGN_BEST     0u   /* mode: the candidate with the smallest residual, ties to the lowest k */
+#define SC_ASSIGN_FIRST    1u   /* mode: the lowest candidate k (sc_peel's claim order)                 */
+#define SC_ASSIGN_SEL_NONE 0u   /* every correspondence takes part                                      */
+#define SC_ASSIGN_SEL_MASK 1u   /* sel: n bytes; m takes part iff sel[m] != 0                           */
+#define SC_ASSIGN_STATUS   1u   /* flags: a pose record holds an int32 status at byte 48                */
+typedef struct sc_assign_params {   /* 32 bytes */
+  uint32_t size;         /* = sizeof(sc_assign_params)  */
+  uint32_t mode;         /* SC_ASSIGN_BEST / _FIRST     */
+  uint32_t sel_mode;     /* SC_ASSIGN_SEL_*             */
+  uint32_t flags;        /* SC_ASSIGN_STATUS or 0       */
+  uint32_t reserved[4];  /* must be 0                   */
+} sc_assign_params;
+typedef struct sc_assign_result {   /* 32 bytes */
+  int32_t  status;       /* SC_OK, the status passed through, or SC_EINVAL   */
+  uint32_t count;        /* correspondences labelled with this pose          */
+  uint64_t score;        /* their score terms, summed (score_mode)           */
+  uint32_t reserved[4];  /* written as 0                                     */
+} sc_assign_result;
+int sc_assign_default_params(sc_assign_params* ap);   /* size set, everything else 0 */
+/* d_pose: n_poses records of pose_stride bytes; d_sel per sel_mode (NULL with SEL_NONE); d_label: n int32; d_d2: n floats or NULL;
+ * d_asg: n_poses records */
+int sc_assign_poses_frame_device(sc_ctx* ctx, const sc_assign_params* ap, const void* d_pose, uint32_t pose_stride, uint32_t n_poses,
+                                 const uint8_t* d_sel, int32_t* d_label, float* d_d2, sc_assign_result* d_asg);
+/* the same with host arrays (pose, sel, label, d2, asg); waits */
+int sc_assign_poses_frame(sc_ctx* ctx, const sc_assign_params* ap, const void* pose, uint32_t pose_stride, uint32_t n_poses,
+                          const uint8_t* sel, int32_t* label, float* d2, sc_assign_result* asg);
+/* every buffer but offset in HBM: d_src / d_tgt total x 3 floats, d_pose n_poses x n_problems records of pose_stride bytes
+ * (motion-major), d_label total int32, d_asg n_poses x n_problems records (motion-major) */
+int sc_assign_poses_batch_device(sc_ctx* ctx, const float* d_src, const float* d_tgt, const uint32_t* offset, uint32_t n_problems,
+                                 const sc_params* params, const sc_assign_params* ap, const void* d_pose, uint32_t pose_stride,
+                                 uint32_t n_poses, int32_t* d_label, sc_assign_result* d_asg);
+/* the same with host arrays; waits */
+int sc_assign_poses_batch(sc_ctx* ctx, const float* src, const float* tgt, const uint32_t* offset, uint32_t n_problems,
+                          const sc_params* params, const sc_assign_params* ap, const void* pose, uint32_t pose_stride,
+                          uint32_t n_poses, int32_t* label, sc_assign_result* asg);
 
 /* ---- two-phase form for one-process-per-GPU sharding --------------------------------
  * Phase 1: A and B replicated, C1+C2 on this rank's blocks of the top-T list; writes this rank's winner key

@@ -49,6 +49,8 @@ EXPORTS = ["sc_version", "sc_strerror", "sc_default_params", "sc_create", "sc_de
            "sc_pose_info_batch", "sc_pose_info_batch_device", "sc_pose_info_batch_slots_device", "sc_pose_info_pairs_slots_device",
            "sc_pose_info_default_params", "sc_pose_info_frame", "sc_pose_info_frame_device",
            "sc_polish_poses_default_params", "sc_polish_poses", "sc_polish_poses_device",
+           "sc_assign_default_params", "sc_assign_poses_frame", "sc_assign_poses_frame_device", "sc_assign_poses_batch",
+           "sc_assign_poses_batch_device",
            "sc_hypothesize_device", "sc_finalize_device",
            "sc_hypothesize_begin_device", "sc_hypothesize_end_device", "sc_finalize_gathered_device", "sc_finalize_gathered_device_async",
            "sc_shard_plan_query", "sc_shard_compat_device", "sc_shard_edges_device", "sc_shard_select_device",
@@ -156,6 +158,25 @@ class ScPolishPosesParams(C.Structure):
 SC_POLISH_POSES_MAX = 1024
 SC_POLISH_POSES_SEL_NONE, SC_POLISH_POSES_SEL_MASK, SC_POLISH_POSES_SEL_LABEL, SC_POLISH_POSES_SEL_ALIVE = 0, 1, 2, 3
 SC_POLISH_POSES_STATUS = 1
+
+
+class ScAssignParams(C.Structure):
+    """Mirror of `sc_assign_params` (include/saccot.h), 32 bytes: SC_ASSIGN_BEST / _FIRST, which correspondences take part
+    (SC_ASSIGN_SEL_*), SC_ASSIGN_STATUS or 0."""
+    _fields_ = [("size", C.c_uint32), ("mode", C.c_uint32), ("sel_mode", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 4)]
+
+
+class ScAssignResult(C.Structure):
+    """Mirror of `sc_assign_result` (include/saccot.h), 32 bytes: one pose's record of sc_assign_poses."""
+    _fields_ = [("status", C.c_int32), ("count", C.c_uint32), ("score", C.c_uint64), ("reserved", C.c_uint32 * 4)]
+
+
+ASSIGN_RESULT_DTYPE = np.dtype([("status", np.int32), ("count", np.uint32), ("score", np.uint64),
+                                ("reserved", np.uint32, 4)])  # sc_assign_result as a numpy record
+SC_ASSIGN_MAX_POSES, SC_ASSIGN_BATCH_MAX_POSES = 1024, 64
+SC_ASSIGN_BEST, SC_ASSIGN_FIRST = 0, 1
+SC_ASSIGN_SEL_NONE, SC_ASSIGN_SEL_MASK = 0, 1
+SC_ASSIGN_STATUS = 1
 SC_MATCH_BATCH_MAX_N = 4096  # rows a side of one problem of sc_match_batch
 SC_INSTANCES_BATCH_MAX = 16  # motions per problem of sc_register_instances_batch at most
 
@@ -288,6 +309,12 @@ def load_library() -> C.CDLL:
     L.sc_polish_poses_default_params.argtypes = [zp]
     L.sc_polish_poses.argtypes = [vp, zp, vp, C.c_uint32, C.c_uint32, vp, vp, vp]
     L.sc_polish_poses_device.argtypes = [vp, zp, vp, C.c_uint32, C.c_uint32, vp, vp, vp]
+    ap = C.POINTER(ScAssignParams)
+    L.sc_assign_default_params.argtypes = [ap]
+    L.sc_assign_poses_frame.argtypes = [vp, ap, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
+    L.sc_assign_poses_frame_device.argtypes = [vp, ap, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
+    L.sc_assign_poses_batch.argtypes = [vp, f32p, f32p, u32p, C.c_uint32, pp, ap, vp, C.c_uint32, C.c_uint32, vp, vp]
+    L.sc_assign_poses_batch_device.argtypes = [vp, vp, vp, u32p, C.c_uint32, pp, ap, vp, C.c_uint32, C.c_uint32, vp, vp]
     L.sc_hypothesize_device.argtypes = [vp, vp, vp, C.c_int64, pp, vp, sp]
     L.sc_finalize_device.argtypes = [vp, vp, vp, vp, sp]
     L.sc_hypothesize_begin_device.argtypes = [vp, vp, vp, C.c_int64, pp, vp, sp]
@@ -339,6 +366,11 @@ def make_polish_poses_params(max_iter: int = 16, sel_mode: int = SC_POLISH_POSES
     """sc_polish_poses_params: max_iter 1 .. 64, sel_mode SC_POLISH_POSES_SEL_*, label0 (SEL_LABEL / SEL_ALIVE only), flags
     SC_POLISH_POSES_STATUS or 0."""
     return ScPolishPosesParams(C.sizeof(ScPolishPosesParams), max_iter, sel_mode, label0, flags)
+
+
+def make_assign_params(mode: int = SC_ASSIGN_BEST, sel_mode: int = SC_ASSIGN_SEL_NONE, flags: int = 0) -> ScAssignParams:
+    """sc_assign_params: mode SC_ASSIGN_BEST / _FIRST, sel_mode SC_ASSIGN_SEL_*, flags SC_ASSIGN_STATUS or 0."""
+    return ScAssignParams(C.sizeof(ScAssignParams), mode, sel_mode, flags)
 
 
 def shard_plan(params: ScParams, n: int) -> ScShardPlan:
@@ -1007,6 +1039,71 @@ class Registrar:
         The frame stays."""
         self._check(self._lib.sc_polish_poses_device(self._h, C.byref(pparams), d_pose, pose_stride, n_poses, d_sel or None, d_pol,
                                                      d_mask or None))
+
+    # ---- correspondences labelled by the pose that fits best (include/saccot.h, sc_assign_poses) ---------------------------------
+    def assign_poses_frame(self, pose, aparams: ScAssignParams | None = None, sel=None, want_d2: bool = True, **kw):
+        """sc_assign_poses_frame: pose (K,) records of any dtype whose items start with float Rt[12] (and, with SC_ASSIGN_STATUS, an
+        int32 status behind it) — or a float32 array (K, 12) / (12,) —; sel None or (n,) uint8 (SC_ASSIGN_SEL_MASK), read only ->
+        (label (n,) int32, d2 (n,) float32 or None, records (K,) of ASSIGN_RESULT_DTYPE).  The frame stays.
+        kw: mode, sel_mode, flags (make_assign_params)."""
+        q = aparams or make_assign_params(**kw)
+        pose = np.ascontiguousarray(pose)
+        if pose.dtype.fields is None:
+            pose = np.ascontiguousarray(pose, dtype=np.float32).reshape(-1, 12)
+            stride = 48
+        else:
+            pose = pose.reshape(-1)
+            stride = pose.dtype.itemsize
+        k, n = len(pose), self._frame_n
+        if sel is not None:
+            sel = np.ascontiguousarray(sel, dtype=np.uint8)
+            if sel.size != n:
+                raise ValueError("assign_poses_frame: sel holds one entry per correspondence of the frame")
+        label = np.zeros(max(n, 1), np.int32)
+        d2 = np.zeros(max(n, 1), np.float32) if want_d2 else None
+        asg = np.zeros(max(k, 1), ASSIGN_RESULT_DTYPE)
+        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        self._check(self._lib.sc_assign_poses_frame(self._h, C.byref(q), vp(pose), stride, k, vp(sel), vp(label), vp(d2), vp(asg)))
+        return label[:n], (None if d2 is None else d2[:n]), asg[:k]
+
+    def assign_poses_frame_device(self, aparams: ScAssignParams, d_pose: int, pose_stride: int, n_poses: int, d_sel: int, d_label: int,
+                                  d_d2: int, d_asg: int):
+        """sc_assign_poses_frame_device: pose records (pose_stride bytes each, read only), the selection (0: none), the labels (n
+        int32), the residuals (n floats; 0: none) and the records (32 bytes each) in HBM; enqueues on the context's stream and returns
+        without waiting.  The frame stays."""
+        self._check(self._lib.sc_assign_poses_frame_device(self._h, C.byref(aparams), d_pose, pose_stride, n_poses, d_sel or None, d_label,
+                                                           d_d2 or None, d_asg))
+
+    def assign_poses_batch(self, src, tgt, offset, params: ScParams, pose, aparams: ScAssignParams | None = None, **kw):
+        """sc_assign_poses_batch on packed arrays: src / tgt / offset as register_batch_raw's; pose (K, B) records, motion-major, of any
+        dtype whose items start with float Rt[12] and int32 status — register_instances_batch_raw's records — read only ->
+        (label (total,) int32, records (K, B) of ASSIGN_RESULT_DTYPE).  kw: mode, flags (make_assign_params)."""
+        q = aparams or make_assign_params(**kw)
+        src, tgt = _f32c(src), _f32c(tgt)
+        offset = np.ascontiguousarray(offset, dtype=np.uint32)
+        pose = np.ascontiguousarray(pose)
+        nb = max(len(offset) - 1, 0)
+        total = int(offset[-1]) if len(offset) else 0
+        if pose.ndim != 2 or pose.shape[1] != nb:
+            raise ValueError("assign_poses_batch: pose holds (n_poses, n_problems) records")
+        k = pose.shape[0]
+        label = np.zeros(max(total, 1), np.int32)
+        asg = np.zeros((max(k, 1), max(nb, 1)), ASSIGN_RESULT_DTYPE)
+        self._frame_n = 0
+        self._check(self._lib.sc_assign_poses_batch(self._h, _p(src, C.c_float), _p(tgt, C.c_float), _p(offset, C.c_uint32), nb,
+                                                    C.byref(params), C.byref(q), pose.ctypes.data_as(C.c_void_p), pose.dtype.itemsize, k,
+                                                    label.ctypes.data_as(C.c_void_p), asg.ctypes.data_as(C.c_void_p)))
+        return label[:total], asg[:k, :nb]
+
+    def assign_poses_batch_device(self, d_src: int, d_tgt: int, offset, params: ScParams, aparams: ScAssignParams, d_pose: int,
+                                  pose_stride: int, n_poses: int, d_label: int, d_asg: int):
+        """sc_assign_poses_batch_device: points, pose records (n_poses x B of pose_stride bytes, motion-major, read only), labels
+        (total int32) and records (n_poses x B of 32 bytes, motion-major) in HBM, offset a HOST array (B + 1,) uint32; enqueues on the
+        context's stream and returns without waiting."""
+        offset = np.ascontiguousarray(offset, dtype=np.uint32)
+        self._frame_n = 0
+        self._check(self._lib.sc_assign_poses_batch_device(self._h, d_src, d_tgt, _p(offset, C.c_uint32), max(len(offset) - 1, 0),
+                                                           C.byref(params), C.byref(aparams), d_pose, pose_stride, n_poses, d_label, d_asg))
 
     def hypothesize_device(self, d_src: int, d_tgt: int, n: int, params: ScParams, d_key: int):
         st = ScStats(C.sizeof(ScStats))

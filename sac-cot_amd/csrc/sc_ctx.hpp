@@ -134,7 +134,11 @@ struct Workspace {
       // sc_polish_poses: allocated by the first such call, never by a frame or by another entry.  tmp: the chunk sums and bit words,
       // n_poses x polish_poses_scratch_bytes(n) — not polish_tmp and not pinfo_frame_tmp: either call may be enqueued behind this
       // one —; the rest: device copies of the host entry's arrays
-      ppose_tmp, ppose_pose, ppose_sel, ppose_out, ppose_mask;
+      ppose_tmp, ppose_pose, ppose_sel, ppose_out, ppose_mask,
+      // sc_assign_poses: allocated by the first such call, never by a frame or by another entry.  The frame form's device entry needs
+      // none of them (the tallies are added into the caller's records).  off: the batch form's copy of the caller's offsets; the
+      // rest: device copies of the host entries' arrays (src / tgt: the batch form's points)
+      asg_off, asg_src, asg_tgt, asg_pose, asg_sel, asg_label, asg_d2, asg_out;
 };
 constexpr size_t N_WORKSPACE_BUFS = sizeof(Workspace) / sizeof(Buf);
 static_assert(std::is_standard_layout<Workspace>::value && alignof(Workspace) == alignof(Buf) && sizeof(Workspace) == N_WORKSPACE_BUFS * sizeof(Buf),

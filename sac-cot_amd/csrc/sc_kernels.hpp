@@ -875,6 +875,52 @@ size_t polish_poses_scratch_bytes(int n);
 // ONE launch, a workgroup of 1024 threads per pose; every record (and mask) is written (complete in stream order).
 void launch_polish_poses(const PolishPosesJob& job, hipStream_t st);
 
+// ---- correspondences labelled by the pose that fits best (sc_assign_poses; sc_assign_frame.hip, sc_assign_batch.hip) ----------
+// One pose's result: sc_assign_result of include/saccot.h, field for field (sc_assign_frame.hip asserts the size and the offsets).
+struct AssignRecord {
+  int32_t status;
+  uint32_t count;
+  uint64_t score;
+  uint32_t reserved[4];
+};
+// The frame form.  Pose k's record starts at byte k * pose_stride of `pose` — float Rt[12] at byte 0 and, if `status`, an int32 status
+// at byte 48: read, never written.  sel: nullptr or n bytes.  label: n int32; d2: n floats or nullptr.  out: n_poses records, ZERO at
+// launch (the workgroups add their tallies into count and score; workgroup 0 stores the status words).  thr: tau^2, 1 / tau^2 or
+// 1 / tau by score_mode.  Everything in device memory.
+struct AssignFrameJob {
+  Points pts;  // the frame's staged planes, in the caller's indexing
+  float tau2, thr;
+  int score_mode;
+  uint32_t mode, n_poses;
+  const void* pose;
+  uint32_t pose_stride;
+  int status;
+  const uint8_t* sel;
+  int32_t* label;
+  float* d2;
+  AssignRecord* out;
+};
+// bytes of dynamic LDS of a launch: a pose's twelve floats and its two tally words
+inline size_t assign_frame_lds_bytes(uint32_t n_poses) { return (size_t)n_poses * (48 + 8); }
+// ONE launch, a workgroup per tile of ASSIGN_TILE correspondences (sc_assign.hpp); every label (and d2) is written.
+void launch_assign_frame(const AssignFrameJob& job, hipStream_t st);
+// The batch form.  Problem b owns rows [offset[b], offset[b + 1]) of src / tgt and of label, as in BatchJob; pose k of problem b starts
+// at byte (k * n_problems + b) * pose_stride — Rt at byte 0, the status at byte 48 always read —, out[k * n_problems + b] is its record.
+struct AssignBatchJob {
+  const float* src; const float* tgt;
+  const uint32_t* offset;
+  uint32_t n_problems, total;
+  int soa, score_mode;
+  float tau2, thr;
+  uint32_t mode, n_poses;
+  const void* pose;
+  uint32_t pose_stride;
+  int32_t* label;
+  AssignRecord* out;
+};
+// ONE launch, a workgroup per problem; every label of a problem's range and every record is written (complete in stream order).
+void launch_assign_batch(const AssignBatchJob& job, hipStream_t st);
+
 // ---- descriptor matching for a batch of small problems (sc_match_batch; sc_match_batch.hip) -----------------
 // Problem b owns rows [src_off[b], src_off[b + 1]) of fsrc and [tgt_off[b], tgt_off[b + 1]) of ftgt (1 .. MATCH_BATCH_MAX_N rows
 // each, checked by the caller) and the output slot that starts at entry slot[b] = src_off[b] * knn.  tile_map: n_tiles pairs
