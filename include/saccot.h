@@ -34,7 +34,7 @@ extern "C" {
 #endif
 
 #define SC_VERSION_MAJOR 0
-#define SC_VERSION_MINOR 10  /* 0.10 + SC_HAS_POLISH: sc_polish / sc_polish_device / sc_polish_default_params (refits iterated to a fixed point on a scored frame; the minor number stays, callers detect the entries by symbol or by SC_HAS_POLISH).  0.10: sc_match / sc_match_device / sc_register_features (descriptor matching on the GPU, feeding the registration).  0.9: sc_peel / sc_peel_device / sc_register_instances (further rigid motions from a scored frame).  0.8: sc_debug_info grew cumulative counters of how a context's frames ran (saccot_debug.h); every entry refuses a context with an outstanding call; a host-free enqueue that does not fit the workspace cap runs the waited way.  0.7: sc_finalize_gathered_device_async (+ sc_wait), sc_hypothesize_device with SC_FLAG_EST_BOUND host-free on a repeated shape.  0.6: SC_FLAG_EST_BOUND also on sc_hypothesize_device (SC_EBOUND from the finalize call); SC_FLAG_SHARD_AB (sc_register_multi replicates stages A and B on small graphs unless told otherwise); sc_debug / sc_debug_info grew (the Gram filter's frame and cut: saccot_debug.h).  0.5: sc_register_device_async / sc_wait (host-free enqueue), SC_FLAG_EST_BOUND / SC_EBOUND (sharded stage B pruned by an estimated bound), sc_stats.bytes_moved, the debug hooks moved to
+#define SC_VERSION_MINOR 10  /* 0.10, lanes: a directly enqueued host-free sc_register_device_async frame on a caller's stream runs on a private lane of its context, ordered after that stream at the call and before it at sc_wait (below; no entry or struct of this header changed; saccot_debug.h: sc_debug.no_lane took the struct's tail padding, sc_debug_info.reserved2 became `lane`, sc_debug_info grew n_lane).  0.10 + SC_HAS_POLISH: sc_polish / sc_polish_device / sc_polish_default_params (refits iterated to a fixed point on a scored frame; the minor number stays, callers detect the entries by symbol or by SC_HAS_POLISH).  0.10: sc_match / sc_match_device / sc_register_features (descriptor matching on the GPU, feeding the registration).  0.9: sc_peel / sc_peel_device / sc_register_instances (further rigid motions from a scored frame).  0.8: sc_debug_info grew cumulative counters of how a context's frames ran (saccot_debug.h); every entry refuses a context with an outstanding call; a host-free enqueue that does not fit the workspace cap runs the waited way.  0.7: sc_finalize_gathered_device_async (+ sc_wait), sc_hypothesize_device with SC_FLAG_EST_BOUND host-free on a repeated shape.  0.6: SC_FLAG_EST_BOUND also on sc_hypothesize_device (SC_EBOUND from the finalize call); SC_FLAG_SHARD_AB (sc_register_multi replicates stages A and B on small graphs unless told otherwise); sc_debug / sc_debug_info grew (the Gram filter's frame and cut: saccot_debug.h).  0.5: sc_register_device_async / sc_wait (host-free enqueue), SC_FLAG_EST_BOUND / SC_EBOUND (sharded stage B pruned by an estimated bound), sc_stats.bytes_moved, the debug hooks moved to
                                 saccot_debug.h; 0.4: sc_debug_last / sc_debug_info, sc_debug.filter_blind; 0.3: sc_set_debug (no environment variables), SC_FLAG_NO_DENSE_S, sc_shard_* (stages A and B sharded); 0.2: SC_FLAG_TIMING_HOT,
                                 SC_STREAM_DEFAULT, sc_hypothesize_begin/end_device, sc_finalize_gathered_device */
 
@@ -199,7 +199,13 @@ int         sc_set_stream(sc_ctx* ctx, void* hip_stream); /* enqueue on a caller
                                                  restores the private stream, which is NON-blocking: nothing
                                                  orders it against other streams.  The device's default
                                                  (null) stream has no handle of its own: pass
-                                                 SC_STREAM_DEFAULT for it (torch reports it as 0)        */
+                                                 SC_STREAM_DEFAULT for it (torch reports it as 0).
+                                                 One kind of call is ordered with that stream at its two
+                                                 ends only, not inside it: a frame of a direct
+                                                 sc_register_device_async call (below) follows everything
+                                                 enqueued on the stream before the call, precedes everything
+                                                 enqueued after its sc_wait, and may run CONCURRENTLY with
+                                                 what the caller enqueues there in between                */
 #define SC_STREAM_DEFAULT ((void*)1)
 const char* sc_last_error(const sc_ctx* ctx);          /* last HIP error text seen by this context    */
 
@@ -223,9 +229,15 @@ int sc_register_device(sc_ctx* ctx, const float* d_src, const float* d_tgt, int6
  * whole path on the context's stream and returns without waiting for the GPU; sc_wait delivers the status and the
  * statistics of that call (and is where the host first looks at anything the GPU produced).  Between the two the host
  * is free — e.g. to enqueue the next frame on a SECOND context bound to the same stream (sc_set_stream): the GPU then
- * runs the frames back to back and never waits for the host.  At most ONE call may be outstanding per context
+ * never waits for the host, and the two frames OVERLAP on it.  At most ONE call may be outstanding per context
  * (SC_EINVAL otherwise); d_src / d_tgt must stay valid and unchanged until sc_wait returns, d_Rt / d_mask are complete
  * when it does (as for sc_register_device).
+ * Ordering on a caller's stream (sc_set_stream): the frame is ordered AFTER everything enqueued on that stream before
+ * sc_register_device_async was called (the producers of d_src / d_tgt, earlier readers of d_Rt / d_mask) and BEFORE everything
+ * enqueued on it after sc_wait has returned (copies of d_mask, sc_peel / sc_polish*, the next frame).  Between the two calls
+ * its kernels do not sit in that stream: a host-free frame (below) runs on a private lane of the context beside it, and may run
+ * concurrently with whatever the caller enqueues on the stream in that window — which therefore must not touch the four
+ * buffers, as the rule above already says.  Work on the stream that has to FOLLOW the frame is enqueued after sc_wait.
  * How it can return early: a call whose shape (n, parameters) equals the previous call's on this context is enqueued
  * "host-free" — its launches are sized by what the previous call needed (plus slack) and read the two data-dependent
  * counts of stage B (edges, triangles of the pruned graph) from device memory instead of from the host.  sc_wait

@@ -50,6 +50,7 @@ typedef struct sc_debug {
   uint32_t gram_kappa_q4;     /* the Gram filter's cut: a hypothesis counts as NEAR the call's reference frame while its reach stays under (value / 16) x tau; 0 = 8 tau (default), 1 = practically no cut (every workgroup walks every correspondence) */
   uint32_t gram_ref_late;     /* 1: the Gram filter's reference frame is voted after the selection, in a launch of its own (what every path but sc_register / sc_register_device does anyway), instead of by an extra workgroup of stage B's counting pass among the estimating sample's best triangles */
   uint32_t gram_guard_fail;   /* 1: the run-time probe of the matrix pipe's accumulation model reports a violation (tests: the Gram filter must then never be chosen) */
+  uint32_t no_lane;           /* 1: a host-free sc_register_device_async frame on a caller's stream is enqueued on that stream (serial with everything else on it) instead of on the context's lane beside it (saccot.h, sc_set_stream); took the struct's tail padding: sizeof(sc_debug) did not change */
 #ifdef SC_ABLATIONS           /* lab builds only (sac-cot_amd/build.py --ablations): NOT in the product's struct */
   uint32_t filter_variant;    /* body of the filter kernel: 1 .. 3 = bit-identical scheduling variants; >= 16 = timing-only ablations that return WRONG counts */
   uint32_t lab_pad_;
@@ -69,7 +70,7 @@ typedef struct sc_debug_info {
   uint32_t gram_guard;        /* run-time probe of the matrix pipe's accumulation arithmetic (once per context, before the first call that could choose the Gram filter): 0 = not run yet, 1 = the model the Gram bound assumes holds, 2 = violated: the Gram filter is disabled for this context */
   uint32_t prune_bound;       /* stage B's pruning bound in the last call: 0 = certified by the sample (or no pruning), 1 = estimated from a 1-in-64 sample of the triangles and verified by the select, 2 = estimated, found too high by the select, call repeated with a certifying sample */
   float    gram_guard_worst;  /* largest |hardware - exact| / largest term the probe saw, in units of 2^-24 (the bound assumes 18.5) */
-  uint32_t reserved2;
+  uint32_t lane;              /* 1: the last call's frame ran on the context's lane (a direct, host-free sc_register_device_async call on a caller's stream) */
   /* the Gram filter's cut in the last call (c2_kernel == 2): of `gram_rows` coefficient rows (hypotheses of this rank, padded to 256)
    * `gram_near_hyp` are near the reference frame and look only at the `gram_near_corr` correspondences near it */
   uint32_t gram_near_corr, gram_near_hyp, gram_rows;
@@ -85,6 +86,7 @@ typedef struct sc_debug_info {
   uint64_t n_est_fail;        /* ... whose estimate was too high: repeated with a certifying sample (prune_bound 2)          */
   uint64_t cover_edges, cover_triangles;  /* what the LAST call's launches covered if it was enqueued host-free (0: it waited)  */
   uint64_t n_hostfree_grow;   /* buffers re-allocated inside host-free enqueues (each synchronises the stream: a stall in a stream of frames)  */
+  uint64_t n_lane;            /* frames that ran on the context's lane (`lane`)                                              */
 } sc_debug_info;
 int         sc_debug_last(sc_ctx* ctx, sc_debug_info* out);
 

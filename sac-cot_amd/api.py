@@ -200,7 +200,7 @@ class ScDebug(C.Structure):
                 ("no_estimate", C.c_uint32), ("est_margin_pct", C.c_uint32), ("no_fast", C.c_uint32),
                 ("score_filter", C.c_uint32), ("filter_splits", C.c_uint32), ("filter_queue_cap", C.c_uint32),
                 ("filter_lds_queue", C.c_uint32), ("filter_blind", C.c_uint32), ("gram_kappa_q4", C.c_uint32),
-                ("gram_ref_late", C.c_uint32), ("gram_guard_fail", C.c_uint32)]
+                ("gram_ref_late", C.c_uint32), ("gram_guard_fail", C.c_uint32), ("no_lane", C.c_uint32)]
     _ALIASES = {"cnt_blocks": ("grid_blocks", 0), "keys_blocks": ("grid_blocks", 1), "sel_blocks": ("grid_blocks", 2),
                 "sample_blocks": ("grid_blocks", 3), "tg_count": ("lanes_per_edge", 0), "tg_keys": ("lanes_per_edge", 1),
                 "tg_sample": ("lanes_per_edge", 2), "tg_events": ("lanes_per_edge", 3)}
@@ -214,15 +214,16 @@ class ScDebugLab(C.Structure):
 
 class ScDebugInfo(C.Structure):
     """Mirror of `sc_debug_info` (include/saccot_debug.h): which C2 kernel the last call ran, the filter's hand-overs,
-    how the call was enqueued (fast_path: 0 waited, 1 host-free, 2 host-free then repeated), the matrix-pipe probe."""
+    how the call was enqueued (fast_path: 0 waited, 1 host-free, 2 host-free then repeated; lane: 1 = on the context's lane beside
+    the caller's stream, n_lane: such frames so far), the matrix-pipe probe."""
     _fields_ = [("size", C.c_uint32), ("c2_kernel", C.c_uint32), ("filter_undecided", C.c_uint64),
                 ("filter_recounts", C.c_uint64), ("filter_splits", C.c_uint32), ("fast_path", C.c_uint32),
                 ("gram_guard", C.c_uint32), ("prune_bound", C.c_uint32), ("gram_guard_worst", C.c_float),
-                ("reserved2", C.c_uint32), ("gram_near_corr", C.c_uint32), ("gram_near_hyp", C.c_uint32),
+                ("lane", C.c_uint32), ("gram_near_corr", C.c_uint32), ("gram_near_hyp", C.c_uint32),
                 ("gram_rows", C.c_uint32), ("gram_ref", C.c_uint32), ("gram_ref_votes_q8", C.c_uint32),
                 ("us_c2_filter", C.c_float),
                 ("n_frames", C.c_uint64), ("n_fast_ok", C.c_uint64), ("n_fast_repeat", C.c_uint64),
-                ("n_est_ok", C.c_uint64), ("n_est_fail", C.c_uint64), ("cover_edges", C.c_uint64), ("cover_triangles", C.c_uint64), ("n_hostfree_grow", C.c_uint64)]
+                ("n_est_ok", C.c_uint64), ("n_est_fail", C.c_uint64), ("cover_edges", C.c_uint64), ("cover_triangles", C.c_uint64), ("n_hostfree_grow", C.c_uint64), ("n_lane", C.c_uint64)]
 
 
 class SacCotError(RuntimeError):

@@ -839,6 +839,10 @@ int sc_create(int device, sc_ctx** out) {
   c->stream = c->own_stream;
   for (int i = 0; i < N_EVENTS; i++)
     if (hipEventCreateWithFlags(&c->ev[i], hipEventDisableSystemFence) != hipSuccess) { sc_destroy(c); return SC_EHIP; }
+  // the lane's fork and join (sc_ctx.hpp): no timestamps; the default fence of a record stays (the join orders a frame's outputs
+  // in front of whatever the caller's stream does with them)
+  if (hipEventCreateWithFlags(&c->lane_fork, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&c->lane_join, hipEventDisableTiming) != hipSuccess) { sc_destroy(c); return SC_EHIP; }
   if (hipHostMalloc((void**)&c->pinned, N_PINNED * sizeof(uint64_t), hipHostMallocDefault) != hipSuccess) {
     sc_destroy(c);
     return SC_EHIP;
@@ -851,6 +855,8 @@ void sc_destroy(sc_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);  // nullptr = the default stream
+  if (c->on_lane) (void)hipStreamSynchronize(c->lane_home);  // (a lane frame outstanding: `stream` above was the lane)
+  else if (c->own_stream && c->stream != c->own_stream) (void)hipStreamSynchronize(c->own_stream);  // (the lane: idle once the caller's stream has passed the join)
   for (sc_ctx::WgMap& m : c->wg_maps) if (m.buf.p) (void)hipFree(m.buf.p);
   for (size_t k = 0; k < N_WORKSPACE_BUFS; k++) if (workspace_bufs(c)[k].p) (void)hipFree(workspace_bufs(c)[k].p);  // every Buf of sc::Workspace
   for (int i = 0; i < N_EVENTS; i++) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
@@ -859,6 +865,8 @@ void sc_destroy(sc_ctx* c) {
   if (c->h_out) (void)hipHostFree(c->h_out);
   if (c->h_batch_off) (void)hipHostFree(c->h_batch_off);
   if (c->batch_off_ev) (void)hipEventDestroy(c->batch_off_ev);
+  if (c->lane_fork) (void)hipEventDestroy(c->lane_fork);
+  if (c->lane_join) (void)hipEventDestroy(c->lane_join);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;
 }
@@ -867,10 +875,12 @@ int sc_set_stream(sc_ctx* c, void* hip_stream) {
   if (!c) return SC_EINVAL;
   SC_TRY(busy(c));
   (void)hipSetDevice(c->device);
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));  // (no call is outstanding: `stream` is not the lane ...
+  if (c->stream != c->own_stream) HIPCHK(c, hipStreamSynchronize(c->own_stream));  // ... which is drained as well)
   c->ev_overhead_us = -1.f;  // event cost differs between streams: calibrate again on the next timed call
   if (hip_stream == SC_STREAM_DEFAULT) c->stream = nullptr;  // the null stream
   else c->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->own_stream;
+  c->caller_stream = hip_stream != nullptr;
   return SC_OK;
 }
 
@@ -912,6 +922,7 @@ int sc_set_debug(sc_ctx* c, const sc_debug* d) {
   t.gram_kappa_q4 = d->gram_kappa_q4;
   t.gram_ref_late = d->gram_ref_late != 0;
   t.no_fast = d->no_fast != 0;
+  t.no_lane = d->no_lane != 0;
   t.gram_guard_fail = d->gram_guard_fail != 0;
   t.no_estimate = d->no_estimate != 0;
   t.no_edge_build = d->no_edge_build != 0;
@@ -934,12 +945,13 @@ int sc_debug_last(sc_ctx* c, sc_debug_info* out) {
   out->filter_undecided = 0; out->filter_recounts = 0;
   out->fast_path = (uint32_t)c->frame.fast_state;
   out->gram_guard = c->tn.gram_guard_fail && c->gram_guard != 0 ? 2u : (uint32_t)c->gram_guard; out->gram_guard_worst = c->gram_guard_worst;
-  out->prune_bound = c->frame.est_failed_call ? 2u : (uint32_t)c->pass.est_state; out->reserved2 = 0;
+  out->prune_bound = c->frame.est_failed_call ? 2u : (uint32_t)c->pass.est_state; out->lane = c->frame.lane ? 1u : 0u;
   out->gram_near_corr = out->gram_near_hyp = out->gram_rows = out->gram_ref_votes_q8 = 0u; out->gram_ref = 0xFFFFFFFFu;
   out->us_c2_filter = (c->pass.hot_ext && c->pass.filter_on) ? ev_us_raw(c, 4, 11) : 0.f;
   out->n_frames = c->n_frames; out->n_fast_ok = c->n_fast_ok; out->n_fast_repeat = c->n_fast_repeat;
   out->n_est_ok = c->n_est_ok; out->n_est_fail = c->n_est_fail;
   out->cover_edges = c->pass.mode.E_cov; out->cover_triangles = c->pass.mode.M_cov; out->n_hostfree_grow = c->n_spec_grow;
+  out->n_lane = c->n_lane;
   if (c->pass.filter_on && c->fx_state.p)
     HIPCHK(c, filter_read_counters(c->fx_state.p, c->pass.fx_plan, c->stream, &out->filter_undecided, &out->filter_recounts));
   if (c->pass.filter_on && c->pass.filter_mode == 2 && c->fx_frame.p) {
@@ -1348,6 +1360,40 @@ namespace sc {
 
 constexpr int SC_ESPEC = -100;  // internal: a host-free call failed validation (never leaves the library)
 
+// ---- the lane (sc_ctx.hpp): a host-free frame of a direct sc_register_device_async call on a caller's stream runs beside that stream
+// Fork: everything the caller enqueued before the call — producers of d_src / d_tgt, earlier readers of d_Rt / d_mask, this context's
+// own earlier launches — is ordered before the frame; from here to the join the frame's launches go to the lane as c->stream.
+static int lane_fork_caller(sc_ctx* c) {
+  HIPCHK(c, hipEventRecord(c->lane_fork, c->stream));
+  HIPCHK(c, hipStreamWaitEvent(c->own_stream, c->lane_fork, 0));
+  c->lane_home = c->stream;
+  c->stream = c->own_stream;
+  c->on_lane = true;
+  return SC_OK;
+}
+// Join (finalize_wait; a no-op off the lane): the caller's stream waits for the event behind the frame's last launch, and is the
+// context's stream again — the validation, a repeat, sc_peel / sc_polish* and the caller's own reads of d_Rt / d_mask follow the
+// frame in stream order, as they do without a lane.
+static int lane_join_caller(sc_ctx* c) {
+  if (!c->on_lane) return SC_OK;
+  c->on_lane = false;
+  c->stream = c->lane_home;
+  HIPCHK(c, hipStreamWaitEvent(c->stream, c->lane_join, 0));
+  return SC_OK;
+}
+// Behind the frame's last launch on the lane: what the join waits for
+static int lane_mark_end(sc_ctx* c) {
+  HIPCHK(c, hipEventRecord(c->lane_join, c->stream));
+  return SC_OK;
+}
+// The enqueue failed half-way: what reached the lane runs out (no join was recorded), then the caller's stream is the context's again
+static void lane_drain(sc_ctx* c) {
+  if (!c->on_lane) return;
+  (void)hipStreamSynchronize(c->own_stream);
+  c->on_lane = false;
+  c->stream = c->lane_home;
+}
+
 // phase 2, first half: the winner / mask kernel (and the optional refit) are enqueued; nothing is waited for
 static int finalize_enqueue(sc_ctx* c, const uint64_t* d_keys, int n_pairs, float* d_Rt, uint8_t* d_mask) {
   SC_TRY(rec(c, 7));
@@ -1398,10 +1444,14 @@ static int finalize_wait(sc_ctx* c, sc_stats* stats) {
   // The finalize kernel publishes key / position / rank.  On a caller-provided stream (sc_set_stream) d_Rt and d_mask
   // are complete in stream order, like any other work the caller enqueues there; on the context's private stream —
   // which the caller cannot order against — and when the per-stage events are read below, wait for everything.
+  // "Private" means that no caller's stream is set — a frame on its lane has the private stream as c->stream and is polled for.
   const bool was_spec = pass_end(c);
-  if (c->pass.timing || c->stream == c->own_stream) HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (c->pass.timing || !c->caller_stream) HIPCHK(c, hipStreamSynchronize(c->stream));
   else if (c->pass.timing_one == 6) HIPCHK(c, hipEventSynchronize(c->ev[8]));  // the mask bracket ends after the kernel polled below
-  if (const int rc = wait_word(c, HW_WINNER)) { c->fast_ok = false; return rc; }
+  const int rc_winner = wait_word(c, HW_WINNER);  // (a lane frame: polled, or after 1 ms synchronised, on the lane)
+  const int rc_join = lane_join_caller(c);        // ... and before anything else the caller's stream is behind the frame
+  if (rc_winner) { c->fast_ok = false; return rc_winner; }
+  if (rc_join) { c->fast_ok = false; return rc_join; }
   HIPCHK(c, hipGetLastError());
   if (was_spec) {
     // Host-free call: every kernel of it has finished (the winner word is the last thing the stream writes), so the two
@@ -1574,8 +1624,12 @@ int sc_finalize_gathered_device_async(sc_ctx* c, const uint64_t* d_keys, int n_p
   return SC_OK;
 }
 
-int sc_register_device_async(sc_ctx* c, const float* d_src, const float* d_tgt, int64_t n, const sc_params* p,
-                             float* d_Rt, uint8_t* d_mask) {
+}  // extern "C"
+
+// sc_register_device_async.  `direct`: the caller gets the context back before the frame is waited for, so a host-free frame on a
+// caller's stream takes the lane; sc_register_device (async + wait in one call) overlaps nothing and pays no fork and join.
+static int register_async(sc_ctx* c, const float* d_src, const float* d_tgt, int64_t n, const sc_params* p,
+                          float* d_Rt, uint8_t* d_mask, bool direct) {
   if (!c || !d_src || !d_tgt || !d_Rt || !d_mask) return SC_EINVAL;
   peel_end(c);
   if (c->frame.pending) { c->last_error = "sc_register_device_async: a call is already outstanding on this context (sc_wait first)"; return SC_EINVAL; }
@@ -1588,9 +1642,15 @@ int sc_register_device_async(sc_ctx* c, const float* d_src, const float* d_tgt, 
   PassMode mode{true};  // (sc_wait repeats a call whose estimated pruning bound fails, like any other failed assumption)
   if (fast_plan(c, n, p, &mode)) {
     // host-free: the whole chain is enqueued without looking at anything the GPU produces; sc_wait validates
-    int rc = hyp_begin(c, d_src, d_tgt, n, p, nullptr, 0, 1, mode);
+    int rc = SC_OK;
+    if (direct && c->caller_stream && !c->tn.no_lane) rc = lane_fork_caller(c);
+    if (!rc) rc = hyp_begin(c, d_src, d_tgt, n, p, nullptr, 0, 1, mode);
     if (!rc) rc = hyp_end(c, nullptr, c->key.as<uint64_t>(), &c->frame.pend_stats);
     if (!rc) rc = finalize_enqueue(c, c->key.as<uint64_t>(), 1, d_Rt, d_mask);
+    if (!rc && c->on_lane) {
+      rc = lane_mark_end(c);
+      if (!rc) { c->frame.lane = true; c->n_lane++; }
+    }
     if (!rc) {
       c->frame.pending = true; c->frame.pend_done = false; c->frame.pend_finalize = false;
       return SC_OK;
@@ -1598,14 +1658,23 @@ int sc_register_device_async(sc_ctx* c, const float* d_src, const float* d_tgt, 
     // The host-free enqueue failed (an allocation sized by the COVERS hit the workspace cap, a launch failed): the waited form of
     // the same call may well fit — "results are identical either way" (include/saccot.h) includes the status.  What was enqueued
     // so far runs out first: its kernels publish into the pinned words the waited call is about to arm.  
+    // A frame on its lane: the lane is drained and the caller's stream is the context's again before the waited form starts.
     pass_end(c); c->fast_ok = false;
-    (void)hipStreamSynchronize(c->stream);
+    if (c->on_lane) lane_drain(c);
+    else (void)hipStreamSynchronize(c->stream);
     (void)hipGetLastError();
   }
   const int rc = register_waited(c, d_src, d_tgt, n, p, d_Rt, d_mask, &c->frame.pend_stats);
   if (rc != SC_OK && rc != SC_ENOHYP) return rc;
   c->frame.pending = true; c->frame.pend_done = true; c->frame.pending_rc = rc; c->frame.pend_finalize = false;
   return SC_OK;
+}
+
+extern "C" {
+
+int sc_register_device_async(sc_ctx* c, const float* d_src, const float* d_tgt, int64_t n, const sc_params* p,
+                             float* d_Rt, uint8_t* d_mask) {
+  return register_async(c, d_src, d_tgt, n, p, d_Rt, d_mask, true);
 }
 
 int sc_wait(sc_ctx* c, sc_stats* stats) {
@@ -1642,7 +1711,7 @@ int sc_wait(sc_ctx* c, sc_stats* stats) {
 
 int sc_register_device(sc_ctx* c, const float* d_src, const float* d_tgt, int64_t n, const sc_params* p,
                        float* d_Rt, uint8_t* d_mask, sc_stats* stats) {
-  SC_TRY(sc_register_device_async(c, d_src, d_tgt, n, p, d_Rt, d_mask));
+  SC_TRY(register_async(c, d_src, d_tgt, n, p, d_Rt, d_mask, false));  // (waited for at once: no lane)
   return sc_wait(c, stats);
 }
 

@@ -82,6 +82,7 @@ struct Pass {
 // second pass) and ends in count_frame.  Assigned Frame{} in frame_begin and nowhere else.
 struct Frame {
   int fast_state = 0;            // 0 waited, 1 host-free and valid, 2 host-free, failed validation, repeated
+  bool lane = false;             // its host-free enqueue ran on the context's lane (sc_ctx::lane_fork)
   bool est_failed_call = false;  // a pass of this frame saw its estimate fail (sc_debug_last: prune_bound 2); the repeat must not forget it
   // the outstanding half of sc_register_device_async / sc_finalize_gathered_device_async (at most one per context)
   bool pending = false;
@@ -152,6 +153,17 @@ struct sc_ctx : sc::Workspace {  // (the workspace buffers are direct members to
   int device = 0;
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
+  // A caller's stream is set (sc_set_stream; SC_STREAM_DEFAULT included): outputs are stream-ordered, nothing synchronises.  NOT
+  // "stream != own_stream": a frame on its lane (below) has the private stream as `stream` and still belongs to a caller's.
+  bool caller_stream = false;
+  // The lane: a host-free frame of a direct sc_register_device_async call on a caller's stream runs on own_stream — idle whenever
+  // a caller's stream is set — beside that stream: lane_fork is recorded on the caller's stream at the call and the lane waits
+  // for it; lane_join is recorded behind the frame's last launch and the caller's stream waits for it in sc_wait (lane_join_caller).
+  // While the frame is outstanding `stream` is the lane and lane_home the caller's stream.
+  hipEvent_t lane_fork = nullptr, lane_join = nullptr;
+  hipStream_t lane_home = nullptr;
+  bool on_lane = false;
+  uint64_t n_lane = 0;  // frames that ran on the lane (sc_debug_last)
   std::string last_error;
   size_t held = 0;
   uint64_t cap_bytes = 64ull << 30;  // what ensure() holds `held` against: every entry point sets it from its sc_params
@@ -380,7 +392,7 @@ inline int scored_frame_begin(sc_ctx* c, const char* who) {
 // Behind the last launch: outputs complete on return with the private stream, stream-ordered with a caller's (as sc_register_device);
 // then the winner's two host words (HW_WINNER, armed by the caller, and HW_WINNER_POS) are there.
 inline int scored_frame_wait(sc_ctx* c) {
-  if (c->pass.timing || c->stream == c->own_stream) HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (c->pass.timing || !c->caller_stream) HIPCHK(c, hipStreamSynchronize(c->stream));
   SC_TRY(wait_word(c, HW_WINNER));
   HIPCHK(c, hipGetLastError());
   return SC_OK;

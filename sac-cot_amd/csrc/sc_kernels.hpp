@@ -55,6 +55,7 @@ struct Tuning {
   uint32_t gram_kappa_q4 = 0;      // the Gram filter's cut: hypotheses whose reach stays under (value / 16) tau' count as NEAR the reference (0 = GX_KAPPA = 8; 1 = practically no cut)
   bool gram_ref_late = false;      // the Gram filter's reference frame is voted after the selection, in a launch of its own (what every path but the hot one does anyway), instead of under the counting pass
   bool no_fast = false;            // sc_register_device never enqueues host-free (always waits for stage B's two counts)
+  bool no_lane = false;            // a host-free sc_register_device_async frame stays on the caller's stream (never on the context's lane)
   bool gram_guard_fail = false;    // the matrix-pipe probe reports a violation (tests of the guard)
   bool filter_blind = false;       // the host decides C2's kernel WITHOUT the coordinate maxima (as if they had not arrived yet)
   bool compat_one_phase = false;   // exact chain on every pair of an interior tile
