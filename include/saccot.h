@@ -48,6 +48,7 @@ extern "C" {
 #define SC_HAS_POSE_INFO_FRAME 1  /* this header declares sc_pose_info_frame* and sc_pose_info_default_params (added within 0.10) */
 #define SC_HAS_POLISH_POSES 1  /* this header declares sc_polish_poses* (added within 0.10) */
 #define SC_HAS_ASSIGN 1  /* this header declares sc_assign_poses* and sc_assign_default_params (added within 0.10) */
+#define SC_HAS_MATCH_GUIDED 1  /* this header declares sc_match_guided*, sc_register_guided_features and sc_guide_default_params (added within 0.10) */
 
 /* status codes */
 #define SC_OK        0
@@ -452,6 +453,71 @@ int sc_match(sc_ctx* ctx, const float* fsrc, int64_t ns, const float* ftgt, int6
 int sc_register_features(sc_ctx* ctx, const float* src_pts, const float* fsrc, int64_t ns, const float* tgt_pts,
                          const float* ftgt, int64_t nt, const sc_match_params* mp, const sc_params* params, float R[9],
                          float t[3], int32_t* corr, float* d2, uint32_t* n, uint8_t* mask, sc_stats* stats);
+
+/* ---- descriptor matching gated by a pose prior: sc_match_guided ("guided matching") ----------------------
+ * Once a pose is known — a frame's winner, a motion of sc_peel, an external prior — a pipeline matches again under it: source
+ * keypoint i may only pair with the target keypoints that lie within a radius of where the pose puts it, and among those the nearest
+ * descriptor wins.  This is NOT sc_match filtered by the gate afterwards: a row whose pose-blind nearest neighbour lies outside the
+ * gate is re-assigned here, not lost.  A function of the input alone, bit for bit:
+ *   The pose: Rt is the library's record, R = Rt[0..8] row-major, t = Rt[9..11], mapping source onto target.
+ *   src_pts: ns points, tgt_pts: nt points, fp32, in guide->layout (SC_AOS: n x 3 row-major; SC_SOA: three planes of n), finite;
+ *   point i belongs to descriptor row i.  fsrc, ftgt, ns, nt and every rule of sc_match_params: as sc_match.
+ *   The gate residual of (i, j), p = src_pts[i], q = tgt_pts[j] — the canonical residual of the masks' inlier test, every operation
+ *   fp32 and rounded to nearest, fma = the fused multiply-add, c in x, y, z:
+ *       e_c = t_c + fma(R_c2, pz, fma(R_c1, py, fma(R_c0, px, -q_c)));   g2 = fma(ez, ez, fma(ey, ey, ex * ex))
+ *   The threshold: gate2 = (float)((double)gate * gate), as tau^2 is derived from tau.
+ *   Admissibility: adm(i, j) <=> g2(i, j) < gate2, a float <: a NaN or infinite residual is never admissible (and raises no flag:
+ *   only the INPUT is tested for finiteness, see below).
+ *   The descriptor distance acc(i, j) and both u64 key orders are sc_match's, unchanged.
+ *   Candidates: row i's candidates are its admissible j only, ordered by (bits(acc) << 32) | j.
+ *     knn = k: the k smallest admissible keys in order, fewer if fewer are admissible; a row with no admissible j yields nothing.
+ *     SC_MATCH_MUTUAL: target j's minimum runs over its admissible i only, under the reverse key (bits(acc) << 32) | i.
+ *     ratio: acc1 < r2 * acc2 with acc2 the second-smallest ADMISSIBLE key; the match is kept when the row has fewer than two
+ *     admissible candidates (the rule nt == 1 follows in sc_match).
+ * Output: corr (n x 2 int32) and d2 (n x fp32: acc) as in sc_match, in ascending (i, rank) order; g2 (n x fp32, optional: NULL ok):
+ * the gate residual of every output entry; count[0] = n, count[1] = 1 if any descriptor, any point or the pose is not finite — then
+ * n = 0, and the host forms return SC_EINVAL with *n = 0.  That flag depends on the input alone: every element of both descriptor
+ * arrays, both point arrays and the pose is tested, whatever the gate excludes.
+ * Determinism: the whole output is a function of the inputs, bit for bit — not of launch geometry, of the context's history or of
+ * which form was called.
+ * Frames and workspace: like sc_match*, these entries end the frame the context may hold; the workspace is sc_match's (the host
+ * forms add their device copies), counted in workspace_bytes and held against the cap; a context that never calls them allocates
+ * nothing new.
+ * Refused with SC_EINVAL on the host before anything is enqueued, sc_last_error naming which: every rule of sc_match_params; a NULL
+ * argument (g2 / d_g2 excepted); guide->size wrong; a layout above SC_SOA; a gate that is not finite and > 0; a flag or reserved word
+ * that is not 0; a call outstanding on the context.
+ * Not here: batch and pairs forms; several poses per call; a gate on anything but the point residual (descriptor-space or scale
+ * gates); soft weighting by g2. */
+typedef struct sc_guide_params {   /* 32 bytes */
+  uint32_t size;         /* = sizeof(sc_guide_params)                                                  */
+  uint32_t layout;       /* SC_AOS / SC_SOA: how src_pts and tgt_pts are laid out                      */
+  float    gate;         /* radius, finite, > 0                                                        */
+  uint32_t flags;        /* must be 0                                                                  */
+  uint32_t reserved[4];  /* must be 0                                                                  */
+} sc_guide_params;
+int sc_guide_default_params(sc_guide_params* gp);   /* size set, SC_AOS, gate 0 (the caller sets it), no flags */
+/* Every buffer in HBM.  d_corr, d_d2, d_count as sc_match_device's; d_g2: ns * knn floats or NULL; d_Rt: 12 floats.  Exactly three
+ * stream operations on the context's stream whatever the sizes (a memset and two launches), no host word; returns without waiting.
+ * d_Rt is read in stream order: it may be the d_Rt that a preceding sc_register_device_async / sc_peel_device /
+ * sc_polish_poses_device on the same stream wrote.  d_count[1] = 1: n = 0 and d_corr / d_d2 / d_g2 are unspecified. */
+int sc_match_guided_device(sc_ctx* ctx, const float* d_src_pts, const float* d_fsrc, int64_t ns, const float* d_tgt_pts,
+                           const float* d_ftgt, int64_t nt, const sc_match_params* mp, const sc_guide_params* gp, const float* d_Rt,
+                           int32_t* d_corr, float* d_d2, float* d_g2, uint32_t* d_count);
+/* The same with host arrays (corr, d2, g2: room for ns * knn entries, g2 may be NULL; the first *n are written); waits.  A
+ * non-finite descriptor, point or pose entry: SC_EINVAL, *n = 0. */
+int sc_match_guided(sc_ctx* ctx, const float* src_pts, const float* fsrc, int64_t ns, const float* tgt_pts, const float* ftgt,
+                    int64_t nt, const sc_match_params* mp, const sc_guide_params* gp, const float Rt[12], int32_t* corr, float* d2,
+                    float* g2, uint32_t* n);
+/* sc_register_features with the guided match in front: the guided match under Rt_prior, the gather on the device, then the
+ * unchanged sc_register_device on the gathered arrays, with one host wait (the count).  guide->layout must equal params->layout (the
+ * keypoints are one pair of arrays); g2 may be NULL.  corr, d2, g2, *n are valid whenever the match itself succeeded; n < 3:
+ * SC_ENOHYP with R = I, t = 0 and the mask untouched; otherwise status, R, t, mask and stats are exactly those of sc_register on
+ * the gathered correspondences, and the call leaves that frame: sc_peel, sc_polish*, sc_pose_info_frame and sc_assign_poses_frame
+ * may follow. */
+int sc_register_guided_features(sc_ctx* ctx, const float* src_pts, const float* fsrc, int64_t ns, const float* tgt_pts,
+                                const float* ftgt, int64_t nt, const sc_match_params* mp, const sc_guide_params* gp,
+                                const float Rt_prior[12], const sc_params* params, float R[9], float t[3], int32_t* corr, float* d2,
+                                float* g2, uint32_t* n, uint8_t* mask, sc_stats* stats);
 
 /* ---- descriptor matching for a whole batch of small problems: sc_match_batch -----------------------------
  * What stands in front of sc_register_batch: its callers (pose candidates, fragment pairs of a few hundred keypoints, cluster pairs)

@@ -41,6 +41,7 @@ EXPORTS = ["sc_version", "sc_strerror", "sc_default_params", "sc_create", "sc_de
            "sc_peel", "sc_peel_device", "sc_register_instances",
            "sc_polish_default_params", "sc_polish_device", "sc_polish",
            "sc_match_default_params", "sc_match_device", "sc_match", "sc_register_features",
+           "sc_guide_default_params", "sc_match_guided_device", "sc_match_guided", "sc_register_guided_features",
            "sc_match_batch", "sc_match_batch_device", "sc_register_batch_features", "sc_register_batch_features_device",
            "sc_polish_batch", "sc_polish_batch_device", "sc_polish_batch_slots_device",
            "sc_register_instances_batch", "sc_register_instances_batch_device", "sc_register_instances_batch_features_device",
@@ -84,6 +85,12 @@ class ScMatchParams(C.Structure):
     """Mirror of `sc_match_params` (include/saccot.h): descriptor length, neighbours per row (1 .. 4), SC_MATCH_* flags, ratio test."""
     _fields_ = [("size", C.c_uint32), ("dim", C.c_uint32), ("knn", C.c_uint32), ("flags", C.c_uint32), ("ratio", C.c_float),
                 ("reserved", C.c_uint32 * 3)]
+
+
+class ScGuideParams(C.Structure):
+    """Mirror of `sc_guide_params` (include/saccot.h): the layout of the keypoints (SC_AOS / SC_SOA) and the gate radius of
+    sc_match_guided."""
+    _fields_ = [("size", C.c_uint32), ("layout", C.c_uint32), ("gate", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 4)]
 
 
 class ScPolishParams(C.Structure):
@@ -281,6 +288,12 @@ def load_library() -> C.CDLL:
     L.sc_match_device.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, mp, vp, vp, vp]
     L.sc_match.argtypes = [vp, f32p, C.c_int64, f32p, C.c_int64, mp, i32p, f32p, u32p]
     L.sc_register_features.argtypes = [vp, f32p, f32p, C.c_int64, f32p, f32p, C.c_int64, mp, pp, f32p, f32p, i32p, f32p, u32p, u8p, sp]
+    gp = C.POINTER(ScGuideParams)
+    L.sc_guide_default_params.argtypes = [gp]
+    L.sc_match_guided_device.argtypes = [vp, vp, vp, C.c_int64, vp, vp, C.c_int64, mp, gp, vp, vp, vp, vp, vp]
+    L.sc_match_guided.argtypes = [vp, f32p, f32p, C.c_int64, f32p, f32p, C.c_int64, mp, gp, f32p, i32p, f32p, f32p, u32p]
+    L.sc_register_guided_features.argtypes = [vp, f32p, f32p, C.c_int64, f32p, f32p, C.c_int64, mp, gp, f32p, pp, f32p, f32p, i32p, f32p,
+                                              f32p, u32p, u8p, sp]
     L.sc_match_batch_device.argtypes = [vp, vp, u32p, vp, u32p, C.c_uint32, mp, vp, vp, vp]
     L.sc_match_batch.argtypes = [vp, f32p, u32p, f32p, u32p, C.c_uint32, mp, i32p, f32p, u32p]
     L.sc_register_batch_features_device.argtypes = [vp, vp, vp, u32p, vp, vp, u32p, C.c_uint32, mp, pp, vp, vp, vp, vp, vp]
@@ -351,6 +364,11 @@ def make_params(sigma=0.1, t_cmp=0.9, tau=0.1, min_len=0.1, max_triangles=50000,
 def make_match_params(dim: int, knn: int = 1, mutual: bool = False, ratio: float = 0.0, flags: int = 0) -> ScMatchParams:
     """sc_match_params for descriptors of length `dim`: knn 1 .. 4; mutual / ratio (in (0, 1), 0 = off) with knn == 1 only."""
     return ScMatchParams(C.sizeof(ScMatchParams), dim, knn, flags | (SC_MATCH_MUTUAL if mutual else 0), ratio)
+
+
+def make_guide_params(gate: float, layout: int = SC_AOS, flags: int = 0) -> ScGuideParams:
+    """sc_guide_params: the gate radius (finite, > 0) and the layout of the keypoint arrays of sc_match_guided."""
+    return ScGuideParams(C.sizeof(ScGuideParams), layout, gate, flags)
 
 
 def make_polish_params(candidates: int = 8, max_iter: int = 16, flags: int = 0) -> ScPolishParams:
@@ -646,6 +664,66 @@ class Registrar:
         self._frame_n = k
         return dict(status=rc, R=R.reshape(3, 3), t=t, n=k, corr=corr[:k].copy(), d2=d2[:k].copy(), mask=mask[:k].copy(),
                     stats=st.as_dict())
+
+    # ---- descriptor matching gated by a pose prior (include/saccot.h, sc_match_guided) --------------------------
+    @staticmethod
+    def _guided_inputs(who, src_pts, fsrc, tgt_pts, ftgt, layout):
+        src_pts, tgt_pts, fsrc, ftgt = _f32c(src_pts), _f32c(tgt_pts), _f32c(fsrc), _f32c(ftgt)
+        if fsrc.ndim != 2 or ftgt.ndim != 2 or fsrc.shape[1] != ftgt.shape[1] or src_pts.ndim != 2 or tgt_pts.ndim != 2:
+            raise ValueError(who + ": fsrc (ns, D) and ftgt (nt, D) with one D, points (n, 3) or, SC_SOA, (3, n)")
+        ax = 1 if layout == SC_SOA else 0
+        if src_pts.shape[ax] != fsrc.shape[0] or tgt_pts.shape[ax] != ftgt.shape[0] or src_pts.shape[1 - ax] != 3 or tgt_pts.shape[1 - ax] != 3:
+            raise ValueError(who + ": one descriptor row per point")
+        return src_pts, fsrc, tgt_pts, ftgt
+
+    def match_guided(self, src_pts, fsrc, tgt_pts, ftgt, Rt, gate: float | None = None, layout: int = SC_AOS,
+                     mparams: ScMatchParams | None = None, gparams: ScGuideParams | None = None, **kw):
+        """sc_match_guided: keypoints and descriptors of both sets, the pose prior Rt (12 floats: R row-major, then t) and the gate
+        radius -> dict(n, corr (n, 2) int32, d2 (n,), g2 (n,): the gate residual of every entry).  Row i may only pair with the
+        targets within `gate` of where Rt puts point i.  kw: knn, mutual, ratio (make_match_params)."""
+        g = gparams or make_guide_params(gate, layout)
+        src_pts, fsrc, tgt_pts, ftgt = self._guided_inputs("match_guided", src_pts, fsrc, tgt_pts, ftgt, g.layout)
+        Rt = _f32c(Rt).reshape(12)
+        m = mparams or make_match_params(fsrc.shape[1], **kw)
+        cap = max(fsrc.shape[0] * max(int(m.knn), 1), 1)
+        corr = np.zeros((cap, 2), np.int32); d2 = np.zeros(cap, np.float32); g2 = np.zeros(cap, np.float32); n = C.c_uint32(0)
+        self._check(self._lib.sc_match_guided(self._h, _p(src_pts, C.c_float), _p(fsrc, C.c_float), fsrc.shape[0], _p(tgt_pts, C.c_float),
+                                              _p(ftgt, C.c_float), ftgt.shape[0], C.byref(m), C.byref(g), _p(Rt, C.c_float),
+                                              _p(corr, C.c_int32), _p(d2, C.c_float), _p(g2, C.c_float), C.byref(n)))
+        k = int(n.value)
+        return dict(n=k, corr=corr[:k].copy(), d2=d2[:k].copy(), g2=g2[:k].copy())
+
+    def match_guided_device(self, d_src_pts: int, d_fsrc: int, ns: int, d_tgt_pts: int, d_ftgt: int, nt: int, mparams: ScMatchParams,
+                            gparams: ScGuideParams, d_Rt: int, d_corr: int, d_d2: int, d_g2: int | None, d_count: int):
+        """sc_match_guided_device: everything in HBM (d_Rt: 12 floats, read in stream order; d_corr, d_d2, d_count as match_device's;
+        d_g2: ns * knn float32 or None); three stream operations on the context's stream, returns without waiting."""
+        self._check(self._lib.sc_match_guided_device(self._h, d_src_pts, d_fsrc, ns, d_tgt_pts, d_ftgt, nt, C.byref(mparams),
+                                                     C.byref(gparams), d_Rt, d_corr, d_d2, d_g2, d_count))
+
+    def register_guided_features(self, src_pts, fsrc, tgt_pts, ftgt, Rt_prior, gate: float | None = None,
+                                 mparams: ScMatchParams | None = None, gparams: ScGuideParams | None = None,
+                                 params: ScParams | None = None, knn: int = 1, mutual: bool = False, ratio: float = 0.0, **kw):
+        """sc_register_guided_features: register_features with the guided match under Rt_prior in front -> dict(status, R, t, n,
+        corr (n, 2), d2 (n,), g2 (n,), mask (n,), stats).  Fewer than 3 matches: SC_ENOHYP, R = I.  Leaves a frame of n
+        correspondences: peel(), polish() ... may follow."""
+        p = params or make_params(**kw)
+        g = gparams or make_guide_params(gate, p.layout)
+        src_pts, fsrc, tgt_pts, ftgt = self._guided_inputs("register_guided_features", src_pts, fsrc, tgt_pts, ftgt, g.layout)
+        Rt = _f32c(Rt_prior).reshape(12)
+        m = mparams or make_match_params(fsrc.shape[1], knn, mutual, ratio)
+        ns, nt = fsrc.shape[0], ftgt.shape[0]
+        cap = max(ns * max(int(m.knn), 1), 1)
+        corr = np.zeros((cap, 2), np.int32); d2 = np.zeros(cap, np.float32); g2 = np.zeros(cap, np.float32); n = C.c_uint32(0)
+        R = np.zeros(9, np.float32); t = np.zeros(3, np.float32); mask = np.zeros(cap, np.uint8)
+        st = ScStats(C.sizeof(ScStats))
+        rc = self._check(self._lib.sc_register_guided_features(
+            self._h, _p(src_pts, C.c_float), _p(fsrc, C.c_float), ns, _p(tgt_pts, C.c_float), _p(ftgt, C.c_float), nt, C.byref(m),
+            C.byref(g), _p(Rt, C.c_float), C.byref(p), _p(R, C.c_float), _p(t, C.c_float), _p(corr, C.c_int32), _p(d2, C.c_float),
+            _p(g2, C.c_float), C.byref(n), _p(mask, C.c_uint8), C.byref(st)), allow=(SC_ENOHYP,))
+        k = int(n.value)
+        self._frame_n = k
+        return dict(status=rc, R=R.reshape(3, 3), t=t, n=k, corr=corr[:k].copy(), d2=d2[:k].copy(), g2=g2[:k].copy(),
+                    mask=mask[:k].copy(), stats=st.as_dict())
 
     # ---- descriptor matching for a batch of small problems (include/saccot.h, sc_match_batch) -------------------
     @staticmethod

@@ -105,8 +105,9 @@ struct Workspace {
       // tmp: the chunk sums, candidates x polish_scratch_bytes(n)
       polish_cand, polish_tmp,
       // sc_match / sc_register_features: allocated by the first match, never by a frame.  part: the slices' partial lists; words: the
-      // "clean" word, the host entries' count pair, then the column minima; the rest: device copies of the host entries' arrays
-      match_part, match_words, match_fsrc, match_ftgt, match_psrc, match_ptgt, match_corr, match_d2, match_gsrc, match_gtgt,
+      // "clean" word, the host entries' count pair, the guided host entries' pose, then the column minima; the rest: device copies of
+      // the host entries' arrays (g2: the guided host entries' only, allocated by the first of them)
+      match_part, match_words, match_fsrc, match_ftgt, match_psrc, match_ptgt, match_corr, match_d2, match_gsrc, match_gtgt, match_g2,
       // sc_register_batch: allocated by the first batch call, never by a frame.  off: the copy of the caller's offsets; the rest:
       // device copies of the host entry's arrays
       batch_off, batch_src, batch_tgt, batch_res, batch_mask,

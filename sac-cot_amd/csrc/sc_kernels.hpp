@@ -680,15 +680,26 @@ struct MatchGather {
   uint32_t s_elem, s_comp, t_elem, t_comp;
   float* gsrc; float* gtgt;
 };
+// sc_match_guided: the keypoints of both sets (point i of src is src[i * s_elem + c * s_comp], as MatchGather's), the pose prior (12
+// floats in HBM, read in stream order) and gate2; cell (i, j) is a candidate only where resid2(Rt, src[i], tgt[j]) < gate2.
+struct MatchGuide {
+  const float* src; const float* tgt;
+  uint32_t s_elem, s_comp, t_elem, t_comp;
+  const float* Rt;
+  float gate2;
+};
 // colmin (SC_MATCH_MUTUAL, else nullptr): nt keys (distance << 32 | row), all ones at launch.  clean: one word, non-zero at launch,
-// cleared when a non-finite descriptor is read.
-void launch_match_dist(const MatchJob& job, const MatchPlan& plan, uint64_t* part, uint64_t* colmin, uint32_t* clean, hipStream_t st);
+// cleared when a non-finite descriptor is read — with a guide (gd != nullptr: sc_match_guided) when any descriptor, any point or the
+// pose is not finite, whatever the gate excludes.
+void launch_match_dist(const MatchJob& job, const MatchPlan& plan, uint64_t* part, uint64_t* colmin, uint32_t* clean, const MatchGuide* gd,
+                       hipStream_t st);
 // merge + mutual / ratio + compaction in (row, rank) order: corr (n x 2 int32), d2 (n), count[0] = n, count[1] = 1 if a non-finite
 // descriptor was read (then n = 0 and nothing else is written).  lb: a look-back launch of match_finish_tiles(ns) tiles (8 bytes of
-// descriptor each).  host_word (optional, pinned): receives n | flag << 32.
+// descriptor each).  host_word (optional, pinned): receives n | flag << 32.  gd, g2 (both optional): g2[m] = the gate residual of entry m.
 uint32_t match_finish_tiles(uint32_t ns);
 void launch_match_finish(const MatchJob& job, const MatchPlan& plan, const uint64_t* part, const uint64_t* colmin, const uint32_t* clean,
-                         int32_t* corr, float* d2, uint32_t* count, const MatchGather& g, LbArgs lb, uint64_t* host_word, hipStream_t st);
+                         int32_t* corr, float* d2, uint32_t* count, const MatchGather& g, LbArgs lb, uint64_t* host_word, const MatchGuide* gd,
+                         float* g2, hipStream_t st);
 
 // ---- many small registrations in one launch (sc_register_batch; sc_batch.hip) ------------------------------
 // One problem's result: sc_batch_result of include/saccot.h, field for field (sc_batch.hip asserts the size).

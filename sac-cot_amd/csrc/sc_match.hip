@@ -19,8 +19,19 @@
 //                        output slots from a decoupled look-back over the tiles (sc_block.hpp, as peel_compact_kernel), writes
 //                        corr / d2 in ascending (row, rank) order, gathers the matched points for sc_register_features, and the
 //                        last tile writes the count and the non-finite flag.
+//
+// sc_match_guided (GUIDED) is the same pair of launches with a pose prior: a cell (i, j) is a candidate only where the canonical
+// residual of the inlier test, resid2(Rt, src_pts[i], tgt_pts[j]) (sc_arith.hpp), is below gate2.  The distance launch stages the
+// workgroup's 128 source points once and a tile's 64 target points per tile, every thread folds its 8 x 4 decisions into one 32-bit
+// word BEFORE the descriptor chunks (the points are not live across the accumulate loop), an inadmissible cell offers no key — not to
+// the row's list, not to the column minimum — and a tile in which no cell of the workgroup is admissible is skipped altogether: no
+// descriptor load, no tile_step (the decision is a workgroup-wide OR behind a barrier every thread passes).  Because a skipped tile's
+// descriptors are never staged, the finiteness rule is carried by a scan of its own in the same launch: every workgroup tests a
+// grid-strided share of both descriptor arrays, both point arrays and the pose.  The finish launch can also emit g2 per entry.
 #include <cstddef>
+#include <type_traits>
 
+#include "sc_arith.hpp"
 #include "sc_block.hpp"
 #include "sc_kernels.hpp"
 #include "sc_match_tile.hpp"
@@ -35,16 +46,30 @@ constexpr int MT_ROWS = 128, MT_COLS = 64, MT_THREADS = 256;  // (MT_KC, the key
 constexpr int MT_LDA = MT_ROWS + 4, MT_LDB = MT_COLS + 4;  // 16-byte aligned rows; the pad spreads the transposing stores over the banks
 constexpr int FIN_THREADS = 256;
 
-template <int KP>
+// this thread's share of n floats, grid-strided over the whole launch: is one of them not finite?
+__device__ __forceinline__ bool scan_not_finite(const float* __restrict__ p, size_t n, size_t me, size_t stride) {
+  bool bad = false;
+  for (size_t e = me; e < n; e += stride) bad = bad || not_finite(p[e]);
+  return bad;
+}
+
+// sc_match's kernel takes no guide: an empty argument
+struct NoGuide {};
+
+// The distance launch, said once.  GUIDED = false is sc_match's kernel; GUIDED = true adds the gate.
+template <int KP, bool GUIDED>
 __global__ __launch_bounds__(MT_THREADS) void match_dist_kernel(const float* __restrict__ fsrc, uint32_t ns,
                                                                 const float* __restrict__ ftgt, uint32_t nt, uint32_t D,
                                                                 uint32_t tiles_per_slice, unsigned long long* __restrict__ part,
                                                                 size_t ld_part, unsigned long long* __restrict__ colmin,
-                                                                uint32_t* __restrict__ clean) {
+                                                                uint32_t* __restrict__ clean,
+                                                                typename std::conditional<GUIDED, MatchGuide, NoGuide>::type gd) {
   __shared__ __attribute__((aligned(16))) float sA[MT_KC][MT_LDA];
   __shared__ __attribute__((aligned(16))) float sB[MT_KC][MT_LDB];
   __shared__ unsigned long long s_top[MT_ROWS][KP];
   __shared__ unsigned long long s_col[MT_COLS];
+  __shared__ float sP[GUIDED ? 3 : 1][GUIDED ? MT_ROWS : 1];  // the workgroup's source points, component-major
+  __shared__ float sQ[GUIDED ? 3 : 1][GUIDED ? MT_COLS : 1];  // the tile's target points
   const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;  // the thread's 4 columns / 8 rows; also (component, row) when it loads
   const uint32_t row0 = blockIdx.x * MT_ROWS;
   const uint32_t n_tiles = (nt + MT_COLS - 1) / MT_COLS;
@@ -52,9 +77,48 @@ __global__ __launch_bounds__(MT_THREADS) void match_dist_kernel(const float* __r
   const uint32_t tile_hi = tile_lo + tiles_per_slice < n_tiles ? tile_lo + tiles_per_slice : n_tiles;
   for (int e = threadIdx.x; e < MT_ROWS * KP; e += MT_THREADS) (&s_top[0][0])[e] = KEY_NONE;
   bool bad = false;
+  float M[12];       // GUIDED: the pose (wave-uniform)
+  uint32_t adm = 0;  // GUIDED: bit r * 4 + cc: cell (row r, column cc) of this thread is admissible in this tile
+  if constexpr (GUIDED) {
+#pragma unroll
+    for (int k = 0; k < 12; k++) { M[k] = gd.Rt[k]; bad = bad || not_finite(M[k]); }
+    // the finiteness rule depends on the input alone: every element is tested here, whatever tiles the gate drops below
+    const size_t stride = (size_t)gridDim.x * gridDim.y * MT_THREADS;
+    const size_t me = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * MT_THREADS + threadIdx.x;
+    bad = scan_not_finite(fsrc, (size_t)ns * D, me, stride) || bad;
+    bad = scan_not_finite(ftgt, (size_t)nt * D, me, stride) || bad;
+    bad = scan_not_finite(gd.src, (size_t)ns * 3, me, stride) || bad;  // (either layout: 3 ns contiguous floats)
+    bad = scan_not_finite(gd.tgt, (size_t)nt * 3, me, stride) || bad;
+    for (int e = threadIdx.x; e < 3 * MT_ROWS; e += MT_THREADS) {
+      const uint32_t comp = e / MT_ROWS, lr = e % MT_ROWS, row = row0 + lr;
+      sP[comp][lr] = row < ns ? gd.src[(size_t)row * gd.s_elem + (size_t)comp * gd.s_comp] : 0.f;
+    }
+  }
   for (uint32_t tile = tile_lo; tile < tile_hi; tile++) {
     const uint32_t col0 = tile * MT_COLS;
     if (threadIdx.x < MT_COLS) s_col[threadIdx.x] = KEY_NONE;
+    if constexpr (GUIDED) {
+      // (nobody still reads the tile before: its last read of sQ is in front of that tile's OR barrier, which every thread has passed)
+      if (threadIdx.x < 3 * MT_COLS) {
+        const uint32_t comp = threadIdx.x / MT_COLS, lc = threadIdx.x % MT_COLS, col = col0 + lc;
+        sQ[comp][lc] = col < nt ? gd.tgt[(size_t)col * gd.t_elem + (size_t)comp * gd.t_comp] : 0.f;
+      }
+      __syncthreads();  // sQ (and, first tile, sP, the lists' and s_col's initial values) are written
+      // One cell at a time, rolled: unrolled, the 32 independent chains are scheduled side by side and the kernel needs 190 to 230
+      // registers (two waves per SIMD instead of sc_match's three); rolled it stays within the accumulate loop's budget.  The reads
+      // are conflict-free: a wave's 4 rows are 8 words apart, its 16 columns 4 words.
+      adm = 0;
+#pragma unroll 1
+      for (int cell = 0; cell < 32; cell++) {
+        const uint32_t lr = ty * 8 + (cell >> 2), lc = tx * 4 + (cell & 3);
+        // a float <: a NaN or infinite residual is never admissible
+        const bool ok = row0 + lr < ns && col0 + lc < nt &&
+                        resid2(M, sP[0][lr], sP[1][lr], sP[2][lr], sQ[0][lc], sQ[1][lc], sQ[2][lc]) < gd.gate2;
+        adm |= (ok ? 1u : 0u) << cell;
+      }
+      // workgroup-uniform, and every thread passes this barrier on both paths; nothing of a skipped tile is a candidate
+      if (!__syncthreads_or(adm != 0u)) continue;
+    }
     f2 acc[8][2];
 #pragma unroll
     for (int r = 0; r < 8; r++) { acc[r][0] = f2{0.f, 0.f}; acc[r][1] = f2{0.f, 0.f}; }
@@ -101,6 +165,9 @@ __global__ __launch_bounds__(MT_THREADS) void match_dist_kernel(const float* __r
 #pragma unroll
       for (int cc = 0; cc < 4; cc++) {
         if (colb + cc >= nt) continue;
+        if constexpr (GUIDED) {
+          if (!((adm >> (r * 4 + cc)) & 1u)) continue;  // an inadmissible cell offers no key
+        }
         const unsigned long long hi = (unsigned long long)__float_as_uint(v[cc]) << 32;
         const unsigned long long key = hi | (colb + cc);
         const unsigned long long rkey = hi | row;
@@ -135,7 +202,8 @@ __global__ __launch_bounds__(FIN_THREADS) void match_finish_kernel(const unsigne
                                                                    const unsigned long long* __restrict__ colmin,
                                                                    const uint32_t* __restrict__ clean, int32_t* __restrict__ corr,
                                                                    float* __restrict__ d2, uint32_t* __restrict__ count,
-                                                                   MatchGather g, LbArgs lb, uint64_t* host_word) {
+                                                                   MatchGather g, LbArgs lb, uint64_t* host_word, MatchGuide gd,
+                                                                   float* __restrict__ g2) {
   __shared__ uint32_t s_tile;
   __shared__ uint64_t s_scan[FIN_THREADS / 64];
   __shared__ uint64_t s_prefix;
@@ -200,6 +268,17 @@ __global__ __launch_bounds__(FIN_THREADS) void match_finish_kernel(const unsigne
         g.gtgt[3 * slot + c] = g.tgt[(size_t)j * g.t_elem + (size_t)c * g.t_comp];
       }
     }
+    if (g2) {  // sc_match_guided: the gate residual of the entry, the distance launch's chain on the same points
+      float M[12], p[3], q[3];
+#pragma unroll
+      for (int k = 0; k < 12; k++) M[k] = gd.Rt[k];
+#pragma unroll
+      for (int c = 0; c < 3; c++) {
+        p[c] = gd.src[(size_t)i * gd.s_elem + (size_t)c * gd.s_comp];
+        q[c] = gd.tgt[(size_t)j * gd.t_elem + (size_t)c * gd.t_comp];
+      }
+      g2[slot] = resid2(M, p[0], p[1], p[2], q[0], q[1], q[2]);
+    }
   }
   if (tile == gridDim.x - 1 && threadIdx.x == 0) {
     const uint32_t n = ok ? (uint32_t)(pre + tot) : 0u;
@@ -231,23 +310,35 @@ MatchPlan match_plan(uint32_t ns, uint32_t nt, uint32_t knn, float r2) {
 
 uint32_t match_finish_tiles(uint32_t ns) { return (ns + FIN_THREADS - 1) / FIN_THREADS; }
 
-void launch_match_dist(const MatchJob& job, const MatchPlan& plan, uint64_t* part, uint64_t* colmin, uint32_t* clean, hipStream_t st) {
+void launch_match_dist(const MatchJob& job, const MatchPlan& plan, uint64_t* part, uint64_t* colmin, uint32_t* clean, const MatchGuide* gd,
+                       hipStream_t st) {
   const dim3 grid(plan.row_blocks, plan.slices), block(MT_THREADS);
   unsigned long long* p = reinterpret_cast<unsigned long long*>(part);
   unsigned long long* cm = reinterpret_cast<unsigned long long*>(colmin);
+  if (gd) {
+    switch (plan.kp) {
+      case 1: hipLaunchKernelGGL((match_dist_kernel<1, true>), grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean, *gd); break;
+      case 2: hipLaunchKernelGGL((match_dist_kernel<2, true>), grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean, *gd); break;
+      case 3: hipLaunchKernelGGL((match_dist_kernel<3, true>), grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean, *gd); break;
+      default: hipLaunchKernelGGL((match_dist_kernel<4, true>), grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean, *gd); break;
+    }
+    return;
+  }
   switch (plan.kp) {
-    case 1: hipLaunchKernelGGL(match_dist_kernel<1>, grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean); break;
-    case 2: hipLaunchKernelGGL(match_dist_kernel<2>, grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean); break;
-    case 3: hipLaunchKernelGGL(match_dist_kernel<3>, grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean); break;
-    default: hipLaunchKernelGGL(match_dist_kernel<4>, grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean); break;
+    case 1: hipLaunchKernelGGL((match_dist_kernel<1, false>), grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean, NoGuide{}); break;
+    case 2: hipLaunchKernelGGL((match_dist_kernel<2, false>), grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean, NoGuide{}); break;
+    case 3: hipLaunchKernelGGL((match_dist_kernel<3, false>), grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean, NoGuide{}); break;
+    default: hipLaunchKernelGGL((match_dist_kernel<4, false>), grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean, NoGuide{}); break;
   }
 }
 
 void launch_match_finish(const MatchJob& job, const MatchPlan& plan, const uint64_t* part, const uint64_t* colmin, const uint32_t* clean,
-                         int32_t* corr, float* d2, uint32_t* count, const MatchGather& g, LbArgs lb, uint64_t* host_word, hipStream_t st) {
+                         int32_t* corr, float* d2, uint32_t* count, const MatchGather& g, LbArgs lb, uint64_t* host_word, const MatchGuide* gd,
+                         float* g2, hipStream_t st) {
   hipLaunchKernelGGL(match_finish_kernel, dim3(match_finish_tiles(job.ns)), dim3(FIN_THREADS), 0, st,
                      reinterpret_cast<const unsigned long long*>(part), plan.ld_part, plan.slices, plan.kp, job,
-                     reinterpret_cast<const unsigned long long*>(colmin), clean, corr, d2, count, g, lb, host_word);
+                     reinterpret_cast<const unsigned long long*>(colmin), clean, corr, d2, count, g, lb, host_word, gd ? *gd : MatchGuide{},
+                     gd ? g2 : nullptr);
 }
 
 }  // namespace sc
