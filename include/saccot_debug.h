@@ -51,6 +51,8 @@ typedef struct sc_debug {
   uint32_t gram_ref_late;     /* 1: the Gram filter's reference frame is voted after the selection, in a launch of its own (what every path but sc_register / sc_register_device does anyway), instead of by an extra workgroup of stage B's counting pass among the estimating sample's best triangles */
   uint32_t gram_guard_fail;   /* 1: the run-time probe of the matrix pipe's accumulation model reports a violation (tests: the Gram filter must then never be chosen) */
   uint32_t no_lane;           /* 1: a host-free sc_register_device_async frame on a caller's stream is enqueued on that stream (serial with everything else on it) instead of on the context's lane beside it (saccot.h, sc_set_stream); took the struct's tail padding: sizeof(sc_debug) did not change */
+  uint32_t scan_ordinals;     /* 1: stage B's hot path keeps the scan of the per-edge triangle counts between the counting pass and the key kernel (what every other path does anyway) instead of taking the ordinals from the ordered strong list */
+  uint32_t ord_chunk_max;     /* chunks of the ordered strong list the key kernel accepts (0 = 8192): a small value forces that form's overflow fall-back (tests) */
 #ifdef SC_ABLATIONS           /* lab builds only (sac-cot_amd/build.py --ablations): NOT in the product's struct */
   uint32_t filter_variant;    /* body of the filter kernel: 1 .. 3 = bit-identical scheduling variants; >= 16 = timing-only ablations that return WRONG counts */
   uint32_t lab_pad_;
@@ -87,6 +89,8 @@ typedef struct sc_debug_info {
   uint64_t cover_edges, cover_triangles;  /* what the LAST call's launches covered if it was enqueued host-free (0: it waited)  */
   uint64_t n_hostfree_grow;   /* buffers re-allocated inside host-free enqueues (each synchronises the stream: a stall in a stream of frames)  */
   uint64_t n_lane;            /* frames that ran on the context's lane (`lane`)                                              */
+  uint32_t ordinals;          /* where the last call's triangle ordinals came from: 0 = the scan of the per-edge counts, 1 = the ordered strong list (no scan launch), 2 = that form, then — an event or chunk overflow — the scan and the row-walking key kernel after all */
+  uint32_t strong_edges;      /* ordinals != 0: strong edges of the last call's pruned graph (entries of the ordered list)   */
 } sc_debug_info;
 int         sc_debug_last(sc_ctx* ctx, sc_debug_info* out);
 

@@ -207,7 +207,8 @@ class ScDebug(C.Structure):
                 ("no_estimate", C.c_uint32), ("est_margin_pct", C.c_uint32), ("no_fast", C.c_uint32),
                 ("score_filter", C.c_uint32), ("filter_splits", C.c_uint32), ("filter_queue_cap", C.c_uint32),
                 ("filter_lds_queue", C.c_uint32), ("filter_blind", C.c_uint32), ("gram_kappa_q4", C.c_uint32),
-                ("gram_ref_late", C.c_uint32), ("gram_guard_fail", C.c_uint32), ("no_lane", C.c_uint32)]
+                ("gram_ref_late", C.c_uint32), ("gram_guard_fail", C.c_uint32), ("no_lane", C.c_uint32),
+                ("scan_ordinals", C.c_uint32), ("ord_chunk_max", C.c_uint32)]
     _ALIASES = {"cnt_blocks": ("grid_blocks", 0), "keys_blocks": ("grid_blocks", 1), "sel_blocks": ("grid_blocks", 2),
                 "sample_blocks": ("grid_blocks", 3), "tg_count": ("lanes_per_edge", 0), "tg_keys": ("lanes_per_edge", 1),
                 "tg_sample": ("lanes_per_edge", 2), "tg_events": ("lanes_per_edge", 3)}
@@ -230,7 +231,8 @@ class ScDebugInfo(C.Structure):
                 ("gram_rows", C.c_uint32), ("gram_ref", C.c_uint32), ("gram_ref_votes_q8", C.c_uint32),
                 ("us_c2_filter", C.c_float),
                 ("n_frames", C.c_uint64), ("n_fast_ok", C.c_uint64), ("n_fast_repeat", C.c_uint64),
-                ("n_est_ok", C.c_uint64), ("n_est_fail", C.c_uint64), ("cover_edges", C.c_uint64), ("cover_triangles", C.c_uint64), ("n_hostfree_grow", C.c_uint64), ("n_lane", C.c_uint64)]
+                ("n_est_ok", C.c_uint64), ("n_est_fail", C.c_uint64), ("cover_edges", C.c_uint64), ("cover_triangles", C.c_uint64), ("n_hostfree_grow", C.c_uint64), ("n_lane", C.c_uint64),
+                ("ordinals", C.c_uint32), ("strong_edges", C.c_uint32)]
 
 
 class SacCotError(RuntimeError):

@@ -581,11 +581,36 @@ static int run_select(sc_ctx* c, const sc_params* p, const uint32_t* hist, bool 
   StrongList sl{nullptr, nullptr, 0};
   const uint64_t* mbits = g.bits;
   const float* smin = nullptr;
+  // The key kernel runs speculatively (below) in the common form only — events, a-priori select window — and not when every stage
+  // is bracketed by events; spec_cap: the keys the arrays of the earlier calls hold (0: none yet, no speculative pass).
+  uint64_t spec_cap = 0;
+  if (use_events && window_known(p) && !c->pass.timing) {
+    spec_cap = c->wkey.cap / 4 < c->kcol.cap / 8 ? c->wkey.cap / 4 : c->kcol.cap / 8;
+    if (spec) spec_cap = c->pass.mode.M_cov;  // (<= that capacity: fast_plan)
+  }
+  // Exactly those calls, on one rank, take their ordinals from an ORDERED strong list (sc_tri.hip
+  // 2c): no scan of the per-edge counts, the key kernel leaves the triangle count where the scan would.  While the pruning kernel's
+  // grid stays within what a workgroup's prologue sums (C3 does not), and until a call's list had more chunks than the key kernel
+  // holds (sc_ctx::ord_off); sc_debug.scan_ordinals keeps the scan.
+  const bool ord_on = spec_cap != 0 && !c->pass.sharded_ab && hist == nullptr && p->shard_world == 1 &&
+                      !c->tn.scan_ordinals && !c->ord_off && (E + ORD_BLOCK_EDGES - 1) / ORD_BLOCK_EDGES <= ORD_MAX_BLOCKS;
+  c->pass.ord_state = ord_on ? 1 : 0;
+  OrdList ord{};
   if (c->pass.pruned) {
     ControlBlock* ctl = c->ctl.as<ControlBlock>();
     if (use_events) {  // the pruning kernel also compacts the strong edges for the counting pass
       ENSURE(c, c->strong, strong_list_bytes(E));  // (a waited call: run_edges left room)
+      ENSURE(c, c->ord_cnt, ORD_MAX_BLOCKS * sizeof(uint32_t));  // (by every call of the event path: a host-free one finds it)
       sl = StrongList{c->strong.as<uint32_t>(), ctl->st_fill, strong_list_cap(E), 0u};
+    }
+    if (ord_on) {
+      // tloc and ctot live where the scan's offsets would: toff holds 2 E + 2 words, tloc takes E of them, ctot at most E / 4 + 4
+      // from the next multiple of four (E >= 4096), and the count lands in toff[E] as ever
+      uint32_t* words = c->toff.as<uint32_t>();
+      ord.cnt = c->ord_cnt.as<uint32_t>(); ord.tloc = words; ord.ctot = words + ((E + 3) & ~(uint64_t)3);
+      ord.n_strong = &ctl->n_strong; ord.total = c->toff.as<uint64_t>() + E; ord.E = E; ord.E_dev = E_dev;
+      ord.chunk_max = c->tn.ord_chunk_max && c->tn.ord_chunk_max < ORD_CHUNK_MAX ? c->tn.ord_chunk_max : ORD_CHUNK_MAX;
+      sl.cnt = ord.cnt;
     }
     const bool recut = c->pass.sharded_ab && p->shard_world > 1 && use_events;
     // contiguous regions: a rank walks only the regions its own edge range touches (unsharded the modulo form stays: the
@@ -626,38 +651,49 @@ static int run_select(sc_ctx* c, const sc_params* p, const uint32_t* hist, bool 
     }
     launch_tri_count_events(g, mbits, sl, c->pass.build ? nullptr : c->ebi.as<uint32_t>(), c->pass.build ? nullptr : c->ebj.as<uint32_t>(), c->ei.as<uint32_t>(),
                             c->ej.as<uint32_t>(), spec ? c->E_last : E, p->rank_mode, c->tcnt.as<uint32_t>(), ev, c->tn, st, own_range_of(c),
-                            c->ebase.as<uint32_t>(), ref.out ? &ref : nullptr);
+                            c->ebase.as<uint32_t>(), ref.out ? &ref : nullptr, ord_on ? &ord : nullptr);
   } else {
     launch_tri_count(g, mbits, c->es.as<float>(), smin, c->ei.as<uint32_t>(), c->ej.as<uint32_t>(), E,
                      c->tcnt.as<uint32_t>(), own_range_of(c), c->tn, st);
   }
   // read-back #2: triangle count (of the pruned graph when pruning), written to pinned memory by the scan
+  // (ordered strong list: by the key kernel, which makes the ordinals without a scan)
   arm_word(c, HW_TRIANGLES);
   ScanExtra xr;  // sharded: the counts outside this rank's edge range are zero — their tiles are skipped
   xr.range = own_range_of(c);
   // a host-free call on the fused edge kernel: the launches cover E edges, the graph has fewer — the scan skips the tiles beyond
   // them (the pruning kernel's workgroups there have left without writing their counts)
   if (spec && c->pass.build && !c->pass.sharded_ab) xr.range = c->ctl.as<ControlBlock>()->live_edges;
-  SC_TRY(lb_next(c, scan_temp_bytes(E), 0, 0, &xr.lb));
-  launch_scan_u32(c->tcnt.as<uint32_t>(), E, c->toff.as<uint64_t>(), c->scan_tmp.p, c->tn, st, spec ? nullptr : &c->pinned[HW_TRIANGLES], &xr);
+  if (!ord_on) {
+    SC_TRY(lb_next(c, scan_temp_bytes(E), 0, 0, &xr.lb));
+    launch_scan_u32(c->tcnt.as<uint32_t>(), E, c->toff.as<uint64_t>(), c->scan_tmp.p, c->tn, st, spec ? nullptr : &c->pinned[HW_TRIANGLES], &xr);
+  }
   // While the host polls for the count, the key kernel already runs into the key arrays this context holds from earlier
-  // calls (it takes everything else from device memory).  Only in the common form — events, a-priori select window —
-  // and not when every stage is bracketed by events; re-run below if the count outgrew the arrays or a region overflowed.
+  // calls (it takes everything else from device memory); re-run below if the count outgrew the arrays or a region overflowed.
   SelectState* sel = &c->ctl.as<ControlBlock>()->sel;
-  uint64_t spec_cap = 0;
-  if (use_events && window_known(p) && !c->pass.timing) {
-    spec_cap = c->wkey.cap / 4 < c->kcol.cap / 8 ? c->wkey.cap / 4 : c->kcol.cap / 8;
-    if (spec) spec_cap = c->pass.mode.M_cov;  // (<= that capacity: fast_plan)
-    if (spec_cap) {
-      ENSURE(c, c->blk_minmax, 2 * 8192 * 4);
-      launch_tri_keys_events(g, c->es.as<float>(), c->toff.as<uint64_t>(), p->rank_mode, ev, c->wkey.as<uint32_t>(),
-                             c->kcol.as<uint2>(), c->blk_minmax.as<uint32_t>(), sel, select_want(c, p),
-                             &c->ctl.as<ControlBlock>()->klb, E, spec_cap, c->tn, st, !c->pass.sharded_ab);
-    }
+  int chunk_shift = 0;  // an OrdList's chunk: the positions a workgroup of the counting pass takes per trip
+  while ((256 >> chunk_shift) > tri_count_events_lanes(g, c->tn)) chunk_shift++;
+  if (spec_cap) {
+    ENSURE(c, c->blk_minmax, 2 * 8192 * 4);
+    launch_tri_keys_events(g, c->es.as<float>(), c->toff.as<uint64_t>(), p->rank_mode, ev, c->wkey.as<uint32_t>(),
+                           c->kcol.as<uint2>(), c->blk_minmax.as<uint32_t>(), sel, select_want(c, p),
+                           &c->ctl.as<ControlBlock>()->klb, E, spec_cap, c->tn, st, !c->pass.sharded_ab,
+                           ord_on ? &ord : nullptr, chunk_shift, (ord_on && !spec) ? &c->pinned[HW_TRIANGLES] : nullptr);
   }
   // host-free call: no wait — M is what the key arrays and the launches below cover, T_eff the requested T; the kernels
   // read the real count from toff[E] (= the scan's total: the counts of [real E, E) are zero) and sc_wait validates
   if (!spec) SC_TRY(wait_word(c, HW_TRIANGLES));
+  if (ord_on && !spec && (uint32_t)c->pinned[HW_EV_OVERFLOW] != 0) {
+    // an event region was full, or the list has more chunks than the key kernel holds: the row-walking key kernel below needs toff —
+    // the scan runs after all, here and only here, over counts whose weak entries nobody has written yet
+    launch_zero_weak_counts(c->es.as<float>(), smin, E, nullptr, c->tcnt.as<uint32_t>(), st);
+    arm_word(c, HW_TRIANGLES);
+    SC_TRY(lb_next(c, scan_temp_bytes(E), 0, 0, &xr.lb));
+    launch_scan_u32(c->tcnt.as<uint32_t>(), E, c->toff.as<uint64_t>(), c->scan_tmp.p, c->tn, st, &c->pinned[HW_TRIANGLES], &xr);
+    SC_TRY(wait_word(c, HW_TRIANGLES));
+    c->pass.ord_state = 2;
+    if (chunk_overflow(c)) c->ord_off = true;
+  }
   c->pass.M_total = spec ? c->pass.mode.M_cov : (have_total ? c->pinned[HW_TOTAL] : c->pinned[HW_TRIANGLES]);
   const uint64_t M = c->pass.M = spec ? c->pass.mode.M_cov : c->pinned[HW_TRIANGLES];
   if (M == 0) {
@@ -689,10 +725,12 @@ static int run_select(sc_ctx* c, const sc_params* p, const uint32_t* hist, bool 
   bool events_ok = use_events;
   if (!spec && use_events && (uint32_t)c->pinned[HW_EV_OVERFLOW] != 0) {  // a region overflowed: this call walks the rows again
     events_ok = false;
-    uint64_t want_cap = c->ev_capacity * 2;          // every event holds >= 1 triangle, so M bounds the need
-    if (want_cap < M + M / 4) want_cap = M + M / 4;
-    if (want_cap > (1ull << 28)) want_cap = 1ull << 28;
-    c->ev_capacity = want_cap;
+    if (!chunk_overflow(c)) {  // (too many chunks of an ordered strong list: a larger event buffer would not help)
+      uint64_t want_cap = c->ev_capacity * 2;          // every event holds >= 1 triangle, so M bounds the need
+      if (want_cap < M + M / 4) want_cap = M + M / 4;
+      if (want_cap > (1ull << 28)) want_cap = 1ull << 28;
+      c->ev_capacity = want_cap;
+    }
   }
   // weight keys of a graph whose edges all weigh >= 2/3 (0.1 % slack) lie in [2.0, 3.0]: window known a priori
   const bool fast_window = events_ok && window_known(p);
@@ -702,7 +740,8 @@ static int run_select(sc_ctx* c, const sc_params* p, const uint32_t* hist, bool 
   } else if (events_ok) {
     launch_tri_keys_events(g, c->es.as<float>(), c->toff.as<uint64_t>(), p->rank_mode, ev, c->wkey.as<uint32_t>(),
                            c->kcol.as<uint2>(), c->blk_minmax.as<uint32_t>(), sel, fast_window ? (uint64_t)select_want(c, p) : (uint64_t)T_eff,
-                           fast_window ? &c->ctl.as<ControlBlock>()->klb : nullptr, E, M, c->tn, st, !c->pass.sharded_ab);
+                           fast_window ? &c->ctl.as<ControlBlock>()->klb : nullptr, E, M, c->tn, st, !c->pass.sharded_ab,
+                           ord_on ? &ord : nullptr, chunk_shift);  // (ord_on: no overflow here, the lists of the counting pass stand)
   } else {
     launch_tri_keys(g, mbits, smin, c->ebase.as<uint32_t>(), c->ei.as<uint32_t>(), c->ej.as<uint32_t>(),
                     c->es.as<float>(), c->toff.as<uint64_t>(), E, p->rank_mode, c->wkey.as<uint32_t>(),
@@ -889,7 +928,7 @@ const char* sc_last_error(const sc_ctx* c) { return c ? c->last_error.c_str() : 
 int sc_set_debug(sc_ctx* c, const sc_debug* d) {
   if (!c) return SC_EINVAL;
   SC_TRY(busy(c));
-  if (!d) { c->tn = Tuning(); c->fast_ok = false; c->est_failed = false; c->est_holdoff = 0; c->est_failures = 0; return SC_OK; }
+  if (!d) { c->tn = Tuning(); c->fast_ok = false; c->est_failed = false; c->est_holdoff = 0; c->est_failures = 0; c->ord_off = false; return SC_OK; }
   if (d->size != sizeof(sc_debug)) return SC_EINVAL;
   auto tg_ok = [](uint32_t t) { return t == 0 || t == 4 || t == 8 || t == 16 || t == 32 || t == 64; };
   for (int k = 0; k < 4; k++) if (!tg_ok(d->lanes_per_edge[k])) return SC_EINVAL;
@@ -926,13 +965,15 @@ int sc_set_debug(sc_ctx* c, const sc_debug* d) {
   t.gram_guard_fail = d->gram_guard_fail != 0;
   t.no_estimate = d->no_estimate != 0;
   t.no_edge_build = d->no_edge_build != 0;
+  t.scan_ordinals = d->scan_ordinals != 0;
+  t.ord_chunk_max = d->ord_chunk_max;
 #ifdef SC_ABLATIONS
   t.filter_variant = d->filter_variant;  // (lab builds only: most values are timing-only bodies that return WRONG counts)
 #endif
   t.est_margin_pct = d->est_margin_pct;
   c->tn = t;
   c->fast_ok = false;  // (the next call waits: its launch geometry may differ from the last call's)
-  c->est_failed = false; c->est_holdoff = 0; c->est_failures = 0;
+  c->est_failed = false; c->est_holdoff = 0; c->est_failures = 0; c->ord_off = false;
   return SC_OK;
 }
 
@@ -952,6 +993,11 @@ int sc_debug_last(sc_ctx* c, sc_debug_info* out) {
   out->n_est_ok = c->n_est_ok; out->n_est_fail = c->n_est_fail;
   out->cover_edges = c->pass.mode.E_cov; out->cover_triangles = c->pass.mode.M_cov; out->n_hostfree_grow = c->n_spec_grow;
   out->n_lane = c->n_lane;
+  out->ordinals = (uint32_t)c->pass.ord_state; out->strong_edges = 0;
+  if (c->pass.ord_state != 0 && c->ctl.p) {  // (the control block of the last call: zeroed by the next one's staging kernel)
+    HIPCHK(c, hipMemcpyAsync(&out->strong_edges, &c->ctl.as<ControlBlock>()->n_strong, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
   if (c->pass.filter_on && c->fx_state.p)
     HIPCHK(c, filter_read_counters(c->fx_state.p, c->pass.fx_plan, c->stream, &out->filter_undecided, &out->filter_recounts));
   if (c->pass.filter_on && c->pass.filter_mode == 2 && c->fx_frame.p) {
@@ -1471,7 +1517,8 @@ static int finalize_wait(sc_ctx* c, sc_stats* stats) {
                c->pass.params.max_triangles, (uint32_t)c->pinned[HW_EV_OVERFLOW]);
       c->last_error = buf;
       c->fast_ok = false;
-      if ((uint32_t)c->pinned[HW_EV_OVERFLOW] != 0 && c->ev_capacity < (1ull << 28)) c->ev_capacity *= 2;  // (the repeat must not overflow again)
+      if (chunk_overflow(c)) c->ord_off = true;  // (the repeat, and the calls after it, scan the per-edge counts)
+      else if ((uint32_t)c->pinned[HW_EV_OVERFLOW] != 0 && c->ev_capacity < (1ull << 28)) c->ev_capacity *= 2;  // (the repeat must not overflow again)
       return SC_ESPEC;
     }
     c->pass.E = E; c->pass.M = c->pass.M_total = M;

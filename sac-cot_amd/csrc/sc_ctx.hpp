@@ -59,6 +59,7 @@ struct Pass {
   bool regular = false;     // every assumption of the host-free form was met (run_select, finalize_wait): note_completed files it as fast_ok
   bool est_active = false;  // stage B prunes by an estimate
   bool est_void = false;    // ... which could not be verified on the path taken (event overflow): repeat
+  int ord_state = 0;        // stage B's ordinals: 0 from the scan of the per-edge counts, 1 from the ordered strong list (sc_tri.hip 2c), 2 that form, then an overflow's fall-back through the scan (run_select; sc_debug_last)
   int est_state = 0;        // 0 certified bound (or no pruning), 1 estimated and verified: finalize_wait's verdict, read by count_frame
   SamplePlan plan{false, 1u, 0};
   // stage C2's reference frame (sc_gramref.hpp): on the hot path the estimating sample leaves candidate triangles behind (ref_cand_n of
@@ -97,7 +98,7 @@ struct Frame {
 struct Workspace {
   Buf in_src, in_tgt, planes, S, bits, deg, degp, wpre, ebase, edge_off, scan_tmp, ei, ej, es, ebi, ebj, tcnt, toff, wkey, kcol, ctl, events, blk_gt,
       blk_eq, blk_minmax, bits2, off_gt, off_eq, sel_ord, sel_key, sortkey, sorted, sort_tmp, tri, tri_rk, key_rk, rt, rt_aos, partial, cnt, key, rt12,
-      mask, refine_tmp, amx_pairs, strong, rowcost, cost_pre, lb_state, lb_ticket, fx_tile, fx_state, fx_mx, fx_part, fx_coef, guard_tmp, fx_frame, ref_cand,
+      mask, refine_tmp, amx_pairs, strong, ord_cnt, rowcost, cost_pre, lb_state, lb_ticket, fx_tile, fx_state, fx_mx, fx_part, fx_coef, guard_tmp, fx_frame, ref_cand,
       // sc_peel / sc_register_instances: allocated by the first round, never by a frame.  peel_cnt: a round's scores — the frame's own stay
       // in `cnt`, where sc_polish reads them whether or not rounds have run
       peel_planes, peel_claimed, peel_words, peel_label, peel_cnt,
@@ -209,6 +210,9 @@ struct sc_ctx : sc::Workspace {  // (the workspace buffers are direct members to
   // C2 call) for the rest of its life; now the k-th failure costs 64 << min(k - 1, 6) certifying calls, then the context estimates
   // again: a stream whose estimates always fail wastes one repeated call in 4096.
   uint32_t est_holdoff = 0, est_failures = 0;
+  // a call's ordered strong list (sc_tri.hip 2c) had more chunks than the key kernel holds and fell back through the scan: the context
+  // takes the scan form from then on — such a graph would overflow again (sc_set_debug resets)
+  bool ord_off = false;
   // the coordinate maxima and boxes the staging kernel of the last completed call published (use_filter): what a host-free call
   // picks stage C2's kernel by when it is enqueued before its own staging kernel has run — a second frame in flight on the stream
   uint64_t mx_last = ~0ull, box_last[6] = {0, 0, 0, 0, 0, 0};
@@ -242,6 +246,8 @@ int rec(sc_ctx* c, int i);
 float ev_us(sc_ctx* c, int a, int b);
 constexpr uint64_t PIN_PENDING = ~0ull;  // a host word whose kernel has not delivered yet (wait_word polls it)
 inline void arm_word(sc_ctx* c, HostWord w) { c->pinned[w] = PIN_PENDING; }
+// HW_EV_OVERFLOW's high half: the overflow (low half) was the ordered strong list's chunk count, not — or not only — an event region
+inline bool chunk_overflow(const sc_ctx* c) { return (c->pinned[HW_EV_OVERFLOW] >> 32) != 0; }
 int wait_word(sc_ctx* c, HostWord idx);
 // "who: what" into last_error; the status of a refused call
 inline int refuse(sc_ctx* c, const char* who, const char* what) {

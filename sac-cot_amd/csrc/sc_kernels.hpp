@@ -59,6 +59,8 @@ struct Tuning {
   bool gram_guard_fail = false;    // the matrix-pipe probe reports a violation (tests of the guard)
   bool filter_blind = false;       // the host decides C2's kernel WITHOUT the coordinate maxima (as if they had not arrived yet)
   bool compat_one_phase = false;   // exact chain on every pair of an interior tile
+  bool scan_ordinals = false;      // stage B's hot path keeps the scan of the per-edge counts (no ordered strong list: sc_tri.hip 2c)
+  uint32_t ord_chunk_max = 0;      // chunks of the ordered strong list the key kernel accepts (0: ORD_CHUNK_MAX; tests force the fallback with a small one)
   int compat_rows = 0;             // tile height of stage A: 0 = by size (16 below 10 000 correspondences, 32 from there), 16, 32, 64
   uint32_t compat_store_mode = 0;  // 0: by size; bit 0: force 4-byte S stores, bit 2: force 16-byte, bit 1: non-temporal
 };
@@ -211,6 +213,10 @@ struct StrongList {
   // blocks (256 edges each), so a region is a contiguous range of edge ids — a rank of the sharded stage B then walks only the
   // regions its own edge range touches (the pruning kernel also zeroes every tcnt entry in this form)
   uint32_t region_blocks;
+  // != nullptr: the ORDERED form (sc_tri.hip 2c; region_blocks == 0, one rank, at most ORD_MAX_BLOCKS blocks).  Block b writes its
+  // strong edges in ascending order into its own slot list[ORD_BLOCK_EDGES b ..] and their number into cnt[b]: no atomic, and the slots'
+  // runs one after the other are the strong edges in edge order.  fill is not touched, and no tcnt entry is zeroed.
+  uint32_t* cnt = nullptr;
 };
 uint32_t strong_list_cap(uint64_t E);
 size_t strong_list_bytes(uint64_t E);
@@ -273,10 +279,28 @@ struct EventList {
   uint32_t* b;       // weight ranking: ebase[j]
   uint32_t* e;       // edge index
   uint32_t* rb;      // rank of the word's first triangle inside its edge
+  uint32_t* x;       // position of the edge in the flat ordered strong list (written with an OrdList only)
   uint32_t* fill;    // EV_SHARDS counters
   uint64_t shard_cap;
   uint32_t* overflow;  // host-pinned flag, set when a region is full
   int W;
+};
+// Ordinals from the ORDERED strong list (sc_tri.hip 2c): no scan of the per-edge counts between the counting pass and the key kernel.
+// The counting pass takes the flat list in chunks of 256 / (lanes per edge) consecutive positions per workgroup and trip; it leaves
+// tloc[x] = triangles of the earlier edges of x's chunk and ctot[c] = triangles of chunk c, and every workgroup of the key kernel
+// makes the prefix over the chunk totals by itself.  cnt == nullptr: off (tcnt -> scan -> toff).
+constexpr uint32_t ORD_BLOCK_EDGES = 1024;  // edges a block of the pruning kernel takes in this form: its slot of the list
+constexpr uint32_t ORD_MAX_BLOCKS = 1024;   // ... and the blocks whose counts a workgroup's prologue sums, four per thread (one 16-byte load)
+constexpr uint32_t ORD_CHUNK_MAX = 8192;   // chunk totals a workgroup of the key kernel holds (LDS, u32: ordinals below 2^32 are a precondition of the path)
+struct OrdList {
+  uint32_t* cnt = nullptr;      // StrongList::cnt (ORD_MAX_BLOCKS entries; only those of the blocks that hold a live edge are read)
+  uint32_t* tloc = nullptr;     // one entry per position of the flat strong list
+  uint32_t* ctot = nullptr;     // one entry per chunk
+  uint32_t* n_strong = nullptr; // ControlBlock::n_strong: strong edges, written by the counting pass
+  uint64_t* total = nullptr;    // where the scan would leave the triangle count (toff[E]): written by workgroup 0 of the key kernel
+  uint64_t E = 0;               // edges the launches cover ...
+  const uint64_t* E_dev = nullptr;  // ... and (host-free calls) the edges there are
+  uint32_t chunk_max = ORD_CHUNK_MAX;
 };
 struct GramRefJob;
 size_t event_bytes(uint64_t capacity);
@@ -287,7 +311,12 @@ void launch_tri_count_events(const Graph& g, const uint64_t* mbits, const Strong
                              uint32_t* tcnt, const EventList& ev, const Tuning& tn, hipStream_t st,
                              const uint64_t* own = nullptr,   // own (optional, device): [lo, hi) of the edges this rank enumerates
                              const uint32_t* ebase = nullptr,  // with ebi == ebj == nullptr: the per-row CSR bases (launch_edge_build)
-                             const GramRefJob* ref = nullptr); // one extra workgroup votes for stage C2's reference frame (sc_gramref.hpp)
+                             const GramRefJob* ref = nullptr,  // one extra workgroup votes for stage C2's reference frame (sc_gramref.hpp)
+                             const OrdList* ord = nullptr);    // the strong list is ordered (sl.cnt): also leave what the key kernel makes the ordinals from
+// lanes per edge launch_tri_count_events uses (a chunk of an OrdList is 256 / this many positions)
+int tri_count_events_lanes(const Graph& g, const Tuning& tn);
+// tcnt[e] = 0 for the edges below *smin: what the pruning kernel leaves out in the ordered form, for the scan of an overflow's fall-back
+void launch_zero_weak_counts(const float* es, const float* smin, uint64_t E, const uint64_t* E_dev, uint32_t* tcnt, hipStream_t st);
 
 // Radix-select state.  Lives in the context's control block, which the staging kernel zeroes per call.
 // r05: no workgroup of a select round stays behind to "pick": a round only adds its keys into hist[r], and the NEXT launch —
@@ -329,7 +358,8 @@ struct ControlBlock {
   uint32_t klb;              // key of the certified lower bound of the pruning (0: none)
   uint32_t pad_fin[2];
   uint32_t own_row[2];       // sharded stage B: this rank's row range [lo, hi) ...
-  uint32_t pad0[9];
+  uint32_t n_strong;         // ordered strong list (OrdList): strong edges, written by the counting pass
+  uint32_t pad0[8];
   uint64_t key2[2];          // internal winner key pair (sc_register_device)
   unsigned long long fin_word;  // finalize_kernel: workgroups finished << 32 | rank count so far — ONE returning atomic per workgroup (left zero)
   uint64_t own_edge[2];      // ... and its CSR edge range (launch_shard_split)
@@ -352,7 +382,9 @@ void launch_tri_keys(const Graph& g, const uint64_t* mbits, const float* smin, c
 void launch_tri_keys_events(const Graph& g, const float* es, const uint64_t* toff, int rank_mode,
                             const EventList& ev, uint32_t* wkey, uint2* kcol, uint32_t* blk_minmax,
                             SelectState* s, uint64_t want, const uint32_t* klb, uint64_t E, uint64_t cap,
-                            const Tuning& tn, hipStream_t st, bool check_bound = false);  // cap: entries of wkey / kcol (writes beyond are dropped); want is clipped to toff[E]
+                            const Tuning& tn, hipStream_t st, bool check_bound = false,  // cap: entries of wkey / kcol (writes beyond are dropped); want is clipped to toff[E]
+                            const OrdList* ord = nullptr, int chunk_shift = 0,  // ordinals from the ordered strong list (toff unused); chunk = 1 << chunk_shift positions
+                            uint64_t* host_total = nullptr);  // (with ord) pinned word that receives the triangle count, as the scan's would
 // check_bound: with a pruning bound in *klb the select must find `want` keys at or above it (SelectState::want_req)
 // klb != nullptr (weight ranking, every edge weight >= 2/3): the kernel presets the select window to
 // [*klb or 2.0, 3.0] and no key-range pass runs; two select rounds then always suffice.
@@ -575,7 +607,7 @@ enum HostWord : int {
   HW_BAD_INPUT = 1,     // non-finite input coordinate.  Cleared by stage_inputs, set (low half) by the staging kernel, read by run_edges / finalize_wait / the hooks
   HW_TRIANGLES = 2,     // triangle count (of the pruned graph when pruning).  Armed and polled by run_select, written by the scan of the counts
   HW_TOTAL = 4,         // 3-cliques of the unpruned graph (SC_FLAG_EXACT_TOTAL).  Written by its scan in run_edges, read by run_select behind HW_TRIANGLES
-  HW_EV_OVERFLOW = 5,   // an event-list region was full.  Cleared by run_select, set (low half) by the counting pass, read by run_select / finalize_wait
+  HW_EV_OVERFLOW = 5,   // an event-list region was full.  Cleared by run_select, set (low half) by the counting pass, read by run_select / finalize_wait; high half: the ordered strong list had too many chunks (chunk_overflow)
   HW_MERGED_T = 6,      // sharded select: merged T_eff.  Armed and polled by sc_shard_score_device, written by merge_prepare ...
   HW_MERGED_M = 7,      // ... together with the number of candidates merged (written before HW_MERGED_T)
   HW_WINNER = 8,        // the winner's key: the last word a call writes.  Armed by finalize_enqueue, written by the finalize kernel, polled by finalize_wait

@@ -13,6 +13,7 @@
 // Everything is integer / bit work except the two fp32 adds of the key; results do not depend on grid size
 // or on the order atomics land in (atomics are only used for commutative integer sums, min and max).
 #include <cstring>
+#include <type_traits>
 
 #include "sc_arith.hpp"
 #include "sc_block.hpp"
@@ -440,7 +441,18 @@ constexpr int EV_SHARDS = 1024;  // ~26 k flushes per call on C2: with 256 count
 // Shapes measured and rejected (C2 unless noted): workgroup staging with two barriers per trip (48 us, and it overflows
 // into per-event global atomics at W = 313: 4.7 ms on C3), per-wave staging with a global-atomic overflow path
 // (235 us), per-group staging (118 us), a one-round-per-iteration state machine with software prefetch (98 us).
-template <int TG>
+//
+// 2c. ORD — ordinals from an ORDERED strong list, without the scan of the per-edge counts.  A triangle's ordinal is (triangles of the
+// earlier edges, in edge order) + (its rank inside its edge), and only strong edges carry triangles.  The pruning kernel's block b
+// (ORD_BLOCK_EDGES consecutive edges) leaves its strong edges in ascending order in its own slot and their number in cnt[b] (StrongList::cnt), so the flat list — the
+// slots' runs one after the other — is in edge order.  A workgroup takes 256 / TG consecutive positions of it per trip: chunk
+// bid + trip * nblk.  At the end of a trip it scans its groups' counts (wave shuffles, four LDS words, one barrier; the rounds loop
+// stays barrier-free) and stores tloc[x], the triangles of the chunk's earlier edges, and ctot[chunk]; an event carries x.  Every
+// workgroup of the key kernel then makes the exclusive prefix over the chunk totals in its prologue (as select_resolve does with a
+// histogram) and a key lands at cpre[x / chunk] + tloc[x] + rank.  The same numbers as toff[e] + rank: same edge order, same rank.
+// Every entry of cnt / tloc / ctot that is read was written by this call (reads are bounded by the live blocks and by S): nothing
+// to clear.  tcnt[e] is still written for the strong edges: the fall-back of an overflow scans it (launch_zero_weak_counts first).
+template <int TG, bool ORD>
 __global__ __launch_bounds__(256) void tri_count_events_kernel(const uint64_t* __restrict__ mbits, int W,
                                                                const uint32_t* __restrict__ deg,
                                                                const uint32_t* __restrict__ ebi,
@@ -450,7 +462,8 @@ __global__ __launch_bounds__(256) void tri_count_events_kernel(const uint64_t* _
                                                                StrongList sl, int rank_mode,
                                                                uint32_t* __restrict__ tcnt, EventList ev,
                                                                const uint64_t* __restrict__ own,
-                                                               const uint32_t* __restrict__ ebase, GramRefJob ref) {
+                                                               const uint32_t* __restrict__ ebase, GramRefJob ref,
+                                                               OrdList ord) {
   // ref (ref.out != null): workgroup 0 is a RIDER — it does none of this kernel's work but votes for the reference frame of
   // stage C2's Gram filter among the candidate triangles the estimating sample left behind (sc_gramref.hpp): ~10 us of one
   // workgroup's latency that would otherwise stand between the selection and the Kabsch launch, hidden under this launch
@@ -462,13 +475,37 @@ __global__ __launch_bounds__(256) void tri_count_events_kernel(const uint64_t* _
   constexpr int EVW = 192;  // records per wave segment: flush above 128, a round adds <= 64
   __shared__ uint64_t l_m[4 * EVW];
   __shared__ uint32_t l_wi[4 * EVW], l_wj[4 * EVW], l_a[4 * EVW], l_b[4 * EVW], l_e[4 * EVW], l_rb[4 * EVW];
-  __shared__ uint32_t l_pre[ST_SHARDS + 1];  // exclusive prefix of the strong-list region fills
+  __shared__ uint32_t l_pre[ORD ? ORD_MAX_BLOCKS + 1 : ST_SHARDS + 1];  // exclusive prefix of the strong-list region fills (ORD: of the pruning kernel's block counts)
+  __shared__ uint32_t l_x[ORD ? 4 * EVW : 1];                // ORD: the events' list positions
+  __shared__ uint32_t l_wtot[2][4];                          // ORD: the waves' triangle counts of a trip (double-buffered: one barrier per trip)
   static_assert(sizeof(l_m) >= GX_REF_LDS_WORDS * sizeof(float), "the rider borrows the event staging area");
   if (rider && blockIdx.x == 0) { gram_ref_block(ref, reinterpret_cast<float*>(l_m)); return; }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int gl = threadIdx.x & (TG - 1);
   static_assert(ST_SHARDS == 256, "one region per thread");
-  {
+  if constexpr (ORD) {
+    // the blocks of the pruning kernel that hold a live edge (a host-free call's grid covers more, and what lies beyond was not
+    // written by this call; a graph that outgrew the cover: nothing was listed at all)
+    static_assert(ORD_MAX_BLOCKS == 4 * 256, "four blocks per thread");
+    __shared__ uint64_t plds[8];
+    const uint64_t Ea = ord.E_dev ? (*ord.E_dev > ord.E ? 0ull : *ord.E_dev) : ord.E;
+    const uint32_t nlive = (uint32_t)min((Ea + ORD_BLOCK_EDGES - 1) / ORD_BLOCK_EDGES, (uint64_t)ORD_MAX_BLOCKS);
+    const uint4 t4 = reinterpret_cast<const uint4*>(ord.cnt)[threadIdx.x];
+    const uint32_t b0 = threadIdx.x * 4;
+    const uint32_t v0 = b0 < nlive ? t4.x : 0u, v1 = b0 + 1 < nlive ? t4.y : 0u, v2 = b0 + 2 < nlive ? t4.z : 0u, v3 = b0 + 3 < nlive ? t4.w : 0u;
+    uint64_t tot;
+    const uint32_t run = (uint32_t)block_exscan_u64((uint64_t)v0 + v1 + v2 + v3, plds, &tot);
+    l_pre[b0] = run; l_pre[b0 + 1] = run + v0; l_pre[b0 + 2] = run + v0 + v1; l_pre[b0 + 3] = run + v0 + v1 + v2;
+    if (threadIdx.x == 0) {
+      l_pre[ORD_MAX_BLOCKS] = (uint32_t)tot;
+      if (bid == 0) {
+        *ord.n_strong = (uint32_t)tot;
+        // more chunks than a workgroup of the key kernel holds: as if an event region were full (the host walks the rows again);
+        // the word's high half says why, so that the context keeps the scan form from then on instead of growing its event buffer
+        if ((tot + (256 / TG) - 1) / (256 / TG) > ord.chunk_max) { ev.overflow[0] = 1u; ev.overflow[1] = 1u; }
+      }
+    }
+  } else {
     __shared__ uint64_t plds[8];
     const uint64_t v = sl.fill[threadIdx.x];
     uint64_t tot;
@@ -476,7 +513,7 @@ __global__ __launch_bounds__(256) void tri_count_events_kernel(const uint64_t* _
     if (threadIdx.x == 0) l_pre[ST_SHARDS] = (uint32_t)tot;
   }
   __syncthreads();
-  const uint64_t S = l_pre[ST_SHARDS];  // strong edges (only they can carry a triangle of the pruned graph)
+  const uint64_t S = l_pre[ORD ? ORD_MAX_BLOCKS : ST_SHARDS];  // strong edges (only they can carry a triangle of the pruned graph)
   // the part of the flat list this rank walks: everything, or — regions being contiguous edge ranges — the regions its own
   // edge range touches (the others' tcnt entries were zeroed by the pruning kernel)
   uint64_t x0 = 0, x1 = S;
@@ -516,6 +553,7 @@ __global__ __launch_bounds__(256) void tri_count_events_kernel(const uint64_t* _
         const int q = wbase + (int)(start + k);
         ev.m[o] = l_m[q]; ev.wi[o] = l_wi[q]; ev.wj[o] = l_wj[q]; ev.a[o] = l_a[q]; ev.b[o] = l_b[q];
         ev.e[o] = l_e[q]; ev.rb[o] = l_rb[q];
+        if constexpr (ORD) ev.x[o] = l_x[q];
       }
       start += fit;
       shard = (shard + 1u) & (EV_SHARDS - 1);
@@ -529,10 +567,10 @@ __global__ __launch_bounds__(256) void tri_count_events_kernel(const uint64_t* _
     uint32_t e = 0, rowi = 0, rowj = 0, fa = 0, fb = 0, c = 0;
     int w0 = 0, jbit = 0, rounds = 0;
     if (on) {
-      int r = 0;  // region of x: the largest r with l_pre[r] <= x
+      int r = 0;  // region of x: the largest r with l_pre[r] <= x (ORD: the pruning kernel's block; empty ones are skipped)
 #pragma unroll
-      for (int step = ST_SHARDS / 2; step > 0; step >>= 1) r += (l_pre[r + step] <= (uint32_t)x) ? step : 0;
-      e = sl.list[(uint64_t)r * sl.cap + ((uint32_t)x - l_pre[r])];
+      for (int step = (ORD ? ORD_MAX_BLOCKS : ST_SHARDS) / 2; step > 0; step >>= 1) r += (l_pre[r + step] <= (uint32_t)x) ? step : 0;
+      e = sl.list[(uint64_t)r * (ORD ? ORD_BLOCK_EDGES : sl.cap) + ((uint32_t)x - l_pre[r])];
       if (!own || ((uint64_t)e >= own[0] && (uint64_t)e < own[1])) {
         const uint32_t i = ei[e], j = ej[e];
         rowi = i * (uint32_t)W; rowj = j * (uint32_t)W;
@@ -555,6 +593,7 @@ __global__ __launch_bounds__(256) void tri_count_events_kernel(const uint64_t* _
           const int q = wbase + (int)scnt + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32),
                                                    __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
           l_m[q] = m; l_wi[q] = rowi + w; l_wj[q] = rowj + w; l_a[q] = fa; l_b[q] = fb; l_e[q] = e; l_rb[q] = rb;
+          if constexpr (ORD) l_x[q] = (uint32_t)x;
         }
         scnt += (uint32_t)__popcll(bal);
         if (scnt > (uint32_t)(EVW - 64)) flush();
@@ -581,12 +620,25 @@ __global__ __launch_bounds__(256) void tri_count_events_kernel(const uint64_t* _
         take(m, w);
       }
     }
-    if (gl == 0 && on) tcnt[e] = c;  // weak edges were zeroed by prune_bits_kernel
+    if (gl == 0 && on) tcnt[e] = c;  // weak edges were zeroed by prune_bits_kernel (ORD: by nobody — only an overflow's fall-back reads tcnt)
+    if constexpr (ORD) {  // the chunk's exclusive prefix over its groups' counts, and its total (trips is the same in every wave)
+      const uint32_t inc = wave_inscan<uint32_t>(gl == 0 ? c : 0u);  // (c is 0 in an idle group)
+      if (lane == 63) l_wtot[trip & 1][wave] = inc;
+      __syncthreads();
+      uint32_t base = 0, tot = 0;
+#pragma unroll
+      for (int w = 0; w < 4; w++) { const uint32_t t = l_wtot[trip & 1][w]; base += w < wave ? t : 0u; tot += t; }
+      if (gl == 0 && on) ord.tloc[x] = base + inc - c;
+      const uint64_t chunk = (x0 + (uint64_t)bid * (256 / TG) + trip * groups) / (256 / TG);  // = bid + trip * nblk
+      if (threadIdx.x == 0 && chunk * (256 / TG) < x1) ord.ctot[chunk] = tot;
+    }
   }
   if (scnt) flush();
 }
 
-// one lane per event
+// one lane per event.  ORD (2c): the ordinals come from the ordered strong list — cpre[x / chunk] + tloc[x] + rank, cpre made here —
+// and workgroup 0 leaves the triangle count where the scan would (ord.total = toff[E]; host_total: the word a waited call polls)
+template <bool ORD>
 __global__ __launch_bounds__(256) void tri_keys_events_kernel(const uint64_t* __restrict__ bits,
                                                               const uint32_t* __restrict__ wpre,
                                                               const uint32_t* __restrict__ deg,
@@ -598,11 +650,58 @@ __global__ __launch_bounds__(256) void tri_keys_events_kernel(const uint64_t* __
                                                               uint32_t* __restrict__ blk_max,
                                                               SelectState* __restrict__ preset,
                                                               const uint32_t* __restrict__ klb, uint64_t want,
-                                                              uint64_t E, uint64_t cap, int check_bound) {
+                                                              uint64_t E, uint64_t cap, int check_bound, OrdList ord,
+                                                              int chunk_shift, uint64_t* __restrict__ host_total) {
   // cap: entries wkey / kcol hold.  The host may launch this kernel BEFORE it knows the triangle count (into the
   // arrays of the previous call, while it polls for the count): writes beyond cap are dropped and the host re-runs.
   // For the same reason `want` is clipped here to the count the scan left in toff[E].
-  __shared__ uint64_t pre[EV_SHARDS + 1];
+  // (ORD: 32-bit — the event buffer holds at most 2^28 records — so that four workgroups' LDS still fit a CU beside cpre)
+  using pre_t = typename std::conditional<ORD, uint32_t, uint64_t>::type;
+  __shared__ pre_t pre[EV_SHARDS + 1];
+  __shared__ uint32_t cpre[ORD ? ORD_CHUNK_MAX : 1];  // ORD: exclusive prefix of the chunk totals
+  uint64_t triangles = 0;  // what the scan leaves in toff[E]
+  if constexpr (ORD) {
+    // wave w scans the chunk totals [w per, (w + 1) per), 64 at a time — coalesced loads, four in flight, conflict-free LDS stores —
+    // and then adds the sum of the waves before it.  More chunks than cpre holds: the counting pass has raised the overflow flag —
+    // the ordinals below are void (in bounds: writes beyond cap are dropped) and workgroup 0 adds the rest to the count in a loop
+    static_assert(ORD_CHUNK_MAX == 4 * 2048, "four waves, at most 2048 chunks each");
+    __shared__ uint64_t plds[8];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t S = *ord.n_strong;
+    const uint32_t nch = (uint32_t)(((uint64_t)S + (1u << chunk_shift) - 1) >> chunk_shift);
+    const uint32_t lim = min(ord.chunk_max, ORD_CHUNK_MAX), nchc = min(nch, lim);
+    const uint32_t per = (nchc + 255) / 256 * 64, lo = min((uint32_t)wave * per, nchc), hi = min(lo + per, nchc);
+    uint64_t carry = 0;
+    for (uint32_t i0 = lo; i0 < hi; i0 += 256) {
+      uint32_t v[4];
+#pragma unroll
+      for (int u = 0; u < 4; u++) { const uint32_t i = i0 + 64 * u + lane; v[u] = i < hi ? ord.ctot[i] : 0u; }
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        const uint32_t i = i0 + 64 * u + lane;
+        const uint32_t inc = wave_inscan<uint32_t>(v[u]);
+        if (i < hi) cpre[i] = (uint32_t)carry + inc - v[u];
+        carry += (uint32_t)__shfl(inc, 63);
+      }
+    }
+    if (lane == 0) plds[wave] = carry;
+    __syncthreads();
+    uint64_t base = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < 4; w++) { const uint64_t t = plds[w]; base += w < wave ? t : 0ull; tot += t; }
+    if (wave) for (uint32_t i = lo + lane; i < hi; i += 64) cpre[i] += (uint32_t)base;
+    if (blockIdx.x == 0 && nch > nchc) {  // (an overflow: the count is still exact; uniform over the workgroup)
+      uint64_t rest = 0;
+      for (uint32_t k = nchc + threadIdx.x; k < nch; k += 256) rest += ord.ctot[k];
+      __syncthreads();
+      tot += block_reduce_u64(rest, plds);
+    }
+    triangles = tot;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      *ord.total = tot;
+      if (host_total) publish_host(host_total, tot);
+    }
+  }
   // Weight keys of a graph whose edges all weigh >= 2/3 live in one binade, [2.0, 3.0]: the select window is known
   // before a single key exists — [certified bound (or 2.0), 3.0] — so no key-range pass, and two 12-bit rounds
   // always resolve it.  (Keys below a certified bound cannot be among the `want` largest: sc_tri.hip 3b.)
@@ -610,7 +709,7 @@ __global__ __launch_bounds__(256) void tri_keys_events_kernel(const uint64_t* __
     const uint32_t lo = *klb ? *klb : 0x40000000u, hi = 0x40400000u;  // 2.0f, 3.0f
     const uint32_t range_m1 = hi - lo;
     preset->kmin = lo; preset->kmax = hi;
-    preset->st[0] = SelSnap{lo, range_m1 == 0 ? 0u : (uint32_t)(32 - __builtin_clz(range_m1)), 1u, 0u, min(want, (uint64_t)toff[E]), 0ull, 0ull, 0ull};
+    preset->st[0] = SelSnap{lo, range_m1 == 0 ? 0u : (uint32_t)(32 - __builtin_clz(range_m1)), 1u, 0u, min(want, ORD ? triangles : (uint64_t)toff[E]), 0ull, 0ull, 0ull};
     // a pruning bound promises `want` keys at or above it — a certified one by construction, an ESTIMATED one (3c) unless
     // it was set too high: whoever resolves the select's first round compares (the UNclipped want: a pruned graph with fewer triangles than
     // that proves nothing about the full one)
@@ -625,8 +724,8 @@ __global__ __launch_bounds__(256) void tri_keys_events_kernel(const uint64_t* __
     uint64_t tot;
     uint64_t run = block_exscan_u64(mine, plds, &tot);
 #pragma unroll
-    for (int k = 0; k < PT; k++) { pre[threadIdx.x * PT + k] = run; run += f[k]; }
-    if (threadIdx.x == 0) pre[EV_SHARDS] = tot;
+    for (int k = 0; k < PT; k++) { pre[threadIdx.x * PT + k] = (pre_t)run; run += f[k]; }
+    if (threadIdx.x == 0) pre[EV_SHARDS] = (pre_t)tot;
     __syncthreads();
   }
   uint32_t kmin = 0xFFFFFFFFu, kmax = 0;
@@ -639,7 +738,13 @@ __global__ __launch_bounds__(256) void tri_keys_events_kernel(const uint64_t* __
       const uint64_t o = (uint64_t)sh * ev.shard_cap + (x - pre[sh]);
       uint64_t m = ev.m[o];
       const uint32_t wi = ev.wi[o], wj = ev.wj[o], fa = ev.a[o], e = ev.e[o];
-      uint64_t out = toff[e] + ev.rb[o];
+      uint64_t out;
+      if constexpr (ORD) {
+        const uint32_t xs = ev.x[o];
+        out = (uint64_t)cpre[min(xs >> chunk_shift, ORD_CHUNK_MAX - 1)] + ord.tloc[xs] + ev.rb[o];
+      } else {
+        out = toff[e] + ev.rb[o];
+      }
       const uint32_t kbase = (uint32_t)(wi % (uint32_t)ev.W) * 64u;  // column index of bit 0 of this word
       if (rank_mode == 0) {
         const uint32_t fb = ev.b[o];
@@ -678,7 +783,7 @@ __global__ __launch_bounds__(256) void tri_keys_events_kernel(const uint64_t* __
   block_minmax_store(kmin, kmax, blk_min, blk_max);
 }
 
-size_t event_bytes(uint64_t capacity) { return (size_t)capacity * 32 + EV_SHARDS * 4 + 64; }
+size_t event_bytes(uint64_t capacity) { return (size_t)capacity * 36 + EV_SHARDS * 4 + 64; }
 
 EventList event_list(void* buf, uint64_t capacity, int W, uint32_t* fill, uint32_t* overflow_host) {
   EventList ev;
@@ -691,6 +796,7 @@ EventList event_list(void* buf, uint64_t capacity, int W, uint32_t* fill, uint32
   ev.b = reinterpret_cast<uint32_t*>(p); p += cap * 4;
   ev.e = reinterpret_cast<uint32_t*>(p); p += cap * 4;
   ev.rb = reinterpret_cast<uint32_t*>(p); p += cap * 4;
+  ev.x = reinterpret_cast<uint32_t*>(p); p += cap * 4;
   ev.fill = fill;  // EV_SHARDS zeroed counters (control block)
   ev.shard_cap = cap / EV_SHARDS;
   ev.overflow = overflow_host;
@@ -701,14 +807,14 @@ EventList event_list(void* buf, uint64_t capacity, int W, uint32_t* fill, uint32
 void launch_tri_count_events(const Graph& g, const uint64_t* mbits, const StrongList& sl, const uint32_t* ebi,
                              const uint32_t* ebj, const uint32_t* ei, const uint32_t* ej, uint64_t E, int rank_mode,
                              uint32_t* tcnt, const EventList& ev, const Tuning& tn, hipStream_t st, const uint64_t* own,
-                             const uint32_t* ebase, const GramRefJob* ref) {
+                             const uint32_t* ebase, const GramRefJob* ref, const OrdList* ord) {
   if (E == 0) return;
   // lanes per edge: a lane walks (W - j / 64) / TG words one dependent round after the other, so wide rows want wide
   // groups (Tuning::tg_events forces one; measured r02: see DESIGN.md)
   // r04c, on the pruned graph (a third of the triangles of r03's: shorter walks, more edges per wave pay): 4 lanes between 65 and 128
   // words — C2 (79): stage B's bracket 101.5 -> 99.4 us in eight alternating pairs of runs, C4 (79): 138.6 vs 138.5 — but not
   // below: C1 (32 words) 68.3 -> 69.7 us with 4
-  int tg = tn.tg_events ? tn.tg_events : (g.W <= 64 ? 8 : (g.W <= 128 ? 4 : (g.W <= 512 ? 16 : 32)));
+  const int tg = tri_count_events_lanes(g, tn);
   const uint64_t per = 256 / tg;
   // the strong edges are a fraction of E that only the device knows (20 - 45 % on C1 .. C4): size the grid for ~E/3
   uint64_t nb = (E / 3 + per - 1) / per;
@@ -717,20 +823,50 @@ void launch_tri_count_events(const Graph& g, const uint64_t* mbits, const Strong
   if (tn.cnt_blocks >= 1 && tn.cnt_blocks <= 65535) nb = tn.cnt_blocks;
   const GramRefJob rj = ref ? *ref : GramRefJob{};
   if (rj.out) nb++;  // (workgroup 0 is the rider)
-#define SC_LAUNCH_CE(TGV) hipLaunchKernelGGL(tri_count_events_kernel<TGV>, dim3((unsigned)nb), dim3(256), 0, st, mbits, g.W, g.deg, ebi, ebj, ei, ej, sl, rank_mode, tcnt, ev, own, ebase, rj)
-  if (tg == 4) SC_LAUNCH_CE(4); else if (tg == 16) SC_LAUNCH_CE(16); else if (tg == 32) SC_LAUNCH_CE(32); else if (tg == 64) SC_LAUNCH_CE(64); else SC_LAUNCH_CE(8);
+  const OrdList ol = ord ? *ord : OrdList{};
+#define SC_LAUNCH_CE(TGV, ORDV) hipLaunchKernelGGL((tri_count_events_kernel<TGV, ORDV>), dim3((unsigned)nb), dim3(256), 0, st, mbits, g.W, g.deg, ebi, ebj, ei, ej, sl, rank_mode, tcnt, ev, own, ebase, rj, ol)
+  if (ol.cnt) {
+    if (tg == 4) SC_LAUNCH_CE(4, true); else if (tg == 16) SC_LAUNCH_CE(16, true); else if (tg == 32) SC_LAUNCH_CE(32, true); else if (tg == 64) SC_LAUNCH_CE(64, true); else SC_LAUNCH_CE(8, true);
+  } else {
+    if (tg == 4) SC_LAUNCH_CE(4, false); else if (tg == 16) SC_LAUNCH_CE(16, false); else if (tg == 32) SC_LAUNCH_CE(32, false); else if (tg == 64) SC_LAUNCH_CE(64, false); else SC_LAUNCH_CE(8, false);
+  }
 #undef SC_LAUNCH_CE
+}
+
+int tri_count_events_lanes(const Graph& g, const Tuning& tn) {
+  return tn.tg_events ? tn.tg_events : (g.W <= 64 ? 8 : (g.W <= 128 ? 4 : (g.W <= 512 ? 16 : 32)));
+}
+
+// (ORD) the fall-back of an overflow scans tcnt: the entries of the weak edges, which no kernel of the ordered form writes
+__global__ __launch_bounds__(256) void zero_weak_counts_kernel(const float* __restrict__ es, const float* __restrict__ smin,
+                                                               uint64_t E, const uint64_t* __restrict__ E_dev,
+                                                               uint32_t* __restrict__ tcnt) {
+  const uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= E) return;
+  const uint64_t Ea = E_dev ? (*E_dev > E ? 0ull : *E_dev) : E;
+  if (e >= Ea || !(es[e] >= *smin)) tcnt[e] = 0u;
+}
+void launch_zero_weak_counts(const float* es, const float* smin, uint64_t E, const uint64_t* E_dev, uint32_t* tcnt, hipStream_t st) {
+  if (E == 0) return;
+  hipLaunchKernelGGL(zero_weak_counts_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, st, es, smin, E, E_dev, tcnt);
 }
 
 void launch_tri_keys_events(const Graph& g, const float* es, const uint64_t* toff, int rank_mode,
                             const EventList& ev, uint32_t* wkey, uint2* kcol, uint32_t* blk_minmax,
                             SelectState* s, uint64_t want, const uint32_t* klb, uint64_t E, uint64_t cap,
-                            const Tuning& tn, hipStream_t st, bool check_bound) {
-  int nb = 2048;
+                            const Tuning& tn, hipStream_t st, bool check_bound, const OrdList* ord, int chunk_shift,
+                            uint64_t* host_total) {
+  // (ordered strong list: every workgroup pays for the prefix over the chunk totals, and four fit a CU beside it — one round of them)
+  int nb = ord && ord->cnt ? 1024 : 2048;
   if (tn.keys_blocks >= 1 && tn.keys_blocks <= (uint32_t)TK_MAX_BLOCKS) nb = (int)tn.keys_blocks;
-  hipLaunchKernelGGL(tri_keys_events_kernel, dim3(nb), dim3(256), 0, st, g.bits, g.wpre, g.deg, es, toff, rank_mode,
-                     ev, wkey, kcol, blk_minmax, blk_minmax + TK_MAX_BLOCKS, klb ? s : (SelectState*)nullptr, klb, want, E, cap,
-                     check_bound ? 1 : 0);
+  if (ord && ord->cnt)
+    hipLaunchKernelGGL(tri_keys_events_kernel<true>, dim3(nb), dim3(256), 0, st, g.bits, g.wpre, g.deg, es, toff, rank_mode,
+                       ev, wkey, kcol, blk_minmax, blk_minmax + TK_MAX_BLOCKS, klb ? s : (SelectState*)nullptr, klb, want, E, cap,
+                       check_bound ? 1 : 0, *ord, chunk_shift, host_total);
+  else
+    hipLaunchKernelGGL(tri_keys_events_kernel<false>, dim3(nb), dim3(256), 0, st, g.bits, g.wpre, g.deg, es, toff, rank_mode,
+                       ev, wkey, kcol, blk_minmax, blk_minmax + TK_MAX_BLOCKS, klb ? s : (SelectState*)nullptr, klb, want, E, cap,
+                       check_bound ? 1 : 0, OrdList{}, 0, (uint64_t*)nullptr);
   if (!klb)  // no a-priori window: the key range comes from the per-block extremes
     hipLaunchKernelGGL(key_range_kernel, dim3(1), dim3(1024), 0, st, blk_minmax, blk_minmax + TK_MAX_BLOCKS, nb, s, want);
 }
@@ -1192,10 +1328,10 @@ __global__ __launch_bounds__(256) void prune_bits_kernel(const uint32_t* __restr
   // a host-free call's grid covers more edges than there are: the workgroups beyond them have nothing to list, and their tcnt
   // entries are never read (the scan of a host-free call skips the tiles beyond ControlBlock::live_edges and treats what lies
   // beyond the count as zero) — they leave before the histogram walk
-  if (trimmed && E_dev && sl.region_blocks == 0 && (uint64_t)blockIdx.x * 256 >= Ea) return;
+  if (trimmed && E_dev && sl.region_blocks == 0 && (uint64_t)blockIdx.x * (sl.cnt ? ORD_BLOCK_EDGES : 256u) >= Ea) return;
   __shared__ uint64_t lds[8];
   __shared__ float s_smin;
-  __shared__ uint32_t s_klb, s_base, s_wcnt[4];
+  __shared__ uint32_t s_klb, s_base, s_wcnt[4], s_rcnt[4][4];
   static_assert(PR_BINS == 256, "one bin per thread, walked from the top");
   const uint32_t bin = PR_BINS - 1 - threadIdx.x;
   uint64_t mine = 0;
@@ -1217,6 +1353,40 @@ __global__ __launch_bounds__(256) void prune_bits_kernel(const uint32_t* __restr
   __syncthreads();
   const float smin = s_smin;
   if (blockIdx.x == 0 && threadIdx.x == 0) { *smin_out = smin; *klb_out = s_klb; }
+  if (sl.cnt) {
+    // the ORDERED form (2c; one rank, region_blocks == 0): the block takes ORD_BLOCK_EDGES consecutive edges — four runs of 256, a
+    // quarter of the histogram walks above — and writes the strong ones in ascending order into its own slot, their number into
+    // cnt[blockIdx]: no atomic, one barrier, and no tcnt entry is zeroed (nothing scans the counts; an overflow's fall-back
+    // zeroes the weak ones)
+    static_assert(ORD_BLOCK_EDGES == 4 * 256, "four runs of 256");
+    const int wave = threadIdx.x >> 6;
+    bool st[4]; uint64_t bal[4];
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      const uint64_t e = (uint64_t)blockIdx.x * ORD_BLOCK_EDGES + q * 256 + threadIdx.x;
+      st[q] = e < Ea && es[e] >= smin;
+      if (st[q]) {
+        const uint32_t i = ei[e], j = ej[e];
+        atomicOr(&mbits[(size_t)i * W + (j >> 6)], 1ull << (j & 63));
+      }
+      bal[q] = __ballot(st[q]);
+      if ((threadIdx.x & 63) == 0) s_rcnt[q][wave] = (uint32_t)__popcll(bal[q]);
+    }
+    __syncthreads();
+    uint32_t run = 0;  // strong edges of the runs and waves before (q, w)
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+#pragma unroll
+      for (int w = 0; w < 4; w++) {
+        if (w == wave && st[q])
+          sl.list[(uint64_t)blockIdx.x * ORD_BLOCK_EDGES + run + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal[q] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal[q], 0u))] =
+              (uint32_t)((uint64_t)blockIdx.x * ORD_BLOCK_EDGES + q * 256 + threadIdx.x);
+        run += s_rcnt[q][w];
+      }
+    }
+    if (threadIdx.x == 0) sl.cnt[blockIdx.x] = run;
+    return;
+  }
   // region = blockIdx % ST_SHARDS in both forms (blocks that run side by side add to different counters: with consecutive
   // blocks on one counter this kernel took 61 us instead of 33 at C3); with contiguous regions the block's 256 EDGES are what
   // moves: block b takes chunk (b % ST_SHARDS) * region_blocks + b / ST_SHARDS
@@ -1394,7 +1564,7 @@ void launch_prune_bits(const Graph& g, const uint32_t* hist, bool hist_is_copies
   uint32_t klo, shift;
   prune_window(key_floor, &klo, &shift);
   if (logbins) shift = PR_LOGBINS;  // the histogram of launch_sample_estimate
-  const uint64_t blocks = sl.region_blocks ? (uint64_t)sl.region_blocks * ST_SHARDS : (E + 255) / 256;
+  const uint64_t blocks = sl.cnt ? (E + ORD_BLOCK_EDGES - 1) / ORD_BLOCK_EDGES : sl.region_blocks ? (uint64_t)sl.region_blocks * ST_SHARDS : (E + 255) / 256;
   hipLaunchKernelGGL(prune_bits_kernel, dim3((unsigned)blocks), dim3(256), 0, st, hist,
                      hist_is_copies ? PR_HCOPIES : 1, want, klo, shift, ei,
                      ej, es, E, g.W, reinterpret_cast<unsigned long long*>(mbits), smin, klb, sl, tcnt, own, E_dev, trimmed ? 1 : 0);
