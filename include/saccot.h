@@ -49,6 +49,7 @@ extern "C" {
 #define SC_HAS_POLISH_POSES 1  /* this header declares sc_polish_poses* (added within 0.10) */
 #define SC_HAS_ASSIGN 1  /* this header declares sc_assign_poses* and sc_assign_default_params (added within 0.10) */
 #define SC_HAS_MATCH_GUIDED 1  /* this header declares sc_match_guided*, sc_register_guided_features and sc_guide_default_params (added within 0.10) */
+#define SC_HAS_MATCH_GUIDED_BATCH 1  /* this header declares sc_match_guided_batch*, sc_match_guided_pairs* and sc_register_guided_{batch,pairs}_features_device (added within 0.10) */
 
 /* status codes */
 #define SC_OK        0
@@ -486,13 +487,13 @@ int sc_register_features(sc_ctx* ctx, const float* src_pts, const float* fsrc, i
  * Refused with SC_EINVAL on the host before anything is enqueued, sc_last_error naming which: every rule of sc_match_params; a NULL
  * argument (g2 / d_g2 excepted); guide->size wrong; a layout above SC_SOA; a gate that is not finite and > 0; a flag or reserved word
  * that is not 0; a call outstanding on the context.
- * Not here: batch and pairs forms; several poses per call; a gate on anything but the point residual (descriptor-space or scale
+ * Not here: batch and pairs forms (entries of their own: sc_match_guided_batch, below); several poses per call; a gate on anything but the point residual (descriptor-space or scale
  * gates); soft weighting by g2. */
 typedef struct sc_guide_params {   /* 32 bytes */
   uint32_t size;         /* = sizeof(sc_guide_params)                                                  */
   uint32_t layout;       /* SC_AOS / SC_SOA: how src_pts and tgt_pts are laid out                      */
   float    gate;         /* radius, finite, > 0                                                        */
-  uint32_t flags;        /* must be 0                                                                  */
+  uint32_t flags;        /* must be 0 (the sc_match_guided_batch entries: SC_GUIDE_POSE_STATUS or 0)   */
   uint32_t reserved[4];  /* must be 0                                                                  */
 } sc_guide_params;
 int sc_guide_default_params(sc_guide_params* gp);   /* size set, SC_AOS, gate 0 (the caller sets it), no flags */
@@ -773,6 +774,75 @@ int sc_polish_pairs_slots_device(sc_ctx* ctx, const float* d_pts, const uint32_t
                                  uint32_t n_pairs, uint32_t knn, const sc_params* params, const sc_polish_params* pp,
                                  const int32_t* d_corr, const uint32_t* d_count, const sc_batch_result* d_res,
                                  sc_polish_batch_result* d_pol, uint8_t* d_mask);
+
+/* ---- pose-gated matching for batches and pairs: sc_match_guided_batch -----------------------------------------
+ * sc_match_guided for the callers of the batch and pairs entries: one pose PER PROBLEM (per pair), on the device, and the stream
+ * operations of sc_match_batch / sc_match_pairs whatever the batch.  What it closes: sc_register_batch_features /
+ * sc_register_pairs_features leave a pose per problem in d_res; re-matching under it through sc_match_guided_device was three stream
+ * operations per problem (and, for pairs, the table expanded per pair again).
+ *   Layout: offsets, slots, count pairs, local indices exactly those of sc_match_batch (sc_match_pairs).  The points — src_pts total_s
+ *   and tgt_pts total_t rows (pairs: pts, the table's rows), point i of the array beside descriptor row i — are in guide->layout
+ *   (SC_AOS: rows x 3; SC_SOA: three planes of ALL rows).  d_g2: optional (NULL ok), slot-positioned like d_d2.
+ *   The pose input: d_pose holds one record per problem (pair), pose_stride bytes apart, float Rt[12] at byte 0; with
+ *   SC_GUIDE_POSE_STATUS in guide->flags also an int32 status at byte 48.  pose_stride: a multiple of 4, >= 48, and >= 52 with the
+ *   flag — so sc_batch_result (80, with the flag), sc_polish_batch_result (64, with the flag) and a plain array of 12-float poses
+ *   (48) all serve unchanged.  d_pose is read in stream order and never written by the match.
+ *   Semantics, per problem b: the slot, g2 and the count pair are, bit for bit, what sc_match_guided returns for that problem alone
+ *   with pose record b, the same sc_match_params and the same gate; every rule of that contract holds per problem (admissibility is
+ *   g2 < gate2, a float <; knn, mutual and ratio run over admissible cells only; a match is kept when its row has fewer than two
+ *   admissible candidates; a hostile but finite pose admits nothing and raises no flag).
+ *   count[2b + 1] = 1, and then n_b = 0, iff any descriptor, any point or the pose of problem b is not finite, whatever the gate
+ *   excludes (pairs: of either set of the pair — a bad value in a set flags every pair that uses the set and no other).  It flags
+ *   that problem only; the call — the host forms too — returns SC_OK.
+ *   SC_GUIDE_POSE_STATUS and a status other than SC_OK: the problem is skipped — its count pair is (0, 0), nothing else of it is read
+ *   or written, its neighbours are not disturbed.
+ *   A problem's outputs are a function of its own inputs, its pose and the parameters only: not of its position, of n_problems, of
+ *   the other problems, of shared sets or of the context's history.
+ *   The features entries: the guided match, then the unchanged registration on the slots (sc_register_batch_features' second half,
+ *   with its rules for flagged problems and n_b < 3; a skipped problem has n_b = 0, hence SC_ENOHYP).  guide->layout must equal
+ *   params->layout; ns_b * knn > SC_BATCH_MAX_N is refused as there.  d_pose MAY be d_res: the registration launch that writes d_res
+ *   is ordered behind both match launches, so the record of problem b is read before it is replaced.
+ * Stream operations: those of the unguided form, independent of any size — one copy, one memset, two launches, plus the
+ * registration's one; no host word.  Frames and workspace: the entries end the frame the context may hold; the workspace is the
+ * batched match's (the host forms add their device copies), counted in workspace_bytes and held against the cap.
+ * Refused with SC_EINVAL on the host before anything is enqueued, sc_last_error naming which: everything sc_match_batch
+ * (sc_match_pairs) and their features entries refuse; every rule of sc_guide_params, but that guide->flags may be
+ * SC_GUIDE_POSE_STATUS (any other bit is refused; sc_match_guided* and sc_register_guided_features keep refusing every flag); a
+ * pose_stride that breaks the rule above; a NULL argument (g2 / d_g2 excepted); a call outstanding on the context.
+ * Not here: host forms of the two features entries; one pose shared by all problems, and several poses per problem; an instances
+ * form. */
+#define SC_GUIDE_POSE_STATUS 1u   /* sc_guide_params.flags, these entries only: the pose records hold an int32 status at byte 48 */
+/* Everything but the offsets in HBM; enqueues on the context's stream and returns without waiting. */
+int sc_match_guided_batch_device(sc_ctx* ctx, const float* d_src_pts, const float* d_fsrc, const uint32_t* src_off,
+                                 const float* d_tgt_pts, const float* d_ftgt, const uint32_t* tgt_off, uint32_t n_problems,
+                                 const sc_match_params* mp, const sc_guide_params* gp, const void* d_pose, uint32_t pose_stride,
+                                 int32_t* d_corr, float* d_d2, float* d_g2, uint32_t* d_count);
+/* The same with host arrays (pose: n_problems * pose_stride bytes, copied as given; g2 may be NULL); waits.  A flagged problem is
+ * its count pair's business: SC_OK. */
+int sc_match_guided_batch(sc_ctx* ctx, const float* src_pts, const float* fsrc, const uint32_t* src_off, const float* tgt_pts,
+                          const float* ftgt, const uint32_t* tgt_off, uint32_t n_problems, const sc_match_params* mp,
+                          const sc_guide_params* gp, const void* pose, uint32_t pose_stride, int32_t* corr, float* d2, float* g2,
+                          uint32_t* count);
+/* The guided match, then sc_batch.hip's registration on the slots; d_res, d_mask as sc_register_batch_features_device's. */
+int sc_register_guided_batch_features_device(sc_ctx* ctx, const float* d_src_pts, const float* d_fsrc, const uint32_t* src_off,
+                                             const float* d_tgt_pts, const float* d_ftgt, const uint32_t* tgt_off,
+                                             uint32_t n_problems, const sc_match_params* mp, const sc_guide_params* gp,
+                                             const void* d_pose, uint32_t pose_stride, const sc_params* params,
+                                             sc_batch_result* d_res, int32_t* d_corr, float* d_d2, float* d_g2, uint32_t* d_count,
+                                             uint8_t* d_mask);
+/* The pairs forms: the table and the list of sc_match_pairs, d_pts the table's points, one pose record per PAIR. */
+int sc_match_guided_pairs_device(sc_ctx* ctx, const float* d_pts, const float* d_feat, const uint32_t* set_off, uint32_t n_sets,
+                                 const uint32_t* pairs, uint32_t n_pairs, const sc_match_params* mp, const sc_guide_params* gp,
+                                 const void* d_pose, uint32_t pose_stride, int32_t* d_corr, float* d_d2, float* d_g2,
+                                 uint32_t* d_count);
+int sc_match_guided_pairs(sc_ctx* ctx, const float* pts, const float* feat, const uint32_t* set_off, uint32_t n_sets,
+                          const uint32_t* pairs, uint32_t n_pairs, const sc_match_params* mp, const sc_guide_params* gp,
+                          const void* pose, uint32_t pose_stride, int32_t* corr, float* d2, float* g2, uint32_t* count);
+int sc_register_guided_pairs_features_device(sc_ctx* ctx, const float* d_pts, const float* d_feat, const uint32_t* set_off,
+                                             uint32_t n_sets, const uint32_t* pairs, uint32_t n_pairs, const sc_match_params* mp,
+                                             const sc_guide_params* gp, const void* d_pose, uint32_t pose_stride,
+                                             const sc_params* params, sc_batch_result* d_res, int32_t* d_corr, float* d_d2,
+                                             float* d_g2, uint32_t* d_count, uint8_t* d_mask);
 
 /* ---- the fp64 information matrix of a batch's poses: sc_pose_info_batch ------------------------------------------
  * The callers of the batch entries feed every pair's pose into a pose graph or a fusion step as an EDGE, and an edge needs a

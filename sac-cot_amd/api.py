@@ -47,6 +47,8 @@ EXPORTS = ["sc_version", "sc_strerror", "sc_default_params", "sc_create", "sc_de
            "sc_register_instances_batch", "sc_register_instances_batch_device", "sc_register_instances_batch_features_device",
            "sc_pairs_layout", "sc_match_pairs", "sc_match_pairs_device", "sc_register_pairs_features", "sc_register_pairs_features_device",
            "sc_polish_pairs_slots_device",
+           "sc_match_guided_batch", "sc_match_guided_batch_device", "sc_register_guided_batch_features_device",
+           "sc_match_guided_pairs", "sc_match_guided_pairs_device", "sc_register_guided_pairs_features_device",
            "sc_pose_info_batch", "sc_pose_info_batch_device", "sc_pose_info_batch_slots_device", "sc_pose_info_pairs_slots_device",
            "sc_pose_info_default_params", "sc_pose_info_frame", "sc_pose_info_frame_device",
            "sc_polish_poses_default_params", "sc_polish_poses", "sc_polish_poses_device",
@@ -184,6 +186,7 @@ SC_ASSIGN_MAX_POSES, SC_ASSIGN_BATCH_MAX_POSES = 1024, 64
 SC_ASSIGN_BEST, SC_ASSIGN_FIRST = 0, 1
 SC_ASSIGN_SEL_NONE, SC_ASSIGN_SEL_MASK = 0, 1
 SC_ASSIGN_STATUS = 1
+SC_GUIDE_POSE_STATUS = 1  # sc_guide_params.flags, the sc_match_guided_batch entries only: the pose records hold an int32 status at byte 48
 SC_MATCH_BATCH_MAX_N = 4096  # rows a side of one problem of sc_match_batch
 SC_INSTANCES_BATCH_MAX = 16  # motions per problem of sc_register_instances_batch at most
 
@@ -313,6 +316,13 @@ def load_library() -> C.CDLL:
     L.sc_register_pairs_features_device.argtypes = [vp, vp, vp, u32p, C.c_uint32, u32p, C.c_uint32, mp, pp, vp, vp, vp, vp, vp]
     L.sc_register_pairs_features.argtypes = [vp, f32p, f32p, u32p, C.c_uint32, u32p, C.c_uint32, mp, pp, vp, i32p, f32p, u32p, u8p]
     L.sc_polish_pairs_slots_device.argtypes = [vp, vp, u32p, C.c_uint32, u32p, C.c_uint32, C.c_uint32, pp, qp, vp, vp, vp, vp, vp]
+    u32 = C.c_uint32
+    L.sc_match_guided_batch_device.argtypes = [vp, vp, vp, u32p, vp, vp, u32p, u32, mp, gp, vp, u32, vp, vp, vp, vp]
+    L.sc_match_guided_batch.argtypes = [vp, f32p, f32p, u32p, f32p, f32p, u32p, u32, mp, gp, vp, u32, i32p, f32p, f32p, u32p]
+    L.sc_register_guided_batch_features_device.argtypes = [vp, vp, vp, u32p, vp, vp, u32p, u32, mp, gp, vp, u32, pp, vp, vp, vp, vp, vp, vp]
+    L.sc_match_guided_pairs_device.argtypes = [vp, vp, vp, u32p, u32, u32p, u32, mp, gp, vp, u32, vp, vp, vp, vp]
+    L.sc_match_guided_pairs.argtypes = [vp, f32p, f32p, u32p, u32, u32p, u32, mp, gp, vp, u32, i32p, f32p, f32p, u32p]
+    L.sc_register_guided_pairs_features_device.argtypes = [vp, vp, vp, u32p, u32, u32p, u32, mp, gp, vp, u32, pp, vp, vp, vp, vp, vp, vp]
     L.sc_pose_info_batch.argtypes = [vp, f32p, f32p, u32p, C.c_uint32, pp, vp, C.c_uint32, vp]
     L.sc_pose_info_batch_device.argtypes = [vp, vp, vp, u32p, C.c_uint32, pp, vp, C.c_uint32, vp]
     L.sc_pose_info_batch_slots_device.argtypes = [vp, vp, u32p, vp, u32p, C.c_uint32, C.c_uint32, pp, vp, vp, vp, C.c_uint32, vp]
@@ -369,7 +379,8 @@ def make_match_params(dim: int, knn: int = 1, mutual: bool = False, ratio: float
 
 
 def make_guide_params(gate: float, layout: int = SC_AOS, flags: int = 0) -> ScGuideParams:
-    """sc_guide_params: the gate radius (finite, > 0) and the layout of the keypoint arrays of sc_match_guided."""
+    """sc_guide_params: the gate radius (finite, > 0) and the layout of the keypoint arrays of sc_match_guided; flags: 0, or — the
+    batch and pairs entries only — SC_GUIDE_POSE_STATUS."""
     return ScGuideParams(C.sizeof(ScGuideParams), layout, gate, flags)
 
 
@@ -1012,6 +1023,110 @@ class Registrar:
         self._frame_n = 0
         self._check(self._lib.sc_polish_pairs_slots_device(self._h, d_pts, _p(set_off, C.c_uint32), ns, _p(pairs, C.c_uint32), npairs, knn,
                                                            C.byref(params), C.byref(pparams), d_corr, d_count, d_res, d_pol, d_mask))
+
+    # ---- pose-gated matching for batches and pairs (include/saccot.h, sc_match_guided_batch) ---------------------------
+    @staticmethod
+    def _pose_records(pose, n):
+        """pose records as the entries take them: an (n, 12) float array (stride 48), or n records of any dtype whose items start
+        with float Rt[12] (and, with SC_GUIDE_POSE_STATUS, an int32 status at byte 48) -> (contiguous array, stride)"""
+        pose = np.ascontiguousarray(pose)
+        if pose.dtype.fields is None:
+            pose = np.ascontiguousarray(pose, np.float32).reshape(-1, 12)
+            stride = 48
+        else:
+            pose = pose.reshape(-1)
+            stride = pose.dtype.itemsize
+        if len(pose) != n:
+            raise ValueError("one pose record per problem")
+        return pose, stride
+
+    def match_guided_batch(self, src_pts, fsrc, src_off, tgt_pts, ftgt, tgt_off, pose, gate: float | None = None, layout: int = SC_AOS,
+                           flags: int = 0, mparams: ScMatchParams | None = None, gparams: ScGuideParams | None = None, want_g2: bool = True,
+                           **kw):
+        """sc_match_guided_batch on packed arrays: points in `layout` ((total, 3), or (3, total) with SC_SOA) beside the descriptors
+        and offsets of match_batch_raw; pose: one record per problem (_pose_records) -> (corr (total_s * knn, 2), d2, g2 or None,
+        count (B, 2)), slot-positioned as match_batch_raw's: problem b's entries are match_guided() of problem b alone under pose b.
+        count[b] = (n_b, 1 if a descriptor, a point or the pose of b is not finite); with SC_GUIDE_POSE_STATUS in flags a record
+        whose status is not SC_OK skips its problem: (0, 0)."""
+        g = gparams or make_guide_params(gate, layout, flags)
+        src_pts, fsrc, tgt_pts, ftgt = _f32c(src_pts), _f32c(fsrc), _f32c(tgt_pts), _f32c(ftgt)
+        src_off, tgt_off = np.ascontiguousarray(src_off, dtype=np.uint32), np.ascontiguousarray(tgt_off, dtype=np.uint32)
+        m = mparams or make_match_params(fsrc.shape[1], **kw)
+        nb = max(len(src_off) - 1, 0)
+        pose, stride = self._pose_records(pose, nb)
+        slots = (int(src_off[-1]) if len(src_off) else 0) * max(int(m.knn), 1)
+        corr = np.zeros((max(slots, 1), 2), np.int32); d2 = np.zeros(max(slots, 1), np.float32); count = np.zeros((max(nb, 1), 2), np.uint32)
+        g2 = np.zeros(max(slots, 1), np.float32) if want_g2 else None
+        self._frame_n = 0
+        self._check(self._lib.sc_match_guided_batch(self._h, _p(src_pts, C.c_float), _p(fsrc, C.c_float), _p(src_off, C.c_uint32),
+                                                    _p(tgt_pts, C.c_float), _p(ftgt, C.c_float), _p(tgt_off, C.c_uint32), nb, C.byref(m),
+                                                    C.byref(g), pose.ctypes.data_as(C.c_void_p), stride, _p(corr, C.c_int32),
+                                                    _p(d2, C.c_float), _p(g2, C.c_float), _p(count, C.c_uint32)))
+        return corr[:slots], d2[:slots], (g2[:slots] if want_g2 else None), count[:nb]
+
+    def match_guided_batch_device(self, d_src_pts: int, d_fsrc: int, src_off, d_tgt_pts: int, d_ftgt: int, tgt_off, mparams: ScMatchParams,
+                                  gparams: ScGuideParams, d_pose: int, pose_stride: int, d_corr: int, d_d2: int, d_g2: int | None,
+                                  d_count: int):
+        """sc_match_guided_batch_device: everything but the offsets in HBM (d_pose: B records pose_stride bytes apart, read in stream
+        order; d_g2: total_s * knn float32 or None; the rest as match_batch_device); returns without waiting."""
+        src_off, tgt_off = np.ascontiguousarray(src_off, dtype=np.uint32), np.ascontiguousarray(tgt_off, dtype=np.uint32)
+        self._frame_n = 0
+        self._check(self._lib.sc_match_guided_batch_device(self._h, d_src_pts, d_fsrc, _p(src_off, C.c_uint32), d_tgt_pts, d_ftgt,
+                                                           _p(tgt_off, C.c_uint32), max(len(src_off) - 1, 0), C.byref(mparams),
+                                                           C.byref(gparams), d_pose, pose_stride, d_corr, d_d2, d_g2, d_count))
+
+    def register_guided_batch_features_device(self, d_src_pts: int, d_fsrc: int, src_off, d_tgt_pts: int, d_ftgt: int, tgt_off,
+                                              mparams: ScMatchParams, gparams: ScGuideParams, d_pose: int, pose_stride: int,
+                                              params: ScParams, d_res: int, d_corr: int, d_d2: int, d_g2: int | None, d_count: int,
+                                              d_mask: int):
+        """sc_register_guided_batch_features_device: match_guided_batch_device, then the registration on the slots (d_res, d_mask as
+        register_batch_features_device's).  d_pose may be d_res; returns without waiting."""
+        src_off, tgt_off = np.ascontiguousarray(src_off, dtype=np.uint32), np.ascontiguousarray(tgt_off, dtype=np.uint32)
+        self._frame_n = 0
+        self._check(self._lib.sc_register_guided_batch_features_device(
+            self._h, d_src_pts, d_fsrc, _p(src_off, C.c_uint32), d_tgt_pts, d_ftgt, _p(tgt_off, C.c_uint32), max(len(src_off) - 1, 0),
+            C.byref(mparams), C.byref(gparams), d_pose, pose_stride, C.byref(params), d_res, d_corr, d_d2, d_g2, d_count, d_mask))
+
+    def match_guided_pairs(self, pts, feat, set_off, pairs, pose, gate: float | None = None, layout: int = SC_AOS, flags: int = 0,
+                           mparams: ScMatchParams | None = None, gparams: ScGuideParams | None = None, want_g2: bool = True, **kw):
+        """sc_match_guided_pairs: the table (pts in `layout`, feat) and the list of match_pairs; pose: one record per PAIR ->
+        (corr, d2, g2 or None, count (P, 2), slot (P + 1,)) as match_pairs', every pair matched under its own pose."""
+        g = gparams or make_guide_params(gate, layout, flags)
+        pts, feat = _f32c(pts), _f32c(feat)
+        m = mparams or make_match_params(feat.shape[1], **kw)
+        set_off, pairs, ns, npairs = self._table(set_off, pairs)
+        pose, stride = self._pose_records(pose, npairs)
+        slot = self.pairs_layout(set_off, pairs, int(m.knn))
+        slots = int(slot[-1])
+        corr = np.zeros((max(slots, 1), 2), np.int32); d2 = np.zeros(max(slots, 1), np.float32); count = np.zeros((max(npairs, 1), 2), np.uint32)
+        g2 = np.zeros(max(slots, 1), np.float32) if want_g2 else None
+        self._frame_n = 0
+        self._check(self._lib.sc_match_guided_pairs(self._h, _p(pts, C.c_float), _p(feat, C.c_float), _p(set_off, C.c_uint32), ns,
+                                                    _p(pairs, C.c_uint32), npairs, C.byref(m), C.byref(g), pose.ctypes.data_as(C.c_void_p),
+                                                    stride, _p(corr, C.c_int32), _p(d2, C.c_float), _p(g2, C.c_float),
+                                                    _p(count, C.c_uint32)))
+        return corr[:slots], d2[:slots], (g2[:slots] if want_g2 else None), count[:npairs], slot
+
+    def match_guided_pairs_device(self, d_pts: int, d_feat: int, set_off, pairs, mparams: ScMatchParams, gparams: ScGuideParams,
+                                  d_pose: int, pose_stride: int, d_corr: int, d_d2: int, d_g2: int | None, d_count: int):
+        """sc_match_guided_pairs_device: the table, the pose records (one per pair) and the outputs in HBM, set_off and pairs HOST
+        arrays; returns without waiting."""
+        set_off, pairs, ns, npairs = self._table(set_off, pairs)
+        self._frame_n = 0
+        self._check(self._lib.sc_match_guided_pairs_device(self._h, d_pts, d_feat, _p(set_off, C.c_uint32), ns, _p(pairs, C.c_uint32),
+                                                           npairs, C.byref(mparams), C.byref(gparams), d_pose, pose_stride, d_corr, d_d2,
+                                                           d_g2, d_count))
+
+    def register_guided_pairs_features_device(self, d_pts: int, d_feat: int, set_off, pairs, mparams: ScMatchParams,
+                                              gparams: ScGuideParams, d_pose: int, pose_stride: int, params: ScParams, d_res: int,
+                                              d_corr: int, d_d2: int, d_g2: int | None, d_count: int, d_mask: int):
+        """sc_register_guided_pairs_features_device: match_guided_pairs_device, then the registration on the slots.  d_pose may be
+        d_res; returns without waiting."""
+        set_off, pairs, ns, npairs = self._table(set_off, pairs)
+        self._frame_n = 0
+        self._check(self._lib.sc_register_guided_pairs_features_device(
+            self._h, d_pts, d_feat, _p(set_off, C.c_uint32), ns, _p(pairs, C.c_uint32), npairs, C.byref(mparams), C.byref(gparams), d_pose,
+            pose_stride, C.byref(params), d_res, d_corr, d_d2, d_g2, d_count, d_mask))
 
     # ---- the fp64 information matrix of a batch's poses (include/saccot.h, sc_pose_info_batch) -------------------------
     def pose_info_batch_raw(self, src, tgt, offset, params: ScParams, pose):

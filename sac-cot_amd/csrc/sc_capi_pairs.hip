@@ -18,13 +18,10 @@ using namespace sc;
 static_assert(PAIR_WORDS == PAIRS_REC_WORDS && PW_SRC == 0 && PW_NS == 1 && PW_TGT == 2 && PW_NT == 3 && PW_TOP == 4 && PW_SLOT == 5 &&
               PW_COL_LO == 6 && PW_COL_HI == 7, "pairs_records (sc_pairs_check.hpp) writes the words the kernels read (sc_kernels.hpp)");
 
-namespace {
-
 using Sizes = MatchBatchSizes;  // n_problems: the pairs; total_s / total_t: the source / target rows of all pairs
 
-// every refusal of the entries; `p` only for the features entries, whose name for the messages is `features`.  Fills *job (but its
-// pointers) and *sz.
-int pairs_check(sc_ctx* c, const uint32_t* set_off, uint32_t n_sets, const uint32_t* pairs, uint32_t n_pairs, const sc_match_params* mp,
+// every refusal of the entries (declared in sc_ctx.hpp: sc_capi_match_guided_batch.hip's pairs entries share it)
+int sc::pairs_check(sc_ctx* c, const uint32_t* set_off, uint32_t n_sets, const uint32_t* pairs, uint32_t n_pairs, const sc_match_params* mp,
                 const sc_params* p, const char* features, MatchJob* job, Sizes* sz) {
   SC_TRY(entry_checks(c, nullptr, ENDS_FRAME | NOT_BUSY));
   SC_TRY(match_check(c, mp, 1, 1, job));  // the parameter rules; the sizes are the table's business
@@ -37,6 +34,8 @@ int pairs_check(sc_ctx* c, const uint32_t* set_off, uint32_t n_sets, const uint3
   sz->meta = pairs_meta_layout(n_pairs, sz->n_tiles);
   return SC_OK;
 }
+
+namespace {
 
 // the match on the list (mbatch_room has been called): the records, the slot starts and the tile map into the staging area,
 // MatchPairsJob and its launches.  p, d_pts: a features entry's sc_params and the table's points (`total` rows), for the gather

@@ -119,6 +119,9 @@ struct Workspace {
       // entries' arrays (pairs: fsrc / psrc hold the one table)
       mbatch_meta, mbatch_top, mbatch_words, mbatch_gsrc, mbatch_gtgt, mbatch_fsrc, mbatch_ftgt, mbatch_psrc, mbatch_ptgt, mbatch_corr,
       mbatch_d2, mbatch_count, mbatch_res, mbatch_mask,
+      // sc_match_guided_batch / sc_match_guided_pairs, the host forms' device copies of the pose records and of g2 (the rest is the
+      // mbatch set): allocated by the first such call, never by a frame or by another batch entry
+      mbatch_pose, mbatch_g2,
       // sc_polish_batch: allocated by the first such call, never by a frame or by another batch entry.  off: the copy of the caller's
       // offsets (the slot form: both arrays and the slot starts; the pairs form: the pairs' records); the rest: device copies of the host entry's arrays
       pbatch_off, pbatch_src, pbatch_tgt, pbatch_res, pbatch_pol, pbatch_mask,
@@ -378,6 +381,12 @@ int mbatch_enqueue_packed(sc_ctx* c, const MatchJob& mj, const MatchBatchSizes& 
 BatchJob mbatch_slots_job(const sc_ctx* c, const MatchBatchSizes& sz, const sc_params* p);
 // sc_batch.hip's kernel on those slots (the count pairs are the caller's)
 int mbatch_register(sc_ctx* c, const MatchBatchSizes& sz, const sc_params* p, const uint32_t* d_count, sc_batch_result* d_res, uint8_t* d_mask);
+
+// ---- defined in sc_capi_pairs.hip, used by the pairs entries of sc_capi_match_guided_batch.hip as well
+// every refusal of a pairs entry; `p` only for the features entries, whose name for the messages is `features`.  Fills *job (but its
+// pointers) and *sz (n_problems: the pairs; total_s / total_t: the source / target rows of all pairs).
+int pairs_check(sc_ctx* c, const uint32_t* set_off, uint32_t n_sets, const uint32_t* pairs, uint32_t n_pairs, const sc_match_params* mp,
+                const sc_params* p, const char* features, MatchJob* job, MatchBatchSizes* sz);
 
 // ---- defined in sc_capi_polish_batch.hip, used by sc_capi_pairs.hip as well
 // sc_polish_params as a batch takes them (one candidate per problem); `who` opens the message

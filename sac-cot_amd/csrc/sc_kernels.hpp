@@ -1015,4 +1015,27 @@ struct MatchPairsJob {
 void launch_match_pairs_dist(const MatchPairsJob& job, hipStream_t st);
 void launch_match_pairs_finish(const MatchPairsJob& job, hipStream_t st);
 
+// ---- both forms under a pose prior per problem (sc_match_guided_batch; sc_match_batch.hip) ---------------------------
+// The keypoints of the batch (point so + i of src is src[(so + i) * s_elem + c * s_comp], as MatchGather's; the pairs form: src ==
+// tgt, the table), one pose record per problem — 12 floats at byte pose_stride * b of `pose`, with use_status an int32 status at
+// byte 48 of the record — and gate2; cell (i, j) of problem b is a candidate only where resid2(Rt_b, src[i], tgt[j]) < gate2.  A
+// problem whose status is not SC_OK is skipped: its count pair is (0, 0) and nothing else of it is read or written.  g2 (optional):
+// the gate residual of every output entry, slot-positioned like d2.
+struct MatchBatchGuide {
+  const float* src; const float* tgt;
+  uint32_t s_elem, s_comp, t_elem, t_comp;
+  const void* pose;
+  uint32_t pose_stride, use_status;
+  float gate2;
+  float* g2;
+};
+// Types of their own, so that the unguided forms' kernel arguments and code stay what they were; everything the base says holds, and
+// `clean` is also cleared when a point of the problem or its pose is not finite, whatever the gate excludes.
+struct MatchGuidedBatchJob : MatchBatchJob { MatchBatchGuide gd; };
+struct MatchGuidedPairsJob : MatchPairsJob { MatchBatchGuide gd; };
+void launch_match_guided_batch_dist(const MatchGuidedBatchJob& job, hipStream_t st);
+void launch_match_guided_batch_finish(const MatchGuidedBatchJob& job, hipStream_t st);
+void launch_match_guided_pairs_dist(const MatchGuidedPairsJob& job, hipStream_t st);
+void launch_match_guided_pairs_finish(const MatchGuidedPairsJob& job, hipStream_t st);
+
 }  // namespace sc

@@ -23,7 +23,21 @@
 // (sc_match_pairs: listed pairs of shared sets, addressed by a record per pair, sc_kernels.hpp).  What differs is where a problem's
 // rows, lists, column minima and slot start: MatchView, filled by view_of for either argument; everything behind it is one text, so
 // a pair's slot holds what the packed form returns for the pair expanded.  The packed instantiation reads what it always read.
+//
+// sc_match_guided_batch (MatchGuidedBatchJob, MatchGuidedPairsJob: the same two arguments with a MatchBatchGuide behind them) is the
+// same pair of launches with a pose prior per problem, as sc_match.hip's GUIDED is for one frame: problem b's pose goes into scalar
+// registers, the tile's 64 source points into LDS once and a column tile's 64 target points per tile; every thread folds its 8 x 4
+// decisions resid2(Rt_b, p_i, q_j) < gate2 into one 32-bit word BEFORE the descriptor chunks (a loop over its rows), an inadmissible
+// cell offers no key — not to the row's list, not to the column minimum — and a tile in which no cell of the workgroup is admissible
+// is skipped altogether (a workgroup-wide OR behind a barrier every thread passes).  A skipped tile's descriptors are never staged, so the
+// finiteness rule is carried by a scan of its own: the ceil(ns_b / 64) workgroups of problem b share a strided scan of the problem's
+// OWN descriptor and point ranges — nothing of a neighbour's — and each tests the pose.  A problem whose record carries a status
+// other than SC_OK (SC_GUIDE_POSE_STATUS) returns before any of this.  GUIDED is a property of the job's type: the unguided
+// instantiations keep their arguments and their code.
 #include <cstddef>
+#include <type_traits>
+
+#include "sc_arith.hpp"
 
 #include "sc_block.hpp"
 #include "sc_kernels.hpp"
@@ -58,8 +72,22 @@ __device__ __forceinline__ MatchView view_of(const MatchPairsJob& job, uint32_t 
                    r[PW_TOP], (size_t)r[PW_COL_LO] | (size_t)r[PW_COL_HI] << 32, r[PW_SLOT]};
 }
 
+// is this job one of the guided forms?  (Decided by the type: the template arguments, hence the names, of the unguided kernels stay.)
+template <class Job> struct guided_job : std::false_type {};
+template <> struct guided_job<MatchGuidedBatchJob> : std::true_type {};
+template <> struct guided_job<MatchGuidedPairsJob> : std::true_type {};
+
+// problem b's pose record: 12 floats, and behind them the status when the caller says there is one
+__device__ __forceinline__ const float* pose_of(const MatchBatchGuide& gd, uint32_t b) {
+  return reinterpret_cast<const float*>(static_cast<const char*>(gd.pose) + (size_t)b * gd.pose_stride);
+}
+__device__ __forceinline__ bool pose_skipped(const MatchBatchGuide& gd, const float* rec) {
+  return gd.use_status != 0u && reinterpret_cast<const int32_t*>(rec)[12] != 0;  // (SC_OK is 0)
+}
+
 template <int KP, class Job>
 __global__ __launch_bounds__(MB_THREADS) void match_batch_dist_kernel(const Job job) {
+  constexpr bool GUIDED = guided_job<Job>::value;
   __shared__ __attribute__((aligned(16))) float sA[MT_KC][MB_LD];
   __shared__ __attribute__((aligned(16))) float sB[MT_KC][MB_LD];
   __shared__ unsigned long long s_top[MB_ROWS][KP];
@@ -68,6 +96,13 @@ __global__ __launch_bounds__(MB_THREADS) void match_batch_dist_kernel(const Job 
   if (blockIdx.x >= job.n_tiles) return;
   const uint32_t b = job.tile_map[2 * blockIdx.x], row0 = job.tile_map[2 * blockIdx.x + 1];
   if (b >= job.n_problems) return;  // (cannot happen: the host built the map)
+  float M[12];  // GUIDED: the problem's pose (workgroup-uniform: scalar registers)
+  if constexpr (GUIDED) {
+    const float* rec = pose_of(job.gd, b);
+    if (pose_skipped(job.gd, rec)) return;  // nothing else of a skipped problem is read or written
+#pragma unroll
+    for (int k = 0; k < 12; k++) M[k] = rec[k];
+  }
   const MatchView v = view_of(job, b);
   const uint32_t ns = v.ns, nt = v.nt, D = job.dim;
   const float* __restrict__ fsrc = v.fsrc;
@@ -76,9 +111,66 @@ __global__ __launch_bounds__(MB_THREADS) void match_batch_dist_kernel(const Job 
   const uint32_t n_tiles = (nt + MB_COLS - 1) / MB_COLS;
   for (int e = threadIdx.x; e < MB_ROWS * KP; e += MB_THREADS) (&s_top[0][0])[e] = KEY_NONE;
   bool bad = false;
+  float(*sP)[MB_ROWS] = nullptr;  // GUIDED: the tile's source points, component-major
+  float(*sQ)[MB_COLS] = nullptr;  // GUIDED: the column tile's target points
+  uint32_t adm = 0;               // GUIDED: bit r * 4 + cc: cell (row r, column cc) of this thread is admissible in this column tile
+  if constexpr (GUIDED) {
+    __shared__ float s_src[3][MB_ROWS];
+    __shared__ float s_tgt[3][MB_COLS];
+    sP = s_src; sQ = s_tgt;
+    const MatchBatchGuide& gd = job.gd;
+#pragma unroll
+    for (int k = 0; k < 12; k++) bad = bad || not_finite(M[k]);
+    // The finiteness rule depends on the input alone: the problem's workgroups share every element of ITS descriptors and points,
+    // whatever tiles the gate drops below.  (A point is read through the strides: in SoA a problem's points are three ranges.)
+    const size_t stride = (size_t)((ns + MB_ROWS - 1) / MB_ROWS) * MB_THREADS, me = (size_t)(row0 / MB_ROWS) * MB_THREADS + threadIdx.x;
+    for (size_t e = me; e < (size_t)ns * D; e += stride) bad = bad || not_finite(fsrc[e]);
+    for (size_t e = me; e < (size_t)nt * D; e += stride) bad = bad || not_finite(ftgt[e]);
+    for (size_t e = me; e < (size_t)ns * 3; e += stride)
+      bad = bad || not_finite(gd.src[((size_t)v.so + e / 3) * gd.s_elem + (e % 3) * gd.s_comp]);
+    for (size_t e = me; e < (size_t)nt * 3; e += stride)
+      bad = bad || not_finite(gd.tgt[((size_t)v.to + e / 3) * gd.t_elem + (e % 3) * gd.t_comp]);
+    for (int e = threadIdx.x; e < 3 * MB_ROWS; e += MB_THREADS) {
+      const uint32_t comp = e / MB_ROWS, lr = e % MB_ROWS, row = row0 + lr;
+      sP[comp][lr] = row < ns ? gd.src[((size_t)v.so + row) * gd.s_elem + (size_t)comp * gd.s_comp] : 0.f;
+    }
+  }
   for (uint32_t tile = 0; tile < n_tiles; tile++) {
     const uint32_t col0 = tile * MB_COLS;
     if (threadIdx.x < MB_COLS) s_col[threadIdx.x] = KEY_NONE;
+    if constexpr (GUIDED) {
+      const MatchBatchGuide& gd = job.gd;
+      // (nobody still reads the tile before: its last read of sQ is in front of that tile's OR barrier, which every thread has passed)
+      for (int e = threadIdx.x; e < 3 * MB_COLS; e += MB_THREADS) {
+        const uint32_t comp = e / MB_COLS, lc = e % MB_COLS, col = col0 + lc;
+        sQ[comp][lc] = col < nt ? gd.tgt[((size_t)v.to + col) * gd.t_elem + (size_t)comp * gd.t_comp] : 0.f;
+      }
+      __syncthreads();  // sQ (and, first tile, sP, the lists' and s_col's initial values) are written
+      // The thread's 4 target points in registers, its 8 rows rolled.  (All 32 cells unrolled cost sc_match.hip's kernel 60+ registers
+      // and a wave per SIMD; this kernel runs two waves per SIMD with or without a gate, and the half-rolled form stays within them:
+      // 203 - 205 registers.  The cell's indices are constants here and a row's point is read once for 4 cells: measured 7 % faster
+      // than the loop over 32 cells)
+      adm = 0;
+      {
+        float qx[4], qy[4], qz[4];
+#pragma unroll
+        for (int cc = 0; cc < 4; cc++) { qx[cc] = sQ[0][tx * 4 + cc]; qy[cc] = sQ[1][tx * 4 + cc]; qz[cc] = sQ[2][tx * 4 + cc]; }
+#pragma unroll 1
+        for (int r = 0; r < 8; r++) {
+          const uint32_t lr = ty * 8 + r;
+          const float px = sP[0][lr], py = sP[1][lr], pz = sP[2][lr];
+          const bool row_in = row0 + lr < ns;
+#pragma unroll
+          for (int cc = 0; cc < 4; cc++) {
+            // a float <: a NaN or infinite residual is never admissible
+            const bool in = row_in && col0 + tx * 4 + cc < nt && resid2(M, px, py, pz, qx[cc], qy[cc], qz[cc]) < gd.gate2;
+            adm |= (in ? 1u : 0u) << (r * 4 + cc);
+          }
+        }
+      }
+      // workgroup-uniform, and every thread passes this barrier on both paths; nothing of a skipped tile is a candidate
+      if (!__syncthreads_or(adm != 0u)) continue;
+    }
     f2 acc[8][2];
 #pragma unroll
     for (int r = 0; r < 8; r++) { acc[r][0] = f2{0.f, 0.f}; acc[r][1] = f2{0.f, 0.f}; }
@@ -125,6 +217,9 @@ __global__ __launch_bounds__(MB_THREADS) void match_batch_dist_kernel(const Job 
 #pragma unroll
       for (int cc = 0; cc < 4; cc++) {
         if (colb + cc >= nt) continue;
+        if constexpr (GUIDED) {
+          if (!((adm >> (r * 4 + cc)) & 1u)) continue;  // an inadmissible cell offers no key
+        }
         const unsigned long long hi = (unsigned long long)__float_as_uint(d[cc]) << 32;
         const unsigned long long key = hi | (colb + cc);
         const unsigned long long rkey = hi | row;
@@ -158,7 +253,18 @@ __global__ __launch_bounds__(MB_THREADS) void match_batch_dist_kernel(const Job 
 template <class Job>
 __global__ __launch_bounds__(MBF_THREADS) void match_batch_finish_kernel(const Job job) {
   __shared__ uint64_t s_scan[MBF_THREADS / 64];
+  constexpr bool GUIDED = guided_job<Job>::value;
   const uint32_t b = blockIdx.x;
+  float M[12];  // GUIDED: the problem's pose
+  if constexpr (GUIDED) {
+    const float* rec = pose_of(job.gd, b);
+    if (pose_skipped(job.gd, rec)) {  // (0, 0), and nothing else of the problem is read or written
+      if (threadIdx.x == 0) { job.count[2 * b] = 0u; job.count[2 * b + 1] = 0u; }
+      return;
+    }
+#pragma unroll
+    for (int k = 0; k < 12; k++) M[k] = rec[k];
+  }
   const MatchView v = view_of(job, b);
   const uint32_t so = v.so, to = v.to, ns = v.ns, nt = v.nt;
   const size_t slot = v.slot, cap = (size_t)ns * job.knn;
@@ -206,6 +312,18 @@ __global__ __launch_bounds__(MBF_THREADS) void match_batch_finish_kernel(const J
           g.gtgt[3 * e + c] = g.tgt[((size_t)to + j) * g.t_elem + (size_t)c * g.t_comp];
         }
       }
+      if constexpr (GUIDED) {
+        const MatchBatchGuide& gd = job.gd;
+        if (gd.g2) {  // the gate residual of the entry: the distance launch's chain on the same points
+          float p[3], q[3];
+#pragma unroll
+          for (int c = 0; c < 3; c++) {
+            p[c] = gd.src[((size_t)so + i) * gd.s_elem + (size_t)c * gd.s_comp];
+            q[c] = gd.tgt[((size_t)to + j) * gd.t_elem + (size_t)c * gd.t_comp];
+          }
+          gd.g2[e] = resid2(M, p[0], p[1], p[2], q[0], q[1], q[2]);
+        }
+      }
     }
     run += (uint32_t)tot;
   }
@@ -218,6 +336,11 @@ __global__ __launch_bounds__(MBF_THREADS) void match_batch_finish_kernel(const J
 }  // namespace
 
 namespace {
+
+template <class Job>
+void launch_finish(const Job& job, hipStream_t st) {
+  hipLaunchKernelGGL(match_batch_finish_kernel<Job>, dim3(job.n_problems), dim3(MBF_THREADS), 0, st, job);
+}
 
 template <class Job>
 void launch_dist(const Job& job, hipStream_t st) {
@@ -241,5 +364,10 @@ void launch_match_batch_finish(const MatchBatchJob& job, hipStream_t st) {
 void launch_match_pairs_finish(const MatchPairsJob& job, hipStream_t st) {
   hipLaunchKernelGGL(match_batch_finish_kernel<MatchPairsJob>, dim3(job.n_problems), dim3(MBF_THREADS), 0, st, job);
 }
+
+void launch_match_guided_batch_dist(const MatchGuidedBatchJob& job, hipStream_t st) { launch_dist(job, st); }
+void launch_match_guided_pairs_dist(const MatchGuidedPairsJob& job, hipStream_t st) { launch_dist(job, st); }
+void launch_match_guided_batch_finish(const MatchGuidedBatchJob& job, hipStream_t st) { launch_finish(job, st); }
+void launch_match_guided_pairs_finish(const MatchGuidedPairsJob& job, hipStream_t st) { launch_finish(job, st); }
 
 }  // namespace sc
