@@ -49,6 +49,7 @@ extern "C" {
 #define SC_HAS_POLISH_POSES 1  /* this header declares sc_polish_poses* (added within 0.10) */
 #define SC_HAS_ASSIGN 1  /* this header declares sc_assign_poses* and sc_assign_default_params (added within 0.10) */
 #define SC_HAS_MATCH_GUIDED 1  /* this header declares sc_match_guided*, sc_register_guided_features and sc_guide_default_params (added within 0.10) */
+#define SC_HAS_MATCH_GUIDED_POSES 1  /* this header declares sc_match_guided_poses*, sc_register_guided_poses_features and SC_GUIDE_MAX_POSES (added within 0.10) */
 #define SC_HAS_MATCH_GUIDED_BATCH 1  /* this header declares sc_match_guided_batch*, sc_match_guided_pairs* and sc_register_guided_{batch,pairs}_features_device (added within 0.10) */
 
 /* status codes */
@@ -487,7 +488,7 @@ int sc_register_features(sc_ctx* ctx, const float* src_pts, const float* fsrc, i
  * Refused with SC_EINVAL on the host before anything is enqueued, sc_last_error naming which: every rule of sc_match_params; a NULL
  * argument (g2 / d_g2 excepted); guide->size wrong; a layout above SC_SOA; a gate that is not finite and > 0; a flag or reserved word
  * that is not 0; a call outstanding on the context.
- * Not here: batch and pairs forms (entries of their own: sc_match_guided_batch, below); several poses per call; a gate on anything but the point residual (descriptor-space or scale
+ * Not here: batch and pairs forms (entries of their own: sc_match_guided_batch, below); several poses per call (entries of their own: sc_match_guided_poses, below); a gate on anything but the point residual (descriptor-space or scale
  * gates); soft weighting by g2. */
 typedef struct sc_guide_params {   /* 32 bytes */
   uint32_t size;         /* = sizeof(sc_guide_params)                                                  */
@@ -809,7 +810,8 @@ int sc_polish_pairs_slots_device(sc_ctx* ctx, const float* d_pts, const uint32_t
  * (sc_match_pairs) and their features entries refuse; every rule of sc_guide_params, but that guide->flags may be
  * SC_GUIDE_POSE_STATUS (any other bit is refused; sc_match_guided* and sc_register_guided_features keep refusing every flag); a
  * pose_stride that breaks the rule above; a NULL argument (g2 / d_g2 excepted); a call outstanding on the context.
- * Not here: host forms of the two features entries; one pose shared by all problems, and several poses per problem; an instances
+ * Not here: host forms of the two features entries; one pose shared by all problems, and several poses per problem (several poses
+ * in ONE problem are the frame form's: sc_match_guided_poses, below); an instances
  * form. */
 #define SC_GUIDE_POSE_STATUS 1u   /* sc_guide_params.flags, these entries only: the pose records hold an int32 status at byte 48 */
 /* Everything but the offsets in HBM; enqueues on the context's stream and returns without waiting. */
@@ -843,6 +845,58 @@ int sc_register_guided_pairs_features_device(sc_ctx* ctx, const float* d_pts, co
                                              const sc_guide_params* gp, const void* d_pose, uint32_t pose_stride,
                                              const sc_params* params, sc_batch_result* d_res, int32_t* d_corr, float* d_d2,
                                              float* d_g2, uint32_t* d_count, uint8_t* d_mask);
+
+/* ---- descriptor matching gated by several poses: sc_match_guided_poses --------------------------------------------
+ * The entrance of the multi-motion chain: sc_register_instances / sc_peel find K rigid motions, sc_polish_poses refits them,
+ * sc_assign_poses_frame relabels, sc_pose_info_frame weighs — and the match that produces better correspondences once the poses are
+ * known took one pose.  K calls of sc_match_guided are not this operation: each re-assigns every source keypoint under its own pose
+ * alone, the K lists overlap and disagree, and each call's mutual and ratio tests see that pose's admissible set only.  Here ONE
+ * match is gated by the union over the poses: target j is a candidate for source i if SOME pose puts i near it, the nearest
+ * descriptor among all such candidates wins, and every output entry says which pose admitted it.  A function of the input alone,
+ * bit for bit; everything not named here — the descriptor distance, both u64 key orders, knn 1 .. 4, mutual and ratio over the
+ * admissible set, the output order, the layouts, the determinism, frames and workspace — is sc_match_guided's.
+ *   The pose records are those of sc_assign_poses / sc_polish_poses: n_poses records pose_stride bytes apart, float Rt[12] at byte
+ *   0 and, with SC_GUIDE_POSE_STATUS in guide->flags (these entries accept it; sc_match_guided* keeps refusing it), an int32 status
+ *   at byte 48.  pose_stride: a multiple of 4, >= 48, and >= 52 with the flag.  1 <= n_poses <= SC_GUIDE_MAX_POSES.  The records
+ *   are read, never written.
+ *   g2_k(i, j): the gate residual of sc_match_guided under record k; gate2 as there.
+ *   use(k): true without the flag; with it, status_k == SC_OK.  A record that is not used is skipped: its Rt is neither read for
+ *   the gate nor tested for finiteness (failed records of sc_register_instances_batch hold the identity, which would admit pairs).
+ *   adm(i, j) <=> there is a k with use(k) and g2_k(i, j) < gate2, a float <: a NaN or infinite residual never admits.
+ *   Every output entry (i, j): label = the used k with the smallest g2_k(i, j), ties to the lowest k; g2 = that minimum; the entry
+ *   is admissible, so g2 < gate2.  label is n x int32 — the array sc_polish_poses and sc_pose_info_frame accept as SEL_LABEL
+ *   (label0 = 0) when a registration on these correspondences has left its frame.
+ *   count[0] = n; count[1] = 1 iff a descriptor, a point or one of the 12 floats of a USED record is not finite — then n = 0, and
+ *   the host forms return SC_EINVAL with *n = 0.  As in sc_match_guided the flag depends on the whole input, not on what the gate
+ *   drops.  No record used: n = 0, and count[1] reports the descriptors and points only.
+ *   n_poses == 1 without the flag: corr, d2, g2 and count equal sc_match_guided_device on that pose bit for bit; every label is 0.
+ * Stream operations of the device form: those of sc_match_guided_device — a memset and two launches, no host word.  d_pose is read
+ * in stream order: it may be what sc_polish_poses_device, or a copy on the same stream, just wrote.
+ * Refused with SC_EINVAL on the host before anything is enqueued, sc_last_error naming which: everything sc_match_guided refuses
+ * (but SC_GUIDE_POSE_STATUS); a NULL d_pose; n_poses out of range; a pose_stride that breaks the rule; any other flag.
+ * Not here: batch and pairs forms of the several-pose gate; a gate radius per pose; per-pose tallies (sc_assign_poses_frame counts
+ * them); soft weighting by the residuals. */
+#define SC_GUIDE_MAX_POSES 64u
+/* Every buffer in HBM.  d_corr, d_d2, d_g2, d_count as sc_match_guided_device's; d_label: ns * knn int32 or NULL. */
+int sc_match_guided_poses_device(sc_ctx* ctx, const float* d_src_pts, const float* d_fsrc, int64_t ns, const float* d_tgt_pts,
+                                 const float* d_ftgt, int64_t nt, const sc_match_params* mp, const sc_guide_params* gp,
+                                 const void* d_pose, uint32_t pose_stride, uint32_t n_poses, int32_t* d_corr, float* d_d2,
+                                 float* d_g2, int32_t* d_label, uint32_t* d_count);
+/* The same with host arrays (pose: n_poses * pose_stride bytes, copied as given; corr, d2, g2, label: room for ns * knn entries,
+ * g2 and label may be NULL; the first *n are written); waits.  A non-finite descriptor, point or used pose: SC_EINVAL, *n = 0. */
+int sc_match_guided_poses(sc_ctx* ctx, const float* src_pts, const float* fsrc, int64_t ns, const float* tgt_pts, const float* ftgt,
+                          int64_t nt, const sc_match_params* mp, const sc_guide_params* gp, const void* pose, uint32_t pose_stride,
+                          uint32_t n_poses, int32_t* corr, float* d2, float* g2, int32_t* label, uint32_t* n);
+/* sc_register_guided_features with the several-pose match in front: that match, the gather on the device, then the unchanged
+ * sc_register_device on the gathered arrays, with one host wait (the count).  guide->layout must equal params->layout; g2 and label
+ * may be NULL.  corr, d2, g2, label, *n are valid whenever the match itself succeeded; n < 3: SC_ENOHYP with R = I, t = 0 and the
+ * mask untouched; otherwise status, R, t, mask and stats are exactly those of sc_register on the gathered correspondences, and the
+ * call leaves that frame: sc_polish_poses / sc_pose_info_frame with SEL_LABEL and the returned labels may follow. */
+int sc_register_guided_poses_features(sc_ctx* ctx, const float* src_pts, const float* fsrc, int64_t ns, const float* tgt_pts,
+                                      const float* ftgt, int64_t nt, const sc_match_params* mp, const sc_guide_params* gp,
+                                      const void* pose, uint32_t pose_stride, uint32_t n_poses, const sc_params* params, float R[9],
+                                      float t[3], int32_t* corr, float* d2, float* g2, int32_t* label, uint32_t* n, uint8_t* mask,
+                                      sc_stats* stats);
 
 /* ---- the fp64 information matrix of a batch's poses: sc_pose_info_batch ------------------------------------------
  * The callers of the batch entries feed every pair's pose into a pose graph or a fusion step as an EDGE, and an edge needs a

@@ -49,6 +49,7 @@ EXPORTS = ["sc_version", "sc_strerror", "sc_default_params", "sc_create", "sc_de
            "sc_polish_pairs_slots_device",
            "sc_match_guided_batch", "sc_match_guided_batch_device", "sc_register_guided_batch_features_device",
            "sc_match_guided_pairs", "sc_match_guided_pairs_device", "sc_register_guided_pairs_features_device",
+           "sc_match_guided_poses", "sc_match_guided_poses_device", "sc_register_guided_poses_features",
            "sc_pose_info_batch", "sc_pose_info_batch_device", "sc_pose_info_batch_slots_device", "sc_pose_info_pairs_slots_device",
            "sc_pose_info_default_params", "sc_pose_info_frame", "sc_pose_info_frame_device",
            "sc_polish_poses_default_params", "sc_polish_poses", "sc_polish_poses_device",
@@ -186,7 +187,8 @@ SC_ASSIGN_MAX_POSES, SC_ASSIGN_BATCH_MAX_POSES = 1024, 64
 SC_ASSIGN_BEST, SC_ASSIGN_FIRST = 0, 1
 SC_ASSIGN_SEL_NONE, SC_ASSIGN_SEL_MASK = 0, 1
 SC_ASSIGN_STATUS = 1
-SC_GUIDE_POSE_STATUS = 1  # sc_guide_params.flags, the sc_match_guided_batch entries only: the pose records hold an int32 status at byte 48
+SC_GUIDE_POSE_STATUS = 1  # sc_guide_params.flags, the sc_match_guided_batch / _poses entries only: the pose records hold an int32 status at byte 48
+SC_GUIDE_MAX_POSES = 64  # pose records per call of sc_match_guided_poses at most
 SC_MATCH_BATCH_MAX_N = 4096  # rows a side of one problem of sc_match_batch
 SC_INSTANCES_BATCH_MAX = 16  # motions per problem of sc_register_instances_batch at most
 
@@ -299,6 +301,11 @@ def load_library() -> C.CDLL:
     L.sc_match_guided.argtypes = [vp, f32p, f32p, C.c_int64, f32p, f32p, C.c_int64, mp, gp, f32p, i32p, f32p, f32p, u32p]
     L.sc_register_guided_features.argtypes = [vp, f32p, f32p, C.c_int64, f32p, f32p, C.c_int64, mp, gp, f32p, pp, f32p, f32p, i32p, f32p,
                                               f32p, u32p, u8p, sp]
+    L.sc_match_guided_poses_device.argtypes = [vp, vp, vp, C.c_int64, vp, vp, C.c_int64, mp, gp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]
+    L.sc_match_guided_poses.argtypes = [vp, f32p, f32p, C.c_int64, f32p, f32p, C.c_int64, mp, gp, vp, C.c_uint32, C.c_uint32, i32p, f32p,
+                                        f32p, i32p, u32p]
+    L.sc_register_guided_poses_features.argtypes = [vp, f32p, f32p, C.c_int64, f32p, f32p, C.c_int64, mp, gp, vp, C.c_uint32, C.c_uint32,
+                                                    pp, f32p, f32p, i32p, f32p, f32p, i32p, u32p, u8p, sp]
     L.sc_match_batch_device.argtypes = [vp, vp, u32p, vp, u32p, C.c_uint32, mp, vp, vp, vp]
     L.sc_match_batch.argtypes = [vp, f32p, u32p, f32p, u32p, C.c_uint32, mp, i32p, f32p, u32p]
     L.sc_register_batch_features_device.argtypes = [vp, vp, vp, u32p, vp, vp, u32p, C.c_uint32, mp, pp, vp, vp, vp, vp, vp]
@@ -738,6 +745,64 @@ class Registrar:
         return dict(status=rc, R=R.reshape(3, 3), t=t, n=k, corr=corr[:k].copy(), d2=d2[:k].copy(), g2=g2[:k].copy(),
                     mask=mask[:k].copy(), stats=st.as_dict())
 
+    # ---- descriptor matching gated by several poses (include/saccot.h, sc_match_guided_poses) -------------------
+    def match_guided_poses(self, src_pts, fsrc, tgt_pts, ftgt, pose, gate: float | None = None, layout: int = SC_AOS, flags: int = 0,
+                           mparams: ScMatchParams | None = None, gparams: ScGuideParams | None = None, **kw):
+        """sc_match_guided_poses: match_guided under the union of K poses.  pose: K records (_pose_records: a (K, 12) float array, or
+        records of a dtype that starts with float Rt[12] and, with SC_GUIDE_POSE_STATUS in flags, holds an int32 status at byte 48)
+        -> dict(n, corr (n, 2) int32, d2 (n,), g2 (n,): the smallest gate residual of every entry, label (n,) int32: the record
+        it belongs to).  kw: knn, mutual, ratio (make_match_params)."""
+        g = gparams or make_guide_params(gate, layout, flags)
+        src_pts, fsrc, tgt_pts, ftgt = self._guided_inputs("match_guided_poses", src_pts, fsrc, tgt_pts, ftgt, g.layout)
+        pose, stride = self._pose_records(pose)
+        m = mparams or make_match_params(fsrc.shape[1], **kw)
+        cap = max(fsrc.shape[0] * max(int(m.knn), 1), 1)
+        corr = np.zeros((cap, 2), np.int32); d2 = np.zeros(cap, np.float32); g2 = np.zeros(cap, np.float32); n = C.c_uint32(0)
+        label = np.zeros(cap, np.int32)
+        self._check(self._lib.sc_match_guided_poses(self._h, _p(src_pts, C.c_float), _p(fsrc, C.c_float), fsrc.shape[0],
+                                                    _p(tgt_pts, C.c_float), _p(ftgt, C.c_float), ftgt.shape[0], C.byref(m), C.byref(g),
+                                                    pose.ctypes.data_as(C.c_void_p), stride, len(pose), _p(corr, C.c_int32),
+                                                    _p(d2, C.c_float), _p(g2, C.c_float), _p(label, C.c_int32), C.byref(n)))
+        k = int(n.value)
+        return dict(n=k, corr=corr[:k].copy(), d2=d2[:k].copy(), g2=g2[:k].copy(), label=label[:k].copy())
+
+    def match_guided_poses_device(self, d_src_pts: int, d_fsrc: int, ns: int, d_tgt_pts: int, d_ftgt: int, nt: int, mparams: ScMatchParams,
+                                  gparams: ScGuideParams, d_pose: int, pose_stride: int, n_poses: int, d_corr: int, d_d2: int,
+                                  d_g2: int | None, d_label: int | None, d_count: int):
+        """sc_match_guided_poses_device: everything in HBM (d_pose: n_poses records pose_stride bytes apart, read in stream order;
+        d_corr, d_d2, d_g2, d_count as match_guided_device's; d_label: ns * knn int32 or None); three stream operations on the
+        context's stream, returns without waiting."""
+        self._check(self._lib.sc_match_guided_poses_device(self._h, d_src_pts, d_fsrc, ns, d_tgt_pts, d_ftgt, nt, C.byref(mparams),
+                                                           C.byref(gparams), d_pose, pose_stride, n_poses, d_corr, d_d2, d_g2, d_label,
+                                                           d_count))
+
+    def register_guided_poses_features(self, src_pts, fsrc, tgt_pts, ftgt, pose, gate: float | None = None, flags: int = 0,
+                                       mparams: ScMatchParams | None = None, gparams: ScGuideParams | None = None,
+                                       params: ScParams | None = None, knn: int = 1, mutual: bool = False, ratio: float = 0.0, **kw):
+        """sc_register_guided_poses_features: register_features with the several-pose match in front -> dict(status, R, t, n,
+        corr (n, 2), d2 (n,), g2 (n,), label (n,), mask (n,), stats).  Fewer than 3 matches: SC_ENOHYP, R = I.  Leaves a frame of n
+        correspondences: polish_poses / pose_info_frame with SEL_LABEL and the returned labels may follow."""
+        p = params or make_params(**kw)
+        g = gparams or make_guide_params(gate, p.layout, flags)
+        src_pts, fsrc, tgt_pts, ftgt = self._guided_inputs("register_guided_poses_features", src_pts, fsrc, tgt_pts, ftgt, g.layout)
+        pose, stride = self._pose_records(pose)
+        m = mparams or make_match_params(fsrc.shape[1], knn, mutual, ratio)
+        ns, nt = fsrc.shape[0], ftgt.shape[0]
+        cap = max(ns * max(int(m.knn), 1), 1)
+        corr = np.zeros((cap, 2), np.int32); d2 = np.zeros(cap, np.float32); g2 = np.zeros(cap, np.float32); n = C.c_uint32(0)
+        label = np.zeros(cap, np.int32)
+        R = np.zeros(9, np.float32); t = np.zeros(3, np.float32); mask = np.zeros(cap, np.uint8)
+        st = ScStats(C.sizeof(ScStats))
+        rc = self._check(self._lib.sc_register_guided_poses_features(
+            self._h, _p(src_pts, C.c_float), _p(fsrc, C.c_float), ns, _p(tgt_pts, C.c_float), _p(ftgt, C.c_float), nt, C.byref(m),
+            C.byref(g), pose.ctypes.data_as(C.c_void_p), stride, len(pose), C.byref(p), _p(R, C.c_float), _p(t, C.c_float),
+            _p(corr, C.c_int32), _p(d2, C.c_float), _p(g2, C.c_float), _p(label, C.c_int32), C.byref(n), _p(mask, C.c_uint8), C.byref(st)),
+            allow=(SC_ENOHYP,))
+        k = int(n.value)
+        self._frame_n = k
+        return dict(status=rc, R=R.reshape(3, 3), t=t, n=k, corr=corr[:k].copy(), d2=d2[:k].copy(), g2=g2[:k].copy(),
+                    label=label[:k].copy(), mask=mask[:k].copy(), stats=st.as_dict())
+
     # ---- descriptor matching for a batch of small problems (include/saccot.h, sc_match_batch) -------------------
     @staticmethod
     def _offsets(sizes):
@@ -1026,9 +1091,10 @@ class Registrar:
 
     # ---- pose-gated matching for batches and pairs (include/saccot.h, sc_match_guided_batch) ---------------------------
     @staticmethod
-    def _pose_records(pose, n):
+    def _pose_records(pose, n=None):
         """pose records as the entries take them: an (n, 12) float array (stride 48), or n records of any dtype whose items start
-        with float Rt[12] (and, with SC_GUIDE_POSE_STATUS, an int32 status at byte 48) -> (contiguous array, stride)"""
+        with float Rt[12] (and, with SC_GUIDE_POSE_STATUS, an int32 status at byte 48) -> (contiguous array, stride); n = None:
+        as many as there are"""
         pose = np.ascontiguousarray(pose)
         if pose.dtype.fields is None:
             pose = np.ascontiguousarray(pose, np.float32).reshape(-1, 12)
@@ -1036,7 +1102,7 @@ class Registrar:
         else:
             pose = pose.reshape(-1)
             stride = pose.dtype.itemsize
-        if len(pose) != n:
+        if n is not None and len(pose) != n:
             raise ValueError("one pose record per problem")
         return pose, stride
 

@@ -30,17 +30,15 @@ int match_check(sc_ctx* c, const sc_match_params* mp, int64_t ns, int64_t nt, Ma
   return SC_OK;
 }
 
-}  // namespace sc
-
-namespace {
-
+// ---- the sequence's steps, shared with sc_capi_match_guided_poses.hip (declared in sc_ctx.hpp)
 // match_words: [0] clean, [2], [3] the host entries' count pair, [4 .. 15] the guided host entries' copy of the pose; the column minima from byte 64
 constexpr size_t MATCH_WORDS_HEAD = 64, MATCH_WORDS_POSE = 16;
 
 // gd (sc_match_guided; nullptr: none): the points, the strides and gate2; its pose is gd->Rt in HBM, or — h_Rt, the host entries —
-// 12 host floats that are copied into the head of match_words behind the memset.  d_g2: optional with a guide.
+// 12 host floats that are copied into the head of match_words behind the memset.  d_g2: optional with a guide.  With pose records
+// (gd->n_poses > 0: sc_match_guided_poses) gd->pose is their place in HBM, and d_label optional.
 int match_enqueue(sc_ctx* c, const MatchJob& job, int32_t* d_corr, float* d_d2, uint32_t* d_count, const MatchGather& g, bool to_host,
-                  const MatchGuide* gd = nullptr, const float* h_Rt = nullptr, float* d_g2 = nullptr) {
+                  const MatchGuide* gd, const float* h_Rt, float* d_g2, int32_t* d_label) {
   hipStream_t st = c->stream;
   const MatchPlan plan = match_plan(job.ns, job.nt, job.knn, job.r2);
   ENSURE(c, c->match_part, plan.part_bytes);
@@ -63,7 +61,7 @@ int match_enqueue(sc_ctx* c, const MatchJob& job, int32_t* d_corr, float* d_d2, 
   if (to_host) arm_word(c, HW_MATCH);
   launch_match_dist(job, plan, c->match_part.as<uint64_t>(), colmin, clean, gd ? &guide : nullptr, st);
   launch_match_finish(job, plan, c->match_part.as<uint64_t>(), colmin, clean, d_corr, d_d2, d_count ? d_count : clean + 2, g, lb,
-                      to_host ? &c->pinned[HW_MATCH] : nullptr, gd ? &guide : nullptr, d_g2, st);
+                      to_host ? &c->pinned[HW_MATCH] : nullptr, gd ? &guide : nullptr, d_g2, st, d_label);
   HIPCHK(c, hipGetLastError());
   return SC_OK;
 }
@@ -83,7 +81,7 @@ int match_stage_host(sc_ctx* c, MatchJob* job, const float* fsrc, const float* f
 
 // the host entries' one wait — the count, or SC_EINVAL for a non-finite descriptor — and the read-back of that many matches
 // (enqueued: the caller synchronises)
-int match_results_to_host(sc_ctx* c, int32_t* corr, float* d2, uint32_t* found, const char* flagged = "non-finite descriptor") {
+int match_results_to_host(sc_ctx* c, int32_t* corr, float* d2, uint32_t* found, const char* flagged) {
   *found = 0;
   SC_TRY(wait_word(c, HW_MATCH));
   const uint64_t w = c->pinned[HW_MATCH];
@@ -97,15 +95,6 @@ int match_results_to_host(sc_ctx* c, int32_t* corr, float* d2, uint32_t* found, 
 }
 
 // ---- sc_match_guided --------------------------------------------------------------------------------------------------------------
-constexpr const char* GUIDED_FLAGGED = "non-finite descriptor, point or pose";
-
-// the rules of sc_guide_params (sc_match_guided_check.hpp) -> the guide but for its pointers
-int guide_check(sc_ctx* c, const char* who, const sc_guide_params* gp, MatchGuide* gd) {
-  if (const char* why = guide_params_error(gp)) return refuse(c, who, why);
-  gd->gate2 = guide_gate2(gp->gate);
-  return SC_OK;
-}
-
 // the points of both sets in the guide's layout, as the kernels are told (MatchGather's strides)
 void guide_points(MatchGuide* gd, const float* src, uint32_t ns, const float* tgt, uint32_t nt, uint32_t layout) {
   const MatchGather g = gather_of(src, ns, tgt, nt, (int)layout, nullptr, nullptr);
@@ -120,6 +109,19 @@ int guided_stage_points(sc_ctx* c, const MatchJob& job, const float* src_pts, co
   ENSURE(c, c->match_g2, (size_t)job.ns * job.knn * 4);
   HIPCHK(c, hipMemcpyAsync(c->match_psrc.p, src_pts, (size_t)job.ns * 12, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->match_ptgt.p, tgt_pts, (size_t)job.nt * 12, hipMemcpyHostToDevice, c->stream));
+  return SC_OK;
+}
+
+}  // namespace sc
+
+namespace {
+
+constexpr const char* GUIDED_FLAGGED = MATCH_GUIDED_FLAGGED;
+
+// the rules of sc_guide_params (sc_match_guided_check.hpp) -> the guide but for its pointers
+int guide_check(sc_ctx* c, const char* who, const sc_guide_params* gp, MatchGuide* gd) {
+  if (const char* why = guide_params_error(gp)) return refuse(c, who, why);
+  gd->gate2 = guide_gate2(gp->gate);
   return SC_OK;
 }
 

@@ -109,6 +109,8 @@ struct Workspace {
       // "clean" word, the host entries' count pair, the guided host entries' pose, then the column minima; the rest: device copies of
       // the host entries' arrays (g2: the guided host entries' only, allocated by the first of them)
       match_part, match_words, match_fsrc, match_ftgt, match_psrc, match_ptgt, match_corr, match_d2, match_gsrc, match_gtgt, match_g2,
+      // sc_match_guided_poses, the host forms' device copies of the pose records and of the labels: allocated by the first of them
+      match_pose, match_label,
       // sc_register_batch: allocated by the first batch call, never by a frame.  off: the copy of the caller's offsets; the rest:
       // device copies of the host entry's arrays
       batch_off, batch_src, batch_tgt, batch_res, batch_mask,
@@ -278,6 +280,19 @@ int outputs_to_host(sc_ctx* c, size_t n, float R[9], float t[3], uint8_t* mask);
 // ---- defined in sc_capi_match.hip / sc_capi_batch.hip, used by the other batch files as well
 // the rules of sc_match_params and of ns, nt; fills everything of *job but the descriptor pointers
 int match_check(sc_ctx* c, const sc_match_params* mp, int64_t ns, int64_t nt, MatchJob* job);
+// The steps of a match on one pair of sets (sc_capi_match.hip; sc_capi_match_guided_poses.hip runs the same sequence).
+// match_enqueue: the memset and the two launches; gd (nullptr: no gate) with its pose in HBM, in h_Rt (12 host floats, copied behind
+// the memset) or — gd->n_poses > 0 — as records at gd->pose; d_g2 / d_label optional.  to_host: the finish launch publishes HW_MATCH.
+int match_enqueue(sc_ctx* c, const MatchJob& job, int32_t* d_corr, float* d_d2, uint32_t* d_count, const MatchGather& g, bool to_host,
+                  const MatchGuide* gd = nullptr, const float* h_Rt = nullptr, float* d_g2 = nullptr, int32_t* d_label = nullptr);
+// the host entries' descriptors -> match_fsrc / match_ftgt (enqueued) and room for corr and d2; their keypoints -> match_psrc /
+// match_ptgt and room for g2; the one wait (HW_MATCH) and the read-back of corr and d2 (enqueued: the caller synchronises)
+int match_stage_host(sc_ctx* c, MatchJob* job, const float* fsrc, const float* ftgt);
+int guided_stage_points(sc_ctx* c, const MatchJob& job, const float* src_pts, const float* tgt_pts);
+int match_results_to_host(sc_ctx* c, int32_t* corr, float* d2, uint32_t* found, const char* flagged = "non-finite descriptor");
+constexpr const char* MATCH_GUIDED_FLAGGED = "non-finite descriptor, point or pose";
+// the points of both sets in the guide's layout, as the kernels are told
+void guide_points(MatchGuide* gd, const float* src, uint32_t ns, const float* tgt, uint32_t nt, uint32_t layout);
 // the caller's points (either layout of sc_params, src_rows / tgt_rows of them) -> two n x 3 arrays, as a finish kernel is told
 inline MatchGather gather_of(const float* src, uint32_t src_rows, const float* tgt, uint32_t tgt_rows, int layout, float* gsrc, float* gtgt) {
   const bool soa = layout == SC_SOA;

@@ -714,11 +714,16 @@ struct MatchGather {
 };
 // sc_match_guided: the keypoints of both sets (point i of src is src[i * s_elem + c * s_comp], as MatchGather's), the pose prior (12
 // floats in HBM, read in stream order) and gate2; cell (i, j) is a candidate only where resid2(Rt, src[i], tgt[j]) < gate2.
+// sc_match_guided_poses (n_poses > 0; Rt is not read): n_poses records in HBM, pose_stride bytes apart, float Rt[12] at byte 0 and —
+// use_status — an int32 status at byte 48; a record whose status is not SC_OK is skipped.  Cell (i, j) is a candidate where SOME
+// used record's residual is below gate2; the finish launch labels every entry with the used record of the smallest residual.
 struct MatchGuide {
   const float* src; const float* tgt;
   uint32_t s_elem, s_comp, t_elem, t_comp;
   const float* Rt;
   float gate2;
+  const void* pose;
+  uint32_t pose_stride, n_poses, use_status;
 };
 // colmin (SC_MATCH_MUTUAL, else nullptr): nt keys (distance << 32 | row), all ones at launch.  clean: one word, non-zero at launch,
 // cleared when a non-finite descriptor is read — with a guide (gd != nullptr: sc_match_guided) when any descriptor, any point or the
@@ -728,10 +733,11 @@ void launch_match_dist(const MatchJob& job, const MatchPlan& plan, uint64_t* par
 // merge + mutual / ratio + compaction in (row, rank) order: corr (n x 2 int32), d2 (n), count[0] = n, count[1] = 1 if a non-finite
 // descriptor was read (then n = 0 and nothing else is written).  lb: a look-back launch of match_finish_tiles(ns) tiles (8 bytes of
 // descriptor each).  host_word (optional, pinned): receives n | flag << 32.  gd, g2 (both optional): g2[m] = the gate residual of entry m.
+// label (optional, gd->n_poses > 0 only): label[m] = the used record with the smallest residual of entry m, and g2[m] is that minimum.
 uint32_t match_finish_tiles(uint32_t ns);
 void launch_match_finish(const MatchJob& job, const MatchPlan& plan, const uint64_t* part, const uint64_t* colmin, const uint32_t* clean,
                          int32_t* corr, float* d2, uint32_t* count, const MatchGather& g, LbArgs lb, uint64_t* host_word, const MatchGuide* gd,
-                         float* g2, hipStream_t st);
+                         float* g2, hipStream_t st, int32_t* label = nullptr);
 
 // ---- many small registrations in one launch (sc_register_batch; sc_batch.hip) ------------------------------
 // One problem's result: sc_batch_result of include/saccot.h, field for field (sc_batch.hip asserts the size).

@@ -28,6 +28,13 @@
 // descriptor load, no tile_step (the decision is a workgroup-wide OR behind a barrier every thread passes).  Because a skipped tile's
 // descriptors are never staged, the finiteness rule is carried by a scan of its own in the same launch: every workgroup tests a
 // grid-strided share of both descriptor arrays, both point arrays and the pose.  The finish launch can also emit g2 per entry.
+//
+// sc_match_guided_poses (GATE_POSES) gates by the union over up to 64 pose records: a cell is a candidate where SOME used record's
+// residual is below gate2.  The records are staged once per workgroup in LDS (a record that SC_GUIDE_POSE_STATUS switches off stages
+// nothing: its bit in s_used stays clear, its floats are neither read nor tested) and a cell walks the used records until one admits
+// it — the pose lives in LDS, not in registers, so nothing of it is carried across the accumulate loop.  Everything behind the word
+// `adm` is the single-pose kernel's.  The finish launch evaluates every used record for the at most ns * knn output entries only:
+// label = the record of the smallest residual (ties: the lowest index), g2 = that minimum.
 #include <cstddef>
 #include <type_traits>
 
@@ -56,20 +63,38 @@ __device__ __forceinline__ bool scan_not_finite(const float* __restrict__ p, siz
 // sc_match's kernel takes no guide: an empty argument
 struct NoGuide {};
 
-// The distance launch, said once.  GUIDED = false is sc_match's kernel; GUIDED = true adds the gate.
-template <int KP, bool GUIDED>
+// the gate of a distance launch: none (sc_match), one pose (sc_match_guided), the union over pose records (sc_match_guided_poses)
+// (plain ints, not an enum: the kernel's signature names the gate in an expression, and an unnamed type is numbered differently in
+// the host's and the device's mangling — the stub would register a name the code object does not hold)
+constexpr int GATE_NONE = 0, GATE_POSE = 1, GATE_POSES = 2;
+constexpr int MT_POSES = (int)SC_GUIDE_MAX_POSES;
+static_assert(MT_POSES == 64, "s_used is one 64-bit word, filled by one ballot of a 64-lane wave");
+
+// record k of a pose list: 12 floats, and behind them the status when the caller says there is one
+__device__ __forceinline__ const float* pose_record(const MatchGuide& gd, uint32_t k) {
+  return reinterpret_cast<const float*>(static_cast<const char*>(gd.pose) + (size_t)k * gd.pose_stride);
+}
+__device__ __forceinline__ bool pose_used(const MatchGuide& gd, uint32_t k) {
+  return gd.use_status == 0u || reinterpret_cast<const int32_t*>(pose_record(gd, k))[12] == 0;  // (SC_OK is 0)
+}
+
+// The distance launch, said once.  GATE_NONE is sc_match's kernel; GATE_POSE adds the gate; GATE_POSES the gate of several poses.
+template <int KP, int GATE>
 __global__ __launch_bounds__(MT_THREADS) void match_dist_kernel(const float* __restrict__ fsrc, uint32_t ns,
                                                                 const float* __restrict__ ftgt, uint32_t nt, uint32_t D,
                                                                 uint32_t tiles_per_slice, unsigned long long* __restrict__ part,
                                                                 size_t ld_part, unsigned long long* __restrict__ colmin,
                                                                 uint32_t* __restrict__ clean,
-                                                                typename std::conditional<GUIDED, MatchGuide, NoGuide>::type gd) {
+                                                                typename std::conditional<GATE != GATE_NONE, MatchGuide, NoGuide>::type gd) {
+  constexpr bool GUIDED = GATE != GATE_NONE, POSES = GATE == GATE_POSES;
   __shared__ __attribute__((aligned(16))) float sA[MT_KC][MT_LDA];
   __shared__ __attribute__((aligned(16))) float sB[MT_KC][MT_LDB];
   __shared__ unsigned long long s_top[MT_ROWS][KP];
   __shared__ unsigned long long s_col[MT_COLS];
   __shared__ float sP[GUIDED ? 3 : 1][GUIDED ? MT_ROWS : 1];  // the workgroup's source points, component-major
   __shared__ float sQ[GUIDED ? 3 : 1][GUIDED ? MT_COLS : 1];  // the tile's target points
+  __shared__ __attribute__((aligned(16))) float sM[POSES ? MT_POSES : 1][12];  // GATE_POSES: the used records' floats
+  __shared__ unsigned long long s_used;                                        // ... and bit k: record k is used
   const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;  // the thread's 4 columns / 8 rows; also (component, row) when it loads
   const uint32_t row0 = blockIdx.x * MT_ROWS;
   const uint32_t n_tiles = (nt + MT_COLS - 1) / MT_COLS;
@@ -77,11 +102,26 @@ __global__ __launch_bounds__(MT_THREADS) void match_dist_kernel(const float* __r
   const uint32_t tile_hi = tile_lo + tiles_per_slice < n_tiles ? tile_lo + tiles_per_slice : n_tiles;
   for (int e = threadIdx.x; e < MT_ROWS * KP; e += MT_THREADS) (&s_top[0][0])[e] = KEY_NONE;
   bool bad = false;
-  float M[12];       // GUIDED: the pose (wave-uniform)
-  uint32_t adm = 0;  // GUIDED: bit r * 4 + cc: cell (row r, column cc) of this thread is admissible in this tile
+  float M[POSES ? 1 : 12];  // GATE_POSE: the pose (wave-uniform)
+  uint32_t adm = 0;         // GUIDED: bit r * 4 + cc: cell (row r, column cc) of this thread is admissible in this tile
   if constexpr (GUIDED) {
+    if constexpr (POSES) {
+      // every workgroup stages (and tests) the used records; the tiles' first barrier publishes them
+      for (uint32_t e = threadIdx.x; e < gd.n_poses * 12u; e += MT_THREADS) {
+        const uint32_t k = e / 12u, f = e % 12u;
+        if (!pose_used(gd, k)) continue;
+        const float v = pose_record(gd, k)[f];
+        bad = bad || not_finite(v);
+        sM[k][f] = v;
+      }
+      if (threadIdx.x < 64) {  // (the first wave, whole)
+        const unsigned long long used = __ballot(threadIdx.x < gd.n_poses && pose_used(gd, threadIdx.x));
+        if (threadIdx.x == 0) s_used = used;
+      }
+    } else {
 #pragma unroll
-    for (int k = 0; k < 12; k++) { M[k] = gd.Rt[k]; bad = bad || not_finite(M[k]); }
+      for (int k = 0; k < 12; k++) { M[k] = gd.Rt[k]; bad = bad || not_finite(M[k]); }
+    }
     // the finiteness rule depends on the input alone: every element is tested here, whatever tiles the gate drops below
     const size_t stride = (size_t)gridDim.x * gridDim.y * MT_THREADS;
     const size_t me = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * MT_THREADS + threadIdx.x;
@@ -108,13 +148,30 @@ __global__ __launch_bounds__(MT_THREADS) void match_dist_kernel(const float* __r
       // registers (two waves per SIMD instead of sc_match's three); rolled it stays within the accumulate loop's budget.  The reads
       // are conflict-free: a wave's 4 rows are 8 words apart, its 16 columns 4 words.
       adm = 0;
+      if constexpr (POSES) {
+        const unsigned long long used = s_used;  // (workgroup-uniform)
 #pragma unroll 1
-      for (int cell = 0; cell < 32; cell++) {
-        const uint32_t lr = ty * 8 + (cell >> 2), lc = tx * 4 + (cell & 3);
-        // a float <: a NaN or infinite residual is never admissible
-        const bool ok = row0 + lr < ns && col0 + lc < nt &&
-                        resid2(M, sP[0][lr], sP[1][lr], sP[2][lr], sQ[0][lc], sQ[1][lc], sQ[2][lc]) < gd.gate2;
-        adm |= (ok ? 1u : 0u) << cell;
+        for (int cell = 0; cell < 32; cell++) {
+          const uint32_t lr = ty * 8 + (cell >> 2), lc = tx * 4 + (cell & 3);
+          if (!(row0 + lr < ns && col0 + lc < nt)) continue;
+          const float px = sP[0][lr], py = sP[1][lr], pz = sP[2][lr], qx = sQ[0][lc], qy = sQ[1][lc], qz = sQ[2][lc];
+          // the OR over the used records of the single-pose test (the same chain, the pose read from LDS: a broadcast); the cell
+          // leaves at its first admitting record
+          bool ok = false;
+#pragma unroll 1
+          for (unsigned long long m = used; m != 0ull && !ok; m &= m - 1ull)
+            ok = resid2(sM[__builtin_ctzll(m)], px, py, pz, qx, qy, qz) < gd.gate2;
+          adm |= (ok ? 1u : 0u) << cell;
+        }
+      } else {
+#pragma unroll 1
+        for (int cell = 0; cell < 32; cell++) {
+          const uint32_t lr = ty * 8 + (cell >> 2), lc = tx * 4 + (cell & 3);
+          // a float <: a NaN or infinite residual is never admissible
+          const bool ok = row0 + lr < ns && col0 + lc < nt &&
+                          resid2(M, sP[0][lr], sP[1][lr], sP[2][lr], sQ[0][lc], sQ[1][lc], sQ[2][lc]) < gd.gate2;
+          adm |= (ok ? 1u : 0u) << cell;
+        }
       }
       // workgroup-uniform, and every thread passes this barrier on both paths; nothing of a skipped tile is a candidate
       if (!__syncthreads_or(adm != 0u)) continue;
@@ -203,7 +260,7 @@ __global__ __launch_bounds__(FIN_THREADS) void match_finish_kernel(const unsigne
                                                                    const uint32_t* __restrict__ clean, int32_t* __restrict__ corr,
                                                                    float* __restrict__ d2, uint32_t* __restrict__ count,
                                                                    MatchGather g, LbArgs lb, uint64_t* host_word, MatchGuide gd,
-                                                                   float* __restrict__ g2) {
+                                                                   float* __restrict__ g2, int32_t* __restrict__ label) {
   __shared__ uint32_t s_tile;
   __shared__ uint64_t s_scan[FIN_THREADS / 64];
   __shared__ uint64_t s_prefix;
@@ -268,7 +325,31 @@ __global__ __launch_bounds__(FIN_THREADS) void match_finish_kernel(const unsigne
         g.gtgt[3 * slot + c] = g.tgt[(size_t)j * g.t_elem + (size_t)c * g.t_comp];
       }
     }
-    if (g2) {  // sc_match_guided: the gate residual of the entry, the distance launch's chain on the same points
+    if (gd.n_poses != 0u) {
+      // sc_match_guided_poses: every used record's residual of the entry (the distance launch's chain on the same points); the
+      // smallest, ties to the lowest index — a NaN never wins, and the entry is admissible: some residual is below gate2
+      if (g2 || label) {
+        float p[3], q[3];
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+          p[c] = gd.src[(size_t)i * gd.s_elem + (size_t)c * gd.s_comp];
+          q[c] = gd.tgt[(size_t)j * gd.t_elem + (size_t)c * gd.t_comp];
+        }
+        float best = __uint_as_float(0x7F800000u);
+        int32_t best_k = 0;
+        for (uint32_t k = 0; k < gd.n_poses; k++) {
+          if (!pose_used(gd, k)) continue;
+          const float* rec = pose_record(gd, k);
+          float M[12];
+#pragma unroll
+          for (int f = 0; f < 12; f++) M[f] = rec[f];
+          const float r = resid2(M, p[0], p[1], p[2], q[0], q[1], q[2]);
+          if (r < best) { best = r; best_k = (int32_t)k; }
+        }
+        if (g2) g2[slot] = best;
+        if (label) label[slot] = best_k;
+      }
+    } else if (g2) {  // sc_match_guided: the gate residual of the entry, the distance launch's chain on the same points
       float M[12], p[3], q[3];
 #pragma unroll
       for (int k = 0; k < 12; k++) M[k] = gd.Rt[k];
@@ -315,30 +396,39 @@ void launch_match_dist(const MatchJob& job, const MatchPlan& plan, uint64_t* par
   const dim3 grid(plan.row_blocks, plan.slices), block(MT_THREADS);
   unsigned long long* p = reinterpret_cast<unsigned long long*>(part);
   unsigned long long* cm = reinterpret_cast<unsigned long long*>(colmin);
+  if (gd && gd->n_poses != 0u) {
+    switch (plan.kp) {
+      case 1: hipLaunchKernelGGL((match_dist_kernel<1, GATE_POSES>), grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean, *gd); break;
+      case 2: hipLaunchKernelGGL((match_dist_kernel<2, GATE_POSES>), grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean, *gd); break;
+      case 3: hipLaunchKernelGGL((match_dist_kernel<3, GATE_POSES>), grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean, *gd); break;
+      default: hipLaunchKernelGGL((match_dist_kernel<4, GATE_POSES>), grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean, *gd); break;
+    }
+    return;
+  }
   if (gd) {
     switch (plan.kp) {
-      case 1: hipLaunchKernelGGL((match_dist_kernel<1, true>), grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean, *gd); break;
-      case 2: hipLaunchKernelGGL((match_dist_kernel<2, true>), grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean, *gd); break;
-      case 3: hipLaunchKernelGGL((match_dist_kernel<3, true>), grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean, *gd); break;
-      default: hipLaunchKernelGGL((match_dist_kernel<4, true>), grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean, *gd); break;
+      case 1: hipLaunchKernelGGL((match_dist_kernel<1, GATE_POSE>), grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean, *gd); break;
+      case 2: hipLaunchKernelGGL((match_dist_kernel<2, GATE_POSE>), grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean, *gd); break;
+      case 3: hipLaunchKernelGGL((match_dist_kernel<3, GATE_POSE>), grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean, *gd); break;
+      default: hipLaunchKernelGGL((match_dist_kernel<4, GATE_POSE>), grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean, *gd); break;
     }
     return;
   }
   switch (plan.kp) {
-    case 1: hipLaunchKernelGGL((match_dist_kernel<1, false>), grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean, NoGuide{}); break;
-    case 2: hipLaunchKernelGGL((match_dist_kernel<2, false>), grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean, NoGuide{}); break;
-    case 3: hipLaunchKernelGGL((match_dist_kernel<3, false>), grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean, NoGuide{}); break;
-    default: hipLaunchKernelGGL((match_dist_kernel<4, false>), grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean, NoGuide{}); break;
+    case 1: hipLaunchKernelGGL((match_dist_kernel<1, GATE_NONE>), grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean, NoGuide{}); break;
+    case 2: hipLaunchKernelGGL((match_dist_kernel<2, GATE_NONE>), grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean, NoGuide{}); break;
+    case 3: hipLaunchKernelGGL((match_dist_kernel<3, GATE_NONE>), grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean, NoGuide{}); break;
+    default: hipLaunchKernelGGL((match_dist_kernel<4, GATE_NONE>), grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean, NoGuide{}); break;
   }
 }
 
 void launch_match_finish(const MatchJob& job, const MatchPlan& plan, const uint64_t* part, const uint64_t* colmin, const uint32_t* clean,
                          int32_t* corr, float* d2, uint32_t* count, const MatchGather& g, LbArgs lb, uint64_t* host_word, const MatchGuide* gd,
-                         float* g2, hipStream_t st) {
+                         float* g2, hipStream_t st, int32_t* label) {
   hipLaunchKernelGGL(match_finish_kernel, dim3(match_finish_tiles(job.ns)), dim3(FIN_THREADS), 0, st,
                      reinterpret_cast<const unsigned long long*>(part), plan.ld_part, plan.slices, plan.kp, job,
                      reinterpret_cast<const unsigned long long*>(colmin), clean, corr, d2, count, g, lb, host_word, gd ? *gd : MatchGuide{},
-                     gd ? g2 : nullptr);
+                     gd ? g2 : nullptr, gd && gd->n_poses != 0u ? label : nullptr);
 }
 
 }  // namespace sc
