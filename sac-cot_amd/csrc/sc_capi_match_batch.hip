@@ -8,7 +8,8 @@
 // and nothing is read back — a problem's count, its non-finite flag and its status are words in device memory.  Everything that can
 // refuse the call is decided on the host before anything is enqueued.  The sequence is said once, for this packed form and for the
 // pairs form (sc_capi_pairs.hip): mbatch_room, mbatch_enqueue (a template over the form's job type, sc_ctx.hpp), mbatch_slots_job
-// and mbatch_register take what differs — the metadata's layout and fill, the job's own fields, the launch pair — from the caller.
+// and mbatch_register take what differs — the metadata's layout and fill, the job's own fields — from the caller; the launch pair
+// follows from the job's type (launch_match_batch_dist / _finish, sc_kernels.hpp).
 #include "sc_ctx.hpp"
 
 using namespace sc;
@@ -61,7 +62,7 @@ int mbatch_enqueue_packed(sc_ctx* c, const MatchJob& mj, const Sizes& sz, const 
                           : MatchGather{};
   return mbatch_enqueue(
       c, mj, sz, job, [&](uint32_t* h) { match_batch_meta_fill(src_off, tgt_off, sz.n_problems, mj.knn, MATCH_BATCH_ROWS, sz.meta, h); },
-      launch_match_batch_dist, launch_match_batch_finish, d_corr, d_d2, d_count, g);
+      d_corr, d_d2, d_count, g);
 }
 
 BatchJob mbatch_slots_job(const sc_ctx* c, const Sizes& sz, const sc_params* p) {

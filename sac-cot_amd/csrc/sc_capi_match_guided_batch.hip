@@ -18,9 +18,6 @@ namespace {
 
 using Sizes = MatchBatchSizes;
 
-// a refused NULL argument, named (the context is there: sc_last_error can say which)
-#define GB_NOT_NULL(c, who, arg) do { if (!(arg)) return refuse((c), (who), #arg " is NULL"); } while (0)
-
 // the rules of the guide block and of the pose stride -> the guide but for its pointers
 int guide_check(sc_ctx* c, const char* who, const sc_guide_params* gp, uint32_t pose_stride, MatchBatchGuide* gd) {
   if (const char* why = guide_batch_params_error(gp)) return refuse(c, who, why);
@@ -30,17 +27,10 @@ int guide_check(sc_ctx* c, const char* who, const sc_guide_params* gp, uint32_t 
   gd->use_status = (gp->flags & SC_GUIDE_POSE_STATUS) ? 1u : 0u;
   return SC_OK;
 }
-// a features entry's keypoints are one pair of arrays: the gate and the gather read them the same way
-int layouts_agree(sc_ctx* c, const char* who, const sc_guide_params* gp, const sc_params* p) {
-  if ((int32_t)gp->layout != p->layout) return refuse(c, who, "guide->layout must be params->layout: the keypoints are one pair of arrays");
-  return SC_OK;
-}
 // the points of both sides in the guide's layout (src_rows / tgt_rows of them), the pose records and g2
 void guide_inputs(MatchBatchGuide* gd, const float* src, size_t src_rows, const float* tgt, size_t tgt_rows, uint32_t layout, const void* d_pose,
                   float* d_g2) {
-  const MatchGather g = gather_of(src, (uint32_t)src_rows, tgt, (uint32_t)tgt_rows, (int)layout, nullptr, nullptr);
-  gd->src = g.src; gd->tgt = g.tgt;
-  gd->s_elem = g.s_elem; gd->s_comp = g.s_comp; gd->t_elem = g.t_elem; gd->t_comp = g.t_comp;
+  guide_points(gd, src, src_rows, tgt, tgt_rows, layout);
   gd->pose = d_pose; gd->g2 = d_g2;
 }
 
@@ -58,7 +48,7 @@ int packed_match(sc_ctx* c, const MatchJob& mj, const Sizes& sz, const MatchBatc
                           : MatchGather{};
   return mbatch_enqueue(
       c, mj, sz, job, [&](uint32_t* h) { match_batch_meta_fill(src_off, tgt_off, sz.n_problems, mj.knn, MATCH_BATCH_ROWS, sz.meta, h); },
-      launch_match_guided_batch_dist, launch_match_guided_batch_finish, d_corr, d_d2, d_count, g);
+      d_corr, d_d2, d_count, g);
 }
 
 // the same on listed pairs of the table (`total` rows: gd.src == gd.tgt are its points)
@@ -71,7 +61,7 @@ int pairs_match(sc_ctx* c, const MatchJob& mj, const Sizes& sz, const MatchBatch
   const MatchGather g = p ? gather_of(gd.src, total, gd.tgt, total, p->layout, c->mbatch_gsrc.as<float>(), c->mbatch_gtgt.as<float>()) : MatchGather{};
   return mbatch_enqueue(
       c, mj, sz, job, [&](uint32_t* h) { pairs_meta_fill(set_off, pairs, sz.n_problems, mj.knn, MATCH_BATCH_ROWS, sz.meta, h); },
-      launch_match_guided_pairs_dist, launch_match_guided_pairs_finish, d_corr, d_d2, d_count, g);
+      d_corr, d_d2, d_count, g);
 }
 
 }  // namespace
@@ -84,9 +74,9 @@ int sc_match_guided_batch_device(sc_ctx* c, const float* d_src_pts, const float*
                                  float* d_g2, uint32_t* d_count) {
   static const char* const who = "sc_match_guided_batch_device";
   if (!c) return SC_EINVAL;
-  GB_NOT_NULL(c, who, d_src_pts); GB_NOT_NULL(c, who, d_fsrc); GB_NOT_NULL(c, who, src_off); GB_NOT_NULL(c, who, d_tgt_pts);
-  GB_NOT_NULL(c, who, d_ftgt); GB_NOT_NULL(c, who, tgt_off); GB_NOT_NULL(c, who, mp); GB_NOT_NULL(c, who, gp); GB_NOT_NULL(c, who, d_pose);
-  GB_NOT_NULL(c, who, d_corr); GB_NOT_NULL(c, who, d_d2); GB_NOT_NULL(c, who, d_count);
+  SC_NOT_NULL(c, who, d_src_pts); SC_NOT_NULL(c, who, d_fsrc); SC_NOT_NULL(c, who, src_off); SC_NOT_NULL(c, who, d_tgt_pts);
+  SC_NOT_NULL(c, who, d_ftgt); SC_NOT_NULL(c, who, tgt_off); SC_NOT_NULL(c, who, mp); SC_NOT_NULL(c, who, gp); SC_NOT_NULL(c, who, d_pose);
+  SC_NOT_NULL(c, who, d_corr); SC_NOT_NULL(c, who, d_d2); SC_NOT_NULL(c, who, d_count);
   MatchJob mj{};
   Sizes sz{};
   SC_TRY(mbatch_check(c, src_off, tgt_off, n_problems, mp, nullptr, nullptr, &mj, &sz));
@@ -104,9 +94,9 @@ int sc_match_guided_batch(sc_ctx* c, const float* src_pts, const float* fsrc, co
                           uint32_t* count) {
   static const char* const who = "sc_match_guided_batch";
   if (!c) return SC_EINVAL;
-  GB_NOT_NULL(c, who, src_pts); GB_NOT_NULL(c, who, fsrc); GB_NOT_NULL(c, who, src_off); GB_NOT_NULL(c, who, tgt_pts);
-  GB_NOT_NULL(c, who, ftgt); GB_NOT_NULL(c, who, tgt_off); GB_NOT_NULL(c, who, mp); GB_NOT_NULL(c, who, gp); GB_NOT_NULL(c, who, pose);
-  GB_NOT_NULL(c, who, corr); GB_NOT_NULL(c, who, d2); GB_NOT_NULL(c, who, count);
+  SC_NOT_NULL(c, who, src_pts); SC_NOT_NULL(c, who, fsrc); SC_NOT_NULL(c, who, src_off); SC_NOT_NULL(c, who, tgt_pts);
+  SC_NOT_NULL(c, who, ftgt); SC_NOT_NULL(c, who, tgt_off); SC_NOT_NULL(c, who, mp); SC_NOT_NULL(c, who, gp); SC_NOT_NULL(c, who, pose);
+  SC_NOT_NULL(c, who, corr); SC_NOT_NULL(c, who, d2); SC_NOT_NULL(c, who, count);
   MatchJob mj{};
   Sizes sz{};
   SC_TRY(mbatch_check(c, src_off, tgt_off, n_problems, mp, nullptr, nullptr, &mj, &sz));
@@ -138,10 +128,10 @@ int sc_register_guided_batch_features_device(sc_ctx* c, const float* d_src_pts, 
                                              float* d_d2, float* d_g2, uint32_t* d_count, uint8_t* d_mask) {
   static const char* const who = "sc_register_guided_batch_features_device";
   if (!c) return SC_EINVAL;
-  GB_NOT_NULL(c, who, d_src_pts); GB_NOT_NULL(c, who, d_fsrc); GB_NOT_NULL(c, who, src_off); GB_NOT_NULL(c, who, d_tgt_pts);
-  GB_NOT_NULL(c, who, d_ftgt); GB_NOT_NULL(c, who, tgt_off); GB_NOT_NULL(c, who, mp); GB_NOT_NULL(c, who, gp); GB_NOT_NULL(c, who, d_pose);
-  GB_NOT_NULL(c, who, p); GB_NOT_NULL(c, who, d_res); GB_NOT_NULL(c, who, d_corr); GB_NOT_NULL(c, who, d_d2); GB_NOT_NULL(c, who, d_count);
-  GB_NOT_NULL(c, who, d_mask);
+  SC_NOT_NULL(c, who, d_src_pts); SC_NOT_NULL(c, who, d_fsrc); SC_NOT_NULL(c, who, src_off); SC_NOT_NULL(c, who, d_tgt_pts);
+  SC_NOT_NULL(c, who, d_ftgt); SC_NOT_NULL(c, who, tgt_off); SC_NOT_NULL(c, who, mp); SC_NOT_NULL(c, who, gp); SC_NOT_NULL(c, who, d_pose);
+  SC_NOT_NULL(c, who, p); SC_NOT_NULL(c, who, d_res); SC_NOT_NULL(c, who, d_corr); SC_NOT_NULL(c, who, d_d2); SC_NOT_NULL(c, who, d_count);
+  SC_NOT_NULL(c, who, d_mask);
   MatchJob mj{};
   Sizes sz{};
   SC_TRY(mbatch_check(c, src_off, tgt_off, n_problems, mp, p, "sc_register_guided_batch_features", &mj, &sz));
@@ -161,8 +151,8 @@ int sc_match_guided_pairs_device(sc_ctx* c, const float* d_pts, const float* d_f
                                  const void* d_pose, uint32_t pose_stride, int32_t* d_corr, float* d_d2, float* d_g2, uint32_t* d_count) {
   static const char* const who = "sc_match_guided_pairs_device";
   if (!c) return SC_EINVAL;
-  GB_NOT_NULL(c, who, d_pts); GB_NOT_NULL(c, who, d_feat); GB_NOT_NULL(c, who, set_off); GB_NOT_NULL(c, who, pairs); GB_NOT_NULL(c, who, mp);
-  GB_NOT_NULL(c, who, gp); GB_NOT_NULL(c, who, d_pose); GB_NOT_NULL(c, who, d_corr); GB_NOT_NULL(c, who, d_d2); GB_NOT_NULL(c, who, d_count);
+  SC_NOT_NULL(c, who, d_pts); SC_NOT_NULL(c, who, d_feat); SC_NOT_NULL(c, who, set_off); SC_NOT_NULL(c, who, pairs); SC_NOT_NULL(c, who, mp);
+  SC_NOT_NULL(c, who, gp); SC_NOT_NULL(c, who, d_pose); SC_NOT_NULL(c, who, d_corr); SC_NOT_NULL(c, who, d_d2); SC_NOT_NULL(c, who, d_count);
   MatchJob mj{};
   Sizes sz{};
   SC_TRY(pairs_check(c, set_off, n_sets, pairs, n_pairs, mp, nullptr, nullptr, &mj, &sz));
@@ -180,8 +170,8 @@ int sc_match_guided_pairs(sc_ctx* c, const float* pts, const float* feat, const 
                           int32_t* corr, float* d2, float* g2, uint32_t* count) {
   static const char* const who = "sc_match_guided_pairs";
   if (!c) return SC_EINVAL;
-  GB_NOT_NULL(c, who, pts); GB_NOT_NULL(c, who, feat); GB_NOT_NULL(c, who, set_off); GB_NOT_NULL(c, who, pairs); GB_NOT_NULL(c, who, mp);
-  GB_NOT_NULL(c, who, gp); GB_NOT_NULL(c, who, pose); GB_NOT_NULL(c, who, corr); GB_NOT_NULL(c, who, d2); GB_NOT_NULL(c, who, count);
+  SC_NOT_NULL(c, who, pts); SC_NOT_NULL(c, who, feat); SC_NOT_NULL(c, who, set_off); SC_NOT_NULL(c, who, pairs); SC_NOT_NULL(c, who, mp);
+  SC_NOT_NULL(c, who, gp); SC_NOT_NULL(c, who, pose); SC_NOT_NULL(c, who, corr); SC_NOT_NULL(c, who, d2); SC_NOT_NULL(c, who, count);
   MatchJob mj{};
   Sizes sz{};
   SC_TRY(pairs_check(c, set_off, n_sets, pairs, n_pairs, mp, nullptr, nullptr, &mj, &sz));
@@ -211,9 +201,9 @@ int sc_register_guided_pairs_features_device(sc_ctx* c, const float* d_pts, cons
                                              int32_t* d_corr, float* d_d2, float* d_g2, uint32_t* d_count, uint8_t* d_mask) {
   static const char* const who = "sc_register_guided_pairs_features_device";
   if (!c) return SC_EINVAL;
-  GB_NOT_NULL(c, who, d_pts); GB_NOT_NULL(c, who, d_feat); GB_NOT_NULL(c, who, set_off); GB_NOT_NULL(c, who, pairs); GB_NOT_NULL(c, who, mp);
-  GB_NOT_NULL(c, who, gp); GB_NOT_NULL(c, who, d_pose); GB_NOT_NULL(c, who, p); GB_NOT_NULL(c, who, d_res); GB_NOT_NULL(c, who, d_corr);
-  GB_NOT_NULL(c, who, d_d2); GB_NOT_NULL(c, who, d_count); GB_NOT_NULL(c, who, d_mask);
+  SC_NOT_NULL(c, who, d_pts); SC_NOT_NULL(c, who, d_feat); SC_NOT_NULL(c, who, set_off); SC_NOT_NULL(c, who, pairs); SC_NOT_NULL(c, who, mp);
+  SC_NOT_NULL(c, who, gp); SC_NOT_NULL(c, who, d_pose); SC_NOT_NULL(c, who, p); SC_NOT_NULL(c, who, d_res); SC_NOT_NULL(c, who, d_corr);
+  SC_NOT_NULL(c, who, d_d2); SC_NOT_NULL(c, who, d_count); SC_NOT_NULL(c, who, d_mask);
   MatchJob mj{};
   Sizes sz{};
   SC_TRY(pairs_check(c, set_off, n_sets, pairs, n_pairs, mp, p, "sc_register_guided_pairs_features", &mj, &sz));

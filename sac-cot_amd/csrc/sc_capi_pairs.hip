@@ -49,7 +49,7 @@ int pairs_match(sc_ctx* c, const MatchJob& mj, const Sizes& sz, const float* d_f
   const MatchGather g = p ? gather_of(d_pts, total, d_pts, total, p->layout, c->mbatch_gsrc.as<float>(), c->mbatch_gtgt.as<float>()) : MatchGather{};
   return mbatch_enqueue(
       c, mj, sz, job, [&](uint32_t* h) { pairs_meta_fill(set_off, pairs, sz.n_problems, mj.knn, MATCH_BATCH_ROWS, sz.meta, h); },
-      launch_match_pairs_dist, launch_match_pairs_finish, d_corr, d_d2, d_count, g);
+      d_corr, d_d2, d_count, g);
 }
 
 }  // namespace

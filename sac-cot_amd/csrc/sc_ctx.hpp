@@ -259,6 +259,8 @@ inline int refuse(sc_ctx* c, const char* who, const char* what) {
   c->last_error = std::string(who) + ": " + what;
   return SC_EINVAL;
 }
+// a refused NULL argument, named (the context is there: sc_last_error can say which)
+#define SC_NOT_NULL(c, who, arg) do { if (!(arg)) return refuse((c), (who), #arg " is NULL"); } while (0)
 // an sc_register_device_async / sc_finalize_gathered_device_async call is outstanding on this context
 inline int busy(sc_ctx* c) { return c->frame.pending ? (c->last_error = "a call is outstanding on this context (sc_wait first)", SC_EINVAL) : SC_OK; }
 // Any computing entry other than sc_peel* ends the frame the context may hold (include/saccot.h, sc_peel)
@@ -281,22 +283,43 @@ int outputs_to_host(sc_ctx* c, size_t n, float R[9], float t[3], uint8_t* mask);
 // the rules of sc_match_params and of ns, nt; fills everything of *job but the descriptor pointers
 int match_check(sc_ctx* c, const sc_match_params* mp, int64_t ns, int64_t nt, MatchJob* job);
 // The steps of a match on one pair of sets (sc_capi_match.hip; sc_capi_match_guided_poses.hip runs the same sequence).
-// match_enqueue: the memset and the two launches; gd (nullptr: no gate) with its pose in HBM, in h_Rt (12 host floats, copied behind
-// the memset) or — gd->n_poses > 0 — as records at gd->pose; d_g2 / d_label optional.  to_host: the finish launch publishes HW_MATCH.
-int match_enqueue(sc_ctx* c, const MatchJob& job, int32_t* d_corr, float* d_d2, uint32_t* d_count, const MatchGather& g, bool to_host,
-                  const MatchGuide* gd = nullptr, const float* h_Rt = nullptr, float* d_g2 = nullptr, int32_t* d_label = nullptr);
-// the host entries' descriptors -> match_fsrc / match_ftgt (enqueued) and room for corr and d2; their keypoints -> match_psrc /
-// match_ptgt and room for g2; the one wait (HW_MATCH) and the read-back of corr and d2 (enqueued: the caller synchronises)
-int match_stage_host(sc_ctx* c, MatchJob* job, const float* fsrc, const float* ftgt);
-int guided_stage_points(sc_ctx* c, const MatchJob& job, const float* src_pts, const float* tgt_pts);
-int match_results_to_host(sc_ctx* c, int32_t* corr, float* d2, uint32_t* found, const char* flagged = "non-finite descriptor");
-constexpr const char* MATCH_GUIDED_FLAGGED = "non-finite descriptor, point or pose";
-// the points of both sets in the guide's layout, as the kernels are told
-void guide_points(MatchGuide* gd, const float* src, uint32_t ns, const float* tgt, uint32_t nt, uint32_t layout);
+// match_enqueue: the memset and the two launches, writing what `o` names (MatchOut, sc_kernels.hpp; o.to_host: a host form)
+int match_enqueue(sc_ctx* c, const MatchJob& job, MatchOut o);
+// What a host form brings: its arrays, and which parts it has.  The sequence match_host runs for all of them: the keypoints ->
+// match_psrc / match_ptgt (a guided form; room for g2 with them), the descriptors -> match_fsrc / match_ftgt, the pose records ->
+// match_pose, match_enqueue, the ONE wait (HW_MATCH: the count, or SC_EINVAL for something not finite), the read-back of that many
+// entries of corr and d2 and — where asked for — g2 and label, and the wait for the stream.  A features form (p: the gather into
+// match_gsrc / match_gtgt) gets all but the last: its read-backs are enqueued, and match_register_gathered goes on from there.
+struct MatchHost {
+  const float* fsrc; const float* ftgt;        // descriptors
+  const float* src_pts; const float* tgt_pts;  // keypoints: the guided and the features forms
+  MatchGuide* gd;                              // a guided form: the guide but for its pointers (guide_check / poses_check), in layout `layout`
+  uint32_t layout;
+  const float* Rt;                             // sc_match_guided: the pose, 12 host floats
+  const void* pose;                            // sc_match_guided_poses: the records, as given
+  const sc_params* p;                          // a features form
+  int32_t* corr; float* d2; float* g2; int32_t* label;  // the caller's arrays (g2, label: optional)
+};
+int match_host(sc_ctx* c, MatchJob job, const MatchHost& h, uint32_t* found);
+// the tail of a features form: fewer than 3 matches -> the identity and SC_ENOHYP; else sc_register_device on the gathered points
+// (n x 3 whatever the caller's layout) and its outputs -> the caller's
+int match_register_gathered(sc_ctx* c, const sc_params* p, uint32_t found, float R[9], float t[3], uint8_t* mask, sc_stats* stats);
 // the caller's points (either layout of sc_params, src_rows / tgt_rows of them) -> two n x 3 arrays, as a finish kernel is told
 inline MatchGather gather_of(const float* src, uint32_t src_rows, const float* tgt, uint32_t tgt_rows, int layout, float* gsrc, float* gtgt) {
   const bool soa = layout == SC_SOA;
   return MatchGather{src, tgt, soa ? 1u : 3u, soa ? src_rows : 1u, soa ? 1u : 3u, soa ? tgt_rows : 1u, gsrc, gtgt};
+}
+// the points of both sets in a guide's layout, as the kernels are told (MatchGuide, MatchBatchGuide: MatchGather's strides)
+template <class Guide>
+void guide_points(Guide* gd, const float* src, size_t src_rows, const float* tgt, size_t tgt_rows, uint32_t layout) {
+  const MatchGather g = gather_of(src, (uint32_t)src_rows, tgt, (uint32_t)tgt_rows, (int)layout, nullptr, nullptr);
+  gd->src = g.src; gd->tgt = g.tgt;
+  gd->s_elem = g.s_elem; gd->s_comp = g.s_comp; gd->t_elem = g.t_elem; gd->t_comp = g.t_comp;
+}
+// a guided features entry's keypoints are one pair of arrays: the gate and the gather read them the same way
+inline int layouts_agree(sc_ctx* c, const char* who, const sc_guide_params* gp, const sc_params* p) {
+  if ((int32_t)gp->layout != p->layout) return refuse(c, who, "guide->layout must be params->layout: the keypoints are one pair of arrays");
+  return SC_OK;
 }
 // what a batch entry refuses of sc_params (shard_world != 1, refit, timing, an estimated bound); `who` opens the message
 int batch_params_check(sc_ctx* c, const sc_params* p, const char* who);
@@ -364,11 +387,11 @@ int mbatch_room(sc_ctx* c, const MatchJob& mj, const MatchBatchSizes& sz, bool g
 inline size_t mbatch_clean_bytes(const MatchBatchSizes& sz) { return (((size_t)sz.n_problems + 1) / 2) * 8; }
 // The staging copy, the memset and the two launches (mbatch_room has been called).  The form passes what is its own: `fill` writes
 // sz.meta.words words of metadata into the staging area; `job` arrives with its inputs and with its pointers into mbatch_meta, but
-// the tile map, set; dist / finish are its launch pair.  Everything else of the job — the fields MatchBatchJob and MatchPairsJob
+// the tile map, set; its launch pair follows from its type.  Everything else of the job — the fields MatchBatchJob and MatchPairsJob
 // share by name — is filled here.
 template <class Job, class Fill>
-int mbatch_enqueue(sc_ctx* c, const MatchJob& mj, const MatchBatchSizes& sz, Job job, Fill fill, void (*dist)(const Job&, hipStream_t),
-                   void (*finish)(const Job&, hipStream_t), int32_t* d_corr, float* d_d2, uint32_t* d_count, const MatchGather& g) {
+int mbatch_enqueue(sc_ctx* c, const MatchJob& mj, const MatchBatchSizes& sz, Job job, Fill fill, int32_t* d_corr, float* d_d2, uint32_t* d_count,
+                   const MatchGather& g) {
   const size_t meta_bytes = sz.meta.words * 4;
   SC_TRY(batch_staging_begin(c, meta_bytes));
   fill(static_cast<uint32_t*>(c->h_batch_off));
@@ -382,8 +405,8 @@ int mbatch_enqueue(sc_ctx* c, const MatchJob& mj, const MatchBatchSizes& sz, Job
   job.colmin = mj.mutual ? reinterpret_cast<uint64_t*>(static_cast<char*>(c->mbatch_words.p) + clean_bytes) : nullptr;
   job.clean = c->mbatch_words.as<uint32_t>();
   job.corr = d_corr; job.d2 = d_d2; job.count = d_count; job.g = g;
-  dist(job, c->stream);
-  finish(job, c->stream);
+  launch_match_batch_dist(job, c->stream);
+  launch_match_batch_finish(job, c->stream);
   HIPCHK(c, hipGetLastError());
   return SC_OK;
 }

@@ -730,14 +730,23 @@ struct MatchGuide {
 // pose is not finite, whatever the gate excludes.
 void launch_match_dist(const MatchJob& job, const MatchPlan& plan, uint64_t* part, uint64_t* colmin, uint32_t* clean, const MatchGuide* gd,
                        hipStream_t st);
-// merge + mutual / ratio + compaction in (row, rank) order: corr (n x 2 int32), d2 (n), count[0] = n, count[1] = 1 if a non-finite
-// descriptor was read (then n = 0 and nothing else is written).  lb: a look-back launch of match_finish_tiles(ns) tiles (8 bytes of
-// descriptor each).  host_word (optional, pinned): receives n | flag << 32.  gd, g2 (both optional): g2[m] = the gate residual of entry m.
-// label (optional, gd->n_poses > 0 only): label[m] = the used record with the smallest residual of entry m, and g2[m] is that minimum.
+// What a match call writes, and the optional parts it may carry; a caller names what it sets and leaves the rest zero.
+struct MatchOut {
+  int32_t* corr; float* d2;  // n x 2 int32 and n, in device memory
+  uint32_t* count;           // count[0] = n, count[1] = 1 if something not finite was read
+  bool to_host;              // match_enqueue: a host form — count and host_word are filled in there (match_words, HW_MATCH armed)
+  uint64_t* host_word;       // optional, pinned: receives n | flag << 32
+  MatchGather g;             // optional: the gather
+  const MatchGuide* gd;      // optional: the gate
+  const float* h_Rt;         // with gd, match_enqueue only: the pose as 12 host floats, copied behind the memset (nullptr: gd->Rt / gd->pose in HBM)
+  float* g2;                 // optional with gd: g2[m] = the gate residual of entry m
+  int32_t* label;            // optional with gd->n_poses > 0: label[m] = the used record with the smallest residual of entry m, g2[m] that minimum
+};
+// merge + mutual / ratio + compaction in (row, rank) order; with the flag raised n = 0 and nothing else is written.  lb: a look-back
+// launch of match_finish_tiles(ns) tiles (8 bytes of descriptor each).
 uint32_t match_finish_tiles(uint32_t ns);
-void launch_match_finish(const MatchJob& job, const MatchPlan& plan, const uint64_t* part, const uint64_t* colmin, const uint32_t* clean,
-                         int32_t* corr, float* d2, uint32_t* count, const MatchGather& g, LbArgs lb, uint64_t* host_word, const MatchGuide* gd,
-                         float* g2, hipStream_t st, int32_t* label = nullptr);
+void launch_match_finish(const MatchJob& job, const MatchPlan& plan, const uint64_t* part, const uint64_t* colmin, const uint32_t* clean, LbArgs lb,
+                         const MatchOut& o, hipStream_t st);
 
 // ---- many small registrations in one launch (sc_register_batch; sc_batch.hip) ------------------------------
 // One problem's result: sc_batch_result of include/saccot.h, field for field (sc_batch.hip asserts the size).
@@ -989,10 +998,7 @@ struct MatchBatchJob {
   int32_t* corr; float* d2; uint32_t* count;  // the slots, and 2 words per problem: n_b, the non-finite flag
   MatchGather g;     // sc_register_batch_features: packed points in, slot-positioned n x 3 arrays out (gsrc == nullptr: no gather)
 };
-// a workgroup per tile: the canonical distances of its rows to every target row of the problem, the rows' kp smallest keys -> top
-void launch_match_batch_dist(const MatchBatchJob& job, hipStream_t st);
-// a workgroup per problem: mutual / ratio per row, compaction inside the slot in ascending (row, rank) order, the count pair, the gather
-void launch_match_batch_finish(const MatchBatchJob& job, hipStream_t st);
+// (its two launches: launch_match_batch_dist / _finish, below, for the four job types)
 
 // ---- the same for listed pairs of shared sets (sc_match_pairs; sc_match_batch.hip, sc_polish_batch.hip) ----------------
 // One table of sets, feat (total x dim), and a list of pairs drawn from it: the problems of the launches are the PAIRS.  A set
@@ -1018,8 +1024,6 @@ struct MatchPairsJob {
   int32_t* corr; float* d2; uint32_t* count;
   MatchGather g;
 };
-void launch_match_pairs_dist(const MatchPairsJob& job, hipStream_t st);
-void launch_match_pairs_finish(const MatchPairsJob& job, hipStream_t st);
 
 // ---- both forms under a pose prior per problem (sc_match_guided_batch; sc_match_batch.hip) ---------------------------
 // The keypoints of the batch (point so + i of src is src[(so + i) * s_elem + c * s_comp], as MatchGather's; the pairs form: src ==
@@ -1039,9 +1043,10 @@ struct MatchBatchGuide {
 // `clean` is also cleared when a point of the problem or its pose is not finite, whatever the gate excludes.
 struct MatchGuidedBatchJob : MatchBatchJob { MatchBatchGuide gd; };
 struct MatchGuidedPairsJob : MatchPairsJob { MatchBatchGuide gd; };
-void launch_match_guided_batch_dist(const MatchGuidedBatchJob& job, hipStream_t st);
-void launch_match_guided_batch_finish(const MatchGuidedBatchJob& job, hipStream_t st);
-void launch_match_guided_pairs_dist(const MatchGuidedPairsJob& job, hipStream_t st);
-void launch_match_guided_pairs_finish(const MatchGuidedPairsJob& job, hipStream_t st);
+// The two launches of every form, on the job type (instantiated in sc_match_batch.hip for the four above).
+// dist: a workgroup per tile: the canonical distances of its rows to every target row of the problem, the rows' kp smallest keys -> top
+// finish: a workgroup per problem: mutual / ratio per row, compaction inside the slot in ascending (row, rank) order, the count pair, the gather
+template <class Job> void launch_match_batch_dist(const Job& job, hipStream_t st);
+template <class Job> void launch_match_batch_finish(const Job& job, hipStream_t st);
 
 }  // namespace sc

@@ -20,6 +20,12 @@
 //                        corr / d2 in ascending (row, rank) order, gathers the matched points for sc_register_features, and the
 //                        last tile writes the count and the non-finite flag.
 //
+// What the two kernels share with sc_match_batch.hip's is said once, in sc_match_tile.hpp: tile_step and top_insert, the finish
+// kernel's row decision (row_kept) and entry write (entry_write, entry_resid), the pose-record accessors and the not-finite scan.
+// The chunk loop, the selection block and the column-minimum flush stay written out in both distance kernels: moved into shared
+// templates they cost this file's gated instantiations an occupancy step or, under a launch bound, time; as they stand the distance
+// kernels compile to the instructions they had before the finish steps were shared.
+//
 // sc_match_guided (GUIDED) is the same pair of launches with a pose prior: a cell (i, j) is a candidate only where the canonical
 // residual of the inlier test, resid2(Rt, src_pts[i], tgt_pts[j]) (sc_arith.hpp), is below gate2.  The distance launch stages the
 // workgroup's 128 source points once and a tile's 64 target points per tile, every thread folds its 8 x 4 decisions into one 32-bit
@@ -53,13 +59,6 @@ constexpr int MT_ROWS = 128, MT_COLS = 64, MT_THREADS = 256;  // (MT_KC, the key
 constexpr int MT_LDA = MT_ROWS + 4, MT_LDB = MT_COLS + 4;  // 16-byte aligned rows; the pad spreads the transposing stores over the banks
 constexpr int FIN_THREADS = 256;
 
-// this thread's share of n floats, grid-strided over the whole launch: is one of them not finite?
-__device__ __forceinline__ bool scan_not_finite(const float* __restrict__ p, size_t n, size_t me, size_t stride) {
-  bool bad = false;
-  for (size_t e = me; e < n; e += stride) bad = bad || not_finite(p[e]);
-  return bad;
-}
-
 // sc_match's kernel takes no guide: an empty argument
 struct NoGuide {};
 
@@ -70,15 +69,10 @@ constexpr int GATE_NONE = 0, GATE_POSE = 1, GATE_POSES = 2;
 constexpr int MT_POSES = (int)SC_GUIDE_MAX_POSES;
 static_assert(MT_POSES == 64, "s_used is one 64-bit word, filled by one ballot of a 64-lane wave");
 
-// record k of a pose list: 12 floats, and behind them the status when the caller says there is one
-__device__ __forceinline__ const float* pose_record(const MatchGuide& gd, uint32_t k) {
-  return reinterpret_cast<const float*>(static_cast<const char*>(gd.pose) + (size_t)k * gd.pose_stride);
-}
-__device__ __forceinline__ bool pose_used(const MatchGuide& gd, uint32_t k) {
-  return gd.use_status == 0u || reinterpret_cast<const int32_t*>(pose_record(gd, k))[12] == 0;  // (SC_OK is 0)
-}
-
 // The distance launch, said once.  GATE_NONE is sc_match's kernel; GATE_POSE adds the gate; GATE_POSES the gate of several poses.
+// The chunk loop, the selection and the flush are this kernel's own text, as they are sc_match_batch.hip's: as shared templates they
+// cost the gated instantiations a wave per SIMD, and under a launch bound that restored the wave 0.5 % of a call
+// (profiles/match_shared.txt).
 template <int KP, int GATE>
 __global__ __launch_bounds__(MT_THREADS) void match_dist_kernel(const float* __restrict__ fsrc, uint32_t ns,
                                                                 const float* __restrict__ ftgt, uint32_t nt, uint32_t D,
@@ -109,13 +103,14 @@ __global__ __launch_bounds__(MT_THREADS) void match_dist_kernel(const float* __r
       // every workgroup stages (and tests) the used records; the tiles' first barrier publishes them
       for (uint32_t e = threadIdx.x; e < gd.n_poses * 12u; e += MT_THREADS) {
         const uint32_t k = e / 12u, f = e % 12u;
-        if (!pose_used(gd, k)) continue;
-        const float v = pose_record(gd, k)[f];
+        const float* rec = pose_record(gd, k);
+        if (!pose_used(gd, rec)) continue;
+        const float v = rec[f];
         bad = bad || not_finite(v);
         sM[k][f] = v;
       }
       if (threadIdx.x < 64) {  // (the first wave, whole)
-        const unsigned long long used = __ballot(threadIdx.x < gd.n_poses && pose_used(gd, threadIdx.x));
+        const unsigned long long used = __ballot(threadIdx.x < gd.n_poses && pose_used(gd, pose_record(gd, threadIdx.x)));
         if (threadIdx.x == 0) s_used = used;
       }
     } else {
@@ -285,17 +280,7 @@ __global__ __launch_bounds__(FIN_THREADS) void match_finish_kernel(const unsigne
         }
       }
     }
-    if (job.mutual || job.r2 > 0.f) {
-      bool keep = top[0] != KEY_NONE;
-      const uint32_t j = (uint32_t)top[0];
-      if (keep && job.mutual) keep = j < job.nt && colmin[j] == ((top[0] & 0xFFFFFFFF00000000ull) | i);
-      if (keep && job.r2 > 0.f && top[1] != KEY_NONE)
-        keep = __uint_as_float((uint32_t)(top[0] >> 32)) < __fmul_rn(job.r2, __uint_as_float((uint32_t)(top[1] >> 32)));
-      cnt = keep ? 1u : 0u;
-    } else {
-#pragma unroll
-      for (int w = 0; w < 4; w++) cnt += (w < (int)job.knn && top[w] != KEY_NONE) ? 1u : 0u;
-    }
+    cnt = row_kept(top, i, job.mutual, job.r2, job.knn, colmin, job.nt);
   }
   uint64_t tot;
   const uint64_t ex = block_exscan_u64(cnt, s_scan, &tot);
@@ -315,31 +300,18 @@ __global__ __launch_bounds__(FIN_THREADS) void match_finish_kernel(const unsigne
     const size_t slot = (size_t)(pre + ex + w);
     const uint32_t j = (uint32_t)top[w];
     if (slot >= cap || j >= job.nt) break;  // (cannot happen: a row emits at most knn keys, each with a column of this call)
-    corr[2 * slot] = (int32_t)i;
-    corr[2 * slot + 1] = (int32_t)j;
-    d2[slot] = __uint_as_float((uint32_t)(top[w] >> 32));
-    if (g.gsrc) {
-#pragma unroll
-      for (int c = 0; c < 3; c++) {
-        g.gsrc[3 * slot + c] = g.src[(size_t)i * g.s_elem + (size_t)c * g.s_comp];
-        g.gtgt[3 * slot + c] = g.tgt[(size_t)j * g.t_elem + (size_t)c * g.t_comp];
-      }
-    }
+    entry_write(slot, i, top[w], corr, d2, g, 0u, 0u);
     if (gd.n_poses != 0u) {
       // sc_match_guided_poses: every used record's residual of the entry (the distance launch's chain on the same points); the
       // smallest, ties to the lowest index — a NaN never wins, and the entry is admissible: some residual is below gate2
       if (g2 || label) {
         float p[3], q[3];
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-          p[c] = gd.src[(size_t)i * gd.s_elem + (size_t)c * gd.s_comp];
-          q[c] = gd.tgt[(size_t)j * gd.t_elem + (size_t)c * gd.t_comp];
-        }
+        entry_points(gd, i, j, p, q);
         float best = __uint_as_float(0x7F800000u);
         int32_t best_k = 0;
         for (uint32_t k = 0; k < gd.n_poses; k++) {
-          if (!pose_used(gd, k)) continue;
           const float* rec = pose_record(gd, k);
+          if (!pose_used(gd, rec)) continue;
           float M[12];
 #pragma unroll
           for (int f = 0; f < 12; f++) M[f] = rec[f];
@@ -350,15 +322,10 @@ __global__ __launch_bounds__(FIN_THREADS) void match_finish_kernel(const unsigne
         if (label) label[slot] = best_k;
       }
     } else if (g2) {  // sc_match_guided: the gate residual of the entry, the distance launch's chain on the same points
-      float M[12], p[3], q[3];
+      float M[12];
 #pragma unroll
       for (int k = 0; k < 12; k++) M[k] = gd.Rt[k];
-#pragma unroll
-      for (int c = 0; c < 3; c++) {
-        p[c] = gd.src[(size_t)i * gd.s_elem + (size_t)c * gd.s_comp];
-        q[c] = gd.tgt[(size_t)j * gd.t_elem + (size_t)c * gd.t_comp];
-      }
-      g2[slot] = resid2(M, p[0], p[1], p[2], q[0], q[1], q[2]);
+      g2[slot] = entry_resid(M, gd, i, j);
     }
   }
   if (tile == gridDim.x - 1 && threadIdx.x == 0) {
@@ -391,44 +358,39 @@ MatchPlan match_plan(uint32_t ns, uint32_t nt, uint32_t knn, float r2) {
 
 uint32_t match_finish_tiles(uint32_t ns) { return (ns + FIN_THREADS - 1) / FIN_THREADS; }
 
-void launch_match_dist(const MatchJob& job, const MatchPlan& plan, uint64_t* part, uint64_t* colmin, uint32_t* clean, const MatchGuide* gd,
-                       hipStream_t st) {
-  const dim3 grid(plan.row_blocks, plan.slices), block(MT_THREADS);
-  unsigned long long* p = reinterpret_cast<unsigned long long*>(part);
-  unsigned long long* cm = reinterpret_cast<unsigned long long*>(colmin);
-  if (gd && gd->n_poses != 0u) {
-    switch (plan.kp) {
-      case 1: hipLaunchKernelGGL((match_dist_kernel<1, GATE_POSES>), grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean, *gd); break;
-      case 2: hipLaunchKernelGGL((match_dist_kernel<2, GATE_POSES>), grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean, *gd); break;
-      case 3: hipLaunchKernelGGL((match_dist_kernel<3, GATE_POSES>), grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean, *gd); break;
-      default: hipLaunchKernelGGL((match_dist_kernel<4, GATE_POSES>), grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean, *gd); break;
-    }
-    return;
-  }
-  if (gd) {
-    switch (plan.kp) {
-      case 1: hipLaunchKernelGGL((match_dist_kernel<1, GATE_POSE>), grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean, *gd); break;
-      case 2: hipLaunchKernelGGL((match_dist_kernel<2, GATE_POSE>), grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean, *gd); break;
-      case 3: hipLaunchKernelGGL((match_dist_kernel<3, GATE_POSE>), grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean, *gd); break;
-      default: hipLaunchKernelGGL((match_dist_kernel<4, GATE_POSE>), grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean, *gd); break;
-    }
-    return;
-  }
+namespace {
+
+// one distance launch under gate GATE: the dispatch over the lists' length
+template <int GATE, class Guide>
+void launch_dist(const MatchJob& job, const MatchPlan& plan, uint64_t* part, uint64_t* colmin, uint32_t* clean, const Guide& gd, hipStream_t st) {
+  const auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(plan.row_blocks, plan.slices), dim3(MT_THREADS), 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim,
+                       plan.tiles_per_slice, reinterpret_cast<unsigned long long*>(part), plan.ld_part,
+                       reinterpret_cast<unsigned long long*>(colmin), clean, gd);
+  };
   switch (plan.kp) {
-    case 1: hipLaunchKernelGGL((match_dist_kernel<1, GATE_NONE>), grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean, NoGuide{}); break;
-    case 2: hipLaunchKernelGGL((match_dist_kernel<2, GATE_NONE>), grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean, NoGuide{}); break;
-    case 3: hipLaunchKernelGGL((match_dist_kernel<3, GATE_NONE>), grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean, NoGuide{}); break;
-    default: hipLaunchKernelGGL((match_dist_kernel<4, GATE_NONE>), grid, block, 0, st, job.fsrc, job.ns, job.ftgt, job.nt, job.dim, plan.tiles_per_slice, p, plan.ld_part, cm, clean, NoGuide{}); break;
+    case 1: go(match_dist_kernel<1, GATE>); break;
+    case 2: go(match_dist_kernel<2, GATE>); break;
+    case 3: go(match_dist_kernel<3, GATE>); break;
+    default: go(match_dist_kernel<4, GATE>); break;
   }
 }
 
-void launch_match_finish(const MatchJob& job, const MatchPlan& plan, const uint64_t* part, const uint64_t* colmin, const uint32_t* clean,
-                         int32_t* corr, float* d2, uint32_t* count, const MatchGather& g, LbArgs lb, uint64_t* host_word, const MatchGuide* gd,
-                         float* g2, hipStream_t st, int32_t* label) {
+}  // namespace
+
+void launch_match_dist(const MatchJob& job, const MatchPlan& plan, uint64_t* part, uint64_t* colmin, uint32_t* clean, const MatchGuide* gd,
+                       hipStream_t st) {
+  if (!gd) launch_dist<GATE_NONE>(job, plan, part, colmin, clean, NoGuide{}, st);
+  else if (gd->n_poses != 0u) launch_dist<GATE_POSES>(job, plan, part, colmin, clean, *gd, st);
+  else launch_dist<GATE_POSE>(job, plan, part, colmin, clean, *gd, st);
+}
+
+void launch_match_finish(const MatchJob& job, const MatchPlan& plan, const uint64_t* part, const uint64_t* colmin, const uint32_t* clean, LbArgs lb,
+                         const MatchOut& o, hipStream_t st) {
   hipLaunchKernelGGL(match_finish_kernel, dim3(match_finish_tiles(job.ns)), dim3(FIN_THREADS), 0, st,
                      reinterpret_cast<const unsigned long long*>(part), plan.ld_part, plan.slices, plan.kp, job,
-                     reinterpret_cast<const unsigned long long*>(colmin), clean, corr, d2, count, g, lb, host_word, gd ? *gd : MatchGuide{},
-                     gd ? g2 : nullptr, gd && gd->n_poses != 0u ? label : nullptr);
+                     reinterpret_cast<const unsigned long long*>(colmin), clean, o.corr, o.d2, o.count, o.g, lb, o.host_word,
+                     o.gd ? *o.gd : MatchGuide{}, o.gd ? o.g2 : nullptr, o.gd && o.gd->n_poses != 0u ? o.label : nullptr);
 }
 
 }  // namespace sc

@@ -1,6 +1,8 @@
 // sc_match_batch.hip — descriptor matching for a whole batch of small problems (include/saccot.h, sc_match_batch): the kernels.
-// The arithmetic and the selection step are sc_match.hip's (sc_match_tile.hpp), so problem b's slot holds what sc_match returns
-// for problem b alone, bit for bit.  Two launches for the batch, whatever its size:
+// The arithmetic and the selection step are sc_match.hip's (tile_step, top_insert: sc_match_tile.hpp), so problem b's slot holds what
+// sc_match returns for problem b alone, bit for bit; the finish kernel's row decision and entry write, the pose-record accessors and
+// the not-finite scan are one text with sc_match.hip's, in the same header.  The chunk loop, the selection block and the
+// column-minimum flush are written out here as they are there (sc_match.hip says why).  Two launches for the batch, whatever its size:
 //
 //   match_batch_dist_kernel    grid = the flattened list of (problem, tile of 64 source rows); the tile map comes from the host with
 //                              the offsets, and a tile never spans two problems.  A workgroup of 128 threads walks ALL target
@@ -77,14 +79,6 @@ template <class Job> struct guided_job : std::false_type {};
 template <> struct guided_job<MatchGuidedBatchJob> : std::true_type {};
 template <> struct guided_job<MatchGuidedPairsJob> : std::true_type {};
 
-// problem b's pose record: 12 floats, and behind them the status when the caller says there is one
-__device__ __forceinline__ const float* pose_of(const MatchBatchGuide& gd, uint32_t b) {
-  return reinterpret_cast<const float*>(static_cast<const char*>(gd.pose) + (size_t)b * gd.pose_stride);
-}
-__device__ __forceinline__ bool pose_skipped(const MatchBatchGuide& gd, const float* rec) {
-  return gd.use_status != 0u && reinterpret_cast<const int32_t*>(rec)[12] != 0;  // (SC_OK is 0)
-}
-
 template <int KP, class Job>
 __global__ __launch_bounds__(MB_THREADS) void match_batch_dist_kernel(const Job job) {
   constexpr bool GUIDED = guided_job<Job>::value;
@@ -98,8 +92,8 @@ __global__ __launch_bounds__(MB_THREADS) void match_batch_dist_kernel(const Job 
   if (b >= job.n_problems) return;  // (cannot happen: the host built the map)
   float M[12];  // GUIDED: the problem's pose (workgroup-uniform: scalar registers)
   if constexpr (GUIDED) {
-    const float* rec = pose_of(job.gd, b);
-    if (pose_skipped(job.gd, rec)) return;  // nothing else of a skipped problem is read or written
+    const float* rec = pose_record(job.gd, b);
+    if (!pose_used(job.gd, rec)) return;  // nothing else of a skipped problem is read or written
 #pragma unroll
     for (int k = 0; k < 12; k++) M[k] = rec[k];
   }
@@ -124,8 +118,8 @@ __global__ __launch_bounds__(MB_THREADS) void match_batch_dist_kernel(const Job 
     // The finiteness rule depends on the input alone: the problem's workgroups share every element of ITS descriptors and points,
     // whatever tiles the gate drops below.  (A point is read through the strides: in SoA a problem's points are three ranges.)
     const size_t stride = (size_t)((ns + MB_ROWS - 1) / MB_ROWS) * MB_THREADS, me = (size_t)(row0 / MB_ROWS) * MB_THREADS + threadIdx.x;
-    for (size_t e = me; e < (size_t)ns * D; e += stride) bad = bad || not_finite(fsrc[e]);
-    for (size_t e = me; e < (size_t)nt * D; e += stride) bad = bad || not_finite(ftgt[e]);
+    bad = scan_not_finite(fsrc, (size_t)ns * D, me, stride) || bad;
+    bad = scan_not_finite(ftgt, (size_t)nt * D, me, stride) || bad;
     for (size_t e = me; e < (size_t)ns * 3; e += stride)
       bad = bad || not_finite(gd.src[((size_t)v.so + e / 3) * gd.s_elem + (e % 3) * gd.s_comp]);
     for (size_t e = me; e < (size_t)nt * 3; e += stride)
@@ -148,7 +142,7 @@ __global__ __launch_bounds__(MB_THREADS) void match_batch_dist_kernel(const Job 
       __syncthreads();  // sQ (and, first tile, sP, the lists' and s_col's initial values) are written
       // The thread's 4 target points in registers, its 8 rows rolled.  (All 32 cells unrolled cost sc_match.hip's kernel 60+ registers
       // and a wave per SIMD; this kernel runs two waves per SIMD with or without a gate, and the half-rolled form stays within them:
-      // 203 - 205 registers.  The cell's indices are constants here and a row's point is read once for 4 cells: measured 7 % faster
+      // profiles/match_shared.txt has the registers.  The cell's indices are constants here and a row's point is read once for 4 cells: measured 7 % faster
       // than the loop over 32 cells)
       adm = 0;
       {
@@ -257,8 +251,8 @@ __global__ __launch_bounds__(MBF_THREADS) void match_batch_finish_kernel(const J
   const uint32_t b = blockIdx.x;
   float M[12];  // GUIDED: the problem's pose
   if constexpr (GUIDED) {
-    const float* rec = pose_of(job.gd, b);
-    if (pose_skipped(job.gd, rec)) {  // (0, 0), and nothing else of the problem is read or written
+    const float* rec = pose_record(job.gd, b);
+    if (!pose_used(job.gd, rec)) {  // (0, 0), and nothing else of the problem is read or written
       if (threadIdx.x == 0) { job.count[2 * b] = 0u; job.count[2 * b + 1] = 0u; }
       return;
     }
@@ -281,17 +275,7 @@ __global__ __launch_bounds__(MBF_THREADS) void match_batch_finish_kernel(const J
 #pragma unroll
       for (int q = 0; q < 4; q++)
         if (q < (int)job.kp) key[q] = top[(size_t)i * job.kp + q];
-      if (job.mutual || job.r2 > 0.f) {
-        bool keep = key[0] != KEY_NONE;
-        const uint32_t j = (uint32_t)key[0];
-        if (keep && job.mutual) keep = j < nt && colmin[j] == ((key[0] & 0xFFFFFFFF00000000ull) | i);
-        if (keep && job.r2 > 0.f && key[1] != KEY_NONE)
-          keep = __uint_as_float((uint32_t)(key[0] >> 32)) < __fmul_rn(job.r2, __uint_as_float((uint32_t)(key[1] >> 32)));
-        cnt = keep ? 1u : 0u;
-      } else {
-#pragma unroll
-        for (int w = 0; w < 4; w++) cnt += (w < (int)job.knn && key[w] != KEY_NONE) ? 1u : 0u;
-      }
+      cnt = row_kept(key, i, job.mutual, job.r2, job.knn, colmin, nt);
     }
     uint64_t tot;
     const uint64_t ex = block_exscan_u64(cnt, s_scan, &tot);
@@ -302,27 +286,9 @@ __global__ __launch_bounds__(MBF_THREADS) void match_batch_finish_kernel(const J
       const uint32_t j = (uint32_t)key[w];
       if (m >= cap || j >= nt) break;  // (cannot happen: a row emits at most knn keys, each with a column of its problem)
       const size_t e = slot + m;
-      job.corr[2 * e] = (int32_t)i;
-      job.corr[2 * e + 1] = (int32_t)j;
-      job.d2[e] = __uint_as_float((uint32_t)(key[w] >> 32));
-      if (g.gsrc) {
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-          g.gsrc[3 * e + c] = g.src[((size_t)so + i) * g.s_elem + (size_t)c * g.s_comp];
-          g.gtgt[3 * e + c] = g.tgt[((size_t)to + j) * g.t_elem + (size_t)c * g.t_comp];
-        }
-      }
+      entry_write(e, i, key[w], job.corr, job.d2, g, so, to);
       if constexpr (GUIDED) {
-        const MatchBatchGuide& gd = job.gd;
-        if (gd.g2) {  // the gate residual of the entry: the distance launch's chain on the same points
-          float p[3], q[3];
-#pragma unroll
-          for (int c = 0; c < 3; c++) {
-            p[c] = gd.src[((size_t)so + i) * gd.s_elem + (size_t)c * gd.s_comp];
-            q[c] = gd.tgt[((size_t)to + j) * gd.t_elem + (size_t)c * gd.t_comp];
-          }
-          gd.g2[e] = resid2(M, p[0], p[1], p[2], q[0], q[1], q[2]);
-        }
+        if (job.gd.g2) job.gd.g2[e] = entry_resid(M, job.gd, (size_t)so + i, (size_t)to + j);  // the gate residual of the entry
       }
     }
     run += (uint32_t)tot;
@@ -335,15 +301,8 @@ __global__ __launch_bounds__(MBF_THREADS) void match_batch_finish_kernel(const J
 
 }  // namespace
 
-namespace {
-
 template <class Job>
-void launch_finish(const Job& job, hipStream_t st) {
-  hipLaunchKernelGGL(match_batch_finish_kernel<Job>, dim3(job.n_problems), dim3(MBF_THREADS), 0, st, job);
-}
-
-template <class Job>
-void launch_dist(const Job& job, hipStream_t st) {
+void launch_match_batch_dist(const Job& job, hipStream_t st) {
   const dim3 grid(job.n_tiles), block(MB_THREADS);
   switch (job.kp) {
     case 1: hipLaunchKernelGGL((match_batch_dist_kernel<1, Job>), grid, block, 0, st, job); break;
@@ -352,22 +311,17 @@ void launch_dist(const Job& job, hipStream_t st) {
     default: hipLaunchKernelGGL((match_batch_dist_kernel<4, Job>), grid, block, 0, st, job); break;
   }
 }
-
-}  // namespace
-
-void launch_match_batch_dist(const MatchBatchJob& job, hipStream_t st) { launch_dist(job, st); }
-void launch_match_pairs_dist(const MatchPairsJob& job, hipStream_t st) { launch_dist(job, st); }
-
-void launch_match_batch_finish(const MatchBatchJob& job, hipStream_t st) {
-  hipLaunchKernelGGL(match_batch_finish_kernel<MatchBatchJob>, dim3(job.n_problems), dim3(MBF_THREADS), 0, st, job);
+template <class Job>
+void launch_match_batch_finish(const Job& job, hipStream_t st) {
+  hipLaunchKernelGGL(match_batch_finish_kernel<Job>, dim3(job.n_problems), dim3(MBF_THREADS), 0, st, job);
 }
-void launch_match_pairs_finish(const MatchPairsJob& job, hipStream_t st) {
-  hipLaunchKernelGGL(match_batch_finish_kernel<MatchPairsJob>, dim3(job.n_problems), dim3(MBF_THREADS), 0, st, job);
-}
-
-void launch_match_guided_batch_dist(const MatchGuidedBatchJob& job, hipStream_t st) { launch_dist(job, st); }
-void launch_match_guided_pairs_dist(const MatchGuidedPairsJob& job, hipStream_t st) { launch_dist(job, st); }
-void launch_match_guided_batch_finish(const MatchGuidedBatchJob& job, hipStream_t st) { launch_finish(job, st); }
-void launch_match_guided_pairs_finish(const MatchGuidedPairsJob& job, hipStream_t st) { launch_finish(job, st); }
+template void launch_match_batch_dist(const MatchBatchJob&, hipStream_t);
+template void launch_match_batch_dist(const MatchPairsJob&, hipStream_t);
+template void launch_match_batch_dist(const MatchGuidedBatchJob&, hipStream_t);
+template void launch_match_batch_dist(const MatchGuidedPairsJob&, hipStream_t);
+template void launch_match_batch_finish(const MatchBatchJob&, hipStream_t);
+template void launch_match_batch_finish(const MatchPairsJob&, hipStream_t);
+template void launch_match_batch_finish(const MatchGuidedBatchJob&, hipStream_t);
+template void launch_match_batch_finish(const MatchGuidedPairsJob&, hipStream_t);
 
 }  // namespace sc
