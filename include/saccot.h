@@ -48,6 +48,7 @@ extern "C" {
 #define SC_HAS_POSE_INFO_FRAME 1  /* this header declares sc_pose_info_frame* and sc_pose_info_default_params (added within 0.10) */
 #define SC_HAS_POLISH_POSES 1  /* this header declares sc_polish_poses* (added within 0.10) */
 #define SC_HAS_ASSIGN 1  /* this header declares sc_assign_poses* and sc_assign_default_params (added within 0.10) */
+#define SC_HAS_SETTLE 1  /* this header declares sc_settle_poses* and sc_settle_default_params (added within 0.10) */
 #define SC_HAS_MATCH_GUIDED 1  /* this header declares sc_match_guided*, sc_register_guided_features and sc_guide_default_params (added within 0.10) */
 #define SC_HAS_MATCH_GUIDED_POSES 1  /* this header declares sc_match_guided_poses*, sc_register_guided_poses_features and SC_GUIDE_MAX_POSES (added within 0.10) */
 #define SC_HAS_MATCH_GUIDED_BATCH 1  /* this header declares sc_match_guided_batch*, sc_match_guided_pairs* and sc_register_guided_{batch,pairs}_features_device (added within 0.10) */
@@ -1203,8 +1204,8 @@ int sc_polish_poses(sc_ctx* ctx, const sc_polish_poses_params* qp, const void* p
  * label -1 throughout and SC_EINVAL in every one of its records; its neighbours are untouched.  A problem's outputs do not depend on
  * its position in the batch or on n_problems.  Like every batch entry it ends the frame a context may hold.  Refusals, workspace
  * (the copy of the offsets, the host form's device copies) and the offset staging wait are sc_pose_info_batch_device's.
- * Not here: slots and pairs forms; soft or weighted assignment; a fused "relabel and refit until stable" entry — the caller composes
- * it from the stream-ordered calls above —; a form for sharded frames, which leave no frame. */
+ * Not here: slots and pairs forms; soft or weighted assignment; "relabel and refit until stable" (an entry of its own:
+ * sc_settle_poses, below); a form for sharded frames, which leave no frame. */
 #define SC_ASSIGN_MAX_POSES       1024u
 #define SC_ASSIGN_BATCH_MAX_POSES 64u
 #define SC_ASSIGN_BEST     0u   /* mode: the candidate with the smallest residual, ties to the lowest k */
@@ -1242,6 +1243,99 @@ int sc_assign_poses_batch_device(sc_ctx* ctx, const float* d_src, const float* d
 int sc_assign_poses_batch(sc_ctx* ctx, const float* src, const float* tgt, const uint32_t* offset, uint32_t n_problems,
                           const sc_params* params, const sc_assign_params* ap, const void* pose, uint32_t pose_stride,
                           uint32_t n_poses, int32_t* label, sc_assign_result* asg);
+
+/* ---- poses relabelled and refitted until stable: sc_settle_poses -----------------------------------------------------
+ * The loop the entries above leave to the caller — sc_assign_poses(BEST), then sc_polish_poses(SEL_LABEL, max_iter 1) on its label,
+ * again until no pose moves — has a stopping rule only the device knows.  A host-free caller enqueues max_iter rounds whether or not
+ * the poses settled in the second; one who stops early pays a host round trip per round.  These entries run the loop to its fixed
+ * point ON THE DEVICE, in ONE kernel launch without a grid barrier, and read nothing back.  Two forms: on a scored frame (ONE
+ * workgroup owns the frame, sc_settle_frame.hip) and on a packed batch (a workgroup per problem, sc_settle_batch.hip).
+ *
+ * Definitions.  The pose records, valid(k), d2_k(m), part(m), cand(k, m) and the SC_ASSIGN_BEST rule are sc_assign_poses's, word for
+ * word: float Rt[12] at byte 0 and, where a status is read, an int32 at byte 48; read, never written; 4-byte aligned.  The refit is
+ * sc_polish_poses's single refit: the canonical fp64 refit over a set, in chunks of 64 consecutive ORIGINAL indices, chunk sums in
+ * chunk order, rounded to fp32; declined with fewer than 3 members or a non-finite result.
+ *   P_0         the input.  A pose that is invalid in P_0 stays invalid and claims nothing.
+ *   round r     r = 1 .. max_iter.  L_r = the BEST labels under P_{r-1} and the selection.  For every valid k, P_r[k] = the refit over
+ *               {m : L_r[m] == k}; a declined refit leaves P_r[k] = P_{r-1}[k], bit for bit.  If P_r equals P_{r-1} bit for bit in
+ *               every pose the call stops with SC_POLISH_STOP_FIXED and this round is NOT counted; otherwise it is counted.
+ *   stop        after max_iter counted rounds: SC_POLISH_STOP_MAX_ITER.
+ *   d_label     n int32: the BEST labels under the FINAL poses (after FIXED the last round's; after MAX_ITER one more labelling
+ *               pass); -1 without a candidate.  d_d2 (frame form, or NULL): their residuals, 0x7F800000 (+inf) where the label is -1.
+ *   record k    sc_polish_batch_result: Rt = the final pose; score0 = pose k's tally — the frame's / params->score_mode term summed
+ *               over its label — under P_0 and L_1; score = the tally under the final poses and labels; iters = the counted rounds
+ *               in which pose k's bits changed; stop = SC_POLISH_STOP_DECLINED if pose k's refit was declined in the last executed
+ *               round, else the call's stop; status SC_OK.  An invalid pose gets sc_polish_poses's record for it: the status
+ *               passed through, or SC_EINVAL for a non-finite Rt; R = I, t = 0, scores 0, iters 0, SC_POLISH_STOP_DECLINED.  The
+ *               records are therefore a pose list for sc_pose_info_frame_device, sc_polish_poses_device, sc_assign_poses_* and for
+ *               this entry again (stride 64, with the status flag).
+ *   d_rounds    two words (NULL: not wanted): [0] the counted rounds, [1] the call's stop.
+ *   Every output is a function of the points, the poses in their order, the selection, tau, score_mode and max_iter only, bit for bit:
+ *   not of the launch geometry, the context's history, how the frame was enqueued, or (batch) a problem's position or n_problems.
+ * What the header promises, each bit for bit:
+ *   (1) the composed loop.  With R = d_rounds[0], plus 1 after FIXED: R rounds of sc_assign_poses_frame_device(BEST, the same
+ *       selection) followed by sc_polish_poses_device(SEL_LABEL, label0 0, max_iter 1, SC_POLISH_POSES_STATUS), each fed the round
+ *       before's records at stride 64, end in the same Rt; one more sc_assign_poses_frame_device on them writes d_label, d_d2 and,
+ *       as its scores, every record's score.
+ *   (2) n_poses == 1 with SC_ASSIGN_SEL_NONE: the record is sc_polish_poses's (SEL_NONE, the same max_iter), label[m] == mask[m] - 1.
+ *   (3) a batch problem's records, labels and rounds are the frame form's on that problem alone.
+ *   (4) a list that came out with SC_POLISH_STOP_FIXED goes in again and comes out with 0 rounds and the same bytes.
+ *
+ * The frame form.  A FRAME is as defined for sc_peel.  The entries read the frame's staged points, its n, tau and score_mode, change
+ * nothing in it and do NOT end it: they may be repeated and interleaved with sc_peel, sc_polish*, sc_pose_info_frame and
+ * sc_assign_poses_frame.  Correspondences are in the caller's ORIGINAL indexing.  sel_mode SC_ASSIGN_SEL_NONE or SC_ASSIGN_SEL_MASK
+ * (d_sel: n bytes).  SC_SETTLE_STATUS: the pose record holds a status at byte 48; without it nothing past byte 47 is read.
+ * pose_stride is a multiple of 4 and at least 48, at least 52 with the flag; 1 <= n_poses <= SC_SETTLE_MAX_POSES.  The device form
+ * enqueues ONE launch whatever n, n_poses and max_iter are and returns without waiting; the host form copies in, enqueues, copies
+ * out and waits.
+ * The batch form, packed only.  The problems of sc_register_batch (offset a HOST array, params->layout, 3 <= n_b <= SC_BATCH_MAX_N);
+ * the poses and the records motion-major as sc_assign_poses_batch has them — one plane of sc_register_instances_batch's d_res per
+ * pose, stride 80 —, the status at byte 48 always read (pose_stride at least 52); 1 <= n_poses <= SC_SETTLE_BATCH_MAX_POSES; sel_mode
+ * must be SC_ASSIGN_SEL_NONE.  d_label: total int32 positioned like sc_register_batch's mask; d_rounds: two words per problem.  A
+ * problem holding a non-finite coordinate gets label -1 throughout, SC_EINVAL in every one of its records (R = I, zeros,
+ * SC_POLISH_STOP_DECLINED) and the words 0, SC_POLISH_STOP_DECLINED; its neighbours are untouched.  Like every batch entry it ends
+ * the frame a context may hold.  params is checked as sc_register_batch checks it; only tau, score_mode and layout are read.
+ * Errors: the CALL returns SC_EINVAL, decided on the host before anything is enqueued, sc_last_error naming which: a NULL argument
+ * (a NULL ctx: no text; d_d2 and d_rounds may be NULL); sp->size wrong; max_iter outside 1 .. 64; sel_mode above 1 (batch: not 0);
+ * d_sel NULL with SC_ASSIGN_SEL_MASK; an unknown flag or a non-zero reserved word; n_poses 0 or above the form's maximum; a
+ * pose_stride that breaks the rule; no frame on the context (sc_peel's refusal, with its text); a call outstanding on the context;
+ * the batch form's offsets and params as sc_assign_poses_batch refuses them.  A refused call leaves the frame.
+ * Workspace: the frame form keeps the member bits and chunk sums of a round in n_poses x ceil(n / 64) x 16 doubles — the buffer
+ * sc_polish_poses keeps, shared: the calls are stream-ordered, a context that uses both holds one —; the batch form the copy of the
+ * offsets; the host forms device copies of their arrays.  Everything is allocated by the first such call, counted in
+ * workspace_bytes and held against the cap (SC_ENOMEM, nothing enqueued, the frame stays).  A context that never calls these entries
+ * allocates and runs nothing new.
+ * The loop this closes, every step stream-ordered and none read back: sc_register_instances -> sc_polish_poses_device(SEL_ALIVE) ->
+ * sc_settle_poses_frame_device -> sc_pose_info_frame_device(SEL_LABEL, d_label, stride 64).
+ * Not here: merging or dropping poses (two copies of a pose split its inliers between them by the tie rule: the lower k takes the
+ * ties, both stay in the list); soft assignment; slots and pairs forms; a form for sharded frames, which leave no frame. */
+#define SC_SETTLE_MAX_POSES       64u   /* frame form */
+#define SC_SETTLE_BATCH_MAX_POSES 16u   /* batch form: SC_INSTANCES_BATCH_MAX planes */
+#define SC_SETTLE_STATUS 1u             /* flags: a pose record holds an int32 status at byte 48 */
+typedef struct sc_settle_params {   /* 32 bytes */
+  uint32_t size;         /* = sizeof(sc_settle_params)                      */
+  uint32_t max_iter;     /* counted rounds at most, 1 .. 64                 */
+  uint32_t sel_mode;     /* SC_ASSIGN_SEL_NONE / _MASK; batch: _NONE        */
+  uint32_t flags;        /* SC_SETTLE_STATUS or 0                           */
+  uint32_t reserved[4];  /* must be 0                                       */
+} sc_settle_params;
+int sc_settle_default_params(sc_settle_params* sp);   /* size set, max_iter 16, everything else 0 */
+/* d_pose: n_poses records of pose_stride bytes; d_sel per sel_mode (NULL with SEL_NONE); d_pol: n_poses records; d_label: n int32;
+ * d_d2: n floats or NULL; d_rounds: 2 words or NULL */
+int sc_settle_poses_frame_device(sc_ctx* ctx, const sc_settle_params* sp, const void* d_pose, uint32_t pose_stride, uint32_t n_poses,
+                                 const uint8_t* d_sel, sc_polish_batch_result* d_pol, int32_t* d_label, float* d_d2, uint32_t* d_rounds);
+/* the same with host arrays (pose, sel, pol, label, d2, rounds); waits */
+int sc_settle_poses_frame(sc_ctx* ctx, const sc_settle_params* sp, const void* pose, uint32_t pose_stride, uint32_t n_poses,
+                          const uint8_t* sel, sc_polish_batch_result* pol, int32_t* label, float* d2, uint32_t* rounds);
+/* every buffer but offset in HBM: d_src / d_tgt total x 3 floats, d_pose n_poses x n_problems records of pose_stride bytes
+ * (motion-major), d_pol n_poses x n_problems records (motion-major), d_label total int32, d_rounds 2 x n_problems words or NULL */
+int sc_settle_poses_batch_device(sc_ctx* ctx, const float* d_src, const float* d_tgt, const uint32_t* offset, uint32_t n_problems,
+                                 const sc_params* params, const sc_settle_params* sp, const void* d_pose, uint32_t pose_stride,
+                                 uint32_t n_poses, sc_polish_batch_result* d_pol, int32_t* d_label, uint32_t* d_rounds);
+/* the same with host arrays; waits */
+int sc_settle_poses_batch(sc_ctx* ctx, const float* src, const float* tgt, const uint32_t* offset, uint32_t n_problems,
+                          const sc_params* params, const sc_settle_params* sp, const void* pose, uint32_t pose_stride,
+                          uint32_t n_poses, sc_polish_batch_result* pol, int32_t* label, uint32_t* rounds);
 
 /* ---- two-phase form for one-process-per-GPU sharding --------------------------------
  * Phase 1: A and B replicated, C1+C2 on this rank's blocks of the top-T list; writes this rank's winner key

@@ -55,6 +55,8 @@ EXPORTS = ["sc_version", "sc_strerror", "sc_default_params", "sc_create", "sc_de
            "sc_polish_poses_default_params", "sc_polish_poses", "sc_polish_poses_device",
            "sc_assign_default_params", "sc_assign_poses_frame", "sc_assign_poses_frame_device", "sc_assign_poses_batch",
            "sc_assign_poses_batch_device",
+           "sc_settle_default_params", "sc_settle_poses_frame", "sc_settle_poses_frame_device", "sc_settle_poses_batch",
+           "sc_settle_poses_batch_device",
            "sc_hypothesize_device", "sc_finalize_device",
            "sc_hypothesize_begin_device", "sc_hypothesize_end_device", "sc_finalize_gathered_device", "sc_finalize_gathered_device_async",
            "sc_shard_plan_query", "sc_shard_compat_device", "sc_shard_edges_device", "sc_shard_select_device",
@@ -187,6 +189,16 @@ SC_ASSIGN_MAX_POSES, SC_ASSIGN_BATCH_MAX_POSES = 1024, 64
 SC_ASSIGN_BEST, SC_ASSIGN_FIRST = 0, 1
 SC_ASSIGN_SEL_NONE, SC_ASSIGN_SEL_MASK = 0, 1
 SC_ASSIGN_STATUS = 1
+
+
+class ScSettleParams(C.Structure):
+    """Mirror of `sc_settle_params` (include/saccot.h), 32 bytes: counted rounds at most (1 .. 64), which correspondences take part
+    (SC_ASSIGN_SEL_*), SC_SETTLE_STATUS or 0."""
+    _fields_ = [("size", C.c_uint32), ("max_iter", C.c_uint32), ("sel_mode", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 4)]
+
+
+SC_SETTLE_MAX_POSES, SC_SETTLE_BATCH_MAX_POSES = 64, 16
+SC_SETTLE_STATUS = 1
 SC_GUIDE_POSE_STATUS = 1  # sc_guide_params.flags, the sc_match_guided_batch / _poses entries only: the pose records hold an int32 status at byte 48
 SC_GUIDE_MAX_POSES = 64  # pose records per call of sc_match_guided_poses at most
 SC_MATCH_BATCH_MAX_N = 4096  # rows a side of one problem of sc_match_batch
@@ -348,6 +360,12 @@ def load_library() -> C.CDLL:
     L.sc_assign_poses_frame_device.argtypes = [vp, ap, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
     L.sc_assign_poses_batch.argtypes = [vp, f32p, f32p, u32p, C.c_uint32, pp, ap, vp, C.c_uint32, C.c_uint32, vp, vp]
     L.sc_assign_poses_batch_device.argtypes = [vp, vp, vp, u32p, C.c_uint32, pp, ap, vp, C.c_uint32, C.c_uint32, vp, vp]
+    tp = C.POINTER(ScSettleParams)
+    L.sc_settle_default_params.argtypes = [tp]
+    L.sc_settle_poses_frame.argtypes = [vp, tp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]
+    L.sc_settle_poses_frame_device.argtypes = [vp, tp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]
+    L.sc_settle_poses_batch.argtypes = [vp, f32p, f32p, u32p, C.c_uint32, pp, tp, vp, C.c_uint32, C.c_uint32, vp, vp, vp]
+    L.sc_settle_poses_batch_device.argtypes = [vp, vp, vp, u32p, C.c_uint32, pp, tp, vp, C.c_uint32, C.c_uint32, vp, vp, vp]
     L.sc_hypothesize_device.argtypes = [vp, vp, vp, C.c_int64, pp, vp, sp]
     L.sc_finalize_device.argtypes = [vp, vp, vp, vp, sp]
     L.sc_hypothesize_begin_device.argtypes = [vp, vp, vp, C.c_int64, pp, vp, sp]
@@ -410,6 +428,11 @@ def make_polish_poses_params(max_iter: int = 16, sel_mode: int = SC_POLISH_POSES
 def make_assign_params(mode: int = SC_ASSIGN_BEST, sel_mode: int = SC_ASSIGN_SEL_NONE, flags: int = 0) -> ScAssignParams:
     """sc_assign_params: mode SC_ASSIGN_BEST / _FIRST, sel_mode SC_ASSIGN_SEL_*, flags SC_ASSIGN_STATUS or 0."""
     return ScAssignParams(C.sizeof(ScAssignParams), mode, sel_mode, flags)
+
+
+def make_settle_params(max_iter: int = 16, sel_mode: int = SC_ASSIGN_SEL_NONE, flags: int = 0) -> ScSettleParams:
+    """sc_settle_params: max_iter 1 .. 64 counted rounds, sel_mode SC_ASSIGN_SEL_*, flags SC_SETTLE_STATUS or 0."""
+    return ScSettleParams(C.sizeof(ScSettleParams), max_iter, sel_mode, flags)
 
 
 def shard_plan(params: ScParams, n: int) -> ScShardPlan:
@@ -1366,6 +1389,78 @@ class Registrar:
         self._frame_n = 0
         self._check(self._lib.sc_assign_poses_batch_device(self._h, d_src, d_tgt, _p(offset, C.c_uint32), max(len(offset) - 1, 0),
                                                            C.byref(params), C.byref(aparams), d_pose, pose_stride, n_poses, d_label, d_asg))
+
+    # ---- poses relabelled and refitted until stable (include/saccot.h, sc_settle_poses) -----------------------------------------
+    def settle_poses_frame(self, pose, sparams: ScSettleParams | None = None, sel=None, want_d2: bool = True, want_rounds: bool = True,
+                           **kw):
+        """sc_settle_poses_frame: pose (K,) records of any dtype whose items start with float Rt[12] (and, with SC_SETTLE_STATUS, an
+        int32 status behind it) — or a float32 array (K, 12) / (12,) —; sel None or (n,) uint8 (SC_ASSIGN_SEL_MASK), read only ->
+        (records (K,) of POLISH_BATCH_RESULT_DTYPE, label (n,) int32, d2 (n,) float32 or None, rounds (2,) uint32 — counted rounds,
+        stop — or None).  The frame stays.  kw: max_iter, sel_mode, flags (make_settle_params)."""
+        q = sparams or make_settle_params(**kw)
+        pose = np.ascontiguousarray(pose)
+        if pose.dtype.fields is None:
+            pose = np.ascontiguousarray(pose, dtype=np.float32).reshape(-1, 12)
+            stride = 48
+        else:
+            pose = pose.reshape(-1)
+            stride = pose.dtype.itemsize
+        k, n = len(pose), self._frame_n
+        if sel is not None:
+            sel = np.ascontiguousarray(sel, dtype=np.uint8)
+            if sel.size != n:
+                raise ValueError("settle_poses_frame: sel holds one entry per correspondence of the frame")
+        pol = np.zeros(max(k, 1), POLISH_BATCH_RESULT_DTYPE)
+        label = np.zeros(max(n, 1), np.int32)
+        d2 = np.zeros(max(n, 1), np.float32) if want_d2 else None
+        rounds = np.zeros(2, np.uint32) if want_rounds else None
+        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        self._check(self._lib.sc_settle_poses_frame(self._h, C.byref(q), vp(pose), stride, k, vp(sel), vp(pol), vp(label), vp(d2),
+                                                    vp(rounds)))
+        return pol[:k], label[:n], (None if d2 is None else d2[:n]), rounds
+
+    def settle_poses_frame_device(self, sparams: ScSettleParams, d_pose: int, pose_stride: int, n_poses: int, d_sel: int, d_pol: int,
+                                  d_label: int, d_d2: int = 0, d_rounds: int = 0):
+        """sc_settle_poses_frame_device: pose records (pose_stride bytes each, read only), the selection (0: none), the output
+        records (64 bytes each), the labels (n int32), the residuals (n floats; 0: none) and the two words (0: none) in HBM;
+        enqueues ONE launch on the context's stream and returns without waiting.  The frame stays."""
+        self._check(self._lib.sc_settle_poses_frame_device(self._h, C.byref(sparams), d_pose, pose_stride, n_poses, d_sel or None, d_pol,
+                                                           d_label, d_d2 or None, d_rounds or None))
+
+    def settle_poses_batch(self, src, tgt, offset, params: ScParams, pose, sparams: ScSettleParams | None = None, **kw):
+        """sc_settle_poses_batch on packed arrays: src / tgt / offset as register_batch_raw's; pose (K, B) records, motion-major, of any
+        dtype whose items start with float Rt[12] and int32 status — register_instances_batch_raw's records — read only ->
+        (records (K, B) of POLISH_BATCH_RESULT_DTYPE, label (total,) int32, rounds (B, 2) uint32).  kw: max_iter, flags
+        (make_settle_params)."""
+        q = sparams or make_settle_params(**kw)
+        src, tgt = _f32c(src), _f32c(tgt)
+        offset = np.ascontiguousarray(offset, dtype=np.uint32)
+        pose = np.ascontiguousarray(pose)
+        nb = max(len(offset) - 1, 0)
+        total = int(offset[-1]) if len(offset) else 0
+        if pose.ndim != 2 or pose.shape[1] != nb:
+            raise ValueError("settle_poses_batch: pose holds (n_poses, n_problems) records")
+        k = pose.shape[0]
+        pol = np.zeros((max(k, 1), max(nb, 1)), POLISH_BATCH_RESULT_DTYPE)
+        label = np.zeros(max(total, 1), np.int32)
+        rounds = np.zeros((max(nb, 1), 2), np.uint32)
+        self._frame_n = 0
+        self._check(self._lib.sc_settle_poses_batch(self._h, _p(src, C.c_float), _p(tgt, C.c_float), _p(offset, C.c_uint32), nb,
+                                                    C.byref(params), C.byref(q), pose.ctypes.data_as(C.c_void_p), pose.dtype.itemsize, k,
+                                                    pol.ctypes.data_as(C.c_void_p), label.ctypes.data_as(C.c_void_p),
+                                                    rounds.ctypes.data_as(C.c_void_p)))
+        return pol[:k, :nb], label[:total], rounds[:nb]
+
+    def settle_poses_batch_device(self, d_src: int, d_tgt: int, offset, params: ScParams, sparams: ScSettleParams, d_pose: int,
+                                  pose_stride: int, n_poses: int, d_pol: int, d_label: int, d_rounds: int = 0):
+        """sc_settle_poses_batch_device: points, pose records (n_poses x B of pose_stride bytes, motion-major, read only), output
+        records (n_poses x B of 64 bytes, motion-major), labels (total int32) and the word pairs (2 x B; 0: none) in HBM, offset a
+        HOST array (B + 1,) uint32; enqueues on the context's stream and returns without waiting."""
+        offset = np.ascontiguousarray(offset, dtype=np.uint32)
+        self._frame_n = 0
+        self._check(self._lib.sc_settle_poses_batch_device(self._h, d_src, d_tgt, _p(offset, C.c_uint32), max(len(offset) - 1, 0),
+                                                           C.byref(params), C.byref(sparams), d_pose, pose_stride, n_poses, d_pol, d_label,
+                                                           d_rounds or None))
 
     def hypothesize_device(self, d_src: int, d_tgt: int, n: int, params: ScParams, d_key: int):
         st = ScStats(C.sizeof(ScStats))

@@ -146,7 +146,11 @@ struct Workspace {
       // sc_assign_poses: allocated by the first such call, never by a frame or by another entry.  The frame form's device entry needs
       // none of them (the tallies are added into the caller's records).  off: the batch form's copy of the caller's offsets; the
       // rest: device copies of the host entries' arrays (src / tgt: the batch form's points)
-      asg_off, asg_src, asg_tgt, asg_pose, asg_sel, asg_label, asg_d2, asg_out;
+      asg_off, asg_src, asg_tgt, asg_pose, asg_sel, asg_label, asg_d2, asg_out,
+      // sc_settle_poses: allocated by the first such call, never by a frame or by another entry.  The frame form's member bits and
+      // chunk sums live in ppose_tmp — sc_polish_poses's buffer, the same layout: the calls are stream-ordered, so one serves both.
+      // off: the batch form's copy of the caller's offsets; the rest: device copies of the host entries' arrays
+      stl_off, stl_src, stl_tgt, stl_pose, stl_sel, stl_out, stl_label, stl_d2, stl_rounds;
 };
 constexpr size_t N_WORKSPACE_BUFS = sizeof(Workspace) / sizeof(Buf);
 static_assert(std::is_standard_layout<Workspace>::value && alignof(Workspace) == alignof(Buf) && sizeof(Workspace) == N_WORKSPACE_BUFS * sizeof(Buf),

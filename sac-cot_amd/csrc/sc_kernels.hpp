@@ -980,6 +980,45 @@ struct AssignBatchJob {
 // ONE launch, a workgroup per problem; every label of a problem's range and every record is written (complete in stream order).
 void launch_assign_batch(const AssignBatchJob& job, hipStream_t st);
 
+// ---- poses relabelled and refitted until stable (sc_settle_poses; sc_settle.hpp, sc_settle_frame.hip, sc_settle_batch.hip) ----
+// The frame form.  The pose records as AssignFrameJob's.  sel: nullptr or n bytes.  label: n int32 (every pass stores it; the last
+// pass's stores are the output); d2: n floats or nullptr; out: n_poses records; rounds: two words or nullptr.  scratch: n_poses *
+// polish_poses_scratch_bytes(pts.n), the layout of PolishPosesJob's.  Everything in device memory.
+struct SettleFrameJob {
+  Points pts;  // the frame's staged planes, in the caller's indexing
+  float tau2, thr;
+  int score_mode;
+  uint32_t max_iter, n_poses;
+  const void* pose;
+  uint32_t pose_stride;
+  int status;
+  const uint8_t* sel;
+  double* scratch;
+  PolishBatchRecord* out;
+  int32_t* label;
+  float* d2;
+  uint32_t* rounds;
+};
+// ONE launch of ONE workgroup of 1024 threads; every label (and d2), every record and the two words are written.
+void launch_settle_frame(const SettleFrameJob& job, hipStream_t st);
+// The batch form.  Problems, poses and records as AssignBatchJob's (motion-major, the status always read); rounds: two words per
+// problem or nullptr.
+struct SettleBatchJob {
+  const float* src; const float* tgt;
+  const uint32_t* offset;
+  uint32_t n_problems, total;
+  int soa, score_mode;
+  float tau2, thr;
+  uint32_t max_iter, n_poses;
+  const void* pose;
+  uint32_t pose_stride;
+  PolishBatchRecord* out;
+  int32_t* label;
+  uint32_t* rounds;
+};
+// ONE launch, a workgroup per problem; every label of a problem's range, every record and word pair is written.
+void launch_settle_batch(const SettleBatchJob& job, hipStream_t st);
+
 // ---- descriptor matching for a batch of small problems (sc_match_batch; sc_match_batch.hip) -----------------
 // Problem b owns rows [src_off[b], src_off[b + 1]) of fsrc and [tgt_off[b], tgt_off[b + 1]) of ftgt (1 .. MATCH_BATCH_MAX_N rows
 // each, checked by the caller) and the output slot that starts at entry slot[b] = src_off[b] * knn.  tile_map: n_tiles pairs

@@ -30,6 +30,67 @@ namespace sc {
 
 enum : uint32_t { GO_FIXED = 0u, GO_CHANGED = 1u, GO_DECLINED = 2u };  // what the solving thread tells the workgroup
 
+// ---- the fp64 chains, once each: refit_iterate below runs them for one pose, the round of sc_settle_poses (sc_settle.hpp) for K poses
+// at a time.  A chain sees a chunk's bit word and the planes, never who set the bits or where the sums are kept.
+// pass 1, slot k of chunk ch: the count (k == 0), sum p (1 .. 3) or sum q (4 .. 6) of the chunk's set bits, sequentially in index order
+__device__ __forceinline__ double refit_chain1(const float* __restrict__ planes, int ld, int ch, int k, unsigned long long b) {
+  const float* __restrict__ own = planes + (size_t)(k ? k - 1 : 0) * ld + (size_t)ch * 64;
+  double c = 0.0;
+  while (b) {
+    const int j = __builtin_ctzll(b);
+    b &= b - 1ull;
+    c += k ? (double)own[j] : 1.0;
+  }
+  return c;
+}
+// the centroids of pass 1's sums S[7] (cnt = S[0] >= 3)
+__device__ __forceinline__ void refit_centroids(const double* S, double cnt, double (&pc)[3], double (&qc)[3]) {
+  pc[0] = S[1] / cnt; pc[1] = S[2] / cnt; pc[2] = S[3] / cnt;
+  qc[0] = S[4] / cnt; qc[1] = S[5] / cnt; qc[2] = S[6] / cnt;
+}
+// pass 2, entry e of H for chunk ch: h = fma(p_r - pc_r, q_c - qc_c, h) over the chunk's set bits
+__device__ __forceinline__ double refit_chain2(const float* __restrict__ planes, int ld, int ch, int e, unsigned long long b,
+                                               const double (&pc)[3], const double (&qc)[3]) {
+  const int r = e / 3, cc = e % 3;
+  const float* __restrict__ pr = planes + (size_t)r * ld + (size_t)ch * 64;
+  const float* __restrict__ qr = planes + (size_t)(3 + cc) * ld + (size_t)ch * 64;
+  const double pcr = r == 0 ? pc[0] : (r == 1 ? pc[1] : pc[2]), qcc = cc == 0 ? qc[0] : (cc == 1 ? qc[1] : qc[2]);
+  double h = 0.0;
+  while (b) {
+    const int j = __builtin_ctzll(b);
+    b &= b - 1ull;
+    h = __builtin_fma((double)pr[j] - pcr, (double)qr[j] - qcc, h);
+  }
+  return h;
+}
+// the chunk sums in chunk order; at(ch): one slot of chunk ch
+template <class At>
+__device__ __forceinline__ double refit_chunk_sum(int nch, At at) {
+  double s = 0.0;
+  for (int ch = 0; ch < nch; ch++) s += at(ch);
+  return s;
+}
+// The solve on H[9] and the centroids, against the iterate M it started from: GO_DECLINED (not finite), GO_FIXED (M's bits again) or
+// GO_CHANGED, and then Rt holds the new iterate.  One thread.
+__device__ __forceinline__ uint32_t refit_solve(const double* H, const double (&pc)[3], const double (&qc)[3], const float* M,
+                                                float* Rt) {
+  double Hs[9];
+#pragma unroll
+  for (int k = 0; k < 9; k++) Hs[k] = H[k];
+  float out[12];
+  uint32_t g = GO_DECLINED;
+  if (refine_solve(Hs, pc, qc, out)) {  // (not finite: declined)
+    g = GO_FIXED;
+#pragma unroll
+    for (int c = 0; c < 12; c++) g |= (__float_as_uint(out[c]) != __float_as_uint(M[c])) ? GO_CHANGED : GO_FIXED;
+    if (g) {
+#pragma unroll
+      for (int c = 0; c < 12; c++) Rt[c] = out[c];
+    }
+  }
+  return g;
+}
+
 // Refits of Rt[12] (LDS; the workgroup sees the caller's stores to it) over the n correspondences of `planes`, until one is declined
 // (fewer than 3 inliers, a non-finite result: SC_POLISH_STOP_DECLINED), returns the bits it started from (_FIXED), or max_iter are
 // done (_MAX_ITER).  Rt holds the last iterate when it returns, visible to every thread.  S[8], H[9], go: LDS words of the workgroup.
@@ -61,70 +122,29 @@ __device__ __forceinline__ Refit refit_iterate(const float* __restrict__ planes,
     }
     ck.publish();
     __syncthreads();
-    // pass 1: lane = (chunk, component): count, sum p (3), sum q (3) of the chunk's inliers, sequentially in index order
+    // pass 1: lane = (chunk, component)
     for (int w = tid; w < nch * 7; w += THREADS) {
       const int ch = w / 7, k = w % 7;
-      const float* __restrict__ own = planes + (size_t)(k ? k - 1 : 0) * ld + (size_t)ch * 64;
-      unsigned long long b = ck.bits(ch);
-      double c = 0.0;
-      while (b) {
-        const int j = __builtin_ctzll(b);
-        b &= b - 1ull;
-        c += k ? (double)own[j] : 1.0;
-      }
-      ck.sum(ch, k) = c;
+      ck.sum(ch, k) = refit_chain1(planes, ld, ch, k, ck.bits(ch));
     }
     ck.publish();
     __syncthreads();
-    if (tid < 7) {  // the chunk sums in chunk order, one lane per component
-      double s = 0.0;
-      for (int ch = 0; ch < nch; ch++) s += ck.sum(ch, tid);
-      S[tid] = s;
-    }
+    if (tid < 7) S[tid] = refit_chunk_sum(nch, [&](int ch) { return ck.sum(ch, tid); });  // one lane per component
     __syncthreads();
     const double cnt = S[0];
     if (cnt < 3.0) { res.stop = SC_POLISH_STOP_DECLINED; break; }  // (uniform) the refit is declined: (R, t) stays
-    const double pc[3] = {S[1] / cnt, S[2] / cnt, S[3] / cnt}, qc[3] = {S[4] / cnt, S[5] / cnt, S[6] / cnt};
-    // pass 2: lane = (chunk, entry of H): h = fma(p_r - pc_r, q_c - qc_c, h) over the chunk's inliers
+    double pc[3], qc[3];
+    refit_centroids(S, cnt, pc, qc);
+    // pass 2: lane = (chunk, entry of H)
     for (int w = tid; w < nch * 9; w += THREADS) {
-      const int ch = w / 9, e = w % 9, r = e / 3, cc = e % 3;
-      const float* __restrict__ pr = planes + (size_t)r * ld + (size_t)ch * 64;
-      const float* __restrict__ qr = planes + (size_t)(3 + cc) * ld + (size_t)ch * 64;
-      const double pcr = r == 0 ? pc[0] : (r == 1 ? pc[1] : pc[2]), qcc = cc == 0 ? qc[0] : (cc == 1 ? qc[1] : qc[2]);
-      unsigned long long b = ck.bits(ch);
-      double h = 0.0;
-      while (b) {
-        const int j = __builtin_ctzll(b);
-        b &= b - 1ull;
-        h = __builtin_fma((double)pr[j] - pcr, (double)qr[j] - qcc, h);
-      }
-      ck.sum(ch, e) = h;
+      const int ch = w / 9, e = w % 9;
+      ck.sum(ch, e) = refit_chain2(planes, ld, ch, e, ck.bits(ch), pc, qc);
     }
     ck.publish();
     __syncthreads();
-    if (tid < 9) {
-      double s = 0.0;
-      for (int ch = 0; ch < nch; ch++) s += ck.sum(ch, tid);
-      H[tid] = s;
-    }
+    if (tid < 9) H[tid] = refit_chunk_sum(nch, [&](int ch) { return ck.sum(ch, tid); });
     __syncthreads();
-    if (tid == 0) {
-      double Hs[9];
-#pragma unroll
-      for (int k = 0; k < 9; k++) Hs[k] = H[k];
-      float out[12];
-      uint32_t g = GO_DECLINED;
-      if (refine_solve(Hs, pc, qc, out)) {  // (not finite: declined)
-        g = GO_FIXED;
-#pragma unroll
-        for (int c = 0; c < 12; c++) g |= (__float_as_uint(out[c]) != __float_as_uint(M[c])) ? GO_CHANGED : GO_FIXED;
-        if (g) {
-#pragma unroll
-          for (int c = 0; c < 12; c++) Rt[c] = out[c];
-        }
-      }
-      *go = g;
-    }
+    if (tid == 0) *go = refit_solve(H, pc, qc, M, Rt);
     __syncthreads();
     const uint32_t g = *go;
     if (g != GO_CHANGED) {  // (uniform) declined, or the fixed point: the refit returned the bits it started from
