@@ -9,7 +9,7 @@
 // copy (enqueued) -> ONE launch, a workgroup per problem.  Nothing is read back by either.  Everything that can refuse a call is
 // decided on the host before anything is enqueued.
 #include "sc_assign_check.hpp"
-#include "sc_ctx.hpp"
+#include "sc_capi_pose.hpp"
 
 using namespace sc;
 
@@ -17,24 +17,12 @@ static_assert(sizeof(sc_assign_params) == 32 && sizeof(sc_assign_result) == 32, 
 
 namespace {
 
-// ---- the frame form: the refusals both entries share, then "is there a frame"; `who` opens the message
-int asg_frame_check(sc_ctx* c, const sc_assign_params* ap, uint32_t pose_stride, uint32_t n_poses, const void* sel, const char* who) {
-  SC_TRY(busy(c));
-  if (const char* what = assign_params_error(ap, pose_stride, n_poses, false, sel != nullptr)) return refuse(c, who, what);
-  return scored_frame_begin(c, who);
-}
-
+// ---- the frame form
 int asg_frame_enqueue(sc_ctx* c, const sc_assign_params* ap, const void* d_pose, uint32_t pose_stride, uint32_t n_poses,
                       const uint8_t* d_sel, int32_t* d_label, float* d_d2, sc_assign_result* d_asg) {
-  const Pass& ps = c->pass;
   AssignFrameJob job{};
-  job.pts = points_of(c);
-  job.tau2 = ps.dv.tau2;
-  job.thr = score_thr(ps.dv, ps.params.score_mode);
-  job.score_mode = ps.params.score_mode;
-  job.mode = ap->mode; job.n_poses = n_poses;
-  job.pose = d_pose; job.pose_stride = pose_stride;
-  job.status = assign_reads_status(ap, false);
+  pose_frame_head(c, &job, d_pose, pose_stride, n_poses, assign_reads_status(ap, false));
+  job.mode = ap->mode;
   job.sel = ap->sel_mode == SC_ASSIGN_SEL_MASK ? d_sel : nullptr;
   job.label = d_label; job.d2 = d_d2;
   job.out = reinterpret_cast<AssignRecord*>(d_asg);
@@ -44,28 +32,13 @@ int asg_frame_enqueue(sc_ctx* c, const sc_assign_params* ap, const void* d_pose,
   return SC_OK;
 }
 
-// ---- the batch form: the refusals both entries share
-int asg_batch_check(sc_ctx* c, const uint32_t* offset, uint32_t n_problems, const sc_params* p, const sc_assign_params* ap,
-                    uint32_t pose_stride, uint32_t n_poses, const char* who) {
-  SC_TRY(entry_checks(c, nullptr, ENDS_FRAME | NOT_BUSY));
-  SC_TRY(batch_params_check(c, p, who));
-  if (const char* what = assign_params_error(ap, pose_stride, n_poses, true, false)) return refuse(c, who, what);
-  if (const char* what = batch_offsets_error(offset, n_problems)) return refuse(c, who, what);
-  return SC_OK;
-}
-
+// ---- the batch form
 int asg_batch_enqueue(sc_ctx* c, const float* d_src, const float* d_tgt, const uint32_t* offset, uint32_t n_problems, const sc_params* p,
                       const sc_assign_params* ap, const void* d_pose, uint32_t pose_stride, uint32_t n_poses, int32_t* d_label,
                       sc_assign_result* d_asg) {
-  SC_TRY(batch_offsets_to_device(c, offset, n_problems, c->asg_off));
-  const Derived dv = derive(p);
   AssignBatchJob job{};
-  job.src = d_src; job.tgt = d_tgt; job.offset = c->asg_off.as<uint32_t>();
-  job.n_problems = n_problems; job.total = offset[n_problems];
-  job.soa = p->layout == SC_SOA; job.score_mode = p->score_mode;
-  job.tau2 = dv.tau2; job.thr = score_thr(dv, p->score_mode);
-  job.mode = ap->mode; job.n_poses = n_poses;
-  job.pose = d_pose; job.pose_stride = pose_stride;
+  SC_TRY(pose_batch_head(c, &job, c->asg_off, d_src, d_tgt, offset, n_problems, p, d_pose, pose_stride, n_poses));
+  job.mode = ap->mode;
   job.label = d_label;
   job.out = reinterpret_cast<AssignRecord*>(d_asg);
   launch_assign_batch(job, c->stream);
@@ -89,7 +62,7 @@ int sc_assign_poses_frame_device(sc_ctx* c, const sc_assign_params* ap, const vo
   static const char* const who = "sc_assign_poses_frame_device";
   if (!c) return SC_EINVAL;
   if (!ap || !d_pose || !d_label || !d_asg) return refuse(c, who, "a NULL argument");
-  SC_TRY(asg_frame_check(c, ap, pose_stride, n_poses, d_sel, who));
+  SC_TRY(pose_frame_check(c, who, assign_params_error(ap, pose_stride, n_poses, false, d_sel != nullptr)));
   return asg_frame_enqueue(c, ap, d_pose, pose_stride, n_poses, d_sel, d_label, d_d2, d_asg);  // (no wait: the outputs are complete in stream order)
 }
 
@@ -98,22 +71,19 @@ int sc_assign_poses_frame(sc_ctx* c, const sc_assign_params* ap, const void* pos
   static const char* const who = "sc_assign_poses_frame";
   if (!c) return SC_EINVAL;
   if (!ap || !pose || !label || !asg) return refuse(c, who, "a NULL argument");
-  SC_TRY(asg_frame_check(c, ap, pose_stride, n_poses, sel, who));
+  SC_TRY(pose_frame_check(c, who, assign_params_error(ap, pose_stride, n_poses, false, sel != nullptr)));
   const size_t n = (size_t)c->pass.n;
   const bool masked = ap->sel_mode == SC_ASSIGN_SEL_MASK;
   HostArrays h(c);
-  h.in(c->asg_pose, pose, (size_t)assign_pose_bytes(n_poses, pose_stride, assign_reads_status(ap, false)));
+  h.in(c->asg_pose, pose, (size_t)pose_bytes_read(n_poses, pose_stride, assign_reads_status(ap, false)));
   if (masked) h.in(c->asg_sel, sel, n);
   h.out(c->asg_label, label, n * 4);
   if (d2) h.out(c->asg_d2, d2, n * 4);
   h.out(c->asg_out, asg, (size_t)n_poses * sizeof(sc_assign_result));
-  SC_TRY(h.room());
-  SC_TRY(h.send());
-  SC_TRY(asg_frame_enqueue(c, ap, c->asg_pose.p, pose_stride, n_poses, masked ? c->asg_sel.as<uint8_t>() : nullptr,
-                           c->asg_label.as<int32_t>(), d2 ? c->asg_d2.as<float>() : nullptr, c->asg_out.as<sc_assign_result>()));
-  SC_TRY(h.fetch());
-  HIPCHK(c, hipGetLastError());
-  return SC_OK;
+  return pose_frame_host(c, h, nullptr, 0, [&] {  // (no scratch: the tallies are added into the records)
+    return asg_frame_enqueue(c, ap, c->asg_pose.p, pose_stride, n_poses, masked ? c->asg_sel.as<uint8_t>() : nullptr,
+                             c->asg_label.as<int32_t>(), d2 ? c->asg_d2.as<float>() : nullptr, c->asg_out.as<sc_assign_result>());
+  });
 }
 
 int sc_assign_poses_batch_device(sc_ctx* c, const float* d_src, const float* d_tgt, const uint32_t* offset, uint32_t n_problems,
@@ -122,9 +92,7 @@ int sc_assign_poses_batch_device(sc_ctx* c, const float* d_src, const float* d_t
   static const char* const who = "sc_assign_poses_batch_device";
   if (!c) return SC_EINVAL;
   if (!d_src || !d_tgt || !offset || !p || !ap || !d_pose || !d_label || !d_asg) return refuse(c, who, "a NULL argument");
-  SC_TRY(asg_batch_check(c, offset, n_problems, p, ap, pose_stride, n_poses, who));
-  HIPCHK(c, hipSetDevice(c->device));
-  c->cap_bytes = workspace_cap(p);
+  SC_TRY(pose_batch_check(c, who, p, assign_params_error(ap, pose_stride, n_poses, true, false), offset, n_problems));
   return asg_batch_enqueue(c, d_src, d_tgt, offset, n_problems, p, ap, d_pose, pose_stride, n_poses, d_label, d_asg);
 }
 
@@ -134,14 +102,12 @@ int sc_assign_poses_batch(sc_ctx* c, const float* src, const float* tgt, const u
   static const char* const who = "sc_assign_poses_batch";
   if (!c) return SC_EINVAL;
   if (!src || !tgt || !offset || !p || !ap || !pose || !label || !asg) return refuse(c, who, "a NULL argument");
-  SC_TRY(asg_batch_check(c, offset, n_problems, p, ap, pose_stride, n_poses, who));
-  HIPCHK(c, hipSetDevice(c->device));
-  c->cap_bytes = workspace_cap(p);
+  SC_TRY(pose_batch_check(c, who, p, assign_params_error(ap, pose_stride, n_poses, true, false), offset, n_problems));
   const size_t total = offset[n_problems], pts = total * 12, records = (size_t)n_poses * n_problems;
   HostArrays h(c);
   h.in(c->asg_src, src, pts);
   h.in(c->asg_tgt, tgt, pts);
-  h.in(c->asg_pose, pose, (size_t)assign_pose_bytes(records, pose_stride, true));
+  h.in(c->asg_pose, pose, (size_t)pose_bytes_read(records, pose_stride, true));
   h.out(c->asg_label, label, total * 4);
   h.out(c->asg_out, asg, records * sizeof(sc_assign_result));
   SC_TRY(h.room());

@@ -6,26 +6,23 @@
 // batch_slot_meta; the pairs form's records: pairs_records) -> device copy (enqueued) -> ONE launch, a workgroup per problem.
 // Nothing is read back: a problem's status is a field of its record.  Everything that can refuse the call is decided on the host
 // before anything is enqueued.
-#include "sc_ctx.hpp"
+#include "sc_capi_pose.hpp"
 #include "sc_pairs_check.hpp"
 
 using namespace sc;
 
 namespace {
 
-constexpr uint32_t POSE_BYTES = 52;  // what is read of a pose record: float Rt[12], int32 status
+// the rule of the stride: the status of a record is always read (sc_pose_check.hpp)
+const char* pinfo_stride_error(uint32_t pose_stride) {
+  return pose_stride_ok(pose_stride, true) ? nullptr : "pose_stride must be a multiple of 4 and at least 52";
+}
 
-// the refusals every form shares: the context, sc_params, the stride of the pose records
+// the refusals the slot and the pairs form share: the context, sc_params, the stride of the pose records
 int pinfo_common_check(sc_ctx* c, const sc_params* p, uint32_t pose_stride, const char* who) {
   SC_TRY(entry_checks(c, nullptr, ENDS_FRAME | NOT_BUSY));
   SC_TRY(batch_params_check(c, p, who));
-  if (pose_stride < POSE_BYTES || pose_stride % 4 != 0) return refuse(c, who, "pose_stride must be a multiple of 4 and at least 52");
-  return SC_OK;
-}
-
-int pinfo_check(sc_ctx* c, const uint32_t* offset, uint32_t n_problems, const sc_params* p, uint32_t pose_stride) {
-  SC_TRY(pinfo_common_check(c, p, pose_stride, "sc_pose_info_batch"));
-  if (const char* what = batch_offsets_error(offset, n_problems)) return refuse(c, "sc_pose_info_batch", what);
+  if (const char* what = pinfo_stride_error(pose_stride)) return refuse(c, who, what);
   return SC_OK;
 }
 
@@ -59,9 +56,7 @@ int sc_pose_info_batch_device(sc_ctx* c, const float* d_src, const float* d_tgt,
                               const sc_params* p, const void* d_pose, uint32_t pose_stride, sc_pose_info_result* d_info) {
   if (!c) return SC_EINVAL;
   if (!d_src || !d_tgt || !offset || !p || !d_pose || !d_info) return refuse(c, "sc_pose_info_batch_device", "a NULL argument");
-  SC_TRY(pinfo_check(c, offset, n_problems, p, pose_stride));
-  HIPCHK(c, hipSetDevice(c->device));
-  c->cap_bytes = workspace_cap(p);
+  SC_TRY(pose_batch_check(c, "sc_pose_info_batch", p, pinfo_stride_error(pose_stride), offset, n_problems));
   return pinfo_enqueue(c, d_src, d_tgt, offset, n_problems, p, d_pose, pose_stride, d_info);
 }
 
@@ -69,14 +64,12 @@ int sc_pose_info_batch(sc_ctx* c, const float* src, const float* tgt, const uint
                        const void* pose, uint32_t pose_stride, sc_pose_info_result* info) {
   if (!c) return SC_EINVAL;
   if (!src || !tgt || !offset || !p || !pose || !info) return refuse(c, "sc_pose_info_batch", "a NULL argument");
-  SC_TRY(pinfo_check(c, offset, n_problems, p, pose_stride));
-  HIPCHK(c, hipSetDevice(c->device));
-  c->cap_bytes = workspace_cap(p);
+  SC_TRY(pose_batch_check(c, "sc_pose_info_batch", p, pinfo_stride_error(pose_stride), offset, n_problems));
   const size_t total = offset[n_problems], pts = total * 12;
   HostArrays h(c);
   h.in(c->pinfo_src, src, pts);
   h.in(c->pinfo_tgt, tgt, pts);
-  h.in(c->pinfo_pose, pose, (size_t)(n_problems - 1) * pose_stride + POSE_BYTES);  // (nothing is read behind the last record's status)
+  h.in(c->pinfo_pose, pose, (size_t)pose_bytes_read(n_problems, pose_stride, true));
   h.out(c->pinfo_out, info, (size_t)n_problems * sizeof(sc_pose_info_result));
   SC_TRY(h.room());
   SC_TRY(h.send());

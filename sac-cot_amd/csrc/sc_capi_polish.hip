@@ -49,7 +49,7 @@ static int polish_run(sc_ctx* c, const sc_polish_params* pp, float* d_Rt, uint8_
   hipStream_t st = c->stream;
   const uint32_t want = pp->candidates;
   ENSURE(c, c->polish_cand, (size_t)POLISH_MAX_CAND * sizeof(PolishCand) + 64);
-  ENSURE(c, c->polish_tmp, (size_t)want * polish_scratch_bytes(ps.n));
+  ENSURE(c, c->polish_tmp, (size_t)want * chunk_scratch_bytes(ps.n));
   PolishCand* cand = c->polish_cand.as<PolishCand>();
   uint32_t* n_cand = reinterpret_cast<uint32_t*>(cand + POLISH_MAX_CAND);
   SC_TRY(rec(c, 0));

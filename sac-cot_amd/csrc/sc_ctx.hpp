@@ -103,7 +103,7 @@ struct Workspace {
       // in `cnt`, where sc_polish reads them whether or not rounds have run
       peel_planes, peel_claimed, peel_words, peel_label, peel_cnt,
       // sc_polish: allocated by the first polish, never by a frame.  cand: 64 candidate records, then the word that counts them;
-      // tmp: the chunk sums, candidates x polish_scratch_bytes(n)
+      // tmp: the chunk sums, candidates x chunk_scratch_bytes(n)
       polish_cand, polish_tmp,
       // sc_match / sc_register_features: allocated by the first match, never by a frame.  part: the slices' partial lists; words: the
       // "clean" word, the host entries' count pair, the guided host entries' pose, then the column minima; the rest: device copies of
@@ -136,11 +136,11 @@ struct Workspace {
       // of the host entry's arrays
       pinfo_off, pinfo_src, pinfo_tgt, pinfo_pose, pinfo_out,
       // sc_pose_info_frame: allocated by the first such call, never by a frame or by another entry.  tmp: the chunk sums and bit
-      // words, n_poses x pose_info_frame_scratch_bytes(n) — not polish_tmp: a polish may be enqueued behind the call —; the rest:
+      // words, n_poses x chunk_scratch_bytes(n) — not polish_tmp: a polish may be enqueued behind the call —; the rest:
       // device copies of the host entry's arrays
       pinfo_frame_tmp, pinfo_frame_pose, pinfo_frame_sel, pinfo_frame_out,
       // sc_polish_poses: allocated by the first such call, never by a frame or by another entry.  tmp: the chunk sums and bit words,
-      // n_poses x polish_poses_scratch_bytes(n) — not polish_tmp and not pinfo_frame_tmp: either call may be enqueued behind this
+      // n_poses x chunk_scratch_bytes(n) — not polish_tmp and not pinfo_frame_tmp: either call may be enqueued behind this
       // one —; the rest: device copies of the host entry's arrays
       ppose_tmp, ppose_pose, ppose_sel, ppose_out, ppose_mask,
       // sc_assign_poses: allocated by the first such call, never by a frame or by another entry.  The frame form's device entry needs
@@ -148,7 +148,7 @@ struct Workspace {
       // rest: device copies of the host entries' arrays (src / tgt: the batch form's points)
       asg_off, asg_src, asg_tgt, asg_pose, asg_sel, asg_label, asg_d2, asg_out,
       // sc_settle_poses: allocated by the first such call, never by a frame or by another entry.  The frame form's member bits and
-      // chunk sums live in ppose_tmp — sc_polish_poses's buffer, the same layout: the calls are stream-ordered, so one serves both.
+      // chunk sums live in ppose_tmp — sc_polish_poses's buffer, one layout (sc_chunks.hpp): the calls are stream-ordered, so one serves both.
       // off: the batch form's copy of the caller's offsets; the rest: device copies of the host entries' arrays
       stl_off, stl_src, stl_tgt, stl_pose, stl_sel, stl_out, stl_label, stl_d2, stl_rounds;
 };

@@ -15,8 +15,7 @@
 //   result     ten lanes add the chunk sums in chunk order; 36 lanes assemble the matrix (info_entry, sc_info.hpp); the record, staged
 //              in LDS, is stored one dword per lane.
 //
-// A chunk's sums and its bit word live in global scratch as PolishScratch keeps them (sc_polish.hip): 16 doubles a chunk, the sums
-// in [0, 10), the bits in slot 15, a block fence before each barrier behind which other lanes read them.  DESIGN §5.8d has the
+// A chunk's ten sums and its bit word live in global scratch as ChunkScratch keeps them (sc_chunks.hpp).  DESIGN §5.8d has the
 // resources and the measured cost.
 #include <cstddef>
 
@@ -24,6 +23,7 @@
 #include "sc_arith.hpp"
 #include "sc_batch_frame.hpp"
 #include "sc_block.hpp"
+#include "sc_chunks.hpp"
 #include "sc_info.hpp"
 #include "sc_kernels.hpp"
 #include "sc_winner.hpp"
@@ -33,19 +33,8 @@ namespace sc {
 namespace {
 
 constexpr int FT = 1024;                               // threads of a workgroup: 16 waves ballot 16 chunks a round, 1024 chains a round
-constexpr int CHUNK_DOUBLES = 16, BITS_SLOT = 15;      // a chunk's scratch: the sums in [0, 10), its 64 inlier bits in [15]
 constexpr int REC_WORDS = sizeof(PoseInfoRecord) / 4;
-static_assert(INFO_NSUM <= BITS_SLOT, "the sums and the bit word do not overlap");
 static_assert(sizeof(PoseInfoRecord) == sizeof(sc_pose_info_result), "PoseInfoRecord is sc_pose_info_result");
-
-struct FrameScratch {
-  double* base;
-  __device__ __forceinline__ double& sum(int ch, int k) const { return base[(size_t)ch * CHUNK_DOUBLES + k]; }
-  __device__ __forceinline__ uint64_t& bits(int ch) const {
-    return reinterpret_cast<uint64_t*>(base)[(size_t)ch * CHUNK_DOUBLES + BITS_SLOT];
-  }
-  __device__ __forceinline__ void publish() const { __threadfence_block(); }
-};
 
 // the record and nothing else: zero but the status
 __device__ __forceinline__ void record_zero(uint32_t* rec, int status) {
@@ -92,7 +81,7 @@ __global__ __launch_bounds__(FT) void pose_info_frame_kernel(const PoseInfoFrame
     return;
   }
   const int nch = (n + 63) / 64;  // (10 nch fits an int whatever n <= 2^24)
-  const FrameScratch ck{job.scratch + (size_t)blockIdx.x * (size_t)nch * CHUNK_DOUBLES};
+  const auto ck = ChunkScratch<INFO_NSUM>::of_pose(job.scratch, blockIdx.x, n);
   const uint8_t* const sel_mask = static_cast<const uint8_t*>(job.sel);
   const int32_t* const sel_label = static_cast<const int32_t*>(job.sel);
   const int32_t want = (int32_t)((uint32_t)job.label0 + blockIdx.x);
@@ -164,8 +153,6 @@ __global__ __launch_bounds__(FT) void pose_info_frame_kernel(const PoseInfoFrame
 }
 
 }  // namespace
-
-size_t pose_info_frame_scratch_bytes(int n) { return (size_t)((n + 63) / 64) * CHUNK_DOUBLES * sizeof(double); }
 
 void launch_pose_info_frame(const PoseInfoFrameJob& job, hipStream_t st) {
   hipLaunchKernelGGL(pose_info_frame_kernel, dim3(job.n_poses), dim3(FT), 0, st, job);

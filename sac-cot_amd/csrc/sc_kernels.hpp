@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/saccot.h"
+#include "sc_chunks.hpp"
 
 namespace sc {
 
@@ -681,8 +682,7 @@ void launch_polish_select(const uint32_t* cnt, const uint32_t* sel_key, uint32_t
                           PolishCand* cand, uint32_t* n_cand, hipStream_t st);
 // One workgroup per candidate, every iteration inside the launch: mask of (R, t) -> refit in refine_kernel's canonical order -> again,
 // until the refit is declined, returns the same bits, or max_iter refits are done; then the score of the last iterate.
-// scratch: want * polish_scratch_bytes(n).  thr: tau^2, 1 / tau^2 or 1 / tau by score_mode.
-size_t polish_scratch_bytes(int n);
+// scratch: want * chunk_scratch_bytes(n) (sc_chunks.hpp).  thr: tau^2, 1 / tau^2 or 1 / tau by score_mode.
 void launch_polish(const Points& pts, PolishCand* cand, const uint32_t* n_cand, uint32_t want, uint32_t max_iter, float tau2, float thr,
                    int score_mode, double* scratch, hipStream_t st);
 // The candidate with the largest score (ties: the earlier one) -> Rt12, mask; the records and their number -> out_cand / out_n (either
@@ -858,8 +858,39 @@ struct PoseInfoRecord {
   uint32_t inliers;
   uint32_t reserved[4];
 };
-// Problem b owns rows [offset[b], offset[b + 1]) of src / tgt, as in BatchJob; its pose record starts at byte b * pose_stride of
-// `pose` — float Rt[12] at byte 0, int32 status at byte 48: read, never written —, out[b] is the result.  Everything in device memory.
+// THE POSE RECORDS of every entry from here to sc_settle_poses, said once.  `pose` is the caller's array of records, pose_stride bytes
+// apart: float Rt[12] at byte 0 and — where the entry reads it — an int32 status at byte 48; read, never written, and nothing of a
+// record behind that is read (sc_pose_check.hpp has the rule of the stride and the bytes a call reads).  A frame form has n_poses
+// records, pose k at byte k * pose_stride, and reads the status only with `status`; out[k] is pose k's result.  A batch form reads the
+// status always; sc_pose_info_batch has one record per problem (problem b at byte b * pose_stride, out[b]), the others n_poses planes
+// of n_problems records, motion-major: pose k of problem b at byte (k * n_problems + b) * pose_stride, out[k * n_problems + b].
+// Problem b of a batch owns rows [offset[b], offset[b + 1]) of src / tgt (and of label), as in BatchJob.  thr: tau^2, 1 / tau^2 or
+// 1 / tau by score_mode.  scratch: n_poses * chunk_scratch_bytes(pts.n) (sc_chunks.hpp).  Everything in device memory.
+// Both heads hold the entry's OWN word — max_iter of the entries that iterate, the mode of sc_assign_poses — where every job had it,
+// between the score and the poses: the kernels' arguments keep their layout, so the kernels compile to the code they were.
+struct PoseFrameHead {  // what every frame form's job opens with (sc_capi_pose.hpp fills it from the context's pass, but the own word)
+  Points pts;  // the frame's staged planes, in the caller's indexing
+  float tau2, thr;
+  int score_mode;
+  union { uint32_t max_iter, mode; };
+  uint32_t n_poses;
+  const void* pose;
+  uint32_t pose_stride;
+  int status;
+};
+struct PoseBatchHead {  // ... and every motion-major batch form's (from sc_params and the offsets)
+  const float* src; const float* tgt;
+  const uint32_t* offset;
+  uint32_t n_problems, total;
+  int soa, score_mode;
+  float tau2, thr;
+  union { uint32_t max_iter, mode; };
+  uint32_t n_poses;
+  const void* pose;
+  uint32_t pose_stride;
+};
+// sc_pose_info_batch: one record per problem, no score.  Its kernels take the job inside the slot and pairs types below, so it
+// keeps its own fields.
 struct PoseInfoJob {
   const float* src; const float* tgt;
   const uint32_t* offset;
@@ -890,39 +921,22 @@ void launch_pose_info_batch_slots(const PoseInfoSlotJob& job, hipStream_t st);
 void launch_pose_info_batch_pairs(const PoseInfoPairsJob& job, hipStream_t st);
 
 // ---- the same on a scored frame (sc_pose_info_frame; sc_info_frame.hip) -----------------------------------------
-// Pose k's record starts at byte k * pose_stride of `pose` — float Rt[12] at byte 0 and, if `status`, an int32 status at byte 48: read,
-// never written —, out[k] is the result.  sel by sel_mode (SC_POSE_INFO_SEL_*): nullptr, n bytes, or n int32 compared with
-// label0 + k.  scratch: n_poses * pose_info_frame_scratch_bytes(pts.n).  Everything in device memory.
-struct PoseInfoFrameJob {
-  Points pts;  // the frame's staged planes, in the caller's indexing
-  float tau2;
-  uint32_t n_poses;
-  const void* pose;
-  uint32_t pose_stride;
-  int status;
+// sel by sel_mode (SC_POSE_INFO_SEL_*): nullptr, n bytes, or n int32 compared with label0 + k.  (thr, score_mode and the own word
+// are not read.)
+struct PoseInfoFrameJob : PoseFrameHead {
   const void* sel;
   uint32_t sel_mode;
   int32_t label0;
   double* scratch;
   PoseInfoRecord* out;
 };
-size_t pose_info_frame_scratch_bytes(int n);
 // ONE launch, a workgroup of 1024 threads per pose; every record is written (complete in stream order).
 void launch_pose_info_frame(const PoseInfoFrameJob& job, hipStream_t st);
 
 // ---- caller-supplied poses refitted on a scored frame (sc_polish_poses; sc_polish_poses.hip) ----------------------
-// Pose k's record starts at byte k * pose_stride of `pose` — float Rt[12] at byte 0 and, if `status`, an int32 status at byte 48: read,
-// never written —, out[k] is the result, mask bytes [k * n, (k + 1) * n) its mask (mask == nullptr: none).  sel by sel_mode
-// (SC_POLISH_POSES_SEL_*): nullptr, n bytes, or n int32 compared with label0 and label0 + k.  thr: tau^2, 1 / tau^2 or 1 / tau by
-// score_mode.  scratch: n_poses * polish_poses_scratch_bytes(pts.n).  Everything in device memory.
-struct PolishPosesJob {
-  Points pts;  // the frame's staged planes, in the caller's indexing
-  float tau2, thr;
-  int score_mode;
-  uint32_t max_iter, n_poses;
-  const void* pose;
-  uint32_t pose_stride;
-  int status;
+// mask bytes [k * n, (k + 1) * n) are pose k's mask (mask == nullptr: none).  sel by sel_mode (SC_POLISH_POSES_SEL_*): nullptr, n
+// bytes, or n int32 compared with label0 and label0 + k.
+struct PolishPosesJob : PoseFrameHead {
   const void* sel;
   uint32_t sel_mode;
   int32_t label0;
@@ -930,7 +944,6 @@ struct PolishPosesJob {
   PolishBatchRecord* out;
   uint8_t* mask;
 };
-size_t polish_poses_scratch_bytes(int n);
 // ONE launch, a workgroup of 1024 threads per pose; every record (and mask) is written (complete in stream order).
 void launch_polish_poses(const PolishPosesJob& job, hipStream_t st);
 
@@ -942,18 +955,9 @@ struct AssignRecord {
   uint64_t score;
   uint32_t reserved[4];
 };
-// The frame form.  Pose k's record starts at byte k * pose_stride of `pose` — float Rt[12] at byte 0 and, if `status`, an int32 status
-// at byte 48: read, never written.  sel: nullptr or n bytes.  label: n int32; d2: n floats or nullptr.  out: n_poses records, ZERO at
-// launch (the workgroups add their tallies into count and score; workgroup 0 stores the status words).  thr: tau^2, 1 / tau^2 or
-// 1 / tau by score_mode.  Everything in device memory.
-struct AssignFrameJob {
-  Points pts;  // the frame's staged planes, in the caller's indexing
-  float tau2, thr;
-  int score_mode;
-  uint32_t mode, n_poses;
-  const void* pose;
-  uint32_t pose_stride;
-  int status;
+// The frame form.  sel: nullptr or n bytes.  label: n int32; d2: n floats or nullptr.  out: n_poses records, ZERO at launch (the
+// workgroups add their tallies into count and score; workgroup 0 stores the status words).
+struct AssignFrameJob : PoseFrameHead {
   const uint8_t* sel;
   int32_t* label;
   float* d2;
@@ -963,17 +967,8 @@ struct AssignFrameJob {
 inline size_t assign_frame_lds_bytes(uint32_t n_poses) { return (size_t)n_poses * (48 + 8); }
 // ONE launch, a workgroup per tile of ASSIGN_TILE correspondences (sc_assign.hpp); every label (and d2) is written.
 void launch_assign_frame(const AssignFrameJob& job, hipStream_t st);
-// The batch form.  Problem b owns rows [offset[b], offset[b + 1]) of src / tgt and of label, as in BatchJob; pose k of problem b starts
-// at byte (k * n_problems + b) * pose_stride — Rt at byte 0, the status at byte 48 always read —, out[k * n_problems + b] is its record.
-struct AssignBatchJob {
-  const float* src; const float* tgt;
-  const uint32_t* offset;
-  uint32_t n_problems, total;
-  int soa, score_mode;
-  float tau2, thr;
-  uint32_t mode, n_poses;
-  const void* pose;
-  uint32_t pose_stride;
+// The batch form.
+struct AssignBatchJob : PoseBatchHead {
   int32_t* label;
   AssignRecord* out;
 };
@@ -981,17 +976,9 @@ struct AssignBatchJob {
 void launch_assign_batch(const AssignBatchJob& job, hipStream_t st);
 
 // ---- poses relabelled and refitted until stable (sc_settle_poses; sc_settle.hpp, sc_settle_frame.hip, sc_settle_batch.hip) ----
-// The frame form.  The pose records as AssignFrameJob's.  sel: nullptr or n bytes.  label: n int32 (every pass stores it; the last
-// pass's stores are the output); d2: n floats or nullptr; out: n_poses records; rounds: two words or nullptr.  scratch: n_poses *
-// polish_poses_scratch_bytes(pts.n), the layout of PolishPosesJob's.  Everything in device memory.
-struct SettleFrameJob {
-  Points pts;  // the frame's staged planes, in the caller's indexing
-  float tau2, thr;
-  int score_mode;
-  uint32_t max_iter, n_poses;
-  const void* pose;
-  uint32_t pose_stride;
-  int status;
+// The frame form.  sel: nullptr or n bytes.  label: n int32 (every pass stores it; the last pass's stores are the output); d2: n
+// floats or nullptr; out: n_poses records; rounds: two words or nullptr.  scratch: PolishPosesJob's, the same buffer.
+struct SettleFrameJob : PoseFrameHead {
   const uint8_t* sel;
   double* scratch;
   PolishBatchRecord* out;
@@ -1001,17 +988,8 @@ struct SettleFrameJob {
 };
 // ONE launch of ONE workgroup of 1024 threads; every label (and d2), every record and the two words are written.
 void launch_settle_frame(const SettleFrameJob& job, hipStream_t st);
-// The batch form.  Problems, poses and records as AssignBatchJob's (motion-major, the status always read); rounds: two words per
-// problem or nullptr.
-struct SettleBatchJob {
-  const float* src; const float* tgt;
-  const uint32_t* offset;
-  uint32_t n_problems, total;
-  int soa, score_mode;
-  float tau2, thr;
-  uint32_t max_iter, n_poses;
-  const void* pose;
-  uint32_t pose_stride;
+// The batch form.  rounds: two words per problem or nullptr.
+struct SettleBatchJob : PoseBatchHead {
   PolishBatchRecord* out;
   int32_t* label;
   uint32_t* rounds;

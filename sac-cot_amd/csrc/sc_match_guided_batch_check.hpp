@@ -4,6 +4,7 @@
 // runs these functions under the sanitizers on the CPU.
 #pragma once
 #include "sc_match_guided_check.hpp"
+#include "sc_pose_check.hpp"
 
 namespace sc {
 
@@ -17,12 +18,11 @@ inline const char* guide_batch_params_error(const sc_guide_params* gp) {
   return guide_params_error(&plain);
 }
 
-// The pose records: float Rt[12] at byte 0 and, with SC_GUIDE_POSE_STATUS, an int32 status at byte 48 — so a multiple of 4, at
-// least 48, at least 52 with the flag.
+// The pose records (sc_pose_check.hpp), the status read with SC_GUIDE_POSE_STATUS: which part of the stride rule is broken.
 inline const char* guide_pose_stride_error(uint32_t flags, uint32_t pose_stride) {
   if (pose_stride % 4u != 0u) return "pose_stride must be a multiple of 4";
-  if (pose_stride < 48u) return "pose_stride must be at least 48 (float Rt[12])";
-  if ((flags & SC_GUIDE_POSE_STATUS) && pose_stride < 52u) return "pose_stride must be at least 52 with SC_GUIDE_POSE_STATUS (the status at byte 48)";
+  if (pose_stride < POSE_RT_BYTES) return "pose_stride must be at least 48 (float Rt[12])";
+  if (!pose_stride_ok(pose_stride, (flags & SC_GUIDE_POSE_STATUS) != 0)) return "pose_stride must be at least 52 with SC_GUIDE_POSE_STATUS (the status at byte 48)";
   return nullptr;
 }
 

@@ -17,6 +17,7 @@
 
 #include "sc_arith.hpp"
 #include "sc_block.hpp"
+#include "sc_chunks.hpp"
 #include "sc_kernels.hpp"
 #include "sc_refit.hpp"
 #include "sc_winner.hpp"
@@ -26,7 +27,6 @@ namespace sc {
 namespace {
 
 constexpr int POLISH_THREADS = 1024;
-constexpr int POLISH_CHUNK_DOUBLES = 16, POLISH_BITS_SLOT = 15;  // a chunk's scratch: the sums in [0, 9), its 64 inlier bits in [15]
 
 // ---- select ------------------------------------------------------------------------------------------------------------------
 // The 96-bit key of hypothesis g as three words, most significant first: w[0] = score, w[1] = ranking key, w[2] = ~g.
@@ -185,16 +185,7 @@ __global__ __launch_bounds__(POLISH_THREADS) void polish_select_kernel(const uin
 }
 
 // ---- polish ------------------------------------------------------------------------------------------------------------------
-// refit_iterate's chunk storage (sc_refit.hpp): global scratch, so a block fence publishes a lane's stores before the barrier
-struct PolishScratch {
-  double* base;
-  __device__ __forceinline__ double& sum(int ch, int k) const { return base[(size_t)ch * POLISH_CHUNK_DOUBLES + k]; }
-  __device__ __forceinline__ uint64_t& bits(int ch) const {
-    return reinterpret_cast<uint64_t*>(base)[(size_t)ch * POLISH_CHUNK_DOUBLES + POLISH_BITS_SLOT];
-  }
-  __device__ __forceinline__ void publish() const { __threadfence_block(); }
-};
-
+// (refit_iterate's chunk storage: ChunkScratch, sc_chunks.hpp — global scratch, the candidate's block)
 __global__ __launch_bounds__(POLISH_THREADS) void polish_kernel(const float* __restrict__ planes, int n, int ld, PolishCand* __restrict__ cand,
                                                                 const uint32_t* __restrict__ n_cand, uint32_t max_iter, float tau2,
                                                                 float thr, int score_mode, double* __restrict__ scratch_all) {
@@ -204,11 +195,11 @@ __global__ __launch_bounds__(POLISH_THREADS) void polish_kernel(const float* __r
   __shared__ uint64_t s_red[POLISH_THREADS / 64];
   if (blockIdx.x >= *n_cand) return;  // (uniform)
   const uint32_t tid = threadIdx.x;
-  double* scratch = scratch_all + (size_t)blockIdx.x * (size_t)((n + 63) / 64) * POLISH_CHUNK_DOUBLES;
+  const auto ck = ChunkScratch<REFIT_NSUM>::of_pose(scratch_all, blockIdx.x, n);
   PolishCand* me = cand + blockIdx.x;
   if (tid < 12) sRt[tid] = me->Rt[tid];
   __syncthreads();
-  const uint32_t iters = refit_iterate<POLISH_THREADS>(planes, ld, n, tau2, max_iter, PolishScratch{scratch}, sRt, sS, sH, &s_go).iters;
+  const uint32_t iters = refit_iterate<POLISH_THREADS>(planes, ld, n, tau2, max_iter, ck, sRt, sS, sH, &s_go).iters;
   // the last iterate's score over all n, in the frame's score mode (a sum of integers: any order)
   float M[12];
 #pragma unroll
@@ -268,8 +259,6 @@ void launch_polish_select(const uint32_t* cnt, const uint32_t* sel_key, uint32_t
                           PolishCand* cand, uint32_t* n_cand, hipStream_t st) {
   hipLaunchKernelGGL(polish_select_kernel, dim3(1), dim3(POLISH_THREADS), 0, st, cnt, sel_key, T, RtSoA, ld_local, want, cand, n_cand);
 }
-
-size_t polish_scratch_bytes(int n) { return (size_t)((n + 63) / 64) * POLISH_CHUNK_DOUBLES * sizeof(double); }
 
 void launch_polish(const Points& pts, PolishCand* cand, const uint32_t* n_cand, uint32_t want, uint32_t max_iter, float tau2, float thr,
                    int score_mode, double* scratch, hipStream_t st) {

@@ -10,8 +10,7 @@
 //   iteration  refit_iterate (sc_refit.hpp) — the ONE definition of the fp64 chains, the function polish_kernel and polish_batch_kernel
 //              run — with the selection as its participation policy: ANDed into every inlier bit in the ballot loop, so the chains
 //              see the chunks of 64 consecutive ORIGINAL indices with the bits of the others cleared.  A chunk's sums and its bit
-//              word live in global scratch as PolishScratch keeps them (sc_polish.hip): 16 doubles a chunk, the sums in [0, 9), the
-//              bits in slot 15, a block fence before each barrier behind which other lanes read them.
+//              word live in global scratch as ChunkScratch keeps them (sc_chunks.hpp).
 //   result     the last iterate's score over the same correspondences, its mask when one is asked for, and the record — staged in
 //              LDS, stored one dword per lane.
 //
@@ -23,6 +22,7 @@
 #include "sc_arith.hpp"
 #include "sc_batch_frame.hpp"
 #include "sc_block.hpp"
+#include "sc_chunks.hpp"
 #include "sc_kernels.hpp"
 #include "sc_refit.hpp"
 #include "sc_winner.hpp"
@@ -35,18 +35,7 @@ static_assert(sizeof(PolishBatchRecord) == sizeof(sc_polish_batch_result) && siz
 namespace {
 
 constexpr int QT = 1024;                               // threads of a workgroup: 16 waves ballot 16 chunks a round, 1024 chains a round
-constexpr int CHUNK_DOUBLES = 16, BITS_SLOT = 15;      // a chunk's scratch: the sums in [0, 9), its 64 inlier bits in [15]
 constexpr int REC_WORDS = sizeof(PolishBatchRecord) / 4;
-
-// refit_iterate's chunk storage (sc_refit.hpp): global scratch, so a block fence publishes a lane's stores before the barrier
-struct PosesScratch {
-  double* base;
-  __device__ __forceinline__ double& sum(int ch, int k) const { return base[(size_t)ch * CHUNK_DOUBLES + k]; }
-  __device__ __forceinline__ uint64_t& bits(int ch) const {
-    return reinterpret_cast<uint64_t*>(base)[(size_t)ch * CHUNK_DOUBLES + BITS_SLOT];
-  }
-  __device__ __forceinline__ void publish() const { __threadfence_block(); }
-};
 
 // refit_iterate's participation policy: the selection of sc_polish_poses for THIS pose (want = label0 + k, a wrapping 32-bit add)
 struct Selection {
@@ -127,7 +116,7 @@ __global__ __launch_bounds__(QT) void polish_poses_kernel(const PolishPosesJob j
     return;
   }
   const Selection part{job.sel, job.sel_mode, job.label0, (int32_t)((uint32_t)job.label0 + blockIdx.x)};
-  const PosesScratch ck{job.scratch + (size_t)blockIdx.x * (size_t)((n + 63) / 64) * CHUNK_DOUBLES};
+  const auto ck = ChunkScratch<REFIT_NSUM>::of_pose(job.scratch, blockIdx.x, n);  // refit_iterate's chunk storage
 
   // ---- the input pose's score
   const uint32_t score0 = score_walk(M, true, planes, ld, n, part, job.thr, job.score_mode, job.tau2, nullptr, s_red);
@@ -145,8 +134,6 @@ __global__ __launch_bounds__(QT) void polish_poses_kernel(const PolishPosesJob j
 }
 
 }  // namespace
-
-size_t polish_poses_scratch_bytes(int n) { return (size_t)((n + 63) / 64) * CHUNK_DOUBLES * sizeof(double); }
 
 void launch_polish_poses(const PolishPosesJob& job, hipStream_t st) {
   hipLaunchKernelGGL(polish_poses_kernel, dim3(job.n_poses), dim3(QT), 0, st, job);

@@ -1,13 +1,9 @@
 // sc_settle_check.hpp — the host-only rules of sc_settle_poses (include/saccot.h): what is refused of sc_settle_params, of the stride
-// and of n_poses, and how many bytes of the pose array a call reads.  The pose records are sc_assign_poses's, so where a record
-// sits and what of it is read is sc_assign_check.hpp's.  No HIP: sc_capi_settle.hip includes it, and so does
+// and of n_poses, and how many bytes of the pose array a call reads.  The pose records are every pose entry's: where a record sits
+// and what of it is read is sc_pose_check.hpp's.  No HIP: sc_capi_settle.hip includes it, and so does
 // tests/native/settle_check_main.cpp, a program of its own that runs these functions under the sanitizers on the CPU.
 #pragma once
-#include <stddef.h>
-#include <stdint.h>
-
-#include "../../include/saccot.h"
-#include "sc_assign_check.hpp"
+#include "sc_pose_check.hpp"
 
 namespace sc {
 
@@ -26,19 +22,13 @@ inline const char* settle_params_error(const sc_settle_params* sp, uint32_t pose
     return "an unknown flag, or a reserved field that is not 0";
   if (batch) {
     if (n_poses < 1 || n_poses > SC_SETTLE_BATCH_MAX_POSES) return "n_poses must be 1 .. SC_SETTLE_BATCH_MAX_POSES";
-    if (pose_stride < ASSIGN_STATUS_BYTES || pose_stride % 4 != 0) return "pose_stride must be a multiple of 4 and at least 52";
+    if (!pose_stride_ok(pose_stride, true)) return "pose_stride must be a multiple of 4 and at least 52";
   } else {
     if (n_poses < 1 || n_poses > SC_SETTLE_MAX_POSES) return "n_poses must be 1 .. SC_SETTLE_MAX_POSES";
-    const uint32_t least = settle_reads_status(sp, false) ? ASSIGN_STATUS_BYTES : ASSIGN_POSE_BYTES;
-    if (pose_stride < least || pose_stride % 4 != 0)
+    if (!pose_stride_ok(pose_stride, settle_reads_status(sp, false)))
       return "pose_stride must be a multiple of 4 and at least 48 (52 with SC_SETTLE_STATUS)";
   }
   return nullptr;
-}
-
-// Bytes of the pose array a call reads (n_records: n_poses, or n_poses x n_problems): assign_pose_bytes, by this entry's flag.
-inline uint64_t settle_pose_bytes(uint64_t n_records, uint32_t pose_stride, const sc_settle_params* sp, bool batch) {
-  return assign_pose_bytes(n_records, pose_stride, settle_reads_status(sp, batch));
 }
 
 }  // namespace sc

@@ -11,13 +11,13 @@
 //   poses      all K records -> LDS, one lane per record; an invalid pose is staged as NaN (sc_assign.hpp) and keeps its status.
 //   rounds     settle_run (sc_settle.hpp): 16 waves label 16 chunks of 64 correspondences a trip, two chunks a wave side by side;
 //              the refit's (pose, chunk, component) chains are dealt 1024 a trip.  The member bits and chunk sums live in global
-//              scratch as polish_poses_kernel keeps them — pose k's block, 16 doubles a chunk, the sums in [0, 9), the bits in slot
-//              15 — with a block fence before each barrier behind which other lanes read them.
+//              scratch as polish_poses_kernel keeps them, seen pose-major (PoseChunks, sc_chunks.hpp).
 //   result     K records, a dword per lane; the two words of d_rounds.
 //
 // DESIGN §5.6d has the resources and the measured cost.
 #include <cstddef>
 
+#include "sc_chunks.hpp"
 #include "sc_kernels.hpp"
 #include "sc_settle.hpp"
 
@@ -29,18 +29,7 @@ namespace {
 
 constexpr int ST = 1024;                           // threads of the one workgroup
 constexpr int SK = (int)SC_SETTLE_MAX_POSES;       // poses at most
-constexpr int CHUNK_DOUBLES = 16, BITS_SLOT = 15;  // a chunk's scratch, as sc_polish_poses.hip's
 static_assert(sizeof(SettleState<SK>) < 16 * 1024, "the poses and their sums: under 16 KB of LDS");
-
-// settle_run's chunk storage: global scratch, pose-major
-struct FrameChunks {
-  double* base;
-  int nch;
-  __device__ __forceinline__ size_t at(int k, int ch) const { return ((size_t)k * nch + ch) * CHUNK_DOUBLES; }
-  __device__ __forceinline__ double& sum(int k, int ch, int slot) const { return base[at(k, ch) + slot]; }
-  __device__ __forceinline__ uint64_t& bits(int k, int ch) const { return reinterpret_cast<uint64_t*>(base)[at(k, ch) + BITS_SLOT]; }
-  __device__ __forceinline__ void publish() const { __threadfence_block(); }
-};
 
 __global__ __launch_bounds__(ST) void settle_frame_kernel(const SettleFrameJob job) {
   __shared__ SettleState<SK> L;
@@ -49,7 +38,7 @@ __global__ __launch_bounds__(ST) void settle_frame_kernel(const SettleFrameJob j
   if (tid < K) settle_stage_pose(L, tid, static_cast<const char*>(job.pose) + (size_t)tid * job.pose_stride, job.status != 0);
   __syncthreads();
   const SettleIn in{job.pts.planes, job.pts.ld, job.pts.n, K, job.sel, job.tau2, job.thr, job.score_mode, job.max_iter, job.label, job.d2};
-  const Settled so = settle_run<ST>(in, L, FrameChunks{job.scratch, (job.pts.n + 63) / 64});
+  const Settled so = settle_run<ST>(in, L, PoseChunks<REFIT_NSUM>{job.scratch, (job.pts.n + 63) / 64});
   for (int x = tid; x < K * SETTLE_REC_WORDS; x += ST) {
     const int k = x / SETTLE_REC_WORDS, w = x % SETTLE_REC_WORDS;
     reinterpret_cast<uint32_t*>(job.out + k)[w] = settle_record_word(L, k, w, so, job.score_mode, false);

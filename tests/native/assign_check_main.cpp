@@ -25,18 +25,18 @@ static void expect(const char* what, const sc_assign_params& ap, uint32_t stride
   delete p;
 }
 
-// every word a call reads of an accepted pose array lies inside assign_pose_bytes, and the last one ends exactly there
+// every word a call reads of an accepted pose array lies inside pose_bytes_read, and the last one ends exactly there
 static void walk(const char* what, uint32_t n_poses, uint32_t n_problems, uint32_t stride, bool reads_status) {
-  const uint64_t records = (uint64_t)n_poses * n_problems, bytes = sc::assign_pose_bytes(records, stride, reads_status);
+  const uint64_t records = (uint64_t)n_poses * n_problems, bytes = sc::pose_bytes_read(records, stride, reads_status);
   unsigned char* pose = new unsigned char[bytes];
   memset(pose, 0, bytes);
-  const uint32_t read = reads_status ? sc::ASSIGN_STATUS_BYTES : sc::ASSIGN_POSE_BYTES;
+  const uint32_t read = reads_status ? sc::POSE_STATUS_BYTES : sc::POSE_RT_BYTES;
   uint64_t last = 0, seen = 0;
   unsigned sum = 0;
   for (uint32_t k = 0; k < n_poses; k++)
     for (uint32_t b = 0; b < n_problems; b++) {
-      const uint64_t at = sc::assign_pose_offset(k, b, n_problems, stride);
-      if (at != sc::assign_record_index(k, b, n_problems) * stride || sc::assign_record_index(k, b, n_problems) != seen) {
+      const uint64_t at = sc::pose_record_offset(k, b, n_problems, stride);
+      if (at != sc::pose_record_index(k, b, n_problems) * stride || sc::pose_record_index(k, b, n_problems) != seen) {
         printf("FAIL %s: record (%u, %u)\n", what, k, b);
         failures++;
       }
@@ -86,11 +86,11 @@ int main() {
   walk("batch, 64 x 7, stride 80", 64, 7, 80, true);
   walk("batch, 1 x 1, stride 52", 1, 1, 52, true);
   // the offsets are 64-bit: 64 planes of 2^26 problems at the largest stride pass 2^32 bytes by far
-  if (sc::assign_pose_offset(63, (1u << 26) - 1, 1u << 26, 0xFFFFFFFCu) != ((uint64_t)63 * (1u << 26) + (1u << 26) - 1) * 0xFFFFFFFCull) {
+  if (sc::pose_record_offset(63, (1u << 26) - 1, 1u << 26, 0xFFFFFFFCu) != ((uint64_t)63 * (1u << 26) + (1u << 26) - 1) * 0xFFFFFFFCull) {
     printf("FAIL the 64-bit offset\n");
     failures++;
   }
-  if (sc::assign_pose_bytes(0, 48, false) != 0) { printf("FAIL no record, no byte\n"); failures++; }
+  if (sc::pose_bytes_read(0, 48, false) != 0) { printf("FAIL no record, no byte\n"); failures++; }
   printf(failures ? "%d FAILED\n" : "all passed\n", failures);
   return failures ? 1 : 0;
 }

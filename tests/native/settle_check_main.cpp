@@ -25,17 +25,17 @@ static void expect(const char* what, const sc_settle_params& sp, uint32_t stride
   delete p;
 }
 
-// every word a call reads of an accepted pose array lies inside settle_pose_bytes, and the last one ends exactly there
+// every word a call reads of an accepted pose array lies inside pose_bytes_read, and the last one ends exactly there
 static void walk(const char* what, uint32_t n_poses, uint32_t n_problems, uint32_t stride, const sc_settle_params& sp, bool batch) {
-  const uint64_t records = (uint64_t)n_poses * n_problems, bytes = sc::settle_pose_bytes(records, stride, &sp, batch);
+  const uint64_t records = (uint64_t)n_poses * n_problems, bytes = sc::pose_bytes_read(records, stride, sc::settle_reads_status(&sp, batch));
   unsigned char* pose = new unsigned char[bytes];
   memset(pose, 0, bytes);
-  const uint32_t read = sc::settle_reads_status(&sp, batch) ? sc::ASSIGN_STATUS_BYTES : sc::ASSIGN_POSE_BYTES;
+  const uint32_t read = sc::settle_reads_status(&sp, batch) ? sc::POSE_STATUS_BYTES : sc::POSE_RT_BYTES;
   uint64_t last = 0;
   unsigned sum = 0;
   for (uint32_t k = 0; k < n_poses; k++)
     for (uint32_t b = 0; b < n_problems; b++) {
-      const uint64_t at = sc::assign_pose_offset(k, b, n_problems, stride);
+      const uint64_t at = sc::pose_record_offset(k, b, n_problems, stride);
       for (uint32_t x = 0; x < read; x++) sum += pose[at + x];
       if (at + read > last) last = at + read;
     }
@@ -87,7 +87,7 @@ int main() {
   walk("frame, one pose", 1, 1, 48, ok, false);
   walk("batch, 16 x 7, stride 80", 16, 7, 80, ok, true);
   walk("batch, 1 x 1, stride 52", 1, 1, 52, ok, true);
-  if (sc::settle_pose_bytes(0, 48, &ok, false) != 0) { printf("FAIL no record, no byte\n"); failures++; }
+  if (sc::pose_bytes_read(0, 48, sc::settle_reads_status(&ok, false)) != 0) { printf("FAIL no record, no byte\n"); failures++; }
   if (sc::settle_reads_status(&ok, false) || !sc::settle_reads_status(&ok, true) || !sc::settle_reads_status(&flag, false)) {
     printf("FAIL who reads the status\n");
     failures++;
