@@ -1,10 +1,19 @@
 """Host-side mirror of the C ABI in include/saccot.h (ctypes over libsaccot.so).
 
-The reference has no operator/plugin interface to mirror (/root/reference/README.md:1-2 is the whole tree), so the
-names follow SURVEY.md §8(b): `register()` is the drop-in entry point — correspondences in, (R, t, inlier mask)
-out — and the `compat` / `triangles` / `kabsch` / `score` / `mask` methods are the per-stage hooks the parity
-tests drive.  Everything computes on the GPU through libsaccot.so; if the library or a HIP device is missing
-this module raises — there is no CPU fallback (the CPU restatement lives in oracle/ and is test-only).
+The reference has no operator/plugin interface to mirror, so the names follow SURVEY.md §8(b): `register()` is the
+drop-in entry point — correspondences in, (R, t, inlier mask) out — and the `compat` / `triangles` / `kabsch` /
+`score` / `mask` methods are the per-stage hooks the parity tests drive.  Everything computes on the GPU through
+libsaccot.so; if the library or a HIP device is missing this module raises — there is no CPU fallback (the CPU
+restatement lives in oracle/ and is test-only).
+
+A new entry point of the header is added in two places: its prototype in `_PROTOTYPES` (`EXPORTS` and `load_library()`
+follow from the table; tests/test_api_mirror.py holds it against the header) and its method, which reads "prepare, one
+library call, slice" on the helpers below `load_library()`: `_p` / `_vp` (pointers), `_u32c` / `_total` (host offset
+arrays), `_n_points`, `_frame_sel`, `_frame_out` / `_frame_cut` and `_slot_out` / `_slot_cut` (the matchers' outputs),
+`_sized` (size-first structures), `_motion_out` / `_result` (one motion and its dict) and `Registrar._pose_records`.
+A record the library writes is declared once, as a `ctypes.Structure`; its numpy dtype is made from that.  The device
+forms on the benchmark's timed path (register_device[_async], wait, hypothesize_*, finalize_*, shard_*, set_stream)
+spell their one call out and go through no helper.
 """
 from __future__ import annotations
 
@@ -34,35 +43,6 @@ def SC_TIMING_STAGE(k: int) -> int:
 
 
 SC_HIST_WORDS = 256  # u32 words of the pruning-sample histogram (sc_hypothesize_begin_device)
-
-EXPORTS = ["sc_version", "sc_strerror", "sc_default_params", "sc_create", "sc_destroy", "sc_set_stream",
-           "sc_last_error", "sc_set_debug", "sc_debug_last", "sc_register", "sc_register_device", "sc_register_device_async", "sc_wait",
-           "sc_register_batch", "sc_register_batch_device",
-           "sc_peel", "sc_peel_device", "sc_register_instances",
-           "sc_polish_default_params", "sc_polish_device", "sc_polish",
-           "sc_match_default_params", "sc_match_device", "sc_match", "sc_register_features",
-           "sc_guide_default_params", "sc_match_guided_device", "sc_match_guided", "sc_register_guided_features",
-           "sc_match_batch", "sc_match_batch_device", "sc_register_batch_features", "sc_register_batch_features_device",
-           "sc_polish_batch", "sc_polish_batch_device", "sc_polish_batch_slots_device",
-           "sc_register_instances_batch", "sc_register_instances_batch_device", "sc_register_instances_batch_features_device",
-           "sc_pairs_layout", "sc_match_pairs", "sc_match_pairs_device", "sc_register_pairs_features", "sc_register_pairs_features_device",
-           "sc_polish_pairs_slots_device",
-           "sc_match_guided_batch", "sc_match_guided_batch_device", "sc_register_guided_batch_features_device",
-           "sc_match_guided_pairs", "sc_match_guided_pairs_device", "sc_register_guided_pairs_features_device",
-           "sc_match_guided_poses", "sc_match_guided_poses_device", "sc_register_guided_poses_features",
-           "sc_pose_info_batch", "sc_pose_info_batch_device", "sc_pose_info_batch_slots_device", "sc_pose_info_pairs_slots_device",
-           "sc_pose_info_default_params", "sc_pose_info_frame", "sc_pose_info_frame_device",
-           "sc_polish_poses_default_params", "sc_polish_poses", "sc_polish_poses_device",
-           "sc_assign_default_params", "sc_assign_poses_frame", "sc_assign_poses_frame_device", "sc_assign_poses_batch",
-           "sc_assign_poses_batch_device",
-           "sc_settle_default_params", "sc_settle_poses_frame", "sc_settle_poses_frame_device", "sc_settle_poses_batch",
-           "sc_settle_poses_batch_device",
-           "sc_hypothesize_device", "sc_finalize_device",
-           "sc_hypothesize_begin_device", "sc_hypothesize_end_device", "sc_finalize_gathered_device", "sc_finalize_gathered_device_async",
-           "sc_shard_plan_query", "sc_shard_compat_device", "sc_shard_edges_device", "sc_shard_select_device",
-           "sc_shard_score_device", "sc_create_multi", "sc_create_multi_loopback", "sc_destroy_multi",
-           "sc_multi_last_error", "sc_register_multi",
-           "sc_compat_host", "sc_triangles_host", "sc_kabsch_host", "sc_score_host", "sc_mask_host"]
 
 
 class ScParams(C.Structure):
@@ -111,8 +91,7 @@ class ScPolishCand(C.Structure):
                 ("reserved", C.c_uint16)]
 
 
-POLISH_CAND_DTYPE = np.dtype([("Rt", np.float32, 12), ("rank", np.uint32), ("score0", np.uint32), ("score", np.uint32),
-                              ("iters", np.uint16), ("reserved", np.uint16)])  # sc_polish_cand as a numpy record
+POLISH_CAND_DTYPE = np.dtype(ScPolishCand)  # sc_polish_cand as a numpy record
 
 
 class ScBatchResult(C.Structure):
@@ -121,9 +100,7 @@ class ScBatchResult(C.Structure):
                 ("tri_total", C.c_uint64), ("best_rank", C.c_uint32), ("best_count", C.c_uint32)]
 
 
-BATCH_RESULT_DTYPE = np.dtype([("Rt", np.float32, 12), ("status", np.int32), ("n", np.uint32), ("edges", np.uint32),
-                               ("tri_kept", np.uint32), ("tri_total", np.uint64), ("best_rank", np.uint32),
-                               ("best_count", np.uint32)])  # sc_batch_result as a numpy record
+BATCH_RESULT_DTYPE = np.dtype(ScBatchResult)  # sc_batch_result as a numpy record
 SC_BATCH_MAX_N = 512
 
 
@@ -133,8 +110,7 @@ class ScPolishBatchResult(C.Structure):
                 ("stop", C.c_uint16)]
 
 
-POLISH_BATCH_RESULT_DTYPE = np.dtype([("Rt", np.float32, 12), ("status", np.int32), ("score0", np.uint32), ("score", np.uint32),
-                                      ("iters", np.uint16), ("stop", np.uint16)])  # sc_polish_batch_result as a numpy record
+POLISH_BATCH_RESULT_DTYPE = np.dtype(ScPolishBatchResult)  # sc_polish_batch_result as a numpy record
 SC_POLISH_STOP_FIXED, SC_POLISH_STOP_DECLINED, SC_POLISH_STOP_MAX_ITER = 0, 1, 2
 
 
@@ -144,8 +120,7 @@ class ScPoseInfoResult(C.Structure):
                 ("reserved", C.c_uint32 * 4)]
 
 
-POSE_INFO_RESULT_DTYPE = np.dtype([("info", np.float64, 36), ("sse", np.float64), ("status", np.int32), ("inliers", np.uint32),
-                                   ("reserved", np.uint32, 4)])  # sc_pose_info_result as a numpy record
+POSE_INFO_RESULT_DTYPE = np.dtype(ScPoseInfoResult)  # sc_pose_info_result as a numpy record
 
 
 class ScPoseInfoParams(C.Structure):
@@ -183,8 +158,7 @@ class ScAssignResult(C.Structure):
     _fields_ = [("status", C.c_int32), ("count", C.c_uint32), ("score", C.c_uint64), ("reserved", C.c_uint32 * 4)]
 
 
-ASSIGN_RESULT_DTYPE = np.dtype([("status", np.int32), ("count", np.uint32), ("score", np.uint64),
-                                ("reserved", np.uint32, 4)])  # sc_assign_result as a numpy record
+ASSIGN_RESULT_DTYPE = np.dtype(ScAssignResult)  # sc_assign_result as a numpy record
 SC_ASSIGN_MAX_POSES, SC_ASSIGN_BATCH_MAX_POSES = 1024, 64
 SC_ASSIGN_BEST, SC_ASSIGN_FIRST = 0, 1
 SC_ASSIGN_SEL_NONE, SC_ASSIGN_SEL_MASK = 0, 1
@@ -258,11 +232,122 @@ class SacCotError(RuntimeError):
         self.status = status
 
 
+# ---- the prototypes of include/saccot.h and include/saccot_debug.h, once: name -> argtypes, or (argtypes, restype) where the
+# function does not return int.  A new export gets its line here and nowhere else. --------------------------------------------
+_INT, _I64, _U32, _VP = C.c_int, C.c_int64, C.c_uint32, C.c_void_p
+_F32P, _U8P, _I32P, _U32P, _U64P = (C.POINTER(t) for t in (C.c_float, C.c_uint8, C.c_int32, C.c_uint32, C.c_uint64))
+_PP, _SP, _QP, _MP, _GP = (C.POINTER(t) for t in (ScParams, ScStats, ScPolishParams, ScMatchParams, ScGuideParams))
+_IP, _ZP, _AP, _TP = (C.POINTER(t) for t in (ScPoseInfoParams, ScPolishPosesParams, ScAssignParams, ScSettleParams))
+_PROTOTYPES = {
+    "sc_version": [],
+    "sc_strerror": ([_INT], C.c_char_p),
+    "sc_default_params": ([_PP], None),
+    "sc_create": [_INT, C.POINTER(_VP)],
+    "sc_destroy": ([_VP], None),
+    "sc_set_stream": [_VP, _VP],
+    "sc_last_error": ([_VP], C.c_char_p),
+    "sc_set_debug": [_VP, C.POINTER(ScDebug)],
+    "sc_debug_last": [_VP, C.POINTER(ScDebugInfo)],
+    "sc_register": [_VP, _F32P, _F32P, _I64, _PP, _F32P, _F32P, _U8P, _SP],
+    "sc_register_device": [_VP, _VP, _VP, _I64, _PP, _VP, _VP, _SP],
+    "sc_register_device_async": [_VP, _VP, _VP, _I64, _PP, _VP, _VP],
+    "sc_wait": [_VP, _SP],
+    "sc_register_batch": [_VP, _F32P, _F32P, _U32P, _U32, _PP, _VP, _U8P],
+    "sc_register_batch_device": [_VP, _VP, _VP, _U32P, _U32, _PP, _VP, _VP],
+    "sc_peel": [_VP, _F32P, _F32P, _U8P, _SP],
+    "sc_peel_device": [_VP, _VP, _VP, _SP],
+    "sc_register_instances": [_VP, _F32P, _F32P, _I64, _PP, _U32, _U32, _F32P, _U32P, _I32P, _U32P, _SP],
+    "sc_polish_default_params": [_QP],
+    "sc_polish_device": [_VP, _QP, _VP, _VP, _VP, _VP, _SP],
+    "sc_polish": [_VP, _QP, _F32P, _F32P, _U8P, _VP, _U32P, _SP],
+    "sc_match_default_params": [_MP],
+    "sc_match_device": [_VP, _VP, _I64, _VP, _I64, _MP, _VP, _VP, _VP],
+    "sc_match": [_VP, _F32P, _I64, _F32P, _I64, _MP, _I32P, _F32P, _U32P],
+    "sc_register_features": [_VP, _F32P, _F32P, _I64, _F32P, _F32P, _I64, _MP, _PP, _F32P, _F32P, _I32P, _F32P, _U32P, _U8P, _SP],
+    "sc_guide_default_params": [_GP],
+    "sc_match_guided_device": [_VP, _VP, _VP, _I64, _VP, _VP, _I64, _MP, _GP, _VP, _VP, _VP, _VP, _VP],
+    "sc_match_guided": [_VP, _F32P, _F32P, _I64, _F32P, _F32P, _I64, _MP, _GP, _F32P, _I32P, _F32P, _F32P, _U32P],
+    "sc_register_guided_features": [_VP, _F32P, _F32P, _I64, _F32P, _F32P, _I64, _MP, _GP, _F32P, _PP, _F32P, _F32P, _I32P, _F32P,
+                                    _F32P, _U32P, _U8P, _SP],
+    "sc_match_batch": [_VP, _F32P, _U32P, _F32P, _U32P, _U32, _MP, _I32P, _F32P, _U32P],
+    "sc_match_batch_device": [_VP, _VP, _U32P, _VP, _U32P, _U32, _MP, _VP, _VP, _VP],
+    "sc_register_batch_features": [_VP, _F32P, _F32P, _U32P, _F32P, _F32P, _U32P, _U32, _MP, _PP, _VP, _I32P, _F32P, _U32P, _U8P],
+    "sc_register_batch_features_device": [_VP, _VP, _VP, _U32P, _VP, _VP, _U32P, _U32, _MP, _PP, _VP, _VP, _VP, _VP, _VP],
+    "sc_polish_batch": [_VP, _F32P, _F32P, _U32P, _U32, _PP, _QP, _VP, _VP, _U8P],
+    "sc_polish_batch_device": [_VP, _VP, _VP, _U32P, _U32, _PP, _QP, _VP, _VP, _VP],
+    "sc_polish_batch_slots_device": [_VP, _VP, _U32P, _VP, _U32P, _U32, _U32, _PP, _QP, _VP, _VP, _VP, _VP, _VP],
+    "sc_register_instances_batch": [_VP, _F32P, _F32P, _U32P, _U32, _PP, _U32, _U32, _VP, _I32P, _U32P],
+    "sc_register_instances_batch_device": [_VP, _VP, _VP, _U32P, _U32, _PP, _U32, _U32, _VP, _VP, _VP],
+    "sc_register_instances_batch_features_device": [_VP, _VP, _VP, _U32P, _VP, _VP, _U32P, _U32, _MP, _PP, _U32, _U32,
+                                                    _VP, _VP, _VP, _VP, _VP, _VP],
+    "sc_pairs_layout": [_U32P, _U32, _U32P, _U32, _U32, _U32P],
+    "sc_match_pairs": [_VP, _F32P, _U32P, _U32, _U32P, _U32, _MP, _I32P, _F32P, _U32P],
+    "sc_match_pairs_device": [_VP, _VP, _U32P, _U32, _U32P, _U32, _MP, _VP, _VP, _VP],
+    "sc_register_pairs_features": [_VP, _F32P, _F32P, _U32P, _U32, _U32P, _U32, _MP, _PP, _VP, _I32P, _F32P, _U32P, _U8P],
+    "sc_register_pairs_features_device": [_VP, _VP, _VP, _U32P, _U32, _U32P, _U32, _MP, _PP, _VP, _VP, _VP, _VP, _VP],
+    "sc_polish_pairs_slots_device": [_VP, _VP, _U32P, _U32, _U32P, _U32, _U32, _PP, _QP, _VP, _VP, _VP, _VP, _VP],
+    "sc_match_guided_batch": [_VP, _F32P, _F32P, _U32P, _F32P, _F32P, _U32P, _U32, _MP, _GP, _VP, _U32, _I32P, _F32P, _F32P, _U32P],
+    "sc_match_guided_batch_device": [_VP, _VP, _VP, _U32P, _VP, _VP, _U32P, _U32, _MP, _GP, _VP, _U32, _VP, _VP, _VP, _VP],
+    "sc_register_guided_batch_features_device": [_VP, _VP, _VP, _U32P, _VP, _VP, _U32P, _U32, _MP, _GP, _VP, _U32, _PP, _VP, _VP, _VP,
+                                                 _VP, _VP, _VP],
+    "sc_match_guided_pairs": [_VP, _F32P, _F32P, _U32P, _U32, _U32P, _U32, _MP, _GP, _VP, _U32, _I32P, _F32P, _F32P, _U32P],
+    "sc_match_guided_pairs_device": [_VP, _VP, _VP, _U32P, _U32, _U32P, _U32, _MP, _GP, _VP, _U32, _VP, _VP, _VP, _VP],
+    "sc_register_guided_pairs_features_device": [_VP, _VP, _VP, _U32P, _U32, _U32P, _U32, _MP, _GP, _VP, _U32, _PP, _VP, _VP, _VP, _VP,
+                                                 _VP, _VP],
+    "sc_match_guided_poses": [_VP, _F32P, _F32P, _I64, _F32P, _F32P, _I64, _MP, _GP, _VP, _U32, _U32, _I32P, _F32P, _F32P, _I32P, _U32P],
+    "sc_match_guided_poses_device": [_VP, _VP, _VP, _I64, _VP, _VP, _I64, _MP, _GP, _VP, _U32, _U32, _VP, _VP, _VP, _VP, _VP],
+    "sc_register_guided_poses_features": [_VP, _F32P, _F32P, _I64, _F32P, _F32P, _I64, _MP, _GP, _VP, _U32, _U32, _PP, _F32P, _F32P,
+                                          _I32P, _F32P, _F32P, _I32P, _U32P, _U8P, _SP],
+    "sc_pose_info_batch": [_VP, _F32P, _F32P, _U32P, _U32, _PP, _VP, _U32, _VP],
+    "sc_pose_info_batch_device": [_VP, _VP, _VP, _U32P, _U32, _PP, _VP, _U32, _VP],
+    "sc_pose_info_batch_slots_device": [_VP, _VP, _U32P, _VP, _U32P, _U32, _U32, _PP, _VP, _VP, _VP, _U32, _VP],
+    "sc_pose_info_pairs_slots_device": [_VP, _VP, _U32P, _U32, _U32P, _U32, _U32, _PP, _VP, _VP, _VP, _U32, _VP],
+    "sc_pose_info_default_params": [_IP],
+    "sc_pose_info_frame": [_VP, _IP, _VP, _U32, _U32, _VP, _VP],
+    "sc_pose_info_frame_device": [_VP, _IP, _VP, _U32, _U32, _VP, _VP],
+    "sc_polish_poses_default_params": [_ZP],
+    "sc_polish_poses": [_VP, _ZP, _VP, _U32, _U32, _VP, _VP, _VP],
+    "sc_polish_poses_device": [_VP, _ZP, _VP, _U32, _U32, _VP, _VP, _VP],
+    "sc_assign_default_params": [_AP],
+    "sc_assign_poses_frame": [_VP, _AP, _VP, _U32, _U32, _VP, _VP, _VP, _VP],
+    "sc_assign_poses_frame_device": [_VP, _AP, _VP, _U32, _U32, _VP, _VP, _VP, _VP],
+    "sc_assign_poses_batch": [_VP, _F32P, _F32P, _U32P, _U32, _PP, _AP, _VP, _U32, _U32, _VP, _VP],
+    "sc_assign_poses_batch_device": [_VP, _VP, _VP, _U32P, _U32, _PP, _AP, _VP, _U32, _U32, _VP, _VP],
+    "sc_settle_default_params": [_TP],
+    "sc_settle_poses_frame": [_VP, _TP, _VP, _U32, _U32, _VP, _VP, _VP, _VP, _VP],
+    "sc_settle_poses_frame_device": [_VP, _TP, _VP, _U32, _U32, _VP, _VP, _VP, _VP, _VP],
+    "sc_settle_poses_batch": [_VP, _F32P, _F32P, _U32P, _U32, _PP, _TP, _VP, _U32, _U32, _VP, _VP, _VP],
+    "sc_settle_poses_batch_device": [_VP, _VP, _VP, _U32P, _U32, _PP, _TP, _VP, _U32, _U32, _VP, _VP, _VP],
+    "sc_hypothesize_device": [_VP, _VP, _VP, _I64, _PP, _VP, _SP],
+    "sc_finalize_device": [_VP, _VP, _VP, _VP, _SP],
+    "sc_hypothesize_begin_device": [_VP, _VP, _VP, _I64, _PP, _VP, _SP],
+    "sc_hypothesize_end_device": [_VP, _VP, _VP, _SP],
+    "sc_finalize_gathered_device": [_VP, _VP, _INT, _VP, _VP, _SP],
+    "sc_finalize_gathered_device_async": [_VP, _VP, _INT, _VP, _VP],
+    "sc_shard_plan_query": [_PP, _I64, C.POINTER(ScShardPlan)],
+    "sc_shard_compat_device": [_VP, _VP, _VP, _I64, _PP, _VP],
+    "sc_shard_edges_device": [_VP, _VP],
+    "sc_shard_select_device": [_VP, _VP, _VP],
+    "sc_shard_score_device": [_VP, _VP, _VP, _SP],
+    "sc_create_multi": [C.POINTER(_INT), _INT, C.POINTER(_VP)],
+    "sc_create_multi_loopback": [_INT, _INT, C.POINTER(_VP)],
+    "sc_destroy_multi": ([_VP], None),
+    "sc_multi_last_error": ([_VP], C.c_char_p),
+    "sc_register_multi": [_VP, _F32P, _F32P, _I64, _PP, _F32P, _F32P, _U8P, _SP],
+    "sc_compat_host": [_VP, _F32P, _F32P, _I64, _PP, _F32P, _U64P, _U32P],
+    "sc_triangles_host": [_VP, _F32P, _F32P, _I64, _PP, _U32P, _U32P, _U32P, _U64P, _U64P],
+    "sc_kabsch_host": [_VP, _F32P, _F32P, _I64, _PP, _U32P, _U32, _F32P],
+    "sc_score_host": [_VP, _F32P, _F32P, _I64, _PP, _F32P, _U32, _U32P, _U64P],
+    "sc_mask_host": [_VP, _F32P, _F32P, _I64, _PP, _F32P, _U8P],
+}
+EXPORTS = list(_PROTOTYPES)
+
 _LIB = None
 
 
 def load_library() -> C.CDLL:
-    """dlopen libsaccot.so and declare every prototype.  Raises if it was not built (run __graft_entry__.build())."""
+    """dlopen libsaccot.so and give every export of `_PROTOTYPES` its argtypes and restype.  Raises if it was not built (run
+    __graft_entry__.build()).  A new entry point: a line in the table, a method on the class — nothing here."""
     global _LIB
     if _LIB is not None:
         return _LIB
@@ -277,179 +362,170 @@ def load_library() -> C.CDLL:
         raise FileNotFoundError(f"{LIB_PATH} is missing: build it with `python __graft_entry__.py` "
                                 "(hipcc --offload-arch=gfx950); there is no CPU fallback")
     L = C.CDLL(LIB_PATH)
-    vp, f32p, u8p, u32p, u64p = C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
-    pp, sp = C.POINTER(ScParams), C.POINTER(ScStats)
-    L.sc_version.restype = C.c_int
-    L.sc_strerror.argtypes = [C.c_int]; L.sc_strerror.restype = C.c_char_p
-    L.sc_default_params.argtypes = [pp]; L.sc_default_params.restype = None
-    L.sc_create.argtypes = [C.c_int, C.POINTER(vp)]
-    L.sc_destroy.argtypes = [vp]; L.sc_destroy.restype = None
-    L.sc_set_stream.argtypes = [vp, vp]
-    L.sc_last_error.argtypes = [vp]; L.sc_last_error.restype = C.c_char_p
-    L.sc_set_debug.argtypes = [vp, C.POINTER(ScDebug)]
-    L.sc_debug_last.argtypes = [vp, C.POINTER(ScDebugInfo)]
-    L.sc_register.argtypes = [vp, f32p, f32p, C.c_int64, pp, f32p, f32p, u8p, sp]
-    L.sc_register_device.argtypes = [vp, vp, vp, C.c_int64, pp, vp, vp, sp]
-    L.sc_register_device_async.argtypes = [vp, vp, vp, C.c_int64, pp, vp, vp]
-    L.sc_wait.argtypes = [vp, sp]
-    L.sc_register_batch.argtypes = [vp, f32p, f32p, u32p, C.c_uint32, pp, vp, u8p]
-    L.sc_register_batch_device.argtypes = [vp, vp, vp, u32p, C.c_uint32, pp, vp, vp]
-    L.sc_peel.argtypes = [vp, f32p, f32p, u8p, sp]
-    L.sc_peel_device.argtypes = [vp, vp, vp, sp]
-    L.sc_register_instances.argtypes = [vp, f32p, f32p, C.c_int64, pp, C.c_uint32, C.c_uint32, f32p, u32p, C.POINTER(C.c_int32),
-                                        u32p, sp]
-    qp = C.POINTER(ScPolishParams)
-    L.sc_polish_default_params.argtypes = [qp]
-    L.sc_polish_device.argtypes = [vp, qp, vp, vp, vp, vp, sp]
-    L.sc_polish.argtypes = [vp, qp, f32p, f32p, u8p, C.c_void_p, u32p, sp]
-    mp, i32p = C.POINTER(ScMatchParams), C.POINTER(C.c_int32)
-    L.sc_match_default_params.argtypes = [mp]
-    L.sc_match_device.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, mp, vp, vp, vp]
-    L.sc_match.argtypes = [vp, f32p, C.c_int64, f32p, C.c_int64, mp, i32p, f32p, u32p]
-    L.sc_register_features.argtypes = [vp, f32p, f32p, C.c_int64, f32p, f32p, C.c_int64, mp, pp, f32p, f32p, i32p, f32p, u32p, u8p, sp]
-    gp = C.POINTER(ScGuideParams)
-    L.sc_guide_default_params.argtypes = [gp]
-    L.sc_match_guided_device.argtypes = [vp, vp, vp, C.c_int64, vp, vp, C.c_int64, mp, gp, vp, vp, vp, vp, vp]
-    L.sc_match_guided.argtypes = [vp, f32p, f32p, C.c_int64, f32p, f32p, C.c_int64, mp, gp, f32p, i32p, f32p, f32p, u32p]
-    L.sc_register_guided_features.argtypes = [vp, f32p, f32p, C.c_int64, f32p, f32p, C.c_int64, mp, gp, f32p, pp, f32p, f32p, i32p, f32p,
-                                              f32p, u32p, u8p, sp]
-    L.sc_match_guided_poses_device.argtypes = [vp, vp, vp, C.c_int64, vp, vp, C.c_int64, mp, gp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]
-    L.sc_match_guided_poses.argtypes = [vp, f32p, f32p, C.c_int64, f32p, f32p, C.c_int64, mp, gp, vp, C.c_uint32, C.c_uint32, i32p, f32p,
-                                        f32p, i32p, u32p]
-    L.sc_register_guided_poses_features.argtypes = [vp, f32p, f32p, C.c_int64, f32p, f32p, C.c_int64, mp, gp, vp, C.c_uint32, C.c_uint32,
-                                                    pp, f32p, f32p, i32p, f32p, f32p, i32p, u32p, u8p, sp]
-    L.sc_match_batch_device.argtypes = [vp, vp, u32p, vp, u32p, C.c_uint32, mp, vp, vp, vp]
-    L.sc_match_batch.argtypes = [vp, f32p, u32p, f32p, u32p, C.c_uint32, mp, i32p, f32p, u32p]
-    L.sc_register_batch_features_device.argtypes = [vp, vp, vp, u32p, vp, vp, u32p, C.c_uint32, mp, pp, vp, vp, vp, vp, vp]
-    L.sc_register_batch_features.argtypes = [vp, f32p, f32p, u32p, f32p, f32p, u32p, C.c_uint32, mp, pp, vp, i32p, f32p, u32p, u8p]
-    L.sc_polish_batch.argtypes = [vp, f32p, f32p, u32p, C.c_uint32, pp, qp, vp, vp, u8p]
-    L.sc_polish_batch_device.argtypes = [vp, vp, vp, u32p, C.c_uint32, pp, qp, vp, vp, vp]
-    L.sc_polish_batch_slots_device.argtypes = [vp, vp, u32p, vp, u32p, C.c_uint32, C.c_uint32, pp, qp, vp, vp, vp, vp, vp]
-    L.sc_register_instances_batch.argtypes = [vp, f32p, f32p, u32p, C.c_uint32, pp, C.c_uint32, C.c_uint32, vp, i32p, u32p]
-    L.sc_register_instances_batch_device.argtypes = [vp, vp, vp, u32p, C.c_uint32, pp, C.c_uint32, C.c_uint32, vp, vp, vp]
-    L.sc_register_instances_batch_features_device.argtypes = [vp, vp, vp, u32p, vp, vp, u32p, C.c_uint32, mp, pp, C.c_uint32, C.c_uint32,
-                                                              vp, vp, vp, vp, vp, vp]
-    L.sc_pairs_layout.argtypes = [u32p, C.c_uint32, u32p, C.c_uint32, C.c_uint32, u32p]
-    L.sc_match_pairs_device.argtypes = [vp, vp, u32p, C.c_uint32, u32p, C.c_uint32, mp, vp, vp, vp]
-    L.sc_match_pairs.argtypes = [vp, f32p, u32p, C.c_uint32, u32p, C.c_uint32, mp, i32p, f32p, u32p]
-    L.sc_register_pairs_features_device.argtypes = [vp, vp, vp, u32p, C.c_uint32, u32p, C.c_uint32, mp, pp, vp, vp, vp, vp, vp]
-    L.sc_register_pairs_features.argtypes = [vp, f32p, f32p, u32p, C.c_uint32, u32p, C.c_uint32, mp, pp, vp, i32p, f32p, u32p, u8p]
-    L.sc_polish_pairs_slots_device.argtypes = [vp, vp, u32p, C.c_uint32, u32p, C.c_uint32, C.c_uint32, pp, qp, vp, vp, vp, vp, vp]
-    u32 = C.c_uint32
-    L.sc_match_guided_batch_device.argtypes = [vp, vp, vp, u32p, vp, vp, u32p, u32, mp, gp, vp, u32, vp, vp, vp, vp]
-    L.sc_match_guided_batch.argtypes = [vp, f32p, f32p, u32p, f32p, f32p, u32p, u32, mp, gp, vp, u32, i32p, f32p, f32p, u32p]
-    L.sc_register_guided_batch_features_device.argtypes = [vp, vp, vp, u32p, vp, vp, u32p, u32, mp, gp, vp, u32, pp, vp, vp, vp, vp, vp, vp]
-    L.sc_match_guided_pairs_device.argtypes = [vp, vp, vp, u32p, u32, u32p, u32, mp, gp, vp, u32, vp, vp, vp, vp]
-    L.sc_match_guided_pairs.argtypes = [vp, f32p, f32p, u32p, u32, u32p, u32, mp, gp, vp, u32, i32p, f32p, f32p, u32p]
-    L.sc_register_guided_pairs_features_device.argtypes = [vp, vp, vp, u32p, u32, u32p, u32, mp, gp, vp, u32, pp, vp, vp, vp, vp, vp, vp]
-    L.sc_pose_info_batch.argtypes = [vp, f32p, f32p, u32p, C.c_uint32, pp, vp, C.c_uint32, vp]
-    L.sc_pose_info_batch_device.argtypes = [vp, vp, vp, u32p, C.c_uint32, pp, vp, C.c_uint32, vp]
-    L.sc_pose_info_batch_slots_device.argtypes = [vp, vp, u32p, vp, u32p, C.c_uint32, C.c_uint32, pp, vp, vp, vp, C.c_uint32, vp]
-    L.sc_pose_info_pairs_slots_device.argtypes = [vp, vp, u32p, C.c_uint32, u32p, C.c_uint32, C.c_uint32, pp, vp, vp, vp, C.c_uint32, vp]
-    ip = C.POINTER(ScPoseInfoParams)
-    L.sc_pose_info_default_params.argtypes = [ip]
-    L.sc_pose_info_frame.argtypes = [vp, ip, vp, C.c_uint32, C.c_uint32, vp, vp]
-    L.sc_pose_info_frame_device.argtypes = [vp, ip, vp, C.c_uint32, C.c_uint32, vp, vp]
-    zp = C.POINTER(ScPolishPosesParams)
-    L.sc_polish_poses_default_params.argtypes = [zp]
-    L.sc_polish_poses.argtypes = [vp, zp, vp, C.c_uint32, C.c_uint32, vp, vp, vp]
-    L.sc_polish_poses_device.argtypes = [vp, zp, vp, C.c_uint32, C.c_uint32, vp, vp, vp]
-    ap = C.POINTER(ScAssignParams)
-    L.sc_assign_default_params.argtypes = [ap]
-    L.sc_assign_poses_frame.argtypes = [vp, ap, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
-    L.sc_assign_poses_frame_device.argtypes = [vp, ap, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
-    L.sc_assign_poses_batch.argtypes = [vp, f32p, f32p, u32p, C.c_uint32, pp, ap, vp, C.c_uint32, C.c_uint32, vp, vp]
-    L.sc_assign_poses_batch_device.argtypes = [vp, vp, vp, u32p, C.c_uint32, pp, ap, vp, C.c_uint32, C.c_uint32, vp, vp]
-    tp = C.POINTER(ScSettleParams)
-    L.sc_settle_default_params.argtypes = [tp]
-    L.sc_settle_poses_frame.argtypes = [vp, tp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]
-    L.sc_settle_poses_frame_device.argtypes = [vp, tp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]
-    L.sc_settle_poses_batch.argtypes = [vp, f32p, f32p, u32p, C.c_uint32, pp, tp, vp, C.c_uint32, C.c_uint32, vp, vp, vp]
-    L.sc_settle_poses_batch_device.argtypes = [vp, vp, vp, u32p, C.c_uint32, pp, tp, vp, C.c_uint32, C.c_uint32, vp, vp, vp]
-    L.sc_hypothesize_device.argtypes = [vp, vp, vp, C.c_int64, pp, vp, sp]
-    L.sc_finalize_device.argtypes = [vp, vp, vp, vp, sp]
-    L.sc_hypothesize_begin_device.argtypes = [vp, vp, vp, C.c_int64, pp, vp, sp]
-    L.sc_hypothesize_end_device.argtypes = [vp, vp, vp, sp]
-    L.sc_finalize_gathered_device.argtypes = [vp, vp, C.c_int, vp, vp, sp]
-    L.sc_finalize_gathered_device_async.argtypes = [vp, vp, C.c_int, vp, vp]
-    L.sc_shard_plan_query.argtypes = [pp, C.c_int64, C.POINTER(ScShardPlan)]
-    L.sc_shard_compat_device.argtypes = [vp, vp, vp, C.c_int64, pp, vp]
-    L.sc_shard_edges_device.argtypes = [vp, vp]
-    L.sc_shard_select_device.argtypes = [vp, vp, vp]
-    L.sc_shard_score_device.argtypes = [vp, vp, vp, sp]
-    L.sc_create_multi.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]
-    L.sc_create_multi_loopback.argtypes = [C.c_int, C.c_int, C.POINTER(vp)]
-    L.sc_destroy_multi.argtypes = [vp]; L.sc_destroy_multi.restype = None
-    L.sc_multi_last_error.argtypes = [vp]; L.sc_multi_last_error.restype = C.c_char_p
-    L.sc_register_multi.argtypes = [vp, f32p, f32p, C.c_int64, pp, f32p, f32p, u8p, sp]
-    L.sc_compat_host.argtypes = [vp, f32p, f32p, C.c_int64, pp, f32p, u64p, u32p]
-    L.sc_triangles_host.argtypes = [vp, f32p, f32p, C.c_int64, pp, u32p, u32p, u32p, u64p, u64p]
-    L.sc_kabsch_host.argtypes = [vp, f32p, f32p, C.c_int64, pp, u32p, C.c_uint32, f32p]
-    L.sc_score_host.argtypes = [vp, f32p, f32p, C.c_int64, pp, f32p, C.c_uint32, u32p, u64p]
-    L.sc_mask_host.argtypes = [vp, f32p, f32p, C.c_int64, pp, f32p, u8p]
+    for name, proto in _PROTOTYPES.items():
+        fn = getattr(L, name)
+        fn.argtypes, fn.restype = proto if isinstance(proto, tuple) else (proto, _INT)
     _LIB = L
     return L
+
+
+def _sized(cls, *fields, **named):
+    """A structure of the ABI whose first field is its own size."""
+    return cls(C.sizeof(cls), *fields, **named)
 
 
 def make_params(sigma=0.1, t_cmp=0.9, tau=0.1, min_len=0.1, max_triangles=50000, rank_mode=SC_RANK_WEIGHT,
                 layout=SC_AOS, shard_rank=0, shard_world=1, shard_block=1024, flags=0, max_workspace=0,
                 score_mode=0, shard_cand_level=0) -> ScParams:
-    return ScParams(C.sizeof(ScParams), sigma, t_cmp, tau, min_len, max_triangles, rank_mode, layout, shard_rank,
-                    shard_world, shard_block, flags, max_workspace, score_mode, shard_cand_level)
+    return _sized(ScParams, sigma, t_cmp, tau, min_len, max_triangles, rank_mode, layout, shard_rank, shard_world, shard_block,
+                  flags, max_workspace, score_mode, shard_cand_level)
 
 
 def make_match_params(dim: int, knn: int = 1, mutual: bool = False, ratio: float = 0.0, flags: int = 0) -> ScMatchParams:
     """sc_match_params for descriptors of length `dim`: knn 1 .. 4; mutual / ratio (in (0, 1), 0 = off) with knn == 1 only."""
-    return ScMatchParams(C.sizeof(ScMatchParams), dim, knn, flags | (SC_MATCH_MUTUAL if mutual else 0), ratio)
+    return _sized(ScMatchParams, dim, knn, flags | (SC_MATCH_MUTUAL if mutual else 0), ratio)
 
 
 def make_guide_params(gate: float, layout: int = SC_AOS, flags: int = 0) -> ScGuideParams:
     """sc_guide_params: the gate radius (finite, > 0) and the layout of the keypoint arrays of sc_match_guided; flags: 0, or — the
     batch and pairs entries only — SC_GUIDE_POSE_STATUS."""
-    return ScGuideParams(C.sizeof(ScGuideParams), layout, gate, flags)
+    return _sized(ScGuideParams, layout, gate, flags)
 
 
 def make_polish_params(candidates: int = 8, max_iter: int = 16, flags: int = 0) -> ScPolishParams:
     """sc_polish_params: the best `candidates` hypotheses of the frame (1 .. 64), at most `max_iter` refits each (1 .. 64)."""
-    return ScPolishParams(C.sizeof(ScPolishParams), candidates, max_iter, flags)
+    return _sized(ScPolishParams, candidates, max_iter, flags)
 
 
 def make_pose_info_params(sel_mode: int = SC_POSE_INFO_SEL_NONE, label0: int = 0, flags: int = 0) -> ScPoseInfoParams:
     """sc_pose_info_params: sel_mode SC_POSE_INFO_SEL_*, label0 (SEL_LABEL only), flags SC_POSE_INFO_STATUS or 0."""
-    return ScPoseInfoParams(C.sizeof(ScPoseInfoParams), sel_mode, label0, flags)
+    return _sized(ScPoseInfoParams, sel_mode, label0, flags)
 
 
 def make_polish_poses_params(max_iter: int = 16, sel_mode: int = SC_POLISH_POSES_SEL_NONE, label0: int = 0, flags: int = 0) -> ScPolishPosesParams:
     """sc_polish_poses_params: max_iter 1 .. 64, sel_mode SC_POLISH_POSES_SEL_*, label0 (SEL_LABEL / SEL_ALIVE only), flags
     SC_POLISH_POSES_STATUS or 0."""
-    return ScPolishPosesParams(C.sizeof(ScPolishPosesParams), max_iter, sel_mode, label0, flags)
+    return _sized(ScPolishPosesParams, max_iter, sel_mode, label0, flags)
 
 
 def make_assign_params(mode: int = SC_ASSIGN_BEST, sel_mode: int = SC_ASSIGN_SEL_NONE, flags: int = 0) -> ScAssignParams:
     """sc_assign_params: mode SC_ASSIGN_BEST / _FIRST, sel_mode SC_ASSIGN_SEL_*, flags SC_ASSIGN_STATUS or 0."""
-    return ScAssignParams(C.sizeof(ScAssignParams), mode, sel_mode, flags)
+    return _sized(ScAssignParams, mode, sel_mode, flags)
 
 
 def make_settle_params(max_iter: int = 16, sel_mode: int = SC_ASSIGN_SEL_NONE, flags: int = 0) -> ScSettleParams:
     """sc_settle_params: max_iter 1 .. 64 counted rounds, sel_mode SC_ASSIGN_SEL_*, flags SC_SETTLE_STATUS or 0."""
-    return ScSettleParams(C.sizeof(ScSettleParams), max_iter, sel_mode, flags)
+    return _sized(ScSettleParams, max_iter, sel_mode, flags)
 
 
 def shard_plan(params: ScParams, n: int) -> ScShardPlan:
     """sc_shard_plan_query: sizes of d_bits_all / the candidate blobs for `params` (shard_world) and n correspondences."""
-    plan = ScShardPlan(size=C.sizeof(ScShardPlan))
+    plan = _sized(ScShardPlan)
     rc = load_library().sc_shard_plan_query(C.byref(params), n, C.byref(plan))
     if rc != SC_OK:
         raise SacCotError(rc, "sc_shard_plan_query")
     return plan
 
 
-def _p(a, t):
-    return None if a is None else a.ctypes.data_as(C.POINTER(t))
+# ---- marshalling, each step said once ------------------------------------------------------------------------------------
+_POINTER_OF = {np.dtype(d): p for d, p in ((np.float32, _F32P), (np.uint8, _U8P), (np.int32, _I32P), (np.uint32, _U32P),
+                                            (np.uint64, _U64P))}
+
+
+def _p(a):
+    """An array as the typed pointer its dtype calls for (a dtype the ABI has no pointer for is a KeyError); None stays NULL."""
+    return None if a is None else a.ctypes.data_as(_POINTER_OF[a.dtype])
+
+
+def _vp(a):
+    """An array of records, or one a `void*` parameter takes, as that; None stays NULL."""
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 def _f32c(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def _u32c(off):
+    """A host offset array (B + 1,) as the entries take it -> (contiguous uint32 array, B); B = 0 for an empty one."""
+    off = np.ascontiguousarray(off, dtype=np.uint32)
+    return off, max(len(off) - 1, 0)
+
+
+def _total(off) -> int:
+    """The rows an offset array spans: its last entry, 0 for an empty one."""
+    return int(off[-1]) if len(off) else 0
+
+
+def _n_points(a, layout) -> int:
+    """The points of an (n, 3) array, or of a (3, n) one with SC_SOA."""
+    return a.shape[0] if layout == SC_AOS else a.shape[1]
+
+
+def _frame_sel(who, sel, dtype, n):
+    """The selection of a frame entry: None, or n entries of the dtype the entry's sel_mode reads (the caller names it)."""
+    if sel is None:
+        return None
+    sel = np.ascontiguousarray(sel, dtype=dtype)
+    if sel.size != n:
+        raise ValueError(who + ": sel holds one entry per correspondence of the frame")
+    return sel
+
+
+def _frame_out(ns, knn, g2=False, label=False, mask=False):
+    """Room for what a frame matcher writes, ns * knn entries and never fewer than 1 -> (arrays by their result key — corr, d2, then
+    g2 / label / mask where asked for —, the count word)."""
+    cap = max(ns * max(int(knn), 1), 1)
+    out = dict(corr=np.zeros((cap, 2), np.int32), d2=np.zeros(cap, np.float32))
+    for key, wanted, dtype in (("g2", g2, np.float32), ("label", label, np.int32), ("mask", mask, np.uint8)):
+        if wanted:
+            out[key] = np.zeros(cap, dtype)
+    return out, C.c_uint32(0)
+
+
+def _frame_cut(out, count) -> dict:
+    """_frame_out's arrays cut to the entries the call counted, each a copy, behind n."""
+    k = int(count.value)
+    return dict(n=k, **{key: a[:k].copy() for key, a in out.items()})
+
+
+def _slot_out(slots, nb, g2=False, registered=False) -> dict:
+    """Room for what a batch or pairs matcher writes: corr, d2 and (g2, else None) of `slots` entries, count of nb problems; with a
+    registration behind the match also res (nb records) and mask (slots bytes).  Never fewer than 1 of either."""
+    s, b = max(slots, 1), max(nb, 1)
+    out = dict(corr=np.zeros((s, 2), np.int32), d2=np.zeros(s, np.float32), g2=np.zeros(s, np.float32) if g2 else None,
+               count=np.zeros((b, 2), np.uint32))
+    if registered:
+        out.update(res=np.zeros(b, BATCH_RESULT_DTYPE), mask=np.zeros(s, np.uint8))
+    return out
+
+
+def _slot_cut(out, slots, nb, *keys) -> tuple:
+    """_slot_out's arrays named by `keys`, in that order, as views: count and res cut to nb problems, the others to `slots`
+    entries; None stays None."""
+    return tuple(None if out[k] is None else out[k][:nb if k in ("count", "res") else slots] for k in keys)
+
+
+def _motion_out():
+    """Room for the one motion an entry returns and for its statistics -> (R (9,), t (3,), sc_stats)."""
+    return np.zeros(9, np.float32), np.zeros(3, np.float32), _sized(ScStats)
+
+
+def _result(rc, R, t, st, **more) -> dict:
+    """dict(status, R (3, 3), t, ..., stats) of the entries that return one motion; `more` (mask, n, corr, ...) goes in between."""
+    return dict(status=rc, R=R.reshape(3, 3), t=t, **more, stats=st.as_dict())
+
+
+def _register(self, fn, src, tgt, params, kw) -> dict:
+    """Registrar.register and MultiRegistrar.register: (n, 3) src / tgt through `fn` of self's handle -> _result with the mask.  The
+    frame's n is stored before the call."""
+    p = params or make_params(**kw)
+    src, tgt = _f32c(src), _f32c(tgt)
+    n = _n_points(src, p.layout)
+    (R, t, st), mask = _motion_out(), np.zeros(n, np.uint8)
+    self._frame_n = n
+    rc = self._check(fn(self._h, _p(src), _p(tgt), n, C.byref(p), _p(R), _p(t), _p(mask), C.byref(st)), allow=(SC_ENOHYP,))
+    return _result(rc, R, t, st, mask=mask)
 
 
 def _pack_problems(problems, layout):
@@ -517,7 +593,7 @@ class Registrar:
             self._check(self._lib.sc_set_debug(self._h, None))
             return
         cls = ScDebugLab if "filter_variant" in knobs else ScDebug   # (lab builds have a field more; the product rejects the lab struct's size)
-        d = cls(size=C.sizeof(cls), compact_self_max=-1, scan_self_max=-1)
+        d = _sized(cls, compact_self_max=-1, scan_self_max=-1)
         names = dict(cls._fields_)
         for k, v in knobs.items():
             if k in cls._ALIASES:
@@ -533,23 +609,14 @@ class Registrar:
         """sc_debug_last: which stage C2 kernel the last call ran (0 plain fp32, 1 linear filter + exact pass, 2 Gram
         filter + exact pass), what the filter handed to the exact pass, how the call was enqueued (fast_path) and the result
         of the matrix-pipe probe (gram_guard).  Synchronises the context's stream."""
-        d = ScDebugInfo(size=C.sizeof(ScDebugInfo))
+        d = _sized(ScDebugInfo)
         self._check(self._lib.sc_debug_last(self._h, C.byref(d)))
-        return {k: getattr(d, k) for k, _ in ScDebugInfo._fields_ if k not in ("size", "reserved", "reserved2")}
+        return {k: getattr(d, k) for k, _ in ScDebugInfo._fields_ if k != "size"}
 
     # ---- drop-in entry point ----------------------------------------------------------------------------
     def register(self, src, tgt, params: ScParams | None = None, **kw):
         """(n,3) src/tgt correspondences -> dict(status, R (3,3), t (3,), mask (n,) uint8, stats)."""
-        p = params or make_params(**kw)
-        src, tgt = _f32c(src), _f32c(tgt)
-        n = src.shape[0] if p.layout == SC_AOS else src.shape[1]
-        R = np.zeros(9, np.float32); t = np.zeros(3, np.float32); mask = np.zeros(n, np.uint8)
-        st = ScStats(C.sizeof(ScStats))
-        self._frame_n = n
-        rc = self._check(self._lib.sc_register(self._h, _p(src, C.c_float), _p(tgt, C.c_float), n, C.byref(p),
-                                               _p(R, C.c_float), _p(t, C.c_float), _p(mask, C.c_uint8), C.byref(st)),
-                         allow=(SC_ENOHYP,))
-        return dict(status=rc, R=R.reshape(3, 3), t=t, mask=mask, stats=st.as_dict())
+        return _register(self, self._lib.sc_register, src, tgt, params, kw)
 
     # ---- device-resident forms (pointers are ints: torch .data_ptr()) -------------------------------------
     def register_device(self, d_src: int, d_tgt: int, n: int, params: ScParams, d_Rt: int, d_mask: int):
@@ -576,13 +643,11 @@ class Registrar:
         """sc_register_batch on packed arrays: src / tgt (total, 3) — or (3, total) with SC_SOA —, offset (B + 1,) uint32 ->
         (records (B,) of BATCH_RESULT_DTYPE, mask (total,) uint8).  A problem's status is a field of its record."""
         src, tgt = _f32c(src), _f32c(tgt)
-        offset = np.ascontiguousarray(offset, dtype=np.uint32)
-        nb = max(len(offset) - 1, 0)
-        total = int(offset[-1]) if len(offset) else 0
+        offset, nb = _u32c(offset)
+        total = _total(offset)
         res = np.zeros(max(nb, 1), BATCH_RESULT_DTYPE); mask = np.zeros(max(total, 1), np.uint8)
         self._frame_n = 0
-        self._check(self._lib.sc_register_batch(self._h, _p(src, C.c_float), _p(tgt, C.c_float), _p(offset, C.c_uint32), nb,
-                                                C.byref(params), res.ctypes.data_as(C.c_void_p), _p(mask, C.c_uint8)))
+        self._check(self._lib.sc_register_batch(self._h, _p(src), _p(tgt), _p(offset), nb, C.byref(params), _vp(res), _p(mask)))
         return res[:nb], mask[:total]
 
     def register_batch(self, problems, params: ScParams | None = None, **kw):
@@ -601,26 +666,22 @@ class Registrar:
     def register_batch_device(self, d_src: int, d_tgt: int, offset, params: ScParams, d_res: int, d_mask: int):
         """sc_register_batch_device: points, records (80 bytes each) and mask in HBM, offset a HOST array (B + 1,) uint32; enqueues
         on the context's stream and returns without waiting."""
-        offset = np.ascontiguousarray(offset, dtype=np.uint32)
+        offset, nb = _u32c(offset)
         self._frame_n = 0
-        self._check(self._lib.sc_register_batch_device(self._h, d_src, d_tgt, _p(offset, C.c_uint32), max(len(offset) - 1, 0),
-                                                       C.byref(params), d_res, d_mask))
+        self._check(self._lib.sc_register_batch_device(self._h, d_src, d_tgt, _p(offset), nb, C.byref(params), d_res, d_mask))
 
     # ---- further rigid motions from the frame the last register* call left (include/saccot.h, sc_peel) ------
     def peel(self):
         """sc_peel: the next round on the frame in this context -> dict(status, R, t, mask, stats) like register()'s; SC_ENOHYP
         (no hypothesis explains an unclaimed correspondence) is a status, not an exception.  The frame's n sizes the mask."""
-        R = np.zeros(9, np.float32); t = np.zeros(3, np.float32)
         n = self._frame_n
-        mask = np.zeros(max(n, 1), np.uint8)
-        st = ScStats(C.sizeof(ScStats))
-        rc = self._check(self._lib.sc_peel(self._h, _p(R, C.c_float), _p(t, C.c_float), _p(mask, C.c_uint8), C.byref(st)),
-                         allow=(SC_ENOHYP,))
-        return dict(status=rc, R=R.reshape(3, 3), t=t, mask=mask[:n], stats=st.as_dict())
+        (R, t, st), mask = _motion_out(), np.zeros(max(n, 1), np.uint8)
+        rc = self._check(self._lib.sc_peel(self._h, _p(R), _p(t), _p(mask), C.byref(st)), allow=(SC_ENOHYP,))
+        return _result(rc, R, t, st, mask=mask[:n])
 
     def peel_device(self, d_Rt: int, d_mask: int):
         """sc_peel_device: the same with the outputs in HBM (d_Rt: 12 floats, d_mask: n bytes) -> (status, stats)."""
-        st = ScStats(C.sizeof(ScStats))
+        st = _sized(ScStats)
         rc = self._check(self._lib.sc_peel_device(self._h, d_Rt, d_mask, C.byref(st)), allow=(SC_ENOHYP,))
         return rc, st.as_dict()
 
@@ -630,19 +691,17 @@ class Registrar:
         dict(status, R, t, mask, n_cand, cand (candidates,) records of POLISH_CAND_DTYPE — those past n_cand zeroed —, stats).  stats["best_count"] is the polished
         score and may be below the frame's.  kw: candidates, max_iter (make_polish_params)."""
         q = pparams or make_polish_params(**kw)
-        R = np.zeros(9, np.float32); t = np.zeros(3, np.float32)
         n = self._frame_n
-        mask = np.zeros(max(n, 1), np.uint8)
+        (R, t, st), mask = _motion_out(), np.zeros(max(n, 1), np.uint8)
         cand = np.zeros(max(int(q.candidates), 1), POLISH_CAND_DTYPE); k = C.c_uint32(0)
-        st = ScStats(C.sizeof(ScStats))
-        rc = self._check(self._lib.sc_polish(self._h, C.byref(q), _p(R, C.c_float), _p(t, C.c_float), _p(mask, C.c_uint8),
-                                             cand.ctypes.data_as(C.c_void_p), C.byref(k), C.byref(st)), allow=(SC_ENOHYP,))
-        return dict(status=rc, R=R.reshape(3, 3), t=t, mask=mask[:n], n_cand=int(k.value), cand=cand, stats=st.as_dict())
+        rc = self._check(self._lib.sc_polish(self._h, C.byref(q), _p(R), _p(t), _p(mask), _vp(cand), C.byref(k), C.byref(st)),
+                         allow=(SC_ENOHYP,))
+        return _result(rc, R, t, st, mask=mask[:n], n_cand=int(k.value), cand=cand)
 
     def polish_device(self, pparams: ScPolishParams, d_Rt: int, d_mask: int, d_cand: int = 0, d_ncand: int = 0):
         """sc_polish_device: the same with the outputs in HBM (d_Rt: 12 floats, d_mask: n bytes, d_cand: `candidates` records of
         64 bytes or 0, d_ncand: one uint32 or 0) -> (status, stats)."""
-        st = ScStats(C.sizeof(ScStats))
+        st = _sized(ScStats)
         rc = self._check(self._lib.sc_polish_device(self._h, C.byref(pparams), d_Rt, d_mask, d_cand or None, d_ncand or None,
                                                     C.byref(st)), allow=(SC_ENOHYP,))
         return rc, st.as_dict()
@@ -652,13 +711,12 @@ class Registrar:
         the motion that claimed each correspondence, -1 for none; stats: the frame's)."""
         p = params or make_params(**kw)
         src, tgt = _f32c(src), _f32c(tgt)
-        n = src.shape[0] if p.layout == SC_AOS else src.shape[1]
+        n = _n_points(src, p.layout)
         Rt = np.zeros((max_instances, 12), np.float32); score = np.zeros(max_instances, np.uint32)
         label = np.full(n, -1, np.int32); found = C.c_uint32(0)
-        st = ScStats(C.sizeof(ScStats))
-        rc = self._check(self._lib.sc_register_instances(self._h, _p(src, C.c_float), _p(tgt, C.c_float), n, C.byref(p),
-                                                         max_instances, min_score, _p(Rt, C.c_float), _p(score, C.c_uint32),
-                                                         _p(label, C.c_int32), C.byref(found), C.byref(st)), allow=(SC_ENOHYP,))
+        st = _sized(ScStats)
+        rc = self._check(self._lib.sc_register_instances(self._h, _p(src), _p(tgt), n, C.byref(p), max_instances, min_score, _p(Rt),
+                                                         _p(score), _p(label), C.byref(found), C.byref(st)), allow=(SC_ENOHYP,))
         self._frame_n = n
         k = int(found.value)
         return dict(status=rc, Rt=Rt[:k].copy(), score=score[:k].copy(), label=label, stats=st.as_dict())
@@ -671,12 +729,10 @@ class Registrar:
         if fsrc.ndim != 2 or ftgt.ndim != 2 or fsrc.shape[1] != ftgt.shape[1]:
             raise ValueError("match: fsrc (ns, D) and ftgt (nt, D) with one D")
         m = mparams or make_match_params(fsrc.shape[1], **kw)
-        cap = max(fsrc.shape[0] * max(int(m.knn), 1), 1)
-        corr = np.zeros((cap, 2), np.int32); d2 = np.zeros(cap, np.float32); n = C.c_uint32(0)
-        self._check(self._lib.sc_match(self._h, _p(fsrc, C.c_float), fsrc.shape[0], _p(ftgt, C.c_float), ftgt.shape[0], C.byref(m),
-                                       _p(corr, C.c_int32), _p(d2, C.c_float), C.byref(n)))
-        k = int(n.value)
-        return dict(n=k, corr=corr[:k].copy(), d2=d2[:k].copy())
+        out, n = _frame_out(fsrc.shape[0], m.knn)
+        self._check(self._lib.sc_match(self._h, _p(fsrc), fsrc.shape[0], _p(ftgt), ftgt.shape[0], C.byref(m), _p(out["corr"]),
+                                       _p(out["d2"]), C.byref(n)))
+        return _frame_cut(out, n)
 
     def match_device(self, d_fsrc: int, ns: int, d_ftgt: int, nt: int, mparams: ScMatchParams, d_corr: int, d_d2: int, d_count: int):
         """sc_match_device: everything in HBM (d_corr: ns * knn x 2 int32, d_d2: ns * knn float32, d_count: 2 x uint32 — the
@@ -692,21 +748,20 @@ class Registrar:
         src_pts, tgt_pts, fsrc, ftgt = _f32c(src_pts), _f32c(tgt_pts), _f32c(fsrc), _f32c(ftgt)
         m = mparams or make_match_params(fsrc.shape[1], knn, mutual, ratio)
         ns, nt = fsrc.shape[0], ftgt.shape[0]
-        if (src_pts.shape[0] if p.layout == SC_AOS else src_pts.shape[1]) != ns or \
-                (tgt_pts.shape[0] if p.layout == SC_AOS else tgt_pts.shape[1]) != nt or fsrc.shape[1] != ftgt.shape[1]:
+        if _n_points(src_pts, p.layout) != ns or _n_points(tgt_pts, p.layout) != nt or fsrc.shape[1] != ftgt.shape[1]:
             raise ValueError("register_features: one descriptor row per point, one D")
-        cap = max(ns * max(int(m.knn), 1), 1)
-        corr = np.zeros((cap, 2), np.int32); d2 = np.zeros(cap, np.float32); n = C.c_uint32(0)
-        R = np.zeros(9, np.float32); t = np.zeros(3, np.float32); mask = np.zeros(cap, np.uint8)
-        st = ScStats(C.sizeof(ScStats))
-        rc = self._check(self._lib.sc_register_features(self._h, _p(src_pts, C.c_float), _p(fsrc, C.c_float), ns, _p(tgt_pts, C.c_float),
-                                                        _p(ftgt, C.c_float), nt, C.byref(m), C.byref(p), _p(R, C.c_float),
-                                                        _p(t, C.c_float), _p(corr, C.c_int32), _p(d2, C.c_float), C.byref(n),
-                                                        _p(mask, C.c_uint8), C.byref(st)), allow=(SC_ENOHYP,))
-        k = int(n.value)
-        self._frame_n = k
-        return dict(status=rc, R=R.reshape(3, 3), t=t, n=k, corr=corr[:k].copy(), d2=d2[:k].copy(), mask=mask[:k].copy(),
-                    stats=st.as_dict())
+        out, n = _frame_out(ns, m.knn, mask=True)
+        R, t, st = _motion_out()
+        rc = self._check(self._lib.sc_register_features(self._h, _p(src_pts), _p(fsrc), ns, _p(tgt_pts), _p(ftgt), nt, C.byref(m),
+                                                        C.byref(p), _p(R), _p(t), _p(out["corr"]), _p(out["d2"]), C.byref(n),
+                                                        _p(out["mask"]), C.byref(st)), allow=(SC_ENOHYP,))
+        return self._features_result(rc, R, t, st, out, n)
+
+    def _features_result(self, rc, R, t, st, out, count):
+        """What the *_features frame entries return, and their rule for the frame: it holds the matches counted, noted after the call."""
+        cut = _frame_cut(out, count)
+        self._frame_n = cut["n"]
+        return _result(rc, R, t, st, **cut)
 
     # ---- descriptor matching gated by a pose prior (include/saccot.h, sc_match_guided) --------------------------
     @staticmethod
@@ -728,13 +783,11 @@ class Registrar:
         src_pts, fsrc, tgt_pts, ftgt = self._guided_inputs("match_guided", src_pts, fsrc, tgt_pts, ftgt, g.layout)
         Rt = _f32c(Rt).reshape(12)
         m = mparams or make_match_params(fsrc.shape[1], **kw)
-        cap = max(fsrc.shape[0] * max(int(m.knn), 1), 1)
-        corr = np.zeros((cap, 2), np.int32); d2 = np.zeros(cap, np.float32); g2 = np.zeros(cap, np.float32); n = C.c_uint32(0)
-        self._check(self._lib.sc_match_guided(self._h, _p(src_pts, C.c_float), _p(fsrc, C.c_float), fsrc.shape[0], _p(tgt_pts, C.c_float),
-                                              _p(ftgt, C.c_float), ftgt.shape[0], C.byref(m), C.byref(g), _p(Rt, C.c_float),
-                                              _p(corr, C.c_int32), _p(d2, C.c_float), _p(g2, C.c_float), C.byref(n)))
-        k = int(n.value)
-        return dict(n=k, corr=corr[:k].copy(), d2=d2[:k].copy(), g2=g2[:k].copy())
+        out, n = _frame_out(fsrc.shape[0], m.knn, g2=True)
+        self._check(self._lib.sc_match_guided(self._h, _p(src_pts), _p(fsrc), fsrc.shape[0], _p(tgt_pts), _p(ftgt), ftgt.shape[0],
+                                              C.byref(m), C.byref(g), _p(Rt), _p(out["corr"]), _p(out["d2"]), _p(out["g2"]),
+                                              C.byref(n)))
+        return _frame_cut(out, n)
 
     def match_guided_device(self, d_src_pts: int, d_fsrc: int, ns: int, d_tgt_pts: int, d_ftgt: int, nt: int, mparams: ScMatchParams,
                             gparams: ScGuideParams, d_Rt: int, d_corr: int, d_d2: int, d_g2: int | None, d_count: int):
@@ -755,18 +808,12 @@ class Registrar:
         Rt = _f32c(Rt_prior).reshape(12)
         m = mparams or make_match_params(fsrc.shape[1], knn, mutual, ratio)
         ns, nt = fsrc.shape[0], ftgt.shape[0]
-        cap = max(ns * max(int(m.knn), 1), 1)
-        corr = np.zeros((cap, 2), np.int32); d2 = np.zeros(cap, np.float32); g2 = np.zeros(cap, np.float32); n = C.c_uint32(0)
-        R = np.zeros(9, np.float32); t = np.zeros(3, np.float32); mask = np.zeros(cap, np.uint8)
-        st = ScStats(C.sizeof(ScStats))
+        out, n = _frame_out(ns, m.knn, g2=True, mask=True)
+        R, t, st = _motion_out()
         rc = self._check(self._lib.sc_register_guided_features(
-            self._h, _p(src_pts, C.c_float), _p(fsrc, C.c_float), ns, _p(tgt_pts, C.c_float), _p(ftgt, C.c_float), nt, C.byref(m),
-            C.byref(g), _p(Rt, C.c_float), C.byref(p), _p(R, C.c_float), _p(t, C.c_float), _p(corr, C.c_int32), _p(d2, C.c_float),
-            _p(g2, C.c_float), C.byref(n), _p(mask, C.c_uint8), C.byref(st)), allow=(SC_ENOHYP,))
-        k = int(n.value)
-        self._frame_n = k
-        return dict(status=rc, R=R.reshape(3, 3), t=t, n=k, corr=corr[:k].copy(), d2=d2[:k].copy(), g2=g2[:k].copy(),
-                    mask=mask[:k].copy(), stats=st.as_dict())
+            self._h, _p(src_pts), _p(fsrc), ns, _p(tgt_pts), _p(ftgt), nt, C.byref(m), C.byref(g), _p(Rt), C.byref(p), _p(R), _p(t),
+            _p(out["corr"]), _p(out["d2"]), _p(out["g2"]), C.byref(n), _p(out["mask"]), C.byref(st)), allow=(SC_ENOHYP,))
+        return self._features_result(rc, R, t, st, out, n)
 
     # ---- descriptor matching gated by several poses (include/saccot.h, sc_match_guided_poses) -------------------
     def match_guided_poses(self, src_pts, fsrc, tgt_pts, ftgt, pose, gate: float | None = None, layout: int = SC_AOS, flags: int = 0,
@@ -779,15 +826,11 @@ class Registrar:
         src_pts, fsrc, tgt_pts, ftgt = self._guided_inputs("match_guided_poses", src_pts, fsrc, tgt_pts, ftgt, g.layout)
         pose, stride = self._pose_records(pose)
         m = mparams or make_match_params(fsrc.shape[1], **kw)
-        cap = max(fsrc.shape[0] * max(int(m.knn), 1), 1)
-        corr = np.zeros((cap, 2), np.int32); d2 = np.zeros(cap, np.float32); g2 = np.zeros(cap, np.float32); n = C.c_uint32(0)
-        label = np.zeros(cap, np.int32)
-        self._check(self._lib.sc_match_guided_poses(self._h, _p(src_pts, C.c_float), _p(fsrc, C.c_float), fsrc.shape[0],
-                                                    _p(tgt_pts, C.c_float), _p(ftgt, C.c_float), ftgt.shape[0], C.byref(m), C.byref(g),
-                                                    pose.ctypes.data_as(C.c_void_p), stride, len(pose), _p(corr, C.c_int32),
-                                                    _p(d2, C.c_float), _p(g2, C.c_float), _p(label, C.c_int32), C.byref(n)))
-        k = int(n.value)
-        return dict(n=k, corr=corr[:k].copy(), d2=d2[:k].copy(), g2=g2[:k].copy(), label=label[:k].copy())
+        out, n = _frame_out(fsrc.shape[0], m.knn, g2=True, label=True)
+        self._check(self._lib.sc_match_guided_poses(self._h, _p(src_pts), _p(fsrc), fsrc.shape[0], _p(tgt_pts), _p(ftgt), ftgt.shape[0],
+                                                    C.byref(m), C.byref(g), _vp(pose), stride, len(pose), _p(out["corr"]),
+                                                    _p(out["d2"]), _p(out["g2"]), _p(out["label"]), C.byref(n)))
+        return _frame_cut(out, n)
 
     def match_guided_poses_device(self, d_src_pts: int, d_fsrc: int, ns: int, d_tgt_pts: int, d_ftgt: int, nt: int, mparams: ScMatchParams,
                                   gparams: ScGuideParams, d_pose: int, pose_stride: int, n_poses: int, d_corr: int, d_d2: int,
@@ -811,20 +854,13 @@ class Registrar:
         pose, stride = self._pose_records(pose)
         m = mparams or make_match_params(fsrc.shape[1], knn, mutual, ratio)
         ns, nt = fsrc.shape[0], ftgt.shape[0]
-        cap = max(ns * max(int(m.knn), 1), 1)
-        corr = np.zeros((cap, 2), np.int32); d2 = np.zeros(cap, np.float32); g2 = np.zeros(cap, np.float32); n = C.c_uint32(0)
-        label = np.zeros(cap, np.int32)
-        R = np.zeros(9, np.float32); t = np.zeros(3, np.float32); mask = np.zeros(cap, np.uint8)
-        st = ScStats(C.sizeof(ScStats))
+        out, n = _frame_out(ns, m.knn, g2=True, label=True, mask=True)
+        R, t, st = _motion_out()
         rc = self._check(self._lib.sc_register_guided_poses_features(
-            self._h, _p(src_pts, C.c_float), _p(fsrc, C.c_float), ns, _p(tgt_pts, C.c_float), _p(ftgt, C.c_float), nt, C.byref(m),
-            C.byref(g), pose.ctypes.data_as(C.c_void_p), stride, len(pose), C.byref(p), _p(R, C.c_float), _p(t, C.c_float),
-            _p(corr, C.c_int32), _p(d2, C.c_float), _p(g2, C.c_float), _p(label, C.c_int32), C.byref(n), _p(mask, C.c_uint8), C.byref(st)),
-            allow=(SC_ENOHYP,))
-        k = int(n.value)
-        self._frame_n = k
-        return dict(status=rc, R=R.reshape(3, 3), t=t, n=k, corr=corr[:k].copy(), d2=d2[:k].copy(), g2=g2[:k].copy(),
-                    label=label[:k].copy(), mask=mask[:k].copy(), stats=st.as_dict())
+            self._h, _p(src_pts), _p(fsrc), ns, _p(tgt_pts), _p(ftgt), nt, C.byref(m), C.byref(g), _vp(pose), stride, len(pose),
+            C.byref(p), _p(R), _p(t), _p(out["corr"]), _p(out["d2"]), _p(out["g2"]), _p(out["label"]), C.byref(n), _p(out["mask"]),
+            C.byref(st)), allow=(SC_ENOHYP,))
+        return self._features_result(rc, R, t, st, out, n)
 
     # ---- descriptor matching for a batch of small problems (include/saccot.h, sc_match_batch) -------------------
     @staticmethod
@@ -836,15 +872,13 @@ class Registrar:
         (corr (total_s * knn, 2) int32, d2 (total_s * knn,) float32, count (B, 2) uint32).  Problem b's slot starts at entry
         src_off[b] * knn; count[b] = (n_b, 1 if the problem read a non-finite descriptor)."""
         fsrc, ftgt = _f32c(fsrc), _f32c(ftgt)
-        src_off, tgt_off = np.ascontiguousarray(src_off, dtype=np.uint32), np.ascontiguousarray(tgt_off, dtype=np.uint32)
-        nb = max(len(src_off) - 1, 0)
-        slots = (int(src_off[-1]) if len(src_off) else 0) * max(int(mparams.knn), 1)
-        corr = np.zeros((max(slots, 1), 2), np.int32); d2 = np.zeros(max(slots, 1), np.float32); count = np.zeros((max(nb, 1), 2), np.uint32)
+        (src_off, nb), (tgt_off, _) = _u32c(src_off), _u32c(tgt_off)
+        slots = _total(src_off) * max(int(mparams.knn), 1)
+        o = _slot_out(slots, nb)
         self._frame_n = 0
-        self._check(self._lib.sc_match_batch(self._h, _p(fsrc, C.c_float), _p(src_off, C.c_uint32), _p(ftgt, C.c_float),
-                                             _p(tgt_off, C.c_uint32), nb, C.byref(mparams), _p(corr, C.c_int32), _p(d2, C.c_float),
-                                             _p(count, C.c_uint32)))
-        return corr[:slots], d2[:slots], count[:nb]
+        self._check(self._lib.sc_match_batch(self._h, _p(fsrc), _p(src_off), _p(ftgt), _p(tgt_off), nb, C.byref(mparams), _p(o["corr"]),
+                                             _p(o["d2"]), _p(o["count"])))
+        return _slot_cut(o, slots, nb, "corr", "d2", "count")
 
     def match_batch(self, problems, mparams: ScMatchParams | None = None, **kw):
         """sc_match_batch: problems, a list of (fsrc (ns_b, D), ftgt (nt_b, D)) with one D and 1 .. SC_MATCH_BATCH_MAX_N rows a side ->
@@ -866,26 +900,23 @@ class Registrar:
     def match_batch_device(self, d_fsrc: int, src_off, d_ftgt: int, tgt_off, mparams: ScMatchParams, d_corr: int, d_d2: int, d_count: int):
         """sc_match_batch_device: descriptors and outputs in HBM (d_corr total_s * knn x 2 int32, d_d2 total_s * knn float32, d_count
         2 x B uint32), the offsets HOST arrays (B + 1,) uint32; enqueues on the context's stream and returns without waiting."""
-        src_off, tgt_off = np.ascontiguousarray(src_off, dtype=np.uint32), np.ascontiguousarray(tgt_off, dtype=np.uint32)
+        (src_off, nb), (tgt_off, _) = _u32c(src_off), _u32c(tgt_off)
         self._frame_n = 0
-        self._check(self._lib.sc_match_batch_device(self._h, d_fsrc, _p(src_off, C.c_uint32), d_ftgt, _p(tgt_off, C.c_uint32),
-                                                    max(len(src_off) - 1, 0), C.byref(mparams), d_corr, d_d2, d_count))
+        self._check(self._lib.sc_match_batch_device(self._h, d_fsrc, _p(src_off), d_ftgt, _p(tgt_off), nb, C.byref(mparams), d_corr, d_d2,
+                                                    d_count))
 
     def register_batch_features_raw(self, src_pts, fsrc, src_off, tgt_pts, ftgt, tgt_off, mparams: ScMatchParams, params: ScParams):
         """sc_register_batch_features on packed arrays (points in params' layout) -> (records (B,), corr, d2, count (B, 2), mask
         (total_s * knn,)), the last four slot-positioned as in match_batch_raw."""
         src_pts, fsrc, tgt_pts, ftgt = _f32c(src_pts), _f32c(fsrc), _f32c(tgt_pts), _f32c(ftgt)
-        src_off, tgt_off = np.ascontiguousarray(src_off, dtype=np.uint32), np.ascontiguousarray(tgt_off, dtype=np.uint32)
-        nb = max(len(src_off) - 1, 0)
-        slots = (int(src_off[-1]) if len(src_off) else 0) * max(int(mparams.knn), 1)
-        res = np.zeros(max(nb, 1), BATCH_RESULT_DTYPE); mask = np.zeros(max(slots, 1), np.uint8)
-        corr = np.zeros((max(slots, 1), 2), np.int32); d2 = np.zeros(max(slots, 1), np.float32); count = np.zeros((max(nb, 1), 2), np.uint32)
+        (src_off, nb), (tgt_off, _) = _u32c(src_off), _u32c(tgt_off)
+        slots = _total(src_off) * max(int(mparams.knn), 1)
+        o = _slot_out(slots, nb, registered=True)
         self._frame_n = 0
-        self._check(self._lib.sc_register_batch_features(self._h, _p(src_pts, C.c_float), _p(fsrc, C.c_float), _p(src_off, C.c_uint32),
-                                                         _p(tgt_pts, C.c_float), _p(ftgt, C.c_float), _p(tgt_off, C.c_uint32), nb,
-                                                         C.byref(mparams), C.byref(params), res.ctypes.data_as(C.c_void_p),
-                                                         _p(corr, C.c_int32), _p(d2, C.c_float), _p(count, C.c_uint32), _p(mask, C.c_uint8)))
-        return res[:nb], corr[:slots], d2[:slots], count[:nb], mask[:slots]
+        self._check(self._lib.sc_register_batch_features(self._h, _p(src_pts), _p(fsrc), _p(src_off), _p(tgt_pts), _p(ftgt), _p(tgt_off),
+                                                         nb, C.byref(mparams), C.byref(params), _vp(o["res"]), _p(o["corr"]),
+                                                         _p(o["d2"]), _p(o["count"]), _p(o["mask"])))
+        return _slot_cut(o, slots, nb, "res", "corr", "d2", "count", "mask")
 
     def register_batch_features(self, problems, mparams: ScMatchParams | None = None, params: ScParams | None = None, knn: int = 1,
                                 mutual: bool = False, ratio: float = 0.0, **kw):
@@ -916,28 +947,25 @@ class Registrar:
                                        d_mask: int):
         """sc_register_batch_features_device: everything but the offsets in HBM (d_res B records of 80 bytes, d_mask total_s * knn
         bytes, the rest as match_batch_device); enqueues on the context's stream and returns without waiting."""
-        src_off, tgt_off = np.ascontiguousarray(src_off, dtype=np.uint32), np.ascontiguousarray(tgt_off, dtype=np.uint32)
+        (src_off, nb), (tgt_off, _) = _u32c(src_off), _u32c(tgt_off)
         self._frame_n = 0
-        self._check(self._lib.sc_register_batch_features_device(self._h, d_src_pts, d_fsrc, _p(src_off, C.c_uint32), d_tgt_pts, d_ftgt,
-                                                                _p(tgt_off, C.c_uint32), max(len(src_off) - 1, 0), C.byref(mparams),
-                                                                C.byref(params), d_res, d_corr, d_d2, d_count, d_mask))
+        self._check(self._lib.sc_register_batch_features_device(self._h, d_src_pts, d_fsrc, _p(src_off), d_tgt_pts, d_ftgt, _p(tgt_off), nb,
+                                                                C.byref(mparams), C.byref(params), d_res, d_corr, d_d2, d_count, d_mask))
 
     # ---- iterated fp64 refits for a batch's winners (include/saccot.h, sc_polish_batch) ------------------------------
     def polish_batch_raw(self, src, tgt, offset, params: ScParams, pparams: ScPolishParams, res):
         """sc_polish_batch on packed arrays: src / tgt / offset as register_batch_raw's, res (B,) records of BATCH_RESULT_DTYPE (the
         input poses and statuses; read only) -> (records (B,) of POLISH_BATCH_RESULT_DTYPE, mask (total,) uint8)."""
         src, tgt = _f32c(src), _f32c(tgt)
-        offset = np.ascontiguousarray(offset, dtype=np.uint32)
+        offset, nb = _u32c(offset)
         res = np.ascontiguousarray(res, dtype=BATCH_RESULT_DTYPE)
-        nb = max(len(offset) - 1, 0)
         if len(res) != nb:
             raise ValueError("polish_batch_raw: one input record per problem")
-        total = int(offset[-1]) if len(offset) else 0
+        total = _total(offset)
         pol = np.zeros(max(nb, 1), POLISH_BATCH_RESULT_DTYPE); mask = np.zeros(max(total, 1), np.uint8)
         self._frame_n = 0
-        self._check(self._lib.sc_polish_batch(self._h, _p(src, C.c_float), _p(tgt, C.c_float), _p(offset, C.c_uint32), nb,
-                                              C.byref(params), C.byref(pparams), res.ctypes.data_as(C.c_void_p),
-                                              pol.ctypes.data_as(C.c_void_p), _p(mask, C.c_uint8)))
+        self._check(self._lib.sc_polish_batch(self._h, _p(src), _p(tgt), _p(offset), nb, C.byref(params), C.byref(pparams), _vp(res),
+                                              _vp(pol), _p(mask)))
         return pol[:nb], mask[:total]
 
     def polish_batch_device(self, d_src: int, d_tgt: int, offset, params: ScParams, pparams: ScPolishParams, d_res: int, d_pol: int,
@@ -945,20 +973,19 @@ class Registrar:
         """sc_polish_batch_device: points, input records (80 bytes each, read only), output records (64 bytes each) and mask in HBM,
         offset a HOST array (B + 1,) uint32; enqueues on the context's stream and returns without waiting.  d_mask may be the
         buffer register_batch_device wrote."""
-        offset = np.ascontiguousarray(offset, dtype=np.uint32)
+        offset, nb = _u32c(offset)
         self._frame_n = 0
-        self._check(self._lib.sc_polish_batch_device(self._h, d_src, d_tgt, _p(offset, C.c_uint32), max(len(offset) - 1, 0),
-                                                     C.byref(params), C.byref(pparams), d_res, d_pol, d_mask))
+        self._check(self._lib.sc_polish_batch_device(self._h, d_src, d_tgt, _p(offset), nb, C.byref(params), C.byref(pparams), d_res,
+                                                     d_pol, d_mask))
 
     def polish_batch_slots_device(self, d_src_pts: int, src_off, d_tgt_pts: int, tgt_off, knn: int, params: ScParams,
                                   pparams: ScPolishParams, d_corr: int, d_count: int, d_res: int, d_pol: int, d_mask: int):
         """sc_polish_batch_slots_device: behind register_batch_features_device — its points, offsets, d_corr, d_count and d_res; d_pol
         B records of 64 bytes, d_mask total_s * knn bytes; enqueues on the context's stream and returns without waiting."""
-        src_off, tgt_off = np.ascontiguousarray(src_off, dtype=np.uint32), np.ascontiguousarray(tgt_off, dtype=np.uint32)
+        (src_off, nb), (tgt_off, _) = _u32c(src_off), _u32c(tgt_off)
         self._frame_n = 0
-        self._check(self._lib.sc_polish_batch_slots_device(self._h, d_src_pts, _p(src_off, C.c_uint32), d_tgt_pts, _p(tgt_off, C.c_uint32),
-                                                           max(len(src_off) - 1, 0), knn, C.byref(params), C.byref(pparams), d_corr,
-                                                           d_count, d_res, d_pol, d_mask))
+        self._check(self._lib.sc_polish_batch_slots_device(self._h, d_src_pts, _p(src_off), d_tgt_pts, _p(tgt_off), nb, knn,
+                                                           C.byref(params), C.byref(pparams), d_corr, d_count, d_res, d_pol, d_mask))
 
     def register_batch_polished(self, problems, params: ScParams | None = None, pparams: ScPolishParams | None = None, max_iter: int = 16,
                                 **kw):
@@ -984,16 +1011,14 @@ class Registrar:
         of BATCH_RESULT_DTYPE, motion-major: records[k, b] is motion k of problem b; label (total,) int32, the motion that claimed a
         correspondence, -1 for none; nfound (B,) uint32)."""
         src, tgt = _f32c(src), _f32c(tgt)
-        offset = np.ascontiguousarray(offset, dtype=np.uint32)
-        nb = max(len(offset) - 1, 0)
-        total = int(offset[-1]) if len(offset) else 0
+        offset, nb = _u32c(offset)
+        total = _total(offset)
         planes = min(max(int(max_instances), 1), SC_INSTANCES_BATCH_MAX)  # (room; the library refuses what is out of range)
         res = np.zeros((planes, max(nb, 1)), BATCH_RESULT_DTYPE); label = np.zeros(max(total, 1), np.int32)
         nfound = np.zeros(max(nb, 1), np.uint32)
         self._frame_n = 0
-        self._check(self._lib.sc_register_instances_batch(self._h, _p(src, C.c_float), _p(tgt, C.c_float), _p(offset, C.c_uint32), nb,
-                                                          C.byref(params), max_instances, min_score, res.ctypes.data_as(C.c_void_p),
-                                                          _p(label, C.c_int32), _p(nfound, C.c_uint32)))
+        self._check(self._lib.sc_register_instances_batch(self._h, _p(src), _p(tgt), _p(offset), nb, C.byref(params), max_instances,
+                                                          min_score, _vp(res), _p(label), _p(nfound)))
         return res[:, :nb], label[:total], nfound[:nb]
 
     def register_instances_batch(self, problems, max_instances: int = 8, min_score: int = 0, params: ScParams | None = None, **kw):
@@ -1014,25 +1039,26 @@ class Registrar:
                                         d_res: int, d_label: int, d_nfound: int):
         """sc_register_instances_batch_device: points, records (max_instances x B of 80 bytes, motion-major), labels (total int32) and
         nfound (B uint32) in HBM, offset a HOST array (B + 1,) uint32; enqueues on the context's stream and returns without waiting."""
-        offset = np.ascontiguousarray(offset, dtype=np.uint32)
+        offset, nb = _u32c(offset)
         self._frame_n = 0
-        self._check(self._lib.sc_register_instances_batch_device(self._h, d_src, d_tgt, _p(offset, C.c_uint32), max(len(offset) - 1, 0),
-                                                                 C.byref(params), max_instances, min_score, d_res, d_label, d_nfound))
+        self._check(self._lib.sc_register_instances_batch_device(self._h, d_src, d_tgt, _p(offset), nb, C.byref(params), max_instances,
+                                                                 min_score, d_res, d_label, d_nfound))
 
     def register_instances_batch_features_device(self, d_src_pts: int, d_fsrc: int, src_off, d_tgt_pts: int, d_ftgt: int, tgt_off,
                                                  mparams: ScMatchParams, params: ScParams, max_instances: int, min_score: int, d_res: int,
                                                  d_corr: int, d_d2: int, d_count: int, d_label: int, d_nfound: int):
         """sc_register_instances_batch_features_device: register_batch_features_device with rounds — d_res max_instances x B records,
         d_label total_s * knn int32 positioned like that entry's mask, d_nfound B uint32; returns without waiting."""
-        src_off, tgt_off = np.ascontiguousarray(src_off, dtype=np.uint32), np.ascontiguousarray(tgt_off, dtype=np.uint32)
+        (src_off, nb), (tgt_off, _) = _u32c(src_off), _u32c(tgt_off)
         self._frame_n = 0
         self._check(self._lib.sc_register_instances_batch_features_device(
-            self._h, d_src_pts, d_fsrc, _p(src_off, C.c_uint32), d_tgt_pts, d_ftgt, _p(tgt_off, C.c_uint32), max(len(src_off) - 1, 0),
-            C.byref(mparams), C.byref(params), max_instances, min_score, d_res, d_corr, d_d2, d_count, d_label, d_nfound))
+            self._h, d_src_pts, d_fsrc, _p(src_off), d_tgt_pts, d_ftgt, _p(tgt_off), nb, C.byref(mparams), C.byref(params), max_instances,
+            min_score, d_res, d_corr, d_d2, d_count, d_label, d_nfound))
 
     # ---- listed pairs of shared keypoint sets (include/saccot.h, sc_match_pairs) ------------------------------------
     @staticmethod
     def _table(set_off, pairs):
+        """set_off (S + 1,) and pairs (P, 2) as the pairs entries take them -> (set_off, pairs, S, P), both flat uint32"""
         set_off = np.ascontiguousarray(set_off, dtype=np.uint32).reshape(-1)
         pairs = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1)
         return set_off, pairs, max(len(set_off) - 1, 0), len(pairs) // 2
@@ -1044,7 +1070,7 @@ class Registrar:
         pairs entries refuse."""
         set_off, pairs, ns, npairs = Registrar._table(set_off, pairs)
         slot = np.zeros(npairs + 1, np.uint32)
-        rc = load_library().sc_pairs_layout(_p(set_off, C.c_uint32), ns, _p(pairs, C.c_uint32), npairs, knn, _p(slot, C.c_uint32))
+        rc = load_library().sc_pairs_layout(_p(set_off), ns, _p(pairs), npairs, knn, _p(slot))
         if rc != SC_OK:
             raise SacCotError(rc, "sc_pairs_layout")
         return slot
@@ -1059,19 +1085,19 @@ class Registrar:
         set_off, pairs, ns, npairs = self._table(set_off, pairs)
         slot = self.pairs_layout(set_off, pairs, int(m.knn))
         slots = int(slot[-1])
-        corr = np.zeros((max(slots, 1), 2), np.int32); d2 = np.zeros(max(slots, 1), np.float32); count = np.zeros((max(npairs, 1), 2), np.uint32)
+        o = _slot_out(slots, npairs)
         self._frame_n = 0
-        self._check(self._lib.sc_match_pairs(self._h, _p(feat, C.c_float), _p(set_off, C.c_uint32), ns, _p(pairs, C.c_uint32), npairs,
-                                             C.byref(m), _p(corr, C.c_int32), _p(d2, C.c_float), _p(count, C.c_uint32)))
-        return corr[:slots], d2[:slots], count[:npairs], slot
+        self._check(self._lib.sc_match_pairs(self._h, _p(feat), _p(set_off), ns, _p(pairs), npairs, C.byref(m), _p(o["corr"]), _p(o["d2"]),
+                                             _p(o["count"])))
+        return _slot_cut(o, slots, npairs, "corr", "d2", "count") + (slot,)
 
     def match_pairs_device(self, d_feat: int, set_off, pairs, mparams: ScMatchParams, d_corr: int, d_d2: int, d_count: int):
         """sc_match_pairs_device: the table's descriptors and the outputs in HBM (d_corr slot[P] x 2 int32, d_d2 slot[P] float32,
         d_count 2 x P uint32), set_off and pairs HOST arrays; enqueues on the context's stream and returns without waiting."""
         set_off, pairs, ns, npairs = self._table(set_off, pairs)
         self._frame_n = 0
-        self._check(self._lib.sc_match_pairs_device(self._h, d_feat, _p(set_off, C.c_uint32), ns, _p(pairs, C.c_uint32), npairs,
-                                                    C.byref(mparams), d_corr, d_d2, d_count))
+        self._check(self._lib.sc_match_pairs_device(self._h, d_feat, _p(set_off), ns, _p(pairs), npairs, C.byref(mparams), d_corr, d_d2,
+                                                    d_count))
 
     def register_pairs_features(self, pts, feat, set_off, pairs, mparams: ScMatchParams | None = None, params: ScParams | None = None,
                                 knn: int = 1, mutual: bool = False, ratio: float = 0.0, **kw):
@@ -1084,14 +1110,12 @@ class Registrar:
         set_off, pairs, ns, npairs = self._table(set_off, pairs)
         slot = self.pairs_layout(set_off, pairs, int(m.knn))
         slots = int(slot[-1])
-        res = np.zeros(max(npairs, 1), BATCH_RESULT_DTYPE); mask = np.zeros(max(slots, 1), np.uint8)
-        corr = np.zeros((max(slots, 1), 2), np.int32); d2 = np.zeros(max(slots, 1), np.float32); count = np.zeros((max(npairs, 1), 2), np.uint32)
+        o = _slot_out(slots, npairs, registered=True)
         self._frame_n = 0
-        self._check(self._lib.sc_register_pairs_features(self._h, _p(pts, C.c_float), _p(feat, C.c_float), _p(set_off, C.c_uint32), ns,
-                                                         _p(pairs, C.c_uint32), npairs, C.byref(m), C.byref(p),
-                                                         res.ctypes.data_as(C.c_void_p), _p(corr, C.c_int32), _p(d2, C.c_float),
-                                                         _p(count, C.c_uint32), _p(mask, C.c_uint8)))
-        return res[:npairs], corr[:slots], d2[:slots], count[:npairs], mask[:slots], slot
+        self._check(self._lib.sc_register_pairs_features(self._h, _p(pts), _p(feat), _p(set_off), ns, _p(pairs), npairs, C.byref(m),
+                                                         C.byref(p), _vp(o["res"]), _p(o["corr"]), _p(o["d2"]), _p(o["count"]),
+                                                         _p(o["mask"])))
+        return _slot_cut(o, slots, npairs, "res", "corr", "d2", "count", "mask") + (slot,)
 
     def register_pairs_features_device(self, d_pts: int, d_feat: int, set_off, pairs, mparams: ScMatchParams, params: ScParams,
                                        d_res: int, d_corr: int, d_d2: int, d_count: int, d_mask: int):
@@ -1099,9 +1123,8 @@ class Registrar:
         bytes, the rest as match_pairs_device); enqueues on the context's stream and returns without waiting."""
         set_off, pairs, ns, npairs = self._table(set_off, pairs)
         self._frame_n = 0
-        self._check(self._lib.sc_register_pairs_features_device(self._h, d_pts, d_feat, _p(set_off, C.c_uint32), ns, _p(pairs, C.c_uint32),
-                                                                npairs, C.byref(mparams), C.byref(params), d_res, d_corr, d_d2, d_count,
-                                                                d_mask))
+        self._check(self._lib.sc_register_pairs_features_device(self._h, d_pts, d_feat, _p(set_off), ns, _p(pairs), npairs,
+                                                                C.byref(mparams), C.byref(params), d_res, d_corr, d_d2, d_count, d_mask))
 
     def polish_pairs_slots_device(self, d_pts: int, set_off, pairs, knn: int, params: ScParams, pparams: ScPolishParams, d_corr: int,
                                   d_count: int, d_res: int, d_pol: int, d_mask: int):
@@ -1109,8 +1132,8 @@ class Registrar:
         d_res; d_pol P records of 64 bytes, d_mask slot[P] bytes; enqueues on the context's stream and returns without waiting."""
         set_off, pairs, ns, npairs = self._table(set_off, pairs)
         self._frame_n = 0
-        self._check(self._lib.sc_polish_pairs_slots_device(self._h, d_pts, _p(set_off, C.c_uint32), ns, _p(pairs, C.c_uint32), npairs, knn,
-                                                           C.byref(params), C.byref(pparams), d_corr, d_count, d_res, d_pol, d_mask))
+        self._check(self._lib.sc_polish_pairs_slots_device(self._h, d_pts, _p(set_off), ns, _p(pairs), npairs, knn, C.byref(params),
+                                                           C.byref(pparams), d_corr, d_count, d_res, d_pol, d_mask))
 
     # ---- pose-gated matching for batches and pairs (include/saccot.h, sc_match_guided_batch) ---------------------------
     @staticmethod
@@ -1139,30 +1162,27 @@ class Registrar:
         whose status is not SC_OK skips its problem: (0, 0)."""
         g = gparams or make_guide_params(gate, layout, flags)
         src_pts, fsrc, tgt_pts, ftgt = _f32c(src_pts), _f32c(fsrc), _f32c(tgt_pts), _f32c(ftgt)
-        src_off, tgt_off = np.ascontiguousarray(src_off, dtype=np.uint32), np.ascontiguousarray(tgt_off, dtype=np.uint32)
+        (src_off, nb), (tgt_off, _) = _u32c(src_off), _u32c(tgt_off)
         m = mparams or make_match_params(fsrc.shape[1], **kw)
-        nb = max(len(src_off) - 1, 0)
         pose, stride = self._pose_records(pose, nb)
-        slots = (int(src_off[-1]) if len(src_off) else 0) * max(int(m.knn), 1)
-        corr = np.zeros((max(slots, 1), 2), np.int32); d2 = np.zeros(max(slots, 1), np.float32); count = np.zeros((max(nb, 1), 2), np.uint32)
-        g2 = np.zeros(max(slots, 1), np.float32) if want_g2 else None
+        slots = _total(src_off) * max(int(m.knn), 1)
+        o = _slot_out(slots, nb, g2=want_g2)
         self._frame_n = 0
-        self._check(self._lib.sc_match_guided_batch(self._h, _p(src_pts, C.c_float), _p(fsrc, C.c_float), _p(src_off, C.c_uint32),
-                                                    _p(tgt_pts, C.c_float), _p(ftgt, C.c_float), _p(tgt_off, C.c_uint32), nb, C.byref(m),
-                                                    C.byref(g), pose.ctypes.data_as(C.c_void_p), stride, _p(corr, C.c_int32),
-                                                    _p(d2, C.c_float), _p(g2, C.c_float), _p(count, C.c_uint32)))
-        return corr[:slots], d2[:slots], (g2[:slots] if want_g2 else None), count[:nb]
+        self._check(self._lib.sc_match_guided_batch(self._h, _p(src_pts), _p(fsrc), _p(src_off), _p(tgt_pts), _p(ftgt), _p(tgt_off), nb,
+                                                    C.byref(m), C.byref(g), _vp(pose), stride, _p(o["corr"]), _p(o["d2"]), _p(o["g2"]),
+                                                    _p(o["count"])))
+        return _slot_cut(o, slots, nb, "corr", "d2", "g2", "count")
 
     def match_guided_batch_device(self, d_src_pts: int, d_fsrc: int, src_off, d_tgt_pts: int, d_ftgt: int, tgt_off, mparams: ScMatchParams,
                                   gparams: ScGuideParams, d_pose: int, pose_stride: int, d_corr: int, d_d2: int, d_g2: int | None,
                                   d_count: int):
         """sc_match_guided_batch_device: everything but the offsets in HBM (d_pose: B records pose_stride bytes apart, read in stream
         order; d_g2: total_s * knn float32 or None; the rest as match_batch_device); returns without waiting."""
-        src_off, tgt_off = np.ascontiguousarray(src_off, dtype=np.uint32), np.ascontiguousarray(tgt_off, dtype=np.uint32)
+        (src_off, nb), (tgt_off, _) = _u32c(src_off), _u32c(tgt_off)
         self._frame_n = 0
-        self._check(self._lib.sc_match_guided_batch_device(self._h, d_src_pts, d_fsrc, _p(src_off, C.c_uint32), d_tgt_pts, d_ftgt,
-                                                           _p(tgt_off, C.c_uint32), max(len(src_off) - 1, 0), C.byref(mparams),
-                                                           C.byref(gparams), d_pose, pose_stride, d_corr, d_d2, d_g2, d_count))
+        self._check(self._lib.sc_match_guided_batch_device(self._h, d_src_pts, d_fsrc, _p(src_off), d_tgt_pts, d_ftgt, _p(tgt_off), nb,
+                                                           C.byref(mparams), C.byref(gparams), d_pose, pose_stride, d_corr, d_d2, d_g2,
+                                                           d_count))
 
     def register_guided_batch_features_device(self, d_src_pts: int, d_fsrc: int, src_off, d_tgt_pts: int, d_ftgt: int, tgt_off,
                                               mparams: ScMatchParams, gparams: ScGuideParams, d_pose: int, pose_stride: int,
@@ -1170,11 +1190,11 @@ class Registrar:
                                               d_mask: int):
         """sc_register_guided_batch_features_device: match_guided_batch_device, then the registration on the slots (d_res, d_mask as
         register_batch_features_device's).  d_pose may be d_res; returns without waiting."""
-        src_off, tgt_off = np.ascontiguousarray(src_off, dtype=np.uint32), np.ascontiguousarray(tgt_off, dtype=np.uint32)
+        (src_off, nb), (tgt_off, _) = _u32c(src_off), _u32c(tgt_off)
         self._frame_n = 0
         self._check(self._lib.sc_register_guided_batch_features_device(
-            self._h, d_src_pts, d_fsrc, _p(src_off, C.c_uint32), d_tgt_pts, d_ftgt, _p(tgt_off, C.c_uint32), max(len(src_off) - 1, 0),
-            C.byref(mparams), C.byref(gparams), d_pose, pose_stride, C.byref(params), d_res, d_corr, d_d2, d_g2, d_count, d_mask))
+            self._h, d_src_pts, d_fsrc, _p(src_off), d_tgt_pts, d_ftgt, _p(tgt_off), nb, C.byref(mparams), C.byref(gparams), d_pose,
+            pose_stride, C.byref(params), d_res, d_corr, d_d2, d_g2, d_count, d_mask))
 
     def match_guided_pairs(self, pts, feat, set_off, pairs, pose, gate: float | None = None, layout: int = SC_AOS, flags: int = 0,
                            mparams: ScMatchParams | None = None, gparams: ScGuideParams | None = None, want_g2: bool = True, **kw):
@@ -1187,14 +1207,11 @@ class Registrar:
         pose, stride = self._pose_records(pose, npairs)
         slot = self.pairs_layout(set_off, pairs, int(m.knn))
         slots = int(slot[-1])
-        corr = np.zeros((max(slots, 1), 2), np.int32); d2 = np.zeros(max(slots, 1), np.float32); count = np.zeros((max(npairs, 1), 2), np.uint32)
-        g2 = np.zeros(max(slots, 1), np.float32) if want_g2 else None
+        o = _slot_out(slots, npairs, g2=want_g2)
         self._frame_n = 0
-        self._check(self._lib.sc_match_guided_pairs(self._h, _p(pts, C.c_float), _p(feat, C.c_float), _p(set_off, C.c_uint32), ns,
-                                                    _p(pairs, C.c_uint32), npairs, C.byref(m), C.byref(g), pose.ctypes.data_as(C.c_void_p),
-                                                    stride, _p(corr, C.c_int32), _p(d2, C.c_float), _p(g2, C.c_float),
-                                                    _p(count, C.c_uint32)))
-        return corr[:slots], d2[:slots], (g2[:slots] if want_g2 else None), count[:npairs], slot
+        self._check(self._lib.sc_match_guided_pairs(self._h, _p(pts), _p(feat), _p(set_off), ns, _p(pairs), npairs, C.byref(m), C.byref(g),
+                                                    _vp(pose), stride, _p(o["corr"]), _p(o["d2"]), _p(o["g2"]), _p(o["count"])))
+        return _slot_cut(o, slots, npairs, "corr", "d2", "g2", "count") + (slot,)
 
     def match_guided_pairs_device(self, d_pts: int, d_feat: int, set_off, pairs, mparams: ScMatchParams, gparams: ScGuideParams,
                                   d_pose: int, pose_stride: int, d_corr: int, d_d2: int, d_g2: int | None, d_count: int):
@@ -1202,9 +1219,8 @@ class Registrar:
         arrays; returns without waiting."""
         set_off, pairs, ns, npairs = self._table(set_off, pairs)
         self._frame_n = 0
-        self._check(self._lib.sc_match_guided_pairs_device(self._h, d_pts, d_feat, _p(set_off, C.c_uint32), ns, _p(pairs, C.c_uint32),
-                                                           npairs, C.byref(mparams), C.byref(gparams), d_pose, pose_stride, d_corr, d_d2,
-                                                           d_g2, d_count))
+        self._check(self._lib.sc_match_guided_pairs_device(self._h, d_pts, d_feat, _p(set_off), ns, _p(pairs), npairs, C.byref(mparams),
+                                                           C.byref(gparams), d_pose, pose_stride, d_corr, d_d2, d_g2, d_count))
 
     def register_guided_pairs_features_device(self, d_pts: int, d_feat: int, set_off, pairs, mparams: ScMatchParams,
                                               gparams: ScGuideParams, d_pose: int, pose_stride: int, params: ScParams, d_res: int,
@@ -1214,8 +1230,8 @@ class Registrar:
         set_off, pairs, ns, npairs = self._table(set_off, pairs)
         self._frame_n = 0
         self._check(self._lib.sc_register_guided_pairs_features_device(
-            self._h, d_pts, d_feat, _p(set_off, C.c_uint32), ns, _p(pairs, C.c_uint32), npairs, C.byref(mparams), C.byref(gparams), d_pose,
-            pose_stride, C.byref(params), d_res, d_corr, d_d2, d_g2, d_count, d_mask))
+            self._h, d_pts, d_feat, _p(set_off), ns, _p(pairs), npairs, C.byref(mparams), C.byref(gparams), d_pose, pose_stride,
+            C.byref(params), d_res, d_corr, d_d2, d_g2, d_count, d_mask))
 
     # ---- the fp64 information matrix of a batch's poses (include/saccot.h, sc_pose_info_batch) -------------------------
     def pose_info_batch_raw(self, src, tgt, offset, params: ScParams, pose):
@@ -1223,35 +1239,32 @@ class Registrar:
         items start with float Rt[12] and int32 status — BATCH_RESULT_DTYPE, POLISH_BATCH_RESULT_DTYPE, a plane of
         register_instances_batch_raw's records — read only -> records (B,) of POSE_INFO_RESULT_DTYPE."""
         src, tgt = _f32c(src), _f32c(tgt)
-        offset = np.ascontiguousarray(offset, dtype=np.uint32)
+        offset, nb = _u32c(offset)
         pose = np.ascontiguousarray(pose)
-        nb = max(len(offset) - 1, 0)
         if pose.ndim != 1 or len(pose) != nb:
             raise ValueError("pose_info_batch_raw: one pose record per problem")
         info = np.zeros(max(nb, 1), POSE_INFO_RESULT_DTYPE)
         self._frame_n = 0
-        self._check(self._lib.sc_pose_info_batch(self._h, _p(src, C.c_float), _p(tgt, C.c_float), _p(offset, C.c_uint32), nb,
-                                                 C.byref(params), pose.ctypes.data_as(C.c_void_p), pose.dtype.itemsize,
-                                                 info.ctypes.data_as(C.c_void_p)))
+        self._check(self._lib.sc_pose_info_batch(self._h, _p(src), _p(tgt), _p(offset), nb, C.byref(params), _vp(pose),
+                                                 pose.dtype.itemsize, _vp(info)))
         return info[:nb]
 
     def pose_info_batch_device(self, d_src: int, d_tgt: int, offset, params: ScParams, d_pose: int, pose_stride: int, d_info: int):
         """sc_pose_info_batch_device: points, pose records (pose_stride bytes each, read only) and output records (320 bytes each) in
         HBM, offset a HOST array (B + 1,) uint32; enqueues on the context's stream and returns without waiting."""
-        offset = np.ascontiguousarray(offset, dtype=np.uint32)
+        offset, nb = _u32c(offset)
         self._frame_n = 0
-        self._check(self._lib.sc_pose_info_batch_device(self._h, d_src, d_tgt, _p(offset, C.c_uint32), max(len(offset) - 1, 0),
-                                                        C.byref(params), d_pose, pose_stride, d_info))
+        self._check(self._lib.sc_pose_info_batch_device(self._h, d_src, d_tgt, _p(offset), nb, C.byref(params), d_pose, pose_stride,
+                                                        d_info))
 
     def pose_info_batch_slots_device(self, d_src_pts: int, src_off, d_tgt_pts: int, tgt_off, knn: int, params: ScParams, d_corr: int,
                                      d_count: int, d_pose: int, pose_stride: int, d_info: int):
         """sc_pose_info_batch_slots_device: behind register_batch_features_device — its points, offsets, d_corr and d_count; d_pose B
         records of pose_stride bytes, d_info B records of 320 bytes; enqueues on the context's stream and returns without waiting."""
-        src_off, tgt_off = np.ascontiguousarray(src_off, dtype=np.uint32), np.ascontiguousarray(tgt_off, dtype=np.uint32)
+        (src_off, nb), (tgt_off, _) = _u32c(src_off), _u32c(tgt_off)
         self._frame_n = 0
-        self._check(self._lib.sc_pose_info_batch_slots_device(self._h, d_src_pts, _p(src_off, C.c_uint32), d_tgt_pts, _p(tgt_off, C.c_uint32),
-                                                              max(len(src_off) - 1, 0), knn, C.byref(params), d_corr, d_count, d_pose,
-                                                              pose_stride, d_info))
+        self._check(self._lib.sc_pose_info_batch_slots_device(self._h, d_src_pts, _p(src_off), d_tgt_pts, _p(tgt_off), nb, knn,
+                                                              C.byref(params), d_corr, d_count, d_pose, pose_stride, d_info))
 
     def pose_info_pairs_slots_device(self, d_pts: int, set_off, pairs, knn: int, params: ScParams, d_corr: int, d_count: int, d_pose: int,
                                      pose_stride: int, d_info: int):
@@ -1260,8 +1273,8 @@ class Registrar:
         waiting."""
         set_off, pairs, ns, npairs = self._table(set_off, pairs)
         self._frame_n = 0
-        self._check(self._lib.sc_pose_info_pairs_slots_device(self._h, d_pts, _p(set_off, C.c_uint32), ns, _p(pairs, C.c_uint32), npairs, knn,
-                                                              C.byref(params), d_corr, d_count, d_pose, pose_stride, d_info))
+        self._check(self._lib.sc_pose_info_pairs_slots_device(self._h, d_pts, _p(set_off), ns, _p(pairs), npairs, knn, C.byref(params),
+                                                              d_corr, d_count, d_pose, pose_stride, d_info))
 
     # ---- the same on the frame the last register* call left (include/saccot.h, sc_pose_info_frame) ---------------------------
     def pose_info_frame(self, pose, iparams: ScPoseInfoParams | None = None, sel=None, **kw):
@@ -1269,21 +1282,11 @@ class Registrar:
         int32 status behind it) — or a float32 array (K, 12) / (12,) —; sel None, (n,) uint8 (SEL_MASK) or (n,) int32 (SEL_LABEL), read
         only -> records (K,) of POSE_INFO_RESULT_DTYPE.  The frame stays.  kw: sel_mode, label0, flags (make_pose_info_params)."""
         q = iparams or make_pose_info_params(**kw)
-        pose = np.ascontiguousarray(pose)
-        if pose.dtype.fields is None:
-            pose = np.ascontiguousarray(pose, dtype=np.float32).reshape(-1, 12)
-            stride = 48
-        else:
-            pose = pose.reshape(-1)
-            stride = pose.dtype.itemsize
+        pose, stride = self._pose_records(pose)
         k = len(pose)
-        if sel is not None:
-            sel = np.ascontiguousarray(sel, dtype=np.int32 if q.sel_mode == SC_POSE_INFO_SEL_LABEL else np.uint8)
-            if sel.size != self._frame_n:
-                raise ValueError("pose_info_frame: sel holds one entry per correspondence of the frame")
+        sel = _frame_sel("pose_info_frame", sel, np.int32 if q.sel_mode == SC_POSE_INFO_SEL_LABEL else np.uint8, self._frame_n)
         info = np.zeros(max(k, 1), POSE_INFO_RESULT_DTYPE)
-        self._check(self._lib.sc_pose_info_frame(self._h, C.byref(q), pose.ctypes.data_as(C.c_void_p), stride, k,
-                                                 None if sel is None else sel.ctypes.data_as(C.c_void_p), info.ctypes.data_as(C.c_void_p)))
+        self._check(self._lib.sc_pose_info_frame(self._h, C.byref(q), _vp(pose), stride, k, _vp(sel), _vp(info)))
         return info[:k]
 
     def pose_info_frame_device(self, iparams: ScPoseInfoParams, d_pose: int, pose_stride: int, n_poses: int, d_sel: int, d_info: int):
@@ -1298,24 +1301,13 @@ class Registrar:
         SEL_ALIVE), read only -> (records (K,) of POLISH_BATCH_RESULT_DTYPE, masks (K, n) uint8 or None).  The frame stays.
         kw: max_iter, sel_mode, label0, flags (make_polish_poses_params)."""
         q = pparams or make_polish_poses_params(**kw)
-        pose = np.ascontiguousarray(pose)
-        if pose.dtype.fields is None:
-            pose = np.ascontiguousarray(pose, dtype=np.float32).reshape(-1, 12)
-            stride = 48
-        else:
-            pose = pose.reshape(-1)
-            stride = pose.dtype.itemsize
-        k = len(pose)
-        if sel is not None:
-            sel = np.ascontiguousarray(sel, dtype=np.uint8 if q.sel_mode == SC_POLISH_POSES_SEL_MASK else np.int32)
-            if sel.size != self._frame_n:
-                raise ValueError("polish_poses: sel holds one entry per correspondence of the frame")
+        pose, stride = self._pose_records(pose)
+        k, n = len(pose), self._frame_n
+        sel = _frame_sel("polish_poses", sel, np.uint8 if q.sel_mode == SC_POLISH_POSES_SEL_MASK else np.int32, n)
         pol = np.zeros(max(k, 1), POLISH_BATCH_RESULT_DTYPE)
-        mask = np.zeros((max(k, 1), max(self._frame_n, 1)), np.uint8) if want_mask else None
-        self._check(self._lib.sc_polish_poses(self._h, C.byref(q), pose.ctypes.data_as(C.c_void_p), stride, k,
-                                              None if sel is None else sel.ctypes.data_as(C.c_void_p), pol.ctypes.data_as(C.c_void_p),
-                                              None if mask is None else mask.ctypes.data_as(C.c_void_p)))
-        return pol[:k], (None if mask is None else mask[:k, :self._frame_n])
+        mask = np.zeros((max(k, 1), max(n, 1)), np.uint8) if want_mask else None
+        self._check(self._lib.sc_polish_poses(self._h, C.byref(q), _vp(pose), stride, k, _vp(sel), _vp(pol), _vp(mask)))
+        return pol[:k], (None if mask is None else mask[:k, :n])
 
     def polish_poses_device(self, pparams: ScPolishPosesParams, d_pose: int, pose_stride: int, n_poses: int, d_sel: int, d_pol: int,
                             d_mask: int = 0):
@@ -1332,23 +1324,13 @@ class Registrar:
         (label (n,) int32, d2 (n,) float32 or None, records (K,) of ASSIGN_RESULT_DTYPE).  The frame stays.
         kw: mode, sel_mode, flags (make_assign_params)."""
         q = aparams or make_assign_params(**kw)
-        pose = np.ascontiguousarray(pose)
-        if pose.dtype.fields is None:
-            pose = np.ascontiguousarray(pose, dtype=np.float32).reshape(-1, 12)
-            stride = 48
-        else:
-            pose = pose.reshape(-1)
-            stride = pose.dtype.itemsize
+        pose, stride = self._pose_records(pose)
         k, n = len(pose), self._frame_n
-        if sel is not None:
-            sel = np.ascontiguousarray(sel, dtype=np.uint8)
-            if sel.size != n:
-                raise ValueError("assign_poses_frame: sel holds one entry per correspondence of the frame")
+        sel = _frame_sel("assign_poses_frame", sel, np.uint8, n)
         label = np.zeros(max(n, 1), np.int32)
         d2 = np.zeros(max(n, 1), np.float32) if want_d2 else None
         asg = np.zeros(max(k, 1), ASSIGN_RESULT_DTYPE)
-        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        self._check(self._lib.sc_assign_poses_frame(self._h, C.byref(q), vp(pose), stride, k, vp(sel), vp(label), vp(d2), vp(asg)))
+        self._check(self._lib.sc_assign_poses_frame(self._h, C.byref(q), _vp(pose), stride, k, _vp(sel), _vp(label), _vp(d2), _vp(asg)))
         return label[:n], (None if d2 is None else d2[:n]), asg[:k]
 
     def assign_poses_frame_device(self, aparams: ScAssignParams, d_pose: int, pose_stride: int, n_poses: int, d_sel: int, d_label: int,
@@ -1365,19 +1347,17 @@ class Registrar:
         (label (total,) int32, records (K, B) of ASSIGN_RESULT_DTYPE).  kw: mode, flags (make_assign_params)."""
         q = aparams or make_assign_params(**kw)
         src, tgt = _f32c(src), _f32c(tgt)
-        offset = np.ascontiguousarray(offset, dtype=np.uint32)
+        offset, nb = _u32c(offset)
         pose = np.ascontiguousarray(pose)
-        nb = max(len(offset) - 1, 0)
-        total = int(offset[-1]) if len(offset) else 0
+        total = _total(offset)
         if pose.ndim != 2 or pose.shape[1] != nb:
             raise ValueError("assign_poses_batch: pose holds (n_poses, n_problems) records")
         k = pose.shape[0]
         label = np.zeros(max(total, 1), np.int32)
         asg = np.zeros((max(k, 1), max(nb, 1)), ASSIGN_RESULT_DTYPE)
         self._frame_n = 0
-        self._check(self._lib.sc_assign_poses_batch(self._h, _p(src, C.c_float), _p(tgt, C.c_float), _p(offset, C.c_uint32), nb,
-                                                    C.byref(params), C.byref(q), pose.ctypes.data_as(C.c_void_p), pose.dtype.itemsize, k,
-                                                    label.ctypes.data_as(C.c_void_p), asg.ctypes.data_as(C.c_void_p)))
+        self._check(self._lib.sc_assign_poses_batch(self._h, _p(src), _p(tgt), _p(offset), nb, C.byref(params), C.byref(q), _vp(pose),
+                                                    pose.dtype.itemsize, k, _vp(label), _vp(asg)))
         return label[:total], asg[:k, :nb]
 
     def assign_poses_batch_device(self, d_src: int, d_tgt: int, offset, params: ScParams, aparams: ScAssignParams, d_pose: int,
@@ -1385,10 +1365,10 @@ class Registrar:
         """sc_assign_poses_batch_device: points, pose records (n_poses x B of pose_stride bytes, motion-major, read only), labels
         (total int32) and records (n_poses x B of 32 bytes, motion-major) in HBM, offset a HOST array (B + 1,) uint32; enqueues on the
         context's stream and returns without waiting."""
-        offset = np.ascontiguousarray(offset, dtype=np.uint32)
+        offset, nb = _u32c(offset)
         self._frame_n = 0
-        self._check(self._lib.sc_assign_poses_batch_device(self._h, d_src, d_tgt, _p(offset, C.c_uint32), max(len(offset) - 1, 0),
-                                                           C.byref(params), C.byref(aparams), d_pose, pose_stride, n_poses, d_label, d_asg))
+        self._check(self._lib.sc_assign_poses_batch_device(self._h, d_src, d_tgt, _p(offset), nb, C.byref(params), C.byref(aparams),
+                                                           d_pose, pose_stride, n_poses, d_label, d_asg))
 
     # ---- poses relabelled and refitted until stable (include/saccot.h, sc_settle_poses) -----------------------------------------
     def settle_poses_frame(self, pose, sparams: ScSettleParams | None = None, sel=None, want_d2: bool = True, want_rounds: bool = True,
@@ -1398,25 +1378,15 @@ class Registrar:
         (records (K,) of POLISH_BATCH_RESULT_DTYPE, label (n,) int32, d2 (n,) float32 or None, rounds (2,) uint32 — counted rounds,
         stop — or None).  The frame stays.  kw: max_iter, sel_mode, flags (make_settle_params)."""
         q = sparams or make_settle_params(**kw)
-        pose = np.ascontiguousarray(pose)
-        if pose.dtype.fields is None:
-            pose = np.ascontiguousarray(pose, dtype=np.float32).reshape(-1, 12)
-            stride = 48
-        else:
-            pose = pose.reshape(-1)
-            stride = pose.dtype.itemsize
+        pose, stride = self._pose_records(pose)
         k, n = len(pose), self._frame_n
-        if sel is not None:
-            sel = np.ascontiguousarray(sel, dtype=np.uint8)
-            if sel.size != n:
-                raise ValueError("settle_poses_frame: sel holds one entry per correspondence of the frame")
+        sel = _frame_sel("settle_poses_frame", sel, np.uint8, n)
         pol = np.zeros(max(k, 1), POLISH_BATCH_RESULT_DTYPE)
         label = np.zeros(max(n, 1), np.int32)
         d2 = np.zeros(max(n, 1), np.float32) if want_d2 else None
         rounds = np.zeros(2, np.uint32) if want_rounds else None
-        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        self._check(self._lib.sc_settle_poses_frame(self._h, C.byref(q), vp(pose), stride, k, vp(sel), vp(pol), vp(label), vp(d2),
-                                                    vp(rounds)))
+        self._check(self._lib.sc_settle_poses_frame(self._h, C.byref(q), _vp(pose), stride, k, _vp(sel), _vp(pol), _vp(label), _vp(d2),
+                                                    _vp(rounds)))
         return pol[:k], label[:n], (None if d2 is None else d2[:n]), rounds
 
     def settle_poses_frame_device(self, sparams: ScSettleParams, d_pose: int, pose_stride: int, n_poses: int, d_sel: int, d_pol: int,
@@ -1434,10 +1404,9 @@ class Registrar:
         (make_settle_params)."""
         q = sparams or make_settle_params(**kw)
         src, tgt = _f32c(src), _f32c(tgt)
-        offset = np.ascontiguousarray(offset, dtype=np.uint32)
+        offset, nb = _u32c(offset)
         pose = np.ascontiguousarray(pose)
-        nb = max(len(offset) - 1, 0)
-        total = int(offset[-1]) if len(offset) else 0
+        total = _total(offset)
         if pose.ndim != 2 or pose.shape[1] != nb:
             raise ValueError("settle_poses_batch: pose holds (n_poses, n_problems) records")
         k = pose.shape[0]
@@ -1445,10 +1414,8 @@ class Registrar:
         label = np.zeros(max(total, 1), np.int32)
         rounds = np.zeros((max(nb, 1), 2), np.uint32)
         self._frame_n = 0
-        self._check(self._lib.sc_settle_poses_batch(self._h, _p(src, C.c_float), _p(tgt, C.c_float), _p(offset, C.c_uint32), nb,
-                                                    C.byref(params), C.byref(q), pose.ctypes.data_as(C.c_void_p), pose.dtype.itemsize, k,
-                                                    pol.ctypes.data_as(C.c_void_p), label.ctypes.data_as(C.c_void_p),
-                                                    rounds.ctypes.data_as(C.c_void_p)))
+        self._check(self._lib.sc_settle_poses_batch(self._h, _p(src), _p(tgt), _p(offset), nb, C.byref(params), C.byref(q), _vp(pose),
+                                                    pose.dtype.itemsize, k, _vp(pol), _vp(label), _vp(rounds)))
         return pol[:k, :nb], label[:total], rounds[:nb]
 
     def settle_poses_batch_device(self, d_src: int, d_tgt: int, offset, params: ScParams, sparams: ScSettleParams, d_pose: int,
@@ -1456,11 +1423,10 @@ class Registrar:
         """sc_settle_poses_batch_device: points, pose records (n_poses x B of pose_stride bytes, motion-major, read only), output
         records (n_poses x B of 64 bytes, motion-major), labels (total int32) and the word pairs (2 x B; 0: none) in HBM, offset a
         HOST array (B + 1,) uint32; enqueues on the context's stream and returns without waiting."""
-        offset = np.ascontiguousarray(offset, dtype=np.uint32)
+        offset, nb = _u32c(offset)
         self._frame_n = 0
-        self._check(self._lib.sc_settle_poses_batch_device(self._h, d_src, d_tgt, _p(offset, C.c_uint32), max(len(offset) - 1, 0),
-                                                           C.byref(params), C.byref(sparams), d_pose, pose_stride, n_poses, d_pol, d_label,
-                                                           d_rounds or None))
+        self._check(self._lib.sc_settle_poses_batch_device(self._h, d_src, d_tgt, _p(offset), nb, C.byref(params), C.byref(sparams),
+                                                           d_pose, pose_stride, n_poses, d_pol, d_label, d_rounds or None))
 
     def hypothesize_device(self, d_src: int, d_tgt: int, n: int, params: ScParams, d_key: int):
         st = ScStats(C.sizeof(ScStats))
@@ -1518,50 +1484,45 @@ class Registrar:
     # ---- stage hooks -----------------------------------------------------------------------------------------
     def compat(self, src, tgt, params: ScParams, want_S=True):
         src, tgt = _f32c(src), _f32c(tgt)
-        n = src.shape[0] if params.layout == SC_AOS else src.shape[1]
+        n = _n_points(src, params.layout)
         W = (n + 63) // 64
         S = np.empty((n, n), np.float32) if want_S else None
         bits = np.zeros((n, W), np.uint64); deg = np.zeros(n, np.uint32)
-        self._check(self._lib.sc_compat_host(self._h, _p(src, C.c_float), _p(tgt, C.c_float), n, C.byref(params),
-                                             _p(S, C.c_float), _p(bits, C.c_uint64), _p(deg, C.c_uint32)))
+        self._check(self._lib.sc_compat_host(self._h, _p(src), _p(tgt), n, C.byref(params), _p(S), _p(bits), _p(deg)))
         return S, bits, deg
 
     def triangles(self, src, tgt, params: ScParams):
         src, tgt = _f32c(src), _f32c(tgt)
-        n = src.shape[0] if params.layout == SC_AOS else src.shape[1]
+        n = _n_points(src, params.layout)
         T = params.max_triangles
         tri = np.zeros((T, 3), np.uint32); key = np.zeros(T, np.uint32)
         t_eff = C.c_uint32(0); total = C.c_uint64(0); edges = C.c_uint64(0)
-        self._check(self._lib.sc_triangles_host(self._h, _p(src, C.c_float), _p(tgt, C.c_float), n, C.byref(params),
-                                                _p(tri, C.c_uint32), _p(key, C.c_uint32), C.byref(t_eff),
+        self._check(self._lib.sc_triangles_host(self._h, _p(src), _p(tgt), n, C.byref(params), _p(tri), _p(key), C.byref(t_eff),
                                                 C.byref(total), C.byref(edges)))
         return tri[: t_eff.value].copy(), key[: t_eff.value].copy(), int(total.value), int(edges.value)
 
     def kabsch(self, src, tgt, params: ScParams, tri):
         src, tgt = _f32c(src), _f32c(tgt)
-        n = src.shape[0] if params.layout == SC_AOS else src.shape[1]
+        n = _n_points(src, params.layout)
         tri = np.ascontiguousarray(tri, dtype=np.uint32)
         Rt = np.zeros((tri.shape[0], 12), np.float32)
-        self._check(self._lib.sc_kabsch_host(self._h, _p(src, C.c_float), _p(tgt, C.c_float), n, C.byref(params),
-                                             _p(tri, C.c_uint32), tri.shape[0], _p(Rt, C.c_float)))
+        self._check(self._lib.sc_kabsch_host(self._h, _p(src), _p(tgt), n, C.byref(params), _p(tri), tri.shape[0], _p(Rt)))
         return Rt
 
     def score(self, src, tgt, params: ScParams, Rt):
         src, tgt = _f32c(src), _f32c(tgt)
-        n = src.shape[0] if params.layout == SC_AOS else src.shape[1]
+        n = _n_points(src, params.layout)
         Rt = _f32c(Rt)
         cnt = np.zeros(Rt.shape[0], np.uint32); key = C.c_uint64(0)
-        self._check(self._lib.sc_score_host(self._h, _p(src, C.c_float), _p(tgt, C.c_float), n, C.byref(params),
-                                            _p(Rt, C.c_float), Rt.shape[0], _p(cnt, C.c_uint32), C.byref(key)))
+        self._check(self._lib.sc_score_host(self._h, _p(src), _p(tgt), n, C.byref(params), _p(Rt), Rt.shape[0], _p(cnt), C.byref(key)))
         return cnt, int(key.value)
 
     def mask(self, src, tgt, params: ScParams, Rt12):
         src, tgt = _f32c(src), _f32c(tgt)
-        n = src.shape[0] if params.layout == SC_AOS else src.shape[1]
+        n = _n_points(src, params.layout)
         Rt12 = _f32c(Rt12).reshape(12)
         m = np.zeros(n, np.uint8)
-        self._check(self._lib.sc_mask_host(self._h, _p(src, C.c_float), _p(tgt, C.c_float), n, C.byref(params),
-                                           _p(Rt12, C.c_float), _p(m, C.c_uint8)))
+        self._check(self._lib.sc_mask_host(self._h, _p(src), _p(tgt), n, C.byref(params), _p(Rt12), _p(m)))
         return m
 
 
@@ -1593,17 +1554,14 @@ class MultiRegistrar:
         except Exception:
             pass
 
-    def register(self, src, tgt, params: ScParams | None = None, **kw):
-        p = params or make_params(**kw)
-        src, tgt = _f32c(src), _f32c(tgt)
-        n = src.shape[0] if p.layout == SC_AOS else src.shape[1]
-        R = np.zeros(9, np.float32); t = np.zeros(3, np.float32); mask = np.zeros(n, np.uint8)
-        st = ScStats(C.sizeof(ScStats))
-        rc = self._lib.sc_register_multi(self._h, _p(src, C.c_float), _p(tgt, C.c_float), n, C.byref(p),
-                                         _p(R, C.c_float), _p(t, C.c_float), _p(mask, C.c_uint8), C.byref(st))
-        if rc not in (SC_OK, SC_ENOHYP):
+    def _check(self, rc: int, allow=()):
+        if rc != SC_OK and rc not in allow:
             raise SacCotError(rc, self._lib.sc_strerror(rc).decode() + " — " + self._lib.sc_multi_last_error(self._h).decode())
-        return dict(status=rc, R=R.reshape(3, 3), t=t, mask=mask, stats=st.as_dict())
+        return rc
+
+    def register(self, src, tgt, params: ScParams | None = None, **kw):
+        """Registrar.register over the handle's GPUs.  (The n it notes in _frame_n serves nothing here: sc_multi keeps no frame.)"""
+        return _register(self, self._lib.sc_register_multi, src, tgt, params, kw)
 
 
 def register(src, tgt, device: int = 0, **kw):
