@@ -49,6 +49,7 @@ extern "C" {
 #define SC_HAS_POLISH_POSES 1  /* this header declares sc_polish_poses* (added within 0.10) */
 #define SC_HAS_ASSIGN 1  /* this header declares sc_assign_poses* and sc_assign_default_params (added within 0.10) */
 #define SC_HAS_SETTLE 1  /* this header declares sc_settle_poses* and sc_settle_default_params (added within 0.10) */
+#define SC_HAS_MERGE 1  /* this header declares sc_merge_poses* and sc_merge_default_params (added within 0.10) */
 #define SC_HAS_MATCH_GUIDED 1  /* this header declares sc_match_guided*, sc_register_guided_features and sc_guide_default_params (added within 0.10) */
 #define SC_HAS_MATCH_GUIDED_POSES 1  /* this header declares sc_match_guided_poses*, sc_register_guided_poses_features and SC_GUIDE_MAX_POSES (added within 0.10) */
 #define SC_HAS_MATCH_GUIDED_BATCH 1  /* this header declares sc_match_guided_batch*, sc_match_guided_pairs* and sc_register_guided_{batch,pairs}_features_device (added within 0.10) */
@@ -1205,7 +1206,8 @@ int sc_polish_poses(sc_ctx* ctx, const sc_polish_poses_params* qp, const void* p
  * its position in the batch or on n_problems.  Like every batch entry it ends the frame a context may hold.  Refusals, workspace
  * (the copy of the offsets, the host form's device copies) and the offset staging wait are sc_pose_info_batch_device's.
  * Not here: slots and pairs forms; soft or weighted assignment; "relabel and refit until stable" (an entry of its own:
- * sc_settle_poses, below); a form for sharded frames, which leave no frame. */
+ * sc_settle_poses, below); merging or dropping poses (an entry of its own: sc_merge_poses, below); a form for sharded frames, which
+ * leave no frame. */
 #define SC_ASSIGN_MAX_POSES       1024u
 #define SC_ASSIGN_BATCH_MAX_POSES 64u
 #define SC_ASSIGN_BEST     0u   /* mode: the candidate with the smallest residual, ties to the lowest k */
@@ -1307,8 +1309,8 @@ int sc_assign_poses_batch(sc_ctx* ctx, const float* src, const float* tgt, const
  * allocates and runs nothing new.
  * The loop this closes, every step stream-ordered and none read back: sc_register_instances -> sc_polish_poses_device(SEL_ALIVE) ->
  * sc_settle_poses_frame_device -> sc_pose_info_frame_device(SEL_LABEL, d_label, stride 64).
- * Not here: merging or dropping poses (two copies of a pose split its inliers between them by the tie rule: the lower k takes the
- * ties, both stay in the list); soft assignment; slots and pairs forms; a form for sharded frames, which leave no frame. */
+ * Not here: merging or dropping poses (an entry of its own: sc_merge_poses, below) (two copies of a pose split its inliers between
+ * them by the tie rule: the lower k takes the ties, both stay in the list); soft assignment; slots and pairs forms; a form for sharded frames, which leave no frame. */
 #define SC_SETTLE_MAX_POSES       64u   /* frame form */
 #define SC_SETTLE_BATCH_MAX_POSES 16u   /* batch form: SC_INSTANCES_BATCH_MAX planes */
 #define SC_SETTLE_STATUS 1u             /* flags: a pose record holds an int32 status at byte 48 */
@@ -1336,6 +1338,130 @@ int sc_settle_poses_batch_device(sc_ctx* ctx, const float* d_src, const float* d
 int sc_settle_poses_batch(sc_ctx* ctx, const float* src, const float* tgt, const uint32_t* offset, uint32_t n_problems,
                           const sc_params* params, const sc_settle_params* sp, const void* pose, uint32_t pose_stride,
                           uint32_t n_poses, sc_polish_batch_result* pol, int32_t* label, uint32_t* rounds);
+
+/* ---- duplicate poses found and folded: sc_merge_poses ----------------------------------------------------------------
+ * A round of sc_peel scores over what the winner before left alive, so the next "motion" is often the same motion again, found on its
+ * borderline correspondences; a pose a caller brings along (the previous frame's, an odometry prior) usually duplicates a motion of
+ * the frame.  sc_settle_poses keeps both copies and splits the motion's inliers between them, and sc_pose_info_frame then sees two
+ * weak edges where there is one strong edge.  "Are these two the same motion?" needs every pose's support set over all n
+ * correspondences and the K x K table of their intersections: these entries build both ON THE DEVICE, decide there, and read nothing
+ * back.  Two forms: on a scored frame (three launches behind one memset: sc_merge_frame.hip) and on a packed batch (ONE launch, a
+ * workgroup per problem: sc_merge_batch.hip).
+ *
+ * Definitions, shared by both forms.  The pose records, valid(k), d2_k(m), part(m) and cand(k, m) are sc_assign_poses's, word for
+ * word: float Rt[12] at byte 0 and, where a status is read (SC_MERGE_STATUS; the batch form always), an int32 at byte 48; read, never
+ * written; 4-byte aligned.  An invalid pose is found on the device and does not fail the call.
+ *   support     I_k = {m : cand(k, m)}: pose k's OWN inlier set — not an exclusive label: the sets of different poses overlap, and that
+ *               is the point.  c_k = |I_k|.  s_k = the sum over I_k of the frame's (params->) score_mode term of pose k, as a uint32:
+ *               the score0 sc_polish_poses reports for that pose under the same selection.  x_jk = |I_j & I_k|.
+ *   strength    larger s_k first, ties to the lower k.
+ *   same(j, k)  x_jk >= 1 and, in 64-bit unsigned integer arithmetic, SC_MERGE_OVER_MIN: x_jk * den >= num * min(c_j, c_k);
+ *               SC_MERGE_OVER_UNION (Jaccard): x_jk * den >= num * (c_j + c_k - x_jk).  1 <= num <= den <= 65536.  No floating point
+ *               enters the decision.
+ *   the fold    greedy, the poses visited in strength order.  An invalid pose is out: parent -1.  A valid pose with c_k < min_count is
+ *               dropped: parent -1.  Otherwise, if some pose j that is already kept has same(j, k), k is FOLDED into the strongest such
+ *               j: parent[k] = j.  Otherwise k is KEPT: parent[k] = k.  Nothing is refitted: a kept pose keeps its input bits;
+ *               sc_settle_poses or sc_polish_poses on the output does the refit over the united support.
+ *   record      sc_merge_pose, 64 bytes, by the pose's fate:
+ *                 kept     Rt = the input's bits, status SC_OK,     index = k,          count = c_k, score = s_k
+ *                 folded   R = I, t = 0,          status SC_ENOHYP, index = its parent, count = c_k, score = s_k
+ *                 dropped  R = I, t = 0,          status SC_ENOHYP, index = -1,         count = c_k, score = s_k
+ *                 invalid  R = I, t = 0,          the status passed through, or SC_EINVAL for a non-finite Rt, index = -1, 0, 0
+ *               The record is itself a pose record — Rt at byte 0, the status at byte 48 — for sc_settle_poses_*, sc_assign_poses_*,
+ *               sc_polish_poses_device, sc_pose_info_frame_device and this entry again, read at stride 64 with their status flag: the
+ *               dead records claim nothing.
+ *   placement   without SC_MERGE_COMPACT the record of pose k sits at position k, so labels written by later entries keep the caller's
+ *               pose numbers.  With it the list is stably partitioned: the kept poses first, in ascending k, then the others, in
+ *               ascending k.  Either way there are n_poses records: a host-free caller passes the same n_poses on; one who waits
+ *               reads the kept count and passes that on.
+ *   d_parent    n_poses int32, by pose number (whatever the placement).
+ *   d_count     two words (NULL: not wanted): [0] the kept poses, [1] the valid poses.  The batch form: two words per problem.
+ *   d_overlap   the frame form only; NULL: not wanted.  n_poses x n_poses uint32, x_jk: symmetric, the diagonal is c_k, the rows and
+ *               columns of invalid poses are 0.
+ *   Every output is a function of the points, the poses in their order, the selection, tau, score_mode and sc_merge_params only, bit
+ *   for bit: not of the launch geometry, the context's history, how the frame was enqueued, or (batch) a problem's position or
+ *   n_problems.  Every sum is a sum of integers.
+ * What the header promises, each bit for bit:
+ *   (1) score[k] is sc_polish_poses's score0[k] under the same selection, in all three score modes; count[k] = #{m : part(m) and
+ *       d2_k(m) < tau^2}.
+ *   (2) a bit-identical copy of a valid pose with c_k >= 1 is folded into its lowest-numbered original (or that original's parent),
+ *       for every num / den and either measure: it is never kept beside it.
+ *   (3) the kept records, fed in again (stride 64, SC_MERGE_STATUS, the same parameters), are all kept again: d_count[0] and their
+ *       bytes are unchanged.
+ *   (4) a batch problem's outputs are the frame form's on that problem alone.
+ *   (5) with num == den and SC_MERGE_OVER_MIN, k is folded into a kept j exactly when one support set contains the other.
+ *
+ * The frame form.  A FRAME is as defined for sc_peel.  The entries read the frame's staged points, its n, tau and score_mode, change
+ * nothing in it and do NOT end it: they may be repeated and interleaved with sc_peel, sc_polish*, sc_pose_info_frame,
+ * sc_assign_poses_frame and sc_settle_poses_frame.  Correspondences are in the caller's ORIGINAL indexing.  sel_mode
+ * SC_ASSIGN_SEL_NONE or SC_ASSIGN_SEL_MASK (d_sel: n bytes).  pose_stride is a multiple of 4 and at least 48, at least 52 with
+ * SC_MERGE_STATUS; 1 <= n_poses <= SC_MERGE_MAX_POSES.  The device form enqueues a fixed number of stream operations whatever n and
+ * n_poses are — one memset (the tally words) and three launches: support, overlap, decide — reads no host word and returns without
+ * waiting; the host form copies in, enqueues, copies out and waits.
+ * The batch form, packed only.  The problems of sc_register_batch (offset a HOST array, params->layout, 3 <= n_b <= SC_BATCH_MAX_N);
+ * the poses, the records and d_parent motion-major as sc_assign_poses_batch has them (pose k of problem b at (k * n_problems + b));
+ * with SC_MERGE_COMPACT position p of problem b is record p * n_problems + b.  The status at byte 48 is always read (pose_stride at
+ * least 52); 1 <= n_poses <= SC_MERGE_BATCH_MAX_POSES; sel_mode must be SC_ASSIGN_SEL_NONE.  A problem holding a non-finite
+ * coordinate gets SC_EINVAL in every record (R = I, t = 0, index -1, 0, 0), parent -1 and the count words 0, 0; its neighbours are
+ * untouched.  Like every batch entry it ends the frame a context may hold.  params is checked as sc_register_batch checks it; only
+ * tau, score_mode and layout are read.
+ * Errors: the CALL returns SC_EINVAL, decided on the host before anything is enqueued, sc_last_error naming which: a NULL argument
+ * (a NULL ctx: no text; d_overlap and d_count may be NULL); mp->size wrong; a measure above 1; num or den outside 1 <= num <= den <=
+ * 65536; sel_mode above 1 (batch: not 0); d_sel NULL with SC_ASSIGN_SEL_MASK; an unknown flag or a non-zero reserved word; n_poses 0
+ * or above the form's maximum; a pose_stride that breaks the rule; no frame on the context (sc_peel's refusal, with its text); a
+ * call outstanding on the context; the batch form's offsets and params as sc_assign_poses_batch refuses them.  A refused call leaves
+ * the frame.
+ * Workspace: the frame form keeps the support sets as bit rows, n_poses x ceil(n / 64) uint64, the tally words, and the overlap table
+ * where the caller passes none; the batch form the copy of the offsets; the host forms device copies of their arrays.  Everything is
+ * allocated by the first such call, counted in workspace_bytes and held against the cap (SC_ENOMEM, nothing enqueued, the frame
+ * stays).  A context that never calls these entries allocates and runs nothing new.
+ * The loop this closes, every step stream-ordered and none read back: sc_register_instances -> sc_polish_poses_device(SEL_ALIVE) ->
+ * sc_merge_poses_frame_device -> sc_settle_poses_frame_device(stride 64, SC_SETTLE_STATUS) -> sc_pose_info_frame_device(SEL_LABEL)
+ * (INTEGRATION.md).
+ * Not here: a refit of the kept poses (sc_settle_poses and sc_polish_poses do it); a relabelled label output (sc_assign_poses and
+ * sc_settle_poses write it); merging by pose distance (angle, translation) rather than by support; slots and pairs forms; a form for
+ * sharded frames, which leave no frame. */
+#define SC_MERGE_MAX_POSES       1024u  /* frame form */
+#define SC_MERGE_BATCH_MAX_POSES 64u    /* batch form */
+#define SC_MERGE_OVER_MIN   0u          /* measure: the intersection over the smaller support */
+#define SC_MERGE_OVER_UNION 1u          /* measure: the intersection over the union (Jaccard) */
+#define SC_MERGE_STATUS  1u             /* flags: a pose record holds an int32 status at byte 48 */
+#define SC_MERGE_COMPACT 2u             /* flags: the kept records first, then the others, each in ascending k */
+typedef struct sc_merge_params {   /* 32 bytes */
+  uint32_t size;         /* = sizeof(sc_merge_params)                       */
+  uint32_t measure;      /* SC_MERGE_OVER_MIN / _OVER_UNION                 */
+  uint32_t num;          /* the fraction num / den: 1 <= num <= den         */
+  uint32_t den;          /* ... <= 65536                                    */
+  uint32_t min_count;    /* a valid pose with fewer inliers is dropped      */
+  uint32_t sel_mode;     /* SC_ASSIGN_SEL_NONE / _MASK; batch: _NONE        */
+  uint32_t flags;        /* SC_MERGE_STATUS, SC_MERGE_COMPACT or 0          */
+  uint32_t reserved[1];  /* must be 0                                       */
+} sc_merge_params;
+typedef struct sc_merge_pose {     /* 64 bytes: a pose record, status at byte 48 */
+  float    Rt[12];       /* kept: the input's bits; else R = I, t = 0        */
+  int32_t  status;       /* SC_OK (kept), SC_ENOHYP (folded, dropped), or the invalid pose's status */
+  int32_t  index;        /* kept: k; folded: its parent; else -1             */
+  uint32_t count;        /* c_k (an invalid pose: 0)                         */
+  uint32_t score;        /* s_k (an invalid pose: 0)                         */
+} sc_merge_pose;
+int sc_merge_default_params(sc_merge_params* mp);   /* size set, SC_MERGE_OVER_MIN, 1 / 2, everything else 0 */
+/* d_pose: n_poses records of pose_stride bytes; d_sel per sel_mode (NULL with SEL_NONE); d_out: n_poses records; d_parent: n_poses
+ * int32; d_overlap: n_poses x n_poses uint32 or NULL; d_count: 2 words or NULL */
+int sc_merge_poses_frame_device(sc_ctx* ctx, const sc_merge_params* mp, const void* d_pose, uint32_t pose_stride, uint32_t n_poses,
+                                const uint8_t* d_sel, sc_merge_pose* d_out, int32_t* d_parent, uint32_t* d_overlap, uint32_t* d_count);
+/* the same with host arrays (pose, sel, out, parent, overlap, count); waits */
+int sc_merge_poses_frame(sc_ctx* ctx, const sc_merge_params* mp, const void* pose, uint32_t pose_stride, uint32_t n_poses,
+                         const uint8_t* sel, sc_merge_pose* out, int32_t* parent, uint32_t* overlap, uint32_t* count);
+/* every buffer but offset in HBM: d_src / d_tgt total x 3 floats, d_pose n_poses x n_problems records of pose_stride bytes
+ * (motion-major), d_out n_poses x n_problems records (motion-major), d_parent n_poses x n_problems int32 (motion-major), d_count
+ * 2 x n_problems words or NULL */
+int sc_merge_poses_batch_device(sc_ctx* ctx, const float* d_src, const float* d_tgt, const uint32_t* offset, uint32_t n_problems,
+                                const sc_params* params, const sc_merge_params* mp, const void* d_pose, uint32_t pose_stride,
+                                uint32_t n_poses, sc_merge_pose* d_out, int32_t* d_parent, uint32_t* d_count);
+/* the same with host arrays; waits */
+int sc_merge_poses_batch(sc_ctx* ctx, const float* src, const float* tgt, const uint32_t* offset, uint32_t n_problems,
+                         const sc_params* params, const sc_merge_params* mp, const void* pose, uint32_t pose_stride,
+                         uint32_t n_poses, sc_merge_pose* out, int32_t* parent, uint32_t* count);
 
 /* ---- two-phase form for one-process-per-GPU sharding --------------------------------
  * Phase 1: A and B replicated, C1+C2 on this rank's blocks of the top-T list; writes this rank's winner key

@@ -173,6 +173,26 @@ class ScSettleParams(C.Structure):
 
 SC_SETTLE_MAX_POSES, SC_SETTLE_BATCH_MAX_POSES = 64, 16
 SC_SETTLE_STATUS = 1
+
+
+class ScMergeParams(C.Structure):
+    """Mirror of `sc_merge_params` (include/saccot.h), 32 bytes: the measure (SC_MERGE_OVER_*), the fraction num / den (1 <= num <= den
+    <= 65536), the inlier count below which a valid pose is dropped, which correspondences take part (SC_ASSIGN_SEL_*),
+    SC_MERGE_STATUS | SC_MERGE_COMPACT or 0."""
+    _fields_ = [("size", C.c_uint32), ("measure", C.c_uint32), ("num", C.c_uint32), ("den", C.c_uint32), ("min_count", C.c_uint32),
+                ("sel_mode", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 1)]
+
+
+class ScMergePose(C.Structure):
+    """Mirror of `sc_merge_pose` (include/saccot.h), 64 bytes: one pose's record of sc_merge_poses — itself a pose record, the status
+    at byte 48."""
+    _fields_ = [("Rt", C.c_float * 12), ("status", C.c_int32), ("index", C.c_int32), ("count", C.c_uint32), ("score", C.c_uint32)]
+
+
+MERGE_POSE_DTYPE = np.dtype(ScMergePose)  # sc_merge_pose as a numpy record
+SC_MERGE_MAX_POSES, SC_MERGE_BATCH_MAX_POSES = 1024, 64
+SC_MERGE_OVER_MIN, SC_MERGE_OVER_UNION = 0, 1
+SC_MERGE_STATUS, SC_MERGE_COMPACT = 1, 2
 SC_GUIDE_POSE_STATUS = 1  # sc_guide_params.flags, the sc_match_guided_batch / _poses entries only: the pose records hold an int32 status at byte 48
 SC_GUIDE_MAX_POSES = 64  # pose records per call of sc_match_guided_poses at most
 SC_MATCH_BATCH_MAX_N = 4096  # rows a side of one problem of sc_match_batch
@@ -237,7 +257,7 @@ class SacCotError(RuntimeError):
 _INT, _I64, _U32, _VP = C.c_int, C.c_int64, C.c_uint32, C.c_void_p
 _F32P, _U8P, _I32P, _U32P, _U64P = (C.POINTER(t) for t in (C.c_float, C.c_uint8, C.c_int32, C.c_uint32, C.c_uint64))
 _PP, _SP, _QP, _MP, _GP = (C.POINTER(t) for t in (ScParams, ScStats, ScPolishParams, ScMatchParams, ScGuideParams))
-_IP, _ZP, _AP, _TP = (C.POINTER(t) for t in (ScPoseInfoParams, ScPolishPosesParams, ScAssignParams, ScSettleParams))
+_IP, _ZP, _AP, _TP, _RP = (C.POINTER(t) for t in (ScPoseInfoParams, ScPolishPosesParams, ScAssignParams, ScSettleParams, ScMergeParams))
 _PROTOTYPES = {
     "sc_version": [],
     "sc_strerror": ([_INT], C.c_char_p),
@@ -318,6 +338,11 @@ _PROTOTYPES = {
     "sc_settle_poses_frame_device": [_VP, _TP, _VP, _U32, _U32, _VP, _VP, _VP, _VP, _VP],
     "sc_settle_poses_batch": [_VP, _F32P, _F32P, _U32P, _U32, _PP, _TP, _VP, _U32, _U32, _VP, _VP, _VP],
     "sc_settle_poses_batch_device": [_VP, _VP, _VP, _U32P, _U32, _PP, _TP, _VP, _U32, _U32, _VP, _VP, _VP],
+    "sc_merge_default_params": [_RP],
+    "sc_merge_poses_frame": [_VP, _RP, _VP, _U32, _U32, _VP, _VP, _VP, _VP, _VP],
+    "sc_merge_poses_frame_device": [_VP, _RP, _VP, _U32, _U32, _VP, _VP, _VP, _VP, _VP],
+    "sc_merge_poses_batch": [_VP, _F32P, _F32P, _U32P, _U32, _PP, _RP, _VP, _U32, _U32, _VP, _VP, _VP],
+    "sc_merge_poses_batch_device": [_VP, _VP, _VP, _U32P, _U32, _PP, _RP, _VP, _U32, _U32, _VP, _VP, _VP],
     "sc_hypothesize_device": [_VP, _VP, _VP, _I64, _PP, _VP, _SP],
     "sc_finalize_device": [_VP, _VP, _VP, _VP, _SP],
     "sc_hypothesize_begin_device": [_VP, _VP, _VP, _I64, _PP, _VP, _SP],
@@ -416,6 +441,13 @@ def make_assign_params(mode: int = SC_ASSIGN_BEST, sel_mode: int = SC_ASSIGN_SEL
 def make_settle_params(max_iter: int = 16, sel_mode: int = SC_ASSIGN_SEL_NONE, flags: int = 0) -> ScSettleParams:
     """sc_settle_params: max_iter 1 .. 64 counted rounds, sel_mode SC_ASSIGN_SEL_*, flags SC_SETTLE_STATUS or 0."""
     return _sized(ScSettleParams, max_iter, sel_mode, flags)
+
+
+def make_merge_params(measure: int = SC_MERGE_OVER_MIN, num: int = 1, den: int = 2, min_count: int = 0, sel_mode: int = SC_ASSIGN_SEL_NONE,
+                      flags: int = 0) -> ScMergeParams:
+    """sc_merge_params: measure SC_MERGE_OVER_*, the fraction num / den (1 <= num <= den <= 65536), min_count, sel_mode
+    SC_ASSIGN_SEL_*, flags SC_MERGE_STATUS | SC_MERGE_COMPACT or 0."""
+    return _sized(ScMergeParams, measure, num, den, min_count, sel_mode, flags)
 
 
 def shard_plan(params: ScParams, n: int) -> ScShardPlan:
@@ -1427,6 +1459,64 @@ class Registrar:
         self._frame_n = 0
         self._check(self._lib.sc_settle_poses_batch_device(self._h, d_src, d_tgt, _p(offset), nb, C.byref(params), C.byref(sparams),
                                                            d_pose, pose_stride, n_poses, d_pol, d_label, d_rounds or None))
+
+    # ---- duplicate poses found and folded (include/saccot.h, sc_merge_poses) ---------------------------------------------------
+    def merge_poses_frame(self, pose, mparams: ScMergeParams | None = None, sel=None, want_overlap: bool = True, want_count: bool = True,
+                          **kw):
+        """sc_merge_poses_frame: pose (K,) records of any dtype whose items start with float Rt[12] (and, with SC_MERGE_STATUS, an
+        int32 status behind it) — or a float32 array (K, 12) / (12,) —; sel None or (n,) uint8 (SC_ASSIGN_SEL_MASK), read only ->
+        (records (K,) of MERGE_POSE_DTYPE, parent (K,) int32, overlap (K, K) uint32 or None, count (2,) uint32 — the kept poses, the
+        valid poses — or None).  The frame stays.  kw: measure, num, den, min_count, sel_mode, flags (make_merge_params)."""
+        q = mparams or make_merge_params(**kw)
+        pose, stride = self._pose_records(pose)
+        k, n = len(pose), self._frame_n
+        sel = _frame_sel("merge_poses_frame", sel, np.uint8, n)
+        out = np.zeros(max(k, 1), MERGE_POSE_DTYPE)
+        parent = np.zeros(max(k, 1), np.int32)
+        overlap = np.zeros((max(k, 1), max(k, 1)), np.uint32) if want_overlap else None
+        count = np.zeros(2, np.uint32) if want_count else None
+        self._check(self._lib.sc_merge_poses_frame(self._h, C.byref(q), _vp(pose), stride, k, _vp(sel), _vp(out), _vp(parent), _vp(overlap),
+                                                   _vp(count)))
+        return out[:k], parent[:k], (None if overlap is None else overlap[:k, :k]), count
+
+    def merge_poses_frame_device(self, mparams: ScMergeParams, d_pose: int, pose_stride: int, n_poses: int, d_sel: int, d_out: int,
+                                 d_parent: int, d_overlap: int = 0, d_count: int = 0):
+        """sc_merge_poses_frame_device: pose records (pose_stride bytes each, read only), the selection (0: none), the output records
+        (64 bytes each), the parents (n_poses int32), the overlap table (n_poses x n_poses uint32; 0: none) and the two count words
+        (0: none) in HBM; enqueues one memset and three launches on the context's stream and returns without waiting.  The frame
+        stays."""
+        self._check(self._lib.sc_merge_poses_frame_device(self._h, C.byref(mparams), d_pose, pose_stride, n_poses, d_sel or None, d_out,
+                                                          d_parent, d_overlap or None, d_count or None))
+
+    def merge_poses_batch(self, src, tgt, offset, params: ScParams, pose, mparams: ScMergeParams | None = None, **kw):
+        """sc_merge_poses_batch on packed arrays: src / tgt / offset as register_batch_raw's; pose (K, B) records, motion-major, of any
+        dtype whose items start with float Rt[12] and int32 status — register_instances_batch_raw's records — read only ->
+        (records (K, B) of MERGE_POSE_DTYPE, parent (K, B) int32, count (B, 2) uint32).  kw: measure, num, den, min_count, flags
+        (make_merge_params)."""
+        q = mparams or make_merge_params(**kw)
+        src, tgt = _f32c(src), _f32c(tgt)
+        offset, nb = _u32c(offset)
+        pose = np.ascontiguousarray(pose)
+        if pose.ndim != 2 or pose.shape[1] != nb:
+            raise ValueError("merge_poses_batch: pose holds (n_poses, n_problems) records")
+        k = pose.shape[0]
+        out = np.zeros((max(k, 1), max(nb, 1)), MERGE_POSE_DTYPE)
+        parent = np.zeros((max(k, 1), max(nb, 1)), np.int32)
+        count = np.zeros((max(nb, 1), 2), np.uint32)
+        self._frame_n = 0
+        self._check(self._lib.sc_merge_poses_batch(self._h, _p(src), _p(tgt), _p(offset), nb, C.byref(params), C.byref(q), _vp(pose),
+                                                   pose.dtype.itemsize, k, _vp(out), _vp(parent), _vp(count)))
+        return out[:k, :nb], parent[:k, :nb], count[:nb]
+
+    def merge_poses_batch_device(self, d_src: int, d_tgt: int, offset, params: ScParams, mparams: ScMergeParams, d_pose: int,
+                                 pose_stride: int, n_poses: int, d_out: int, d_parent: int, d_count: int = 0):
+        """sc_merge_poses_batch_device: points, pose records (n_poses x B of pose_stride bytes, motion-major, read only), output
+        records (n_poses x B of 64 bytes, motion-major), parents (n_poses x B int32, motion-major) and the word pairs (2 x B; 0: none)
+        in HBM, offset a HOST array (B + 1,) uint32; enqueues ONE launch on the context's stream and returns without waiting."""
+        offset, nb = _u32c(offset)
+        self._frame_n = 0
+        self._check(self._lib.sc_merge_poses_batch_device(self._h, d_src, d_tgt, _p(offset), nb, C.byref(params), C.byref(mparams),
+                                                          d_pose, pose_stride, n_poses, d_out, d_parent, d_count or None))
 
     def hypothesize_device(self, d_src: int, d_tgt: int, n: int, params: ScParams, d_key: int):
         st = ScStats(C.sizeof(ScStats))

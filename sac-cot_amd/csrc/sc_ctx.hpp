@@ -150,7 +150,11 @@ struct Workspace {
       // sc_settle_poses: allocated by the first such call, never by a frame or by another entry.  The frame form's member bits and
       // chunk sums live in ppose_tmp — sc_polish_poses's buffer, one layout (sc_chunks.hpp): the calls are stream-ordered, so one serves both.
       // off: the batch form's copy of the caller's offsets; the rest: device copies of the host entries' arrays
-      stl_off, stl_src, stl_tgt, stl_pose, stl_sel, stl_out, stl_label, stl_d2, stl_rounds;
+      stl_off, stl_src, stl_tgt, stl_pose, stl_sel, stl_out, stl_label, stl_d2, stl_rounds,
+      // sc_merge_poses: allocated by the first such call, never by a frame or by another entry.  rows: the frame form's support sets,
+      // n_poses x ceil(n / 64) u64, and behind them the 2 x n_poses tally words; table: the overlap table where the caller passes none;
+      // off: the batch form's copy of the caller's offsets; the rest: device copies of the host entries' arrays
+      mrg_rows, mrg_table, mrg_off, mrg_src, mrg_tgt, mrg_pose, mrg_sel, mrg_out, mrg_parent, mrg_overlap, mrg_count;
 };
 constexpr size_t N_WORKSPACE_BUFS = sizeof(Workspace) / sizeof(Buf);
 static_assert(std::is_standard_layout<Workspace>::value && alignof(Workspace) == alignof(Buf) && sizeof(Workspace) == N_WORKSPACE_BUFS * sizeof(Buf),

@@ -997,6 +997,45 @@ struct SettleBatchJob : PoseBatchHead {
 // ONE launch, a workgroup per problem; every label of a problem's range, every record and word pair is written.
 void launch_settle_batch(const SettleBatchJob& job, hipStream_t st);
 
+// ---- duplicate poses found and folded (sc_merge_poses; sc_merge.hpp, sc_merge_frame.hip, sc_merge_batch.hip) -----------------
+// One pose's record: sc_merge_pose of include/saccot.h, field for field (sc_merge_frame.hip asserts the size and the offsets).
+struct MergeRecord {
+  float Rt[12];
+  int32_t status, index;
+  uint32_t count, score;
+};
+// What both forms read of sc_merge_params.
+struct MergeRule {
+  uint32_t measure, num, den, min_count;
+  int compact;
+};
+// The frame form.  sel: nullptr or n bytes.  rows: n_poses x merge_row_words(n) u64, every word written by the support launch.
+// tally: 2 x n_poses words — the counts, then the scores —, ZERO at launch (the workgroups of the support launch add into them).
+// overlap: n_poses x n_poses words, the caller's or the workspace's.  out, parent: n_poses; count: two words or nullptr.
+struct MergeFrameJob : PoseFrameHead {
+  const uint8_t* sel;
+  MergeRule rule;
+  uint64_t* rows;
+  uint32_t* tally;
+  uint32_t* overlap;
+  MergeRecord* out;
+  int32_t* parent;
+  uint32_t* count;
+};
+__host__ __device__ inline size_t merge_row_words(int n) { return ((size_t)n + 63) / 64; }
+// THREE launches: support (a workgroup per tile of MERGE_TILE correspondences: the bit rows and the tallies), overlap (a workgroup
+// per tile of pose pairs j <= k: the table, mirrored), decide (ONE workgroup: the strength order, the fold, every output).
+void launch_merge_frame(const MergeFrameJob& job, hipStream_t st);
+// The batch form.  out, parent: n_poses x n_problems, motion-major; count: two words per problem or nullptr.
+struct MergeBatchJob : PoseBatchHead {
+  MergeRule rule;
+  MergeRecord* out;
+  int32_t* parent;
+  uint32_t* count;
+};
+// ONE launch, a workgroup per problem; every record, parent and word pair is written (complete in stream order).
+void launch_merge_batch(const MergeBatchJob& job, hipStream_t st);
+
 // ---- descriptor matching for a batch of small problems (sc_match_batch; sc_match_batch.hip) -----------------
 // Problem b owns rows [src_off[b], src_off[b + 1]) of fsrc and [tgt_off[b], tgt_off[b + 1]) of ftgt (1 .. MATCH_BATCH_MAX_N rows
 // each, checked by the caller) and the output slot that starts at entry slot[b] = src_off[b] * knn.  tile_map: n_tiles pairs
