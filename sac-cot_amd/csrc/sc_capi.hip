@@ -1,5 +1,6 @@
 // sc_capi.hip — the core of the C ABI of include/saccot.h: the context's lifetime and its grow-only device workspace, sc_set_debug /
-// sc_debug_last, pass and frame, every run_* stage sequencer, and the register, hypothesize, finalize, shard and wait entries.  The
+// sc_debug_last, pass and frame, the stage sequencers of stages A and C, the lane, and the register, hypothesize, finalize, shard and
+// wait entries.  Stage B's sequencer (run_edges, run_select, the host-free plan) is sc_capi_tri.hip.  The
 // rest of the ABI sits in host-only files of its own, on sc_ctx.hpp (sc_ctx itself and the shared helpers): sc_capi_hooks.hip (the
 // sc_*_host stage hooks), sc_capi_peel.hip (sc_peel*, sc_register_instances), sc_capi_match.hip (sc_match*, sc_register_features), sc_capi_polish.hip (sc_polish*),
 // sc_capi_batch.hip (sc_register_batch*).
@@ -63,44 +64,6 @@ int ensure_room(sc_ctx* c, Buf& b, size_t need, size_t room) {
   }
   return ensure(c, b, need);
 }
-// what a host-free repetition of a call's shape is sized to cover (fast_plan): the last count plus half, and the largest count of
-// the shape's recent calls plus a quarter (sc_ctx::E_hi / M_hi)
-// While the shape is young on this context (fewer than HI_YOUNG of its calls seen) the last count is doubled instead: the first
-// frames of a stream say little about the spread of the frames to come, and a miss costs a whole repeated call (bench.py's
-// stream, frames of 386 k .. 697 k edges: with "plus half" from the first frame on, one of the first twenty was repeated).
-static uint64_t cover_of(uint64_t last, const uint64_t hi[2], bool young) {
-  const uint64_t h = hi[0] > hi[1] ? hi[0] : hi[1];
-  const uint64_t b = h + h / 4;
-  // young: twice the last count (or the window's maximum plus a quarter, if larger); later the window alone decides — the last
-  // count is in it — so that a stream's covers stay put from frame to frame instead of following every large frame by half
-  // (a cover beyond 2^20 edges takes the scan's two-launch form, and every launch sized by it grows with it)
-  const uint64_t a = young ? 2 * last : (h ? 0 : last + last / 2);
-  return (a > b ? a : b) + 4096;
-}
-
-// entries the edge arrays hold (what fast_plan caps a host-free call's edge cover by)
-static uint64_t edge_capacity(const sc_ctx* c, bool build) {
-  uint64_t cap = c->es.cap / 4 >= 2 ? c->es.cap / 4 - 2 : 0;  // es carries two pad entries
-  for (const Buf* b : {&c->ei, &c->ej}) cap = b->cap / 4 < cap ? b->cap / 4 : cap;
-  if (!build) for (const Buf* b : {&c->ebi, &c->ebj}) cap = b->cap / 4 < cap ? b->cap / 4 : cap;
-  return cap;
-}
-// the parameters that make two calls "the same shape" (a host-free call repeats the last call's; timing flags aside)
-static bool same_shape(const sc_params* p, const sc_params* q) {
-  constexpr uint32_t TIMING_BITS = SC_FLAG_TIMING | SC_FLAG_TIMING_HOT | SC_FLAG_TIMING_ONE | (15u << 8);
-  return p->sigma == q->sigma && p->t_cmp == q->t_cmp && p->tau == q->tau && p->min_len == q->min_len &&
-         p->max_triangles == q->max_triangles && p->rank_mode == q->rank_mode && p->layout == q->layout &&
-         p->shard_world == q->shard_world && p->shard_rank == q->shard_rank && p->shard_block == q->shard_block &&
-         p->score_mode == q->score_mode && (p->flags & ~TIMING_BITS) == (q->flags & ~TIMING_BITS);
-}
-// entries a waited call leaves in an array indexed by one of stage B's two counts: what the host-free repetitions of its shape
-// will want to cover (the window's maxima only while the shape continues: note_completed empties it after a change)
-static uint64_t room_of(const sc_ctx* c, uint64_t count, const uint64_t hi[2]) {
-  static const uint64_t none[2] = {0, 0};
-  const bool continues = c->pass.n == c->last_n && same_shape(&c->pass.params, &c->last_p);
-  return cover_of(count, continues ? hi : none, !continues || c->hi_seen < sc_ctx::HI_YOUNG);
-}
-
 int check_params(const sc_params* p) {
   if (!p || p->size != sizeof(sc_params)) return SC_EINVAL;
   if (!(p->sigma > 0.f) || !(p->t_cmp > 0.f) || !(p->t_cmp < 1.f) || !(p->tau > 0.f) || !(p->min_len >= 0.f))
@@ -127,24 +90,8 @@ Derived derive(const sc_params* p) {
   return d;
 }
 
-// The smallest key a triangle can have in weight ranking: every edge has s >= t_cmp up to rounding (0.1 % slack), so w >= ~3 t_cmp — what
-// the select's a-priori window and the pruning samples' floors rest on.  NOT when -1 / (2 sigma^2) overflowed fp32 (sigma below 2^-64.5 =
-// 3.8e-20): (d * d) * -inf is -inf or NaN, sc_expf clamps both to its floor, every weight is e^-87 and nothing bounds the keys from below
-// (tests/test_gpu_range.py: the select then returned keys of its window, [2, 3], that no triangle has).
-static float key_floor(const sc_params* p) {
-  const float nis = (float)(-1.0 / (2.0 * (double)p->sigma * (double)p->sigma));  // derive()'s neg_inv2sig2
-  return std::isfinite(nis) ? 3.0f * p->t_cmp * 0.999f : 0.0f;
-}
-// ... and whether that floor puts every key into the a-priori window [2, 3]: what the select, the estimating sample, the fused edge
-// kernel and the host-free form all go by — one answer for all of them
-static bool window_known(const sc_params* p) { return p->rank_mode == SC_RANK_WEIGHT && key_floor(p) >= 2.0f; }
-
 static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
-static Graph graph_of(const sc_ctx* c) {
-  return Graph{c->pass.bits_cur, c->S.as<float>(), c->deg.as<uint32_t>(), c->degp.as<uint32_t>(),
-               c->wpre.as<uint32_t>(), c->pass.n, c->pass.ld, c->pass.ld >> 6};
-}
 // Look-back launches (single-pass scans, fused row kernel, fused compaction).  lb_state holds the tile descriptors and
 // is written by look-back kernels only: zeroed when new, when it grew, and when the 12-bit epoch wraps.  The TICKET and
 // error words live in a small buffer of their own (lb_ticket, zeroed once): a ticket inside the descriptor area would,
@@ -168,24 +115,12 @@ int lb_next(sc_ctx* c, size_t bytes, int slot, size_t desc_off, LbArgs* out) {
   return SC_OK;
 }
 
-// how many triangles stage B selects: T — or, when B is sharded, what one candidate blob holds (this rank's own best)
-static uint32_t select_want(const sc_ctx* c, const sc_params* p) {
-  if (!c->pass.sharded_ab) return p->max_triangles;
-  const uint32_t cap = (uint32_t)cand_cap(p->max_triangles, (uint32_t)p->shard_world, p->shard_cand_level);
-  return cap < p->max_triangles ? cap : p->max_triangles;
-}
-
-// sharded stage B: the device-side edge range [lo, hi) this rank enumerates (nullptr: every edge)
-static const uint64_t* own_range_of(const sc_ctx* c) {
-  return c->pass.sharded_ab ? c->ctl.as<ControlBlock>()->own_edge : nullptr;
-}
-
 static TriSource tri_source_of(const sc_ctx* c) {
   TriSource ts{c->sel_ord.as<uint64_t>(), c->kcol.as<uint2>(), c->ei.as<uint32_t>(), c->ej.as<uint32_t>(), nullptr, 0, 0, 0u, 0u, 0ull};
   if (c->pass.mode.host_free) { ts.lim_vertex = (uint32_t)c->pass.n; ts.lim_edge = (uint32_t)c->pass.mode.E_cov; ts.lim_ord = c->pass.mode.M_cov; }
   // an ESTIMATED pruning bound that turns out too high leaves a selection shorter than the T_eff the launches were sized for
   // (the call is then repeated): what lies beyond it in sel_ord must not be followed
-  else if (c->pass.est_active) { ts.lim_vertex = (uint32_t)c->pass.n; ts.lim_edge = (uint32_t)c->pass.E; ts.lim_ord = c->pass.M; }
+  else if (c->pass.form.est_active) { ts.lim_vertex = (uint32_t)c->pass.n; ts.lim_edge = (uint32_t)c->pass.E; ts.lim_ord = c->pass.M; }
   if (c->pass.sharded_ab && c->pass.cand_all) {  // the selection indexes the gathered candidate blobs
     const size_t cap = cand_cap(c->pass.params.max_triangles, (uint32_t)c->pass.params.shard_world, c->pass.params.shard_cand_level);
     ts.cand_recs = cand_blob(const_cast<void*>(c->pass.cand_all), cap).recs;
@@ -226,7 +161,6 @@ static int calibrate_events(sc_ctx* c) {
   c->ev_overhead_us = best < 1e8f ? best : 0.f;
   return SC_OK;
 }
-static bool fast_plan(const sc_ctx* c, int64_t n, const sc_params* p, PassMode* mode);
 
 // SC_FLAG_TIMING / _HOT / _ONE -> the context's timing state for this call
 static int set_timing(sc_ctx* c, const sc_params* p) {
@@ -262,12 +196,12 @@ int stage_inputs(sc_ctx* c, const float* d_src, const float* d_tgt, int64_t n, c
   }
   ENSURE(c, c->fx_part, stage_part_words(c->pass.ld) * 4);
   c->pinned[HW_COORD_MAX] = ~0ull;  // "maxima not known yet"
-  if (c->pass.build) ENSURE(c, c->degp, (size_t)c->pass.ld * sizeof(uint32_t));  // stage A accumulates deg+ there: cleared on the way
+  if (c->pass.form.build) ENSURE(c, c->degp, (size_t)c->pass.ld * sizeof(uint32_t));  // stage A accumulates deg+ there: cleared on the way
   launch_stage_points(d_src, d_tgt, c->pass.n, c->pass.ld, p->layout, c->planes.as<float>(),
                       reinterpret_cast<uint32_t*>(&c->pinned[HW_BAD_INPUT]), c->ctl.as<uint32_t>(),
                       (uint32_t)(sizeof(ControlBlock) / 4), c->fx_mx.as<uint32_t>(), c->fx_part.as<uint32_t>(),
                       c->pass.mode.host_free ? nullptr : c->fx_mx.as<uint32_t>() + FX_MX_WORDS, c->pass.mode.host_free ? nullptr : &c->pinned[HW_COORD_MAX], c->pass.mode.host_free ? nullptr : &c->pinned[HW_BOX], c->stream,  // (host-free: no ticket — stage A's launch reduces the rows, run_compat; finalize hands the words over, DeferredPub)
-                      c->pass.build ? c->degp.as<uint32_t>() : nullptr, c->pass.build ? (uint32_t)c->pass.ld : 0u);
+                      c->pass.form.build ? c->degp.as<uint32_t>() : nullptr, c->pass.form.build ? (uint32_t)c->pass.ld : 0u);
   return SC_OK;
 }
 
@@ -305,7 +239,7 @@ int run_compat(sc_ctx* c, bool dense) {
     map = slot->buf.as<uint32_t>(); map_len = slot->len;
   }
   launch_compat(points_of(c), c->pass.dv, dense ? c->S.as<float>() : nullptr, c->pass.bits_cur, 0, c->pass.n, c->tn, c->stream,
-                c->pass.build ? c->degp.as<uint32_t>() : nullptr, map, map_len, c->pass.mode.host_free ? c->fx_part.as<uint32_t>() : nullptr,
+                c->pass.form.build ? c->degp.as<uint32_t>() : nullptr, map, map_len, c->pass.mode.host_free ? c->fx_part.as<uint32_t>() : nullptr,
                 c->fx_mx.as<uint32_t>());
   return SC_OK;
 }
@@ -314,7 +248,7 @@ int run_compat(sc_ctx* c, bool dense) {
 // hot: the fused form (row statistics + CSR offsets + edge count in one launch; run_edges then launches no scan)
 int run_row_stats(sc_ctx* c, bool will_prune, bool hot) {
   c->pass.rows_fused = false;
-  if (hot && c->pass.build) {  // launch_edge_build (run_edges) does all of it
+  if (hot && c->pass.form.build) {  // launch_edge_build (run_edges) does all of it
     ENSURE(c, c->bits2, (size_t)c->pass.n * (c->pass.ld >> 6) * sizeof(uint64_t));
     return SC_OK;
   }
@@ -372,401 +306,6 @@ int wait_word(sc_ctx* c, HostWord idx) {
   std::atomic_thread_fence(std::memory_order_acquire);
   if (*w == PIN_PENDING) { c->last_error = "a kernel did not deliver its result"; return SC_EHIP; }
   return SC_OK;
-}
-
-// The hot path's fused form of row_stats_scan + edge_fill + the estimating sample (sc_tri.hip 1'): where the pruning bound
-// will be an estimate (the same conditions as sample_plan's in run_edges, minus what only the edge count decides) and the
-// bit rows are short enough for the kernel
-static bool edge_build_ok(const sc_ctx* c, const sc_params* p, int64_t n, bool may_estimate) {
-  return may_estimate && !c->est_failed && window_known(p) && may_prune(p) && !c->tn.no_events && !c->tn.no_estimate &&
-         c->tn.sample_mode == 0 && !c->tn.no_edge_build && !c->tn.rows_unfused && edge_build_fits((int)n) &&  // (stage C may be dealt over ranks: shard_world)
-         p->max_triangles != 0;
-}
-
-// Stage B, first half: CSR edge list and this process's share (`part` of `parts`) of the pruning sample, accumulated
-// into `hist` (256 u32 on the device, already zero; nullptr = the control block's own histogram).  Sets c->pass.E and the
-// decisions the second half needs.
-// the Gram filter's frame (sc_gramref.hpp): 512 bytes per context
-static int ensure_frame(sc_ctx* c) {
-  if (!c->fx_frame.p) {
-    ENSURE(c, c->fx_frame, gram_frame_bytes());
-    HIPCHK(c, hipMemsetAsync(c->fx_frame.p, 0, gram_frame_bytes(), c->stream));
-  }
-  return SC_OK;
-}
-
-static int run_edges(sc_ctx* c, const sc_params* p, uint32_t* hist, uint32_t part, uint32_t parts) {
-  const size_t n = c->pass.n;
-  hipStream_t st = c->stream;
-  c->pass.ref_cand_n = 0; c->pass.ref_done = false;
-  ENSURE(c, c->edge_off, (n + 1) * sizeof(uint64_t));
-  ENSURE(c, c->scan_tmp, scan_temp_bytes(n));
-  // read-back #1: the scan kernel itself writes the edge count to host-pinned memory (no copy kernel)
-  const bool build = c->pass.build && hist == nullptr && parts == 1;
-  if (c->pass.build && !build) { c->last_error = "internal: the fused edge kernel was chosen for a call that shares its sample"; return SC_EHIP; }
-  const bool fused = c->pass.rows_fused || build;
-  c->pass.rows_fused = false;
-  if (!fused || build) arm_word(c, HW_EDGES);
-  ENSURE(c, c->ebase, n * 4);
-  ScanExtra xe;  // the scan of deg+ also writes the per-row CSR bases edge_fill reads
-  xe.deg = c->deg.as<uint32_t>(); xe.degp = c->degp.as<uint32_t>(); xe.ebase = c->ebase.as<uint32_t>();
-  ScanExtra xc;  // (sharded) the scan of the row costs
-  if (!fused && scan_writes_ebase(n)) {  // tiled scans: the single-pass form, each on its own half of the state area
-    const size_t half = scan_temp_bytes(n);
-    SC_TRY(lb_next(c, 2 * half, 0, 0, &xe.lb));
-    if (c->pass.sharded_ab) SC_TRY(lb_next(c, 2 * half, 1, half, &xc.lb));  // (same size: the area stays)
-  }
-  if (c->pass.sharded_ab) {
-    // also the prefix of the per-row work estimate and, from it, this rank's contiguous row / edge range
-    ENSURE(c, c->cost_pre, (n + 1) * sizeof(uint64_t));
-    if (!fused)
-      launch_scan_u32_pair(c->degp.as<uint32_t>(), c->edge_off.as<uint64_t>(), c->rowcost.as<uint32_t>(),
-                           c->cost_pre.as<uint64_t>(), n, c->scan_tmp.p, c->tn, st, &c->pinned[HW_EDGES], &xe, &xc);
-    ControlBlock* ctl = c->ctl.as<ControlBlock>();
-    launch_shard_split(c->cost_pre.as<uint64_t>(), c->edge_off.as<uint64_t>(), c->pass.n, (uint32_t)p->shard_rank,
-                       (uint32_t)p->shard_world, ctl->own_row, ctl->own_edge, st);
-  } else if (!fused) {
-    launch_scan_u32(c->degp.as<uint32_t>(), n, c->edge_off.as<uint64_t>(), c->scan_tmp.p, c->tn, st, &c->pinned[HW_EDGES], &xe);
-  }
-  // While the host polls for the edge count, edge_fill already runs into the edge arrays this context holds from
-  // earlier calls (it needs no host-side count: one wave per row, offsets from the scan).  Writes beyond their
-  // capacity are dropped by the kernel; in that case, or on a first call, it runs (again) after the read-back.
-  const Graph g = graph_of(c);
-  const uint64_t spec_cap = edge_capacity(c, build);
-  // the weight histogram of the heaviest-edge pruning sample is collected by the same kernel (sc_debug.sample_mode = ...
-  // any: it costs edge_fill ~1 us and saves a launch whenever that sample is chosen)
-  uint32_t* es_hist = c->ctl.as<ControlBlock>()->es_hist;
-  auto fill_edges = [&](uint64_t cap) {
-    if (build) {
-      launch_edge_build(g, points_of(c), c->pass.dv, c->bits2.as<uint64_t>(), c->edge_off.as<uint64_t>(), c->ebase.as<uint32_t>(),
-                        c->ei.as<uint32_t>(), c->ej.as<uint32_t>(), c->es.as<float>(), cap, c->pass.mode.host_free ? nullptr : &c->pinned[HW_EDGES], st,
-                        c->pass.mode.host_free ? c->ctl.as<ControlBlock>()->live_edges : nullptr);
-      return;
-    }
-    launch_edge_fill(g, points_of(c), c->pass.dv, c->edge_off.as<uint64_t>(), c->ei.as<uint32_t>(), c->ej.as<uint32_t>(),
-                     c->es.as<float>(), c->ebase.as<uint32_t>(), fused || scan_writes_ebase(n), c->ebi.as<uint32_t>(),
-                     c->ebj.as<uint32_t>(), cap, es_hist, st);
-  };
-  if (spec_cap || build) fill_edges(spec_cap);  // (the fused kernel also makes the row statistics and the count itself)
-  // Host-free call (c->pass.mode.host_free; fast_plan() made sure E_cov <= spec_cap): no wait.  E is then what the launches and arrays
-  // COVER; the kernels below take the real count from edge_off[n] (E_dev) and the end of the call validates it.
-  const bool spec = c->pass.mode.host_free;
-  const uint64_t* E_dev = spec ? c->edge_off.as<uint64_t>() + n : nullptr;
-  if (!spec) {
-    SC_TRY(wait_word(c, HW_EDGES));
-    if ((uint32_t)c->pinned[HW_BAD_INPUT] != 0) { c->last_error = "non-finite input coordinate"; return SC_EINVAL; }
-  }
-  const uint64_t E = c->pass.E = spec ? c->pass.mode.E_cov : c->pinned[HW_EDGES];
-  c->pass.M = 0; c->pass.M_total = 0; c->pass.T_eff = 0; c->pass.pruned = false; c->pass.use_events = false; c->pass.have_total = false;
-  c->pass.est_active = false; c->pass.est_void = false; c->pass.plan = SamplePlan{false, 1u, p->max_triangles};
-  c->pinned[HW_SELECT_SHORT] = 0;  // "the select found fewer keys above the pruning bound than it promised" (select_round_kernel)
-  // an exchanged histogram is written on every path (zeros where no sample runs: the control block's copies are zero)
-  if (hist && (E == 0 || !(may_prune(p) && E >= 4096))) launch_hist_reduce(c->ctl.as<ControlBlock>()->prune_hist, hist, st);
-  if (E == 0) return SC_OK;
-  // edge ids, CSR bases and the strong list are u32 (include/saccot.h, limits): a graph beyond that is refused, not wrapped
-  if (E >= (1ull << 32)) { c->last_error = "the compatibility graph has 2^32 or more edges"; return SC_ETOOMANY; }
-  // (a waited call leaves room for what a host-free repetition of its shape will want to cover: fast_plan caps by these arrays)
-  const uint64_t E_room = spec ? E : room_of(c, E, c->E_hi);
-  const size_t edge_arrays_before[5] = {c->ei.cap, c->ej.cap, c->es.cap, c->ebi.cap, c->ebj.cap};
-  ENSURE_ROOM(c, c->ei, E * 4, E_room * 4);
-  ENSURE_ROOM(c, c->ej, E * 4, E_room * 4);
-  ENSURE_ROOM(c, c->es, (E + 2) * 4, (E_room + 2) * 4);  // +1: the 4-way unrolled gathers of idle slots may touch index E
-  if (!build) { ENSURE_ROOM(c, c->ebi, E * 4, E_room * 4); ENSURE_ROOM(c, c->ebj, E * 4, E_room * 4); }
-  // every other array indexed by the edge count gets room for whatever the edge arrays can hold — that is what fast_plan caps a
-  // host-free call's cover by, so no such call ever has to grow one of them (a re-allocation synchronises the stream: 0.35 ms in
-  // the middle of bench.py's stream, once per array and rise of the cover)
-  const uint64_t E_hold = spec ? E : edge_capacity(c, build);
-  ENSURE_ROOM(c, c->tcnt, E * 4, E_hold * 4);
-  ENSURE_ROOM(c, c->toff, (E + 1) * 8, (E_hold + 1) * 8);
-  ENSURE_ROOM(c, c->scan_tmp, scan_temp_bytes(E), scan_temp_bytes(E_hold));
-  if (!spec) {
-    ENSURE_ROOM(c, c->strong, strong_list_bytes(E), strong_list_bytes(E_hold));
-    ENSURE_ROOM(c, c->lb_state, scan_temp_bytes(E), 2 * scan_temp_bytes(E_hold));
-  }
-  // (an array that was re-allocated above — for this call's count, or only for the ROOM the next calls want — has lost what the
-  // speculative launch wrote into it.  By CAPACITY, not by address: hipFree + hipMalloc hand the same address back often enough)
-  const size_t edge_arrays_after[5] = {c->ei.cap, c->ej.cap, c->es.cap, c->ebi.cap, c->ebj.cap};
-  bool edge_arrays_moved = false;
-  for (int k = 0; k < (build ? 3 : 5); k++) edge_arrays_moved = edge_arrays_moved || edge_arrays_before[k] != edge_arrays_after[k];
-  if (E > spec_cap || edge_arrays_moved) {  // first call, or the graph outgrew the arrays (just re-allocated above)
-    if (spec_cap && !build) HIPCHK(c, hipMemsetAsync(es_hist, 0, sizeof(uint32_t) * PR_HCOPIES * 256, st));  // the partial run's counts
-    fill_edges(E);
-  }
-  // certified pruning (sc_tri.hip 3b): weight ranking only; pointless on tiny graphs
-  c->pass.pruned = may_prune(p) && E >= 4096;
-  // counting pass + event list (sc_tri.hip 2b) on the pruned graph; Tuning::no_events keeps the row-walking pair
-  c->pass.use_events = c->pass.pruned && !c->tn.no_events;
-  if (c->pass.pruned) {
-    ControlBlock* ctl = c->ctl.as<ControlBlock>();
-    if (p->flags & SC_FLAG_EXACT_TOTAL) {  // statistics only: 3-cliques of the whole graph
-      launch_tri_count(g, g.bits, c->es.as<float>(), nullptr, c->ei.as<uint32_t>(), c->ej.as<uint32_t>(), E,
-                       c->tcnt.as<uint32_t>(), nullptr, c->tn, st);
-      launch_scan_u32(c->tcnt.as<uint32_t>(), E, c->toff.as<uint64_t>(), c->scan_tmp.p, c->tn, st, &c->pinned[HW_TOTAL]);
-      c->pass.have_total = true;
-    }
-    // the smallest possible weight is ~3 t_cmp (every edge has s >= t_cmp up to rounding); 0.1 % slack
-    // An ESTIMATED bound where the call can be repeated should the select find it too high (sc_tri.hip 3c): the common
-    // form only — event list, a-priori select window (the check rides the window's first round), the whole sample here
-    // (sharded, SC_FLAG_EST_BOUND: every rank takes the WHOLE sample — it is cheaper than the latency of the all-reduce that
-    // would sum the ranks' shares — and the merge of the candidates verifies the bound: sc_shard_score_device)
-    const bool est_local = c->pass.mode.may_estimate && !c->est_failed && hist == nullptr && parts == 1 && !c->pass.sharded_ab;
-    const bool est_shard = c->pass.sharded_ab && hist != nullptr && (p->flags & SC_FLAG_EST_BOUND) != 0;
-    c->pass.plan = sample_plan(p->max_triangles, (est_local || est_shard) && c->pass.use_events && window_known(p), c->tn,
-                          spec ? c->E_last : E, g.W);
-    c->pass.est_active = c->pass.plan.estimate;
-    if (build && !c->pass.plan.estimate) { c->last_error = "internal: the fused edge kernel ran but the bound is not an estimate"; return SC_EHIP; }
-    if (c->pass.plan.estimate) {
-      // an estimating sample (the single-GPU hot path; sharded, SC_FLAG_EST_BOUND: every rank takes the whole of it), inlier count, a call
-      // big enough for stage C2's Gram filter to be in question: the sample also
-      // leaves its workgroups' best triangles behind — the voters of that filter's reference frame (run_select passes them on)
-      uint4* cand = nullptr;
-      if ((est_local || est_shard) && p->score_mode == 0 && c->tn.score_filter != 1 && c->tn.score_filter != 2 && !c->tn.gram_ref_late &&
-          (uint64_t)p->max_triangles * (uint64_t)c->pass.n >= (1ull << 27)) {
-        if (!c->ref_cand.p) {
-          ENSURE(c, c->ref_cand, 4096 * sizeof(uint4));
-          HIPCHK(c, hipMemsetAsync(c->ref_cand.p, 0, 4096 * sizeof(uint4), st));
-        }
-        cand = c->ref_cand.as<uint4>();
-        c->pass.ref_cand_n = sample_candidate_blocks(E, c->tn);
-      }
-      launch_sample_estimate(g, build ? nullptr : c->ebi.as<uint32_t>(), build ? nullptr : c->ebj.as<uint32_t>(), c->ei.as<uint32_t>(),
-                             c->ej.as<uint32_t>(), c->es.as<float>(), E, key_floor(p), c->pass.plan.rate, ctl->prune_hist, c->tn,
-                             st, E_dev, c->ebase.as<uint32_t>(), cand, cand ? ctl->ref_slot : nullptr);
-    } else {
-      // SC_FLAG_EST_BOUND on the phase API where the plan is NOT an estimate (select window unknown: t_cmp below ~0.668; sc_debug's
-      // no_events / no_estimate / sample_mode): the caller still skips the histogram all-reduce, so every rank must end up with the
-      // SAME histogram — each takes the WHOLE certifying sample, not its share (with shares the ranks derived different
-      // bounds, cut the strong list differently, and the merged top-T could miss triangles)
-      const bool whole = est_shard;
-      launch_sample_hist(g, c->ebi.as<uint32_t>(), c->ebj.as<uint32_t>(), c->ei.as<uint32_t>(), c->ej.as<uint32_t>(),
-                         c->es.as<float>(), E, p->max_triangles, key_floor(p), whole ? 0u : part, whole ? 1u : parts,
-                         ctl->prune_hist, ctl->es_hist, c->tn, st, E_dev, spec ? c->E_last : 0);
-    }
-    if (hist) launch_hist_reduce(ctl->prune_hist, hist, st);  // the exchanged form: one 256-bin histogram
-  }
-  return SC_OK;
-}
-
-// Ordinal-order compaction of the keys at or above the threshold the select found -> sel_ord / sel_key.
-// Two launches (count per tile; write, every tile summing the counts before it by itself).  (The ONE-launch form — counts of the
-// earlier tiles by decoupled look-back — was built as VERDICT r01 asked, bit-exact and slower: 16.4 us against 4.7 + 4.7 on C2;
-// removed in r05.)  Tuning::compact_self_max == 0 (a test) takes the scanned three-launch form.
-static int run_compaction(sc_ctx* c, const KeyView& view, size_t nb, int rounds, uint64_t* host_short) {
-  hipStream_t st = c->stream;
-  SelectState* sel = &c->ctl.as<ControlBlock>()->sel;
-  launch_compact_count(view, sel, rounds, c->blk_gt.as<uint32_t>(), c->blk_eq.as<uint32_t>(), st, host_short);
-  // few tiles (and M < 2^32): compact_write adds up the tile counts itself, no scan launch in between
-  const bool self_off = nb <= c->tn.compact_self_max && view.M < (1ull << 32);
-  if (!self_off)
-    launch_scan_u32_pair(c->blk_gt.as<uint32_t>(), c->off_gt.as<uint64_t>(), c->blk_eq.as<uint32_t>(),
-                         c->off_eq.as<uint64_t>(), nb, c->scan_tmp.p, c->tn, st);
-  launch_compact_write(view, sel, c->blk_gt.as<uint32_t>(), c->blk_eq.as<uint32_t>(),
-                       self_off ? nullptr : c->off_gt.as<uint64_t>(), self_off ? nullptr : c->off_eq.as<uint64_t>(),
-                       c->sel_ord.as<uint64_t>(), c->sel_key.as<uint32_t>(),
-                       c->sel_ord.cap / 8 < c->sel_key.cap / 4 ? c->sel_ord.cap / 8 : c->sel_key.cap / 4, st);
-  return SC_OK;
-}
-
-// Stage B, second half: prune with the (summed) sample histogram, enumerate, select.  On return c->pass.M, c->pass.T_eff are set
-// and sel_ord / sel_key hold the selection.  want_list: also materialise the T x 3 triangle list (stage hook; the hot
-// path reads triangles through TriSource).  hist == nullptr: the control block's own histogram.
-static int run_select(sc_ctx* c, const sc_params* p, const uint32_t* hist, bool want_list) {
-  hipStream_t st = c->stream;
-  const uint64_t E = c->pass.E;
-  if (E == 0) return SC_OK;
-  const bool spec = c->pass.mode.host_free;  // host-free call: E is the cover, the real count sits in edge_off[n] (see run_edges)
-  const uint64_t* E_dev = spec ? c->edge_off.as<uint64_t>() + c->pass.n : nullptr;
-  const Graph g = graph_of(c);
-  const bool use_events = c->pass.use_events, have_total = c->pass.have_total;
-  StrongList sl{nullptr, nullptr, 0};
-  const uint64_t* mbits = g.bits;
-  const float* smin = nullptr;
-  // The key kernel runs speculatively (below) in the common form only — events, a-priori select window — and not when every stage
-  // is bracketed by events; spec_cap: the keys the arrays of the earlier calls hold (0: none yet, no speculative pass).
-  uint64_t spec_cap = 0;
-  if (use_events && window_known(p) && !c->pass.timing) {
-    spec_cap = c->wkey.cap / 4 < c->kcol.cap / 8 ? c->wkey.cap / 4 : c->kcol.cap / 8;
-    if (spec) spec_cap = c->pass.mode.M_cov;  // (<= that capacity: fast_plan)
-  }
-  // Exactly those calls, on one rank, take their ordinals from an ORDERED strong list (sc_tri.hip
-  // 2c): no scan of the per-edge counts, the key kernel leaves the triangle count where the scan would.  While the pruning kernel's
-  // grid stays within what a workgroup's prologue sums (C3 does not), and until a call's list had more chunks than the key kernel
-  // holds (sc_ctx::ord_off); sc_debug.scan_ordinals keeps the scan.
-  const bool ord_on = spec_cap != 0 && !c->pass.sharded_ab && hist == nullptr && p->shard_world == 1 &&
-                      !c->tn.scan_ordinals && !c->ord_off && (E + ORD_BLOCK_EDGES - 1) / ORD_BLOCK_EDGES <= ORD_MAX_BLOCKS;
-  c->pass.ord_state = ord_on ? 1 : 0;
-  OrdList ord{};
-  if (c->pass.pruned) {
-    ControlBlock* ctl = c->ctl.as<ControlBlock>();
-    if (use_events) {  // the pruning kernel also compacts the strong edges for the counting pass
-      ENSURE(c, c->strong, strong_list_bytes(E));  // (a waited call: run_edges left room)
-      ENSURE(c, c->ord_cnt, ORD_MAX_BLOCKS * sizeof(uint32_t));  // (by every call of the event path: a host-free one finds it)
-      sl = StrongList{c->strong.as<uint32_t>(), ctl->st_fill, strong_list_cap(E), 0u};
-    }
-    if (ord_on) {
-      // tloc and ctot live where the scan's offsets would: toff holds 2 E + 2 words, tloc takes E of them, ctot at most E / 4 + 4
-      // from the next multiple of four (E >= 4096), and the count lands in toff[E] as ever
-      uint32_t* words = c->toff.as<uint32_t>();
-      ord.cnt = c->ord_cnt.as<uint32_t>(); ord.tloc = words; ord.ctot = words + ((E + 3) & ~(uint64_t)3);
-      ord.n_strong = &ctl->n_strong; ord.total = c->toff.as<uint64_t>() + E; ord.E = E; ord.E_dev = E_dev;
-      ord.chunk_max = c->tn.ord_chunk_max && c->tn.ord_chunk_max < ORD_CHUNK_MAX ? c->tn.ord_chunk_max : ORD_CHUNK_MAX;
-      sl.cnt = ord.cnt;
-    }
-    const bool recut = c->pass.sharded_ab && p->shard_world > 1 && use_events;
-    // contiguous regions: a rank walks only the regions its own edge range touches (unsharded the modulo form stays: the
-    // counting pass is no faster with contiguous regions at C2 / C4 and 20 us slower at C3)
-    if (recut) sl.region_blocks = sl.cap / 256;
-    // Sharded (event path): the ranks' row ranges are cut AFTER the certificate, by the work of the pruned graph (VERDICT r02
-    // #5: a correspondence list in keypoint order puts nearly every strong edge into a few rows).  Every rank holds the
-    // whole strong matrix, so every rank computes the same cut: the pruning kernel lists EVERY strong edge, two small
-    // launches make the cut, and the counting pass skips the edges of the other ranks.
-    launch_prune_bits(g, hist ? hist : ctl->prune_hist, hist == nullptr, c->ei.as<uint32_t>(), c->ej.as<uint32_t>(), c->es.as<float>(), E,
-                      c->pass.est_active ? c->pass.plan.hist_want : (uint64_t)p->max_triangles, key_floor(p), c->bits2.as<uint64_t>(), &ctl->smin, &ctl->klb, sl,
-                      c->tcnt.as<uint32_t>(), recut ? nullptr : own_range_of(c), st, E_dev, c->pass.est_active,
-                      spec && c->pass.build && !c->pass.sharded_ab);  // (the scan of such a call is trimmed to the real edges: below)
-    if (recut) {
-      ENSURE(c, c->rowcost, ((size_t)c->pass.n + 4 + 1024) * 4);  // (cost_split_kernel reads whole 16-byte pieces)
-      launch_strong_rowcost(g, c->bits2.as<uint64_t>(), c->rowcost.as<uint32_t>(), st);
-      launch_cost_split(c->rowcost.as<uint32_t>(), c->edge_off.as<uint64_t>(), c->pass.n, (uint32_t)p->shard_rank,
-                        (uint32_t)p->shard_world, ctl->own_row, ctl->own_edge, st);
-    }
-    mbits = c->bits2.as<uint64_t>();
-    smin = &ctl->smin;
-  }
-  EventList ev{};
-  if (use_events) {
-    // Tuning::event_cap (test hook) forces a (too) small buffer for THIS call without touching the context's own
-    // capacity, which only grows (after an overflow)
-    const uint64_t ev_cap = c->tn.event_cap >= 256 ? c->tn.event_cap : c->ev_capacity;
-    ENSURE(c, c->events, event_bytes(ev_cap));
-    c->pinned[HW_EV_OVERFLOW] = 0;
-    ev = event_list(c->events.p, ev_cap, g.W, c->ctl.as<ControlBlock>()->ev_fill,
-                    reinterpret_cast<uint32_t*>(&c->pinned[HW_EV_OVERFLOW]));
-    GramRefJob ref{};
-    if (c->pass.ref_cand_n) {  // (run_edges) one extra workgroup votes for stage C2's reference frame under this launch
-      SC_TRY(ensure_frame(c));
-      ref = gram_ref_job(points_of(c), c->fx_mx.as<uint32_t>(), c->pass.dv.tau2, c->tn, c->fx_frame.p);
-      ref.src.cand = c->ref_cand.as<uint4>(); ref.src.n_cand = c->pass.ref_cand_n; ref.src.cand_slot = c->ctl.as<ControlBlock>()->ref_slot;
-      c->pass.ref_done = true;
-    }
-    launch_tri_count_events(g, mbits, sl, c->pass.build ? nullptr : c->ebi.as<uint32_t>(), c->pass.build ? nullptr : c->ebj.as<uint32_t>(), c->ei.as<uint32_t>(),
-                            c->ej.as<uint32_t>(), spec ? c->E_last : E, p->rank_mode, c->tcnt.as<uint32_t>(), ev, c->tn, st, own_range_of(c),
-                            c->ebase.as<uint32_t>(), ref.out ? &ref : nullptr, ord_on ? &ord : nullptr);
-  } else {
-    launch_tri_count(g, mbits, c->es.as<float>(), smin, c->ei.as<uint32_t>(), c->ej.as<uint32_t>(), E,
-                     c->tcnt.as<uint32_t>(), own_range_of(c), c->tn, st);
-  }
-  // read-back #2: triangle count (of the pruned graph when pruning), written to pinned memory by the scan
-  // (ordered strong list: by the key kernel, which makes the ordinals without a scan)
-  arm_word(c, HW_TRIANGLES);
-  ScanExtra xr;  // sharded: the counts outside this rank's edge range are zero — their tiles are skipped
-  xr.range = own_range_of(c);
-  // a host-free call on the fused edge kernel: the launches cover E edges, the graph has fewer — the scan skips the tiles beyond
-  // them (the pruning kernel's workgroups there have left without writing their counts)
-  if (spec && c->pass.build && !c->pass.sharded_ab) xr.range = c->ctl.as<ControlBlock>()->live_edges;
-  if (!ord_on) {
-    SC_TRY(lb_next(c, scan_temp_bytes(E), 0, 0, &xr.lb));
-    launch_scan_u32(c->tcnt.as<uint32_t>(), E, c->toff.as<uint64_t>(), c->scan_tmp.p, c->tn, st, spec ? nullptr : &c->pinned[HW_TRIANGLES], &xr);
-  }
-  // While the host polls for the count, the key kernel already runs into the key arrays this context holds from earlier
-  // calls (it takes everything else from device memory); re-run below if the count outgrew the arrays or a region overflowed.
-  SelectState* sel = &c->ctl.as<ControlBlock>()->sel;
-  int chunk_shift = 0;  // an OrdList's chunk: the positions a workgroup of the counting pass takes per trip
-  while ((256 >> chunk_shift) > tri_count_events_lanes(g, c->tn)) chunk_shift++;
-  if (spec_cap) {
-    ENSURE(c, c->blk_minmax, 2 * 8192 * 4);
-    launch_tri_keys_events(g, c->es.as<float>(), c->toff.as<uint64_t>(), p->rank_mode, ev, c->wkey.as<uint32_t>(),
-                           c->kcol.as<uint2>(), c->blk_minmax.as<uint32_t>(), sel, select_want(c, p),
-                           &c->ctl.as<ControlBlock>()->klb, E, spec_cap, c->tn, st, !c->pass.sharded_ab,
-                           ord_on ? &ord : nullptr, chunk_shift, (ord_on && !spec) ? &c->pinned[HW_TRIANGLES] : nullptr);
-  }
-  // host-free call: no wait — M is what the key arrays and the launches below cover, T_eff the requested T; the kernels
-  // read the real count from toff[E] (= the scan's total: the counts of [real E, E) are zero) and sc_wait validates
-  if (!spec) SC_TRY(wait_word(c, HW_TRIANGLES));
-  if (ord_on && !spec && (uint32_t)c->pinned[HW_EV_OVERFLOW] != 0) {
-    // an event region was full, or the list has more chunks than the key kernel holds: the row-walking key kernel below needs toff —
-    // the scan runs after all, here and only here, over counts whose weak entries nobody has written yet
-    launch_zero_weak_counts(c->es.as<float>(), smin, E, nullptr, c->tcnt.as<uint32_t>(), st);
-    arm_word(c, HW_TRIANGLES);
-    SC_TRY(lb_next(c, scan_temp_bytes(E), 0, 0, &xr.lb));
-    launch_scan_u32(c->tcnt.as<uint32_t>(), E, c->toff.as<uint64_t>(), c->scan_tmp.p, c->tn, st, &c->pinned[HW_TRIANGLES], &xr);
-    SC_TRY(wait_word(c, HW_TRIANGLES));
-    c->pass.ord_state = 2;
-    if (chunk_overflow(c)) c->ord_off = true;
-  }
-  c->pass.M_total = spec ? c->pass.mode.M_cov : (have_total ? c->pinned[HW_TOTAL] : c->pinned[HW_TRIANGLES]);
-  const uint64_t M = c->pass.M = spec ? c->pass.mode.M_cov : c->pinned[HW_TRIANGLES];
-  if (M == 0) {
-    // no triangle in the pruned graph: under a CERTIFIED bound (or none) the graph has none; an ESTIMATED bound has verified nothing
-    // (the select that checks it never runs): the call is repeated with a certifying sample (finalize_wait)
-    if (c->pass.est_active) c->pass.est_void = true;
-    return SC_OK;
-  }
-  const uint32_t want_sel = select_want(c, p);
-  const uint32_t T_eff = c->pass.T_eff = (uint32_t)(M < want_sel ? M : want_sel);
-  if (M * 12 > c->cap_bytes) { c->last_error = "triangle keys exceed the workspace cap"; return SC_ETOOMANY; }
-  const size_t nb = compact_blocks(M);
-  const uint64_t M_room = spec ? M : room_of(c, M, c->M_hi);
-  const size_t key_arrays_before[2] = {c->wkey.cap, c->kcol.cap};
-  ENSURE_ROOM(c, c->wkey, M * 4, M_room * 4);
-  ENSURE_ROOM(c, c->kcol, M * 8, M_room * 8);
-  const bool key_arrays_moved = key_arrays_before[0] != c->wkey.cap || key_arrays_before[1] != c->kcol.cap;  // (re-allocated: what the speculative key pass wrote is gone)
-  ENSURE(c, c->blk_minmax, 2 * 8192 * 4);
-  const size_t nb_room = compact_blocks(spec ? M : (uint64_t)(c->wkey.cap / 4 < c->kcol.cap / 8 ? c->wkey.cap / 4 : c->kcol.cap / 8));  // (whatever the key arrays can hold: fast_plan's cap)
-  ENSURE_ROOM(c, c->blk_gt, nb * 4, nb_room * 4);
-  ENSURE_ROOM(c, c->blk_eq, nb * 4, nb_room * 4);
-  ENSURE_ROOM(c, c->off_gt, (nb + 1) * 8, (nb_room + 1) * 8);
-  ENSURE_ROOM(c, c->off_eq, (nb + 1) * 8, (nb_room + 1) * 8);
-  ENSURE(c, c->scan_tmp, scan_temp_bytes(nb));
-  ENSURE(c, c->sel_ord, (size_t)T_eff * 8);
-  ENSURE(c, c->sel_key, (size_t)T_eff * 4);
-  if (want_list) ENSURE(c, c->tri, (size_t)T_eff * 12);
-  if (c->pass.timing) HIPCHK(c, hipEventRecord(c->ev[9], st));
-  bool events_ok = use_events;
-  if (!spec && use_events && (uint32_t)c->pinned[HW_EV_OVERFLOW] != 0) {  // a region overflowed: this call walks the rows again
-    events_ok = false;
-    if (!chunk_overflow(c)) {  // (too many chunks of an ordered strong list: a larger event buffer would not help)
-      uint64_t want_cap = c->ev_capacity * 2;          // every event holds >= 1 triangle, so M bounds the need
-      if (want_cap < M + M / 4) want_cap = M + M / 4;
-      if (want_cap > (1ull << 28)) want_cap = 1ull << 28;
-      c->ev_capacity = want_cap;
-    }
-  }
-  // weight keys of a graph whose edges all weigh >= 2/3 (0.1 % slack) lie in [2.0, 3.0]: window known a priori
-  const bool fast_window = events_ok && window_known(p);
-  const bool keys_done = spec_cap != 0 && events_ok && M <= spec_cap && !key_arrays_moved;  // the speculative pass wrote every key
-  if (keys_done) {
-    // nothing to do
-  } else if (events_ok) {
-    launch_tri_keys_events(g, c->es.as<float>(), c->toff.as<uint64_t>(), p->rank_mode, ev, c->wkey.as<uint32_t>(),
-                           c->kcol.as<uint2>(), c->blk_minmax.as<uint32_t>(), sel, fast_window ? (uint64_t)select_want(c, p) : (uint64_t)T_eff,
-                           fast_window ? &c->ctl.as<ControlBlock>()->klb : nullptr, E, M, c->tn, st, !c->pass.sharded_ab,
-                           ord_on ? &ord : nullptr, chunk_shift);  // (ord_on: no overflow here, the lists of the counting pass stand)
-  } else {
-    launch_tri_keys(g, mbits, smin, c->ebase.as<uint32_t>(), c->ei.as<uint32_t>(), c->ej.as<uint32_t>(),
-                    c->es.as<float>(), c->toff.as<uint64_t>(), E, p->rank_mode, c->wkey.as<uint32_t>(),
-                    c->kcol.as<uint2>(), c->blk_minmax.as<uint32_t>(), sel, T_eff, own_range_of(c), c->tn, st);
-  }
-  if (c->pass.timing) HIPCHK(c, hipEventRecord(c->ev[10], st));
-  c->pass.timed_trikeys = c->pass.timing;
-  KeyView view = plain_view(c->wkey.as<uint32_t>(), M);
-  if (spec) view.M_dev = c->toff.as<uint64_t>() + E;
-  // an estimated bound is verified by the first round over the a-priori window; any other path leaves it unverified
-  if (c->pass.est_active && !fast_window) c->pass.est_void = true;
-  launch_select_rounds(view, sel, fast_window ? 2 : 3, c->tn, st, c->pass.sharded_ab ? nullptr : &c->pinned[HW_SELECT_SHORT]);
-  SC_TRY(run_compaction(c, view, nb, fast_window ? 2 : 3, c->pass.sharded_ab ? nullptr : &c->pinned[HW_SELECT_SHORT]));
-  // the list stays in ordinal order: no sort on the hot path (the winner is found by (count, key, position))
-  if (want_list)
-    launch_tri_decode(c->ei.as<uint32_t>(), c->ej.as<uint32_t>(), c->kcol.as<uint2>(), c->sel_ord.as<uint64_t>(), T_eff,
-                      c->tri.as<uint32_t>(), st);
-  // the shape a host-free repetition of this call assumes (fast_plan / finalize_wait)
-  c->pass.regular = !spec && events_ok && fast_window && !have_total && !c->pass.timing && M >= want_sel && hist == nullptr;
-  return SC_OK;
-}
-
-int run_triangles(sc_ctx* c, const sc_params* p, bool want_list) {
-  SC_TRY(run_edges(c, p, nullptr, 0, 1));
-  return run_select(c, p, nullptr, want_list);
 }
 
 void fill_stats(const sc_ctx* c, sc_stats* s) {
@@ -993,8 +532,8 @@ int sc_debug_last(sc_ctx* c, sc_debug_info* out) {
   out->n_est_ok = c->n_est_ok; out->n_est_fail = c->n_est_fail;
   out->cover_edges = c->pass.mode.E_cov; out->cover_triangles = c->pass.mode.M_cov; out->n_hostfree_grow = c->n_spec_grow;
   out->n_lane = c->n_lane;
-  out->ordinals = (uint32_t)c->pass.ord_state; out->strong_edges = 0;
-  if (c->pass.ord_state != 0 && c->ctl.p) {  // (the control block of the last call: zeroed by the next one's staging kernel)
+  out->ordinals = (uint32_t)c->pass.form.ord_state; out->strong_edges = 0;
+  if (c->pass.form.ord_state != 0 && c->ctl.p) {  // (the control block of the last call: zeroed by the next one's staging kernel)
     HIPCHK(c, hipMemcpyAsync(&out->strong_edges, &c->ctl.as<ControlBlock>()->n_strong, 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
@@ -1059,7 +598,7 @@ static int hyp_begin(sc_ctx* c, const float* d_src, const float* d_tgt, int64_t 
     c->last_error = "SC_FLAG_EST_BOUND belongs to the sc_shard_* phase API and to sc_hypothesize_device";
     return SC_EINVAL;
   }
-  c->pass.build = d_hist == nullptr && parts == 1 && edge_build_ok(c, p, n, mode.may_estimate);
+  c->pass.form.build = d_hist == nullptr && parts == 1 && edge_build_ok(c, p, n, mode.may_estimate);  // (the whole sample, own histogram: run_edges checks that it is told the same)
   SC_TRY(rec(c, 0));
   SC_TRY(stage_inputs(c, d_src, d_tgt, n, p));
   SC_TRY(rec(c, 1));
@@ -1071,17 +610,6 @@ static int hyp_begin(sc_ctx* c, const float* d_src, const float* d_tgt, int64_t 
   return SC_OK;
 }
 
-// C2: the counts of this shard's hypotheses into c->partial; *rows: rows of c->partial the arg-max has to add up.
-// SC_SCORE_COUNT runs the matrix-pipe filter + the exact fix-up (sc_score.hip); the truncated scores, and
-// sc_debug.score_filter = 1, the plain fp32 kernel.
-// C2 by filter?  By mode / size / knobs (score_uses_filter), and — unless forced — only when tau is on a scale the filter
-// can bound (a tau below ~2.4e-4 of the scene's extent, or above 8 x, would send every wave to the exact recount, which
-// is slower than the plain kernel): the staging kernel has told the host the coordinate maxima long before this point.
-// Evaluated ONCE per call (decide_filter stores the answer in the context): the word it reads is written by the GPU, so
-// two evaluations could disagree.  On the path the maxima have always arrived by then (the host has polled results of
-// later kernels of the same stream); the stage hook waits for the word.  Not known (sc_debug.filter_blind forces that
-// case) means "assume in range": the filter itself hands whatever it cannot bound to the exact recount, so the counts
-// are the same either way, only slower.
 // The coordinate statistics as the host words hold them now (mx all ones: not arrived; the boxes then mean nothing).
 // flag, THEN data: the staging kernel writes the six box words before the word of maxima, so the maxima are loaded with
 // acquire semantics and the boxes only afterwards (the fence used to sit behind both loads, which only the
@@ -1107,6 +635,9 @@ static CoordStats filter_stats(const sc_ctx* c) {
   }
   return cs;
 }
+// C2 by filter?  By mode / size / knobs (score_uses_filter), and — unless forced — only when tau is on a scale the filter
+// can bound (a tau below ~2.4e-4 of the scene's extent, or above 8 x, would send every wave to the exact recount, which
+// is slower than the plain kernel): the staging kernel has told the host the coordinate maxima long before this point.
 static int use_filter(const sc_ctx* c, const sc_params* p, const Shard& sh) {
   const CoordStats cs = filter_stats(c);
   return score_filter_mode(p->score_mode, c->tn, c->pass.n, sh.ld_local, cs.mx, cs.mx == ~0ull ? nullptr : cs.box, c->pass.dv.tau2);
@@ -1123,6 +654,11 @@ static int run_gram_guard(sc_ctx* c) {
   c->gram_guard = (sub_ok && compared != 0 && worst <= gram_guard_limit()) ? 1 : 2;
   return SC_OK;
 }
+// Evaluated ONCE per call (decide_filter stores the answer in the context): the word it reads is written by the GPU, so
+// two evaluations could disagree.  On the path the maxima have always arrived by then (the host has polled results of
+// later kernels of the same stream); the stage hook waits for the word.  Not known (sc_debug.filter_blind forces that
+// case) means "assume in range": the filter itself hands whatever it cannot bound to the exact recount, so the counts
+// are the same either way, only slower.
 int decide_filter(sc_ctx* c, const sc_params* p, const Shard& sh) {
   c->pass.filter_mode = use_filter(c, p, sh);
   if (c->pass.filter_mode == 2) {
@@ -1153,6 +689,9 @@ static int filter_job(sc_ctx* c, const Shard& sh, FilterTileJob* job) {
   return SC_OK;
 }
 
+// C2: the counts of this shard's hypotheses into c->partial; *rows: rows of c->partial the arg-max has to add up.
+// SC_SCORE_COUNT runs the matrix-pipe filter + the exact fix-up (sc_score.hip); the truncated scores, and
+// sc_debug.score_filter = 1, the plain fp32 kernel.
 int run_score(sc_ctx* c, const sc_params* p, const Shard& sh, uint32_t* rows, bool tile_done, hipEvent_t ev0, hipEvent_t ev1,
               hipEvent_t ev_mid) {
   if (c->pass.filter_on) {  // decide_filter() ran earlier in this call
@@ -1202,7 +741,7 @@ static int run_stage_c(sc_ctx* c, uint64_t* d_key, sc_stats* stats) {
     if (filter) SC_TRY(filter_job(c, sh, &job));
     // host-free call: the selection may turn out shorter than the T this launch was sized for (then the call is repeated);
     // its real length is what the select left in sel.want
-    const uint64_t* t_eff_dev = (c->pass.mode.host_free || c->pass.est_active) ? &c->ctl.as<ControlBlock>()->sel.want : nullptr;
+    const uint64_t* t_eff_dev = (c->pass.mode.host_free || c->pass.form.est_active) ? &c->ctl.as<ControlBlock>()->sel.want : nullptr;
     if (filter && c->pass.fx_plan.mode == 2 && !c->pass.ref_done)  // the Gram filter's reference frame, where the counting pass did not carry the vote: among 64 hypotheses of the selection
       launch_gram_ref(points_of(c), tri_source_of(c), sh, nullptr, t_eff_dev, c->fx_mx.as<uint32_t>(), c->pass.dv.tau2, c->tn,
                       c->fx_frame.p, c->stream);
@@ -1374,20 +913,14 @@ int sc_shard_score_device(sc_ctx* c, const void* d_cand_all, uint64_t* d_key, sc
   SelectState* sel = &ctl->sel;
   const KeyView view = cand_view(d_cand_all, blob_bytes, G, cap);
   const size_t nb = compact_blocks(view.M);
-  ENSURE(c, c->blk_gt, nb * 4);
-  ENSURE(c, c->blk_eq, nb * 4);
-  ENSURE(c, c->off_gt, (nb + 1) * 8);
-  ENSURE(c, c->off_eq, (nb + 1) * 8);
-  ENSURE(c, c->scan_tmp, scan_temp_bytes(nb));
-  ENSURE(c, c->sel_ord, (size_t)T * 8);
-  ENSURE(c, c->sel_key, (size_t)T * 4);
+  SC_TRY(ensure_compaction(c, nb, nb, T));  // (no room beyond the need: no host-free call comes here)
   arm_word(c, HW_MERGED_T);
   c->pinned[HW_MERGE_SHORT] = 0;  // "an estimated bound promised T keys above it and the merged candidates hold fewer" (merge_prepare_kernel)
   launch_merge_prepare(d_cand_all, blob_bytes, G, T, window_known(p), &ctl->klb, sel, &c->pinned[HW_MERGED_T], st,
-                       c->pass.est_active ? &c->pinned[HW_MERGE_SHORT] : nullptr);
-  launch_select_rounds(view, sel, window_known(p) ? 2 : 3, c->tn, st);
+                       c->pass.form.est_active ? &c->pinned[HW_MERGE_SHORT] : nullptr);
+  launch_select_rounds(view, sel, select_rounds(window_known(p)), c->tn, st);
   c->pinned[HW_CAND_CUT] = 0;  // "a cut candidate list could have mattered": read by the finalize call (SC_ERETRY)
-  SC_TRY(run_compaction(c, view, nb, window_known(p) ? 2 : 3, nullptr));
+  SC_TRY(run_compaction(c, view, nb, select_rounds(window_known(p)), nullptr));
   launch_merge_check(d_cand_all, blob_bytes, G, sel, &c->pinned[HW_CAND_CUT], st);  // (behind the compaction: its counting kernel is what resolves the last round into k*)
   // the merged length, published by merge_prepare long before the compaction ends: the poll costs no GPU time
   SC_TRY(wait_word(c, HW_MERGED_T));
@@ -1462,8 +995,8 @@ static int finalize_enqueue(sc_ctx* c, const uint64_t* d_keys, int n_pairs, floa
 
 // what the next call on this context may assume (fast_plan): the call that just completed was a "regular" one
 static void note_completed(sc_ctx* c, bool regular) {
-  c->fast_ok = regular && !c->pass.sharded_ab && c->pass.E >= 4096 && c->pass.T_eff == c->pass.params.max_triangles;  // (stages A and B whole on this GPU: one rank, or replicated ranks)
-  if (c->pass.n != c->last_n || !same_shape(&c->pass.params, &c->last_p)) { c->E_hi[0] = c->E_hi[1] = c->M_hi[0] = c->M_hi[1] = 0; c->hi_n = 0; c->hi_seen = 0; }
+  c->fast_ok = hostfree_next_ok(c, regular);
+  if (!shape_continues(c)) { c->E_hi[0] = c->E_hi[1] = c->M_hi[0] = c->M_hi[1] = 0; c->hi_n = 0; c->hi_seen = 0; }
   if (c->fast_ok) {  // (the counts of a regular call of this shape: what a host-free repetition has to cover)
     if (c->hi_seen < 0xFFFFFFFFu) c->hi_seen++;
     if (c->pass.E > c->E_hi[0]) c->E_hi[0] = c->pass.E;
@@ -1482,7 +1015,7 @@ static void note_completed(sc_ctx* c, bool regular) {
   }
   // room for the event list of a call like this one: an event holds >= 1 triangle, so 2 M records can only overflow a region
   // on a fill 2 x off the mean (the regions fill evenly: a wave moves to the next one with every flush)
-  if (c->pass.use_events && c->ev_capacity < 2 * c->pass.M) c->ev_capacity = 2 * c->pass.M < (1ull << 28) ? 2 * c->pass.M : (1ull << 28);
+  if (c->pass.form.use_events && c->ev_capacity < 2 * c->pass.M) c->ev_capacity = 2 * c->pass.M < (1ull << 28) ? 2 * c->pass.M : (1ull << 28);
 }
 
 // phase 2, second half: wait for the winner; a host-free call is validated here
@@ -1508,9 +1041,7 @@ static int finalize_wait(sc_ctx* c, sc_stats* stats) {
     // (the finalize kernel handed both counts over in one word: DeferredPub)
     const uint64_t em = c->pinned[HW_EDGES];
     const uint64_t E = em == PIN_PENDING ? PIN_PENDING : (em & 0xFFFFFFFFull), M = em == PIN_PENDING ? PIN_PENDING : (em >> 32);
-    const bool ok = E != PIN_PENDING && M != PIN_PENDING && E >= 4096 && E <= c->pass.mode.E_cov && M <= c->pass.mode.M_cov &&
-                    M >= (uint64_t)c->pass.params.max_triangles && (uint32_t)c->pinned[HW_EV_OVERFLOW] == 0;
-    if (!ok) {
+    if (!hostfree_valid(c, E, M)) {
       char buf[256];  // (why, for sc_last_error: the repeat itself is silent)
       snprintf(buf, sizeof buf, "host-free call repeated: edges %llu (covered %llu), triangles %llu (covered %llu, T %u), event overflow %u",
                (unsigned long long)E, (unsigned long long)c->pass.mode.E_cov, (unsigned long long)M, (unsigned long long)c->pass.mode.M_cov,
@@ -1525,16 +1056,16 @@ static int finalize_wait(sc_ctx* c, sc_stats* stats) {
     c->frame.fast_state = 1;
     c->pass.regular = true;
   }
-  c->pass.est_state = c->pass.est_active ? 1 : 0;
+  c->pass.est_state = c->pass.form.est_active ? 1 : 0;
   // SC_EBOUND: the caller repeats the call without the flag (include/saccot.h), on every rank alike
   static const char* const bound_too_high = "the estimated pruning bound was too high for this input: repeat the call without SC_FLAG_EST_BOUND";
-  if (c->pass.sharded_ab && c->pass.est_active && (c->pinned[HW_MERGE_SHORT] != 0 || c->pass.est_void)) {
+  if (c->pass.sharded_ab && c->pass.form.est_active && (c->pinned[HW_MERGE_SHORT] != 0 || c->pass.est_void)) {
     c->last_error = bound_too_high;  // (every rank holds the same gathered blobs, so every rank ends here together)
     return SC_EBOUND;
   }
-  if (c->pinned[HW_SELECT_SHORT] != 0 || (c->pass.est_active && c->pass.est_void)) {
+  if (c->pinned[HW_SELECT_SHORT] != 0 || (c->pass.form.est_active && c->pass.est_void)) {
     // select_round_kernel: fewer keys at or above the pruning bound than it promised (or the bound went unverified)
-    if (!c->pass.est_active) {  // a CERTIFIED bound holds by construction: this would be a defect, not an input
+    if (!c->pass.form.est_active) {  // a CERTIFIED bound holds by construction: this would be a defect, not an input
       c->last_error = "internal: the select found fewer keys above a certified pruning bound than the certificate counted";
       return SC_EHIP;
     }
@@ -1587,25 +1118,6 @@ static int finalize_wait(sc_ctx* c, sc_stats* stats) {
     }
   }
   return key ? SC_OK : SC_ENOHYP;
-}
-
-// May this call be enqueued host-free?  Only a repetition of the last call's shape on this context, and only when that call
-// was regular (note_completed); sets what the launches cover: the last counts plus half, within what the arrays hold.
-static bool fast_plan(const sc_ctx* c, int64_t n, const sc_params* p, PassMode* mode) {
-  if (!c->fast_ok || c->tn.no_fast || c->tn.no_events || n != c->last_n) return false;
-  if (p->flags & (SC_FLAG_TIMING | SC_FLAG_EXACT_TOTAL | SC_FLAG_NO_PRUNE)) return false;
-  if (!same_shape(p, &c->last_p)) return false;
-  if (!window_known(p)) return false;  // the a-priori select window
-  const uint64_t ecap = edge_capacity(c, edge_build_ok(c, p, n, true));  // (every entry point that comes here may estimate; the fused edge kernel writes no per-edge bases)
-  const uint64_t kcap = c->wkey.cap / 4 < c->kcol.cap / 8 ? c->wkey.cap / 4 : c->kcol.cap / 8;
-  // the last call's counts plus half, and the largest counts of the shape's recent calls plus a quarter (sc_ctx::E_hi)
-  const bool young = c->hi_seen < sc_ctx::HI_YOUNG;
-  uint64_t ecov = cover_of(c->E_last, c->E_hi, young), mcov = cover_of(c->M_last, c->M_hi, young);
-  if (ecov > ecap) ecov = ecap;
-  if (mcov > kcap) mcov = kcap;
-  if (ecov < c->E_last || ecov < 4096 || ecov >= (1ull << 32) || mcov < c->M_last || mcov < p->max_triangles) return false;
-  mode->host_free = true; mode->E_cov = ecov; mode->M_cov = mcov;
-  return true;
 }
 
 // the whole path the waiting way (what sc_register_device always did): complete on return.  The only caller of the phases

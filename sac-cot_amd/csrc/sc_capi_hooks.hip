@@ -11,7 +11,7 @@ int host_to_planes(sc_ctx* c, const float* src, const float* tgt, int64_t n, con
   SC_TRY(busy(c));
   c->pass.mode.host_free = false;  // (a host-free call that was never finalized must not leave its covers to a stage hook)
   c->pass.mode.may_estimate = false;  // (a hook cannot repeat itself: certified bounds only)
-  c->pass.build = false;  // (stage hooks: the separate kernels)
+  c->pass.form.build = false;  // (stage hooks: the separate kernels)
   c->pass.timing = c->pass.timing_hot = false; c->pass.timing_one = -1;  // (... and no event brackets)
   c->cap_bytes = workspace_cap(p);
   c->pass.dv = derive(p);

@@ -36,16 +36,46 @@ struct PassMode {
   uint64_t E_cov = 0, M_cov = 0;
 };
 
+// Stage B's form: which of its kernels a call runs, in which variant.  Each field is decided ONCE, by the function named above it
+// (sc_capi_tri.hip; the reasons stand there), and every later line of run_edges / run_select reads it here.  run_edges starts from
+// StageBForm{} — but for `build`, which stage A's launches read before, and `ord_state`, which run_select sets — so a stage hook, which
+// starts no pass, finds nothing of the call before.
+struct StageBForm {
+  // ---- hyp_begin (before stage A: stage_inputs, run_compat and run_row_stats read it); a stage hook clears it
+  bool build = false;       // launch_edge_build: row statistics + edge list + estimating sample in one launch
+  // ---- form_begin, at the top of run_edges
+  bool spec = false;        // host-free (PassMode): no wait; E and M are what the launches COVER, the kernels read the real counts from device memory
+  bool own_sample = false;  // the whole sample goes into the context's own histogram (no exchanged histogram, one part); run_select must be handed the same
+  bool fused = false;       // edge_off / ebase are made by the row kernel (run_row_stats) or by the fused edge kernel: no scan of the degrees
+  bool est_local = false;   // the bound may be an estimate: the call can be repeated and the whole sample is taken here
+  bool est_shard = false;   // ... sharded, SC_FLAG_EST_BOUND: every rank takes the whole sample, the merge verifies
+  // ---- form_counted, behind the edge count
+  bool pruned = false;      // certified pruning (sc_tri.hip 3b)
+  bool use_events = false;  // counting pass + event list (sc_tri.hip 2b)
+  bool have_total = false;  // SC_FLAG_EXACT_TOTAL: the 3-cliques of the whole graph are counted as well (HW_TOTAL)
+  bool est_active = false;  // stage B prunes by an estimate (Pass::plan.estimate)
+  // ---- form_select, at the top of run_select (these need the edge count)
+  uint64_t spec_cap = 0;    // keys the speculative key pass may write (0: no speculative pass)
+  bool ord_on = false;      // ordinals from the ordered strong list (sc_tri.hip 2c): no scan of the per-edge counts
+  bool recut = false;       // sharded event path: the ranks' edge ranges are cut again after the certificate
+  bool trimmed = false;     // host-free on the fused edge kernel: pruning kernel and scan stop at the real edge count
+  int ord_state = 0;        // 0 ordinals from the scan of the per-edge counts, 1 from the ordered strong list, 2 that form, then an overflow's fall-back through the scan (read_triangle_count raises it; sc_debug_last)
+  // ---- form_keys, behind the triangle count
+  bool events_ok = false;   // the event list holds every event (no region overflowed)
+  bool fast_window = false; // the select takes the a-priori window [2, 3]: two rounds, and an estimated bound is verified by the first
+  bool keys_done = false;   // the speculative key pass wrote every key: no second pass
+};
+
 // One run through hyp_begin (or sc_shard_compat_device) to finalize_wait.  Assigned Pass{} in pass_begin and nowhere else: what a pass
 // did not set itself reads as "no".  Fields are READ after the pass as well — by a finalize call that comes later (have_hyp links the
-// two, and it may come twice), by note_completed (E, M, n, params, use_events), by fill_stats and sc_debug_last (counts, covers, filter_*,
-// est_state, hot_ext) — so nothing is cleared when a pass ends except mode.host_free.  The stage hooks (sc_*_host) start no pass: they
-// run single kernels on the context's buffers and touch only what host_to_planes says.
+// two, and it may come twice), by note_completed (E, M, n, params, form.use_events), by fill_stats and sc_debug_last (counts, covers,
+// filter_*, est_state, form.ord_state, hot_ext) — so nothing is cleared when a pass ends except mode.host_free.  The stage hooks
+// (sc_*_host) start no pass: they run single kernels on the context's buffers and touch only what host_to_planes says.
 struct Pass {
   PassMode mode;
   int n = 0, ld = 0; uint32_t T_eff = 0;
   uint64_t E = 0, M = 0, M_total = 0;  // stage B's counts (host-free: the covers until finalize_wait has validated, then the real ones)
-  bool pruned = false, use_events = false, have_total = false;
+  StageBForm form;          // stage B's decisions (above)
   Derived dv{}; Shard sh{};
   bool begun = false, have_hyp = false;  // sc_hypothesize_begin_device is done (_end may follow); the hypothesize half is done (finalize may follow)
   sc_params params{};
@@ -55,11 +85,8 @@ struct Pass {
   uint32_t amx_blocks = 0;  // workgroups of the arg-max launch whose pairs this context's finalize step reduces itself (0: one reduced pair in `key`)
   uint64_t* bits_cur = nullptr;  // the adjacency bit matrix: the context's own buffer, or — sharded stage A — the caller's all-gathered one
   bool rows_fused = false;  // run_row_stats already produced edge_off / ebase / cost_pre and armed the edge count
-  bool build = false;       // launch_edge_build: row statistics + edge list + estimating sample in one launch
   bool regular = false;     // every assumption of the host-free form was met (run_select, finalize_wait): note_completed files it as fast_ok
-  bool est_active = false;  // stage B prunes by an estimate
-  bool est_void = false;    // ... which could not be verified on the path taken (event overflow): repeat
-  int ord_state = 0;        // stage B's ordinals: 0 from the scan of the per-edge counts, 1 from the ordered strong list (sc_tri.hip 2c), 2 that form, then an overflow's fall-back through the scan (run_select; sc_debug_last)
+  bool est_void = false;    // stage B's estimate (form.est_active) could not be verified on the path taken (event overflow): repeat
   int est_state = 0;        // 0 certified bound (or no pruning), 1 estimated and verified: finalize_wait's verdict, read by count_frame
   SamplePlan plan{false, 1u, 0};
   // stage C2's reference frame (sc_gramref.hpp): on the hot path the estimating sample leaves candidate triangles behind (ref_cand_n of
@@ -206,7 +233,7 @@ struct sc_ctx : sc::Workspace {  // (the workspace buffers are direct members to
   // run-time probe of the matrix pipe's accumulation model (sc_score.hip gram_guard): 0 not run, 1 holds, 2 violated
   int gram_guard = 0; float gram_guard_worst = 0.f;
 
-  // ---- history: what a completed call leaves for the next one (note_completed writes it, fast_plan / room_of / edge_build_ok read it)
+  // ---- history: what a completed call leaves for the next one (note_completed writes it; fast_plan / room_of / edge_build_ok, sc_capi_tri.hip, read it)
   bool fast_ok = false;      // the last completed call was regular (events, a-priori window, T triangles found): the next may be enqueued host-free
   uint64_t E_last = 0, M_last = 0;
   int last_n = 0;
@@ -481,6 +508,24 @@ int run_compat(sc_ctx* c, bool dense);
 int run_row_stats(sc_ctx* c, bool will_prune, bool hot = false);
 inline bool may_prune(const sc_params* p) { return p->rank_mode == SC_RANK_WEIGHT && !(p->flags & SC_FLAG_NO_PRUNE); }
 int run_triangles(sc_ctx* c, const sc_params* p, bool want_list);
+
+// ---- stage B's host side: defined in sc_capi_tri.hip, called by sc_capi.hip (what each does is said at its definition).  SC_LOCAL:
+// shared by the host files and no part of the library's dynamic symbol table.
+#define SC_LOCAL __attribute__((visibility("hidden")))
+SC_LOCAL int run_edges(sc_ctx* c, const sc_params* p, uint32_t* hist, uint32_t part, uint32_t parts);
+SC_LOCAL int run_select(sc_ctx* c, const sc_params* p, const uint32_t* hist, bool want_list);
+SC_LOCAL int ensure_compaction(sc_ctx* c, size_t nb, size_t nb_room, uint32_t T_eff);
+SC_LOCAL int run_compaction(sc_ctx* c, const KeyView& view, size_t nb, int rounds, uint64_t* host_short);
+inline int select_rounds(bool window) { return window ? 2 : 3; }  // the a-priori window spares the round that measures the key range
+SC_LOCAL bool window_known(const sc_params* p);
+SC_LOCAL uint32_t select_want(const sc_ctx* c, const sc_params* p);
+SC_LOCAL bool edge_build_ok(const sc_ctx* c, const sc_params* p, int64_t n, bool may_estimate);
+SC_LOCAL int ensure_frame(sc_ctx* c);
+SC_LOCAL bool shape_continues(const sc_ctx* c);
+// what a host-free frame assumes (one page of sc_capi_tri.hip): the plan, the validation at its end, what the completed call leaves
+SC_LOCAL bool fast_plan(const sc_ctx* c, int64_t n, const sc_params* p, PassMode* mode);
+SC_LOCAL bool hostfree_valid(const sc_ctx* c, uint64_t E, uint64_t M);
+SC_LOCAL bool hostfree_next_ok(const sc_ctx* c, bool regular);
 int decide_filter(sc_ctx* c, const sc_params* p, const Shard& sh);
 int run_score(sc_ctx* c, const sc_params* p, const Shard& sh, uint32_t* rows, bool tile_done, hipEvent_t ev0 = nullptr,
               hipEvent_t ev1 = nullptr, hipEvent_t ev_mid = nullptr);
