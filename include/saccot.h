@@ -50,6 +50,7 @@ extern "C" {
 #define SC_HAS_ASSIGN 1  /* this header declares sc_assign_poses* and sc_assign_default_params (added within 0.10) */
 #define SC_HAS_SETTLE 1  /* this header declares sc_settle_poses* and sc_settle_default_params (added within 0.10) */
 #define SC_HAS_MERGE 1  /* this header declares sc_merge_poses* and sc_merge_default_params (added within 0.10) */
+#define SC_HAS_PAIRS_CYCLES 1  /* this header declares sc_pairs_cycles*, sc_cycles_default_params and sc_cycles_thresholds (added within 0.10) */
 #define SC_HAS_MATCH_GUIDED 1  /* this header declares sc_match_guided*, sc_register_guided_features and sc_guide_default_params (added within 0.10) */
 #define SC_HAS_MATCH_GUIDED_POSES 1  /* this header declares sc_match_guided_poses*, sc_register_guided_poses_features and SC_GUIDE_MAX_POSES (added within 0.10) */
 #define SC_HAS_MATCH_GUIDED_BATCH 1  /* this header declares sc_match_guided_batch*, sc_match_guided_pairs* and sc_register_guided_{batch,pairs}_features_device (added within 0.10) */
@@ -847,6 +848,103 @@ int sc_register_guided_pairs_features_device(sc_ctx* ctx, const float* d_pts, co
                                              const sc_guide_params* gp, const void* d_pose, uint32_t pose_stride,
                                              const sc_params* params, sc_batch_result* d_res, int32_t* d_corr, float* d_d2,
                                              float* d_g2, uint32_t* d_count, uint8_t* d_mask);
+
+/* ---- loop consistency of a pair list's poses: sc_pairs_cycles ------------------------------------------------------
+ * The pairs entries leave a relative pose per pair on the device, and their caller — a loop-closure or fragment-registration back
+ * end — takes each as an edge of a pose graph.  A wrong pairwise registration (a repeated structure, a symmetric object) has a high
+ * inlier count and a well-conditioned information matrix: nothing computed per pair tells it from a right one.  The other pairs do:
+ * three pairs on three sets close a loop, and the composed motion round the loop is the identity or it is not.  These entries count,
+ * for every pair, the loops of three it closes and the consistent ones among them, and prune the list to a fixed point: rigidity
+ * triangles that vote, one level up — sets for points, poses for lengths.  On the device, stream-ordered behind the entries that
+ * produce the poses, no host word in between.
+ *
+ * Inputs.  n_sets; pairs: a HOST array of 2 * n_pairs words, exactly the list of sc_match_pairs — pair p relates source set
+ * pairs[2p] to target set pairs[2p + 1], in any order; self pairs and repeated pairs are legal, and (a, b) and (b, a) may both be
+ * listed.  The library copies the list and keeps no pointer.  d_pose: n_pairs pose records, pose_stride bytes apart, under the rules
+ * of every pose entry: float Rt[12] at byte 0 (R row-major, then t) maps the SOURCE set's coordinates onto the TARGET's; with
+ * SC_CYCLES_STATUS an int32 status at byte 48; pose_stride a multiple of 4, at least 48, at least 52 with the flag; read, never
+ * written.  sc_batch_result (80), sc_polish_batch_result (64) and plain 12-float records (48) all fit.  d_keep: n_pairs bytes or
+ * NULL; a pair with keep[p] != 0 is never dropped (odometry edges) and still takes part in loops.
+ * Thresholds, derived on the host in double: tr_min = 1.0 + 2.0 * cos((double)rot_tol), e2_max = (double)trans_tol *
+ * (double)trans_tol.  sc_cycles_thresholds returns exactly the two values a call uses.
+ *
+ * Definitions.  The call is a function of the list, the poses, keep and the parameters alone, bit for bit.  All arithmetic is fp64
+ * on the exactly widened fp32 entries; every operation is a plain rounded product or sum in the order written; nothing is fused.
+ *   valid(p)   Rt is finite and, where a status is read, it is SC_OK.
+ *   edge(p)    valid(p) and pairs[2p] != pairs[2p + 1].
+ *   T(x->y)    from pair p: stored as (x, y): (R, t); stored as (y, x): (R^T, t') with
+ *              t'_c = -((R_0c * t_0 + R_1c * t_1) + R_2c * t_2).
+ *   M = B o A  M.R_ij = ((B.R_i0 * A.R_0j + B.R_i1 * A.R_1j) + B.R_i2 * A.R_2j)
+ *              M.t_i  = ((B.R_i0 * A.t_0 + B.R_i1 * A.t_1) + B.R_i2 * A.t_2) + B.t_i
+ *   triangle   three edges p, q, r on three distinct sets a < b < c, p on {a, b}, q on {b, c}, r on {a, c}.  Repeated pairs are edges
+ *              of their own: two pairs on {a, b} give two triangles with the same q and r.  Its error is
+ *              E = T_r(c->a) o (T_q(b->c) o T_p(a->b)), with tr = (E.R_00 + E.R_11) + E.R_22 and
+ *              e2 = (E.t_0 * E.t_0 + E.t_1 * E.t_1) + E.t_2 * E.t_2.
+ *   consistent tr >= tr_min && e2 <= e2_max.  Finite fp32 poses cannot overflow these chains: there is no NaN to order.
+ *   rounds     alive_0 = edge.  Round k = 1, 2, ...: ok_k(p) = the consistent triangles of p whose three pairs are all in
+ *              alive_{k-1}; alive_k(p) = alive_{k-1}(p) && (ok_k(p) >= min_ok || keep[p]).  The rounds stop after the first round K
+ *              with alive_K == alive_{K-1} (stable), or at K = max_rounds.  The stable result is the largest sub-list in which
+ *              every unprotected pair closes at least min_ok consistent loops inside the sub-list; it does not depend on order.
+ * Outputs.  sc_cycle_result (48 bytes) per pair at d_res[p]; an invalid pair or a self pair has every count 0, min_trace 3.0,
+ * max_e2 0.0, is never alive and takes part in nothing: its neighbours are untouched.  sc_cycle_summary (32 bytes) at d_sum.
+ * Forms.  sc_pairs_cycles_device: poses, keep and outputs in HBM; it enqueues and returns without waiting, reads no host word, and
+ * its number of stream operations depends on max_rounds only, never on n_pairs or the graph (a copy, a memset, max_rounds + 2
+ * launches; a round's launch returns at once when the list is already stable).  (It may wait for the previous batch call's copy
+ * out of the staging area the batch entries share.)  sc_pairs_cycles: host arrays; waits.  Like every batch entry they end the
+ * frame a context may hold.
+ * Errors: the CALL returns SC_EINVAL, decided on the host before anything is enqueued, sc_last_error naming which: a NULL argument
+ * other than d_keep (a NULL ctx: no text); n_sets == 0, n_pairs == 0 or n_pairs > SC_CYCLES_MAX_PAIRS; a set index >= n_sets; a set
+ * named by more than SC_CYCLES_MAX_DEGREE listed pairs (a self pair names its set once) — then no uint32 count can overflow: a
+ * pair's triangles are at most deg a * deg b; size wrong, max_rounds outside 1 .. 64, rot_tol not finite or outside [0, pi] (the
+ * float nearest pi is accepted), trans_tol not finite or negative, an unknown flag or a non-zero reserved word; a pose_stride that
+ * breaks the pose rule; a call outstanding on the context.
+ * Workspace: the copied list with every set's sorted neighbour entries, the oriented fp64 poses (192 bytes a pair), two alive bytes
+ * a pair and the round words; the host form adds device copies of its arrays.  Allocated by the first such call, counted in
+ * workspace_bytes and held against the cap (SC_ENOMEM, nothing enqueued).  A context that never calls these entries allocates and
+ * runs nothing new.
+ * Not here: solving the pose graph; loops longer than three; weighting a loop's test by the pairs' information matrices; a sharded
+ * form. */
+#define SC_CYCLES_STATUS     1u         /* flags: a pose record holds an int32 status at byte 48 */
+#define SC_CYCLES_MAX_PAIRS  4194304u   /* 2^22 */
+#define SC_CYCLES_MAX_DEGREE 65535u     /* listed pairs that may name one set */
+typedef struct sc_cycle_params {   /* 32 bytes */
+  uint32_t size;         /* = sizeof(sc_cycle_params)                                  */
+  uint32_t min_ok;       /* consistent loops an unprotected pair must close; default 1 */
+  uint32_t max_rounds;   /* 1 .. 64; default 16                                        */
+  uint32_t flags;        /* SC_CYCLES_STATUS or 0                                      */
+  float    rot_tol;      /* radians, finite, in [0, pi]                                */
+  float    trans_tol;    /* finite, >= 0, in the poses' unit                           */
+  uint32_t reserved[2];  /* must be 0                                                  */
+} sc_cycle_params;
+typedef struct sc_cycle_result {   /* 48 bytes */
+  int32_t  status;         /* SC_OK, the status passed through, or SC_EINVAL for a non-finite Rt */
+  uint32_t cycles;         /* triangles of alive_0 that contain p                      */
+  uint32_t ok;             /* the consistent ones among them                           */
+  uint32_t ok_alive;       /* ok_K(p); 0 if p is not in alive_{K-1}                    */
+  uint32_t alive;          /* alive_K(p)                                               */
+  uint32_t dropped_round;  /* the k at which p left; 0 if it is alive or never was an edge */
+  double   min_trace;      /* min tr over p's `cycles` triangles; 3.0 when cycles is 0 */
+  double   max_e2;         /* max e2 over p's `cycles` triangles; 0.0 when cycles is 0 */
+  uint32_t reserved[2];    /* written as 0                                             */
+} sc_cycle_result;
+typedef struct sc_cycle_summary {  /* 32 bytes */
+  uint32_t rounds;         /* K                                                        */
+  uint32_t stable;         /* 1: alive_K == alive_{K-1}                                */
+  uint32_t alive;          /* pairs in alive_K                                         */
+  uint32_t edges;          /* pairs in alive_0                                         */
+  uint64_t triangles;      /* triangles of alive_0                                     */
+  uint64_t consistent;     /* the consistent ones among them                           */
+} sc_cycle_summary;
+int sc_cycles_default_params(sc_cycle_params* cp);   /* size, min_ok 1, max_rounds 16; everything else 0: the tolerances are the caller's */
+/* host only, no context: out[0] = tr_min, out[1] = e2_max; SC_EINVAL for a NULL argument, a wrong size or a tolerance out of range */
+int sc_cycles_thresholds(const sc_cycle_params* cp, double out[2]);
+/* pairs a HOST array; d_pose n_pairs records of pose_stride bytes, d_keep n_pairs bytes or NULL, d_res n_pairs records, d_sum one */
+int sc_pairs_cycles_device(sc_ctx* ctx, uint32_t n_sets, const uint32_t* pairs, uint32_t n_pairs, const sc_cycle_params* cp,
+                           const void* d_pose, uint32_t pose_stride, const uint8_t* d_keep, sc_cycle_result* d_res,
+                           sc_cycle_summary* d_sum);
+/* the same with host arrays (pose, keep, res, sum); waits */
+int sc_pairs_cycles(sc_ctx* ctx, uint32_t n_sets, const uint32_t* pairs, uint32_t n_pairs, const sc_cycle_params* cp,
+                    const void* pose, uint32_t pose_stride, const uint8_t* keep, sc_cycle_result* res, sc_cycle_summary* sum);
 
 /* ---- descriptor matching gated by several poses: sc_match_guided_poses --------------------------------------------
  * The entrance of the multi-motion chain: sc_register_instances / sc_peel find K rigid motions, sc_polish_poses refits them,

@@ -193,6 +193,31 @@ MERGE_POSE_DTYPE = np.dtype(ScMergePose)  # sc_merge_pose as a numpy record
 SC_MERGE_MAX_POSES, SC_MERGE_BATCH_MAX_POSES = 1024, 64
 SC_MERGE_OVER_MIN, SC_MERGE_OVER_UNION = 0, 1
 SC_MERGE_STATUS, SC_MERGE_COMPACT = 1, 2
+
+
+class ScCycleParams(C.Structure):
+    """Mirror of `sc_cycle_params` (include/saccot.h), 32 bytes: the consistent loops an unprotected pair must close, the rounds at
+    most (1 .. 64), SC_CYCLES_STATUS or 0, the rotation tolerance (radians, in [0, pi]) and the translation tolerance (>= 0)."""
+    _fields_ = [("size", C.c_uint32), ("min_ok", C.c_uint32), ("max_rounds", C.c_uint32), ("flags", C.c_uint32), ("rot_tol", C.c_float),
+                ("trans_tol", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
+class ScCycleResult(C.Structure):
+    """Mirror of `sc_cycle_result` (include/saccot.h), 48 bytes: one pair's record of sc_pairs_cycles."""
+    _fields_ = [("status", C.c_int32), ("cycles", C.c_uint32), ("ok", C.c_uint32), ("ok_alive", C.c_uint32), ("alive", C.c_uint32),
+                ("dropped_round", C.c_uint32), ("min_trace", C.c_double), ("max_e2", C.c_double), ("reserved", C.c_uint32 * 2)]
+
+
+class ScCycleSummary(C.Structure):
+    """Mirror of `sc_cycle_summary` (include/saccot.h), 32 bytes: the rounds run, whether the list is stable, the pairs alive at the
+    end and at the start, the triangles of the start and the consistent ones among them."""
+    _fields_ = [("rounds", C.c_uint32), ("stable", C.c_uint32), ("alive", C.c_uint32), ("edges", C.c_uint32), ("triangles", C.c_uint64),
+                ("consistent", C.c_uint64)]
+
+
+CYCLE_RESULT_DTYPE = np.dtype(ScCycleResult)    # sc_cycle_result as a numpy record
+CYCLE_SUMMARY_DTYPE = np.dtype(ScCycleSummary)  # sc_cycle_summary as a numpy record
+SC_CYCLES_STATUS, SC_CYCLES_MAX_PAIRS, SC_CYCLES_MAX_DEGREE = 1, 1 << 22, 65535
 SC_GUIDE_POSE_STATUS = 1  # sc_guide_params.flags, the sc_match_guided_batch / _poses entries only: the pose records hold an int32 status at byte 48
 SC_GUIDE_MAX_POSES = 64  # pose records per call of sc_match_guided_poses at most
 SC_MATCH_BATCH_MAX_N = 4096  # rows a side of one problem of sc_match_batch
@@ -258,6 +283,7 @@ _INT, _I64, _U32, _VP = C.c_int, C.c_int64, C.c_uint32, C.c_void_p
 _F32P, _U8P, _I32P, _U32P, _U64P = (C.POINTER(t) for t in (C.c_float, C.c_uint8, C.c_int32, C.c_uint32, C.c_uint64))
 _PP, _SP, _QP, _MP, _GP = (C.POINTER(t) for t in (ScParams, ScStats, ScPolishParams, ScMatchParams, ScGuideParams))
 _IP, _ZP, _AP, _TP, _RP = (C.POINTER(t) for t in (ScPoseInfoParams, ScPolishPosesParams, ScAssignParams, ScSettleParams, ScMergeParams))
+_CP = C.POINTER(ScCycleParams)
 _PROTOTYPES = {
     "sc_version": [],
     "sc_strerror": ([_INT], C.c_char_p),
@@ -343,6 +369,10 @@ _PROTOTYPES = {
     "sc_merge_poses_frame_device": [_VP, _RP, _VP, _U32, _U32, _VP, _VP, _VP, _VP, _VP],
     "sc_merge_poses_batch": [_VP, _F32P, _F32P, _U32P, _U32, _PP, _RP, _VP, _U32, _U32, _VP, _VP, _VP],
     "sc_merge_poses_batch_device": [_VP, _VP, _VP, _U32P, _U32, _PP, _RP, _VP, _U32, _U32, _VP, _VP, _VP],
+    "sc_cycles_default_params": [_CP],
+    "sc_cycles_thresholds": [_CP, C.POINTER(C.c_double)],
+    "sc_pairs_cycles": [_VP, _U32, _U32P, _U32, _CP, _VP, _U32, _U8P, _VP, _VP],
+    "sc_pairs_cycles_device": [_VP, _U32, _U32P, _U32, _CP, _VP, _U32, _VP, _VP, _VP],
     "sc_hypothesize_device": [_VP, _VP, _VP, _I64, _PP, _VP, _SP],
     "sc_finalize_device": [_VP, _VP, _VP, _VP, _SP],
     "sc_hypothesize_begin_device": [_VP, _VP, _VP, _I64, _PP, _VP, _SP],
@@ -448,6 +478,21 @@ def make_merge_params(measure: int = SC_MERGE_OVER_MIN, num: int = 1, den: int =
     """sc_merge_params: measure SC_MERGE_OVER_*, the fraction num / den (1 <= num <= den <= 65536), min_count, sel_mode
     SC_ASSIGN_SEL_*, flags SC_MERGE_STATUS | SC_MERGE_COMPACT or 0."""
     return _sized(ScMergeParams, measure, num, den, min_count, sel_mode, flags)
+
+
+def make_cycle_params(rot_tol: float, trans_tol: float, min_ok: int = 1, max_rounds: int = 16, flags: int = 0) -> ScCycleParams:
+    """sc_cycle_params: the tolerances (rot_tol in radians, in [0, pi]; trans_tol >= 0) are the caller's; min_ok, max_rounds 1 .. 64,
+    flags SC_CYCLES_STATUS or 0."""
+    return _sized(ScCycleParams, min_ok, max_rounds, flags, rot_tol, trans_tol)
+
+
+def cycles_thresholds(cparams: ScCycleParams) -> tuple[float, float]:
+    """sc_cycles_thresholds: (tr_min, e2_max), exactly the two values a call with these parameters uses."""
+    out = (C.c_double * 2)()
+    rc = load_library().sc_cycles_thresholds(C.byref(cparams), out)
+    if rc != SC_OK:
+        raise SacCotError(rc, "sc_cycles_thresholds")
+    return out[0], out[1]
 
 
 def shard_plan(params: ScParams, n: int) -> ScShardPlan:
@@ -1517,6 +1562,36 @@ class Registrar:
         self._frame_n = 0
         self._check(self._lib.sc_merge_poses_batch_device(self._h, d_src, d_tgt, _p(offset), nb, C.byref(params), C.byref(mparams),
                                                           d_pose, pose_stride, n_poses, d_out, d_parent, d_count or None))
+
+    # ---- loop consistency of a pair list's poses (include/saccot.h, sc_pairs_cycles) --------------------------------------------
+    def pairs_cycles(self, n_sets: int, pairs, pose, cparams: ScCycleParams | None = None, keep=None, **kw):
+        """sc_pairs_cycles: pairs (P, 2) set indices (source, target); pose (P,) records of any dtype whose items start with float
+        Rt[12] (and, with SC_CYCLES_STATUS, an int32 status at byte 48) — or a float32 array (P, 12); keep None or (P,) uint8, non-zero:
+        never dropped -> (records (P,) of CYCLE_RESULT_DTYPE, summary: one record of CYCLE_SUMMARY_DTYPE).  kw: rot_tol, trans_tol,
+        min_ok, max_rounds, flags (make_cycle_params)."""
+        q = cparams or make_cycle_params(**kw)
+        pairs = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1)
+        npairs = len(pairs) // 2
+        pose, stride = self._pose_records(pose, npairs)
+        if keep is not None:
+            keep = np.ascontiguousarray(keep, dtype=np.uint8).reshape(-1)
+            if len(keep) != npairs:
+                raise ValueError("pairs_cycles: keep holds one byte per pair")
+        res = np.zeros(max(npairs, 1), CYCLE_RESULT_DTYPE)
+        summary = np.zeros(1, CYCLE_SUMMARY_DTYPE)
+        self._frame_n = 0
+        self._check(self._lib.sc_pairs_cycles(self._h, n_sets, _p(pairs), npairs, C.byref(q), _vp(pose), stride, _p(keep), _vp(res), _vp(summary)))
+        return res[:npairs], summary[0]
+
+    def pairs_cycles_device(self, n_sets: int, pairs, cparams: ScCycleParams, d_pose: int, pose_stride: int, d_keep: int, d_res: int,
+                            d_sum: int):
+        """sc_pairs_cycles_device: pairs a HOST array (P, 2); pose records (pose_stride bytes each, read only), the keep bytes (0:
+        none), the output records (P of 48 bytes) and the summary (32 bytes) in HBM; enqueues on the context's stream — a number of
+        operations that depends on max_rounds only — and returns without waiting."""
+        pairs = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1)
+        self._frame_n = 0
+        self._check(self._lib.sc_pairs_cycles_device(self._h, n_sets, _p(pairs), len(pairs) // 2, C.byref(cparams), d_pose, pose_stride,
+                                                     d_keep or None, d_res, d_sum))
 
     def hypothesize_device(self, d_src: int, d_tgt: int, n: int, params: ScParams, d_key: int):
         st = ScStats(C.sizeof(ScStats))

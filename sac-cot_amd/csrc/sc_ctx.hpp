@@ -181,7 +181,11 @@ struct Workspace {
       // sc_merge_poses: allocated by the first such call, never by a frame or by another entry.  rows: the frame form's support sets,
       // n_poses x ceil(n / 64) u64, and behind them the 2 x n_poses tally words; table: the overlap table where the caller passes none;
       // off: the batch form's copy of the caller's offsets; the rest: device copies of the host entries' arrays
-      mrg_rows, mrg_table, mrg_off, mrg_src, mrg_tgt, mrg_pose, mrg_sel, mrg_out, mrg_parent, mrg_overlap, mrg_count;
+      mrg_rows, mrg_table, mrg_off, mrg_src, mrg_tgt, mrg_pose, mrg_sel, mrg_out, mrg_parent, mrg_overlap, mrg_count,
+      // sc_pairs_cycles: allocated by the first such call, never by a frame or by another entry.  meta: the pairs' records and the
+      // sorted neighbour entries (sc_cycles_check.hpp); wide: the oriented fp64 poses; state: the round words and the two buffers of
+      // alive bytes; the rest: device copies of the host entry's arrays
+      cyc_meta, cyc_wide, cyc_state, cyc_pose, cyc_keep, cyc_res, cyc_sum;
 };
 constexpr size_t N_WORKSPACE_BUFS = sizeof(Workspace) / sizeof(Buf);
 static_assert(std::is_standard_layout<Workspace>::value && alignof(Workspace) == alignof(Buf) && sizeof(Workspace) == N_WORKSPACE_BUFS * sizeof(Buf),

@@ -1036,6 +1036,46 @@ struct MergeBatchJob : PoseBatchHead {
 // ONE launch, a workgroup per problem; every record, parent and word pair is written (complete in stream order).
 void launch_merge_batch(const MergeBatchJob& job, hipStream_t st);
 
+// ---- loop consistency of a pair list's poses (sc_pairs_cycles; sc_cycles.hip) -------------------------------------------------
+// One pair's record and the summary: sc_cycle_result and sc_cycle_summary of include/saccot.h, field for field (sc_cycles.hip
+// asserts the sizes and the offsets).
+struct CycleRecord {
+  int32_t status;
+  uint32_t cycles, ok, ok_alive, alive, dropped_round;
+  double min_trace, max_e2;
+  uint32_t reserved[2];
+};
+struct CycleSummary {
+  uint32_t rounds, stable, alive, edges;
+  uint64_t triangles, consistent;
+};
+// The round words, ZERO at launch: dropped[k], k = 1 .. max_rounds, the pairs round k dropped — a round's launch returns at once
+// when the round before dropped none, and writes nothing, so every later word stays 0 as well; dropped[0] is never read.
+struct CyclesCtl {
+  uint32_t dropped[65];
+  uint32_t edges;                  // pairs in alive_0
+  uint64_t triangles, consistent;  // of alive_0, each counted by its pair on the two lowest sets
+};
+// rec: the pairs' records, entries: the sorted neighbour lists (sc_cycles_check.hpp); pose: the caller's records; keep: nullptr or
+// n_pairs bytes; wide: 2 x 12 doubles a pair; alive: 2 x n_pairs bytes, buffer k & 1 holds alive_k; res: n_pairs; sum: one.
+struct CyclesJob {
+  const uint32_t* rec;
+  const uint64_t* entries;
+  const void* pose;
+  const uint8_t* keep;
+  double* wide;
+  uint8_t* alive;
+  CyclesCtl* ctl;
+  CycleRecord* res;
+  CycleSummary* sum;
+  double tr_min, e2_max;
+  uint32_t n_pairs, pose_stride, min_ok, max_rounds;
+  int status;  // a record holds a status at byte 48
+};
+// max_rounds + 2 launches: prepare (validity, the oriented fp64 poses, alive_0, every record's head), a launch per round (a wave per
+// pair: its two sorted lists intersected, the loops composed, the verdict), finish (the summary).
+void launch_pairs_cycles(const CyclesJob& job, hipStream_t st);
+
 // ---- descriptor matching for a batch of small problems (sc_match_batch; sc_match_batch.hip) -----------------
 // Problem b owns rows [src_off[b], src_off[b + 1]) of fsrc and [tgt_off[b], tgt_off[b + 1]) of ftgt (1 .. MATCH_BATCH_MAX_N rows
 // each, checked by the caller) and the output slot that starts at entry slot[b] = src_off[b] * knn.  tile_map: n_tiles pairs
