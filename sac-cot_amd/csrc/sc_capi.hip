@@ -1,6 +1,7 @@
 // sc_capi.hip — the core of the C ABI of include/saccot.h: the context's lifetime and its grow-only device workspace, sc_set_debug /
-// sc_debug_last, pass and frame, the stage sequencers of stages A and C, the lane, and the register, hypothesize, finalize, shard and
-// wait entries.  Stage B's sequencer (run_edges, run_select, the host-free plan) is sc_capi_tri.hip.  The
+// sc_debug_last, pass and frame begin, the stage sequencers of stages A and C, and the hypothesize and shard entries.  Stage B's
+// sequencer (run_edges, run_select, the host-free plan) is sc_capi_tri.hip; a frame's end (the lane, the finalize step, the verdict,
+// the register, finalize and wait entries) is sc_capi_frame.hip.  The
 // rest of the ABI sits in host-only files of its own, on sc_ctx.hpp (sc_ctx itself and the shared helpers): sc_capi_hooks.hip (the
 // sc_*_host stage hooks), sc_capi_peel.hip (sc_peel*, sc_register_instances), sc_capi_match.hip (sc_match*, sc_register_features), sc_capi_polish.hip (sc_polish*),
 // sc_capi_batch.hip (sc_register_batch*).
@@ -115,7 +116,7 @@ int lb_next(sc_ctx* c, size_t bytes, int slot, size_t desc_off, LbArgs* out) {
   return SC_OK;
 }
 
-static TriSource tri_source_of(const sc_ctx* c) {
+TriSource tri_source_of(const sc_ctx* c) {
   TriSource ts{c->sel_ord.as<uint64_t>(), c->kcol.as<uint2>(), c->ei.as<uint32_t>(), c->ej.as<uint32_t>(), nullptr, 0, 0, 0u, 0u, 0ull};
   if (c->pass.mode.host_free) { ts.lim_vertex = (uint32_t)c->pass.n; ts.lim_edge = (uint32_t)c->pass.mode.E_cov; ts.lim_ord = c->pass.mode.M_cov; }
   // an ESTIMATED pruning bound that turns out too high leaves a selection shorter than the T_eff the launches were sized for
@@ -129,9 +130,6 @@ static TriSource tri_source_of(const sc_ctx* c) {
   }
   return ts;
 }
-
-// stage brackets as (first event, second event): stage, compat, triangles, kabsch, score, argmax, mask
-constexpr int STAGE_EV[7][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 4}, {4, 5}, {5, 6}, {7, 8}};
 
 int rec(sc_ctx* c, int i) {
   const bool hot = i == 4 || i == 5;
@@ -324,7 +322,7 @@ void fill_stats(const sc_ctx* c, sc_stats* s) {
                    + 52 * (uint64_t)c->pass.sh.n_local + 24 * n + n;   // C: (R,t) out and in, counts, the correspondences, the mask
 }
 
-static float ev_us_raw(sc_ctx* c, int a, int b) {  // start / stop of kernel dispatches: nothing to subtract
+float ev_us_raw(sc_ctx* c, int a, int b) {  // start / stop of kernel dispatches: nothing to subtract
   float ms = 0.f;
   if (hipEventSynchronize(c->ev[b]) != hipSuccess || hipEventElapsedTime(&ms, c->ev[a], c->ev[b]) != hipSuccess) {
     (void)hipGetLastError();
@@ -464,10 +462,14 @@ int sc_set_stream(sc_ctx* c, void* hip_stream) {
 
 const char* sc_last_error(const sc_ctx* c) { return c ? c->last_error.c_str() : "null context"; }
 
+// sc_set_debug: the next call waits (its launch geometry may differ from the last call's), estimates again and takes its ordinals from
+// the ordered strong list again.  The shape's history stays: the counts are the knobs' in no way.
+static void reset_history(sc_ctx* c) { c->fast_ok = false; c->est.reset(); c->ord_off = false; }
+
 int sc_set_debug(sc_ctx* c, const sc_debug* d) {
   if (!c) return SC_EINVAL;
   SC_TRY(busy(c));
-  if (!d) { c->tn = Tuning(); c->fast_ok = false; c->est_failed = false; c->est_holdoff = 0; c->est_failures = 0; c->ord_off = false; return SC_OK; }
+  if (!d) { c->tn = Tuning(); reset_history(c); return SC_OK; }
   if (d->size != sizeof(sc_debug)) return SC_EINVAL;
   auto tg_ok = [](uint32_t t) { return t == 0 || t == 4 || t == 8 || t == 16 || t == 32 || t == 64; };
   for (int k = 0; k < 4; k++) if (!tg_ok(d->lanes_per_edge[k])) return SC_EINVAL;
@@ -511,8 +513,7 @@ int sc_set_debug(sc_ctx* c, const sc_debug* d) {
 #endif
   t.est_margin_pct = d->est_margin_pct;
   c->tn = t;
-  c->fast_ok = false;  // (the next call waits: its launch geometry may differ from the last call's)
-  c->est_failed = false; c->est_holdoff = 0; c->est_failures = 0; c->ord_off = false;
+  reset_history(c);
   return SC_OK;
 }
 
@@ -553,7 +554,7 @@ namespace sc {
 
 // An entry that continues what an earlier one began (the _end, shard and finalize entries): frame over, context free, the earlier
 // half there — `otherwise` is the refusal's text — then the device
-static int continue_pass(sc_ctx* c, bool in_order, const char* otherwise) {
+int continue_pass(sc_ctx* c, bool in_order, const char* otherwise) {
   SC_TRY(entry_checks(c, nullptr, ENDS_FRAME | NOT_BUSY));
   if (!in_order) { c->last_error = otherwise; return SC_EINVAL; }
   HIPCHK(c, hipSetDevice(c->device));
@@ -562,7 +563,7 @@ static int continue_pass(sc_ctx* c, bool in_order, const char* otherwise) {
 
 // A frame starts here and nowhere else: every entry point that begins a call of its own (not the library's repeat of one) comes
 // through here, and finds nothing of the previous frame
-static int frame_begin(sc_ctx* c) {
+int frame_begin(sc_ctx* c) {
   SC_TRY(entry_checks(c, nullptr, ENDS_FRAME | NOT_BUSY));
   c->frame = Frame{};
   return SC_OK;
@@ -585,10 +586,10 @@ static int pass_begin(sc_ctx* c, const sc_params* p, const PassMode& mode) {
 // A pass ends when its finalize step starts to wait (or its enqueue fails): nothing more is enqueued host-free, whichever way
 // finalize_wait is left — validated, void, failed, timed out.  ensure() and tri_source_of() read the flag, so an entry that starts no
 // pass of its own (a stage hook, a second finalize call) must not find it set.  Returns whether the pass was host-free.
-static bool pass_end(sc_ctx* c) { return std::exchange(c->pass.mode.host_free, false); }
+bool pass_end(sc_ctx* c) { return std::exchange(c->pass.mode.host_free, false); }
 
 // phase 1, first half: staging, stage A, the edge list and this process's share of the pruning sample
-static int hyp_begin(sc_ctx* c, const float* d_src, const float* d_tgt, int64_t n, const sc_params* p, uint32_t* d_hist,
+int hyp_begin(sc_ctx* c, const float* d_src, const float* d_tgt, int64_t n, const sc_params* p, uint32_t* d_hist,
               uint32_t part, uint32_t parts, const PassMode& mode) {
   SC_TRY(check_params(p));
   SC_TRY(pass_begin(c, p, mode));
@@ -614,8 +615,7 @@ static int hyp_begin(sc_ctx* c, const float* d_src, const float* d_tgt, int64_t 
 // flag, THEN data: the staging kernel writes the six box words before the word of maxima, so the maxima are loaded with
 // acquire semantics and the boxes only afterwards (the fence used to sit behind both loads, which only the
 // load order of x86 made right)
-struct CoordStats { uint64_t mx, box[6]; };
-static CoordStats read_coord_stats(const sc_ctx* c) {
+CoordStats read_coord_stats(const sc_ctx* c) {
   CoordStats cs;
   cs.mx = __atomic_load_n(&c->pinned[HW_COORD_MAX], __ATOMIC_ACQUIRE);
   for (int k = 0; k < 6; k++) cs.box[k] = *const_cast<volatile uint64_t*>(&c->pinned[HW_BOX + k]);
@@ -773,7 +773,7 @@ static int run_stage_c(sc_ctx* c, uint64_t* d_key, sc_stats* stats) {
 }
 
 // phase 1, second half: prune with the (summed) histogram, enumerate, select, then stage C on this rank's share
-static int hyp_end(sc_ctx* c, const uint32_t* d_hist, uint64_t* d_key, sc_stats* stats) {
+int hyp_end(sc_ctx* c, const uint32_t* d_hist, uint64_t* d_key, sc_stats* stats) {
   const sc_params* p = &c->pass.params;
   c->pass.begun = false;
   SC_TRY(run_select(c, p, d_hist, false));
@@ -798,7 +798,7 @@ int sc_hypothesize_device(sc_ctx* c, const float* d_src, const float* d_tgt, int
   // without the flag" — the waiting, certifying way handles every case), on every rank alike: stages A and B are replicated.
   PassMode mode{est};
   if (est && check_params(p) == SC_OK) fast_plan(c, n, p, &mode);
-  if (est) c->est_failed = false;  // (the CALLER decides when to stop estimating on this entry; fast_plan above still went by the context's own verdict)
+  if (est) c->est.caller_decides();  // (the CALLER decides when to stop estimating on this entry; fast_plan above still went by the context's own verdict)
   int rc = hyp_begin(c, d_src, d_tgt, n, p, nullptr, 0, 1, mode);  // the whole sample, into the context's histogram
   if (rc == SC_OK) rc = hyp_end(c, nullptr, d_key, stats);
   if (rc != SC_OK && mode.host_free) c->fast_ok = false;
@@ -927,402 +927,6 @@ int sc_shard_score_device(sc_ctx* c, const void* d_cand_all, uint64_t* d_key, sc
   c->pass.T_eff = (uint32_t)c->pinned[HW_MERGED_T];
   c->pass.M = c->pass.M_total = c->pinned[HW_MERGED_M];
   return run_stage_c(c, d_key, stats);
-}
-
-int sc_finalize_device(sc_ctx* c, const uint64_t* d_key, float* d_Rt, uint8_t* d_mask, sc_stats* stats) {
-  return sc_finalize_gathered_device(c, d_key, 1, d_Rt, d_mask, stats);
-}
-
-}  // extern "C" (the halves of the finalize step and the host-free machinery are internal)
-
-namespace sc {
-
-constexpr int SC_ESPEC = -100;  // internal: a host-free call failed validation (never leaves the library)
-
-// ---- the lane (sc_ctx.hpp): a host-free frame of a direct sc_register_device_async call on a caller's stream runs beside that stream
-// Fork: everything the caller enqueued before the call — producers of d_src / d_tgt, earlier readers of d_Rt / d_mask, this context's
-// own earlier launches — is ordered before the frame; from here to the join the frame's launches go to the lane as c->stream.
-static int lane_fork_caller(sc_ctx* c) {
-  HIPCHK(c, hipEventRecord(c->lane_fork, c->stream));
-  HIPCHK(c, hipStreamWaitEvent(c->own_stream, c->lane_fork, 0));
-  c->lane_home = c->stream;
-  c->stream = c->own_stream;
-  c->on_lane = true;
-  return SC_OK;
-}
-// Join (finalize_wait; a no-op off the lane): the caller's stream waits for the event behind the frame's last launch, and is the
-// context's stream again — the validation, a repeat, sc_peel / sc_polish* and the caller's own reads of d_Rt / d_mask follow the
-// frame in stream order, as they do without a lane.
-static int lane_join_caller(sc_ctx* c) {
-  if (!c->on_lane) return SC_OK;
-  c->on_lane = false;
-  c->stream = c->lane_home;
-  HIPCHK(c, hipStreamWaitEvent(c->stream, c->lane_join, 0));
-  return SC_OK;
-}
-// Behind the frame's last launch on the lane: what the join waits for
-static int lane_mark_end(sc_ctx* c) {
-  HIPCHK(c, hipEventRecord(c->lane_join, c->stream));
-  return SC_OK;
-}
-// The enqueue failed half-way: what reached the lane runs out (no join was recorded), then the caller's stream is the context's again
-static void lane_drain(sc_ctx* c) {
-  if (!c->on_lane) return;
-  (void)hipStreamSynchronize(c->own_stream);
-  c->on_lane = false;
-  c->stream = c->lane_home;
-}
-
-// phase 2, first half: the winner / mask kernel (and the optional refit) are enqueued; nothing is waited for
-static int finalize_enqueue(sc_ctx* c, const uint64_t* d_keys, int n_pairs, float* d_Rt, uint8_t* d_mask) {
-  SC_TRY(rec(c, 7));
-  ControlBlock* ctl = c->ctl.as<ControlBlock>();
-  arm_word(c, HW_WINNER);
-  // a host-free call's kernels have published nothing yet: this one hands the counts and the coordinate statistics over with the winner
-  DeferredPub dp{c->edge_off.as<uint64_t>() + c->pass.n, c->toff.as<uint64_t>() + c->pass.E, c->fx_mx.as<uint32_t>(),
-                 reinterpret_cast<unsigned long long*>(c->pinned), (c->n_fast_ok & 63u) == 63u ? 1 : 0};
-  if (d_keys == c->key.as<uint64_t>() && n_pairs == 1 && c->pass.amx_blocks) { d_keys = c->amx_pairs.as<uint64_t>(); n_pairs = (int)c->pass.amx_blocks; }
-  launch_finalize(points_of(c), tri_source_of(c), c->pass.sh, c->pass.sh.n_local ? c->rt.as<float>() : nullptr,
-                  c->pass.T_eff ? c->sel_key.as<uint32_t>() : nullptr, c->pass.T_eff, d_keys, n_pairs,
-                  ctl->key2, c->pass.dv.tau2, d_Rt, d_mask, &ctl->fin_word, &c->pinned[HW_WINNER], c->stream,
-                  c->pass.mode.host_free ? &dp : nullptr);
-  if (c->pass.refine) {  // fp64 least-squares refit over the winner's inliers (mask unchanged)
-    ENSURE(c, c->refine_tmp, refine_scratch_bytes(c->pass.n));
-    launch_refine(points_of(c), d_mask, ctl->key2, c->refine_tmp.as<double>(), d_Rt, c->stream);
-  }
-  return rec(c, 8);
-}
-
-// what the next call on this context may assume (fast_plan): the call that just completed was a "regular" one
-static void note_completed(sc_ctx* c, bool regular) {
-  c->fast_ok = hostfree_next_ok(c, regular);
-  if (!shape_continues(c)) { c->E_hi[0] = c->E_hi[1] = c->M_hi[0] = c->M_hi[1] = 0; c->hi_n = 0; c->hi_seen = 0; }
-  if (c->fast_ok) {  // (the counts of a regular call of this shape: what a host-free repetition has to cover)
-    if (c->hi_seen < 0xFFFFFFFFu) c->hi_seen++;
-    if (c->pass.E > c->E_hi[0]) c->E_hi[0] = c->pass.E;
-    if (c->pass.M > c->M_hi[0]) c->M_hi[0] = c->pass.M;
-    if (++c->hi_n >= sc_ctx::HI_WINDOW) { c->E_hi[1] = c->E_hi[0]; c->M_hi[1] = c->M_hi[0]; c->E_hi[0] = c->M_hi[0] = 0; c->hi_n = 0; }
-  }
-  c->E_last = c->pass.E; c->M_last = c->pass.M; c->last_n = c->pass.n;
-  c->last_p = c->pass.params;
-  if (c->est_failed && !c->frame.est_failed_call && c->est_holdoff != 0 && --c->est_holdoff == 0) c->est_failed = false;  // (the repeat itself does not count)
-  // (the call is complete: its staging kernel's words have arrived — unless it was a host-free call, whose statistics travel with
-  // the winner only now and then: DeferredPub; the last ones known stay)
-  const CoordStats cs = read_coord_stats(c);
-  if (cs.mx != ~0ull) {
-    c->mx_last = cs.mx;
-    for (int k = 0; k < 6; k++) c->box_last[k] = cs.box[k];
-  }
-  // room for the event list of a call like this one: an event holds >= 1 triangle, so 2 M records can only overflow a region
-  // on a fill 2 x off the mean (the regions fill evenly: a wave moves to the next one with every flush)
-  if (c->pass.form.use_events && c->ev_capacity < 2 * c->pass.M) c->ev_capacity = 2 * c->pass.M < (1ull << 28) ? 2 * c->pass.M : (1ull << 28);
-}
-
-// phase 2, second half: wait for the winner; a host-free call is validated here
-static int finalize_wait(sc_ctx* c, sc_stats* stats) {
-  // The finalize kernel publishes key / position / rank.  On a caller-provided stream (sc_set_stream) d_Rt and d_mask
-  // are complete in stream order, like any other work the caller enqueues there; on the context's private stream —
-  // which the caller cannot order against — and when the per-stage events are read below, wait for everything.
-  // "Private" means that no caller's stream is set — a frame on its lane has the private stream as c->stream and is polled for.
-  const bool was_spec = pass_end(c);
-  if (c->pass.timing || !c->caller_stream) HIPCHK(c, hipStreamSynchronize(c->stream));
-  else if (c->pass.timing_one == 6) HIPCHK(c, hipEventSynchronize(c->ev[8]));  // the mask bracket ends after the kernel polled below
-  const int rc_winner = wait_word(c, HW_WINNER);  // (a lane frame: polled, or after 1 ms synchronised, on the lane)
-  const int rc_join = lane_join_caller(c);        // ... and before anything else the caller's stream is behind the frame
-  if (rc_winner) { c->fast_ok = false; return rc_winner; }
-  if (rc_join) { c->fast_ok = false; return rc_join; }
-  HIPCHK(c, hipGetLastError());
-  if (was_spec) {
-    // Host-free call: every kernel of it has finished (the winner word is the last thing the stream writes), so the two
-    // counts and the flags are final.  The launches covered E_cov edges and M_cov keys and assumed T triangles exist, an
-    // event list that did not overflow and a graph big enough to prune: anything else and the outputs are void — the
-    // caller (sc_wait) repeats the call the waiting way, which handles every one of these cases.
-    if ((uint32_t)c->pinned[HW_BAD_INPUT] != 0) { c->fast_ok = false; c->last_error = "non-finite input coordinate"; return SC_EINVAL; }
-    // (the finalize kernel handed both counts over in one word: DeferredPub)
-    const uint64_t em = c->pinned[HW_EDGES];
-    const uint64_t E = em == PIN_PENDING ? PIN_PENDING : (em & 0xFFFFFFFFull), M = em == PIN_PENDING ? PIN_PENDING : (em >> 32);
-    if (!hostfree_valid(c, E, M)) {
-      char buf[256];  // (why, for sc_last_error: the repeat itself is silent)
-      snprintf(buf, sizeof buf, "host-free call repeated: edges %llu (covered %llu), triangles %llu (covered %llu, T %u), event overflow %u",
-               (unsigned long long)E, (unsigned long long)c->pass.mode.E_cov, (unsigned long long)M, (unsigned long long)c->pass.mode.M_cov,
-               c->pass.params.max_triangles, (uint32_t)c->pinned[HW_EV_OVERFLOW]);
-      c->last_error = buf;
-      c->fast_ok = false;
-      if (chunk_overflow(c)) c->ord_off = true;  // (the repeat, and the calls after it, scan the per-edge counts)
-      else if ((uint32_t)c->pinned[HW_EV_OVERFLOW] != 0 && c->ev_capacity < (1ull << 28)) c->ev_capacity *= 2;  // (the repeat must not overflow again)
-      return SC_ESPEC;
-    }
-    c->pass.E = E; c->pass.M = c->pass.M_total = M;
-    c->frame.fast_state = 1;
-    c->pass.regular = true;
-  }
-  c->pass.est_state = c->pass.form.est_active ? 1 : 0;
-  // SC_EBOUND: the caller repeats the call without the flag (include/saccot.h), on every rank alike
-  static const char* const bound_too_high = "the estimated pruning bound was too high for this input: repeat the call without SC_FLAG_EST_BOUND";
-  if (c->pass.sharded_ab && c->pass.form.est_active && (c->pinned[HW_MERGE_SHORT] != 0 || c->pass.est_void)) {
-    c->last_error = bound_too_high;  // (every rank holds the same gathered blobs, so every rank ends here together)
-    return SC_EBOUND;
-  }
-  if (c->pinned[HW_SELECT_SHORT] != 0 || (c->pass.form.est_active && c->pass.est_void)) {
-    // select_round_kernel: fewer keys at or above the pruning bound than it promised (or the bound went unverified)
-    if (!c->pass.form.est_active) {  // a CERTIFIED bound holds by construction: this would be a defect, not an input
-      c->last_error = "internal: the select found fewer keys above a certified pruning bound than the certificate counted";
-      return SC_EHIP;
-    }
-    if (c->pass.params.flags & SC_FLAG_EST_BOUND) {  // sc_hypothesize_device + sc_finalize*_device
-      c->last_error = bound_too_high;
-      c->frame.est_failed_call = true;
-      return SC_EBOUND;
-    }
-    c->last_error = "estimated pruning bound too high: call repeated with a certifying sample";
-    c->est_failed = true;  // this context certifies for a while (note_completed counts the hold-off down)
-    c->est_failures++;
-    c->est_holdoff = 64u << (c->est_failures - 1 < 6 ? c->est_failures - 1 : 6);
-    c->frame.est_failed_call = true;
-    c->fast_ok = false;
-    return SC_ESPEC;
-  }
-  if (c->pass.sharded_ab && c->pass.cand_all && c->pinned[HW_CAND_CUT] != 0) {
-    // merge_check_kernel (an earlier kernel of this stream: its system-scope store is visible once the winner word is):
-    // some rank's candidate list was cut at a key the merged threshold does not clear
-    c->last_error = "a candidate blob was too small for this input: repeat the call with sc_params.shard_cand_level raised by one";
-    return SC_ERETRY;
-  }
-  if (c->pinned[HW_WINNER_POS] == ~0ull) {  // finalize_kernel: a pair decodes to a position outside the selection (outputs: identity, zero mask)
-    c->last_error = "a winner key pair points outside the selected list (stale / uninitialised pair, or ranks that disagree on T or the parameters)";
-    return SC_EINVAL;
-  }
-  note_completed(c, c->pass.regular);
-  const uint64_t key = c->pinned[HW_WINNER];
-  if (stats && stats->size == sizeof(sc_stats)) {
-    fill_stats(c, stats);
-    stats->best_count = (uint32_t)(key >> 32);
-    stats->best_rank = key ? (uint32_t)(c->pinned[HW_WINNER_POS] >> 32) : 0u;  // (rank index << 32 | position: one word beside the key)
-    if (c->pass.timing) {
-      stats->us_stage = ev_us(c, 0, 1);
-      stats->us_compat = ev_us(c, 1, 2);
-      stats->us_triangles = ev_us(c, 2, 3);  // includes its two 8-byte read-backs
-      stats->us_trikeys = c->pass.timed_trikeys ? ev_us(c, 9, 10) : 0.f;
-      stats->us_kabsch = ev_us(c, 3, 4);
-      stats->us_score = ev_us(c, 4, 5);
-      stats->us_argmax = ev_us(c, 5, 6);
-      stats->us_mask = ev_us(c, 7, 8);
-      stats->us_total = stats->us_stage + stats->us_compat + stats->us_triangles + stats->us_kabsch +
-                        stats->us_score + stats->us_argmax + stats->us_mask;
-    } else if (c->pass.timing_hot) {
-      stats->us_score = c->pass.hot_ext ? ev_us_raw(c, 4, 5) : ev_us(c, 4, 5);
-    } else if (c->pass.timing_one >= 0) {  // one bracket, recorded on the hot path (speculative launches on)
-      float* dst[7] = {&stats->us_stage, &stats->us_compat, &stats->us_triangles, &stats->us_kabsch, &stats->us_score,
-                       &stats->us_argmax, &stats->us_mask};
-      *dst[c->pass.timing_one] = ev_us(c, STAGE_EV[c->pass.timing_one][0], STAGE_EV[c->pass.timing_one][1]);
-    }
-  }
-  return key ? SC_OK : SC_ENOHYP;
-}
-
-// the whole path the waiting way (what sc_register_device always did): complete on return.  The only caller of the phases
-// that may prune by an ESTIMATED bound (it can repeat the call): a failed estimate comes back as SC_ESPEC from finalize_wait
-// and has switched estimating off for this context, so the second pass certifies.
-static int register_waited(sc_ctx* c, const float* d_src, const float* d_tgt, int64_t n, const sc_params* p, float* d_Rt,
-                    uint8_t* d_mask, sc_stats* stats) {
-  int rc = SC_OK;
-  for (int pass = 0; pass < 2; pass++) {
-    rc = hyp_begin(c, d_src, d_tgt, n, p, nullptr, 0, 1, PassMode{true});  // (waited; may estimate)
-    if (!rc) rc = hyp_end(c, nullptr, c->key.as<uint64_t>(), stats);
-    if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    rc = finalize_enqueue(c, c->key.as<uint64_t>(), 1, d_Rt, d_mask);
-    if (!rc) rc = finalize_wait(c, stats);
-    if (rc != SC_ESPEC) return rc;
-  }
-  c->last_error = "internal: a call was asked to repeat twice";
-  return SC_EHIP;
-}
-
-}  // namespace sc
-
-extern "C" {
-
-// one more frame (a call of sc_register_device(_async) / sc_register, or sc_hypothesize_device + its finalize call) has come to its
-// end with status rc: the context's cumulative counters (sc_debug_last)
-static void count_frame(sc_ctx* c, int rc) {
-  c->n_frames++;
-  if (c->frame.est_failed_call) c->n_est_fail++;
-  else if (c->pass.est_state == 1 && (rc == SC_OK || rc == SC_ENOHYP)) c->n_est_ok++;
-  if (c->frame.fast_state == 2 || (rc == SC_EBOUND && !c->frame.est_failed_call)) c->n_fast_repeat++;  // host-free, void: repeated (here, or by the caller)
-  else if (c->frame.fast_state == 1) c->n_fast_ok++;
-}
-
-// the finalize call of a HOST-FREE sc_hypothesize_device: a failed validation is the caller's to repeat (every rank alike)
-static int finalize_status(sc_ctx* c, int rc) {
-  if (rc != SC_ESPEC) return rc;
-  c->last_error += " — repeat sc_hypothesize_device and the finalize call without SC_FLAG_EST_BOUND";
-  return SC_EBOUND;
-}
-
-// the finalize call's two forms: arguments, a free context, a hypothesize half to finalize; then the winner / mask kernel is enqueued
-static int finalize_begin(sc_ctx* c, const uint64_t* d_keys, int n_pairs, float* d_Rt, uint8_t* d_mask) {
-  if (!c || !d_keys || !d_Rt || !d_mask || n_pairs < 1 || n_pairs > 4096) return SC_EINVAL;
-  SC_TRY(continue_pass(c, c->pass.have_hyp, "sc_finalize_device without a preceding sc_hypothesize_device"));
-  return finalize_enqueue(c, d_keys, n_pairs, d_Rt, d_mask);
-}
-
-int sc_finalize_gathered_device(sc_ctx* c, const uint64_t* d_keys, int n_pairs, float* d_Rt, uint8_t* d_mask,
-                                sc_stats* stats) {
-  SC_TRY(finalize_begin(c, d_keys, n_pairs, d_Rt, d_mask));
-  const int rc = finalize_status(c, finalize_wait(c, stats));
-  count_frame(c, rc);
-  return rc;
-}
-
-int sc_finalize_gathered_device_async(sc_ctx* c, const uint64_t* d_keys, int n_pairs, float* d_Rt, uint8_t* d_mask) {
-  SC_TRY(finalize_begin(c, d_keys, n_pairs, d_Rt, d_mask));
-  c->frame.pend_stats = sc_stats{};
-  c->frame.pend_stats.size = sizeof(sc_stats);
-  c->frame.pending = true; c->frame.pend_done = false; c->frame.pend_finalize = true;
-  return SC_OK;
-}
-
-}  // extern "C"
-
-// sc_register_device_async.  `direct`: the caller gets the context back before the frame is waited for, so a host-free frame on a
-// caller's stream takes the lane; sc_register_device (async + wait in one call) overlaps nothing and pays no fork and join.
-static int register_async(sc_ctx* c, const float* d_src, const float* d_tgt, int64_t n, const sc_params* p,
-                          float* d_Rt, uint8_t* d_mask, bool direct) {
-  if (!c || !d_src || !d_tgt || !d_Rt || !d_mask) return SC_EINVAL;
-  peel_end(c);
-  if (c->frame.pending) { c->last_error = "sc_register_device_async: a call is already outstanding on this context (sc_wait first)"; return SC_EINVAL; }
-  SC_TRY(entry_checks(c, p, PARAMS | ONE_RANK));  // (the frame ended above; "busy" has this entry's own text)
-  HIPCHK(c, hipSetDevice(c->device));
-  ENSURE(c, c->key, 64);
-  SC_TRY(frame_begin(c));
-  c->frame.pend_src = d_src; c->frame.pend_tgt = d_tgt; c->frame.pend_n = n; c->frame.pend_p = *p; c->frame.pend_Rt = d_Rt; c->frame.pend_mask = d_mask;
-  c->frame.pend_stats.size = sizeof(sc_stats);
-  PassMode mode{true};  // (sc_wait repeats a call whose estimated pruning bound fails, like any other failed assumption)
-  if (fast_plan(c, n, p, &mode)) {
-    // host-free: the whole chain is enqueued without looking at anything the GPU produces; sc_wait validates
-    int rc = SC_OK;
-    if (direct && c->caller_stream && !c->tn.no_lane) rc = lane_fork_caller(c);
-    if (!rc) rc = hyp_begin(c, d_src, d_tgt, n, p, nullptr, 0, 1, mode);
-    if (!rc) rc = hyp_end(c, nullptr, c->key.as<uint64_t>(), &c->frame.pend_stats);
-    if (!rc) rc = finalize_enqueue(c, c->key.as<uint64_t>(), 1, d_Rt, d_mask);
-    if (!rc && c->on_lane) {
-      rc = lane_mark_end(c);
-      if (!rc) { c->frame.lane = true; c->n_lane++; }
-    }
-    if (!rc) {
-      c->frame.pending = true; c->frame.pend_done = false; c->frame.pend_finalize = false;
-      return SC_OK;
-    }
-    // The host-free enqueue failed (an allocation sized by the COVERS hit the workspace cap, a launch failed): the waited form of
-    // the same call may well fit — "results are identical either way" (include/saccot.h) includes the status.  What was enqueued
-    // so far runs out first: its kernels publish into the pinned words the waited call is about to arm.  
-    // A frame on its lane: the lane is drained and the caller's stream is the context's again before the waited form starts.
-    pass_end(c); c->fast_ok = false;
-    if (c->on_lane) lane_drain(c);
-    else (void)hipStreamSynchronize(c->stream);
-    (void)hipGetLastError();
-  }
-  const int rc = register_waited(c, d_src, d_tgt, n, p, d_Rt, d_mask, &c->frame.pend_stats);
-  if (rc != SC_OK && rc != SC_ENOHYP) return rc;
-  c->frame.pending = true; c->frame.pend_done = true; c->frame.pending_rc = rc; c->frame.pend_finalize = false;
-  return SC_OK;
-}
-
-extern "C" {
-
-int sc_register_device_async(sc_ctx* c, const float* d_src, const float* d_tgt, int64_t n, const sc_params* p,
-                             float* d_Rt, uint8_t* d_mask) {
-  return register_async(c, d_src, d_tgt, n, p, d_Rt, d_mask, true);
-}
-
-int sc_wait(sc_ctx* c, sc_stats* stats) {
-  if (!c) return SC_EINVAL;
-  if (!c->frame.pending) { c->last_error = "sc_wait without an outstanding sc_register_device_async / sc_finalize_gathered_device_async"; return SC_EINVAL; }
-  HIPCHK(c, hipSetDevice(c->device));
-  c->frame.pending = false;
-  if (c->frame.pend_finalize) {  // sc_finalize_gathered_device's second half
-    c->frame.pend_finalize = false;
-    const int rc = finalize_status(c, finalize_wait(c, &c->frame.pend_stats));
-    count_frame(c, rc);
-    copy_stats(stats, c->frame.pend_stats);
-    return rc;
-  }
-  int rc = c->frame.pending_rc;
-  if (!c->frame.pend_done) {
-    rc = finalize_wait(c, &c->frame.pend_stats);
-    if (rc == SC_ESPEC) {  // a count outgrew what the launches covered (or another fallback was needed): the waiting way
-      rc = register_waited(c, c->frame.pend_src, c->frame.pend_tgt, c->frame.pend_n, &c->frame.pend_p, c->frame.pend_Rt, c->frame.pend_mask, &c->frame.pend_stats);
-      c->frame.fast_state = 2;
-    }
-  }
-  count_frame(c, rc);
-  copy_stats(stats, c->frame.pend_stats);
-  if (rc == SC_OK) {
-    // a frame: sc_peel may follow.  The same state whichever way the frame ran (waited, host-free, repeated after a miss): the
-    // winner's words are those of the pass that delivered the outputs
-    c->pass.peelable = true; c->pass.peel_round = 0;
-    c->pass.peel_prev = (uint32_t)c->pinned[HW_WINNER_POS];
-    c->pass.peel_claimed = (uint32_t)(c->pinned[HW_WINNER] >> 32);
-  }
-  return rc;
-}
-
-int sc_register_device(sc_ctx* c, const float* d_src, const float* d_tgt, int64_t n, const sc_params* p,
-                       float* d_Rt, uint8_t* d_mask, sc_stats* stats) {
-  SC_TRY(register_async(c, d_src, d_tgt, n, p, d_Rt, d_mask, false));  // (waited for at once: no lane)
-  return sc_wait(c, stats);
-}
-
-int sc_register(sc_ctx* c, const float* src, const float* tgt, int64_t n, const sc_params* p, float R[9],
-                float t[3], uint8_t* mask, sc_stats* stats) {
-  if (c) peel_end(c);
-  if (!c || !src || !tgt || !R || !t || !mask || n < 3 || n > (1 << 24)) return SC_EINVAL;
-  SC_TRY(entry_checks(c, p, PARAMS | ONE_RANK));  // (busy: sc_register_device_async's answer, below)
-  HIPCHK(c, hipSetDevice(c->device));
-  c->cap_bytes = workspace_cap(p);
-  if (n <= (1 << 20)) {
-    // Zero-copy form (up to 1 M correspondences = 24 MB in, 1 MB out over the host link): two memcpys on the host into a
-    // pinned, device-mapped area; the staging kernel reads it, the finalize kernel writes (R, t) and the mask into the
-    // other.  No hipMemcpy at all: a pageable-memory copy costs 10-20 us of driver time each (C2: 0.36 -> 0.31 ms).
-    const size_t in_bytes = (size_t)n * 24, out_bytes = 64 + (size_t)n;
-    auto grow = [&](void** p_, size_t* cap, size_t want) -> int {
-      if (*cap >= want) return SC_OK;
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      if (*p_) { (void)hipHostFree(*p_); *p_ = nullptr; *cap = 0; }
-      size_t sz = want + want / 4 + 4096;
-      if (hipHostMalloc(p_, sz, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); *p_ = nullptr; c->last_error = "hipHostMalloc failed"; return SC_ENOMEM; }
-      *cap = sz;
-      return SC_OK;
-    };
-    SC_TRY(grow(&c->h_in, &c->h_in_cap, in_bytes));
-    SC_TRY(grow(&c->h_out, &c->h_out_cap, out_bytes));
-    float* hs = static_cast<float*>(c->h_in);
-    float* ht = hs + (size_t)n * 3;
-    memcpy(hs, src, (size_t)n * 12);
-    memcpy(ht, tgt, (size_t)n * 12);
-    void *d_s = nullptr, *d_t = nullptr, *d_o = nullptr;
-    HIPCHK(c, hipHostGetDevicePointer(&d_s, hs, 0));
-    HIPCHK(c, hipHostGetDevicePointer(&d_t, ht, 0));
-    HIPCHK(c, hipHostGetDevicePointer(&d_o, c->h_out, 0));
-    const int rc = sc_register_device(c, static_cast<float*>(d_s), static_cast<float*>(d_t), n, p, static_cast<float*>(d_o),
-                            static_cast<uint8_t*>(d_o) + 64, stats);
-    if (rc != SC_OK && rc != SC_ENOHYP) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));  // (idle already on the private stream; a caller's stream may hold the refit)
-    const float* Rt = static_cast<const float*>(c->h_out);
-    memcpy(R, Rt, 36);
-    memcpy(t, Rt + 9, 12);
-    memcpy(mask, static_cast<const uint8_t*>(c->h_out) + 64, (size_t)n);
-    return rc;
-  }
-  ENSURE(c, c->rt12, 64);
-  ENSURE(c, c->mask, (size_t)n);
-  SC_TRY(points_to_device(c, src, tgt, n));
-  const int rc = sc_register_device(c, c->in_src.as<float>(), c->in_tgt.as<float>(), n, p, c->rt12.as<float>(),
-                          c->mask.as<uint8_t>(), stats);
-  if (rc != SC_OK && rc != SC_ENOHYP) return rc;
-  SC_TRY(outputs_to_host(c, (size_t)n, R, t, mask));
-  return rc;
 }
 
 }  // extern "C"

@@ -18,21 +18,6 @@ namespace sc {
 
 // ---- sizes and small answers ---------------------------------------------------------------------------------------------------
 
-// what a host-free repetition of a call's shape is sized to cover (fast_plan): the last count plus half, and the largest count of
-// the shape's recent calls plus a quarter (sc_ctx::E_hi / M_hi)
-// While the shape is young on this context (fewer than HI_YOUNG of its calls seen) the last count is doubled instead: the first
-// frames of a stream say little about the spread of the frames to come, and a miss costs a whole repeated call (bench.py's
-// stream, frames of 386 k .. 697 k edges: with "plus half" from the first frame on, one of the first twenty was repeated).
-static uint64_t cover_of(uint64_t last, const uint64_t hi[2], bool young) {
-  const uint64_t h = hi[0] > hi[1] ? hi[0] : hi[1];
-  const uint64_t b = h + h / 4;
-  // young: twice the last count (or the window's maximum plus a quarter, if larger); later the window alone decides — the last
-  // count is in it — so that a stream's covers stay put from frame to frame instead of following every large frame by half
-  // (a cover beyond 2^20 edges takes the scan's two-launch form, and every launch sized by it grows with it)
-  const uint64_t a = young ? 2 * last : (h ? 0 : last + last / 2);
-  return (a > b ? a : b) + 4096;
-}
-
 // entries the edge arrays hold (what fast_plan caps a host-free call's edge cover by)
 static uint64_t edge_capacity(const sc_ctx* c, bool build) {
   uint64_t cap = c->es.cap / 4 >= 2 ? c->es.cap / 4 - 2 : 0;  // es carries two pad entries
@@ -42,24 +27,6 @@ static uint64_t edge_capacity(const sc_ctx* c, bool build) {
 }
 // ... and the key arrays (what fast_plan caps its key cover by, and the speculative key pass may write)
 static uint64_t key_capacity(const sc_ctx* c) { return c->wkey.cap / 4 < c->kcol.cap / 8 ? c->wkey.cap / 4 : c->kcol.cap / 8; }
-
-// the parameters that make two calls "the same shape" (a host-free call repeats the last call's; timing flags aside)
-static bool same_shape(const sc_params* p, const sc_params* q) {
-  constexpr uint32_t TIMING_BITS = SC_FLAG_TIMING | SC_FLAG_TIMING_HOT | SC_FLAG_TIMING_ONE | (15u << 8);
-  return p->sigma == q->sigma && p->t_cmp == q->t_cmp && p->tau == q->tau && p->min_len == q->min_len &&
-         p->max_triangles == q->max_triangles && p->rank_mode == q->rank_mode && p->layout == q->layout &&
-         p->shard_world == q->shard_world && p->shard_rank == q->shard_rank && p->shard_block == q->shard_block &&
-         p->score_mode == q->score_mode && (p->flags & ~TIMING_BITS) == (q->flags & ~TIMING_BITS);
-}
-// the pass in hand continues the shape of the last completed call (note_completed empties the window of maxima when it does not)
-bool shape_continues(const sc_ctx* c) { return c->pass.n == c->last_n && same_shape(&c->pass.params, &c->last_p); }
-// entries a waited call leaves in an array indexed by one of stage B's two counts: what the host-free repetitions of its shape
-// will want to cover (the window's maxima only while the shape continues: note_completed empties it after a change)
-static uint64_t room_of(const sc_ctx* c, uint64_t count, const uint64_t hi[2]) {
-  static const uint64_t none[2] = {0, 0};
-  const bool continues = shape_continues(c);
-  return cover_of(count, continues ? hi : none, !continues || c->hi_seen < sc_ctx::HI_YOUNG);
-}
 
 // The smallest key a triangle can have in weight ranking: every edge has s >= t_cmp up to rounding (0.1 % slack), so w >= ~3 t_cmp — what
 // the select's a-priori window and the pruning samples' floors rest on.  NOT when -1 / (2 sigma^2) overflowed fp32 (sigma below 2^-64.5 =
@@ -126,7 +93,7 @@ int ensure_frame(sc_ctx* c) {
 // bit rows are short enough for the kernel.  hyp_begin asks — with "the whole sample, own histogram" (StageBForm::own_sample) —
 // before stage A, and fast_plan, because the fused kernel writes no per-edge bases.
 bool edge_build_ok(const sc_ctx* c, const sc_params* p, int64_t n, bool may_estimate) {
-  return may_estimate && !c->est_failed && window_known(p) && may_prune(p) && !c->tn.no_events && !c->tn.no_estimate &&
+  return may_estimate && !c->est.failed && window_known(p) && may_prune(p) && !c->tn.no_events && !c->tn.no_estimate &&
          c->tn.sample_mode == 0 && !c->tn.no_edge_build && !c->tn.rows_unfused && edge_build_fits((int)n) &&  // (stage C may be dealt over ranks: shard_world)
          p->max_triangles != 0;
 }
@@ -147,7 +114,7 @@ static int form_begin(sc_ctx* c, const sc_params* p, const uint32_t* hist, uint3
   // form only — event list, a-priori select window (the check rides the window's first round), the whole sample here
   // (sharded, SC_FLAG_EST_BOUND: every rank takes the WHOLE sample — it is cheaper than the latency of the all-reduce that
   // would sum the ranks' shares — and the merge of the candidates verifies the bound: sc_shard_score_device)
-  f.est_local = c->pass.mode.may_estimate && !c->est_failed && f.own_sample && !c->pass.sharded_ab;
+  f.est_local = c->pass.mode.may_estimate && !c->est.failed && f.own_sample && !c->pass.sharded_ab;
   f.est_shard = c->pass.sharded_ab && hist != nullptr && (p->flags & SC_FLAG_EST_BOUND) != 0;
   c->pass.form = f;
   return SC_OK;
@@ -163,7 +130,7 @@ static void form_counted(sc_ctx* c, const sc_params* p, const Graph& g, uint64_t
   f.have_total = f.pruned && (p->flags & SC_FLAG_EXACT_TOTAL) != 0;  // statistics only: 3-cliques of the whole graph
   // the smallest possible weight is ~3 t_cmp (every edge has s >= t_cmp up to rounding); 0.1 % slack
   c->pass.plan = f.pruned ? sample_plan(p->max_triangles, (f.est_local || f.est_shard) && f.use_events && window_known(p), c->tn,
-                                        f.spec ? c->E_last : E, g.W)
+                                        f.spec ? c->shape.E_last : E, g.W)
                           : SamplePlan{false, 1u, p->max_triangles};
   f.est_active = c->pass.plan.estimate;
 }
@@ -247,7 +214,7 @@ static int read_edge_count(sc_ctx* c, const sc_params* p, const Graph& g, uint32
 static int grow_edge_arrays(sc_ctx* c, uint64_t E, bool* moved) {
   const StageBForm& f = c->pass.form;
   // (a waited call leaves room for what a host-free repetition of its shape will want to cover: fast_plan caps by these arrays)
-  const uint64_t E_room = f.spec ? E : room_of(c, E, c->E_hi);
+  const uint64_t E_room = f.spec ? E : c->shape.room(E, ShapeHistory::EDGES, shape_continues(c));
   Caps edge_arrays;
   edge_arrays.add(c->ei); edge_arrays.add(c->ej); edge_arrays.add(c->es);
   if (!f.build) { edge_arrays.add(c->ebi); edge_arrays.add(c->ebj); }
@@ -309,7 +276,7 @@ static int run_sample(sc_ctx* c, const sc_params* p, const Graph& g, uint64_t E,
     const bool whole = f.est_shard;
     launch_sample_hist(g, c->ebi.as<uint32_t>(), c->ebj.as<uint32_t>(), c->ei.as<uint32_t>(), c->ej.as<uint32_t>(),
                        c->es.as<float>(), E, p->max_triangles, key_floor(p), whole ? 0u : part, whole ? 1u : parts,
-                       ctl->prune_hist, ctl->es_hist, c->tn, st, E_dev, f.spec ? c->E_last : 0);
+                       ctl->prune_hist, ctl->es_hist, c->tn, st, E_dev, f.spec ? c->shape.E_last : 0);
   }
   if (hist) launch_hist_reduce(ctl->prune_hist, hist, st);  // the exchanged form: one 256-bin histogram
   return SC_OK;
@@ -461,7 +428,7 @@ static int count_triangles(sc_ctx* c, const sc_params* p, uint64_t E, SelectArgs
     c->pass.ref_done = true;
   }
   const EdgeBases eb = edge_bases_of(c);
-  launch_tri_count_events(a.g, a.mbits, a.sl, eb.i, eb.j, c->ei.as<uint32_t>(), c->ej.as<uint32_t>(), f.spec ? c->E_last : E,
+  launch_tri_count_events(a.g, a.mbits, a.sl, eb.i, eb.j, c->ei.as<uint32_t>(), c->ej.as<uint32_t>(), f.spec ? c->shape.E_last : E,
                           p->rank_mode, c->tcnt.as<uint32_t>(), a.ev, c->tn, st, own_range_of(c), c->ebase.as<uint32_t>(),
                           ref.out ? &ref : nullptr, f.ord_on ? &a.ord : nullptr);
   return SC_OK;
@@ -530,7 +497,7 @@ int ensure_compaction(sc_ctx* c, size_t nb, size_t nb_room, uint32_t T_eff) {
 // speculative key pass wrote is gone.
 static int grow_key_arrays(sc_ctx* c, uint64_t M, uint32_t T_eff, bool want_list, bool* moved) {
   const bool spec = c->pass.form.spec;
-  const uint64_t M_room = spec ? M : room_of(c, M, c->M_hi);
+  const uint64_t M_room = spec ? M : c->shape.room(M, ShapeHistory::KEYS, shape_continues(c));
   Caps key_arrays;
   key_arrays.add(c->wkey); key_arrays.add(c->kcol);
   ENSURE_ROOM(c, c->wkey, M * 4, M_room * 4);
@@ -663,54 +630,43 @@ int run_triangles(sc_ctx* c, const sc_params* p, bool want_list) {
 //   (a) the parameters and knobs of the common form: events, the a-priori select window, pruning, no stage timing, no exact total,
 //       and the last completed call's shape                                                              — hostfree_shape_ok
 //   (b) counts that fit: a graph big enough to prune (E >= 4096), E and M within what the launches cover,
-//       and T triangles found (M >= T)                                                                   — counts_fit
+//       and T triangles found (M >= T)                                                                   — counts_fit (sc_frame_check.hpp)
 //   (c) that the call it repeats took that form itself: waited, events that did not overflow, the a-priori window, the whole sample
 //       in its own histogram, stages A and B whole on this GPU (one rank, or replicated ranks)           — hostfree_form_met, hostfree_next_ok
-// Four places ask: fast_plan PREDICTS (a) and (b) from the last call's counts; run_select NOTES (c) for the call in hand;
-// finalize_wait VALIDATES (b) and the event list once the frame has run; note_completed FILES all of it as sc_ctx::fast_ok.
-
-static bool counts_fit(uint64_t E, uint64_t M, uint64_t E_cov, uint64_t M_cov, uint32_t T) {
-  return E >= 4096 && E <= E_cov && M <= M_cov && M >= (uint64_t)T;
-}
+// Four places ask: fast_plan PREDICTS (a) and (b) from the last call's counts; run_select NOTES (c) for the call in hand; the frame's
+// verdict (frame_end -> hostfree_valid, sc_frame_check.hpp; finalize_wait, sc_capi_frame.hip) VALIDATES (b) and the event list once
+// the frame has run; note_completed (sc_capi_frame.hip) FILES all of it as sc_ctx::fast_ok and in sc_ctx::shape.
 
 static bool hostfree_shape_ok(const sc_ctx* c, int64_t n, const sc_params* p) {
-  if (c->tn.no_fast || c->tn.no_events || n != c->last_n) return false;
+  if (c->tn.no_fast || c->tn.no_events || n != c->shape.n) return false;
   if (p->flags & (SC_FLAG_TIMING | SC_FLAG_EXACT_TOTAL | SC_FLAG_NO_PRUNE)) return false;
-  if (!same_shape(p, &c->last_p)) return false;
+  if (!ShapeHistory::same_shape(p, &c->shape.p)) return false;
   return window_known(p);  // the a-priori select window (weight ranking with it)
 }
 
 // May this call be enqueued host-free?  Only a repetition of the last call's shape on this context, and only when that call
-// was regular (note_completed); sets what the launches cover: the last counts plus half, within what the arrays hold.
+// was regular (note_completed); sets what the launches cover (ShapeHistory::cover), within what the arrays hold.
 bool fast_plan(const sc_ctx* c, int64_t n, const sc_params* p, PassMode* mode) {
   if (!c->fast_ok || !hostfree_shape_ok(c, n, p)) return false;
   const uint64_t ecap = edge_capacity(c, edge_build_ok(c, p, n, true));  // (every entry point that comes here may estimate; the fused edge kernel writes no per-edge bases)
   const uint64_t kcap = key_capacity(c);
-  // the last call's counts plus half, and the largest counts of the shape's recent calls plus a quarter (sc_ctx::E_hi)
-  const bool young = c->hi_seen < sc_ctx::HI_YOUNG;
-  uint64_t ecov = cover_of(c->E_last, c->E_hi, young), mcov = cover_of(c->M_last, c->M_hi, young);
+  const ShapeHistory& h = c->shape;
+  uint64_t ecov = h.cover(h.E_last, h.E_hi), mcov = h.cover(h.M_last, h.M_hi);
   if (ecov > ecap) ecov = ecap;
   if (mcov > kcap) mcov = kcap;
   // The prediction: the last call's counts fit the covers.  (fast_ok says of those counts what counts_fit asks beside the covers —
   // E_last >= 4096, M_last >= T: hostfree_next_ok — so the covers are at least that large as well.)
-  if (!counts_fit(c->E_last, c->M_last, ecov, mcov, p->max_triangles) || ecov >= (1ull << 32)) return false;
+  if (!counts_fit(h.E_last, h.M_last, ecov, mcov, p->max_triangles) || ecov >= (1ull << 32)) return false;
   mode->host_free = true; mode->E_cov = ecov; mode->M_cov = mcov;
   return true;
 }
 
 // run_select, of the waited call in hand: the shape a host-free repetition of it assumes.  (A host-free call notes nothing here:
-// finalize_wait says "regular" once it has validated.)  Differs from (a) in looking at what the call DID, not at its parameters:
+// apply_verdict says "regular" once the frame is validated.)  Differs from (a) in looking at what the call DID, not at its parameters:
 // events_ok and fast_window fold in use_events, pruning and window_known; have_total is SC_FLAG_EXACT_TOTAL on a pruned graph.
 static bool hostfree_form_met(const sc_ctx* c, uint64_t M, uint32_t want_sel) {
   const StageBForm& f = c->pass.form;
   return !f.spec && f.events_ok && f.fast_window && !f.have_total && !c->pass.timing && M >= want_sel && f.own_sample;
-}
-
-// finalize_wait, of a host-free frame that has run (E, M: the real counts; all ones: the word never arrived): the launches covered
-// E_cov edges and M_cov keys and assumed T triangles exist, an event list that did not overflow and a graph big enough to prune
-bool hostfree_valid(const sc_ctx* c, uint64_t E, uint64_t M) {
-  return E != PIN_PENDING && M != PIN_PENDING && counts_fit(E, M, c->pass.mode.E_cov, c->pass.mode.M_cov, c->pass.params.max_triangles) &&
-         (uint32_t)c->pinned[HW_EV_OVERFLOW] == 0;
 }
 
 // note_completed, of the call that just completed (regular: hostfree_form_met's answer, or a validated host-free frame): may the

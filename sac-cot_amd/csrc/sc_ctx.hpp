@@ -9,6 +9,7 @@
 
 #include "../../include/saccot.h"
 #include "../../include/saccot_debug.h"
+#include "sc_frame_check.hpp"
 #include "sc_kernels.hpp"
 #include "sc_match_batch_check.hpp"
 
@@ -27,7 +28,7 @@ static_assert(HW_MERGED_M == HW_MERGED_T + 1 && HW_WINNER_POS == HW_WINNER + 1, 
 // How a pass is enqueued: decided by the entry point BEFORE the pass starts and handed to hyp_begin, which stores it in the fresh pass.
 struct PassMode {
   // the entry point can repeat the call (sc_register*), or its caller does (sc_hypothesize_device with SC_FLAG_EST_BOUND): stage B
-  // may prune by an ESTIMATED bound (sc_tri.hip 3c); the select verifies it, finalize_wait reads the verdict
+  // may prune by an ESTIMATED bound (sc_tri.hip 3c); the select verifies it, finalize_wait reads the verdict (frame_end)
   bool may_estimate = false;
   // host-free enqueue (include/saccot.h): a call of the last one's shape does not wait for stage B's two counts; its launches cover E_cov
   // edges / M_cov keys (fast_plan) and read the real counts from device memory; finalize_wait validates, and the call is repeated the waiting
@@ -66,11 +67,12 @@ struct StageBForm {
   bool keys_done = false;   // the speculative key pass wrote every key: no second pass
 };
 
-// One run through hyp_begin (or sc_shard_compat_device) to finalize_wait.  Assigned Pass{} in pass_begin and nowhere else: what a pass
-// did not set itself reads as "no".  Fields are READ after the pass as well — by a finalize call that comes later (have_hyp links the
-// two, and it may come twice), by note_completed (E, M, n, params, form.use_events), by fill_stats and sc_debug_last (counts, covers,
-// filter_*, est_state, form.ord_state, hot_ext) — so nothing is cleared when a pass ends except mode.host_free.  The stage hooks
-// (sc_*_host) start no pass: they run single kernels on the context's buffers and touch only what host_to_planes says.
+// One run through hyp_begin (or sc_shard_compat_device) to finalize_wait (sc_capi_frame.hip).  Assigned Pass{} in pass_begin and
+// nowhere else: what a pass did not set itself reads as "no".  Fields are READ after the pass as well — by a finalize call that comes
+// later (have_hyp links the two, and it may come twice), by note_completed (E, M, n, params, form.use_events), by fill_stats and
+// sc_debug_last (counts, covers, filter_*, est_state, form.ord_state, hot_ext) — so nothing is cleared when a pass ends except
+// mode.host_free.  The stage hooks (sc_*_host) start no pass: they run single kernels on the context's buffers and touch only what
+// host_to_planes says.
 struct Pass {
   PassMode mode;
   int n = 0, ld = 0; uint32_t T_eff = 0;
@@ -85,9 +87,9 @@ struct Pass {
   uint32_t amx_blocks = 0;  // workgroups of the arg-max launch whose pairs this context's finalize step reduces itself (0: one reduced pair in `key`)
   uint64_t* bits_cur = nullptr;  // the adjacency bit matrix: the context's own buffer, or — sharded stage A — the caller's all-gathered one
   bool rows_fused = false;  // run_row_stats already produced edge_off / ebase / cost_pre and armed the edge count
-  bool regular = false;     // every assumption of the host-free form was met (run_select, finalize_wait): note_completed files it as fast_ok
+  bool regular = false;     // every assumption of the host-free form was met (run_select, apply_verdict): note_completed files it as fast_ok
   bool est_void = false;    // stage B's estimate (form.est_active) could not be verified on the path taken (event overflow): repeat
-  int est_state = 0;        // 0 certified bound (or no pruning), 1 estimated and verified: finalize_wait's verdict, read by count_frame
+  int est_state = 0;        // 0 certified bound (or no pruning), 1 estimated and verified: apply_verdict sets it, count_frame reads it
   SamplePlan plan{false, 1u, 0};
   // stage C2's reference frame (sc_gramref.hpp): on the hot path the estimating sample leaves candidate triangles behind (ref_cand_n of
   // them) and the counting pass carries the vote as an extra workgroup (ref_done); everywhere else stage C votes in a launch of its own
@@ -106,18 +108,29 @@ struct Pass {
   uint32_t peel_claimed = 0;         // inlier-count mode: correspondences claimed so far (the best_counts add up to it)
 };
 
+// The outstanding half of sc_register_device_async / sc_finalize_gathered_device_async (at most one per context; sc_wait ends it)
+enum class Outstanding {
+  None,
+  Enqueued,  // a host-free register: sc_wait validates it and may repeat it the waiting way (PendingCall)
+  Complete,  // a waited register: done, its status held (Frame::held_rc)
+  Finalize,  // the second half of sc_finalize_gathered_device_async: no repeat inside the library
+};
+// the arguments of an Enqueued call, kept for its repeat
+struct PendingCall {
+  const float* src = nullptr; const float* tgt = nullptr; int64_t n = 0; sc_params p{};
+  float* Rt = nullptr; uint8_t* mask = nullptr;
+};
+
 // One call of an entry point as its caller sees it: it survives the library's own repeat of the call (sc_wait -> register_waited: a
 // second pass) and ends in count_frame.  Assigned Frame{} in frame_begin and nowhere else.
 struct Frame {
   int fast_state = 0;            // 0 waited, 1 host-free and valid, 2 host-free, failed validation, repeated
   bool lane = false;             // its host-free enqueue ran on the context's lane (sc_ctx::lane_fork)
   bool est_failed_call = false;  // a pass of this frame saw its estimate fail (sc_debug_last: prune_bound 2); the repeat must not forget it
-  // the outstanding half of sc_register_device_async / sc_finalize_gathered_device_async (at most one per context)
-  bool pending = false;
-  bool pend_done = false; int pending_rc = 0;  // ... and it was a waited call: complete, with this status
-  bool pend_finalize = false;  // ... it is sc_finalize_gathered_device_async's (sc_wait: no repeat inside the library)
-  const float* pend_src = nullptr; const float* pend_tgt = nullptr; float* pend_Rt = nullptr; uint8_t* pend_mask = nullptr;
-  int64_t pend_n = 0; sc_params pend_p{}; sc_stats pend_stats{};
+  Outstanding outstanding = Outstanding::None;  // set by leave_outstanding, taken back by sc_wait (sc_capi_frame.hip)
+  int held_rc = 0;               // Complete: the status sc_wait delivers
+  PendingCall call;
+  sc_stats pend_stats{};         // the library's own copy of the call's statistics: sc_wait hands it to the caller
 };
 
 // The grow-only device workspace: Buf members and nothing else.  sc_destroy walks it as an array (workspace_bufs), so a Buf declared
@@ -237,23 +250,11 @@ struct sc_ctx : sc::Workspace {  // (the workspace buffers are direct members to
   // run-time probe of the matrix pipe's accumulation model (sc_score.hip gram_guard): 0 not run, 1 holds, 2 violated
   int gram_guard = 0; float gram_guard_worst = 0.f;
 
-  // ---- history: what a completed call leaves for the next one (note_completed writes it; fast_plan / room_of / edge_build_ok, sc_capi_tri.hip, read it)
+  // ---- history: what a completed call leaves for the next one (note_completed and apply_verdict, sc_capi_frame.hip, write it;
+  // fast_plan, the array growers and edge_build_ok, sc_capi_tri.hip, read it).  The two rules are sc_frame_check.hpp's.
   bool fast_ok = false;      // the last completed call was regular (events, a-priori window, T triangles found): the next may be enqueued host-free
-  uint64_t E_last = 0, M_last = 0;
-  int last_n = 0;
-  sc_params last_p{};
-  // r05: what the covers are sized by.  A stream of DIFFERENT frames of one shape (bench.py's: 32 scenes whose inlier ratio moves the
-  // edge count by 1.6 x and the triangle count by 4 x) outgrew "the last call's counts plus half" in a frame out of six; the covers now
-  // follow the largest counts of the last HI_WINDOW .. 2 HI_WINDOW completed calls of the shape (two buckets: the current one and the one
-  // before it), so a stream pays for the spread of its frames once.  A change of shape empties the window (note_completed).
-  static constexpr uint32_t HI_WINDOW = 64, HI_YOUNG = 8;
-  uint64_t E_hi[2] = {0, 0}, M_hi[2] = {0, 0};
-  uint32_t hi_n = 0, hi_seen = 0;  // calls in the current bucket; regular calls of this shape seen so far (saturating)
-  bool est_failed = false;   // an estimate failed on this context: it certifies for the next est_holdoff completed calls (sc_set_debug resets)
-  // r04c: not for ever.  One frame whose estimate fails — a change of scene — used to cost the context its estimating sample (25 us per
-  // C2 call) for the rest of its life; now the k-th failure costs 64 << min(k - 1, 6) certifying calls, then the context estimates
-  // again: a stream whose estimates always fail wastes one repeated call in 4096.
-  uint32_t est_holdoff = 0, est_failures = 0;
+  sc::ShapeHistory shape;    // the last call's counts and shape, the window of maxima the covers are sized by
+  sc::EstHistory est;        // an estimate failed on this context: it certifies for a while (sc_set_debug resets)
   // a call's ordered strong list (sc_tri.hip 2c) had more chunks than the key kernel holds and fell back through the scan: the context
   // takes the scan form from then on — such a graph would overflow again (sc_set_debug resets)
   bool ord_off = false;
@@ -288,10 +289,9 @@ inline Points points_of(const sc_ctx* c) { return Points{c->planes.as<float>(), 
 int lb_next(sc_ctx* c, size_t bytes, int slot, size_t desc_off, LbArgs* out);
 int rec(sc_ctx* c, int i);
 float ev_us(sc_ctx* c, int a, int b);
-constexpr uint64_t PIN_PENDING = ~0ull;  // a host word whose kernel has not delivered yet (wait_word polls it)
 inline void arm_word(sc_ctx* c, HostWord w) { c->pinned[w] = PIN_PENDING; }
 // HW_EV_OVERFLOW's high half: the overflow (low half) was the ordered strong list's chunk count, not — or not only — an event region
-inline bool chunk_overflow(const sc_ctx* c) { return (c->pinned[HW_EV_OVERFLOW] >> 32) != 0; }
+inline bool chunk_overflow(const sc_ctx* c) { return chunks_overflowed(c->pinned[HW_EV_OVERFLOW]); }
 int wait_word(sc_ctx* c, HostWord idx);
 // "who: what" into last_error; the status of a refused call
 inline int refuse(sc_ctx* c, const char* who, const char* what) {
@@ -301,9 +301,16 @@ inline int refuse(sc_ctx* c, const char* who, const char* what) {
 // a refused NULL argument, named (the context is there: sc_last_error can say which)
 #define SC_NOT_NULL(c, who, arg) do { if (!(arg)) return refuse((c), (who), #arg " is NULL"); } while (0)
 // an sc_register_device_async / sc_finalize_gathered_device_async call is outstanding on this context
-inline int busy(sc_ctx* c) { return c->frame.pending ? (c->last_error = "a call is outstanding on this context (sc_wait first)", SC_EINVAL) : SC_OK; }
+inline int busy(sc_ctx* c) { return c->frame.outstanding != Outstanding::None ? (c->last_error = "a call is outstanding on this context (sc_wait first)", SC_EINVAL) : SC_OK; }
 // Any computing entry other than sc_peel* ends the frame the context may hold (include/saccot.h, sc_peel)
 inline void peel_end(sc_ctx* c) { c->pass.peelable = false; }
+// ... and sc_wait opens one where a frame's status is SC_OK.  The same state whichever way the frame ran (waited, host-free, repeated
+// after a miss): the winner's words are those of the pass that delivered the outputs
+inline void peel_open(sc_ctx* c) {
+  c->pass.peelable = true; c->pass.peel_round = 0;
+  c->pass.peel_prev = (uint32_t)c->pinned[HW_WINNER_POS];
+  c->pass.peel_claimed = (uint32_t)(c->pinned[HW_WINNER] >> 32);
+}
 void fill_stats(const sc_ctx* c, sc_stats* s);
 
 // What an entry point checks before it touches the context, always in this order: peel_end, busy, check_params(p), p->shard_world == 1.
@@ -525,11 +532,27 @@ SC_LOCAL bool window_known(const sc_params* p);
 SC_LOCAL uint32_t select_want(const sc_ctx* c, const sc_params* p);
 SC_LOCAL bool edge_build_ok(const sc_ctx* c, const sc_params* p, int64_t n, bool may_estimate);
 SC_LOCAL int ensure_frame(sc_ctx* c);
-SC_LOCAL bool shape_continues(const sc_ctx* c);
-// what a host-free frame assumes (one page of sc_capi_tri.hip): the plan, the validation at its end, what the completed call leaves
+// the pass in hand continues the shape of the last completed call
+inline bool shape_continues(const sc_ctx* c) { return c->shape.continues(c->pass.n, &c->pass.params); }
+// what a host-free frame assumes (one page of sc_capi_tri.hip): the plan, and what the completed call leaves (the validation at its
+// end is sc_frame_check.hpp's hostfree_valid)
 SC_LOCAL bool fast_plan(const sc_ctx* c, int64_t n, const sc_params* p, PassMode* mode);
-SC_LOCAL bool hostfree_valid(const sc_ctx* c, uint64_t E, uint64_t M);
 SC_LOCAL bool hostfree_next_ok(const sc_ctx* c, bool regular);
+
+// ---- a frame's end is sc_capi_frame.hip; what it calls of sc_capi.hip (what each does is said at its definition)
+SC_LOCAL int frame_begin(sc_ctx* c);
+SC_LOCAL int continue_pass(sc_ctx* c, bool in_order, const char* otherwise);
+SC_LOCAL bool pass_end(sc_ctx* c);
+SC_LOCAL int hyp_begin(sc_ctx* c, const float* d_src, const float* d_tgt, int64_t n, const sc_params* p, uint32_t* d_hist, uint32_t part,
+                       uint32_t parts, const PassMode& mode);
+SC_LOCAL int hyp_end(sc_ctx* c, const uint32_t* d_hist, uint64_t* d_key, sc_stats* stats);
+SC_LOCAL TriSource tri_source_of(const sc_ctx* c);
+struct CoordStats { uint64_t mx, box[6]; };
+SC_LOCAL CoordStats read_coord_stats(const sc_ctx* c);
+// stage brackets as (first event, second event): stage, compat, triangles, kabsch, score, argmax, mask
+constexpr int STAGE_EV[7][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 4}, {4, 5}, {5, 6}, {7, 8}};
+SC_LOCAL float ev_us_raw(sc_ctx* c, int a, int b);
+
 int decide_filter(sc_ctx* c, const sc_params* p, const Shard& sh);
 int run_score(sc_ctx* c, const sc_params* p, const Shard& sh, uint32_t* rows, bool tile_done, hipEvent_t ev0 = nullptr,
               hipEvent_t ev1 = nullptr, hipEvent_t ev_mid = nullptr);
