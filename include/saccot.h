@@ -287,6 +287,10 @@ int sc_wait(sc_ctx* ctx, sc_stats* stats);
  *   - The call ends the frame a context may hold and leaves none: sc_peel / sc_polish after it return SC_EINVAL.
  *   - Workspace: the copy of offset, plus the host form's device copies of its arrays; allocated by the first batch call, counted in
  *     workspace_bytes and held against params->max_workspace (SC_ENOMEM).  A context that never batches allocates and runs nothing new.
+ *     (The device copies of a host form — this one's and those of every host-array entry below — live in ONE pool the host forms
+ *     of a context share: a host form returns with the stream idle, so nothing in the pool outlives it, and a context that uses
+ *     several of them holds one copy of the largest arrays, not one per entry.  Whatever a host form returns, no copy from or
+ *     into the caller's arrays is in flight.)
  * Cost: a problem occupies ONE compute unit's workgroup for (triangles of its graph) x (3 .. 10 enumeration passes) + (kept triangles)
  * x n_b.  The graphs of a few hundred putative correspondences hold 10^3 .. 10^5 triangles; a DENSE 512-point problem (2 x 10^7
  * triangles) keeps its workgroup busy for tens of milliseconds while the rest of the batch has long finished — such problems belong
@@ -899,7 +903,8 @@ int sc_register_guided_pairs_features_device(sc_ctx* ctx, const float* d_pts, co
  * float nearest pi is accepted), trans_tol not finite or negative, an unknown flag or a non-zero reserved word; a pose_stride that
  * breaks the pose rule; a call outstanding on the context.
  * Workspace: the copied list with every set's sorted neighbour entries, the oriented fp64 poses (192 bytes a pair), two alive bytes
- * a pair and the round words; the host form adds device copies of its arrays.  Allocated by the first such call, counted in
+ * a pair and the round words; the host form adds device copies of its arrays, in the pool every host form shares
+ * (sc_register_batch).  Allocated by the first such call, counted in
  * workspace_bytes and held against the cap (SC_ENOMEM, nothing enqueued).  A context that never calls these entries allocates and
  * runs nothing new.
  * Not here: solving the pose graph; loops longer than three; weighting a loop's test by the pairs' information matrices; a sharded
@@ -1050,8 +1055,8 @@ int sc_register_guided_poses_features(sc_ctx* ctx, const float* src_pts, const f
  * the offsets, sc_params, knn, the table and the list; a call outstanding on the context.  The device forms enqueue on the context's
  * stream and return without waiting: outputs are complete in stream order.  (They may wait for the previous batch call's copy out of
  * the offset staging area, as the sibling entries do.)  All entries end the frame a context may hold and leave none.
- * Workspace: the copy of the offsets (records), plus the host form's device copies of its arrays; buffers of these entries' own,
- * allocated by the first such call, counted in workspace_bytes and held against params->max_workspace (SC_ENOMEM).  A context that
+ * Workspace: the copy of the offsets (records), a buffer of these entries' own, plus the host form's device copies of its arrays,
+ * in the pool every host form shares (sc_register_batch); allocated by the first such call, counted in workspace_bytes and held against params->max_workspace (SC_ENOMEM).  A context that
  * never calls these entries allocates and runs nothing new.
  * Not here: a mask output (sc_polish_batch writes it); weights per correspondence.  (The form for a scored frame is
  * sc_pose_info_frame, below.) */
@@ -1138,8 +1143,8 @@ int sc_pose_info_pairs_slots_device(sc_ctx* ctx, const float* d_pts, const uint3
  * returned SC_ENOHYP: sc_peel's refusal, with its text —; a call outstanding on the context.  A refused call leaves the frame.
  * The device form enqueues on the context's stream and returns without waiting, and needs no host word: d_info is complete in
  * stream order.  The host form copies in, enqueues, copies out and waits.
- * Workspace: the chunk sums' scratch — n_poses x ceil(n / 64) x 16 doubles — plus the host form's device copies; buffers of these
- * entries' own, allocated by the first such call, counted in workspace_bytes and held against the frame's cap (SC_ENOMEM, nothing
+ * Workspace: the chunk sums' scratch — n_poses x ceil(n / 64) x 16 doubles, a buffer of these entries' own — plus the host form's
+ * device copies, in the pool every host form shares (sc_register_batch); allocated by the first such call, counted in workspace_bytes and held against the frame's cap (SC_ENOMEM, nothing
  * enqueued, the frame stays).  A context that never calls these entries allocates and runs nothing new.
  * Not here: weights per correspondence; a form for sharded / multi-GPU frames, which leave no frame. */
 #define SC_POSE_INFO_MAX_POSES 1024u
@@ -1221,7 +1226,7 @@ int sc_pose_info_frame(sc_ctx* ctx, const sc_pose_info_params* ip, const void* p
  * context.  A refused call leaves the frame.  The device form enqueues on the context's stream and returns without waiting, and
  * needs no host word: d_pol and d_mask are complete in stream order.  The host form copies in, enqueues, copies out and waits.
  * Workspace: the chunk sums' scratch — n_poses x ceil(n / 64) x 16 doubles, a buffer of these entries' own — plus the host form's
- * device copies (n_poses x n mask bytes among them when a mask is asked for); allocated by the first such call, counted in
+ * device copies (n_poses x n mask bytes among them when a mask is asked for), in the pool every host form shares; allocated by the first such call, counted in
  * workspace_bytes and held against the frame's cap (SC_ENOMEM, nothing enqueued, the frame stays).  A context that never calls these
  * entries allocates and runs nothing new.
  * Not here: a relabelled label output (sc_assign_poses_frame, below, writes it); a form for sharded frames; weights per correspondence; a batch form (sc_polish_batch takes
@@ -1287,8 +1292,8 @@ int sc_polish_poses(sc_ctx* ctx, const sc_polish_poses_params* qp, const void* p
  * text), ap, d_pose, d_label or d_asg; ap->size wrong; mode above 1; sel_mode above 1; d_sel NULL with SC_ASSIGN_SEL_MASK; an
  * unknown flag or a non-zero reserved word; n_poses out of range; a pose_stride that breaks the rule; no frame on the context
  * (sc_peel's refusal, with its text); a call outstanding on the context.  A refused call leaves the frame.
- * Workspace: the device form needs none — the tallies are added into d_asg itself —; the host form's device copies are buffers of
- * these entries' own, allocated by the first such call, counted in workspace_bytes and held against the frame's cap (SC_ENOMEM,
+ * Workspace: the device form needs none — the tallies are added into d_asg itself —; the host form's device copies are slots of the
+ * pool every host form shares (sc_register_batch), allocated by the first such call, counted in workspace_bytes and held against the frame's cap (SC_ENOMEM,
  * nothing enqueued, the frame stays).  A context that never calls these entries allocates nothing new.
  * The loop this closes, every step stream-ordered: sc_register_instances -> sc_polish_poses_device(SEL_ALIVE) ->
  * sc_assign_poses_frame_device(BEST) -> sc_polish_poses_device(SEL_LABEL, max_iter = 1) -> sc_pose_info_frame_device(SEL_LABEL), so
@@ -1402,7 +1407,8 @@ int sc_assign_poses_batch(sc_ctx* ctx, const float* src, const float* tgt, const
  * the batch form's offsets and params as sc_assign_poses_batch refuses them.  A refused call leaves the frame.
  * Workspace: the frame form keeps the member bits and chunk sums of a round in n_poses x ceil(n / 64) x 16 doubles — the buffer
  * sc_polish_poses keeps, shared: the calls are stream-ordered, a context that uses both holds one —; the batch form the copy of the
- * offsets; the host forms device copies of their arrays.  Everything is allocated by the first such call, counted in
+ * offsets; the host forms device copies of their arrays, in the pool every host form shares
+ * (sc_register_batch).  Everything is allocated by the first such call, counted in
  * workspace_bytes and held against the cap (SC_ENOMEM, nothing enqueued, the frame stays).  A context that never calls these entries
  * allocates and runs nothing new.
  * The loop this closes, every step stream-ordered and none read back: sc_register_instances -> sc_polish_poses_device(SEL_ALIVE) ->
@@ -1510,7 +1516,8 @@ int sc_settle_poses_batch(sc_ctx* ctx, const float* src, const float* tgt, const
  * call outstanding on the context; the batch form's offsets and params as sc_assign_poses_batch refuses them.  A refused call leaves
  * the frame.
  * Workspace: the frame form keeps the support sets as bit rows, n_poses x ceil(n / 64) uint64, the tally words, and the overlap table
- * where the caller passes none; the batch form the copy of the offsets; the host forms device copies of their arrays.  Everything is
+ * where the caller passes none; the batch form the copy of the offsets; the host forms device copies of their arrays, in the pool every host form shares
+ * (sc_register_batch).  Everything is
  * allocated by the first such call, counted in workspace_bytes and held against the cap (SC_ENOMEM, nothing enqueued, the frame
  * stays).  A context that never calls these entries allocates and runs nothing new.
  * The loop this closes, every step stream-ordered and none read back: sc_register_instances -> sc_polish_poses_device(SEL_ALIVE) ->

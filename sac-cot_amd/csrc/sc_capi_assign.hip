@@ -74,15 +74,15 @@ int sc_assign_poses_frame(sc_ctx* c, const sc_assign_params* ap, const void* pos
   SC_TRY(pose_frame_check(c, who, assign_params_error(ap, pose_stride, n_poses, false, sel != nullptr)));
   const size_t n = (size_t)c->pass.n;
   const bool masked = ap->sel_mode == SC_ASSIGN_SEL_MASK;
-  HostArrays h(c);
-  h.in(c->asg_pose, pose, (size_t)pose_bytes_read(n_poses, pose_stride, assign_reads_status(ap, false)));
-  if (masked) h.in(c->asg_sel, sel, n);
-  h.out(c->asg_label, label, n * 4);
-  if (d2) h.out(c->asg_d2, d2, n * 4);
-  h.out(c->asg_out, asg, (size_t)n_poses * sizeof(sc_assign_result));
-  return pose_frame_host(c, h, nullptr, 0, [&] {  // (no scratch: the tallies are added into the records)
-    return asg_frame_enqueue(c, ap, c->asg_pose.p, pose_stride, n_poses, masked ? c->asg_sel.as<uint8_t>() : nullptr,
-                             c->asg_label.as<int32_t>(), d2 ? c->asg_d2.as<float>() : nullptr, c->asg_out.as<sc_assign_result>());
+  HostArrays h(c);  // the family's list: src, tgt, pose, sel, label, d2, asg
+  h.absent(2);
+  const int a_pose = h.in(pose, (size_t)pose_bytes_read(n_poses, pose_stride, assign_reads_status(ap, false)));
+  const int a_sel = h.in(masked ? sel : nullptr, n);
+  const int a_label = h.out(label, n * 4), a_d2 = h.out(d2, n * 4);
+  const int a_asg = h.out(asg, (size_t)n_poses * sizeof(sc_assign_result));
+  return h.run([&] {  // (no scratch: the tallies are added into the records)
+    return asg_frame_enqueue(c, ap, h.at<void>(a_pose), pose_stride, n_poses, h.at<uint8_t>(a_sel), h.at<int32_t>(a_label), h.at<float>(a_d2),
+                             h.at<sc_assign_result>(a_asg));
   });
 }
 
@@ -104,17 +104,18 @@ int sc_assign_poses_batch(sc_ctx* c, const float* src, const float* tgt, const u
   if (!src || !tgt || !offset || !p || !ap || !pose || !label || !asg) return refuse(c, who, "a NULL argument");
   SC_TRY(pose_batch_check(c, who, p, assign_params_error(ap, pose_stride, n_poses, true, false), offset, n_problems));
   const size_t total = offset[n_problems], pts = total * 12, records = (size_t)n_poses * n_problems;
-  HostArrays h(c);
-  h.in(c->asg_src, src, pts);
-  h.in(c->asg_tgt, tgt, pts);
-  h.in(c->asg_pose, pose, (size_t)pose_bytes_read(records, pose_stride, true));
-  h.out(c->asg_label, label, total * 4);
-  h.out(c->asg_out, asg, records * sizeof(sc_assign_result));
-  SC_TRY(h.room());
-  SC_TRY(h.send());
-  SC_TRY(asg_batch_enqueue(c, c->asg_src.as<float>(), c->asg_tgt.as<float>(), offset, n_problems, p, ap, c->asg_pose.p, pose_stride, n_poses,
-                           c->asg_label.as<int32_t>(), c->asg_out.as<sc_assign_result>()));
-  return h.fetch();
+  HostArrays h(c);  // the family's list: src, tgt, pose, sel, label, d2, asg
+  const int a_src = h.in(src, pts), a_tgt = h.in(tgt, pts);
+  const int a_pose = h.in(pose, (size_t)pose_bytes_read(records, pose_stride, true));
+  h.absent();
+  const int a_label = h.out(label, total * 4);
+  h.absent();
+  const int a_asg = h.out(asg, records * sizeof(sc_assign_result));
+  h.also(c->asg_off, batch_offsets_bytes(n_problems));
+  return h.run([&] {
+    return asg_batch_enqueue(c, h.at<float>(a_src), h.at<float>(a_tgt), offset, n_problems, p, ap, h.at<void>(a_pose), pose_stride, n_poses,
+                             h.at<int32_t>(a_label), h.at<sc_assign_result>(a_asg));
+  });
 }
 
 }  // extern "C"

@@ -76,7 +76,7 @@ int batch_staging_send(sc_ctx* c, Buf& dst, size_t bytes) {
 }
 
 int batch_offsets_to_device(sc_ctx* c, const uint32_t* offset, uint32_t n_problems, Buf& dst) {
-  const size_t bytes = ((size_t)n_problems + 1) * 4;
+  const size_t bytes = batch_offsets_bytes(n_problems);
   ENSURE(c, dst, bytes);
   SC_TRY(batch_staging_begin(c, bytes));
   memcpy(c->h_batch_off, offset, bytes);
@@ -84,14 +84,18 @@ int batch_offsets_to_device(sc_ctx* c, const uint32_t* offset, uint32_t n_proble
 }
 
 int HostArrays::room() {
-  if (n > MAX) return refuse(c, "HostArrays", "more arrays than it holds");
-  for (int i = 0; i < n; i++) ENSURE(c, *arr[i].buf, arr[i].bytes);
+  if (n > MAX || n_also > MAX_ALSO) return refuse(c, "HostArrays", "more arrays than it holds");
+  if (c->host_arr_live) return refuse(c, "HostArrays", "a second one on this context");
+  for (int i = 0; i < n; i++)
+    if (arr[i].from || arr[i].to) ENSURE(c, c->host_arr[i], arr[i].bytes);
+  for (int i = 0; i < n_also; i++) ENSURE(c, *more[i], more_bytes[i]);
+  c->host_arr_live = true;  // until finish
   return SC_OK;
 }
 
 int HostArrays::send() {
   for (int i = 0; i < n; i++)
-    if (arr[i].from) HIPCHK(c, hipMemcpyAsync(arr[i].buf->p, arr[i].from, arr[i].bytes, hipMemcpyHostToDevice, c->stream));
+    if (arr[i].from) HIPCHK(c, hipMemcpyAsync(c->host_arr[i].p, arr[i].from, arr[i].bytes, hipMemcpyHostToDevice, c->stream));
   return SC_OK;
 }
 
@@ -99,8 +103,18 @@ int HostArrays::fetch() {
   for (int pass = 0; pass < 2; pass++)  // those declared `first`, then the others
     for (int i = 0; i < n; i++)
       if (arr[i].to && arr[i].first == (pass == 0))
-        HIPCHK(c, hipMemcpyAsync(arr[i].to, arr[i].buf->p, arr[i].bytes, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemcpyAsync(arr[i].to, c->host_arr[i].p, arr[i].bytes, hipMemcpyDeviceToHost, c->stream));
+  return SC_OK;
+}
+
+// rc: what the copies in and the enqueue came to.  The wait comes whatever rc is, and a failed step's status before the wait's own.
+int HostArrays::finish(int rc) {
+  if (rc == SC_OK) rc = fetch();
+  const hipError_t waited = hipStreamSynchronize(c->stream);
+  c->host_arr_live = false;
+  SC_TRY(rc);
+  HIPCHK(c, waited);
+  HIPCHK(c, hipGetLastError());
   return SC_OK;
 }
 
@@ -127,15 +141,12 @@ int sc_register_batch(sc_ctx* c, const float* src, const float* tgt, const uint3
   c->cap_bytes = workspace_cap(p);
   const size_t total = offset[n_problems], pts = total * 12;
   HostArrays h(c);
-  h.in(c->batch_src, src, pts);
-  h.in(c->batch_tgt, tgt, pts);
-  h.out(c->batch_res, res, (size_t)n_problems * sizeof(sc_batch_result));
-  h.out(c->batch_mask, mask, total);
-  SC_TRY(h.room());
-  SC_TRY(h.send());
-  SC_TRY(batch_enqueue(c, c->batch_src.as<float>(), c->batch_tgt.as<float>(), offset, n_problems, p,
-                       c->batch_res.as<sc_batch_result>(), c->batch_mask.as<uint8_t>()));
-  return h.fetch();
+  const int a_src = h.in(src, pts), a_tgt = h.in(tgt, pts);
+  const int a_res = h.out(res, (size_t)n_problems * sizeof(sc_batch_result)), a_mask = h.out(mask, total);
+  h.also(c->batch_off, batch_offsets_bytes(n_problems));
+  return h.run([&] {
+    return batch_enqueue(c, h.at<float>(a_src), h.at<float>(a_tgt), offset, n_problems, p, h.at<sc_batch_result>(a_res), h.at<uint8_t>(a_mask));
+  });
 }
 
 }  // extern "C"

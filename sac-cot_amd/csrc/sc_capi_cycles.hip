@@ -114,17 +114,15 @@ int sc_pairs_cycles(sc_ctx* c, uint32_t n_sets, const uint32_t* pairs, uint32_t 
   std::vector<uint32_t> off;
   SC_TRY(cyc_check(c, who, n_sets, pairs, n_pairs, cp, pose_stride, &off));
   const uint64_t n_entries = cycles_entry_count(pairs, n_pairs);
+  SC_TRY(cyc_room(c, n_pairs, n_entries));
   HostArrays h(c);
-  h.in(c->cyc_pose, pose, (size_t)pose_bytes_read(n_pairs, pose_stride, cycles_reads_status(cp)));
-  if (keep) h.in(c->cyc_keep, keep, n_pairs);
-  h.out(c->cyc_res, res, (size_t)n_pairs * sizeof(sc_cycle_result));
-  h.out(c->cyc_sum, sum, sizeof(sc_cycle_summary));
-  SC_TRY(h.room());
-  SC_TRY(cyc_room(c, n_pairs, n_entries));  // (nothing is enqueued yet)
-  SC_TRY(h.send());
-  SC_TRY(cyc_enqueue(c, n_sets, pairs, n_pairs, n_entries, cp, off.data(), c->cyc_pose.p, pose_stride, keep ? c->cyc_keep.as<uint8_t>() : nullptr,
-                     c->cyc_res.as<sc_cycle_result>(), c->cyc_sum.as<sc_cycle_summary>()));
-  return h.fetch();
+  const int a_pose = h.in(pose, (size_t)pose_bytes_read(n_pairs, pose_stride, cycles_reads_status(cp)));
+  const int a_keep = h.in(keep, n_pairs);
+  const int a_res = h.out(res, (size_t)n_pairs * sizeof(sc_cycle_result)), a_sum = h.out(sum, sizeof(sc_cycle_summary));
+  return h.run([&] {
+    return cyc_enqueue(c, n_sets, pairs, n_pairs, n_entries, cp, off.data(), h.at<void>(a_pose), pose_stride, h.at<uint8_t>(a_keep),
+                       h.at<sc_cycle_result>(a_res), h.at<sc_cycle_summary>(a_sum));
+  });
 }
 
 }  // extern "C"

@@ -67,15 +67,14 @@ int sc_pose_info_batch(sc_ctx* c, const float* src, const float* tgt, const uint
   SC_TRY(pose_batch_check(c, "sc_pose_info_batch", p, pinfo_stride_error(pose_stride), offset, n_problems));
   const size_t total = offset[n_problems], pts = total * 12;
   HostArrays h(c);
-  h.in(c->pinfo_src, src, pts);
-  h.in(c->pinfo_tgt, tgt, pts);
-  h.in(c->pinfo_pose, pose, (size_t)pose_bytes_read(n_problems, pose_stride, true));
-  h.out(c->pinfo_out, info, (size_t)n_problems * sizeof(sc_pose_info_result));
-  SC_TRY(h.room());
-  SC_TRY(h.send());
-  SC_TRY(pinfo_enqueue(c, c->pinfo_src.as<float>(), c->pinfo_tgt.as<float>(), offset, n_problems, p, c->pinfo_pose.p, pose_stride,
-                       c->pinfo_out.as<sc_pose_info_result>()));
-  return h.fetch();
+  const int a_src = h.in(src, pts), a_tgt = h.in(tgt, pts);
+  const int a_pose = h.in(pose, (size_t)pose_bytes_read(n_problems, pose_stride, true));
+  const int a_info = h.out(info, (size_t)n_problems * sizeof(sc_pose_info_result));
+  h.also(c->pinfo_off, batch_offsets_bytes(n_problems));
+  return h.run([&] {
+    return pinfo_enqueue(c, h.at<float>(a_src), h.at<float>(a_tgt), offset, n_problems, p, h.at<void>(a_pose), pose_stride,
+                         h.at<sc_pose_info_result>(a_info));
+  });
 }
 
 int sc_pose_info_batch_slots_device(sc_ctx* c, const float* d_src_pts, const uint32_t* src_off, const float* d_tgt_pts,

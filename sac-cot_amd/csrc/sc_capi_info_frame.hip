@@ -58,11 +58,12 @@ int sc_pose_info_frame(sc_ctx* c, const sc_pose_info_params* ip, const void* pos
   SC_TRY(pose_frame_check(c, who, pose_info_params_error(ip, pose_stride, n_poses, sel != nullptr)));
   const size_t n = (size_t)c->pass.n;
   HostArrays h(c);
-  h.in(c->pinfo_frame_pose, pose, (size_t)pose_bytes_read(n_poses, pose_stride, pose_info_reads_status(ip)));
-  if (ip->sel_mode != SC_POSE_INFO_SEL_NONE) h.in(c->pinfo_frame_sel, sel, ip->sel_mode == SC_POSE_INFO_SEL_MASK ? n : n * 4);
-  h.out(c->pinfo_frame_out, info, (size_t)n_poses * sizeof(sc_pose_info_result));
-  return pose_frame_host(c, h, &c->pinfo_frame_tmp, pose_frame_scratch_bytes(c, n_poses), [&] {
-    return pinfo_frame_enqueue(c, ip, c->pinfo_frame_pose.p, pose_stride, n_poses, c->pinfo_frame_sel.p, c->pinfo_frame_out.as<sc_pose_info_result>());
+  const int a_pose = h.in(pose, (size_t)pose_bytes_read(n_poses, pose_stride, pose_info_reads_status(ip)));
+  const int a_sel = h.in(ip->sel_mode != SC_POSE_INFO_SEL_NONE ? sel : nullptr, ip->sel_mode == SC_POSE_INFO_SEL_MASK ? n : n * 4);
+  const int a_info = h.out(info, (size_t)n_poses * sizeof(sc_pose_info_result));
+  h.also(c->pinfo_frame_tmp, pose_frame_scratch_bytes(c, n_poses));
+  return h.run([&] {
+    return pinfo_frame_enqueue(c, ip, h.at<void>(a_pose), pose_stride, n_poses, h.at<void>(a_sel), h.at<sc_pose_info_result>(a_info));
   });
 }
 

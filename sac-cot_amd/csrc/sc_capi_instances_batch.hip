@@ -73,16 +73,14 @@ int sc_register_instances_batch(sc_ctx* c, const float* src, const float* tgt, c
   c->cap_bytes = workspace_cap(p);
   const size_t total = offset[n_problems], pts = total * 12;
   HostArrays h(c);
-  h.in(c->ibatch_src, src, pts);
-  h.in(c->ibatch_tgt, tgt, pts);
-  h.out(c->ibatch_res, res, (size_t)max_instances * n_problems * sizeof(sc_batch_result));
-  h.out(c->ibatch_label, label, total * 4);
-  h.out(c->ibatch_nfound, nfound, (size_t)n_problems * 4);
-  SC_TRY(h.room());
-  SC_TRY(h.send());
-  SC_TRY(ibatch_enqueue(c, c->ibatch_src.as<float>(), c->ibatch_tgt.as<float>(), offset, n_problems, p, max_instances, min_score,
-                        c->ibatch_res.as<sc_batch_result>(), c->ibatch_label.as<int32_t>(), c->ibatch_nfound.as<uint32_t>()));
-  return h.fetch();
+  const int a_src = h.in(src, pts), a_tgt = h.in(tgt, pts);
+  const int a_res = h.out(res, (size_t)max_instances * n_problems * sizeof(sc_batch_result));
+  const int a_label = h.out(label, total * 4), a_nfound = h.out(nfound, (size_t)n_problems * 4);
+  h.also(c->ibatch_off, batch_offsets_bytes(n_problems));
+  return h.run([&] {
+    return ibatch_enqueue(c, h.at<float>(a_src), h.at<float>(a_tgt), offset, n_problems, p, max_instances, min_score,
+                          h.at<sc_batch_result>(a_res), h.at<int32_t>(a_label), h.at<uint32_t>(a_nfound));
+  });
 }
 
 int sc_register_instances_batch_features_device(sc_ctx* c, const float* d_src_pts, const float* d_fsrc, const uint32_t* src_off,

@@ -119,16 +119,13 @@ int sc_match_batch(sc_ctx* c, const float* fsrc, const uint32_t* src_off, const 
   Sizes sz{};
   SC_TRY(mbatch_check(c, src_off, tgt_off, n_problems, mp, nullptr, nullptr, &mj, &sz));
   HIPCHK(c, hipSetDevice(c->device));
-  HostArrays h(c);
-  h.in(c->mbatch_fsrc, fsrc, sz.total_s * mj.dim * 4);
-  h.in(c->mbatch_ftgt, ftgt, sz.total_t * mj.dim * 4);
-  mbatch_outputs(h, c, sz, corr, d2, count);
   SC_TRY(mbatch_room(c, mj, sz, false));
-  SC_TRY(h.room());
-  SC_TRY(h.send());
-  SC_TRY(mbatch_enqueue_packed(c, mj, sz, c->mbatch_fsrc.as<float>(), c->mbatch_ftgt.as<float>(), src_off, tgt_off, c->mbatch_corr.as<int32_t>(),
-                               c->mbatch_d2.as<float>(), c->mbatch_count.as<uint32_t>()));
-  return h.fetch();
+  HostArrays h(c);
+  const MatchBatchArrays a = mbatch_arrays(h, sz, mj.dim, fsrc, sz.total_s, ftgt, sz.total_t, nullptr, nullptr, corr, d2, count);
+  return h.run([&] {
+    return mbatch_enqueue_packed(c, mj, sz, h.at<float>(a.fsrc), h.at<float>(a.ftgt), src_off, tgt_off, h.at<int32_t>(a.corr), h.at<float>(a.d2),
+                                 h.at<uint32_t>(a.count));
+  });
 }
 
 int sc_register_batch_features_device(sc_ctx* c, const float* d_src_pts, const float* d_fsrc, const uint32_t* src_off,
@@ -158,21 +155,15 @@ int sc_register_batch_features(sc_ctx* c, const float* src_pts, const float* fsr
   SC_TRY(mbatch_check(c, src_off, tgt_off, n_problems, mp, p, "sc_register_batch_features", &mj, &sz));
   HIPCHK(c, hipSetDevice(c->device));
   c->cap_bytes = workspace_cap(p);
-  HostArrays h(c);
-  h.in(c->mbatch_fsrc, fsrc, sz.total_s * mj.dim * 4);
-  h.in(c->mbatch_ftgt, ftgt, sz.total_t * mj.dim * 4);
-  h.in(c->mbatch_psrc, src_pts, sz.total_s * 12);
-  h.in(c->mbatch_ptgt, tgt_pts, sz.total_t * 12);
-  mbatch_outputs(h, c, sz, corr, d2, count);
-  h.out(c->mbatch_res, res, (size_t)n_problems * sizeof(sc_batch_result), true);  // the records are fetched first
-  h.out(c->mbatch_mask, mask, sz.slots);
   SC_TRY(mbatch_room(c, mj, sz, true));
-  SC_TRY(h.room());
-  SC_TRY(h.send());
-  SC_TRY(features_enqueue(c, mj, sz, c->mbatch_psrc.as<float>(), c->mbatch_fsrc.as<float>(), src_off, c->mbatch_ptgt.as<float>(),
-                          c->mbatch_ftgt.as<float>(), tgt_off, p, c->mbatch_res.as<sc_batch_result>(), c->mbatch_corr.as<int32_t>(),
-                          c->mbatch_d2.as<float>(), c->mbatch_count.as<uint32_t>(), c->mbatch_mask.as<uint8_t>()));
-  return h.fetch();
+  HostArrays h(c);
+  const MatchBatchArrays a = mbatch_arrays(h, sz, mj.dim, fsrc, sz.total_s, ftgt, sz.total_t, src_pts, tgt_pts, corr, d2, count);
+  const int a_res = h.out(res, (size_t)n_problems * sizeof(sc_batch_result), true);  // the records are fetched first
+  const int a_mask = h.out(mask, sz.slots);
+  return h.run([&] {
+    return features_enqueue(c, mj, sz, h.at<float>(a.psrc), h.at<float>(a.fsrc), src_off, h.at<float>(a.ptgt), h.at<float>(a.ftgt), tgt_off, p,
+                            h.at<sc_batch_result>(a_res), h.at<int32_t>(a.corr), h.at<float>(a.d2), h.at<uint32_t>(a.count), h.at<uint8_t>(a_mask));
+  });
 }
 
 }  // extern "C"

@@ -103,22 +103,16 @@ int sc_match_guided_batch(sc_ctx* c, const float* src_pts, const float* fsrc, co
   MatchBatchGuide gd{};
   SC_TRY(guide_check(c, who, gp, pose_stride, &gd));
   HIPCHK(c, hipSetDevice(c->device));
-  HostArrays h(c);
-  h.in(c->mbatch_fsrc, fsrc, sz.total_s * mj.dim * 4);
-  h.in(c->mbatch_ftgt, ftgt, sz.total_t * mj.dim * 4);
-  h.in(c->mbatch_psrc, src_pts, sz.total_s * 12);
-  h.in(c->mbatch_ptgt, tgt_pts, sz.total_t * 12);
-  h.in(c->mbatch_pose, pose, (size_t)n_problems * pose_stride);  // the records as given
-  mbatch_outputs(h, c, sz, corr, d2, count);
-  if (g2) h.out(c->mbatch_g2, g2, sz.slots * 4);  // fetched only when asked for
   SC_TRY(mbatch_room(c, mj, sz, false));
-  SC_TRY(h.room());
-  SC_TRY(h.send());
-  guide_inputs(&gd, c->mbatch_psrc.as<float>(), sz.total_s, c->mbatch_ptgt.as<float>(), sz.total_t, gp->layout, c->mbatch_pose.p,
-               g2 ? c->mbatch_g2.as<float>() : nullptr);
-  SC_TRY(packed_match(c, mj, sz, gd, c->mbatch_fsrc.as<float>(), c->mbatch_ftgt.as<float>(), src_off, tgt_off, c->mbatch_corr.as<int32_t>(),
-                      c->mbatch_d2.as<float>(), c->mbatch_count.as<uint32_t>()));
-  return h.fetch();
+  HostArrays h(c);
+  const MatchBatchArrays a = mbatch_arrays(h, sz, mj.dim, fsrc, sz.total_s, ftgt, sz.total_t, src_pts, tgt_pts, corr, d2, count);
+  const int a_pose = h.in(pose, (size_t)n_problems * pose_stride);  // the records as given
+  const int a_g2 = h.out(g2, sz.slots * 4);                         // fetched only when asked for
+  return h.run([&] {
+    guide_inputs(&gd, h.at<float>(a.psrc), sz.total_s, h.at<float>(a.ptgt), sz.total_t, gp->layout, h.at<void>(a_pose), h.at<float>(a_g2));
+    return packed_match(c, mj, sz, gd, h.at<float>(a.fsrc), h.at<float>(a.ftgt), src_off, tgt_off, h.at<int32_t>(a.corr), h.at<float>(a.d2),
+                        h.at<uint32_t>(a.count));
+  });
 }
 
 int sc_register_guided_batch_features_device(sc_ctx* c, const float* d_src_pts, const float* d_fsrc, const uint32_t* src_off,
@@ -179,20 +173,16 @@ int sc_match_guided_pairs(sc_ctx* c, const float* pts, const float* feat, const 
   SC_TRY(guide_check(c, who, gp, pose_stride, &gd));
   HIPCHK(c, hipSetDevice(c->device));
   const uint32_t total = set_off[n_sets];
-  HostArrays h(c);
-  h.in(c->mbatch_fsrc, feat, (size_t)total * mj.dim * 4);  // the table, descriptors and points: one copy of each serves both sides
-  h.in(c->mbatch_psrc, pts, (size_t)total * 12);
-  h.in(c->mbatch_pose, pose, (size_t)n_pairs * pose_stride);  // the records as given
-  mbatch_outputs(h, c, sz, corr, d2, count);
-  if (g2) h.out(c->mbatch_g2, g2, sz.slots * 4);  // fetched only when asked for
   SC_TRY(mbatch_room(c, mj, sz, false));
-  SC_TRY(h.room());
-  SC_TRY(h.send());
-  guide_inputs(&gd, c->mbatch_psrc.as<float>(), total, c->mbatch_psrc.as<float>(), total, gp->layout, c->mbatch_pose.p,
-               g2 ? c->mbatch_g2.as<float>() : nullptr);
-  SC_TRY(pairs_match(c, mj, sz, gd, c->mbatch_fsrc.as<float>(), set_off, pairs, total, c->mbatch_corr.as<int32_t>(), c->mbatch_d2.as<float>(),
-                     c->mbatch_count.as<uint32_t>()));
-  return h.fetch();
+  HostArrays h(c);
+  // the table, descriptors and points: one copy of each serves both sides
+  const MatchBatchArrays a = mbatch_arrays(h, sz, mj.dim, feat, total, nullptr, 0, pts, nullptr, corr, d2, count);
+  const int a_pose = h.in(pose, (size_t)n_pairs * pose_stride);  // the records as given
+  const int a_g2 = h.out(g2, sz.slots * 4);                      // fetched only when asked for
+  return h.run([&] {
+    guide_inputs(&gd, h.at<float>(a.psrc), total, h.at<float>(a.psrc), total, gp->layout, h.at<void>(a_pose), h.at<float>(a_g2));
+    return pairs_match(c, mj, sz, gd, h.at<float>(a.fsrc), set_off, pairs, total, h.at<int32_t>(a.corr), h.at<float>(a.d2), h.at<uint32_t>(a.count));
+  });
 }
 
 int sc_register_guided_pairs_features_device(sc_ctx* c, const float* d_pts, const float* d_feat, const uint32_t* set_off, uint32_t n_sets,

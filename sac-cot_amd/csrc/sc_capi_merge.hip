@@ -90,18 +90,17 @@ int sc_merge_poses_frame(sc_ctx* c, const sc_merge_params* mp, const void* pose,
   SC_TRY(pose_frame_check(c, who, merge_params_error(mp, pose_stride, n_poses, false, sel != nullptr)));
   const size_t n = (size_t)c->pass.n;
   const bool masked = mp->sel_mode == SC_ASSIGN_SEL_MASK;
-  HostArrays h(c);
-  h.in(c->mrg_pose, pose, (size_t)pose_bytes_read(n_poses, pose_stride, merge_reads_status(mp, false)));
-  if (masked) h.in(c->mrg_sel, sel, n);
-  h.out(c->mrg_out, out, (size_t)n_poses * sizeof(sc_merge_pose));
-  h.out(c->mrg_parent, parent, (size_t)n_poses * 4);
-  if (overlap) h.out(c->mrg_overlap, overlap, (size_t)merge_table_bytes(n_poses));
-  if (count) h.out(c->mrg_count, count, 8);
-  if (!overlap) ENSURE(c, c->mrg_table, (size_t)merge_table_bytes(n_poses));  // (nothing is enqueued yet)
-  return pose_frame_host(c, h, &c->mrg_rows, (size_t)merge_scratch_bytes(n, n_poses), [&] {
-    return mrg_frame_enqueue(c, mp, c->mrg_pose.p, pose_stride, n_poses, masked ? c->mrg_sel.as<uint8_t>() : nullptr,
-                             c->mrg_out.as<sc_merge_pose>(), c->mrg_parent.as<int32_t>(), overlap ? c->mrg_overlap.as<uint32_t>() : nullptr,
-                             count ? c->mrg_count.as<uint32_t>() : nullptr);
+  HostArrays h(c);  // the family's list: src, tgt, pose, sel, out, parent, overlap, count
+  h.absent(2);
+  const int a_pose = h.in(pose, (size_t)pose_bytes_read(n_poses, pose_stride, merge_reads_status(mp, false)));
+  const int a_sel = h.in(masked ? sel : nullptr, n);
+  const int a_out = h.out(out, (size_t)n_poses * sizeof(sc_merge_pose)), a_parent = h.out(parent, (size_t)n_poses * 4);
+  const int a_overlap = h.out(overlap, (size_t)merge_table_bytes(n_poses)), a_count = h.out(count, 8);
+  h.also(c->mrg_rows, (size_t)merge_scratch_bytes(n, n_poses));
+  if (!overlap) h.also(c->mrg_table, (size_t)merge_table_bytes(n_poses));
+  return h.run([&] {
+    return mrg_frame_enqueue(c, mp, h.at<void>(a_pose), pose_stride, n_poses, h.at<uint8_t>(a_sel), h.at<sc_merge_pose>(a_out),
+                             h.at<int32_t>(a_parent), h.at<uint32_t>(a_overlap), h.at<uint32_t>(a_count));
   });
 }
 
@@ -123,18 +122,18 @@ int sc_merge_poses_batch(sc_ctx* c, const float* src, const float* tgt, const ui
   if (!src || !tgt || !offset || !p || !mp || !pose || !out || !parent) return refuse(c, who, "a NULL argument");
   SC_TRY(pose_batch_check(c, who, p, merge_params_error(mp, pose_stride, n_poses, true, false), offset, n_problems));
   const size_t total = offset[n_problems], pts = total * 12, records = (size_t)n_poses * n_problems;
-  HostArrays h(c);
-  h.in(c->mrg_src, src, pts);
-  h.in(c->mrg_tgt, tgt, pts);
-  h.in(c->mrg_pose, pose, (size_t)pose_bytes_read(records, pose_stride, true));
-  h.out(c->mrg_out, out, records * sizeof(sc_merge_pose));
-  h.out(c->mrg_parent, parent, records * 4);
-  if (count) h.out(c->mrg_count, count, (size_t)n_problems * 8);
-  SC_TRY(h.room());
-  SC_TRY(h.send());
-  SC_TRY(mrg_batch_enqueue(c, c->mrg_src.as<float>(), c->mrg_tgt.as<float>(), offset, n_problems, p, mp, c->mrg_pose.p, pose_stride, n_poses,
-                           c->mrg_out.as<sc_merge_pose>(), c->mrg_parent.as<int32_t>(), count ? c->mrg_count.as<uint32_t>() : nullptr));
-  return h.fetch();
+  HostArrays h(c);  // the family's list: src, tgt, pose, sel, out, parent, overlap, count
+  const int a_src = h.in(src, pts), a_tgt = h.in(tgt, pts);
+  const int a_pose = h.in(pose, (size_t)pose_bytes_read(records, pose_stride, true));
+  h.absent();
+  const int a_out = h.out(out, records * sizeof(sc_merge_pose)), a_parent = h.out(parent, records * 4);
+  h.absent();
+  const int a_count = h.out(count, (size_t)n_problems * 8);
+  h.also(c->mrg_off, batch_offsets_bytes(n_problems));
+  return h.run([&] {
+    return mrg_batch_enqueue(c, h.at<float>(a_src), h.at<float>(a_tgt), offset, n_problems, p, mp, h.at<void>(a_pose), pose_stride, n_poses,
+                             h.at<sc_merge_pose>(a_out), h.at<int32_t>(a_parent), h.at<uint32_t>(a_count));
+  });
 }
 
 }  // extern "C"

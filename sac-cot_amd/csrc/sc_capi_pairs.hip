@@ -83,15 +83,13 @@ int sc_match_pairs(sc_ctx* c, const float* feat, const uint32_t* set_off, uint32
   Sizes sz{};
   SC_TRY(pairs_check(c, set_off, n_sets, pairs, n_pairs, mp, nullptr, nullptr, &mj, &sz));
   HIPCHK(c, hipSetDevice(c->device));
-  HostArrays h(c);
-  h.in(c->mbatch_fsrc, feat, (size_t)set_off[n_sets] * mj.dim * 4);  // the table: one copy serves both sides
-  mbatch_outputs(h, c, sz, corr, d2, count);
   SC_TRY(mbatch_room(c, mj, sz, false));
-  SC_TRY(h.room());
-  SC_TRY(h.send());
-  SC_TRY(pairs_match(c, mj, sz, c->mbatch_fsrc.as<float>(), set_off, pairs, c->mbatch_corr.as<int32_t>(), c->mbatch_d2.as<float>(),
-                     c->mbatch_count.as<uint32_t>()));
-  return h.fetch();
+  HostArrays h(c);
+  // the table: one copy serves both sides
+  const MatchBatchArrays a = mbatch_arrays(h, sz, mj.dim, feat, set_off[n_sets], nullptr, 0, nullptr, nullptr, corr, d2, count);
+  return h.run([&] {
+    return pairs_match(c, mj, sz, h.at<float>(a.fsrc), set_off, pairs, h.at<int32_t>(a.corr), h.at<float>(a.d2), h.at<uint32_t>(a.count));
+  });
 }
 
 int sc_register_pairs_features_device(sc_ctx* c, const float* d_pts, const float* d_feat, const uint32_t* set_off, uint32_t n_sets,
@@ -122,20 +120,18 @@ int sc_register_pairs_features(sc_ctx* c, const float* pts, const float* feat, c
   HIPCHK(c, hipSetDevice(c->device));
   c->cap_bytes = workspace_cap(p);
   const size_t total = set_off[n_sets];
-  HostArrays h(c);
-  h.in(c->mbatch_fsrc, feat, total * mj.dim * 4);  // the table, descriptors and points: one copy of each serves both sides
-  h.in(c->mbatch_psrc, pts, total * 12);
-  mbatch_outputs(h, c, sz, corr, d2, count);
-  h.out(c->mbatch_res, res, (size_t)n_pairs * sizeof(sc_batch_result), true);  // the records are fetched first
-  h.out(c->mbatch_mask, mask, sz.slots);
   SC_TRY(mbatch_room(c, mj, sz, true));
-  SC_TRY(h.room());
-  SC_TRY(h.send());
-  uint32_t* d_count = c->mbatch_count.as<uint32_t>();
-  SC_TRY(pairs_match(c, mj, sz, c->mbatch_fsrc.as<float>(), set_off, pairs, c->mbatch_corr.as<int32_t>(), c->mbatch_d2.as<float>(), d_count, p,
-                     c->mbatch_psrc.as<float>(), (uint32_t)total));
-  SC_TRY(mbatch_register(c, sz, p, d_count, c->mbatch_res.as<sc_batch_result>(), c->mbatch_mask.as<uint8_t>()));
-  return h.fetch();
+  HostArrays h(c);
+  // the table, descriptors and points: one copy of each serves both sides
+  const MatchBatchArrays a = mbatch_arrays(h, sz, mj.dim, feat, total, nullptr, 0, pts, nullptr, corr, d2, count);
+  const int a_res = h.out(res, (size_t)n_pairs * sizeof(sc_batch_result), true);  // the records are fetched first
+  const int a_mask = h.out(mask, sz.slots);
+  return h.run([&] {
+    uint32_t* d_count = h.at<uint32_t>(a.count);
+    SC_TRY(pairs_match(c, mj, sz, h.at<float>(a.fsrc), set_off, pairs, h.at<int32_t>(a.corr), h.at<float>(a.d2), d_count, p, h.at<float>(a.psrc),
+                       (uint32_t)total));
+    return mbatch_register(c, sz, p, d_count, h.at<sc_batch_result>(a_res), h.at<uint8_t>(a_mask));
+  });
 }
 
 int sc_polish_pairs_slots_device(sc_ctx* c, const float* d_pts, const uint32_t* set_off, uint32_t n_sets, const uint32_t* pairs,

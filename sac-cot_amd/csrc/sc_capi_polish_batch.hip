@@ -80,16 +80,14 @@ int sc_polish_batch(sc_ctx* c, const float* src, const float* tgt, const uint32_
   c->cap_bytes = workspace_cap(p);
   const size_t total = offset[n_problems], pts = total * 12;
   HostArrays h(c);
-  h.in(c->pbatch_src, src, pts);
-  h.in(c->pbatch_tgt, tgt, pts);
-  h.in(c->pbatch_res, res, (size_t)n_problems * sizeof(sc_batch_result));
-  h.out(c->pbatch_pol, pol, (size_t)n_problems * sizeof(sc_polish_batch_result));
-  h.out(c->pbatch_mask, mask, total);
-  SC_TRY(h.room());
-  SC_TRY(h.send());
-  SC_TRY(pbatch_enqueue(c, c->pbatch_src.as<float>(), c->pbatch_tgt.as<float>(), offset, n_problems, p, pp, c->pbatch_res.as<sc_batch_result>(),
-                        c->pbatch_pol.as<sc_polish_batch_result>(), c->pbatch_mask.as<uint8_t>()));
-  return h.fetch();
+  const int a_src = h.in(src, pts), a_tgt = h.in(tgt, pts);
+  const int a_res = h.in(res, (size_t)n_problems * sizeof(sc_batch_result));
+  const int a_pol = h.out(pol, (size_t)n_problems * sizeof(sc_polish_batch_result)), a_mask = h.out(mask, total);
+  h.also(c->pbatch_off, batch_offsets_bytes(n_problems));
+  return h.run([&] {
+    return pbatch_enqueue(c, h.at<float>(a_src), h.at<float>(a_tgt), offset, n_problems, p, pp, h.at<sc_batch_result>(a_res),
+                          h.at<sc_polish_batch_result>(a_pol), h.at<uint8_t>(a_mask));
+  });
 }
 
 int sc_polish_batch_slots_device(sc_ctx* c, const float* d_src_pts, const uint32_t* src_off, const float* d_tgt_pts, const uint32_t* tgt_off,

@@ -62,13 +62,13 @@ int sc_polish_poses(sc_ctx* c, const sc_polish_poses_params* qp, const void* pos
   SC_TRY(pose_frame_check(c, who, polish_poses_params_error(qp, pose_stride, n_poses, sel != nullptr)));
   const size_t n = (size_t)c->pass.n;
   HostArrays h(c);
-  h.in(c->ppose_pose, pose, (size_t)pose_bytes_read(n_poses, pose_stride, polish_poses_reads_status(qp)));
-  if (polish_poses_reads_sel(qp->sel_mode)) h.in(c->ppose_sel, sel, polish_poses_sel_is_label(qp->sel_mode) ? n * 4 : n);
-  h.out(c->ppose_out, pol, (size_t)n_poses * sizeof(sc_polish_batch_result));
-  if (mask) h.out(c->ppose_mask, mask, (size_t)n_poses * n);
-  return pose_frame_host(c, h, &c->ppose_tmp, pose_frame_scratch_bytes(c, n_poses), [&] {
-    return ppose_enqueue(c, qp, c->ppose_pose.p, pose_stride, n_poses, c->ppose_sel.p, c->ppose_out.as<sc_polish_batch_result>(),
-                         mask ? c->ppose_mask.as<uint8_t>() : nullptr);
+  const int a_pose = h.in(pose, (size_t)pose_bytes_read(n_poses, pose_stride, polish_poses_reads_status(qp)));
+  const int a_sel = h.in(polish_poses_reads_sel(qp->sel_mode) ? sel : nullptr, polish_poses_sel_is_label(qp->sel_mode) ? n * 4 : n);
+  const int a_pol = h.out(pol, (size_t)n_poses * sizeof(sc_polish_batch_result)), a_mask = h.out(mask, (size_t)n_poses * n);
+  h.also(c->ppose_tmp, pose_frame_scratch_bytes(c, n_poses));
+  return h.run([&] {
+    return ppose_enqueue(c, qp, h.at<void>(a_pose), pose_stride, n_poses, h.at<void>(a_sel), h.at<sc_polish_batch_result>(a_pol),
+                         h.at<uint8_t>(a_mask));
   });
 }
 

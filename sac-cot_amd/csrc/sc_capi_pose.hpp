@@ -1,7 +1,7 @@
 // sc_capi_pose.hpp — the host steps the entries on a caller's pose records share (sc_pose_info_frame, sc_polish_poses,
 // sc_assign_poses, sc_settle_poses; the batch check also sc_pose_info_batch's), said once: the heads of their jobs (PoseFrameHead,
-// PoseBatchHead: sc_kernels.hpp), the order of a frame form's and of a batch form's refusals, and the tail of a frame form's host
-// entry.  Each entry brings what is its own: its rule (sc_pose_check.hpp and the check headers beside it), its buffers, its launch.
+// PoseBatchHead: sc_kernels.hpp) and the order of a frame form's and of a batch form's refusals.  A host form's sequence is
+// HostArrays::run (sc_ctx.hpp).  Each entry brings what is its own: its rule (sc_pose_check.hpp and the check headers beside it), its scratch, its launch.
 // Everything that can refuse a call is decided before anything is enqueued.
 #pragma once
 #include "sc_ctx.hpp"
@@ -28,20 +28,8 @@ inline void pose_frame_head(const sc_ctx* c, PoseFrameHead* h, const void* d_pos
   h->pose = d_pose; h->pose_stride = pose_stride;
   h->status = reads_status;
 }
-// the chunk scratch of an entry that keeps one: a block per pose (sc_chunks.hpp)
+// the chunk scratch of an entry that keeps one: a block per pose (sc_chunks.hpp); a host form names it with HostArrays::also
 inline size_t pose_frame_scratch_bytes(const sc_ctx* c, uint32_t n_poses) { return (size_t)n_poses * chunk_scratch_bytes(c->pass.n); }
-// The host form behind its check and the declaration of its arrays: room for every buffer, then for the scratch (tmp == nullptr: the
-// entry has none) — nothing is enqueued before — the copies in, the device form's enqueue on the buffers, the copies out and the wait.
-template <class Enqueue>
-int pose_frame_host(sc_ctx* c, HostArrays& h, Buf* tmp, size_t tmp_bytes, Enqueue enqueue) {
-  SC_TRY(h.room());
-  if (tmp) ENSURE(c, *tmp, tmp_bytes);
-  SC_TRY(h.send());
-  SC_TRY(enqueue());
-  SC_TRY(h.fetch());
-  HIPCHK(c, hipGetLastError());
-  return SC_OK;
-}
 
 // ---- a batch form
 // The refusals, in this order: the context, sc_params, the family's rule (`broken`), the offsets; then the context's device and cap.

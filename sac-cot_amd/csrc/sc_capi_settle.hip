@@ -77,17 +77,16 @@ int sc_settle_poses_frame(sc_ctx* c, const sc_settle_params* sp, const void* pos
   SC_TRY(pose_frame_check(c, who, settle_params_error(sp, pose_stride, n_poses, false, sel != nullptr)));
   const size_t n = (size_t)c->pass.n;
   const bool masked = sp->sel_mode == SC_ASSIGN_SEL_MASK;
-  HostArrays h(c);
-  h.in(c->stl_pose, pose, (size_t)pose_bytes_read(n_poses, pose_stride, settle_reads_status(sp, false)));
-  if (masked) h.in(c->stl_sel, sel, n);
-  h.out(c->stl_out, pol, (size_t)n_poses * sizeof(sc_polish_batch_result));
-  h.out(c->stl_label, label, n * 4);
-  if (d2) h.out(c->stl_d2, d2, n * 4);
-  if (rounds) h.out(c->stl_rounds, rounds, 8);
-  return pose_frame_host(c, h, &c->ppose_tmp, pose_frame_scratch_bytes(c, n_poses), [&] {
-    return stl_frame_enqueue(c, sp, c->stl_pose.p, pose_stride, n_poses, masked ? c->stl_sel.as<uint8_t>() : nullptr,
-                             c->stl_out.as<sc_polish_batch_result>(), c->stl_label.as<int32_t>(), d2 ? c->stl_d2.as<float>() : nullptr,
-                             rounds ? c->stl_rounds.as<uint32_t>() : nullptr);
+  HostArrays h(c);  // the family's list: src, tgt, pose, sel, pol, label, d2, rounds
+  h.absent(2);
+  const int a_pose = h.in(pose, (size_t)pose_bytes_read(n_poses, pose_stride, settle_reads_status(sp, false)));
+  const int a_sel = h.in(masked ? sel : nullptr, n);
+  const int a_pol = h.out(pol, (size_t)n_poses * sizeof(sc_polish_batch_result));
+  const int a_label = h.out(label, n * 4), a_d2 = h.out(d2, n * 4), a_rounds = h.out(rounds, 8);
+  h.also(c->ppose_tmp, pose_frame_scratch_bytes(c, n_poses));
+  return h.run([&] {
+    return stl_frame_enqueue(c, sp, h.at<void>(a_pose), pose_stride, n_poses, h.at<uint8_t>(a_sel), h.at<sc_polish_batch_result>(a_pol),
+                             h.at<int32_t>(a_label), h.at<float>(a_d2), h.at<uint32_t>(a_rounds));
   });
 }
 
@@ -109,18 +108,19 @@ int sc_settle_poses_batch(sc_ctx* c, const float* src, const float* tgt, const u
   if (!src || !tgt || !offset || !p || !sp || !pose || !pol || !label) return refuse(c, who, "a NULL argument");
   SC_TRY(pose_batch_check(c, who, p, settle_params_error(sp, pose_stride, n_poses, true, false), offset, n_problems));
   const size_t total = offset[n_problems], pts = total * 12, records = (size_t)n_poses * n_problems;
-  HostArrays h(c);
-  h.in(c->stl_src, src, pts);
-  h.in(c->stl_tgt, tgt, pts);
-  h.in(c->stl_pose, pose, (size_t)pose_bytes_read(records, pose_stride, true));
-  h.out(c->stl_out, pol, records * sizeof(sc_polish_batch_result));
-  h.out(c->stl_label, label, total * 4);
-  if (rounds) h.out(c->stl_rounds, rounds, (size_t)n_problems * 8);
-  SC_TRY(h.room());
-  SC_TRY(h.send());
-  SC_TRY(stl_batch_enqueue(c, c->stl_src.as<float>(), c->stl_tgt.as<float>(), offset, n_problems, p, sp, c->stl_pose.p, pose_stride, n_poses,
-                           c->stl_out.as<sc_polish_batch_result>(), c->stl_label.as<int32_t>(), rounds ? c->stl_rounds.as<uint32_t>() : nullptr));
-  return h.fetch();
+  HostArrays h(c);  // the family's list: src, tgt, pose, sel, pol, label, d2, rounds
+  const int a_src = h.in(src, pts), a_tgt = h.in(tgt, pts);
+  const int a_pose = h.in(pose, (size_t)pose_bytes_read(records, pose_stride, true));
+  h.absent();
+  const int a_pol = h.out(pol, records * sizeof(sc_polish_batch_result));
+  const int a_label = h.out(label, total * 4);
+  h.absent();
+  const int a_rounds = h.out(rounds, (size_t)n_problems * 8);
+  h.also(c->stl_off, batch_offsets_bytes(n_problems));
+  return h.run([&] {
+    return stl_batch_enqueue(c, h.at<float>(a_src), h.at<float>(a_tgt), offset, n_problems, p, sp, h.at<void>(a_pose), pose_stride, n_poses,
+                             h.at<sc_polish_batch_result>(a_pol), h.at<int32_t>(a_label), h.at<uint32_t>(a_rounds));
+  });
 }
 
 }  // extern "C"

@@ -133,6 +133,9 @@ struct Frame {
   sc_stats pend_stats{};         // the library's own copy of the call's statistics: sc_wait hands it to the caller
 };
 
+// What a host form may stage at once (HostArrays, below): sc_register_batch_features has nine arrays
+constexpr int N_HOST_ARR = 9;
+
 // The grow-only device workspace: Buf members and nothing else.  sc_destroy walks it as an array (workspace_bufs), so a Buf declared
 // here is freed; there is no second list to keep in step.
 struct Workspace {
@@ -151,54 +154,41 @@ struct Workspace {
       match_part, match_words, match_fsrc, match_ftgt, match_psrc, match_ptgt, match_corr, match_d2, match_gsrc, match_gtgt, match_g2,
       // sc_match_guided_poses, the host forms' device copies of the pose records and of the labels: allocated by the first of them
       match_pose, match_label,
-      // sc_register_batch: allocated by the first batch call, never by a frame.  off: the copy of the caller's offsets; the rest:
-      // device copies of the host entry's arrays
-      batch_off, batch_src, batch_tgt, batch_res, batch_mask,
+      // The staging pool of every other host form (HostArrays, below): slot k holds the device copy of the k-th array the form
+      // declares.  Allocated by the first host form that needs the slot, never by a frame or a device form; alive for one host form
+      // at a time, dead on its return.
+      host_arr[N_HOST_ARR],
+      // ---- what follows is allocated by the first call of the entry named, host or device form, never by a frame or by another entry
+      // sc_register_batch.  off: the copy of the caller's offsets
+      batch_off,
       // sc_match_batch / sc_register_batch_features, and sc_match_pairs / sc_register_pairs_features (a pair is a problem of theirs,
-      // found through a record): allocated by the first such call, never by a frame.  meta: the copies of both offset arrays, the
-      // slot starts and the tile map (pairs: the pairs' records, the slot starts, the tile map); top: the rows' lists between the two launches; words: a "clean" word per
-      // problem, then the column minima; gsrc / gtgt: the gathered points, slot-positioned; the rest: device copies of the host
-      // entries' arrays (pairs: fsrc / psrc hold the one table)
-      mbatch_meta, mbatch_top, mbatch_words, mbatch_gsrc, mbatch_gtgt, mbatch_fsrc, mbatch_ftgt, mbatch_psrc, mbatch_ptgt, mbatch_corr,
-      mbatch_d2, mbatch_count, mbatch_res, mbatch_mask,
-      // sc_match_guided_batch / sc_match_guided_pairs, the host forms' device copies of the pose records and of g2 (the rest is the
-      // mbatch set): allocated by the first such call, never by a frame or by another batch entry
-      mbatch_pose, mbatch_g2,
-      // sc_polish_batch: allocated by the first such call, never by a frame or by another batch entry.  off: the copy of the caller's
-      // offsets (the slot form: both arrays and the slot starts; the pairs form: the pairs' records); the rest: device copies of the host entry's arrays
-      pbatch_off, pbatch_src, pbatch_tgt, pbatch_res, pbatch_pol, pbatch_mask,
-      // sc_register_instances_batch: allocated by the first such call, never by a frame or by another batch entry.  off: the copy of
-      // the caller's offsets; the rest: device copies of the host entry's arrays (the features form holds what
+      // found through a record).  meta: the copies of both offset arrays, the slot starts and the tile map (pairs: the pairs' records,
+      // the slot starts, the tile map); top: the rows' lists between the two launches; words: a "clean" word per problem, then the
+      // column minima; gsrc / gtgt: the gathered points, slot-positioned
+      mbatch_meta, mbatch_top, mbatch_words, mbatch_gsrc, mbatch_gtgt,
+      // sc_polish_batch.  off: the copy of the caller's offsets (the slot form: both arrays and the slot starts; the pairs form: the
+      // pairs' records)
+      pbatch_off,
+      // sc_register_instances_batch.  off: the copy of the caller's offsets (the features form holds what
       // sc_register_batch_features_device holds, in the mbatch buffers)
-      ibatch_off, ibatch_src, ibatch_tgt, ibatch_res, ibatch_label, ibatch_nfound,
-      // sc_pose_info_batch: allocated by the first such call, never by a frame or by another batch entry.  off: the copy of the
-      // caller's offsets (the slot form: both arrays and the slot starts; the pairs form: the pairs' records); the rest: device copies
-      // of the host entry's arrays
-      pinfo_off, pinfo_src, pinfo_tgt, pinfo_pose, pinfo_out,
-      // sc_pose_info_frame: allocated by the first such call, never by a frame or by another entry.  tmp: the chunk sums and bit
-      // words, n_poses x chunk_scratch_bytes(n) — not polish_tmp: a polish may be enqueued behind the call —; the rest:
-      // device copies of the host entry's arrays
-      pinfo_frame_tmp, pinfo_frame_pose, pinfo_frame_sel, pinfo_frame_out,
-      // sc_polish_poses: allocated by the first such call, never by a frame or by another entry.  tmp: the chunk sums and bit words,
-      // n_poses x chunk_scratch_bytes(n) — not polish_tmp and not pinfo_frame_tmp: either call may be enqueued behind this
-      // one —; the rest: device copies of the host entry's arrays
-      ppose_tmp, ppose_pose, ppose_sel, ppose_out, ppose_mask,
-      // sc_assign_poses: allocated by the first such call, never by a frame or by another entry.  The frame form's device entry needs
-      // none of them (the tallies are added into the caller's records).  off: the batch form's copy of the caller's offsets; the
-      // rest: device copies of the host entries' arrays (src / tgt: the batch form's points)
-      asg_off, asg_src, asg_tgt, asg_pose, asg_sel, asg_label, asg_d2, asg_out,
-      // sc_settle_poses: allocated by the first such call, never by a frame or by another entry.  The frame form's member bits and
-      // chunk sums live in ppose_tmp — sc_polish_poses's buffer, one layout (sc_chunks.hpp): the calls are stream-ordered, so one serves both.
-      // off: the batch form's copy of the caller's offsets; the rest: device copies of the host entries' arrays
-      stl_off, stl_src, stl_tgt, stl_pose, stl_sel, stl_out, stl_label, stl_d2, stl_rounds,
-      // sc_merge_poses: allocated by the first such call, never by a frame or by another entry.  rows: the frame form's support sets,
-      // n_poses x ceil(n / 64) u64, and behind them the 2 x n_poses tally words; table: the overlap table where the caller passes none;
-      // off: the batch form's copy of the caller's offsets; the rest: device copies of the host entries' arrays
-      mrg_rows, mrg_table, mrg_off, mrg_src, mrg_tgt, mrg_pose, mrg_sel, mrg_out, mrg_parent, mrg_overlap, mrg_count,
-      // sc_pairs_cycles: allocated by the first such call, never by a frame or by another entry.  meta: the pairs' records and the
-      // sorted neighbour entries (sc_cycles_check.hpp); wide: the oriented fp64 poses; state: the round words and the two buffers of
-      // alive bytes; the rest: device copies of the host entry's arrays
-      cyc_meta, cyc_wide, cyc_state, cyc_pose, cyc_keep, cyc_res, cyc_sum;
+      ibatch_off,
+      // sc_pose_info_batch.  off: the copy of the caller's offsets (the slot form: both arrays and the slot starts; the pairs form:
+      // the pairs' records)
+      pinfo_off,
+      // sc_pose_info_frame.  tmp: the chunk sums and bit words, n_poses x chunk_scratch_bytes(n) — not polish_tmp: a polish may be
+      // enqueued behind the call
+      pinfo_frame_tmp,
+      // sc_polish_poses.  tmp: the chunk sums and bit words, n_poses x chunk_scratch_bytes(n) — not polish_tmp and not
+      // pinfo_frame_tmp: either call may be enqueued behind this one.  sc_settle_poses's frame form keeps its member bits and chunk
+      // sums here as well: one layout (sc_chunks.hpp), and the calls are stream-ordered, so one serves both
+      ppose_tmp,
+      // sc_assign_poses, sc_settle_poses, sc_merge_poses.  off: the batch form's copy of the caller's offsets (assign's frame form
+      // needs no buffer: the tallies are added into the caller's records).  mrg_rows: merge's frame form's support sets, n_poses x
+      // ceil(n / 64) u64, and behind them the 2 x n_poses tally words; mrg_table: its overlap table where the caller passes none
+      asg_off, stl_off, mrg_off, mrg_rows, mrg_table,
+      // sc_pairs_cycles.  meta: the pairs' records and the sorted neighbour entries (sc_cycles_check.hpp); wide: the oriented fp64
+      // poses; state: the round words and the two buffers of alive bytes
+      cyc_meta, cyc_wide, cyc_state;
 };
 constexpr size_t N_WORKSPACE_BUFS = sizeof(Workspace) / sizeof(Buf);
 static_assert(std::is_standard_layout<Workspace>::value && alignof(Workspace) == alignof(Buf) && sizeof(Workspace) == N_WORKSPACE_BUFS * sizeof(Buf),
@@ -243,6 +233,7 @@ struct sc_ctx : sc::Workspace {  // (the workspace buffers are direct members to
   // copy out of it (the next batch call waits for it before it overwrites the area)
   void* h_batch_off = nullptr; size_t h_batch_off_cap = 0;
   hipEvent_t batch_off_ev = nullptr;
+  bool host_arr_live = false;  // a host form is between its room and its return: host_arr is its (HostArrays::run)
   uint64_t ev_capacity = 1ull << 21;  // event records (32 B each); doubled after an overflow
   sc::Tuning tn;  // defaults unless sc_set_debug() changed them; the library reads no environment variable
   // decoupled look-back launches (single-pass scan, fused compaction): their state area and its epoch
@@ -385,29 +376,51 @@ inline BatchJob batch_job_of(const sc_params* p) {
 int batch_staging_begin(sc_ctx* c, size_t bytes);
 int batch_staging_send(sc_ctx* c, Buf& dst, size_t bytes);
 // the caller's offsets (n_problems + 1 words) through that area into dst (enqueued)
+inline size_t batch_offsets_bytes(uint32_t n_problems) { return ((size_t)n_problems + 1) * 4; }
 int batch_offsets_to_device(sc_ctx* c, const uint32_t* offset, uint32_t n_problems, Buf& dst);
 
-// The host-array form of a batch entry (defined in sc_capi_batch.hip): the entry declares its arrays — an input is copied in, an
-// output copied out, each through a workspace buffer of the entry's own and each with its byte count said once — and then runs
-//   room (ENSURE every buffer, in declaration order; nothing is enqueued before the last one has its room, so SC_ENOMEM leaves no
-//   copy from the caller's memory in flight) -> send (the copies in, in declaration order) -> the device form's sequence on the
-//   buffers -> fetch (the copies out — those declared `first` before the others, each group in declaration order — and the wait
-//   for the stream).
+// The host-array form of an entry (defined in sc_capi_batch.hip).  The entry declares its arrays — an input is copied in, an output
+// copied out, each with its byte count said once — and gets a handle for each; the k-th array declared is staged in slot k of the
+// context's pool (Workspace::host_arr), whichever entry declares it.  An optional array the caller did not pass is declared all the
+// same, with its host pointer NULL: it keeps its slot, needs no room, is not copied, and `at` gives nullptr for it.  `also` names a
+// workspace buffer of the entry's own (its scratch, its copy of the offsets) that its enqueue is going to ENSURE.  Then
+//   run(enqueue): room for every staged array, in declaration order, then for every `also` buffer — nothing is enqueued before the
+//   last one has its room, so SC_ENOMEM leaves no copy from the caller's memory in flight -> the copies in, in declaration order ->
+//   enqueue(), the device form's sequence on at<T>(handle) -> the copies out — those declared `first` before the others, each group
+//   in declaration order -> the wait for the stream.  A step that fails behind the room is waited for as well: whatever a host form
+//   returns, no copy from or into the caller's memory is in flight.
+// One HostArrays is alive per context (sc_ctx::host_arr_live); between its return and the next one's room the pool holds nothing.
 struct HostArrays {
-  static constexpr int MAX = 9;  // sc_register_batch_features has nine
+  static constexpr int MAX = N_HOST_ARR;
+  static constexpr int MAX_ALSO = 2;  // sc_merge_poses_frame: its rows and its own table
   explicit HostArrays(sc_ctx* ctx) : c(ctx) {}
-  void in(Buf& b, const void* host, size_t bytes) { add(Arr{&b, host, nullptr, bytes, false}); }
-  void out(Buf& b, void* host, size_t bytes, bool first = false) { add(Arr{&b, nullptr, host, bytes, first}); }
+  int in(const void* host, size_t bytes) { return add(Arr{host, nullptr, bytes, false}); }
+  int out(void* host, size_t bytes, bool first = false) { return add(Arr{nullptr, host, bytes, first}); }
+  // k arrays that only the family's other form has (a frame form's src, tgt; a batch form's sel): their slots stay theirs.  The two
+  // forms of a family declare ONE list in ONE order, so that an array has the same slot in both — as it had one buffer in both
+  void absent(int k = 1) { while (k-- > 0) add(Arr{nullptr, nullptr, 0, false}); }
+  void also(Buf& b, size_t bytes) { if (n_also < MAX_ALSO) { more[n_also] = &b; more_bytes[n_also] = bytes; } n_also++; }
+  // the device copy of a declared array, once run has made its room (nullptr: the caller did not pass it)
+  template <class T> T* at(int k) const { return k < MAX && (arr[k].from || arr[k].to) ? c->host_arr[k].as<T>() : nullptr; }
+  template <class Enqueue> int run(Enqueue enqueue) {
+    SC_TRY(room());
+    int rc = send();
+    if (rc == SC_OK) rc = enqueue();
+    return finish(rc);
+  }
+
+ private:
+  struct Arr { const void* from; void* to; size_t bytes; bool first; };
+  int add(const Arr& a) { if (n < MAX) arr[n] = a; return n++; }  // (room refuses an entry that declared more)
   int room();
   int send();
   int fetch();
-
- private:
-  struct Arr { Buf* buf; const void* from; void* to; size_t bytes; bool first; };
-  void add(const Arr& a) { if (n < MAX) arr[n] = a; n++; }  // (room refuses an entry that declared more)
+  int finish(int rc);
   sc_ctx* c;
   Arr arr[MAX];
-  int n = 0;
+  Buf* more[MAX_ALSO];
+  size_t more_bytes[MAX_ALSO];
+  int n = 0, n_also = 0;
 };
 
 // ---- the batched match sequence: defined in sc_capi_match_batch.hip but for the template, used by sc_capi_instances_batch.hip
@@ -417,11 +430,21 @@ struct MatchBatchSizes {
   size_t total_s, total_t, slots;  // rows of fsrc, rows of ftgt, output entries (total_s * knn)
   BatchMetaLayout meta;            // the metadata of the form (sc_match_batch_check.hpp): its words, where the slot starts and the tile map sit
 };
-// the arrays a match writes, as its host entries declare them
-inline void mbatch_outputs(HostArrays& h, sc_ctx* c, const MatchBatchSizes& sz, int32_t* corr, float* d2, uint32_t* count) {
-  h.out(c->mbatch_corr, corr, sz.slots * 8);
-  h.out(c->mbatch_d2, d2, sz.slots * 4);
-  h.out(c->mbatch_count, count, (size_t)sz.n_problems * 8);
+// The arrays every host form of a match declares, always these seven in this order (their slots are the same in every form): the
+// descriptors and keypoints of both sides — NULL for what a form has not: a match alone has no keypoints, a pairs form one table
+// (its rows in fsrc / psrc: one copy serves both sides) — and the three outputs of the match.
+struct MatchBatchArrays { int fsrc, ftgt, psrc, ptgt, corr, d2, count; };
+inline MatchBatchArrays mbatch_arrays(HostArrays& h, const MatchBatchSizes& sz, uint32_t dim, const float* fsrc, size_t src_rows, const float* ftgt,
+                                      size_t tgt_rows, const float* psrc, const float* ptgt, int32_t* corr, float* d2, uint32_t* count) {
+  MatchBatchArrays a;
+  a.fsrc = h.in(fsrc, src_rows * dim * 4);
+  a.ftgt = h.in(ftgt, tgt_rows * dim * 4);
+  a.psrc = h.in(psrc, src_rows * 12);
+  a.ptgt = h.in(ptgt, tgt_rows * 12);
+  a.corr = h.out(corr, sz.slots * 8);
+  a.d2 = h.out(d2, sz.slots * 4);
+  a.count = h.out(count, (size_t)sz.n_problems * 8);
+  return a;
 }
 // every refusal of a packed batched match; `p` only for a features entry, whose name for the messages is `features` (nullptr: the
 // match alone).  Fills *job (but its pointers) and *sz.

@@ -275,7 +275,9 @@ def _assert_slots(got, exp, slot, what):
 
 def test_a_capped_workspace_refuses_before_anything_is_enqueued(pkg, O):
     """max_workspace = 1: the first buffer an entry asks for is SC_ENOMEM on a fresh context and on a used one — host arithmetic,
-    made before the first copy or launch.  The same call under the default cap on the same context then equals the reference."""
+    made before the first copy or launch.  The same call under the default cap on the same context then equals the reference.  (The
+    host forms' device copies are one pool: the last entry finds every buffer it needs on the used context, so its refusal is shown on
+    a fresh one, and on the used one it runs under the same cap.)"""
     import torch
     reg = pkg.Registrar(0)
     try:
@@ -341,9 +343,18 @@ def test_a_capped_workspace_refuses_before_anything_is_enqueued(pkg, O):
         got = run(pkg.make_params(**P.KW))
         _assert_slots(got[:5], P.features(O, tab, pairs, mkw, P.KW), got[5], "sc_register_pairs_features")
 
-        run = lambda a: reg.register_batch_features_raw(packed[0], packed[1], so, packed[2], packed[3], to, mp, a)  # noqa: E731
-        refused(lambda: run(pkg.make_params(**M.KW, max_workspace=1)), "sc_register_batch_features")
+        # the packed form of the same family: refused on a context of its own.  On this one nothing of its own is missing — the match's
+        # buffers are the pairs form's, and the nine slots of the host forms' pool were warmed by the entries above (every array here is
+        # below the 64 KiB a slot holds at least) — and a call that allocates nothing is refused by no cap: it equals the reference
+        run = lambda a, r=reg: r.register_batch_features_raw(packed[0], packed[1], so, packed[2], packed[3], to, mp, a)  # noqa: E731
+        fresh = pkg.Registrar(0)
+        try:
+            refused(lambda: run(pkg.make_params(**M.KW, max_workspace=1), fresh), "sc_register_batch_features")
+        finally:
+            fresh.close()
         efeat = [M.features_one(O, s[0], s[1], s[2], s[3], mkw, M.KW) for s in scenes]
-        _assert_slots(run(pkg.make_params(**M.KW)), efeat, so.astype(np.int64) * int(mp.knn), "sc_register_batch_features")
+        slot = so.astype(np.int64) * int(mp.knn)
+        _assert_slots(run(pkg.make_params(**M.KW, max_workspace=1)), efeat, slot, "sc_register_batch_features, nothing to allocate")
+        _assert_slots(run(pkg.make_params(**M.KW)), efeat, slot, "sc_register_batch_features")
     finally:
         reg.close()
