@@ -1604,7 +1604,7 @@ int sc_finalize_gathered_device(sc_ctx* ctx, const uint64_t* d_keys, int n_pairs
  * the finalize call / sc_wait deliver the real ones.) */
 int sc_finalize_gathered_device_async(sc_ctx* ctx, const uint64_t* d_keys, int n_pairs, float* d_Rt, uint8_t* d_mask);
 
-/* Phase 1 in two halves, for large T_total over several GPUs: stage B's certificate (sc_tri.hip 3b) samples ~5T/8
+/* Phase 1 in two halves, for large T_total over several GPUs: stage B's certificate (sc_tri_prune.hip 3b) samples ~5T/8
  * edges, which every rank would otherwise repeat (126 us at T_total = 400 k against 33 us at 50 k).  `begin` runs A,
  * the edge list and THIS rank's share of the sample (every shard_world-th sampled edge) into d_hist (device,
  * SC_HIST_WORDS x u32, zeroed here); the caller SUMS d_hist over the ranks (one 1 KiB all-reduce; any order: integer

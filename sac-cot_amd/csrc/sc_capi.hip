@@ -888,8 +888,7 @@ int sc_shard_select_device(sc_ctx* c, const uint32_t* d_hist, void* d_cand_mine)
   if (c->pass.M == 0) {  // nothing enumerated here (also E == 0): an empty blob
     HIPCHK(c, hipMemsetAsync(b.hdr, 0, CAND_HDR_WORDS * 8, c->stream));
   } else {
-    launch_cand_emit(c->sel_ord.as<uint64_t>(), c->sel_key.as<uint32_t>(), c->kcol.as<uint2>(), c->ei.as<uint32_t>(),
-                     c->ej.as<uint32_t>(), &c->ctl.as<ControlBlock>()->sel, c->toff.as<uint64_t>(), c->pass.E, c->pass.T_eff,
+    launch_cand_emit(selection_of(c), keys_of(c), edges_of(c), counts_of(c), c->pass.T_eff,
                      // a full-length list (T entries) is never "cut": the global top-T takes at most T from one rank
                      select_want(c, p) < p->max_triangles ? (uint64_t)c->pass.T_eff : ~0ull, b, c->stream);
   }
@@ -916,9 +915,9 @@ int sc_shard_score_device(sc_ctx* c, const void* d_cand_all, uint64_t* d_key, sc
   SC_TRY(ensure_compaction(c, nb, nb, T));  // (no room beyond the need: no host-free call comes here)
   arm_word(c, HW_MERGED_T);
   c->pinned[HW_MERGE_SHORT] = 0;  // "an estimated bound promised T keys above it and the merged candidates hold fewer" (merge_prepare_kernel)
-  launch_merge_prepare(d_cand_all, blob_bytes, G, T, window_known(p), &ctl->klb, sel, &c->pinned[HW_MERGED_T], st,
-                       c->pass.form.est_active ? &c->pinned[HW_MERGE_SHORT] : nullptr);
-  launch_select_rounds(view, sel, select_rounds(window_known(p)), c->tn, st);
+  launch_merge_prepare(d_cand_all, blob_bytes, G, T, window_known(p), &ctl->klb, sel, &c->pinned[HW_MERGED_T],
+                       c->pass.form.est_active ? &c->pinned[HW_MERGE_SHORT] : nullptr, st);
+  launch_select_rounds(view, sel, select_rounds(window_known(p)), nullptr, c->tn, st);
   c->pinned[HW_CAND_CUT] = 0;  // "a cut candidate list could have mattered": read by the finalize call (SC_ERETRY)
   SC_TRY(run_compaction(c, view, nb, select_rounds(window_known(p)), nullptr));
   launch_merge_check(d_cand_all, blob_bytes, G, sel, &c->pinned[HW_CAND_CUT], st);  // (behind the compaction: its counting kernel is what resolves the last round into k*)

@@ -87,7 +87,7 @@ int sc_triangles_host(sc_ctx* c, const float* src, const float* tgt, int64_t n, 
     ENSURE(c, c->sort_tmp, sort_bytes + 16);
     ENSURE(c, c->tri_rk, T * 12);
     ENSURE(c, c->key_rk, T * 4);
-    launch_rank_order(c->tri.as<uint32_t>(), c->sel_key.as<uint32_t>(), c->pass.T_eff, c->sortkey.as<uint64_t>(),
+    launch_rank_order(c->tri.as<uint32_t>(), selection_of(c), c->pass.T_eff, c->sortkey.as<uint64_t>(),
                       c->sorted.as<uint64_t>(), c->sort_tmp.p, sort_bytes, c->tri_rk.as<uint32_t>(),
                       c->key_rk.as<uint32_t>(), c->stream);
     HIPCHK(c, hipMemcpyAsync(tri, c->tri_rk.p, T * 12, hipMemcpyDeviceToHost, c->stream));

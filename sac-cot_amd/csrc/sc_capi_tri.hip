@@ -1,4 +1,4 @@
-// sc_capi_tri.hip — stage B's host side: which of sc_tri.hip's kernels a call runs, in what order, into which arrays.  Host-only, on
+// sc_capi_tri.hip — stage B's host side: which of stage B's kernels (sc_tri_edges.hip, sc_tri_prune.hip, sc_tri.hip) a call runs, in what order, into which arrays.  Host-only, on
 // the context (sc_ctx.hpp); sc_capi.hip's entries and the stage hooks call run_edges / run_select / run_triangles.
 //
 // Four jobs, each in its own place:
@@ -25,8 +25,6 @@ static uint64_t edge_capacity(const sc_ctx* c, bool build) {
   if (!build) for (const Buf* b : {&c->ebi, &c->ebj}) cap = b->cap / 4 < cap ? b->cap / 4 : cap;
   return cap;
 }
-// ... and the key arrays (what fast_plan caps its key cover by, and the speculative key pass may write)
-static uint64_t key_capacity(const sc_ctx* c) { return c->wkey.cap / 4 < c->kcol.cap / 8 ? c->wkey.cap / 4 : c->kcol.cap / 8; }
 
 // The smallest key a triangle can have in weight ranking: every edge has s >= t_cmp up to rounding (0.1 % slack), so w >= ~3 t_cmp — what
 // the select's a-priori window and the pruning samples' floors rest on.  NOT when -1 / (2 sigma^2) overflowed fp32 (sigma below 2^-64.5 =
@@ -53,18 +51,32 @@ uint32_t select_want(const sc_ctx* c, const sc_params* p) {
   return cap < p->max_triangles ? cap : p->max_triangles;
 }
 
-// sharded stage B: the device-side edge range [lo, hi) this rank enumerates (nullptr: every edge)
-static const uint64_t* own_range_of(const sc_ctx* c) {
-  return c->pass.sharded_ab ? c->ctl.as<ControlBlock>()->own_edge : nullptr;
+// The views of the context's stage-B arrays (sc_kernels.hpp), as they stand NOW: taken again behind whatever grows an array.
+// The edge list: E is c->pass.E (read_edge_count sets it); a host-free call's real count sits in edge_off[n]; the fused edge kernel
+// writes no per-edge bases
+EdgeList edges_of(const sc_ctx* c) {
+  const StageBForm& f = c->pass.form;
+  return EdgeList{c->ei.as<uint32_t>(), c->ej.as<uint32_t>(), c->es.as<float>(),
+                  f.build ? nullptr : c->ebi.as<uint32_t>(), f.build ? nullptr : c->ebj.as<uint32_t>(), c->ebase.as<uint32_t>(),
+                  c->pass.E, f.spec ? c->edge_off.as<uint64_t>() + c->pass.n : nullptr, f.spec ? c->shape.E_last : c->pass.E,
+                  edge_capacity(c, f.build)};
 }
-// a host-free call's real edge count, in device memory (edge_off[n]; nullptr on a waited call: E is the count)
-static const uint64_t* edge_count_dev(const sc_ctx* c) {
-  return c->pass.form.spec ? c->edge_off.as<uint64_t>() + c->pass.n : nullptr;
+// the per-edge counts; sharded stage B: the device-side edge range [lo, hi) this rank enumerates (nullptr: every edge)
+EdgeCounts counts_of(const sc_ctx* c) {
+  return EdgeCounts{c->tcnt.as<uint32_t>(), c->toff.as<uint64_t>(), c->pass.sharded_ab ? c->ctl.as<ControlBlock>()->own_edge : nullptr};
 }
-// the per-edge CSR bases (the fused edge kernel writes none: its consumers take the per-row bases, ebase, instead)
-struct EdgeBases { const uint32_t* i; const uint32_t* j; };
-static EdgeBases edge_bases_of(const sc_ctx* c) {
-  return c->pass.form.build ? EdgeBases{nullptr, nullptr} : EdgeBases{c->ebi.as<uint32_t>(), c->ebj.as<uint32_t>()};
+// the key arrays (cap: what fast_plan caps its key cover by, and the speculative key pass may write)
+KeyArrays keys_of(const sc_ctx* c) {
+  return KeyArrays{c->wkey.as<uint32_t>(), c->kcol.as<uint2>(), c->wkey.cap / 4 < c->kcol.cap / 8 ? c->wkey.cap / 4 : c->kcol.cap / 8,
+                   c->blk_minmax.as<uint32_t>(), &c->ctl.as<ControlBlock>()->sel};
+}
+Selection selection_of(const sc_ctx* c) {
+  return Selection{c->sel_ord.as<uint64_t>(), c->sel_key.as<uint32_t>(), c->sel_ord.cap / 8 < c->sel_key.cap / 4 ? c->sel_ord.cap / 8 : c->sel_key.cap / 4};
+}
+// what the pruning kernel writes (no strong list yet: prune() says which form)
+static Pruned pruned_of(const sc_ctx* c) {
+  ControlBlock* ctl = c->ctl.as<ControlBlock>();
+  return Pruned{c->bits2.as<uint64_t>(), &ctl->smin, &ctl->klb, StrongList{nullptr, nullptr, 0u, 0u}};
 }
 // the host word of "the select found fewer keys above the pruning bound than it promised" (sharded: the merge's word says it)
 static uint64_t* select_short_word(sc_ctx* c) { return c->pass.sharded_ab ? nullptr : &c->pinned[HW_SELECT_SHORT]; }
@@ -88,7 +100,7 @@ int ensure_frame(sc_ctx* c) {
   return SC_OK;
 }
 
-// The hot path's fused form of row_stats_scan + edge_fill + the estimating sample (sc_tri.hip 1'): where the pruning bound
+// The hot path's fused form of row_stats_scan + edge_fill + the estimating sample (sc_tri_edges.hip 1'): where the pruning bound
 // will be an estimate (the same conditions as form_begin's and form_counted's, minus what only the edge count decides) and the
 // bit rows are short enough for the kernel.  hyp_begin asks — with "the whole sample, own histogram" (StageBForm::own_sample) —
 // before stage A, and fast_plan, because the fused kernel writes no per-edge bases.
@@ -110,7 +122,7 @@ static int form_begin(sc_ctx* c, const sc_params* p, const uint32_t* hist, uint3
   if (f.build && !f.own_sample) { c->last_error = "internal: the fused edge kernel was chosen for a call that shares its sample"; return SC_EHIP; }
   f.fused = c->pass.rows_fused || f.build;
   c->pass.rows_fused = false;
-  // An ESTIMATED bound where the call can be repeated should the select find it too high (sc_tri.hip 3c): the common
+  // An ESTIMATED bound where the call can be repeated should the select find it too high (sc_tri_prune.hip 3c): the common
   // form only — event list, a-priori select window (the check rides the window's first round), the whole sample here
   // (sharded, SC_FLAG_EST_BOUND: every rank takes the WHOLE sample — it is cheaper than the latency of the all-reduce that
   // would sum the ranks' shares — and the merge of the candidates verifies the bound: sc_shard_score_device)
@@ -123,7 +135,7 @@ static int form_begin(sc_ctx* c, const sc_params* p, const uint32_t* hist, uint3
 // What the edge count decides (E: the count, or a host-free call's cover): pruning, the event path, the sample's plan.
 static void form_counted(sc_ctx* c, const sc_params* p, const Graph& g, uint64_t E) {
   StageBForm& f = c->pass.form;
-  // certified pruning (sc_tri.hip 3b): weight ranking only; pointless on tiny graphs
+  // certified pruning (sc_tri_prune.hip 3b): weight ranking only; pointless on tiny graphs
   f.pruned = may_prune(p) && E >= 4096;
   // counting pass + event list (sc_tri.hip 2b) on the pruned graph; Tuning::no_events keeps the row-walking pair
   f.use_events = f.pruned && !c->tn.no_events;
@@ -171,26 +183,23 @@ static int scan_degrees(sc_ctx* c, const sc_params* p) {
   return SC_OK;
 }
 
-// The edge list, into arrays that hold `cap` entries (writes beyond are dropped by the kernel).  The fused kernel also makes the
+// The edge list, into arrays that hold el.cap entries (writes beyond are dropped by the kernel).  The fused kernel also makes the
 // row statistics and the count itself.
 // the weight histogram of the heaviest-edge pruning sample is collected by the same kernel (sc_debug.sample_mode = ...
 // any: it costs edge_fill ~1 us and saves a launch whenever that sample is chosen)
-static void fill_edges(sc_ctx* c, const Graph& g, uint64_t cap) {
+static void fill_edges(sc_ctx* c, const Graph& g, const EdgeList& el) {
   const StageBForm& f = c->pass.form;
-  hipStream_t st = c->stream;
-  if (f.build) {
-    launch_edge_build(g, points_of(c), c->pass.dv, c->bits2.as<uint64_t>(), c->edge_off.as<uint64_t>(), c->ebase.as<uint32_t>(),
-                      c->ei.as<uint32_t>(), c->ej.as<uint32_t>(), c->es.as<float>(), cap, f.spec ? nullptr : &c->pinned[HW_EDGES], st,
-                      f.spec ? c->ctl.as<ControlBlock>()->live_edges : nullptr);
-    return;
-  }
-  launch_edge_fill(g, points_of(c), c->pass.dv, c->edge_off.as<uint64_t>(), c->ei.as<uint32_t>(), c->ej.as<uint32_t>(),
-                   c->es.as<float>(), c->ebase.as<uint32_t>(), f.fused || scan_writes_ebase((size_t)c->pass.n), c->ebi.as<uint32_t>(),
-                   c->ebj.as<uint32_t>(), cap, c->ctl.as<ControlBlock>()->es_hist, st);
+  ControlBlock* ctl = c->ctl.as<ControlBlock>();
+  if (f.build)  // (the count: to the host that waits for it, or — host-free — as the range the scan of the counts stops at)
+    launch_edge_build(g, points_of(c), c->pass.dv, c->bits2.as<uint64_t>(), c->edge_off.as<uint64_t>(), el,
+                      f.spec ? nullptr : &c->pinned[HW_EDGES], f.spec ? ctl->live_edges : nullptr, c->stream);
+  else
+    launch_edge_fill(g, points_of(c), c->pass.dv, c->edge_off.as<uint64_t>(), el, f.fused || scan_writes_ebase((size_t)c->pass.n),
+                     ctl->es_hist, c->stream);
 }
 
 // The first wait.  Host-free call (fast_plan() made sure E_cov <= the arrays' capacity): no wait.  E is then what the launches and
-// arrays COVER; the kernels take the real count from edge_off[n] (edge_count_dev) and the end of the call validates it.
+// arrays COVER; the kernels take the real count from edge_off[n] (EdgeList::E_dev) and the end of the call validates it.
 // Sets c->pass.E, the form's second part, and "nothing yet" for what run_select delivers.
 static int read_edge_count(sc_ctx* c, const sc_params* p, const Graph& g, uint32_t* hist) {
   const bool spec = c->pass.form.spec;
@@ -239,44 +248,41 @@ static int grow_edge_arrays(sc_ctx* c, uint64_t E, bool* moved) {
 
 // The pruning sample — this process's share (`part` of `parts`), or the whole of it — into the control block's histogram, and from
 // there into `hist` where the histogram is exchanged; before it, where asked for, the exact count of the whole graph's 3-cliques.
-static int run_sample(sc_ctx* c, const sc_params* p, const Graph& g, uint64_t E, uint32_t* hist, uint32_t part, uint32_t parts) {
+static int run_sample(sc_ctx* c, const sc_params* p, const Graph& g, const EdgeList& el, uint32_t* hist, uint32_t part, uint32_t parts) {
   const StageBForm& f = c->pass.form;
   if (!f.pruned) return SC_OK;
   hipStream_t st = c->stream;
   ControlBlock* ctl = c->ctl.as<ControlBlock>();
-  const uint64_t* E_dev = edge_count_dev(c);
-  if (f.have_total) {
-    launch_tri_count(g, g.bits, c->es.as<float>(), nullptr, c->ei.as<uint32_t>(), c->ej.as<uint32_t>(), E,
-                     c->tcnt.as<uint32_t>(), nullptr, c->tn, st);
-    launch_scan_u32(c->tcnt.as<uint32_t>(), E, c->toff.as<uint64_t>(), c->scan_tmp.p, c->tn, st, &c->pinned[HW_TOTAL]);
+  if (f.have_total) {  // the whole graph, every rank's edges
+    EdgeCounts all = counts_of(c);
+    all.own = nullptr;
+    launch_tri_count(g, Pruned{}, el, all, c->tn, st);
+    launch_scan_u32(all.tcnt, el.E, all.toff, c->scan_tmp.p, c->tn, st, &c->pinned[HW_TOTAL]);
   }
   if (f.build && !f.est_active) { c->last_error = "internal: the fused edge kernel ran but the bound is not an estimate"; return SC_EHIP; }
   if (f.est_active) {
     // an estimating sample (the single-GPU hot path; sharded, SC_FLAG_EST_BOUND: every rank takes the whole of it), inlier count, a call
     // big enough for stage C2's Gram filter to be in question: the sample also
     // leaves its workgroups' best triangles behind — the voters of that filter's reference frame (count_triangles passes them on)
-    uint4* cand = nullptr;
+    SampleCands cands;
     if ((f.est_local || f.est_shard) && p->score_mode == 0 && c->tn.score_filter != 1 && c->tn.score_filter != 2 && !c->tn.gram_ref_late &&
         (uint64_t)p->max_triangles * (uint64_t)c->pass.n >= (1ull << 27)) {
       if (!c->ref_cand.p) {
         ENSURE(c, c->ref_cand, 4096 * sizeof(uint4));
         HIPCHK(c, hipMemsetAsync(c->ref_cand.p, 0, 4096 * sizeof(uint4), st));
       }
-      cand = c->ref_cand.as<uint4>();
-      c->pass.ref_cand_n = sample_candidate_blocks(E, c->tn);
+      cands = SampleCands{c->ref_cand.as<uint4>(), ctl->ref_slot};
+      c->pass.ref_cand_n = sample_candidate_blocks(el.E, c->tn);
     }
-    const EdgeBases eb = edge_bases_of(c);
-    launch_sample_estimate(g, eb.i, eb.j, c->ei.as<uint32_t>(), c->ej.as<uint32_t>(), c->es.as<float>(), E, key_floor(p),
-                           c->pass.plan.rate, ctl->prune_hist, c->tn, st, E_dev, c->ebase.as<uint32_t>(), cand, cand ? ctl->ref_slot : nullptr);
+    launch_sample_estimate(g, el, c->pass.plan.rate, ctl->prune_hist, cands, c->tn, st);
   } else {
     // SC_FLAG_EST_BOUND on the phase API where the plan is NOT an estimate (select window unknown: t_cmp below ~0.668; sc_debug's
     // no_events / no_estimate / sample_mode): the caller still skips the histogram all-reduce, so every rank must end up with the
     // SAME histogram — each takes the WHOLE certifying sample, not its share (with shares the ranks derived different
     // bounds, cut the strong list differently, and the merged top-T could miss triangles)
     const bool whole = f.est_shard;
-    launch_sample_hist(g, c->ebi.as<uint32_t>(), c->ebj.as<uint32_t>(), c->ei.as<uint32_t>(), c->ej.as<uint32_t>(),
-                       c->es.as<float>(), E, p->max_triangles, key_floor(p), whole ? 0u : part, whole ? 1u : parts,
-                       ctl->prune_hist, ctl->es_hist, c->tn, st, E_dev, f.spec ? c->shape.E_last : 0);
+    launch_sample_hist(g, el, p->max_triangles, key_floor(p), whole ? 0u : part, whole ? 1u : parts, ctl->prune_hist, ctl->es_hist,
+                       c->tn, st);
   }
   if (hist) launch_hist_reduce(ctl->prune_hist, hist, st);  // the exchanged form: one 256-bin histogram
   return SC_OK;
@@ -295,18 +301,19 @@ int run_edges(sc_ctx* c, const sc_params* p, uint32_t* hist, uint32_t part, uint
   // capacity are dropped by the kernel; in that case, or on a first call, it runs (again) after the read-back.
   const Graph g = graph_of(c);
   const uint64_t spec_cap = edge_capacity(c, f.build);
-  if (spec_cap || f.build) fill_edges(c, g, spec_cap);  // (the fused kernel also makes the row statistics and the count itself)
+  if (spec_cap || f.build) fill_edges(c, g, edges_of(c));  // (the fused kernel also makes the row statistics and the count itself)
   SC_TRY(read_edge_count(c, p, g, hist));
   const uint64_t E = c->pass.E;
   if (E == 0) return SC_OK;
   bool edge_arrays_moved = false;
   SC_TRY(grow_edge_arrays(c, E, &edge_arrays_moved));
+  const EdgeList el = edges_of(c);  // (the count is known, the arrays hold it)
   if (E > spec_cap || edge_arrays_moved) {  // first call, or the graph outgrew the arrays (just re-allocated above)
     if (spec_cap && !f.build)  // the partial run's counts
       HIPCHK(c, hipMemsetAsync(c->ctl.as<ControlBlock>()->es_hist, 0, sizeof(uint32_t) * PR_HCOPIES * 256, c->stream));
-    fill_edges(c, g, E);
+    fill_edges(c, g, el);
   }
-  return run_sample(c, p, g, E, hist, part, parts);
+  return run_sample(c, p, g, el, hist, part, parts);
 }
 
 // ---- the form, second half -----------------------------------------------------------------------------------------------------
@@ -320,7 +327,7 @@ static int form_select(sc_ctx* c, const sc_params* p, const uint32_t* hist) {
   // is bracketed by events; spec_cap: the keys the arrays of the earlier calls hold (0: none yet, no speculative pass).
   f.spec_cap = 0;
   if (f.use_events && window_known(p) && !c->pass.timing)
-    f.spec_cap = f.spec ? c->pass.mode.M_cov : key_capacity(c);  // (M_cov <= that capacity: fast_plan)
+    f.spec_cap = f.spec ? c->pass.mode.M_cov : keys_of(c).cap;  // (M_cov <= that capacity: fast_plan)
   // Exactly those calls, on one rank, take their ordinals from an ORDERED strong list (sc_tri.hip
   // 2c): no scan of the per-edge counts, the key kernel leaves the triangle count where the scan would.  While the pruning kernel's
   // grid stays within what a workgroup's prologue sums (C3 does not), and until a call's list had more chunks than the key kernel
@@ -355,10 +362,10 @@ static void form_keys(sc_ctx* c, const sc_params* p, uint64_t M, bool key_arrays
 // what the steps hand on to each other
 struct SelectArgs {
   Graph g;
-  StrongList sl{nullptr, nullptr, 0};
+  EdgeList el;       // (E = el.E: the count, or a host-free call's cover)
+  EdgeCounts cnt;
+  Pruned pr{};       // the bit rows the counting pass walks and the weight bound: none until prune() has pruned
   OrdList ord{};
-  const uint64_t* mbits = nullptr;  // the bit rows the counting pass walks: the graph's, or the pruned copy
-  const float* smin = nullptr;      // the certified weight bound (device; nullptr: no pruning)
   EventList ev{};
   ScanExtra xr;                     // the range of the scan of the per-edge counts (counts_range)
   int chunk_shift = 0;              // an OrdList's chunk: the positions a workgroup of the counting pass takes per trip
@@ -366,51 +373,52 @@ struct SelectArgs {
 
 // Prune with the (summed) sample histogram: the strong bit rows, the strong list — ordered where the ordinals come from it — and,
 // sharded, the second cut of the ranks' ranges.
-static int prune(sc_ctx* c, const sc_params* p, const uint32_t* hist, uint64_t E, SelectArgs& a) {
+static int prune(sc_ctx* c, const sc_params* p, const uint32_t* hist, SelectArgs& a) {
   const StageBForm& f = c->pass.form;
-  a.mbits = a.g.bits;
   if (!f.pruned) return SC_OK;
+  const uint64_t E = a.el.E;
   hipStream_t st = c->stream;
   ControlBlock* ctl = c->ctl.as<ControlBlock>();
+  a.pr = pruned_of(c);
   if (f.use_events) {  // the pruning kernel also compacts the strong edges for the counting pass
     ENSURE(c, c->strong, strong_list_bytes(E));  // (a waited call: run_edges left room)
     ENSURE(c, c->ord_cnt, ORD_MAX_BLOCKS * sizeof(uint32_t));  // (by every call of the event path: a host-free one finds it)
-    a.sl = StrongList{c->strong.as<uint32_t>(), ctl->st_fill, strong_list_cap(E), 0u};
+    a.pr.sl = StrongList{c->strong.as<uint32_t>(), ctl->st_fill, strong_list_cap(E), 0u};
   }
   if (f.ord_on) {
     // tloc and ctot live where the scan's offsets would: toff holds 2 E + 2 words, tloc takes E of them, ctot at most E / 4 + 4
     // from the next multiple of four (E >= 4096), and the count lands in toff[E] as ever
-    uint32_t* words = c->toff.as<uint32_t>();
+    uint32_t* words = a.cnt.words();
     a.ord.cnt = c->ord_cnt.as<uint32_t>(); a.ord.tloc = words; a.ord.ctot = words + ((E + 3) & ~(uint64_t)3);
-    a.ord.n_strong = &ctl->n_strong; a.ord.total = c->toff.as<uint64_t>() + E; a.ord.E = E; a.ord.E_dev = edge_count_dev(c);
+    a.ord.n_strong = &ctl->n_strong; a.ord.total = a.cnt.toff + E; a.ord.E = E; a.ord.E_dev = a.el.E_dev;
     a.ord.chunk_max = c->tn.ord_chunk_max && c->tn.ord_chunk_max < ORD_CHUNK_MAX ? c->tn.ord_chunk_max : ORD_CHUNK_MAX;
-    a.sl.cnt = a.ord.cnt;
+    a.pr.sl.cnt = a.ord.cnt;
   }
   // contiguous regions: a rank walks only the regions its own edge range touches (unsharded the modulo form stays: the
   // counting pass is no faster with contiguous regions at C2 / C4 and 20 us slower at C3)
-  if (f.recut) a.sl.region_blocks = a.sl.cap / 256;
-  launch_prune_bits(a.g, f.own_sample ? ctl->prune_hist : hist, f.own_sample, c->ei.as<uint32_t>(), c->ej.as<uint32_t>(), c->es.as<float>(), E,
-                    f.est_active ? c->pass.plan.hist_want : (uint64_t)p->max_triangles, key_floor(p), c->bits2.as<uint64_t>(), &ctl->smin, &ctl->klb, a.sl,
-                    c->tcnt.as<uint32_t>(), f.recut ? nullptr : own_range_of(c), st, edge_count_dev(c), f.est_active, f.trimmed);
+  if (f.recut) a.pr.sl.region_blocks = a.pr.sl.cap / 256;
+  EdgeCounts listed = a.cnt;  // (recut: EVERY rank's strong edges are listed — the cut comes behind the list)
+  if (f.recut) listed.own = nullptr;
+  PruneOpts po;
+  po.logbins = f.est_active; po.trimmed = f.trimmed;
+  launch_prune_bits(a.g, f.own_sample ? ctl->prune_hist : hist, f.own_sample, a.el,
+                    f.est_active ? c->pass.plan.hist_want : (uint64_t)p->max_triangles, key_floor(p), a.pr, listed, po, st);
   if (f.recut) {
     ENSURE(c, c->rowcost, ((size_t)c->pass.n + 4 + 1024) * 4);  // (cost_split_kernel reads whole 16-byte pieces)
-    launch_strong_rowcost(a.g, c->bits2.as<uint64_t>(), c->rowcost.as<uint32_t>(), st);
+    launch_strong_rowcost(a.g, a.pr, c->rowcost.as<uint32_t>(), st);
     launch_cost_split(c->rowcost.as<uint32_t>(), c->edge_off.as<uint64_t>(), c->pass.n, (uint32_t)p->shard_rank,
                       (uint32_t)p->shard_world, ctl->own_row, ctl->own_edge, st);
   }
-  a.mbits = c->bits2.as<uint64_t>();
-  a.smin = &ctl->smin;
   return SC_OK;
 }
 
 // The counting pass: per-edge triangle counts — with the event list, and under the same launch the vote for stage C2's reference
 // frame, or walking the rows.
-static int count_triangles(sc_ctx* c, const sc_params* p, uint64_t E, SelectArgs& a) {
+static int count_triangles(sc_ctx* c, const sc_params* p, SelectArgs& a) {
   const StageBForm& f = c->pass.form;
   hipStream_t st = c->stream;
   if (!f.use_events) {
-    launch_tri_count(a.g, a.mbits, c->es.as<float>(), a.smin, c->ei.as<uint32_t>(), c->ej.as<uint32_t>(), E,
-                     c->tcnt.as<uint32_t>(), own_range_of(c), c->tn, st);
+    launch_tri_count(a.g, a.pr, a.el, a.cnt, c->tn, st);
     return SC_OK;
   }
   // Tuning::event_cap (test hook) forces a (too) small buffer for THIS call without touching the context's own
@@ -427,50 +435,46 @@ static int count_triangles(sc_ctx* c, const sc_params* p, uint64_t E, SelectArgs
     ref.src.cand = c->ref_cand.as<uint4>(); ref.src.n_cand = c->pass.ref_cand_n; ref.src.cand_slot = c->ctl.as<ControlBlock>()->ref_slot;
     c->pass.ref_done = true;
   }
-  const EdgeBases eb = edge_bases_of(c);
-  launch_tri_count_events(a.g, a.mbits, a.sl, eb.i, eb.j, c->ei.as<uint32_t>(), c->ej.as<uint32_t>(), f.spec ? c->shape.E_last : E,
-                          p->rank_mode, c->tcnt.as<uint32_t>(), a.ev, c->tn, st, own_range_of(c), c->ebase.as<uint32_t>(),
-                          ref.out ? &ref : nullptr, f.ord_on ? &a.ord : nullptr);
+  launch_tri_count_events(a.g, a.pr, a.el, a.cnt, p->rank_mode, a.ev, a.ord, ref.out ? &ref : nullptr, c->tn, st);
   return SC_OK;
 }
 
 // the edges whose counts the scan reads.  sharded: the counts outside this rank's edge range are zero — their tiles are skipped;
 // trimmed (form_select): the tiles beyond the real edges
 static void counts_range(sc_ctx* c, SelectArgs& a) {
-  a.xr.range = c->pass.form.trimmed ? c->ctl.as<ControlBlock>()->live_edges : own_range_of(c);
+  a.xr.range = c->pass.form.trimmed ? c->ctl.as<ControlBlock>()->live_edges : a.cnt.own;
 }
 
 // read-back #2: triangle count (of the pruned graph when pruning), written to pinned memory by the scan of the per-edge counts ->
 // toff (host-free: not written, the kernels read toff[E])
-static int scan_counts(sc_ctx* c, uint64_t E, SelectArgs& a) {
+static int scan_counts(sc_ctx* c, SelectArgs& a) {
   arm_word(c, HW_TRIANGLES);
-  SC_TRY(lb_next(c, scan_temp_bytes(E), 0, 0, &a.xr.lb));
-  launch_scan_u32(c->tcnt.as<uint32_t>(), E, c->toff.as<uint64_t>(), c->scan_tmp.p, c->tn, c->stream,
+  SC_TRY(lb_next(c, scan_temp_bytes(a.el.E), 0, 0, &a.xr.lb));
+  launch_scan_u32(a.cnt.tcnt, a.el.E, a.cnt.toff, c->scan_tmp.p, c->tn, c->stream,
                   c->pass.form.spec ? nullptr : &c->pinned[HW_TRIANGLES], &a.xr);
   return SC_OK;
 }
 
-// The key pass over the event list: `cap` keys at most (writes beyond are dropped); want / klb: what the select's first round is
-// told (klb == nullptr: no a-priori window); host_count: the pinned word that receives the triangle count, as the scan's would.
-static void key_pass(sc_ctx* c, const sc_params* p, uint64_t E, const SelectArgs& a, uint64_t want, const uint32_t* klb, uint64_t cap,
-                     uint64_t* host_count) {
-  const bool ord_on = c->pass.form.ord_on;
-  launch_tri_keys_events(a.g, c->es.as<float>(), c->toff.as<uint64_t>(), p->rank_mode, a.ev, c->wkey.as<uint32_t>(),
-                         c->kcol.as<uint2>(), c->blk_minmax.as<uint32_t>(), &c->ctl.as<ControlBlock>()->sel, want, klb, E, cap, c->tn,
-                         c->stream, !c->pass.sharded_ab, ord_on ? &a.ord : nullptr, a.chunk_shift, host_count);
+// The key pass over the event list, into the key arrays as they stand (writes beyond what they hold are dropped); want / window:
+// what the select's first round is told (window: the a-priori one); host_count: the pinned word that receives the triangle count,
+// as the scan's would.
+static void key_pass(sc_ctx* c, const sc_params* p, const SelectArgs& a, uint64_t want, bool window, uint64_t* host_count) {
+  KeyPassOpts o;
+  o.window = window; o.check_bound = !c->pass.sharded_ab; o.chunk_shift = a.chunk_shift; o.host_total = host_count;
+  launch_tri_keys_events(a.g, a.pr, a.el, a.cnt, p->rank_mode, a.ev, a.ord, keys_of(c), want, o, c->tn, c->stream);
 }
 
 // The second wait.  Host-free call: none — M is what the key arrays and the launches cover, T_eff the requested T; the kernels
 // read the real count from toff[E] (= the scan's total: the counts of [real E, E) are zero) and sc_wait validates.  Sets
 // c->pass.M and M_total.
-static int read_triangle_count(sc_ctx* c, uint64_t E, SelectArgs& a) {
+static int read_triangle_count(sc_ctx* c, SelectArgs& a) {
   StageBForm& f = c->pass.form;
   if (!f.spec) SC_TRY(wait_word(c, HW_TRIANGLES));
   if (f.ord_on && !f.spec && (uint32_t)c->pinned[HW_EV_OVERFLOW] != 0) {
     // an event region was full, or the list has more chunks than the key kernel holds: the row-walking key kernel needs toff —
     // the scan runs after all, here and only here, over counts whose weak entries nobody has written yet
-    launch_zero_weak_counts(c->es.as<float>(), a.smin, E, nullptr, c->tcnt.as<uint32_t>(), c->stream);
-    SC_TRY(scan_counts(c, E, a));
+    launch_zero_weak_counts(a.el, a.pr, a.cnt, c->stream);
+    SC_TRY(scan_counts(c, a));
     SC_TRY(wait_word(c, HW_TRIANGLES));
     f.ord_state = 2;
     if (chunk_overflow(c)) c->ord_off = true;
@@ -504,7 +508,7 @@ static int grow_key_arrays(sc_ctx* c, uint64_t M, uint32_t T_eff, bool want_list
   ENSURE_ROOM(c, c->kcol, M * 8, M_room * 8);
   *moved = key_arrays.moved();
   ENSURE(c, c->blk_minmax, 2 * 8192 * 4);
-  SC_TRY(ensure_compaction(c, compact_blocks(M), compact_blocks(spec ? M : key_capacity(c)), T_eff));
+  SC_TRY(ensure_compaction(c, compact_blocks(M), compact_blocks(spec ? M : keys_of(c).cap), T_eff));
   if (want_list) ENSURE(c, c->tri, (size_t)T_eff * 12);
   return SC_OK;
 }
@@ -516,16 +520,14 @@ static int grow_key_arrays(sc_ctx* c, uint64_t M, uint32_t T_eff, bool want_list
 int run_compaction(sc_ctx* c, const KeyView& view, size_t nb, int rounds, uint64_t* host_short) {
   hipStream_t st = c->stream;
   SelectState* sel = &c->ctl.as<ControlBlock>()->sel;
-  launch_compact_count(view, sel, rounds, c->blk_gt.as<uint32_t>(), c->blk_eq.as<uint32_t>(), st, host_short);
+  launch_compact_count(view, sel, rounds, c->blk_gt.as<uint32_t>(), c->blk_eq.as<uint32_t>(), host_short, st);
   // few tiles (and M < 2^32): compact_write adds up the tile counts itself, no scan launch in between
   const bool self_off = nb <= c->tn.compact_self_max && view.M < (1ull << 32);
   if (!self_off)
     launch_scan_u32_pair(c->blk_gt.as<uint32_t>(), c->off_gt.as<uint64_t>(), c->blk_eq.as<uint32_t>(),
                          c->off_eq.as<uint64_t>(), nb, c->scan_tmp.p, c->tn, st);
   launch_compact_write(view, sel, c->blk_gt.as<uint32_t>(), c->blk_eq.as<uint32_t>(),
-                       self_off ? nullptr : c->off_gt.as<uint64_t>(), self_off ? nullptr : c->off_eq.as<uint64_t>(),
-                       c->sel_ord.as<uint64_t>(), c->sel_key.as<uint32_t>(),
-                       c->sel_ord.cap / 8 < c->sel_key.cap / 4 ? c->sel_ord.cap / 8 : c->sel_key.cap / 4, st);
+                       self_off ? nullptr : c->off_gt.as<uint64_t>(), self_off ? nullptr : c->off_eq.as<uint64_t>(), selection_of(c), st);
   return SC_OK;
 }
 
@@ -541,18 +543,15 @@ static void grow_event_capacity(sc_ctx* c, uint64_t M) {
 
 // Every key into wkey / kcol, now that the count is known and the arrays hold it: nothing where the speculative pass wrote them
 // all, the key pass again, or — after an event overflow — the row-walking kernel.  SC_FLAG_TIMING brackets it (events 9, 10).
-static int write_keys(sc_ctx* c, const sc_params* p, uint64_t E, uint64_t M, const SelectArgs& a) {
+static int write_keys(sc_ctx* c, const sc_params* p, const SelectArgs& a) {
   const StageBForm& f = c->pass.form;
-  ControlBlock* ctl = c->ctl.as<ControlBlock>();
   if (c->pass.timing) HIPCHK(c, hipEventRecord(c->ev[9], c->stream));
   if (f.keys_done) {
     // nothing to do
   } else if (f.events_ok) {  // (ord_on: no overflow here, the lists of the counting pass stand)
-    key_pass(c, p, E, a, f.fast_window ? (uint64_t)select_want(c, p) : (uint64_t)c->pass.T_eff, f.fast_window ? &ctl->klb : nullptr, M, nullptr);
+    key_pass(c, p, a, f.fast_window ? (uint64_t)select_want(c, p) : (uint64_t)c->pass.T_eff, f.fast_window, nullptr);
   } else {
-    launch_tri_keys(a.g, a.mbits, a.smin, c->ebase.as<uint32_t>(), c->ei.as<uint32_t>(), c->ej.as<uint32_t>(),
-                    c->es.as<float>(), c->toff.as<uint64_t>(), E, p->rank_mode, c->wkey.as<uint32_t>(),
-                    c->kcol.as<uint2>(), c->blk_minmax.as<uint32_t>(), &ctl->sel, c->pass.T_eff, own_range_of(c), c->tn, c->stream);
+    launch_tri_keys(a.g, a.pr, a.el, a.cnt, p->rank_mode, keys_of(c), c->pass.T_eff, c->tn, c->stream);
   }
   if (c->pass.timing) HIPCHK(c, hipEventRecord(c->ev[10], c->stream));
   c->pass.timed_trikeys = c->pass.timing;
@@ -560,13 +559,14 @@ static int write_keys(sc_ctx* c, const sc_params* p, uint64_t E, uint64_t M, con
 }
 
 // The exact threshold key, then the keys at or above it in ordinal order -> sel_ord / sel_key
-static int select_and_compact(sc_ctx* c, uint64_t E, uint64_t M) {
+static int select_and_compact(sc_ctx* c, uint64_t M, const SelectArgs& a) {
   const StageBForm& f = c->pass.form;
-  KeyView view = plain_view(c->wkey.as<uint32_t>(), M);
-  if (f.spec) view.M_dev = c->toff.as<uint64_t>() + E;
+  const KeyArrays ka = keys_of(c);
+  KeyView view = plain_view(ka.wkey, M);
+  if (f.spec) view.M_dev = a.cnt.toff + a.el.E;
   // an estimated bound is verified by the first round over the a-priori window; any other path leaves it unverified
   if (f.est_active && !f.fast_window) c->pass.est_void = true;
-  launch_select_rounds(view, &c->ctl.as<ControlBlock>()->sel, select_rounds(f.fast_window), c->tn, c->stream, select_short_word(c));
+  launch_select_rounds(view, ka.sel, select_rounds(f.fast_window), select_short_word(c), c->tn, c->stream);
   return run_compaction(c, view, compact_blocks(M), select_rounds(f.fast_window), select_short_word(c));
 }
 
@@ -581,21 +581,23 @@ int run_select(sc_ctx* c, const sc_params* p, const uint32_t* hist, bool want_li
   SC_TRY(form_select(c, p, hist));
   const StageBForm& f = c->pass.form;
   SelectArgs a;
-  a.g = graph_of(c);
-  SC_TRY(prune(c, p, hist, E, a));
-  SC_TRY(count_triangles(c, p, E, a));
+  a.g = graph_of(c); a.el = edges_of(c); a.cnt = counts_of(c);  // (run_edges grew them: they stay where they are — `held` below)
+  Caps held;
+  held.add(c->ei); held.add(c->ej); held.add(c->es); held.add(c->tcnt); held.add(c->toff);
+  SC_TRY(prune(c, p, hist, a));
+  SC_TRY(count_triangles(c, p, a));
   counts_range(c, a);
   // (ordered strong list: the count comes from the key kernel, which makes the ordinals without a scan)
   if (f.ord_on) arm_word(c, HW_TRIANGLES);
-  else SC_TRY(scan_counts(c, E, a));
+  else SC_TRY(scan_counts(c, a));
   // While the host polls for the count, the key kernel already runs into the key arrays this context holds from earlier
   // calls (it takes everything else from device memory); re-run below if the count outgrew the arrays or a region overflowed.
   while ((256 >> a.chunk_shift) > tri_count_events_lanes(a.g, c->tn)) a.chunk_shift++;
   if (f.spec_cap) {
     ENSURE(c, c->blk_minmax, 2 * 8192 * 4);
-    key_pass(c, p, E, a, select_want(c, p), &c->ctl.as<ControlBlock>()->klb, f.spec_cap, (f.ord_on && !f.spec) ? &c->pinned[HW_TRIANGLES] : nullptr);
+    key_pass(c, p, a, select_want(c, p), true, (f.ord_on && !f.spec) ? &c->pinned[HW_TRIANGLES] : nullptr);
   }
-  SC_TRY(read_triangle_count(c, E, a));
+  SC_TRY(read_triangle_count(c, a));
   const uint64_t M = c->pass.M;
   if (M == 0) {
     // no triangle in the pruned graph: under a CERTIFIED bound (or none) the graph has none; an ESTIMATED bound has verified nothing
@@ -610,12 +612,11 @@ int run_select(sc_ctx* c, const sc_params* p, const uint32_t* hist, bool want_li
   SC_TRY(grow_key_arrays(c, M, T_eff, want_list, &key_arrays_moved));
   form_keys(c, p, M, key_arrays_moved);
   if (f.use_events && !f.events_ok) grow_event_capacity(c, M);
-  SC_TRY(write_keys(c, p, E, M, a));
-  SC_TRY(select_and_compact(c, E, M));
+  if (held.moved()) { c->last_error = "internal: an edge array was re-allocated under run_select's views"; return SC_EHIP; }
+  SC_TRY(write_keys(c, p, a));
+  SC_TRY(select_and_compact(c, M, a));
   // the list stays in ordinal order: no sort on the hot path (the winner is found by (count, key, position))
-  if (want_list)
-    launch_tri_decode(c->ei.as<uint32_t>(), c->ej.as<uint32_t>(), c->kcol.as<uint2>(), c->sel_ord.as<uint64_t>(), T_eff,
-                      c->tri.as<uint32_t>(), c->stream);
+  if (want_list) launch_tri_decode(a.el, keys_of(c), selection_of(c), T_eff, c->tri.as<uint32_t>(), c->stream);
   c->pass.regular = hostfree_form_met(c, M, want_sel);
   return SC_OK;
 }
@@ -649,7 +650,7 @@ static bool hostfree_shape_ok(const sc_ctx* c, int64_t n, const sc_params* p) {
 bool fast_plan(const sc_ctx* c, int64_t n, const sc_params* p, PassMode* mode) {
   if (!c->fast_ok || !hostfree_shape_ok(c, n, p)) return false;
   const uint64_t ecap = edge_capacity(c, edge_build_ok(c, p, n, true));  // (every entry point that comes here may estimate; the fused edge kernel writes no per-edge bases)
-  const uint64_t kcap = key_capacity(c);
+  const uint64_t kcap = keys_of(c).cap;
   const ShapeHistory& h = c->shape;
   uint64_t ecov = h.cover(h.E_last, h.E_hi), mcov = h.cover(h.M_last, h.M_hi);
   if (ecov > ecap) ecov = ecap;

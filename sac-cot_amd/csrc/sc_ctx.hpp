@@ -28,7 +28,7 @@ static_assert(HW_MERGED_M == HW_MERGED_T + 1 && HW_WINNER_POS == HW_WINNER + 1, 
 // How a pass is enqueued: decided by the entry point BEFORE the pass starts and handed to hyp_begin, which stores it in the fresh pass.
 struct PassMode {
   // the entry point can repeat the call (sc_register*), or its caller does (sc_hypothesize_device with SC_FLAG_EST_BOUND): stage B
-  // may prune by an ESTIMATED bound (sc_tri.hip 3c); the select verifies it, finalize_wait reads the verdict (frame_end)
+  // may prune by an ESTIMATED bound (sc_tri_prune.hip 3c); the select verifies it, finalize_wait reads the verdict (frame_end)
   bool may_estimate = false;
   // host-free enqueue (include/saccot.h): a call of the last one's shape does not wait for stage B's two counts; its launches cover E_cov
   // edges / M_cov keys (fast_plan) and read the real counts from device memory; finalize_wait validates, and the call is repeated the waiting
@@ -51,7 +51,7 @@ struct StageBForm {
   bool est_local = false;   // the bound may be an estimate: the call can be repeated and the whole sample is taken here
   bool est_shard = false;   // ... sharded, SC_FLAG_EST_BOUND: every rank takes the whole sample, the merge verifies
   // ---- form_counted, behind the edge count
-  bool pruned = false;      // certified pruning (sc_tri.hip 3b)
+  bool pruned = false;      // certified pruning (sc_tri_prune.hip 3b)
   bool use_events = false;  // counting pass + event list (sc_tri.hip 2b)
   bool have_total = false;  // SC_FLAG_EXACT_TOTAL: the 3-cliques of the whole graph are counted as well (HW_TOTAL)
   bool est_active = false;  // stage B prunes by an estimate (Pass::plan.estimate)
@@ -548,6 +548,11 @@ int run_triangles(sc_ctx* c, const sc_params* p, bool want_list);
 #define SC_LOCAL __attribute__((visibility("hidden")))
 SC_LOCAL int run_edges(sc_ctx* c, const sc_params* p, uint32_t* hist, uint32_t part, uint32_t parts);
 SC_LOCAL int run_select(sc_ctx* c, const sc_params* p, const uint32_t* hist, bool want_list);
+// the views of the context's stage-B arrays (sc_kernels.hpp): the one place each Buf becomes a typed pointer
+SC_LOCAL EdgeList edges_of(const sc_ctx* c);
+SC_LOCAL EdgeCounts counts_of(const sc_ctx* c);
+SC_LOCAL KeyArrays keys_of(const sc_ctx* c);
+SC_LOCAL Selection selection_of(const sc_ctx* c);
 SC_LOCAL int ensure_compaction(sc_ctx* c, size_t nb, size_t nb_room, uint32_t T_eff);
 SC_LOCAL int run_compaction(sc_ctx* c, const KeyView& view, size_t nb, int rounds, uint64_t* host_short);
 inline int select_rounds(bool window) { return window ? 2 : 3; }  // the a-priori window spares the round that measures the key range

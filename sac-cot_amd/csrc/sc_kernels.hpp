@@ -42,7 +42,7 @@ struct Tuning {
   uint32_t sample_mode = 0;        // pruning sample: 0 by size (launch_sample_hist), 1 every stride-th edge, 2 the heaviest edges (both CERTIFY their bound)
   bool no_edge_build = false;      // row statistics and edge list as separate launches (not launch_edge_build)
   bool compat_linear_order = false;  // stage A's 64 x 64 blocks in index order (r03) instead of the XCD-aware order
-  bool no_estimate = false;        // never prune by an ESTIMATED bound (sc_tri.hip 3c): always one of the certifying samples
+  bool no_estimate = false;        // never prune by an ESTIMATED bound (sc_tri_prune.hip 3c): always one of the certifying samples
   uint32_t est_margin_pct = 0;     // the estimate aims at the (pct / 100 x T)-th key (0: 200; tests force failures with a small one)
   uint32_t sample_blocks = 0;      // grid of the heaviest-edge sample (0: one block per 256 edges)
   bool rows_unfused = false;       // row_stats and the scan(s) of the row counts as separate launches (round 1's form)
@@ -181,28 +181,43 @@ struct Graph {
   const uint32_t* wpre;  // n x W word-prefix popcounts of `bits`
   int n, ld, W;
 };
+// The context's stage-B arrays as the launches see them — EdgeList, EdgeCounts, Pruned, KeyArrays, Selection: plain views, each
+// filled by one accessor of the host driver (sc_capi_tri.hip: edges_of, counts_of, pruned_of, keys_of, selection_of).  A launcher
+// takes the views it reads or writes, then what is per launch, then the stream.
+//
 // CSR edge list of the upper triangle, rows ascending, columns ascending: ei/ej/es (es = S[i][j]).
 // ebase[i] (u32, modular): CSR index of edge (i,k), k > i, is ebase[i] + wpre[i][k/64] + popc(bits[i][k/64] below k).
-// ebi[e] / ebj[e]: the bases of both ends of edge e (so an edge is fetched in one memory level).
+// ebi[e] / ebj[e]: the bases of both ends of edge e (so an edge is fetched in one memory level).  ebi == ebj == nullptr: the
+// fused edge kernel (launch_edge_build) made the list and wrote no per-edge bases — whoever wants them looks them up in ebase.
+// E: the edge count — or, in a host-free call (launched before the host knows it, sc_capi_tri.hip), what the grids and the arrays
+// COVER: the true count is then *E_dev (device; nullptr on a waited call) and the kernels work on min(E, *E_dev) edges.
+// E_hint: the count that host-side choices which only cost time go by (the sample's form and stride, the counting pass's grid): E,
+// or a host-free call's last known count.  cap: entries the arrays hold (the kernels that fill them drop writes beyond it).
+struct EdgeList {
+  uint32_t* ei; uint32_t* ej; float* es;
+  uint32_t* ebi; uint32_t* ebj; uint32_t* ebase;
+  uint64_t E; const uint64_t* E_dev; uint64_t E_hint;
+  uint64_t cap;
+};
+// Per-edge triangle counts and what their scan makes of them: toff[e] = triangles of the edges before e, toff[E] = all of them.
+// own (optional, device; sharded stage B): [lo, hi) of the edges this rank enumerates — the others count 0.
+struct EdgeCounts {
+  uint32_t* tcnt; uint64_t* toff; const uint64_t* own;
+  // toff as its 2 E + 2 u32 words: where an OrdList's tloc and ctot live (no scan writes toff then; the count still lands in toff[E])
+  uint32_t* words() const { return reinterpret_cast<uint32_t*>(toff); }
+};
 // ebase_ready: the per-row CSR bases were written by the scan of deg+ (ScanExtra, tiled form) and are READ here;
 // otherwise they are derived on the fly and this kernel writes them.  scan_writes_ebase(n) tells which.
 bool scan_writes_ebase(size_t n);
-void launch_edge_fill(const Graph& g, const Points& pts, const Derived& dv, const uint64_t* edge_off, uint32_t* ei,
-                      uint32_t* ej, float* es, uint32_t* ebase, bool ebase_ready, uint32_t* ebi, uint32_t* ebj,
-                      uint64_t cap, uint32_t* es_hist, hipStream_t st);  // es_hist: see launch_sample_hist (optional)
+void launch_edge_fill(const Graph& g, const Points& pts, const Derived& dv, const uint64_t* edge_off, const EdgeList& el,
+                      bool ebase_ready, uint32_t* es_hist, hipStream_t st);  // es_hist: see launch_sample_hist (optional)
 // The hot path's form (r04; n <= 20 480, weight ranking, estimated pruning bound): row statistics (wpre), CSR offsets and
 // bases from g.degp — which launch_compat accumulated —, the strong-bit rows cleared and the edge list (ei / ej / es; NO ebi /
-// ebj: launch_tri_count_events looks the bases up), in one launch.  host_total (pinned) receives the edge count, which also
-// lands in edge_off[n].
+// ebj: launch_tri_count_events looks the bases up), in one launch.  The edge count lands in edge_off[n] and, where given, in
+// host_total (pinned) and as [0, edge count) in live_range (device, 2 x u64).
 bool edge_build_fits(int n);
-void launch_edge_build(const Graph& g, const Points& pts, const Derived& dv, uint64_t* zero_rows, uint64_t* edge_off, uint32_t* ebase,
-                       uint32_t* ei, uint32_t* ej, float* es, uint64_t cap, uint64_t* host_total, hipStream_t st,
-                       uint64_t* live_range = nullptr);  // live_range (optional, device, 2 x u64): receives [0, edge count)
-// tcnt[e] = #k > j adjacent (in `mbits`) to both ends of edge e = (i,j); edges with es[e] < *smin count 0
-// (smin == nullptr: no pruning, mbits = g.bits).
-void launch_tri_count(const Graph& g, const uint64_t* mbits, const float* es, const float* smin, const uint32_t* ei,
-                      const uint32_t* ej, uint64_t E, uint32_t* tcnt, const uint64_t* own, const Tuning& tn,
-                      hipStream_t st);  // own (optional, device): [lo, hi) of the edges this rank enumerates
+void launch_edge_build(const Graph& g, const Points& pts, const Derived& dv, uint64_t* zero_rows, uint64_t* edge_off, const EdgeList& el,
+                       uint64_t* host_total, uint64_t* live_range, hipStream_t st);
 // Compact list of the strong edges (those of the pruned graph), written by the pruning kernel in ST_SHARDS regions of
 // `cap` entries (fill[r] = entries of region r; ST_SHARDS zeroed counters of the control block).  list == nullptr: off.
 constexpr int ST_SHARDS = 256;
@@ -221,23 +236,29 @@ struct StrongList {
 };
 uint32_t strong_list_cap(uint64_t E);
 size_t strong_list_bytes(uint64_t E);
+// What the pruning leaves (launch_prune_bits): the strong upper-triangle bit matrix mbits (n x W), the strong-edge threshold *smin
+// (device float; -1 = nothing certified), *klb (key of the bound or 0) and the strong list.  All null (Pruned{}): no pruning —
+// membership is the graph's own bit rows (member_bits) and every edge counts.
+struct Pruned {
+  uint64_t* mbits;
+  float* smin;
+  uint32_t* klb;
+  StrongList sl;
+};
+inline const uint64_t* member_bits(const Graph& g, const Pruned& pr) { return pr.mbits ? pr.mbits : g.bits; }
+// tcnt[e] = #k > j adjacent (in member_bits) to both ends of edge e = (i,j); edges with es[e] < *smin count 0
+void launch_tri_count(const Graph& g, const Pruned& pr, const EdgeList& el, const EdgeCounts& ec, const Tuning& tn, hipStream_t st);
 
 // Certified pruning (weight ranking), two launches:
 //  launch_sample_hist: the triangles of every R-th edge go into `hist` (256 u32, zeroed by the caller); `part` of
 //    `parts`: this launch takes every parts-th SAMPLED edge starting at `part` (one process per GPU: the histograms of
 //    all parts are summed before launch_prune_bits sees them).  key_floor: a value at or below the smallest possible
 //    triangle weight.
-//  launch_prune_bits: derives the strong-edge threshold *smin (device float; -1 = nothing certified) and *klb (key of
-//    the bound or 0) from the histogram, builds the strong upper-triangle bit matrix `mbits` (n x W, already zero), and
+//  launch_prune_bits: derives *smin and *klb from the histogram, builds the strong bit matrix (already zero), and
 //    with sl.list set also compacts the strong edges and zeroes tcnt of the weak ones.
-// E_dev (optional, device): the true edge count when the host launches before it knows it (host-free path, sc_capi.hip):
-// the kernels then work on min(E, *E_dev) edges — E is what the grids and arrays cover; E_hint (0: E): the edge count the
-// host-side choices (sample form, stride) are made with.
-void launch_sample_hist(const Graph& g, const uint32_t* ebi, const uint32_t* ebj, const uint32_t* ei,
-                        const uint32_t* ej, const float* es, uint64_t E, uint64_t want, float key_floor, uint32_t part,
-                        uint32_t parts, uint32_t* hist, uint32_t* es_hist, const Tuning& tn, hipStream_t st,
-                        const uint64_t* E_dev = nullptr, uint64_t E_hint = 0);
-// The ESTIMATING sample (r04, sc_tri.hip 3c): one sampled 64-column word in `rate` of every edge's row pair, its triangles'
+void launch_sample_hist(const Graph& g, const EdgeList& el, uint64_t want, float key_floor, uint32_t part, uint32_t parts,
+                        uint32_t* hist, uint32_t* es_hist, const Tuning& tn, hipStream_t st);
+// The ESTIMATING sample (r04, sc_tri_prune.hip 3c): one sampled 64-column word in `rate` of every edge's row pair, its triangles'
 // keys into `hist` — a uniform 1-in-rate sample of ALL the graph's triangles.  launch_prune_bits then takes the bin where
 // rate x (count from the top) reaches margin x T as the bound: an estimate, not a certificate — the select verifies it
 // (SelectState::want_req) and the caller repeats the call with a certifying sample when it was too high.
@@ -246,11 +267,13 @@ struct SamplePlan {
   uint32_t rate;       // power of two
   uint64_t hist_want;  // what launch_prune_bits looks for in the histogram
 };
-SamplePlan sample_plan(uint64_t want, bool allow_estimate, const Tuning& tn, uint64_t E = 0, int W = 0);  // E, W: the graph (0: not known: rate <= 64)
-void launch_sample_estimate(const Graph& g, const uint32_t* ebi, const uint32_t* ebj, const uint32_t* ei, const uint32_t* ej,
-                            const float* es, uint64_t E, float key_floor, uint32_t rate, uint32_t* hist, const Tuning& tn,
-                            hipStream_t st, const uint64_t* E_dev = nullptr, const uint32_t* ebase = nullptr,  // ebase: with ebi == ebj == nullptr
-                            uint4* cand = nullptr, unsigned long long* cand_slot = nullptr);  // cand (optional, sample_estimate_blocks() entries): the best-keyed triangle each workgroup sampled {key bits, i, j, k} — the voters of stage C2's reference frame (sc_gramref.hpp)
+SamplePlan sample_plan(uint64_t want, bool allow_estimate, const Tuning& tn, uint64_t E, int W);  // E, W: the graph (0: not known: rate <= 64)
+struct SampleCands {  // (off: none kept)
+  uint4* cand = nullptr;  // sample_estimate_blocks() entries: the best-keyed triangle each workgroup sampled {key bits, i, j, k} — the voters of stage C2's reference frame (sc_gramref.hpp)
+  unsigned long long* slot = nullptr;  // ControlBlock::ref_slot
+};
+void launch_sample_estimate(const Graph& g, const EdgeList& el, uint32_t rate, uint32_t* hist, const SampleCands& cands, const Tuning& tn,
+                            hipStream_t st);
 uint32_t sample_estimate_blocks(uint64_t E, const Tuning& tn);  // workgroups launch_sample_estimate uses
 uint32_t sample_candidate_blocks(uint64_t E, const Tuning& tn);  // ... of which the first so many leave a candidate behind
 // es_hist: PR_HCOPIES x 256 words (control block): the weight histogram of the heaviest-edge sample, filled by launch_edge_fill
@@ -258,15 +281,16 @@ uint32_t sample_candidate_blocks(uint64_t E, const Tuning& tn);  // ... of which
 // launch_hist_reduce sums them into one 256-bin histogram (the exchanged form); launch_prune_bits reads either
 // (hist_is_copies).
 void launch_hist_reduce(const uint32_t* copies, uint32_t* out, hipStream_t st);
-void launch_prune_bits(const Graph& g, const uint32_t* hist, bool hist_is_copies, const uint32_t* ei, const uint32_t* ej, const float* es,
-                       uint64_t E, uint64_t want, float key_floor, uint64_t* mbits, float* smin, uint32_t* klb,
-                       const StrongList& sl, uint32_t* tcnt, const uint64_t* own, hipStream_t st,
-                       const uint64_t* E_dev = nullptr,   // E_dev: as above; with sl.list the tcnt entries of [*E_dev, E) are zeroed too
-                       bool logbins = false,              // hist comes from launch_sample_estimate (logarithmic bins of 3.0 - key)
-                       bool trimmed = false);             // (with E_dev) the scan that follows skips the counts beyond *E_dev: the workgroups there leave at once
+struct PruneOpts {
+  bool logbins = false;  // hist comes from launch_sample_estimate (logarithmic bins of 3.0 - key)
+  bool trimmed = false;  // (with el.E_dev) the scan that follows skips the counts beyond *E_dev: the workgroups there leave at once
+};
+// (with el.E_dev and sl.list the tcnt entries of [*E_dev, E) are zeroed too; ec.own: only this rank's strong edges are listed)
+void launch_prune_bits(const Graph& g, const uint32_t* hist, bool hist_is_copies, const EdgeList& el, uint64_t want, float key_floor,
+                       const Pruned& pr, const EdgeCounts& ec, const PruneOpts& o, hipStream_t st);
 // sharded stage B, after the certificate: work estimate per row of the PRUNED graph (strong_rowcost_kernel), and — in one
 // single-block launch — its prefix and this rank's row / edge range (the rule of launch_shard_split)
-void launch_strong_rowcost(const Graph& g, const uint64_t* mbits, uint32_t* rowcost, hipStream_t st);
+void launch_strong_rowcost(const Graph& g, const Pruned& pr, uint32_t* rowcost, hipStream_t st);
 void launch_cost_split(const uint32_t* rowcost, const uint64_t* edge_off, int n, uint32_t rank, uint32_t world,
                        uint32_t* own_row, uint64_t* own_edge, hipStream_t st);
 
@@ -306,18 +330,15 @@ struct OrdList {
 struct GramRefJob;
 size_t event_bytes(uint64_t capacity);
 EventList event_list(void* buf, uint64_t capacity, int W, uint32_t* fill, uint32_t* overflow_host);
-// counting pass that also emits the events (replaces launch_tri_count when an event buffer is available)
-void launch_tri_count_events(const Graph& g, const uint64_t* mbits, const StrongList& sl, const uint32_t* ebi,
-                             const uint32_t* ebj, const uint32_t* ei, const uint32_t* ej, uint64_t E, int rank_mode,
-                             uint32_t* tcnt, const EventList& ev, const Tuning& tn, hipStream_t st,
-                             const uint64_t* own = nullptr,   // own (optional, device): [lo, hi) of the edges this rank enumerates
-                             const uint32_t* ebase = nullptr,  // with ebi == ebj == nullptr: the per-row CSR bases (launch_edge_build)
-                             const GramRefJob* ref = nullptr,  // one extra workgroup votes for stage C2's reference frame (sc_gramref.hpp)
-                             const OrdList* ord = nullptr);    // the strong list is ordered (sl.cnt): also leave what the key kernel makes the ordinals from
+// counting pass that also emits the events (replaces launch_tri_count when an event buffer is available).  The grid goes by el.E_hint.
+// ord (cnt != nullptr): the strong list is ordered (pr.sl.cnt) — also leave what the key kernel makes the ordinals from.
+// ref (optional): one extra workgroup votes for stage C2's reference frame (sc_gramref.hpp)
+void launch_tri_count_events(const Graph& g, const Pruned& pr, const EdgeList& el, const EdgeCounts& ec, int rank_mode, const EventList& ev,
+                             const OrdList& ord, const GramRefJob* ref, const Tuning& tn, hipStream_t st);
 // lanes per edge launch_tri_count_events uses (a chunk of an OrdList is 256 / this many positions)
 int tri_count_events_lanes(const Graph& g, const Tuning& tn);
 // tcnt[e] = 0 for the edges below *smin: what the pruning kernel leaves out in the ordered form, for the scan of an overflow's fall-back
-void launch_zero_weak_counts(const float* es, const float* smin, uint64_t E, const uint64_t* E_dev, uint32_t* tcnt, hipStream_t st);
+void launch_zero_weak_counts(const EdgeList& el, const Pruned& pr, const EdgeCounts& ec, hipStream_t st);
 
 // Radix-select state.  Lives in the context's control block, which the staging kernel zeroes per call.
 // r05: no workgroup of a select round stays behind to "pick": a round only adds its keys into hist[r], and the NEXT launch —
@@ -338,7 +359,7 @@ struct SelectState {
   uint64_t want;           //   keys kept
   uint64_t need_eq;        //   how many keys == kstar among them
   uint64_t want_req;       // != 0: the window's floor is a bound that must have this many keys at or above it (whoever resolves a
-                           // round reports a shortfall: an ESTIMATED pruning bound that was too high, sc_tri.hip 3c)
+                           // round reports a shortfall: an ESTIMATED pruning bound that was too high, sc_tri_prune.hip 3c)
   uint64_t pad;
   SelSnap st[4];           // st[r]: the state BEFORE round r (st[0]: key_range_kernel / the key kernel's preset / merge_prepare_kernel)
   uint32_t hist[3][4096];  // hist[r]: round r's bins; all zero between selects (compact_write_kernel clears them behind the select)
@@ -373,22 +394,26 @@ struct ControlBlock {
 };
 static_assert(offsetof(ControlBlock, sel) % 16 == 0, "ControlBlock::sel must be 16-byte aligned");
 
-// key of every triangle, in ordinal (lexicographic i,j,k) order: wkey[toff[e] + r].
-// blk_minmax: 2 * 8192 u32 scratch (per-block key min / max, reduced into s->kmin / s->kmax; s->want = want).
-void launch_tri_keys(const Graph& g, const uint64_t* mbits, const float* smin, const uint32_t* ebase,
-                     const uint32_t* ei, const uint32_t* ej, const float* es, const uint64_t* toff, uint64_t E,
-                     int rank_mode, uint32_t* wkey, uint2* kcol, uint32_t* blk_minmax, SelectState* s,
-                     uint64_t want, const uint64_t* own, const Tuning& tn, hipStream_t st);  // kcol[ordinal] = {the triangle's third vertex, its edge id}
-// keys from the event list (replaces launch_tri_keys when no region overflowed)
-void launch_tri_keys_events(const Graph& g, const float* es, const uint64_t* toff, int rank_mode,
-                            const EventList& ev, uint32_t* wkey, uint2* kcol, uint32_t* blk_minmax,
-                            SelectState* s, uint64_t want, const uint32_t* klb, uint64_t E, uint64_t cap,
-                            const Tuning& tn, hipStream_t st, bool check_bound = false,  // cap: entries of wkey / kcol (writes beyond are dropped); want is clipped to toff[E]
-                            const OrdList* ord = nullptr, int chunk_shift = 0,  // ordinals from the ordered strong list (toff unused); chunk = 1 << chunk_shift positions
-                            uint64_t* host_total = nullptr);  // (with ord) pinned word that receives the triangle count, as the scan's would
-// check_bound: with a pruning bound in *klb the select must find `want` keys at or above it (SelectState::want_req)
-// klb != nullptr (weight ranking, every edge weight >= 2/3): the kernel presets the select window to
-// [*klb or 2.0, 3.0] and no key-range pass runs; two select rounds then always suffice.
+// key of every triangle, in ordinal (lexicographic i,j,k) order: wkey[toff[e] + r]; kcol[ordinal] = {the triangle's third vertex, its
+// edge id}.  cap: entries wkey / kcol hold.  blk_minmax: 2 * 8192 u32 scratch (per-block key min / max, reduced into sel->kmin /
+// sel->kmax; sel->want = want).  sel: the select state of the control block.
+struct KeyArrays { uint32_t* wkey; uint2* kcol; uint64_t cap; uint32_t* blk_minmax; SelectState* sel; };
+// the selection: sel_ord[g] = ordinal of the g-th selected triangle, (i,j,k) ascending, sel_key[g] its key; n: entries both hold
+struct Selection { uint64_t* sel_ord; uint32_t* sel_key; uint64_t n; };
+void launch_tri_keys(const Graph& g, const Pruned& pr, const EdgeList& el, const EdgeCounts& ec, int rank_mode, const KeyArrays& ka,
+                     uint64_t want, const Tuning& tn, hipStream_t st);
+// keys from the event list (replaces launch_tri_keys when no region overflowed): ka.cap keys at most (writes beyond are dropped);
+// want is clipped to toff[E].  ord (cnt != nullptr): ordinals from the ordered strong list (toff unused)
+struct KeyPassOpts {
+  // (weight ranking, every edge weight >= 2/3) the kernel presets the select window to [*pr.klb or 2.0, 3.0] and no key-range pass
+  // runs; two select rounds then always suffice
+  bool window = false;  // (needs pr.klb: with Pruned{} there is no bound to read and the key range is measured as without it)
+  bool check_bound = false;  // with a pruning bound in *pr.klb the select must find `want` keys at or above it (SelectState::want_req)
+  int chunk_shift = 0;       // (with ord) chunk = 1 << chunk_shift positions
+  uint64_t* host_total = nullptr;  // (with ord) pinned word that receives the triangle count, as the scan's would
+};
+void launch_tri_keys_events(const Graph& g, const Pruned& pr, const EdgeList& el, const EdgeCounts& ec, int rank_mode, const EventList& ev,
+                            const OrdList& ord, const KeyArrays& ka, uint64_t want, const KeyPassOpts& o, const Tuning& tn, hipStream_t st);
 // A key array as the select / compaction kernels see it.  Plain (seg_len == 0): M keys at base.  Segmented (the
 // all-gathered candidate blobs of sharded stage B): M = segments x seg_len logical entries, seg_len a multiple of 1024;
 // segment s holds valid[s * valid_stride] real keys at base + s * seg_stride, the rest of it reads as 0.
@@ -408,16 +433,14 @@ KeyView plain_view(const uint32_t* wkey, uint64_t M);
 // see SelectState) find the exact threshold key
 // host_short (optional, pinned u64): set to 1 when SelectState::want_req keys were promised above the window's floor and
 // fewer are there
-void launch_select_rounds(const KeyView& view, SelectState* s, int rounds, const Tuning& tn, hipStream_t st,
-                          uint64_t* host_short = nullptr);
+void launch_select_rounds(const KeyView& view, SelectState* s, int rounds, uint64_t* host_short, const Tuning& tn, hipStream_t st);
 // compaction of the selected keys in ordinal order
 size_t compact_blocks(uint64_t M);
 // rounds: what launch_select_rounds was given (the counting kernel resolves the last round's histogram; host_short as there)
-void launch_compact_count(const KeyView& view, SelectState* s, int rounds, uint32_t* blk_gt, uint32_t* blk_eq,
-                          hipStream_t st, uint64_t* host_short = nullptr);
-void launch_compact_write(const KeyView& view, SelectState* s, const uint32_t* blk_gt,
-                          const uint32_t* blk_eq, const uint64_t* off_gt, const uint64_t* off_eq,
-                          uint64_t* sel_ord, uint32_t* sel_key, uint64_t n_sel, hipStream_t st);  // n_sel: entries sel_ord / sel_key hold
+void launch_compact_count(const KeyView& view, SelectState* s, int rounds, uint32_t* blk_gt, uint32_t* blk_eq, uint64_t* host_short,
+                          hipStream_t st);
+void launch_compact_write(const KeyView& view, SelectState* s, const uint32_t* blk_gt, const uint32_t* blk_eq, const uint64_t* off_gt,
+                          const uint64_t* off_eq, const Selection& out, hipStream_t st);
 
 // ---- sharded stage B: the candidate blob a rank sends, and the merge of the gathered blobs ----
 constexpr int CAND_HDR_WORDS = 32;  // u64 words: [0] triangles enumerated, [1] entries sent, [2] local threshold key,
@@ -436,14 +459,13 @@ struct CandBlob {
 size_t cand_cap(uint32_t T, uint32_t world, int level);
 size_t cand_blob_bytes(size_t cap);  // bytes per rank
 CandBlob cand_blob(void* blob, size_t cap);
-// this rank's selection (sel_ord / sel_key, n_max an upper bound of its length) -> blob
-void launch_cand_emit(const uint64_t* sel_ord, const uint32_t* sel_key, const uint2* kcol, const uint32_t* ei,
-                      const uint32_t* ej, const SelectState* sel, const uint64_t* toff, uint64_t E, uint32_t n_max,
+// this rank's selection (n_max an upper bound of its length) -> blob
+void launch_cand_emit(const Selection& sl, const KeyArrays& ka, const EdgeList& el, const EdgeCounts& ec, uint32_t n_max,
                       uint64_t want_requested, const CandBlob& b, hipStream_t st);
 // sums the gathered headers, arms `sel` for the merge select; host_out[0] <- T_eff (polled), host_out[1] <- triangles
+// host_short (pinned, optional): set when *klb is an ESTIMATED bound and fewer than T candidates came
 void launch_merge_prepare(const void* blobs, size_t blob_bytes, uint32_t world, uint32_t T, bool fast, const uint32_t* klb,
-                          SelectState* sel, uint64_t* host_out, hipStream_t st,
-                          uint64_t* host_short = nullptr);  // host_short (pinned): set when *klb is an ESTIMATED bound and fewer than T candidates came
+                          SelectState* sel, uint64_t* host_out, uint64_t* host_short, hipStream_t st);
 KeyView cand_view(const void* blobs, size_t blob_bytes, uint32_t world, size_t cap);
 // After the merge select: a rank whose list was cut sent everything above its local threshold key k_r; the merged
 // selection is exact iff the merged threshold k* lies strictly above k_r for every such rank (everything it did not send
@@ -454,10 +476,9 @@ void launch_merge_check(const void* blobs, size_t blob_bytes, uint32_t world, co
 size_t sort_temp_bytes(size_t n);
 void launch_sort_u64(const uint64_t* in, uint64_t* out, size_t n, void* temp, size_t temp_bytes, hipStream_t st);
 // selected position -> (i,j,k); the list stays in ordinal ((i,j,k) ascending) order
-void launch_tri_decode(const uint32_t* ei, const uint32_t* ej, const uint2* kcol, const uint64_t* sel_ord, uint32_t T,
-                       uint32_t* tri, hipStream_t st);
+void launch_tri_decode(const EdgeList& el, const KeyArrays& ka, const Selection& sl, uint32_t T, uint32_t* tri, hipStream_t st);
 // ranked order (key desc, ordinal asc) of the ordinal-ordered list: only the stage hook needs it
-void launch_rank_order(const uint32_t* tri, const uint32_t* sel_key, uint32_t T, uint64_t* sortkey, uint64_t* sorted,
+void launch_rank_order(const uint32_t* tri, const Selection& sl, uint32_t T, uint64_t* sortkey, uint64_t* sorted,
                        void* sort_tmp, size_t sort_bytes, uint32_t* tri_ranked, uint32_t* key_ranked, hipStream_t st);
 
 // ---- stage C ---------------------------------------------------------------------------------------

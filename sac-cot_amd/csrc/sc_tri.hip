@@ -1,208 +1,9 @@
-// sc_tri.hip — stage B: triangles_topT on the GPU.
-//
-// Total order of the output: key descending, then (i,j,k) lexicographic ascending.  The trick that makes the
-// tie-break free: triangles are enumerated edge by edge in CSR order (i asc, j asc) and, inside an edge, in
-// ascending k, so a triangle's position in that enumeration — its *ordinal* — orders like (i,j,k).  So:
-//   1. edge_fill       CSR list of upper-triangle edges (ei, ej, es = s_ij) from the bit rows
-//   2. tri_count       per edge: popcount(row_i & row_j & bits above j)          -> scan -> ordinals
-//   3. tri_keys        per triangle: key at wkey[ordinal]  (s_ik / s_jk come from the compact edge-weight
-//                      array through prefix popcounts, not from the 4N^2-byte dense matrix)
-//   4. select rounds   exact radix select of the T-th largest key over wkey (<= 3 histogram rounds)
-//   5. compact         keys > k*, plus the first (T - #greater) keys == k* by ordinal, in ordinal order
-//   6. sort (rocPRIM)  by (~key, position)    7. tri_decode  ordinal -> (i,j,k)
-// Everything is integer / bit work except the two fp32 adds of the key; results do not depend on grid size
-// or on the order atomics land in (atomics are only used for commutative integer sums, min and max).
-#include <cstring>
-#include <type_traits>
-
-#include "sc_arith.hpp"
-#include "sc_block.hpp"
-#include "sc_kernels.hpp"
+// sc_tri.hip — stage B, the enumeration: per-edge triangle counts and per-triangle keys, by rows or by the event list; then
+// selection and hand-over: radix select, compaction, the sharded candidate exchange, decode, ranked order (sc_tri.hpp: the pipeline).
+#include "sc_tri.hpp"
 #include "sc_gramref.hpp"
 
 namespace sc {
-
-// Pop up to four set bits of m (lowest first).  nb = how many were popped; b[] are their positions (0 for unused
-// slots, so derived indices stay in range).  Lets a lane issue the gathers of four triangles before it consumes the
-// first: a lane's triangles would otherwise cost one dependent L2 round trip each.
-__device__ __forceinline__ int pop4(uint64_t& m, int b[4]) {
-  int nb = 0;
-#pragma unroll
-  for (int q = 0; q < 4; q++) {
-    const bool has = m != 0;
-    b[q] = has ? __builtin_ctzll(m) : 0;
-    m = has ? (m & (m - 1)) : 0;
-    nb += has ? 1 : 0;
-  }
-  return nb;
-}
-
-// One end of an edge at one 64-column word: the CSR index of the word's first edge (row base + wpre) and the full-graph
-// word; edge (v, k) of that row then sits at first + popc(word & below k).
-struct CsrWord { uint32_t first; uint64_t word; };
-
-// The weights s_ik, s_jk of one pop4 batch.  All eight gathers are issued before the first use; idle slots read es[0]
-// (their modular index may be out of range).
-__device__ __forceinline__ void tri_weights4(const float* __restrict__ es, const int (&b)[4], int nbits, CsrWord ri,
-                                             CsrWord rj, float (&s_ik)[4], float (&s_jk)[4]) {
-#pragma unroll
-  for (int q = 0; q < 4; q++) {
-    const uint64_t below = (1ull << b[q]) - 1ull;
-    const bool live = q < nbits;
-    s_ik[q] = es[live ? ri.first + (uint32_t)__popcll(ri.word & below) : 0u];
-    s_jk[q] = es[live ? rj.first + (uint32_t)__popcll(rj.word & below) : 0u];
-  }
-}
-
-// The extremes of a 256-thread block's keys -> one plain store per block (no same-address atomics: they serialise at
-// ~12 ns each).  Every thread calls it.
-__device__ __forceinline__ void block_minmax_store(uint32_t kmin, uint32_t kmax, uint32_t* __restrict__ blk_min,
-                                                   uint32_t* __restrict__ blk_max) {
-  __shared__ uint32_t lmin[4], lmax[4];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    kmin = min(kmin, (uint32_t)__shfl_xor(kmin, o));
-    kmax = max(kmax, (uint32_t)__shfl_xor(kmax, o));
-  }
-  if ((threadIdx.x & 63) == 0) { lmin[threadIdx.x >> 6] = kmin; lmax[threadIdx.x >> 6] = kmax; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    blk_min[blockIdx.x] = min(min(lmin[0], lmin[1]), min(lmin[2], lmin[3]));
-    blk_max[blockIdx.x] = max(max(lmax[0], lmax[1]), max(lmax[2], lmax[3]));
-  }
-}
-
-// A row's upper-triangle edges, as edge_fill_kernel and edge_build_kernel emit them.  RowSide: what every edge of row i
-// needs of the row itself — its correspondence (wave-uniform: scalar loads), the AoS copy behind the planes that the
-// other end is gathered from (8 floats per correspondence: two 16-byte loads) and the pair test's constants.
-// EdgeOut: the CSR arrays and the entries they hold (writes beyond cap are dropped).
-struct RowSide {
-  int i;
-  float px, py, pz, qx, qy, qz;
-  const float4* __restrict__ aos4;
-  Derived dv;
-};
-struct EdgeOut { uint32_t* __restrict__ ei; uint32_t* __restrict__ ej; float* __restrict__ es; uint64_t cap; };
-
-__device__ __forceinline__ RowSide row_side(const float* __restrict__ planes, int ld, int i, const Derived& dv) {
-  return RowSide{i, planes[i], planes[ld + i], planes[2 * ld + i], planes[3 * ld + i], planes[4 * ld + i], planes[5 * ld + i],
-                 reinterpret_cast<const float4*>(planes + 6 * (size_t)ld), dv};
-}
-
-// One wave, one round of 64 words of the row: lane holds word w with only the bits above the diagonal left in v; the edges go
-// to base, base + 1, ... in column order.  CH column indices are staged per chunk in l_j (this wave's); extra(e, j, weight)
-// runs after the three stores of each edge.  Returns the number of edges of the round.
-template <int CH, typename Extra>
-__device__ __forceinline__ uint32_t row_edges_emit(uint32_t* l_j, uint64_t v, int w, uint64_t base, const RowSide& row,
-                                                   const EdgeOut& out, Extra extra) {
-  const int lane = threadIdx.x & 63;
-  uint32_t tot;
-  const uint32_t r = group_exscan<64>((uint32_t)__popcll(v), &tot);
-  for (uint32_t c0 = 0; c0 < tot; c0 += CH) {  // wave-uniform; one chunk unless the row is very dense
-    // (1) divergent part, LDS only: the columns of this chunk in ascending order
-    uint64_t vv = v;
-    uint32_t rr = r - c0;  // modular: positions outside [0, CH) are skipped
-    while (vv) {
-      const int b = __builtin_ctzll(vv);
-      vv &= vv - 1;
-      if (rr < (uint32_t)CH) l_j[rr] = (uint32_t)(w * 64 + b);
-      rr++;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // LDS is in-order within a wave
-    // (2) flat part, one lane per edge: gathers, weight, coalesced stores
-    const uint32_t cnt = min((uint32_t)CH, tot - c0);
-    for (uint32_t t = lane; t < cnt; t += 64) {
-      const uint32_t j = l_j[t];
-      const uint64_t e = base + c0 + t;
-      if (e >= out.cap) continue;
-      const float4 a4 = row.aos4[2 * (size_t)j], b4 = row.aos4[2 * (size_t)j + 1];
-      const float dp = dist3(row.px, row.py, row.pz, a4.x, a4.y, a4.z);
-      const float dq = dist3(row.qx, row.qy, row.qz, a4.w, b4.x, b4.y);
-      bool edge;
-      const float sw = pair_weight(dp, dq, row.dv.d_thr, row.dv.min_len, row.dv.neg_inv2sig2, edge);
-      out.ei[e] = (uint32_t)row.i;
-      out.ej[e] = j;
-      out.es[e] = sw;
-      extra(e, j, sw);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // l_j is rewritten by the next chunk
-  }
-  return tot;
-}
-
-// ------------------------------------------------------------------------------------------------
-// 1. edge_fill: one wave per row
-// ------------------------------------------------------------------------------------------------
-// The edge weight is RECOMPUTED from the two correspondences with stage A's own chain (pair_weight over dist3: the
-// same correctly rounded operations on the same operands give the same bits; the squares make the argument order
-// irrelevant) instead of being gathered from S: a gather moves a 64-byte sector of the n x n matrix for 4 useful
-// bytes (C3: 215 us), the recomputation is ~80 VALU operations on points that sit in L2.
-__device__ __forceinline__ uint32_t weight_bin(uint32_t wbits, uint32_t wlo, uint32_t wshift);  // §3b
-
-__global__ __launch_bounds__(256) void edge_fill_kernel(const uint64_t* __restrict__ bits,
-                                                        const float* __restrict__ planes, Derived dv,
-                                                        int n, int ld, int W,
-                                                        const uint64_t* __restrict__ edge_off,
-                                                        uint32_t* __restrict__ ei, uint32_t* __restrict__ ej,
-                                                        float* __restrict__ es,
-                                                        const uint32_t* __restrict__ deg,
-                                                        const uint32_t* __restrict__ degp,
-                                                        uint32_t* __restrict__ ebase, int ebase_ready,
-                                                        uint32_t* __restrict__ ebi,
-                                                        uint32_t* __restrict__ ebj, uint64_t cap,
-                                                        uint32_t* __restrict__ es_hist) {
-  // cap: entries the edge arrays hold.  The host may launch this kernel BEFORE it knows the edge count (into the
-  // arrays of the previous call, while it polls for the count); writes beyond cap are dropped and the host re-runs.
-  // es_hist (optional): the 256-bin histogram of the edge weights that sizes the heaviest-edge pruning sample (§3b;
-  // PR_HCOPIES global copies) — collected here, where the weights are made, instead of by a launch of its own (7 us).
-  constexpr int CH = 512;  // column indices staged per wave and chunk
-  __shared__ uint32_t l_j[4][CH];
-  __shared__ uint32_t l_h[2][256];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int i = blockIdx.x * 4 + wave;
-  if (es_hist) {
-    l_h[0][threadIdx.x] = 0u; l_h[1][threadIdx.x] = 0u;
-    __syncthreads();
-  }
-  if (i < n) {
-  uint64_t base = edge_off[i];
-  // CSR base of row i: edge_off[i] - (# bits of row i at or below i) = edge_off[i] - (deg - deg+), modular u32.
-  // ebase_ready: the (tiled) scan of deg+ wrote every row's base already, so the base of the OTHER end is one gather;
-  // otherwise (small n: a one-block scan, where the extra loads cost more than they save here) it is derived on the fly
-  // from three and this wave records its own row's.
-  const uint32_t my_base = ebase_ready ? ebase[i] : (uint32_t)base - (deg[i] - degp[i]);
-  if (!ebase_ready && lane == 0) ebase[i] = my_base;
-  const int w0 = i >> 6;
-  const RowSide row = row_side(planes, ld, i, dv);
-  const EdgeOut out{ei, ej, es, cap};
-  for (int wb = w0; wb < W; wb += 64) {
-    const int w = wb + lane;
-    uint64_t v = 0;
-    if (w < W) {
-      v = bits[(size_t)i * W + w];
-      if (w == w0) v &= mask_above(i & 63);
-    }
-    base += row_edges_emit<CH>(l_j[wave], v, w, base, row, out, [&](uint64_t e, uint32_t j, float sw) {
-      if (es_hist) atomicAdd(&l_h[lane & 1][weight_bin(__float_as_uint(sw), 0u, 0u)], 1u);  // integer sums: order-free
-      // both CSR bases travel with the edge, so stage B fetches an edge in ONE memory level
-      ebi[e] = my_base;
-      ebj[e] = ebase_ready ? ebase[j] : (uint32_t)edge_off[j] - (deg[j] - degp[j]);
-    });
-  }
-  }  // i < n
-  if (es_hist) {
-    __syncthreads();
-    const uint32_t v = l_h[0][threadIdx.x] + l_h[1][threadIdx.x];
-    if (v) atomicAdd(&es_hist[(size_t)(blockIdx.x & (PR_HCOPIES - 1)) * 256 + threadIdx.x], v);
-  }
-}
-
-void launch_edge_fill(const Graph& g, const Points& pts, const Derived& dv, const uint64_t* edge_off, uint32_t* ei,
-                      uint32_t* ej, float* es, uint32_t* ebase, bool ebase_ready, uint32_t* ebi, uint32_t* ebj,
-                      uint64_t cap, uint32_t* es_hist, hipStream_t st) {
-  hipLaunchKernelGGL(edge_fill_kernel, dim3((g.n + 3) / 4), dim3(256), 0, st, g.bits, pts.planes, dv, g.n, g.ld, g.W,
-                     edge_off, ei, ej, es, g.deg, g.degp, ebase, ebase_ready ? 1 : 0, ebi, ebj, cap, es_hist);
-}
 
 // ------------------------------------------------------------------------------------------------
 // 2. tri_count: 16 lanes per edge
@@ -276,17 +77,16 @@ __global__ __launch_bounds__(256) void tri_count_kernel(const uint64_t* __restri
   }
 }
 
-void launch_tri_count(const Graph& g, const uint64_t* mbits, const float* es, const float* smin, const uint32_t* ei,
-                      const uint32_t* ej, uint64_t E, uint32_t* tcnt, const uint64_t* own, const Tuning& tn,
-                      hipStream_t st) {
-  if (E == 0) return;
+void launch_tri_count(const Graph& g, const Pruned& pr, const EdgeList& el, const EdgeCounts& ec, const Tuning& tn, hipStream_t st) {
+  if (el.E == 0) return;
   const int tg = tn.tg_count;
   const uint64_t per = (uint64_t)(256 / tg) * EB;
-  uint64_t nb = (E + per - 1) / per;
+  uint64_t nb = (el.E + per - 1) / per;
   if (nb > 4096) nb = 4096;
-#define SC_LAUNCH_COUNT(TGV) hipLaunchKernelGGL(tri_count_kernel<TGV>, dim3((unsigned)nb), dim3(256), 0, st, mbits, g.W, ei, ej, es, smin, E, tcnt, own)
-  if (tg == 4) SC_LAUNCH_COUNT(4); else if (tg == 8) SC_LAUNCH_COUNT(8); else if (tg == 32) SC_LAUNCH_COUNT(32); else SC_LAUNCH_COUNT(16);
-#undef SC_LAUNCH_COUNT
+  with_lanes<16, 4, 8, 32>(tg, [&](auto lanes) {  // (no 64-lane form)
+    hipLaunchKernelGGL(tri_count_kernel<decltype(lanes)::value>, dim3((unsigned)nb), dim3(256), 0, st, member_bits(g, pr), g.W,
+                       el.ei, el.ej, el.es, pr.smin, el.E, ec.tcnt, ec.own);
+  });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -405,17 +205,17 @@ size_t tri_keys_blocks(uint64_t E, int tg) {
   return (size_t)(nb < (uint64_t)TK_MAX_BLOCKS ? nb : (uint64_t)TK_MAX_BLOCKS);
 }
 
-void launch_tri_keys(const Graph& g, const uint64_t* mbits, const float* smin, const uint32_t* ebase,
-                     const uint32_t* ei, const uint32_t* ej, const float* es, const uint64_t* toff, uint64_t E,
-                     int rank_mode, uint32_t* wkey, uint2* kcol, uint32_t* blk_minmax, SelectState* s,
-                     uint64_t want, const uint64_t* own, const Tuning& tn, hipStream_t st) {
-  if (E == 0) return;
+void launch_tri_keys(const Graph& g, const Pruned& pr, const EdgeList& el, const EdgeCounts& ec, int rank_mode, const KeyArrays& ka,
+                     uint64_t want, const Tuning& tn, hipStream_t st) {
+  if (el.E == 0) return;
   const int tg = tn.tg_keys;
-  const int nb = (int)tri_keys_blocks(E, tg);
-#define SC_LAUNCH_KEYS(TGV) hipLaunchKernelGGL(tri_keys_kernel<TGV>, dim3(nb), dim3(256), 0, st, g.bits, mbits, smin, g.W, g.deg, g.wpre, ebase, ei, ej, es, toff, E, rank_mode, wkey, kcol, blk_minmax, blk_minmax + TK_MAX_BLOCKS, own)
-  if (tg == 4) SC_LAUNCH_KEYS(4); else if (tg == 8) SC_LAUNCH_KEYS(8); else if (tg == 32) SC_LAUNCH_KEYS(32); else if (tg == 64) SC_LAUNCH_KEYS(64); else SC_LAUNCH_KEYS(16);
-#undef SC_LAUNCH_KEYS
-  hipLaunchKernelGGL(key_range_kernel, dim3(1), dim3(1024), 0, st, blk_minmax, blk_minmax + TK_MAX_BLOCKS, nb, s, want);
+  const int nb = (int)tri_keys_blocks(el.E, tg);
+  with_lanes<16, 4, 8, 32, 64>(tg, [&](auto lanes) {
+    hipLaunchKernelGGL(tri_keys_kernel<decltype(lanes)::value>, dim3(nb), dim3(256), 0, st, g.bits, member_bits(g, pr), pr.smin, g.W, g.deg,
+                       g.wpre, el.ebase, el.ei, el.ej, el.es, ec.toff, el.E, rank_mode, ka.wkey, ka.kcol, ka.blk_minmax,
+                       ka.blk_minmax + TK_MAX_BLOCKS, ec.own);
+  });
+  hipLaunchKernelGGL(key_range_kernel, dim3(1), dim3(1024), 0, st, ka.blk_minmax, ka.blk_minmax + TK_MAX_BLOCKS, nb, ka.sel, want);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -704,7 +504,7 @@ __global__ __launch_bounds__(256) void tri_keys_events_kernel(const uint64_t* __
   }
   // Weight keys of a graph whose edges all weigh >= 2/3 live in one binade, [2.0, 3.0]: the select window is known
   // before a single key exists — [certified bound (or 2.0), 3.0] — so no key-range pass, and two 12-bit rounds
-  // always resolve it.  (Keys below a certified bound cannot be among the `want` largest: sc_tri.hip 3b.)
+  // always resolve it.  (Keys below a certified bound cannot be among the `want` largest: sc_tri_prune.hip 3b.)
   if (preset && blockIdx.x == 0 && threadIdx.x == 0) {
     const uint32_t lo = *klb ? *klb : 0x40000000u, hi = 0x40400000u;  // 2.0f, 3.0f
     const uint32_t range_m1 = hi - lo;
@@ -804,10 +604,9 @@ EventList event_list(void* buf, uint64_t capacity, int W, uint32_t* fill, uint32
   return ev;
 }
 
-void launch_tri_count_events(const Graph& g, const uint64_t* mbits, const StrongList& sl, const uint32_t* ebi,
-                             const uint32_t* ebj, const uint32_t* ei, const uint32_t* ej, uint64_t E, int rank_mode,
-                             uint32_t* tcnt, const EventList& ev, const Tuning& tn, hipStream_t st, const uint64_t* own,
-                             const uint32_t* ebase, const GramRefJob* ref, const OrdList* ord) {
+void launch_tri_count_events(const Graph& g, const Pruned& pr, const EdgeList& el, const EdgeCounts& ec, int rank_mode, const EventList& ev,
+                             const OrdList& ord, const GramRefJob* ref, const Tuning& tn, hipStream_t st) {
+  const uint64_t E = el.E_hint;  // (only the grid goes by it)
   if (E == 0) return;
   // lanes per edge: a lane walks (W - j / 64) / TG words one dependent round after the other, so wide rows want wide
   // groups (Tuning::tg_events forces one; measured r02: see DESIGN.md)
@@ -823,14 +622,13 @@ void launch_tri_count_events(const Graph& g, const uint64_t* mbits, const Strong
   if (tn.cnt_blocks >= 1 && tn.cnt_blocks <= 65535) nb = tn.cnt_blocks;
   const GramRefJob rj = ref ? *ref : GramRefJob{};
   if (rj.out) nb++;  // (workgroup 0 is the rider)
-  const OrdList ol = ord ? *ord : OrdList{};
-#define SC_LAUNCH_CE(TGV, ORDV) hipLaunchKernelGGL((tri_count_events_kernel<TGV, ORDV>), dim3((unsigned)nb), dim3(256), 0, st, mbits, g.W, g.deg, ebi, ebj, ei, ej, sl, rank_mode, tcnt, ev, own, ebase, rj, ol)
-  if (ol.cnt) {
-    if (tg == 4) SC_LAUNCH_CE(4, true); else if (tg == 16) SC_LAUNCH_CE(16, true); else if (tg == 32) SC_LAUNCH_CE(32, true); else if (tg == 64) SC_LAUNCH_CE(64, true); else SC_LAUNCH_CE(8, true);
-  } else {
-    if (tg == 4) SC_LAUNCH_CE(4, false); else if (tg == 16) SC_LAUNCH_CE(16, false); else if (tg == 32) SC_LAUNCH_CE(32, false); else if (tg == 64) SC_LAUNCH_CE(64, false); else SC_LAUNCH_CE(8, false);
-  }
-#undef SC_LAUNCH_CE
+  auto launch = [&](auto lanes, auto ordered) {
+    hipLaunchKernelGGL((tri_count_events_kernel<decltype(lanes)::value, decltype(ordered)::value>), dim3((unsigned)nb), dim3(256), 0, st,
+                       member_bits(g, pr), g.W, g.deg, el.ebi, el.ebj, el.ei, el.ej, pr.sl, rank_mode, ec.tcnt, ev, ec.own, el.ebase, rj, ord);
+  };
+  with_lanes<8, 4, 16, 32, 64>(tg, [&](auto lanes) {
+    if (ord.cnt) launch(lanes, std::true_type{}); else launch(lanes, std::false_type{});
+  });
 }
 
 int tri_count_events_lanes(const Graph& g, const Tuning& tn) {
@@ -846,854 +644,28 @@ __global__ __launch_bounds__(256) void zero_weak_counts_kernel(const float* __re
   const uint64_t Ea = E_dev ? (*E_dev > E ? 0ull : *E_dev) : E;
   if (e >= Ea || !(es[e] >= *smin)) tcnt[e] = 0u;
 }
-void launch_zero_weak_counts(const float* es, const float* smin, uint64_t E, const uint64_t* E_dev, uint32_t* tcnt, hipStream_t st) {
-  if (E == 0) return;
-  hipLaunchKernelGGL(zero_weak_counts_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, st, es, smin, E, E_dev, tcnt);
+void launch_zero_weak_counts(const EdgeList& el, const Pruned& pr, const EdgeCounts& ec, hipStream_t st) {
+  if (el.E == 0) return;
+  hipLaunchKernelGGL(zero_weak_counts_kernel, dim3((unsigned)((el.E + 255) / 256)), dim3(256), 0, st, el.es, pr.smin, el.E, el.E_dev, ec.tcnt);
 }
 
-void launch_tri_keys_events(const Graph& g, const float* es, const uint64_t* toff, int rank_mode,
-                            const EventList& ev, uint32_t* wkey, uint2* kcol, uint32_t* blk_minmax,
-                            SelectState* s, uint64_t want, const uint32_t* klb, uint64_t E, uint64_t cap,
-                            const Tuning& tn, hipStream_t st, bool check_bound, const OrdList* ord, int chunk_shift,
-                            uint64_t* host_total) {
+void launch_tri_keys_events(const Graph& g, const Pruned& pr, const EdgeList& el, const EdgeCounts& ec, int rank_mode, const EventList& ev,
+                            const OrdList& ord, const KeyArrays& ka, uint64_t want, const KeyPassOpts& o, const Tuning& tn, hipStream_t st) {
   // (ordered strong list: every workgroup pays for the prefix over the chunk totals, and four fit a CU beside it — one round of them)
-  int nb = ord && ord->cnt ? 1024 : 2048;
+  int nb = ord.cnt ? 1024 : 2048;
   if (tn.keys_blocks >= 1 && tn.keys_blocks <= (uint32_t)TK_MAX_BLOCKS) nb = (int)tn.keys_blocks;
-  if (ord && ord->cnt)
-    hipLaunchKernelGGL(tri_keys_events_kernel<true>, dim3(nb), dim3(256), 0, st, g.bits, g.wpre, g.deg, es, toff, rank_mode,
-                       ev, wkey, kcol, blk_minmax, blk_minmax + TK_MAX_BLOCKS, klb ? s : (SelectState*)nullptr, klb, want, E, cap,
-                       check_bound ? 1 : 0, *ord, chunk_shift, host_total);
+  const uint32_t* klb = o.window ? pr.klb : nullptr;  // (no bound to read — Pruned{} — : no preset, the key range is measured)
+  SelectState* preset = klb ? ka.sel : nullptr;
+  if (ord.cnt)
+    hipLaunchKernelGGL(tri_keys_events_kernel<true>, dim3(nb), dim3(256), 0, st, g.bits, g.wpre, g.deg, el.es, ec.toff, rank_mode,
+                       ev, ka.wkey, ka.kcol, ka.blk_minmax, ka.blk_minmax + TK_MAX_BLOCKS, preset, klb, want, el.E, ka.cap,
+                       o.check_bound ? 1 : 0, ord, o.chunk_shift, o.host_total);
   else
-    hipLaunchKernelGGL(tri_keys_events_kernel<false>, dim3(nb), dim3(256), 0, st, g.bits, g.wpre, g.deg, es, toff, rank_mode,
-                       ev, wkey, kcol, blk_minmax, blk_minmax + TK_MAX_BLOCKS, klb ? s : (SelectState*)nullptr, klb, want, E, cap,
-                       check_bound ? 1 : 0, OrdList{}, 0, (uint64_t*)nullptr);
+    hipLaunchKernelGGL(tri_keys_events_kernel<false>, dim3(nb), dim3(256), 0, st, g.bits, g.wpre, g.deg, el.es, ec.toff, rank_mode,
+                       ev, ka.wkey, ka.kcol, ka.blk_minmax, ka.blk_minmax + TK_MAX_BLOCKS, preset, klb, want, el.E, ka.cap,
+                       o.check_bound ? 1 : 0, OrdList{}, 0, (uint64_t*)nullptr);
   if (!klb)  // no a-priori window: the key range comes from the per-block extremes
-    hipLaunchKernelGGL(key_range_kernel, dim3(1), dim3(1024), 0, st, blk_minmax, blk_minmax + TK_MAX_BLOCKS, nb, s, want);
-}
-
-// ------------------------------------------------------------------------------------------------
-// 3b. certified pruning (weight ranking only)
-//
-// Claim: let LB be any value such that at least T triangles have key >= LB.  Then the top-T list of the full graph
-// equals the top-T list of the subgraph of "strong" edges, s >= smin := LB - 2 - 1e-6.
-// Proof: w = fl(fl(a+b)+c) with a,b,c in (0,1] satisfies w <= a+b+c + 5*2^-24, so a triangle with w >= LB has every
-// edge >= LB - 2 - 3e-7 > smin: all triangles with key >= LB live in the strong subgraph, there are >= T of them, and
-// every triangle outside it has key < LB, i.e. strictly below at least T others — it cannot enter the top-T, ties
-// included.  Ordinals keep their relative order (same CSR edge order, same ascending k), so the tie-break is unchanged.
-// LB comes from a SAMPLE: the triangles of every R-th edge are enumerated once, their keys go into a 256-bin
-// histogram over [klo, khi]; walking it from the top to the first bin where the count reaches T gives a bin whose
-// lower edge is a valid LB (>= T genuine triangles lie at or above it).  Bin 0 collects everything below klo, so a
-// crossing in bin 0 certifies nothing and disables the pruning (smin = -1).
-// ------------------------------------------------------------------------------------------------
-constexpr int PR_BINS = 256;   // coarse is enough: LB only needs to be a valid, reasonably tight lower bound
-constexpr int PR_COPIES = 16;  // one private copy per lane-in-group: same-bin hits land on different LDS words
-constexpr int EST_COPIES = 4;  // the estimating sample (one lane per edge, ~200 hits per workgroup): fewer copies to clear and to add up
-
-// Flush of a workgroup's LDS histogram, COPIES rotated copies laid out [bin][copy], into one of PR_HCOPIES global copies
-// (by block): a thousand blocks adding into the SAME 256 words serialise at the memory side (~12 ns per add and address);
-// the copies are summed by the reader.  Every thread of a 256-thread block calls it; it starts with the barrier that
-// ends the counting.
-template <int COPIES>
-__device__ __forceinline__ void hist_flush(const uint32_t* lh, uint32_t* __restrict__ hist) {
-  __syncthreads();
-  uint32_t* __restrict__ myh = hist + (size_t)(blockIdx.x & (PR_HCOPIES - 1)) * PR_BINS;
-  for (int b = threadIdx.x; b < PR_BINS; b += 256) {
-    uint32_t v = 0;
-#pragma unroll
-    for (int c = 0; c < COPIES; c++) v += lh[b * COPIES + ((c + threadIdx.x) & (COPIES - 1))];
-    if (v) atomicAdd(&myh[b], v);
-  }
-}
-
-__device__ __forceinline__ uint32_t prune_bin(uint32_t key, uint32_t klo, uint32_t shift) {
-  if (key <= klo) return 0u;
-  const uint32_t b = (key - klo) >> shift;
-  return b < (uint32_t)PR_BINS ? b : (uint32_t)(PR_BINS - 1);
-}
-
-// The ESTIMATING sample (3c) bins by d = 3.0 - key instead — exact in fp32 for keys in [2, 3] — LOGARITHMICALLY, 16 bins per
-// octave of d over [2^-17, 2^-1): the top-T keys crowd against 3.0 (three weights near 1), where linear bins of 0.002
-// cannot tell the key of rank T from the key of rank 5 T; a bin 4.4 % wide in d is ~13 % wide in rank.  Bin 0: d >= 0.5
-// (nothing can be said), bin 255: d < 2^-17 (1 + 1/16).  Selected by shift == PR_LOGBINS.
-constexpr uint32_t PR_LOGBINS = 0xFFFFFFFFu;
-__device__ __forceinline__ uint32_t est_bin(uint32_t key) {
-  const float d = 3.0f - __uint_as_float(key);
-  if (!(d > 0.0f)) return (uint32_t)(PR_BINS - 1);
-  const uint32_t u = __float_as_uint(d) >> 19;  // exponent and four mantissa bits
-  return u >= 2016u ? 0u : (u <= 1761u ? (uint32_t)(PR_BINS - 1) : 2016u - u);
-}
-// a value every key of bin b (>= 1) lies strictly ABOVE: 3.0 - (upper edge of the bin's d interval), exact in fp32
-__device__ __forceinline__ float est_bin_floor(uint32_t b) { return 3.0f - __uint_as_float((2017u - b) << 19); }
-
-// Which edges are sampled.  Any subset of genuine triangles certifies a bound; the question is which subset certifies
-// a TIGHT one for the fewest key evaluations.
-//   TOP = false: every stride-th edge (round 1).  The T-th largest sampled key is then about the (stride x T)-th key
-//     of the graph: with ~32 k sampled edges on C2 the certified subgraph still holds 1.47 M triangles for T = 50 k.
-//   TOP = true: the `target` HEAVIEST edges (weight at or above the lower edge of the bin of a 256-bin weight histogram
-//     where the count from the top reaches target; es_hist_kernel).  A top triangle has three heavy edges, so its first
-//     edge is far more likely to be in this set than in a uniform sample of the same size.  A block takes a contiguous
-//     chunk of the edge list, compacts the qualifying edges into LDS (coalesced read of es, ballot prefix) and deals
-//     them to its groups.
-constexpr int SM_CHUNK = 256;  // edges per block and chunk in the TOP form (small: a chunk inside an inlier row is all heavy edges)
-
-// Weight -> bin, heavier = higher, LOGARITHMIC in 1 - s: the weights of good edges crowd against 1.0 (s = exp(-d^2 / 2
-// sigma^2) with d << sigma), so linear bins would put tens of thousands of edges into the top one and the sample could
-// not be sized.  1 - s is exact in fp32 for s >= 0.5; its exponent and top three mantissa bits give 8 bins per octave:
-// 1 - s in [2^-24, 2^-3) -> bins 255 .. 80, s == 1 -> 255, lighter edges -> the low bins.  (wlo / wshift: unused.)
-__device__ __forceinline__ uint32_t weight_bin(uint32_t wbits, uint32_t wlo, uint32_t wshift) {
-  (void)wlo; (void)wshift;
-  const uint32_t lb = __float_as_uint(1.0f - __uint_as_float(wbits)) >> 20;  // sign 0, exponent, 3 mantissa bits
-  const int b = (int)(103u << 3) + 255 - (int)lb;                              // 2^-24 has exponent field 103
-  return (uint32_t)(b < 0 ? 0 : (b > 255 ? 255 : b));
-}
-
-template <int TG, bool TOP>
-__global__ __launch_bounds__(256) void tri_sample_hist_kernel(const uint64_t* __restrict__ bits, int W,
-                                                              const uint32_t* __restrict__ wpre,
-                                                              const uint32_t* __restrict__ ebi,
-                                                              const uint32_t* __restrict__ ebj,
-                                                              const uint32_t* __restrict__ ei,
-                                                              const uint32_t* __restrict__ ej,
-                                                              const float* __restrict__ es, uint64_t E,
-                                                              uint32_t stride, uint32_t part, uint32_t parts,
-                                                              uint32_t klo, uint32_t shift,
-                                                              uint32_t* __restrict__ hist,
-                                                              const uint32_t* __restrict__ es_hist, uint64_t target,
-                                                              uint32_t wlo, uint32_t wshift,
-                                                              const uint64_t* __restrict__ E_dev) {
-  // Launched before the host knew the count (E: what the arrays hold).  More edges than that: the CSR indices this kernel
-  // derives from the bit rows would point beyond the edge arrays — nothing may run (the host repeats the call: sc_capi.hip).
-  if (E_dev && *E_dev > E) return;
-  if (E_dev) E = *E_dev;
-  __shared__ uint32_t lh[PR_BINS * PR_COPIES];  // [bin][copy]
-  __shared__ uint32_t l_e[TOP ? SM_CHUNK : 1];  // TOP: the qualifying edges of the current chunk
-  __shared__ uint32_t s_theta, s_cnt, s_wtot[4];
-  __shared__ uint64_t plds[8];
-  for (int b = threadIdx.x; b < PR_BINS * PR_COPIES; b += 256) lh[b] = 0;
-  if (TOP) {  // the weight bin at which the count from the top reaches `target` (no such bin: every edge qualifies)
-    static_assert(PR_BINS == 256, "one bin per thread, walked from the top");
-    const uint32_t bin = PR_BINS - 1 - threadIdx.x;
-    uint64_t mine = 0;
-    for (int c = 0; c < PR_HCOPIES; c++) mine += es_hist[c * PR_BINS + bin];
-    if (threadIdx.x == 0) s_theta = 0u;
-    uint64_t tot;
-    const uint64_t before = block_exscan_u64(mine, plds, &tot);  // (its barriers also order the s_theta default)
-    if (before < target && target <= before + mine) s_theta = bin;
-  }
-  __syncthreads();
-  const int gl = threadIdx.x & (TG - 1);
-  const uint64_t n_s = (E + stride - 1) / stride;  // sampled edges: e = g * stride, g = 0 .. n_s - 1
-  // this launch takes the sampled edges g = part, part + parts, ... (one process per GPU: every rank samples its share
-  // and the histograms are summed by an all-reduce — distinct edges give distinct triangles, so the sum certifies)
-  const uint64_t n_loc = n_s > part ? (n_s - part + parts - 1) / parts : 0;
-  const uint64_t groups = TOP ? (256 / TG) : (uint64_t)gridDim.x * (256 / TG);
-  const uint32_t theta = TOP ? s_theta : 0u;
-  // a chunk is SM_CHUNK x parts consecutive edges, of which this rank considers every parts-th: the same number of
-  // candidates per block whatever the number of ranks sharing the sample (per-block fixed costs stay amortised)
-  const uint64_t chunk_edges = (uint64_t)SM_CHUNK * parts;
-  const uint64_t n_chunks = TOP ? (E + chunk_edges - 1) / chunk_edges : 1;
-  for (uint64_t ch = TOP ? blockIdx.x : 0; ch < n_chunks; ch += TOP ? gridDim.x : 1) {
-  uint64_t q_end = n_loc;
-  if (TOP) {
-    // compaction of the chunk's qualifying edges, in edge order: four rounds of 256 edges (ballot prefix per wave,
-    // wave totals through LDS); part / parts: this rank takes the qualifying edges with e % parts == part
-    if (threadIdx.x == 0) s_cnt = 0u;
-    __syncthreads();
-    for (uint32_t r = 0; r < (SM_CHUNK / 256) * parts; r++) {
-      // thread t of round r looks at edge (chunk base + r * 256 + t) only if it is this rank's (e % parts == part):
-      // the edges are dealt so that consecutive threads of a round see consecutive edges of THIS rank
-      const uint64_t e = ch * chunk_edges + ((uint64_t)r * 256 + threadIdx.x);
-      const bool ok = e < E && (e % parts) == part && weight_bin(__float_as_uint(es[e]), wlo, wshift) >= theta;
-      const uint64_t bal = __ballot(ok);
-      const int wave = threadIdx.x >> 6;
-      if ((threadIdx.x & 63) == 0) s_wtot[wave] = (uint32_t)__popcll(bal);
-      __syncthreads();
-      uint32_t pos = s_cnt + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-      for (int w = 0; w < wave; w++) pos += s_wtot[w];
-      if (ok) l_e[pos] = (uint32_t)e;
-      __syncthreads();
-      if (threadIdx.x == 0) s_cnt += s_wtot[0] + s_wtot[1] + s_wtot[2] + s_wtot[3];
-      __syncthreads();
-    }
-    q_end = s_cnt;
-  }
-  for (uint64_t q = TOP ? (threadIdx.x / TG) : (uint64_t)blockIdx.x * (256 / TG) + (threadIdx.x / TG); q < q_end; q += groups) {
-    const uint64_t e = TOP ? (uint64_t)l_e[q] : (q * parts + part) * stride;
-    const uint32_t i = ei[e], j = ej[e];
-    const uint32_t rowi = i * (uint32_t)W, rowj = j * (uint32_t)W;
-    const int w0 = j >> 6;
-    const float s_ij = es[e];
-    const uint32_t bi = ebi[e], bj = ebj[e];  // the CSR bases travel with the edge: same memory level as ei / ej
-    // No cross-lane step: every lane owns its words.  The loads of RB rounds are issued together, level by level (row
-    // words -> prefix words -> weights).  Measured on C2: 33 us either way — the time is not the per-round latency chain
-    // but gather / LDS-atomic throughput: most sampled edges join two inliers (the inlier clique holds ~60 % of all
-    // edges) with ~250 common neighbours above j each, i.e. ~8 M key evaluations per call.
-    constexpr int RB = 4;
-    for (int wb = w0 + gl; wb < W; wb += TG * RB) {
-      uint64_t ai[RB], aj[RB], m[RB];
-#pragma unroll
-      for (int r = 0; r < RB; r++) {  // level 1: row words
-        const int w = wb + r * TG;
-        const bool live = w < W;
-        ai[r] = bits[rowi + (live ? w : w0)];
-        aj[r] = bits[rowj + (live ? w : w0)];
-        m[r] = live ? (ai[r] & aj[r]) : 0ull;
-        if (w == w0) m[r] &= mask_above(j & 63);
-      }
-      uint32_t pi[RB], pj[RB];
-#pragma unroll
-      for (int r = 0; r < RB; r++) {  // level 2: prefix words (idle slots re-read the row's first one)
-        const int w = wb + r * TG;
-        pi[r] = bi + wpre[rowi + (m[r] ? w : w0)];
-        pj[r] = bj + wpre[rowj + (m[r] ? w : w0)];
-      }
-#pragma unroll
-      for (int r = 0; r < RB; r++) {  // level 3: weights of the common neighbours, four at a time
-        uint64_t mr = m[r];
-        while (mr) {
-          int b[4];
-          const int nbits = pop4(mr, b);
-          float s_ik[4], s_jk[4];
-          tri_weights4(es, b, nbits, {pi[r], ai[r]}, {pj[r], aj[r]}, s_ik, s_jk);
-#pragma unroll
-          for (int q = 0; q < 4; q++)
-            if (q < nbits)
-              atomicAdd(&lh[prune_bin(tri_key_weight(s_ij, s_ik[q], s_jk[q]), klo, shift) * PR_COPIES +
-                            (threadIdx.x & (PR_COPIES - 1))], 1u);
-        }
-      }
-    }
-  }
-  if (TOP) __syncthreads();  // l_e is rewritten by the next chunk
-  }  // chunks
-  hist_flush<PR_COPIES>(lh, hist);
-}
-
-// ------------------------------------------------------------------------------------------------
-// 3c. pruning by an ESTIMATED bound (r04)
-//
-// The certifying samples above pay for their certificate: to exhibit T genuine triangles above the bound they evaluate
-// 4 - 8 M keys at C2 (25 us, the largest launch of stage B), and the bound they can certify sits well below the T-th
-// key, so the pruned graph still holds 10 T triangles.  But the bound need not be certified BEFORE it is used: it can be
-// verified AFTERWARDS, for free.  Take ANY value LB, prune with smin = LB - 2 - 1e-6, enumerate, select.  If the strong
-// subgraph turns out to hold >= T triangles with key >= LB, the proof of 3b applies word for word (it only needs "at least
-// T triangles have key >= LB") and the selection is the full graph's top-T, ties included; if not, nothing is known and the
-// call is repeated with a certifying sample.  The select's first round already counts the keys in [LB, 3.0] — the check
-// is one comparison where that round is resolved (select_resolve, SelectState::want_req).
-// So LB only has to be a good GUESS of a key of rank ~2 T: the lower edge of the histogram bin where
-// rate x (sampled count from the top) reaches margin x T, from a uniform 1-in-rate sample of ALL the graph's triangles.
-// The sample: a triangle (i, j, k), i < j < k, is found from its edge (i, j) in the 64-column word k / 64 of the row pair;
-// edge e looks at the words w >= j / 64 with w = hash(e) (mod rate) only — every (edge, word) pair, hence every triangle,
-// with probability exactly 1 / rate, independently across edges and words, so the sample is not dominated by a few edges
-// (an inlier-inlier edge has hundreds of triangles; a sampled word holds a handful).  One lane per edge: an edge record,
-// two gathered row words and — where they meet — the two prefix words and two weights per triangle: 0.36 M key
-// evaluations at C2 instead of 4 M, no block-level step at all.
-// With margin = 2 the estimate fails when the sample overstates the density of the top keys twofold: at >= 1000 expected
-// samples above the bound that is > 10 sigma even with word-sized clusters.  Failing costs a repeated call, never a wrong
-// result; a context that has seen one failure stops estimating (sc_capi.hip).
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t edge_hash(uint32_t e) {
-  e ^= e >> 16; e *= 0x7FEB352Du; e ^= e >> 15; e *= 0x846CA68Bu; e ^= e >> 16;  // (lowbias32)
-  return e;
-}
-
-constexpr uint32_t SAMPLE_CAND_BLOCKS = 256;  // workgroups of the estimating sample that leave a candidate triangle behind
-__global__ __launch_bounds__(256) void tri_sample_words_kernel(const uint64_t* __restrict__ bits, int W,
-                                                               const uint32_t* __restrict__ wpre,
-                                                               const uint32_t* __restrict__ ebi,
-                                                               const uint32_t* __restrict__ ebj,
-                                                               const uint32_t* __restrict__ ei,
-                                                               const uint32_t* __restrict__ ej,
-                                                               const float* __restrict__ es, uint64_t E, uint32_t rmask,
-                                                               uint32_t* __restrict__ hist,
-                                                               const uint64_t* __restrict__ E_dev,
-                                                               const uint32_t* __restrict__ ebase, uint4* __restrict__ cand,
-                                                               unsigned long long* __restrict__ cand_slot) {
-  // ebase (with ebi == ebj == nullptr): the per-row CSR bases are looked up (after launch_edge_build)
-  // cand (optional): the best-keyed triangle this workgroup sampled, {key bits, i, j, k} (key 0: none) — the voters of stage
-  // C2's reference frame (sc_gramref.hpp)
-  if (E_dev && *E_dev > E) return;  // (launched before the host knew the count: see tri_sample_hist_kernel)
-  if (E_dev) E = *E_dev;
-  // a host-free call's grid covers more edges than there are: the workgroups beyond them leave before they clear 16 KiB of LDS
-  // (one that would have left a candidate says "none": cand is not cleared between calls)
-  if ((uint64_t)blockIdx.x * 256 >= E) {
-    if (cand != nullptr && blockIdx.x < SAMPLE_CAND_BLOCKS && threadIdx.x == 0) cand[blockIdx.x] = make_uint4(0u, 0u, 0u, 0u);
-    return;
-  }
-  uint32_t best_key = 0u, best_e = 0u, best_k = 0u;  // (E < 2^32)
-  // only the first SAMPLE_CAND_BLOCKS workgroups keep their best triangle (tracking it in every one cost the launch 3.6 us at C2;
-  // 64 voters want 64 good triangles, and the best of these workgroups' ~50 000 sampled keys per voter is that)
-  const bool track = cand != nullptr && blockIdx.x < SAMPLE_CAND_BLOCKS;
-  __shared__ uint32_t lh[PR_BINS * EST_COPIES];
-  for (int b = threadIdx.x; b < PR_BINS * EST_COPIES; b += 256) lh[b] = 0;
-  __syncthreads();
-  const uint64_t stride = (uint64_t)gridDim.x * 256;
-  for (uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x; e < E; e += stride) {
-    const uint32_t j = ej[e], i = ei[e];
-    const int w0 = (int)(j >> 6);
-    // the first word >= w0 in this edge's residue class (hashed by its END POINTS: the sample does not depend on the edge numbering)
-    int w = w0 + (int)((edge_hash(i * 0x9E3779B1u + j) - (uint32_t)w0) & rmask);
-    if (w >= W) continue;
-    const uint32_t rowi = i * (uint32_t)W, rowj = j * (uint32_t)W;
-    for (; w < W; w += (int)rmask + 1) {
-      const uint64_t ai = bits[rowi + w], aj = bits[rowj + w];
-      uint64_t m = ai & aj;
-      if (w == w0) m &= mask_above((int)(j & 63));
-      if (m == 0) continue;
-      // only the lanes that found a triangle pay for the edge's weight and CSR bases (one memory level, beside the prefix words)
-      const float s_ij = es[e];
-      const uint32_t bi = ebi ? ebi[e] : ebase[i], bj = ebj ? ebj[e] : ebase[j];
-      const uint32_t pi = bi + wpre[rowi + w], pj = bj + wpre[rowj + w];
-      while (m) {
-        int b[4];
-        const int nbits = pop4(m, b);
-        float s_ik[4], s_jk[4];
-        tri_weights4(es, b, nbits, {pi, ai}, {pj, aj}, s_ik, s_jk);
-#pragma unroll
-        for (int q = 0; q < 4; q++)
-          if (q < nbits) {
-            const uint32_t kb = tri_key_weight(s_ij, s_ik[q], s_jk[q]);
-            atomicAdd(&lh[est_bin(kb) * EST_COPIES + (threadIdx.x & (EST_COPIES - 1))], 1u);
-            if (track && kb > best_key) { best_key = kb; best_e = (uint32_t)e; best_k = (uint32_t)(64 * w + b[q]); }
-          }
-      }
-    }
-  }
-  hist_flush<EST_COPIES>(lh, hist);
-  if (track) {  // (workgroup-uniform) the workgroup's best: by key, then by lowest thread — the sample is deterministic, so is this
-    __shared__ uint32_t s_best[4], s_who[4];
-    uint32_t bk = best_key;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) bk = max(bk, (uint32_t)__shfl_xor((int)bk, o));
-    const uint64_t holders = __ballot(best_key == bk);
-    if ((threadIdx.x & 63) == 0) { s_best[threadIdx.x >> 6] = bk; s_who[threadIdx.x >> 6] = (threadIdx.x & ~63u) + (uint32_t)(__ffsll((unsigned long long)holders) - 1); }
-    __syncthreads();
-    uint32_t wk = s_best[0], wt = s_who[0];
-#pragma unroll
-    for (int v = 1; v < 4; v++)
-      if (s_best[v] > wk) { wk = s_best[v]; wt = s_who[v]; }  // (waves in order: equal keys keep the lower thread)
-    if (threadIdx.x == wt) {
-      cand[blockIdx.x] = wk ? make_uint4(best_key, ei[best_e], ej[best_e], best_k) : make_uint4(0u, 0u, 0u, 0u);
-      // voter v of the frame = the best candidate among the workgroups = v (mod 64): one 64-bit max per workgroup (ControlBlock::ref_slot, zeroed per call)
-      if (wk) atomicMax(&cand_slot[blockIdx.x & 63u], ((unsigned long long)wk << 32) | (unsigned long long)blockIdx.x);
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// 1'. edge_build (r04): everything between stage A and the estimating sample in ONE launch — the hot path's form of
-//     row_stats_scan + edge_fill (two launches, 29.5 us at C2).
-//
-// What made the row kernel a launch of its own was the prefix over the rows: a wave cannot place row i's edges before it
-// knows how many edges the rows before it hold, and counting them meant reading their bit rows.  Stage A now leaves
-// deg+[i] behind (atomics where the adjacency words are made, sc_compat.hip), so a workgroup of EBK_ROWS waves sums
-// deg+[0 .. its first row) itself — a few 16-byte loads per thread, no look-back, no cross-workgroup dependency — and then
-// each wave, for its row: word-prefix popcounts (wpre), the CSR offset and base, the strong-bit row cleared, the row's
-// edges with their recomputed weights (as edge_fill_kernel).
-// (r04 also took the ESTIMATING sample here — sampled triangles recomputed from the correspondences through a per-wave LDS
-// queue: 50.3 us against 16.4 + 13.7 for the two launches, a dense row being one wave's serial chain; removed in r05,
-// profiles/r04_ab_edge_build.txt keeps the numbers.)
-// The CSR bases of an edge's OTHER end (ebj) are not known here (row j's wave may not have run): the counting pass looks
-// them up in ebase instead (one more gather, beside its row loads).  n <= 64 * EBK_WMAX only.
-// ------------------------------------------------------------------------------------------------
-constexpr int EBK_ROWS = 8;     // rows (waves) per workgroup
-constexpr int EBK_CH = 256;     // column indices staged per wave and chunk
-constexpr int EBK_WMAX = 320;   // words per bit row it can handle (n <= 20 480): NCH = 2 chunks of 64 words up to 8192, 5 beyond
-
-template <int NCH>  // 64-word chunks of a bit row: W <= 64 NCH
-__global__ __launch_bounds__(64 * EBK_ROWS) void edge_build_kernel(const uint64_t* __restrict__ bits,
-                                                                   const float* __restrict__ planes, Derived dv, int n,
-                                                                   int ld, int W, const uint32_t* __restrict__ degp,
-                                                                   uint32_t* __restrict__ wpre,
-                                                                   uint64_t* __restrict__ zero_rows,
-                                                                   uint64_t* __restrict__ edge_off,
-                                                                   uint32_t* __restrict__ ebase,
-                                                                   uint32_t* __restrict__ ei, uint32_t* __restrict__ ej,
-                                                                   float* __restrict__ es, uint64_t cap,
-                                                                   uint64_t* __restrict__ host_total,
-                                                                   uint64_t* __restrict__ live_range) {
-  __shared__ uint64_t s_red[EBK_ROWS];
-  __shared__ uint32_t l_j[EBK_ROWS][EBK_CH];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int r0 = blockIdx.x * EBK_ROWS, i = r0 + wave;
-  // edges of the rows before this workgroup's (r0 is a multiple of 4: whole 16-byte pieces)
-  uint64_t acc = 0;
-  {  // (four 16-byte loads in flight: the loop's trips were dependent round trips — up to three for the last rows at C2, ten at C3)
-    constexpr int QS = 64 * EBK_ROWS * 4;
-    int q = tid * 4;
-    for (; q + 3 * QS < r0; q += 4 * QS) {
-      const uint4 v0 = *reinterpret_cast<const uint4*>(degp + q), v1 = *reinterpret_cast<const uint4*>(degp + q + QS),
-                  v2 = *reinterpret_cast<const uint4*>(degp + q + 2 * QS), v3 = *reinterpret_cast<const uint4*>(degp + q + 3 * QS);
-      acc += ((uint64_t)v0.x + v0.y + v0.z + v0.w) + ((uint64_t)v1.x + v1.y + v1.z + v1.w) + ((uint64_t)v2.x + v2.y + v2.z + v2.w) +
-             ((uint64_t)v3.x + v3.y + v3.z + v3.w);
-    }
-    uint4 w[3];
-    int nw = 0;
-#pragma unroll
-    for (int u = 0; u < 3; u++) { const bool in = q + u * QS < r0; w[u] = in ? *reinterpret_cast<const uint4*>(degp + q + u * QS) : make_uint4(0u, 0u, 0u, 0u); nw += in; }
-#pragma unroll
-    for (int u = 0; u < 3; u++) acc += (uint64_t)w[u].x + w[u].y + w[u].z + w[u].w;
-    (void)nw;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-  if (lane == 0) s_red[wave] = acc;
-  __syncthreads();
-  if (i >= n) return;
-  uint64_t my_off = 0;
-#pragma unroll
-  for (int w8 = 0; w8 < EBK_ROWS; w8++) my_off += s_red[w8];
-  for (int r = r0; r < i; r++) my_off += degp[r];  // wave-uniform: scalar loads
-  const int wi = i >> 6, bi = i & 63;
-  const RowSide row = row_side(planes, ld, i, dv);
-  const EdgeOut out{ei, ej, es, cap};
-  // ---- the row's words: prefix popcounts, the strong row cleared (not sc_compat.hip's row_word_stats: this form keeps the
-  // upper-triangle words in registers for the edges below and counts the bits BELOW the diagonal, for the CSR base)
-  uint32_t d_all = 0, d_low = 0;
-  uint64_t up[NCH];
-#pragma unroll
-  for (int c = 0; c < NCH; c++) {
-    const int w = 64 * c + lane;
-    const uint64_t v = w < W ? bits[(size_t)i * W + w] : 0ull;
-    const uint32_t pc = (uint32_t)__popcll(v);
-    uint32_t tot;
-    const uint32_t ex = group_exscan<64>(pc, &tot);
-    if (w < W) {
-      wpre[(size_t)i * W + w] = d_all + ex;
-      zero_rows[(size_t)i * W + w] = 0ull;
-    }
-    d_all += tot;
-    const uint64_t below = (1ull << bi) - 1ull;
-    d_low += w < wi ? pc : (w == wi ? (uint32_t)__popcll(v & below) : 0u);
-    up[c] = w < wi ? 0ull : (w == wi ? (v & mask_above(bi)) : v);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) d_low += __shfl_xor(d_low, o);
-  const uint32_t my_base = (uint32_t)my_off - d_low;
-  if (lane == 0) { edge_off[i] = my_off; ebase[i] = my_base; }
-  // ---- edges, chunk by chunk
-  uint64_t ebase_row = my_off;
-#pragma unroll
-  for (int c = 0; c < NCH; c++)
-    ebase_row += row_edges_emit<EBK_CH>(l_j[wave], up[c], 64 * c + lane, ebase_row, row, out, [](uint64_t, uint32_t, float) {});
-  if (i == n - 1 && lane == 0) {  // the last row's wave knows the edge count: the host polls for it
-    edge_off[n] = ebase_row;
-    if (live_range) { live_range[0] = 0ull; live_range[1] = ebase_row; }
-    if (host_total) publish_host(host_total, ebase_row);  // (nullptr: a host-free call reads the count from edge_off[n] — DeferredPub)
-  }
-}
-
-bool edge_build_fits(int n) { return n <= 64 * EBK_WMAX; }
-
-void launch_edge_build(const Graph& g, const Points& pts, const Derived& dv, uint64_t* zero_rows, uint64_t* edge_off, uint32_t* ebase,
-                       uint32_t* ei, uint32_t* ej, float* es, uint64_t cap, uint64_t* host_total, hipStream_t st, uint64_t* live_range) {
-  const dim3 grid((g.n + EBK_ROWS - 1) / EBK_ROWS), block(64 * EBK_ROWS);
-  if (g.W <= 128)
-    hipLaunchKernelGGL(edge_build_kernel<2>, grid, block, 0, st, g.bits, pts.planes, dv, g.n, g.ld, g.W, g.degp,
-                       const_cast<uint32_t*>(g.wpre), zero_rows, edge_off, ebase, ei, ej, es, cap, host_total, live_range);
-  else
-    hipLaunchKernelGGL(edge_build_kernel<5>, grid, block, 0, st, g.bits, pts.planes, dv, g.n, g.ld, g.W, g.degp,
-                       const_cast<uint32_t*>(g.wpre), zero_rows, edge_off, ebase, ei, ej, es, cap, host_total, live_range);
-}
-
-// sum of the copies -> one 256-bin histogram (the form the ranks exchange)
-__global__ __launch_bounds__(256) void hist_reduce_kernel(const uint32_t* __restrict__ copies, uint32_t* __restrict__ out) {
-  uint32_t v = 0;
-#pragma unroll
-  for (int c = 0; c < PR_HCOPIES; c++) v += copies[c * PR_BINS + threadIdx.x];
-  out[threadIdx.x] = v;
-}
-void launch_hist_reduce(const uint32_t* copies, uint32_t* out, hipStream_t st) {
-  hipLaunchKernelGGL(hist_reduce_kernel, dim3(1), dim3(256), 0, st, copies, out);
-}
-
-// every block derives smin from the histogram (256 bins: cheap) and sets the strong bits of its edges in `mbits`
-// (zeroed beforehand; only upper-triangle entries are needed: bit j of row i for i < j).  Block 0 publishes smin.
-__global__ __launch_bounds__(256) void prune_bits_kernel(const uint32_t* __restrict__ hist, int copies, uint64_t want,
-                                                         uint32_t klo, uint32_t shift,
-                                                         const uint32_t* __restrict__ ei,
-                                                         const uint32_t* __restrict__ ej,
-                                                         const float* __restrict__ es, uint64_t E, int W,
-                                                         unsigned long long* __restrict__ mbits,
-                                                         float* __restrict__ smin_out,
-                                                         uint32_t* __restrict__ klb_out, StrongList sl,
-                                                         uint32_t* __restrict__ tcnt,
-                                                         const uint64_t* __restrict__ own,
-                                                         const uint64_t* __restrict__ E_dev, int trimmed) {
-  // E: what the grid and the arrays cover; Ea: the edges there really are (E_dev: launched before the host knew).  More than
-  // the arrays hold: nothing may run — no strong edge is listed, so the counting and key kernels that follow find no work
-  // (the host repeats the call)
-  if (E_dev && *E_dev > E) return;
-  const uint64_t Ea = E_dev ? *E_dev : E;
-  // a host-free call's grid covers more edges than there are: the workgroups beyond them have nothing to list, and their tcnt
-  // entries are never read (the scan of a host-free call skips the tiles beyond ControlBlock::live_edges and treats what lies
-  // beyond the count as zero) — they leave before the histogram walk
-  if (trimmed && E_dev && sl.region_blocks == 0 && (uint64_t)blockIdx.x * (sl.cnt ? ORD_BLOCK_EDGES : 256u) >= Ea) return;
-  __shared__ uint64_t lds[8];
-  __shared__ float s_smin;
-  __shared__ uint32_t s_klb, s_base, s_wcnt[4], s_rcnt[4][4];
-  static_assert(PR_BINS == 256, "one bin per thread, walked from the top");
-  const uint32_t bin = PR_BINS - 1 - threadIdx.x;
-  uint64_t mine = 0;
-  if (copies == PR_HCOPIES) {  // (the sample's own copies: four loads in flight — a loop of `copies` trips is four round trips to hipcc)
-    static_assert(PR_HCOPIES == 4, "four copies");
-    const uint32_t h0 = hist[bin], h1 = hist[PR_BINS + bin], h2 = hist[2 * PR_BINS + bin], h3 = hist[3 * PR_BINS + bin];
-    mine = (uint64_t)h0 + h1 + h2 + h3;
-  } else {
-    for (int c = 0; c < copies; c++) mine += hist[c * PR_BINS + bin];  // (1: summed by the caller)
-  }
-  if (threadIdx.x == 0) { s_smin = -1.0f; s_klb = 0u; }  // default: no certified bound -> every edge is strong
-  uint64_t tot;
-  const uint64_t before = block_exscan_u64(mine, lds, &tot);
-  if (before < want && want <= before + mine && bin > 0) {
-    const float lb = shift == PR_LOGBINS ? est_bin_floor(bin) : __uint_as_float(klo + (bin << shift));  // lower edge of the crossing bin
-    s_smin = (lb - 2.0f) - 1e-6f;
-    s_klb = __float_as_uint(lb);  // >= want triangles have a key >= this one: the select may ignore anything below
-  }
-  __syncthreads();
-  const float smin = s_smin;
-  if (blockIdx.x == 0 && threadIdx.x == 0) { *smin_out = smin; *klb_out = s_klb; }
-  if (sl.cnt) {
-    // the ORDERED form (2c; one rank, region_blocks == 0): the block takes ORD_BLOCK_EDGES consecutive edges — four runs of 256, a
-    // quarter of the histogram walks above — and writes the strong ones in ascending order into its own slot, their number into
-    // cnt[blockIdx]: no atomic, one barrier, and no tcnt entry is zeroed (nothing scans the counts; an overflow's fall-back
-    // zeroes the weak ones)
-    static_assert(ORD_BLOCK_EDGES == 4 * 256, "four runs of 256");
-    const int wave = threadIdx.x >> 6;
-    bool st[4]; uint64_t bal[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      const uint64_t e = (uint64_t)blockIdx.x * ORD_BLOCK_EDGES + q * 256 + threadIdx.x;
-      st[q] = e < Ea && es[e] >= smin;
-      if (st[q]) {
-        const uint32_t i = ei[e], j = ej[e];
-        atomicOr(&mbits[(size_t)i * W + (j >> 6)], 1ull << (j & 63));
-      }
-      bal[q] = __ballot(st[q]);
-      if ((threadIdx.x & 63) == 0) s_rcnt[q][wave] = (uint32_t)__popcll(bal[q]);
-    }
-    __syncthreads();
-    uint32_t run = 0;  // strong edges of the runs and waves before (q, w)
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-#pragma unroll
-      for (int w = 0; w < 4; w++) {
-        if (w == wave && st[q])
-          sl.list[(uint64_t)blockIdx.x * ORD_BLOCK_EDGES + run + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal[q] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal[q], 0u))] =
-              (uint32_t)((uint64_t)blockIdx.x * ORD_BLOCK_EDGES + q * 256 + threadIdx.x);
-        run += s_rcnt[q][w];
-      }
-    }
-    if (threadIdx.x == 0) sl.cnt[blockIdx.x] = run;
-    return;
-  }
-  // region = blockIdx % ST_SHARDS in both forms (blocks that run side by side add to different counters: with consecutive
-  // blocks on one counter this kernel took 61 us instead of 33 at C3); with contiguous regions the block's 256 EDGES are what
-  // moves: block b takes chunk (b % ST_SHARDS) * region_blocks + b / ST_SHARDS
-  const uint32_t region = blockIdx.x & (ST_SHARDS - 1);
-  const uint64_t chunk = sl.region_blocks ? (uint64_t)region * sl.region_blocks + blockIdx.x / ST_SHARDS : (uint64_t)blockIdx.x;
-  const uint64_t e = (sl.region_blocks && blockIdx.x / ST_SHARDS >= sl.region_blocks) ? E : chunk * 256 + threadIdx.x;
-  bool strong = e < Ea && es[e] >= smin;
-  if (strong) {  // the strong bit matrix is whole on every rank: membership of ANY vertex pair is looked up in it
-    const uint32_t i = ei[e], j = ej[e];
-    atomicOr(&mbits[(size_t)i * W + (j >> 6)], 1ull << (j & 63));
-  }
-  // sharded stage B: only this rank's edge range [own[0], own[1]) enters the list of edges to enumerate
-  if (own) strong = strong && e >= own[0] && e < own[1];
-  if (sl.list) {
-    // the strong edges, compacted (any order: everything downstream is indexed by the edge id): one atomic per block
-    // on one of ST_SHARDS counters; region r receives the blocks with blockIdx % ST_SHARDS == r (or, StrongList::region_blocks,
-    // a run of consecutive blocks: ceil(blocks / ST_SHARDS) of them), so sl.cap = ceil(blocks / ST_SHARDS) * 256 entries can
-    // never overflow.  Weak edges carry no triangle: count 0.
-    if (e < E && (!strong || sl.region_blocks)) tcnt[e] = 0u;
-    const uint64_t bal = __ballot(strong);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) s_wcnt[wave] = (uint32_t)__popcll(bal);
-    __syncthreads();
-    if (threadIdx.x == 0) {  // ONE atomic per block (returning atomics on a shared address cost ~170 ns each here)
-      const uint32_t tot = s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
-      s_base = tot ? atomicAdd(&sl.fill[region], tot) : 0u;
-    }
-    __syncthreads();
-    if (strong) {
-      uint32_t pos = s_base + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-      for (int w = 0; w < wave; w++) pos += s_wcnt[w];
-      sl.list[(uint64_t)region * sl.cap + pos] = (uint32_t)e;
-    }
-  }
-}
-
-uint32_t strong_list_cap(uint64_t E) {
-  const uint64_t blocks = (E + 255) / 256;
-  return (uint32_t)(((blocks + ST_SHARDS - 1) / ST_SHARDS) * 256);
-}
-size_t strong_list_bytes(uint64_t E) { return (size_t)strong_list_cap(E) * ST_SHARDS * sizeof(uint32_t); }
-
-
-// histogram window in key space: [bits(key_floor), bits(3.0f)], monotone in the value; (khi - klo) >> shift < 256
-static void prune_window(float key_floor, uint32_t* klo_out, uint32_t* shift_out) {
-  const uint32_t khi = 0x40400000u;  // 3.0f
-  uint32_t klo;
-  memcpy(&klo, &key_floor, 4);
-  if (!(key_floor > 0.f) || klo >= khi) klo = 0x3F800000u;  // 1.0f
-  const uint32_t range = khi - klo;
-  const int bitsn = 32 - __builtin_clz(range);
-  *klo_out = klo;
-  *shift_out = bitsn > 8 ? (uint32_t)(bitsn - 8) : 0u;
-}
-
-void launch_sample_hist(const Graph& g, const uint32_t* ebi, const uint32_t* ebj, const uint32_t* ei,
-                        const uint32_t* ej, const float* es, uint64_t E, uint64_t want, float key_floor, uint32_t part,
-                        uint32_t parts, uint32_t* hist, uint32_t* es_hist, const Tuning& tn, hipStream_t st,
-                        const uint64_t* E_dev, uint64_t E_hint) {
-  uint32_t klo, shift;
-  prune_window(key_floor, &klo, &shift);
-  const uint64_t Ed = E_hint ? E_hint : E;  // the count the host-side choices are made with
-  // Which form (r02 sweeps, profiles/r02_ab_heaviest_edge_sample.txt and r02_ab_sample_size.txt): the heaviest edges
-  // certify a much tighter bound per sampled edge, but each of them is a costly one (an edge between two inliers has
-  // hundreds of common neighbours).  That pays when T is a small part of the graph's triangles — C3 (N = 20 000, T = 200 k):
-  // stage B 962 -> 551 us, 10.6 M -> 2.1 M enumerated — is a wash on C2 (167 vs 165 us) and loses where T is most of
-  // what there is (C4, T = 500 k of 8.8 M triangles: the uniform sample at stride 1 already certifies 2 T: 211 vs 248 us).
-  // C1 (N = 2000, T = 10 k) loses too: 94 vs 82 us; C2, a wash with every stage bracketed, gains on the hot path (stage B
-  // 154.5 -> 138.5 us: fewer keys also means the speculative launches finish sooner).  What separates them is how small T
-  // is against the triangles the graph holds, for which E^2 / N is a proxy known before any is counted: C3 2550 T, C2
-  // 890 T, C1 320 T, C4 90 T.
-  // sample_mode: 0 = by this rule (E^2 / N >= 600 T), 1 = every stride-th edge, 2 = the heaviest edges.
-  const bool top = tn.sample_mode == 2 ||
-                   (tn.sample_mode == 0 && (double)Ed * (double)Ed / (double)(g.n > 0 ? g.n : 1) >= 600.0 * (double)want);
-  if (top && es_hist) {
-    // the heaviest edges (TOP form): weight histogram, then the sample itself
-    uint32_t wlo, wshift;
-    {
-      const float wfloor = key_floor / 3.0f;
-      uint32_t lo; memcpy(&lo, &wfloor, 4);
-      const uint32_t hi = 0x3F800000u;  // 1.0f
-      if (!(wfloor > 0.f) || lo >= hi) lo = 0x3F000000u;  // 0.5f
-      const int bitsn = 32 - __builtin_clz(hi - lo);
-      wlo = lo; wshift = bitsn > 8 ? (uint32_t)(bitsn - 8) : 0u;
-    }
-    uint64_t target = tn.sample_edges ? tn.sample_edges : (want / 3 < 16384 ? 16384 : want / 3);
-    const int tg = tn.tg_sample ? tn.tg_sample : (g.W > 256 ? 32 : 16);  // C3 (W = 313): 134 (16) vs 107 us (32); C2: 24.4 vs 25.9
-    uint64_t nb = (E + (uint64_t)SM_CHUNK * parts - 1) / ((uint64_t)SM_CHUNK * parts);
-    if (nb > 8192) nb = 8192;
-    if (tn.sample_blocks) nb = tn.sample_blocks;
-#define SC_LAUNCH_TOP(TGV) hipLaunchKernelGGL((tri_sample_hist_kernel<TGV, true>), dim3((unsigned)nb), dim3(256), 0, st, g.bits, g.W, g.wpre, ebi, ebj, ei, ej, es, E, 1u, part, parts, klo, shift, hist, es_hist, target, wlo, wshift, E_dev)
-    if (tg == 4) SC_LAUNCH_TOP(4); else if (tg == 8) SC_LAUNCH_TOP(8); else if (tg == 32) SC_LAUNCH_TOP(32); else if (tg == 64) SC_LAUNCH_TOP(64); else SC_LAUNCH_TOP(16);
-#undef SC_LAUNCH_TOP
-    return;
-  }
-  // every R-th edge.  The sample must grow with T: the bound is the T-th largest SAMPLED key, so a small sample of a
-  // large T certifies little.  ~5T/8 sampled edges (>= 32k) is the sweet spot on C2 for T = 50k ... 400k (swept again
-  // at the end of round 1); Tuning::sample_edges overrides.
-  uint64_t target = want * 5 / 8;
-  if (target < 32768) target = 32768;
-  if (tn.sample_edges) target = tn.sample_edges;
-  uint64_t stride = Ed / (target ? target : 1);
-  if (stride < 1) stride = 1;
-  if (stride > 64) stride = 64;
-  const uint64_t n_s = (E + stride - 1) / stride;
-  const uint64_t n_loc = n_s > part ? (n_s - part + parts - 1) / parts : 0;
-  if (n_loc == 0) return;
-  // lanes per sampled edge (r02 sweep, profiles/r02_ab_lanes_per_edge.txt): 16 while the sample is small enough for
-  // about one edge per group (C2 26.9 -> 19.8 us, C3 129 -> 112), 8 once groups take several trips (C4: 74 vs 81)
-  const int tg = tn.tg_sample ? tn.tg_sample : ((n_loc <= 131072 || g.W > 256) ? 16 : 8);
-  uint64_t nb = (n_loc + (256 / tg) - 1) / (256 / tg);
-  // about one sampled edge per group (measured: 256 blocks 70 us, 1024+ blocks 35 us on C2)
-  if (nb > 4096) nb = 4096;
-#define SC_LAUNCH_SAMPLE(TGV) hipLaunchKernelGGL((tri_sample_hist_kernel<TGV, false>), dim3((unsigned)nb), dim3(256), 0, st, g.bits, g.W, g.wpre, ebi, ebj, ei, ej, es, E, (uint32_t)stride, part, parts, klo, shift, hist, (const uint32_t*)nullptr, (uint64_t)0, 0u, 0u, E_dev)
-  if (tg == 4) SC_LAUNCH_SAMPLE(4); else if (tg == 8) SC_LAUNCH_SAMPLE(8); else if (tg == 32) SC_LAUNCH_SAMPLE(32); else if (tg == 64) SC_LAUNCH_SAMPLE(64); else SC_LAUNCH_SAMPLE(16);
-#undef SC_LAUNCH_SAMPLE
-}
-
-SamplePlan sample_plan(uint64_t want, bool allow_estimate, const Tuning& tn, uint64_t E, int W) {
-  SamplePlan sp{false, 1u, want};
-  if (!allow_estimate || tn.no_estimate || tn.sample_mode != 0 || want == 0) return sp;
-  // rate: 64 while 2 T still leaves >= 1024 expected samples above the bound, halved below that, never under 8 (a whole-graph
-  // enumeration is what the pruning is there to avoid)
-  uint32_t rate = 64;
-  while (rate > 8 && 2 * want / rate < 1024) rate >>= 1;
-  // ... and beyond 64 on big graphs: the sample looks at E x (row words) / rate word pairs — 16 M random 8-byte gathers at C3
-  // (N = 20 000, rate 64: 156 us) for 6000 samples above the bound where 1500 do (rate 256: 45 us)
-  while (rate < 512 && 2 * want / (2 * rate) >= 1024 && (double)E * (double)(W > 0 ? W : 1) / 2.0 / rate > 2.0e6) rate <<= 1;  // (an edge has ~W / 2 words beyond its higher end)
-  // the rank the bound aims at, in % of T: T plus FIVE standard deviations of the sampled count at rank T — a sampled word
-  // brings its triangles together, ~8 at a time — within [115, 200] (C2 151, C3 151 at its rate of 256, C4 116).  Eight until r05
-  // (C2 181): over 30 000 frames of 256 distinct C2 scenes no estimate failed at 130 % nor at 115 %, 17 did at 105 % — and the bound is
-  // the lower edge of the histogram bin that holds the aimed rank (256 log bins: ~0.4 T keys per bin up there), which adds to
-  // the margin more often than not.  A failed estimate costs a repeated call, never a result.  C2: 186 k -> 151 k triangles
-  // enumerated, - 1.9 us per frame.
-  uint64_t margin = tn.est_margin_pct;
-  if (!margin) {
-    const double at_T = (double)want / rate;
-    double m = 1.0 + 5.0 * __builtin_sqrt(8.0 / (at_T > 1.0 ? at_T : 1.0));
-    m = m < 1.15 ? 1.15 : (m > 2.0 ? 2.0 : m);
-    margin = (uint64_t)(m * 100.0 + 0.5);
-  }
-  const uint64_t aim = (want * margin + 99) / 100;
-  uint64_t hw = (aim + rate - 1) / rate;
-  if (hw < 128 && !tn.est_margin_pct) hw = 128;
-  if (hw < 1) hw = 1;
-  sp.estimate = true; sp.rate = rate; sp.hist_want = hw;
-  return sp;
-}
-
-uint32_t sample_estimate_blocks(uint64_t E, const Tuning& tn) {
-  uint64_t nb = (E + 255) / 256;
-  if (nb > 4096) nb = 4096;
-  if (tn.sample_blocks) nb = tn.sample_blocks;
-  return (uint32_t)nb;
-}
-uint32_t sample_candidate_blocks(uint64_t E, const Tuning& tn) {  // how many of them write a candidate (launch_sample_estimate, cand)
-  const uint32_t nb = sample_estimate_blocks(E, tn);
-  return nb < SAMPLE_CAND_BLOCKS ? nb : SAMPLE_CAND_BLOCKS;
-}
-
-void launch_sample_estimate(const Graph& g, const uint32_t* ebi, const uint32_t* ebj, const uint32_t* ei, const uint32_t* ej,
-                            const float* es, uint64_t E, float key_floor, uint32_t rate, uint32_t* hist, const Tuning& tn,
-                            hipStream_t st, const uint64_t* E_dev, const uint32_t* ebase, uint4* cand, unsigned long long* cand_slot) {
-  if (E == 0) return;
-  (void)key_floor;  // (the logarithmic bins need no window)
-  const uint32_t nb = sample_estimate_blocks(E, tn);
-  hipLaunchKernelGGL(tri_sample_words_kernel, dim3(nb), dim3(256), 0, st, g.bits, g.W, g.wpre, ebi, ebj, ei, ej, es, E,
-                     rate - 1u, hist, E_dev, ebase, cand_slot ? cand : nullptr, cand_slot);
-}
-
-void launch_prune_bits(const Graph& g, const uint32_t* hist, bool hist_is_copies, const uint32_t* ei, const uint32_t* ej, const float* es,
-                       uint64_t E, uint64_t want, float key_floor, uint64_t* mbits, float* smin, uint32_t* klb,
-                       const StrongList& sl, uint32_t* tcnt, const uint64_t* own, hipStream_t st, const uint64_t* E_dev, bool logbins,
-                       bool trimmed) {
-  uint32_t klo, shift;
-  prune_window(key_floor, &klo, &shift);
-  if (logbins) shift = PR_LOGBINS;  // the histogram of launch_sample_estimate
-  const uint64_t blocks = sl.cnt ? (E + ORD_BLOCK_EDGES - 1) / ORD_BLOCK_EDGES : sl.region_blocks ? (uint64_t)sl.region_blocks * ST_SHARDS : (E + 255) / 256;
-  hipLaunchKernelGGL(prune_bits_kernel, dim3((unsigned)blocks), dim3(256), 0, st, hist,
-                     hist_is_copies ? PR_HCOPIES : 1, want, klo, shift, ei,
-                     ej, es, E, g.W, reinterpret_cast<unsigned long long*>(mbits), smin, klb, sl, tcnt, own, E_dev, trimmed ? 1 : 0);
-}
-
-// Sharded stage B, after the certificate: what enumerating row i of the PRUNED graph costs — 32 x the triangles of a
-// SAMPLE of its strong edges (every edge (i, j) with (i + j) % 32 == 0: AND + popcount of the two strong rows above j,
-// exactly what the counting pass does, for one edge in 32) plus one per strong edge (the counting pass spends
-// about a triangle's worth of time on an edge without any).  One wave per row: the sampled edges are taken one after the
-// other (wave-uniform), the 64 lanes AND the row words in parallel.  Saturated to u32.  The prefix of these costs cuts the
-// rows into the ranks' ranges: a correspondence list in keypoint order puts the inliers — and nearly all the triangles of
-// the pruned graph — into a few rows, which the a-priori estimate of row_stats_kernel (every edge of the FULL graph weighs
-// the same) cannot see.  (A proxy from the strong degrees alone left 1.4 x between the ranks on such a scene: outlier rows
-// have strong edges but hardly a triangle.)
-__global__ __launch_bounds__(256) void strong_rowcost_kernel(const uint64_t* __restrict__ mbits, int n, int W,
-                                                             uint32_t* __restrict__ rowcost) {
-  const int lane = threadIdx.x & 63;
-  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (i >= n) return;
-  const uint64_t* __restrict__ ri = mbits + (size_t)i * W;
-  const uint64_t pattern = 0x0000000100000001ull << ((32 - (i & 31)) & 31);  // bits b of any word with (i + 64 w + b) % 32 == 0
-  uint64_t tri = 0, sdeg = 0;
-  for (int wb = i >> 6; wb < W; wb += 64) {
-    const int w = wb + lane;
-    const uint64_t v = w < W ? ri[w] : 0ull;  // (only bits above i are ever set: the strong matrix is upper-triangular)
-    sdeg += (uint64_t)__popcll(v);
-    const uint64_t sm = v & pattern;
-    uint64_t bal = __ballot(sm != 0);
-    while (bal) {  // wave-uniform: one lane's word after the other
-      const int L = __builtin_ctzll(bal);
-      bal &= bal - 1;
-      const int wL = wb + L;
-      uint64_t mL = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(sm >> 32), L) << 32) |
-                    (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)sm, L);
-      while (mL) {
-        const int bpos = __builtin_ctzll(mL);
-        mL &= mL - 1;
-        const uint64_t* __restrict__ rj = mbits + (size_t)(wL * 64 + bpos) * W;
-        for (int w2 = wL + lane; w2 < W; w2 += 64) {
-          uint64_t m = ri[w2] & rj[w2];
-          if (w2 == wL) m &= mask_above(bpos);
-          tri += (uint64_t)__popcll(m);
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { tri += __shfl_xor(tri, o); sdeg += __shfl_xor(sdeg, o); }
-  const uint64_t cost = 32ull * tri + sdeg;
-  if (lane == 0) rowcost[i] = cost > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)cost;
-}
-
-// prefix of the row costs AND this rank's range in one single-block launch (n values: 80 KB at N = 20 000): rows [lo, hi)
-// with lo = the first row whose cost prefix reaches rank / world of the total (the rule of shard_split_kernel).
-// Wave w of 16 takes the w-th sixteenth of the rows, 256 rows per step (a lane loads four consecutive rows with one 16-byte
-// load: a quarter of the dependent trips the 4-byte form made — at N = 20 000 this launch took 20 us, nearly all of it load
-// latency); the wave whose segment holds a boundary walks it a second time.  rowcost holds roundup(n, 4) + 1024 entries.
-__device__ __forceinline__ uint4 cost4(const uint32_t* __restrict__ rowcost, int r, int r1) {  // rows r .. r + 3, zero from r1 on
-  uint4 v = *reinterpret_cast<const uint4*>(rowcost + r);
-  if (r + 0 >= r1) v.x = 0u;
-  if (r + 1 >= r1) v.y = 0u;
-  if (r + 2 >= r1) v.z = 0u;
-  if (r + 3 >= r1) v.w = 0u;
-  return v;
-}
-__global__ __launch_bounds__(1024) void cost_split_kernel(const uint32_t* __restrict__ rowcost,
-                                                          const uint64_t* __restrict__ edge_off, int n, uint32_t rank,
-                                                          uint32_t world, uint32_t* __restrict__ own_row,
-                                                          uint64_t* __restrict__ own_edge) {
-  __shared__ uint64_t s_tot[16];
-  __shared__ uint32_t s_row[2];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int seg = ((n + 15) / 16 + 255) / 256 * 256, r0 = min(n, wave * seg), r1 = min(n, r0 + seg);
-  uint64_t mine = 0;
-#pragma unroll 4
-  for (int rb = r0; rb < r1; rb += 256) {
-    const uint4 v = cost4(rowcost, rb + 4 * lane, r1);
-    mine += (uint64_t)v.x + v.y + v.z + v.w;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o);
-  if (lane == 0) s_tot[wave] = mine;
-  if (threadIdx.x < 2) s_row[threadIdx.x] = (uint32_t)n;
-  __syncthreads();
-  uint64_t pre = 0, total = 0;
-  for (int w = 0; w < 16; w++) { if (w < wave) pre += s_tot[w]; total += s_tot[w]; }
-  for (int which = 0; which < 2; which++) {
-    const uint32_t l = rank + (uint32_t)which;
-    if (l == 0 || l >= world) continue;
-    const uint64_t target = (uint64_t)(((unsigned __int128)total * l) / world);
-    // the first row r with (sum of the costs before r) >= target lies in this wave's segment iff pre < target <= pre + mine,
-    // or it is the segment's first row (pre >= target and the wave before did not reach it: handled by the min below)
-    if (pre + mine < target && wave != 15) continue;       // (wave-uniform) beyond this segment
-    if (pre >= target) { if (lane == 0) atomicMin(&s_row[which], (uint32_t)min(r0, n)); continue; }
-    uint64_t run = pre;
-    for (int rb = r0; rb < r1; rb += 256) {
-      const int r = rb + 4 * lane;
-      const uint4 v = cost4(rowcost, r, r1);
-      const uint64_t lane_sum = (uint64_t)v.x + v.y + v.z + v.w;
-      const uint64_t inc = wave_inscan(lane_sum);
-      const uint64_t b0 = run + inc - lane_sum;              // sum of the costs before row r
-      const uint64_t b1 = b0 + v.x, b2 = b1 + v.y, b3 = b2 + v.z;
-      // the first of this lane's four rows whose "before" reaches the target (4: none)
-      const int k = (r < r1 && b0 >= target) ? 0 : ((r + 1 < r1 && b1 >= target) ? 1 : ((r + 2 < r1 && b2 >= target) ? 2 : ((r + 3 < r1 && b3 >= target) ? 3 : 4)));
-      const uint64_t hit = __ballot(k < 4);
-      if (hit) {
-        const int L = __builtin_ctzll(hit);  // "before" grows with the row: the lowest lane that hit holds the first such row
-        const int kk = __shfl(k, L);
-        if (lane == 0) atomicMin(&s_row[which], (uint32_t)(rb + 4 * L + kk));
-        break;
-      }
-      run += __shfl(inc, 63);
-    }
-    // (no row of the segment reached it: the boundary is the first row of the next segment, or n — its wave reports r0)
-  }
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    const uint32_t l = rank + threadIdx.x;
-    const uint32_t row = l == 0 ? 0u : (l >= world ? (uint32_t)n : s_row[threadIdx.x]);
-    own_row[threadIdx.x] = row;
-    own_edge[threadIdx.x] = edge_off[row];
-  }
-}
-void launch_cost_split(const uint32_t* rowcost, const uint64_t* edge_off, int n, uint32_t rank, uint32_t world,
-                       uint32_t* own_row, uint64_t* own_edge, hipStream_t st) {
-  hipLaunchKernelGGL(cost_split_kernel, dim3(1), dim3(1024), 0, st, rowcost, edge_off, n, rank, world, own_row, own_edge);
-}
-void launch_strong_rowcost(const Graph& g, const uint64_t* mbits, uint32_t* rowcost, hipStream_t st) {
-  hipLaunchKernelGGL(strong_rowcost_kernel, dim3((unsigned)((g.n + 3) / 4)), dim3(256), 0, st, mbits, g.n, g.W, rowcost);
+    hipLaunchKernelGGL(key_range_kernel, dim3(1), dim3(1024), 0, st, ka.blk_minmax, ka.blk_minmax + TK_MAX_BLOCKS, nb, ka.sel, want);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1772,7 +744,7 @@ __device__ __forceinline__ uint4 view_load4(const KeyView& v, uint64_t q) {
 // The state after round r from the state before it and the round's histogram.  Whole workgroup (SEL_THREADS threads, all
 // arrive); lds: 10 words of 8 bytes.  Thread t owns `per` bins counted from the TOP: bins nbins - 1 - (per t + k).  The bins were
 // filled by the previous launch's L2-side atomics: plain loads see them.  *shortfall: a pruning bound promised want_req keys at
-// or above the window's floor and did not keep it (an estimate set too high — sc_tri.hip 3c): the selection of this call proves
+// or above the window's floor and did not keep it (an estimate set too high — sc_tri_prune.hip 3c): the selection of this call proves
 // nothing; the host repeats it with a certifying sample.
 __device__ SelSnap select_resolve(const SelectState* __restrict__ sel, int r, int rounds, uint64_t* lds, bool* shortfall) {
   static_assert(SEL_THREADS == 256 && SEL_PER == 16, "256 threads, at most 16 bins each");
@@ -1884,8 +856,7 @@ __global__ __launch_bounds__(SEL_THREADS) void select_round_kernel(KeyView view,
 
 KeyView plain_view(const uint32_t* wkey, uint64_t M) { return KeyView{wkey, M, 0, 0, nullptr, 0, nullptr}; }
 
-void launch_select_rounds(const KeyView& view, SelectState* s, int rounds, const Tuning& tn, hipStream_t st,
-                          uint64_t* host_short) {
+void launch_select_rounds(const KeyView& view, SelectState* s, int rounds, uint64_t* host_short, const Tuning& tn, hipStream_t st) {
   const uint64_t M = view.M;
   if (M == 0) return;
   uint64_t blocks = (M + (uint64_t)SEL_THREADS * SEL_ITEMS - 1) / ((uint64_t)SEL_THREADS * SEL_ITEMS);
@@ -1966,8 +937,8 @@ __global__ __launch_bounds__(CP_THREADS) void compact_count_kernel(KeyView view,
   }
 }
 
-void launch_compact_count(const KeyView& view, SelectState* s, int rounds, uint32_t* blk_gt, uint32_t* blk_eq,
-                          hipStream_t st, uint64_t* host_short) {
+void launch_compact_count(const KeyView& view, SelectState* s, int rounds, uint32_t* blk_gt, uint32_t* blk_eq, uint64_t* host_short,
+                          hipStream_t st) {
   if (view.M == 0) return;
   if (rounds > 3) rounds = 3;
   const dim3 grid((unsigned)compact_blocks(view.M));
@@ -2032,17 +1003,16 @@ __global__ __launch_bounds__(CP_THREADS) void compact_write_kernel(KeyView view,
   }
 }
 
-void launch_compact_write(const KeyView& view, SelectState* s, const uint32_t* blk_gt,
-                          const uint32_t* blk_eq, const uint64_t* off_gt, const uint64_t* off_eq,
-                          uint64_t* sel_ord, uint32_t* sel_key, uint64_t n_sel, hipStream_t st) {
+void launch_compact_write(const KeyView& view, SelectState* s, const uint32_t* blk_gt, const uint32_t* blk_eq, const uint64_t* off_gt,
+                          const uint64_t* off_eq, const Selection& out, hipStream_t st) {
   if (view.M == 0) return;
   const dim3 grid((unsigned)compact_blocks(view.M));
   if (view.seg_len)
     hipLaunchKernelGGL(compact_write_kernel<true>, grid, dim3(CP_THREADS), 0, st, view, s, blk_gt, blk_eq, off_gt, off_eq,
-                       sel_ord, sel_key, n_sel);
+                       out.sel_ord, out.sel_key, out.n);
   else
     hipLaunchKernelGGL(compact_write_kernel<false>, grid, dim3(CP_THREADS), 0, st, view, s, blk_gt, blk_eq, off_gt, off_eq,
-                       sel_ord, sel_key, n_sel);
+                       out.sel_ord, out.sel_key, out.n);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2108,12 +1078,11 @@ CandBlob cand_blob(void* blob, size_t cap) {
   return b;
 }
 
-void launch_cand_emit(const uint64_t* sel_ord, const uint32_t* sel_key, const uint2* kcol, const uint32_t* ei,
-                      const uint32_t* ej, const SelectState* sel, const uint64_t* toff, uint64_t E, uint32_t n_max,
+void launch_cand_emit(const Selection& sl, const KeyArrays& ka, const EdgeList& el, const EdgeCounts& ec, uint32_t n_max,
                       uint64_t want_requested, const CandBlob& b, hipStream_t st) {
   const unsigned blocks = n_max ? (n_max + 255) / 256 : 1;
-  hipLaunchKernelGGL(cand_emit_kernel, dim3(blocks), dim3(256), 0, st, sel_ord, sel_key, kcol, ei, ej, sel, toff, E, b.hdr,
-                     b.keys, b.recs, (uint64_t)b.cap, want_requested);
+  hipLaunchKernelGGL(cand_emit_kernel, dim3(blocks), dim3(256), 0, st, sl.sel_ord, sl.sel_key, ka.kcol, el.ei, el.ej, ka.sel, ec.toff, el.E,
+                     b.hdr, b.keys, b.recs, (uint64_t)b.cap, want_requested);
 }
 
 __global__ __launch_bounds__(64) void merge_check_kernel(const uint64_t* __restrict__ blobs, uint64_t blob_words,
@@ -2172,14 +1141,14 @@ __global__ __launch_bounds__(64) void merge_prepare_kernel(const uint64_t* __res
   sel->want = want;  // (what the candidate kernels read if no select runs: an empty view)
   // SC_FLAG_EST_BOUND: the bound in *klb was an estimate.  A rank only ever sends keys at or above it (its select window's
   // floor), so fewer than T entries in all means fewer than T triangles of the whole graph lie above it — unless it certified
-  // nothing (0: no pruning) — and the top-T of the pruned graph proves nothing about the full one (sc_tri.hip 3c)
+  // nothing (0: no pruning) — and the top-T of the pruned graph proves nothing about the full one (sc_tri_prune.hip 3c)
   if (host_short && *klb != 0u && ns < (uint64_t)T) publish_host(host_short, 1ull);
   host_out[1] = m;
   publish_host(host_out, want);
 }
 
 void launch_merge_prepare(const void* blobs, size_t blob_bytes, uint32_t world, uint32_t T, bool fast, const uint32_t* klb,
-                          SelectState* sel, uint64_t* host_out, hipStream_t st, uint64_t* host_short) {
+                          SelectState* sel, uint64_t* host_out, uint64_t* host_short, hipStream_t st) {
   hipLaunchKernelGGL(merge_prepare_kernel, dim3(1), dim3(64), 0, st, static_cast<const uint64_t*>(blobs),
                      (uint64_t)(blob_bytes / 8), world, T, fast ? 1 : 0, klb, sel, host_out, host_short);
 }
@@ -2217,10 +1186,9 @@ __global__ __launch_bounds__(256) void tri_decode_kernel(const uint32_t* __restr
   tri[3 * (size_t)t + 2] = ke.x;
 }
 
-void launch_tri_decode(const uint32_t* ei, const uint32_t* ej, const uint2* kcol, const uint64_t* sel_ord, uint32_t T,
-                       uint32_t* tri, hipStream_t st) {
+void launch_tri_decode(const EdgeList& el, const KeyArrays& ka, const Selection& sl, uint32_t T, uint32_t* tri, hipStream_t st) {
   if (T == 0) return;
-  hipLaunchKernelGGL(tri_decode_kernel, dim3((T + 255) / 256), dim3(256), 0, st, ei, ej, kcol, sel_ord, T, tri);
+  hipLaunchKernelGGL(tri_decode_kernel, dim3((T + 255) / 256), dim3(256), 0, st, el.ei, el.ej, ka.kcol, sl.sel_ord, T, tri);
 }
 
 // ---- ranked order for the stage hook: sort (~key, position), then gather
@@ -2243,13 +1211,13 @@ __global__ __launch_bounds__(256) void gather_ranked_kernel(const uint64_t* __re
   key_ranked[t] = sel_key[src];
 }
 
-void launch_rank_order(const uint32_t* tri, const uint32_t* sel_key, uint32_t T, uint64_t* sortkey, uint64_t* sorted,
+void launch_rank_order(const uint32_t* tri, const Selection& sl, uint32_t T, uint64_t* sortkey, uint64_t* sorted,
                        void* sort_tmp, size_t sort_bytes, uint32_t* tri_ranked, uint32_t* key_ranked,
                        hipStream_t st) {
   if (T == 0) return;
-  hipLaunchKernelGGL(sortkey_kernel, dim3((T + 255) / 256), dim3(256), 0, st, sel_key, T, sortkey);
+  hipLaunchKernelGGL(sortkey_kernel, dim3((T + 255) / 256), dim3(256), 0, st, sl.sel_key, T, sortkey);
   launch_sort_u64(sortkey, sorted, T, sort_tmp, sort_bytes, st);
-  hipLaunchKernelGGL(gather_ranked_kernel, dim3((T + 255) / 256), dim3(256), 0, st, sorted, tri, sel_key, T,
+  hipLaunchKernelGGL(gather_ranked_kernel, dim3((T + 255) / 256), dim3(256), 0, st, sorted, tri, sl.sel_key, T,
                      tri_ranked, key_ranked);
 }
 

@@ -1,4 +1,4 @@
-"""GPU: stage B pruned by an ESTIMATED bound (sc_tri.hip 3c).
+"""GPU: stage B pruned by an ESTIMATED bound (sc_tri_prune.hip 3c).
 
 sc_register / sc_register_device(_async) prune the graph by a bound guessed from a 1-in-64 sample of its triangles instead
 of one certified by a 4 M-key sample; the select verifies the guess (it must find T keys at or above it) and a call whose

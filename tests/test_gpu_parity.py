@@ -277,7 +277,7 @@ def test_register_matches_oracle(pkg, O, reg, name):
 
 @pytest.mark.parametrize("name", ["C0", "C1", "C2"])
 def test_certified_pruning_changes_nothing_but_the_work(pkg, reg, name):
-    """Stage B enumerates only the certified 'strong' subgraph by default (sc_tri.hip 3b).  The ranked list — keys,
+    """Stage B enumerates only the certified 'strong' subgraph by default (sc_tri_prune.hip 3b).  The ranked list — keys,
     triangles, order — and the whole result must be identical with the pruning switched off, while the number of
     enumerated 3-cliques must drop."""
     cfg, scene = pkg.synth.make_config_scene(name)
