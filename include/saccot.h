@@ -884,7 +884,12 @@ int sc_register_guided_pairs_features_device(sc_ctx* ctx, const float* d_pts, co
  *              of their own: two pairs on {a, b} give two triangles with the same q and r.  Its error is
  *              E = T_r(c->a) o (T_q(b->c) o T_p(a->b)), with tr = (E.R_00 + E.R_11) + E.R_22 and
  *              e2 = (E.t_0 * E.t_0 + E.t_1 * E.t_1) + E.t_2 * E.t_2.
- *   consistent tr >= tr_min && e2 <= e2_max.  Finite fp32 poses cannot overflow these chains: there is no NaN to order.
+ *   consistent tr >= tr_min && e2 <= e2_max, both cuts inclusive.  No NaN arises from finite fp32 poses, so there is none to order:
+ *              tr cannot overflow (three factors below 2^128 each), and nothing is infinite before the squares of e2.  e2 itself
+ *              may overflow to +inf with hostile finite poses — an inverted pose's t' carried through two more poses puts |E.t|
+ *              near 2^517 —; +inf is then the largest max_e2 there is, and it is never consistent, trans_tol being finite.
+ *              A loop off by exactly a half turn (tr = -1) is not consistent at any rot_tol: at the largest one accepted, the
+ *              float nearest pi, tr_min = -1 + 7.5e-15, that float being 8.7e-8 away from pi.
  *   rounds     alive_0 = edge.  Round k = 1, 2, ...: ok_k(p) = the consistent triangles of p whose three pairs are all in
  *              alive_{k-1}; alive_k(p) = alive_{k-1}(p) && (ok_k(p) >= min_ok || keep[p]).  The rounds stop after the first round K
  *              with alive_K == alive_{K-1} (stable), or at K = max_rounds.  The stable result is the largest sub-list in which

@@ -4,7 +4,8 @@ families they share.
 The arithmetic is numpy float64 on the exactly widened float32 entries, every product and every sum written out element by element in
 the header's order — no `@`, no dot, no einsum: a BLAS may fuse or reorder.  (A numpy ufunc call rounds once per operation.)  The
 thresholds are arguments: the GPU tests pass the two values sc_cycles_thresholds returns.  The families are built with whatever is
-convenient; only `cycles` is the reference.
+convenient; only `cycles` is the reference.  The families of tests/test_gpu_pairs_cycles_range.py stand at the end, with what the reference
+measures on them as literals; exact24 brings an integer evaluation of its own, which shares no code with `cycles`.
 """
 import functools
 import itertools
@@ -239,3 +240,160 @@ def one_triangle(directions, consistent):
     if not consistent:
         rt = corrupt(rt, [2], 6, 30.0, 30.0)
     return Family(3, pairs, rt, () if consistent else (2,), rot_tol=ROT_TOL, trans_tol=TRANS_TOL)
+
+
+# ---- the families of the range tests: past one trip of either loop, on the cuts, at the ends of the number range ---------------------
+# k130: what the reference measures, asserted by tests/test_cycles_abi.py.  Without keep, min_ok <= 103 stops after 2 rounds with only the
+# corrupted pairs gone and min_ok 104 .. 111 unravels the whole list; with every pair among the first 40 sets kept, min_ok 104 leaves
+# those 780 pairs after 12 rounds, and the 193 pairs of the second grid trip (index >= 8192) leave in nine different rounds
+# ([14 alive, 7, 0, 2, 2, 3, 0, 3, 8, 31, 108, 15]).
+K130_SEED, K130_BAD = 130, 419  # (5 % of the 8385 pairs corrupted)
+K130_PROTECTED, K130_MIN_OK = 40, 104  # every pair among the sets below K130_PROTECTED is kept
+K130_SUMMARY = (12, 1, 780, 8385, 357760, 306786)  # rounds, stable, alive, edges, triangles, consistent
+K130_DROPS = [780, 379, 5, 36, 133, 242, 25, 131, 406, 1182, 4344, 722, 0]  # pairs by dropped_round: [alive, round 1, ..., round 12]
+K130_SHORT = 5  # a max_rounds below K130_SUMMARY's: stable == 0
+K130_NO_KEEP = (12, 1, 0)  # rounds, stable, alive with keep NULL ([0, 420, 5, 40, 199, 207, 29, 162, 481, 1723, 4748, 371] by round)
+# the repeats' copies close loops of their own: min_ok 104 .. 108 stops after 2 rounds, 110 unravels to the kept pairs in 9
+# ([795, 389, 113, 121, 222, 348, 1290, 4332, 975] by round)
+K130_REPEATS_MIN_OK, K130_REPEATS_SUMMARY = 110, (9, 1, 795, 8585, 383994, 330422)
+
+
+def _complete(n, rng):
+    """every pair of n sets, in random stored directions and shuffled order"""
+    pairs = np.array(list(itertools.combinations(range(n), 2)))
+    flip = rng.random(len(pairs)) < 0.5
+    pairs[flip] = pairs[flip][:, ::-1]
+    return pairs[rng.permutation(len(pairs))]
+
+
+@functools.lru_cache(maxsize=None)
+def k130():
+    """130 sets, all 8385 pairs in random stored directions and shuffled order, 419 corrupted: more pairs than a round's grid has
+    waves (2048 x 4), and every neighbour list has 129 entries — three trips of a wave's lanes"""
+    rng = np.random.default_rng(K130_SEED)
+    pairs = _complete(130, rng)
+    R, t = absolute_poses(130, K130_SEED + 1)
+    bad = rng.choice(len(pairs), K130_BAD, replace=False)
+    keep = (pairs.max(axis=1) < K130_PROTECTED).astype(np.uint8)
+    return Family(130, pairs, corrupt(relative_poses(pairs, R, t), bad, K130_SEED + 2), bad, keep=keep, rot_tol=ROT_TOL, trans_tol=TRANS_TOL,
+                  min_ok=K130_MIN_OK, max_rounds=64)
+
+
+@functools.lru_cache(maxsize=None)
+def k130_repeats():
+    """k130 with 200 of its pairs listed a second time (the copies' poses clean), 100 of those reversed: runs of equal neighbours
+    inside lists that are longer than a wave"""
+    f = k130()
+    which = np.random.default_rng(K130_SEED + 3).choice(len(f.pairs), 200, replace=False)
+    again = f.pairs[which].copy()
+    again[:100] = again[:100, ::-1]
+    R, t = absolute_poses(130, K130_SEED + 1)
+    pairs = np.concatenate([f.pairs, again])
+    keep = (pairs.max(axis=1) < K130_PROTECTED).astype(np.uint8)
+    return Family(130, pairs, np.concatenate([f.rt, relative_poses(again, R, t)]), f.bad, keep=keep, **dict(f.params, min_ok=K130_REPEATS_MIN_OK))
+
+
+# The 24 proper signed permutation matrices (the rotations of a cube): traces 3, 1, 0, -1 for the identity, the quarter turns, the
+# third turns and the half turns.
+GROUP24 = [np.array(m) for m in (np.eye(3, dtype=np.int64)[list(perm)] * np.array(signs)[:, None]
+                                 for perm in itertools.permutations(range(3)) for signs in itertools.product((1, -1), repeat=3))
+           if round(np.linalg.det(m)) == 1]
+EXACT24_SEED = 24
+
+
+@functools.lru_cache(maxsize=None)
+def exact24():
+    """24 sets posed by cube rotations and integer translations in [-8, 8], all 276 pairs in random directions and shuffled, about a
+    third of the pairs off by an integer step: every entry, every tr and every e2 is a small integer, exact in every format"""
+    rng = np.random.default_rng(EXACT24_SEED)
+    pairs = _complete(24, rng)
+    R = [GROUP24[g] for g in rng.permutation(24)]
+    t = rng.integers(-8, 9, (24, 3))
+    rt = np.zeros((276, 12), np.int64)
+    for p, (a, b) in enumerate(pairs.tolist()):
+        rt[p, :9] = (R[b].T @ R[a]).ravel()
+        rt[p, 9:] = R[b].T @ (t[a] - t[b])
+    bad = np.sort(rng.choice(276, 92, replace=False))
+    for p in bad:
+        kind = rng.integers(3)
+        if kind == 0:
+            rt[p, 9 + rng.integers(3)] += 1
+        elif kind == 1:
+            rt[p, 9:] += (1, 1, 0)
+        else:
+            rt[p, :9] = (GROUP24[1 + rng.integers(23)] @ rt[p, :9].reshape(3, 3)).ravel()
+    assert (GROUP24[0] == np.eye(3)).all()
+    return Family(24, pairs, rt, bad, rot_tol=0.0, trans_tol=0.0)
+
+
+def exact24_integers():
+    """(tp, tq, tr_, tr, e2): every triangle of exact24 and its error in np.int64 arithmetic, by the header's composition — its own
+    enumeration of the triangles and none of the fp64 code above"""
+    f = exact24()
+    rt = f.rt.astype(np.int64)
+    assert (rt == f.rt).all()
+    where = {tuple(ab): p for p, ab in enumerate(f.pairs.tolist())}
+
+    def T(x, y):  # x -> y, and the pair it comes from
+        if (x, y) in where:
+            p = where[(x, y)]
+            return p, rt[p, :9].reshape(3, 3), rt[p, 9:]
+        p = where[(y, x)]
+        Rm, tv = rt[p, :9].reshape(3, 3), rt[p, 9:]
+        return p, Rm.T, -(Rm.T @ tv)
+
+    out = []
+    for a, b, c in itertools.combinations(range(24), 3):
+        (p, PR, Pt), (q, QR, Qt), (r, CR_, Ct) = T(a, b), T(b, c), T(c, a)
+        MR, Mt = QR @ PR, QR @ Pt + Qt
+        ER, Et = CR_ @ MR, CR_ @ Mt + Ct
+        out.append((p, q, r, int(np.trace(ER)), int(Et @ Et)))
+    out = np.array(out, np.int64)
+    return tuple(out[:, k] for k in range(5))
+
+
+PI32 = float(np.float32(np.pi))  # the float nearest pi, the largest rot_tol the host rules accept: tr_min = -1 + 7.6e-15
+# (rot_tol, trans_tol) -> the consistent triangles of exact24, from the integers
+EXACT24_CUTS = {(0.0, 0.0): 610, (0.0, 1.0): 884, (0.0, 2.0): 1373, (float(np.float32(np.pi / 2)), 1.0): 929, (PI32, 1.0): 950,
+                (float(np.float32(2 * np.pi / 3)), 0.0): 666}
+
+
+def scaled(f, k):
+    """the family with every translation and trans_tol multiplied by 2^k, in float"""
+    rt = f.rt.copy()
+    rt[:, 9:] = np.ldexp(rt[:, 9:], k).astype(np.float32)
+    params = dict(f.params, trans_tol=float(np.ldexp(np.float32(f.params["trans_tol"]), k).astype(np.float32)))
+    return Family(f.n_sets, f.pairs, rt, f.bad, keep=f.keep, **params)
+
+
+FLT_MAX = float(np.finfo(np.float32).max)
+HOSTILE24_SEED = 666
+
+
+@functools.lru_cache(maxsize=None)
+def hostile24():
+    """k24's list with poses that are no rotations: random finite bit patterns over the whole exponent range and both signs, and a
+    few records planted — every entry FLT_MAX on a triangle's three pairs, two of them stored reversed (two inverted poses and a third
+    factor: |E.t| near 2^517, and its square is +inf), subnormals, -0.0, and one record that is all zero"""
+    f = k24()
+    rng = np.random.default_rng(HOSTILE24_SEED)
+    bits = rng.integers(0, 1 << 32, (276, 12), dtype=np.uint64).astype(np.uint32)
+    bits[(bits >> np.uint32(23)) & np.uint32(0xFF) == 0xFF] ^= np.uint32(1 << 23)  # exponent 255 -> 254: finite
+    rt = bits.view(np.float32).copy()
+    where = {tuple(ab): p for p, ab in enumerate(f.pairs.tolist())}
+    # a triangle a < b < c whose pairs on {a, b} and {b, c} are stored reversed: both are inverted on the way round
+    a, b, c = next((a, b, c) for a, b, c in itertools.combinations(range(24), 3) if (b, a) in where and (c, b) in where)
+    planted = [where[(b, a)], where[(c, b)], where[(a, c)] if (a, c) in where else where[(c, a)]]
+    rt[planted] = FLT_MAX
+    free = [p for p in range(276) if p not in planted]
+    rt[free[0]] = 0.0  # all zero: finite, so valid
+    rt[free[1]] = np.array([1, 0x7FFFFF, 0x80000001, 0x807FFFFF] * 3, np.uint32).view(np.float32)  # subnormals, both signs
+    rt[free[2], ::2] = -0.0
+    rt[free[3]] = -0.0
+    return Family(24, f.pairs, rt, planted, rot_tol=ROT_TOL, trans_tol=TRANS_TOL)
+
+
+def flt_max_triangle(directions):
+    """one_triangle's list with every entry of every pose FLT_MAX"""
+    f = one_triangle(directions, True)
+    return Family(3, f.pairs, np.full((3, 12), FLT_MAX, np.float32), rot_tol=ROT_TOL, trans_tol=TRANS_TOL)

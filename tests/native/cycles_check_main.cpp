@@ -173,6 +173,22 @@ int main() {
     }
     adjacency("all pairs of 40 sets", 41, all);
   }
+  {
+    std::vector<uint32_t> all;  // every pair of 130 sets, scrambled: 8385 pairs, more than a round's waves; every list 129 entries, longer than two waves
+    const uint32_t n = 130, np = n * (n - 1) / 2;
+    for (uint32_t k = 0; k < np; k++) {
+      const uint32_t j = (uint32_t)(((uint64_t)k * 2579) % np);  // (2579 is prime and does not divide 8385)
+      uint32_t a = 0, left = j;
+      while (left >= n - 1 - a) { left -= n - 1 - a; a++; }
+      const uint32_t b = a + 1 + left;
+      all.push_back(k % 2 ? b : a); all.push_back(k % 2 ? a : b);
+    }
+    std::vector<uint32_t> deg;
+    bool ok = list_error(n, all, &deg) == nullptr && all.size() == 2 * 8385u;
+    for (uint32_t s = 0; s < n && ok; s++) ok = deg[s] == 129;
+    check("all pairs of 130 sets: every degree is 129", ok);
+    adjacency("all pairs of 130 sets", n, all);
+  }
 
   if (failures) { printf("%d failed\n", failures); return 1; }
   printf("all passed\n");

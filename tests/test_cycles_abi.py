@@ -63,6 +63,12 @@ def test_the_section_says_what_is_not_here_and_states_every_rule():
                  "e2 = (E.t_0 * E.t_0 + E.t_1 * E.t_1) + E.t_2 * E.t_2", "tr >= tr_min && e2 <= e2_max",
                  "alive_k(p) = alive_{k-1}(p) && (ok_k(p) >= min_ok || keep[p])"):
         assert rule in flat, rule
+    # what finite poses can and cannot do to the chains, and the half turn
+    for claim in ("both cuts inclusive", "No NaN arises from finite fp32 poses", "tr cannot overflow", "e2 itself may overflow to +inf with hostile finite poses",
+                  "+inf is then the largest max_e2 there is, and it is never consistent", "A loop off by exactly a half turn (tr = -1) is not consistent at any rot_tol",
+                  "tr_min = -1 + 7.5e-15"):
+        assert claim in flat, claim
+    assert "cannot overflow these chains" not in flat
     integration = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     assert "2f-1" in integration and "sc_pairs_cycles_device" in integration
 
@@ -212,3 +218,122 @@ def test_the_other_families():
     others = np.setdiff1d(np.arange(276), [5, 9, 11])
     alone = CR.cycles(24, pairs[others], rt[others], *_thr(f))
     assert res[others].tobytes() == alone[0].tobytes()
+
+
+# ---- the families of the range tests (tests/test_gpu_pairs_cycles_range.py) -----------------------------------------------------------
+def _cut(rot_tol, trans_tol):
+    return 1.0 + 2.0 * math.cos(float(np.float32(rot_tol))), float(np.float32(trans_tol)) ** 2
+
+
+def test_k130_is_past_one_trip_of_both_loops():
+    f = CR.k130()
+    P = len(f.pairs)
+    assert f.n_sets == 130 and P == 8385 and P > 2048 * 4 and P % 4 and len(f.bad) == CR.K130_BAD
+    assert len({(min(a, b), max(a, b)) for a, b in f.pairs.tolist()}) == P and 3000 < (f.pairs[:, 0] > f.pairs[:, 1]).sum() < 5400
+    degree = np.bincount(f.pairs.reshape(-1), minlength=130)
+    assert (np.minimum(degree[f.pairs[:, 0]], degree[f.pairs[:, 1]]) == 129).all()  # every pair's shorter list: three trips of 64 lanes (64 + 64 + 1)
+    late = np.arange(P) >= 8192  # the pairs of the second grid trip
+    res, s = CR.cycles(130, f.pairs, f.rt, *_thr(f), min_ok=f.params["min_ok"], max_rounds=64, keep=f.keep)
+    drops = np.bincount(res["dropped_round"], minlength=s["rounds"] + 1).tolist()
+    print("k130", s, "drops by round", drops, "late pairs by round", np.bincount(res["dropped_round"][late]).tolist(), "late alive", res["alive"][late].sum())
+    assert (s["rounds"], s["stable"], s["alive"], s["edges"], s["triangles"], s["consistent"]) == CR.K130_SUMMARY and s["rounds"] >= 4 and s["stable"] == 1
+    assert 0 < s["alive"] < s["edges"] == P and drops == CR.K130_DROPS
+    assert len(set(res["dropped_round"][late & (res["dropped_round"] > 0)].tolist())) >= 2 and res["alive"][late].any()
+    assert (res["cycles"] == 128).all() and (res["alive"][f.keep != 0] == 1).all() and 0 < f.keep.sum() < P and f.keep[late].any() and not f.keep[late].all()
+    # cut short: not stable
+    res, s = CR.cycles(130, f.pairs, f.rt, *_thr(f), min_ok=f.params["min_ok"], max_rounds=CR.K130_SHORT, keep=f.keep)
+    assert (s["rounds"], s["stable"]) == (CR.K130_SHORT, 0) and CR.K130_SHORT < CR.K130_SUMMARY[0] and s["alive"] == P - sum(drops[1:CR.K130_SHORT + 1])
+    # without the keep bytes the whole list unravels
+    res, s = CR.cycles(130, f.pairs, f.rt, *_thr(f), min_ok=f.params["min_ok"], max_rounds=64)
+    print("k130, no keep", s, np.bincount(res["dropped_round"]).tolist())
+    assert (s["rounds"], s["stable"], s["alive"]) == CR.K130_NO_KEEP
+    # the repeats: runs of equal neighbours in lists longer than a wave
+    g = CR.k130_repeats()
+    assert len(g.pairs) == P + 200 and (g.pairs[P:P + 100, 0] == f.pairs[:, 1][_index_of(f, g.pairs[P:P + 100, ::-1])]).all()
+    res, s = CR.cycles(130, g.pairs, g.rt, *_thr(g), min_ok=g.params["min_ok"], max_rounds=64, keep=g.keep)
+    print("k130_repeats", s, np.bincount(res["dropped_round"]).tolist(), "cycles", res["cycles"].min(), res["cycles"].max())
+    assert (s["rounds"], s["stable"], s["alive"], s["edges"], s["triangles"], s["consistent"]) == CR.K130_REPEATS_SUMMARY
+    assert s["triangles"] > 357760 and res["cycles"].max() > 128 and 0 < s["alive"] < s["edges"] and s["stable"] == 1
+
+
+def _index_of(f, pairs):
+    where = {tuple(ab): p for p, ab in enumerate(f.pairs.tolist())}
+    return np.array([where[tuple(ab)] for ab in np.asarray(pairs).tolist()])
+
+
+def test_exact24_is_integers_and_sits_on_the_cuts():
+    f = CR.exact24()
+    assert f.n_sets == 24 and len(f.pairs) == 276 and len(f.bad) == 92 and len(CR.GROUP24) == 24
+    assert all((g @ g.T == np.eye(3)).all() for g in CR.GROUP24) and len({g.tobytes() for g in CR.GROUP24}) == 24
+    tp, tq, tr_, tr, e2 = CR.exact24_integers()
+    assert len(tp) == 2024 and sorted(zip(tp.tolist(), tq.tolist(), tr_.tolist())) == sorted(zip(*(x.tolist() for x in CR.triangles(f.pairs, np.ones(276, bool)))))
+    ftr, fe2 = CR.errors(f.pairs, f.rt, tp, tq, tr_)
+    assert (ftr == tr).all() and (fe2 == e2).all()  # exactly: every value is a small integer
+    print("exact24 tr", dict(zip(*(x.tolist() for x in np.unique(tr, return_counts=True)))), "e2 <= 4", [int((e2 == v).sum()) for v in range(5)], "max", e2.max())
+    assert set(tr.tolist()) == {3, 1, 0, -1} and e2.min() == 0
+    counts = {}
+    for (rot_tol, trans_tol), planted in CR.EXACT24_CUTS.items():
+        tr_min, e2_max = _cut(rot_tol, trans_tol)
+        good = (tr >= tr_min) & (e2 <= e2_max)
+        res, s = CR.cycles(24, f.pairs, f.rt, tr_min, e2_max, min_ok=3)
+        print("exact24", rot_tol, trans_tol, "tr_min", tr_min, "e2_max", e2_max, "consistent", good.sum(), s)
+        assert ((ftr >= tr_min) & (fe2 <= e2_max)).tolist() == good.tolist() and s["consistent"] == good.sum() == planted
+        ok = sum(np.bincount(role[good], minlength=276) for role in (tp, tq, tr_))
+        assert (res["ok"] == ok).all()
+        counts[(rot_tol, trans_tol)] = int(good.sum())
+    # the cuts are inclusive and there are triangles on them
+    assert _cut(0.0, 0.0) == (3.0, 0.0) and _cut(0.0, 1.0)[1] == 1.0 and _cut(0.0, 2.0)[1] == 4.0
+    assert ((tr == 3) & (e2 == 0)).sum() == counts[(0.0, 0.0)] > 0  # tr == tr_min and e2 == e2_max at once: > or < would leave nothing
+    assert ((tr == 3) & (e2 == 1)).sum() == counts[(0.0, 1.0)] - counts[(0.0, 0.0)] > 0
+    assert ((tr == 3) & (e2 == 4)).sum() > 0 and ((tr == 3) & (e2 <= 4)).sum() == counts[(0.0, 2.0)] > counts[(0.0, 1.0)] + ((tr == 3) & (e2 == 4)).sum()
+    # a loop off by exactly a half turn is not consistent even at the largest rot_tol: tr_min = -1 + 7.6e-15
+    assert -1.0 < _cut(CR.PI32, 1.0)[0] < -1.0 + 1e-14 and ((tr == -1) & (e2 <= 1)).sum() > 0
+    assert counts[(CR.PI32, 1.0)] == ((tr > -1) & (e2 <= 1)).sum()
+    quarter, third = float(np.float32(np.pi / 2)), float(np.float32(2 * np.pi / 3))
+    assert counts[(quarter, 1.0)] == ((tr >= 1) & (e2 <= 1)).sum() and counts[(third, 0.0)] == ((tr >= 0) & (e2 == 0)).sum()
+
+
+def test_scaling_the_translations_scales_max_e2_alone():
+    for f, min_ok, keep in ((CR.k24(), 3, None), (CR.k130(), CR.K130_MIN_OK, CR.k130().keep)):
+        base, bs = CR.cycles(f.n_sets, f.pairs, f.rt, *_thr(f), min_ok=min_ok, max_rounds=64, keep=keep)
+        for k in (-100, -40, 40, 100):
+            g = CR.scaled(f, k)
+            assert (g.rt[:, :9] == f.rt[:, :9]).all() and (g.rt[:, 9:].astype(np.float64) == np.ldexp(f.rt[:, 9:].astype(np.float64), k)).all()
+            assert _thr(g)[1] == math.ldexp(_thr(f)[1], 2 * k)
+            res, s = CR.cycles(g.n_sets, g.pairs, g.rt, *_thr(g), min_ok=min_ok, max_rounds=64, keep=keep)
+            assert s.tobytes() == bs.tobytes()
+            for name in res.dtype.names:
+                want = np.ldexp(base["max_e2"], 2 * k) if name == "max_e2" else base[name]
+                assert res[name].tobytes() == want.tobytes(), (k, name)
+        g = CR.scaled(f, -140)  # subnormal floats: valid input, no covariance claimed
+        assert np.isfinite(g.rt).all() and 0 < g.params["trans_tol"] < np.finfo(np.float32).tiny
+        assert ((g.rt[:, 9:] != 0) & (np.abs(g.rt[:, 9:]) < np.finfo(np.float32).tiny)).any()
+        g = CR.scaled(f, 120)
+        assert np.isfinite(g.rt).all() and np.isfinite(np.float32(g.params["trans_tol"]))
+
+
+def test_hostile24_is_finite_and_overflows_only_e2():
+    f = CR.hostile24()
+    assert np.isfinite(f.rt).all() and (f.pairs == CR.k24().pairs).all()
+    exponent = (f.rt.view(np.uint32) >> 23) & 0xFF
+    assert exponent.min() == 0 and exponent.max() == 254 and len(set(exponent.reshape(-1).tolist())) > 250 and (f.rt < 0).any() and (f.rt > 0).any()
+    assert (f.rt.view(np.uint32) == 0x80000000).any() and (f.rt == 0).all(axis=1).any()  # -0.0; one all-zero record
+    assert ((exponent == 0) & (f.rt != 0)).any()  # subnormals
+    assert (f.rt[f.bad] == CR.FLT_MAX).all() and len(f.bad) == 3
+    for min_ok in (0, 1):
+        res, s = CR.cycles(24, f.pairs, f.rt, *_thr(f), min_ok=min_ok)
+        print("hostile24", min_ok, s, "max_e2 inf", np.isinf(res["max_e2"]).sum(), "min_trace", res["min_trace"].min(), res["min_trace"].max())
+        assert (res["status"] == SC_OK).all() and s["edges"] == 276 and s["triangles"] == 2024
+        assert not np.isnan(res["min_trace"]).any() and not np.isnan(res["max_e2"]).any() and np.isfinite(res["min_trace"]).all()
+        assert (res["max_e2"][f.bad] == np.inf).all() and np.isinf(res["max_e2"]).sum() == 3 and (res["max_e2"] >= 0).all()
+        assert (res["min_trace"] < -1e100).any() and (res["min_trace"] < -1.0).sum() > 200
+        assert s["alive"] == (276 if min_ok == 0 else 276 - (res["ok"] == 0).sum())
+    for directions in range(8):
+        g = CR.flt_max_triangle(directions)
+        res, s = CR.cycles(3, g.pairs, g.rt, *_thr(g))
+        inverted = bin(directions ^ 4).count("1")  # pairs 0 and 1 are inverted where stored reversed, pair 2 (c -> a) where it is not
+        print("FLT_MAX triangle", g.pairs.tolist(), res["min_trace"][0], res["max_e2"][0])
+        assert (s["triangles"], s["consistent"], s["alive"]) == (1, 0, 0) and np.isfinite(res["min_trace"]).all() and abs(res["min_trace"][0]) > 1e116
+        assert (res["max_e2"] == res["max_e2"][0]).all() and np.isinf(res["max_e2"][0]) == bool(directions & 1) and not np.isnan(res["max_e2"]).any()
+    assert CR.cycles(3, [(1, 0), (2, 1), (0, 2)], g.rt, *_thr(g))[0]["max_e2"].view(np.uint64).tolist() == [0x7FF0000000000000] * 3
+    assert CR.cycles(3, [(0, 1), (1, 2), (0, 2)], g.rt, *_thr(g))[0]["max_e2"].max() < 3.78e233
