@@ -8,7 +8,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsaccot.so")
-SOURCES = ["sc_compat.hip", "sc_tri_edges.hip", "sc_tri_prune.hip", "sc_tri.hip", "sc_score.hip", "sc_final.hip", "sc_sort.hip", "sc_capi.hip", "sc_capi_tri.hip", "sc_capi_frame.hip", "sc_capi_hooks.hip", "sc_capi_peel.hip", "sc_capi_match.hip", "sc_capi_polish.hip", "sc_multi.hip", "sc_peel.hip", "sc_match.hip",
+SOURCES = ["sc_compat.hip", "sc_tri_edges.hip", "sc_tri_prune.hip", "sc_tri.hip", "sc_kabsch.hip", "sc_score.hip", "sc_filter.hip", "sc_gram_guard.hip", "sc_final.hip", "sc_sort.hip", "sc_capi.hip", "sc_capi_tri.hip", "sc_capi_frame.hip", "sc_capi_hooks.hip", "sc_capi_peel.hip", "sc_capi_match.hip", "sc_capi_polish.hip", "sc_multi.hip", "sc_peel.hip", "sc_match.hip",
            "sc_polish.hip", "sc_capi_batch.hip", "sc_batch.hip", "sc_capi_match_batch.hip", "sc_match_batch.hip",
            "sc_capi_polish_batch.hip", "sc_polish_batch.hip", "sc_capi_instances_batch.hip", "sc_capi_pairs.hip", "sc_capi_match_guided_batch.hip", "sc_capi_match_guided_poses.hip",
            "sc_capi_info_batch.hip", "sc_info_batch.hip", "sc_capi_info_frame.hip", "sc_info_frame.hip",
@@ -16,7 +16,7 @@ SOURCES = ["sc_compat.hip", "sc_tri_edges.hip", "sc_tri_prune.hip", "sc_tri.hip"
            "sc_capi_settle.hip", "sc_settle_frame.hip", "sc_settle_batch.hip",
            "sc_capi_merge.hip", "sc_merge_frame.hip", "sc_merge_batch.hip",
            "sc_capi_cycles.hip", "sc_cycles.hip"]
-HEADERS = ["sc_arith.hpp", "sc_block.hpp", "sc_kernels.hpp", "sc_tri.hpp", "sc_gramref.hpp", "sc_refine.hpp", "sc_refit.hpp", "sc_batch_frame.hpp", "sc_info.hpp", "sc_winner.hpp", "sc_ctx.hpp", "sc_frame_check.hpp", "sc_match_tile.hpp", "sc_match_batch_check.hpp", "sc_match_guided_check.hpp", "sc_match_guided_batch_check.hpp", "sc_match_guided_poses_check.hpp", "sc_pairs_check.hpp", "sc_chunks.hpp", "sc_capi_pose.hpp", "sc_pose_check.hpp", "sc_assign.hpp", "sc_assign_check.hpp", "sc_settle.hpp", "sc_settle_check.hpp", "sc_merge.hpp", "sc_merge_check.hpp", "sc_cycles_check.hpp", os.path.join("..", "..", "include", "saccot.h"),
+HEADERS = ["sc_arith.hpp", "sc_block.hpp", "sc_kernels.hpp", "sc_tri.hpp", "sc_score.hpp", "sc_gramref.hpp", "sc_refine.hpp", "sc_refit.hpp", "sc_batch_frame.hpp", "sc_info.hpp", "sc_winner.hpp", "sc_ctx.hpp", "sc_frame_check.hpp", "sc_match_tile.hpp", "sc_match_batch_check.hpp", "sc_match_guided_check.hpp", "sc_match_guided_batch_check.hpp", "sc_match_guided_poses_check.hpp", "sc_pairs_check.hpp", "sc_chunks.hpp", "sc_capi_pose.hpp", "sc_pose_check.hpp", "sc_assign.hpp", "sc_assign_check.hpp", "sc_settle.hpp", "sc_settle_check.hpp", "sc_merge.hpp", "sc_merge_check.hpp", "sc_cycles_check.hpp", os.path.join("..", "..", "include", "saccot.h"),
            os.path.join("..", "..", "include", "saccot_debug.h")]
 # -ffp-contract=off: the canonical arithmetic (sc_arith.hpp) fuses only where it says fmaf.
 # -amdgpu-mfma-vgpr-form: MFMA results land in VGPRs (unified register file on gfx950), no v_accvgpr_read copies.

@@ -195,11 +195,12 @@ int stage_inputs(sc_ctx* c, const float* d_src, const float* d_tgt, int64_t n, c
   ENSURE(c, c->fx_part, stage_part_words(c->pass.ld) * 4);
   c->pinned[HW_COORD_MAX] = ~0ull;  // "maxima not known yet"
   if (c->pass.form.build) ENSURE(c, c->degp, (size_t)c->pass.ld * sizeof(uint32_t));  // stage A accumulates deg+ there: cleared on the way
-  launch_stage_points(d_src, d_tgt, c->pass.n, c->pass.ld, p->layout, c->planes.as<float>(),
-                      reinterpret_cast<uint32_t*>(&c->pinned[HW_BAD_INPUT]), c->ctl.as<uint32_t>(),
-                      (uint32_t)(sizeof(ControlBlock) / 4), c->fx_mx.as<uint32_t>(), c->fx_part.as<uint32_t>(),
-                      c->pass.mode.host_free ? nullptr : c->fx_mx.as<uint32_t>() + FX_MX_WORDS, c->pass.mode.host_free ? nullptr : &c->pinned[HW_COORD_MAX], c->pass.mode.host_free ? nullptr : &c->pinned[HW_BOX], c->stream,  // (host-free: no ticket — stage A's launch reduces the rows, run_compat; finalize hands the words over, DeferredPub)
-                      c->pass.form.build ? c->degp.as<uint32_t>() : nullptr, c->pass.form.build ? (uint32_t)c->pass.ld : 0u);
+  const bool hf = c->pass.mode.host_free;  // (host-free: no ticket — stage A's launch reduces the rows, run_compat; finalize hands the words over, DeferredPub)
+  const CoordStatsOut cs{c->fx_mx.as<uint32_t>(), c->fx_part.as<uint32_t>(), hf ? nullptr : c->fx_mx.as<uint32_t>() + FX_MX_WORDS,
+                         hf ? nullptr : &c->pinned[HW_COORD_MAX], hf ? nullptr : &c->pinned[HW_BOX]};
+  const ZeroSpan zero[2] = {{c->ctl.as<uint32_t>(), (uint32_t)(sizeof(ControlBlock) / 4)}, {c->pass.form.build ? c->degp.as<uint32_t>() : nullptr, c->pass.form.build ? (uint32_t)c->pass.ld : 0u}};
+  launch_stage_points(cs, zero, d_src, d_tgt, c->pass.n, c->pass.ld, p->layout, c->planes.as<float>(),
+                      reinterpret_cast<uint32_t*>(&c->pinned[HW_BAD_INPUT]), c->stream);
   return SC_OK;
 }
 
@@ -236,9 +237,9 @@ int run_compat(sc_ctx* c, bool dense) {
     slot->used = ++c->wg_map_clock;
     map = slot->buf.as<uint32_t>(); map_len = slot->len;
   }
-  launch_compat(points_of(c), c->pass.dv, dense ? c->S.as<float>() : nullptr, c->pass.bits_cur, 0, c->pass.n, c->tn, c->stream,
-                c->pass.form.build ? c->degp.as<uint32_t>() : nullptr, map, map_len, c->pass.mode.host_free ? c->fx_part.as<uint32_t>() : nullptr,
-                c->fx_mx.as<uint32_t>());
+  const CompatOpts opts{c->pass.form.build ? c->degp.as<uint32_t>() : nullptr, map, map_len,
+                        c->pass.mode.host_free ? c->fx_part.as<uint32_t>() : nullptr, c->fx_mx.as<uint32_t>()};
+  launch_compat(points_of(c), opts, c->pass.dv, dense ? c->S.as<float>() : nullptr, c->pass.bits_cur, 0, c->pass.n, c->tn, c->stream);
   return SC_OK;
 }
 
@@ -642,7 +643,7 @@ static int use_filter(const sc_ctx* c, const sc_params* p, const Shard& sh) {
   const CoordStats cs = filter_stats(c);
   return score_filter_mode(p->score_mode, c->tn, c->pass.n, sh.ld_local, cs.mx, cs.mx == ~0ull ? nullptr : cs.box, c->pass.dv.tau2);
 }
-// The Gram filter's bound rests on a measured model of the matrix pipe (sc_score.hip, gram_guard_kernel): probe the pipe this
+// The Gram filter's bound rests on a measured model of the matrix pipe (sc_gram_guard.hip, gram_guard_kernel): probe the pipe this
 // context runs on, once, the first time a call would choose that filter.  0 not run, 1 the model holds, 2 violated.
 static int run_gram_guard(sc_ctx* c) {
   if (c->gram_guard != 0) return SC_OK;
@@ -677,44 +678,51 @@ int decide_filter(sc_ctx* c, const sc_params* p, const Shard& sh) {
   return SC_OK;
 }
 
-// the filter's buffers for this shard, and the job that fills the tile / clears the state
-static int filter_job(sc_ctx* c, const Shard& sh, FilterTileJob* job) {
+// the filter's buffers for this pass's plan; filter_of(c) is taken behind it
+static int ensure_filter(sc_ctx* c) {
   const FilterPlan& fp = c->pass.fx_plan;
   ENSURE(c, c->fx_tile, fp.tile_bytes);
   ENSURE(c, c->fx_state, fp.state_bytes);
   if (fp.coef_bytes) ENSURE(c, c->fx_coef, fp.coef_bytes);
-  uint32_t* mx = c->fx_mx.as<uint32_t>();
   if (fp.mode == 2) SC_TRY(ensure_frame(c));
-  *job = filter_tile_job(fp, mx, nullptr, c->fx_tile.p, c->fx_state.p, c->fx_coef.p, sh.ld_local, c->pass.dv.tau2, c->fx_frame.p);
   return SC_OK;
 }
+// the views of the context's stage-C arrays (sc_kernels.hpp): the one place each Buf becomes a typed pointer.
+// hyps_of: behind the ENSUREs of rt and rt_aos and behind decide_filter (aos: only where the exact pass will read it); t_eff_dev: a
+// host-free call, or one with an estimated bound — the selection may turn out shorter than the T its launches were sized for (then the
+// call is repeated); its real length is what the select left in sel.want
+Hyps hyps_of(const sc_ctx* c) {
+  return Hyps{c->pass.sh, c->pass.sh.n_local ? c->rt.as<float>() : nullptr, c->pass.filter_on ? c->rt_aos.as<float>() : nullptr,
+              (c->pass.mode.host_free || c->pass.form.est_active) ? &c->ctl.as<ControlBlock>()->sel.want : nullptr};
+}
+FilterBufs filter_of(const sc_ctx* c) {
+  return FilterBufs{c->pass.fx_plan, c->fx_tile.p, c->fx_state.p, c->fx_coef.p, c->fx_frame.p, c->fx_mx.as<uint32_t>()};
+}
 
-// C2: the counts of this shard's hypotheses into c->partial; *rows: rows of c->partial the arg-max has to add up.
-// SC_SCORE_COUNT runs the matrix-pipe filter + the exact fix-up (sc_score.hip); the truncated scores, and
+// C2: the counts of the hypotheses h into c->partial; *out: that array and the rows of it the arg-max has to add up.
+// SC_SCORE_COUNT runs the matrix-pipe filter + the exact fix-up (sc_filter.hip); the truncated scores, and
 // sc_debug.score_filter = 1, the plain fp32 kernel.
-int run_score(sc_ctx* c, const sc_params* p, const Shard& sh, uint32_t* rows, bool tile_done, hipEvent_t ev0, hipEvent_t ev1,
-              hipEvent_t ev_mid) {
+int run_score(sc_ctx* c, const sc_params* p, const Hyps& h, Partial* out, bool tile_done, const Stamps& ev) {
   if (c->pass.filter_on) {  // decide_filter() ran earlier in this call
     const FilterPlan& fp = c->pass.fx_plan;
-    *rows = fp.splits;
-    ENSURE(c, c->partial, (size_t)fp.splits * sh.ld_local * 4);
-    if (!tile_done) {  // (the stage hook; the path builds the tile inside the Kabsch launch)
-      FilterTileJob job;
-      SC_TRY(filter_job(c, sh, &job));
+    ENSURE(c, c->partial, (size_t)fp.splits * h.sh.ld_local * 4);
+    *out = Partial{c->partial.as<uint32_t>(), fp.splits};
+    if (!tile_done) SC_TRY(ensure_filter(c));  // (the stage hook; the path builds the tile inside the Kabsch launch)
+    const FilterBufs fb = filter_of(c);
+    if (!tile_done) {
+      const FilterTileJob job = filter_tile_job(fb, h.sh.ld_local, c->pass.dv.tau2);
       if (fp.mode == 2)  // the frame first: tile and coefficients are made in it (the hypotheses exist already: it votes among them)
-        launch_gram_ref(points_of(c), TriSource{}, sh, c->rt.as<float>(), nullptr, c->fx_mx.as<uint32_t>(), c->pass.dv.tau2, c->tn,
-                        c->fx_frame.p, c->stream);
+        launch_gram_ref(points_of(c), nullptr, h, fb, c->pass.dv.tau2, c->tn, c->stream);
       launch_filter_tile(points_of(c), job, c->stream);
-      if (fp.mode == 2) launch_gram_coef(c->rt.as<float>(), sh, c->pass.dv.tau2, job.coef, c->stream);
+      if (fp.mode == 2) launch_gram_coef(h, c->pass.dv.tau2, job.coef, c->stream);
     }
-    launch_score_filter(points_of(c), c->rt.as<float>(), c->rt_aos.as<float>(), sh, c->pass.dv, fp, c->fx_tile.p, c->fx_state.p,
-                        c->fx_coef.p, c->fx_frame.p, c->partial.as<uint32_t>(), c->tn, c->stream, ev0, ev1, ev_mid);
+    launch_score_filter(points_of(c), h, fb, *out, ev, c->pass.dv, c->tn, c->stream);
     return SC_OK;
   }
-  *rows = score_chunks(c->pass.n, sh.ld_local);
-  if (sh.ld_local) ENSURE(c, c->partial, (size_t)*rows * sh.ld_local * 4);
-  launch_score(points_of(c), c->rt.as<float>(), c->rt_aos.as<float>(), sh, c->pass.dv, p->score_mode, c->partial.as<uint32_t>(),
-               c->tn, c->stream, ev0, ev1);
+  const uint32_t rows = score_chunks(c->pass.n, h.sh.ld_local);
+  if (h.sh.ld_local) ENSURE(c, c->partial, (size_t)rows * h.sh.ld_local * 4);
+  *out = Partial{c->partial.as<uint32_t>(), rows};
+  launch_score(points_of(c), h, *out, ev, c->pass.dv, p->score_mode, c->tn, c->stream);
   return SC_OK;
 }
 
@@ -730,41 +738,40 @@ static int run_stage_c(sc_ctx* c, uint64_t* d_key, sc_stats* stats) {
   sh.n_local = shard_local_count(sh.T_eff, sh.block, sh.rank, sh.world);
   sh.ld_local = (uint32_t)(((uint64_t)sh.n_local + 255u) / 256u * 256u);  // T <= 2^32 - 256 (check_params)
   c->pass.sh = sh;
+  c->pass.filter_on = false; c->pass.filter_mode = 0;  // (nothing to score: no filter; else decide_filter says)
   if (sh.n_local) {
     ENSURE(c, c->rt, (size_t)12 * sh.ld_local * 4);
     ENSURE(c, c->cnt, (size_t)sh.ld_local * 4);
     SC_TRY(decide_filter(c, p, sh));
-    const bool filter = c->pass.filter_on;
-    const bool aos = filter;  // (the exact pass reads 12 consecutive floats per hypothesis)
-    if (aos) ENSURE(c, c->rt_aos, (size_t)12 * sh.ld_local * 4);
+    if (c->pass.filter_on) { ENSURE(c, c->rt_aos, (size_t)12 * sh.ld_local * 4); SC_TRY(ensure_filter(c)); }  // (rt_aos: the exact pass reads 12 consecutive floats per hypothesis)
+  }
+  const Hyps h = hyps_of(c);  // once, behind the ENSUREs of rt, cnt and rt_aos: every launch of the stage takes this one
+  if (sh.n_local) {
+    const TriSource ts = tri_source_of(c);
     FilterTileJob job;
-    if (filter) SC_TRY(filter_job(c, sh, &job));
-    // host-free call: the selection may turn out shorter than the T this launch was sized for (then the call is repeated);
-    // its real length is what the select left in sel.want
-    const uint64_t* t_eff_dev = (c->pass.mode.host_free || c->pass.form.est_active) ? &c->ctl.as<ControlBlock>()->sel.want : nullptr;
-    if (filter && c->pass.fx_plan.mode == 2 && !c->pass.ref_done)  // the Gram filter's reference frame, where the counting pass did not carry the vote: among 64 hypotheses of the selection
-      launch_gram_ref(points_of(c), tri_source_of(c), sh, nullptr, t_eff_dev, c->fx_mx.as<uint32_t>(), c->pass.dv.tau2, c->tn,
-                      c->fx_frame.p, c->stream);
-    launch_kabsch(points_of(c), tri_source_of(c), sh, c->rt.as<float>(), aos ? c->rt_aos.as<float>() : nullptr,
-                  filter ? &job : nullptr, c->stream, t_eff_dev);
-  } else {
-    c->pass.filter_on = false; c->pass.filter_mode = 0;
+    if (c->pass.filter_on) {
+      const FilterBufs fb = filter_of(c);
+      job = filter_tile_job(fb, sh.ld_local, c->pass.dv.tau2);
+      if (fb.plan.mode == 2 && !c->pass.ref_done)  // the Gram filter's reference frame, where the counting pass did not carry the vote: among 64 hypotheses of the selection
+        launch_gram_ref(points_of(c), &ts, h, fb, c->pass.dv.tau2, c->tn, c->stream);
+    }
+    launch_kabsch(points_of(c), ts, h, c->pass.filter_on ? &job : nullptr, c->stream);
   }
   // SC_FLAG_TIMING_HOT: the score stage's duration from the dispatch packets of its own kernels (no record on the stream:
   // the two records of a bracket opened ~4.5 us gaps before and after the stage — 3 % of a C2 step)
   const bool hot_ext = c->pass.timing_hot && sh.n_local != 0;
   c->pass.hot_ext = hot_ext;
   if (!hot_ext) SC_TRY(rec(c, 4));
-  uint32_t score_rows = 0;
-  SC_TRY(run_score(c, p, sh, &score_rows, true, hot_ext ? c->ev[4] : nullptr, hot_ext ? c->ev[5] : nullptr, hot_ext ? c->ev[11] : nullptr));
+  Partial partial{};
+  SC_TRY(run_score(c, p, h, &partial, true, hot_ext ? Stamps{c->ev[4], c->ev[5], c->ev[11]} : Stamps{}));
   if (!hot_ext) SC_TRY(rec(c, 5));
   ENSURE(c, c->amx_pairs, argmax_scratch_bytes(sh.ld_local));
   // the winner pair: reduced by the launch for a caller that gathers it; left as one pair per workgroup for this context's own
   // finalize step (sc_register*: d_key is the context's own word), whose workgroups reduce them themselves
   const bool own_pairs = d_key == c->key.as<uint64_t>() && sh.n_local != 0;
   c->pass.amx_blocks = own_pairs ? argmax_blocks(sh.ld_local) : 0u;
-  launch_argmax(sh, c->partial.as<uint32_t>(), score_rows, c->pass.T_eff ? c->sel_key.as<uint32_t>() : nullptr,
-                c->cnt.as<uint32_t>(), c->amx_pairs.as<uint64_t>(), &c->ctl.as<ControlBlock>()->amx_ticket, own_pairs ? nullptr : d_key, c->stream);
+  launch_argmax(sh, partial, ArgmaxOut{c->pass.T_eff ? c->sel_key.as<uint32_t>() : nullptr, c->cnt.as<uint32_t>(), c->amx_pairs.as<uint64_t>(),
+                                       &c->ctl.as<ControlBlock>()->amx_ticket, own_pairs ? nullptr : d_key}, c->stream);
   SC_TRY(rec(c, 6));
   HIPCHK(c, hipGetLastError());
   c->pass.have_hyp = true;
@@ -860,7 +867,7 @@ int sc_shard_compat_device(sc_ctx* c, const float* d_src, const float* d_tgt, in
   c->pass.bits_cur = static_cast<uint64_t*>(d_bits_all);
   c->pass.sharded_ab = true;
   // world == 1: [0, n) -> the symmetric tiles; else the one-sided row-block form, bit rows at their global index
-  launch_compat(points_of(c), c->pass.dv, dense ? c->S.as<float>() : nullptr, c->pass.bits_cur, r0, r1, c->tn, c->stream);
+  launch_compat(points_of(c), CompatOpts{}, c->pass.dv, dense ? c->S.as<float>() : nullptr, c->pass.bits_cur, r0, r1, c->tn, c->stream);
   SC_TRY(rec(c, 2));
   HIPCHK(c, hipGetLastError());
   c->pass.shard_phase = 1;

@@ -55,10 +55,9 @@ static int finalize_enqueue(sc_ctx* c, const uint64_t* d_keys, int n_pairs, floa
   DeferredPub dp{c->edge_off.as<uint64_t>() + c->pass.n, c->toff.as<uint64_t>() + c->pass.E, c->fx_mx.as<uint32_t>(),
                  reinterpret_cast<unsigned long long*>(c->pinned), (c->n_fast_ok & 63u) == 63u ? 1 : 0};
   if (d_keys == c->key.as<uint64_t>() && n_pairs == 1 && c->pass.amx_blocks) { d_keys = c->amx_pairs.as<uint64_t>(); n_pairs = (int)c->pass.amx_blocks; }
-  launch_finalize(points_of(c), tri_source_of(c), c->pass.sh, c->pass.sh.n_local ? c->rt.as<float>() : nullptr,
-                  c->pass.T_eff ? c->sel_key.as<uint32_t>() : nullptr, c->pass.T_eff, d_keys, n_pairs,
-                  ctl->key2, c->pass.dv.tau2, d_Rt, d_mask, &ctl->fin_word, &c->pinned[HW_WINNER], c->stream,
-                  c->pass.mode.host_free ? &dp : nullptr);
+  launch_finalize(points_of(c), tri_source_of(c), hyps_of(c), WinnerIn{c->pass.T_eff ? c->sel_key.as<uint32_t>() : nullptr, c->pass.T_eff, d_keys, n_pairs},
+                  WinnerOut{d_Rt, d_mask, &c->pinned[HW_WINNER]}, c->pass.dv.tau2, ctl->key2, &ctl->fin_word,
+                  c->pass.mode.host_free ? &dp : nullptr, c->stream);
   if (c->pass.refine) {  // fp64 least-squares refit over the winner's inliers (mask unchanged)
     ENSURE(c, c->refine_tmp, refine_scratch_bytes(c->pass.n));
     launch_refine(points_of(c), d_mask, ctl->key2, c->refine_tmp.as<double>(), d_Rt, c->stream);

@@ -133,12 +133,13 @@ int sc_score_host(sc_ctx* c, const float* src, const float* tgt, int64_t n, cons
   if (!c->tn.filter_blind) SC_TRY(wait_word(c, HW_COORD_MAX));
   c->pass.sh = sh;
   SC_TRY(decide_filter(c, p, sh));
-  uint32_t score_rows = 0;
-  SC_TRY(run_score(c, p, sh, &score_rows, false));
+  const Hyps h{sh, c->rt.as<float>(), c->rt_aos.as<float>(), nullptr};  // (behind the ENSUREs above; decide_filter touches neither array)
+  Partial partial{};
+  SC_TRY(run_score(c, p, h, &partial, false, Stamps{}));
   ENSURE(c, c->cnt, (size_t)(sh.ld_local ? sh.ld_local : 256) * 4);
   ENSURE(c, c->amx_pairs, argmax_scratch_bytes(sh.ld_local));
-  launch_argmax(sh, c->partial.as<uint32_t>(), score_rows, nullptr, c->cnt.as<uint32_t>(), c->amx_pairs.as<uint64_t>(),
-                &c->ctl.as<ControlBlock>()->amx_ticket, c->key.as<uint64_t>(), c->stream);  // positions in Rt ARE the rank indices here: single-stage key
+  launch_argmax(sh, partial, ArgmaxOut{nullptr, c->cnt.as<uint32_t>(), c->amx_pairs.as<uint64_t>(), &c->ctl.as<ControlBlock>()->amx_ticket,
+                                       c->key.as<uint64_t>()}, c->stream);  // positions in Rt ARE the rank indices here: single-stage key
   SC_TRY(check_flag(c));
   if (cnt && n_hyp) HIPCHK(c, hipMemcpyAsync(cnt, c->cnt.p, (size_t)n_hyp * 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(key, c->key.p, 8, hipMemcpyDeviceToHost, c->stream));

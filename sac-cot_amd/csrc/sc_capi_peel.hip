@@ -27,6 +27,7 @@ static int peel_round(sc_ctx* c, float* d_Rt, uint8_t* d_mask, sc_stats* stats) 
     HIPCHK(c, hipMemsetAsync(c->peel_words.p, 0, c->peel_words.cap, st));
   }
   PeelWords* words = c->peel_words.as<PeelWords>();
+  const Hyps h{sh, c->rt.as<float>(), nullptr, nullptr};  // (the scored frame's: no call of a round grows c->rt)
   SC_TRY(rec(c, 0));
   LbArgs lb;
   SC_TRY(lb_next(c, (size_t)peel_compact_tiles(ps.n) * 8, 2, 0, &lb));
@@ -34,8 +35,8 @@ static int peel_round(sc_ctx* c, float* d_Rt, uint8_t* d_mask, sc_stats* stats) 
   // popcount(mask) there); in the truncated modes the compaction hands it over (one word, polled)
   const bool read_alive = p->score_mode != SC_SCORE_COUNT;
   if (read_alive) arm_word(c, HW_PEEL_ALIVE);
-  launch_peel_compact(points_of(c), c->rt.as<float>(), sh.ld_local, ps.peel_prev, ps.dv.tau2, ps.peel_round == 0,
-                      c->peel_claimed.as<uint8_t>(), c->peel_planes.as<float>(), words, lb, read_alive ? &c->pinned[HW_PEEL_ALIVE] : nullptr, st);
+  launch_peel_compact(points_of(c), h, PeelSets{c->peel_claimed.as<uint8_t>(), c->peel_planes.as<float>(), read_alive ? &c->pinned[HW_PEEL_ALIVE] : nullptr},
+                      ps.peel_prev, ps.dv.tau2, ps.peel_round == 0, words, lb, st);
   ps.peel_prev = 0xFFFFFFFFu;  // folded in
   SC_TRY(rec(c, 1));
   uint64_t n_alive = n - ps.peel_claimed;
@@ -49,18 +50,19 @@ static int peel_round(sc_ctx* c, float* d_Rt, uint8_t* d_mask, sc_stats* stats) 
     const Points alive{c->peel_planes.as<float>(), (int)n_alive, ps.ld};  // (the six planes only: the plain kernel reads nothing else)
     const uint32_t rows = score_chunks((int)n_alive, sh.ld_local);
     ENSURE(c, c->partial, (size_t)rows * sh.ld_local * 4);
-    launch_score(alive, c->rt.as<float>(), nullptr, sh, ps.dv, p->score_mode, c->partial.as<uint32_t>(), c->tn, st);
+    const Partial partial{c->partial.as<uint32_t>(), rows};
+    launch_score(alive, h, partial, Stamps{}, ps.dv, p->score_mode, c->tn, st);
     SC_TRY(rec(c, 2));
     ENSURE(c, c->peel_cnt, (size_t)sh.ld_local * 4);  // (not c->cnt: the frame's scores stay for sc_polish)
     ENSURE(c, c->amx_pairs, argmax_scratch_bytes(sh.ld_local));
-    launch_argmax(sh, c->partial.as<uint32_t>(), rows, c->sel_key.as<uint32_t>(), c->peel_cnt.as<uint32_t>(), c->amx_pairs.as<uint64_t>(),
-                  &c->ctl.as<ControlBlock>()->amx_ticket, nullptr, st);  // (one pair per workgroup: the winner kernel reduces them)
+    launch_argmax(sh, partial, ArgmaxOut{c->sel_key.as<uint32_t>(), c->peel_cnt.as<uint32_t>(), c->amx_pairs.as<uint64_t>(),
+                                         &c->ctl.as<ControlBlock>()->amx_ticket, nullptr}, st);  // (one pair per workgroup: the winner kernel reduces them)
     npairs = (int)argmax_blocks(sh.ld_local);
   } else SC_TRY(rec(c, 2));
   SC_TRY(rec(c, 3));
   arm_word(c, HW_WINNER);
-  launch_peel_winner(points_of(c), c->peel_claimed.as<uint8_t>(), c->rt.as<float>(), sh.ld_local, c->sel_key.as<uint32_t>(), ps.T_eff,
-                     c->amx_pairs.as<uint64_t>(), npairs, ps.dv.tau2, d_Rt, d_mask, words, &c->pinned[HW_WINNER], st);
+  launch_peel_winner(points_of(c), h, WinnerIn{c->sel_key.as<uint32_t>(), ps.T_eff, c->amx_pairs.as<uint64_t>(), npairs},
+                     WinnerOut{d_Rt, d_mask, &c->pinned[HW_WINNER]}, c->peel_claimed.as<uint8_t>(), ps.dv.tau2, words, st);
   if (ps.refine) {  // fp64 refit over mask_r, in refine_kernel's canonical order over the ORIGINAL indices (the mask stays the fp32 winner's)
     ENSURE(c, c->refine_tmp, refine_scratch_bytes(ps.n));
     launch_refine(points_of(c), d_mask, reinterpret_cast<const uint64_t*>(words->key2), c->refine_tmp.as<double>(), d_Rt, st);

@@ -431,7 +431,7 @@ static int count_triangles(sc_ctx* c, const sc_params* p, SelectArgs& a) {
   GramRefJob ref{};
   if (c->pass.ref_cand_n) {  // (run_sample) one extra workgroup votes for stage C2's reference frame under this launch
     SC_TRY(ensure_frame(c));
-    ref = gram_ref_job(points_of(c), c->fx_mx.as<uint32_t>(), c->pass.dv.tau2, c->tn, c->fx_frame.p);
+    ref = gram_ref_job(points_of(c), filter_of(c), c->pass.dv.tau2, c->tn);  // (reads the statistics and the frame only: the plan and the other buffers are stage C's to make)
     ref.src.cand = c->ref_cand.as<uint4>(); ref.src.n_cand = c->pass.ref_cand_n; ref.src.cand_slot = c->ctl.as<ControlBlock>()->ref_slot;
     c->pass.ref_done = true;
   }

@@ -119,13 +119,11 @@ __global__ __launch_bounds__(256) void stage_points_kernel(const float* __restri
   aos[2 * (size_t)m + 1] = make_float4(v[4], v[5], 0.0f, 0.0f);
 }
 
-void launch_stage_points(const float* d_src, const float* d_tgt, int n, int ld, int layout, float* planes,
-                         uint32_t* bad_flag, uint32_t* zero, uint32_t zero_words, uint32_t* coord_max, uint32_t* coord_part,
-                         uint32_t* mx_ticket, uint64_t* host_max, uint64_t* host_box, hipStream_t st, uint32_t* zero2,
-                         uint32_t zero2_words) {
+void launch_stage_points(const CoordStatsOut& cs, const ZeroSpan (&zero)[2], const float* d_src, const float* d_tgt, int n, int ld,
+                         int layout, float* planes, uint32_t* bad_flag, hipStream_t st) {
   hipLaunchKernelGGL(stage_points_kernel, dim3((ld + 255) / 256), dim3(256), 0, st, d_src, d_tgt, n, ld, layout,
-                     planes, bad_flag, zero, zero_words, coord_max, coord_part, mx_ticket, host_max, host_box, zero2,
-                     zero2_words);
+                     planes, bad_flag, zero[0].p, zero[0].words, cs.coord_max, cs.coord_part, cs.mx_ticket, cs.host_max, cs.host_box,
+                     zero[1].p, zero[1].words);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -657,10 +655,9 @@ std::vector<uint32_t> compat_wg_map(int W) {
   return map;
 }
 
-void launch_compat(const Points& pts, const Derived& dv, float* S, uint64_t* bits, int row0, int row1, const Tuning& tn,
-                   hipStream_t st, uint32_t* degp, const uint32_t* wg_map, uint32_t wg_map_len, const uint32_t* stat_part,
-                   uint32_t* stat_out) {
-  const StatsJob sj{stat_part, stat_part ? (uint32_t)((pts.ld + 255) / 256) : 0u, stat_out};
+void launch_compat(const Points& pts, const CompatOpts& o, const Derived& dv, float* S, uint64_t* bits, int row0, int row1,
+                   const Tuning& tn, hipStream_t st) {
+  const StatsJob sj{o.stat_part, o.stat_part ? (uint32_t)((pts.ld + 255) / 256) : 0u, o.stat_out};
   const int W = pts.ld >> 6;
   const int two_phase = tn.compat_one_phase ? 0 : 1;  // the one-phase interior form stays for A/B and parity
   const bool rect = !(row0 == 0 && row1 >= pts.n);
@@ -674,7 +671,7 @@ void launch_compat(const Points& pts, const Derived& dv, float* S, uint64_t* bit
   if (tn.compat_store_mode & 1u) mode = 1;
   if (tn.compat_store_mode & 4u) mode = 0;
   mode |= (int)(tn.compat_store_mode & 2u);
-#define SC_COMPAT_ARGS pts.planes, pts.n, pts.ld, dv.d_thr, dv.min_len, dv.neg_inv2sig2, S, bits, n_tiles, two_phase, row0, row1, mode, degp, map_arg, sj
+#define SC_COMPAT_ARGS pts.planes, pts.n, pts.ld, dv.d_thr, dv.min_len, dv.neg_inv2sig2, S, bits, n_tiles, two_phase, row0, row1, mode, o.degp, map_arg, sj
   const uint32_t* map_arg = nullptr;  // (only the symmetric 16- and 32-row forms take the map: there a workgroup is a 64 x 64 block)
   if (rect) {
     if (row1 <= row0) return;
@@ -694,8 +691,8 @@ void launch_compat(const Points& pts, const Derived& dv, float* S, uint64_t* bit
   const int tr = tn.compat_rows == 64 ? 64 : (tn.compat_rows == 32 ? 32 : (tn.compat_rows == 16 ? 16 : (pts.n >= 10000 ? 32 : 16)));
   if (tr == 32) {
     const int n_tiles = 2 * W * (W + 1) / 2;
-    map_arg = wg_map;
-    const unsigned grid = wg_map ? wg_map_len : (unsigned)((n_tiles + 1) / 2);
+    map_arg = o.wg_map;
+    const unsigned grid = o.wg_map ? o.wg_map_len : (unsigned)((n_tiles + 1) / 2);
     if (S) hipLaunchKernelGGL((compat_tiles_kernel<32, 2, true, false>), dim3(grid), dim3(128), 0, st, SC_COMPAT_ARGS);
     else hipLaunchKernelGGL((compat_tiles_kernel<32, 2, false, false>), dim3(grid), dim3(128), 0, st, SC_COMPAT_ARGS);
   } else if (tr == 64) {
@@ -704,8 +701,8 @@ void launch_compat(const Points& pts, const Derived& dv, float* S, uint64_t* bit
     else hipLaunchKernelGGL((compat_tiles_kernel<64, 1, false, false>), dim3(n_tiles), dim3(64), 0, st, SC_COMPAT_ARGS);
   } else {
     const int n_tiles = 4 * W * (W + 1) / 2;
-    map_arg = wg_map;
-    const unsigned grid = wg_map ? wg_map_len : (unsigned)((n_tiles + 3) / 4);
+    map_arg = o.wg_map;
+    const unsigned grid = o.wg_map ? o.wg_map_len : (unsigned)((n_tiles + 3) / 4);
     if (S) hipLaunchKernelGGL((compat_tiles_kernel<16, 4, true, false>), dim3(grid), dim3(256), 0, st, SC_COMPAT_ARGS);
     else hipLaunchKernelGGL((compat_tiles_kernel<16, 4, false, false>), dim3(grid), dim3(256), 0, st, SC_COMPAT_ARGS);
   }

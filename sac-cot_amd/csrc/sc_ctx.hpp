@@ -238,7 +238,7 @@ struct sc_ctx : sc::Workspace {  // (the workspace buffers are direct members to
   sc::Tuning tn;  // defaults unless sc_set_debug() changed them; the library reads no environment variable
   // decoupled look-back launches (single-pass scan, fused compaction): their state area and its epoch
   uint32_t lb_epoch = 0; void* lb_zeroed = nullptr; size_t lb_zeroed_cap = 0;
-  // run-time probe of the matrix pipe's accumulation model (sc_score.hip gram_guard): 0 not run, 1 holds, 2 violated
+  // run-time probe of the matrix pipe's accumulation model (sc_gram_guard.hip): 0 not run, 1 holds, 2 violated
   int gram_guard = 0; float gram_guard_worst = 0.f;
 
   // ---- history: what a completed call leaves for the next one (note_completed and apply_verdict, sc_capi_frame.hip, write it;
@@ -582,7 +582,9 @@ constexpr int STAGE_EV[7][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 4}, {4, 5}, {5, 6}, 
 SC_LOCAL float ev_us_raw(sc_ctx* c, int a, int b);
 
 int decide_filter(sc_ctx* c, const sc_params* p, const Shard& sh);
-int run_score(sc_ctx* c, const sc_params* p, const Shard& sh, uint32_t* rows, bool tile_done, hipEvent_t ev0 = nullptr,
-              hipEvent_t ev1 = nullptr, hipEvent_t ev_mid = nullptr);
+// the views of the context's stage-C arrays (sc_kernels.hpp; what each is taken behind is said at its definition)
+SC_LOCAL Hyps hyps_of(const sc_ctx* c);
+SC_LOCAL FilterBufs filter_of(const sc_ctx* c);
+int run_score(sc_ctx* c, const sc_params* p, const Hyps& h, Partial* out, bool tile_done, const Stamps& ev);
 
 }  // namespace sc

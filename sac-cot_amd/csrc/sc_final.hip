@@ -109,13 +109,12 @@ __global__ __launch_bounds__(256) void mask_kernel(const float* __restrict__ pla
   mask[m] = winner_inlier(Rt12, key == nullptr || *key != 0ull, load_corr(planes, ld, m), tau2) ? 1 : 0;
 }
 
-void launch_finalize(const Points& pts, const TriSource& ts, const Shard& sh, const float* RtSoA,
-                     const uint32_t* sel_key, uint32_t T, const uint64_t* key2, int npairs, uint64_t* key_out, float tau2, float* Rt12, uint8_t* mask,
-                     unsigned long long* fin_word, uint64_t* host_out, hipStream_t st, const DeferredPub* dp) {
-  hipLaunchKernelGGL(finalize_kernel, dim3(winner_blocks(pts.n, T)), dim3(256), 0, st, pts.planes, pts.n, pts.ld, ts, sh, RtSoA, sel_key, T,
-                     reinterpret_cast<const unsigned long long*>(key2), npairs,
-                     reinterpret_cast<unsigned long long*>(key_out), tau2, Rt12, mask, fin_word,
-                     reinterpret_cast<unsigned long long*>(host_out), dp ? *dp : DeferredPub{nullptr, nullptr, nullptr, nullptr, 0});
+void launch_finalize(const Points& pts, const TriSource& ts, const Hyps& h, const WinnerIn& in, const WinnerOut& out, float tau2,
+                     uint64_t* key_out, unsigned long long* fin_word, const DeferredPub* dp, hipStream_t st) {
+  hipLaunchKernelGGL(finalize_kernel, dim3(winner_blocks(pts.n, in.T)), dim3(256), 0, st, pts.planes, pts.n, pts.ld, ts, h.sh,
+                     h.soa, in.sel_key, in.T, reinterpret_cast<const unsigned long long*>(in.keys), in.npairs,
+                     reinterpret_cast<unsigned long long*>(key_out), tau2, out.Rt12, out.mask, fin_word,
+                     reinterpret_cast<unsigned long long*>(out.host_out), dp ? *dp : DeferredPub{nullptr, nullptr, nullptr, nullptr, 0});
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 // sc_gramref.hpp — the reference frame of the Gram filter (stage C2): its layout and the workgroup that votes for it.
-// Shared by sc_score.hip (which makes tile and coefficients in this frame, and votes in a launch of its own where nothing else
+// Shared by sc_kabsch.hip (which makes tile and coefficients in this frame, and votes in a launch of its own where nothing else
 // can) and sc_tri.hip (whose counting pass carries the vote as an extra workgroup on the hot path).  Device code only.
 #pragma once
 #include <cstddef>

@@ -52,7 +52,7 @@ struct Tuning {
   uint32_t filter_splits = 0;      // grid.y of the filter (0: by size)
   uint32_t filter_queue_cap = 0;   // entries of the filter's global queue (0: by size; tests force overflows with a small one)
   uint32_t filter_lds_queue = 0;   // entries of a wave's LDS queue, 64 .. 256 (0: 256)
-  uint32_t filter_variant = 0;     // body of the filter kernel (sc_score.hip): 0 default, bit-identical scheduling variants, >= 16 timing-only ablations
+  uint32_t filter_variant = 0;     // body of the filter kernel (sc_filter.hip): 0 default, bit-identical scheduling variants, >= 16 timing-only ablations
   uint32_t gram_kappa_q4 = 0;      // the Gram filter's cut: hypotheses whose reach stays under (value / 16) tau' count as NEAR the reference (0 = GX_KAPPA = 8; 1 = practically no cut)
   bool gram_ref_late = false;      // the Gram filter's reference frame is voted after the selection, in a launch of its own (what every path but the hot one does anyway), instead of under the counting pass
   bool no_fast = false;            // sc_register_device never enqueues host-free (always waits for stage B's two counts)
@@ -90,7 +90,7 @@ struct Points {
 // ---- input staging -----------------------------------------------------------------------------
 // user layout (AoS n x 3 or SoA 3 x n) -> padded planes; sets *bad_flag != 0 when a value is not finite.
 // bad_flag may be host-pinned memory: it is only touched (atomicOr) when a non-finite value is found.
-// zero / zero_words: a buffer (the per-call control block) the kernel clears on the way — saves a memset launch.
+// zero[0]: a buffer (the per-call control block) the kernel clears on the way — saves a memset launch; zero[1]: a second one.
 // coord_max (optional, 2 x u32): atomicMax of the bit patterns of max |src coordinate| and max |tgt coordinate|; with it:
 // coord_max_next (the pair the NEXT call uses: cleared by the last block), mx_ticket (a zeroed u32, left zero; nullptr: the rows
 // of coord_part stay unreduced — launch_compat's stat_part) and
@@ -102,10 +102,11 @@ struct Points {
 // coordinate, written before host_max.
 constexpr int FX_MX_WORDS = 16;
 inline size_t stage_part_words(int ld) { return (size_t)((ld + 255) / 256) * 16; }
-void launch_stage_points(const float* d_src, const float* d_tgt, int n, int ld, int layout, float* planes,
-                         uint32_t* bad_flag, uint32_t* zero, uint32_t zero_words, uint32_t* coord_max, uint32_t* coord_part,
-                         uint32_t* mx_ticket, uint64_t* host_max, uint64_t* host_box, hipStream_t st,
-                         uint32_t* zero2 = nullptr, uint32_t zero2_words = 0);  // zero2: a second buffer cleared on the way
+// The launch's views (host-side; stage_inputs fills them): where the coordinate statistics go, and the buffers cleared on the way.
+struct CoordStatsOut { uint32_t* coord_max; uint32_t* coord_part; uint32_t* mx_ticket; uint64_t* host_max; uint64_t* host_box; };
+struct ZeroSpan { uint32_t* p; uint32_t words; };
+void launch_stage_points(const CoordStatsOut& cs, const ZeroSpan (&zero)[2], const float* d_src, const float* d_tgt, int n, int ld,
+                         int layout, float* planes, uint32_t* bad_flag, hipStream_t st);
 // order-preserving map float -> u32 (all finite floats and infinities; 0 is below every float) and back
 __host__ __device__ inline uint32_t float_key(float f) {
   union { float f; uint32_t u; } x; x.f = f;
@@ -128,9 +129,9 @@ bool filter_in_range(uint64_t host_max, float tau2);
 // device — the launch then has wg_map_len workgroups.
 // stat_part / stat_out (optional): the staging launch was given no ticket (mx_ticket == nullptr) and left its per-workgroup rows
 // of coordinate statistics unreduced: one wave of this launch reduces them into the FX_MX_WORDS words.
-void launch_compat(const Points& pts, const Derived& dv, float* S, uint64_t* bits, int row0, int row1, const Tuning& tn,
-                   hipStream_t st, uint32_t* degp = nullptr, const uint32_t* wg_map = nullptr, uint32_t wg_map_len = 0,
-                   const uint32_t* stat_part = nullptr, uint32_t* stat_out = nullptr);
+struct CompatOpts { uint32_t* degp; const uint32_t* wg_map; uint32_t wg_map_len; const uint32_t* stat_part; uint32_t* stat_out; };  // (CompatOpts{}: none)
+void launch_compat(const Points& pts, const CompatOpts& o, const Derived& dv, float* S, uint64_t* bits, int row0, int row1,
+                   const Tuning& tn, hipStream_t st);
 // deg[i] = edges of i; degp[i] = edges (i,j) with j > i; wpre: n x (ld/64) u32, set bits of row i in words [0,w).
 // zero_rows (optional): an n x W u64 matrix cleared on the way (the pruned bit matrix of stage B).
 // rowcost (optional, n u32): per-row estimate of stage B's work (see row_stats_kernel), for launch_shard_split.
@@ -506,30 +507,39 @@ struct TriSource {
   uint32_t lim_vertex, lim_edge;
   uint64_t lim_ord;
 };
-// C1: RtSoA[c * ld_local + l], c = 0..11, for the local hypotheses of the shard (global rank index derived).
-// RtAoS (optional): also 12 consecutive floats per local hypothesis (ld_local x 12), for the lane = correspondence kernel
+// The context's stage-C arrays as the launches see them — Hyps, FilterBufs, Partial, ArgmaxOut, and the Stamps of a timed launch:
+// plain host-side views, as stage B's are, each filled by one accessor of the host driver (sc_capi.hip: hyps_of, filter_of; run_score
+// fills the Partial).  A view is taken after the last ENSURE of every buffer it names and is not kept across one.
+//
+// This rank's hypotheses.  soa: RtSoA[c * ld_local + l], c = 0..11, for the local hypotheses of the shard (global rank index derived).
+// aos (null where no exact pass reads it): also 12 consecutive floats per local hypothesis (ld_local x 12), for the lane =
+// correspondence kernel.
+// t_eff_dev (null on waited, certified calls; device u64): the true length of the selection when the host launched with sh.T_eff =
+// the requested T before it knew (host-free path): positions at or beyond it are treated as padding and never looked up
+struct Hyps { Shard sh; float* soa; float* aos; const uint64_t* t_eff_dev; };
+// What C2 leaves for the arg-max: rows x ld_local u32 counts
+struct Partial { uint32_t* counts; uint32_t rows; };
+// first / last (both or neither): start and stop timestamps taken from the dispatch packets of the stage's first and last kernel
+// (hipExtLaunchKernelGGL) — no extra packet on the stream, unlike a bracket of hipEventRecord calls (~4.5 us each on this part).
+// mid (optional): stop timestamp of the FILTER kernel's own dispatch (first .. mid = that kernel alone).  Stamps{}: plain launches.
+struct Stamps { hipEvent_t first, last, mid; };
+// C1 writes h.soa and, where given, h.aos.
 // tile_job (optional): the filter's tile kernel rides in the same launch as extra workgroups (C1 alone leaves most of the
 // chip idle: T / 256 workgroups), which saves a launch on the critical path.
 struct FilterTileJob;
-// t_eff_dev (optional, device u64): the true length of the selection when the host launched with sh.T_eff = the requested
-// T before it knew (host-free path): positions at or beyond it are treated as padding and never looked up
-void launch_kabsch(const Points& pts, const TriSource& ts, const Shard& sh, float* RtSoA, float* RtAoS,
-                   const FilterTileJob* tile_job, hipStream_t st, const uint64_t* t_eff_dev = nullptr);
+void launch_kabsch(const Points& pts, const TriSource& ts, const Hyps& h, const FilterTileJob* tile_job, hipStream_t st);
 // C1 on an explicit triangle list to AoS T x 12 (stage hook)
 void launch_kabsch_aos(const Points& pts, const uint32_t* tri, uint32_t T, float* Rt, hipStream_t st);
 // AoS T x 12 -> SoA planes (stage hook for sc_score_host)
 void launch_rt_to_soa(const float* Rt, uint32_t T, uint32_t ld_local, float* RtSoA, hipStream_t st);
-// C2: inlier counts.  partial: n_chunks * ld_local u32 scratch.
+// C2: inlier counts.  out.counts: n_chunks * ld_local u32 scratch.
 // The plain C2 kernel: lane = hypothesis with the points in LDS (every score mode, the matrix-pipe share).
-// score_chunks: point chunks that launch will use (rows of `partial`).
+// score_chunks: point chunks that launch will use (out.rows).
 uint32_t score_chunks(int n, uint32_t ld_local);
 // score_mode: 0 inlier count, 1 truncated squared residual, 2 truncated absolute residual (include/saccot.h)
-// ev0 / ev1 (both or neither): start and stop timestamps taken from the dispatch packets of the stage's first and last kernel
-// (hipExtLaunchKernelGGL) — no extra packet on the stream, unlike a bracket of hipEventRecord calls (~4.5 us each on this part)
-void launch_score(const Points& pts, const float* RtSoA, const float* RtAoS, const Shard& sh, const Derived& dv,
-                  int score_mode, uint32_t* partial, const Tuning& tn, hipStream_t st, hipEvent_t ev0 = nullptr,
-                  hipEvent_t ev1 = nullptr);
-// C2, inlier count, by filter + exact fix-up (sc_score.hip): which calls use it, what it needs, and its two launches.
+void launch_score(const Points& pts, const Hyps& h, const Partial& out, const Stamps& ev, const Derived& dv, int score_mode,
+                  const Tuning& tn, hipStream_t st);
+// C2, inlier count, by filter + exact fix-up (sc_filter.hip): which calls use it, what it needs, and its two launches.
 // The tile (fp16 image of the correspondences) depends on the points only: launch_filter_tile runs once per call, any
 // time after launch_stage_points (whose atomicMax fills mx_cur); mx_cur / mx_next are two u32 pairs that alternate
 // from call to call (the tile kernel clears the next call's).  partial: fp.splits rows of ld_local counts.
@@ -545,8 +555,11 @@ struct FilterPlan {
   uint32_t windows, splits, n_waves, rows, queue_cap;
   size_t tile_bytes, state_bytes, coef_bytes;  // coef_bytes: the Gram filter's per-hypothesis coefficients and its two permutations (0 for the linear one)
 };
+// The filter's plan and buffers: tile (plan.tile_bytes), state (plan.state_bytes), coef (plan.coef_bytes; Gram), frame (gram_frame_bytes();
+// Gram) and mx, the FX_MX_WORDS coordinate statistics the staging kernel wrote.
+struct FilterBufs { FilterPlan plan; void* tile; void* state; void* coef; void* frame; const uint32_t* mx; };
 // Gram filter: what its waves load instead of computing it (made once per call: launch_kabsch's threads, or launch_gram_coef).
-// Rows are PERMUTED: hypotheses near the call's reference frame first (sc_score.hip, "the cut"); so are the tile's rows.
+// Rows are PERMUTED: hypotheses near the call's reference frame first (sc_filter.hip, "the cut"); so are the tile's rows.
 struct GramFrame;
 struct GramCoef {
   void* A;            // 64 bytes per row: fp16 halves of its 16 coefficients
@@ -568,27 +581,23 @@ struct FilterTileJob {  // what the tile kernel needs (filter_tile_job fills it)
   uint32_t rows; const uint32_t* mx_cur; uint32_t* mx_next; void* tile; void* info; uint32_t* zero; uint32_t zero_words; uint32_t mode;
   GramCoef coef; float tau2;  // mode 2: the Kabsch threads of the same launch also write their hypotheses' coefficients
 };
-FilterTileJob filter_tile_job(const FilterPlan& fp, const uint32_t* mx_cur, uint32_t* mx_next, void* tile, void* state,
-                              void* coef, uint32_t ld_local, float tau2, void* frame);
+FilterTileJob filter_tile_job(const FilterBufs& fb, uint32_t ld_local, float tau2);  // (mx_cur = fb.mx; mx_next stays null)
 // Gram filter: the call's reference frame (sc_gramref.hpp; `frame`: gram_frame_bytes() of device memory, per context).  One
 // workgroup votes for it among 64 hypotheses and clears the class counters — BEFORE the tile and the coefficients are made.  In a
-// launch of its own (launch_gram_ref: RtSoA = the hypotheses if they exist already — stage hook —, else null: they are solved
-// from the selection `ts`), or, on the hot path, as an extra workgroup of the counting pass (launch_tri_count_events, `ref`) fed
-// by the candidate triangles the estimating sample leaves behind (launch_sample_estimate, `cand`).
+// launch of its own (launch_gram_ref: ts == nullptr: the hypotheses exist already — stage hook — and are read from h.soa; else
+// they are solved from the selection `*ts`), or, on the hot path, as an extra workgroup of the counting pass
+// (launch_tri_count_events, `ref`) fed by the candidate triangles the estimating sample leaves behind (launch_sample_estimate, `cand`).
 size_t gram_frame_bytes();
 struct GramRefJob;
-GramRefJob gram_ref_job(const Points& pts, const uint32_t* mx, float tau2, const Tuning& tn, void* frame);  // (source left empty)
-void launch_gram_ref(const Points& pts, const TriSource& ts, const Shard& sh, const float* RtSoA, const uint64_t* t_eff_dev,
-                     const uint32_t* mx, float tau2, const Tuning& tn, void* frame, hipStream_t st);
+GramRefJob gram_ref_job(const Points& pts, const FilterBufs& fb, float tau2, const Tuning& tn);  // (fb.mx and fb.frame only; source left empty)
+void launch_gram_ref(const Points& pts, const TriSource* ts, const Hyps& h, const FilterBufs& fb, float tau2, const Tuning& tn, hipStream_t st);
 // the coefficients on their own (stage hook sc_score_host, which has no Kabsch launch)
-void launch_gram_coef(const float* RtSoA, const Shard& sh, float tau2, const GramCoef& coef, hipStream_t st);
+void launch_gram_coef(const Hyps& h, float tau2, const GramCoef& coef, hipStream_t st);
 void launch_filter_tile(const Points& pts, const FilterTileJob& job, hipStream_t st);  // on its own (stage hook sc_score_host)
-// RtAoS: 12 consecutive floats per hypothesis (what the exact pass loads; launch_kabsch / the stage hook write them)
-void launch_score_filter(const Points& pts, const float* RtSoA, const float* RtAoS, const Shard& sh, const Derived& dv,
-                         const FilterPlan& fp, const void* tile, void* state, void* coef, void* frame, uint32_t* partial, const Tuning& tn,
-                         hipStream_t st, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr,
-                         hipEvent_t ev_mid = nullptr);  // ev_mid (optional): stop timestamp of the FILTER kernel's own dispatch (ev0 .. ev_mid = that kernel alone)
-// Run-time probe of the matrix pipe's accumulation arithmetic (the model the Gram filter's bound assumes; sc_score.hip):
+// h.aos: 12 consecutive floats per hypothesis (what the exact pass loads; launch_kabsch / the stage hook write them); out: fb.plan.splits rows
+void launch_score_filter(const Points& pts, const Hyps& h, const FilterBufs& fb, const Partial& out, const Stamps& ev, const Derived& dv,
+                         const Tuning& tn, hipStream_t st);
+// Run-time probe of the matrix pipe's accumulation arithmetic (the model the Gram filter's bound assumes; sc_gram_guard.hip):
 // blocking, ~1e6 cancelling dot products.  scratch: 16 bytes of device memory.  worst_units: largest |hardware - exact| /
 // largest term seen, in units of 2^-24 (the bound assumes 18.5; gram_guard_limit() is what a context tolerates).
 hipError_t gram_guard_probe(void* scratch, hipStream_t st, float* worst_units, bool* subnormals_kept, uint32_t* compared);
@@ -608,8 +617,8 @@ hipError_t filter_read_frame(const void* frame, hipStream_t st, uint32_t out[5])
 // per-block (key, position) pairs; ticket: a zeroed u32 in the control block (left zero).
 size_t argmax_scratch_bytes(uint32_t ld_local);
 uint32_t argmax_blocks(uint32_t ld_local);  // workgroups of launch_argmax = pairs it leaves when key2 == nullptr
-void launch_argmax(const Shard& sh, const uint32_t* partial, uint32_t n_chunks, const uint32_t* sel_key,
-                   uint32_t* cnt, uint64_t* pairs, uint32_t* ticket, uint64_t* key2, hipStream_t st);
+struct ArgmaxOut { const uint32_t* sel_key; uint32_t* cnt; uint64_t* pairs; uint32_t* ticket; uint64_t* key2; };
+void launch_argmax(const Shard& sh, const Partial& in, const ArgmaxOut& out, hipStream_t st);
 // C3 (sc_final.hip): winner decode + re-solve + mask.  Rt12 receives R (row-major) and t; identity / zero mask when key2[0] == 0.
 // sel_key / T: the ordinal-ordered ranking keys (for the winner's rank index); host_out (pinned, 2 x u64) receives
 // [1] = rank index << 32 | position (all ones: the key pair decodes to nothing of the selection) and then, released, [0] = key2[0].
@@ -651,9 +660,12 @@ struct DeferredPub {
   unsigned long long* host;
   int with_stats;
 };
-void launch_finalize(const Points& pts, const TriSource& ts, const Shard& sh, const float* RtSoA,
-                     const uint32_t* sel_key, uint32_t T, const uint64_t* key2, int npairs, uint64_t* key_out, float tau2, float* Rt12, uint8_t* mask,
-                     unsigned long long* fin_word, uint64_t* host_out, hipStream_t st, const DeferredPub* dp = nullptr);
+// Frame end: what a winner launch (launch_finalize, launch_peel_winner) decodes — keys: the npairs key pairs (`key2` above) — and
+// what it leaves.  h: this rank's shard and hypotheses (h.sh / h.soa: `sh / RtSoA` above; h.soa null: nothing scored locally).
+struct WinnerIn { const uint32_t* sel_key; uint32_t T; const uint64_t* keys; int npairs; };
+struct WinnerOut { float* Rt12; uint8_t* mask; uint64_t* host_out; };
+void launch_finalize(const Points& pts, const TriSource& ts, const Hyps& h, const WinnerIn& in, const WinnerOut& out, float tau2,
+                     uint64_t* key_out, unsigned long long* fin_word, const DeferredPub* dp, hipStream_t st);
 // SURVEY §8f-2 (SC_FLAG_REFINE): fp64 least-squares refit of Rt12 over the inlier mask; no-op when key2[0] == 0 or
 // fewer than 3 inliers.  scratch: refine_scratch_bytes(n).
 size_t refine_scratch_bytes(int n);
@@ -670,20 +682,20 @@ struct PeelWords {
   uint32_t n_alive;             // peel_compact_kernel: correspondences it kept
   uint32_t pad;
 };
-// claim + compact, ONE launch: claimed[m] |= (|R p_m + t - q_m|^2 < tau2) for the hypothesis at position prev_pos of RtSoA (the
+// claim + compact, ONE launch: claimed[m] |= (|R p_m + t - q_m|^2 < tau2) for the hypothesis at position prev_pos of h.soa (the
 // winner of the round before; prev_pos == ~0u: nothing to fold in), then the correspondences still unclaimed go, order preserved,
 // into the six planes of `alive` (stride pts.ld).  fresh: `claimed` holds nothing yet (round 1): read as zeros, written whole.
 // lb: a look-back launch of peel_compact_tiles(n) tiles (8 bytes of descriptor each).  host_alive (optional, pinned): receives the
 // number kept (the host needs it to size the scoring launch where the scores do not tell it: the truncated score modes).
 uint32_t peel_compact_tiles(int n);
-void launch_peel_compact(const Points& pts, const float* RtSoA, uint32_t ld_local, uint32_t prev_pos, float tau2, bool fresh,
-                         uint8_t* claimed, float* alive, PeelWords* words, LbArgs lb, uint64_t* host_alive, hipStream_t st);
-// winner + mask of a round: finalize_kernel's work on ONE shard (the hypothesis at position g is RtSoA[.. + g]) with
-// mask[m] = !claimed[m] && inlier.  pairs / npairs: what launch_argmax left (key2 == nullptr form); npairs == 0: no hypothesis
-// (identity, zero mask).  host_out as launch_finalize's.
-void launch_peel_winner(const Points& pts, const uint8_t* claimed, const float* RtSoA, uint32_t ld_local, const uint32_t* sel_key,
-                        uint32_t T, const uint64_t* pairs, int npairs, float tau2, float* Rt12, uint8_t* mask, PeelWords* words,
-                        uint64_t* host_out, hipStream_t st);
+struct PeelSets { uint8_t* claimed; float* alive; uint64_t* host_alive; };
+void launch_peel_compact(const Points& pts, const Hyps& h, const PeelSets& ps, uint32_t prev_pos, float tau2, bool fresh,
+                         PeelWords* words, LbArgs lb, hipStream_t st);
+// winner + mask of a round: finalize_kernel's work on ONE shard (the hypothesis at position g is h.soa[.. + g]) with
+// mask[m] = !claimed[m] && inlier.  in.keys / in.npairs: what launch_argmax left (key2 == nullptr form); npairs == 0: no hypothesis
+// (identity, zero mask).  out.host_out as launch_finalize's.
+void launch_peel_winner(const Points& pts, const Hyps& h, const WinnerIn& in, const WinnerOut& out, const uint8_t* claimed, float tau2,
+                        PeelWords* words, hipStream_t st);
 // label[m] = value where mask[m] (sc_register_instances: one launch per accepted motion)
 void launch_peel_label(const uint8_t* mask, int n, int32_t value, int32_t* label, hipStream_t st);
 

@@ -131,18 +131,17 @@ __global__ __launch_bounds__(256) void peel_label_kernel(const uint8_t* __restri
 
 uint32_t peel_compact_tiles(int n) { return (uint32_t)((n + PEEL_THREADS - 1) / PEEL_THREADS); }
 
-void launch_peel_compact(const Points& pts, const float* RtSoA, uint32_t ld_local, uint32_t prev_pos, float tau2, bool fresh,
-                         uint8_t* claimed, float* alive, PeelWords* words, LbArgs lb, uint64_t* host_alive, hipStream_t st) {
+void launch_peel_compact(const Points& pts, const Hyps& h, const PeelSets& ps, uint32_t prev_pos, float tau2, bool fresh,
+                         PeelWords* words, LbArgs lb, hipStream_t st) {
   hipLaunchKernelGGL(peel_compact_kernel, dim3(peel_compact_tiles(pts.n)), dim3(PEEL_THREADS), 0, st, pts.planes, pts.n, pts.ld,
-                     RtSoA, ld_local, prev_pos, tau2, fresh ? 1 : 0, claimed, alive, words, lb, host_alive);
+                     h.soa, h.sh.ld_local, prev_pos, tau2, fresh ? 1 : 0, ps.claimed, ps.alive, words, lb, ps.host_alive);
 }
 
-void launch_peel_winner(const Points& pts, const uint8_t* claimed, const float* RtSoA, uint32_t ld_local, const uint32_t* sel_key,
-                        uint32_t T, const uint64_t* pairs, int npairs, float tau2, float* Rt12, uint8_t* mask, PeelWords* words,
-                        uint64_t* host_out, hipStream_t st) {
-  hipLaunchKernelGGL(peel_winner_kernel, dim3(winner_blocks(pts.n, T)), dim3(256), 0, st, pts.planes, pts.n, pts.ld, claimed, RtSoA, ld_local,
-                     sel_key, T, reinterpret_cast<const unsigned long long*>(pairs), npairs, tau2, Rt12, mask, words,
-                     reinterpret_cast<unsigned long long*>(host_out));
+void launch_peel_winner(const Points& pts, const Hyps& h, const WinnerIn& in, const WinnerOut& out, const uint8_t* claimed, float tau2,
+                        PeelWords* words, hipStream_t st) {
+  hipLaunchKernelGGL(peel_winner_kernel, dim3(winner_blocks(pts.n, in.T)), dim3(256), 0, st, pts.planes, pts.n, pts.ld, claimed,
+                     h.soa, h.sh.ld_local, in.sel_key, in.T, reinterpret_cast<const unsigned long long*>(in.keys),
+                     in.npairs, tau2, out.Rt12, out.mask, words, reinterpret_cast<unsigned long long*>(out.host_out));
 }
 
 void launch_peel_label(const uint8_t* mask, int n, int32_t value, int32_t* label, hipStream_t st) {

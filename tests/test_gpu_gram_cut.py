@@ -1,4 +1,4 @@
-"""GPU: the Gram filter's reference frame and its cut (sc_score.hip, "the frame" / "the cut"; sc_gramref.hpp).
+"""GPU: the Gram filter's reference frame and its cut (sc_filter.hip, "the frame" / "the cut"; sc_gramref.hpp).
 
 Stage C2's Gram filter evaluates the squared residual in the frame of a reference hypothesis that 64 voters elect, and a
 hypothesis near that frame only looks at the correspondences near it — every other test is decided by the triangle inequality.

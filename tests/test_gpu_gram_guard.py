@@ -1,7 +1,7 @@
 """GPU: the run-time guard of the Gram filter's silicon model, and a GPU-vs-GPU fuzz net around the filter.
 
 The Gram filter (stage C2's default at the C2 / C4 sizes) is bit-exact only as long as one v_mfma_f32_32x32x16_f16 stays
-within GX_ACC = 18.5 x 2^-24 of its largest term — a MEASURED property of gfx950's matrix pipe (sc_score.hip).  Every
+within GX_ACC = 18.5 x 2^-24 of its largest term — a MEASURED property of gfx950's matrix pipe (sc_gram_guard.hip).  Every
 context therefore probes its own pipe before the first call that would choose that filter (gram_guard_kernel); these
 tests pin (a) what the probe reports on the box the suite runs on, (b) that a failing probe really takes the Gram filter
 out of the path with identical results, and (c) Gram == fp32 kernel on clouds the synthetic BASELINE scenes never show

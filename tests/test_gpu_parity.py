@@ -1087,7 +1087,7 @@ def test_sharded_candidate_blobs_too_small_are_detected_and_retried(pkg, O):
 
 
 # ---------------------------------------------------------------------------------------------------------
-# C2 by filter + exact fix-up (sc_score.hip): every count must be the canonical fp32 kernel's / the oracle's
+# C2 by filter + exact fix-up (sc_filter.hip): every count must be the canonical fp32 kernel's / the oracle's
 # ---------------------------------------------------------------------------------------------------------
 def _hyps_near_truth(O, sc, T, seed):
     """T hypotheses: half from inlier triangles (many inliers, residuals spread around tau), half from random ones."""

@@ -1,5 +1,5 @@
-"""CPU: the exact-arithmetic half of the Gram filter's error bound, restated in numpy (sac-cot_amd/csrc/sc_score.hip, header of the
-Gram filter; gram_coef_block / gram_tile_block; sc_gramref.hpp).
+"""CPU: the exact-arithmetic half of the Gram filter's error bound, restated in numpy (sac-cot_amd/csrc/sc_filter.hip, header of the
+Gram filter; gram_coef_block / gram_tile_block in sc_kabsch.hip; sc_gramref.hpp).
 
 The filter evaluates  s^2 |R_h p + t_h - q|^2  as a 48-slot dot product of fp16 halves in the frame of a reference motion.  Its
 shell eps_h has two kinds of terms: what the MATRIX PIPE loses when it adds the products (GX_ACC: a measured model, probed at run
@@ -32,7 +32,7 @@ def _small_rot(rng, ang):
 
 
 def _split(x):
-    """x (float64 array) -> (hi, lo) fp16 values as float64: hi = fp16(fp32(x)), lo = fp16(fp32(x - hi)) — split2 in sc_score.hip."""
+    """x (float64 array) -> (hi, lo) fp16 values as float64: hi = fp16(fp32(x)), lo = fp16(fp32(x - hi)) — split2 in sc_kabsch.hip."""
     hi = np.float32(x).astype(np.float16).astype(np.float64)
     lo = np.float32(x - hi).astype(np.float16).astype(np.float64)
     return hi, lo
@@ -140,7 +140,7 @@ def test_far_correspondences_of_a_near_hypothesis_are_outliers_by_the_triangle_i
 
 
 def test_group_major_grid_order_is_a_bijection_and_spreads_the_working_workgroups_over_the_xcds():
-    """score_gram_kernel's group-major decode of its one-dimensional grid (sc_score.hip; restated here on purpose):
+    """score_gram_kernel's group-major decode of its one-dimensional grid (sc_filter.hip; restated here on purpose):
     workgroup b -> row block groups - 1 - b / splits, split (b % splits + r) % splits with r = (b / splits * g / 8) % g,
     g = gcd(splits, 8).  Every (row block, split) is taken once, and for every ns the workgroups with split < ns — the
     ones of the near rows that work — fall on all eight XCDs (workgroup b runs on XCD b % 8) evenly."""

@@ -1,6 +1,6 @@
 // How far is the filter's fp16-split residual from the true one, against the bound eta it assumes?
 //   bash tools/ubench/run.sh filter_error
-// Same operand construction as score_filter_kernel (sc_score.hip): E' = 1024 s (R p + t - q) through one
+// Same operand construction as score_filter_kernel (sc_filter.hip): E' = 1024 s (R p + t - q) through one
 // v_mfma_f32_32x32x16_f16 per 8 hypotheses x 32 correspondences, fp16 hi / lo splits, t through C.  For every test the
 // kernel compares E' / (1024 s) with the residual evaluated in fp64 from the same fp32 inputs, and with the canonical
 // fp32 chain; it reports the largest vector error in units of eta = 2^-16 (2.6 Pmax + Qmax + Tmax) / s.

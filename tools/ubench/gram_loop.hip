@@ -1,4 +1,4 @@
-// Microbenchmark: the loop skeleton of score_gram_kernel (sc_score.hip) with its parts switched on one by one, to see which
+// Microbenchmark: the loop skeleton of score_gram_kernel (sc_filter.hip) with its parts switched on one by one, to see which
 // part keeps the matrix pipe from overlapping the vector work.  512-thread workgroups (8 waves x 32 hypotheses), two per CU,
 // units of 256 correspondences (2 x 16 KiB in LDS, staged by LDS-DMA), 8 steps per unit, per step two ds_read_b128 + three
 // chained v_mfma_f32_32x32x16_f16 + an epilogue.

@@ -1,6 +1,6 @@
 // Microbenchmark: what one SIMD sustains for  { ds_read_b128 of the B operand ; v_mfma_f32_32x32x16_f16 ; V vector
 // instructions on the result }  per step, as a function of waves per SIMD, prefetch distance and V — the shape of stage
-// C2's filter loop (sc_score.hip).  Prints nominal cycles per step at 2.4 GHz and the real ones from s_memtime / s_memrealtime.
+// C2's filter loop (sc_filter.hip).  Prints nominal cycles per step at 2.4 GHz and the real ones from s_memtime / s_memrealtime.
 //   hipcc -O3 -w --offload-arch=gfx950 -mllvm -amdgpu-mfma-vgpr-form=1 tools/ubench/mfma_lds.hip -o /tmp/mfma_lds && /tmp/mfma_lds
 #include <hip/hip_runtime.h>
 #include <cstdio>

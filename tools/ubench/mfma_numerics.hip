@@ -1,5 +1,5 @@
 // Probe: how v_mfma_f32_32x32x16_f16 rounds and accumulates (nothing in the ISA text pins it down; the Gram filter's error
-// bound — sc_score.hip — states which of these properties it relies on).  Each case sets the 16 products of D[0][0] and C.
+// bound — sc_filter.hip — states which of these properties it relies on).  Each case sets the 16 products of D[0][0] and C.
 //   hipcc -O3 -w --offload-arch=gfx950 -mllvm -amdgpu-mfma-vgpr-form=1 tools/ubench/mfma_numerics.hip -o /tmp/mn && /tmp/mn
 #include <hip/hip_runtime.h>
 #include <cstdio>
