@@ -51,6 +51,7 @@ extern "C" {
 #define SC_HAS_SETTLE 1  /* this header declares sc_settle_poses* and sc_settle_default_params (added within 0.10) */
 #define SC_HAS_MERGE 1  /* this header declares sc_merge_poses* and sc_merge_default_params (added within 0.10) */
 #define SC_HAS_PAIRS_CYCLES 1  /* this header declares sc_pairs_cycles*, sc_cycles_default_params and sc_cycles_thresholds (added within 0.10) */
+#define SC_HAS_PAIRS_SYNC 1  /* this header declares sc_pairs_sync*, sc_sync_default_params and sc_sync_thresholds (added within 0.10) */
 #define SC_HAS_MATCH_GUIDED 1  /* this header declares sc_match_guided*, sc_register_guided_features and sc_guide_default_params (added within 0.10) */
 #define SC_HAS_MATCH_GUIDED_POSES 1  /* this header declares sc_match_guided_poses*, sc_register_guided_poses_features and SC_GUIDE_MAX_POSES (added within 0.10) */
 #define SC_HAS_MATCH_GUIDED_BATCH 1  /* this header declares sc_match_guided_batch*, sc_match_guided_pairs* and sc_register_guided_{batch,pairs}_features_device (added within 0.10) */
@@ -1572,6 +1573,136 @@ int sc_merge_poses_batch_device(sc_ctx* ctx, const float* d_src, const float* d_
 int sc_merge_poses_batch(sc_ctx* ctx, const float* src, const float* tgt, const uint32_t* offset, uint32_t n_problems,
                          const sc_params* params, const sc_merge_params* mp, const void* pose, uint32_t pose_stride,
                          uint32_t n_poses, sc_merge_pose* out, int32_t* parent, uint32_t* count);
+
+/* ---- absolute poses of a pair list's sets: sc_pairs_sync ----------------------------------------------------------------
+ * The pairs chain leaves a relative pose per listed pair and, behind sc_pairs_cycles, a verdict on which pairs close consistent
+ * loops.  What its caller — fragment registration, loop closure, multi-scan alignment — wants next is where the sets lie in ONE
+ * frame.  These entries place every set that the list connects to an anchor set, on the device, stream-ordered behind
+ * sc_pairs_cycles_device with no host word in between: the poses they leave are legal priors for sc_match_guided* as they stand.
+ *
+ * The method is anchored Jacobi averaging: breadth-first propagation and refinement in one rule.  X_s maps set s's coordinates
+ * into the anchor's frame; pair p, stored (a, b) with pose T (a onto b), is the constraint X_a = X_b o T.  known_0 = {anchor},
+ * X_0(anchor) = identity.  Round k recomputes every other set from the neighbours that were known after round k-1: the rotation
+ * nearest the weighted sum of the predicted rotations (the chordal mean), the weighted mean of the predicted translations.  A round
+ * reads X_{k-1} and writes every set of X_k (Jacobi, not Gauss-Seidel: nothing depends on scheduling), so a set first becomes known
+ * in the round equal to its hop distance from the anchor.
+ * The method's limits.  It is the synchronisation step a pose-graph solver is started from, and on well-connected lists also the
+ * answer: 24 sets with all pairs stop in 4 - 5 rounds, 512 sets with 20 pairs a set in 9 - 14.  Along chains it DIFFUSES: a bare
+ * ring of 40 sets needs 89 rounds at a tolerance of 1e-4 and 461 at 1e-6, an odometry strip of 200 sets with 40 closures 47 and 938
+ * — more than max_rounds admits.  And "no set moved more than the tolerances in a round" is a STOPPING RULE, not an accuracy bound:
+ * a slow mode moves every set by less than the tolerance a round, for many rounds.  Threshold the residuals (r2, e2 below) to judge
+ * the result.
+ *
+ * Inputs.  n_sets, pairs (HOST), n_pairs, d_pose, pose_stride: exactly those of sc_pairs_cycles, under the same rules and limits
+ * (SC_CYCLES_MAX_PAIRS, SC_CYCLES_MAX_DEGREE; SC_SYNC_STATUS for SC_CYCLES_STATUS).  d_use: NULL (every pair may be used) or a
+ * uint32 read at byte p * use_stride, non-zero: pair p may be used; use_stride a multiple of 4, at least 4, ignored with NULL.
+ * &d_res[0].alive of sc_pairs_cycles_device's records with use_stride 48 is the chain.  d_weight: NULL (every weight 1.0) or
+ * n_pairs floats, widened to double; a pair whose weight is not finite or not greater than 0 is not used.  Nothing of the inputs is
+ * written.
+ * Thresholds, derived on the host in double: r2_max = 2.0 * (double)rot_tol * (double)rot_tol, e2_max = (double)trans_tol *
+ * (double)trans_tol.  sc_sync_thresholds returns exactly the two values a call uses.  r2_max bounds the squared Frobenius distance
+ * of two rotations, 2 theta^2 to first order; it is deliberately not a trace: 1 + 2 cos(rot_tol) is exactly 3.0 below 2e-8, and the
+ * rounds would never stop.
+ *
+ * Definitions.  The call is a function of the list, the poses, use, weight and the parameters alone, bit for bit.  All arithmetic is
+ * fp64 on the exactly widened fp32 entries; every operation is a plain rounded product, sum, quotient or square root in the order
+ * written; nothing is fused.  valid(p), T(x->y) and M = B o A are those of sc_pairs_cycles.
+ *   usable(p)  valid(p), pairs[2p] != pairs[2p + 1], use(p) != 0 (or d_use NULL), and w_p = (double)weight[p] (or 1.0) finite and
+ *              > 0.
+ *   sorted list  of set s: one entry for every listed pair that names s and another set n, in ascending order of (n, p).
+ *   update     of set s != anchor in round k.  Its entries are taken in the order of its sorted list, i = 0, 1, ...  Entry i, on
+ *              pair p to neighbour n, is LIVE if usable(p) and n is in known_{k-1}; then P = X_{k-1}(n) o T_p(s->n).  64 slots of
+ *              13 doubles (acc[0 .. 11], accW), each +0.0.  Entry i adds into slot i mod 64, in increasing i:
+ *              acc[c] = acc[c] + w_p * P[c] for the 12 components (P.R row-major, then P.t), accW = accW + w_p; an entry that is not
+ *              live adds nothing.  The slots are folded: for h = 32, 16, 8, 4, 2, 1: slot[j] = slot[j] + slot[j + h] for j < h, every
+ *              component.  With no live entry the set is unchanged.  Otherwise, from slot 0: M = acc[0 .. 8], c = acc[9 .. 11],
+ *              W = accW; R' = rot(M), t'_i = c_i / W.  If any of the twelve is not finite (NaN or infinite) the set is unchanged —
+ *              not known if it was not — and its `degenerate` grows by one.  Otherwise X_k(s) = (R', t') and s is in known_k.  The
+ *              anchor is never recomputed.
+ *   rot(M)     B_c = row c of M (c = 0, 1, 2), V_c = row c of the identity; dot(a, b) = (a_0 * b_0 + a_1 * b_1) + a_2 * b_2.
+ *              Ten sweeps; a sweep takes (p, q) = (0, 1), (0, 2), (1, 2) in this order: alpha = dot(B_p, B_p), beta = dot(B_q, B_q),
+ *              gamma = dot(B_p, B_q); if gamma != 0.0: zeta = (beta - alpha) / (gamma + gamma),
+ *              tt = 1.0 / (|zeta| + sqrt(zeta * zeta + 1.0)), negated if zeta < 0.0, cs = 1.0 / sqrt(tt * tt + 1.0), sn = cs * tt;
+ *              then for r = 0, 1, 2, with x = B_p[r], y = B_q[r]: B_p[r] = cs * x - sn * y, B_q[r] = sn * x + cs * y, and the same
+ *              for V_p[r], V_q[r].  Then n_c = dot(B_c, B_c); i1 = the first c with the largest n_c (1 replaces 0 only if
+ *              n_1 > n_0, 2 replaces that only if n_2 is greater still); i2 = the lower of the two other indices unless the
+ *              higher one's n is greater.  s1 = sqrt(dot(B_i1, B_i1)), s2 = sqrt(dot(B_i2, B_i2)); u1 = B_i1 / s1, u2 = B_i2 / s2
+ *              (component by component), v1 = V_i1, v2 = V_i2; u3 = u1 x u2, v3 = v1 x v2, with
+ *              (a x b)_0 = a_1 * b_2 - a_2 * b_1, (a x b)_1 = a_2 * b_0 - a_0 * b_2, (a x b)_2 = a_0 * b_1 - a_1 * b_0;
+ *              R'_rc = (v1[r] * u1[c] + v2[r] * u2[c]) + v3[r] * u3[c].  (The fp64 solve of the library's rigid refit applied to
+ *              H = M^T, every fused multiply-add of it replaced by the rounded product followed by the rounded sum in the same
+ *              nesting: the rotation nearest M in the Frobenius norm, a proper one whatever M's determinant.)
+ *   changed    dR2 = the sum over the nine entries, row-major, of (R'_ij - R_ij) * (R'_ij - R_ij), added left to right; dt2
+ *              likewise over the three of t.  Set s is changed in round k if it is in known_k and not in known_{k-1}, or
+ *              dR2 > r2_max, or dt2 > e2_max: both cuts inclusive on the quiet side.
+ *   rounds     K is the first round in which no set is changed (converged = 1), or max_rounds.  The outputs are X_K and known_K.
+ *   residual   of pair p stored (a, b), when usable(p) and a and b are both in known_K: Q = X_K(b) o T_p(a->b) — the record
+ *              itself —, r2 = the sum over the nine entries, row-major, of (X_K(a).R_ij - Q.R_ij) squared, added left to right,
+ *              e2 = likewise over the three of t.
+ * Outputs.  sc_sync_set (160 bytes) per set at d_set[s]: Rt is X_K(s) rounded once to fp32 and status SC_OK, so that d_set is an
+ * array of legal pose records, with a status, of stride 160 for every pose entry; a set that was never reached has Rt and X all
+ * zero and status SC_ENOHYP.  sc_sync_pair (32 bytes) per pair at d_pair[p].  sc_sync_summary (32 bytes) at d_sum.
+ * Forms.  sc_pairs_sync_device: poses, use, weight and outputs in HBM; it enqueues and returns without waiting, reads no host
+ * word, and its number of stream operations depends on max_rounds only (a copy, a memset, max_rounds + 2 launches; a round's launch
+ * returns at once when the round before changed no set).  (It may wait for the previous batch call's copy out of the staging area
+ * the batch entries share.)  sc_pairs_sync: host arrays; waits.  Like every batch entry they end the frame a context may hold.
+ * Errors: the CALL returns SC_EINVAL, decided on the host before anything is enqueued, sc_last_error naming which: a NULL argument
+ * other than d_use and d_weight (a NULL ctx: no text); everything sc_pairs_cycles refuses of n_sets, n_pairs and the list; size
+ * wrong, max_rounds outside 1 .. 256, rot_tol not finite or outside [0, pi], trans_tol not finite or negative, an unknown flag or a
+ * non-zero reserved word; a pose_stride that breaks the pose rule; with d_use, a use_stride below 4 or no multiple of 4; an anchor
+ * >= n_sets; a call outstanding on the context.
+ * Workspace: the copied list with every set's sorted neighbour entries and the list starts, the oriented fp64 poses and a weight
+ * (200 bytes a pair), two states and the tallies of a set (224 bytes a set) and the round words; the host form adds device copies
+ * of its arrays, in the pool every host form shares.  Allocated by the first such call, counted in workspace_bytes and held against
+ * the cap (SC_ENOMEM, nothing enqueued).  A context that never calls these entries allocates and runs nothing new.
+ * Not here / not built: a block solver — conjugate gradients on the graph Laplacian, Gauss-Newton on the pairs' 6 x 6 information
+ * matrices — which is the follow-up where lists are chains: this entry diffuses along them, as said above; robust re-weighting
+ * between the rounds; several anchors; a sharded form. */
+#define SC_SYNC_STATUS 1u   /* flags: a pose record holds an int32 status at byte 48 */
+typedef struct sc_sync_params {    /* 32 bytes */
+  uint32_t size;         /* = sizeof(sc_sync_params)                                   */
+  uint32_t anchor;       /* the set whose frame is the common one; < n_sets; default 0 */
+  uint32_t max_rounds;   /* 1 .. 256; default 32                                       */
+  uint32_t flags;        /* SC_SYNC_STATUS or 0                                        */
+  float    rot_tol;      /* radians, finite, in [0, pi]                                */
+  float    trans_tol;    /* finite, >= 0, in the poses' unit                           */
+  uint32_t reserved[2];  /* must be 0                                                  */
+} sc_sync_params;
+typedef struct sc_sync_set {       /* 160 bytes */
+  float    Rt[12];         /* X_K(s) rounded once: R row-major, then t; all 0 where s was never reached */
+  int32_t  status;         /* SC_OK; SC_ENOHYP: never reached                                           */
+  uint32_t known_round;    /* the k at which s became known; 0 for the anchor and for a set never reached */
+  uint32_t used;           /* live entries of s in round K; 0 for the anchor                            */
+  uint32_t degenerate;     /* rounds among 1 .. K in which s's sum gave no finite pose                   */
+  double   X[12];          /* X_K(s); all 0 where s was never reached                                   */
+} sc_sync_set;
+typedef struct sc_sync_pair {      /* 32 bytes */
+  int32_t  status;         /* SC_OK, the status passed through, or SC_EINVAL for a non-finite Rt        */
+  uint32_t used;           /* 1: usable(p) and both of its sets are in known_K                          */
+  double   r2;             /* the residual's rotation part; 0.0 where used is 0                         */
+  double   e2;             /* the residual's translation part; 0.0 where used is 0                      */
+  uint32_t reserved[2];    /* written as 0                                                              */
+} sc_sync_pair;
+typedef struct sc_sync_summary {   /* 32 bytes */
+  uint32_t rounds;         /* K                                                        */
+  uint32_t converged;      /* 1: no set changed in round K                             */
+  uint32_t known;          /* sets in known_K, the anchor among them                   */
+  uint32_t used;           /* pairs whose `used` is 1                                  */
+  uint32_t changed_last;   /* sets changed in round K                                  */
+  uint32_t reserved[3];    /* written as 0                                             */
+} sc_sync_summary;
+int sc_sync_default_params(sc_sync_params* sp);   /* size, anchor 0, max_rounds 32; everything else 0: the tolerances are the caller's */
+/* host only, no context: out[0] = r2_max, out[1] = e2_max; SC_EINVAL for a NULL argument, a wrong size or a tolerance out of range */
+int sc_sync_thresholds(const sc_sync_params* sp, double out[2]);
+/* pairs a HOST array; d_pose n_pairs records of pose_stride bytes, d_use NULL or a word every use_stride bytes, d_weight NULL or
+ * n_pairs floats, d_set n_sets records, d_pair n_pairs records, d_sum one */
+int sc_pairs_sync_device(sc_ctx* ctx, uint32_t n_sets, const uint32_t* pairs, uint32_t n_pairs, const sc_sync_params* sp,
+                         const void* d_pose, uint32_t pose_stride, const void* d_use, uint32_t use_stride, const float* d_weight,
+                         sc_sync_set* d_set, sc_sync_pair* d_pair, sc_sync_summary* d_sum);
+/* the same with host arrays (pose, use, weight, set, pair, sum); waits */
+int sc_pairs_sync(sc_ctx* ctx, uint32_t n_sets, const uint32_t* pairs, uint32_t n_pairs, const sc_sync_params* sp,
+                  const void* pose, uint32_t pose_stride, const void* use, uint32_t use_stride, const float* weight,
+                  sc_sync_set* set, sc_sync_pair* pair, sc_sync_summary* sum);
 
 /* ---- two-phase form for one-process-per-GPU sharding --------------------------------
  * Phase 1: A and B replicated, C1+C2 on this rank's blocks of the top-T list; writes this rank's winner key

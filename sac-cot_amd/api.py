@@ -218,6 +218,36 @@ class ScCycleSummary(C.Structure):
 CYCLE_RESULT_DTYPE = np.dtype(ScCycleResult)    # sc_cycle_result as a numpy record
 CYCLE_SUMMARY_DTYPE = np.dtype(ScCycleSummary)  # sc_cycle_summary as a numpy record
 SC_CYCLES_STATUS, SC_CYCLES_MAX_PAIRS, SC_CYCLES_MAX_DEGREE = 1, 1 << 22, 65535
+class ScSyncParams(C.Structure):
+    """Mirror of `sc_sync_params` (include/saccot.h), 32 bytes: the anchor set, the rounds at most (1 .. 256), SC_SYNC_STATUS or 0, the
+    rotation tolerance (radians, in [0, pi]) and the translation tolerance (>= 0) of the stopping rule."""
+    _fields_ = [("size", C.c_uint32), ("anchor", C.c_uint32), ("max_rounds", C.c_uint32), ("flags", C.c_uint32), ("rot_tol", C.c_float),
+                ("trans_tol", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
+class ScSyncSet(C.Structure):
+    """Mirror of `sc_sync_set` (include/saccot.h), 160 bytes: one set's record of sc_pairs_sync — a legal pose record with a status
+    (Rt, status) in front of the tallies and the fp64 pose."""
+    _fields_ = [("Rt", C.c_float * 12), ("status", C.c_int32), ("known_round", C.c_uint32), ("used", C.c_uint32), ("degenerate", C.c_uint32),
+                ("X", C.c_double * 12)]
+
+
+class ScSyncPair(C.Structure):
+    """Mirror of `sc_sync_pair` (include/saccot.h), 32 bytes: one pair's status, whether it was used, and its residual."""
+    _fields_ = [("status", C.c_int32), ("used", C.c_uint32), ("r2", C.c_double), ("e2", C.c_double), ("reserved", C.c_uint32 * 2)]
+
+
+class ScSyncSummary(C.Structure):
+    """Mirror of `sc_sync_summary` (include/saccot.h), 32 bytes: the rounds run, whether they converged, the sets known and the pairs
+    used at the end, the sets the last round changed."""
+    _fields_ = [("rounds", C.c_uint32), ("converged", C.c_uint32), ("known", C.c_uint32), ("used", C.c_uint32), ("changed_last", C.c_uint32),
+                ("reserved", C.c_uint32 * 3)]
+
+
+SYNC_SET_DTYPE = np.dtype(ScSyncSet)          # sc_sync_set as a numpy record
+SYNC_PAIR_DTYPE = np.dtype(ScSyncPair)        # sc_sync_pair as a numpy record
+SYNC_SUMMARY_DTYPE = np.dtype(ScSyncSummary)  # sc_sync_summary as a numpy record
+SC_SYNC_STATUS = 1
 SC_GUIDE_POSE_STATUS = 1  # sc_guide_params.flags, the sc_match_guided_batch / _poses entries only: the pose records hold an int32 status at byte 48
 SC_GUIDE_MAX_POSES = 64  # pose records per call of sc_match_guided_poses at most
 SC_MATCH_BATCH_MAX_N = 4096  # rows a side of one problem of sc_match_batch
@@ -284,6 +314,7 @@ _F32P, _U8P, _I32P, _U32P, _U64P = (C.POINTER(t) for t in (C.c_float, C.c_uint8,
 _PP, _SP, _QP, _MP, _GP = (C.POINTER(t) for t in (ScParams, ScStats, ScPolishParams, ScMatchParams, ScGuideParams))
 _IP, _ZP, _AP, _TP, _RP = (C.POINTER(t) for t in (ScPoseInfoParams, ScPolishPosesParams, ScAssignParams, ScSettleParams, ScMergeParams))
 _CP = C.POINTER(ScCycleParams)
+_YP = C.POINTER(ScSyncParams)
 _PROTOTYPES = {
     "sc_version": [],
     "sc_strerror": ([_INT], C.c_char_p),
@@ -373,6 +404,10 @@ _PROTOTYPES = {
     "sc_cycles_thresholds": [_CP, C.POINTER(C.c_double)],
     "sc_pairs_cycles": [_VP, _U32, _U32P, _U32, _CP, _VP, _U32, _U8P, _VP, _VP],
     "sc_pairs_cycles_device": [_VP, _U32, _U32P, _U32, _CP, _VP, _U32, _VP, _VP, _VP],
+    "sc_sync_default_params": [_YP],
+    "sc_sync_thresholds": [_YP, C.POINTER(C.c_double)],
+    "sc_pairs_sync": [_VP, _U32, _U32P, _U32, _YP, _VP, _U32, _VP, _U32, _F32P, _VP, _VP, _VP],
+    "sc_pairs_sync_device": [_VP, _U32, _U32P, _U32, _YP, _VP, _U32, _VP, _U32, _VP, _VP, _VP, _VP],
     "sc_hypothesize_device": [_VP, _VP, _VP, _I64, _PP, _VP, _SP],
     "sc_finalize_device": [_VP, _VP, _VP, _VP, _SP],
     "sc_hypothesize_begin_device": [_VP, _VP, _VP, _I64, _PP, _VP, _SP],
@@ -492,6 +527,21 @@ def cycles_thresholds(cparams: ScCycleParams) -> tuple[float, float]:
     rc = load_library().sc_cycles_thresholds(C.byref(cparams), out)
     if rc != SC_OK:
         raise SacCotError(rc, "sc_cycles_thresholds")
+    return out[0], out[1]
+
+
+def make_sync_params(rot_tol: float = 0.0, trans_tol: float = 0.0, anchor: int = 0, max_rounds: int = 32, flags: int = 0) -> ScSyncParams:
+    """sc_sync_params: the tolerances of the stopping rule (rot_tol in radians, in [0, pi]; trans_tol >= 0) are the caller's; anchor
+    < n_sets, max_rounds 1 .. 256, flags SC_SYNC_STATUS or 0."""
+    return _sized(ScSyncParams, anchor, max_rounds, flags, rot_tol, trans_tol)
+
+
+def sync_thresholds(sparams: ScSyncParams) -> tuple[float, float]:
+    """sc_sync_thresholds: (r2_max, e2_max), exactly the two values a call with these parameters uses."""
+    out = (C.c_double * 2)()
+    rc = load_library().sc_sync_thresholds(C.byref(sparams), out)
+    if rc != SC_OK:
+        raise SacCotError(rc, "sc_sync_thresholds")
     return out[0], out[1]
 
 
@@ -1592,6 +1642,49 @@ class Registrar:
         self._frame_n = 0
         self._check(self._lib.sc_pairs_cycles_device(self._h, n_sets, _p(pairs), len(pairs) // 2, C.byref(cparams), d_pose, pose_stride,
                                                      d_keep or None, d_res, d_sum))
+
+    # ---- absolute poses of a pair list's sets (include/saccot.h, sc_pairs_sync) ---------------------------------------------------
+    def pairs_sync(self, n_sets: int, pairs, pose, sparams: ScSyncParams | None = None, use=None, weight=None, **kw):
+        """sc_pairs_sync: pairs (P, 2) set indices (source, target); pose (P,) records as pairs_cycles takes them; use None or (P,)
+        uint32, non-zero: the pair may be used — or (P,) records of pairs_cycles (CYCLE_RESULT_DTYPE), whose `alive` words are read in
+        place; weight None or (P,) float32 -> (sets (n_sets,) of SYNC_SET_DTYPE, pairs (P,) of SYNC_PAIR_DTYPE, summary: one record of
+        SYNC_SUMMARY_DTYPE).  kw: rot_tol, trans_tol, anchor, max_rounds, flags (make_sync_params)."""
+        q = sparams or make_sync_params(**kw)
+        pairs = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1)
+        npairs = len(pairs) // 2
+        pose, stride = self._pose_records(pose, npairs)
+        use_ptr, use_stride = None, 4
+        if use is not None:
+            use = np.ascontiguousarray(use)
+            if use.dtype == CYCLE_RESULT_DTYPE:
+                use_ptr, use_stride = use.ctypes.data + CYCLE_RESULT_DTYPE.fields["alive"][1], CYCLE_RESULT_DTYPE.itemsize
+            else:
+                use = np.ascontiguousarray(use, dtype=np.uint32).reshape(-1)
+                use_ptr = use.ctypes.data
+            if len(use) != npairs:
+                raise ValueError("pairs_sync: use holds one word (or one sc_cycle_result) per pair")
+        if weight is not None:
+            weight = _f32c(weight).reshape(-1)
+            if len(weight) != npairs:
+                raise ValueError("pairs_sync: weight holds one float per pair")
+        sets = np.zeros(max(n_sets, 1), SYNC_SET_DTYPE)
+        res = np.zeros(max(npairs, 1), SYNC_PAIR_DTYPE)
+        summary = np.zeros(1, SYNC_SUMMARY_DTYPE)
+        self._frame_n = 0
+        self._check(self._lib.sc_pairs_sync(self._h, n_sets, _p(pairs), npairs, C.byref(q), _vp(pose), stride, use_ptr, use_stride, _p(weight),
+                                            _vp(sets), _vp(res), _vp(summary)))
+        return sets[:n_sets], res[:npairs], summary[0]
+
+    def pairs_sync_device(self, n_sets: int, pairs, sparams: ScSyncParams, d_pose: int, pose_stride: int, d_use: int, use_stride: int,
+                          d_weight: int, d_set: int, d_pair: int, d_sum: int):
+        """sc_pairs_sync_device: pairs a HOST array (P, 2); pose records (pose_stride bytes each), the use words (one every use_stride
+        bytes; 0: every pair), the weights (P floats; 0: 1.0), the set records (n_sets of 160 bytes), the pair records (P of 32 bytes)
+        and the summary (32 bytes) in HBM; enqueues on the context's stream — a number of operations that depends on max_rounds only —
+        and returns without waiting."""
+        pairs = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1)
+        self._frame_n = 0
+        self._check(self._lib.sc_pairs_sync_device(self._h, n_sets, _p(pairs), len(pairs) // 2, C.byref(sparams), d_pose, pose_stride,
+                                                   d_use or None, use_stride, d_weight or None, d_set, d_pair, d_sum))
 
     def hypothesize_device(self, d_src: int, d_tgt: int, n: int, params: ScParams, d_key: int):
         st = ScStats(C.sizeof(ScStats))

@@ -188,7 +188,10 @@ struct Workspace {
       asg_off, stl_off, mrg_off, mrg_rows, mrg_table,
       // sc_pairs_cycles.  meta: the pairs' records and the sorted neighbour entries (sc_cycles_check.hpp); wide: the oriented fp64
       // poses; state: the round words and the two buffers of alive bytes
-      cyc_meta, cyc_wide, cyc_state;
+      cyc_meta, cyc_wide, cyc_state,
+      // sc_pairs_sync.  meta: the pairs' records, the sorted neighbour entries and the list starts; wide: the oriented fp64 poses and
+      // the pairs' weights; state: the round words, the two buffers of the sets' states and their tallies (sc_sync_check.hpp)
+      sync_meta, sync_wide, sync_state;
 };
 constexpr size_t N_WORKSPACE_BUFS = sizeof(Workspace) / sizeof(Buf);
 static_assert(std::is_standard_layout<Workspace>::value && alignof(Workspace) == alignof(Buf) && sizeof(Workspace) == N_WORKSPACE_BUFS * sizeof(Buf),

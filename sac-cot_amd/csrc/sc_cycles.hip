@@ -24,6 +24,7 @@
 #include "sc_arith.hpp"
 #include "sc_cycles_check.hpp"
 #include "sc_kernels.hpp"
+#include "sc_pose64.hpp"
 
 #pragma clang fp contract(off)
 
@@ -47,44 +48,6 @@ namespace {
 constexpr int CT = 256;           // threads of a workgroup of either launch: four waves, a pair each in a round
 constexpr int CYCLES_BLOCKS = 2048;  // a round's grid at most: eight workgroups a CU, the pairs dealt round-robin to the waves
 
-struct T64 { double R[9], t[3]; };
-
-__device__ __forceinline__ T64 load_t64(const double* __restrict__ w) {
-  T64 T;
-#pragma unroll
-  for (int c = 0; c < 9; c++) T.R[c] = w[c];
-#pragma unroll
-  for (int c = 0; c < 3; c++) T.t[c] = w[9 + c];
-  return T;
-}
-__device__ __forceinline__ void store_t64(double* __restrict__ w, const T64& T) {
-#pragma unroll
-  for (int c = 0; c < 9; c++) w[c] = T.R[c];
-#pragma unroll
-  for (int c = 0; c < 3; c++) w[9 + c] = T.t[c];
-}
-// (R^T, t'), t'_c = -((R_0c t_0 + R_1c t_1) + R_2c t_2)
-__device__ __forceinline__ T64 inverse_t64(const T64& A) {
-  T64 I;
-#pragma unroll
-  for (int i = 0; i < 3; i++)
-#pragma unroll
-    for (int j = 0; j < 3; j++) I.R[3 * i + j] = A.R[3 * j + i];
-#pragma unroll
-  for (int c = 0; c < 3; c++) I.t[c] = -((A.R[c] * A.t[0] + A.R[3 + c] * A.t[1]) + A.R[6 + c] * A.t[2]);
-  return I;
-}
-// M = B o A
-__device__ __forceinline__ T64 compose_t64(const T64& B, const T64& A) {
-  T64 M;
-#pragma unroll
-  for (int i = 0; i < 3; i++) {
-#pragma unroll
-    for (int j = 0; j < 3; j++) M.R[3 * i + j] = ((B.R[3 * i] * A.R[j] + B.R[3 * i + 1] * A.R[3 + j]) + B.R[3 * i + 2] * A.R[6 + j]);
-    M.t[i] = ((B.R[3 * i] * A.t[0] + B.R[3 * i + 1] * A.t[1]) + B.R[3 * i + 2] * A.t[2]) + B.t[i];
-  }
-  return M;
-}
 // tr and e2 of E = C o M: the diagonal of E.R and E.t are all a test reads, and each is the full composition's entry
 __device__ __forceinline__ void loop_error(const T64& C, const T64& M, double* tr, double* e2) {
   double d[3], t[3];
@@ -134,18 +97,7 @@ __global__ __launch_bounds__(CT) void cycles_prepare_kernel(const CyclesJob job)
     if (status == SC_OK && !finite12(M)) status = SC_EINVAL;
     const uint32_t* const r = job.rec + (size_t)CYCLES_REC_WORDS * p;
     edge = status == SC_OK && r[CW_LO] != r[CW_HI];
-    if (edge) {
-      T64 A;
-#pragma unroll
-      for (int c = 0; c < 9; c++) A.R[c] = (double)M[c];
-#pragma unroll
-      for (int c = 0; c < 3; c++) A.t[c] = (double)M[9 + c];
-      const T64 I = inverse_t64(A);
-      const bool fwd = r[CW_FWD] != 0;  // stored (lower, higher): the record is lower -> higher
-      double* const wide = job.wide + (size_t)24 * p;
-      store_t64(wide, fwd ? A : I);
-      store_t64(wide + 12, fwd ? I : A);
-    }
+    if (edge) store_oriented_pair(widen_t64(M), r, job.wide, p);
     job.alive[p] = edge ? 1 : 0;  // alive_0 (buffer 1 is written whole by round 1)
     CycleRecord out{};
     out.status = status;

@@ -1109,6 +1109,66 @@ struct CyclesJob {
 // pair: its two sorted lists intersected, the loops composed, the verdict), finish (the summary).
 void launch_pairs_cycles(const CyclesJob& job, hipStream_t st);
 
+// ---- absolute poses of a pair list's sets (sc_pairs_sync; sc_sync.hip) --------------------------------------------------------
+// The three output records: sc_sync_set, sc_sync_pair and sc_sync_summary of include/saccot.h, field for field (sc_sync.hip asserts
+// the sizes and the offsets).
+struct SyncSetRecord {
+  float Rt[12];
+  int32_t status;
+  uint32_t known_round, used, degenerate;
+  double X[12];
+};
+struct SyncPairRecord {
+  int32_t status;
+  uint32_t used;
+  double r2, e2;
+  uint32_t reserved[2];
+};
+struct SyncSummary {
+  uint32_t rounds, converged, known, used, changed_last, reserved[3];
+};
+// A set's state in one of the two buffers (buffer k & 1 holds X_k and known_k): 104 bytes.
+struct SyncState {
+  double X[12];
+  uint32_t known, pad;
+};
+// What a set's own wave keeps about it across the rounds (one writer: no second buffer).
+struct SyncInfo {
+  uint32_t known_round, used, degenerate, pad;
+};
+// The round words, ZERO at launch: changed[k], k = 1 .. max_rounds, the sets round k changed — a round's launch returns at once when
+// the round before changed none, and writes nothing, so every later word stays 0 as well; changed[0] is never read.  known, used,
+// done: the finish launch's tallies and its ticket.
+struct SyncCtl {
+  uint32_t changed[257];
+  uint32_t known, used, done;
+};
+// rec, entries: the pairs' records and the sorted neighbour lists (sc_cycles_check.hpp), off: the n_sets + 1 list starts; pose, use,
+// weight: the caller's (use, weight: nullptr or an array); wide: 2 x 12 doubles a pair; wt: a double a pair, 0.0 where the pair is
+// not usable; state: 2 x n_sets; info: n_sets.
+struct SyncJob {
+  const uint32_t* rec;
+  const uint64_t* entries;
+  const uint32_t* off;
+  const void* pose;
+  const void* use;
+  const float* weight;
+  double* wide;
+  double* wt;
+  SyncState* state;
+  SyncInfo* info;
+  SyncCtl* ctl;
+  SyncSetRecord* set;
+  SyncPairRecord* pair;
+  SyncSummary* sum;
+  double r2_max, e2_max;
+  uint32_t n_sets, n_pairs, pose_stride, use_stride, anchor, max_rounds;
+  int status;  // a record holds a status at byte 48
+};
+// max_rounds + 2 launches: prepare (a thread per pair: validity, use, weight, the oriented fp64 poses; a thread per set: X_0), a
+// launch per round (a wave per set, a lane per slot of the header's sum), finish (the set records, the residuals, the summary).
+void launch_pairs_sync(const SyncJob& job, hipStream_t st);
+
 // ---- descriptor matching for a batch of small problems (sc_match_batch; sc_match_batch.hip) -----------------
 // Problem b owns rows [src_off[b], src_off[b + 1]) of fsrc and [tgt_off[b], tgt_off[b + 1]) of ftgt (1 .. MATCH_BATCH_MAX_N rows
 // each, checked by the caller) and the output slot that starts at entry slot[b] = src_off[b] * knn.  tile_map: n_tiles pairs
