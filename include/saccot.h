@@ -1578,7 +1578,8 @@ int sc_merge_poses_batch(sc_ctx* ctx, const float* src, const float* tgt, const 
  * The pairs chain leaves a relative pose per listed pair and, behind sc_pairs_cycles, a verdict on which pairs close consistent
  * loops.  What its caller — fragment registration, loop closure, multi-scan alignment — wants next is where the sets lie in ONE
  * frame.  These entries place every set that the list connects to an anchor set, on the device, stream-ordered behind
- * sc_pairs_cycles_device with no host word in between: the poses they leave are legal priors for sc_match_guided* as they stand.
+ * sc_pairs_cycles_device with no host word in between: the poses they leave are priors for sc_match_guided* as they stand
+ * (where every component fits fp32: "Outputs" below).
  *
  * The method is anchored Jacobi averaging: breadth-first propagation and refinement in one rule.  X_s maps set s's coordinates
  * into the anchor's frame; pair p, stored (a, b) with pose T (a onto b), is the constraint X_a = X_b o T.  known_0 = {anchor},
@@ -1639,9 +1640,14 @@ int sc_merge_poses_batch(sc_ctx* ctx, const float* src, const float* tgt, const 
  *   residual   of pair p stored (a, b), when usable(p) and a and b are both in known_K: Q = X_K(b) o T_p(a->b) — the record
  *              itself —, r2 = the sum over the nine entries, row-major, of (X_K(a).R_ij - Q.R_ij) squared, added left to right,
  *              e2 = likewise over the three of t.
- * Outputs.  sc_sync_set (160 bytes) per set at d_set[s]: Rt is X_K(s) rounded once to fp32 and status SC_OK, so that d_set is an
- * array of legal pose records, with a status, of stride 160 for every pose entry; a set that was never reached has Rt and X all
- * zero and status SC_ENOHYP.  sc_sync_pair (32 bytes) per pair at d_pair[p].  sc_sync_summary (32 bytes) at d_sum.
+ * Outputs.  sc_sync_set (160 bytes) per set at d_set[s]: Rt is X_K(s) rounded once to fp32 and status SC_OK, so that d_set has the
+ * layout of an array of pose records, with a status, of stride 160 for every pose entry — sc_pairs_sync itself among them; a set
+ * that was never reached has Rt and X all zero and status SC_ENOHYP.  The rounding is the only one: a component of X_K whose
+ * magnitude exceeds FLT_MAX becomes +-inf in Rt.  That can happen with finite inputs — translations add along a path, and records
+ * that are no rotations multiply them: entries near FLT_MAX reach |X_K.t| of 1e76 within a few hops.  The status stays SC_OK and X
+ * holds the finite value; every pose entry treats such a record as it treats any record that is not finite (fed back to
+ * sc_pairs_sync: SC_EINVAL for that pair).  A caller that feeds d_set on looks at X, or lets the next entry's status say so.
+ * sc_sync_pair (32 bytes) per pair at d_pair[p].  sc_sync_summary (32 bytes) at d_sum.
  * Forms.  sc_pairs_sync_device: poses, use, weight and outputs in HBM; it enqueues and returns without waiting, reads no host
  * word, and its number of stream operations depends on max_rounds only (a copy, a memset, max_rounds + 2 launches; a round's launch
  * returns at once when the round before changed no set).  (It may wait for the previous batch call's copy out of the staging area

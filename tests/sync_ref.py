@@ -6,7 +6,9 @@ element by element in the header's order, vectorised over the sets (a numpy ufun
 einsum: a BLAS may fuse or reorder).  The 64 slots of a set's sum are 64 columns of an array, entry i adds into column i mod 64 in
 increasing i, and the fold is the header's: for h = 32 .. 1, columns [0, h) += columns [h, 2h).  The composition, the inverse and the
 widening are tests/cycles_ref.py's.  The thresholds are arguments: the GPU tests pass the two values sc_sync_thresholds returns.
-Only `sync` is the reference; the families are built with whatever is convenient.
+Only `sync` is the reference; the families are built with whatever is convenient.  The families of
+tests/test_gpu_pairs_sync_range.py stand at the end; `integers` is exact24's and exact_ring's expectation in np.int64, which shares
+no code with `sync`.
 """
 import functools
 
@@ -176,7 +178,8 @@ def sync(n_sets, pairs, rt, r2_max, e2_max, anchor=0, max_rounds=32, use=None, w
     sets = np.zeros(n_sets, SET_DTYPE)
     Xa = np.stack(X, axis=1)
     sets["X"] = Xa
-    sets["Rt"] = Xa.astype(np.float32)
+    with np.errstate(over="ignore"):  # a component past FLT_MAX rounds to an infinity
+        sets["Rt"] = Xa.astype(np.float32)
     sets["status"] = np.where(known, SC_OK, UNREACHED)
     sets["known_round"], sets["used"], sets["degenerate"] = known_round, used, degenerate
     res = np.zeros(P, PAIR_DTYPE)
@@ -204,6 +207,7 @@ class Family:
         self.n_sets, self.pairs, self.rt = n_sets, np.ascontiguousarray(pairs, np.uint32).reshape(-1, 2), np.ascontiguousarray(rt, np.float32)
         self.R, self.t = R, t  # the absolute poses the list was made from, where there are any
         self.params = dict(dict(rot_tol=TOL, trans_tol=TOL), **params)
+        self.use = self.weight = self.statuses = None  # per pair, where a family brings them
 
 
 def truth(f, anchor=0):
@@ -326,16 +330,27 @@ def degenerate():
 CUT_SET, CUT_NEAR, CUT_STEP, CUT_TOL = 5, 9, 2.0 ** -3, 2.0 ** -4
 
 
-@functools.lru_cache(maxsize=None)
-def cut24():
-    rng = np.random.default_rng(CR.EXACT24_SEED)  # exact24's draws, in its order
+def _exact_world():
+    """(pairs, R, t) of cycles_ref.exact24 before its corruption, from its draws in its order: all 276 pairs in random stored
+    directions and shuffled, 24 cube rotations and integer translations in [-8, 8], as np.int64"""
+    rng = np.random.default_rng(CR.EXACT24_SEED)
     pairs = CR._complete(24, rng)
     R = [CR.GROUP24[g] for g in rng.permutation(24)]
-    t = rng.integers(-8, 9, (24, 3))
-    rt = np.zeros((276, 12))
+    return pairs, R, rng.integers(-8, 9, (24, 3))
+
+
+def _exact_records(pairs, R, t):
+    rt = np.zeros((len(pairs), 12))
     for p, (a, b) in enumerate(pairs.tolist()):
         rt[p, :9] = (R[b].T @ R[a]).ravel()
         rt[p, 9:] = R[b].T @ (t[a] - t[b])
+    return rt
+
+
+@functools.lru_cache(maxsize=None)
+def cut24():
+    pairs, R, t = _exact_world()
+    rt = _exact_records(pairs, R, t)
     use = np.ones(276, np.uint32)
     for p, (a, b) in enumerate(pairs.tolist()):
         if CUT_SET in (a, b):
@@ -346,3 +361,125 @@ def cut24():
     f = Family(24, pairs, rt, R, t.astype(np.float64), rot_tol=0.0, trans_tol=CUT_TOL)
     f.use = use
     return f
+
+
+# ---- the families of the range tests: on the rotation cut, exact in integers, at the ends of the number range, to the round limit ---
+# (tests/test_sync_abi.py asserts what the reference measures on them, as literals)
+
+# The rotation cut.  Round 1 places sets 1, 2 and 3 at the identity by the anchor alone.  In round 2 set 1 sums I + 2 diag(1, -1, -1)
+# = diag(3, -1, -1): orthogonal rows, no Jacobi turn, rot gives diag(1, -1, -1) exactly and dR2 = 8.0 = r2_max at rot_tol 2.0.  Sets 2
+# and 3 sum I + diag(1, -1, -1) = diag(2, 0, 0), of rank one: known sets that meet a degenerate sum and keep their pose.
+RCUT_TOL = 2.0
+
+
+@functools.lru_cache(maxsize=None)
+def rcut():
+    I = [1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0]
+    half = [1, 0, 0, 0, -1, 0, 0, 0, -1, 0, 0, 0]
+    return Family(4, [(1, 0), (2, 0), (3, 0), (1, 2), (1, 3)], np.array([I, I, I, half, half], np.float32), rot_tol=RCUT_TOL, trans_tol=0.0)
+
+
+@functools.lru_cache(maxsize=None)
+def exact24(anchor=0):
+    """cut24's world with nothing corrupted and every pair usable: every prediction of a set is the truth, a sum of k equal signed
+    permutation matrices has orthogonal rows and k t / k is exact, so every round is exact"""
+    pairs, R, t = _exact_world()
+    return Family(24, pairs, _exact_records(pairs, R, t), R, t, rot_tol=0.0, trans_tol=0.0, anchor=anchor)
+
+
+@functools.lru_cache(maxsize=None)
+def exact_ring():
+    """the same 24 absolute poses, the ring pairs (i, i + 1 mod 24) only, every other one stored reversed"""
+    _all, R, t = _exact_world()
+    pairs = np.array([(i, (i + 1) % 24) if i % 2 else ((i + 1) % 24, i) for i in range(24)])
+    return Family(24, pairs, _exact_records(pairs, R, t), R, t, rot_tol=0.0, trans_tol=0.0)
+
+
+def integers(f, anchor=0):
+    """(n_sets, 12) np.int64: every set's pose in the anchor's frame from the integer absolute poses, in integer arithmetic — none
+    of the reference's code"""
+    out = np.zeros((f.n_sets, 12), np.int64)
+    Ra, ta = np.asarray(f.R[anchor], np.int64), np.asarray(f.t[anchor], np.int64)
+    for s in range(f.n_sets):
+        out[s, :9] = (Ra.T @ np.asarray(f.R[s], np.int64)).ravel()
+        out[s, 9:] = Ra.T @ (np.asarray(f.t[s], np.int64) - ta)
+    return out
+
+
+SCALES_EXACT = (-100, -60, 60, 100, 120)  # 2^k of these leaves every translation of k24 and TOL a normal float: exact
+SCALE_UNDER = -140  # trans_tol becomes 0.0 and translations go subnormal: rounded
+
+
+@functools.lru_cache(maxsize=None)
+def scaled(k, noise=True):
+    """k24 with every translation and trans_tol multiplied by 2^k, in float (cycles_ref.scaled's rule)"""
+    f = k24(noise)
+    rt = f.rt.copy()
+    rt[:, 9:] = np.ldexp(rt[:, 9:], k).astype(np.float32)
+    return Family(f.n_sets, f.pairs, rt, f.R, f.t, rot_tol=TOL, trans_tol=float(np.ldexp(np.float32(TOL), k).astype(np.float32)))
+
+
+WEIGHT_SEED = 2401
+
+
+@functools.lru_cache(maxsize=None)
+def weight_scaled(k):
+    """k24 with one fixed weight vector, 1 .. 2 times 2^-20 .. 2^20, multiplied by 2^k in float"""
+    rng = np.random.default_rng(WEIGHT_SEED)
+    f = k24()
+    g = Family(f.n_sets, f.pairs, f.rt, f.R, f.t)
+    g.weight = np.ldexp(np.ldexp(rng.uniform(1, 2, 276), rng.integers(-20, 21, 276)).astype(np.float32), k).astype(np.float32)
+    return g
+
+
+FLT_MAX = np.float32(CR.FLT_MAX)
+WEIGHTS_RANGE_PLANTED = {7: np.float32(1e-45), 19: FLT_MAX, 101: np.float32(-0.0), 202: np.float32(0.0)}  # pair -> weight
+
+
+@functools.lru_cache(maxsize=None)
+def weights_range():
+    """k24 with weights over the whole fp32 range, 1 .. 2 times 2^-149 .. 2^127, and four planted: the smallest subnormal, FLT_MAX and
+    both zeros (which are not greater than 0: those two pairs are not usable)"""
+    rng = np.random.default_rng(WEIGHT_SEED + 1)
+    f = k24()
+    g = Family(f.n_sets, f.pairs, f.rt, f.R, f.t)
+    g.weight = np.ldexp(rng.uniform(1, 2, 276), rng.integers(-149, 128, 276)).astype(np.float32)
+    for p, w in WEIGHTS_RANGE_PLANTED.items():
+        g.weight[p] = w
+    return g
+
+
+@functools.lru_cache(maxsize=None)
+def hostile():
+    """cycles_ref.hostile24's records — random finite bit patterns over the whole exponent range, a FLT_MAX triangle, subnormals, -0.0
+    and an all-zero record — as the poses of k24's list"""
+    f = CR.hostile24()
+    return Family(24, f.pairs, f.rt)
+
+
+RING40_SEED = 40
+
+
+@functools.lru_cache(maxsize=None)
+def ring40():
+    """the header's bare ring: 40 noisy sets, the pairs (i, i + 1 mod 40) and nothing else.  It diffuses."""
+    pairs = np.array([(i, (i + 1) % 40) for i in range(40)])
+    R, t = CR.absolute_poses(40, RING40_SEED)
+    return Family(40, pairs, noisy(CR.relative_poses(pairs, R, t), RING40_SEED + 1), R, t, max_rounds=256)
+
+
+@functools.lru_cache(maxsize=None)
+def sparse(n=WIDE_SETS):
+    """chain()'s 41 pairs among n sets: all but 42 of the sets have empty lists, and the sets past one trip of the round kernel's
+    grid loop have nothing to do"""
+    f = chain()
+    return Family(n, f.pairs, f.rt, max_rounds=64)
+
+
+def self_star(sets, anchor):
+    """a first call's set records as the pose records of a second: the pairs (s, anchor) for every s — the anchor's a self pair —,
+    pair s's record the 160 bytes of set s, whose Rt maps s onto the anchor and whose status stands at byte 48"""
+    n = len(sets)
+    g = Family(n, np.stack([np.arange(n), np.full(n, anchor)], axis=1), sets["Rt"], anchor=anchor, flags=STATUS)
+    g.statuses = sets["status"].astype(np.int32)
+    return g

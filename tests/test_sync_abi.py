@@ -152,7 +152,8 @@ def test_the_host_rules_under_the_sanitizers(tmp_path):
 def _run(f, **kw):
     p = dict(f.params); p.update(kw)
     thr = SR.thresholds(p.pop("rot_tol"), p.pop("trans_tol"))
-    return SR.sync(f.n_sets, f.pairs, f.rt, *thr, **p)
+    statuses = f.statuses if p.pop("flags", 0) & SR.STATUS else None
+    return SR.sync(f.n_sets, f.pairs, f.rt, *thr, use=f.use, weight=f.weight, statuses=statuses, **p)
 
 
 def _noise_put_in(noisy, exact):
@@ -305,3 +306,204 @@ def test_invalid_unused_and_unweighted_pairs_take_part_in_nothing():
     # the weights matter: the same list with every weight 1 is another result
     plain = SR.sync(24, pairs[others], rt[others], *SR.thresholds(SR.TOL, SR.TOL))
     assert plain[0]["X"].tobytes() != sets["X"].tobytes()
+
+
+# ---- the families of tests/test_gpu_pairs_sync_range.py: what the reference measures on them, as literals -------------------------
+def _summary(s, n=4):
+    return tuple(int(s[name]) for name in ("rounds", "converged", "known", "used", "changed_last")[:n])
+
+
+RCUT_BELOW = float(np.nextafter(np.float32(SR.RCUT_TOL), np.float32(0)))
+RCUT_ROUNDS = {SR.RCUT_TOL: (2, 1), RCUT_BELOW: (3, 1)}  # rot_tol -> (rounds, converged)
+RCUT_DEGENERATE, RCUT_USED, RCUT_R1 = [0, 0, 1, 1], [0, 3, 2, 2], [1, 0, 0, 0, -1, 0, 0, 0, -1]
+EXACT24_SUMMARY, EXACT_RING_SUMMARY = (2, 1, 24, 276), (13, 1, 24, 24)
+EXACT_RING_HOPS = list(range(13)) + list(range(11, 0, -1))
+K24_SUMMARY = (4, 1, 24, 276)  # at every exact scale
+SCALE_UNDER_SUMMARY = (32, 0, 24, 276, 23)
+WEIGHT_SCALED_SUMMARY = (26, 1, 24, 276)  # at k = 0, -100 and 100
+WEIGHT_UNDER = ((28, 1, 24, 228), 48, 166)  # at k = -140: the summary, the weights that are 0.0, those that are subnormal
+WEIGHTS_RANGE_SUMMARY = (32, 0, 24, 274, 23)
+# hostile: (anchor, max_rounds) -> summary; the sets whose degenerate is 1; the components of Rt that are not finite
+HOSTILE = {(0, 32): ((32, 0, 24, 276, 23), [3, 7], 69), (0, 256): ((256, 0, 24, 276, 23), [3, 7], 69), (11, 32): ((32, 0, 24, 276, 23), [], 69)}
+RING40 = {(1e-6, 256): (256, 0, 40, 40, 18), (1e-4, 256): (120, 1, 40, 40, 0), (1e-4, 1): (1, 0, 3, 2, 2)}  # (tolerances, max_rounds) -> summary
+SPARSE_SUMMARY = (42, 1, 42, 41, 0)
+# family -> the anchor, the second call's summary (hostile: the anchor aside every set's Rt has an infinite component, under SC_OK)
+SELF_STAR = {"k24": (3, (2, 1, 24, 23)), "two_components": (0, (2, 1, 24, 23)), "hostile": (0, (1, 1, 1, 0))}
+
+
+def _rounds_with(compare, trace, r2_max, e2_max):
+    """(rounds, converged) of a run whose rounds are `trace`, the header's rule for `changed` restated with `compare` for its `>`"""
+    known = None
+    for k, (_changed, dR2, dt2, update) in enumerate(trace, 1):
+        fresh = update if known is None else update & ~known
+        if not (update & (fresh | compare(dR2, r2_max) | compare(dt2, e2_max))).any():
+            return k, 1
+        known = update if known is None else known | update
+    return len(trace), 0
+
+
+def test_rcut_sits_on_the_rotation_cut_and_a_known_set_meets_a_degenerate_sum():
+    f = SR.rcut()
+    assert f.n_sets == 4 and f.pairs.tolist() == [[1, 0], [2, 0], [3, 0], [1, 2], [1, 3]] and not f.rt[:, 9:].any()
+    assert SR.thresholds(SR.RCUT_TOL, 0.0) == (8.0, 0.0) and SR.thresholds(RCUT_BELOW, 0.0)[0] < 8.0
+    traces = {}
+    for tol, want in RCUT_ROUNDS.items():
+        traces[tol] = []
+        sets, pairs, s = _run(f, rot_tol=tol, trace=traces[tol])
+        assert _summary(s, 2) == want and len(traces[tol]) == want[0], tol
+        assert sets["degenerate"].tolist() == RCUT_DEGENERATE and sets["used"].tolist() == RCUT_USED and sets["X"][1][:9].tolist() == RCUT_R1
+        assert (sets["status"] == SC_OK).all() and sets["known_round"].tolist() == [0, 1, 1, 1]  # sets 2 and 3 stay known, at the identity
+        assert sets["X"][2].tolist() == sets["X"][3].tolist() == [1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0]
+    # round 1: every set placed by the anchor alone; round 2: set 1 turns by exactly dR2 = 8.0 = r2_max and is quiet, sets 2 and 3
+    # meet a sum of rank one and are not updated
+    changed, dR2, dt2, update = traces[SR.RCUT_TOL][0]
+    assert changed.tolist() == update.tolist() == [False, True, True, True]
+    changed, dR2, dt2, update = traces[SR.RCUT_TOL][1]
+    assert dR2[1] == 8.0 == SR.thresholds(SR.RCUT_TOL, 0.0)[0] and dt2[1] == 0.0 and update.tolist() == [False, True, False, False] and not changed.any()
+    assert traces[RCUT_BELOW][1][0].tolist() == [False, True, False, False] and not traces[RCUT_BELOW][2][0].any()
+    # the bite: the rule restated over the three rounds (a round's sums do not depend on the tolerances) agrees with the reference
+    # with `>` at both tolerances, and with `>=` it runs a third round ON the cut
+    full = traces[RCUT_BELOW]
+    for tol, want in RCUT_ROUNDS.items():
+        assert _rounds_with(np.greater, full, *SR.thresholds(tol, 0.0)) == want
+    mutant = _rounds_with(np.greater_equal, full, *SR.thresholds(SR.RCUT_TOL, 1.0))  # (trans_tol 1: only the rotation cut is sat on)
+    assert mutant == (3, 1) != RCUT_ROUNDS[SR.RCUT_TOL] and _rounds_with(np.greater, full, *SR.thresholds(SR.RCUT_TOL, 1.0)) == (2, 1)
+
+
+def test_exact24_and_the_exact_ring_equal_the_integers():
+    """the expectation is SR.integers: np.int64 products of the absolute poses, none of the reference's arithmetic"""
+    cut = SR.cut24()
+    for anchor in (0, 13):
+        f = SR.exact24(anchor)
+        assert (f.pairs == cut.pairs).all() and all((a == b).all() for a, b in zip(f.R, cut.R)) and (f.t == cut.t).all()  # cut24's world
+        assert (f.rt == np.round(f.rt)).all() and f.t.dtype == np.int64 and np.abs(f.t).max() <= 8 and f.params["anchor"] == anchor
+        want = SR.integers(f, anchor)
+        assert want.dtype == np.int64 and want[anchor].tolist() == [1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0] and (want == SR.truth(f, anchor)).all()
+        sets, pairs, s = _run(f)
+        assert _summary(s) == EXACT24_SUMMARY and (sets["X"] == want).all() and (sets["Rt"] == want).all()
+        assert not pairs["r2"].any() and not pairs["e2"].any() and (pairs["used"] == 1).all()  # exactly 0.0, on all 276 pairs
+    ring = SR.exact_ring()
+    assert len(ring.pairs) == 24 and (ring.pairs[:, 0] > ring.pairs[:, 1]).sum() == 12 + 1 and (ring.t == cut.t).all()
+    assert sorted(tuple(sorted(p)) for p in ring.pairs.tolist()) == sorted(tuple(sorted((i, (i + 1) % 24))) for i in range(24))
+    sets, pairs, s = _run(ring)
+    want = SR.integers(ring)
+    assert _summary(s) == EXACT_RING_SUMMARY and (sets["X"] == want).all() and (sets["Rt"] == want).all() and not pairs["r2"].any() and not pairs["e2"].any()
+    assert sets["known_round"].tolist() == EXACT_RING_HOPS == [min(i, 24 - i) for i in range(24)]
+
+
+def test_scaled_translations_and_weights_are_exact_where_they_are_used_as_exact():
+    base = SR.k24()
+    sets0, pairs0, s0 = _run(base)
+    assert _summary(s0) == K24_SUMMARY
+    for k in SR.SCALES_EXACT:
+        g = SR.scaled(k)
+        assert (np.ldexp(g.rt[:, 9:].astype(np.float64), -k) == base.rt[:, 9:]).all() and (g.rt[:, :9] == base.rt[:, :9]).all()  # nothing was rounded
+        assert np.ldexp(np.float64(np.float32(g.params["trans_tol"])), -k) == np.float32(SR.TOL) and np.isfinite(g.rt).all()
+        sets, pairs, s = _run(g)
+        assert s.tobytes() == s0.tobytes() and sets["X"][:, :9].tobytes() == sets0["X"][:, :9].tobytes() and pairs["r2"].tobytes() == pairs0["r2"].tobytes()
+        assert sets["X"][:, 9:].tobytes() == np.ldexp(sets0["X"][:, 9:], k).tobytes() and pairs["e2"].tobytes() == np.ldexp(pairs0["e2"], 2 * k).tobytes()
+        assert (pairs["e2"] > 0).all() and np.isfinite(pairs["e2"]).all()
+    g = SR.scaled(SR.SCALE_UNDER)  # the tolerance underflows to 0.0 and translations are rounded to subnormals: no relation holds
+    tiny = np.abs(g.rt[:, 9:])
+    assert g.params["trans_tol"] == 0.0 and ((tiny > 0) & (tiny < np.finfo(np.float32).tiny)).sum() > 100
+    assert (np.ldexp(g.rt[:, 9:].astype(np.float64), -SR.SCALE_UNDER) != base.rt[:, 9:]).any()
+    assert _summary(_run(g)[2], 5) == SCALE_UNDER_SUMMARY
+    w0 = SR.weight_scaled(0)
+    e = np.frexp(w0.weight)[1] - 1
+    assert e.min() == -20 and e.max() == 20 and len(set(e.tolist())) == 41
+    r0 = _run(w0)
+    assert _summary(r0[2]) == WEIGHT_SCALED_SUMMARY and r0[0].tobytes() != sets0.tobytes()  # the weights matter
+    for k in (-100, 100):
+        g = SR.weight_scaled(k)
+        assert (np.ldexp(g.weight.astype(np.float64), -k) == w0.weight).all() and (g.weight >= np.finfo(np.float32).tiny).all() and np.isfinite(g.weight).all()
+        assert all(a.tobytes() == b.tobytes() for a, b in zip(_run(g), r0))  # every output byte
+    g = SR.weight_scaled(SR.SCALE_UNDER)
+    s = _run(g)[2]
+    assert (_summary(s), int((g.weight == 0).sum()), int(((g.weight > 0) & (g.weight < np.finfo(np.float32).tiny)).sum())) == WEIGHT_UNDER
+
+
+def test_weights_over_the_whole_range():
+    g = SR.weights_range()
+    w = g.weight
+    assert w.dtype == np.float32 and w[[7, 19, 101, 202]].view(np.uint32).tolist() == [1, 0x7F7FFFFF, 0x80000000, 0]
+    e = np.frexp(w[w > 0].astype(np.float64))[1] - 1
+    assert e.min() == -149 and e.max() == 127 and np.isfinite(w).all() and (w == 0).sum() == 2 and ((w > 0) & (w < np.finfo(np.float32).tiny)).sum() > 10
+    sets, pairs, s = _run(g)
+    assert _summary(s, 5) == WEIGHTS_RANGE_SUMMARY and not sets["degenerate"].any() and np.isfinite(sets["X"]).all() and np.isfinite(sets["Rt"]).all()
+    assert np.flatnonzero(pairs["used"] == 0).tolist() == [101, 202]
+
+
+def _hostile_facts(sets, pairs):
+    return [int(x) for x in np.flatnonzero(sets["degenerate"])], int((~np.isfinite(sets["Rt"])).sum())
+
+
+def test_hostile_records_overflow_fp32_under_status_ok():
+    """The finding the header now states: every X is finite — |t| up to 4e76 — and 69 components of Rt, X rounded once to fp32, are
+    infinite, under status SC_OK."""
+    f = SR.hostile()
+    assert f.rt.tobytes() == CR.hostile24().rt.tobytes() and np.isfinite(f.rt).all() and (f.pairs == SR.k24().pairs).all()
+    for (anchor, max_rounds), (summary, degenerate, not_finite) in HOSTILE.items():
+        sets, pairs, s = _run(f, anchor=anchor, max_rounds=max_rounds)
+        assert _summary(s, 5) == summary and _hostile_facts(sets, pairs) == (degenerate, not_finite), (anchor, max_rounds)
+        assert (sets["degenerate"] <= 1).all() and (sets["status"] == SC_OK).all() and (pairs["status"] == SC_OK).all()
+        assert np.isfinite(sets["X"]).all() and 1e76 < np.abs(sets["X"][:, 9:]).max() < 1e77
+        assert np.isfinite(pairs["r2"]).all() and np.isfinite(pairs["e2"]).all() and 1e77 < pairs["r2"].max() < 1e79
+        assert np.isinf(sets["Rt"][~np.isfinite(sets["Rt"])]).all() and (np.abs(sets["X"])[np.isinf(sets["Rt"])] > CR.FLT_MAX).all()
+    # the bite: a result whose Rt stops at +-FLT_MAX where it should be infinite is told apart by the GPU tests' comparison
+    from test_gpu_pairs_sync import _assert_same
+    exp = _run(f)
+    _assert_same(exp, _run(f), "hostile against itself")
+    clamped = exp[0].copy()
+    clamped["Rt"] = np.clip(exp[0]["Rt"], -SR.FLT_MAX, SR.FLT_MAX)
+    assert (clamped["Rt"] != exp[0]["Rt"]).sum() == 69 and np.isfinite(clamped["Rt"]).all()
+    try:
+        _assert_same((clamped, exp[1], exp[2]), exp, "hostile, Rt clamped")
+    except AssertionError as e:
+        assert "Rt" in str(e)
+    else:
+        raise AssertionError("a clamped Rt passes the comparison")
+
+
+def test_the_ring_of_40_to_the_round_limit():
+    f = SR.ring40()
+    assert f.n_sets == 40 and len(f.pairs) == 40 and f.params["max_rounds"] == 256
+    for (tol, max_rounds), want in RING40.items():
+        sets, pairs, s = _run(f, rot_tol=tol, trans_tol=tol, max_rounds=max_rounds)
+        assert _summary(s, 5) == want, (tol, max_rounds)
+    assert np.flatnonzero(sets["status"] == SC_OK).tolist() == [0, 1, 39]  # one round: the anchor and its two neighbours
+    assert 256 - RING40[(1e-4, 256)][0] > 30  # launches that find the stop ahead of them
+
+
+def test_sparse_is_the_chain_among_sets_with_empty_lists():
+    f, c = SR.sparse(), SR.chain()
+    assert f.n_sets == SR.WIDE_SETS > 2048 * 4 and (f.pairs == c.pairs).all() and f.rt.tobytes() == c.rt.tobytes()
+    assert sorted(set(SR.adjacency(f.pairs)[0].tolist())) == list(range(42)) and f.params["max_rounds"] == 64
+    # (a set's round reads its own list and its neighbours: run here among 200 sets, which takes a twentieth of the time; the GPU test
+    # runs the reference at 8200 and holds it to the same summary)
+    few = SR.sparse(200)
+    assert (few.pairs == f.pairs).all() and few.rt.tobytes() == f.rt.tobytes() and few.params == f.params
+    sets, pairs, s = _run(few)
+    assert _summary(s, 5) == SPARSE_SUMMARY and (sets["status"] == SC_ENOHYP).sum() == 200 - 42
+    empty = np.zeros(200 - 42, SR.SET_DTYPE); empty["status"] = SC_ENOHYP
+    assert sets[42:].tobytes() == empty.tobytes()  # all zero but the status
+    alone = _run(c, max_rounds=64)
+    assert sets[:42].tobytes() == alone[0].tobytes() and pairs.tobytes() == alone[1].tobytes() and s.tobytes() == alone[2].tobytes()
+
+
+def test_a_result_fed_back_as_pose_records():
+    for name, (anchor, want) in SELF_STAR.items():
+        f = getattr(SR, name)()
+        first = _run(f, anchor=anchor)
+        g = SR.self_star(first[0], anchor)
+        assert g.pairs.tolist() == [[s, anchor] for s in range(f.n_sets)] and g.rt.tobytes() == first[0]["Rt"].tobytes() and g.params["flags"] == SR.STATUS
+        sets, pairs, s = _run(g)
+        assert _summary(s) == want
+        # SC_ENOHYP passes through as the pair's status, and a record that is not finite is SC_EINVAL whatever its status word says
+        finite = np.isfinite(first[0]["Rt"]).all(axis=1)
+        legal = (first[0]["status"] == SC_OK) & finite
+        assert (pairs["status"] == np.where((first[0]["status"] == SC_OK) & ~finite, SC_EINVAL, first[0]["status"])).all()
+        assert (sets["status"] == np.where(legal, SC_OK, SC_ENOHYP)).all() and not sets["X"][~legal].any()
+        assert pairs["used"].tolist() == [int(ok and s_ != anchor) for s_, ok in enumerate(legal)]
+        assert (~legal).sum() == {"k24": 0, "two_components": 6, "hostile": 23}[name]
+        if name != "hostile":
+            assert np.abs(sets["X"] - first[0]["X"]).max() < 1e-7  # (a sanity note: fp32 rounding and one rot)
