@@ -8,7 +8,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsaccot.so")
-SOURCES = ["sc_compat.hip", "sc_tri_edges.hip", "sc_tri_prune.hip", "sc_tri.hip", "sc_kabsch.hip", "sc_score.hip", "sc_filter.hip", "sc_gram_guard.hip", "sc_final.hip", "sc_sort.hip", "sc_capi.hip", "sc_capi_tri.hip", "sc_capi_frame.hip", "sc_capi_hooks.hip", "sc_capi_peel.hip", "sc_capi_match.hip", "sc_capi_polish.hip", "sc_multi.hip", "sc_peel.hip", "sc_match.hip",
+SOURCES = ["sc_stage.hip", "sc_compat.hip", "sc_rows.hip", "sc_scan.hip", "sc_tri_edges.hip", "sc_tri_prune.hip", "sc_tri.hip", "sc_kabsch.hip", "sc_score.hip", "sc_filter.hip", "sc_gram_guard.hip", "sc_final.hip", "sc_sort.hip", "sc_capi.hip", "sc_capi_compat.hip", "sc_capi_tri.hip", "sc_capi_frame.hip", "sc_capi_hooks.hip", "sc_capi_peel.hip", "sc_capi_match.hip", "sc_capi_polish.hip", "sc_multi.hip", "sc_peel.hip", "sc_match.hip",
            "sc_polish.hip", "sc_capi_batch.hip", "sc_batch.hip", "sc_capi_match_batch.hip", "sc_match_batch.hip",
            "sc_capi_polish_batch.hip", "sc_polish_batch.hip", "sc_capi_instances_batch.hip", "sc_capi_pairs.hip", "sc_capi_match_guided_batch.hip", "sc_capi_match_guided_poses.hip",
            "sc_capi_info_batch.hip", "sc_info_batch.hip", "sc_capi_info_frame.hip", "sc_info_frame.hip",

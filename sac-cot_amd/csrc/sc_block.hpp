@@ -6,7 +6,7 @@
 //   block_max_u64 / block_lexmax_u64     maximum of a key, and lexicographic maximum of a key pair, over a 256-thread workgroup
 //   last_workgroup_sum                   "one returning atomic, the last workgroup holds the total": the tail of a launch that publishes once
 //   lb_*                                 decoupled look-back over the tiles of one launch
-// (mask_above and group_exscan came from sc_tri.hip; wave_inscan replaces the single-value loops sc_compat.hip and sc_tri.hip wrote out by hand.)
+// (mask_above and group_exscan came from sc_tri.hip; wave_inscan replaces the single-value loops sc_rows.hip, sc_scan.hip and sc_tri.hip wrote out by hand.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

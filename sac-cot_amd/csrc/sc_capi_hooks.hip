@@ -1,5 +1,5 @@
 // sc_capi_hooks.hip — the C ABI's stage hooks (include/saccot.h, sc_*_host): one stage at a time on host arrays, for the tests that
-// compare a stage with the CPU restatement.  Host-only, on the context and the stage sequencers of sc_capi.hip (sc_ctx.hpp).
+// compare a stage with the CPU restatement.  Host-only, on the context and the stage sequencers of sc_capi.hip, sc_capi_compat.hip and sc_capi_tri.hip (sc_ctx.hpp).
 #include "sc_ctx.hpp"
 
 using namespace sc;

@@ -53,13 +53,14 @@ static int polish_run(sc_ctx* c, const sc_polish_params* pp, float* d_Rt, uint8_
   PolishCand* cand = c->polish_cand.as<PolishCand>();
   uint32_t* n_cand = reinterpret_cast<uint32_t*>(cand + POLISH_MAX_CAND);
   SC_TRY(rec(c, 0));
-  launch_polish_select(c->cnt.as<uint32_t>(), c->sel_key.as<uint32_t>(), ps.T_eff, c->rt.as<float>(), sh.ld_local, want, cand, n_cand, st);
+  const PolishSet set{cand, n_cand, want};
+  launch_polish_select(set, c->cnt.as<uint32_t>(), c->sel_key.as<uint32_t>(), ps.T_eff, c->rt.as<float>(), sh.ld_local, st);
   SC_TRY(rec(c, 1));
-  launch_polish(points_of(c), cand, n_cand, want, pp->max_iter, ps.dv.tau2, score_thr(ps.dv, p->score_mode), p->score_mode, c->polish_tmp.as<double>(), st);
+  launch_polish(points_of(c), set, pp->max_iter, ps.dv.tau2, score_thr(ps.dv, p->score_mode), p->score_mode, c->polish_tmp.as<double>(), st);
   SC_TRY(rec(c, 2));
   arm_word(c, HW_WINNER);
-  launch_polish_winner(points_of(c), cand, n_cand, want, ps.dv.tau2, d_Rt, d_mask, reinterpret_cast<PolishCand*>(d_cand), d_ncand,
-                       &c->pinned[HW_WINNER], st);
+  launch_polish_winner(points_of(c), set, WinnerOut{d_Rt, d_mask, &c->pinned[HW_WINNER]}, reinterpret_cast<PolishCand*>(d_cand), d_ncand,
+                       ps.dv.tau2, st);
   SC_TRY(rec(c, 3));
   SC_TRY(scored_frame_wait(c));
   const uint32_t K = (uint32_t)c->pinned[HW_WINNER];

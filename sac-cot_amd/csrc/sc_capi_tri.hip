@@ -40,8 +40,8 @@ static float key_floor(const sc_params* p) {
 bool window_known(const sc_params* p) { return p->rank_mode == SC_RANK_WEIGHT && key_floor(p) >= 2.0f; }
 
 static Graph graph_of(const sc_ctx* c) {
-  return Graph{c->pass.bits_cur, c->S.as<float>(), c->deg.as<uint32_t>(), c->degp.as<uint32_t>(),
-               c->wpre.as<uint32_t>(), c->pass.n, c->pass.ld, c->pass.ld >> 6};
+  const RowStats rs = rows_of(c);
+  return Graph{c->pass.bits_cur, c->S.as<float>(), rs.deg, rs.degp, rs.wpre, c->pass.n, c->pass.ld, c->pass.ld >> 6};
 }
 
 // how many triangles stage B selects: T — or, when B is sharded, what one candidate blob holds (this rank's own best)
@@ -79,6 +79,11 @@ static Pruned pruned_of(const sc_ctx* c) {
   return Pruned{c->bits2.as<uint64_t>(), &ctl->smin, &ctl->klb, StrongList{nullptr, nullptr, 0u, 0u}};
 }
 // the host word of "the select found fewer keys above the pruning bound than it promised" (sharded: the merge's word says it)
+// this rank's share of the rows, as either split writes it into the control block
+static ShardCut cut_of(const sc_ctx* c, const sc_params* p) {
+  ControlBlock* ctl = c->ctl.as<ControlBlock>();
+  return ShardCut{(uint32_t)p->shard_rank, (uint32_t)p->shard_world, ctl->own_row, ctl->own_edge};
+}
 static uint64_t* select_short_word(sc_ctx* c) { return c->pass.sharded_ab ? nullptr : &c->pinned[HW_SELECT_SHORT]; }
 
 // "Did any of these arrays move?"  An array that was re-allocated — for this call's count, or only for the ROOM the next calls
@@ -160,8 +165,12 @@ static int scan_degrees(sc_ctx* c, const sc_params* p) {
   ENSURE(c, c->scan_tmp, scan_temp_bytes(n));
   if (!f.fused || f.build) arm_word(c, HW_EDGES);
   ENSURE(c, c->ebase, n * 4);
+  if (c->pass.sharded_ab) ENSURE(c, c->cost_pre, (n + 1) * sizeof(uint64_t));  // (sharded) the prefix of the per-row work estimate
+  const RowStats rs = rows_of(c);
+  const RowOffsets ro = offsets_of(c);
+  const ScanWork work{c->scan_tmp.p, c->tn};
   ScanExtra xe;  // the scan of deg+ also writes the per-row CSR bases edge_fill reads
-  xe.deg = c->deg.as<uint32_t>(); xe.degp = c->degp.as<uint32_t>(); xe.ebase = c->ebase.as<uint32_t>();
+  xe.deg = rs.deg; xe.degp = rs.degp; xe.ebase = ro.ebase; xe.host_total = &c->pinned[HW_EDGES];
   ScanExtra xc;  // (sharded) the scan of the row costs
   if (!f.fused && scan_writes_ebase(n)) {  // tiled scans: the single-pass form, each on its own half of the state area
     const size_t half = scan_temp_bytes(n);
@@ -170,15 +179,11 @@ static int scan_degrees(sc_ctx* c, const sc_params* p) {
   }
   if (c->pass.sharded_ab) {
     // also the prefix of the per-row work estimate and, from it, this rank's contiguous row / edge range
-    ENSURE(c, c->cost_pre, (n + 1) * sizeof(uint64_t));
     if (!f.fused)
-      launch_scan_u32_pair(c->degp.as<uint32_t>(), c->edge_off.as<uint64_t>(), c->rowcost.as<uint32_t>(),
-                           c->cost_pre.as<uint64_t>(), n, c->scan_tmp.p, c->tn, st, &c->pinned[HW_EDGES], &xe, &xc);
-    ControlBlock* ctl = c->ctl.as<ControlBlock>();
-    launch_shard_split(c->cost_pre.as<uint64_t>(), c->edge_off.as<uint64_t>(), c->pass.n, (uint32_t)p->shard_rank,
-                       (uint32_t)p->shard_world, ctl->own_row, ctl->own_edge, st);
+      launch_scan_u32_pair(work, ScanJob{rs.degp, ro.edge_off, xe}, ScanJob{c->rowcost.as<uint32_t>(), ro.cost_pre, xc}, n, st);
+    launch_shard_split(ro, cut_of(c, p), c->pass.n, st);
   } else if (!f.fused) {
-    launch_scan_u32(c->degp.as<uint32_t>(), n, c->edge_off.as<uint64_t>(), c->scan_tmp.p, c->tn, st, &c->pinned[HW_EDGES], &xe);
+    launch_scan_u32(work, rs.degp, n, ro.edge_off, xe, st);
   }
   return SC_OK;
 }
@@ -257,7 +262,9 @@ static int run_sample(sc_ctx* c, const sc_params* p, const Graph& g, const EdgeL
     EdgeCounts all = counts_of(c);
     all.own = nullptr;
     launch_tri_count(g, Pruned{}, el, all, c->tn, st);
-    launch_scan_u32(all.tcnt, el.E, all.toff, c->scan_tmp.p, c->tn, st, &c->pinned[HW_TOTAL]);
+    ScanExtra xt;
+    xt.host_total = &c->pinned[HW_TOTAL];
+    launch_scan_u32(ScanWork{c->scan_tmp.p, c->tn}, all.tcnt, el.E, all.toff, xt, st);
   }
   if (f.build && !f.est_active) { c->last_error = "internal: the fused edge kernel ran but the bound is not an estimate"; return SC_EHIP; }
   if (f.est_active) {
@@ -406,8 +413,7 @@ static int prune(sc_ctx* c, const sc_params* p, const uint32_t* hist, SelectArgs
   if (f.recut) {
     ENSURE(c, c->rowcost, ((size_t)c->pass.n + 4 + 1024) * 4);  // (cost_split_kernel reads whole 16-byte pieces)
     launch_strong_rowcost(a.g, a.pr, c->rowcost.as<uint32_t>(), st);
-    launch_cost_split(c->rowcost.as<uint32_t>(), c->edge_off.as<uint64_t>(), c->pass.n, (uint32_t)p->shard_rank,
-                      (uint32_t)p->shard_world, ctl->own_row, ctl->own_edge, st);
+    launch_cost_split(offsets_of(c), cut_of(c, p), c->rowcost.as<uint32_t>(), c->pass.n, st);
   }
   return SC_OK;
 }
@@ -450,8 +456,8 @@ static void counts_range(sc_ctx* c, SelectArgs& a) {
 static int scan_counts(sc_ctx* c, SelectArgs& a) {
   arm_word(c, HW_TRIANGLES);
   SC_TRY(lb_next(c, scan_temp_bytes(a.el.E), 0, 0, &a.xr.lb));
-  launch_scan_u32(a.cnt.tcnt, a.el.E, a.cnt.toff, c->scan_tmp.p, c->tn, c->stream,
-                  c->pass.form.spec ? nullptr : &c->pinned[HW_TRIANGLES], &a.xr);
+  a.xr.host_total = c->pass.form.spec ? nullptr : &c->pinned[HW_TRIANGLES];
+  launch_scan_u32(ScanWork{c->scan_tmp.p, c->tn}, a.cnt.tcnt, a.el.E, a.cnt.toff, a.xr, c->stream);
   return SC_OK;
 }
 
@@ -524,8 +530,8 @@ int run_compaction(sc_ctx* c, const KeyView& view, size_t nb, int rounds, uint64
   // few tiles (and M < 2^32): compact_write adds up the tile counts itself, no scan launch in between
   const bool self_off = nb <= c->tn.compact_self_max && view.M < (1ull << 32);
   if (!self_off)
-    launch_scan_u32_pair(c->blk_gt.as<uint32_t>(), c->off_gt.as<uint64_t>(), c->blk_eq.as<uint32_t>(),
-                         c->off_eq.as<uint64_t>(), nb, c->scan_tmp.p, c->tn, st);
+    launch_scan_u32_pair(ScanWork{c->scan_tmp.p, c->tn}, ScanJob{c->blk_gt.as<uint32_t>(), c->off_gt.as<uint64_t>()},
+                         ScanJob{c->blk_eq.as<uint32_t>(), c->off_eq.as<uint64_t>()}, nb, st);
   launch_compact_write(view, sel, c->blk_gt.as<uint32_t>(), c->blk_eq.as<uint32_t>(),
                        self_off ? nullptr : c->off_gt.as<uint64_t>(), self_off ? nullptr : c->off_eq.as<uint64_t>(), selection_of(c), st);
   return SC_OK;

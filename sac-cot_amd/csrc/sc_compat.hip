@@ -1,4 +1,6 @@
-// sc_compat.hip — input staging, stage A (compat_graph) and the exclusive scan.
+// sc_compat.hip — stage A (compat_graph): the tiles of the compatibility matrix and their adjacency words,
+// the XCD-aware block order, launch_compat.  Input staging is sc_stage.hip; the row statistics and the shard split (stage B's first
+// step) are sc_rows.hip; the exclusive scan is sc_scan.hip.
 //
 // Stage A's output is 4 N^2 bytes of weights + N^2/8 bytes of adjacency bits (103 MB at N = 5000): the HBM write
 // roofline is its bound; see the stage-A section below for the tiling that gets the arithmetic out of the way.
@@ -11,120 +13,6 @@
 #include "sc_kernels.hpp"
 
 namespace sc {
-
-// ------------------------------------------------------------------------------------------------
-// input staging: user layout -> 6 zero-padded planes, plus a finiteness check
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void stage_points_kernel(const float* __restrict__ src,
-                                                           const float* __restrict__ tgt, int n, int ld,
-                                                           int layout, float* __restrict__ planes,
-                                                           uint32_t* __restrict__ bad_flag,
-                                                           uint32_t* __restrict__ zero, uint32_t zero_words,
-                                                           uint32_t* __restrict__ coord_max,
-                                                           uint32_t* __restrict__ coord_part,
-                                                           uint32_t* __restrict__ mx_ticket,
-                                                           uint64_t* __restrict__ host_max,
-                                                           uint64_t* __restrict__ host_box,
-                                                           uint32_t* __restrict__ zero2, uint32_t zero2_words) {
-  int m = blockIdx.x * 256 + threadIdx.x;
-  for (uint32_t z = (uint32_t)m; z < zero_words; z += gridDim.x * 256) zero[z] = 0u;  // the per-call control block
-  for (uint32_t z = (uint32_t)m; z < zero2_words; z += gridDim.x * 256) zero2[z] = 0u;  // (stage A's deg+ accumulators)
-  float v[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  if (m < n) {
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-      size_t idx = layout ? ((size_t)c * n + m) : ((size_t)m * 3 + c);
-      v[c] = src[idx];
-      v[3 + c] = tgt[idx];
-    }
-    bool ok = true;
-#pragma unroll
-    for (int c = 0; c < 6; c++) ok = ok && (fabsf(v[c]) < __builtin_inff());
-    if (!ok) atomicOr(bad_flag, 1u);
-  }
-  if (coord_max) {  // largest |coordinate| of either cloud and the two bounding boxes (C2's filters scale and centre by them)
-    // coord_max: FX_MX_WORDS words — [0] max |p|, [1] max |q| (non-negative floats order as integers), [2 + c] key(max of
-    // coordinate c), [8 + c] key(max of MINUS coordinate c), c = px py pz qx qy qz (float_key orders all floats as
-    // unsigned integers, key 0 = "nothing yet").  Pad lanes (m >= n) contribute nothing to the boxes.
-    // No same-address atomics (14 words of one cache line from every wave: 15 us): every block leaves its 14 maxima in
-    // its own row of coord_part; the block that takes the last ticket reduces the rows.
-    __shared__ uint32_t red[4][14];
-    uint32_t k14[14];
-    k14[0] = __float_as_uint(fmaxf(fabsf(v[0]), fmaxf(fabsf(v[1]), fabsf(v[2]))));
-    k14[1] = __float_as_uint(fmaxf(fabsf(v[3]), fmaxf(fabsf(v[4]), fabsf(v[5]))));
-#pragma unroll
-    for (int c = 0; c < 6; c++) { k14[2 + c] = m < n ? float_key(v[c]) : 0u; k14[8 + c] = m < n ? float_key(-v[c]) : 0u; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1)
-#pragma unroll
-      for (int c = 0; c < 14; c++) k14[c] = max(k14[c], (uint32_t)__shfl_xor(k14[c], o));
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-      for (int c = 0; c < 14; c++) red[threadIdx.x >> 6][c] = k14[c];
-    __syncthreads();
-    if (threadIdx.x < 14)
-      coord_part[(size_t)blockIdx.x * 16 + threadIdx.x] = max(max(red[0][threadIdx.x], red[1][threadIdx.x]), max(red[2][threadIdx.x], red[3][threadIdx.x]));
-    // mx_ticket == nullptr (a host-free call): no workgroup stays behind — stage A's first workgroup reduces the rows (stats_reduce_wave)
-    __shared__ uint32_t s_last;
-    if (mx_ticket == nullptr) {
-      if (threadIdx.x == 0) s_last = 0u;
-    } else {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      const uint32_t t = __hip_atomic_fetch_add(mx_ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      s_last = (t == gridDim.x - 1) ? 1u : 0u;
-      if (s_last) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    }
-    }
-    __syncthreads();
-    if (s_last) {  // (block-uniform) the last block: reduce the rows, publish
-      __shared__ uint32_t fin[16][16];
-      const uint32_t c = threadIdx.x & 15, r0 = threadIdx.x >> 4;  // 16 row groups x 16 words
-      uint32_t best = 0;
-      if (c < 14)
-        for (uint32_t r = r0; r < gridDim.x; r += 16)
-          best = max(best, __hip_atomic_load(&coord_part[(size_t)r * 16 + c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-      fin[r0][c] = best;
-      __syncthreads();
-      if (threadIdx.x < 14) {
-        uint32_t b2 = 0;
-        for (int r = 0; r < 16; r++) b2 = max(b2, fin[r][threadIdx.x]);
-        coord_max[threadIdx.x] = b2;   // (plain stores: the next kernels of the stream read them)
-        fin[0][threadIdx.x] = b2;
-      }
-      __syncthreads();
-      if (threadIdx.x == 0) {
-        // the host gets the two maxima (max |q| << 32 | max |p|, bit patterns) and the boxes: it decides from them which C2
-        // kernel can work at this tau (sc_capi.hip decide_filter); nothing waits for it
-        if (host_box && host_max)
-          for (int k = 0; k < 6; k++)  // (relaxed system-scope stores: the release of host_max below orders them)
-            __hip_atomic_store(&host_box[k], ((uint64_t)fin[0][8 + k] << 32) | fin[0][2 + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(mx_ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next call
-        // (host_max == nullptr: a host-free call — nothing on the host looks at these words before the call's last kernel, which
-        // hands them over with the winner: launch_finalize's DeferredPub.  A system-scope release here costs the staging kernel ~1 us
-        // and the launch behind it another: measured, profiles/r05_ab_deferred_publish.txt)
-        if (host_max) publish_host(host_max, ((uint64_t)fin[0][1] << 32) | fin[0][0]);  // last: the host takes this word as "the boxes are there too"
-      }
-    }
-  }
-  if (m >= ld) return;
-#pragma unroll
-  for (int c = 0; c < 6; c++) planes[(size_t)c * ld + m] = v[c];
-  // AoS copy behind the planes (8 floats per correspondence, 32-byte aligned): stage A fetches a ROW operand with one
-  // s_load_dwordx8 instead of six scalar loads and their address arithmetic
-  float4* aos = reinterpret_cast<float4*>(planes + 6 * (size_t)ld);
-  aos[2 * (size_t)m] = make_float4(v[0], v[1], v[2], v[3]);
-  aos[2 * (size_t)m + 1] = make_float4(v[4], v[5], 0.0f, 0.0f);
-}
-
-void launch_stage_points(const CoordStatsOut& cs, const ZeroSpan (&zero)[2], const float* d_src, const float* d_tgt, int n, int ld,
-                         int layout, float* planes, uint32_t* bad_flag, hipStream_t st) {
-  hipLaunchKernelGGL(stage_points_kernel, dim3((ld + 255) / 256), dim3(256), 0, st, d_src, d_tgt, n, ld, layout,
-                     planes, bad_flag, zero[0].p, zero[0].words, cs.coord_max, cs.coord_part, cs.mx_ticket, cs.host_max, cs.host_box,
-                     zero[1].p, zero[1].words);
-}
 
 // ------------------------------------------------------------------------------------------------
 // stage A
@@ -453,170 +341,6 @@ __global__ __launch_bounds__(64 * COMPAT_WAVES) void compat_tiles_kernel(const f
   }
 }
 
-// What one wave learns from the words of row i (row_stats_kernel, row_stats_scan_kernel): it writes wpre[i][w] = #set bits of
-// the row in words [0, w) and clears the row of zero_rows (optional); d_all = the row's degree (wave-uniform); d_up, cost = this
-// LANE's share of deg+ (bits above i) and of the row's stage B cost (see rowcost below) — the caller sums them over the wave.
-struct RowWordStats { uint32_t d_all, d_up; uint64_t cost; };
-__device__ __forceinline__ RowWordStats row_word_stats(const uint64_t* __restrict__ bits, int i, int W, uint32_t* __restrict__ wpre,
-                                                       uint64_t* __restrict__ zero_rows) {
-  const int lane = threadIdx.x & 63;
-  if (zero_rows)
-    for (int w = lane; w < W; w += 64) zero_rows[(size_t)i * W + w] = 0ull;
-  uint32_t d_all = 0, d_up = 0;
-  uint64_t cost = 0;
-  for (int wb = 0; wb < W; wb += 64) {
-    const int w = wb + lane;
-    const uint64_t v = w < W ? bits[(size_t)i * W + w] : 0ull;
-    const uint32_t pc = (uint32_t)__popcll(v);
-    const uint32_t inc = wave_inscan(pc);  // of the word popcounts
-    if (w < W) {
-      wpre[(size_t)i * W + w] = d_all + inc - pc;
-      uint64_t up = v;
-      if (w < (i >> 6)) up = 0;
-      else if (w == (i >> 6)) up &= mask_above(i & 63);
-      d_up += __popcll(up);
-      cost += (uint64_t)__popcll(up) * (uint64_t)(W - w + 4);
-    }
-    d_all += __shfl(inc, 63);
-  }
-  return RowWordStats{d_all, d_up, cost};
-}
-
-// deg[i], degp[i] (bits above i) and wpre[i][w] = #set bits of row i in words [0, w): one wave per row.
-// rowcost (optional): estimate of stage B's work for the edges (i, j), j > i, of row i — the words the counting pass
-// ANDs for each of them plus a constant: sum over j of (W - j / 64 + 4), saturated to u32.  Its prefix over the rows
-// splits the rows into contiguous, equally heavy ranges when stage B is sharded.
-__global__ __launch_bounds__(256) void row_stats_kernel(const uint64_t* __restrict__ bits, int n, int W,
-                                                        uint32_t* __restrict__ deg, uint32_t* __restrict__ degp,
-                                                        uint32_t* __restrict__ wpre,
-                                                        uint64_t* __restrict__ zero_rows,
-                                                        uint32_t* __restrict__ rowcost) {
-  const int lane = threadIdx.x & 63;
-  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (i >= n) return;
-  RowWordStats rs = row_word_stats(bits, i, W, wpre, zero_rows);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) rs.d_up += __shfl_xor(rs.d_up, o);
-  if (rowcost) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) rs.cost += __shfl_xor(rs.cost, o);
-  }
-  if (lane == 0) {
-    deg[i] = rs.d_all; degp[i] = rs.d_up;
-    if (rowcost) rowcost[i] = rs.cost > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)rs.cost;
-  }
-}
-
-// row_stats + the prefix over the rows in ONE launch ("fold row_stats ..."): a workgroup takes RS_ROWS rows
-// (16 waves x RS_RPW rows), computes what row_stats_kernel computes, scans its edge counts (and row costs) in one wave and
-// gets the sums of the tiles before it by decoupled look-back (sc_block.hpp) — so edge_off (the CSR row offsets), the
-// per-row CSR bases, the cost prefix and the edge count for the host all come out of the kernel that read the bit rows;
-// the separate scan launch(es) and their extra pass over deg / deg+ disappear.  157 tiles at N = 5000, 625 at 20 000 (64-row tiles: 14.7 us on C2, fewer CUs busy).
-constexpr int RS_ROWS = 32;           // rows per tile: 16 waves x RS_RPW rows
-constexpr int RS_RPW = RS_ROWS / 16;  // rows a wave takes, one after the other
-__global__ __launch_bounds__(1024) void row_stats_scan_kernel(const uint64_t* __restrict__ bits, int n, int W,
-                                                             uint32_t* __restrict__ deg, uint32_t* __restrict__ degp,
-                                                             uint32_t* __restrict__ wpre,
-                                                             uint64_t* __restrict__ zero_rows,
-                                                             uint64_t* __restrict__ edge_off,
-                                                             uint32_t* __restrict__ ebase,
-                                                             uint64_t* __restrict__ cost_pre, LbArgs lb,
-                                                             uint64_t* __restrict__ host_total) {
-  __shared__ uint32_t l_degp[RS_ROWS], l_dlow[RS_ROWS];
-  __shared__ uint64_t l_cost[RS_ROWS];
-  __shared__ uint32_t s_tile;
-  uint32_t* ticket = lb.ticket;
-  const uint32_t epoch = lb.epoch;
-  if (threadIdx.x == 0) s_tile = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __syncthreads();
-  const uint32_t tile = s_tile, nb = gridDim.x;
-  if (tile >= nb) return;  // (a ticket that was not zero at launch: never index memory with it)
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int rr = 0; rr < RS_RPW; rr++) {
-    const int slot = wave * RS_RPW + rr;
-    const int i = (int)tile * RS_ROWS + slot;
-    uint32_t d_all = 0, d_up = 0;
-    uint64_t cost = 0;
-    if (i < n) {  // wave-uniform
-      const RowWordStats rs = row_word_stats(bits, i, W, wpre, zero_rows);
-      d_all = rs.d_all; d_up = rs.d_up; cost = rs.cost;
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) { d_up += __shfl_xor(d_up, o); cost += __shfl_xor(cost, o); }
-    }
-    if (lane == 0) {
-      if (i < n) { deg[i] = d_all; degp[i] = d_up; }
-      l_degp[slot] = d_up; l_dlow[slot] = d_all - d_up; l_cost[slot] = cost;
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x >= 64) return;  // wave 0: scan of the tile's 64 rows, look-back, outputs
-  const uint64_t mine_e = lane < RS_ROWS ? l_degp[lane] : 0u, mine_c = lane < RS_ROWS ? l_cost[lane] : 0ull;
-  const uint64_t inc_e = wave_inscan(mine_e), inc_c = wave_inscan(mine_c);
-  const uint64_t tot_e = __shfl(inc_e, 63), tot_c = __shfl(inc_c, 63);
-  uint64_t* const desc[2] = {lb.desc, lb.desc + nb};
-  const uint64_t own[2] = {tot_e, tot_c};
-  uint64_t pre[2];
-  lb_lookback<2>(desc, tile, epoch, own, pre, lb.err);
-  const int i = (int)tile * RS_ROWS + lane;
-  if (lane < RS_ROWS && i < n) {
-    const uint64_t off = pre[0] + inc_e - mine_e;
-    edge_off[i] = off;
-    ebase[i] = (uint32_t)off - l_dlow[lane];  // (lane < RS_ROWS here)
-    if (cost_pre) cost_pre[i] = pre[1] + inc_c - mine_c;
-  }
-  if (tile == nb - 1 && lane == 0) {
-    edge_off[n] = pre[0] + tot_e;
-    if (cost_pre) cost_pre[n] = pre[1] + tot_c;
-    if (host_total) publish_host(host_total, pre[0] + tot_e);
-    __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // every tile has taken its ticket
-  }
-}
-
-size_t row_stats_scan_state_bytes(int n) { return (size_t)(2 * ((n + RS_ROWS - 1) / RS_ROWS)) * sizeof(uint64_t); }
-
-void launch_row_stats_scan(const Points& pts, const uint64_t* bits, uint32_t* deg, uint32_t* degp, uint32_t* wpre,
-                           uint64_t* zero_rows, uint64_t* edge_off, uint32_t* ebase, uint64_t* cost_pre, const LbArgs& lb,
-                           uint64_t* host_total, hipStream_t st) {
-  hipLaunchKernelGGL(row_stats_scan_kernel, dim3((pts.n + RS_ROWS - 1) / RS_ROWS), dim3(1024), 0, st, bits, pts.n,
-                     pts.ld >> 6, deg, degp, wpre, zero_rows, edge_off, ebase, cost_pre, lb, host_total);
-}
-
-// Contiguous row range of one rank: rows [lo, hi) with lo = first row whose cost prefix reaches rank / world of the
-// total (row 0 for rank 0, n for the end of the last rank).  own_row[0..1] and the CSR edge range own_edge[0..1] of
-// those rows go to the control block; every rank computes the same boundaries from the same replicated arrays.
-__global__ __launch_bounds__(64) void shard_split_kernel(const uint64_t* __restrict__ cost_pre,
-                                                         const uint64_t* __restrict__ edge_off, int n, uint32_t rank,
-                                                         uint32_t world, uint32_t* __restrict__ own_row,
-                                                         uint64_t* __restrict__ own_edge) {
-  // one wave; both boundaries (lo = boundary `rank`, hi = boundary `rank + 1`) by a 64-ary search: every step the 64
-  // lanes probe 64 evenly spaced rows at once (3 steps for n = 20 000 instead of 15 dependent loads)
-  const int lane = threadIdx.x;
-  const uint64_t total = cost_pre[n];
-  for (int which = 0; which < 2; which++) {
-    const uint32_t l = rank + (uint32_t)which;
-    int row;
-    if (l == 0) row = 0;
-    else if (l >= world) row = n;
-    else {
-      const uint64_t target = (uint64_t)(((unsigned __int128)total * l) / world);
-      int lo = 0, hi = n;  // invariant: the answer (first r in [0, n] with cost_pre[r] >= target) lies in [lo, hi]
-      while (hi - lo > 0) {
-        const int span = hi - lo, step = (span + 63) / 64;
-        const int probe = lo + lane * step;                   // probes lo, lo + step, ... (those < hi are real)
-        const bool ge = probe < hi ? (cost_pre[probe] >= target) : true;
-        const uint64_t m = __ballot(ge);
-        // first probe at or above the target; none (the last real probe is still below it): the answer lies above it
-        const int first = m ? __builtin_ctzll(m) : 64;
-        if (first == 0) { hi = lo; }                                                // cost_pre[lo] >= target
-        else if (first == 64) { lo = lo + 63 * step + 1; }                          // in (probe[63], hi]
-        else { const int plo = lo + (first - 1) * step + 1; hi = min(hi, lo + first * step); lo = plo; }  // in (probe[first-1], probe[first]]
-      }
-      row = lo;
-    }
-    if (lane == 0) { own_row[which] = (uint32_t)row; own_edge[which] = edge_off[row]; }
-  }
-}
-
 // rows [row0, row1) of the graph (row0 a multiple of 64, row1 <= n); the whole matrix (symmetric tiles, each pair
 // evaluated once) when the range is [0, n).  S == nullptr: adjacency bits only (SC_FLAG_NO_DENSE_S).  For a proper
 // sub-range S holds the rows of the range only (row i at S + (i - row0) * ld).
@@ -707,302 +431,6 @@ void launch_compat(const Points& pts, const CompatOpts& o, const Derived& dv, fl
     else hipLaunchKernelGGL((compat_tiles_kernel<16, 4, false, false>), dim3(grid), dim3(256), 0, st, SC_COMPAT_ARGS);
   }
 #undef SC_COMPAT_ARGS
-}
-
-void launch_row_stats(const Points& pts, const uint64_t* bits, uint32_t* deg, uint32_t* degp, uint32_t* wpre,
-                      uint64_t* zero_rows, uint32_t* rowcost, hipStream_t st) {
-  hipLaunchKernelGGL(row_stats_kernel, dim3((pts.n + 3) / 4), dim3(256), 0, st, bits, pts.n, pts.ld >> 6, deg, degp,
-                     wpre, zero_rows, rowcost);
-}
-
-void launch_shard_split(const uint64_t* cost_pre, const uint64_t* edge_off, int n, uint32_t rank, uint32_t world,
-                        uint32_t* own_row, uint64_t* own_edge, hipStream_t st) {
-  hipLaunchKernelGGL(shard_split_kernel, dim3(1), dim3(64), 0, st, cost_pre, edge_off, n, rank, world, own_row, own_edge);
-}
-
-// ------------------------------------------------------------------------------------------------
-// exclusive scan u32 -> u64: block sums, then a down-sweep whose blocks add up the sums before them (two launches);
-// beyond SCAN_SELF_MAX tiles a one-block scan of the sums runs in between
-// ------------------------------------------------------------------------------------------------
-constexpr int SCAN_THREADS = 256;
-constexpr int SCAN_ITEMS = 16;
-constexpr int SCAN_TILE = SCAN_THREADS * SCAN_ITEMS;
-
-// range (optional, device): [lo, hi) outside which every input is known to be zero (sharded stage B: the per-edge
-// triangle counts of the edges other ranks enumerate) — tiles wholly outside are neither read nor written.
-// ... and inside a tile that straddles an end of the range the elements outside it read as zero WITHOUT being read (r05: a host-free
-// call's per-edge counts beyond its real edge count are never written — sc_capi.hip, ControlBlock::live_edges)
-__device__ __forceinline__ bool scan_live(const uint64_t* __restrict__ range, size_t idx) {
-  return !range || ((uint64_t)idx >= range[0] && (uint64_t)idx < range[1]);
-}
-__device__ __forceinline__ bool scan_tile_dead(const uint64_t* __restrict__ range, size_t tile) {
-  if (!range) return false;
-  const uint64_t t0 = (uint64_t)tile * SCAN_TILE;
-  return t0 + SCAN_TILE <= range[0] || t0 >= range[1];
-}
-
-// ---- a tile of the scans, coalesced (r05).  By time stamps inside the look-back kernel's tiles a tile's life was 3 us of loads + local scan
-// and 3 us of stores around 1 us of look-back: every thread owned SCAN_ITEMS CONSECUTIVE elements, so a wave's load touched 64 pieces 64
-// bytes apart and its 8-byte stores 64 lines each, sixteen times over.  Now a tile is SCAN_SUB sub-tiles of 1024 elements and a thread takes
-// four consecutive elements of each: a wave reads 1 KiB and writes 2 KiB at a stretch (C2: scan_lookback_kernel 11.7 -> 9.3 us).  A piece
-// inside the array is loaded BEFORE `range` is looked at (its two words were a dependent round trip at the head of the chain) and masked
-// afterwards: what lies beyond a host-free call's real edge count was never written, but it is the array's own memory.
-constexpr int SCAN_SUB = SCAN_ITEMS / 4;
-static_assert(SCAN_ITEMS % 4 == 0 && SCAN_THREADS == 256, "sub-tiles of 4 x 256 elements, four waves");
-struct ScanTile { uint32_t v[SCAN_SUB][4]; uint64_t ex[SCAN_SUB]; uint64_t tot; bool dead; };
-// loads + masks the tile's elements; returns with ex[r] = sum of the tile's elements before this thread's piece of sub-tile r and tot =
-// the tile's sum.  wsum: 4 x SCAN_SUB words of LDS; one barrier; every thread of the workgroup calls it.
-// (mask_dead: a tile wholly outside `range` reads as zeros — t.dead says so; `range` is looked at only AFTER the loads are on their way)
-__device__ __forceinline__ void scan_tile_load(const uint32_t* __restrict__ in, size_t n, size_t tile, const uint64_t* __restrict__ range,
-                                               bool mask_dead, uint64_t (*wsum)[SCAN_SUB], ScanTile& t) {
-  const size_t tbase = tile * SCAN_TILE + (size_t)threadIdx.x * 4;
-  if ((tile + 1) * SCAN_TILE <= n) {  // (block-uniform: ONE branch around all the loads — a branch per piece made the compiler wait for each)
-    uint4 q[SCAN_SUB];
-#pragma unroll
-    for (int r = 0; r < SCAN_SUB; r++) q[r] = *reinterpret_cast<const uint4*>(in + tbase + (size_t)r * 1024);
-#pragma unroll
-    for (int r = 0; r < SCAN_SUB; r++) { t.v[r][0] = q[r].x; t.v[r][1] = q[r].y; t.v[r][2] = q[r].z; t.v[r][3] = q[r].w; }
-  } else {
-#pragma unroll
-    for (int r = 0; r < SCAN_SUB; r++)
-#pragma unroll
-      for (int k = 0; k < 4; k++) { const size_t idx = tbase + (size_t)r * 1024 + k; t.v[r][k] = idx < n ? in[idx] : 0u; }
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const bool dead = mask_dead && scan_tile_dead(range, tile);  // block-uniform
-  t.dead = dead;
-  uint64_t inc[SCAN_SUB], mine[SCAN_SUB];
-#pragma unroll
-  for (int r = 0; r < SCAN_SUB; r++) {
-    const size_t idx = tbase + (size_t)r * 1024;
-    uint64_t a = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) { t.v[r][k] = (!dead && scan_live(range, idx + k)) ? t.v[r][k] : 0u; a += t.v[r][k]; }
-    mine[r] = a; inc[r] = a;
-  }
-  // (wave_inscan's steps for the SCAN_SUB values TOGETHER, step by step: one value after the other, hipcc waits for each sub-tile's
-  // load in turn where this form has all four in flight — 19 more s_waitcnt in scan_lookback_kernel, the hot path's scan)
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1)
-#pragma unroll
-    for (int r = 0; r < SCAN_SUB; r++) {
-      const uint64_t x = __shfl_up(inc[r], o);
-      if (lane >= o) inc[r] += x;
-    }
-  if (lane == 63)
-#pragma unroll
-    for (int r = 0; r < SCAN_SUB; r++) wsum[wave][r] = inc[r];
-  __syncthreads();
-  uint64_t tot = 0;
-#pragma unroll
-  for (int r = 0; r < SCAN_SUB; r++) {
-    uint64_t before = tot;
-#pragma unroll
-    for (int w = 0; w < 4; w++) { const uint64_t x = wsum[w][r]; before += w < wave ? x : 0ull; tot += x; }
-    t.ex[r] = before + inc[r] - mine[r];
-  }
-  t.tot = tot;
-}
-struct ScanEbase { const uint32_t* deg; const uint32_t* degp; uint32_t* ebase; };
-// out[i] = pre + (exclusive prefix inside the tile) for the tile's elements below n; eb: see scan_downsweep_kernel
-__device__ __forceinline__ void scan_tile_store(uint64_t* __restrict__ out, size_t n, size_t tile, uint64_t pre, const ScanTile& t, const ScanEbase& eb) {
-  const size_t tbase = tile * SCAN_TILE + (size_t)threadIdx.x * 4;
-  const bool whole = (tile + 1) * SCAN_TILE <= n;  // block-uniform
-#pragma unroll
-  for (int r = 0; r < SCAN_SUB; r++) {
-    const size_t idx = tbase + (size_t)r * 1024;
-    uint64_t o4[4], run = pre + t.ex[r];
-#pragma unroll
-    for (int k = 0; k < 4; k++) { o4[k] = run; run += t.v[r][k]; }
-    if (whole) {
-      typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
-      u64x2* dst = reinterpret_cast<u64x2*>(out + idx);  // (idx is a multiple of 4: 32-byte aligned)
-      dst[0] = u64x2{o4[0], o4[1]}; dst[1] = u64x2{o4[2], o4[3]};
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; k++) if (idx + k < n) out[idx + k] = o4[k];
-    }
-    if (eb.ebase)
-#pragma unroll
-      for (int k = 0; k < 4; k++) if (idx + k < n) eb.ebase[idx + k] = (uint32_t)o4[k] - (eb.deg[idx + k] - eb.degp[idx + k]);
-  }
-}
-
-__global__ __launch_bounds__(SCAN_THREADS) void scan_block_sums_kernel(const uint32_t* __restrict__ in, size_t n,
-                                                                       uint64_t* __restrict__ bsum,
-                                                                       const uint64_t* __restrict__ range) {
-  __shared__ uint64_t wsum[4][SCAN_SUB];
-  if (scan_tile_dead(range, blockIdx.x)) { if (threadIdx.x == 0) bsum[blockIdx.x] = 0; return; }
-  ScanTile t;
-  scan_tile_load(in, n, blockIdx.x, range, false, wsum, t);
-  if (threadIdx.x == 0) bsum[blockIdx.x] = t.tot;
-}
-
-__global__ __launch_bounds__(1024) void scan_of_sums_kernel(uint64_t* __restrict__ bsum, size_t nb,
-                                                            uint64_t* __restrict__ total_out,
-                                                            uint64_t* __restrict__ host_total) {
-  __shared__ uint64_t lds[16];
-  uint64_t carry = 0;
-  for (size_t b0 = 0; b0 < nb; b0 += 1024) {
-    const size_t b = b0 + threadIdx.x;
-    const uint64_t v = b < nb ? bsum[b] : 0;
-    uint64_t tot;
-    const uint64_t ex = block_exscan_u64(v, lds, &tot);
-    if (b < nb) bsum[b] = carry + ex;
-    carry += tot;
-  }
-  if (threadIdx.x == 0) {
-    *total_out = carry;
-    if (host_total) publish_host(host_total, carry);
-  }
-}
-
-// SELF: every block sums the raw block sums before it by itself (<= SCAN_SELF_MAX of them, from L2) and the last one
-// writes the total — the single-block scan-of-sums launch (a ~4.6 us floor) disappears.
-// eb (optional): also ebase[i] = (u32) out[i] - (deg[i] - degp[i]), the CSR base of row i (see launch_edge_fill)
-template <bool SELF>
-__global__ __launch_bounds__(SCAN_THREADS) void scan_downsweep_kernel(const uint32_t* __restrict__ in, size_t n,
-                                                                      const uint64_t* __restrict__ bsum,
-                                                                      uint64_t* __restrict__ out,
-                                                                      uint64_t* __restrict__ host_total,
-                                                                      const uint64_t* __restrict__ range,
-                                                                      ScanEbase eb) {
-  __shared__ uint64_t lds[8];
-  __shared__ uint64_t wsum[4][SCAN_SUB];
-  const bool dead = scan_tile_dead(range, blockIdx.x) && !(SELF && blockIdx.x == gridDim.x - 1);  // block-uniform
-  if (dead) return;
-  ScanTile t;
-  scan_tile_load(in, n, blockIdx.x, range, false, wsum, t);
-  uint64_t pre;
-  if (SELF) {
-    uint64_t a = 0;
-    for (uint32_t b = threadIdx.x; b < blockIdx.x; b += SCAN_THREADS) a += bsum[b];
-    pre = block_reduce_u64(a, lds);
-  } else {
-    pre = bsum[blockIdx.x];
-  }
-  scan_tile_store(out, n, blockIdx.x, pre, t, eb);
-  if (SELF && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
-    out[n] = pre + t.tot;
-    if (host_total) publish_host(host_total, pre + t.tot);
-  }
-}
-
-// Single-pass form (decoupled look-back, sc_block.hpp): one launch instead of block sums + down-sweep.
-// lb: ticket (zero between launches: the last tile resets it), error flag, one descriptor per tile, this launch's epoch.
-__global__ __launch_bounds__(SCAN_THREADS) void scan_lookback_kernel(const uint32_t* __restrict__ in, size_t n,
-                                                                     uint64_t* __restrict__ out, LbArgs lb,
-                                                                     uint64_t* __restrict__ host_total,
-                                                                     const uint64_t* __restrict__ range, ScanEbase eb) {
-  __shared__ uint32_t s_tile;
-  __shared__ uint64_t s_prefix;
-  uint32_t* ticket = lb.ticket;
-  const uint32_t epoch = lb.epoch;
-  if (threadIdx.x == 0) s_tile = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __syncthreads();
-  const uint32_t tile = s_tile;
-  if (tile >= gridDim.x) return;  // (a ticket that was not zero at launch: never index memory with it)
-  __shared__ uint64_t wsum[4][SCAN_SUB];
-  ScanTile t;
-  scan_tile_load(in, n, tile, range, true, wsum, t);  // (a tile wholly outside the range: known zeros, never written)
-  const bool dead = t.dead;
-  const uint64_t tot = t.tot;
-  if (threadIdx.x < 64) {
-    uint64_t* const desc[1] = {lb.desc};
-    const uint64_t own[1] = {tot};
-    uint64_t pre[1];
-    lb_lookback<1>(desc, tile, epoch, own, pre, lb.err);
-    if (threadIdx.x == 0) s_prefix = pre[0];
-  }
-  __syncthreads();
-  const uint64_t pre = s_prefix;
-  if (!dead) scan_tile_store(out, n, tile, pre, t, eb);
-  if (tile == gridDim.x - 1 && threadIdx.x == 0) {
-    out[n] = pre + tot;
-    if (host_total) publish_host(host_total, pre + tot);
-    __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // every tile has taken its ticket
-  }
-}
-
-// small inputs: ONE block scans up to two arrays in one launch (three launches of the tiled scan are pure latency there)
-__global__ __launch_bounds__(1024) void scan_small_kernel(const uint32_t* __restrict__ in0, uint64_t* __restrict__ out0,
-                                                          const uint32_t* __restrict__ in1, uint64_t* __restrict__ out1,
-                                                          size_t n, uint64_t* __restrict__ host_total) {
-  __shared__ uint64_t lds[16];
-  constexpr int PER = 8;  // consecutive elements per thread and pass: 8192 per pass, so a few passes at most
-  const int arrays = in1 ? 2 : 1;
-  for (int a = 0; a < arrays; a++) {
-    const uint32_t* in = a ? in1 : in0;
-    uint64_t* out = a ? out1 : out0;
-    uint64_t carry = 0;
-    for (size_t b0 = 0; b0 < n; b0 += 1024 * PER) {
-      const size_t base = b0 + (size_t)threadIdx.x * PER;
-      uint32_t v[PER];
-      uint64_t sum = 0;
-#pragma unroll
-      for (int k = 0; k < PER; k++) { v[k] = (base + k < n) ? in[base + k] : 0u; sum += v[k]; }
-      uint64_t tot;
-      uint64_t run = carry + block_exscan_u64(sum, lds, &tot);
-#pragma unroll
-      for (int k = 0; k < PER; k++) {
-        if (base + k < n) out[base + k] = run;
-        run += v[k];
-      }
-      carry += tot;
-    }
-    if (threadIdx.x == 0) {
-      out[n] = carry;
-      if (a == 0 && host_total) publish_host(host_total, carry);
-    }
-  }
-}
-
-constexpr size_t SCAN_SMALL_MAX = 8192;  // one pass of the single block; beyond it the tiled form is faster (N = 20 000: 26 -> ~9 us)
-// Tuning::scan_self_max (4096 tiles = 16.7 M elements): beyond it the scan of sums is its own launch
-
-void launch_scan_u32_pair(const uint32_t* in0, uint64_t* out0, const uint32_t* in1, uint64_t* out1, size_t n,
-                          void* temp, const Tuning& tn, hipStream_t st, uint64_t* host_total, const ScanExtra* x0,
-                          const ScanExtra* x1) {
-  if (n <= SCAN_SMALL_MAX) {
-    hipLaunchKernelGGL(scan_small_kernel, dim3(1), dim3(1024), 0, st, in0, out0, in1, out1, n, host_total);
-  } else {
-    launch_scan_u32(in0, n, out0, temp, tn, st, host_total, x0);
-    if (in1) launch_scan_u32(in1, n, out1, temp, tn, st, nullptr, x1);
-  }
-}
-
-bool scan_writes_ebase(size_t n) { return n > SCAN_SMALL_MAX; }
-
-size_t scan_temp_bytes(size_t n) { return ((n + SCAN_TILE - 1) / SCAN_TILE + 4) * sizeof(uint64_t); }
-
-void launch_scan_u32(const uint32_t* in, size_t n, uint64_t* out, void* temp, const Tuning& tn, hipStream_t st,
-                     uint64_t* host_total, const ScanExtra* x) {
-  const ScanEbase eb{x ? x->deg : nullptr, x ? x->degp : nullptr, x ? x->ebase : nullptr};
-  const uint64_t* range = x ? x->range : nullptr;
-  if (n <= SCAN_SMALL_MAX) {
-    hipLaunchKernelGGL(scan_small_kernel, dim3(1), dim3(1024), 0, st, in, out, (const uint32_t*)nullptr,
-                       (uint64_t*)nullptr, n, host_total);
-    return;
-  }
-  uint64_t* bsum = static_cast<uint64_t*>(temp);
-  const size_t nb = (n + SCAN_TILE - 1) / SCAN_TILE;
-  if (nb == 0) return;  // n == 0 is handled by the small path above
-  // single-pass form while the look-back stays shallow (r02: 116 tiles 10.6 us against 4.9 + 7.9; 781 tiles 16.4 against
-  // 5.0 + 9.4 — every 64 tiles are one more dependent round of descriptor loads)
-  if (x && x->lb.epoch && x->lb.desc && x->lb.ticket && tn.scan_self_max != 0 && nb <= (size_t)(range ? 512 : 256)) {  // (tiles outside a range publish a zero at once: a trimmed launch may be longer)
-    hipLaunchKernelGGL(scan_lookback_kernel, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, st, in, n, out, x->lb, host_total,
-                       range, eb);
-    return;
-  }
-  hipLaunchKernelGGL(scan_block_sums_kernel, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, st, in, n, bsum, range);
-  if (nb <= tn.scan_self_max) {  // (a test sets scan_self_max = 0 to force the three-kernel form)
-    hipLaunchKernelGGL(scan_downsweep_kernel<true>, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, st, in, n, bsum, out,
-                       host_total, range, eb);
-  } else {
-    hipLaunchKernelGGL(scan_of_sums_kernel, dim3(1), dim3(1024), 0, st, bsum, nb, out + n, host_total);
-    hipLaunchKernelGGL(scan_downsweep_kernel<false>, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, st, in, n, bsum, out,
-                       (uint64_t*)nullptr, range, eb);
-  }
 }
 
 }  // namespace sc

@@ -280,6 +280,7 @@ int check_params(const sc_params* p);
 Derived derive(const sc_params* p);
 inline uint64_t workspace_cap(const sc_params* p) { return p->max_workspace ? p->max_workspace : (64ull << 30); }
 inline Points points_of(const sc_ctx* c) { return Points{c->planes.as<float>(), c->pass.n, c->pass.ld}; }
+inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 int lb_next(sc_ctx* c, size_t bytes, int slot, size_t desc_off, LbArgs* out);
 int rec(sc_ctx* c, int i);
 float ev_us(sc_ctx* c, int a, int b);
@@ -539,7 +540,8 @@ inline void scored_frame_stats(sc_ctx* c, sc_stats* stats, uint32_t best_count, 
   stats->us_total = stats->us_stage + stats->us_score + stats->us_argmax + stats->us_mask;
 }
 
-// the stage sequencers the stage hooks run one at a time (sc_capi_hooks.hip)
+// the stage sequencers the stage hooks run one at a time (sc_capi_hooks.hip): stage A's three are defined in sc_capi_compat.hip,
+// run_triangles in sc_capi_tri.hip
 int stage_inputs(sc_ctx* c, const float* d_src, const float* d_tgt, int64_t n, const sc_params* p);
 int run_compat(sc_ctx* c, bool dense);
 int run_row_stats(sc_ctx* c, bool will_prune, bool hot = false);
@@ -556,6 +558,9 @@ SC_LOCAL EdgeList edges_of(const sc_ctx* c);
 SC_LOCAL EdgeCounts counts_of(const sc_ctx* c);
 SC_LOCAL KeyArrays keys_of(const sc_ctx* c);
 SC_LOCAL Selection selection_of(const sc_ctx* c);
+// ... and of the row arrays (defined in sc_capi_compat.hip; scan_degrees and graph_of use them too)
+SC_LOCAL RowStats rows_of(const sc_ctx* c);
+SC_LOCAL RowOffsets offsets_of(const sc_ctx* c);
 SC_LOCAL int ensure_compaction(sc_ctx* c, size_t nb, size_t nb_room, uint32_t T_eff);
 SC_LOCAL int run_compaction(sc_ctx* c, const KeyView& view, size_t nb, int rounds, uint64_t* host_short);
 inline int select_rounds(bool window) { return window ? 2 : 3; }  // the a-priori window spares the round that measures the key range

@@ -11,7 +11,7 @@
 
 namespace sc {
 
-std::vector<uint32_t> compat_wg_map(int W);  // sc_compat.hip: which 64 x 64 block workgroup b of stage A takes (XCD-aware)
+std::vector<uint32_t> compat_wg_map(int W);  // sc_compat.hip (run_compat, sc_capi_compat.hip, caches it per row width): which 64 x 64 block workgroup b of stage A takes (XCD-aware)
 
 // Derived fp32 constants, computed once per call on the host in fp64.
 struct Derived {
@@ -102,7 +102,7 @@ struct Points {
 // coordinate, written before host_max.
 constexpr int FX_MX_WORDS = 16;
 inline size_t stage_part_words(int ld) { return (size_t)((ld + 255) / 256) * 16; }
-// The launch's views (host-side; stage_inputs fills them): where the coordinate statistics go, and the buffers cleared on the way.
+// The launch's views (host-side; stage_inputs, sc_capi_compat.hip, fills them): where the coordinate statistics go, and the buffers cleared on the way.
 struct CoordStatsOut { uint32_t* coord_max; uint32_t* coord_part; uint32_t* mx_ticket; uint64_t* host_max; uint64_t* host_box; };
 struct ZeroSpan { uint32_t* p; uint32_t words; };
 void launch_stage_points(const CoordStatsOut& cs, const ZeroSpan (&zero)[2], const float* d_src, const float* d_tgt, int n, int ld,
@@ -132,27 +132,32 @@ bool filter_in_range(uint64_t host_max, float tau2);
 struct CompatOpts { uint32_t* degp; const uint32_t* wg_map; uint32_t wg_map_len; const uint32_t* stat_part; uint32_t* stat_out; };  // (CompatOpts{}: none)
 void launch_compat(const Points& pts, const CompatOpts& o, const Derived& dv, float* S, uint64_t* bits, int row0, int row1,
                    const Tuning& tn, hipStream_t st);
+// The row arrays as the launches see them — RowStats, RowOffsets, ShardCut: plain host-side views, as stage B's are, each filled by one
+// accessor of the host driver (sc_capi_compat.hip: rows_of, offsets_of; sc_capi_tri.hip: cut_of), behind the last ENSURE of what it names.
+//
 // deg[i] = edges of i; degp[i] = edges (i,j) with j > i; wpre: n x (ld/64) u32, set bits of row i in words [0,w).
 // zero_rows (optional): an n x W u64 matrix cleared on the way (the pruned bit matrix of stage B).
 // rowcost (optional, n u32): per-row estimate of stage B's work (see row_stats_kernel), for launch_shard_split.
-void launch_row_stats(const Points& pts, const uint64_t* bits, uint32_t* deg, uint32_t* degp, uint32_t* wpre,
-                      uint64_t* zero_rows, uint32_t* rowcost, hipStream_t st);
-// row_stats and the prefixes over the rows in one launch (decoupled look-back over 64-row tiles): also edge_off (n + 1
-// CSR row offsets), ebase (n per-row CSR bases), cost_pre (optional, n + 1: prefix of the row costs) and the edge count
-// into host_total.  state: row_stats_scan_state_bytes(n) of the caller's look-back state area; epoch: this launch's.
+struct RowStats { uint32_t* deg; uint32_t* degp; uint32_t* wpre; uint64_t* zero_rows; uint32_t* rowcost; };
+// edge_off (n + 1 CSR row offsets), ebase (n per-row CSR bases), cost_pre (optional, n + 1: prefix of the row costs)
+struct RowOffsets { uint64_t* edge_off; uint32_t* ebase; uint64_t* cost_pre; };
+// one rank's share of the rows: own_row[0..1] and the CSR edge range own_edge[0..1] (ControlBlock), written by either split
+struct ShardCut { uint32_t rank, world; uint32_t* own_row; uint64_t* own_edge; };
+void launch_row_stats(const Points& pts, const uint64_t* bits, const RowStats& rs, hipStream_t st);
+// row_stats and the prefixes over the rows in one launch (decoupled look-back over 64-row tiles): also ro (rs.rowcost is not written:
+// the costs go straight into ro.cost_pre) and the edge count
+// into host_total.  lb: row_stats_scan_state_bytes(n) of the caller's look-back state area and this launch's epoch.
 size_t row_stats_scan_state_bytes(int n);
-void launch_row_stats_scan(const Points& pts, const uint64_t* bits, uint32_t* deg, uint32_t* degp, uint32_t* wpre,
-                           uint64_t* zero_rows, uint64_t* edge_off, uint32_t* ebase, uint64_t* cost_pre, const LbArgs& lb,
+void launch_row_stats_scan(const Points& pts, const uint64_t* bits, const RowStats& rs, const RowOffsets& ro, const LbArgs& lb,
                            uint64_t* host_total, hipStream_t st);
 // this rank's contiguous, equally heavy row range (own_row[0..1]) and its CSR edge range (own_edge[0..1])
-// from the exclusive prefix of rowcost (n + 1 entries) — device-side, identical on every rank.
-void launch_shard_split(const uint64_t* cost_pre, const uint64_t* edge_off, int n, uint32_t rank, uint32_t world,
-                        uint32_t* own_row, uint64_t* own_edge, hipStream_t st);
+// from the exclusive prefix of rowcost (ro.cost_pre, n + 1 entries) — device-side, identical on every rank.
+void launch_shard_split(const RowOffsets& ro, const ShardCut& cut, int n, hipStream_t st);
 
 // ---- exclusive scan u32 -> u64 (out has n+1 entries; out[n] = total) -----------------------------
-// host_total (optional): host-pinned u64 that also receives the total, written by the kernel itself — the host
-// reads it after its next stream synchronise, with no copy kernel in between.
-// Extras a scan can do on its way (all optional):
+// Extras a scan can do on its way (all optional; ScanExtra{}: none):
+//   host_total: host-pinned u64 that also receives the total, written by the kernel itself — the host
+//     reads it after its next stream synchronise, with no copy kernel in between;
 //   range (device, [lo, hi)): outside it every input is known to be zero — tiles wholly outside are neither read nor
 //     written (sharded stage B: the triangle counts of the edges other ranks enumerate); out[n] is still the total;
 //   deg / degp / ebase: also ebase[i] = (u32) out[i] - (deg[i] - degp[i]), the CSR base of row i (launch_edge_fill).
@@ -163,15 +168,16 @@ struct ScanExtra {
   const uint32_t* deg = nullptr;
   const uint32_t* degp = nullptr;
   uint32_t* ebase = nullptr;
+  uint64_t* host_total = nullptr;
 };
+// what every scan of a caller works with: temp (scan_temp_bytes(n) of scratch) and the knobs
+struct ScanWork { void* temp; const Tuning& tn; };
+struct ScanJob { const uint32_t* in; uint64_t* out; ScanExtra x; };
 size_t scan_temp_bytes(size_t n);
-void launch_scan_u32(const uint32_t* in, size_t n, uint64_t* out, void* temp, const Tuning& tn, hipStream_t st,
-                     uint64_t* host_total = nullptr, const ScanExtra* x = nullptr);
-// two arrays of the same length in one go (one launch when n is small); in1/out1 may be null; host_total and x0: of
-// array 0
-void launch_scan_u32_pair(const uint32_t* in0, uint64_t* out0, const uint32_t* in1, uint64_t* out1, size_t n,
-                          void* temp, const Tuning& tn, hipStream_t st, uint64_t* host_total = nullptr,
-                          const ScanExtra* x0 = nullptr, const ScanExtra* x1 = nullptr);
+void launch_scan_u32(const ScanWork& w, const uint32_t* in, size_t n, uint64_t* out, const ScanExtra& x, hipStream_t st);
+// two arrays of the same length in one go (one launch when n is small); b.in may be null (ScanJob{}: no second array); host_total:
+// of array a only (b's is not looked at)
+void launch_scan_u32_pair(const ScanWork& w, const ScanJob& a, const ScanJob& b, size_t n, hipStream_t st);
 
 // ---- stage B: triangles_topT ---------------------------------------------------------------------
 struct Graph {
@@ -292,8 +298,7 @@ void launch_prune_bits(const Graph& g, const uint32_t* hist, bool hist_is_copies
 // sharded stage B, after the certificate: work estimate per row of the PRUNED graph (strong_rowcost_kernel), and — in one
 // single-block launch — its prefix and this rank's row / edge range (the rule of launch_shard_split)
 void launch_strong_rowcost(const Graph& g, const Pruned& pr, uint32_t* rowcost, hipStream_t st);
-void launch_cost_split(const uint32_t* rowcost, const uint64_t* edge_off, int n, uint32_t rank, uint32_t world,
-                       uint32_t* own_row, uint64_t* own_edge, hipStream_t st);
+void launch_cost_split(const RowOffsets& ro, const ShardCut& cut, const uint32_t* rowcost, int n, hipStream_t st);  // (reads ro.edge_off only)
 
 // Event list of stage B (sc_tri.hip 2b): one record per non-zero member word of a strong edge, SoA, split into
 // EV_SHARDS regions of shard_cap records; fill[shard] = records appended to that region.
@@ -709,19 +714,22 @@ struct PolishCand {
 };
 static_assert(sizeof(PolishCand) == 64, "sc_polish_cand is 64 bytes");
 constexpr uint32_t POLISH_MAX_CAND = 64;
+// The candidate set as the three launches see it (sc_capi_polish.hip fills it): cand holds POLISH_MAX_CAND records, *n_cand = K of them
+// filled, want = the candidates asked for.
+struct PolishSet { PolishCand* cand; uint32_t* n_cand; uint32_t want; };
 // The first K = min(want, hypotheses with cnt > 0) of the T hypotheses under (cnt desc, sel_key desc, position asc) — the frame's
 // total order — into cand[0 .. K) in that order, with their rank in the ranked list; cand[K .. want) zeroed; *n_cand = K.  One workgroup.
-void launch_polish_select(const uint32_t* cnt, const uint32_t* sel_key, uint32_t T, const float* RtSoA, uint32_t ld_local, uint32_t want,
-                          PolishCand* cand, uint32_t* n_cand, hipStream_t st);
+void launch_polish_select(const PolishSet& ps, const uint32_t* cnt, const uint32_t* sel_key, uint32_t T, const float* RtSoA, uint32_t ld_local,
+                          hipStream_t st);
 // One workgroup per candidate, every iteration inside the launch: mask of (R, t) -> refit in refine_kernel's canonical order -> again,
 // until the refit is declined, returns the same bits, or max_iter refits are done; then the score of the last iterate.
 // scratch: want * chunk_scratch_bytes(n) (sc_chunks.hpp).  thr: tau^2, 1 / tau^2 or 1 / tau by score_mode.
-void launch_polish(const Points& pts, PolishCand* cand, const uint32_t* n_cand, uint32_t want, uint32_t max_iter, float tau2, float thr,
-                   int score_mode, double* scratch, hipStream_t st);
-// The candidate with the largest score (ties: the earlier one) -> Rt12, mask; the records and their number -> out_cand / out_n (either
-// may be null); host_out (pinned, 2 x u64): [1] = rank << 32 | score, then, released, [0] = winner index << 32 | K (0: no candidate).
-void launch_polish_winner(const Points& pts, const PolishCand* cand, const uint32_t* n_cand, uint32_t want, float tau2, float* Rt12,
-                          uint8_t* mask, PolishCand* out_cand, uint32_t* out_n, uint64_t* host_out, hipStream_t st);
+void launch_polish(const Points& pts, const PolishSet& ps, uint32_t max_iter, float tau2, float thr, int score_mode, double* scratch,
+                   hipStream_t st);
+// The candidate with the largest score (ties: the earlier one) -> out.Rt12, out.mask; the records and their number -> out_cand / out_n (either
+// may be null); out.host_out (pinned, 2 x u64): [1] = rank << 32 | score, then, released, [0] = winner index << 32 | K (0: no candidate).
+void launch_polish_winner(const Points& pts, const PolishSet& ps, const WinnerOut& out, PolishCand* out_cand, uint32_t* out_n, float tau2,
+                          hipStream_t st);
 
 // ---- descriptor matching (sc_match; sc_match.hip) -------------------------------------------------------
 // One call: fsrc ns x dim, ftgt nt x dim (row-major fp32, device); knn 1 .. 4; mutual / r2 (> 0: the ratio test, r2 = ratio^2) with

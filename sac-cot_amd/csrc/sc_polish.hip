@@ -255,21 +255,22 @@ __global__ __launch_bounds__(256) void polish_winner_kernel(const float* __restr
 
 }  // namespace
 
-void launch_polish_select(const uint32_t* cnt, const uint32_t* sel_key, uint32_t T, const float* RtSoA, uint32_t ld_local, uint32_t want,
-                          PolishCand* cand, uint32_t* n_cand, hipStream_t st) {
-  hipLaunchKernelGGL(polish_select_kernel, dim3(1), dim3(POLISH_THREADS), 0, st, cnt, sel_key, T, RtSoA, ld_local, want, cand, n_cand);
+void launch_polish_select(const PolishSet& ps, const uint32_t* cnt, const uint32_t* sel_key, uint32_t T, const float* RtSoA, uint32_t ld_local,
+                          hipStream_t st) {
+  hipLaunchKernelGGL(polish_select_kernel, dim3(1), dim3(POLISH_THREADS), 0, st, cnt, sel_key, T, RtSoA, ld_local, ps.want, ps.cand, ps.n_cand);
 }
 
-void launch_polish(const Points& pts, PolishCand* cand, const uint32_t* n_cand, uint32_t want, uint32_t max_iter, float tau2, float thr,
-                   int score_mode, double* scratch, hipStream_t st) {
-  hipLaunchKernelGGL(polish_kernel, dim3(want), dim3(POLISH_THREADS), 0, st, pts.planes, pts.n, pts.ld, cand, n_cand, max_iter, tau2, thr,
-                     score_mode, scratch);
+void launch_polish(const Points& pts, const PolishSet& ps, uint32_t max_iter, float tau2, float thr, int score_mode, double* scratch,
+                   hipStream_t st) {
+  hipLaunchKernelGGL(polish_kernel, dim3(ps.want), dim3(POLISH_THREADS), 0, st, pts.planes, pts.n, pts.ld, ps.cand, (const uint32_t*)ps.n_cand,
+                     max_iter, tau2, thr, score_mode, scratch);
 }
 
-void launch_polish_winner(const Points& pts, const PolishCand* cand, const uint32_t* n_cand, uint32_t want, float tau2, float* Rt12,
-                          uint8_t* mask, PolishCand* out_cand, uint32_t* out_n, uint64_t* host_out, hipStream_t st) {
-  hipLaunchKernelGGL(polish_winner_kernel, dim3((pts.n + 255) / 256), dim3(256), 0, st, pts.planes, pts.n, pts.ld, cand, n_cand, want, tau2,
-                     Rt12, mask, out_cand, out_n, reinterpret_cast<unsigned long long*>(host_out));
+void launch_polish_winner(const Points& pts, const PolishSet& ps, const WinnerOut& out, PolishCand* out_cand, uint32_t* out_n, float tau2,
+                          hipStream_t st) {
+  hipLaunchKernelGGL(polish_winner_kernel, dim3((pts.n + 255) / 256), dim3(256), 0, st, pts.planes, pts.n, pts.ld, (const PolishCand*)ps.cand,
+                     (const uint32_t*)ps.n_cand, ps.want, tau2, out.Rt12, out.mask, out_cand, out_n,
+                     reinterpret_cast<unsigned long long*>(out.host_out));
 }
 
 }  // namespace sc

@@ -83,7 +83,7 @@ void launch_sort_u64(const uint64_t* in, uint64_t* out, size_t n, void* temp, si
     uint64_t* dst = (pass & 1) ? out : pong;
     const int shift = 32 + 8 * pass;
     hipLaunchKernelGGL(rs_hist_kernel, dim3(nb), dim3(256), 0, st, src, n, shift, bh, nb);
-    launch_scan_u32(bh, cells, off, scan_tmp, tn, st);
+    launch_scan_u32(ScanWork{scan_tmp, tn}, bh, cells, off, ScanExtra{}, st);
     hipLaunchKernelGGL(rs_scatter_kernel, dim3(nb), dim3(64), 0, st, src, dst, n, shift, off, nb);
     src = dst;
   }

@@ -199,7 +199,7 @@ __global__ __launch_bounds__(64 * EBK_ROWS) void edge_build_kernel(const uint64_
   const int wi = i >> 6, bi = i & 63;
   const RowSide row = row_side(planes, ld, i, dv);
   const EdgeOut out{ei, ej, es, cap};
-  // ---- the row's words: prefix popcounts, the strong row cleared (not sc_compat.hip's row_word_stats: this form keeps the
+  // ---- the row's words: prefix popcounts, the strong row cleared (not sc_rows.hip's row_word_stats: this form keeps the
   // upper-triangle words in registers for the edges below and counts the bits BELOW the diagonal, for the CSR base)
   uint32_t d_all = 0, d_low = 0;
   uint64_t up[NCH];

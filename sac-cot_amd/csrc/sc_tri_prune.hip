@@ -692,9 +692,9 @@ __global__ __launch_bounds__(1024) void cost_split_kernel(const uint32_t* __rest
     own_edge[threadIdx.x] = edge_off[row];
   }
 }
-void launch_cost_split(const uint32_t* rowcost, const uint64_t* edge_off, int n, uint32_t rank, uint32_t world,
-                       uint32_t* own_row, uint64_t* own_edge, hipStream_t st) {
-  hipLaunchKernelGGL(cost_split_kernel, dim3(1), dim3(1024), 0, st, rowcost, edge_off, n, rank, world, own_row, own_edge);
+void launch_cost_split(const RowOffsets& ro, const ShardCut& cut, const uint32_t* rowcost, int n, hipStream_t st) {
+  hipLaunchKernelGGL(cost_split_kernel, dim3(1), dim3(1024), 0, st, rowcost, (const uint64_t*)ro.edge_off, n, cut.rank, cut.world,
+                     cut.own_row, cut.own_edge);
 }
 void launch_strong_rowcost(const Graph& g, const Pruned& pr, uint32_t* rowcost, hipStream_t st) {
   hipLaunchKernelGGL(strong_rowcost_kernel, dim3((unsigned)((g.n + 3) / 4)), dim3(256), 0, st, pr.mbits, g.n, g.W, rowcost);
