@@ -71,6 +71,8 @@ struct Tuning {
 // 1 .. 4095 are handed out one per launch, so words of earlier launches read as "nothing yet".  ticket / err: two
 // words that are NEVER descriptor storage (a ticket that aliased an old descriptor would hand out garbage tile
 // indices): the ticket is zero between launches (the last tile of a launch resets it).
+// A descriptor carries 50 bits of value (sc_block.hpp): every prefix of a look-back launch, its total included, stays below
+// 2^50.  desc is 8-byte aligned; one area serves launches of any tile count, each under an epoch of its own.
 struct LbArgs {
   uint32_t* ticket = nullptr;
   uint32_t* err = nullptr;
@@ -161,7 +163,11 @@ void launch_shard_split(const RowOffsets& ro, const ShardCut& cut, int n, hipStr
 //   range (device, [lo, hi)): outside it every input is known to be zero — tiles wholly outside are neither read nor
 //     written (sharded stage B: the triangle counts of the edges other ranks enumerate); out[n] is still the total;
 //   deg / degp / ebase: also ebase[i] = (u32) out[i] - (deg[i] - degp[i]), the CSR base of row i (launch_edge_fill).
-//   lb.epoch != 0: the single-pass (decoupled look-back) form.
+//   lb.epoch != 0: the single-pass (decoupled look-back) form.  PRECONDITION: the total is below 2^50 (the value field of a
+//     descriptor, see LbArgs) — the forms without look-back carry 64 bits and have no such limit.
+// Alignment (every form, and the select / compaction kernels' key arrays likewise): `in` / wkey and `out` are 16-byte aligned —
+// whole tiles are read as uint4 and written as pairs of u64.  The one-block form (n <= 8192) does not look at `range`: there the
+// inputs outside it ARE zero.
 struct ScanExtra {
   LbArgs lb;
   const uint64_t* range = nullptr;
@@ -478,7 +484,8 @@ KeyView cand_view(const void* blobs, size_t blob_bytes, uint32_t world, size_t c
 // is then below k*).  Otherwise *host_flag = 1 (pinned; 0 is written otherwise): the call must be repeated with bigger blobs.
 void launch_merge_check(const void* blobs, size_t blob_bytes, uint32_t world, const SelectState* sel, uint64_t* host_flag,
                         hipStream_t st);
-// ranked order: sortkey ascending = (key desc, ordinal asc).  Implemented with rocPRIM (sc_sort.hip).
+// ranked order: sortkey ascending = (key desc, ordinal asc).  A hand-written stable LSD radix sort of the HIGH 32 bits (sc_sort.hip):
+// the low halves must already ascend (they are the input positions).  temp: sort_temp_bytes(n); less, and nothing is launched.
 size_t sort_temp_bytes(size_t n);
 void launch_sort_u64(const uint64_t* in, uint64_t* out, size_t n, void* temp, size_t temp_bytes, hipStream_t st);
 // selected position -> (i,j,k); the list stays in ordinal ((i,j,k) ascending) order

@@ -155,8 +155,8 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_downsweep_kernel(const uint
                                                                       ScanEbase eb) {
   __shared__ uint64_t lds[8];
   __shared__ uint64_t wsum[4][SCAN_SUB];
-  const bool dead = scan_tile_dead(range, blockIdx.x) && !(SELF && blockIdx.x == gridDim.x - 1);  // block-uniform
-  if (dead) return;
+  const bool outside = scan_tile_dead(range, blockIdx.x);  // block-uniform
+  if (outside && !(SELF && blockIdx.x == gridDim.x - 1)) return;  // (the last tile of the SELF form still owes out[n])
   ScanTile t;
   scan_tile_load(in, n, blockIdx.x, range, false, wsum, t);
   uint64_t pre;
@@ -167,7 +167,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_downsweep_kernel(const uint
   } else {
     pre = bsum[blockIdx.x];
   }
-  scan_tile_store(out, n, blockIdx.x, pre, t, eb);
+  if (!outside) scan_tile_store(out, n, blockIdx.x, pre, t, eb);  // (a tile wholly outside the range is never written, in any form)
   if (SELF && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
     out[n] = pre + t.tot;
     if (host_total) publish_host(host_total, pre + t.tot);
