@@ -52,6 +52,7 @@ extern "C" {
 #define SC_HAS_MERGE 1  /* this header declares sc_merge_poses* and sc_merge_default_params (added within 0.10) */
 #define SC_HAS_PAIRS_CYCLES 1  /* this header declares sc_pairs_cycles*, sc_cycles_default_params and sc_cycles_thresholds (added within 0.10) */
 #define SC_HAS_PAIRS_SYNC 1  /* this header declares sc_pairs_sync*, sc_sync_default_params and sc_sync_thresholds (added within 0.10) */
+#define SC_HAS_PAIRS_SOLVE 1  /* this header declares sc_pairs_solve*, sc_solve_default_params and sc_solve_thresholds (added within 0.10) */
 #define SC_HAS_MATCH_GUIDED 1  /* this header declares sc_match_guided*, sc_register_guided_features and sc_guide_default_params (added within 0.10) */
 #define SC_HAS_MATCH_GUIDED_POSES 1  /* this header declares sc_match_guided_poses*, sc_register_guided_poses_features and SC_GUIDE_MAX_POSES (added within 0.10) */
 #define SC_HAS_MATCH_GUIDED_BATCH 1  /* this header declares sc_match_guided_batch*, sc_match_guided_pairs* and sc_register_guided_{batch,pairs}_features_device (added within 0.10) */
@@ -1661,9 +1662,9 @@ int sc_merge_poses_batch(sc_ctx* ctx, const float* src, const float* tgt, const 
  * (200 bytes a pair), two states and the tallies of a set (224 bytes a set) and the round words; the host form adds device copies
  * of its arrays, in the pool every host form shares.  Allocated by the first such call, counted in workspace_bytes and held against
  * the cap (SC_ENOMEM, nothing enqueued).  A context that never calls these entries allocates and runs nothing new.
- * Not here / not built: a block solver — conjugate gradients on the graph Laplacian, Gauss-Newton on the pairs' 6 x 6 information
- * matrices — which is the follow-up where lists are chains: this entry diffuses along them, as said above; robust re-weighting
- * between the rounds; several anchors; a sharded form. */
+ * Not here: a block solver — Gauss-Newton on the pairs' 6 x 6 information matrices, conjugate gradients on the graph Laplacian —
+ * is sc_pairs_solve (below), which takes this entry's d_set as its start and is the answer where lists are chains: this entry
+ * diffuses along them, as said above.  Not built: robust re-weighting between the rounds; several anchors; a sharded form. */
 #define SC_SYNC_STATUS 1u   /* flags: a pose record holds an int32 status at byte 48 */
 typedef struct sc_sync_params {    /* 32 bytes */
   uint32_t size;         /* = sizeof(sc_sync_params)                                   */
@@ -1709,6 +1710,179 @@ int sc_pairs_sync_device(sc_ctx* ctx, uint32_t n_sets, const uint32_t* pairs, ui
 int sc_pairs_sync(sc_ctx* ctx, uint32_t n_sets, const uint32_t* pairs, uint32_t n_pairs, const sc_sync_params* sp,
                   const void* pose, uint32_t pose_stride, const void* use, uint32_t use_stride, const float* weight,
                   sc_sync_set* set, sc_sync_pair* pair, sc_sync_summary* sum);
+
+/* ---- Gauss-Newton pose-graph solve of a pair list's sets: sc_pairs_solve --------------------------------------------------
+ * sc_pairs_sync places the sets, and diffuses along chains; sc_pose_info_* leaves a 6 x 6 information matrix per pair that weighs
+ * its pose.  These entries take both: from a start X_0 (sc_pairs_sync's d_set as it stands, or an earlier call's own d_set) they
+ * minimise the sum over the usable pairs of xi_p^T info_p xi_p, xi_p the six-vector by which the pair's two sets miss its pose, by
+ * Gauss-Newton steps whose linear systems are solved by block-Jacobi preconditioned conjugate gradients, all of it on the device,
+ * stream-ordered behind sc_pairs_sync_device with no host word in between.
+ * The method's limits.  No damping and no line search: a step that raises the cost is undone and ends the call (SC_SOLVE_STOP_ROSE),
+ * so the start has to lie in the basin that sc_pairs_sync's result lies in.  The stopping rule is sc_pairs_sync's — no set moved
+ * by more than the tolerances in a step — and here a step is a Newton step, not a diffusion round.  Measured on the reference
+ * (tests/solve_ref.py), noise 0.01 rad / 0.02 units, info from 100 points a pair, tolerances 1e-6, cg_tol 1e-3: the bare ring of 40
+ * sets, which sc_pairs_sync leaves unconverged after 256 rounds at 1e-6, stops CONVERGED from that result after 5 steps of 64 inner
+ * iterations, cost 0.02326 -> 0.010395 (a dense solver's optimum: 0.010395); the odometry strip of 200 sets with 40 closures, which
+ * sc_pairs_sync leaves unconverged likewise, keeps 4 steps of 64 at the defaults, cost 0.7261 -> 0.410234, and the fifth rises in
+ * the last digits (ROSE); at max_inner 256 it stops CONVERGED after 4 steps and 510 iterations (dense optimum 0.410230: Gauss-Newton
+ * drops a second-order term, and its fixed point is a relative 1e-5 above).  On chains the inner solve is the slow part: block
+ * Jacobi does not shorten a chain, every step of the ring runs to max_inner.  A component of known
+ * sets that no usable path joins to the anchor is legal and deterministic, and solved only up to its own gauge: its sets move
+ * together by whatever rigid motion conjugate gradients from zero leave in the singular system.
+ *
+ * Inputs.  n_sets, pairs (HOST), n_pairs, d_pose, pose_stride, d_use, use_stride: exactly those of sc_pairs_sync, under the same
+ * rules and limits (SC_CYCLES_MAX_PAIRS, SC_CYCLES_MAX_DEGREE; SC_SOLVE_STATUS for SC_SYNC_STATUS).  d_info: NULL (every matrix
+ * the 6 x 6 identity) or n_pairs records of info_stride bytes: double info[36] at byte 0, row-major, order and meaning those of
+ * sc_pose_info_result; with SC_SOLVE_INFO_STATUS an int32 status at byte 296.  info_stride is a multiple of 8 and at least 288
+ * (300 with the flag): an array of sc_pose_info_result fits as it stands, stride 320.  d_init: n_sets records of init_stride
+ * bytes, a multiple of 8 and at least 160: an int32 status at byte 48 and double X[12] at byte 64 — sc_sync_set and sc_solve_set
+ * are such records.  A NULL d_info and an array of identity records give the same bytes.  Nothing of the inputs is written; d_set
+ * may be d_init.
+ * Thresholds, derived on the host in double: r2_max and e2_max exactly as sc_sync_thresholds derives them from rot_tol and
+ * trans_tol, and cg2 = (double)cg_tol * (double)cg_tol.  sc_solve_thresholds returns exactly the three values a call uses.
+ *
+ * Definitions.  The call is a function of the list, the poses, use, info, init and the parameters alone, bit for bit.  All
+ * arithmetic is fp64; every operation is a plain rounded product, sum, difference, quotient or square root in the order written;
+ * nothing is fused; no sine, cosine or other library function appears.  "sum_k a_k, left to right" is ((a_0 + a_1) + a_2) + ...,
+ * the first term taken as it is.  valid(p), T(x->y), the inverse and M = B o A are those of sc_pairs_cycles; rot(M), the sorted
+ * list of a set, and "64 slots, folded" are those of sc_pairs_sync.
+ *   known(s)   init status(s) == SC_OK and the twelve of init X(s) finite.  X_0(s) = init X(s), bit for bit, for every s.
+ *   usable(p)  valid(p), pairs[2p] != pairs[2p + 1], use(p) != 0 (or d_use NULL), the 36 of info_p finite and its status SC_OK (or no
+ *              flag; d_info NULL: info_p = the identity, 1.0 and +0.0), and both of its sets known.
+ *   state(s)   SC_SOLVE_UNKNOWN if not known(s); else SC_SOLVE_ANCHOR if s == anchor; else SC_SOLVE_ISOLATED if no usable pair
+ *              names s; else SC_SOLVE_FREE.  Only free sets ever move; every other set keeps X_0(s).
+ *   error      of usable pair p stored (a, b) at state X: Xi = the inverse of X(b), D = Xi o X(a), E = D o T_p(b->a) (the inverse of
+ *              the record, as sc_pairs_cycles orients it).  xi = (omega, v): omega_0 = (E.R_21 - E.R_12) / 2.0,
+ *              omega_1 = (E.R_02 - E.R_20) / 2.0, omega_2 = (E.R_10 - E.R_01) / 2.0, v = E.t.  y_i = sum_j info[6 i + j] * xi_j,
+ *              j = 0 .. 5 left to right; cost_p = sum_i xi_i * y_i, left to right; w2 = sum_i omega_i * omega_i,
+ *              v2 = sum_i v_i * v_i, left to right.  A pair that is not usable has cost_p = w2 = v2 = +0.0.
+ *   cost       of a state: chunks of 64 consecutive pairs (the last one shorter), each summed from +0.0 in increasing p,
+ *              s = s + cost_p; then the chunk sums summed from +0.0 in increasing order.
+ *   linearised under X'(s) = exp(delta_s) o X(s), the perturbation on the left, in the common frame, rotation first: with R, t of
+ *              X(b), A is the 6 x 6 matrix Ad(X(b)^-1): A[i][j] = A[3 + i][3 + j] = R_ji, A[i][3 + j] = +0.0,
+ *              A[3 + i][j] = -(c x t)_j with c = column i of R = (R_0i, R_1i, R_2i) and x sc_pairs_sync's cross product
+ *              (i, j = 0 .. 2).  M[i][j] = sum_k info[6 i + k] * A[k][j]; W[i][j] = W[j][i] = sum_k A[k][i] * M[k][j] for i <= j;
+ *              g_i = sum_k A[k][i] * y_k; every k = 0 .. 5 left to right, the zeros of A multiplied like any entry.  The dependence
+ *              of xi's Jacobian on xi is dropped (Gauss-Newton).  The normal matrix is the graph Laplacian with the blocks W_p:
+ *              H_aa += W_p, H_bb += W_p, H_ab = H_ba = -W_p; the right-hand side is -g, g_a += g_p, g_b -= g_p.
+ *   row sums   of a free set s over its sorted list: entry i, on pair p to neighbour n, is LIVE if usable(p).  64 slots, each
+ *              component +0.0; a live entry i adds into slot i mod 64 in increasing i, the slots are folded h = 32 .. 1, the sum
+ *              is slot 0.  G(s): acc_c = acc_c + g_p[c] where s is the pair's stored first set, acc_c = acc_c - g_p[c] where it
+ *              is the second.  Hd(s): acc_c = acc_c + W_p[c] for the 21 c with row <= column.  (H d)(s) for a vector d with a
+ *              six-vector per set: e_j = d(s)_j - d(n)_j, u_c = sum_j W_p[c][j] * e_j left to right, acc_c = acc_c + u_c.
+ *   factor     of Hd(s), H_ij = H_ji its entries, once per step: for j = 0 .. 5: u_k = L_jk * D_k (k < j); a = H_jj, then
+ *              a = a - L_jk * u_k for k = 0 .. j-1; D_j = a; for i = j+1 .. 5: a = H_ij, then a = a - L_ik * u_k for
+ *              k = 0 .. j-1; L_ij = a / D_j.  If any D_j is not > 0.0 or not finite, s is HELD for this step: it does not
+ *              move, and its `degenerate` grows by one.  ACTIVE = free and not held.
+ *   solve      z = Hd(s)^-1 r of an active s: y_i = r_i, then y_i = y_i - L_ik * y_k for k = 0 .. i-1 (i = 0 .. 5);
+ *              w_i = y_i / D_i; for i = 5 .. 0: z_i = w_i, then z_i = z_i - L_ki * z_k for k = i+1 .. 5.  z = 0 where s is not
+ *              active.
+ *   grand sum  of a value per set (a.b = sum_c a_c * b_c, c = 0 .. 5 left to right, for an active set; +0.0 for every other):
+ *              chunks of 64 consecutive sets, each summed from +0.0 in increasing s, then the chunk sums summed from +0.0 in
+ *              increasing order.
+ *   inner      the solve of step j, preconditioned conjugate gradients on the active sets (d = 0 elsewhere): x = 0, r = -G,
+ *              z = solve(r), rz_0 = grand sum of r.z.  If rz_0 == 0.0 the solve ends with no iteration.  Iteration
+ *              i = 1 .. max_inner: p = z if i == 1, else beta = rz_{i-1} / rz_{i-2}, p_c = z_c + beta * p_c; q = (H p); pq = grand
+ *              sum of p.q; if pq is not > 0.0 or not finite the solve ends and this iteration is not applied.  alpha =
+ *              rz_{i-1} / pq; x_c = x_c + alpha * p_c; r_c = r_c - alpha * q_c; z = solve(r); rz_i = grand sum of r.z; the solve
+ *              ends if rz_i <= cg2 * rz_0, or at i == max_inner.  inner_j = the iterations applied.
+ *   step       of an active set with x = (omega, v): Q = rot(I + [omega]x), the matrix rows (1.0, -omega_2, omega_1),
+ *              (omega_2, 1.0, -omega_0), (-omega_1, omega_0, 1.0); R' = rot(Q R), Q R by the composition's rule; t'_i =
+ *              ((Q_i0 * t_0 + Q_i1 * t_1) + Q_i2 * t_2) + v_i.  If any of the twelve is not finite the set is unchanged and its
+ *              `degenerate` grows by one: no NaN is ever written into X.  A set is CHANGED in step j if it was stepped and
+ *              dR2 > r2_max or dt2 > e2_max, dR2 and dt2 sc_pairs_sync's between X_j(s) and X_{j-1}(s).
+ *   outer      c_0 = cost(X_0).  If no set is free: K = 0, SC_SOLVE_STOP_CONVERGED.  Step j = 1 .. max_outer: linearise at
+ *              X_{j-1}, factor, inner solve, step, c_j = cost(X_j).  If !(c_j <= c_{j-1}) — a cost that is not finite
+ *              included — the step is undone: K = j - 1, SC_SOLVE_STOP_ROSE.  Otherwise, if no set changed in step j or rz_0 was
+ *              0.0: K = j, SC_SOLVE_STOP_CONVERGED; otherwise at j == max_outer: K = j, SC_SOLVE_STOP_MAX_OUTER.  J = the last
+ *              step taken (K, or K + 1 after ROSE).  The outputs are X_K and the pairs' errors at X_K.
+ * Outputs.  sc_solve_set (160 bytes, the layout of sc_sync_set) per set at d_set[s]: Rt is X_K(s) rounded once to fp32 (sc_pairs_sync's
+ * remark on components past FLT_MAX holds), status the init status passed through, X = X_K(s); an unknown set's X is its init X.
+ * sc_solve_pair (48 bytes) per pair at d_pair[p], sc_solve_summary (64 bytes) at d_sum.
+ * Forms.  sc_pairs_solve_device: everything but pairs in HBM; it enqueues and returns without waiting, reads no host word, and the
+ * number of its stream operations depends on max_outer and max_inner only: a copy, a memset and
+ * 5 + max_outer * (4 + 2 * max_inner) launches (prepare, sets, linearise, decide; per step: factor, two per inner iteration —
+ * the product, which forms p on the fly, and the update —, step, linearise, decide; finish).  Every stop is the device's: a
+ * launch whose work is over returns at once on a word an earlier launch left.  A call with max_outer * max_inner > 2048 is
+ * refused.  sc_pairs_solve: host arrays; waits.  Like every batch entry they end the frame a context may hold.
+ * Errors: the CALL returns SC_EINVAL, decided on the host before anything is enqueued, sc_last_error naming which: a NULL argument
+ * other than d_use and d_info (a NULL ctx: no text); everything sc_pairs_sync refuses of n_sets, n_pairs, the list, pose_stride and
+ * use_stride; size wrong, max_outer outside 1 .. 32, max_inner outside 1 .. 256, their product above 2048, rot_tol or trans_tol
+ * as sc_pairs_sync refuses them, cg_tol not finite or outside [0, 1), an unknown flag; with d_info, an info_stride that breaks the
+ * rule above; an init_stride that does; an anchor >= n_sets; a call outstanding on the context.
+ * Workspace: the copied list as sc_pairs_sync stages it, 584 bytes a pair (the oriented poses, W_p, g_p, the errors of two states),
+ * 664 bytes a set (two states, the vectors of the inner solve with p twice, the factor, the tallies), the chunk sums and the
+ * control words.  Allocated by the first such call, counted in workspace_bytes and held against the cap (SC_ENOMEM, nothing
+ * enqueued); the host form adds device copies of its arrays, in the pool every host form shares.  A context that never calls
+ * these entries allocates and runs nothing new.
+ * Not here / not built: Levenberg-Marquardt damping; robust re-weighting or line processes; the exact point cost from the moments
+ * sc_pose_info sums; a one-workgroup form for small graphs (a small list pays the launches: see DESIGN); several anchors; a
+ * sharded form.  The ends of the fp32 range are the next, test-only change; the finite guards above are built and stated now. */
+#define SC_SOLVE_STATUS 1u       /* flags: a pose record holds an int32 status at byte 48 */
+#define SC_SOLVE_INFO_STATUS 2u  /* flags: an info record holds an int32 status at byte 296 */
+#define SC_SOLVE_FREE 0u
+#define SC_SOLVE_ANCHOR 1u
+#define SC_SOLVE_UNKNOWN 2u
+#define SC_SOLVE_ISOLATED 3u
+#define SC_SOLVE_STOP_CONVERGED 1u
+#define SC_SOLVE_STOP_ROSE 2u
+#define SC_SOLVE_STOP_MAX_OUTER 3u
+typedef struct sc_solve_params {   /* 32 bytes */
+  uint32_t size;         /* = sizeof(sc_solve_params)                                  */
+  uint32_t anchor;       /* the set that keeps its X; < n_sets; default 0              */
+  uint32_t max_outer;    /* Gauss-Newton steps at most, 1 .. 32; default 8             */
+  uint32_t max_inner;    /* iterations of a step's solve at most, 1 .. 256; default 64 */
+  uint32_t flags;        /* SC_SOLVE_STATUS | SC_SOLVE_INFO_STATUS, or 0               */
+  float    rot_tol;      /* radians, finite, in [0, pi]                                */
+  float    trans_tol;    /* finite, >= 0, in the poses' unit                           */
+  float    cg_tol;       /* finite, in [0, 1)                                          */
+} sc_solve_params;
+typedef struct sc_solve_set {      /* 160 bytes */
+  float    Rt[12];         /* X_K(s) rounded once: R row-major, then t                                  */
+  int32_t  status;         /* the init status, passed through                                           */
+  uint32_t state;          /* SC_SOLVE_FREE / ANCHOR / UNKNOWN / ISOLATED                               */
+  uint32_t degenerate;     /* steps among 1 .. J in which s was held, or stepped to no finite pose      */
+  uint32_t reserved;       /* written as 0                                                              */
+  double   X[12];          /* X_K(s)                                                                    */
+} sc_solve_set;
+typedef struct sc_solve_pair {     /* 48 bytes */
+  int32_t  status;         /* SC_OK, the pose status passed through, or SC_EINVAL for a non-finite Rt   */
+  uint32_t used;           /* 1: usable(p)                                                              */
+  double   cost;           /* cost_p at X_K                                                             */
+  double   w2;             /* omega.omega at X_K                                                        */
+  double   v2;             /* v.v at X_K                                                                */
+  uint32_t reserved[4];    /* written as 0                                                              */
+} sc_solve_pair;
+typedef struct sc_solve_summary {  /* 64 bytes */
+  uint32_t outer;          /* K                                                        */
+  uint32_t stop;           /* SC_SOLVE_STOP_*                                          */
+  uint32_t inner_total;    /* inner_1 + ... + inner_J                                  */
+  uint32_t inner_last;     /* inner_J; 0 where J is 0                                  */
+  uint32_t free_sets;      /* sets whose state is SC_SOLVE_FREE                        */
+  uint32_t used_pairs;     /* pairs whose `used` is 1                                  */
+  uint32_t held_last;      /* sets held in step J                                      */
+  uint32_t reserved;       /* written as 0                                             */
+  double   cost0;          /* c_0                                                      */
+  double   cost;           /* c_K                                                      */
+  double   rz0;            /* rz_0 of step J; 0.0 where J is 0                         */
+  double   reserved2;      /* written as 0.0                                           */
+} sc_solve_summary;
+int sc_solve_default_params(sc_solve_params* sp);   /* size, anchor 0, max_outer 8, max_inner 64; everything else 0: the tolerances are the caller's */
+/* host only, no context: out[0] = r2_max, out[1] = e2_max, out[2] = cg2; SC_EINVAL for a NULL argument or parameters a call refuses
+ * (the anchor apart) */
+int sc_solve_thresholds(const sc_solve_params* sp, double out[3]);
+/* pairs a HOST array; d_pose n_pairs records of pose_stride bytes, d_use NULL or a word every use_stride bytes, d_info NULL or
+ * n_pairs records of info_stride bytes, d_init n_sets records of init_stride bytes, d_set n_sets records, d_pair n_pairs records,
+ * d_sum one */
+int sc_pairs_solve_device(sc_ctx* ctx, uint32_t n_sets, const uint32_t* pairs, uint32_t n_pairs, const sc_solve_params* sp,
+                          const void* d_pose, uint32_t pose_stride, const void* d_use, uint32_t use_stride,
+                          const void* d_info, uint32_t info_stride, const void* d_init, uint32_t init_stride,
+                          sc_solve_set* d_set, sc_solve_pair* d_pair, sc_solve_summary* d_sum);
+/* the same with host arrays (pose, use, info, init, set, pair, sum); waits */
+int sc_pairs_solve(sc_ctx* ctx, uint32_t n_sets, const uint32_t* pairs, uint32_t n_pairs, const sc_solve_params* sp,
+                   const void* pose, uint32_t pose_stride, const void* use, uint32_t use_stride,
+                   const void* info, uint32_t info_stride, const void* init, uint32_t init_stride,
+                   sc_solve_set* set, sc_solve_pair* pair, sc_solve_summary* sum);
 
 /* ---- two-phase form for one-process-per-GPU sharding --------------------------------
  * Phase 1: A and B replicated, C1+C2 on this rank's blocks of the top-T list; writes this rank's winner key

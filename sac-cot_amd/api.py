@@ -248,6 +248,41 @@ SYNC_SET_DTYPE = np.dtype(ScSyncSet)          # sc_sync_set as a numpy record
 SYNC_PAIR_DTYPE = np.dtype(ScSyncPair)        # sc_sync_pair as a numpy record
 SYNC_SUMMARY_DTYPE = np.dtype(ScSyncSummary)  # sc_sync_summary as a numpy record
 SC_SYNC_STATUS = 1
+class ScSolveParams(C.Structure):
+    """Mirror of `sc_solve_params` (include/saccot.h), 32 bytes: the anchor set, the Gauss-Newton steps at most (1 .. 32), the iterations
+    of a step's solve at most (1 .. 256; their product at most 2048), SC_SOLVE_STATUS | SC_SOLVE_INFO_STATUS or 0, the two tolerances
+    of the stopping rule and the relative tolerance of the inner solve (in [0, 1))."""
+    _fields_ = [("size", C.c_uint32), ("anchor", C.c_uint32), ("max_outer", C.c_uint32), ("max_inner", C.c_uint32), ("flags", C.c_uint32),
+                ("rot_tol", C.c_float), ("trans_tol", C.c_float), ("cg_tol", C.c_float)]
+
+
+class ScSolveSet(C.Structure):
+    """Mirror of `sc_solve_set` (include/saccot.h), 160 bytes, the layout of sc_sync_set: a legal pose record with a status (Rt,
+    status) in front of the set's state, its tally and the fp64 pose."""
+    _fields_ = [("Rt", C.c_float * 12), ("status", C.c_int32), ("state", C.c_uint32), ("degenerate", C.c_uint32), ("reserved", C.c_uint32),
+                ("X", C.c_double * 12)]
+
+
+class ScSolvePair(C.Structure):
+    """Mirror of `sc_solve_pair` (include/saccot.h), 48 bytes: one pair's status, whether it was used, its cost and the two parts of
+    its error at the result."""
+    _fields_ = [("status", C.c_int32), ("used", C.c_uint32), ("cost", C.c_double), ("w2", C.c_double), ("v2", C.c_double), ("reserved", C.c_uint32 * 4)]
+
+
+class ScSolveSummary(C.Structure):
+    """Mirror of `sc_solve_summary` (include/saccot.h), 64 bytes: the steps kept, why the call stopped, the inner iterations, the free
+    sets and used pairs, the sets held in the last step, the cost at the start and at the result, rz_0 of the last step."""
+    _fields_ = [("outer", C.c_uint32), ("stop", C.c_uint32), ("inner_total", C.c_uint32), ("inner_last", C.c_uint32), ("free_sets", C.c_uint32),
+                ("used_pairs", C.c_uint32), ("held_last", C.c_uint32), ("reserved", C.c_uint32), ("cost0", C.c_double), ("cost", C.c_double),
+                ("rz0", C.c_double), ("reserved2", C.c_double)]
+
+
+SOLVE_SET_DTYPE = np.dtype(ScSolveSet)          # sc_solve_set as a numpy record
+SOLVE_PAIR_DTYPE = np.dtype(ScSolvePair)        # sc_solve_pair as a numpy record
+SOLVE_SUMMARY_DTYPE = np.dtype(ScSolveSummary)  # sc_solve_summary as a numpy record
+SC_SOLVE_STATUS, SC_SOLVE_INFO_STATUS = 1, 2
+SC_SOLVE_FREE, SC_SOLVE_ANCHOR, SC_SOLVE_UNKNOWN, SC_SOLVE_ISOLATED = 0, 1, 2, 3
+SC_SOLVE_STOP_CONVERGED, SC_SOLVE_STOP_ROSE, SC_SOLVE_STOP_MAX_OUTER = 1, 2, 3
 SC_GUIDE_POSE_STATUS = 1  # sc_guide_params.flags, the sc_match_guided_batch / _poses entries only: the pose records hold an int32 status at byte 48
 SC_GUIDE_MAX_POSES = 64  # pose records per call of sc_match_guided_poses at most
 SC_MATCH_BATCH_MAX_N = 4096  # rows a side of one problem of sc_match_batch
@@ -315,6 +350,7 @@ _PP, _SP, _QP, _MP, _GP = (C.POINTER(t) for t in (ScParams, ScStats, ScPolishPar
 _IP, _ZP, _AP, _TP, _RP = (C.POINTER(t) for t in (ScPoseInfoParams, ScPolishPosesParams, ScAssignParams, ScSettleParams, ScMergeParams))
 _CP = C.POINTER(ScCycleParams)
 _YP = C.POINTER(ScSyncParams)
+_VSP = C.POINTER(ScSolveParams)
 _PROTOTYPES = {
     "sc_version": [],
     "sc_strerror": ([_INT], C.c_char_p),
@@ -408,6 +444,10 @@ _PROTOTYPES = {
     "sc_sync_thresholds": [_YP, C.POINTER(C.c_double)],
     "sc_pairs_sync": [_VP, _U32, _U32P, _U32, _YP, _VP, _U32, _VP, _U32, _F32P, _VP, _VP, _VP],
     "sc_pairs_sync_device": [_VP, _U32, _U32P, _U32, _YP, _VP, _U32, _VP, _U32, _VP, _VP, _VP, _VP],
+    "sc_solve_default_params": [_VSP],
+    "sc_solve_thresholds": [_VSP, C.POINTER(C.c_double)],
+    "sc_pairs_solve": [_VP, _U32, _U32P, _U32, _VSP, _VP, _U32, _VP, _U32, _VP, _U32, _VP, _U32, _VP, _VP, _VP],
+    "sc_pairs_solve_device": [_VP, _U32, _U32P, _U32, _VSP, _VP, _U32, _VP, _U32, _VP, _U32, _VP, _U32, _VP, _VP, _VP],
     "sc_hypothesize_device": [_VP, _VP, _VP, _I64, _PP, _VP, _SP],
     "sc_finalize_device": [_VP, _VP, _VP, _VP, _SP],
     "sc_hypothesize_begin_device": [_VP, _VP, _VP, _I64, _PP, _VP, _SP],
@@ -543,6 +583,23 @@ def sync_thresholds(sparams: ScSyncParams) -> tuple[float, float]:
     if rc != SC_OK:
         raise SacCotError(rc, "sc_sync_thresholds")
     return out[0], out[1]
+
+
+def make_solve_params(rot_tol: float = 0.0, trans_tol: float = 0.0, cg_tol: float = 0.0, anchor: int = 0, max_outer: int = 8, max_inner: int = 64,
+                      flags: int = 0) -> ScSolveParams:
+    """sc_solve_params: the tolerances of the stopping rule (rot_tol in radians, in [0, pi]; trans_tol >= 0) and of the inner solve
+    (cg_tol in [0, 1)) are the caller's; anchor < n_sets, max_outer 1 .. 32, max_inner 1 .. 256, max_outer * max_inner <= 2048, flags
+    SC_SOLVE_STATUS | SC_SOLVE_INFO_STATUS or 0."""
+    return _sized(ScSolveParams, anchor, max_outer, max_inner, flags, rot_tol, trans_tol, cg_tol)
+
+
+def solve_thresholds(vparams: ScSolveParams) -> tuple[float, float, float]:
+    """sc_solve_thresholds: (r2_max, e2_max, cg2), exactly the three values a call with these parameters uses."""
+    out = (C.c_double * 3)()
+    rc = load_library().sc_solve_thresholds(C.byref(vparams), out)
+    if rc != SC_OK:
+        raise SacCotError(rc, "sc_solve_thresholds")
+    return float(out[0]), float(out[1]), float(out[2])
 
 
 def shard_plan(params: ScParams, n: int) -> ScShardPlan:
@@ -1685,6 +1742,58 @@ class Registrar:
         self._frame_n = 0
         self._check(self._lib.sc_pairs_sync_device(self._h, n_sets, _p(pairs), len(pairs) // 2, C.byref(sparams), d_pose, pose_stride,
                                                    d_use or None, use_stride, d_weight or None, d_set, d_pair, d_sum))
+
+    # ---- Gauss-Newton pose-graph solve of a pair list's sets (include/saccot.h, sc_pairs_solve) ----------------------------------
+    def pairs_solve(self, n_sets: int, pairs, pose, init, vparams: ScSolveParams | None = None, use=None, info=None, **kw):
+        """sc_pairs_solve: pairs, pose and use as pairs_sync takes them; init (n_sets,) records of 160 bytes or more with an int32
+        status at byte 48 and double X[12] at byte 64 — pairs_sync's sets, or an earlier call's own; info None (every matrix the
+        identity), (P, 36) float64, or (P,) records with the 36 doubles at byte 0 (POSE_INFO_RESULT_DTYPE: pose_info's records as they
+        stand) -> (sets (n_sets,) of SOLVE_SET_DTYPE, pairs (P,) of SOLVE_PAIR_DTYPE, summary: one record of SOLVE_SUMMARY_DTYPE).
+        kw: rot_tol, trans_tol, cg_tol, anchor, max_outer, max_inner, flags (make_solve_params)."""
+        q = vparams or make_solve_params(**kw)
+        pairs = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1)
+        npairs = len(pairs) // 2
+        pose, stride = self._pose_records(pose, npairs)
+        use_ptr, use_stride = None, 4
+        if use is not None:
+            use = np.ascontiguousarray(use)
+            if use.dtype == CYCLE_RESULT_DTYPE:
+                use_ptr, use_stride = use.ctypes.data + CYCLE_RESULT_DTYPE.fields["alive"][1], CYCLE_RESULT_DTYPE.itemsize
+            else:
+                use = np.ascontiguousarray(use, dtype=np.uint32).reshape(-1)
+                use_ptr = use.ctypes.data
+            if len(use) != npairs:
+                raise ValueError("pairs_solve: use holds one word (or one sc_cycle_result) per pair")
+        info_ptr, info_stride = None, 288
+        if info is not None:
+            info = np.ascontiguousarray(info)
+            if info.dtype.fields is None:
+                info = np.ascontiguousarray(info, dtype=np.float64).reshape(-1, 36)
+            if len(info) != npairs:
+                raise ValueError("pairs_solve: info holds 36 doubles (or one record) per pair")
+            info_ptr, info_stride = info.ctypes.data, info.strides[0]
+        init = np.ascontiguousarray(init)
+        if init.dtype.fields is None or len(init) != n_sets:
+            raise ValueError("pairs_solve: init holds one record (SYNC_SET_DTYPE, SOLVE_SET_DTYPE) per set")
+        sets = np.zeros(max(n_sets, 1), SOLVE_SET_DTYPE)
+        res = np.zeros(max(npairs, 1), SOLVE_PAIR_DTYPE)
+        summary = np.zeros(1, SOLVE_SUMMARY_DTYPE)
+        self._frame_n = 0
+        self._check(self._lib.sc_pairs_solve(self._h, n_sets, _p(pairs), npairs, C.byref(q), _vp(pose), stride, use_ptr, use_stride, info_ptr,
+                                             info_stride, init.ctypes.data, init.strides[0], _vp(sets), _vp(res), _vp(summary)))
+        return sets[:n_sets], res[:npairs], summary[0]
+
+    def pairs_solve_device(self, n_sets: int, pairs, vparams: ScSolveParams, d_pose: int, pose_stride: int, d_use: int, use_stride: int,
+                           d_info: int, info_stride: int, d_init: int, init_stride: int, d_set: int, d_pair: int, d_sum: int):
+        """sc_pairs_solve_device: pairs a HOST array (P, 2); pose records, the use words (0: every pair), the info records (0: the
+        identity), the init records (n_sets), the set records (n_sets of 160 bytes), the pair records (P of 48 bytes) and the summary
+        (64 bytes) in HBM; enqueues on the context's stream — a number of operations that depends on max_outer and max_inner only —
+        and returns without waiting."""
+        pairs = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1)
+        self._frame_n = 0
+        self._check(self._lib.sc_pairs_solve_device(self._h, n_sets, _p(pairs), len(pairs) // 2, C.byref(vparams), d_pose, pose_stride,
+                                                    d_use or None, use_stride, d_info or None, info_stride, d_init, init_stride, d_set, d_pair,
+                                                    d_sum))
 
     def hypothesize_device(self, d_src: int, d_tgt: int, n: int, params: ScParams, d_key: int):
         st = ScStats(C.sizeof(ScStats))

@@ -191,7 +191,11 @@ struct Workspace {
       cyc_meta, cyc_wide, cyc_state,
       // sc_pairs_sync.  meta: the pairs' records, the sorted neighbour entries and the list starts; wide: the oriented fp64 poses and
       // the pairs' weights; state: the round words, the two buffers of the sets' states and their tallies (sc_sync_check.hpp)
-      sync_meta, sync_wide, sync_state;
+      sync_meta, sync_wide, sync_state,
+      // sc_pairs_solve.  meta: as sync_meta; pair: the oriented fp64 poses, W_p, g_p, the errors of two states and the usable words;
+      // set: the two states, the vectors of the inner solve, the factors and the sets' tallies; ctl: the control words, the sets'
+      // tallies of usable pairs and the chunk sums (sc_solve_check.hpp)
+      solve_meta, solve_pair, solve_set, solve_ctl;
 };
 constexpr size_t N_WORKSPACE_BUFS = sizeof(Workspace) / sizeof(Buf);
 static_assert(std::is_standard_layout<Workspace>::value && alignof(Workspace) == alignof(Buf) && sizeof(Workspace) == N_WORKSPACE_BUFS * sizeof(Buf),

@@ -1184,6 +1184,91 @@ struct SyncJob {
 // launch per round (a wave per set, a lane per slot of the header's sum), finish (the set records, the residuals, the summary).
 void launch_pairs_sync(const SyncJob& job, hipStream_t st);
 
+// ---- Gauss-Newton pose-graph solve of a pair list's sets (sc_pairs_solve; sc_solve.hip) ---------------------------------------
+// The three output records: sc_solve_set, sc_solve_pair and sc_solve_summary of include/saccot.h, field for field (sc_solve.hip
+// asserts the sizes and the offsets).
+struct SolveSetRecord {
+  float Rt[12];
+  int32_t status;
+  uint32_t state, degenerate, reserved;
+  double X[12];
+};
+struct SolvePairRecord {
+  int32_t status;
+  uint32_t used;
+  double cost, w2, v2;
+  uint32_t reserved[4];
+};
+struct SolveSummary {
+  uint32_t outer, stop, inner_total, inner_last, free_sets, used_pairs, held_last, reserved;
+  double cost0, cost, rz0, reserved2;
+};
+constexpr uint32_t SOLVE_OUTER_MAX = 32, SOLVE_INNER_MAX = 256, SOLVE_PRODUCT_MAX = 2048;
+// The control words, ZERO at launch.  A word is written by ONE workgroup of a launch (or added to by atomics) and read by LATER
+// launches only, never by the launch that writes it: nothing depends on the order in which a launch's workgroups run.
+//   stop, K, J     the decide launch's verdict: stop != 0 ends every later launch at once.
+//   free_sets, used_pairs   tallies of the sets and prepare launches.
+//   changed[j], held[j], inner[j]   tallies of step j: sets changed by the step launch, sets held by the factor launch, and the
+//                  iterations applied (the decide launch counts them from live_u).
+//   live_p[x], live_u[x], x = (j - 1) * max_inner + i: iteration i of step j is to be multiplied (written by its product launch,
+//                  read by its update launch) / has been applied (written by its update launch, read by the next product launch).
+//                  A word left 0 ends the chain: every later launch of the step finds its predecessor's word 0.
+//   cost[j]        c_j;  rz0[j]: rz_0 of step j;  rz[i]: rz_i of the step in hand.
+struct SolveCtl {
+  uint32_t stop, K, J, free_sets, used_pairs, pad[3];
+  uint32_t changed[SOLVE_OUTER_MAX + 1], held[SOLVE_OUTER_MAX + 1], inner[SOLVE_OUTER_MAX + 1], pad2;
+  double cost[SOLVE_OUTER_MAX + 1], rz0[SOLVE_OUTER_MAX + 1], rz[SOLVE_INNER_MAX + 1];
+  uint32_t live_p[SOLVE_PRODUCT_MAX + 2], live_u[SOLVE_PRODUCT_MAX + 2];
+};
+// What a set's launches keep about it: its state (SC_SOLVE_*), whether it is active in the step in hand, the init status, and the
+// steps in which it was held or stepped to no finite pose.
+struct SolveInfo {
+  uint32_t state, active;
+  int32_t status;
+  uint32_t degenerate;
+};
+// rec, entries, off: as SyncJob's; pose, use, info, init: the caller's (use, info: nullptr or an array).  Per pair: wide 2 x 12
+// doubles, usable a word, W 36 doubles, g 6, err 2 x 3 (cost_p, w2, v2 of state j & 1).  Per set: X 2 x 12 doubles (buffer j & 1
+// holds X_j), x, r, z, q 6 each, p 2 x 6 (buffer i & 1 holds the p of iteration i), fac 21 (L row-major below the diagonal, then D),
+// sinfo; deg: the usable pairs that name it (a tally, zeroed with ctl).  Chunk sums: rzc 2 x set chunks (buffer i & 1: rz_i), pqc
+// set chunks, costc pair chunks.
+struct SolveJob {
+  const uint32_t* rec;
+  const uint64_t* entries;
+  const uint32_t* off;
+  const void* pose;
+  const void* use;
+  const void* info;
+  const void* init;
+  double* wide;
+  uint32_t* usable;
+  double* W;
+  double* g;
+  double* err;
+  double* X;
+  double* x;
+  double* r;
+  double* z;
+  double* q;
+  double* p;
+  double* fac;
+  SolveInfo* sinfo;
+  uint32_t* deg;
+  double* rzc;
+  double* pqc;
+  double* costc;
+  SolveCtl* ctl;
+  SolveSetRecord* set;
+  SolvePairRecord* pair;
+  SolveSummary* sum;
+  double r2_max, e2_max, cg2;
+  uint32_t n_sets, n_pairs, pose_stride, use_stride, info_stride, init_stride, anchor, max_outer, max_inner;
+  int status, info_status;  // a pose record holds a status at byte 48; an info record one at byte 296
+};
+// 5 + max_outer * (4 + 2 * max_inner) launches: prepare, sets, linearise, decide; per step: factor, (product, update) per inner
+// iteration, step, linearise, decide; finish.
+void launch_pairs_solve(const SolveJob& job, hipStream_t st);
+
 // ---- descriptor matching for a batch of small problems (sc_match_batch; sc_match_batch.hip) -----------------
 // Problem b owns rows [src_off[b], src_off[b + 1]) of fsrc and [tgt_off[b], tgt_off[b + 1]) of ftgt (1 .. MATCH_BATCH_MAX_N rows
 // each, checked by the caller) and the output slot that starts at entry slot[b] = src_off[b] * knn.  tile_map: n_tiles pairs

@@ -1,9 +1,9 @@
 // sc_pose64.hpp — a rigid transform in fp64 and the three operations the pair-list entries define on it in include/saccot.h
-// (sc_pairs_cycles, sc_pairs_sync): the inverse, the composition, and the widening of a caller's pose record into the pair's TWO
+// (sc_pairs_cycles, sc_pairs_sync, sc_pairs_solve): the inverse, the composition, and the widening of a caller's pose record into the pair's TWO
 // oriented transforms — lower set -> higher set and back, one of them the record itself, the other its inverse by the header's
 // formula.  Every operation is a plain rounded product or sum in the order written: the files that include this say
-// `#pragma clang fp contract(off)` themselves, and the library is built with -ffp-contract=off.  Device code only; two users:
-// sc_cycles.hip and sc_sync.hip.
+// `#pragma clang fp contract(off)` themselves, and the library is built with -ffp-contract=off.  Device code only; three users:
+// sc_cycles.hip, sc_sync.hip and sc_solve.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
