@@ -1670,6 +1670,29 @@ class Registrar:
         self._check(self._lib.sc_merge_poses_batch_device(self._h, d_src, d_tgt, _p(offset), nb, C.byref(params), C.byref(mparams),
                                                           d_pose, pose_stride, n_poses, d_out, d_parent, d_count or None))
 
+    # ---- the entries on a pair list: what they take alike -----------------------------------------------------------------------
+    @staticmethod
+    def _pair_list(pairs):
+        """pairs (P, 2) set indices as the pair-list entries take them -> (flat uint32 array, P)"""
+        pairs = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1)
+        return pairs, len(pairs) // 2
+
+    @staticmethod
+    def _use_words(use, npairs: int, who: str):
+        """use as pairs_sync and pairs_solve take it: None, (P,) words, or (P,) records of CYCLE_RESULT_DTYPE whose `alive` words are
+        read in place -> (the array to keep alive through the call, address of the first word or None, stride in bytes)"""
+        if use is None:
+            return None, None, 4
+        use = np.ascontiguousarray(use)
+        if use.dtype == CYCLE_RESULT_DTYPE:
+            ptr, stride = use.ctypes.data + CYCLE_RESULT_DTYPE.fields["alive"][1], CYCLE_RESULT_DTYPE.itemsize
+        else:
+            use = np.ascontiguousarray(use, dtype=np.uint32).reshape(-1)
+            ptr, stride = use.ctypes.data, 4
+        if len(use) != npairs:
+            raise ValueError(f"{who}: use holds one word (or one sc_cycle_result) per pair")
+        return use, ptr, stride
+
     # ---- loop consistency of a pair list's poses (include/saccot.h, sc_pairs_cycles) --------------------------------------------
     def pairs_cycles(self, n_sets: int, pairs, pose, cparams: ScCycleParams | None = None, keep=None, **kw):
         """sc_pairs_cycles: pairs (P, 2) set indices (source, target); pose (P,) records of any dtype whose items start with float
@@ -1677,8 +1700,7 @@ class Registrar:
         never dropped -> (records (P,) of CYCLE_RESULT_DTYPE, summary: one record of CYCLE_SUMMARY_DTYPE).  kw: rot_tol, trans_tol,
         min_ok, max_rounds, flags (make_cycle_params)."""
         q = cparams or make_cycle_params(**kw)
-        pairs = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1)
-        npairs = len(pairs) // 2
+        pairs, npairs = self._pair_list(pairs)
         pose, stride = self._pose_records(pose, npairs)
         if keep is not None:
             keep = np.ascontiguousarray(keep, dtype=np.uint8).reshape(-1)
@@ -1695,9 +1717,9 @@ class Registrar:
         """sc_pairs_cycles_device: pairs a HOST array (P, 2); pose records (pose_stride bytes each, read only), the keep bytes (0:
         none), the output records (P of 48 bytes) and the summary (32 bytes) in HBM; enqueues on the context's stream — a number of
         operations that depends on max_rounds only — and returns without waiting."""
-        pairs = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1)
+        pairs, npairs = self._pair_list(pairs)
         self._frame_n = 0
-        self._check(self._lib.sc_pairs_cycles_device(self._h, n_sets, _p(pairs), len(pairs) // 2, C.byref(cparams), d_pose, pose_stride,
+        self._check(self._lib.sc_pairs_cycles_device(self._h, n_sets, _p(pairs), npairs, C.byref(cparams), d_pose, pose_stride,
                                                      d_keep or None, d_res, d_sum))
 
     # ---- absolute poses of a pair list's sets (include/saccot.h, sc_pairs_sync) ---------------------------------------------------
@@ -1707,19 +1729,9 @@ class Registrar:
         place; weight None or (P,) float32 -> (sets (n_sets,) of SYNC_SET_DTYPE, pairs (P,) of SYNC_PAIR_DTYPE, summary: one record of
         SYNC_SUMMARY_DTYPE).  kw: rot_tol, trans_tol, anchor, max_rounds, flags (make_sync_params)."""
         q = sparams or make_sync_params(**kw)
-        pairs = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1)
-        npairs = len(pairs) // 2
+        pairs, npairs = self._pair_list(pairs)
         pose, stride = self._pose_records(pose, npairs)
-        use_ptr, use_stride = None, 4
-        if use is not None:
-            use = np.ascontiguousarray(use)
-            if use.dtype == CYCLE_RESULT_DTYPE:
-                use_ptr, use_stride = use.ctypes.data + CYCLE_RESULT_DTYPE.fields["alive"][1], CYCLE_RESULT_DTYPE.itemsize
-            else:
-                use = np.ascontiguousarray(use, dtype=np.uint32).reshape(-1)
-                use_ptr = use.ctypes.data
-            if len(use) != npairs:
-                raise ValueError("pairs_sync: use holds one word (or one sc_cycle_result) per pair")
+        use, use_ptr, use_stride = self._use_words(use, npairs, "pairs_sync")
         if weight is not None:
             weight = _f32c(weight).reshape(-1)
             if len(weight) != npairs:
@@ -1738,9 +1750,9 @@ class Registrar:
         bytes; 0: every pair), the weights (P floats; 0: 1.0), the set records (n_sets of 160 bytes), the pair records (P of 32 bytes)
         and the summary (32 bytes) in HBM; enqueues on the context's stream — a number of operations that depends on max_rounds only —
         and returns without waiting."""
-        pairs = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1)
+        pairs, npairs = self._pair_list(pairs)
         self._frame_n = 0
-        self._check(self._lib.sc_pairs_sync_device(self._h, n_sets, _p(pairs), len(pairs) // 2, C.byref(sparams), d_pose, pose_stride,
+        self._check(self._lib.sc_pairs_sync_device(self._h, n_sets, _p(pairs), npairs, C.byref(sparams), d_pose, pose_stride,
                                                    d_use or None, use_stride, d_weight or None, d_set, d_pair, d_sum))
 
     # ---- Gauss-Newton pose-graph solve of a pair list's sets (include/saccot.h, sc_pairs_solve) ----------------------------------
@@ -1751,19 +1763,9 @@ class Registrar:
         stand) -> (sets (n_sets,) of SOLVE_SET_DTYPE, pairs (P,) of SOLVE_PAIR_DTYPE, summary: one record of SOLVE_SUMMARY_DTYPE).
         kw: rot_tol, trans_tol, cg_tol, anchor, max_outer, max_inner, flags (make_solve_params)."""
         q = vparams or make_solve_params(**kw)
-        pairs = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1)
-        npairs = len(pairs) // 2
+        pairs, npairs = self._pair_list(pairs)
         pose, stride = self._pose_records(pose, npairs)
-        use_ptr, use_stride = None, 4
-        if use is not None:
-            use = np.ascontiguousarray(use)
-            if use.dtype == CYCLE_RESULT_DTYPE:
-                use_ptr, use_stride = use.ctypes.data + CYCLE_RESULT_DTYPE.fields["alive"][1], CYCLE_RESULT_DTYPE.itemsize
-            else:
-                use = np.ascontiguousarray(use, dtype=np.uint32).reshape(-1)
-                use_ptr = use.ctypes.data
-            if len(use) != npairs:
-                raise ValueError("pairs_solve: use holds one word (or one sc_cycle_result) per pair")
+        use, use_ptr, use_stride = self._use_words(use, npairs, "pairs_solve")
         info_ptr, info_stride = None, 288
         if info is not None:
             info = np.ascontiguousarray(info)
@@ -1789,9 +1791,9 @@ class Registrar:
         identity), the init records (n_sets), the set records (n_sets of 160 bytes), the pair records (P of 48 bytes) and the summary
         (64 bytes) in HBM; enqueues on the context's stream — a number of operations that depends on max_outer and max_inner only —
         and returns without waiting."""
-        pairs = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1)
+        pairs, npairs = self._pair_list(pairs)
         self._frame_n = 0
-        self._check(self._lib.sc_pairs_solve_device(self._h, n_sets, _p(pairs), len(pairs) // 2, C.byref(vparams), d_pose, pose_stride,
+        self._check(self._lib.sc_pairs_solve_device(self._h, n_sets, _p(pairs), npairs, C.byref(vparams), d_pose, pose_stride,
                                                     d_use or None, use_stride, d_info or None, info_stride, d_init, init_stride, d_set, d_pair,
                                                     d_sum))
 

@@ -18,7 +18,7 @@ SOURCES = ["sc_stage.hip", "sc_compat.hip", "sc_rows.hip", "sc_scan.hip", "sc_tr
            "sc_capi_cycles.hip", "sc_cycles.hip",
            "sc_capi_sync.hip", "sc_sync.hip",
            "sc_capi_solve.hip", "sc_solve.hip"]
-HEADERS = ["sc_arith.hpp", "sc_block.hpp", "sc_kernels.hpp", "sc_tri.hpp", "sc_score.hpp", "sc_gramref.hpp", "sc_refine.hpp", "sc_refit.hpp", "sc_batch_frame.hpp", "sc_info.hpp", "sc_winner.hpp", "sc_ctx.hpp", "sc_frame_check.hpp", "sc_match_tile.hpp", "sc_match_batch_check.hpp", "sc_match_guided_check.hpp", "sc_match_guided_batch_check.hpp", "sc_match_guided_poses_check.hpp", "sc_pairs_check.hpp", "sc_chunks.hpp", "sc_capi_pose.hpp", "sc_pose_check.hpp", "sc_assign.hpp", "sc_assign_check.hpp", "sc_settle.hpp", "sc_settle_check.hpp", "sc_merge.hpp", "sc_merge_check.hpp", "sc_cycles_check.hpp", "sc_pose64.hpp", "sc_sync_check.hpp", "sc_rot.hpp", "sc_solve_check.hpp", os.path.join("..", "..", "include", "saccot.h"),
+HEADERS = ["sc_arith.hpp", "sc_block.hpp", "sc_kernels.hpp", "sc_tri.hpp", "sc_score.hpp", "sc_gramref.hpp", "sc_refine.hpp", "sc_refit.hpp", "sc_batch_frame.hpp", "sc_info.hpp", "sc_winner.hpp", "sc_ctx.hpp", "sc_frame_check.hpp", "sc_match_tile.hpp", "sc_match_batch_check.hpp", "sc_match_guided_check.hpp", "sc_match_guided_batch_check.hpp", "sc_match_guided_poses_check.hpp", "sc_pairs_check.hpp", "sc_chunks.hpp", "sc_capi_pose.hpp", "sc_capi_graph.hpp", "sc_pose_check.hpp", "sc_assign.hpp", "sc_assign_check.hpp", "sc_settle.hpp", "sc_settle_check.hpp", "sc_merge.hpp", "sc_merge_check.hpp", "sc_cycles_check.hpp", "sc_pose64.hpp", "sc_sync_check.hpp", "sc_rot.hpp", "sc_solve_check.hpp", os.path.join("..", "..", "include", "saccot.h"),
            os.path.join("..", "..", "include", "saccot_debug.h")]
 # -ffp-contract=off: the canonical arithmetic (sc_arith.hpp) fuses only where it says fmaf.
 # -amdgpu-mfma-vgpr-form: MFMA results land in VGPRs (unified register file on gfx950), no v_accvgpr_read copies.

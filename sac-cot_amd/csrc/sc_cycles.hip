@@ -2,9 +2,8 @@
 // the list to a fixed point.  max_rounds + 2 launches on data the host staged once (sc_cycles_check.hpp: a record per pair, every
 // set's neighbour entries sorted by (neighbour, pair)):
 //
-//   prepare   a thread per pair: the record's validity, its status, the pose widened ONCE into two oriented fp64 transforms —
-//             lower set -> higher set and back, one of them the record itself, the other its inverse by the header's formula —,
-//             alive_0, and the head of the pair's output record.
+//   prepare   a thread per pair: the prologue every pair-list entry shares (sc_pose64.hpp: the record's validity, its status, the
+//             pose widened ONCE into two oriented fp64 transforms), alive_0, and the head of the pair's output record.
 //   round k   a WAVE per pair that is in alive_{k-1}.  The pair sits on {lo, hi}; a loop of three closes through every set z that
 //             is a neighbour of both.  The lanes take the entries of the SHORTER of the two lists, one each, and look the entry's
 //             set up in the longer list by binary search: a list longer than a workgroup (a hub) costs its pairs a logarithm, not a
@@ -69,11 +68,6 @@ __device__ __forceinline__ double order_value(uint64_t k) {
   return __longlong_as_double((long long)((k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k));
 }
 constexpr uint64_t KEY_MAX = ~0ull;  // above every double's key: "no triangle yet" of a minimum
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 __device__ __forceinline__ uint64_t wave_min_u64(uint64_t v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) { const uint64_t u = __shfl_xor(v, o); v = u < v ? u : v; }
@@ -89,15 +83,7 @@ __global__ __launch_bounds__(CT) void cycles_prepare_kernel(const CyclesJob job)
   const uint32_t p = blockIdx.x * CT + threadIdx.x;
   bool edge = false;
   if (p < job.n_pairs) {
-    const uint32_t* const w = reinterpret_cast<const uint32_t*>(static_cast<const char*>(job.pose) + (size_t)p * job.pose_stride);
-    float M[12];
-#pragma unroll
-    for (int c = 0; c < 12; c++) M[c] = __uint_as_float(w[c]);
-    int status = job.status ? (int)w[12] : SC_OK;  // (without the flag nothing past byte 47 is read)
-    if (status == SC_OK && !finite12(M)) status = SC_EINVAL;
-    const uint32_t* const r = job.rec + (size_t)CYCLES_REC_WORDS * p;
-    edge = status == SC_OK && r[CW_LO] != r[CW_HI];
-    if (edge) store_oriented_pair(widen_t64(M), r, job.wide, p);
+    const int status = pair_prologue(job.pose, job.pose_stride, job.status, job.rec, job.wide, p, &edge);
     job.alive[p] = edge ? 1 : 0;  // alive_0 (buffer 1 is written whole by round 1)
     CycleRecord out{};
     out.status = status;

@@ -1,10 +1,13 @@
-// sc_cycles_check.hpp — the host-only rules of sc_pairs_cycles (include/saccot.h): what is refused of sc_cycle_params, of the stride
-// and of the list, the two thresholds, and the ADJACENCY a call builds from the list alone — every set's neighbour entries, sorted
-// by (neighbour set, pair index), as offsets plus entries — with the record a pair's wave finds its two lists through.  The pose
-// records are every pose entry's (sc_pose_check.hpp).  No HIP: sc_capi_cycles.hip includes it, and so does
-// tests/native/cycles_check_main.cpp, a program of its own that runs these functions under the sanitizers on the CPU.
+// sc_cycles_check.hpp — the host-only rules of sc_pairs_cycles (include/saccot.h), and what every entry on a pair list shares with
+// it (sc_pairs_sync, sc_pairs_solve), said once: the rules of the two tolerances, of use_stride and of the anchor with their
+// thresholds; what is refused of sc_cycle_params, of the stride and of the list; the ADJACENCY a call builds from the list alone —
+// every set's neighbour entries, sorted by (neighbour set, pair index), as offsets plus entries — with the record a pair's wave
+// finds its two lists through; and the IMAGE a call stages for the device (pairs_image).  The pose records are every pose entry's
+// (sc_pose_check.hpp).  No HIP: sc_capi_graph.hpp includes it, and so do tests/native/cycles_check_main.cpp and
+// sync_check_main.cpp, programs of their own that run these functions under the sanitizers on the CPU.
 #pragma once
 #include <math.h>
+#include <string.h>
 
 #include <algorithm>
 
@@ -15,6 +18,21 @@ namespace sc {
 constexpr float CYCLES_ROT_TOL_MAX = 3.14159274f;  // the float nearest pi
 constexpr uint32_t CYCLES_ROUNDS_MAX = 64;
 
+// ---- what the pair-list entries ask alike of their parameters — the rule that is broken; nullptr: it is kept — and the thresholds
+// they derive alike.  r2_max is on the squared Frobenius distance of two rotations, 2 theta^2 to first order — not on a trace:
+// 1 + 2 cos(rot_tol) is exactly 3.0 below 2e-8.
+inline const char* pairs_tol_error(float rot_tol, float trans_tol) {
+  if (!(rot_tol >= 0.f && rot_tol <= CYCLES_ROT_TOL_MAX)) return "rot_tol must be finite and in [0, pi]";
+  if (!(trans_tol >= 0.f && trans_tol < INFINITY)) return "trans_tol must be finite and >= 0";
+  return nullptr;
+}
+inline const char* pairs_use_stride_error(bool has_use, uint32_t use_stride) {
+  return has_use && (use_stride < 4 || use_stride % 4 != 0) ? "use_stride must be a multiple of 4 and at least 4" : nullptr;
+}
+inline const char* pairs_anchor_error(uint32_t anchor, uint32_t n_sets) { return anchor >= n_sets ? "anchor must be less than n_sets" : nullptr; }
+inline double pairs_r2_max(float rot_tol) { return 2.0 * (double)rot_tol * (double)rot_tol; }
+inline double pairs_e2_max(float trans_tol) { return (double)trans_tol * (double)trans_tol; }
+
 inline bool cycles_reads_status(const sc_cycle_params* cp) { return (cp->flags & SC_CYCLES_STATUS) != 0; }
 
 // What a call refuses of its parameter block and of the stride — the rule that is broken, for the caller to put its name in front
@@ -22,8 +40,7 @@ inline bool cycles_reads_status(const sc_cycle_params* cp) { return (cp->flags &
 inline const char* cycles_params_error(const sc_cycle_params* cp) {
   if (cp->size != sizeof(sc_cycle_params)) return "params->size is not sizeof(sc_cycle_params)";
   if (cp->max_rounds < 1 || cp->max_rounds > CYCLES_ROUNDS_MAX) return "max_rounds must be 1 .. 64";
-  if (!(cp->rot_tol >= 0.f && cp->rot_tol <= CYCLES_ROT_TOL_MAX)) return "rot_tol must be finite and in [0, pi]";
-  if (!(cp->trans_tol >= 0.f && cp->trans_tol < INFINITY)) return "trans_tol must be finite and >= 0";
+  if (const char* what = pairs_tol_error(cp->rot_tol, cp->trans_tol)) return what;
   if ((cp->flags & ~SC_CYCLES_STATUS) || cp->reserved[0] || cp->reserved[1]) return "an unknown flag, or a reserved field that is not 0";
   return nullptr;
 }
@@ -35,7 +52,7 @@ inline const char* cycles_stride_error(const sc_cycle_params* cp, uint32_t pose_
 // The two thresholds a call uses (of parameters that cycles_params_error accepts): tr_min, e2_max.
 inline void cycles_thresholds(const sc_cycle_params* cp, double out[2]) {
   out[0] = 1.0 + 2.0 * cos((double)cp->rot_tol);
-  out[1] = (double)cp->trans_tol * (double)cp->trans_tol;
+  out[1] = pairs_e2_max(cp->trans_tol);
 }
 
 // What a call refuses of the list.  deg: scratch of n_sets words, left holding every set's degree — the listed pairs that name it, a
@@ -80,8 +97,6 @@ inline uint64_t cycles_entry_count(const uint32_t* pairs, uint32_t n_pairs) {
   for (uint32_t p = 0; p < n_pairs; p++) n += pairs[2 * (size_t)p] != pairs[2 * (size_t)p + 1] ? 2 : 0;
   return n;
 }
-// what a call stages for the device: the pairs' records, then the entries (the records are a multiple of 8 bytes)
-inline uint64_t cycles_meta_bytes(uint32_t n_pairs, uint64_t n_entries) { return (uint64_t)CYCLES_REC_WORDS * 4 * n_pairs + 8 * n_entries; }
 
 // The build, on a list that cycles_list_error accepts.  off: n_sets + 1 words; entries: cycles_entry_count of them; rec:
 // CYCLES_REC_WORDS x n_pairs words — all three written whole.  A counting sort by set, then every list sorted.
@@ -110,6 +125,24 @@ inline void cycles_adjacency(uint32_t n_sets, const uint32_t* pairs, uint32_t n_
     r[CW_LO_BEGIN] = self ? 0 : off[lo]; r[CW_LO_END] = self ? 0 : off[lo + 1];
     r[CW_HI_BEGIN] = self ? 0 : off[hi]; r[CW_HI_END] = self ? 0 : off[hi + 1];
   }
+}
+
+// ---- the image: what a call stages for the device.  The pairs' records, then the entries, then — for an entry whose waves own a
+// set, not a pair — the n_sets + 1 list starts (the records and the entries are multiples of 8 bytes: each part is aligned).
+struct PairsImageAt { uint64_t rec, entries, starts; };  // where a reader finds the three parts, in bytes
+inline PairsImageAt pairs_image_at(uint32_t n_pairs, uint64_t n_entries) {
+  return PairsImageAt{0, (uint64_t)CYCLES_REC_WORDS * 4 * n_pairs, (uint64_t)CYCLES_REC_WORDS * 4 * n_pairs + 8 * n_entries};
+}
+inline uint64_t cycles_meta_bytes(uint32_t n_pairs, uint64_t n_entries) { return pairs_image_at(n_pairs, n_entries).starts; }  // without the starts
+inline uint64_t sync_off_at(uint32_t n_pairs, uint64_t n_entries) { return pairs_image_at(n_pairs, n_entries).starts; }
+inline uint64_t sync_meta_bytes(uint32_t n_sets, uint32_t n_pairs, uint64_t n_entries) { return sync_off_at(n_pairs, n_entries) + 4 * ((uint64_t)n_sets + 1); }
+// The image of a list that cycles_list_error accepts, written whole into `image`: sync_meta_bytes of them with the starts,
+// cycles_meta_bytes without.  off: n_sets + 1 words of scratch, left holding the list starts; n_entries: cycles_entry_count's.
+inline void pairs_image(uint32_t n_sets, const uint32_t* pairs, uint32_t n_pairs, uint64_t n_entries, uint32_t* off, bool starts, void* image) {
+  const PairsImageAt at = pairs_image_at(n_pairs, n_entries);
+  char* const h = static_cast<char*>(image);
+  cycles_adjacency(n_sets, pairs, n_pairs, off, reinterpret_cast<uint64_t*>(h + at.entries), reinterpret_cast<uint32_t*>(h + at.rec));
+  if (starts) memcpy(h + at.starts, off, ((size_t)n_sets + 1) * 4);
 }
 
 // ---- the device workspace behind the staged words: the oriented fp64 poses, two records of 12 doubles a pair (lower -> higher

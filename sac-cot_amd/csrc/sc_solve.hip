@@ -1,9 +1,10 @@
 // sc_solve.hip — the kernels of sc_pairs_solve (include/saccot.h): Gauss-Newton on a pair list's pose graph, the linear system of a
 // step solved by block-Jacobi preconditioned conjugate gradients.  5 + max_outer * (4 + 2 * max_inner) launches on data the host
-// staged once (sc_sync_check.hpp's records, sorted neighbour entries and list starts):
+// staged once (sc_cycles_check.hpp's image: the records, the sorted neighbour entries and the list starts):
 //
-//   prepare   a thread per pair: validity, status, use, the info record and whether both sets are known — one word a pair —, the
-//             pose widened ONCE into the two oriented fp64 transforms (sc_pose64.hpp), and the sets' tallies of usable pairs.
+//   prepare   a thread per pair: the prologue every pair-list entry shares (sc_pose64.hpp: validity, status, the pose widened ONCE
+//             into the two oriented fp64 transforms), use, the info record and whether both sets are known — one word a pair —,
+//             and the sets' tallies of usable pairs.
 //   sets      a thread per set: X_0 into buffer 0, the set's state, its record of tallies.
 //   linearise a thread per pair, a workgroup per chunk of 64 pairs: at X_j the pair's error, its cost, W_p and g_p; the chunk's
 //             cost sum.  (Launch j serves step j + 1 and is the cost evaluation of step j.)
@@ -58,25 +59,11 @@ constexpr int CH = (int)SOLVE_CHUNK; // a chunk: 64 pairs or sets, the workgroup
 constexpr int WT = 1024;             // threads of a workgroup of product: 16 waves, four of the chunk's sets each
 constexpr int FT = 256;              // of factor, whose waves hold a 6 x 6 block and its factor: 4 waves, sixteen sets each
 
-__device__ __forceinline__ bool finite64(double x) { return __builtin_fabs(x) < __builtin_inf(); }  // false for inf and NaN
-
 __device__ __forceinline__ double dot6(const double* a, const double* b) {
   double s = a[0] * b[0];
 #pragma unroll
   for (int c = 1; c < 6; c++) s = s + a[c] * b[c];
   return s;
-}
-
-// the header's inverse of a transform
-__device__ __forceinline__ T64 inverse_t64(const T64& A) {
-  T64 I;
-#pragma unroll
-  for (int i = 0; i < 3; i++)
-#pragma unroll
-    for (int j = 0; j < 3; j++) I.R[3 * i + j] = A.R[3 * j + i];
-#pragma unroll
-  for (int c = 0; c < 3; c++) I.t[c] = -((A.R[c] * A.t[0] + A.R[3 + c] * A.t[1]) + A.R[6 + c] * A.t[2]);
-  return I;
 }
 
 __device__ __forceinline__ bool init_known(const SolveJob& job, uint32_t s) {
@@ -147,16 +134,10 @@ __global__ __launch_bounds__(ST) void solve_prepare_kernel(const SolveJob job) {
   const uint32_t p = blockIdx.x * ST + threadIdx.x;
   bool usable = false;
   if (p < job.n_pairs) {
-    const uint32_t* const w = reinterpret_cast<const uint32_t*>(static_cast<const char*>(job.pose) + (size_t)p * job.pose_stride);
-    float M[12];
-#pragma unroll
-    for (int c = 0; c < 12; c++) M[c] = __uint_as_float(w[c]);
-    int status = job.status ? (int)w[12] : SC_OK;  // (without the flag nothing past byte 47 is read)
-    if (status == SC_OK && !finite12(M)) status = SC_EINVAL;
+    bool edge;
+    const int status = pair_prologue(job.pose, job.pose_stride, job.status, job.rec, job.wide, p, &edge);
     const uint32_t* const r = job.rec + (size_t)CYCLES_REC_WORDS * p;
-    const bool edge = status == SC_OK && r[CW_LO] != r[CW_HI];
-    if (edge) store_oriented_pair(widen_t64(M), r, job.wide, p);
-    const bool use = !job.use || *reinterpret_cast<const uint32_t*>(static_cast<const char*>(job.use) + (size_t)p * job.use_stride) != 0;
+    const bool use = pair_use(job.use, job.use_stride, p);
     bool info_ok = true;
     if (job.info) {
       const char* const rec = static_cast<const char*>(job.info) + (size_t)p * job.info_stride;
@@ -202,11 +183,10 @@ __global__ __launch_bounds__(CH) void solve_lin_kernel(const SolveJob job, const
   double cost = 0.0, w2 = 0.0, v2 = 0.0;
   if (p < job.n_pairs && job.usable[p]) {
     const uint32_t* const rc = job.rec + (size_t)CYCLES_REC_WORDS * p;
-    const bool fwd = rc[CW_FWD] != 0;
-    const uint32_t a = fwd ? rc[CW_LO] : rc[CW_HI], b = fwd ? rc[CW_HI] : rc[CW_LO];  // stored (a, b)
-    const T64 Xb = load_t64(X + (size_t)12 * b);
-    const T64 D = compose_t64(inverse_t64(Xb), load_t64(X + (size_t)12 * a));
-    const T64 E = compose_t64(D, load_t64(job.wide + (size_t)24 * p + (fwd ? 12 : 0)));  // T_p(b -> a): higher -> lower at 12
+    const StoredPair sp = stored_pair(rc);
+    const T64 Xb = load_t64(X + (size_t)12 * sp.b);
+    const T64 D = compose_t64(inverse_t64(Xb), load_t64(X + (size_t)12 * sp.a));
+    const T64 E = compose_t64(D, load_t64(job.wide + (size_t)24 * p + (sp.fwd ? 12 : 0)));  // T_p(b -> a): higher -> lower at 12
     double xi[6], y[6], info[36];
     xi[0] = (E.R[7] - E.R[5]) / 2.0;
     xi[1] = (E.R[2] - E.R[6]) / 2.0;

@@ -1,7 +1,7 @@
 // sc_solve_check.hpp — the host-only rules of sc_pairs_solve (include/saccot.h) that sc_pairs_sync does not already have: what is
 // refused of sc_solve_params, of the four strides and of the anchor, the three thresholds, and where the workspace areas lie.  The
-// list's rules and the adjacency are sc_cycles_check.hpp's, the staged words sc_sync_check.hpp's (the records, the entries, the
-// list starts), the pose records every pose entry's (sc_pose_check.hpp).  No HIP: sc_capi_solve.hip includes it, and so does
+// list's rules, the adjacency, the staged image (the records, the entries, the list starts) and the rules every pair-list entry
+// shares are sc_cycles_check.hpp's, the pose records every pose entry's (sc_pose_check.hpp).  No HIP: sc_capi_solve.hip includes it, and so does
 // tests/native/solve_check_main.cpp, a program of its own that runs these functions under the sanitizers on the CPU.
 #pragma once
 #include "sc_sync_check.hpp"
@@ -21,8 +21,7 @@ inline const char* solve_params_error(const sc_solve_params* sp) {
   if (sp->max_outer < 1 || sp->max_outer > SOLVE_MAX_OUTER) return "max_outer must be 1 .. 32";
   if (sp->max_inner < 1 || sp->max_inner > SOLVE_MAX_INNER) return "max_inner must be 1 .. 256";
   if (sp->max_outer * sp->max_inner > SOLVE_MAX_PRODUCT) return "max_outer * max_inner must not exceed 2048";
-  if (!(sp->rot_tol >= 0.f && sp->rot_tol <= CYCLES_ROT_TOL_MAX)) return "rot_tol must be finite and in [0, pi]";
-  if (!(sp->trans_tol >= 0.f && sp->trans_tol < INFINITY)) return "trans_tol must be finite and >= 0";
+  if (const char* what = pairs_tol_error(sp->rot_tol, sp->trans_tol)) return what;
   if (!(sp->cg_tol >= 0.f && sp->cg_tol < 1.f)) return "cg_tol must be finite and in [0, 1)";
   if (sp->flags & ~(SC_SOLVE_STATUS | SC_SOLVE_INFO_STATUS)) return "an unknown flag";
   return nullptr;
@@ -30,22 +29,19 @@ inline const char* solve_params_error(const sc_solve_params* sp) {
 inline const char* solve_stride_error(const sc_solve_params* sp, uint32_t pose_stride, bool has_use, uint32_t use_stride, bool has_info,
                                       uint32_t info_stride, uint32_t init_stride) {
   if (!pose_stride_ok(pose_stride, solve_reads_status(sp))) return "pose_stride must be a multiple of 4 and at least 48 (52 with SC_SOLVE_STATUS)";
-  if (has_use && (use_stride < 4 || use_stride % 4 != 0)) return "use_stride must be a multiple of 4 and at least 4";
+  if (const char* what = pairs_use_stride_error(has_use, use_stride)) return what;
   if (has_info && (info_stride % 8 != 0 || info_stride < (solve_reads_info_status(sp) ? SOLVE_INFO_STATUS_AT + 4 : SOLVE_INFO_BYTES)))
     return "info_stride must be a multiple of 8 and at least 288 (300 with SC_SOLVE_INFO_STATUS)";
   if (init_stride % 8 != 0 || init_stride < SOLVE_INIT_BYTES) return "init_stride must be a multiple of 8 and at least 160";
   return nullptr;
 }
-inline const char* solve_anchor_error(const sc_solve_params* sp, uint32_t n_sets) {
-  if (sp->anchor >= n_sets) return "anchor must be less than n_sets";
-  return nullptr;
-}
+inline const char* solve_anchor_error(const sc_solve_params* sp, uint32_t n_sets) { return pairs_anchor_error(sp->anchor, n_sets); }
 
-// The three thresholds a call uses (of parameters that solve_params_error accepts): r2_max and e2_max as sync_thresholds derives
-// them, and cg2.
+// The three thresholds a call uses (of parameters that solve_params_error accepts): r2_max and e2_max from where sync_thresholds
+// takes them, and cg2.
 inline void solve_thresholds(const sc_solve_params* sp, double out[3]) {
-  out[0] = 2.0 * (double)sp->rot_tol * (double)sp->rot_tol;
-  out[1] = (double)sp->trans_tol * (double)sp->trans_tol;
+  out[0] = pairs_r2_max(sp->rot_tol);
+  out[1] = pairs_e2_max(sp->trans_tol);
   out[2] = (double)sp->cg_tol * (double)sp->cg_tol;
 }
 

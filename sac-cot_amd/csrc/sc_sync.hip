@@ -1,9 +1,10 @@
 // sc_sync.hip — the kernels of sc_pairs_sync (include/saccot.h): the absolute poses of a pair list's sets by anchored Jacobi
-// averaging.  max_rounds + 2 launches on data the host staged once (sc_cycles_check.hpp's records and sorted neighbour entries,
-// and the list starts behind them: sc_sync_check.hpp):
+// averaging.  max_rounds + 2 launches on data the host staged once (sc_cycles_check.hpp's image: the records, the sorted
+// neighbour entries, and the list starts behind them):
 //
-//   prepare   a thread per pair: the record's validity, its status, use and weight — one double a pair, 0.0 where the pair is not
-//             usable —, and the pose widened ONCE into the two oriented fp64 transforms (sc_pose64.hpp, shared with sc_cycles.hip);
+//   prepare   a thread per pair: the prologue every pair-list entry shares (sc_pose64.hpp: the record's validity, its status, the
+//             pose widened ONCE into the two oriented fp64 transforms), use and weight — one double a pair, 0.0 where the pair is
+//             not usable;
 //             a thread per set: X_0 and known_0 in buffer 0, and the set's tallies cleared.
 //   round k   a WAVE per set.  The header's sum has 64 slots and entry i adds into slot i mod 64: a lane IS a slot, and takes
 //             entries lane, lane + 64, ... of the set's sorted list in that order.  For a live entry it loads the neighbour's state
@@ -47,28 +48,13 @@ namespace {
 constexpr int ST = 256;            // threads of a workgroup of every launch: four waves, a set each in a round
 constexpr int SYNC_BLOCKS = 2048;  // a round's grid at most: 8192 waves, the sets dealt round-robin to them
 
-__device__ __forceinline__ bool finite64(double x) { return __builtin_fabs(x) < __builtin_inf(); }  // false for inf and NaN
-
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 __global__ __launch_bounds__(ST) void sync_prepare_kernel(const SyncJob job) {
   const uint32_t i = blockIdx.x * ST + threadIdx.x;
   if (i < job.n_pairs) {
     const uint32_t p = i;
-    const uint32_t* const w = reinterpret_cast<const uint32_t*>(static_cast<const char*>(job.pose) + (size_t)p * job.pose_stride);
-    float M[12];
-#pragma unroll
-    for (int c = 0; c < 12; c++) M[c] = __uint_as_float(w[c]);
-    int status = job.status ? (int)w[12] : SC_OK;  // (without the flag nothing past byte 47 is read)
-    if (status == SC_OK && !finite12(M)) status = SC_EINVAL;
-    const uint32_t* const r = job.rec + (size_t)CYCLES_REC_WORDS * p;
-    const bool edge = status == SC_OK && r[CW_LO] != r[CW_HI];
-    if (edge) store_oriented_pair(widen_t64(M), r, job.wide, p);
-    const bool use = !job.use || *reinterpret_cast<const uint32_t*>(static_cast<const char*>(job.use) + (size_t)p * job.use_stride) != 0;
+    bool edge;
+    const int status = pair_prologue(job.pose, job.pose_stride, job.status, job.rec, job.wide, p, &edge);
+    const bool use = pair_use(job.use, job.use_stride, p);
     const double wt = job.weight ? (double)job.weight[p] : 1.0;
     job.wt[p] = (edge && use && wt > 0.0 && wt < __builtin_inf()) ? wt : 0.0;  // (a NaN is neither)
     job.pair[p].status = status;  // (the rest of the record is finish's)
@@ -187,13 +173,12 @@ __global__ __launch_bounds__(ST) void sync_finish_kernel(const SyncJob job) {
   }
   if (i < job.n_pairs) {
     const uint32_t* const r = job.rec + (size_t)CYCLES_REC_WORDS * i;
-    const bool fwd = r[CW_FWD] != 0;
-    const uint32_t a = fwd ? r[CW_LO] : r[CW_HI], b = fwd ? r[CW_HI] : r[CW_LO];  // stored (a, b)
+    const StoredPair sp = stored_pair(r);
     double r2 = 0.0, e2 = 0.0;
-    used = job.wt[i] > 0.0 && fin[a].known && fin[b].known;
+    used = job.wt[i] > 0.0 && fin[sp.a].known && fin[sp.b].known;
     if (used) {
-      const T64 A = load_t64(fin[a].X);
-      const T64 Q = compose_t64(load_t64(fin[b].X), load_t64(job.wide + (size_t)24 * i + (fwd ? 0 : 12)));  // the record itself
+      const T64 A = load_t64(fin[sp.a].X);
+      const T64 Q = compose_t64(load_t64(fin[sp.b].X), load_t64(job.wide + (size_t)24 * i + (sp.fwd ? 0 : 12)));  // the record itself
 #pragma unroll
       for (int c = 0; c < 9; c++) { const double d = A.R[c] - Q.R[c]; r2 = c ? r2 + d * d : d * d; }
 #pragma unroll

@@ -3,7 +3,9 @@
 // read or write past one ends the run when this is built with -fsanitize=address,undefined (tests/test_cycles_abi.py builds and
 // runs it that way; no GPU, no Python in the process).  The adjacency of every list is checked against its definition, restated
 // here the slow way: set s's entries are the pairs that name s and another set, ordered by (that set, pair index), each flagged
-// with its stored direction; a pair's record names its two sets in ascending order and the two lists' ranges.
+// with its stored direction; a pair's record names its two sets in ascending order and the two lists' ranges.  The adjacency is
+// read out of the image that a call stages (pairs_image, without the list starts), written into a buffer of exactly
+// cycles_meta_bytes; the 7-set list is written with the starts as well.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -57,9 +59,11 @@ static void adjacency(const char* what, uint32_t n_sets, const std::vector<uint3
   if (list_error(n_sets, pairs)) { printf("FAIL %s: the list is refused\n", what); failures++; return; }
   const uint64_t n_entries = sc::cycles_entry_count(pairs.data(), n_pairs);
   uint32_t* off = new uint32_t[(size_t)n_sets + 1];
-  uint64_t* entries = new uint64_t[n_entries];
-  uint32_t* rec = new uint32_t[(size_t)sc::CYCLES_REC_WORDS * n_pairs];
-  sc::cycles_adjacency(n_sets, pairs.data(), n_pairs, off, entries, rec);
+  const sc::PairsImageAt at = sc::pairs_image_at(n_pairs, n_entries);
+  char* image = new char[sc::cycles_meta_bytes(n_pairs, n_entries)];
+  sc::pairs_image(n_sets, pairs.data(), n_pairs, n_entries, off, false, image);
+  const uint64_t* entries = reinterpret_cast<const uint64_t*>(image + at.entries);
+  const uint32_t* rec = reinterpret_cast<const uint32_t*>(image + at.rec);
   bool ok = off[0] == 0 && off[n_sets] == n_entries && sc::cycles_meta_bytes(n_pairs, n_entries) == 32ull * n_pairs + 8 * n_entries;
   // every list: ascending (strictly: an entry is unique), only pairs that name s and another set, with the right direction
   std::vector<uint32_t> seen(n_pairs, 0);
@@ -88,8 +92,25 @@ static void adjacency(const char* what, uint32_t n_sets, const std::vector<uint3
     else ok = ok && r[sc::CW_LO_BEGIN] == off[lo] && r[sc::CW_LO_END] == off[lo + 1] && r[sc::CW_HI_BEGIN] == off[hi] && r[sc::CW_HI_END] == off[hi + 1];
   }
   if (!ok) { printf("FAIL %s: the adjacency is not what the list says\n", what); failures++; }
-  delete[] rec;
-  delete[] entries;
+  delete[] image;
+  delete[] off;
+}
+
+// the image with the list starts against the one without: the same records and entries, then the n_sets + 1 offsets
+static void image_with_starts(const char* what, uint32_t n_sets, const std::vector<uint32_t>& pairs) {
+  const uint32_t n_pairs = (uint32_t)(pairs.size() / 2);
+  const uint64_t n_entries = sc::cycles_entry_count(pairs.data(), n_pairs);
+  const sc::PairsImageAt at = sc::pairs_image_at(n_pairs, n_entries);
+  const uint64_t bytes = sc::sync_meta_bytes(n_sets, n_pairs, n_entries);
+  uint32_t* off = new uint32_t[(size_t)n_sets + 1];
+  char* without = new char[at.starts];
+  char* with = new char[bytes];
+  sc::pairs_image(n_sets, pairs.data(), n_pairs, n_entries, off, false, without);
+  sc::pairs_image(n_sets, pairs.data(), n_pairs, n_entries, off, true, with);
+  check(what, at.rec == 0 && at.entries == 32ull * n_pairs && at.starts == at.entries + 8 * n_entries && bytes == at.starts + 4 * ((uint64_t)n_sets + 1) &&
+                  memcmp(with, without, at.starts) == 0 && memcmp(with + at.starts, off, ((size_t)n_sets + 1) * 4) == 0 && off[n_sets] == n_entries);
+  delete[] with;
+  delete[] without;
   delete[] off;
 }
 
@@ -162,6 +183,8 @@ int main() {
   adjacency("one pair", 2, {1, 0});
   adjacency("only self pairs", 2, {0, 0, 1, 1});
   adjacency("self pairs, repeats, both directions, an unreferenced set", 6, {4, 1, 0, 0, 1, 4, 4, 1, 0, 1, 5, 4, 1, 5, 4, 4, 0, 4, 1, 4});
+  adjacency("seven sets: a self pair, a repeat, unreferenced sets", 7, {4, 1, 0, 0, 1, 4, 4, 1, 0, 1, 5, 4, 1, 5});
+  image_with_starts("seven sets: the image with its list starts", 7, {4, 1, 0, 0, 1, 4, 4, 1, 0, 1, 5, 4, 1, 5});
   {
     std::vector<uint32_t> all;  // every pair of 40 sets in a scrambled order and direction, every third one twice
     for (uint32_t k = 0; k < 40 * 39 / 2; k++) {

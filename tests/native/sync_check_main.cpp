@@ -3,7 +3,8 @@
 // reads, and where the staged words and the workspace areas lie — on exactly sized heap copies, so that a read past one ends the run
 // when this is built with -fsanitize=address,undefined (tests/test_sync_abi.py builds and runs it that way; no GPU, no Python in the
 // process).  The list's rules and the adjacency are sc_cycles_check.hpp's and have a program of their own (cycles_check_main.cpp);
-// here the staged image of a call is built the way sc_capi_sync.hip builds it, in a buffer of exactly sync_meta_bytes, and read back.
+// here the staged image of a call is written by the function that every entry stages it with (sc_cycles_check.hpp: pairs_image),
+// into a buffer of exactly sync_meta_bytes — and of exactly cycles_meta_bytes without the list starts —, and read back.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -101,11 +102,12 @@ int main() {
     const uint64_t n_entries = sc::cycles_entry_count(pairs.data(), n_pairs);
     const uint64_t bytes = sc::sync_meta_bytes(n_sets, n_pairs, n_entries), off_at = sc::sync_off_at(n_pairs, n_entries);
     check("meta bytes", n_entries == 12 && off_at == 32 * 7 + 8 * 12 && bytes == off_at + 4 * 8 && off_at % 8 == 0);
+    const sc::PairsImageAt at = sc::pairs_image_at(n_pairs, n_entries);
+    check("the image's parts", at.rec == 0 && at.entries == 32 * n_pairs && at.starts == off_at);
     char* h = new char[bytes];
-    sc::cycles_adjacency(n_sets, pairs.data(), n_pairs, off, reinterpret_cast<uint64_t*>(h + 32 * n_pairs), reinterpret_cast<uint32_t*>(h));
-    memcpy(h + off_at, off, (n_sets + 1) * 4);
-    const uint32_t* staged = reinterpret_cast<const uint32_t*>(h + off_at);
-    const uint64_t* entries = reinterpret_cast<const uint64_t*>(h + 32 * n_pairs);
+    sc::pairs_image(n_sets, pairs.data(), n_pairs, n_entries, off, true, h);
+    const uint32_t* staged = reinterpret_cast<const uint32_t*>(h + at.starts);
+    const uint64_t* entries = reinterpret_cast<const uint64_t*>(h + at.entries);
     bool ok = staged[0] == 0 && staged[n_sets] == n_entries;
     for (uint32_t s = 0; s < n_sets && ok; s++) {
       ok = staged[s] <= staged[s + 1];
@@ -116,6 +118,11 @@ int main() {
       }
     }
     check("the staged list starts", ok && staged[2] == staged[3] && staged[6] == staged[7]);  // sets 2, 3 and 6 are named by no pair
+    // the image without the starts: the same records and entries in a buffer that ends where the starts would begin
+    char* g = new char[at.starts];
+    sc::pairs_image(n_sets, pairs.data(), n_pairs, n_entries, off, false, g);
+    check("the image without the starts", sc::cycles_meta_bytes(n_pairs, n_entries) == at.starts && memcmp(g, h, at.starts) == 0);
+    delete[] g;
     delete[] h;
     delete[] off;
   }
